@@ -48,6 +48,11 @@ The JSON line carries
                  exchange at all, `value` at N > 1 the literal configs[3] step — a scaling curve over `value` compares the
                  two; the like-for-like first point of the N > 1 series is `dp_reference_at_1.literal.value`.
 
+`--dump-outputs DIR` (N = 1): right after the timed steps, the last step's results for view 0 (its camera does not depend
+on the calibration) go to DIR as float32 .npy files: render, radii, dL_dmeans2D and grad_<raw parameter>, a fixed sample
+beyond 64 MB in all (write_outputs).  The inputs are seeded, so two builds run with the same arguments can be compared
+array for array; `dumped_outputs` in the line says where and what fraction was kept.
+
 Diagnostics: FR_BENCH_HOST_TIME=1 prints how long the host took to enqueue a step; FR_BENCH_ORDER=coherent stores the scene's
 Gaussians in a spatially coherent order (not the metric's scene: what a coherent input order would be worth); FR_BENCH_BATCH_X_STREAMS=1 adds more
 (views per chain, chains) shapes to `batched_views`.
@@ -161,6 +166,9 @@ class _View:
                                   eng.dev, fused_activations=eng.args.fused_activations)
                     for _ in range(2 if eng.exchanging else 1)]
         self.pc = self.pcs[0]
+        # --dump-outputs, per replica: the tensors the frame that overwrites its gradient buffers hands back
+        # (HipEngine.outputs); for a captured frame these are the graph's own buffers, which every replay rewrites
+        self.outs = [None] * len(self.pcs)
         self.cam = TorchCamera(scene.camera, eng.dev)
         self.bg = torch.from_numpy(scene.bg).to(eng.dev)
         H = W = eng.args.res
@@ -206,6 +214,7 @@ class HipEngine:
         self.graph = None
         self.grads_read = [None, None]   # events: the exchange has read the gradient buffers of set 0 / 1
         self._chains, self._extra_views = {}, []
+        self._chain_outs = {}            # (K, streams) -> {view k: HipEngine.outputs of its captured launch chain}
         self.chains = None               # (K, streams, views, graphs) when the timed steps run batched launch chains
 
     def set_mode(self, K, rounds):
@@ -225,6 +234,38 @@ class HipEngine:
         # place — FR_FLAG_ACCUMULATE through the parameters' gradient slots: local gradient accumulation)
         out = self._render(v.cam, pc, v.bg)                        # activations + HIP rasterizer forward
         torch.autograd.backward(out["render"], grad_tensors=v.dL_dpix)  # HIP rasterizer backward (+ activations)
+        if not add and self.recording():
+            v.outs[which] = self.outputs(pc, out)
+
+    def recording(self):
+        """--dump-outputs only: keep what a frame hands back — of the captured frame when frames are replayed as graphs
+        (nothing of an eager frame outlives it then, as without the option), of every frame otherwise."""
+        return bool(self.args.dump_outputs) and (not self.args.graph or torch.cuda.is_current_stream_capturing())
+
+    @staticmethod
+    def outputs(pc, out):
+        """What a caller of render() + backward receives: the image, the radii, the screen-space mean gradient and the
+        gradient of every raw Gaussian parameter — detached references to the tensors (not copies).  Detached, because a
+        kept autograd graph keeps its AccumulateGrad nodes: the next frame would reuse them with the stream they were
+        made on (the warm-up's default stream), and autograd would join that stream into the next captured frame."""
+        o = {"render": out["render"], "radii": out["radii"], "dL_dmeans2D": out["viewspace_points"].grad}
+        for name, _ in pc.FIELDS:
+            o["grad" + name] = getattr(pc, name).grad
+        return {k: None if t is None else t.detach() for k, t in o.items()}
+
+    def last_outputs(self):
+        """--dump-outputs: view 0's outputs of the step enqueued last, as float32 host arrays.  View 0 (the same camera
+        whatever the calibration picks) is in every N = 1 mode's step, and its graph (or launch chain) rewrites the
+        same buffers at every replay."""
+        v = self.all_views[0]
+        rec = self._chain_outs[self.chains[:2]][v.k] if self.chains is not None else v.outs[0]
+        torch.cuda.synchronize()
+        res = {}
+        for name, t in rec.items():
+            if t is None:   # (a gradient the backward left unset is zero: FlatGaussians.collect_grads)
+                t = torch.zeros_like(getattr(v.pc, name[len("grad"):]))
+            res[name] = t.detach().float().cpu().numpy()
+        return res
 
     def prepare(self):
         """Per view: eager warm-up (sizes the binning capacity, fills the allocator pools), then capture ONE frame."""
@@ -265,6 +306,9 @@ class HipEngine:
             v.pc.begin_step()
         outs = render_batch([v.cam for v in views], [v.pc for v in views], [v.bg for v in views], slots=[v.k for v in views])
         torch.autograd.backward([o["render"] for o in outs], grad_tensors=[v.dL_dpix for v in views])
+        if self.recording():
+            return {v.k: self.outputs(v.pc, o) for v, o in zip(views, outs)}
+        return {}
 
     def setup_chains(self, K, streams):
         """`streams` launch chains of K views each (fr_forward_batch / fr_backward_batch: every kernel of the frame launched
@@ -286,7 +330,7 @@ class HipEngine:
         groups = [views[i * K:(i + 1) * K] for i in range(streams)]
         sts = concurrent_streams(streams, self.dev, also_with=[torch.cuda.current_stream(self.dev)]) if streams > 1 \
             else [torch.cuda.Stream(device=self.dev)]
-        graphs = []
+        graphs, chain_outs = [], {}
         for grp, side in zip(groups, sts):
             for _ in range(3):
                 self.batch_frame(grp)
@@ -299,10 +343,11 @@ class HipEngine:
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                    self.batch_frame(grp)
+                    chain_outs.update(self.batch_frame(grp))
             graphs.append((g, side))
         torch.cuda.synchronize()
         self._chains[key] = (views, graphs)
+        self._chain_outs[key] = chain_outs
         return self._chains[key]
 
     @staticmethod
@@ -543,6 +588,9 @@ class StubEngine:
     def flat_grads(self):
         return self.grads
 
+    def last_outputs(self):
+        return {"flat_grad": self.grads[0].numpy().copy()}
+
     def join(self):
         pass
 
@@ -615,6 +663,27 @@ class GradExchange:
 
     def latest(self) -> torch.Tensor:
         return self.last
+
+
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this much on disk
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_BYTES):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32.  When they would take more than `limit` bytes
+    in all, each keeps the same fraction of its (flattened) elements, at sorted positions drawn from a generator seeded
+    with the array's size: the same arguments write the same sample, run after run and build after build.
+    Returns the fraction kept."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32) for k, a in arrays.items()}
+    payload = limit - 1024 * len(arrays)   # (room for the .npy headers)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, payload / total) if total else 1.0
+    for name, a in arrays.items():
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, int(a.size * frac), replace=False, shuffle=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return frac
 
 
 def _flush_c_stdio():
@@ -791,7 +860,15 @@ def main():
                     help="sigmoid/exp/normalize inside the HIP kernels (SURVEY.md §8f row 1)")
     ap.add_argument("--torch-activations", dest="fused_activations", action="store_false",
                     help="reference behaviour: activations as stock PyTorch ops")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last one computed for view 0 (image, radii, "
+                         "screen-space and raw-parameter gradients) as DIR/<name>.npy, float32, at most 64 MB in all "
+                         "(a fixed sample of every array beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.exchange_at_1):
+        ap.error("--dump-outputs covers the N = 1 path only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torchrun: become the launcher (one rank per GPU of this node)
@@ -853,6 +930,7 @@ def main():
 
     rounds = max(1, args.rounds)
     modes = {}
+    dumped = None
     if exchanging:
         # BASELINE configs[3] as written: one view per rank, exchange, then the next step (see the module docstring)
         el, xl = run_mode(1, 1, False)
@@ -872,6 +950,9 @@ def main():
     else:
         elapsed, xchg = run_mode(K_best, rounds, False)
         frames_per_step = K_best * rounds
+        if args.dump_outputs:   # before anything else runs a frame into the same buffers
+            dumped = {"dir": args.dump_outputs, "view": 0,
+                      "fraction_kept": write_outputs(args.dump_outputs, eng.last_outputs())}
         if getattr(eng, "chains", None) is not None:
             frames_per_step = eng.chains[0] * eng.chains[1] * rounds
 
@@ -1034,7 +1115,7 @@ def main():
             "metric": "render+backward frames/sec at 512^2, 100k Gaussians", "value": round(fps, 2), "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "stub" if STUB else "synthetic",
+            "data": "stub" if STUB else "synthetic", "dumped_outputs": dumped,
             "config": {"workload": f"{cfg_name}: {args.P} Gaussians on the head template, "
                                    f"{args.res}x{args.res}, SH deg {args.sh_degree} (M={M}), "
                                    "forward+backward through render() with a fixed dL/dpixel",

@@ -184,30 +184,29 @@ def test_frames_rendered_from_their_binding_refuse_cpu_tensors_and_bad_shapes():
         render_bound_batch([cam] * 5, pc, z(4, 3), mb, torch.ones(3))
 
 
-def test_reference_render_runs_against_the_alias_packages_up_to_the_device_boundary():
-    """The reference's OWN volume_rendering/render_3dgs.py (imported from the read-only checkout, present only in the
-    build container) must import against the alias package and drive it with its keyword arguments; on CPU tensors the
-    call has to get as far as the C-ABI boundary and stop there with the no-CPU-path error (nothing earlier may fail)."""
-    import importlib
-    import os
-    import sys
-    import pytest
-    import torch
-    if not os.path.exists("/root/reference/volume_rendering/render_3dgs.py"):
-        pytest.skip("the reference checkout is only present in the build container")
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, "/root/reference")
-    try:
-        ref = importlib.import_module("volume_rendering.render_3dgs")
-    finally:
-        sys.path.remove("/root/reference")
-    from fateavatar_amd import scenes
-    from fateavatar_amd.model import FlatGaussians, TorchCamera
+def test_reference_style_render_call_runs_against_the_alias_packages_up_to_the_device_boundary():
+    """The calls the reference's volume_rendering/render_3dgs.py makes on `diff_gaussian_rasterization` (settings built by
+    keyword, a non-leaf zero means2D that retains its gradient, the rasterizer called by keyword with SH coefficients or
+    with precomputed colours) must be accepted by the alias package; on CPU tensors they have to get as far as the C-ABI
+    boundary and stop there with the no-CPU-path error (nothing earlier may fail)."""
+    import math
+    from fateavatar_amd.model import TorchCamera
     s = scenes.random_scene(50, 32, 32, sh_degree=1, seed=0)
     pc = FlatGaussians(s.means3D, s.shs, s.opacities, s.scales, s.rotations, 1, torch.device("cpu"))
     cam = TorchCamera(s.camera, torch.device("cpu"))
-    with pytest.raises(RuntimeError, match="HIP device|no CPU"):
-        ref.render(cam, pc, torch.from_numpy(s.bg), device="cpu")
+    settings = dgr.GaussianRasterizationSettings(
+        image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
+        tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.from_numpy(s.bg), scale_modifier=1.0, viewmatrix=cam.world_view_transform,
+        projmatrix=cam.full_proj_transform, sh_degree=pc.max_sh_degree, campos=cam.camera_center, prefiltered=False,
+        debug=False)
+    raster = dgr.GaussianRasterizer(raster_settings=settings)
+    for override in (None, torch.rand(s.P, 3)):
+        means2D = torch.zeros_like(pc.get_xyz, dtype=pc.get_xyz.dtype, requires_grad=True, device="cpu") + 0
+        means2D.retain_grad()
+        with pytest.raises(RuntimeError, match="HIP device|no CPU"):
+            raster(means3D=pc.get_xyz, means2D=means2D, shs=pc.get_features if override is None else None,
+                   colors_precomp=override, opacities=pc.get_opacity, scales=pc.get_scaling, rotations=pc.get_rotation,
+                   cov3D_precomp=None)
 
 
 def test_handle_slot_is_scoped():

@@ -1,8 +1,6 @@
 """UV-raster / area-weighted sampling of binding points (volume_rendering/mesh_sampling.py:86-169 stand-ins)."""
-import os
 
 import numpy as np
-import pytest
 
 from fateavatar_amd import mesh_sampling as ms
 
@@ -94,11 +92,11 @@ def test_random_sampling_is_area_weighted():
     assert abs((fi == 1).mean() - 0.9) < 0.01 and np.allclose(bc.sum(-1), 1, atol=1e-6)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/weights/head_template_mouth_close.obj"),
-                    reason="the reference checkout is only present in the build container")
 def test_head_template_uv_sampling():
-    from fateavatar_amd.obj import load_obj
-    m = load_obj("/root/reference/weights/head_template_mouth_close.obj")
+    # the template's arrays as the repository ships them (verts / faces / vt / per-corner vt indices of
+    # weights/head_template_mouth_close.obj, exported by tests/golden/make_golden.py:gen_head)
+    from fateavatar_amd import scenes
+    m = dict(np.load(scenes.HEAD_GEOM))
     fi, bc = ms.uniform_sampling_barycoords(10000, m["verts_uvs"], m["faces_uvs"])
     assert fi.shape == (10000,) and fi.max() < len(m["faces"]) and (bc >= 0).all()
     # the template's UV faces are wound counter-clockwise but for five (the faces pytorch3d's cull_backfaces=True drops):
