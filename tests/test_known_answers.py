@@ -136,6 +136,14 @@ def test_known_answers_cover_the_branches():
     assert float(i["scale_modifier"]) == pytest.approx(1.5) and int((o["final_T"] < 1e-3).sum()) > 50 and np.abs(o["dL_dscales"]).max() > 0
 
 
+def test_batched_known_answers_cover_every_fixture():
+    """tests/test_gpu_batch_parity.py runs the fixtures in batches of four: every fixture exactly once (checked without a
+    device, so that an added or renamed fixture is noticed on any machine)."""
+    from tests.test_gpu_batch_parity import KA_BATCHES
+    got = [n for grp in KA_BATCHES for n in grp]
+    assert sorted(got) == sorted(NAMES) and len(got) == len(set(got)) and all(len(g) == 4 for g in KA_BATCHES)
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_oracle_matches_known_answers(name):
     from oracle import oracle
@@ -152,32 +160,49 @@ def test_oracle_matches_known_answers(name):
              tol_img=1e-5 if deep else 3e-6, tol_grad=1e-4 if name in LONG_LISTS else 2e-5)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", NAMES)
-def test_hip_matches_known_answers(name, gpu_device):
+def hip_forward_args(i, dev):
+    """The scene `i` (the fixture's inputs) as the positional arguments of `rasterizer.rasterize_gaussians`, and a function
+    that turns that forward's (radii, geom, R, binning, img) into the arguments of `rasterize_gaussians_backward` (the
+    fixture's dL/dpixel; zero for a scene without gradients)."""
     import torch
-    from fateavatar_amd import rasterizer
-    i, want = _scene(name)
-    t = lambda k: torch.from_numpy(np.ascontiguousarray(i[k], dtype=np.float32)).to(gpu_device) if k in i else torch.empty(0)  # noqa: E731
+    t = lambda k: torch.from_numpy(np.ascontiguousarray(i[k], dtype=np.float32)).to(dev) if k in i else torch.empty(0)  # noqa: E731
     H, W = int(i["H"]), int(i["W"])
-    args = (t("bg"), t("means3D"), t("colors_precomp"), t("opacities"), t("scales"), t("rotations"), float(i["scale_modifier"]),
-            t("cov3D_precomp"), t("viewmatrix"), t("projmatrix"), float(i["tanfovx"]), float(i["tanfovy"]), H, W, t("shs"),
-            int(i["D"]), t("campos"), False, False)
-    R, color, radii, geom, binning, img = rasterizer.rasterize_gaussians(*args)
-    fT, _ = rasterizer.image_aux(img, H, W)
+    fwd = (t("bg"), t("means3D"), t("colors_precomp"), t("opacities"), t("scales"), t("rotations"), float(i["scale_modifier"]),
+           t("cov3D_precomp"), t("viewmatrix"), t("projmatrix"), float(i["tanfovx"]), float(i["tanfovy"]), H, W, t("shs"),
+           int(i["D"]), t("campos"), False, False)
+
+    def bwd(radii, geom, R, binning, img):
+        dpix = t("dL_dpix") if "dL_dpix" in i else torch.zeros((3, H, W), device=dev)
+        return (t("bg"), t("means3D"), radii, t("colors_precomp"), t("scales"), t("rotations"), float(i["scale_modifier"]),
+                t("cov3D_precomp"), t("viewmatrix"), t("projmatrix"), float(i["tanfovx"]), float(i["tanfovy"]), dpix,
+                t("shs"), int(i["D"]), t("campos"), geom, R, binning, img, False)
+    return fwd, bwd
+
+
+def hip_compare(name, want, color, final_T, radii, grads, max_tile_list):
+    """Hold one HIP frame of the fixture `name` to its known answer (tolerances of test_hip_matches_known_answers).
+    `grads`: the backward's eight arrays in rasterize_gaussians_backward's order, or None for a scene without gradients;
+    `max_tile_list`: fr_counts::max_tile_list of the frame's handle."""
     # n_contrib in reference (16x16-list) semantics is not what the 8x8 implementation stores; the image, the
     # transmittance and the radii pin the same decisions
     b = None
     if "dL_dmeans3D" in want:
-        out = rasterizer.rasterize_gaussians_backward(
-            t("bg"), t("means3D"), radii, t("colors_precomp"), t("scales"), t("rotations"), float(i["scale_modifier"]),
-            t("cov3D_precomp"), t("viewmatrix"), t("projmatrix"), float(i["tanfovx"]), float(i["tanfovy"]), t("dL_dpix"),
-            t("shs"), int(i["D"]), t("campos"), geom, R, binning, img, False)
         names = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations"]
-        b = {k: v.cpu().numpy() for k, v in zip(names, out)}
+        b = {k: v.cpu().numpy() for k, v in zip(names, grads)}
     if name in LONG_LISTS:   # the fixture is only worth its name if the HIP path really took its long-list machinery
-        c = rasterizer.last_counts[gpu_device.index or 0]
-        assert c.max_tile_list > (256 if name == "big_lists" else 128), c.max_tile_list   # (8 x 8 lists: several blend units each)
+        assert max_tile_list > (256 if name == "big_lists" else 128), (name, max_tile_list)   # (8 x 8 lists: several blend units each)
     deep = int(want["n_contrib"].max()) > 128
-    _compare(name, (color.cpu().numpy(), fT.cpu().numpy(), want["n_contrib"], radii.cpu().numpy()), b, want,
+    _compare(name, (color.cpu().numpy(), final_T.cpu().numpy(), want["n_contrib"], radii.cpu().numpy()), b, want,
              tol_img=2e-5 if deep else 1e-5, tol_grad=2e-4 if name in LONG_LISTS else 1e-4)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NAMES)
+def test_hip_matches_known_answers(name, gpu_device):
+    from fateavatar_amd import rasterizer
+    i, want = _scene(name)
+    fwd, bwd = hip_forward_args(i, gpu_device)
+    R, color, radii, geom, binning, img = rasterizer.rasterize_gaussians(*fwd)
+    fT, _ = rasterizer.image_aux(img, int(i["H"]), int(i["W"]))
+    grads = rasterizer.rasterize_gaussians_backward(*bwd(radii, geom, R, binning, img)) if "dL_dmeans3D" in want else None
+    hip_compare(name, want, color, fT, radii, grads, rasterizer.last_counts[gpu_device.index or 0].max_tile_list)

@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -23,10 +24,14 @@ def oracle_forward(s: GaussianScene, colors_precomp=None, cov3D_precomp=None, sc
         scale_modifier=scale_modifier)
 
 
-class HipFrame:
-    """One forward (+ optional backward) through the C ABI."""
+GRAD_NAMES = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")
 
-    def __init__(self, s: GaussianScene, dev, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0, debug=False):
+
+class _Frame:
+    """What HipFrame and a view of HipBatch share: the scene's inputs on the device, the argument tuples of the
+    rasterizer's forward and backward, and the forward state read back (`geometry`)."""
+
+    def _upload(self, s: GaussianScene, dev, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0, debug=False):
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
         e = torch.empty(0)
         c = s.camera
@@ -40,11 +45,22 @@ class HipFrame:
         self.view, self.proj, self.campos = t(c.world_view_transform), t(c.full_proj_transform), t(c.camera_center)
         self.mod, self.debug = scale_modifier, debug
         self.H, self.W = c.image_height, c.image_width
-        (self.num_rendered, self.color, self.radii, self.geom, self.binning, self.img) = rasterizer.rasterize_gaussians(
-            self.bg, self.means3D, self.colors, self.op, self.scales, self.rots, scale_modifier, self.cov, self.view,
-            self.proj, c.tanfovx, c.tanfovy, self.H, self.W, self.sh, s.sh_degree, self.campos, False, debug)
-        self.counts = rasterizer.last_counts[dev.index or 0]
+
+    def _forward_args(self):
+        c = self.s.camera
+        return (self.bg, self.means3D, self.colors, self.op, self.scales, self.rots, self.mod, self.cov, self.view, self.proj,
+                c.tanfovx, c.tanfovy, self.H, self.W, self.sh, self.s.sh_degree, self.campos, False, self.debug)
+
+    def _take_forward(self, result):
+        (self.num_rendered, self.color, self.radii, self.geom, self.binning, self.img) = result
         self.final_T, self.n_contrib = rasterizer.image_aux(self.img, self.H, self.W)
+
+    def _backward_args(self, g: torch.Tensor, fw=None):
+        """`fw`: another forward's (num_rendered, color, radii, geom, binning, img) of this scene instead of this frame's."""
+        c = self.s.camera
+        R, _, radii, geom, binning, img = fw if fw is not None else (self.num_rendered, None, self.radii, self.geom, self.binning, self.img)
+        return (self.bg, self.means3D, radii, self.colors, self.scales, self.rots, self.mod, self.cov, self.view,
+                self.proj, c.tanfovx, c.tanfovy, g, self.sh, self.s.sh_degree, self.campos, geom, R, binning, img, self.debug)
 
     def geometry(self, field: int, cols: int, dtype=torch.float32):
         """A per-Gaussian array of the forward state.  Fields 0 (pixel-space centre), 1 (depth) and 3 (colour) live inside the
@@ -63,16 +79,78 @@ class HipFrame:
         nbytes = P * cols * torch.empty(0, dtype=dtype).element_size()
         return self.geom[off:off + nbytes].view(dtype).view(P, cols).cpu().numpy()
 
+
+class HipFrame(_Frame):
+    """One forward (+ optional backward) through the C ABI."""
+
+    def __init__(self, s: GaussianScene, dev, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0, debug=False):
+        self._upload(s, dev, colors_precomp, cov3D_precomp, scale_modifier, debug)
+        self._take_forward(rasterizer.rasterize_gaussians(*self._forward_args()))
+        self.counts = rasterizer.last_counts[dev.index or 0]
+
     def backward(self, dL_dpix: np.ndarray):
-        c = self.s.camera
         g = torch.from_numpy(np.ascontiguousarray(dL_dpix)).to(self.dev)
-        out = rasterizer.rasterize_gaussians_backward(
-            self.bg, self.means3D, self.radii, self.colors, self.scales, self.rots, self.mod, self.cov, self.view,
-            self.proj, c.tanfovx, c.tanfovy, g, self.sh, self.s.sh_degree, self.campos, self.geom, self.num_rendered,
-            self.binning, self.img, self.debug)
-        names = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
-                 "dL_drotations"]
-        return {k: v.cpu().numpy() for k, v in zip(names, out)}
+        out = rasterizer.rasterize_gaussians_backward(*self._backward_args(g))
+        return {k: v.cpu().numpy() for k, v in zip(GRAD_NAMES, out)}
+
+
+class HipBatchView(_Frame):
+    """View k of a HipBatch: looks like a HipFrame from the outside.  `counts` are read from the view's own handle slot
+    (rasterizer.last_counts only holds a batch's last view).  `backward(dpix)` runs the batched backward for ALL views of
+    the batch — this one with `dpix`, the others with their `default_dpix` — and returns this view's gradients."""
+
+    def __init__(self, batch, k, s, dev, slot, kw):
+        # (a weak reference: a view -> batch -> view cycle would keep every buffer of the batch alive until the cyclic
+        # garbage collector happens to run, which device memory does not trigger)
+        self._batch, self.k, self.slot = weakref.ref(batch), k, slot
+        self._upload(s, dev, **kw)
+        H, W = self.H, self.W
+        self.default_dpix = (np.random.default_rng([4242, k]).uniform(-1, 1, (3, H, W)) / (H * W)).astype(np.float32)
+
+    def backward(self, dL_dpix: np.ndarray):
+        batch = self._batch()
+        assert batch is not None, "the HipBatch of this view is gone: keep it alive while its views are used"
+        dpixs = [None] * len(batch)
+        dpixs[self.k] = dL_dpix
+        return batch.backward_all(dpixs)[self.k]
+
+
+class HipBatch:
+    """K scenes through ONE `rasterizer.rasterize_gaussians_batch` call (fr_forward_batch) on the handle slots `slots`
+    (default 0 .. K-1); `per_view_kwargs[k]`: HipFrame's keyword arguments for view k (colors_precomp, cov3D_precomp,
+    scale_modifier, debug).  `batch[k]` / iteration: the views, each a HipFrame look-alike whose gradients come from
+    fr_backward_batch."""
+
+    def __init__(self, scenes, dev, slots=None, per_view_kwargs=None):
+        K = len(scenes)
+        self.dev = dev
+        self.slots = list(range(K)) if slots is None else [int(x) for x in slots]
+        kws = per_view_kwargs or [{}] * K
+        self.views = [HipBatchView(self, k, s, dev, self.slots[k], kws[k] or {}) for k, s in enumerate(scenes)]
+        res = rasterizer.rasterize_gaussians_batch([v._forward_args() for v in self.views], slots=self.slots)
+        torch.cuda.synchronize(dev)
+        for v, r in zip(self.views, res):
+            v._take_forward(r)
+            v.counts = rasterizer.read_counts(dev.index or 0, v.slot)
+
+    def __len__(self):
+        return len(self.views)
+
+    def __getitem__(self, k):
+        return self.views[k]
+
+    def __iter__(self):
+        return iter(self.views)
+
+    def backward_all(self, dpixs, wants=None, outs=None, stats=None, accumulates=None, as_numpy=True):
+        """One fr_backward_batch for every view: `dpixs[k]` is view k's dL/dpixel (None: its default).  The remaining
+        arguments are rasterize_gaussians_backward_batch's per-view lists.  Returns per view a dict of its gradients."""
+        gs = [torch.from_numpy(np.ascontiguousarray(v.default_dpix if d is None else d)).to(self.dev)
+              for v, d in zip(self.views, dpixs)]
+        out = rasterizer.rasterize_gaussians_backward_batch([v._backward_args(g) for v, g in zip(self.views, gs)],
+                                                            slots=self.slots, wants=wants, outs=outs, stats=stats,
+                                                            accumulates=accumulates)
+        return [{k: (a.cpu().numpy() if as_numpy and a is not None else a) for k, a in zip(GRAD_NAMES, o)} for o in out]
 
 
 def frac_close(a, b, rtol, atol):
