@@ -12,16 +12,15 @@ forward and to atomic-summation order in the backward.
 """
 from __future__ import annotations
 
-import math
 from typing import NamedTuple, Optional
 
 import torch
 
 from . import _lib
 from .binding import _chk, _desc
-from .rasterizer import (NUM_CHANNELS, GaussianRasterizationSettings, GradOut, rasterize_gaussians_backward_batch,
+from .rasterizer import (NUM_CHANNELS, _backward_args, _forward_args, _FrameGrads, rasterize_gaussians_backward_batch,
                          rasterize_gaussians_batch)
-from .render import _zero_points
+from .render import _result, _screenspace_points, _settings
 
 
 class MeshBinding(NamedTuple):
@@ -66,12 +65,10 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             rot = torch.empty((N, 4), dtype=torch.float32, device=dev)
             scl = torch.empty((N, 3), dtype=torch.float32, device=dev)
             bound.append((xyz, rot, scl))
-            views.append((rs.bg, xyz, empty, opacities, scl, rot, rs.scale_modifier, empty, rs.viewmatrix, rs.projmatrix,
-                          rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, rs.campos, rs.prefiltered,
-                          rs.debug))
+            views.append(_forward_args(rs, xyz, means2D, sh, empty, opacities, scl, rot, empty))
             viss.append(torch.empty((N,), dtype=torch.bool, device=dev))
         res = rasterize_gaussians_batch(views, slots=slots, raw=True, visibles=viss, bindings=descs)
-        ctx.stats, ctx.num_rendered, ctx.grad_slots, ctx.grad_owners, ctx.offset_shapes = [], [], [], [], []
+        ctx.stats, ctx.num_rendered, ctx.grads, ctx.offset_shapes = [], [], [], []
         saved, outs = [], []
         for k in range(K):
             verts, offset, rotation, scaling, means2D, sh, opacities = tensors[n * k:n * k + n]
@@ -81,11 +78,8 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             ctx.stats.append(getattr(means2D, "_fr_densification_stats", None))
             ctx.num_rendered.append(num_rendered)
             ctx.offset_shapes.append(tuple(offset.shape))
-            slots_k = {"dL_dsh": GradOut.of(sh) if sh.numel() else None, "dL_dopacity": GradOut.of(opacities),
-                       "d_offset": GradOut.of(offset), "d_rotation": GradOut.of(rotation), "d_scaling": GradOut.of(scaling)}
-            owners = {"dL_dsh": sh, "dL_dopacity": opacities, "d_offset": offset, "d_rotation": rotation, "d_scaling": scaling}
-            ctx.grad_slots.append(slots_k)
-            ctx.grad_owners.append({m: t for m, t in owners.items() if slots_k.get(m) is not None and t.is_leaf})
+            ctx.grads.append(_FrameGrads({"dL_dsh": sh if sh.numel() else None, "dL_dopacity": opacities, "d_offset": offset,
+                                          "d_rotation": rotation, "d_scaling": scaling}, sh, bound=True))
             saved += [*checked[k], sh, radii, geomBuffer, binningBuffer, imgBuffer, *bound[k]]
             outs += [color, radii]
         ctx.save_for_backward(*saved)
@@ -95,12 +89,11 @@ class _RasterizeBoundBatch(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grad_outs):
         K, n = ctx.K, _RasterizeBoundBatch.PER_VIEW
-        none = (None, None, None) + (None,) * (n * K)
         grad_colors = grad_outs[0::2]
         if all(g is None for g in grad_colors):
-            return none
+            return (None, None, None) + (None,) * (n * K)
         empty = torch.Tensor([])
-        views, wants, outs, descs, bgrads = [], [], [], [], []
+        views, outs, descs, bgrads = [], [], [], []
         for k, (rs, mb) in enumerate(zip(ctx.settings, ctx.bindings)):
             verts, offset, rotation, scaling, sh, radii, geomBuffer, binningBuffer, imgBuffer, xyz, rot, scl = \
                 ctx.saved_tensors[12 * k:12 * k + 12]
@@ -108,22 +101,16 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             g = grad_colors[k]
             if g is None:
                 g = torch.zeros((NUM_CHANNELS, rs.image_height, rs.image_width), dtype=torch.float32, device=dev)
-            views.append((rs.bg, xyz, radii, empty, scl, rot, rs.scale_modifier, empty, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
-                          rs.tanfovy, g, sh, rs.sh_degree, rs.campos, geomBuffer, ctx.num_rendered[k], binningBuffer, imgBuffer,
-                          rs.debug))
-            want = {"dL_dmeans2D", "dL_dopacity"}
-            if sh.numel():
-                want.add("dL_dsh")
-            claims = {m: slot.claim(ctx.grad_owners[k].get(m)) for m, slot in ctx.grad_slots[k].items() if slot is not None}
-            wants.append(want)
-            outs.append({m: c[0] for m, c in claims.items() if not c[1] and m.startswith("dL_")})
+            views.append(_backward_args(rs, (empty, xyz, scl, rot, empty, radii, sh, geomBuffer, binningBuffer, imgBuffer), g,
+                                        ctx.num_rendered[k]))
+            claimed = ctx.grads[k].claim(accumulate=False)[0]
+            outs.append({m: b for m, b in claimed.items() if m.startswith("dL_")})
             need_v, need_o, need_r, need_s = ctx.needs_input_grad[3 + n * k:3 + n * k + 4]
 
             def buf(need, name, shape):
                 if not need:
                     return None
-                c = claims.get(name)
-                b = c[0] if (c is not None and not c[1]) else None
+                b = claimed.get(name)
                 if b is not None and b.numel() == int(torch.Size(shape).numel()) and b.is_contiguous():
                     return b.view(shape)
                 return torch.empty(shape, dtype=torch.float32, device=dev)
@@ -132,8 +119,8 @@ class _RasterizeBoundBatch(torch.autograd.Function):
                                mb.shell_len, mb.resize_scale))
             bgrads.append({"d_verts": torch.zeros_like(verts) if need_v else None, "d_offset": buf(need_o, "d_offset", (N,)),
                            "d_rotation": buf(need_r, "d_rotation", (N, 4)), "d_scaling": buf(need_s, "d_scaling", (N, 3))})
-        res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=wants, outs=outs, stats=ctx.stats,
-                                                 bindings=descs, bind_grads=bgrads)
+        res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=[fg.want for fg in ctx.grads], outs=outs,
+                                                 stats=ctx.stats, bindings=descs, bind_grads=bgrads)
         flat = [None, None, None]
         for k in range(K):
             grad_means2D, _, grad_opacities, _, _, grad_sh, _, _ = res[k]
@@ -170,25 +157,14 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding: MeshBinding
                      if binding.face_scale_canonical is not None else None, float(binding.shell_len), bool(binding.resize_scale))
     settings, tensors, points = [], [], []
     for cam, pc, bg, verts in zip(viewpoint_cameras, pcs, bg_colors, posed_verts):
-        sp = _zero_points(pc._scaling)
-        stats = getattr(pc, "fused_densification_stats", None)
-        if stats is not None:
-            sp._fr_densification_stats = stats
-        try:
-            sp.retain_grad()
-        except Exception:
-            pass
-        settings.append(GaussianRasterizationSettings(
-            image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
-            tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scaling_modifier, viewmatrix=cam.world_view_transform,
-            projmatrix=cam.full_proj_transform, sh_degree=pc.max_sh_degree, campos=cam.camera_center, prefiltered=False,
-            debug=False))
+        sp = _screenspace_points(pc._scaling, pc)
+        settings.append(_settings(cam, pc, bg, scaling_modifier))
         tensors += [verts, pc._offset, pc._rotation, pc._scaling, sp, pc.get_features, pc._opacity]
         points.append(sp)
     res = _RasterizeBoundBatch.apply(settings, [mb] * K, list(range(K)) if slots is None else list(slots), *tensors)
     out = []
     for k, sp in enumerate(points):
-        image, radii = res[2 * k], res[2 * k + 1]
-        out.append({"render": image, "viewspace_points": sp, "visibility_filter": radii._fr_visible, "radii": radii,
-                    "bound": tuple(t.detach() for t in radii._fr_bound) if radii._fr_bound is not None else None})
+        o = _result(res[2 * k], res[2 * k + 1], sp)
+        o["bound"] = tuple(t.detach() for t in o["radii"]._fr_bound)
+        out.append(o)
     return out

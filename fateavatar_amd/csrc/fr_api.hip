@@ -204,15 +204,9 @@ size_t fr_binning_bytes(uint64_t capacity, int32_t W, int32_t H)
 int fr_forward(fr_handle* hh, const fr_params* prm, const fr_inputs* in, float* out_color, int32_t* radii,
                void* geometry, void* image, void* binning, uint64_t binning_capacity, fr_counts* counts, void* stream)
 {
-    fr_handle_impl* h = reinterpret_cast<fr_handle_impl*>(hh);
-    if (!h) return fail_msg(FR_ERR_INVALID_ARGUMENT, "null handle");
-    int rc = check_frame(prm, in, true);
-    if (rc) return rc;
-    if (!out_color || !image || (prm->P > 0 && (!radii || !geometry)) || (binning_capacity > 0 && !binning))
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "null output / scratch pointer");
-    if (binning_capacity >= (1ull << 32)) return fail_msg(FR_ERR_UNSUPPORTED, "binning capacity must be < 2^32 instances");
-    const ForwardCall c = {h, prm, in, out_color, radii, geometry, image, binning, binning_capacity, counts};
-    return launch_forward(1, &c, static_cast<hipStream_t>(stream));
+    // (a batch of one: the same checks, codes and messages; a single view may have P == 0)
+    return fr_forward_batch(1, &hh, &prm, &in, &out_color, &radii, &geometry, &image, &binning, &binning_capacity, counts,
+                            stream);
 }
 
 int fr_forward_batch(int32_t n_views, fr_handle* const* handles, const fr_params* const* prm, const fr_inputs* const* in,
@@ -252,17 +246,24 @@ int fr_read_counts(fr_handle* hh, fr_counts* counts)
     return FR_OK;
 }
 
+// One view of a backward.  P == 0 passes (fr_backward has nothing to do) unless the view is part of a batch.
+static int check_backward(const BackwardCall& c, bool batched)
+{
+    if (!c.h) return fail_msg(FR_ERR_INVALID_ARGUMENT, "null handle");
+    int rc = check_frame(c.prm, c.in, false);
+    if (rc) return rc;
+    if (c.prm->P == 0) return batched ? fail_msg(FR_ERR_INVALID_ARGUMENT, "batched views need P > 0") : FR_OK;
+    if (!c.radii || !c.geometry || !c.image || !c.binning || !c.dL_dpix || !c.grads)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "null pointer");
+    return FR_OK;
+}
+
 int fr_backward(fr_handle* hh, const fr_params* prm, const fr_inputs* in, const int32_t* radii, void* geometry,
                 const void* image, const void* binning, const float* dL_dpix, const fr_grads* grads, void* stream)
 {
-    fr_handle_impl* h = reinterpret_cast<fr_handle_impl*>(hh);
-    if (!h) return fail_msg(FR_ERR_INVALID_ARGUMENT, "null handle");
-    int rc = check_frame(prm, in, false);
-    if (rc) return rc;
-    if (prm->P == 0) return FR_OK;
-    if (!radii || !geometry || !image || !binning || !dL_dpix || !grads)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "null pointer");
-    const BackwardCall c = {h, prm, in, radii, geometry, image, binning, dL_dpix, grads};
+    const BackwardCall c = {reinterpret_cast<fr_handle_impl*>(hh), prm, in, radii, geometry, image, binning, dL_dpix, grads};
+    int rc = check_backward(c, false);
+    if (rc || prm->P == 0) return rc;
     return launch_backward(1, &c, static_cast<hipStream_t>(stream));
 }
 
@@ -275,16 +276,12 @@ int fr_backward_batch(int32_t n_views, fr_handle* const* handles, const fr_param
         return fail_msg(FR_ERR_INVALID_ARGUMENT, "null argument array");
     BackwardCall c[kMaxBatch];
     for (int k = 0; k < n_views; k++) {
-        fr_handle_impl* h = reinterpret_cast<fr_handle_impl*>(handles[k]);
-        if (!h) return fail_msg(FR_ERR_INVALID_ARGUMENT, "null handle");
-        for (int j = 0; j < k; j++)
+        for (int j = 0; j < k; j++)   // (never two null handles: the first has failed check_backward)
             if (handles[j] == handles[k]) return fail_msg(FR_ERR_INVALID_ARGUMENT, "the views of a batch need a handle each");
-        int rc = check_frame(prm[k], in[k], false);
+        c[k] = BackwardCall{reinterpret_cast<fr_handle_impl*>(handles[k]), prm[k], in[k], radii[k], geometry[k], image[k],
+                            binning[k], dL_dpix[k], grads[k]};
+        int rc = check_backward(c[k], true);
         if (rc) return rc;
-        if (prm[k]->P <= 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "batched views need P > 0");
-        if (!radii[k] || !geometry[k] || !image[k] || !binning[k] || !dL_dpix[k] || !grads[k])
-            return fail_msg(FR_ERR_INVALID_ARGUMENT, "null pointer");
-        c[k] = BackwardCall{h, prm[k], in[k], radii[k], geometry[k], image[k], binning[k], dL_dpix[k], grads[k]};
     }
     return launch_backward(n_views, c, static_cast<hipStream_t>(stream));
 }

@@ -34,14 +34,14 @@ def _dev_index(t: torch.Tensor) -> int:
     return t.device.index if t.device.index is not None else torch.cuda.current_device()
 
 
-def _f32c(t: torch.Tensor) -> torch.Tensor:
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
+def _f32c(*tensors) -> list:
+    """Tensors as the kernels read them: float32 and contiguous (None stays None)."""
+    return [t if t is None else (t if t.dtype == torch.float32 else t.float()).contiguous() for t in tensors]
 
 
-def _ptr(t: torch.Tensor | None) -> int:
-    return 0 if t is None or t.numel() == 0 else t.data_ptr()
+def _ptrs(*tensors) -> list:
+    """Device pointers for a C struct: 0 for an absent (None or empty) tensor."""
+    return [0 if t is None or t.numel() == 0 else t.data_ptr() for t in tensors]
 
 
 def _check(rc: int, what: str):
@@ -161,8 +161,143 @@ def _aux(visible=None, grad_accum=None, denom=None, binding=None, bind_grads=Non
 
 
 def _inputs(bg, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos):
-    return _lib.fr_inputs(_ptr(bg), _ptr(means3D), _ptr(sh), _ptr(colors), _ptr(opacity), _ptr(scales),
-                          _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos))
+    return _lib.fr_inputs(*_ptrs(bg, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                                 campos))
+
+
+def _grad_shapes(P, M):
+    """rasterize_gaussians_backward's results (rasterize_points.cu:151-159, 195), in the order of fr_grads."""
+    return dict(dL_dmeans2D=(P, 3), dL_dcolors=(P, NUM_CHANNELS), dL_dopacity=(P, 1), dL_dmeans3D=(P, 3),
+                dL_dcov3D=(P, 6), dL_dsh=(P, M, 3), dL_dscales=(P, 3), dL_drotations=(P, 4))
+
+
+_GRAD_NAMES = tuple(_grad_shapes(0, 0))
+
+
+def _forward_view(args, raw=False, visible=None, binding=None) -> dict:
+    """One view of a forward, from the positional arguments of `rasterize_gaussians`: its inputs as the kernels read them
+    (kept alive in the view), its fr_params / fr_inputs, outputs and binning capacity.  The launcher allocates the binning
+    buffer."""
+    (background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+     tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug) = args
+    if means3D.dim() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    dev = _dev_index(means3D)
+    P, H, W = means3D.size(0), int(image_height), int(image_width)
+    keep = _f32c(background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos)
+    M = sh.size(1) if sh.numel() != 0 else 0
+    L, opts = _lib.lib(), dict(device=means3D.device)
+    return dict(dev=dev, W=W, H=H, opts=opts, keep=keep, inp=_inputs(*keep),
+                prm=_params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, prefiltered, debug, raw,
+                            _aux(visible=visible, binding=binding)),
+                out_color=torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, **opts),
+                radii=torch.empty((P,), dtype=torch.int32, **opts),
+                geom=torch.empty((L.fr_geometry_bytes(P),), dtype=torch.uint8, **opts),
+                img=torch.empty((L.fr_image_bytes(W, H),), dtype=torch.uint8, **opts),
+                cap=max(_capacity_hint.get(dev, 0), 4 * P + 65536))
+
+
+def _backward_view(args, raw=False, want=None, out=None, stats=None, accumulate=(), binding=None, bind_grads=None,
+                   what="rasterize_gaussians_backward") -> dict:
+    """One view of a backward, from the positional arguments of `rasterize_gaussians_backward` and its keyword
+    arguments: the gradient tensors it returns, its inputs as the kernels read them (kept alive in the view), and its
+    fr_params / fr_inputs / fr_grads."""
+    (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+     tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug) = args
+    dev = _dev_index(means3D)
+    P, H, W = means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
+    M = sh.size(1) if sh.numel() != 0 else 0
+    shapes = _grad_shapes(P, M)
+    out = out or {}
+    for k in accumulate:
+        if out.get(k) is None:
+            raise RuntimeError(f"{what}: cannot accumulate into {k}: no buffer was given for it")
+    # the kernel writes every row of every array it is given, so uninitialised memory is fine
+    g = {k: (torch.empty(s, device=means3D.device, dtype=torch.float32) if (want is None or k in want) else None)
+         for k, s in shapes.items()}
+    for k, buf in out.items():  # caller-provided gradient buffers (e.g. views into a flat gradient buffer): written in place
+        if buf is not None:
+            assert buf.shape == shapes[k] and buf.is_contiguous() and buf.dtype == torch.float32, k
+            # a FRESH view object: autograd's AccumulateGrad only adopts an incoming gradient without
+            # cloning it when nobody else holds a reference to that tensor object
+            g[k] = buf.view(buf.shape)
+    *keep, dpix = _f32c(background, means3D, sh, colors, None, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                        campos, dL_dout_color)
+    acc_flags = sum(1 << (_lib.FR_FLAG_ACCUMULATE_SHIFT + _GRAD_NAMES.index(k)) for k in accumulate)
+    aux = None
+    if stats is not None or binding is not None:
+        grad_accum, denom, overflow_out = _stats3(stats)
+        aux = _aux(grad_accum=grad_accum, denom=denom, overflow_out=overflow_out, binding=binding, bind_grads=bind_grads)
+    return dict(dev=dev, g=g, keep=keep, inp=_inputs(*keep), grads=_lib.fr_grads(*_ptrs(*g.values())),
+                prm=_params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, False, debug, raw, aux, acc_flags),
+                radii=radii.contiguous(), geom=geomBuffer, img=imageBuffer, binning=binningBuffer, dpix=dpix)
+
+
+def _batch_arrays(views, slots, dev):
+    """What fr_forward_batch / fr_backward_batch take per view: handles, fr_params and fr_inputs pointers, and
+    `arr(key)`, the device pointers of one buffer of every view."""
+    K = len(views)
+    return ((C.c_void_p * K)(*[_lib.handle(dev, sl) for sl in slots]),
+            (C.POINTER(_lib.fr_params) * K)(*[C.pointer(v["prm"]) for v in views]),
+            (C.POINTER(_lib.fr_inputs) * K)(*[C.pointer(v["inp"]) for v in views]),
+            lambda key: (C.c_void_p * K)(*[v[key].data_ptr() for v in views]))
+
+
+def _launch_forward(views, slots, batch):
+    """The forward of views from `_forward_view` on the device's handles `slots`: fr_forward_batch, or fr_forward for a
+    single frame (`batch` False).  A view that overflows its binning capacity is rerun with the capacity it needs.
+    Returns the `rasterize_gaussians` result tuple of every view."""
+    K, dev, L = len(views), views[0]["dev"], _lib.lib()
+    counts = (_lib.fr_counts * K)()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if batch:
+            handles, prm_p, inp_p, arr = _batch_arrays(views, slots, dev)
+        else:
+            h, one = _lib.handle(dev, slots[0]), views[0]
+        while True:
+            for v in views:
+                v["binning"] = torch.empty((L.fr_binning_bytes(v["cap"], v["W"], v["H"]),), dtype=torch.uint8, **v["opts"])
+            if batch:
+                rc = L.fr_forward_batch(K, handles, prm_p, inp_p, arr("out_color"), arr("radii"), arr("geom"), arr("img"),
+                                        arr("binning"), (C.c_uint64 * K)(*[v["cap"] for v in views]), counts, stream)
+            else:
+                rc = L.fr_forward(h, C.byref(one["prm"]), C.byref(one["inp"]), one["out_color"].data_ptr(),
+                                  one["radii"].data_ptr(), one["geom"].data_ptr(), one["img"].data_ptr(),
+                                  one["binning"].data_ptr(), one["cap"], counts, stream)
+            if rc != _lib.FR_ERR_BINNING_CAPACITY:
+                break
+            for v, c in zip(views, counts):
+                if c.overflow:
+                    v["cap"] = int(c.num_instances * 1.25) + 1024
+    _check(rc, "fr_forward_batch" if batch else "fr_forward")
+    out = []
+    for v, c in zip(views, counts):
+        if not _no_wait:  # (with it, the counts arrive later: read_counts / check_async_overflow)
+            _capacity_hint[dev] = max(_capacity_hint.get(dev, 0), int(c.num_instances * 1.25) + 1024)
+            last_counts[dev] = c
+        out.append((0 if _no_wait else int(c.num_rendered), v["out_color"], v["radii"], v["geom"], v["binning"], v["img"]))
+    return out
+
+
+def _launch_backward(views, slots, batch):
+    """The backward of views from `_backward_view` on the device's handles `slots`: fr_backward_batch, or fr_backward for
+    a single frame (`batch` False).  Returns the `rasterize_gaussians_backward` result tuple of every view."""
+    K, dev, L = len(views), views[0]["dev"], _lib.lib()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if batch:
+            handles, prm_p, inp_p, arr = _batch_arrays(views, slots, dev)
+            grd_p = (C.POINTER(_lib.fr_grads) * K)(*[C.pointer(v["grads"]) for v in views])
+            rc = L.fr_backward_batch(K, handles, prm_p, inp_p, arr("radii"), arr("geom"), arr("img"), arr("binning"),
+                                     arr("dpix"), grd_p, stream)
+        else:
+            v = views[0]
+            rc = L.fr_backward(_lib.handle(dev, slots[0]), C.byref(v["prm"]), C.byref(v["inp"]), v["radii"].data_ptr(),
+                               v["geom"].data_ptr(), v["img"].data_ptr(), v["binning"].data_ptr(), v["dpix"].data_ptr(),
+                               C.byref(v["grads"]), stream)
+    _check(rc, "fr_backward_batch" if batch else "fr_backward")
+    return [tuple(v["g"].values()) for v in views]
 
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
@@ -173,48 +308,13 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 
     Returns (num_rendered, out_color[3,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer); the three
     byte buffers are opaque and must be handed back to `rasterize_gaussians_backward`."""
-    if means3D.dim() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    dev = _dev_index(means3D)
-    P, H, W = means3D.size(0), int(image_height), int(image_width)
-    opts = dict(device=means3D.device)
-    out_color = torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, **opts)
-    radii = torch.empty((P,), dtype=torch.int32, **opts)
-    if P == 0:  # rasterize_points.cu:81 skips the rasterizer entirely
-        empty = torch.empty((0,), dtype=torch.uint8, **opts)
-        return 0, out_color.zero_(), radii, empty, empty.clone(), empty.clone()
-
-    background, means3D, opacity = _f32c(background), _f32c(means3D), _f32c(opacity)
-    colors, scales, rotations, cov3D_precomp, sh = (_f32c(t) for t in (colors, scales, rotations, cov3D_precomp, sh))
-    viewmatrix, projmatrix, campos = _f32c(viewmatrix), _f32c(projmatrix), _f32c(campos)
-    M = sh.size(1) if sh.numel() != 0 else 0
-
-    L = _lib.lib()
-    h = _lib.handle(dev, _slot)
-    prm = _params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, prefiltered, debug, _raw,
-                  _aux(visible=_visible))
-    inp = _inputs(background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                  campos)
-    geom = torch.empty((L.fr_geometry_bytes(P),), dtype=torch.uint8, **opts)
-    img = torch.empty((L.fr_image_bytes(W, H),), dtype=torch.uint8, **opts)
-    cap = max(_capacity_hint.get(dev, 0), 4 * P + 65536)
-    counts = _lib.fr_counts()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        while True:
-            binning = torch.empty((L.fr_binning_bytes(cap, W, H),), dtype=torch.uint8, **opts)
-            rc = L.fr_forward(h, C.byref(prm), C.byref(inp), out_color.data_ptr(), radii.data_ptr(), geom.data_ptr(),
-                              img.data_ptr(), binning.data_ptr(), cap, C.byref(counts), stream)
-            if rc == _lib.FR_ERR_BINNING_CAPACITY:
-                cap = int(counts.num_instances * 1.25) + 1024
-                continue
-            _check(rc, "fr_forward")
-            break
-    if _no_wait:  # counts arrive later (read_counts / check_async_overflow)
-        return 0, out_color, radii, geom, binning, img
-    _capacity_hint[dev] = max(_capacity_hint.get(dev, 0), int(counts.num_instances * 1.25) + 1024)
-    last_counts[dev] = counts
-    return int(counts.num_rendered), out_color, radii, geom, binning, img
+    v = _forward_view((background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                       projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug),
+                      _raw, _visible)
+    if v["prm"].P == 0:  # rasterize_points.cu:81 skips the rasterizer entirely
+        empty = torch.empty((0,), dtype=torch.uint8, device=means3D.device)
+        return 0, v["out_color"].zero_(), v["radii"], empty, empty.clone(), empty.clone()
+    return _launch_forward([v], [_slot], batch=False)[0]
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -226,52 +326,16 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     Returns (dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dsh[P,M,3],
     dL_dscales[P,3], dL_drotations[P,4]).  `_stats=(xyz_gradient_accum[P,1], denom[P,1])` (extension): the kernel
     also does `_add_densification_stats` (model/fateavatar.py:734-737) for the Gaussians with radii > 0.
-    `_accumulate` (extension): names of `_out` buffers the frame's gradient is ADDED to (FR_FLAG_ACCUMULATE)."""
-    dev = _dev_index(means3D)
-    P = means3D.size(0)
-    H, W = dL_dout_color.size(1), dL_dout_color.size(2)
-    M = sh.size(1) if sh.numel() != 0 else 0
-    opts = dict(device=means3D.device, dtype=torch.float32)
-    shapes = dict(dL_dmeans2D=(P, 3), dL_dcolors=(P, NUM_CHANNELS), dL_dopacity=(P, 1), dL_dmeans3D=(P, 3),
-                  dL_dcov3D=(P, 6), dL_dsh=(P, M, 3), dL_dscales=(P, 3), dL_drotations=(P, 4))
-    names = tuple(shapes)
-    for k in _accumulate:
-        if not (_out and _out.get(k) is not None):
-            raise RuntimeError(f"rasterize_gaussians_backward: cannot accumulate into {k}: no buffer was given for it")
-    if P == 0:
-        return tuple((_out[k] if k in _accumulate else torch.zeros(s, **opts)) for k, s in shapes.items())
-    acc_flags = sum(1 << (_lib.FR_FLAG_ACCUMULATE_SHIFT + names.index(k)) for k in _accumulate)
-    # the kernel writes every row of every array it is given, so uninitialised memory is fine
-    g = {k: (torch.empty(s, **opts) if (_want is None or k in _want) else None) for k, s in shapes.items()}
-    if _out:  # caller-provided gradient buffers (e.g. views into a flat gradient buffer): written in place
-        for k, buf in _out.items():
-            if buf is not None:
-                assert buf.shape == shapes[k] and buf.is_contiguous() and buf.dtype == torch.float32, k
-                # a FRESH view object: autograd's AccumulateGrad only adopts an incoming gradient without
-                # cloning it when nobody else holds a reference to that tensor object
-                g[k] = buf.view(buf.shape)
-
-    background, means3D = _f32c(background), _f32c(means3D)
-    colors, scales, rotations, cov3D_precomp, sh = (_f32c(t) for t in (colors, scales, rotations, cov3D_precomp, sh))
-    viewmatrix, projmatrix, campos = _f32c(viewmatrix), _f32c(projmatrix), _f32c(campos)
-    dL_dout_color = _f32c(dL_dout_color)
-    radii = radii.contiguous()
-
-    L = _lib.lib()
-    h = _lib.handle(dev, _slot)
-    aux = _aux(grad_accum=_stats3(_stats)[0], denom=_stats3(_stats)[1], overflow_out=_stats3(_stats)[2]) if _stats is not None else None
-    prm = _params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, False, debug, _raw, aux, acc_flags)
-    inp = _inputs(background, means3D, sh, colors, None, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                  campos)
-    grads = _lib.fr_grads(*[_ptr(g[k]) for k in ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D",
-                                                  "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")])
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = L.fr_backward(h, C.byref(prm), C.byref(inp), radii.data_ptr(), geomBuffer.data_ptr(),
-                           imageBuffer.data_ptr(), binningBuffer.data_ptr(), dL_dout_color.data_ptr(),
-                           C.byref(grads), stream)
-    _check(rc, "fr_backward")
-    return tuple(g.values())
+    `_want` (extension): the names of the gradients to compute (the others come back as None); `_out`: caller-provided
+    gradient buffers, written in place; `_accumulate`: names of `_out` buffers the frame's gradient is ADDED to
+    (FR_FLAG_ACCUMULATE)."""
+    v = _backward_view((background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                        projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
+                        imageBuffer, debug), _raw, _want, _out, _stats, _accumulate)
+    if v["prm"].P == 0:
+        return tuple((_out[k] if k in _accumulate else torch.zeros(s, device=means3D.device, dtype=torch.float32))
+                     for k, s in _grad_shapes(0, v["prm"].M).items())
+    return _launch_backward([v], [_slot], batch=False)[0]
 
 
 # ------------------------------------------------------------------ batched frames (fr_forward_batch / fr_backward_batch)
@@ -290,70 +354,17 @@ def rasterize_gaussians_batch(views, slots=None, raw=False, visibles=None, bindi
         raise RuntimeError("rasterize_gaussians_batch: the views of a batch need a handle slot each")
     visibles = visibles or [None] * K
     bindings = bindings or [None] * K
-    L = _lib.lib()
     st = []
-    dev = None
     for k, a in enumerate(views):
-        (background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
-         tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug) = a
-        if bindings[k] is not None and not all(t.is_contiguous() and t.dtype == torch.float32 for t in (means3D, scales, rotations)):
+        if bindings[k] is not None and not all(t.is_contiguous() and t.dtype == torch.float32 for t in (a[1], a[4], a[5])):
             raise RuntimeError("rasterize_gaussians_batch: a bound view's means3D / scales / rotations are written in place")
-        if means3D.dim() != 2 or means3D.size(1) != 3:
-            raise RuntimeError("means3D must have dimensions (num_points, 3)")
-        d = _dev_index(means3D)
-        if dev is None:
-            dev = d
-        elif d != dev:
+        v = _forward_view(a, raw, visibles[k], bindings[k])
+        if st and v["dev"] != st[0]["dev"]:
             raise RuntimeError("rasterize_gaussians_batch: the views of a batch live on one device")
-        P, H, W = means3D.size(0), int(image_height), int(image_width)
-        if P == 0:
+        if v["prm"].P == 0:
             raise RuntimeError("rasterize_gaussians_batch: batched views need at least one Gaussian")
-        opts = dict(device=means3D.device)
-        background, means3D, opacity = _f32c(background), _f32c(means3D), _f32c(opacity)
-        colors, scales, rotations, cov3D_precomp, sh = (_f32c(t) for t in (colors, scales, rotations, cov3D_precomp, sh))
-        viewmatrix, projmatrix, campos = _f32c(viewmatrix), _f32c(projmatrix), _f32c(campos)
-        M = sh.size(1) if sh.numel() != 0 else 0
-        v = dict(P=P, H=H, W=W, opts=opts,
-                 keep=(background, means3D, opacity, colors, scales, rotations, cov3D_precomp, sh, viewmatrix, projmatrix, campos),
-                 prm=_params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, prefiltered, debug, raw,
-                             _aux(visible=visibles[k], binding=bindings[k])),
-                 inp=_inputs(background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos),
-                 out_color=torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, **opts),
-                 radii=torch.empty((P,), dtype=torch.int32, **opts),
-                 geom=torch.empty((L.fr_geometry_bytes(P),), dtype=torch.uint8, **opts),
-                 img=torch.empty((L.fr_image_bytes(W, H),), dtype=torch.uint8, **opts),
-                 cap=max(_capacity_hint.get(d, 0), 4 * P + 65536))
         st.append(v)
-    handles = (C.c_void_p * K)(*[_lib.handle(dev, sl) for sl in slots])
-    prm_p = (C.POINTER(_lib.fr_params) * K)(*[C.pointer(v["prm"]) for v in st])
-    inp_p = (C.POINTER(_lib.fr_inputs) * K)(*[C.pointer(v["inp"]) for v in st])
-    arr = lambda key: (C.c_void_p * K)(*[v[key].data_ptr() for v in st])  # noqa: E731
-    counts = (_lib.fr_counts * K)()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        while True:
-            for v in st:
-                v["binning"] = torch.empty((L.fr_binning_bytes(v["cap"], v["W"], v["H"]),), dtype=torch.uint8, **v["opts"])
-            caps = (C.c_uint64 * K)(*[v["cap"] for v in st])
-            rc = L.fr_forward_batch(K, handles, prm_p, inp_p, arr("out_color"), arr("radii"), arr("geom"), arr("img"),
-                                    arr("binning"), caps, counts, stream)
-            if rc == _lib.FR_ERR_BINNING_CAPACITY:
-                for k, v in enumerate(st):
-                    if counts[k].overflow:
-                        v["cap"] = int(counts[k].num_instances * 1.25) + 1024
-                continue
-            _check(rc, "fr_forward_batch")
-            break
-    out = []
-    for k, v in enumerate(st):
-        if _no_wait:
-            out.append((0, v["out_color"], v["radii"], v["geom"], v["binning"], v["img"]))
-            continue
-        c = _lib.fr_counts(counts[k].num_rendered, counts[k].num_instances, counts[k].max_tile_list, counts[k].overflow)
-        _capacity_hint[dev] = max(_capacity_hint.get(dev, 0), int(c.num_instances * 1.25) + 1024)
-        last_counts[dev] = c
-        out.append((int(c.num_rendered), v["out_color"], v["radii"], v["geom"], v["binning"], v["img"]))
-    return out
+    return _launch_forward(st, slots, batch=True)
 
 
 def rasterize_gaussians_backward_batch(views, slots=None, raw=False, wants=None, outs=None, stats=None, accumulates=None,
@@ -369,62 +380,15 @@ def rasterize_gaussians_backward_batch(views, slots=None, raw=False, wants=None,
     slots = list(range(K)) if slots is None else [int(x) for x in slots]
     wants, outs, stats, accumulates, bindings, bind_grads = (x or [None] * K for x in (wants, outs, stats, accumulates, bindings,
                                                                                       bind_grads))
-    L = _lib.lib()
-    st = []
-    dev = None
-    names = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")
-    for k, a in enumerate(views):
-        (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
-         tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug) = a
-        d = _dev_index(means3D)
-        dev = d if dev is None else dev
-        P = means3D.size(0)
-        H, W = dL_dout_color.size(1), dL_dout_color.size(2)
-        M = sh.size(1) if sh.numel() != 0 else 0
-        opts = dict(device=means3D.device, dtype=torch.float32)
-        shapes = dict(dL_dmeans2D=(P, 3), dL_dcolors=(P, NUM_CHANNELS), dL_dopacity=(P, 1), dL_dmeans3D=(P, 3),
-                      dL_dcov3D=(P, 6), dL_dsh=(P, M, 3), dL_dscales=(P, 3), dL_drotations=(P, 4))
-        acc = tuple(accumulates[k] or ())
-        out_k = outs[k] or {}
-        for n in acc:
-            if out_k.get(n) is None:
-                raise RuntimeError(f"rasterize_gaussians_backward_batch: cannot accumulate into {n}: no buffer was given for it")
-        acc_flags = sum(1 << (_lib.FR_FLAG_ACCUMULATE_SHIFT + names.index(n)) for n in acc)
-        g = {n: (torch.empty(sh_, **opts) if (wants[k] is None or n in wants[k]) else None) for n, sh_ in shapes.items()}
-        for n, buf in out_k.items():
-            if buf is not None:
-                assert buf.shape == shapes[n] and buf.is_contiguous() and buf.dtype == torch.float32, n
-                g[n] = buf.view(buf.shape)
-        background, means3D = _f32c(background), _f32c(means3D)
-        colors, scales, rotations, cov3D_precomp, sh = (_f32c(t) for t in (colors, scales, rotations, cov3D_precomp, sh))
-        viewmatrix, projmatrix, campos = _f32c(viewmatrix), _f32c(projmatrix), _f32c(campos)
-        dL_dout_color = _f32c(dL_dout_color)
-        radii = radii.contiguous()
-        aux = _aux(grad_accum=_stats3(stats[k])[0], denom=_stats3(stats[k])[1], overflow_out=_stats3(stats[k])[2],
-                   binding=bindings[k], bind_grads=bind_grads[k])
-        v = dict(g=g, keep=(background, means3D, colors, scales, rotations, cov3D_precomp, sh, viewmatrix, projmatrix, campos,
-                            dL_dout_color, radii, geomBuffer, binningBuffer, imageBuffer),
-                 prm=_params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, False, debug, raw, aux, acc_flags),
-                 inp=_inputs(background, means3D, sh, colors, None, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos),
-                 grads=_lib.fr_grads(*[_ptr(g[n]) for n in names]),
-                 radii=radii, geom=geomBuffer, img=imageBuffer, binning=binningBuffer, dpix=dL_dout_color)
-        st.append(v)
+    st = [_backward_view(a, raw, wants[k], outs[k], stats[k], tuple(accumulates[k] or ()), bindings[k], bind_grads[k],
+                         "rasterize_gaussians_backward_batch") for k, a in enumerate(views)]
     # fr_aux::overflow_out is OVERWRITTEN (0 or 1) by every backward: views of one launch that shared a word would race, and a
     # view that did not overflow could clear the flag of one that did (the optimizer would step on a partly zero gradient)
     words = [int(_stats3(stats[k])[2].data_ptr()) for k in range(K) if _stats3(stats[k])[2] is not None]
     if len(set(words)) != len(words):
         raise RuntimeError("rasterize_gaussians_backward_batch: the views of a batch need ONE overflow word EACH "
                            "(fused_densification_stats[2]); give every view its own statistics tuple")
-    handles = (C.c_void_p * K)(*[_lib.handle(dev, sl) for sl in slots])
-    prm_p = (C.POINTER(_lib.fr_params) * K)(*[C.pointer(v["prm"]) for v in st])
-    inp_p = (C.POINTER(_lib.fr_inputs) * K)(*[C.pointer(v["inp"]) for v in st])
-    grd_p = (C.POINTER(_lib.fr_grads) * K)(*[C.pointer(v["grads"]) for v in st])
-    arr = lambda key: (C.c_void_p * K)(*[v[key].data_ptr() for v in st])  # noqa: E731
-    with torch.cuda.device(dev):
-        rc = L.fr_backward_batch(K, handles, prm_p, inp_p, arr("radii"), arr("geom"), arr("img"), arr("binning"), arr("dpix"),
-                                 grd_p, torch.cuda.current_stream(dev).cuda_stream)
-    _check(rc, "fr_backward_batch")
-    return [tuple(v["g"].values()) for v in st]
+    return _launch_backward(st, slots, batch=True)
 
 
 class _RasterizeGaussiansBatch(torch.autograd.Function):
@@ -437,29 +401,20 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         assert len(tensors) == 8 * K
         ctx.raw, ctx.K, ctx.settings, ctx.slots = bool(raw_activations), K, settings, slots
         ctx.set_materialize_grads(False)
-        views, viss = [], []
-        for k, rs in enumerate(settings):
-            means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = tensors[8 * k:8 * k + 8]
-            views.append((rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-                          rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
-                          rs.sh_degree, rs.campos, rs.prefiltered, rs.debug))
-            viss.append(torch.empty((means3D.shape[0],), dtype=torch.bool, device=means3D.device))
-        res = rasterize_gaussians_batch(views, slots=slots, raw=ctx.raw, visibles=viss)
-        ctx.stats, ctx.num_rendered, ctx.grad_slots, ctx.grad_owners = [], [], [], []
+        per_view = [tensors[8 * k:8 * k + 8] for k in range(K)]
+        viss = [torch.empty((t[0].shape[0],), dtype=torch.bool, device=t[0].device) for t in per_view]
+        res = rasterize_gaussians_batch([_forward_args(rs, *t) for rs, t in zip(settings, per_view)], slots=slots,
+                                        raw=ctx.raw, visibles=viss)
+        ctx.stats, ctx.num_rendered, ctx.grads = [], [], []
         saved, outs = [], []
-        for k in range(K):
-            means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = tensors[8 * k:8 * k + 8]
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = res[k]
-            radii._fr_visible = viss[k]
+        for (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), vis, r in \
+                zip(per_view, viss, res):
+            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = r
+            radii._fr_visible = vis
             ctx.stats.append(getattr(means2D, "_fr_densification_stats", None))
             ctx.num_rendered.append(num_rendered)
-            slots_k = {"dL_dmeans3D": GradOut.of(means3D), "dL_dsh": GradOut.of(sh) if sh.numel() else None}
-            owners = {"dL_dmeans3D": means3D, "dL_dsh": sh}
-            if ctx.raw:
-                slots_k.update(dL_dopacity=GradOut.of(opacities), dL_dscales=GradOut.of(scales), dL_drotations=GradOut.of(rotations))
-                owners.update(dL_dopacity=opacities, dL_dscales=scales, dL_drotations=rotations)
-            ctx.grad_slots.append(slots_k)
-            ctx.grad_owners.append({n: t for n, t in owners.items() if slots_k.get(n) is not None and t.is_leaf})
+            ctx.grads.append(_FrameGrads.of_frame(ctx.raw, means3D, sh, colors_precomp, opacities, scales, rotations,
+                                                  cov3Ds_precomp))
             saved += [colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer]
             outs += [color, radii]
         ctx.save_for_backward(*saved)
@@ -468,43 +423,21 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grad_outs):
-        K = ctx.K
-        none = (None, None, None) + (None,) * (8 * K)
         grad_colors = grad_outs[0::2]
         if all(g is None for g in grad_colors):
-            return none
-        views, wants, outs, accs = [], [], [], []
-        for k, rs in enumerate(ctx.settings):
-            colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = \
-                ctx.saved_tensors[10 * k:10 * k + 10]
-            g = grad_colors[k]
+            return (None, None, None) + (None,) * (8 * ctx.K)
+        views, outs = [], []
+        for k, (rs, g) in enumerate(zip(ctx.settings, grad_colors)):
+            saved = ctx.saved_tensors[10 * k:10 * k + 10]
             if g is None:   # (a view nobody differentiated: its frame still runs with a zero image gradient)
-                g = torch.zeros((NUM_CHANNELS, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
-            views.append((rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
-                          rs.projmatrix, rs.tanfovx, rs.tanfovy, g, sh, rs.sh_degree, rs.campos, geomBuffer, ctx.num_rendered[k],
-                          binningBuffer, imgBuffer, rs.debug))
-            want = {"dL_dmeans2D", "dL_dopacity", "dL_dmeans3D", "dL_dscales", "dL_drotations"}
-            if colors_precomp.numel():
-                want.add("dL_dcolors")
-            if cov3Ds_precomp.numel():
-                want.add("dL_dcov3D")
-            if sh.numel():
-                want.add("dL_dsh")
-            claims = {n: slot.claim(ctx.grad_owners[k].get(n)) for n, slot in ctx.grad_slots[k].items() if slot is not None}
+                g = torch.zeros((NUM_CHANNELS, rs.image_height, rs.image_width), dtype=torch.float32, device=saved[1].device)
+            views.append(_backward_args(rs, saved, g, ctx.num_rendered[k]))
             # (in-kernel accumulation across the views of ONE batch would race: a later view of the same parameters gets a
             # fresh tensor, which autograd adds)
-            wants.append(want)
-            outs.append({n: c[0] for n, c in claims.items() if not c[1]})
-            accs.append(())
-        res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=ctx.raw, wants=wants, outs=outs, stats=ctx.stats,
-                                                 accumulates=accs)
-        flat = [None, None, None]
-        for k in range(K):
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-             grad_rotations) = res[k]
-            flat += [grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                     grad_cov3Ds_precomp]
-        return tuple(flat)
+            outs.append(ctx.grads[k].claim(accumulate=False)[0])
+        res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=ctx.raw, wants=[fg.want for fg in ctx.grads],
+                                                 outs=outs, stats=ctx.stats)
+        return (None, None, None) + tuple(t for grads in res for t in _input_grads(grads))
 
 
 def rasterize_views_autograd(settings, per_view_tensors, raw_activations=False, slots=None):
@@ -523,7 +456,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     P = means3D.size(0)
     present = torch.zeros((P,), dtype=torch.bool, device=means3D.device)
     if P != 0:
-        means3D, viewmatrix, projmatrix = _f32c(means3D), _f32c(viewmatrix), _f32c(projmatrix)
+        means3D, viewmatrix, projmatrix = _f32c(means3D, viewmatrix, projmatrix)
         with torch.cuda.device(dev):
             rc = _lib.lib().fr_mark_visible(P, means3D.data_ptr(), viewmatrix.data_ptr(), projmatrix.data_ptr(),
                                             present.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
@@ -545,6 +478,19 @@ def image_aux(imgBuffer: torch.Tensor, H: int, W: int):
 
 def cpu_deep_copy_tuple(input_tuple):
     return tuple(item.cpu().clone() if isinstance(item, torch.Tensor) else item for item in input_tuple)
+
+
+def _snapshot_on_error(debug, dump, message, fn, args, **kw):
+    """fn(*args, **kw); in debug mode a CPU copy of `args` is saved to `dump` if it raises (__init__.py:83-92, 132-141)."""
+    if not debug:
+        return fn(*args, **kw)
+    cpu_args = cpu_deep_copy_tuple(args)
+    try:
+        return fn(*args, **kw)
+    except Exception:
+        torch.save(cpu_args, dump)
+        print(message)
+        raise
 
 
 class GradOut:
@@ -587,6 +533,82 @@ class GradOut:
         return None, False
 
 
+class _FrameGrads:
+    """One frame's gradients as its autograd Function sees them: `want`, the names its backward computes, and the GradOut
+    slots of its inputs (taken in the forward, claimed in the backward)."""
+
+    def __init__(self, owners, sh, colors_precomp=None, cov3Ds_precomp=None, bound=False):
+        """`owners`: gradient name -> the input tensor whose GradOut slot may receive it, or None.  `bound`: a frame rendered from
+        its mesh binding, whose means3D / scales / rotations are kernel outputs (the kernel carries their gradients on to
+        the binding's inputs)."""
+        # gradients nobody can receive are not computed: dL_dcolors without colors_precomp, dL_dcov3D without
+        # cov3D_precomp, dL_dsh without sh (the reference fills them in and autograd drops them)
+        self.want = {"dL_dmeans2D", "dL_dopacity"} if bound else \
+            {"dL_dmeans2D", "dL_dopacity", "dL_dmeans3D", "dL_dscales", "dL_drotations"}
+        for k, t in (("dL_dcolors", colors_precomp), ("dL_dcov3D", cov3Ds_precomp), ("dL_dsh", sh)):
+            if t is not None and t.numel():
+                self.want.add(k)
+        self.slots, self.owners = {}, {}
+        for k, t in owners.items():
+            slot = GradOut.of(t) if t is not None else None
+            if slot is not None:
+                self.slots[k] = slot
+                if t.is_leaf:  # (leaves only: a reference to a non-leaf input from its own grad_fn's context would be a cycle)
+                    self.owners[k] = t
+
+    @staticmethod
+    def of_frame(raw, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
+        # optional extension: an input tensor may carry `_fr_grad_out`, a GradOut slot whose preallocated buffer
+        # receives its gradient (zero-copy into e.g. a flat data-parallel gradient buffer)
+        owners = {"dL_dmeans3D": means3D, "dL_dsh": sh if sh.numel() else None}
+        if raw:  # raw parameters reach the kernels directly: their gradients can be written in place too
+            owners.update(dL_dopacity=opacities, dL_dscales=scales, dL_drotations=rotations)
+        return _FrameGrads(owners, sh, colors_precomp, cov3Ds_precomp)
+
+    def claim(self, accumulate=True):
+        """-> (outs, added): per slot the buffer the backward writes into (None: a fresh tensor), and the names the kernel
+        ADDS to their buffer (only with `accumulate`; otherwise such a slot is left out).  The FIRST backward of a step may
+        write a gradient straight into its slot's buffer; any further backward of the same step (several frames rendered
+        from the same parameters) gets a fresh tensor, which autograd then adds to the first (see GradOut)."""
+        outs, added = {}, []
+        for k, slot in self.slots.items():
+            buf, add = slot.claim(self.owners.get(k))
+            if add and not accumulate:
+                continue
+            outs[k] = buf
+            if add:
+                added.append(k)
+        return outs, tuple(added)
+
+
+def _forward_args(rs, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
+    """The positional arguments of `rasterize_gaussians` for a frame's eight tensor inputs, in the order of
+    `_RasterizeGaussians.forward` (means2D is not one of them): diff_gaussian_rasterization/__init__.py:60-80."""
+    return (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+            rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, rs.campos,
+            rs.prefiltered, rs.debug)
+
+
+def _backward_args(rs, saved, grad_out_color, num_rendered):
+    """The positional arguments of `rasterize_gaussians_backward` from what the forward saved: (colors_precomp, means3D,
+    scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer): __init__.py:109-129."""
+    colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = saved
+    return (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+            rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geomBuffer, num_rendered,
+            binningBuffer, imgBuffer, rs.debug)
+
+
+_INPUT_GRADS = [(k, _GRAD_NAMES.index(k)) for k in ("dL_dmeans3D", "dL_dmeans2D", "dL_dsh", "dL_dcolors", "dL_dopacity",
+                                                     "dL_dscales", "dL_drotations", "dL_dcov3D")]
+
+
+def _input_grads(grads, added=()):
+    """The results of `rasterize_gaussians_backward` in the order of the frame's tensor inputs (means3D, means2D, sh,
+    colors_precomp, opacities, scales, rotations, cov3Ds_precomp); None for the names in `added`, whose gradient is
+    already in the parameter's .grad (nothing for autograd to add)."""
+    return tuple([None if k in added else grads[i] for k, i in _INPUT_GRADS])
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """diff_gaussian_rasterization/__init__.py:44-155."""
 
@@ -598,24 +620,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.fr_slot = _slot   # the backward goes through the handle the forward used
         # the gradient slot of the int32 `radii` output would otherwise be materialised as a zero tensor per backward
         ctx.set_materialize_grads(False)
-        args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
-                rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
+        args = _forward_args(rs, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         # extension: the visibility mask (radii > 0) comes out of the preprocess kernel; render() picks it up from
         # `radii._fr_visible` instead of launching a compare kernel
         vis = torch.empty((means3D.shape[0],), dtype=torch.bool, device=means3D.device) if means3D.is_cuda else None
-        if rs.debug:
-            cpu_args = cpu_deep_copy_tuple(args)
-            try:
-                num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = \
-                    rasterize_gaussians(*args, _raw=ctx.raw, _visible=vis)
-            except Exception as ex:
-                torch.save(cpu_args, "snapshot_fw.dump")
-                print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                raise ex
-        else:
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = \
-                rasterize_gaussians(*args, _raw=ctx.raw, _visible=vis)
+        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _snapshot_on_error(
+            rs.debug, "snapshot_fw.dump", "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.",
+            rasterize_gaussians, args, _raw=ctx.raw, _visible=vis)
         if vis is not None and means3D.shape[0] > 0:
             radii._fr_visible = vis
         # extension: `means2D._fr_densification_stats = (xyz_gradient_accum, denom)` makes the backward kernel
@@ -623,16 +634,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.stats = getattr(means2D, "_fr_densification_stats", None)
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
-        # optional extension: an input tensor may carry `_fr_grad_out`, a GradOut slot whose preallocated buffer
-        # receives its gradient (zero-copy into e.g. a flat data-parallel gradient buffer)
-        ctx.grad_slots = {"dL_dmeans3D": GradOut.of(means3D), "dL_dsh": GradOut.of(sh) if sh.numel() else None}
-        owners = {"dL_dmeans3D": means3D, "dL_dsh": sh}
-        if ctx.raw:  # raw parameters reach the kernels directly: their gradients can be written in place too
-            ctx.grad_slots.update(dL_dopacity=GradOut.of(opacities), dL_dscales=GradOut.of(scales),
-                                  dL_drotations=GradOut.of(rotations))
-            owners.update(dL_dopacity=opacities, dL_dscales=scales, dL_drotations=rotations)
-        # (leaves only: a reference to a non-leaf input from its own grad_fn's context would be a cycle)
-        ctx.grad_owners = {k: t for k, t in owners.items() if ctx.grad_slots.get(k) is not None and t.is_leaf}
+        ctx.grads = _FrameGrads.of_frame(ctx.raw, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
                               binningBuffer, imgBuffer)
         ctx.mark_non_differentiable(radii)
@@ -640,51 +642,17 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, _):
-        num_rendered = ctx.num_rendered
         rs = ctx.raster_settings
         if grad_out_color is None:
             return (None,) * 10
-        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = \
-            ctx.saved_tensors
-        args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
-                geomBuffer, num_rendered, binningBuffer, imgBuffer, rs.debug)
-        # gradients nobody can receive are not computed: dL_dcolors without colors_precomp, dL_dcov3D without
-        # cov3D_precomp, dL_dsh without sh (the reference fills them in and autograd drops them)
-        want = {"dL_dmeans2D", "dL_dopacity", "dL_dmeans3D", "dL_dscales", "dL_drotations"}
-        if colors_precomp.numel():
-            want.add("dL_dcolors")
-        if cov3Ds_precomp.numel():
-            want.add("dL_dcov3D")
-        if sh.numel():
-            want.add("dL_dsh")
-        if rs.debug:
-            cpu_args = cpu_deep_copy_tuple(args)
-            try:
-                with handle_slot(ctx.fr_slot):
-                    grads = rasterize_gaussians_backward(*args, _raw=ctx.raw, _stats=ctx.stats, _want=want)
-            except Exception as ex:
-                torch.save(cpu_args, "snapshot_bw.dump")
-                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                raise ex
-        else:
-            # the FIRST backward of a step may write a gradient straight into its slot's buffer; any further backward
-            # of the same step (several frames rendered from the same parameters) gets a fresh tensor, which autograd
-            # then adds to the first
-            claims = {k: slot.claim(ctx.grad_owners.get(k)) for k, slot in ctx.grad_slots.items() if slot is not None}
-            out = {k: c[0] for k, c in claims.items()}
-            added = tuple(k for k, c in claims.items() if c[1])
-            with handle_slot(ctx.fr_slot):
-                grads = rasterize_gaussians_backward(*args, _out=out, _raw=ctx.raw, _stats=ctx.stats, _want=want,
-                                                     _accumulate=added)
-            if added:   # already in the parameter's .grad: nothing for autograd to add
-                names = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
-                         "dL_drotations")
-                grads = tuple(None if n in added else g for n, g in zip(names, grads))
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = grads
-        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
-                grad_rotations, grad_cov3Ds_precomp, None, None)
+        args = _backward_args(rs, ctx.saved_tensors, grad_out_color, ctx.num_rendered)
+        out, added = ({}, ()) if rs.debug else ctx.grads.claim()   # (debug mode claims no GradOut slot)
+        with handle_slot(ctx.fr_slot):
+            grads = _snapshot_on_error(
+                rs.debug, "snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n",
+                rasterize_gaussians_backward, args, _out=out, _raw=ctx.raw, _stats=ctx.stats, _want=ctx.grads.want,
+                _accumulate=added)
+        return _input_grads(grads, added) + (None, None)
 
 
 def rasterize_gaussians_autograd(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,

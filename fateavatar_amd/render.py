@@ -30,63 +30,52 @@ def _zero_points(means3D: torch.Tensor) -> torch.Tensor:
     return z.detach().requires_grad_(True)
 
 
+def _screenspace_points(means3D: torch.Tensor, pc) -> torch.Tensor:
+    """The tensor whose .grad receives the screen-space mean gradients (render_3dgs.py:21-27).  The reference adds `+ 0`
+    and retains the gradient of the resulting non-leaf; a leaf collects the same .grad with one kernel less and lets
+    autograd adopt the rasterizer's gradient buffer instead of copying it."""
+    sp = _zero_points(means3D)
+    stats = getattr(pc, "fused_densification_stats", None)
+    if stats is not None:  # extension: (xyz_gradient_accum, denom) updated inside the backward kernel
+        sp._fr_densification_stats = stats
+    return sp
+
+
+def _settings(cam, pc, bg, scaling_modifier) -> GaussianRasterizationSettings:
+    """render_3dgs.py:30-46."""
+    return GaussianRasterizationSettings(
+        image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
+        tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scaling_modifier, viewmatrix=cam.world_view_transform,
+        projmatrix=cam.full_proj_transform, sh_degree=pc.max_sh_degree, campos=cam.camera_center, prefiltered=False,
+        debug=False)
+
+
+def _activations(pc):
+    """(fused, opacity, scales, rotations).  Extension: a holder that sets `fused_activations` hands
+    over its RAW opacity / scaling / rotation and the HIP kernels apply sigmoid / exp / normalize (and their derivatives)
+    themselves, instead of ~15 small PyTorch kernels per frame.  The default is the reference behaviour."""
+    if getattr(pc, "fused_activations", False):
+        return True, pc._opacity, pc._scaling, pc._rotation
+    return False, pc.get_opacity, pc.get_scaling, pc.get_rotation
+
+
+def _result(image, radii, screenspace_points) -> dict:
+    visible = getattr(radii, "_fr_visible", None)  # written by the preprocess kernel (same values as radii > 0)
+    return {"render": image, "viewspace_points": screenspace_points,
+            "visibility_filter": visible if visible is not None else radii > 0, "radii": radii}
+
+
 def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, override_color: torch.Tensor = None,
            device='cuda'):
     means3D = pc.get_xyz
-    # zero tensor whose .grad receives the screen-space mean gradients (render_3dgs.py:21-27).  The reference adds
-    # `+ 0` and retains the gradient of the resulting non-leaf; a leaf collects the same .grad with one kernel less
-    # and lets autograd adopt the rasterizer's gradient buffer instead of copying it.
-    screenspace_points = _zero_points(means3D)
-    stats = getattr(pc, "fused_densification_stats", None)
-    if stats is not None:  # extension: (xyz_gradient_accum, denom) updated inside the backward kernel
-        screenspace_points._fr_densification_stats = stats
-    if screenspace_points.requires_grad:
-        try:
-            screenspace_points.retain_grad()
-        except Exception:
-            pass
-
-    tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
-    tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
-    raster_settings = GaussianRasterizationSettings(
-        image_height=int(viewpoint_camera.image_height),
-        image_width=int(viewpoint_camera.image_width),
-        tanfovx=tanfovx,
-        tanfovy=tanfovy,
-        bg=bg_color,
-        scale_modifier=scaling_modifier,
-        viewmatrix=viewpoint_camera.world_view_transform,
-        projmatrix=viewpoint_camera.full_proj_transform,
-        sh_degree=pc.max_sh_degree,
-        campos=viewpoint_camera.camera_center,
-        prefiltered=False,
-        debug=False,
-    )
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
-    means2D = screenspace_points
-    # Extension: a holder that sets `fused_activations` hands over its RAW opacity / scaling /
-    # rotation and the HIP kernels apply sigmoid / exp / normalize (and their derivatives) themselves, instead of
-    # ~15 small PyTorch kernels per frame.  The default is the reference behaviour.
-    fused = bool(getattr(pc, "fused_activations", False))
-    if fused:
-        opacity, scales, rotations = pc._opacity, pc._scaling, pc._rotation
-    else:
-        opacity = pc.get_opacity
-        scales = pc.get_scaling
-        rotations = pc.get_rotation
-    cov3D_precomp = None
-    shs = pc.get_features
-    if override_color is None:
-        colors_precomp = None
-    else:
-        colors_precomp = override_color
-        shs = None
-    rendered_image, radii = rasterizer(means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp,
-                                       opacities=opacity, scales=scales, rotations=rotations,
-                                       cov3D_precomp=cov3D_precomp, **({"raw_activations": True} if fused else {}))
-    visible = getattr(radii, "_fr_visible", None)  # written by the preprocess kernel (same values as radii > 0)
-    return {"render": rendered_image, "viewspace_points": screenspace_points,
-            "visibility_filter": visible if visible is not None else radii > 0, "radii": radii}
+    screenspace_points = _screenspace_points(means3D, pc)
+    rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, pc, bg_color, scaling_modifier))
+    fused, opacity, scales, rotations = _activations(pc)
+    shs, colors_precomp = (pc.get_features, None) if override_color is None else (None, override_color)
+    rendered_image, radii = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
+                                       opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=None,
+                                       **({"raw_activations": True} if fused else {}))
+    return _result(rendered_image, radii, screenspace_points)
 
 
 def render_batch(viewpoint_cameras, pcs, bg_colors, scaling_modifier=1.0, slots=None):
@@ -95,42 +84,22 @@ def render_batch(viewpoint_cameras, pcs, bg_colors, scaling_modifier=1.0, slots=
     leave most of an MI355X idle; here every kernel of the frame is launched once for all K views, with no stream or
     hardware-queue arrangement on the caller's side.  `pcs` / `bg_colors`: one per view, or a single holder / tensor
     for all of them (shared Gaussians: autograd then sums the views' gradients).  Returns the list of render() dicts."""
-    import torch as _torch
     K = len(viewpoint_cameras)
     if not isinstance(pcs, (list, tuple)):
         pcs = [pcs] * K
-    if isinstance(bg_colors, _torch.Tensor):
+    if isinstance(bg_colors, torch.Tensor):
         bg_colors = [bg_colors] * K
     settings, tensors, points = [], [], []
     fused = bool(getattr(pcs[0], "fused_activations", False))
-    empty = _torch.Tensor([])
+    empty = torch.Tensor([])
     for cam, pc, bg in zip(viewpoint_cameras, pcs, bg_colors):
-        if bool(getattr(pc, "fused_activations", False)) != fused:
+        fused_k, opacity, scales, rotations = _activations(pc)
+        if fused_k != fused:
             raise RuntimeError("render_batch: the views' holders must agree on fused_activations")
         means3D = pc.get_xyz
-        sp = _zero_points(means3D)
-        stats = getattr(pc, "fused_densification_stats", None)
-        if stats is not None:
-            sp._fr_densification_stats = stats
-        try:
-            sp.retain_grad()
-        except Exception:
-            pass
-        settings.append(GaussianRasterizationSettings(
-            image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
-            tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scaling_modifier, viewmatrix=cam.world_view_transform,
-            projmatrix=cam.full_proj_transform, sh_degree=pc.max_sh_degree, campos=cam.camera_center, prefiltered=False,
-            debug=False))
-        if fused:
-            opacity, scales, rotations = pc._opacity, pc._scaling, pc._rotation
-        else:
-            opacity, scales, rotations = pc.get_opacity, pc.get_scaling, pc.get_rotation
+        sp = _screenspace_points(means3D, pc)
+        settings.append(_settings(cam, pc, bg, scaling_modifier))
         tensors.append((means3D, sp, pc.get_features, empty, opacity, scales, rotations, empty))
         points.append(sp)
     res = rasterize_views_autograd(settings, tensors, raw_activations=fused, slots=slots)
-    out = []
-    for (image, radii), sp in zip(res, points):
-        visible = getattr(radii, "_fr_visible", None)
-        out.append({"render": image, "viewspace_points": sp,
-                    "visibility_filter": visible if visible is not None else radii > 0, "radii": radii})
-    return out
+    return [_result(image, radii, sp) for (image, radii), sp in zip(res, points)]
