@@ -18,8 +18,8 @@ import torch
 
 from . import _lib
 from .binding import _chk, _desc
-from .rasterizer import (NUM_CHANNELS, _backward_args, _forward_args, _FrameGrads, rasterize_gaussians_backward_batch,
-                         rasterize_gaussians_batch)
+from .rasterizer import (NUM_CHANNELS, _backward_args, _forward_args, _FrameGrads, _pick_forward_only,
+                         rasterize_gaussians_backward_batch, rasterize_gaussians_batch)
 from .render import _result, _screenspace_points, _settings
 
 
@@ -40,7 +40,7 @@ class _RasterizeBoundBatch(torch.autograd.Function):
     PER_VIEW = 7
 
     @staticmethod
-    def forward(ctx, settings, bindings, slots, *tensors):
+    def forward(ctx, settings, bindings, slots, forward_only, *tensors):
         K, n = len(settings), _RasterizeBoundBatch.PER_VIEW
         assert len(tensors) == n * K and len(bindings) == K
         ctx.K, ctx.settings, ctx.bindings, ctx.slots = K, settings, bindings, slots
@@ -67,7 +67,7 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             bound.append((xyz, rot, scl))
             views.append(_forward_args(rs, xyz, means2D, sh, empty, opacities, scl, rot, empty))
             viss.append(torch.empty((N,), dtype=torch.bool, device=dev))
-        res = rasterize_gaussians_batch(views, slots=slots, raw=True, visibles=viss, bindings=descs)
+        res = rasterize_gaussians_batch(views, slots=slots, raw=True, visibles=viss, bindings=descs, forward_only=forward_only)
         ctx.stats, ctx.num_rendered, ctx.grads, ctx.offset_shapes = [], [], [], []
         saved, outs = [], []
         for k in range(K):
@@ -91,7 +91,7 @@ class _RasterizeBoundBatch(torch.autograd.Function):
         K, n = ctx.K, _RasterizeBoundBatch.PER_VIEW
         grad_colors = grad_outs[0::2]
         if all(g is None for g in grad_colors):
-            return (None, None, None) + (None,) * (n * K)
+            return (None,) * 4 + (None,) * (n * K)
         empty = torch.Tensor([])
         views, outs, descs, bgrads = [], [], [], []
         for k, (rs, mb) in enumerate(zip(ctx.settings, ctx.bindings)):
@@ -105,7 +105,7 @@ class _RasterizeBoundBatch(torch.autograd.Function):
                                         ctx.num_rendered[k]))
             claimed = ctx.grads[k].claim(accumulate=False)[0]
             outs.append({m: b for m, b in claimed.items() if m.startswith("dL_")})
-            need_v, need_o, need_r, need_s = ctx.needs_input_grad[3 + n * k:3 + n * k + 4]
+            need_v, need_o, need_r, need_s = ctx.needs_input_grad[4 + n * k:4 + n * k + 4]
 
             def buf(need, name, shape):
                 if not need:
@@ -121,7 +121,7 @@ class _RasterizeBoundBatch(torch.autograd.Function):
                            "d_rotation": buf(need_r, "d_rotation", (N, 4)), "d_scaling": buf(need_s, "d_scaling", (N, 3))})
         res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=[fg.want for fg in ctx.grads], outs=outs,
                                                  stats=ctx.stats, bindings=descs, bind_grads=bgrads)
-        flat = [None, None, None]
+        flat = [None, None, None, None]
         for k in range(K):
             grad_means2D, _, grad_opacities, _, _, grad_sh, _, _ = res[k]
             b = bgrads[k]
@@ -161,7 +161,8 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding: MeshBinding
         settings.append(_settings(cam, pc, bg, scaling_modifier))
         tensors += [verts, pc._offset, pc._rotation, pc._scaling, sp, pc.get_features, pc._opacity]
         points.append(sp)
-    res = _RasterizeBoundBatch.apply(settings, [mb] * K, list(range(K)) if slots is None else list(slots), *tensors)
+    res = _RasterizeBoundBatch.apply(settings, [mb] * K, list(range(K)) if slots is None else list(slots),
+                                     _pick_forward_only(tensors), *tensors)
     out = []
     for k, sp in enumerate(points):
         o = _result(res[2 * k], res[2 * k + 1], sp)

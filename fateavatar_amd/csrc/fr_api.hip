@@ -228,8 +228,14 @@ int fr_forward_batch(int32_t n_views, fr_handle* const* handles, const fr_params
         if (!out_color[k] || !image[k] || (prm[k]->P > 0 && (!radii[k] || !geometry[k])) || (binning_capacity[k] > 0 && !binning[k]))
             return fail_msg(FR_ERR_INVALID_ARGUMENT, "null output / scratch pointer");
         if (binning_capacity[k] >= (1ull << 32)) return fail_msg(FR_ERR_UNSUPPORTED, "binning capacity must be < 2^32 instances");
+        if ((prm[k]->flags ^ prm[0]->flags) & FR_FLAG_FORWARD_ONLY)
+            return fail_msg(FR_ERR_INVALID_ARGUMENT, "the views of a batch must agree on FR_FLAG_FORWARD_ONLY");
         c[k] = ForwardCall{h, prm[k], in[k], out_color[k], radii[k], geometry[k], image[k], binning[k], binning_capacity[k],
                            counts ? counts + k : nullptr};
+    }
+    for (int k = 0; k < n_views; k++) {   // (what fr_backward checks its buffers against)
+        c[k].h->last_fwd_flags = prm[k]->flags;
+        c[k].h->last_fwd_geometry = geometry[k], c[k].h->last_fwd_binning = binning[k];
     }
     return launch_forward(n_views, c, static_cast<hipStream_t>(stream));
 }
@@ -255,6 +261,10 @@ static int check_backward(const BackwardCall& c, bool batched)
     if (c.prm->P == 0) return batched ? fail_msg(FR_ERR_INVALID_ARGUMENT, "batched views need P > 0") : FR_OK;
     if (!c.radii || !c.geometry || !c.image || !c.binning || !c.dL_dpix || !c.grads)
         return fail_msg(FR_ERR_INVALID_ARGUMENT, "null pointer");
+    if ((c.h->last_fwd_flags & FR_FLAG_FORWARD_ONLY) && (c.geometry == c.h->last_fwd_geometry || c.binning == c.h->last_fwd_binning))
+        return fail_msg(FR_ERR_INVALID_ARGUMENT,
+                        "these buffers come from a forward-only frame (FR_FLAG_FORWARD_ONLY), which leaves no backward hand-off: "
+                        "render the frame without the flag to differentiate it");
     return FR_OK;
 }
 
@@ -316,8 +326,29 @@ const void* fr_debug_geometry_field(const void* geometry, int32_t P, int32_t fie
         case 6: return g.clamped;
         case 7: return nullptr;   // (the gradient accumulators moved into the handle)
         case 8: return g.rec_tmpl;   // [P][12]: x, y, a', b', c', opacity, r, g, b, id bits, depth, 0
+        case 9: return g.dcolor_ddir;   // [P][9]
+        case 10: return g.opacity_act;
         default: return nullptr;
     }
+}
+
+const void* fr_debug_binning_region(const void* binning, uint64_t capacity, int32_t W, int32_t H, int32_t region, size_t* bytes)
+{
+    if (bytes) *bytes = 0;
+    if (W <= 0 || H <= 0) return nullptr;
+    const ImageView v = ImageView::make(nullptr, W, H);
+    const BinningView b = BinningView::make(const_cast<void*>(binning), (size_t)capacity, (size_t)v.tiles_x * v.tiles_y);
+    const void* p = nullptr;
+    size_t n = 0;
+    switch (region) {
+        case 0: p = b.masks, n = b.cap * sizeof(uint2); break;
+        case 1: p = b.walks, n = b.unit_cap * kUnit * sizeof(uint2); break;
+        case 2: p = b.bwd_units, n = b.unit_cap * sizeof(BwdUnit); break;
+        case 3: p = b.unit_state, n = b.unit_cap * kUnit * sizeof(float4); break;
+        default: return nullptr;
+    }
+    if (bytes) *bytes = n;
+    return p;
 }
 
 int fr_debug_selftest_reduce(const float* in, float* out, void* stream)

@@ -954,8 +954,9 @@ __device__ __forceinline__ float load_row(const float* p)
 }
 
 // One wave, one tile: the image, and the backward entry state of every unit, from the units' final
-// contributions.  Pure loads and adds: the rows of 8 units are requested together.
-template <bool COHERENT>
+// contributions.  Pure loads and adds: the rows of 8 units are requested together.  FWD_ONLY (FR_FLAG_FORWARD_ONLY):
+// no entry state is stored, the image / final_T / n_contrib are the same.
+template <bool COHERENT, bool FWD_ONLY>
 __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, uint32_t u0, uint32_t nu, const float* g_out,
                                             float4* __restrict__ unit_state, int W, int H, float bg0, float bg1, float bg2,
                                             float* __restrict__ out_color, int lane)
@@ -995,7 +996,7 @@ __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, u
             if ((uint32_t)k < nu) {
                 const float inv = (To[k] >= 0.0001f) ? __builtin_amdgcn_rcpf(To[k]) : 0.f;   // (dead on entry: T may have underflowed)
                 // (the tile's LAST unit has nothing behind it and leaves with final_T: the backward builds that state itself)
-                if ((uint32_t)k + 1u < nu)
+                if (!FWD_ONLY && (uint32_t)k + 1u < nu)
                     unit_state[(size_t)(u0 + (uint32_t)k) * kUnit + lane] = make_float4(Sr * inv, Sg * inv, Sb * inv, To[k]);
                 Sr += cr[k], Sg += cg[k], Sb += cb[k];
             }
@@ -1026,7 +1027,7 @@ __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, u
                     if (!dead && !have_T) Tf = To[k], have_T = true;
                     if (!dead && !have_n && last) ncon = last, have_n = true;
                     const float inv = (To[k] >= 0.0001f) ? __builtin_amdgcn_rcpf(To[k]) : 0.f;
-                    if (base + (uint32_t)k + 1u < nu && !__all(dead))
+                    if (!FWD_ONLY && base + (uint32_t)k + 1u < nu && !__all(dead))
                         unit_state[(size_t)(u0 + base + (uint32_t)k) * kUnit + lane] = make_float4(Sr * inv, Sg * inv, Sb * inv, To[k]);
                     Sr += cr[k], Sg += cg[k], Sb += cb[k];
                 }
@@ -1190,6 +1191,10 @@ struct ChainArgs {
     uint32_t chain_spins;
 };
 
+// FWD_ONLY (FR_FLAG_FORWARD_ONLY): a frame no backward will follow.  The footprint masks are still built and transposed
+// (the walks run on them) but neither `masks` nor `walks` is stored, no unit takes a slot in the backward's work list, and
+// the gather stores no entry state; the products, rows, unit_done flags and the image are exactly the full forward's.
+template <bool FWD_ONLY>
 __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
 {
     DeviceCounts* __restrict__ counts = a.counts;
@@ -1235,13 +1240,13 @@ __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
         fm = footprint_mask(rr.q0.x, rr.q0.y, rr.q0.z, rr.q0.w, rr.q1.x, rr.q1.y,
                             (float)((int)ui.tx * kTile), (float)((int)ui.ty * kTile));
         rr.q2.z = __uint_as_float(fm.x), rr.q2.w = __uint_as_float(fm.y);
-        masks[(size_t)ui.start + ui.base + (uint32_t)lane] = fm;
+        if (!FWD_ONLY) masks[(size_t)ui.start + ui.base + (uint32_t)lane] = fm;
     }
     rec[lane * kRecQuads + 0] = rr.q0;
     rec[lane * kRecQuads + 1] = rr.q1;
     rec[lane * kRecQuads + 2] = rr.q2;
     const uint2 bt = transpose_bits64(fm, lane, tc);
-    a.walks[(size_t)u * kUnit + lane] = bt;   // (BinningView::walks: the backward does not repeat the transpose)
+    if (!FWD_ONLY) a.walks[(size_t)u * kUnit + lane] = bt;   // (BinningView::walks: the backward does not repeat the transpose)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const u64 Bp = ui.inside ? (((u64)bt.y << 32) | bt.x) : 0ull;
@@ -1257,7 +1262,7 @@ __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
     if (ui.base + kUnit < ui.n)   // (nobody reads the last unit's product)
         __hip_atomic_store(g_tseg + (size_t)u * kUnit + lane, fmaxf(o.T, 1e-30f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // the unit's place in the backward's work list (BwdUnit): long walks from the front of its stripe, the others from the back
-    if (lane == 0) {
+    if (!FWD_ONLY && lane == 0) {
         const bool heavy = npairs >= a.heavy_pairs;
         // Which stripe?  Stripe j holds slots j, j + 64, ...: n_j = ceil((nu - j) / 64) of them, and the hardware runs
         // the waves of slot w on XCD (w / 4) % 8, i.e. XCD x owns the eight stripes 4x .. 4x+3 and 32+4x .. 32+4x+3.
@@ -1378,18 +1383,22 @@ __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
     }
     asm volatile("" ::: "memory");
     FW_STAMP(6);   // (a tile's last unit) the other units' rows are there
-    gather_tile<true>(v, ui.ty * (uint32_t)v.tiles_x + ui.tx, u0, ui.seg + 1u, g_out, unit_state, W, H, bg[0], bg[1], bg[2], out_color, lane);
+    gather_tile<true, FWD_ONLY>(v, ui.ty * (uint32_t)v.tiles_x + ui.tx, u0, ui.seg + 1u, g_out, unit_state, W, H, bg[0], bg[1], bg[2], out_color, lane);
     FW_STAMP(7);   // gathered
     FW_STAMPV(12, __builtin_amdgcn_s_memrealtime());
 }
 
-__global__ void __launch_bounds__(256) k_unit_blend_chained(ChainArgs a) { unit_blend_chained_body(a); }
-__global__ void __launch_bounds__(256) k_unit_blend_chained_batch(BatchOf<ChainArgs> b) { unit_blend_chained_body(b.v[blockIdx.y]); }
+__global__ void __launch_bounds__(256) k_unit_blend_chained(ChainArgs a) { unit_blend_chained_body<false>(a); }
+__global__ void __launch_bounds__(256) k_unit_blend_chained_batch(BatchOf<ChainArgs> b) { unit_blend_chained_body<false>(b.v[blockIdx.y]); }
+// forward-only frames (FR_FLAG_FORWARD_ONLY): no backward hand-off
+__global__ void __launch_bounds__(256) k_unit_blend_chained_fwd_only(ChainArgs a) { unit_blend_chained_body<true>(a); }
+__global__ void __launch_bounds__(256) k_unit_blend_chained_fwd_only_batch(BatchOf<ChainArgs> b) { unit_blend_chained_body<true>(b.v[blockIdx.y]); }
 
 // the gather as its own launch (FR_BLEND_FWD=gather): one wave per tile
-__global__ void __launch_bounds__(256) k_tile_gather(const DeviceCounts* __restrict__ counts, const ImageView v,
-                                                    const float* __restrict__ g_out, float4* __restrict__ unit_state, int W,
-                                                    int H, const float* __restrict__ bg, float* __restrict__ out_color)
+template <bool FWD_ONLY>
+__device__ __forceinline__ void tile_gather_body(const DeviceCounts* __restrict__ counts, const ImageView& v,
+                                                 const float* __restrict__ g_out, float4* __restrict__ unit_state, int W, int H,
+                                                 const float* __restrict__ bg, float* __restrict__ out_color)
 {
     const uint32_t n_tiles = (uint32_t)v.tiles_x * v.tiles_y;
     const int lane = threadIdx.x & 63;
@@ -1401,7 +1410,19 @@ __global__ void __launch_bounds__(256) k_tile_gather(const DeviceCounts* __restr
     const uint32_t n = v.tile_total[tile];
     const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
     if (overflow) return;
-    gather_tile<false>(v, tile, u0, (n + kUnit - 1) / kUnit, g_out, unit_state, W, H, bg0, bg1, bg2, out_color, lane);
+    gather_tile<false, FWD_ONLY>(v, tile, u0, (n + kUnit - 1) / kUnit, g_out, unit_state, W, H, bg0, bg1, bg2, out_color, lane);
+}
+__global__ void __launch_bounds__(256) k_tile_gather(const DeviceCounts* __restrict__ counts, const ImageView v,
+                                                    const float* __restrict__ g_out, float4* __restrict__ unit_state, int W,
+                                                    int H, const float* __restrict__ bg, float* __restrict__ out_color)
+{
+    tile_gather_body<false>(counts, v, g_out, unit_state, W, H, bg, out_color);
+}
+__global__ void __launch_bounds__(256) k_tile_gather_fwd_only(const DeviceCounts* __restrict__ counts, const ImageView v,
+                                                             const float* __restrict__ g_out, float4* __restrict__ unit_state,
+                                                             int W, int H, const float* __restrict__ bg, float* __restrict__ out_color)
+{
+    tile_gather_body<true>(counts, v, g_out, unit_state, W, H, bg, out_color);
 }
 
 
@@ -1696,6 +1717,7 @@ static int debug_sync(bool debug, hipStream_t s, const char* stage)
 int launch_sort_and_blend(int n, const FrameView* f, hipStream_t s, bool debug)
 {
     fr_handle_impl* h0 = f[0].h;
+    const bool fwd_only = (f[0].prm->flags & FR_FLAG_FORWARD_ONLY) != 0;   // (the same for every view of a batch)
     int rc;
     SortArgs sa[kMaxBatch];
     BigSortArgs ba[kMaxBatch];
@@ -1759,9 +1781,10 @@ int launch_sort_and_blend(int n, const FrameView* f, hipStream_t s, bool debug)
     {
         StageScope sc(h0, ST_BLEND_FWD, s);
         // (one workgroup per four units, no grid-stride loop: see k_unit_blend_chained on forward progress)
-        launch_views(k_unit_blend_chained, k_unit_blend_chained_batch, n, ca, unit_wgs, 64 * kWavesPerWG, 0, s);
+        if (fwd_only) launch_views(k_unit_blend_chained_fwd_only, k_unit_blend_chained_fwd_only_batch, n, ca, unit_wgs, 64 * kWavesPerWG, 0, s);
+        else launch_views(k_unit_blend_chained, k_unit_blend_chained_batch, n, ca, unit_wgs, 64 * kWavesPerWG, 0, s);
         if (!h0->gather_in_chain)   // (n == 1, see above)
-            hipLaunchKernelGGL(k_tile_gather, dim3(gather_blocks), dim3(64 * kWavesPerWG), 0, s, f[0].v.counts, f[0].v,
+            hipLaunchKernelGGL(fwd_only ? k_tile_gather_fwd_only : k_tile_gather, dim3(gather_blocks), dim3(64 * kWavesPerWG), 0, s, f[0].v.counts, f[0].v,
                                f[0].b.unit_out, f[0].b.unit_state, f[0].prm->W, f[0].prm->H, f[0].in->background, f[0].out_color);
     }
     FR_HIP(hipGetLastError());

@@ -311,6 +311,10 @@ struct fr_handle_impl {
     uint32_t chain_spins = 1u << 16;   // polls before a blend unit stops waiting for another one and computes its product / row itself (FR_CHAIN_SPINS)
     bool gather_in_chain = true;    // FR_BLEND_FWD=gather: a separate k_tile_gather launch instead of the tile's last unit gathering
     bool profiling = false;      // fr_profile_enable: bracket every stage launch with HIP events
+    // flags and scratch of the most recent forward: a backward handed the buffers of a forward-only frame is refused
+    int32_t last_fwd_flags = 0;
+    const void* last_fwd_geometry = nullptr;
+    const void* last_fwd_binning = nullptr;
     StageEvents ev[ST_COUNT];
 };
 

@@ -213,6 +213,10 @@ __host__ __device__ constexpr int pre_wave_lds_bytes(int M3)
     return 256 * M3 + kCountLdsBytes;
 }
 
+// FWD_ONLY (FR_FLAG_FORWARD_ONLY): a frame no backward will follow.  The backward's hand-off — dcolor_ddir (and the
+// direction derivative behind it), opacity_act, clamped — is neither evaluated nor stored; every other output (records,
+// keys, radii, visible, the bound means3D / rotations / scales) is written exactly as by the full forward.
+template <bool FWD_ONLY>
 __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
 {
     extern __shared__ __attribute__((aligned(16))) float s_sh[];
@@ -610,7 +614,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
                         if (v < 0) clamp_bits |= (uint8_t)(1u << c);
                         col[c] = fmaxf(v, 0.0f);
                         raw_sum += v;
-                        sh_dchannel_ddir(sh, c, a.D, dx, dy, dz, dd[c], dd[3 + c], dd[6 + c]);
+                        if (!FWD_ONLY) sh_dchannel_ddir(sh, c, a.D, dx, dy, dz, dd[c], dd[3 + c], dd[6 + c]);
                     }
                 };
                 const float* lrow = wave_lds + lane * M3;
@@ -632,14 +636,16 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
             dead_colour = !(fabsf(raw_sum) < 3.0e38f);
             if (!dead_colour) {
                 radius_out = mr_out;
-                if (from_sh) {
-                    float* o = a.g.dcolor_ddir + (size_t)idx * 9;
-                    if (!FR_PRE_ABLATE(6))
-                        for (int k = 0; k < 9; k++) o[k] = dd[k];
-                    else asm volatile("" ::"v"(dd[0]), "v"(dd[1]), "v"(dd[2]), "v"(dd[3]), "v"(dd[4]), "v"(dd[5]), "v"(dd[6]), "v"(dd[7]), "v"(dd[8]));
+                if (!FWD_ONLY) {
+                    if (from_sh) {
+                        float* o = a.g.dcolor_ddir + (size_t)idx * 9;
+                        if (!FR_PRE_ABLATE(6))
+                            for (int k = 0; k < 9; k++) o[k] = dd[k];
+                        else asm volatile("" ::"v"(dd[0]), "v"(dd[1]), "v"(dd[2]), "v"(dd[3]), "v"(dd[4]), "v"(dd[5]), "v"(dd[6]), "v"(dd[7]), "v"(dd[8]));
+                    }
+                    a.g.opacity_act[idx] = rec_op;
+                    a.g.clamped[idx] = clamp_bits;
                 }
-                a.g.opacity_act[idx] = rec_op;
-                a.g.clamped[idx] = clamp_bits;
             }
             {
                 // the blend record (GeomView::rec_tmpl): the conic as (-0.5 a, -b, -0.5 c) — exact scalings — so that the blend
@@ -686,9 +692,12 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
     }
 }
 
-__global__ void __launch_bounds__(kPreWG) k_preprocess_fwd(PreArgs a) { preprocess_fwd_body(a); }
+__global__ void __launch_bounds__(kPreWG) k_preprocess_fwd(PreArgs a) { preprocess_fwd_body<false>(a); }
 // batched frames: view blockIdx.y
-__global__ void __launch_bounds__(kPreWG) k_preprocess_fwd_batch(BatchOf<PreArgs> b) { preprocess_fwd_body(b.v[blockIdx.y]); }
+__global__ void __launch_bounds__(kPreWG) k_preprocess_fwd_batch(BatchOf<PreArgs> b) { preprocess_fwd_body<false>(b.v[blockIdx.y]); }
+// forward-only frames (FR_FLAG_FORWARD_ONLY): no backward hand-off
+__global__ void __launch_bounds__(kPreWG) k_preprocess_fwd_only(PreArgs a) { preprocess_fwd_body<true>(a); }
+__global__ void __launch_bounds__(kPreWG) k_preprocess_fwd_only_batch(BatchOf<PreArgs> b) { preprocess_fwd_body<true>(b.v[blockIdx.y]); }
 
 // Everything between the counting pass and the sort, in ONE wide launch (it used to be a totals kernel plus a
 // single-workgroup scan): per tile, add up the eight per-XCD counter copies, write the sub-list table and leave the
@@ -971,6 +980,8 @@ int launch_forward(int n, const ForwardCall* calls, hipStream_t s)
     size_t pre_lds = 0;
     uint32_t pre_blocks = 0, tot_blocks = 0;
     bool debug = false, no_wait = true;
+    // (fr_forward_batch has checked that the views agree on it)
+    const bool fwd_only = (calls[0].prm->flags & FR_FLAG_FORWARD_ONLY) != 0;
     for (int k = 0; k < n; k++) {
         size_t lds;
         if ((rc = prepare_forward(calls[k], s, capturing, f[k], pre[k], tot[k], lds))) return rc;
@@ -984,7 +995,8 @@ int launch_forward(int n, const ForwardCall* calls, hipStream_t s)
     if (pre_blocks > 0) {
         {
             StageScope sc(h0, ST_PREPROCESS_FWD, s);
-            launch_views(k_preprocess_fwd, k_preprocess_fwd_batch, n, pre, pre_blocks, kPreWG, pre_lds, s);
+            if (fwd_only) launch_views(k_preprocess_fwd_only, k_preprocess_fwd_only_batch, n, pre, pre_blocks, kPreWG, pre_lds, s);
+            else launch_views(k_preprocess_fwd, k_preprocess_fwd_batch, n, pre, pre_blocks, kPreWG, pre_lds, s);
         }
         FR_HIP(hipGetLastError());
         if ((rc = debug_sync(debug, s, "preprocess_fwd"))) return rc;

@@ -25,6 +25,7 @@ NUM_CHANNELS = 3  # cuda_rasterizer/config.h:15
 # per-device guess of the binning capacity (instances); grows when a frame overflows it
 _capacity_hint: dict = {}
 last_counts: dict = {}  # device index -> fr_counts of the most recent forward (diagnostics)
+last_forward_only: dict = {}  # device index -> whether the most recent forward was forward-only (diagnostics)
 
 
 def _dev_index(t: torch.Tensor) -> int:
@@ -75,6 +76,37 @@ class no_wait:
         global _no_wait
         _no_wait = self._prev
         return False
+
+
+# Forward-only frames (FR_FLAG_FORWARD_ONLY): the autograd-level entry points render a frame that autograd will not record
+# — grad mode off (torch.no_grad(), inference mode) or no tensor input requiring grad — without the backward's hand-off.
+_forward_only_auto = True
+
+
+class set_forward_only:
+    """`rasterizer.set_forward_only(False)` turns the automatic choice of forward-only frames off (True: on, the default),
+    process-wide; `with rasterizer.set_forward_only(auto):` sets it for the block only and restores the previous setting
+    on exit.  For A/B measurements: images and radii are the same either way."""
+
+    def __init__(self, auto: bool):
+        global _forward_only_auto
+        self._prev, _forward_only_auto = _forward_only_auto, bool(auto)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _forward_only_auto
+        _forward_only_auto = self._prev
+        return False
+
+
+def _pick_forward_only(tensors) -> bool:
+    """Whether a frame of these tensor inputs can skip the backward's hand-off: autograd will not record it.  Decided
+    BEFORE `Function.apply` (grad mode is always off inside `Function.forward`)."""
+    if not _forward_only_auto:
+        return False
+    return not torch.is_grad_enabled() or not any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
 _slot = 0   # which fr_handle of the device the calls of this thread of control use (see handle_slot)
@@ -174,10 +206,10 @@ def _grad_shapes(P, M):
 _GRAD_NAMES = tuple(_grad_shapes(0, 0))
 
 
-def _forward_view(args, raw=False, visible=None, binding=None) -> dict:
+def _forward_view(args, raw=False, visible=None, binding=None, forward_only=False) -> dict:
     """One view of a forward, from the positional arguments of `rasterize_gaussians`: its inputs as the kernels read them
     (kept alive in the view), its fr_params / fr_inputs, outputs and binning capacity.  The launcher allocates the binning
-    buffer."""
+    buffer.  `forward_only`: FR_FLAG_FORWARD_ONLY (no backward may be run on the frame's buffers)."""
     (background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
      tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug) = args
     if means3D.dim() != 2 or means3D.size(1) != 3:
@@ -189,7 +221,7 @@ def _forward_view(args, raw=False, visible=None, binding=None) -> dict:
     L, opts = _lib.lib(), dict(device=means3D.device)
     return dict(dev=dev, W=W, H=H, opts=opts, keep=keep, inp=_inputs(*keep),
                 prm=_params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, prefiltered, debug, raw,
-                            _aux(visible=visible, binding=binding)),
+                            _aux(visible=visible, binding=binding), _lib.FR_FLAG_FORWARD_ONLY if forward_only else 0),
                 out_color=torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, **opts),
                 radii=torch.empty((P,), dtype=torch.int32, **opts),
                 geom=torch.empty((L.fr_geometry_bytes(P),), dtype=torch.uint8, **opts),
@@ -272,6 +304,7 @@ def _launch_forward(views, slots, batch):
                     v["cap"] = int(c.num_instances * 1.25) + 1024
     _check(rc, "fr_forward_batch" if batch else "fr_forward")
     out = []
+    last_forward_only[dev] = bool(views[0]["prm"].flags & _lib.FR_FLAG_FORWARD_ONLY)
     for v, c in zip(views, counts):
         if not _no_wait:  # (with it, the counts arrive later: read_counts / check_async_overflow)
             _capacity_hint[dev] = max(_capacity_hint.get(dev, 0), int(c.num_instances * 1.25) + 1024)
@@ -302,15 +335,17 @@ def _launch_backward(views, slots, batch):
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                        prefiltered, debug, _raw=False, _visible=None):
+                        prefiltered, debug, _raw=False, _visible=None, _forward_only=False):
     """`_C.rasterize_gaussians` (rasterize_points.cu:35-115).  `_raw=True` (extension, FR_FLAG_RAW_ACTIVATIONS):
     opacity / scales / rotations are the RAW parameters and the kernels apply sigmoid / exp / normalize.
+    `_forward_only=True` (extension, FR_FLAG_FORWARD_ONLY): the frame is rendered without the backward's hand-off — same
+    image and radii — and its buffers cannot be handed to `rasterize_gaussians_backward`.  Never chosen here on its own.
 
     Returns (num_rendered, out_color[3,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer); the three
     byte buffers are opaque and must be handed back to `rasterize_gaussians_backward`."""
     v = _forward_view((background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                        projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug),
-                      _raw, _visible)
+                      _raw, _visible, forward_only=_forward_only)
     if v["prm"].P == 0:  # rasterize_points.cu:81 skips the rasterizer entirely
         empty = torch.empty((0,), dtype=torch.uint8, device=means3D.device)
         return 0, v["out_color"].zero_(), v["radii"], empty, empty.clone(), empty.clone()
@@ -339,13 +374,14 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
 
 
 # ------------------------------------------------------------------ batched frames (fr_forward_batch / fr_backward_batch)
-def rasterize_gaussians_batch(views, slots=None, raw=False, visibles=None, bindings=None):
+def rasterize_gaussians_batch(views, slots=None, raw=False, visibles=None, bindings=None, forward_only=False):
     """K views through ONE launch chain (include/fr_rasterizer.h, fr_forward_batch): `views` is a list of the positional
     argument tuples of `rasterize_gaussians` (background ... debug), one per view; view k uses the device's handle
     `slots[k]` (default k).  Returns the list of `rasterize_gaussians` result tuples.  The results are those of K separate
     calls; what changes is that every kernel of the frame is launched once for all views.
     `bindings` (extension, fr_aux::binding): per view an `_lib.fr_binding` or None — the view's means3D / scales / rotations
-    tensors are then OUTPUTS (written by the preprocess kernel from the mesh binding)."""
+    tensors are then OUTPUTS (written by the preprocess kernel from the mesh binding).  `forward_only` (extension,
+    FR_FLAG_FORWARD_ONLY): every view is rendered without the backward's hand-off; never chosen here on its own."""
     K = len(views)
     if not 1 <= K <= _lib.FR_MAX_BATCH:
         raise RuntimeError(f"rasterize_gaussians_batch: 1 .. {_lib.FR_MAX_BATCH} views")
@@ -358,7 +394,7 @@ def rasterize_gaussians_batch(views, slots=None, raw=False, visibles=None, bindi
     for k, a in enumerate(views):
         if bindings[k] is not None and not all(t.is_contiguous() and t.dtype == torch.float32 for t in (a[1], a[4], a[5])):
             raise RuntimeError("rasterize_gaussians_batch: a bound view's means3D / scales / rotations are written in place")
-        v = _forward_view(a, raw, visibles[k], bindings[k])
+        v = _forward_view(a, raw, visibles[k], bindings[k], forward_only)
         if st and v["dev"] != st[0]["dev"]:
             raise RuntimeError("rasterize_gaussians_batch: the views of a batch live on one device")
         if v["prm"].P == 0:
@@ -396,7 +432,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
     colors_precomp, opacities, scales, rotations, cov3Ds_precomp); outputs: per view (color, radii)."""
 
     @staticmethod
-    def forward(ctx, settings, raw_activations, slots, *tensors):
+    def forward(ctx, settings, raw_activations, slots, forward_only, *tensors):
         K = len(settings)
         assert len(tensors) == 8 * K
         ctx.raw, ctx.K, ctx.settings, ctx.slots = bool(raw_activations), K, settings, slots
@@ -404,7 +440,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         per_view = [tensors[8 * k:8 * k + 8] for k in range(K)]
         viss = [torch.empty((t[0].shape[0],), dtype=torch.bool, device=t[0].device) for t in per_view]
         res = rasterize_gaussians_batch([_forward_args(rs, *t) for rs, t in zip(settings, per_view)], slots=slots,
-                                        raw=ctx.raw, visibles=viss)
+                                        raw=ctx.raw, visibles=viss, forward_only=forward_only)
         ctx.stats, ctx.num_rendered, ctx.grads = [], [], []
         saved, outs = [], []
         for (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), vis, r in \
@@ -425,7 +461,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
     def backward(ctx, *grad_outs):
         grad_colors = grad_outs[0::2]
         if all(g is None for g in grad_colors):
-            return (None, None, None) + (None,) * (8 * ctx.K)
+            return (None,) * 4 + (None,) * (8 * ctx.K)
         views, outs = [], []
         for k, (rs, g) in enumerate(zip(ctx.settings, grad_colors)):
             saved = ctx.saved_tensors[10 * k:10 * k + 10]
@@ -437,7 +473,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             outs.append(ctx.grads[k].claim(accumulate=False)[0])
         res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=ctx.raw, wants=[fg.want for fg in ctx.grads],
                                                  outs=outs, stats=ctx.stats)
-        return (None, None, None) + tuple(t for grads in res for t in _input_grads(grads))
+        return (None,) * 4 + tuple(t for grads in res for t in _input_grads(grads))
 
 
 def rasterize_views_autograd(settings, per_view_tensors, raw_activations=False, slots=None):
@@ -446,7 +482,8 @@ def rasterize_views_autograd(settings, per_view_tensors, raw_activations=False, 
     empty tensors for what a view does not use.  Returns [(color, radii), ...]."""
     K = len(settings)
     flat = [t for v in per_view_tensors for t in v]
-    out = _RasterizeGaussiansBatch.apply(list(settings), bool(raw_activations), list(range(K)) if slots is None else list(slots), *flat)
+    out = _RasterizeGaussiansBatch.apply(list(settings), bool(raw_activations), list(range(K)) if slots is None else list(slots),
+                                         _pick_forward_only(flat), *flat)
     return [(out[2 * k], out[2 * k + 1]) for k in range(K)]
 
 
@@ -614,7 +651,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, raw_activations=False):
+                raster_settings, raw_activations=False, forward_only=False):
         rs = raster_settings
         ctx.raw = bool(raw_activations)
         ctx.fr_slot = _slot   # the backward goes through the handle the forward used
@@ -626,7 +663,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         vis = torch.empty((means3D.shape[0],), dtype=torch.bool, device=means3D.device) if means3D.is_cuda else None
         num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _snapshot_on_error(
             rs.debug, "snapshot_fw.dump", "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.",
-            rasterize_gaussians, args, _raw=ctx.raw, _visible=vis)
+            rasterize_gaussians, args, _raw=ctx.raw, _visible=vis, _forward_only=forward_only)
         if vis is not None and means3D.shape[0] > 0:
             radii._fr_visible = vis
         # extension: `means2D._fr_densification_stats = (xyz_gradient_accum, denom)` makes the backward kernel
@@ -644,7 +681,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, grad_out_color, _):
         rs = ctx.raster_settings
         if grad_out_color is None:
-            return (None,) * 10
+            return (None,) * 11
         args = _backward_args(rs, ctx.saved_tensors, grad_out_color, ctx.num_rendered)
         out, added = ({}, ()) if rs.debug else ctx.grads.claim()   # (debug mode claims no GradOut slot)
         with handle_slot(ctx.fr_slot):
@@ -652,13 +689,14 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.debug, "snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n",
                 rasterize_gaussians_backward, args, _out=out, _raw=ctx.raw, _stats=ctx.stats, _want=ctx.grads.want,
                 _accumulate=added)
-        return _input_grads(grads, added) + (None, None)
+        return _input_grads(grads, added) + (None, None, None)
 
 
 def rasterize_gaussians_autograd(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                  raster_settings, raw_activations=False):
+    forward_only = _pick_forward_only((means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp))
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, raw_activations)
+                                     cov3Ds_precomp, raster_settings, raw_activations, forward_only)
 
 
 class GaussianRasterizationSettings(NamedTuple):

@@ -133,6 +133,19 @@ typedef struct fr_params {
  * dL_drotations.  Requires scales + rotations (not cov3D_precomp).  Pass the same flag to fr_backward. */
 #define FR_FLAG_RAW_ACTIVATIONS 2
 
+/* fr_forward / fr_forward_batch: a frame NO BACKWARD will follow (evaluation, fps measurement, reenactment, a GUI — the
+ * reference renders those under torch.no_grad()).  The forward skips the backward's hand-off: it neither evaluates nor
+ * stores the colour's derivative with respect to the view direction, stores no clamp bits and no activated opacities in
+ * `geometry`, and no footprint masks, pixel-major walks, backward work list or per-unit entry state in `binning`
+ * (fr_debug_geometry_field 6, 9, 10 and fr_debug_binning_region 0 .. 3: they keep whatever they held, i.e. are undefined).
+ * The image, radii, fr_aux::visible, the bound means3D / rotations / scales of fr_aux::binding, and the final transmittance
+ * and contributor count in `image` (fr_image_final_T / fr_image_n_contrib) are written as by the full forward of the same
+ * frame, bit for bit.  All views of a batch must agree on the flag (FR_ERR_INVALID_ARGUMENT otherwise).  The handle
+ * remembers the flags and the geometry / binning pointers of its most recent forward: fr_backward / fr_backward_batch
+ * handed the geometry or binning buffer of a forward-only frame return FR_ERR_INVALID_ARGUMENT and enqueue nothing.  A
+ * forward-only frame leaves the handle as any frame does: a full forward + backward may follow it on the same handle. */
+#define FR_FLAG_FORWARD_ONLY 4
+
 /* fr_backward only: FR_FLAG_ACCUMULATE(k) makes the k-th array of fr_grads (k = position of the pointer in the
  * struct: 0 = dL_dmeans2D ... 7 = dL_drotations) ACCUMULATE: the frame's gradient is added to what the array holds
  * instead of overwriting it (culled Gaussians then touch nothing).  A batch of frames rendered from the same
@@ -341,8 +354,17 @@ const uint32_t* fr_image_n_contrib(const void* image, int32_t W, int32_t H);
  * depth and the colour that fields 0, 1 and 3 used to hold are its columns 0-1, 10 and 6-8; 2 was conic_opacity (the
  * conic as (-0.5 a, -b, -0.5 c) and the opacity are columns 2-5; the backward inverts its own 2D covariance), 4 was cov3D, which is no
  * longer stored (both per-Gaussian kernels compute it); 5 was the tile rectangle, 7 the gradient accumulators: they
- * live in the handle now).  NULL for any other field. */
+ * live in the handle now), 9 the colour's derivative with respect to the view direction (9 floats: dR/dx, dG/dx, dB/dx,
+ * then /dy, /dz; written for frames rendered from SH coefficients), 10 the activated opacity (float).  NULL for any other
+ * field. */
 const void* fr_debug_geometry_field(const void* geometry, int32_t P, int32_t field);
+
+/* Test/diagnostic accessor: device pointer and size (*bytes, may be NULL) of one region of the backward's hand-off inside a
+ * binning buffer of `capacity` instances for a W x H image (fr_binning_bytes(capacity, W, H) bytes): 0 the footprint masks
+ * (8 bytes per instance), 1 the pixel-major walks (512 bytes per blend unit), 2 the backward's work list (32 bytes per unit),
+ * 3 the per-unit entry state (1 KB per unit).  A forward-only frame (FR_FLAG_FORWARD_ONLY) writes none of them.  NULL (and
+ * *bytes = 0) for any other region. */
+const void* fr_debug_binning_region(const void* binning, uint64_t capacity, int32_t W, int32_t H, int32_t region, size_t* bytes);
 
 /* Test hook for the wave reduce-scatter used by the blend backward: in[64*36] (lane-major), out[64]:
  * out[l] = sum over lanes of in[lane*36 + bitrev6(l)] for bitrev6(l) < 36. */
