@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py — render+backward frames/s of the MI355X rasterizer on BASELINE.json's metric config.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what `value` needs and no more: it sets up (scenes, graphs, and the calibration that picks how the
+frames are in flight), warms up, times the K steps, writes `--dump-outputs`, checks that no captured frame overflowed its
+binning capacity and prints the JSON line.  `--full` adds, after the timed region, everything else this file measures:
+the fields marked [full] below, the other N = 1 modes (`one_frame_at_a_time`, `batched_views`) and, at N > 1, the
+amortised and avatar modes; without it they are null.
 
 With N > 1 and no torchrun environment the script re-executes itself through
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -17,7 +23,7 @@ raw Gaussian parameters, replayed as one HIP graph.
          chain) — `--chains off` keeps the per-view streams, `--chains 4x3` forces a shape.  Every view has its own
          camera, handle, scratch buffers and gradient buffers either way; `one_frame_at_a_time`, `views_on_streams` and
          `batched_views` in the line are the other modes' rates on the same box.
-  N > 1: TWO modes are timed in the same run, each with its own K steps, and both are in the line (`dp.modes`):
+  N > 1: TWO modes are timed in the same run ([full]: the second), each with its own K steps, and both are in the line (`dp.modes`):
     literal    BASELINE configs[3] as written — every rank renders ONE view of the replicated Gaussians, then ONE RCCL
                all-reduce(AVG) of the flat gradient buffer (in place, on the view's stream), and only then the next step
                starts (a synchronous data-parallel optimisation step: the next frame needs the averaged gradient's
@@ -25,25 +31,25 @@ raw Gaussian parameters, replayed as one HIP graph.
     amortised  `--rounds` x (views in flight) frames per rank and exchange, their mean folded into one of two exchange
                buffers and all-reduced while the next step's frames render (local gradient accumulation; step k+2 waits
                for the collective of step k; the timed region ends when the last one has finished).
-  The un-overlapped all-reduce time is reported for both payloads of SURVEY.md §8e: the generic parameter set (59 floats
+  [full] The un-overlapped all-reduce time is reported for both payloads of SURVEY.md §8e: the generic parameter set (59 floats
   per Gaussian, 23.6 MB at 100 k) and FateAvatar's 'gs' group (12 floats, 4.8 MB; train/optim.py:15-21).
 Workload (config.workload): BASELINE.json configs[1] — 100 000 Gaussians sampled on the head template, 512x512,
 SH degree 3 (M=16), synthetic data, random-init appearance.  Inputs are resident in HBM before the timed region.
 
 The JSON line carries
-  roofline     — the blend backward (the graded kernel): algorithmic bytes 76*R + 20*H*W + 8*T (SURVEY.md §8d;
+  roofline     — [full] the blend backward (the graded kernel): algorithmic bytes 76*R + 20*H*W + 8*T (SURVEY.md §8d;
                  R = num_rendered, T = 16x16 tiles, reference semantics) / that kernel's mean launch duration, measured
                  with HIP events on the launch stream (handed to the dispatch itself, hipExtLaunchKernelGGL: the
                  kernel's execution as a profiler times it) over eager launches of the same frame right after the timed
                  region (events inside a replayed graph cannot be read back), against the 8 TB/s HBM peak.  `traffic`
                  and `valu_frac` are NOT measured by this run: they come from the committed counter profile named in
                  `counters_source` (rocprofv3 --pmc passes, tools/pmc.sh), or are null when no profile matches.
-  stage_frac   — every stage's algorithmic bytes / its measured time / 8 TB/s (formulas: STAGE_BYTES below).
-  cpu_baseline — the CPU oracle (oracle/fr_oracle.c, OpenMP, kind "port": the reference has no CPU rasterizer) on a
+  stage_frac   — [full] every stage's algorithmic bytes / its measured time / 8 TB/s (formulas: STAGE_BYTES below).
+  cpu_baseline — [full] the CPU oracle (oracle/fr_oracle.c, OpenMP, kind "port": the reference has no CPU rasterizer) on a
                  bounded sample of the same frames: best thread count of a quick sweep, and one thread.
-  dp           — N > 1: ranks seen, backend, RCCL version, per-rank num_rendered, both modes' frame rates, and the
-                 un-overlapped all-reduce duration per payload.
-  dp_reference_at_1 — N = 1: the two N > 1 steps measured on a one-rank RCCL group (this script again, as a child
+  dp           — N > 1: ranks seen, backend, RCCL version, per-rank num_rendered, both modes' frame rates, and ([full])
+                 the un-overlapped all-reduce duration per payload.
+  dp_reference_at_1 — [full] N = 1: the two N > 1 steps measured on a one-rank RCCL group (this script again, as a child
                  process with --exchange-at-1, after the timed region): `value` at N = 1 is frames in flight with no
                  exchange at all, `value` at N > 1 the literal configs[3] step — a scaling curve over `value` compares the
                  two; the like-for-like first point of the N > 1 series is `dp_reference_at_1.literal.value`.
@@ -512,8 +518,9 @@ class HipEngine:
         except Exception as e:   # (the headline modes must not be lost to this one)
             return {"status": "failed: " + repr(e)[:300]}
 
-    def finish(self):
-        """After the timed region: overflow check of the captured frames, per-kernel durations, counts."""
+    def finish(self, profile=True):
+        """After the timed region: overflow check of the captured frames, counts, and (`profile`: --full) per-kernel
+        durations."""
         from fateavatar_amd import _lib
         if self.chains is not None and self.chains_overflowed(self.chains[2]):
             raise SystemExit("binning capacity overflowed inside a captured launch chain; rerun (capacity hint was raised)")
@@ -523,6 +530,11 @@ class HipEngine:
                     c = self.rasterizer.last_counts[self.local]
                     raise SystemExit(f"binning capacity overflowed inside the captured graph (instances {c.num_instances}, "
                                      f"num_rendered {c.num_rendered}, max list {c.max_tile_list}); rerun (capacity hint was raised)")
+        if not profile:
+            # view 0's counts as its last frame of the timed steps left them (handle slot 0, the one `frame()` uses below)
+            torch.cuda.synchronize()
+            c = self.rasterizer.read_counts(self.local, slot=self.all_views[0].k)
+            return {}, dict(num_rendered=int(c.num_rendered), num_instances=int(c.num_instances), max_tile_list=int(c.max_tile_list))
         # HIP events around every stage launch, on the launch stream, over eager frames of ONE view (event records inside
         # a replayed graph cannot be read back)
         # (in no-wait mode, like the captured frames: the host does not block on each frame's counts, so the launches
@@ -600,7 +612,7 @@ class StubEngine:
     def sync(self):
         pass
 
-    def finish(self):
+    def finish(self, profile=True):
         return {}, dict(num_rendered=1000 + self.rank, num_instances=0, max_tile_list=0)
 
 
@@ -702,14 +714,15 @@ def _free_port() -> int:
 
 
 def _child_line(extra, timeout=240):
-    """This script again as a child process of ONE rank (its own HIP context), after the timed region: its JSON line."""
+    """This script again as a child process of ONE rank (its own HIP context), after the timed region: its JSON line.
+    The child runs with --full (its readers take per-stage and per-mode fields from it); `extra` says what to leave out."""
     # (not torchrun's environment: the child is a world of its own — with TORCHELASTIC_USE_AGENT_STORE set it would wait for
     # the parent job's rendezvous store)
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "OMP_NUM_THREADS")
            and not k.startswith(("TORCHELASTIC_", "ROLE_", "GROUP_", "TORCH_NCCL_", "NCCL_ASYNC"))}
     env["MASTER_PORT"] = str(_free_port())
-    out = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra, capture_output=True, text=True, timeout=timeout, env=env)
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--full"] + extra, capture_output=True, text=True, timeout=timeout, env=env)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     if out.returncode != 0 or not lines:
         raise RuntimeError(f"child bench exited {out.returncode}: {(out.stderr or out.stdout)[-300:]}")
@@ -836,7 +849,11 @@ def main():
     ap.add_argument("--exchange-at-1", action="store_true",
                     help="diagnostic: run N = 1 with the N > 1 machinery (second gradient-buffer sets, per-round fold, "
                          "all-reduce on a one-rank RCCL group): what the exchange costs the rendering apart from the wire")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, measure everything beside `value` as well: the CPU baseline, the other "
+                         "in-flight modes, per-stage durations and rooflines, the second runs of this script (--no-* below "
+                         "leave single ones out) and, at N > 1, the amortised and avatar modes and the all-reduce table")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: budget of the CPU baseline sample (0 = skip)")
     ap.add_argument("--no-dp-reference", dest="dp_reference", action="store_false", default=True,
                     help="N = 1: do not add `dp_reference_at_1` (the N > 1 step — one view, one all-reduce on a one-rank RCCL "
                          "group — measured by a second run of this script after the timed region)")
@@ -937,16 +954,17 @@ def main():
         modes["literal"] = {"frames_per_step_per_gpu": 1, "rounds_per_step": 1, "frames_in_flight_per_gpu": 1, "overlap": False,
                             "ms_per_step": round(el / args.steps * 1e3, 4), "value": round(world * args.steps / el, 2),
                             "unit": "frames/s", "grad_checksum": float(xl.latest().double().abs().sum().item())}
-        ea, xchg = run_mode(K_best, rounds, args.overlap)
-        modes["amortised"] = {"frames_per_step_per_gpu": K_best * rounds, "rounds_per_step": rounds,
-                              "frames_in_flight_per_gpu": K_best, "overlap": bool(args.overlap),
-                              "ms_per_step": round(ea / args.steps * 1e3, 4),
-                              "value": round(world * K_best * rounds * args.steps / ea, 2), "unit": "frames/s"}
-        elapsed, frames_per_step = el, 1
-        # ... and the reference's OWN step (train/optim.py:15-21, train/iteration.py:50-60): FateAvatar's mesh-bound
-        # parameters at SH degree 0 — the 'gs' group, 12 floats per Gaussian (4.8 MB at 100 k) — one frame per rank:
-        # bind, render, L1, backward, all-reduce(AVG), Adam as ONE captured graph, the collective a node of it
-        modes["avatar"] = eng.run_avatar_mode(args, world)
+        elapsed, frames_per_step, xchg = el, 1, xl
+        if args.full:
+            ea, xchg = run_mode(K_best, rounds, args.overlap)
+            modes["amortised"] = {"frames_per_step_per_gpu": K_best * rounds, "rounds_per_step": rounds,
+                                  "frames_in_flight_per_gpu": K_best, "overlap": bool(args.overlap),
+                                  "ms_per_step": round(ea / args.steps * 1e3, 4),
+                                  "value": round(world * K_best * rounds * args.steps / ea, 2), "unit": "frames/s"}
+            # ... and the reference's OWN step (train/optim.py:15-21, train/iteration.py:50-60): FateAvatar's mesh-bound
+            # parameters at SH degree 0 — the 'gs' group, 12 floats per Gaussian (4.8 MB at 100 k) — one frame per rank:
+            # bind, render, L1, backward, all-reduce(AVG), Adam as ONE captured graph, the collective a node of it
+            modes["avatar"] = eng.run_avatar_mode(args, world)
     else:
         elapsed, xchg = run_mode(K_best, rounds, False)
         frames_per_step = K_best * rounds
@@ -958,7 +976,7 @@ def main():
 
     # the same engine with ONE view in flight (what `value` measured until views overlapped): a reference point
     single = None
-    if not STUB and K_best > 1 and not exchanging:
+    if args.full and not STUB and K_best > 1 and not exchanging:
         eng.sync()
         t1 = time.perf_counter()
         for _ in range(args.steps * rounds):
@@ -968,13 +986,13 @@ def main():
 
     # K views through ONE launch chain (render_batch): the in-flight gain without any stream / hardware-queue arrangement
     batched = None
-    if not STUB and not exchanging and args.graph:
+    if args.full and not STUB and not exchanging and args.graph:
         combos = [(2, 1), (3, 1), (4, 1)]
         if os.environ.get("FR_BENCH_BATCH_X_STREAMS"):   # (experiment: batched chains in flight together)
             combos += [(4, 2), (3, 3), (4, 3), (4, 4), (2, 3)]
         batched = [b for b in (eng.measure_batched(K, max(20, args.steps * rounds // 2), S) for K, S in combos) if b is not None]
 
-    prof, counts = eng.finish()
+    prof, counts = eng.finish(profile=args.full)
 
     # ---- data-parallel record: who took part, what was exchanged, how long one exchange takes on its own
     dpinfo = None
@@ -1000,9 +1018,11 @@ def main():
 
         # the payload the steps exchanged (the generic set: 59 floats per Gaussian at SH degree 3), and FateAvatar's own
         # optimizer group (opacity 1 + offset 1 + colour 3 + rotation 4 + scaling 3 = 12 floats, train/optim.py:15-21)
-        table = [dict(time_allreduce(reduced.numel()), what="flat gradient of the timed steps (generic parameter set)")]
-        if not STUB:
-            table.append(dict(time_allreduce(12 * args.P), what="FateAvatar 'gs' optimizer group, 12 floats per Gaussian"))
+        table = None
+        if args.full:
+            table = [dict(time_allreduce(reduced.numel()), what="flat gradient of the timed steps (generic parameter set)")]
+            if not STUB:
+                table.append(dict(time_allreduce(12 * args.P), what="FateAvatar 'gs' optimizer group, 12 floats per Gaussian"))
         mine = torch.tensor([counts["num_rendered"]], dtype=torch.int64, device=eng.dev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
@@ -1014,8 +1034,9 @@ def main():
                 rccl = None
         dpinfo = {"ranks_seen": dist.get_world_size(), "backend": dist.get_backend(), "rccl_version": rccl,
                   "num_rendered_per_rank": [int(t.item()) for t in allr],
-                  "allreduce_payload_bytes": table[0]["payload_bytes"], "allreduce_us": table[0]["us"],
-                  "allreduce_busbw_GBps": table[0]["busbw_GBps"], "allreduce_table": table,
+                  "allreduce_payload_bytes": reduced.numel() * reduced.element_size(),
+                  "allreduce_us": table[0]["us"] if table else None,
+                  "allreduce_busbw_GBps": table[0]["busbw_GBps"] if table else None, "allreduce_table": table,
                   "group_of_one": bool(args.exchange_at_1),
                   "overlap": bool(args.overlap),
                   "modes": modes,
@@ -1024,12 +1045,14 @@ def main():
         # The generic literal step is wire-bound by construction: every gradient array leaves one kernel at the end of the
         # step and the next forward needs the update, so nothing can overlap the exchange.  Its ceiling, from this run's own
         # numbers: frame / (frame + un-overlapped all-reduce of the same payload).
-        frame_us = modes["literal"]["ms_per_step"] * 1e3 - table[0]["us"]
-        dpinfo["literal_ceiling"] = {"frame_us": round(max(frame_us, 0.0), 1), "allreduce_us": table[0]["us"],
-                                     "efficiency_ceiling": round(max(frame_us, 0.0) / max(modes["literal"]["ms_per_step"] * 1e3, 1e-9), 4),
-                                     "what": "frame_us / (frame_us + allreduce_us): the scaling efficiency the literal mode can reach "
-                                             "against the same step without a wire (frame_us = its step time minus the un-overlapped "
-                                             "all-reduce of its payload, allreduce_table[0])"}
+        dpinfo["literal_ceiling"] = None
+        if table:
+            frame_us = modes["literal"]["ms_per_step"] * 1e3 - table[0]["us"]
+            dpinfo["literal_ceiling"] = {"frame_us": round(max(frame_us, 0.0), 1), "allreduce_us": table[0]["us"],
+                                         "efficiency_ceiling": round(max(frame_us, 0.0) / max(modes["literal"]["ms_per_step"] * 1e3, 1e-9), 4),
+                                         "what": "frame_us / (frame_us + allreduce_us): the scaling efficiency the literal mode can reach "
+                                                 "against the same step without a wire (frame_us = its step time minus the un-overlapped "
+                                                 "all-reduce of its payload, allreduce_table[0])"}
 
     if rank == 0:
         fps = world * frames_per_step * args.steps / elapsed
@@ -1077,24 +1100,24 @@ def main():
                         "measured": "dispatch-tied HIP events around ISOLATED launches (eager no-wait frames of one view, queued "
                                     "behind each other, nothing else on the GPU); rocprofv3 of `bench.py --in-flight 1` agrees (profiles/)"}
         cpu = None
-        if args.cpu_seconds > 0 and world == 1 and eng.scene is not None:
+        if args.full and args.cpu_seconds > 0 and world == 1 and eng.scene is not None:
             cpu = cpu_baseline(eng.scene, args.cpu_seconds)
         # What `value` is on N > 1 GPUs (the literal configs[3] step) measured at ONE rank, so that a scaling curve has a
         # like-for-like first point: `value` at N = 1 is frames in flight without any exchange, a different mode.
         dp_ref = opaque = None
-        if not exchanging or world > 1:
+        if args.full and (not exchanging or world > 1):
             if args.dp_reference and args.graph and (not STUB or world > 1):
                 dp_ref = _dp_reference_at_1(args)
-        if not STUB and world == 1 and not exchanging and args.opaque and args.graph and args.opacity == 0.1:
+        if args.full and not STUB and world == 1 and not exchanging and args.opaque and args.graph and args.opacity == 0.1:
             opaque = _opaque_scene(args)
         rt_defaults = None
-        if not STUB and world == 1 and not exchanging and args.runtime_defaults and args.graph and stock_run(args):
+        if args.full and not STUB and world == 1 and not exchanging and args.runtime_defaults and args.graph and stock_run(args):
             rt_defaults = _runtime_defaults(args)
         config5 = None
-        if not STUB and world == 1 and not exchanging and args.config5 and args.graph and stock_run(args) and (args.P, args.res) == (100_000, 512):
+        if args.full and not STUB and world == 1 and not exchanging and args.config5 and args.graph and stock_run(args) and (args.P, args.res) == (100_000, 512):
             config5 = _config5_scene(args)
         coherent = None
-        if (not STUB and world == 1 and not exchanging and args.coherent and args.graph and args.scale is None
+        if (args.full and not STUB and world == 1 and not exchanging and args.coherent and args.graph and args.scale is None
                 and os.environ.get("FR_BENCH_ORDER") is None):
             coherent = _coherent_layout(args)
         # the like-for-like first point of a scaling curve over the N > 1 `value` (the literal step), and this run against it

@@ -29,7 +29,7 @@ def test_bench_spawns_two_ranks_and_reports_both_modes(overlap, K, R):
     finished before the next step), and the amortised mode (R rounds of K views per exchange, overlapped) sits beside it in
     dp.modes; every step of both modes averages its gradient over the ranks."""
     steps, warm = 7, 3
-    j = _run(["--gpus", "2", "--steps", str(steps), "--warmup", str(warm), "--in-flight", str(K), "--rounds", str(R)]
+    j = _run(["--gpus", "2", "--steps", str(steps), "--warmup", str(warm), "--in-flight", str(K), "--rounds", str(R), "--full"]
              + ([] if overlap else ["--no-overlap"]))
     assert j["n_gpus"] == 2 and j["data"] == "stub" and j["steps"] == steps and j["scaling"] == "weak"
     d = j["dp"]
@@ -69,6 +69,24 @@ def test_bench_spawns_two_ranks_and_reports_both_modes(overlap, K, R):
     c = d["literal_ceiling"]
     assert c["allreduce_us"] == d["allreduce_table"][0]["us"] and 0.0 <= c["efficiency_ceiling"] <= 1.0
     assert abs(c["efficiency_ceiling"] - c["frame_us"] / (lit["ms_per_step"] * 1e3)) <= 2e-3
+
+
+def test_bench_plain_two_rank_run_times_the_literal_step_only():
+    """Without --full, N > 1 times `value`'s mode alone: the literal step, averaged over the ranks as in a full run; the
+    amortised and avatar modes, the all-reduce table and the one-rank reference are left out (null)."""
+    steps, warm = 5, 2
+    j = _run(["--gpus", "2", "--steps", str(steps), "--warmup", str(warm), "--in-flight", "2", "--rounds", "2"])
+    assert j["n_gpus"] == 2 and j["data"] == "stub" and j["steps"] == steps
+    d = j["dp"]
+    assert d["ranks_seen"] == 2 and d["num_rendered_per_rank"] == [1000, 1001] and list(d["modes"]) == ["literal"]
+    lit = d["modes"]["literal"]
+    assert j["value"] == lit["value"] and j["ms_per_step"] == lit["ms_per_step"]
+    assert j["config"]["frames_per_step_per_gpu"] == 1
+    want = sum(i * 1e-3 + 1.5 * (warm + steps) for i in range(4096))
+    assert abs(lit["grad_checksum"] - want) <= 1e-4 * want and abs(d["grad_checksum"] - want) <= 1e-4 * want
+    assert d["allreduce_payload_bytes"] == 4 * 4096
+    assert d["allreduce_table"] is None and d["allreduce_us"] is None and d["literal_ceiling"] is None
+    assert j["dp_reference_at_1"] is None and j["scaling_reference"] is None and j["efficiency"] is None
 
 
 def test_bench_single_rank_stub_line_is_well_formed():

@@ -404,7 +404,7 @@ def test_train_step_captures_the_rccl_exchange_in_its_graph(gpu_device):
 
 
 def test_bench_exchange_machinery_on_one_gpu_accumulates_rounds_in_place(gpu_device):
-    """`bench.py --exchange-at-1`: the N > 1 step (two gradient-buffer sets, rounds that ADD to the set in the backward
+    """`bench.py --exchange-at-1 --full`: the N > 1 step (two gradient-buffer sets, rounds that ADD to the set in the backward
     kernel, one fold and one RCCL all-reduce per step) on a one-rank group.  Every round renders the same views, so
     the step's mean gradient must not depend on the number of rounds, and the JSON line must be the LAST line of the
     run (RCCL prints a banner through C stdio)."""
@@ -416,7 +416,7 @@ def test_bench_exchange_machinery_on_one_gpu_accumulates_rounds_in_place(gpu_dev
     sums = {}
     for rounds in (1, 3):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--exchange-at-1", "--rounds", str(rounds), "--P", "20000",
-                            "--res", "256", "--steps", "6", "--warmup", "4", "--cpu-seconds", "0", "--in-flight", "2"],
+                            "--res", "256", "--steps", "6", "--warmup", "4", "--cpu-seconds", "0", "--in-flight", "2", "--full"],
                            capture_output=True, text=True, timeout=600, cwd=root,
                            env=dict(os.environ, MASTER_PORT=str(29541 + rounds)))
         assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

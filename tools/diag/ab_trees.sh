@@ -5,6 +5,7 @@
 # durations of tools/probe.py at config 2, config 5 and the opaque scene, then bench.py twice, alternating; every run bounded.
 cd "${GRAFT_REPO_ROOT:-.}"
 R=$PWD
+# (--full where the tree's bench.py has the option: before it, every run measured everything it does now with --full)
 for t in "$@"; do
   D=$R/$t; tag=$(echo $t | tr '/.' '__')
   for sc in "c2:" "c5:--P 500000 --res 1024 --iters 20" "opaque:--opacity 0.9 --iters 30"; do
@@ -17,5 +18,5 @@ for t in "$@"; do
 done
 for i in 1 2; do for t in "$@"; do
   echo -n "$t: "
-  (cd $R/$t && timeout -k 10 400 python bench.py --cpu-seconds 0 --steps 100 --no-dp-reference --no-opaque --no-coherent --no-runtime-defaults --no-config5 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['one_frame_at_a_time']['value'], d['stage_us'])")
+  (cd $R/$t && timeout -k 10 400 python bench.py $(grep -qs '"--full"' bench.py && echo --full) --cpu-seconds 0 --steps 100 --no-dp-reference --no-opaque --no-coherent --no-runtime-defaults --no-config5 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['one_frame_at_a_time']['value'], d['stage_us'])")
 done; done

@@ -9,7 +9,7 @@ if [ "$1" = hist ]; then
 fi
 run() {
   for A in "" "--P 500000 --res 1024" "--P 100000 --res 512 --scale 3e-3 --opacity 0.3" "--P 500000 --res 1024 --scale 6.085e-4 --opacity 0.5" "--opacity 0.9"; do
-    python bench.py --cpu-seconds 0 --steps 100 $A 2>/dev/null | python -c 'import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["value"], d["stage_us"])'
+    python bench.py --full --cpu-seconds 0 --steps 100 $A 2>/dev/null | python -c 'import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["value"], d["stage_us"])'
   done
 }
 echo "== default"; run
