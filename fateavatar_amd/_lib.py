@@ -20,6 +20,7 @@ FR_ERR_UNSUPPORTED = 4
 FR_FLAG_NO_WAIT = 1
 FR_FLAG_RAW_ACTIVATIONS = 2
 FR_FLAG_FORWARD_ONLY = 4       # fr_forward: a frame no backward follows (no backward hand-off is written)
+FR_FLAG_DEPTH_ALPHA = 8        # depth and alpha planes next to the image (fr_aux::out_depth / out_alpha, their gradients)
 FR_FLAG_ACCUMULATE_SHIFT = 8   # fr_backward: bit (8 + k) = add into the k-th array of fr_grads
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -35,7 +36,9 @@ class fr_binding(C.Structure):
 class fr_aux(C.Structure):
     _fields_ = [("visible", C.c_void_p), ("grad_accum", C.c_void_p), ("denom", C.c_void_p),
                 ("binding", C.POINTER(fr_binding)), ("d_verts", C.c_void_p), ("d_offset", C.c_void_p),
-                ("d_rotation", C.c_void_p), ("d_scaling", C.c_void_p), ("overflow_out", C.c_void_p)]
+                ("d_rotation", C.c_void_p), ("d_scaling", C.c_void_p), ("overflow_out", C.c_void_p),
+                ("out_depth", C.c_void_p), ("out_alpha", C.c_void_p), ("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p),
+                ("planes", C.c_void_p)]
 
 
 class fr_params(C.Structure):
@@ -75,7 +78,7 @@ class fr_counts(C.Structure):
 
 
 EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile_enable", "fr_profile_read", "fr_geometry_bytes", "fr_image_bytes",
-           "fr_binning_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
+           "fr_binning_bytes", "fr_planes_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
            "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
            "fr_bind_forward", "fr_bind_backward"]
 
@@ -121,6 +124,8 @@ def lib():
     L.fr_image_bytes.restype = C.c_size_t
     L.fr_binning_bytes.argtypes = [C.c_uint64, C.c_int32, C.c_int32]
     L.fr_binning_bytes.restype = C.c_size_t
+    L.fr_planes_bytes.argtypes = [C.c_uint64, C.c_int32, C.c_int32]
+    L.fr_planes_bytes.restype = C.c_size_t
     L.fr_forward.argtypes = [C.c_void_p, C.POINTER(fr_params), C.POINTER(fr_inputs), _fp, _fp, _fp, _fp, _fp,
                              C.c_uint64, C.POINTER(fr_counts), C.c_void_p]
     L.fr_forward.restype = C.c_int

@@ -36,14 +36,16 @@ class MeshBinding(NamedTuple):
 
 class _RasterizeBoundBatch(torch.autograd.Function):
     """Tensor arguments per view: (verts, offset, rotation, scaling, means2D, sh, opacities) — the RAW parameters, as
-    render() hands them over with `fused_activations`.  Outputs per view: (color, radii)."""
+    render() hands them over with `fused_activations`.  Outputs per view: (color, radii), with `depth_alpha` (color, radii,
+    depth [1,H,W], alpha [1,H,W])."""
     PER_VIEW = 7
 
     @staticmethod
-    def forward(ctx, settings, bindings, slots, forward_only, *tensors):
+    def forward(ctx, settings, bindings, slots, forward_only, depth_alpha, *tensors):
         K, n = len(settings), _RasterizeBoundBatch.PER_VIEW
         assert len(tensors) == n * K and len(bindings) == K
         ctx.K, ctx.settings, ctx.bindings, ctx.slots = K, settings, bindings, slots
+        ctx.depth_alpha = bool(depth_alpha)
         ctx.set_materialize_grads(False)
         empty = torch.Tensor([])
         views, viss, descs, bound, checked = [], [], [], [], []
@@ -67,12 +69,13 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             bound.append((xyz, rot, scl))
             views.append(_forward_args(rs, xyz, means2D, sh, empty, opacities, scl, rot, empty))
             viss.append(torch.empty((N,), dtype=torch.bool, device=dev))
-        res = rasterize_gaussians_batch(views, slots=slots, raw=True, visibles=viss, bindings=descs, forward_only=forward_only)
+        res = rasterize_gaussians_batch(views, slots=slots, raw=True, visibles=viss, bindings=descs, forward_only=forward_only,
+                                        depth_alpha=ctx.depth_alpha)
         ctx.stats, ctx.num_rendered, ctx.grads, ctx.offset_shapes = [], [], [], []
         saved, outs = [], []
         for k in range(K):
             verts, offset, rotation, scaling, means2D, sh, opacities = tensors[n * k:n * k + n]
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = res[k]
+            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = res[k][:6]
             radii._fr_visible = viss[k]
             radii._fr_bound = bound[k]           # (xyz, rotation, scaling) as bind_gaussians returns them
             ctx.stats.append(getattr(means2D, "_fr_densification_stats", None))
@@ -82,21 +85,28 @@ class _RasterizeBoundBatch(torch.autograd.Function):
                                           "d_rotation": rotation, "d_scaling": scaling}, sh, bound=True))
             saved += [*checked[k], sh, radii, geomBuffer, binningBuffer, imgBuffer, *bound[k]]
             outs += [color, radii]
+            if ctx.depth_alpha:
+                saved.append(res[k][8])
+                outs += [res[k][6].unsqueeze(0), res[k][7].unsqueeze(0)]
         ctx.save_for_backward(*saved)
-        ctx.mark_non_differentiable(*outs[1::2])
+        n_out = 4 if ctx.depth_alpha else 2
+        ctx.mark_non_differentiable(*outs[1::n_out])
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *grad_outs):
         K, n = ctx.K, _RasterizeBoundBatch.PER_VIEW
-        grad_colors = grad_outs[0::2]
-        if all(g is None for g in grad_colors):
-            return (None,) * 4 + (None,) * (n * K)
+        n_out, n_saved = (4, 13) if ctx.depth_alpha else (2, 12)
+        grad_colors = grad_outs[0::n_out]
+        grad_planes = [grad_outs[n_out * k + 2:n_out * k + 4] for k in range(K)] if ctx.depth_alpha else [(None, None)] * K
+        if all(g is None for g in grad_colors) and all(g is None for gp in grad_planes for g in gp):
+            return (None,) * 5 + (None,) * (n * K)
         empty = torch.Tensor([])
-        views, outs, descs, bgrads = [], [], [], []
+        views, outs, descs, bgrads, planes = [], [], [], [], []
         for k, (rs, mb) in enumerate(zip(ctx.settings, ctx.bindings)):
             verts, offset, rotation, scaling, sh, radii, geomBuffer, binningBuffer, imgBuffer, xyz, rot, scl = \
-                ctx.saved_tensors[12 * k:12 * k + 12]
+                ctx.saved_tensors[n_saved * k:n_saved * k + 12]
+            planes.append((ctx.saved_tensors[n_saved * k + 12], *grad_planes[k]) if ctx.depth_alpha else None)
             dev, N = verts.device, xyz.shape[0]
             g = grad_colors[k]
             if g is None:
@@ -105,7 +115,7 @@ class _RasterizeBoundBatch(torch.autograd.Function):
                                         ctx.num_rendered[k]))
             claimed = ctx.grads[k].claim(accumulate=False)[0]
             outs.append({m: b for m, b in claimed.items() if m.startswith("dL_")})
-            need_v, need_o, need_r, need_s = ctx.needs_input_grad[4 + n * k:4 + n * k + 4]
+            need_v, need_o, need_r, need_s = ctx.needs_input_grad[5 + n * k:5 + n * k + 4]   # (after the 5 non-tensor arguments)
 
             def buf(need, name, shape):
                 if not need:
@@ -120,8 +130,9 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             bgrads.append({"d_verts": torch.zeros_like(verts) if need_v else None, "d_offset": buf(need_o, "d_offset", (N,)),
                            "d_rotation": buf(need_r, "d_rotation", (N, 4)), "d_scaling": buf(need_s, "d_scaling", (N, 3))})
         res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=[fg.want for fg in ctx.grads], outs=outs,
-                                                 stats=ctx.stats, bindings=descs, bind_grads=bgrads)
-        flat = [None, None, None, None]
+                                                 stats=ctx.stats, bindings=descs, bind_grads=bgrads,
+                                                 planes=planes if ctx.depth_alpha else None)
+        flat = [None, None, None, None, None]
         for k in range(K):
             grad_means2D, _, grad_opacities, _, _, grad_sh, _, _ = res[k]
             b = bgrads[k]
@@ -132,7 +143,8 @@ class _RasterizeBoundBatch(torch.autograd.Function):
         return tuple(flat)
 
 
-def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding: MeshBinding, bg_colors, scaling_modifier=1.0, slots=None):
+def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding: MeshBinding, bg_colors, scaling_modifier=1.0, slots=None,
+                       depth_alpha=False):
     """`bind_gaussians` + `render_batch` for K views in one launch chain without binding kernels.
 
     `pcs`: per view (or one for all) a holder with the raw parameters `_opacity` [N,1], `_offset` [N,1], `_rotation` [N,4],
@@ -141,7 +153,7 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding: MeshBinding
     (xyz, rotation, scaling) the reference assigns to the Gaussians before render() (model/fateavatar.py:256-258) as plain
     kernel OUTPUTS, DETACHED from autograd: gradients reach offset / rotation / scaling / verts through the image only.  A
     regulariser on the bound values themselves needs the differentiable stand-alone op (`binding.bind_gaussians`, what
-    `AvatarStep(fold_binding=False)` renders through)."""
+    `AvatarStep(fold_binding=False)` renders through).  `depth_alpha=True` (extension): "depth" and "alpha" as in render()."""
     K = len(viewpoint_cameras)
     if not 1 <= K <= _lib.FR_MAX_BATCH:
         raise RuntimeError(f"render_bound_batch: 1 .. {_lib.FR_MAX_BATCH} views")
@@ -162,10 +174,11 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding: MeshBinding
         tensors += [verts, pc._offset, pc._rotation, pc._scaling, sp, pc.get_features, pc._opacity]
         points.append(sp)
     res = _RasterizeBoundBatch.apply(settings, [mb] * K, list(range(K)) if slots is None else list(slots),
-                                     _pick_forward_only(tensors), *tensors)
+                                     _pick_forward_only(tensors), bool(depth_alpha), *tensors)
+    n_out = 4 if depth_alpha else 2
     out = []
     for k, sp in enumerate(points):
-        o = _result(res[2 * k], res[2 * k + 1], sp)
+        o = _result(res[n_out * k], res[n_out * k + 1], sp, res[n_out * k + 2:n_out * k + 4] if depth_alpha else None)
         o["bound"] = tuple(t.detach() for t in o["radii"]._fr_bound)
         out.append(o)
     return out

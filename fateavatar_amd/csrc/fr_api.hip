@@ -201,6 +201,12 @@ size_t fr_binning_bytes(uint64_t capacity, int32_t W, int32_t H)
     return BinningView::bytes((size_t)capacity, (size_t)v.tiles_x * v.tiles_y);
 }
 
+size_t fr_planes_bytes(uint64_t capacity, int32_t W, int32_t H)
+{
+    ImageView v = ImageView::make(nullptr, W, H);
+    return PlaneView::bytes((size_t)capacity, (size_t)v.tiles_x * v.tiles_y);
+}
+
 int fr_forward(fr_handle* hh, const fr_params* prm, const fr_inputs* in, float* out_color, int32_t* radii,
                void* geometry, void* image, void* binning, uint64_t binning_capacity, fr_counts* counts, void* stream)
 {
@@ -230,6 +236,10 @@ int fr_forward_batch(int32_t n_views, fr_handle* const* handles, const fr_params
         if (binning_capacity[k] >= (1ull << 32)) return fail_msg(FR_ERR_UNSUPPORTED, "binning capacity must be < 2^32 instances");
         if ((prm[k]->flags ^ prm[0]->flags) & FR_FLAG_FORWARD_ONLY)
             return fail_msg(FR_ERR_INVALID_ARGUMENT, "the views of a batch must agree on FR_FLAG_FORWARD_ONLY");
+        if ((prm[k]->flags ^ prm[0]->flags) & FR_FLAG_DEPTH_ALPHA)
+            return fail_msg(FR_ERR_INVALID_ARGUMENT, "the views of a batch must agree on FR_FLAG_DEPTH_ALPHA");
+        if ((prm[k]->flags & FR_FLAG_DEPTH_ALPHA) && (!prm[k]->aux || !prm[k]->aux->out_depth || !prm[k]->aux->out_alpha || !prm[k]->aux->planes))
+            return fail_msg(FR_ERR_INVALID_ARGUMENT, "FR_FLAG_DEPTH_ALPHA needs fr_aux::out_depth, out_alpha and planes");
         c[k] = ForwardCall{h, prm[k], in[k], out_color[k], radii[k], geometry[k], image[k], binning[k], binning_capacity[k],
                            counts ? counts + k : nullptr};
     }
@@ -265,6 +275,15 @@ static int check_backward(const BackwardCall& c, bool batched)
         return fail_msg(FR_ERR_INVALID_ARGUMENT,
                         "these buffers come from a forward-only frame (FR_FLAG_FORWARD_ONLY), which leaves no backward hand-off: "
                         "render the frame without the flag to differentiate it");
+    const fr_aux* aux = c.prm->aux;
+    if (aux && (aux->dL_ddepth || aux->dL_dalpha)) {
+        if (!(c.prm->flags & FR_FLAG_DEPTH_ALPHA))
+            return fail_msg(FR_ERR_INVALID_ARGUMENT, "a depth or alpha gradient needs FR_FLAG_DEPTH_ALPHA");
+        if (!(c.h->last_fwd_flags & FR_FLAG_DEPTH_ALPHA) && (c.geometry == c.h->last_fwd_geometry || c.binning == c.h->last_fwd_binning))
+            return fail_msg(FR_ERR_INVALID_ARGUMENT,
+                            "a depth or alpha gradient for a frame rendered without FR_FLAG_DEPTH_ALPHA: it has no planes to differentiate");
+        if (!aux->planes) return fail_msg(FR_ERR_INVALID_ARGUMENT, "FR_FLAG_DEPTH_ALPHA with a plane gradient needs fr_aux::planes");
+    }
     return FR_OK;
 }
 
@@ -292,6 +311,8 @@ int fr_backward_batch(int32_t n_views, fr_handle* const* handles, const fr_param
                             binning[k], dL_dpix[k], grads[k]};
         int rc = check_backward(c[k], true);
         if (rc) return rc;
+        if ((prm[k]->flags ^ prm[0]->flags) & FR_FLAG_DEPTH_ALPHA)
+            return fail_msg(FR_ERR_INVALID_ARGUMENT, "the views of a batch must agree on FR_FLAG_DEPTH_ALPHA");
     }
     return launch_backward(n_views, c, static_cast<hipStream_t>(stream));
 }

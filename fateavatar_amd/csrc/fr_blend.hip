@@ -15,6 +15,7 @@
 #include "fr_diag.hpp"
 #include <hip/hip_ext.h>
 #include <cstdlib>
+#include <type_traits>
 
 namespace fr {
 
@@ -344,7 +345,9 @@ struct SortArgs {
     uint32_t* stripe_cursor;
 };
 
-__device__ __forceinline__ void tile_sort_body(const SortArgs& a)
+// PLANES (FR_FLAG_DEPTH_ALPHA): a tile without instances also gets depth 0 and alpha 0 in out_depth / out_alpha.
+template <bool PLANES>
+__device__ __forceinline__ void tile_sort_body(const SortArgs& a, float* __restrict__ out_depth, float* __restrict__ out_alpha)
 {
     const ImageView v = a.v;
     const uint32_t T = a.T, Q = a.Q, unit_cap = a.unit_cap;
@@ -439,6 +442,7 @@ __device__ __forceinline__ void tile_sort_body(const SortArgs& a)
                     v.final_T[pix] = 1.0f;
                     v.n_contrib[pix] = 0u;
                     empty_color[pix] = bg[0], empty_color[HW + pix] = bg[1], empty_color[2 * HW + pix] = bg[2];
+                    if (PLANES) out_depth[pix] = 0.f, out_alpha[pix] = 0.f;
                 }
             }
             if (n > 0 && n <= (uint32_t)kSortWaveMax) {
@@ -450,8 +454,19 @@ __device__ __forceinline__ void tile_sort_body(const SortArgs& a)
     }
 }
 
-__global__ void __launch_bounds__(256) k_tile_sort(SortArgs a) { tile_sort_body(a); }
-__global__ void __launch_bounds__(256) k_tile_sort_batch(BatchOf<SortArgs> b) { tile_sort_body(b.v[blockIdx.y]); }
+__global__ void __launch_bounds__(256) k_tile_sort(SortArgs a) { tile_sort_body<false>(a, nullptr, nullptr); }
+__global__ void __launch_bounds__(256) k_tile_sort_batch(BatchOf<SortArgs> b) { tile_sort_body<false>(b.v[blockIdx.y], nullptr, nullptr); }
+// frames with depth and alpha planes (FR_FLAG_DEPTH_ALPHA)
+struct SortPlanesArgs {
+    SortArgs s;
+    float* out_depth;
+    float* out_alpha;
+};
+__global__ void __launch_bounds__(256) k_tile_sort_planes(SortPlanesArgs a) { tile_sort_body<true>(a.s, a.out_depth, a.out_alpha); }
+__global__ void __launch_bounds__(256) k_tile_sort_planes_batch(BatchOf<SortPlanesArgs> b)
+{
+    tile_sort_body<true>(b.v[blockIdx.y].s, b.v[blockIdx.y].out_depth, b.v[blockIdx.y].out_alpha);
+}
 
 // Lists longer than kSortGroupMax (dense / zoomed-in scenes): 4 waves x 16 keys per lane up to 4096, the
 // global-memory network beyond.  A separate kernel so that its register budget (16 keys per lane) does not
@@ -656,6 +671,45 @@ __device__ __forceinline__ float reduce_scatter_36(const float (&r)[36], int lan
     return b0 ? hi : lo;
 }
 
+// reduce_scatter_36 for 40 values (four records x 10 components: the blend backward of a frame with depth and alpha planes):
+// lane l holds the wave total of value bitrev6(l) for bitrev6(l) < 40.  The same butterfly; only the first three levels
+// have more registers to pair (and level 3 no value left over).
+__device__ __forceinline__ float reduce_scatter_40(const float (&r)[40], int lane)
+{
+    float a[20], b[10], c[5], d[3], e[2];
+    typedef float v2f __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int i = 0; i < 20; i += 2) {                                        // lane bit 5 <- value bit 0
+        auto p0 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, r[2 * i]), __builtin_bit_cast(unsigned, r[2 * i + 1]), false, false);
+        auto p1 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, r[2 * i + 2]), __builtin_bit_cast(unsigned, r[2 * i + 3]), false, false);
+        const v2f x = {__builtin_bit_cast(float, (unsigned)p0[0]), __builtin_bit_cast(float, (unsigned)p1[0])};
+        const v2f y = {__builtin_bit_cast(float, (unsigned)p0[1]), __builtin_bit_cast(float, (unsigned)p1[1])};
+        const v2f z = x + y;
+        a[i] = z.x, a[i + 1] = z.y;
+    }
+#pragma unroll
+    for (int i = 0; i < 10; i++) b[i] = swap16_add(a[2 * i], a[2 * i + 1]);  // lane bit 4 <- value bit 1
+    const bool b3 = (lane & 8) != 0, b2 = (lane & 4) != 0, b1 = (lane & 2) != 0, b0 = (lane & 1) != 0;
+#pragma unroll
+    for (int i = 0; i < 5; i++) {                                            // lane bit 3 <- value bit 2
+        const float lo = FR_DPP_ADD(b[2 * i], 0x128), hi = FR_DPP_ADD(b[2 * i + 1], 0x128);  // row_ror:8
+        c[i] = b3 ? hi : lo;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; i++) {                                            // lane bit 2 <- value bit 3
+        const float lo = FR_DPP_ADD(c[2 * i], 0x141), hi = FR_DPP_ADD(c[2 * i + 1], 0x141);  // row_half_mirror
+        d[i] = b2 ? hi : lo;
+    }
+    d[2] = FR_DPP_ADD(c[4], 0x141);
+    {                                                                        // lane bit 1 <- value bit 4
+        const float lo = FR_DPP_ADD(d[0], 0x4E), hi = FR_DPP_ADD(d[1], 0x4E);  // quad_perm [2,3,0,1]
+        e[0] = b1 ? hi : lo;
+        e[1] = FR_DPP_ADD(d[2], 0x4E);
+    }
+    const float lo = FR_DPP_ADD(e[0], 0xB1), hi = FR_DPP_ADD(e[1], 0xB1);      // quad_perm [1,0,3,2]; lane bit 0 <- value bit 5
+    return b0 ? hi : lo;
+}
+
 __device__ __forceinline__ int bitrev6(int l)
 {
     return ((l & 1) << 5) | ((l & 2) << 3) | ((l & 4) << 1) | ((l & 8) >> 1) | ((l & 16) >> 3) | ((l & 32) >> 5);
@@ -663,11 +717,16 @@ __device__ __forceinline__ int bitrev6(int l)
 
 // All 64 x 64 pairs of one staged unit, back to front, four records at a time: every lane (= pixel) evaluates the four
 // records, the 36 partial sums are reduce-scattered over the wave and 36 lanes issue one atomic each.  T / A enter as
-// the state behind the unit (see k_unit_blend_bwd_sparse); lanes with lim <= 0 carry T = A = 0.
-__device__ __forceinline__ void bwd_unit_all_pairs(const float4* __restrict__ s_rec, int m, int lim, float fx, float fy, float T,
-                                                   float A, float T_final, float bg_dot_dpixel, float dpr, float dpg,
-                                                   float dpb, float* __restrict__ accum, int lane, int vv, int own_u, int own_c)
+// the state behind the unit (see k_unit_blend_bwd_sparse); lanes with lim <= 0 carry T = A = 0.  PLANES (FR_FLAG_DEPTH_ALPHA):
+// the records' view-space depths s_z are a fourth colour channel with dL/dpixel dpz (A and bg_dot_dpixel carry it), and a
+// tenth component, ACC_Z = alpha T dpz, goes with the nine: 40 partial sums, 40 lanes.
+template <bool PLANES>
+__device__ __forceinline__ void bwd_unit_all_pairs(const float4* __restrict__ s_rec, const float* __restrict__ s_z, int m, int lim,
+                                                   float fx, float fy, float T, float A, float T_final, float bg_dot_dpixel,
+                                                   float dpr, float dpg, float dpb, float dpz, float* __restrict__ accum, int lane,
+                                                   int vv, int own_u, int own_c)
 {
+    constexpr int NC = PLANES ? 10 : 9;   // components per record
     for (int j = ((m + kGroup - 1) & ~(kGroup - 1)) - kGroup; j >= 0; j -= kGroup) {
         float araw[kGroup], cd[kGroup], dx[kGroup], dy[kGroup], gx[kGroup], gy[kGroup];
         bool ok[kGroup];
@@ -686,10 +745,11 @@ __device__ __forceinline__ void bwd_unit_all_pairs(const float4* __restrict__ s_
             ok[k] = (j + k < lim) && !(power > 0.0f) && !(araw[k] < 1.0f / 255.0f);
             any_ok = any_ok || ok[k];
             cd[k] = (q1.z * dpr + q1.w * dpg) + q2x * dpb;  // colour . dL_dpixel
+            if (PLANES) cd[k] += s_z[j + k] * dpz;          // (+ depth . dL_ddepth)
         }
         if (!__any(any_ok)) continue;
 
-        float s[kGroup * 9];
+        float s[kGroup * NC];
 #pragma unroll
         for (int k = kGroup - 1; k >= 0; k--) {  // back to front
             // Lanes that fail the tests take alpha = G = 0: every state update below is then the identity and
@@ -707,7 +767,7 @@ __device__ __forceinline__ void bwd_unit_all_pairs(const float4* __restrict__ s_
             // combination with the conic / opacity happens once per Gaussian in k_preprocess_bwd.
             const float q = dL_dalpha * ar_e;
             const float qdx = q * dx[k], qdy = q * dy[k];
-            float* su = s + k * 9;
+            float* su = s + k * NC;
             su[ACC_MX] = q * gx[k];   // combined with the conic per PIXEL, as backward.cu:540-546 does (see ACC_MX)
             su[ACC_MY] = q * gy[k];
             su[ACC_CA] = qdx * dx[k];
@@ -717,9 +777,12 @@ __device__ __forceinline__ void bwd_unit_all_pairs(const float4* __restrict__ s_
             su[ACC_R] = wgt * dpr;
             su[ACC_G] = wgt * dpg;
             su[ACC_B] = wgt * dpb;
+            if (PLANES) su[ACC_Z] = wgt * dpz;
         }
-        const float total = reduce_scatter_36(reinterpret_cast<const float(&)[36]>(s), lane);
-        if (vv < kGroup * 9 && (j + own_u) < m) {
+        float total;
+        if constexpr (PLANES) total = reduce_scatter_40(s, lane);
+        else total = reduce_scatter_36(s, lane);
+        if (vv < kGroup * NC && (j + own_u) < m) {
             const uint32_t id = __float_as_uint(s_rec[(j + own_u) * kRecQuads + 2].y);
             atomic_add_f32(accum + (size_t)id * kAccumStride + own_c, total);
         }
@@ -837,16 +900,20 @@ struct WalkOut {
     uint32_t last;
     bool term;
     uint32_t iters;   // loop iterations taken (wave-uniform): the unit's cost class for the backward
+    float Cd;         // PLANES: the depth channel, sum of z alpha T (0 otherwise)
 };
 
 // Front-to-back blend of the records in `Bg` (bit j = record j of the staged unit) for this lane's pixel, starting at
 // transmittance T0; TERMINATE: apply the reference's T test (forward.cu:346-351).  Two records per iteration: their alpha
-// evaluations are independent instruction streams, only the short T / colour recurrence is serial.
-template <bool TERMINATE>
+// evaluations are independent instruction streams, only the short T / colour recurrence is serial.  PLANES
+// (FR_FLAG_DEPTH_ALPHA): the record's view-space depth (third quad, .z) is blended as a fourth colour channel, with the
+// colours' arithmetic.  (It is finite for every record that is binned, the null records of non-finite colours included, and
+// a pair that fails its tests is weighted by an exact 0.)
+template <bool TERMINATE, bool PLANES = false>
 __device__ __forceinline__ WalkOut walk_unit_fwd(const float4* __restrict__ rec, u64 Bg, float T0, float fx, float fy, uint32_t base)
 {
     WalkOut o;
-    o.Cr = o.Cg = o.Cb = 0.f;
+    o.Cr = o.Cg = o.Cb = o.Cd = 0.f;
     o.T = T0;
     o.last = 0u;
     o.term = false;
@@ -861,7 +928,7 @@ __device__ __forceinline__ WalkOut walk_unit_fwd(const float4* __restrict__ rec,
             j[k] = low_bit_or_any(Bg);
             Bg &= Bg - 1ull;
         }
-        float alpha[2], cr[2], cg[2], cb[2];
+        float alpha[2], cr[2], cg[2], cb[2], cz[2];
         bool ok[2];
 #pragma unroll
         for (int k = 0; k < 2; k++) {
@@ -873,6 +940,7 @@ __device__ __forceinline__ WalkOut walk_unit_fwd(const float4* __restrict__ rec,
             alpha[k] = fminf(0.99f, q1.y * __builtin_amdgcn_exp2f(power * kLog2e));
             ok[k] = act[k] && !(power > 0.0f) && !(alpha[k] < 1.0f / 255.0f);
             cr[k] = q1.z, cg[k] = q1.w, cb[k] = q2x;
+            cz[k] = PLANES ? rec[j[k] * kRecQuads + 2].z : 0.f;
         }
 #pragma unroll
         for (int k = 0; k < 2; k++) {
@@ -887,6 +955,7 @@ __device__ __forceinline__ WalkOut walk_unit_fwd(const float4* __restrict__ rec,
             o.Cr += cr[k] * w;
             o.Cg += cg[k] * w;
             o.Cb += cb[k] * w;
+            if (PLANES) o.Cd += cz[k] * w;
             o.T = c ? test_T : o.T;
             o.last = c ? (base + (uint32_t)j[k] + 1u) : o.last;
         }
@@ -899,18 +968,18 @@ __device__ __forceinline__ WalkOut walk_unit_fwd(const float4* __restrict__ rec,
 // independent alpha evaluations in flight, no divergent walk): measured break-even around a fifth of the pairs.
 
 // walk_unit_fwd from T = 1 over ALL records of the staged unit
-template <bool TERMINATE>
+template <bool TERMINATE, bool PLANES = false>
 __device__ __forceinline__ WalkOut blend_unit_dense_local(const float4* __restrict__ rec, uint32_t m, bool inside, float fx,
                                                           float fy, uint32_t base)
 {
     WalkOut o;
-    o.Cr = o.Cg = o.Cb = 0.f;
+    o.Cr = o.Cg = o.Cb = o.Cd = 0.f;
     o.T = 1.f;
     o.last = 0u;
     o.term = false;
     o.iters = 64u;   // (a dense unit is a heavy unit)
     for (uint32_t j = 0; j < m; j += kGroup) {
-        float alpha[kGroup], cr[kGroup], cg[kGroup], cb[kGroup];
+        float alpha[kGroup], cr[kGroup], cg[kGroup], cb[kGroup], cz[kGroup];
         bool ok[kGroup];
 #pragma unroll
         for (int k = 0; k < kGroup; k++) {   // (records beyond m are zero padding: alpha = 0)
@@ -922,6 +991,7 @@ __device__ __forceinline__ WalkOut blend_unit_dense_local(const float4* __restri
             alpha[k] = fminf(0.99f, q1.y * __builtin_amdgcn_exp2f(power * kLog2e));
             ok[k] = inside && !(power > 0.0f) && !(alpha[k] < 1.0f / 255.0f);
             cr[k] = q1.z, cg[k] = q1.w, cb[k] = q2x;
+            cz[k] = PLANES ? rec[(j + k) * kRecQuads + 2].z : 0.f;
         }
 #pragma unroll
         for (int k = 0; k < kGroup; k++) {
@@ -936,6 +1006,7 @@ __device__ __forceinline__ WalkOut blend_unit_dense_local(const float4* __restri
             o.Cr += cr[k] * w;
             o.Cg += cg[k] * w;
             o.Cb += cb[k] * w;
+            if (PLANES) o.Cd += cz[k] * w;
             o.T = c ? test_T : o.T;
             o.last = c ? (base + j + (uint32_t)k + 1u) : o.last;
         }
@@ -953,23 +1024,33 @@ __device__ __forceinline__ float load_row(const float* p)
     return COHERENT ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
 }
 
+// The depth and alpha planes of a frame with FR_FLAG_DEPTH_ALPHA: where the forward blend keeps the depth channel's unit
+// rows and entry state (PlaneView), and the two output planes.
+struct PlaneArgs {
+    float* unit_depth;
+    float* depth_state;
+    float* out_depth;
+    float* out_alpha;
+};
+
 // One wave, one tile: the image, and the backward entry state of every unit, from the units' final
 // contributions.  Pure loads and adds: the rows of 8 units are requested together.  FWD_ONLY (FR_FLAG_FORWARD_ONLY):
-// no entry state is stored, the image / final_T / n_contrib are the same.
-template <bool COHERENT, bool FWD_ONLY>
+// no entry state is stored, the image / final_T / n_contrib are the same.  PLANES (FR_FLAG_DEPTH_ALPHA): the depth rows
+// are summed like a colour channel (same order) into out_depth and the entry state's depth, out_alpha = 1 - final_T.
+template <bool COHERENT, bool FWD_ONLY, bool PLANES = false>
 __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, uint32_t u0, uint32_t nu, const float* g_out,
                                             float4* __restrict__ unit_state, int W, int H, float bg0, float bg1, float bg2,
-                                            float* __restrict__ out_color, int lane)
+                                            float* __restrict__ out_color, int lane, const PlaneArgs& pl = PlaneArgs{})
 {
     constexpr int R = 8;
     const int px = (int)(tile % (uint32_t)v.tiles_x) * kTile + (lane & 7);
     const int py = (int)(tile / (uint32_t)v.tiles_x) * kTile + (lane >> 3);
     const bool inside = px < W && py < H;
     const size_t pix = (size_t)py * W + px, HW = (size_t)H * W;
-    float Cr = 0.f, Cg = 0.f, Cb = 0.f, Tf = 1.0f;
+    float Cr = 0.f, Cg = 0.f, Cb = 0.f, Cd = 0.f, Tf = 1.0f;
     uint32_t ncon = 0;
     if (nu <= (uint32_t)R) {   // short tile: one round of loads, the image front to back, the suffix pass on the registers
-        float cr[R], cg[R], cb[R], To[R];
+        float cr[R], cg[R], cb[R], cd[R], To[R];
         uint32_t lw[R];
 #pragma unroll
         for (int k = 0; k < R; k++) {
@@ -978,27 +1059,32 @@ __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, u
             cr[k] = load_row<COHERENT>(o), cg[k] = load_row<COHERENT>(o + kUnit), cb[k] = load_row<COHERENT>(o + 2 * kUnit);
             To[k] = load_row<COHERENT>(o + 3 * kUnit);
             lw[k] = __float_as_uint(load_row<COHERENT>(o + 4 * kUnit));
+            cd[k] = PLANES ? load_row<COHERENT>(pl.unit_depth + (size_t)(u0 + kk) * kUnit + lane) : 0.f;
         }
 #pragma unroll
         for (int k = 0; k < R; k++) {
             if ((uint32_t)k < nu) {
                 const bool dead = (lw[k] & kDeadBit) != 0u;
                 Cr += cr[k], Cg += cg[k], Cb += cb[k];   // (a dead pixel's contribution is stored as 0)
+                if (PLANES) Cd += cd[k];
                 if (!dead) {
                     Tf = To[k];
                     if (lw[k] & ~kDeadBit) ncon = lw[k] & ~kDeadBit;
                 }
             }
         }
-        float Sr = 0.f, Sg = 0.f, Sb = 0.f;
+        float Sr = 0.f, Sg = 0.f, Sb = 0.f, Sd = 0.f;
 #pragma unroll
         for (int k = R - 1; k >= 0; k--) {
             if ((uint32_t)k < nu) {
                 const float inv = (To[k] >= 0.0001f) ? __builtin_amdgcn_rcpf(To[k]) : 0.f;   // (dead on entry: T may have underflowed)
                 // (the tile's LAST unit has nothing behind it and leaves with final_T: the backward builds that state itself)
-                if (!FWD_ONLY && (uint32_t)k + 1u < nu)
+                if (!FWD_ONLY && (uint32_t)k + 1u < nu) {
                     unit_state[(size_t)(u0 + (uint32_t)k) * kUnit + lane] = make_float4(Sr * inv, Sg * inv, Sb * inv, To[k]);
+                    if (PLANES) pl.depth_state[(size_t)(u0 + (uint32_t)k) * kUnit + lane] = Sd * inv;
+                }
                 Sr += cr[k], Sg += cg[k], Sb += cb[k];
+                if (PLANES) Sd += cd[k];
             }
         }
     } else {
@@ -1006,10 +1092,10 @@ __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, u
         // of the rows behind it, the image the sum of all of them (in this order), the final transmittance and contributor
         // count come from the last unit that was alive for the pixel.  (Units whose every pixel is dead get no state: the
         // backward never reads it.)
-        float Sr = 0.f, Sg = 0.f, Sb = 0.f;
+        float Sr = 0.f, Sg = 0.f, Sb = 0.f, Sd = 0.f;
         bool have_T = false, have_n = false;
         for (uint32_t base = (nu - 1u) & ~(uint32_t)(R - 1);; base -= R) {
-            float cr[R], cg[R], cb[R], To[R];
+            float cr[R], cg[R], cb[R], cd[R], To[R];
             uint32_t lw[R];
 #pragma unroll
             for (int k = 0; k < R; k++) {
@@ -1018,6 +1104,7 @@ __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, u
                 cr[k] = load_row<COHERENT>(o), cg[k] = load_row<COHERENT>(o + kUnit), cb[k] = load_row<COHERENT>(o + 2 * kUnit);
                 To[k] = load_row<COHERENT>(o + 3 * kUnit);
                 lw[k] = __float_as_uint(load_row<COHERENT>(o + 4 * kUnit));
+                cd[k] = PLANES ? load_row<COHERENT>(pl.unit_depth + (size_t)(u0 + kk) * kUnit + lane) : 0.f;
             }
 #pragma unroll
             for (int k = R - 1; k >= 0; k--) {
@@ -1027,14 +1114,17 @@ __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, u
                     if (!dead && !have_T) Tf = To[k], have_T = true;
                     if (!dead && !have_n && last) ncon = last, have_n = true;
                     const float inv = (To[k] >= 0.0001f) ? __builtin_amdgcn_rcpf(To[k]) : 0.f;
-                    if (!FWD_ONLY && base + (uint32_t)k + 1u < nu && !__all(dead))
+                    if (!FWD_ONLY && base + (uint32_t)k + 1u < nu && !__all(dead)) {
                         unit_state[(size_t)(u0 + base + (uint32_t)k) * kUnit + lane] = make_float4(Sr * inv, Sg * inv, Sb * inv, To[k]);
+                        if (PLANES) pl.depth_state[(size_t)(u0 + base + (uint32_t)k) * kUnit + lane] = Sd * inv;
+                    }
                     Sr += cr[k], Sg += cg[k], Sb += cb[k];
+                    if (PLANES) Sd += cd[k];
                 }
             }
             if (base == 0) break;
         }
-        Cr = Sr, Cg = Sg, Cb = Sb;
+        Cr = Sr, Cg = Sg, Cb = Sb, Cd = Sd;
     }
     if (inside) {
         v.final_T[pix] = Tf;
@@ -1042,6 +1132,7 @@ __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, u
         out_color[pix] = Cr + Tf * bg0;
         out_color[HW + pix] = Cg + Tf * bg1;
         out_color[2 * HW + pix] = Cb + Tf * bg2;
+        if (PLANES) pl.out_depth[pix] = Cd, pl.out_alpha[pix] = 1.f - Tf;   // (the depth's background is 0)
     }
 }
 
@@ -1087,6 +1178,8 @@ __device__ __forceinline__ void pair_alpha_from_memory(const float4* __restrict_
     ok = inside && !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
     c0 = q1.z, c1 = q1.w, c2 = r[2].x;
 }
+// the record's view-space depth (GeomView::rec_tmpl column 10)
+__device__ __forceinline__ float depth_from_memory(const float4* __restrict__ r) { return reinterpret_cast<const float*>(r + 2)[2]; }
 
 // per-pixel product of (1 - alpha) over unit p's blendable records: what unit p publishes
 __device__ float unit_product_from_memory(const uint4* __restrict__ unit_tile, const RecSrc& recs, uint32_t p, float fx,
@@ -1153,6 +1246,46 @@ __device__ UnitRow unit_row_from_memory(const uint4* __restrict__ unit_tile, con
     return o;
 }
 
+// FR_FLAG_DEPTH_ALPHA: the depth word of unit q's final row, the same walks and arithmetic as unit_row_from_memory's colours
+__device__ float unit_depth_from_memory(const uint4* __restrict__ unit_tile, const RecSrc& recs, uint32_t q, float Tin, float fx,
+                                        float fy, bool inside)
+{
+    const uint4 d = unit_tile[q];
+    const uint32_t base = d.y * kUnit, m = min((uint32_t)kUnit, d.w - base);
+    const size_t r0 = (size_t)d.z + base;
+    float t = 1.0f, cd = 0.f;
+    for (uint32_t j = 0; j < m; j++) {
+        float alpha, c0, c1, c2;
+        bool ok;
+        pair_alpha_from_memory(recs.at(r0 + j), fx, fy, inside, alpha, ok, c0, c1, c2);
+        const float w = ok ? alpha * t : 0.f;
+        cd += depth_from_memory(recs.at(r0 + j)) * w;
+        t = ok ? t * (1.f - alpha) : t;
+    }
+    const bool dead = !inside || (Tin < 0.0001f);
+    const bool crosses = !dead && (Tin * t < 0.0001f);
+    float o = dead ? 0.f : Tin * cd;
+    if (__any(crosses)) {
+        float T = Tin, xd = 0.f;
+        bool term = false;
+        for (uint32_t j = 0; j < m; j++) {
+            float alpha, c0, c1, c2;
+            bool ok;
+            pair_alpha_from_memory(recs.at(r0 + j), fx, fy, inside, alpha, ok, c0, c1, c2);
+            bool c = ok && crosses;
+            const float test_T = T * (1.f - alpha);
+            const bool fin = c && !term && (test_T < 0.0001f);
+            term = term || fin;
+            c = c && !term;
+            const float w = c ? alpha * T : 0.f;
+            xd += depth_from_memory(recs.at(r0 + j)) * w;
+            T = c ? test_T : T;
+        }
+        if (crosses) o = xd;
+    }
+    return o;
+}
+
 // the product unit p published — or, if it has not appeared after `spins` polls, computed here
 __device__ __forceinline__ float chain_product(float* g_tseg, const uint4* __restrict__ unit_tile, const RecSrc& recs,
                                                uint32_t p, float first, uint32_t spins, int lane, float fx, float fy, bool inside)
@@ -1194,8 +1327,11 @@ struct ChainArgs {
 // FWD_ONLY (FR_FLAG_FORWARD_ONLY): a frame no backward will follow.  The footprint masks are still built and transposed
 // (the walks run on them) but neither `masks` nor `walks` is stored, no unit takes a slot in the backward's work list, and
 // the gather stores no entry state; the products, rows, unit_done flags and the image are exactly the full forward's.
-template <bool FWD_ONLY>
-__device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
+// PLANES (FR_FLAG_DEPTH_ALPHA): the records keep their view-space depth in the staged third quad (the forward reads the
+// footprint masks from registers only), the walks blend it as a fourth colour channel, every unit row gets a depth word in
+// PlaneView::unit_depth, and the gather writes the depth and alpha planes; everything the plain forward writes is the same.
+template <bool FWD_ONLY, bool PLANES>
+__device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a, const PlaneArgs& pl)
 {
     DeviceCounts* __restrict__ counts = a.counts;
     const uint4* __restrict__ unit_tile = a.unit_tile;
@@ -1239,7 +1375,7 @@ __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
     if (ui.base + (uint32_t)lane < ui.n) {
         fm = footprint_mask(rr.q0.x, rr.q0.y, rr.q0.z, rr.q0.w, rr.q1.x, rr.q1.y,
                             (float)((int)ui.tx * kTile), (float)((int)ui.ty * kTile));
-        rr.q2.z = __uint_as_float(fm.x), rr.q2.w = __uint_as_float(fm.y);
+        if (!PLANES) rr.q2.z = __uint_as_float(fm.x), rr.q2.w = __uint_as_float(fm.y);
         if (!FWD_ONLY) masks[(size_t)ui.start + ui.base + (uint32_t)lane] = fm;
     }
     rec[lane * kRecQuads + 0] = rr.q0;
@@ -1257,8 +1393,8 @@ __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
     FW_STAMP(2);   // staged, masks, transpose
     FW_STAMPV(9, npairs);
     // ---- local blend from T = 1, no termination test
-    const WalkOut o = npairs > dense_pairs ? blend_unit_dense_local<false>(rec, ui.m, ui.inside, fx, fy, ui.base)
-                                           : walk_unit_fwd<false>(rec, Bp, 1.0f, fx, fy, ui.base);
+    const WalkOut o = npairs > dense_pairs ? blend_unit_dense_local<false, PLANES>(rec, ui.m, ui.inside, fx, fy, ui.base)
+                                           : walk_unit_fwd<false, PLANES>(rec, Bp, 1.0f, fx, fy, ui.base);
     if (ui.base + kUnit < ui.n)   // (nobody reads the last unit's product)
         __hip_atomic_store(g_tseg + (size_t)u * kUnit + lane, fmaxf(o.T, 1e-30f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // the unit's place in the backward's work list (BwdUnit): long walks from the front of its stripe, the others from the back
@@ -1309,9 +1445,11 @@ __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
     float Cr = dead ? 0.f : Tin * o.Cr, Cg = dead ? 0.f : Tin * o.Cg, Cb = dead ? 0.f : Tin * o.Cb;
     float To = dead ? Tin : Tin * o.T;
     uint32_t last = dead ? 0u : o.last;
+    float Cd = PLANES && !dead ? Tin * o.Cd : 0.f;
     if (__any(crosses)) {   // the records are still staged, the walk sets still in registers
-        const WalkOut x = walk_unit_fwd<true>(rec, crosses ? Bp : 0ull, Tin, fx, fy, ui.base);
+        const WalkOut x = walk_unit_fwd<true, PLANES>(rec, crosses ? Bp : 0ull, Tin, fx, fy, ui.base);
         if (crosses) Cr = x.Cr, Cg = x.Cg, Cb = x.Cb, To = x.T, last = x.last;
+        if (PLANES && crosses) Cd = x.Cd;
     }
     if (unit_done && ui.seg == 0u && ui.base + kUnit >= ui.n) {
         // the tile's ONLY unit (12 % of BASELINE config 2's tiles; most tiles of a sparser scene): nothing to hand over, nothing to gather — the pixels are
@@ -1323,6 +1461,7 @@ __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
             out_color[pix] = Cr + To * bg[0];
             out_color[HW + pix] = Cg + To * bg[1];
             out_color[2 * HW + pix] = Cb + To * bg[2];
+            if (PLANES) pl.out_depth[pix] = Cd, pl.out_alpha[pix] = 1.f - To;
         }
         return;
     }
@@ -1334,6 +1473,7 @@ __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
         out[2 * kUnit] = Cb;
         out[3 * kUnit] = To;
         out[4 * kUnit] = __uint_as_float(lw);
+        if (PLANES) pl.unit_depth[(size_t)u * kUnit + lane] = Cd;
         return;
     }
     // ---- gather in the chain: the tile's LAST unit adds everything up once the others have delivered.  The rows are
@@ -1345,6 +1485,7 @@ __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
     __hip_atomic_store(out + 2 * kUnit, Cb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(out + 3 * kUnit, To, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(out + 4 * kUnit, __uint_as_float(lw), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (PLANES) __hip_atomic_store(pl.unit_depth + (size_t)u * kUnit + lane, Cd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     FW_STAMP(5);   // row written
     FW_STAMPV(12, __builtin_amdgcn_s_memrealtime());
@@ -1378,27 +1519,47 @@ __device__ __forceinline__ void unit_blend_chained_body(const ChainArgs& a)
             __hip_atomic_store(o2 + 2 * kUnit, rr.cb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(o2 + 3 * kUnit, rr.To, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(o2 + 4 * kUnit, __uint_as_float(rr.lw), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (PLANES)
+                __hip_atomic_store(pl.unit_depth + (size_t)qq * kUnit + lane, unit_depth_from_memory(unit_tile, recs, qq, tin, fx, fy, ui.inside),
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     asm volatile("" ::: "memory");
     FW_STAMP(6);   // (a tile's last unit) the other units' rows are there
-    gather_tile<true, FWD_ONLY>(v, ui.ty * (uint32_t)v.tiles_x + ui.tx, u0, ui.seg + 1u, g_out, unit_state, W, H, bg[0], bg[1], bg[2], out_color, lane);
+    gather_tile<true, FWD_ONLY, PLANES>(v, ui.ty * (uint32_t)v.tiles_x + ui.tx, u0, ui.seg + 1u, g_out, unit_state, W, H, bg[0], bg[1], bg[2],
+                                        out_color, lane, pl);
     FW_STAMP(7);   // gathered
     FW_STAMPV(12, __builtin_amdgcn_s_memrealtime());
 }
 
-__global__ void __launch_bounds__(256) k_unit_blend_chained(ChainArgs a) { unit_blend_chained_body<false>(a); }
-__global__ void __launch_bounds__(256) k_unit_blend_chained_batch(BatchOf<ChainArgs> b) { unit_blend_chained_body<false>(b.v[blockIdx.y]); }
+__global__ void __launch_bounds__(256) k_unit_blend_chained(ChainArgs a) { unit_blend_chained_body<false, false>(a, PlaneArgs{}); }
+__global__ void __launch_bounds__(256) k_unit_blend_chained_batch(BatchOf<ChainArgs> b) { unit_blend_chained_body<false, false>(b.v[blockIdx.y], PlaneArgs{}); }
 // forward-only frames (FR_FLAG_FORWARD_ONLY): no backward hand-off
-__global__ void __launch_bounds__(256) k_unit_blend_chained_fwd_only(ChainArgs a) { unit_blend_chained_body<true>(a); }
-__global__ void __launch_bounds__(256) k_unit_blend_chained_fwd_only_batch(BatchOf<ChainArgs> b) { unit_blend_chained_body<true>(b.v[blockIdx.y]); }
+__global__ void __launch_bounds__(256) k_unit_blend_chained_fwd_only(ChainArgs a) { unit_blend_chained_body<true, false>(a, PlaneArgs{}); }
+__global__ void __launch_bounds__(256) k_unit_blend_chained_fwd_only_batch(BatchOf<ChainArgs> b) { unit_blend_chained_body<true, false>(b.v[blockIdx.y], PlaneArgs{}); }
+// frames with depth and alpha planes (FR_FLAG_DEPTH_ALPHA), with and without the backward hand-off
+struct ChainPlanesArgs {
+    ChainArgs c;
+    PlaneArgs p;
+};
+__global__ void __launch_bounds__(256) k_unit_blend_chained_planes(ChainPlanesArgs a) { unit_blend_chained_body<false, true>(a.c, a.p); }
+__global__ void __launch_bounds__(256) k_unit_blend_chained_planes_batch(BatchOf<ChainPlanesArgs> b)
+{
+    unit_blend_chained_body<false, true>(b.v[blockIdx.y].c, b.v[blockIdx.y].p);
+}
+__global__ void __launch_bounds__(256) k_unit_blend_chained_fwd_only_planes(ChainPlanesArgs a) { unit_blend_chained_body<true, true>(a.c, a.p); }
+__global__ void __launch_bounds__(256) k_unit_blend_chained_fwd_only_planes_batch(BatchOf<ChainPlanesArgs> b)
+{
+    unit_blend_chained_body<true, true>(b.v[blockIdx.y].c, b.v[blockIdx.y].p);
+}
 
 // the gather as its own launch (FR_BLEND_FWD=gather): one wave per tile
-template <bool FWD_ONLY>
+template <bool FWD_ONLY, bool PLANES = false>
 __device__ __forceinline__ void tile_gather_body(const DeviceCounts* __restrict__ counts, const ImageView& v,
                                                  const float* __restrict__ g_out, float4* __restrict__ unit_state, int W, int H,
-                                                 const float* __restrict__ bg, float* __restrict__ out_color)
+                                                 const float* __restrict__ bg, float* __restrict__ out_color,
+                                                 const PlaneArgs& pl = PlaneArgs{})
 {
     const uint32_t n_tiles = (uint32_t)v.tiles_x * v.tiles_y;
     const int lane = threadIdx.x & 63;
@@ -1410,7 +1571,7 @@ __device__ __forceinline__ void tile_gather_body(const DeviceCounts* __restrict_
     const uint32_t n = v.tile_total[tile];
     const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
     if (overflow) return;
-    gather_tile<false, FWD_ONLY>(v, tile, u0, (n + kUnit - 1) / kUnit, g_out, unit_state, W, H, bg0, bg1, bg2, out_color, lane);
+    gather_tile<false, FWD_ONLY, PLANES>(v, tile, u0, (n + kUnit - 1) / kUnit, g_out, unit_state, W, H, bg0, bg1, bg2, out_color, lane, pl);
 }
 __global__ void __launch_bounds__(256) k_tile_gather(const DeviceCounts* __restrict__ counts, const ImageView v,
                                                     const float* __restrict__ g_out, float4* __restrict__ unit_state, int W,
@@ -1423,6 +1584,20 @@ __global__ void __launch_bounds__(256) k_tile_gather_fwd_only(const DeviceCounts
                                                              int W, int H, const float* __restrict__ bg, float* __restrict__ out_color)
 {
     tile_gather_body<true>(counts, v, g_out, unit_state, W, H, bg, out_color);
+}
+__global__ void __launch_bounds__(256) k_tile_gather_planes(const DeviceCounts* __restrict__ counts, const ImageView v,
+                                                           const float* __restrict__ g_out, float4* __restrict__ unit_state, int W,
+                                                           int H, const float* __restrict__ bg, float* __restrict__ out_color,
+                                                           const PlaneArgs pl)
+{
+    tile_gather_body<false, true>(counts, v, g_out, unit_state, W, H, bg, out_color, pl);
+}
+__global__ void __launch_bounds__(256) k_tile_gather_fwd_only_planes(const DeviceCounts* __restrict__ counts, const ImageView v,
+                                                                    const float* __restrict__ g_out, float4* __restrict__ unit_state,
+                                                                    int W, int H, const float* __restrict__ bg,
+                                                                    float* __restrict__ out_color, const PlaneArgs pl)
+{
+    tile_gather_body<true, true>(counts, v, g_out, unit_state, W, H, bg, out_color, pl);
 }
 
 
@@ -1438,8 +1613,26 @@ struct BlendBwdArgs {
     uint32_t dense_pairs;
 };
 
-__device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a)
+// What the blend backward of a frame with depth and alpha planes reads besides (FR_FLAG_DEPTH_ALPHA): the planes' upstream
+// gradients (either may be null: zero) and the depth part of the units' entry state.
+struct BwdPlaneArgs {
+    const float* dL_ddepth;
+    const float* dL_dalpha;
+    const float* depth_state;
+};
+// the staged records' view-space depths next to the plain form's LDS (PLANES only)
+struct SparseLdsPlanes : SparseLds {
+    float z[kBatch];
+};
+
+// PLANES (FR_FLAG_DEPTH_ALPHA): the depth plane is a fourth colour channel whose colour is the record's view-space depth and
+// whose background is 0 (A, the per-pair colour dot and phase B's tenth sum, ACC_Z = dL/dz), and the alpha plane
+// 1 - T_final enters through the background term: dL/dT_final = bg . dL_dpixel - dL_dalpha.
+template <bool PLANES>
+__device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a, const BwdPlaneArgs& pl)
 {
+    constexpr int NC = PLANES ? 10 : 9;     // gradient components per record
+    constexpr int RPF = PLANES ? 6 : 7;     // records per flush atomic (NC * RPF <= 63 lanes)
     const DeviceCounts* __restrict__ counts = a.counts;
     const ImageView v = a.v;
     void* binning = a.binning;
@@ -1448,7 +1641,7 @@ __device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a
     const float* __restrict__ dL_dpix = a.dL_dpix;
     float* __restrict__ accum = a.accum;
     const uint32_t dense_pairs = a.dense_pairs;
-    __shared__ SparseLds s_all[kWavesPerWG];
+    __shared__ std::conditional_t<PLANES, SparseLdsPlanes, SparseLds> s_all[kWavesPerWG];
     const int lane = threadIdx.x & 63;
     const int wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // The first unit's descriptor is requested BEFORE the counts are known (one round trip less in front of every
@@ -1464,16 +1657,16 @@ __device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a
     // parks it behind the loop's entry test, i.e. behind the counts' round trip)
     asm volatile("" ::"v"(d_first.x), "v"(u_of_first), "s"(nu), "s"(capacity));
     const BinningView b = BinningView::make(binning, (size_t)capacity, (size_t)n_tiles);
-    SparseLds& S = s_all[wave_in_wg];
+    auto& S = s_all[wave_in_wg];
     const uint32_t wave_stride = gridDim.x * kWavesPerWG;
     const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
     // flush: lanes 0..62 = 7 records x 9 components; lane l of a septet starting at record r0 reads word r0 * 9 + l of
-    // the [record][9] sums and adds it to component l % 9 of record r0 + l / 9
-    const int fl_rec = lane / 9, fl_c = lane - fl_rec * 9;
+    // the [record][9] sums and adds it to component l % 9 of record r0 + l / 9 (PLANES: 6 records x 10 components)
+    const int fl_rec = lane / NC, fl_c = lane - fl_rec * NC;
     float* const accum_c = accum + fl_c;
-    // the same for the all-pairs form (bwd_unit_all_pairs): 4 records x 9 components after its reduce-scatter
+    // the same for the all-pairs form (bwd_unit_all_pairs): 4 records x 9 (10) components after its reduce-scatter
     const int vv = bitrev6(lane);
-    const int own_u = vv / 9, own_c = vv - own_u * 9;
+    const int own_u = vv / NC, own_c = vv - own_u * NC;
     const size_t HW = (size_t)H * W;
     for (uint32_t w = w_first; w < nu; w += wave_stride) {
         // ---- every load below depends on the descriptor only: all of them are in flight together (clamped indices keep
@@ -1503,6 +1696,15 @@ __device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a
         const bool last_unit = base + (uint32_t)kUnit >= n;
         if (!last_unit) st = b.unit_state[(size_t)u * kUnit + lane];
         const float d0 = dL_dpix[pix], d1 = dL_dpix[HW + pix], d2 = dL_dpix[2 * HW + pix];
+        // (PLANES: the record's depth, the two plane gradients and the depth entry state, with the other loads)
+        float rz = 0.f, dz_raw = 0.f, da_raw = 0.f, sd = 0.f;
+        if (PLANES) {
+            rz = reinterpret_cast<const float*>(rsrc + 2)[2];
+            if (pl.dL_ddepth) dz_raw = pl.dL_ddepth[pix];
+            if (pl.dL_dalpha) da_raw = pl.dL_dalpha[pix];
+            if (pl.dL_ddepth && !last_unit) sd = pl.depth_state[(size_t)u * kUnit + lane];   // (only ever multiplied by dL_ddepth)
+            asm volatile("" ::"v"(rz), "v"(dz_raw), "v"(da_raw), "v"(sd));
+        }
         // (pinned: otherwise everything but n_contrib is sunk below the early exit, a second round trip)
         asm volatile("" ::"v"(last_raw), "v"(rq0.x), "v"(rq1.x), "v"(rq2.x), "v"(mraw.x), "v"(bt.x), "v"(st.x), "v"(Tf_raw), "v"(d0), "v"(d1), "v"(d2));
         const uint32_t last = inside ? last_raw : 0u;
@@ -1526,6 +1728,7 @@ __device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a
         S.rec[lane * kRecQuads + 1] = make_float4(valid_rec ? rq1.x : 0.f, valid_rec ? rq1.y : 0.f, valid_rec ? rq1.z : 0.f, valid_rec ? rq1.w : 0.f);
         // the walks read (colour b, first pair slot, mask) from the third quad, the all-pairs form (colour b, id)
         S.rec[lane * kRecQuads + 2] = make_float4(rq2.x, dense ? rq2.y : __uint_as_float(cum - cnt), __uint_as_float(mj.x), __uint_as_float(mj.y));
+        if constexpr (PLANES) S.z[lane] = valid_rec ? rz : 0.f;
         // the pixel's walk set, limited to the records in front of its last contributor
         const int lim = (int)last - (int)base;      // records [0, lim) of this unit can contribute to this pixel
         u64 Bp = ((u64)bt.y << 32) | bt.x;
@@ -1534,18 +1737,24 @@ __device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a
         const float T_final = inside ? Tf_raw : 0.f;
         const float dpr = inside ? d0 : 0.f, dpg = inside ? d1 : 0.f, dpb = inside ? d2 : 0.f;
         const float fx = (float)px, fy = (float)py;
-        const float bgd = (bg0 * dpr + bg1 * dpg) + bg2 * dpb;
+        const float dpz = inside ? dz_raw : 0.f, dpa = inside ? da_raw : 0.f;   // (PLANES; 0 otherwise)
+        float bgd = (bg0 * dpr + bg1 * dpg) + bg2 * dpb;
+        if (PLANES) bgd -= dpa;                                                // alpha = 1 - T_final
         const float tfb = -T_final * bgd;                                      // -T_final * (bg . dL_dpixel)
         float T = lim > 0 ? (last_unit ? Tf_raw : st.w) : 0.f;
         float A = lim > 0 ? (st.x * dpr + st.y * dpg) + st.z * dpb : 0.f;     // accum_rec . dL_dpixel: the recurrence is linear, one scalar is carried
+        if (PLANES) A += lim > 0 ? sd * dpz : 0.f;
+        const float* s_z = nullptr;
+        if constexpr (PLANES) s_z = S.z;
         if (dense) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            bwd_unit_all_pairs(S.rec, (int)m, lim, fx, fy, T, A, T_final, bgd, dpr, dpg, dpb, accum, lane, vv, own_u, own_c);
+            bwd_unit_all_pairs<PLANES>(S.rec, s_z, (int)m, lim, fx, fy, T, A, T_final, bgd, dpr, dpg, dpb, dpz, accum, lane, vv, own_u,
+                                       own_c);
             __builtin_amdgcn_wave_barrier();   // (S.rec is restaged by the next unit)
             continue;
         }
-        S.pix[lane] = make_float4(dpr, dpg, dpb, 0.f);
+        S.pix[lane] = make_float4(dpr, dpg, dpb, PLANES ? dpz : 0.f);
         const float rxl = rq0.x - (float)tx0, ryl = rq0.y - (float)ty0;           // own record centre, tile-local
         // own record's conic as stored, (a', b', c') = (-0.5 a, -b, -0.5 c) EXACTLY: phase B combines a pair's (dx, dy) with it
         // per PIXEL — (2 a' dx + b' dy, b' dx + 2 c' dy) = -(a dx + b dy, b dx + c dy) = dG/d(centre) / G — as backward.cu:540-546 does
@@ -1607,6 +1816,7 @@ __device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a
                     const float araw = q1.y * __builtin_amdgcn_exp2f(power * kLog2e);   // opacity * G (alpha before the 0.99 clamp)
                     const bool ok = act[k] && !(power > 0.0f) && !(araw < 1.0f / 255.0f);
                     cd[k] = (q1.z * dpr + q1.w * dpg) + q2.x * dpb;              // colour . dL_dpixel
+                    if (PLANES) cd[k] += s_z[j[k]] * dpz;                       // (+ depth . dL_ddepth)
                     ar_e[k] = ok ? araw : 0.f;                                  // failed pair: alpha = 0, every update is the identity
                     // rank of this pixel among the record's pixels: mask bits below this lane (v_mbcnt: popcount of
                     // (operand & lanes-below-mine) + accumulator, two instructions for the 64 bits)
@@ -1632,7 +1842,7 @@ __device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a
             // ---- phase B: lane = record, over its own pixels (two per iteration); its pairs are consecutive slots
             typedef float v2f __attribute__((ext_vector_type(2)));
             v2f s_m = {0.f, 0.f}, s_ab = {0.f, 0.f}, s_rg = {0.f, 0.f};   // (MX, MY) (CA, CB) (R, G)
-            float s_cc = 0.f, s_op = 0.f, s_b = 0.f;
+            float s_cc = 0.f, s_op = 0.f, s_b = 0.f, s_z_sum = 0.f;
             u64 Mg = (lane >= lo && lane < hi) ? Mj : 0ull;
             uint32_t slot = (cum - cnt) - slot0;
             if (__any(Mg != 0ull) && !FR_ABLATE(3)) do {
@@ -1656,25 +1866,28 @@ __device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a
                     s_op += q;
                     s_rg += wgt * (v2f){dp.x, dp.y};
                     s_b += wgt * dp.z;
+                    if (PLANES) s_z_sum += wgt * dp.w;
                 }
             } while (__any(Mg != 0ull));
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             FR_TR(5);   // phase B
             // ---- flush: [record][9] through LDS (the pair slots are dead now), then 7 records x 9 components per atomic
+            // (PLANES: [record][10], 6 records x 10 components)
             float* fl = reinterpret_cast<float*>(S.pair);
             {
-                float* o = fl + lane * 9;
+                float* o = fl + lane * NC;
                 o[ACC_MX] = s_m.x, o[ACC_MY] = s_m.y, o[ACC_CA] = s_ab.x, o[ACC_CB] = s_ab.y, o[ACC_CC] = s_cc, o[ACC_OP] = s_op;
                 o[ACC_R] = s_rg.x, o[ACC_G] = s_rg.y, o[ACC_B] = s_b;
+                if (PLANES) o[ACC_Z] = s_z_sum;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            for (int r0 = lo; r0 < hi; r0 += 7) {
+            for (int r0 = lo; r0 < hi; r0 += RPF) {
                 const int rj = r0 + fl_rec;
                 const uint32_t id = (uint32_t)__builtin_amdgcn_ds_bpermute(min(rj, 63) << 2, (int)my_id);
-                const float val = fl[r0 * 9 + lane];
-                if (lane < 63 && rj < hi && val != 0.f && !FR_ABLATE(4)) {
+                const float val = fl[r0 * NC + lane];
+                if (lane < RPF * NC && rj < hi && val != 0.f && !FR_ABLATE(4)) {
                     if (FR_ABLATE(5)) accum_c[(size_t)id * kAccumStride] = val;   // (timing experiment: plain stores)
                     else atomic_add_f32(accum_c + (size_t)id * kAccumStride, val);
                 }
@@ -1688,8 +1901,21 @@ __device__ __forceinline__ void unit_blend_bwd_sparse_body(const BlendBwdArgs& a
     }
 }
 
-__global__ void __launch_bounds__(256) k_unit_blend_bwd_sparse(BlendBwdArgs a) { unit_blend_bwd_sparse_body(a); }
-__global__ void __launch_bounds__(256) k_unit_blend_bwd_sparse_batch(BatchOf<BlendBwdArgs> b) { unit_blend_bwd_sparse_body(b.v[blockIdx.y]); }
+__global__ void __launch_bounds__(256) k_unit_blend_bwd_sparse(BlendBwdArgs a) { unit_blend_bwd_sparse_body<false>(a, BwdPlaneArgs{}); }
+__global__ void __launch_bounds__(256) k_unit_blend_bwd_sparse_batch(BatchOf<BlendBwdArgs> b)
+{
+    unit_blend_bwd_sparse_body<false>(b.v[blockIdx.y], BwdPlaneArgs{});
+}
+// frames with depth and alpha planes (FR_FLAG_DEPTH_ALPHA) whose backward is handed a plane gradient
+struct BlendBwdPlanesArgs {
+    BlendBwdArgs b;
+    BwdPlaneArgs p;
+};
+__global__ void __launch_bounds__(256) k_unit_blend_bwd_sparse_planes(BlendBwdPlanesArgs a) { unit_blend_bwd_sparse_body<true>(a.b, a.p); }
+__global__ void __launch_bounds__(256) k_unit_blend_bwd_sparse_planes_batch(BatchOf<BlendBwdPlanesArgs> b)
+{
+    unit_blend_bwd_sparse_body<true>(b.v[blockIdx.y].b, b.v[blockIdx.y].p);
+}
 
 // test hook: run the 36-value reduce-scatter on in[lane*36 + k] and return each lane's result
 __global__ void __launch_bounds__(64) k_selftest_reduce(const float* in, float* out)
@@ -1718,10 +1944,13 @@ int launch_sort_and_blend(int n, const FrameView* f, hipStream_t s, bool debug)
 {
     fr_handle_impl* h0 = f[0].h;
     const bool fwd_only = (f[0].prm->flags & FR_FLAG_FORWARD_ONLY) != 0;   // (the same for every view of a batch)
+    const bool planes = (f[0].prm->flags & FR_FLAG_DEPTH_ALPHA) != 0;      // (likewise)
     int rc;
     SortArgs sa[kMaxBatch];
     BigSortArgs ba[kMaxBatch];
     ChainArgs ca[kMaxBatch];
+    SortPlanesArgs sp[kMaxBatch];
+    ChainPlanesArgs cp[kMaxBatch];
     uint32_t sort_blocks = 0, unit_wgs = 0, gather_blocks = 0;
     // The big sorter is only launched when the most recent frame whose counts have reached the host had a list
     // longer than kSortGroupMax (or none has been seen yet); otherwise k_tile_sort keeps a slow but correct path for them.
@@ -1759,6 +1988,10 @@ int launch_sort_and_blend(int n, const FrameView* f, hipStream_t s, bool debug)
         c.unit_done = h->gather_in_chain ? b.unit_done : nullptr;
         c.v = v, c.unit_state = b.unit_state, c.bg = f[k].in->background, c.out_color = f[k].out_color;
         c.chain_spins = h->chain_spins;
+        if (planes) {
+            sp[k] = SortPlanesArgs{a, f[k].out_depth, f[k].out_alpha};
+            cp[k] = ChainPlanesArgs{c, PlaneArgs{f[k].pv.unit_depth, f[k].pv.depth_state, f[k].out_depth, f[k].out_alpha}};
+        }
     }
     {
         StageScope sc(h0, ST_SORT, s);
@@ -1770,7 +2003,8 @@ int launch_sort_and_blend(int n, const FrameView* f, hipStream_t s, bool debug)
             launch_views(k_tile_sort_big, k_tile_sort_big_batch, n, ba, kBigSorters, 256, 0, h0->side_stream);
             FR_HIP(hipEventRecord(h0->side_join, h0->side_stream));
         }
-        launch_views(k_tile_sort, k_tile_sort_batch, n, sa, sort_blocks, 256, 0, s);
+        if (planes) launch_views(k_tile_sort_planes, k_tile_sort_planes_batch, n, sp, sort_blocks, 256, 0, s);
+        else launch_views(k_tile_sort, k_tile_sort_batch, n, sa, sort_blocks, 256, 0, s);
         // the counts reach the pinned host slots with this kernel: the (waiting) forward blocks on them, not on the frame
         for (int k = 0; k < n; k++)
             if (!(f[k].prm->flags & FR_FLAG_NO_WAIT)) FR_HIP(hipEventRecord(f[k].h->counts_ready, s));
@@ -1781,9 +2015,16 @@ int launch_sort_and_blend(int n, const FrameView* f, hipStream_t s, bool debug)
     {
         StageScope sc(h0, ST_BLEND_FWD, s);
         // (one workgroup per four units, no grid-stride loop: see k_unit_blend_chained on forward progress)
-        if (fwd_only) launch_views(k_unit_blend_chained_fwd_only, k_unit_blend_chained_fwd_only_batch, n, ca, unit_wgs, 64 * kWavesPerWG, 0, s);
+        if (planes) {
+            if (fwd_only) launch_views(k_unit_blend_chained_fwd_only_planes, k_unit_blend_chained_fwd_only_planes_batch, n, cp, unit_wgs, 64 * kWavesPerWG, 0, s);
+            else launch_views(k_unit_blend_chained_planes, k_unit_blend_chained_planes_batch, n, cp, unit_wgs, 64 * kWavesPerWG, 0, s);
+        } else if (fwd_only) launch_views(k_unit_blend_chained_fwd_only, k_unit_blend_chained_fwd_only_batch, n, ca, unit_wgs, 64 * kWavesPerWG, 0, s);
         else launch_views(k_unit_blend_chained, k_unit_blend_chained_batch, n, ca, unit_wgs, 64 * kWavesPerWG, 0, s);
-        if (!h0->gather_in_chain)   // (n == 1, see above)
+        if (!h0->gather_in_chain && planes)
+            hipLaunchKernelGGL(fwd_only ? k_tile_gather_fwd_only_planes : k_tile_gather_planes, dim3(gather_blocks), dim3(64 * kWavesPerWG), 0, s,
+                               f[0].v.counts, f[0].v, f[0].b.unit_out, f[0].b.unit_state, f[0].prm->W, f[0].prm->H, f[0].in->background,
+                               f[0].out_color, cp[0].p);
+        else if (!h0->gather_in_chain)   // (n == 1, see above)
             hipLaunchKernelGGL(fwd_only ? k_tile_gather_fwd_only : k_tile_gather, dim3(gather_blocks), dim3(64 * kWavesPerWG), 0, s, f[0].v.counts, f[0].v,
                                f[0].b.unit_out, f[0].b.unit_state, f[0].prm->W, f[0].prm->H, f[0].in->background, f[0].out_color);
     }
@@ -1792,7 +2033,7 @@ int launch_sort_and_blend(int n, const FrameView* f, hipStream_t s, bool debug)
     return FR_OK;
 }
 
-int launch_blend_backward(int n, const BackwardCall* calls, const GeomView* g, const ImageView* v, hipStream_t s, bool debug)
+int launch_blend_backward(int n, const BackwardCall* calls, const GeomView* g, const ImageView* v, bool planes, hipStream_t s, bool debug)
 {
     // The unit count lives on the device: grid-stride loop over the units, whatever the grid.  The grid follows the unit
     // count of the handle's most recent frame whose counts have reached the host (+ 1/8), between 256 and kUnitGrid
@@ -1810,6 +2051,18 @@ int launch_blend_backward(int n, const BackwardCall* calls, const GeomView* g, c
         a[k].rec_tmpl = g[k].rec_tmpl;
         a[k].W = calls[k].prm->W, a[k].H = calls[k].prm->H, a[k].bg = calls[k].in->background;
         a[k].dL_dpix = calls[k].dL_dpix, a[k].accum = g[k].accum, a[k].dense_pairs = calls[k].h->dense_pairs_bwd;
+    }
+    if (planes) {   // (a plane gradient, FR_FLAG_DEPTH_ALPHA: checked by fr_backward)
+        BlendBwdPlanesArgs ap[kMaxBatch];
+        for (int k = 0; k < n; k++) {
+            const fr_aux* aux = calls[k].prm->aux;
+            ap[k] = BlendBwdPlanesArgs{a[k], BwdPlaneArgs{aux ? aux->dL_ddepth : nullptr, aux ? aux->dL_dalpha : nullptr,
+                                                          aux && aux->planes ? PlaneView::make(aux->planes, 0, 0).depth_state : nullptr}};
+        }
+        StageScope sc(calls[0].h, ST_BLEND_BWD, s);
+        launch_views(k_unit_blend_bwd_sparse_planes, k_unit_blend_bwd_sparse_planes_batch, n, ap, unit_grid, 64 * kWavesPerWG, 0, s);
+        FR_HIP(hipGetLastError());
+        return debug_sync(debug, s, "blend_bwd");
     }
     hipEvent_t ev_a, ev_b;
     if (n == 1 && next_stage_events(calls[0].h, ST_BLEND_BWD, &ev_a, &ev_b)) {

@@ -39,7 +39,9 @@ constexpr int kSortRegMax = 4096;    // longest list k_tile_sort_big sorts in re
 // of two only) — summing q*dx and q*dy and combining afterwards lets the two products of an elongated splat cancel only after
 // N pixels' worth of rounding, and a conic whose entries were rounded independently puts its rounding into that cancellation.
 // k_preprocess_bwd turns them into the reference's dL_dmean2D / dL_dconic / dL_dopacity / dL_dcolor.
-enum { ACC_MX = 0, ACC_MY = 1, ACC_CA = 2, ACC_CB = 3, ACC_CC = 4, ACC_OP = 5, ACC_R = 6, ACC_G = 7, ACC_B = 8 };
+// Z (frames with depth and alpha planes, FR_FLAG_DEPTH_ALPHA, only): alpha*T*dL/ddepth, i.e. dL/dz of the view-space depth.
+// Plain frames never write it; k_preprocess_bwd re-zeroes it with the rest of the row either way.
+enum { ACC_MX = 0, ACC_MY = 1, ACC_CA = 2, ACC_CB = 3, ACC_CC = 4, ACC_OP = 5, ACC_R = 6, ACC_G = 7, ACC_B = 8, ACC_Z = 9 };
 
 extern thread_local char g_err[512];
 int fail_hip(hipError_t e, const char* what, const char* file, int line);
@@ -246,6 +248,28 @@ struct BinningView {
     }
 };
 
+// The per-unit scratch of a frame with depth and alpha planes (FR_FLAG_DEPTH_ALPHA, fr_aux::planes): the depth channel's share
+// of the unit hand-off, kept out of the binning buffer so that plain frames keep their sizes.  Same unit indexing.
+struct PlaneView {
+    float* depth_state;   // [unit_cap*64] backward entry state per pixel: depth behind the unit / T_out.  FIRST: its address does
+                          // not depend on the capacity, which the host does not know in the backward
+    float* unit_depth;    // [unit_cap*64] forward partial per pixel: the depth row next to BinningView::unit_out's Cr, Cg, Cb
+    __host__ __device__ static PlaneView make(void* buf, size_t cap, size_t T)
+    {
+        char* p = static_cast<char*>(buf);
+        const size_t units = BinningView::units_for(cap, T);
+        PlaneView pv;
+        pv.depth_state = carve<float>(p, units * kUnit);
+        pv.unit_depth = carve<float>(p, units * kUnit);
+        return pv;
+    }
+    static size_t bytes(size_t cap, size_t T)
+    {
+        PlaneView pv = make(nullptr, cap, T);
+        return reinterpret_cast<size_t>(pv.unit_depth + BinningView::units_for(cap, T) * kUnit) + 256;
+    }
+};
+
 // Where the blend kernels read the record at position `pos` of the sorted lists: the Gaussian's template record
 // (GeomView::rec_tmpl, 4.8 MB at 100 k Gaussians: L2 / MALL resident), found through the sorted id.  (Round 2 had
 // k_tile_sort gather the template and write a 48-byte copy per instance: 3.4 us more in the sort, 1.5 us less in each
@@ -397,6 +421,10 @@ struct FrameView {
     ImageView v;
     BinningView b;
     float* out_color;
+    // FR_FLAG_DEPTH_ALPHA: the planes' scratch and outputs (fr_aux::planes, out_depth, out_alpha), unset otherwise
+    PlaneView pv;
+    float* out_depth;
+    float* out_alpha;
 };
 // kernel for one view, its *_batch twin for several: the twin takes BatchOf<A> and a (gx, n) grid
 template <typename A, typename KS, typename KB>

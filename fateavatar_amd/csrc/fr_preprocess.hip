@@ -960,6 +960,11 @@ static int prepare_forward(const ForwardCall& c, hipStream_t s, bool capturing, 
     tot.v = v, tot.T = T, tot.capacity = c.cap, tot.block_ref_tiles = g.block_ref_tiles;
     tot.n_blocks = (uint32_t)((P + kPreWG - 1) / kPreWG);
     f.h = h, f.prm = c.prm, f.in = c.in, f.g = g, f.v = v, f.b = b, f.out_color = c.out_color;
+    f.pv = PlaneView{}, f.out_depth = f.out_alpha = nullptr;
+    if (prm.flags & FR_FLAG_DEPTH_ALPHA) {   // (fr_forward_batch has checked the three pointers)
+        f.pv = PlaneView::make(prm.aux->planes, c.cap, (size_t)T);
+        f.out_depth = prm.aux->out_depth, f.out_alpha = prm.aux->out_alpha;
+    }
     return FR_OK;
 }
 

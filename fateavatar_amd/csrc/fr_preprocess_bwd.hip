@@ -56,7 +56,9 @@ __device__ __forceinline__ void store3(float* p, size_t i, float a, float b, flo
 }
 
 // Everything for ONE Gaussian.  `row` (LDS, may be null) receives this Gaussian's dL_dsh row (the kernel writes the rows
-// of a wave through LDS for coalesced HBM access).
+// of a wave through LDS for coalesced HBM access).  PLANES (a backward with a depth gradient, FR_FLAG_DEPTH_ALPHA): the
+// accumulated dL/dz of the view-space depth (ACC_Z) joins dL/dmean3D through z = view[2] x + view[6] y + view[10] z + view[14].
+template <bool PLANES>
 __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const CameraRegs& cam, const int radius,
                                                    const int idx, float* row)
 {
@@ -291,6 +293,10 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
     } else if (a.out.dL_dsh && !row && !adds(G_SH)) {
         for (int k = 0; k < Mc * 3; k++) a.out.dL_dsh[i * Mc * 3 + k] = 0.f;
     }
+    if (PLANES) {
+        const float dz = acc[ACC_Z];
+        dmx += dz * vm[2], dmy += dz * vm[6], dmz += dz * vm[10];
+    }
     store3(a.out.dL_dmeans3D, i, old_m3[0] + dmx, old_m3[1] + dmy, old_m3[2] + dmz, false);
     const float g_mean[3] = {dmx, dmy, dmz};   // (this frame's, for the binding)
     float g_scl[3] = {0.f, 0.f, 0.f}, g_rot[4] = {0.f, 0.f, 0.f, 0.f};
@@ -408,6 +414,7 @@ __device__ __forceinline__ void unstage_rows(float* __restrict__ dst, const floa
 #endif
 constexpr int kPreBwdWaves = FR_PREBWD_WAVES;  // waves per workgroup of k_preprocess_bwd
 
+template <bool PLANES>
 __device__ __forceinline__ void preprocess_bwd_body(const PreBwdArgs& a)
 {
     extern __shared__ __attribute__((aligned(16))) float s_rows[];
@@ -424,24 +431,33 @@ __device__ __forceinline__ void preprocess_bwd_body(const PreBwdArgs& a)
     // camera and radius are requested before the SH block is staged: one round trip for all of them
     const CameraRegs cam = load_camera(a.view, a.proj, a.campos, lane);
     const int radius = idx < a.P ? a.radii[idx] : 0;
-    if (idx < a.P) preprocess_bwd_one(a, cam, radius, idx, staged ? w_rows + lane * stride : nullptr);
+    if (idx < a.P) preprocess_bwd_one<PLANES>(a, cam, radius, idx, staged ? w_rows + lane * stride : nullptr);
     __syncthreads();
     if (staged && rows > 0) unstage_rows(a.out.dL_dsh + (size_t)wave_first * M3, w_rows, stride, rows, M3, lane, ((a.acc >> G_SH) & 1u) != 0u);
 }
 
-__global__ void __launch_bounds__(64 * kPreBwdWaves) k_preprocess_bwd(PreBwdArgs a) { preprocess_bwd_body(a); }
-__global__ void __launch_bounds__(64 * kPreBwdWaves) k_preprocess_bwd_batch(BatchOf<PreBwdArgs> b) { preprocess_bwd_body(b.v[blockIdx.y]); }
+__global__ void __launch_bounds__(64 * kPreBwdWaves) k_preprocess_bwd(PreBwdArgs a) { preprocess_bwd_body<false>(a); }
+__global__ void __launch_bounds__(64 * kPreBwdWaves) k_preprocess_bwd_batch(BatchOf<PreBwdArgs> b) { preprocess_bwd_body<false>(b.v[blockIdx.y]); }
+// backward passes handed a depth or alpha gradient (FR_FLAG_DEPTH_ALPHA): + dL/dz
+__global__ void __launch_bounds__(64 * kPreBwdWaves) k_preprocess_bwd_planes(PreBwdArgs a) { preprocess_bwd_body<true>(a); }
+__global__ void __launch_bounds__(64 * kPreBwdWaves) k_preprocess_bwd_planes_batch(BatchOf<PreBwdArgs> b) { preprocess_bwd_body<true>(b.v[blockIdx.y]); }
 
-// implemented in fr_blend.hip: the blend backward of n views (their accumulators in g[k].accum)
-int launch_blend_backward(int n, const BackwardCall* calls, const GeomView* g, const ImageView* v, hipStream_t s, bool debug);
+// implemented in fr_blend.hip: the blend backward of n views (their accumulators in g[k].accum); `planes`: the views'
+// plane gradients (fr_aux::dL_ddepth / dL_dalpha) go in too
+int launch_blend_backward(int n, const BackwardCall* calls, const GeomView* g, const ImageView* v, bool planes, hipStream_t s, bool debug);
 
 int launch_backward(int n, const BackwardCall* calls, hipStream_t s)
 {
     GeomView g[kMaxBatch];
     ImageView v[kMaxBatch];
     PreBwdArgs args[kMaxBatch];
-    bool capturing = false, debug = false;
+    bool capturing = false, debug = false, planes = false;
     for (int k = 0; k < n; k++) capturing = note_capture(calls[k].h, s) || capturing;
+    // a depth or alpha gradient in any view (FR_FLAG_DEPTH_ALPHA, checked by fr_backward): the planes instances for all of them
+    for (int k = 0; k < n; k++) {
+        const fr_aux* aux = calls[k].prm->aux;
+        planes = planes || ((calls[k].prm->flags & FR_FLAG_DEPTH_ALPHA) && aux && (aux->dL_ddepth || aux->dL_dalpha));
+    }
     size_t lds = 0;
     uint32_t blocks = 0;
     const int wg = 64 * kPreBwdWaves;
@@ -490,11 +506,12 @@ int launch_backward(int n, const BackwardCall* calls, hipStream_t s)
         blocks = max(blocks, (uint32_t)((P + wg - 1) / wg));
     }
     // g.accum is all zero here: zeroed when allocated, and again by k_preprocess_bwd after every backward
-    int rc = launch_blend_backward(n, calls, g, v, s, debug);
+    int rc = launch_blend_backward(n, calls, g, v, planes, s, debug);
     if (rc) return rc;
     {
         StageScope sc(calls[0].h, ST_PREPROCESS_BWD, s);
-        launch_views(k_preprocess_bwd, k_preprocess_bwd_batch, n, args, blocks, (uint32_t)wg, lds, s);
+        if (planes) launch_views(k_preprocess_bwd_planes, k_preprocess_bwd_planes_batch, n, args, blocks, (uint32_t)wg, lds, s);
+        else launch_views(k_preprocess_bwd, k_preprocess_bwd_batch, n, args, blocks, (uint32_t)wg, lds, s);
     }
     FR_HIP(hipGetLastError());
     if (!capturing)

@@ -165,11 +165,13 @@ def _stats3(stats):
     return stats[0], stats[1], (stats[2] if len(stats) > 2 else None)
 
 
-def _aux(visible=None, grad_accum=None, denom=None, binding=None, bind_grads=None, overflow_out=None):
+def _aux(visible=None, grad_accum=None, denom=None, binding=None, bind_grads=None, overflow_out=None, planes=None):
     """fr_aux (optional fused side inputs / outputs) from torch tensors, or None if nothing is asked for.  `binding`: an
     `_lib.fr_binding` descriptor (the frame is rendered straight from its mesh binding); `bind_grads`: dict with the
-    backward's d_verts / d_offset / d_rotation / d_scaling tensors (any may be None)."""
-    if visible is None and grad_accum is None and denom is None and binding is None and overflow_out is None:
+    backward's d_verts / d_offset / d_rotation / d_scaling tensors (any may be None).  `planes` (FR_FLAG_DEPTH_ALPHA): dict
+    of the out_depth / out_alpha / dL_ddepth / dL_dalpha tensors and the `planes` scratch (any may be None; the scratch of a
+    forward is set by the launcher, which sizes it with the binning buffer)."""
+    if visible is None and grad_accum is None and denom is None and binding is None and overflow_out is None and planes is None:
         return None
     for t, dt in ((visible, (torch.bool, torch.uint8)), (grad_accum, (torch.float32,)), (denom, (torch.float32,))):
         if t is not None and (t.dtype not in dt or not t.is_contiguous() or not t.is_cuda):
@@ -189,6 +191,13 @@ def _aux(visible=None, grad_accum=None, denom=None, binding=None, bind_grads=Non
                 if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
                     raise RuntimeError(f"binding gradient {n} must be a contiguous float32 device tensor")
                 setattr(aux, n, t.data_ptr())
+    if planes is not None:
+        aux._planes_keepalive = planes
+        for n, t in planes.items():
+            if t is not None:
+                if not (t.is_cuda and t.is_contiguous() and (t.dtype == torch.float32 or n == "planes")):
+                    raise RuntimeError(f"{n} must be a contiguous float32 device tensor")
+                setattr(aux, n, t.data_ptr())
     return aux
 
 
@@ -206,10 +215,11 @@ def _grad_shapes(P, M):
 _GRAD_NAMES = tuple(_grad_shapes(0, 0))
 
 
-def _forward_view(args, raw=False, visible=None, binding=None, forward_only=False) -> dict:
+def _forward_view(args, raw=False, visible=None, binding=None, forward_only=False, depth_alpha=False) -> dict:
     """One view of a forward, from the positional arguments of `rasterize_gaussians`: its inputs as the kernels read them
     (kept alive in the view), its fr_params / fr_inputs, outputs and binning capacity.  The launcher allocates the binning
-    buffer.  `forward_only`: FR_FLAG_FORWARD_ONLY (no backward may be run on the frame's buffers)."""
+    buffer.  `forward_only`: FR_FLAG_FORWARD_ONLY (no backward may be run on the frame's buffers).  `depth_alpha`:
+    FR_FLAG_DEPTH_ALPHA (the view also returns depth [H,W], alpha [H,W] and the planes scratch its backward needs)."""
     (background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
      tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug) = args
     if means3D.dim() != 2 or means3D.size(1) != 3:
@@ -219,9 +229,13 @@ def _forward_view(args, raw=False, visible=None, binding=None, forward_only=Fals
     keep = _f32c(background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos)
     M = sh.size(1) if sh.numel() != 0 else 0
     L, opts = _lib.lib(), dict(device=means3D.device)
-    return dict(dev=dev, W=W, H=H, opts=opts, keep=keep, inp=_inputs(*keep),
-                prm=_params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, prefiltered, debug, raw,
-                            _aux(visible=visible, binding=binding), _lib.FR_FLAG_FORWARD_ONLY if forward_only else 0),
+    planes = None
+    if depth_alpha:
+        planes = dict(out_depth=torch.empty((H, W), dtype=torch.float32, **opts), out_alpha=torch.empty((H, W), dtype=torch.float32, **opts))
+    aux = _aux(visible=visible, binding=binding, planes=planes)
+    flags = (_lib.FR_FLAG_FORWARD_ONLY if forward_only else 0) | (_lib.FR_FLAG_DEPTH_ALPHA if depth_alpha else 0)
+    return dict(dev=dev, W=W, H=H, opts=opts, keep=keep, inp=_inputs(*keep), aux=aux, planes=planes,
+                prm=_params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, prefiltered, debug, raw, aux, flags),
                 out_color=torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, **opts),
                 radii=torch.empty((P,), dtype=torch.int32, **opts),
                 geom=torch.empty((L.fr_geometry_bytes(P),), dtype=torch.uint8, **opts),
@@ -230,10 +244,11 @@ def _forward_view(args, raw=False, visible=None, binding=None, forward_only=Fals
 
 
 def _backward_view(args, raw=False, want=None, out=None, stats=None, accumulate=(), binding=None, bind_grads=None,
-                   what="rasterize_gaussians_backward") -> dict:
+                   what="rasterize_gaussians_backward", planes=None) -> dict:
     """One view of a backward, from the positional arguments of `rasterize_gaussians_backward` and its keyword
     arguments: the gradient tensors it returns, its inputs as the kernels read them (kept alive in the view), and its
-    fr_params / fr_inputs / fr_grads."""
+    fr_params / fr_inputs / fr_grads.  `planes` (FR_FLAG_DEPTH_ALPHA): (planesBuffer, dL_ddepth, dL_dalpha) of a frame
+    rendered with depth and alpha planes; either gradient may be None (zero)."""
     (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
      tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug) = args
     dev = _dev_index(means3D)
@@ -256,10 +271,15 @@ def _backward_view(args, raw=False, want=None, out=None, stats=None, accumulate=
     *keep, dpix = _f32c(background, means3D, sh, colors, None, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
                         campos, dL_dout_color)
     acc_flags = sum(1 << (_lib.FR_FLAG_ACCUMULATE_SHIFT + _GRAD_NAMES.index(k)) for k in accumulate)
-    aux = None
-    if stats is not None or binding is not None:
+    aux, pl = None, None
+    if planes is not None:
+        buf, dz, da = planes
+        pl = dict(planes=buf, dL_ddepth=None if dz is None else _f32c(dz.reshape(H, W))[0],
+                  dL_dalpha=None if da is None else _f32c(da.reshape(H, W))[0])
+        acc_flags |= _lib.FR_FLAG_DEPTH_ALPHA
+    if stats is not None or binding is not None or pl is not None:
         grad_accum, denom, overflow_out = _stats3(stats)
-        aux = _aux(grad_accum=grad_accum, denom=denom, overflow_out=overflow_out, binding=binding, bind_grads=bind_grads)
+        aux = _aux(grad_accum=grad_accum, denom=denom, overflow_out=overflow_out, binding=binding, bind_grads=bind_grads, planes=pl)
     return dict(dev=dev, g=g, keep=keep, inp=_inputs(*keep), grads=_lib.fr_grads(*_ptrs(*g.values())),
                 prm=_params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, False, debug, raw, aux, acc_flags),
                 radii=radii.contiguous(), geom=geomBuffer, img=imageBuffer, binning=binningBuffer, dpix=dpix)
@@ -290,6 +310,9 @@ def _launch_forward(views, slots, batch):
         while True:
             for v in views:
                 v["binning"] = torch.empty((L.fr_binning_bytes(v["cap"], v["W"], v["H"]),), dtype=torch.uint8, **v["opts"])
+                if v["planes"] is not None:   # (FR_FLAG_DEPTH_ALPHA: sized with the binning buffer)
+                    v["planes"]["planes"] = torch.empty((L.fr_planes_bytes(v["cap"], v["W"], v["H"]),), dtype=torch.uint8, **v["opts"])
+                    v["aux"].planes = v["planes"]["planes"].data_ptr()
             if batch:
                 rc = L.fr_forward_batch(K, handles, prm_p, inp_p, arr("out_color"), arr("radii"), arr("geom"), arr("img"),
                                         arr("binning"), (C.c_uint64 * K)(*[v["cap"] for v in views]), counts, stream)
@@ -309,7 +332,10 @@ def _launch_forward(views, slots, batch):
         if not _no_wait:  # (with it, the counts arrive later: read_counts / check_async_overflow)
             _capacity_hint[dev] = max(_capacity_hint.get(dev, 0), int(c.num_instances * 1.25) + 1024)
             last_counts[dev] = c
-        out.append((0 if _no_wait else int(c.num_rendered), v["out_color"], v["radii"], v["geom"], v["binning"], v["img"]))
+        r = (0 if _no_wait else int(c.num_rendered), v["out_color"], v["radii"], v["geom"], v["binning"], v["img"])
+        if v["planes"] is not None:
+            r += (v["planes"]["out_depth"], v["planes"]["out_alpha"], v["planes"]["planes"])
+        out.append(r)
     return out
 
 
@@ -335,27 +361,33 @@ def _launch_backward(views, slots, batch):
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                        prefiltered, debug, _raw=False, _visible=None, _forward_only=False):
+                        prefiltered, debug, _raw=False, _visible=None, _forward_only=False, _depth_alpha=False):
     """`_C.rasterize_gaussians` (rasterize_points.cu:35-115).  `_raw=True` (extension, FR_FLAG_RAW_ACTIVATIONS):
     opacity / scales / rotations are the RAW parameters and the kernels apply sigmoid / exp / normalize.
     `_forward_only=True` (extension, FR_FLAG_FORWARD_ONLY): the frame is rendered without the backward's hand-off — same
     image and radii — and its buffers cannot be handed to `rasterize_gaussians_backward`.  Never chosen here on its own.
+    `_depth_alpha=True` (extension, FR_FLAG_DEPTH_ALPHA): the frame also renders its depth and alpha planes.
 
     Returns (num_rendered, out_color[3,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer); the three
-    byte buffers are opaque and must be handed back to `rasterize_gaussians_backward`."""
+    byte buffers are opaque and must be handed back to `rasterize_gaussians_backward`.  With `_depth_alpha`, three more:
+    depth[H,W], alpha[H,W] and planesBuffer (opaque: `rasterize_gaussians_backward(..., _planes=(planesBuffer, dL_ddepth,
+    dL_dalpha))`)."""
     v = _forward_view((background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                        projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug),
-                      _raw, _visible, forward_only=_forward_only)
+                      _raw, _visible, forward_only=_forward_only, depth_alpha=_depth_alpha)
     if v["prm"].P == 0:  # rasterize_points.cu:81 skips the rasterizer entirely
         empty = torch.empty((0,), dtype=torch.uint8, device=means3D.device)
-        return 0, v["out_color"].zero_(), v["radii"], empty, empty.clone(), empty.clone()
+        r = (0, v["out_color"].zero_(), v["radii"], empty, empty.clone(), empty.clone())
+        if _depth_alpha:
+            r += (v["planes"]["out_depth"].zero_(), v["planes"]["out_alpha"].zero_(), empty.clone())
+        return r
     return _launch_forward([v], [_slot], batch=False)[0]
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                  geomBuffer, R, binningBuffer, imageBuffer, debug, _want=None, _out=None, _raw=False,
-                                 _stats=None, _accumulate=()):
+                                 _stats=None, _accumulate=(), _planes=None):
     """`_C.rasterize_gaussians_backward` (rasterize_points.cu:117-196).
 
     Returns (dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dsh[P,M,3],
@@ -363,10 +395,11 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     also does `_add_densification_stats` (model/fateavatar.py:734-737) for the Gaussians with radii > 0.
     `_want` (extension): the names of the gradients to compute (the others come back as None); `_out`: caller-provided
     gradient buffers, written in place; `_accumulate`: names of `_out` buffers the frame's gradient is ADDED to
-    (FR_FLAG_ACCUMULATE)."""
+    (FR_FLAG_ACCUMULATE); `_planes=(planesBuffer, dL_ddepth, dL_dalpha)` (FR_FLAG_DEPTH_ALPHA): the gradients of the depth
+    and alpha planes of a frame rendered with `_depth_alpha` (either may be None)."""
     v = _backward_view((background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                         projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                        imageBuffer, debug), _raw, _want, _out, _stats, _accumulate)
+                        imageBuffer, debug), _raw, _want, _out, _stats, _accumulate, planes=_planes)
     if v["prm"].P == 0:
         return tuple((_out[k] if k in _accumulate else torch.zeros(s, device=means3D.device, dtype=torch.float32))
                      for k, s in _grad_shapes(0, v["prm"].M).items())
@@ -374,14 +407,15 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
 
 
 # ------------------------------------------------------------------ batched frames (fr_forward_batch / fr_backward_batch)
-def rasterize_gaussians_batch(views, slots=None, raw=False, visibles=None, bindings=None, forward_only=False):
+def rasterize_gaussians_batch(views, slots=None, raw=False, visibles=None, bindings=None, forward_only=False, depth_alpha=False):
     """K views through ONE launch chain (include/fr_rasterizer.h, fr_forward_batch): `views` is a list of the positional
     argument tuples of `rasterize_gaussians` (background ... debug), one per view; view k uses the device's handle
     `slots[k]` (default k).  Returns the list of `rasterize_gaussians` result tuples.  The results are those of K separate
     calls; what changes is that every kernel of the frame is launched once for all views.
     `bindings` (extension, fr_aux::binding): per view an `_lib.fr_binding` or None — the view's means3D / scales / rotations
     tensors are then OUTPUTS (written by the preprocess kernel from the mesh binding).  `forward_only` (extension,
-    FR_FLAG_FORWARD_ONLY): every view is rendered without the backward's hand-off; never chosen here on its own."""
+    FR_FLAG_FORWARD_ONLY): every view is rendered without the backward's hand-off; never chosen here on its own.
+    `depth_alpha` (extension, FR_FLAG_DEPTH_ALPHA): every view's result also holds depth, alpha and planesBuffer."""
     K = len(views)
     if not 1 <= K <= _lib.FR_MAX_BATCH:
         raise RuntimeError(f"rasterize_gaussians_batch: 1 .. {_lib.FR_MAX_BATCH} views")
@@ -394,7 +428,7 @@ def rasterize_gaussians_batch(views, slots=None, raw=False, visibles=None, bindi
     for k, a in enumerate(views):
         if bindings[k] is not None and not all(t.is_contiguous() and t.dtype == torch.float32 for t in (a[1], a[4], a[5])):
             raise RuntimeError("rasterize_gaussians_batch: a bound view's means3D / scales / rotations are written in place")
-        v = _forward_view(a, raw, visibles[k], bindings[k], forward_only)
+        v = _forward_view(a, raw, visibles[k], bindings[k], forward_only, depth_alpha)
         if st and v["dev"] != st[0]["dev"]:
             raise RuntimeError("rasterize_gaussians_batch: the views of a batch live on one device")
         if v["prm"].P == 0:
@@ -404,20 +438,21 @@ def rasterize_gaussians_batch(views, slots=None, raw=False, visibles=None, bindi
 
 
 def rasterize_gaussians_backward_batch(views, slots=None, raw=False, wants=None, outs=None, stats=None, accumulates=None,
-                                       bindings=None, bind_grads=None):
+                                       bindings=None, bind_grads=None, planes=None):
     """`rasterize_gaussians_backward` for K views in ONE launch chain (fr_backward_batch): `views` is a list of its
     positional argument tuples (background ... debug); `wants` / `outs` / `stats` / `accumulates`: per-view lists of the
     corresponding keyword arguments.  Returns the list of gradient tuples.  `bindings` / `bind_grads` (extension,
     fr_aux::binding): per view the descriptor the forward was given and a dict of the d_verts / d_offset / d_rotation /
-    d_scaling tensors the kernel writes (d_verts: adds)."""
+    d_scaling tensors the kernel writes (d_verts: adds).  `planes` (FR_FLAG_DEPTH_ALPHA): per view the `_planes` tuple of
+    `rasterize_gaussians_backward`; the views must agree on having one."""
     K = len(views)
     if not 1 <= K <= _lib.FR_MAX_BATCH:
         raise RuntimeError(f"rasterize_gaussians_backward_batch: 1 .. {_lib.FR_MAX_BATCH} views")
     slots = list(range(K)) if slots is None else [int(x) for x in slots]
-    wants, outs, stats, accumulates, bindings, bind_grads = (x or [None] * K for x in (wants, outs, stats, accumulates, bindings,
-                                                                                      bind_grads))
+    wants, outs, stats, accumulates, bindings, bind_grads, planes = (x or [None] * K for x in (wants, outs, stats, accumulates,
+                                                                                              bindings, bind_grads, planes))
     st = [_backward_view(a, raw, wants[k], outs[k], stats[k], tuple(accumulates[k] or ()), bindings[k], bind_grads[k],
-                         "rasterize_gaussians_backward_batch") for k, a in enumerate(views)]
+                         "rasterize_gaussians_backward_batch", planes[k]) for k, a in enumerate(views)]
     # fr_aux::overflow_out is OVERWRITTEN (0 or 1) by every backward: views of one launch that shared a word would race, and a
     # view that did not overflow could clear the flag of one that did (the optimizer would step on a partly zero gradient)
     words = [int(_stats3(stats[k])[2].data_ptr()) for k in range(K) if _stats3(stats[k])[2] is not None]
@@ -429,23 +464,25 @@ def rasterize_gaussians_backward_batch(views, slots=None, raw=False, wants=None,
 
 class _RasterizeGaussiansBatch(torch.autograd.Function):
     """`_RasterizeGaussians` for K views rendered together.  Tensor arguments: per view (means3D, means2D, sh,
-    colors_precomp, opacities, scales, rotations, cov3Ds_precomp); outputs: per view (color, radii)."""
+    colors_precomp, opacities, scales, rotations, cov3Ds_precomp); outputs: per view (color, radii), and with `depth_alpha`
+    (color, radii, depth [1,H,W], alpha [1,H,W])."""
 
     @staticmethod
-    def forward(ctx, settings, raw_activations, slots, forward_only, *tensors):
+    def forward(ctx, settings, raw_activations, slots, forward_only, depth_alpha, *tensors):
         K = len(settings)
         assert len(tensors) == 8 * K
         ctx.raw, ctx.K, ctx.settings, ctx.slots = bool(raw_activations), K, settings, slots
+        ctx.depth_alpha = bool(depth_alpha)
         ctx.set_materialize_grads(False)
         per_view = [tensors[8 * k:8 * k + 8] for k in range(K)]
         viss = [torch.empty((t[0].shape[0],), dtype=torch.bool, device=t[0].device) for t in per_view]
         res = rasterize_gaussians_batch([_forward_args(rs, *t) for rs, t in zip(settings, per_view)], slots=slots,
-                                        raw=ctx.raw, visibles=viss, forward_only=forward_only)
+                                        raw=ctx.raw, visibles=viss, forward_only=forward_only, depth_alpha=ctx.depth_alpha)
         ctx.stats, ctx.num_rendered, ctx.grads = [], [], []
         saved, outs = [], []
         for (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), vis, r in \
                 zip(per_view, viss, res):
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = r
+            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = r[:6]
             radii._fr_visible = vis
             ctx.stats.append(getattr(means2D, "_fr_densification_stats", None))
             ctx.num_rendered.append(num_rendered)
@@ -453,18 +490,25 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                                                   cov3Ds_precomp))
             saved += [colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer]
             outs += [color, radii]
+            if ctx.depth_alpha:
+                saved.append(r[8])
+                outs += [r[6].unsqueeze(0), r[7].unsqueeze(0)]
         ctx.save_for_backward(*saved)
-        ctx.mark_non_differentiable(*outs[1::2])
+        n_out = 4 if ctx.depth_alpha else 2
+        ctx.mark_non_differentiable(*outs[1::n_out])
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *grad_outs):
-        grad_colors = grad_outs[0::2]
-        if all(g is None for g in grad_colors):
-            return (None,) * 4 + (None,) * (8 * ctx.K)
-        views, outs = [], []
+        n_out, n_saved = (4, 11) if ctx.depth_alpha else (2, 10)
+        grad_colors = grad_outs[0::n_out]
+        grad_planes = [grad_outs[n_out * k + 2:n_out * k + 4] for k in range(ctx.K)] if ctx.depth_alpha else [(None, None)] * ctx.K
+        if all(g is None for g in grad_colors) and all(g is None for gp in grad_planes for g in gp):
+            return (None,) * 5 + (None,) * (8 * ctx.K)
+        views, outs, planes = [], [], []
         for k, (rs, g) in enumerate(zip(ctx.settings, grad_colors)):
-            saved = ctx.saved_tensors[10 * k:10 * k + 10]
+            saved = ctx.saved_tensors[n_saved * k:n_saved * k + 10]
+            planes.append((ctx.saved_tensors[n_saved * k + 10], *grad_planes[k]) if ctx.depth_alpha else None)
             if g is None:   # (a view nobody differentiated: its frame still runs with a zero image gradient)
                 g = torch.zeros((NUM_CHANNELS, rs.image_height, rs.image_width), dtype=torch.float32, device=saved[1].device)
             views.append(_backward_args(rs, saved, g, ctx.num_rendered[k]))
@@ -472,19 +516,21 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             # fresh tensor, which autograd adds)
             outs.append(ctx.grads[k].claim(accumulate=False)[0])
         res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=ctx.raw, wants=[fg.want for fg in ctx.grads],
-                                                 outs=outs, stats=ctx.stats)
-        return (None,) * 4 + tuple(t for grads in res for t in _input_grads(grads))
+                                                 outs=outs, stats=ctx.stats, planes=planes if ctx.depth_alpha else None)
+        return (None,) * 5 + tuple(t for grads in res for t in _input_grads(grads))
 
 
-def rasterize_views_autograd(settings, per_view_tensors, raw_activations=False, slots=None):
+def rasterize_views_autograd(settings, per_view_tensors, raw_activations=False, slots=None, depth_alpha=False):
     """K views through one launch chain, differentiable: `settings` a list of GaussianRasterizationSettings,
     `per_view_tensors` a list of (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp) with
-    empty tensors for what a view does not use.  Returns [(color, radii), ...]."""
+    empty tensors for what a view does not use.  Returns [(color, radii), ...], with `depth_alpha` (extension,
+    FR_FLAG_DEPTH_ALPHA) [(color, radii, depth [1,H,W], alpha [1,H,W]), ...] (both planes differentiable)."""
     K = len(settings)
     flat = [t for v in per_view_tensors for t in v]
     out = _RasterizeGaussiansBatch.apply(list(settings), bool(raw_activations), list(range(K)) if slots is None else list(slots),
-                                         _pick_forward_only(flat), *flat)
-    return [(out[2 * k], out[2 * k + 1]) for k in range(K)]
+                                         _pick_forward_only(flat), bool(depth_alpha), *flat)
+    n = 4 if depth_alpha else 2
+    return [tuple(out[n * k:n * k + n]) for k in range(K)]
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):
@@ -651,8 +697,9 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, raw_activations=False, forward_only=False):
+                raster_settings, raw_activations=False, forward_only=False, depth_alpha=False):
         rs = raster_settings
+        ctx.depth_alpha = bool(depth_alpha)
         ctx.raw = bool(raw_activations)
         ctx.fr_slot = _slot   # the backward goes through the handle the forward used
         # the gradient slot of the int32 `radii` output would otherwise be materialised as a zero tensor per backward
@@ -661,9 +708,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         # extension: the visibility mask (radii > 0) comes out of the preprocess kernel; render() picks it up from
         # `radii._fr_visible` instead of launching a compare kernel
         vis = torch.empty((means3D.shape[0],), dtype=torch.bool, device=means3D.device) if means3D.is_cuda else None
-        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _snapshot_on_error(
+        res = _snapshot_on_error(
             rs.debug, "snapshot_fw.dump", "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.",
-            rasterize_gaussians, args, _raw=ctx.raw, _visible=vis, _forward_only=forward_only)
+            rasterize_gaussians, args, _raw=ctx.raw, _visible=vis, _forward_only=forward_only, _depth_alpha=ctx.depth_alpha)
+        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = res[:6]
         if vis is not None and means3D.shape[0] > 0:
             radii._fr_visible = vis
         # extension: `means2D._fr_densification_stats = (xyz_gradient_accum, denom)` makes the backward kernel
@@ -673,28 +721,38 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.num_rendered = num_rendered
         ctx.grads = _FrameGrads.of_frame(ctx.raw, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer)
+                              binningBuffer, imgBuffer, *res[8:9])
         ctx.mark_non_differentiable(radii)
+        if ctx.depth_alpha:
+            return color, radii, res[6].unsqueeze(0), res[7].unsqueeze(0)
         return color, radii
 
     @staticmethod
-    def backward(ctx, grad_out_color, _):
+    def backward(ctx, grad_out_color, _, grad_depth=None, grad_alpha=None):
         rs = ctx.raster_settings
-        if grad_out_color is None:
-            return (None,) * 11
-        args = _backward_args(rs, ctx.saved_tensors, grad_out_color, ctx.num_rendered)
+        n_args = 12 if ctx.depth_alpha else 11   # (depth_alpha is passed only when it is set)
+        if grad_out_color is None and grad_depth is None and grad_alpha is None:
+            return (None,) * n_args
+        if grad_out_color is None:   # (only a plane is differentiated: the image's gradient is zero)
+            grad_out_color = torch.zeros((NUM_CHANNELS, rs.image_height, rs.image_width), dtype=torch.float32,
+                                         device=ctx.saved_tensors[1].device)
+        planes = (ctx.saved_tensors[10], grad_depth, grad_alpha) if ctx.depth_alpha else None
+        args = _backward_args(rs, ctx.saved_tensors[:10], grad_out_color, ctx.num_rendered)
         out, added = ({}, ()) if rs.debug else ctx.grads.claim()   # (debug mode claims no GradOut slot)
         with handle_slot(ctx.fr_slot):
             grads = _snapshot_on_error(
                 rs.debug, "snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n",
                 rasterize_gaussians_backward, args, _out=out, _raw=ctx.raw, _stats=ctx.stats, _want=ctx.grads.want,
-                _accumulate=added)
-        return _input_grads(grads, added) + (None, None, None)
+                _accumulate=added, _planes=planes)
+        return _input_grads(grads, added) + (None,) * (n_args - 8)
 
 
 def rasterize_gaussians_autograd(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                 raster_settings, raw_activations=False):
+                                 raster_settings, raw_activations=False, depth_alpha=False):
     forward_only = _pick_forward_only((means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp))
+    if depth_alpha:   # (extension, FR_FLAG_DEPTH_ALPHA: (color, radii, depth, alpha))
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, raster_settings, raw_activations, forward_only, True)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, raw_activations, forward_only)
 
@@ -727,9 +785,12 @@ class GaussianRasterizer(nn.Module):
             return mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, raw_activations=False):
+                cov3D_precomp=None, raw_activations=False, depth_alpha=False):
         """`raw_activations=True` (extension, not in the reference): opacities / scales / rotations are the RAW
-        parameters; sigmoid / exp / normalize and their derivatives run inside the HIP kernels."""
+        parameters; sigmoid / exp / normalize and their derivatives run inside the HIP kernels.  `depth_alpha=True`
+        (extension, FR_FLAG_DEPTH_ALPHA): returns (color, radii, depth [1,H,W], alpha [1,H,W]) — depth = sum of z alpha T
+        over the pixel's blended Gaussians (z: view-space depth; expected depth is depth / alpha), alpha = 1 - the final
+        transmittance — both differentiable."""
         rs = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -750,4 +811,4 @@ class GaussianRasterizer(nn.Module):
         if raw_activations and (scales is None or scales.numel() == 0):
             raise Exception('raw_activations needs the scale/rotation pair')
         return rasterize_gaussians_autograd(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                            cov3D_precomp, rs, raw_activations)
+                                            cov3D_precomp, rs, raw_activations, depth_alpha=depth_alpha)

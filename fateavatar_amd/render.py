@@ -59,31 +59,37 @@ def _activations(pc):
     return False, pc.get_opacity, pc.get_scaling, pc.get_rotation
 
 
-def _result(image, radii, screenspace_points) -> dict:
+def _result(image, radii, screenspace_points, planes=None) -> dict:
     visible = getattr(radii, "_fr_visible", None)  # written by the preprocess kernel (same values as radii > 0)
-    return {"render": image, "viewspace_points": screenspace_points,
-            "visibility_filter": visible if visible is not None else radii > 0, "radii": radii}
+    out = {"render": image, "viewspace_points": screenspace_points,
+           "visibility_filter": visible if visible is not None else radii > 0, "radii": radii}
+    if planes is not None:   # (extension: depth_alpha=True)
+        out["depth"], out["alpha"] = planes
+    return out
 
 
 def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, override_color: torch.Tensor = None,
-           device='cuda'):
+           device='cuda', depth_alpha=False):
+    """`depth_alpha=True` (extension): the dict also holds "depth" and "alpha" [1,H,W] — the alpha-weighted view-space depth
+    (sum of z alpha T; expected depth is depth / alpha) and the accumulated opacity 1 - T_final — both differentiable."""
     means3D = pc.get_xyz
     screenspace_points = _screenspace_points(means3D, pc)
     rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, pc, bg_color, scaling_modifier))
     fused, opacity, scales, rotations = _activations(pc)
     shs, colors_precomp = (pc.get_features, None) if override_color is None else (None, override_color)
-    rendered_image, radii = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
-                                       opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=None,
-                                       **({"raw_activations": True} if fused else {}))
-    return _result(rendered_image, radii, screenspace_points)
+    out = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+                     scales=scales, rotations=rotations, cov3D_precomp=None, **({"raw_activations": True} if fused else {}),
+                     **({"depth_alpha": True} if depth_alpha else {}))
+    return _result(out[0], out[1], screenspace_points, out[2:] if depth_alpha else None)
 
 
-def render_batch(viewpoint_cameras, pcs, bg_colors, scaling_modifier=1.0, slots=None):
+def render_batch(viewpoint_cameras, pcs, bg_colors, scaling_modifier=1.0, slots=None, depth_alpha=False):
     """`render()` for K views IN ONE LAUNCH CHAIN (include/fr_rasterizer.h: fr_forward_batch / fr_backward_batch): the
     reference renders the frames of a batch one after the other (model/fateavatar.py:251-276), and one frame's kernels
     leave most of an MI355X idle; here every kernel of the frame is launched once for all K views, with no stream or
     hardware-queue arrangement on the caller's side.  `pcs` / `bg_colors`: one per view, or a single holder / tensor
-    for all of them (shared Gaussians: autograd then sums the views' gradients).  Returns the list of render() dicts."""
+    for all of them (shared Gaussians: autograd then sums the views' gradients).  Returns the list of render() dicts (with
+    "depth" and "alpha" under `depth_alpha`, as render())."""
     K = len(viewpoint_cameras)
     if not isinstance(pcs, (list, tuple)):
         pcs = [pcs] * K
@@ -101,5 +107,5 @@ def render_batch(viewpoint_cameras, pcs, bg_colors, scaling_modifier=1.0, slots=
         settings.append(_settings(cam, pc, bg, scaling_modifier))
         tensors.append((means3D, sp, pc.get_features, empty, opacity, scales, rotations, empty))
         points.append(sp)
-    res = rasterize_views_autograd(settings, tensors, raw_activations=fused, slots=slots)
-    return [_result(image, radii, sp) for (image, radii), sp in zip(res, points)]
+    res = rasterize_views_autograd(settings, tensors, raw_activations=fused, slots=slots, depth_alpha=depth_alpha)
+    return [_result(r[0], r[1], sp, r[2:] if depth_alpha else None) for r, sp in zip(res, points)]

@@ -106,6 +106,21 @@ typedef struct fr_aux {
      * every backward call: frames that feed one optimizer step need ONE WORD EACH (fr_adam_config::skip takes up to
      * FR_ADAM_MAX_GRADS of them); the views of one fr_backward_batch call must not share a word. */
     float* overflow_out;
+    /* FR_FLAG_DEPTH_ALPHA only (appended: positional construction of the members above is unchanged; all unused without the
+     * flag).  fr_forward / fr_forward_batch out [H,W], both required under the flag: out_depth = sum over the pixel's blended
+     * Gaussians of z_i alpha_i T_i (z_i the view-space depth of the mean; 0 where nothing is blended), out_alpha = 1 - the final
+     * transmittance fr_image_final_T holds (0 where nothing is blended).  Expected depth is out_depth / out_alpha. */
+    float* out_depth;
+    float* out_alpha;
+    /* fr_backward / fr_backward_batch in [H,W]: the planes' upstream gradients.  Either may be NULL (zero); with both NULL the
+     * backward is the plain one.  dL/dz reaches dL_dmeans3D through row 2 of the view matrix (and from there fr_aux::binding
+     * and FR_FLAG_ACCUMULATE as every means3D gradient); dL_dmeans2D's z stays 0. */
+    const float* dL_ddepth;
+    const float* dL_dalpha;
+    /* fr_planes_bytes(capacity, W, H) bytes of caller-owned device scratch (capacity = the frame's binning capacity), required
+     * under the flag: the depth channel's share of the blend hand-off.  The forward fills it and the backward of the same frame
+     * reads it, like `binning`: hand the backward the same buffer. */
+    void* planes;
 } fr_aux;
 
 /* Frame parameters: the scalar arguments of Rasterizer::forward/backward. */
@@ -145,6 +160,19 @@ typedef struct fr_params {
  * handed the geometry or binning buffer of a forward-only frame return FR_ERR_INVALID_ARGUMENT and enqueue nothing.  A
  * forward-only frame leaves the handle as any frame does: a full forward + backward may follow it on the same handle. */
 #define FR_FLAG_FORWARD_ONLY 4
+
+/* A frame with per-pixel DEPTH and ALPHA planes next to the image (fr_aux::out_depth / out_alpha; the reference's rasterizer
+ * returns neither: silhouette / mask losses, compositing over anything, depth regularisers).  Honoured by fr_forward,
+ * fr_forward_batch, fr_backward and fr_backward_batch; combines with FR_FLAG_FORWARD_ONLY, FR_FLAG_RAW_ACTIVATIONS,
+ * FR_FLAG_NO_WAIT, FR_FLAG_ACCUMULATE and fr_aux::binding.  The image, radii, fr_aux::visible, final transmittance,
+ * contributor counts and bound means3D / rotations / scales are those of the same frame without the flag, bit for bit; the
+ * depth is blended as a fourth colour channel (colour z_i, background 0) with the colours' arithmetic.  Under the flag the
+ * forward needs fr_aux::out_depth, out_alpha and planes (FR_ERR_INVALID_ARGUMENT otherwise).  The backward takes the planes'
+ * gradients in fr_aux::dL_ddepth / dL_dalpha with the flag set (a plane gradient without the flag is FR_ERR_INVALID_ARGUMENT);
+ * handed the geometry or binning buffer of the handle's most recent forward while that forward had no planes, it returns
+ * FR_ERR_INVALID_ARGUMENT and enqueues nothing.  All views of a batch must agree on the flag.  Scratch sizes of frames without
+ * the flag are unchanged; a frame with it needs fr_planes_bytes() more. */
+#define FR_FLAG_DEPTH_ALPHA 8
 
 /* fr_backward only: FR_FLAG_ACCUMULATE(k) makes the k-th array of fr_grads (k = position of the pointer in the
  * struct: 0 = dL_dmeans2D ... 7 = dL_drotations) ACCUMULATE: the frame's gradient is added to what the array holds
@@ -213,6 +241,9 @@ int fr_profile_read(fr_handle* h, int32_t stage, double* total_ms, uint32_t* lau
 size_t fr_geometry_bytes(int32_t P);
 size_t fr_image_bytes(int32_t W, int32_t H);
 size_t fr_binning_bytes(uint64_t capacity, int32_t W, int32_t H);
+/* fr_aux::planes of a frame with FR_FLAG_DEPTH_ALPHA whose binning buffer holds `capacity` instances: 512 bytes per blend
+ * unit (capacity / 64 + tiles + 1 of them), plus alignment.  Regrow it with the binning buffer. */
+size_t fr_planes_bytes(uint64_t capacity, int32_t W, int32_t H);
 
 /* out_color [3,H,W], radii [P] (reference semantics: ceil(3*sigma_max), 0 if culled).
  * Returns FR_OK, or FR_ERR_BINNING_CAPACITY with counts->num_instances = capacity required
