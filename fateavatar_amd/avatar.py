@@ -399,7 +399,7 @@ class AvatarStep(TrainStep):
         # 'optimizer' and 'densification' are additions a seamless resume needs; the reference saves neither
         return {"global_step": self.adam.step_count, "model": model,
                 "optimizer": {"exp_avg": self.adam.exp_avg.clone(), "exp_avg_sq": self.adam.exp_avg_sq.clone(),
-                              "state": self.adam.state[:4].clone()},
+                              "state": self.adam.state_words()},
                 "densification": {"xyz_gradient_accum": self.xyz_gradient_accum.clone(), "denom": self.denom.clone()}}
 
     @torch.no_grad()
@@ -428,8 +428,7 @@ class AvatarStep(TrainStep):
         if opt is not None:
             self.adam.exp_avg.copy_(opt["exp_avg"])
             self.adam.exp_avg_sq.copy_(opt["exp_avg_sq"])
-            self.adam.state.zero_()
-            self.adam.state[:4].copy_(opt["state"][:4])
+            self.adam.load_state_words(opt["state"])
         self.host_steps = self.adam.step_count          # (skipped_steps counts from the restored state on)
         if dens is not None:
             self.xyz_gradient_accum.copy_(dens["xyz_gradient_accum"])

@@ -439,6 +439,7 @@ int fr_adam_step(const fr_adam_config* cfg, float* param, const float* grad, flo
     if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
          reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
         return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step: arrays must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(state) & 7) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step: state must be 8-byte aligned");
     const float* one[1] = {grad};
     return launch_adam(*cfg, param, one, 1, exp_avg, exp_avg_sq, n, state, static_cast<hipStream_t>(stream));
 }
@@ -462,6 +463,7 @@ int fr_adam_step_multi(const fr_adam_config* cfg, float* param, const float* con
     if (prev != n) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: the last segment must end at n");
     if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
         return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: arrays must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(state) & 7) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: state must be 8-byte aligned");
     return launch_adam(*cfg, param, grads, n_grads, exp_avg, exp_avg_sq, n, state, static_cast<hipStream_t>(stream));
 }
 

@@ -32,15 +32,21 @@ struct AdamArgs {
     unsigned seg_period[FR_ADAM_MAX_SEGMENTS], seg_split[FR_ADAM_MAX_SEGMENTS];
     float seg_lr2[FR_ADAM_MAX_SEGMENTS];
     float beta1, beta2, omb1, omb2, eps, grad_scale;  // omb = 1 - beta, rounded from double
+    double beta1_d, beta2_d, omb1_d, omb2_d;          // the same, unrounded: the bias corrections are carried in double
     int n_skip;                                        // fr_adam_config::skip: any non-zero word -> the step does nothing
     const float* skip[FR_ADAM_MAX_GRADS];
 };
 
-// state = {step, 1 - beta1^step, 1 - beta2^step, -, ..., done-counters from word 32}: advanced on the device so that the host passes
-// nothing that changes from step to step (graph replay).  The bias corrections c_t = 1 - beta^t are carried by the recurrence
-// c_{t+1} = (1 - beta) + beta c_t (all terms positive: no cancellation; 1 - 0.999f alone is off by 1.3e-5).  Every
-// workgroup of k_adam derives this step's corrections from the OLD state; the workgroup that finishes last
-// (last_workgroup) stores the new one — no launch of its own for three floats.
+// state = {step, 1 - beta1^step, 1 - beta2^step, -, the two corrections as doubles in words 4..7, ..., done-counters from
+// word 32}: advanced on the device so that the host passes nothing that changes from step to step (graph replay).  The
+// bias corrections c_t = 1 - beta^t are carried by the recurrence c_{t+1} = (1 - beta) + beta c_t.  All its terms are
+// positive, so no single step cancels, but every step rounds, and the map contracts errors only by beta per step: in
+// float32 with beta = 0.999f about a thousand roundings stay alive, the sequence is off by 40 x 2^-24 at step 1000, and
+// it stops moving at 0.99997020 instead of reaching 1 (every later update 1.5e-5 too large).  So the recurrence runs in
+// DOUBLE, with beta and 1 - beta as the doubles the configuration holds (1 - 0.999f alone is off by 1.3e-5): accumulated
+// error at most 2^-53 / (1 - beta) = 1.1e-13 at any step count, far inside the float32 rounding of the value the update uses.  Words 1 and 2 keep
+// the corrections rounded to float for readers of the state.  Every workgroup of k_adam derives this step's corrections
+// from the OLD state; the workgroup that finishes last (last_workgroup) stores the new one — no launch of its own.
 __device__ __forceinline__ float adam_one(float& p, float g, float& m, float& v, float lr_over_bc1, float inv_sqrt_bc2,
                                           const AdamArgs& a)
 {
@@ -81,7 +87,9 @@ __global__ void __launch_bounds__(256) k_adam(AdamArgs a, float4* __restrict__ p
     for (int k = 0; k < a.n_skip; k++)
         if (a.skip[k][0] != 0.0f) return;
     const float step_new = state[0] + 1.0f;
-    const float bc1 = a.omb1 + a.beta1 * state[1], bc2 = a.omb2 + a.beta2 * state[2];
+    const double* const carried = reinterpret_cast<const double*>(state + 4);   // (8-byte aligned: fr_adam_step checks)
+    const double bc1_d = a.omb1_d + a.beta1_d * carried[0], bc2_d = a.omb2_d + a.beta2_d * carried[1];
+    const float bc1 = (float)bc1_d, bc2 = (float)bc2_d;
     const float inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
     const unsigned long long n4 = n / 4, stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n + 3) / 4; i += stride) {
@@ -121,7 +129,10 @@ __global__ void __launch_bounds__(256) k_adam(AdamArgs a, float4* __restrict__ p
     // knows that all have
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (last_workgroup(reinterpret_cast<unsigned*>(state + 32))) state[0] = step_new, state[1] = bc1, state[2] = bc2;
+        if (last_workgroup(reinterpret_cast<unsigned*>(state + 32))) {
+            double* const carry = reinterpret_cast<double*>(state + 4);
+            state[0] = step_new, state[1] = bc1, state[2] = bc2, carry[0] = bc1_d, carry[1] = bc2_d;
+        }
     }
 }
 
@@ -143,6 +154,7 @@ int launch_adam(const fr_adam_config& cfg, float* param, const float* const* gra
     }
     a.beta1 = (float)cfg.beta1, a.beta2 = (float)cfg.beta2, a.eps = (float)cfg.eps, a.grad_scale = cfg.grad_scale;
     a.omb1 = (float)(1.0 - cfg.beta1), a.omb2 = (float)(1.0 - cfg.beta2);
+    a.beta1_d = cfg.beta1, a.beta2_d = cfg.beta2, a.omb1_d = 1.0 - cfg.beta1, a.omb2_d = 1.0 - cfg.beta2;
     a.n_skip = cfg.n_skip < 0 ? 0 : (cfg.n_skip > FR_ADAM_MAX_GRADS ? FR_ADAM_MAX_GRADS : cfg.n_skip);
     for (int k = 0; k < FR_ADAM_MAX_GRADS; k++) a.skip[k] = k < a.n_skip ? cfg.skip[k] : nullptr;
     const unsigned long long quads = (n + 3) / 4;

@@ -34,7 +34,8 @@ class FusedAdam:
         self.param, self.grad = flat_param, flat_grad
         self.exp_avg = torch.zeros_like(flat_param)
         self.exp_avg_sq = torch.zeros_like(flat_param)
-        # step, 1 - beta1^t, 1 - beta2^t, -, kernel bookkeeping (FR_ADAM_STATE_FLOATS)
+        # step, 1 - beta1^t, 1 - beta2^t, -, the two corrections as doubles (words 4..7), kernel bookkeeping
+        # (FR_ADAM_STATE_FLOATS)
         self.state = torch.zeros(_lib.FR_ADAM_STATE_FLOATS, dtype=torch.float32, device=flat_param.device)
         cfg = _lib.fr_adam_config()
         cfg.n_segments = len(segments)
@@ -134,6 +135,26 @@ class FusedAdam:
                                                    self.state.data_ptr(), stream)
         if rc != _lib.FR_OK:
             raise RuntimeError(f"fr_adam_step failed: {_lib.last_error()}")
+
+    STATE_WORDS = 8   # what a checkpoint has to carry: the step, the float corrections and the doubles behind them
+
+    def state_words(self) -> torch.Tensor:
+        """The part of the device state a resume needs (a copy): hand it to `load_state_words`."""
+        return self.state[:self.STATE_WORDS].clone()
+
+    @torch.no_grad()
+    def load_state_words(self, words: torch.Tensor) -> None:
+        """Restore what `state_words` returned.  A state of four words (written before the corrections were carried as
+        doubles) holds only their float roundings: the doubles are then rebuilt from the step count, 1 - beta^t."""
+        words = words.detach().to("cpu", torch.float32).reshape(-1)
+        self.state.zero_()
+        if words.numel() >= self.STATE_WORDS:
+            self.state[:self.STATE_WORDS].copy_(words[:self.STATE_WORDS])
+            return
+        t = int(words[0].item())
+        carried = torch.tensor([1.0 - float(b) ** t for b in (self.cfg.beta1, self.cfg.beta2)], dtype=torch.float64)
+        self.state[:words.numel()].copy_(words)
+        self.state[4:self.STATE_WORDS].copy_(carried.view(torch.float32))
 
     @property
     def step_count(self) -> int:

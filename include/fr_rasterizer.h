@@ -283,9 +283,10 @@ int fr_backward_batch(int32_t n_views, fr_handle* const* handles, const fr_param
  * Gaussian parameter groups of train/optim.py:11-37: betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad).
  * The buffer is cut into up to FR_ADAM_MAX_SEGMENTS consecutive segments, each with its own learning rate (the
  * reference's param groups); param / grad / exp_avg / exp_avg_sq are device arrays of n floats with the same
- * layout.  `state` is a device array of FR_ADAM_STATE_FLOATS floats owned by the caller, zero-initialised once: {step,
- * 1 - beta1^step, 1 - beta2^step, unused, ..., kernel bookkeeping from word 32 on that is zero between calls}; every call
- * advances it on the device (so the call is hipGraph-capturable: nothing step-dependent is a kernel argument) and applies
+ * layout.  `state` is a device array of FR_ADAM_STATE_FLOATS floats owned by the caller, 8-byte aligned, zero-initialised
+ * once: {step, 1 - beta1^step, 1 - beta2^step, unused, the same two corrections as DOUBLES in words 4..7 (the values the
+ * kernel carries forward: save and restore words 0..7 together), ..., kernel bookkeeping from word 32 on that is zero
+ * between calls}; every call advances it on the device (so the call is hipGraph-capturable: nothing step-dependent is a kernel argument) and applies
  *   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
  * with g = grad_scale * grad (grad_scale: e.g. 1/world_size after a SUM all-reduce). */
 #define FR_ADAM_MAX_SEGMENTS 16

@@ -41,6 +41,7 @@ def lib():
                                    C.c_float, fp, fp, fp, fp, fp, C.c_float, C.c_float, C.POINTER(C.c_int), fp] + [fp] * 9
         L.fro_mark_visible.argtypes = [C.c_int, fp, fp, fp, C.POINTER(C.c_uint8)]
         L.fro_knn_mean_dist2.argtypes = [C.c_int, fp, fp]
+        L.fro_knn_dist2.argtypes = [C.c_int, fp, fp, fp]
         L.fro_num_rendered.argtypes = [C.c_void_p]
         L.fro_num_rendered.restype = C.c_int
         L.fro_eval_sh.argtypes = [C.c_int, C.c_int, fp, fp, fp, fp, C.POINTER(C.c_uint8)]
@@ -200,6 +201,17 @@ def knn_mean_dist2(points) -> np.ndarray:
     if P:
         lib().fro_knn_mean_dist2(P, _p(pts), _p(out))
     return out
+
+
+def knn_dist2(points):
+    """(mean of the three smallest squared distances, the smallest one) from ONE search: `knn_mean_dist2` and the
+    reference for `fateavatar_amd.knn.nearest_dist2`."""
+    pts = _f32(points)
+    P = pts.shape[0]
+    mean, nearest = np.zeros((P,), np.float32), np.zeros((P,), np.float32)
+    if P:
+        lib().fro_knn_dist2(P, _p(pts), _p(mean), _p(nearest))
+    return mean, nearest
 
 
 def num_threads() -> int:

@@ -353,6 +353,70 @@ def test_mark_visible(gpu_device):
     assert 0 < ref.sum() < s.P
 
 
+def _mark_visible_both(pts, view, proj, dev):
+    import torch
+    from fateavatar_amd import rasterizer
+    from oracle import oracle
+    got = rasterizer.mark_visible(torch.from_numpy(pts).to(dev), torch.from_numpy(view).to(dev), torch.from_numpy(proj).to(dev))
+    return got.cpu().numpy(), oracle.mark_visible(pts, view, proj)
+
+
+def test_mark_visible_at_the_near_threshold(gpu_device):
+    """View-space z exactly 0.2f (NOT visible: the test is z <= 0.2f), its float neighbours on both sides, zero and
+    negative, under a view matrix that passes z through unchanged; P = 1, 255, 257 and 1 000 003 (workgroups of 256)."""
+    f = np.float32
+    near = f(0.2)
+    special = np.array([near, np.nextafter(near, f(1)), np.nextafter(near, f(0)), 0.0, -0.0, -near, -5.0, 0.25, 1e-30, 3e38], f)
+    want_special = np.array([False, True, False, False, False, False, False, True, False, True])
+    eye = np.eye(4, dtype=f)
+    rng = np.random.default_rng(8)
+    for P in (1, 255, 257, 1_000_003):
+        pts = rng.normal(size=(P, 3)).astype(f)
+        pts[:, 2] = special[(np.arange(P) + P) % len(special)]
+        pts[-1, 2] = near                                      # the last element of the last, partial workgroup
+        got, ref = _mark_visible_both(pts, eye, eye, gpu_device)
+        want = want_special[(np.arange(P) + P) % len(special)]
+        want[-1] = False
+        np.testing.assert_array_equal(ref, want)
+        np.testing.assert_array_equal(got, want)
+    # x and y do not matter, however large
+    pts = np.array([[1e30, -1e30, np.nextafter(near, f(1))], [-1e30, 1e30, near]], f)
+    got, ref = _mark_visible_both(pts, eye, eye, gpu_device)
+    assert got.tolist() == ref.tolist() == [True, False]
+
+
+def test_mark_visible_general_camera_large_and_strided(gpu_device):
+    """A general (orbiting) camera: a cloud around the head plus a thin slab around the plane z_view = 0.2, so that many
+    points lie within a few ulp of the threshold; P not a multiple of 256; a non-contiguous input."""
+    import torch
+    from fateavatar_amd import rasterizer
+    from oracle import oracle
+    s = scenes.head_scene(P=1000, res=64, sh_degree=0, seed=1, view=1, n_views=4)
+    c = s.camera
+    view = c.world_view_transform
+    rng = np.random.default_rng(9)
+    P = 200_003
+    cloud = (s.means3D.mean(0) + rng.normal(size=(P // 2, 3))).astype(np.float32)
+    # world points whose view-space z is 0.2 +- 2e-6: p = (q - t) R^-1 for view-space q (row-vector convention)
+    q = np.concatenate([rng.uniform(-1, 1, (P - P // 2, 2)), 0.2 + rng.uniform(-2e-6, 2e-6, (P - P // 2, 1))], axis=1)
+    R, t = view[:3, :3].astype(np.float64), view[3, :3].astype(np.float64)
+    slab = ((q - t) @ np.linalg.inv(R)).astype(np.float32)
+    pts = np.ascontiguousarray(np.concatenate([cloud, slab])[rng.permutation(P)])
+    got, ref = _mark_visible_both(pts, view, c.full_proj_transform, gpu_device)
+    np.testing.assert_array_equal(got, ref)
+    z = pts.astype(np.float64) @ R[:, 2] + t[2]
+    near = np.abs(z - 0.2) < 3e-6                     # (the slab really straddles the threshold)
+    assert 0 < ref.sum() < P and near.sum() > P // 3 and 0.3 < ref[near].mean() < 0.7
+    # non-contiguous: every second row of a wider array
+    wide = torch.zeros((2 * P, 5), device=gpu_device)
+    wide[::2, 1:4] = torch.from_numpy(pts).to(gpu_device)
+    strided = wide[::2, 1:4]
+    assert not strided.is_contiguous()
+    got2 = rasterizer.mark_visible(strided, torch.from_numpy(view).to(gpu_device),
+                                   torch.from_numpy(c.full_proj_transform).to(gpu_device)).cpu().numpy()
+    np.testing.assert_array_equal(got2, ref)
+
+
 def test_reduce_scatter_selftest(gpu_device):
     """The 36-value wave reduce-scatter of the blend backward, in isolation."""
     import torch

@@ -115,6 +115,109 @@ def test_scaled_sum(gpu_device):
         scaled_sum(dst, [srcs[0][:10]], 1.0)
 
 
+POISON = -12345.5
+
+
+def _guarded(count, offset_words, dev):
+    """A destination of `count` floats inside a larger poisoned buffer, `offset_words` floats past a 16-byte boundary."""
+    front = 64 + offset_words
+    whole = torch.full((front + count + 67,), POISON, device=dev)
+    assert whole.data_ptr() % 16 == 0
+    return whole, whole[front:front + count]
+
+
+def _source(count, offset_words, rng, dev):
+    whole = torch.from_numpy(rng.standard_normal(64 + offset_words + count).astype(np.float32)).to(dev)
+    return whole[64 + offset_words:]
+
+
+COPY_COUNTS = [0, 1, 2, 3, 5, 4096, 0, 2048 * 256 * 4 + 4099, 4, 0, 1001, 600_001]
+
+
+@pytest.mark.parametrize("misaligned", ["neither", "source", "destination", "both", "mixed"])
+def test_multi_copy_twelve_segments_inside_guard_words(gpu_device, misaligned):
+    """All 12 segments of one launch (through the C ABI, so that EMPTY segments between full ones reach the kernel): counts
+    0, 1, 2, 3, 5, 4 096, one above what the launch's grid covers in one trip (2 048 x 256 float4) and one above it on
+    the scalar path; source misaligned only, destination only, both, and a different misalignment per segment.  Every
+    destination sits inside a larger poisoned buffer whose other words are untouched afterwards."""
+    import ctypes as C
+    from fateavatar_amd import _lib
+    assert len(COPY_COUNTS) == 12 and max(COPY_COUNTS) > 2048 * 256 * 4
+    rng = np.random.default_rng(len(misaligned))
+    offs = {"neither": lambda i: (0, 0), "source": lambda i: (1 + i % 3, 0), "destination": lambda i: (0, 1 + i % 3),
+            "both": lambda i: (1 + i % 3, 1 + (i + 1) % 3), "mixed": lambda i: (i % 4, (i // 4 + i) % 4)}[misaligned]
+    srcs, wholes, dsts = [], [], []
+    for i, n in enumerate(COPY_COUNTS):
+        so, do = offs(i)
+        srcs.append(_source(n, so, rng, gpu_device))
+        w, d = _guarded(n, do, gpu_device)
+        wholes.append(w), dsts.append(d)
+        assert n == 0 or (srcs[-1].data_ptr() % 16 == 4 * so and d.data_ptr() % 16 == 4 * do)
+    k = len(COPY_COUNTS)
+    rc = _lib.lib().fr_multi_copy(k, (C.c_void_p * k)(*[d.data_ptr() for d in dsts]), (C.c_void_p * k)(*[s_.data_ptr() for s_ in srcs]),
+                                  (C.c_uint64 * k)(*COPY_COUNTS), torch.cuda.current_stream(gpu_device).cuda_stream)
+    assert rc == _lib.FR_OK, _lib.last_error()
+    torch.cuda.synchronize()
+    for i, (n, s_, w, d) in enumerate(zip(COPY_COUNTS, srcs, wholes, dsts)):
+        assert torch.equal(d, s_), (i, n)
+        front = w.numel() - n - 67
+        assert bool((w[:front] == POISON).all()) and bool((w[front + n:] == POISON).all()), (i, n)
+    # the same through multi_copy() (which drops the empty pairs itself), into fresh destinations
+    again = [_guarded(n, offs(i)[1], gpu_device) for i, n in enumerate(COPY_COUNTS)]
+    from fateavatar_amd.loss import multi_copy
+    multi_copy([(d, s_) for (_, d), s_ in zip(again, srcs)])
+    for i, (n, s_, (w, d)) in enumerate(zip(COPY_COUNTS, srcs, again)):
+        assert torch.equal(d, s_), (i, n)
+        front = w.numel() - n - 67
+        assert bool((w[:front] == POISON).all()) and bool((w[front + n:] == POISON).all()), (i, n)
+
+
+def test_multi_copy_refuses_thirteen_segments(gpu_device):
+    import ctypes as C
+    from fateavatar_amd import _lib
+    from fateavatar_amd.loss import multi_copy
+    src = [torch.ones(8, device=gpu_device) for _ in range(13)]
+    dst = [torch.zeros(8, device=gpu_device) for _ in range(13)]
+    with pytest.raises(RuntimeError, match="twelve"):
+        multi_copy(list(zip(dst, src)))
+    rc = _lib.lib().fr_multi_copy(13, (C.c_void_p * 13)(*[d.data_ptr() for d in dst]), (C.c_void_p * 13)(*[s_.data_ptr() for s_ in src]),
+                                  (C.c_uint64 * 13)(*[8] * 13), torch.cuda.current_stream(gpu_device).cuda_stream)
+    assert rc != _lib.FR_OK
+    torch.cuda.synchronize()
+    assert all(float(d.abs().max()) == 0.0 for d in dst)
+    multi_copy(list(zip(dst[:12], src[:12])))
+    assert all(torch.equal(d, s_) for d, s_ in zip(dst[:12], src[:12])) and float(dst[12].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 5, 4096 * 256 * 4 + 4099])
+def test_scaled_sum_small_counts_the_grid_stride_loop_and_in_place(gpu_device, n):
+    """Counts 1, 2, 3, 5 (scalar tail only) and one above what the launch's grid covers in one trip (4 096 x 256 float4),
+    K = 1 .. 4, and in place with dst being each of the sources in turn.  Expected: the float32 expression in the
+    kernel's order, bit for bit; the words behind dst stay as they were."""
+    from fateavatar_amd.loss import scaled_sum
+    g = torch.Generator().manual_seed(n % 1000)
+    srcs = [torch.randn(n, generator=g).to(gpu_device) * (10.0 ** (k - 1)) for k in range(4)]
+
+    def expected(ts, scale):
+        want = ts[0].clone()
+        for t in ts[1:]:
+            want = want + t
+        return want * scale
+
+    for K in (1, 2, 3, 4):
+        scale = 1.0 / K
+        whole = torch.full((n + 64,), POISON, device=gpu_device)
+        scaled_sum(whole[:n], srcs[:K], scale)
+        assert torch.equal(whole[:n], expected(srcs[:K], scale)) and bool((whole[n:] == POISON).all()), K
+        for j in range(K):                              # dst is source j
+            work = [t.clone() for t in srcs[:K]]
+            want = expected(work, scale)
+            scaled_sum(work[j], work, scale)
+            assert torch.equal(work[j], want), (K, j)
+            for i in range(K):
+                assert i == j or torch.equal(work[i], srcs[i])
+
+
 def test_concurrent_streams_overlap(gpu_device):
     """fateavatar_amd.streams: the runtime maps streams onto a few hardware queues; streams on one queue are serialised.
     concurrent_streams() returns streams that overlap pairwise and with the caller's stream."""

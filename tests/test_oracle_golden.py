@@ -126,3 +126,23 @@ def test_knn_oracle_is_exact():
     d2.sort(axis=1)
     ref = ((d2[:, 0] + d2[:, 1]) + d2[:, 2]) / np.float32(3.0)
     np.testing.assert_array_equal(got, ref.astype(np.float32))
+
+
+def test_knn_oracle_equals_float32_brute_force_on_awkward_point_sets():
+    """The oracle's Morton-pruned search == plain float32 brute force with the reference's expressions, bit for bit, mean
+    and nearest, on every point set the GPU k-NN tests use with P <= 6000: P = 1, 2 (inf) and 3 (FLT_MAX / 3), exact
+    duplicates, a plane, a line, a lattice full of ties, far-offset, all-negative, clustered.  This pins the oracle as
+    the reference for the point sets that are too large for brute force."""
+    from tests import util
+    sets = util.knn_point_sets()
+    assert len(sets) >= 12
+    for name, pts in sets.items():
+        assert pts.dtype == np.float32 and pts.shape[0] <= 6000
+        mean, nearest = oracle.knn_dist2(pts)
+        want_mean, want_nearest = util.knn_brute_force(pts)
+        np.testing.assert_array_equal(mean, want_mean, err_msg=name)
+        np.testing.assert_array_equal(nearest, want_nearest, err_msg=name)
+        np.testing.assert_array_equal(oracle.knn_mean_dist2(pts), want_mean, err_msg=name)
+    assert np.all(np.isinf(oracle.knn_mean_dist2(sets["normal_2"]))) and np.isinf(oracle.knn_mean_dist2(sets["normal_1"])[0])
+    assert abs(float(oracle.knn_mean_dist2(sets["normal_3"])[0]) / 1.1342e38 - 1) < 1e-3
+    assert float(oracle.knn_dist2(sets["one_point_300_times"])[0].max()) == 0.0

@@ -322,3 +322,54 @@ def fuzz_inputs(seed, k, s):
     if r.random() < 0.5:
         extra["scale_modifier"] = float(r.uniform(0.4, 1.6))
     return extra
+
+
+# ------------------------------------------------------------------ k-NN: brute force and the awkward point sets
+FLT_MAX = np.float32(np.finfo(np.float32).max)
+
+
+def knn_brute_force(pts):
+    """(mean of the three smallest squared distances to the OTHER points, the smallest one) by plain float32 brute force,
+    with the reference's expressions (simple_knn.cu:131-184): `(dx*dx + dy*dy) + dz*dz`, three smallest b0 <= b1 <= b2 out
+    of a list that starts at FLT_MAX, `((b0 + b1) + b2) / 3`.  P <= 2 gives inf (FLT_MAX + FLT_MAX), P = 3 gives
+    FLT_MAX / 3.  Exact duplicates are other points, at distance 0.  O(P^2): meant for P <= 6000."""
+    pts = np.ascontiguousarray(pts, np.float32)
+    P = pts.shape[0]
+    mean, nearest = np.empty((P,), np.float32), np.empty((P,), np.float32)
+    rows = max(1, (1 << 22) // max(P, 1))
+    for b in range(0, P, rows):
+        d = pts[b:b + rows, None, :] - pts[None, :, :]
+        d = d * d
+        d2 = (d[..., 0] + d[..., 1]) + d[..., 2]
+        assert d2.dtype == np.float32
+        d2[np.arange(d2.shape[0]), np.arange(b, b + d2.shape[0])] = FLT_MAX          # not itself
+        d2 = np.concatenate([d2, np.full((d2.shape[0], 3), FLT_MAX, np.float32)], axis=1)
+        best = np.sort(np.partition(d2, 2, axis=1)[:, :3], axis=1)
+        with np.errstate(over="ignore"):
+            mean[b:b + rows] = ((best[:, 0] + best[:, 1]) + best[:, 2]) / np.float32(3.0)
+        nearest[b:b + rows] = best[:, 0]
+    return mean, nearest
+
+
+def knn_point_sets():
+    """name -> [P,3] float32: the sizes around one workgroup and the geometry that decides how many grid shells a search
+    walks and where it stops (the grid is a cube sized by the longest axis).  The last two put thousands of points into
+    ONE cell, P^2 distance evaluations: they stay at these sizes."""
+    rng = np.random.default_rng(11)
+    f = np.float32
+    sets = {f"normal_{P}": rng.normal(size=(P, 3)).astype(f) for P in (1, 2, 3, 4, 255, 256, 257)}
+    sets["one_point_300_times"] = np.repeat(rng.normal(size=(1, 3)).astype(f), 300, axis=0)
+    plane = rng.uniform(-1, 1, (4000, 3)).astype(f)
+    plane[:, 2] = 0
+    sets["plane_z0"] = plane
+    line = np.zeros((2000, 3), f)
+    line[:, 0] = rng.uniform(-3, 3, 2000).astype(f)
+    sets["line_x"] = line
+    sets["lattice_18"] = np.stack(np.meshgrid(*[np.arange(18)] * 3, indexing="ij"), -1).reshape(-1, 3).astype(f)
+    sets["far_offset"] = (1000.0 + 1e-3 * rng.normal(size=(5000, 3))).astype(f)
+    sets["all_negative"] = (-rng.uniform(1, 4, (5000, 3))).astype(f)
+    two = 1e-3 * rng.normal(size=(6000, 3))
+    two[3000:, 0] += 5.0
+    sets["two_clusters"] = two.astype(f)
+    sets["one_outlier"] = np.concatenate([rng.normal(size=(3000, 3)), [[1e4, 1e4, 1e4]]]).astype(f)
+    return sets
