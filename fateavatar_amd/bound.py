@@ -18,8 +18,8 @@ import torch
 
 from . import _lib
 from .binding import _chk, _desc
-from .rasterizer import (NUM_CHANNELS, _backward_args, _forward_args, _FrameGrads, _pick_forward_only,
-                         rasterize_gaussians_backward_batch, rasterize_gaussians_batch)
+from .rasterizer import (_GRAD_NAMES, _any_grad, _backward_args, _forward_args, _forward_batch, _FrameGrads, _per_view_outputs,
+                         _pick_forward_only, _SavedFrame, rasterize_gaussians_backward_batch)
 from .render import _result, _screenspace_points, _settings
 
 
@@ -36,21 +36,19 @@ class MeshBinding(NamedTuple):
 
 class _RasterizeBoundBatch(torch.autograd.Function):
     """Tensor arguments per view: (verts, offset, rotation, scaling, means2D, sh, opacities) — the RAW parameters, as
-    render() hands them over with `fused_activations`.  Outputs per view: (color, radii), with `depth_alpha` (color, radii,
-    depth [1,H,W], alpha [1,H,W])."""
+    render() hands them over with `fused_activations`.  Outputs per view: those of `_SavedFrame`."""
     PER_VIEW = 7
 
     @staticmethod
     def forward(ctx, settings, bindings, slots, forward_only, depth_alpha, *tensors):
         K, n = len(settings), _RasterizeBoundBatch.PER_VIEW
         assert len(tensors) == n * K and len(bindings) == K
-        ctx.K, ctx.settings, ctx.bindings, ctx.slots = K, settings, bindings, slots
-        ctx.depth_alpha = bool(depth_alpha)
-        ctx.set_materialize_grads(False)
+        ctx.bindings, ctx.slots, ctx.offset_shapes = bindings, slots, []
         empty = torch.Tensor([])
         views, viss, descs, bound, checked = [], [], [], [], []
         for k, (rs, mb) in enumerate(zip(settings, bindings)):
             verts, offset, rotation, scaling, means2D, sh, opacities = tensors[n * k:n * k + n]
+            ctx.offset_shapes.append(tuple(offset.shape))
             verts, offset = _chk(verts, torch.float32, "verts"), _chk(offset, torch.float32, "offset")
             rotation, scaling = _chk(rotation, torch.float32, "rotation"), _chk(scaling, torch.float32, "scaling")
             checked.append((verts, offset, rotation, scaling))   # (what the descriptor points at: alive until the launch, saved for the backward)
@@ -69,51 +67,29 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             bound.append((xyz, rot, scl))
             views.append(_forward_args(rs, xyz, means2D, sh, empty, opacities, scl, rot, empty))
             viss.append(torch.empty((N,), dtype=torch.bool, device=dev))
-        res = rasterize_gaussians_batch(views, slots=slots, raw=True, visibles=viss, bindings=descs, forward_only=forward_only,
-                                        depth_alpha=ctx.depth_alpha)
-        ctx.stats, ctx.num_rendered, ctx.grads, ctx.offset_shapes = [], [], [], []
-        saved, outs = [], []
-        for k in range(K):
+        res = _forward_batch(views, slots, True, viss, descs, forward_only, depth_alpha)
+        frames = []
+        for k, rs in enumerate(settings):
             verts, offset, rotation, scaling, means2D, sh, opacities = tensors[n * k:n * k + n]
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = res[k][:6]
-            radii._fr_visible = viss[k]
-            radii._fr_bound = bound[k]           # (xyz, rotation, scaling) as bind_gaussians returns them
-            ctx.stats.append(getattr(means2D, "_fr_densification_stats", None))
-            ctx.num_rendered.append(num_rendered)
-            ctx.offset_shapes.append(tuple(offset.shape))
-            ctx.grads.append(_FrameGrads({"dL_dsh": sh if sh.numel() else None, "dL_dopacity": opacities, "d_offset": offset,
-                                          "d_rotation": rotation, "d_scaling": scaling}, sh, bound=True))
-            saved += [*checked[k], sh, radii, geomBuffer, binningBuffer, imgBuffer, *bound[k]]
-            outs += [color, radii]
-            if ctx.depth_alpha:
-                saved.append(res[k][8])
-                outs += [res[k][6].unsqueeze(0), res[k][7].unsqueeze(0)]
-        ctx.save_for_backward(*saved)
-        n_out = 4 if ctx.depth_alpha else 2
-        ctx.mark_non_differentiable(*outs[1::n_out])
-        return tuple(outs)
+            grads = _FrameGrads({"dL_dsh": sh if sh.numel() else None, "dL_dopacity": opacities, "d_offset": offset,
+                                 "d_rotation": rotation, "d_scaling": scaling}, sh, bound=True)
+            frames.append(_SavedFrame(rs, res[k], viss[k], means2D, grads, (*checked[k], sh, *bound[k])))
+            res[k].radii._fr_bound = bound[k]           # (xyz, rotation, scaling) as bind_gaussians returns them
+        return _SavedFrame.save(ctx, frames)
 
     @staticmethod
     def backward(ctx, *grad_outs):
-        K, n = ctx.K, _RasterizeBoundBatch.PER_VIEW
-        n_out, n_saved = (4, 13) if ctx.depth_alpha else (2, 12)
-        grad_colors = grad_outs[0::n_out]
-        grad_planes = [grad_outs[n_out * k + 2:n_out * k + 4] for k in range(K)] if ctx.depth_alpha else [(None, None)] * K
-        if all(g is None for g in grad_colors) and all(g is None for gp in grad_planes for g in gp):
-            return (None,) * 5 + (None,) * (n * K)
+        K, n = len(ctx.frames), _RasterizeBoundBatch.PER_VIEW
+        if not _any_grad(grad_outs):
+            return (None,) * (5 + n * K)
         empty = torch.Tensor([])
         views, outs, descs, bgrads, planes = [], [], [], [], []
-        for k, (rs, mb) in enumerate(zip(ctx.settings, ctx.bindings)):
-            verts, offset, rotation, scaling, sh, radii, geomBuffer, binningBuffer, imgBuffer, xyz, rot, scl = \
-                ctx.saved_tensors[n_saved * k:n_saved * k + 12]
-            planes.append((ctx.saved_tensors[n_saved * k + 12], *grad_planes[k]) if ctx.depth_alpha else None)
+        for k, (f, own, fw, g, pl) in enumerate(_SavedFrame.load(ctx, grad_outs)):
+            (verts, offset, rotation, scaling, sh, xyz, rot, scl), mb = own, ctx.bindings[k]
             dev, N = verts.device, xyz.shape[0]
-            g = grad_colors[k]
-            if g is None:
-                g = torch.zeros((NUM_CHANNELS, rs.image_height, rs.image_width), dtype=torch.float32, device=dev)
-            views.append(_backward_args(rs, (empty, xyz, scl, rot, empty, radii, sh, geomBuffer, binningBuffer, imgBuffer), g,
-                                        ctx.num_rendered[k]))
-            claimed = ctx.grads[k].claim(accumulate=False)[0]
+            views.append(_backward_args(f.rs, (empty, xyz, scl, rot, empty, sh), fw, g))
+            planes.append(pl)
+            claimed = f.grads.claim(accumulate=False)[0]
             outs.append({m: b for m, b in claimed.items() if m.startswith("dL_")})
             need_v, need_o, need_r, need_s = ctx.needs_input_grad[5 + n * k:5 + n * k + 4]   # (after the 5 non-tensor arguments)
 
@@ -129,17 +105,16 @@ class _RasterizeBoundBatch(torch.autograd.Function):
                                mb.shell_len, mb.resize_scale))
             bgrads.append({"d_verts": torch.zeros_like(verts) if need_v else None, "d_offset": buf(need_o, "d_offset", (N,)),
                            "d_rotation": buf(need_r, "d_rotation", (N, 4)), "d_scaling": buf(need_s, "d_scaling", (N, 3))})
-        res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=[fg.want for fg in ctx.grads], outs=outs,
-                                                 stats=ctx.stats, bindings=descs, bind_grads=bgrads,
-                                                 planes=planes if ctx.depth_alpha else None)
+        res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=[f.grads.want for f in ctx.frames],
+                                                 outs=outs, stats=[f.stats for f in ctx.frames], bindings=descs, bind_grads=bgrads,
+                                                 planes=planes if ctx.frames[0].has_planes else None)
         flat = [None, None, None, None, None]
-        for k in range(K):
-            grad_means2D, _, grad_opacities, _, _, grad_sh, _, _ = res[k]
-            b = bgrads[k]
-            d_off = b["d_offset"].view(ctx.offset_shapes[k]) if b["d_offset"] is not None else None
+        for grads, b, offset_shape in zip(res, bgrads, ctx.offset_shapes):
+            g = dict(zip(_GRAD_NAMES, grads))
+            d_off = b["d_offset"].view(offset_shape) if b["d_offset"] is not None else None
             # (fresh view objects: AccumulateGrad adopts a gradient without a copy only if nobody else references it)
             fresh = lambda t: t.view(t.shape) if t is not None else None  # noqa: E731
-            flat += [b["d_verts"], d_off, fresh(b["d_rotation"]), fresh(b["d_scaling"]), grad_means2D, grad_sh, grad_opacities]
+            flat += [b["d_verts"], d_off, fresh(b["d_rotation"]), fresh(b["d_scaling"]), g["dL_dmeans2D"], g["dL_dsh"], g["dL_dopacity"]]
         return tuple(flat)
 
 
@@ -175,10 +150,9 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding: MeshBinding
         points.append(sp)
     res = _RasterizeBoundBatch.apply(settings, [mb] * K, list(range(K)) if slots is None else list(slots),
                                      _pick_forward_only(tensors), bool(depth_alpha), *tensors)
-    n_out = 4 if depth_alpha else 2
     out = []
-    for k, sp in enumerate(points):
-        o = _result(res[n_out * k], res[n_out * k + 1], sp, res[n_out * k + 2:n_out * k + 4] if depth_alpha else None)
+    for r, sp in zip(_per_view_outputs(res, K), points):
+        o = _result(r, sp)
         o["bound"] = tuple(t.detach() for t in o["radii"]._fr_bound)
         out.append(o)
     return out

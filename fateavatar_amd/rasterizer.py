@@ -13,7 +13,7 @@ All tensors must live on a HIP device ("cuda" in PyTorch-ROCm).  There is no CPU
 from __future__ import annotations
 
 import ctypes as C
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -215,6 +215,24 @@ def _grad_shapes(P, M):
 _GRAD_NAMES = tuple(_grad_shapes(0, 0))
 
 
+class _Forward(NamedTuple):
+    """What the forward of one view returns, by name.  The first six are `_C.rasterize_gaussians`' tuple
+    (rasterize_points.cu:114); depth [H,W], alpha [H,W] and the opaque planes buffer exist with FR_FLAG_DEPTH_ALPHA only."""
+    num_rendered: int
+    color: torch.Tensor
+    radii: torch.Tensor
+    geom: torch.Tensor
+    binning: torch.Tensor
+    img: torch.Tensor
+    depth: Optional[torch.Tensor] = None
+    alpha: Optional[torch.Tensor] = None
+    planes: Optional[torch.Tensor] = None
+
+    def as_tuple(self) -> tuple:
+        """The documented result of `rasterize_gaussians`: the reference's six, nine with the planes."""
+        return tuple(self) if self.planes is not None else tuple(self[:6])
+
+
 def _forward_view(args, raw=False, visible=None, binding=None, forward_only=False, depth_alpha=False) -> dict:
     """One view of a forward, from the positional arguments of `rasterize_gaussians`: its inputs as the kernels read them
     (kept alive in the view), its fr_params / fr_inputs, outputs and binning capacity.  The launcher allocates the binning
@@ -298,7 +316,7 @@ def _batch_arrays(views, slots, dev):
 def _launch_forward(views, slots, batch):
     """The forward of views from `_forward_view` on the device's handles `slots`: fr_forward_batch, or fr_forward for a
     single frame (`batch` False).  A view that overflows its binning capacity is rerun with the capacity it needs.
-    Returns the `rasterize_gaussians` result tuple of every view."""
+    Returns the `_Forward` record of every view."""
     K, dev, L = len(views), views[0]["dev"], _lib.lib()
     counts = (_lib.fr_counts * K)()
     with torch.cuda.device(dev):
@@ -332,10 +350,9 @@ def _launch_forward(views, slots, batch):
         if not _no_wait:  # (with it, the counts arrive later: read_counts / check_async_overflow)
             _capacity_hint[dev] = max(_capacity_hint.get(dev, 0), int(c.num_instances * 1.25) + 1024)
             last_counts[dev] = c
-        r = (0 if _no_wait else int(c.num_rendered), v["out_color"], v["radii"], v["geom"], v["binning"], v["img"])
-        if v["planes"] is not None:
-            r += (v["planes"]["out_depth"], v["planes"]["out_alpha"], v["planes"]["planes"])
-        out.append(r)
+        pl = v["planes"] or {}
+        out.append(_Forward(0 if _no_wait else int(c.num_rendered), v["out_color"], v["radii"], v["geom"], v["binning"], v["img"],
+                            pl.get("out_depth"), pl.get("out_alpha"), pl.get("planes")))
     return out
 
 
@@ -376,12 +393,10 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                        projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug),
                       _raw, _visible, forward_only=_forward_only, depth_alpha=_depth_alpha)
     if v["prm"].P == 0:  # rasterize_points.cu:81 skips the rasterizer entirely
-        empty = torch.empty((0,), dtype=torch.uint8, device=means3D.device)
-        r = (0, v["out_color"].zero_(), v["radii"], empty, empty.clone(), empty.clone())
-        if _depth_alpha:
-            r += (v["planes"]["out_depth"].zero_(), v["planes"]["out_alpha"].zero_(), empty.clone())
-        return r
-    return _launch_forward([v], [_slot], batch=False)[0]
+        empty, pl = torch.empty((0,), dtype=torch.uint8, device=means3D.device), v["planes"]
+        return _Forward(0, v["out_color"].zero_(), v["radii"], empty, empty.clone(), empty.clone(),
+                        *((pl["out_depth"].zero_(), pl["out_alpha"].zero_(), empty.clone()) if pl else ())).as_tuple()
+    return _launch_forward([v], [_slot], batch=False)[0].as_tuple()
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -416,6 +431,11 @@ def rasterize_gaussians_batch(views, slots=None, raw=False, visibles=None, bindi
     tensors are then OUTPUTS (written by the preprocess kernel from the mesh binding).  `forward_only` (extension,
     FR_FLAG_FORWARD_ONLY): every view is rendered without the backward's hand-off; never chosen here on its own.
     `depth_alpha` (extension, FR_FLAG_DEPTH_ALPHA): every view's result also holds depth, alpha and planesBuffer."""
+    return [r.as_tuple() for r in _forward_batch(views, slots, raw, visibles, bindings, forward_only, depth_alpha)]
+
+
+def _forward_batch(views, slots, raw, visibles, bindings, forward_only, depth_alpha) -> list:
+    """`rasterize_gaussians_batch` with every view's result as its `_Forward` record."""
     K = len(views)
     if not 1 <= K <= _lib.FR_MAX_BATCH:
         raise RuntimeError(f"rasterize_gaussians_batch: 1 .. {_lib.FR_MAX_BATCH} views")
@@ -463,60 +483,39 @@ def rasterize_gaussians_backward_batch(views, slots=None, raw=False, wants=None,
 
 
 class _RasterizeGaussiansBatch(torch.autograd.Function):
-    """`_RasterizeGaussians` for K views rendered together.  Tensor arguments: per view (means3D, means2D, sh,
-    colors_precomp, opacities, scales, rotations, cov3Ds_precomp); outputs: per view (color, radii), and with `depth_alpha`
-    (color, radii, depth [1,H,W], alpha [1,H,W])."""
+    """`_RasterizeGaussians` for K views rendered together.  Tensor arguments: per view the eight of `_RasterizeGaussians`
+    (means3D ... cov3Ds_precomp); outputs: per view those of `_SavedFrame`."""
 
     @staticmethod
     def forward(ctx, settings, raw_activations, slots, forward_only, depth_alpha, *tensors):
         K = len(settings)
         assert len(tensors) == 8 * K
-        ctx.raw, ctx.K, ctx.settings, ctx.slots = bool(raw_activations), K, settings, slots
-        ctx.depth_alpha = bool(depth_alpha)
-        ctx.set_materialize_grads(False)
+        ctx.raw, ctx.slots = bool(raw_activations), slots
         per_view = [tensors[8 * k:8 * k + 8] for k in range(K)]
         viss = [torch.empty((t[0].shape[0],), dtype=torch.bool, device=t[0].device) for t in per_view]
-        res = rasterize_gaussians_batch([_forward_args(rs, *t) for rs, t in zip(settings, per_view)], slots=slots,
-                                        raw=ctx.raw, visibles=viss, forward_only=forward_only, depth_alpha=ctx.depth_alpha)
-        ctx.stats, ctx.num_rendered, ctx.grads = [], [], []
-        saved, outs = [], []
-        for (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), vis, r in \
-                zip(per_view, viss, res):
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = r[:6]
-            radii._fr_visible = vis
-            ctx.stats.append(getattr(means2D, "_fr_densification_stats", None))
-            ctx.num_rendered.append(num_rendered)
-            ctx.grads.append(_FrameGrads.of_frame(ctx.raw, means3D, sh, colors_precomp, opacities, scales, rotations,
-                                                  cov3Ds_precomp))
-            saved += [colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer]
-            outs += [color, radii]
-            if ctx.depth_alpha:
-                saved.append(r[8])
-                outs += [r[6].unsqueeze(0), r[7].unsqueeze(0)]
-        ctx.save_for_backward(*saved)
-        n_out = 4 if ctx.depth_alpha else 2
-        ctx.mark_non_differentiable(*outs[1::n_out])
-        return tuple(outs)
+        res = _forward_batch([_forward_args(rs, *t) for rs, t in zip(settings, per_view)], slots, ctx.raw, viss, None,
+                             forward_only, depth_alpha)
+        return _SavedFrame.save(ctx, [
+            _SavedFrame(rs, r, vis, means2D, _FrameGrads.of_frame(ctx.raw, means3D, sh, colors_precomp, opacities, scales,
+                                                                  rotations, cov3Ds_precomp),
+                        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh))
+            for rs, r, vis, (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+            in zip(settings, res, viss, per_view)])
 
     @staticmethod
     def backward(ctx, *grad_outs):
-        n_out, n_saved = (4, 11) if ctx.depth_alpha else (2, 10)
-        grad_colors = grad_outs[0::n_out]
-        grad_planes = [grad_outs[n_out * k + 2:n_out * k + 4] for k in range(ctx.K)] if ctx.depth_alpha else [(None, None)] * ctx.K
-        if all(g is None for g in grad_colors) and all(g is None for gp in grad_planes for g in gp):
-            return (None,) * 5 + (None,) * (8 * ctx.K)
+        if not _any_grad(grad_outs):
+            return (None,) * (5 + 8 * len(ctx.frames))
         views, outs, planes = [], [], []
-        for k, (rs, g) in enumerate(zip(ctx.settings, grad_colors)):
-            saved = ctx.saved_tensors[n_saved * k:n_saved * k + 10]
-            planes.append((ctx.saved_tensors[n_saved * k + 10], *grad_planes[k]) if ctx.depth_alpha else None)
-            if g is None:   # (a view nobody differentiated: its frame still runs with a zero image gradient)
-                g = torch.zeros((NUM_CHANNELS, rs.image_height, rs.image_width), dtype=torch.float32, device=saved[1].device)
-            views.append(_backward_args(rs, saved, g, ctx.num_rendered[k]))
+        for f, own, fw, g, pl in _SavedFrame.load(ctx, grad_outs):
+            views.append(_backward_args(f.rs, own, fw, g))
+            planes.append(pl)
             # (in-kernel accumulation across the views of ONE batch would race: a later view of the same parameters gets a
             # fresh tensor, which autograd adds)
-            outs.append(ctx.grads[k].claim(accumulate=False)[0])
-        res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=ctx.raw, wants=[fg.want for fg in ctx.grads],
-                                                 outs=outs, stats=ctx.stats, planes=planes if ctx.depth_alpha else None)
+            outs.append(f.grads.claim(accumulate=False)[0])
+        res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=ctx.raw, wants=[f.grads.want for f in ctx.frames],
+                                                 outs=outs, stats=[f.stats for f in ctx.frames],
+                                                 planes=planes if ctx.frames[0].has_planes else None)
         return (None,) * 5 + tuple(t for grads in res for t in _input_grads(grads))
 
 
@@ -529,8 +528,7 @@ def rasterize_views_autograd(settings, per_view_tensors, raw_activations=False, 
     flat = [t for v in per_view_tensors for t in v]
     out = _RasterizeGaussiansBatch.apply(list(settings), bool(raw_activations), list(range(K)) if slots is None else list(slots),
                                          _pick_forward_only(flat), bool(depth_alpha), *flat)
-    n = 4 if depth_alpha else 2
-    return [tuple(out[n * k:n * k + n]) for k in range(K)]
+    return _per_view_outputs(out, K)
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):
@@ -672,13 +670,14 @@ def _forward_args(rs, means3D, means2D, sh, colors_precomp, opacities, scales, r
             rs.prefiltered, rs.debug)
 
 
-def _backward_args(rs, saved, grad_out_color, num_rendered):
-    """The positional arguments of `rasterize_gaussians_backward` from what the forward saved: (colors_precomp, means3D,
-    scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer): __init__.py:109-129."""
-    colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = saved
-    return (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
-            rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geomBuffer, num_rendered,
-            binningBuffer, imgBuffer, rs.debug)
+def _backward_args(rs, own, fw, grad_out_color):
+    """The positional arguments of `rasterize_gaussians_backward` from what the forward saved — `own`: (colors_precomp,
+    means3D, scales, rotations, cov3Ds_precomp, sh); `fw`: the frame's `_Forward` as `_SavedFrame.load` restores it:
+    __init__.py:109-129."""
+    colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh = own
+    return (rs.bg, means3D, fw.radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+            rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, fw.geom, fw.num_rendered,
+            fw.binning, fw.img, rs.debug)
 
 
 _INPUT_GRADS = [(k, _GRAD_NAMES.index(k)) for k in ("dL_dmeans3D", "dL_dmeans2D", "dL_dsh", "dL_dcolors", "dL_dopacity",
@@ -692,69 +691,107 @@ def _input_grads(grads, added=()):
     return tuple([None if k in added else grads[i] for k, i in _INPUT_GRADS])
 
 
+class _SavedFrame:
+    """One view of a frame between its autograd Function's forward and backward (a list of them sits on `ctx.frames`): the
+    ONE place that knows what a view returns to autograd — (color, radii), with planes (color, radii, depth [1,H,W],
+    alpha [1,H,W]) — and what it saves — the Function's `own` tensors, then radii, geomBuffer, binningBuffer, imgBuffer and,
+    with planes, planesBuffer.  It holds no tensor of the frame itself (an output kept on `ctx` would be a cycle)."""
+
+    def __init__(self, rs, fw, visible, means2D, grads, own):
+        """`visible`: the mask the preprocess kernel wrote (or None); `own`: the tensors the Function wants back in its backward."""
+        # extension: the visibility mask (radii > 0) comes out of the preprocess kernel; render() picks it up from
+        # `radii._fr_visible` instead of launching a compare kernel
+        if visible is not None:
+            fw.radii._fr_visible = visible
+        # extension: `means2D._fr_densification_stats = (xyz_gradient_accum, denom)` makes the backward kernel
+        # accumulate the densification statistics itself
+        self.stats = getattr(means2D, "_fr_densification_stats", None)
+        self.rs, self.grads, self.num_rendered, self.has_planes = rs, grads, fw.num_rendered, fw.planes is not None
+        self._outputs = (fw.color, fw.radii) + ((fw.depth.unsqueeze(0), fw.alpha.unsqueeze(0)) if self.has_planes else ())
+        self._saved = (*own, fw.radii, fw.geom, fw.binning, fw.img) + ((fw.planes,) if self.has_planes else ())
+        self.n_own, self.n_saved, self.n_out = len(own), len(self._saved), len(self._outputs)
+
+    @staticmethod
+    def save(ctx, frames) -> tuple:
+        """The end of a Function's forward: saves every view's tensors, marks the radii non-differentiable and returns
+        the Function's outputs, view after view."""
+        ctx.frames = frames
+        # the gradient slot of the int32 `radii` output would otherwise be materialised as a zero tensor per backward
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*[t for f in frames for t in f._saved])
+        outs = tuple(t for f in frames for t in f._outputs)
+        ctx.mark_non_differentiable(*[f._outputs[1] for f in frames])
+        for f in frames:
+            del f._outputs, f._saved
+        return outs
+
+    @staticmethod
+    def load(ctx, grad_outs):
+        """The start of a Function's backward, view after view: (frame, its `own` tensors, its `_Forward` restored from the
+        saved tensors (no color, depth, alpha), the image gradient, the `_planes` tuple (planesBuffer, dL_ddepth, dL_dalpha)
+        or None)."""
+        all_saved, s, o = ctx.saved_tensors, 0, 0
+        for f in ctx.frames:
+            saved, (g, _, *g_planes) = all_saved[s:s + f.n_saved], grad_outs[o:o + f.n_out]
+            s, o = s + f.n_saved, o + f.n_out
+            radii, geom, binning, img, *planes = saved[f.n_own:]
+            if g is None:   # (this view's image was not differentiated, something else was: a zero image gradient)
+                g = torch.zeros((NUM_CHANNELS, f.rs.image_height, f.rs.image_width), dtype=torch.float32, device=radii.device)
+            yield (f, saved[:f.n_own], _Forward(f.num_rendered, None, radii, geom, binning, img, None, None, *planes), g,
+                   (*planes, *g_planes) if f.has_planes else None)
+
+
+def _any_grad(grad_outs) -> bool:
+    """Whether anything of a Function's outputs was differentiated (if not, its backward returns None throughout)."""
+    return any(g is not None for g in grad_outs)
+
+
+def _per_view_outputs(outs, K) -> list:
+    """A Function's flat outputs as one tuple per view (the K views of one Function agree on having planes)."""
+    n = len(outs) // K
+    return [tuple(outs[n * k:n * k + n]) for k in range(K)]
+
+
 class _RasterizeGaussians(torch.autograd.Function):
-    """diff_gaussian_rasterization/__init__.py:44-155."""
+    """diff_gaussian_rasterization/__init__.py:44-155.  Tensor arguments: (means3D, means2D, sh, colors_precomp, opacities,
+    scales, rotations, cov3Ds_precomp), then raster_settings; outputs: those of `_SavedFrame`."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, raw_activations=False, forward_only=False, depth_alpha=False):
         rs = raster_settings
-        ctx.depth_alpha = bool(depth_alpha)
         ctx.raw = bool(raw_activations)
         ctx.fr_slot = _slot   # the backward goes through the handle the forward used
-        # the gradient slot of the int32 `radii` output would otherwise be materialised as a zero tensor per backward
-        ctx.set_materialize_grads(False)
         args = _forward_args(rs, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-        # extension: the visibility mask (radii > 0) comes out of the preprocess kernel; render() picks it up from
-        # `radii._fr_visible` instead of launching a compare kernel
         vis = torch.empty((means3D.shape[0],), dtype=torch.bool, device=means3D.device) if means3D.is_cuda else None
         res = _snapshot_on_error(
             rs.debug, "snapshot_fw.dump", "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.",
-            rasterize_gaussians, args, _raw=ctx.raw, _visible=vis, _forward_only=forward_only, _depth_alpha=ctx.depth_alpha)
-        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = res[:6]
-        if vis is not None and means3D.shape[0] > 0:
-            radii._fr_visible = vis
-        # extension: `means2D._fr_densification_stats = (xyz_gradient_accum, denom)` makes the backward kernel
-        # accumulate the densification statistics itself
-        ctx.stats = getattr(means2D, "_fr_densification_stats", None)
-        ctx.raster_settings = rs
-        ctx.num_rendered = num_rendered
-        ctx.grads = _FrameGrads.of_frame(ctx.raw, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, *res[8:9])
-        ctx.mark_non_differentiable(radii)
-        if ctx.depth_alpha:
-            return color, radii, res[6].unsqueeze(0), res[7].unsqueeze(0)
-        return color, radii
+            rasterize_gaussians, args, _raw=ctx.raw, _visible=vis, _forward_only=forward_only, _depth_alpha=bool(depth_alpha))
+        grads = _FrameGrads.of_frame(ctx.raw, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        return _SavedFrame.save(ctx, [_SavedFrame(rs, _Forward(*res), vis if means3D.shape[0] > 0 else None, means2D, grads,
+                                                  (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh))])
 
     @staticmethod
-    def backward(ctx, grad_out_color, _, grad_depth=None, grad_alpha=None):
-        rs = ctx.raster_settings
-        n_args = 12 if ctx.depth_alpha else 11   # (depth_alpha is passed only when it is set)
-        if grad_out_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * n_args
-        if grad_out_color is None:   # (only a plane is differentiated: the image's gradient is zero)
-            grad_out_color = torch.zeros((NUM_CHANNELS, rs.image_height, rs.image_width), dtype=torch.float32,
-                                         device=ctx.saved_tensors[1].device)
-        planes = (ctx.saved_tensors[10], grad_depth, grad_alpha) if ctx.depth_alpha else None
-        args = _backward_args(rs, ctx.saved_tensors[:10], grad_out_color, ctx.num_rendered)
-        out, added = ({}, ()) if rs.debug else ctx.grads.claim()   # (debug mode claims no GradOut slot)
+    def backward(ctx, *grad_outs):
+        if not _any_grad(grad_outs):
+            return (None,) * 12
+        (f, own, fw, grad_out_color, planes), = _SavedFrame.load(ctx, grad_outs)
+        out, added = ({}, ()) if f.rs.debug else f.grads.claim()   # (debug mode claims no GradOut slot)
         with handle_slot(ctx.fr_slot):
             grads = _snapshot_on_error(
-                rs.debug, "snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n",
-                rasterize_gaussians_backward, args, _out=out, _raw=ctx.raw, _stats=ctx.stats, _want=ctx.grads.want,
-                _accumulate=added, _planes=planes)
-        return _input_grads(grads, added) + (None,) * (n_args - 8)
+                f.rs.debug, "snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n",
+                rasterize_gaussians_backward, _backward_args(f.rs, own, fw, grad_out_color), _out=out, _raw=ctx.raw,
+                _stats=f.stats, _want=f.grads.want, _accumulate=added, _planes=planes)
+        # (autograd drops the surplus trailing None of a call with the reference's nine arguments)
+        return _input_grads(grads, added) + (None,) * 4
 
 
 def rasterize_gaussians_autograd(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                  raster_settings, raw_activations=False, depth_alpha=False):
+    """`depth_alpha` (extension, FR_FLAG_DEPTH_ALPHA): (color, radii, depth, alpha) instead of (color, radii)."""
     forward_only = _pick_forward_only((means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp))
-    if depth_alpha:   # (extension, FR_FLAG_DEPTH_ALPHA: (color, radii, depth, alpha))
-        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                         cov3Ds_precomp, raster_settings, raw_activations, forward_only, True)
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, raw_activations, forward_only)
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                     raster_settings, raw_activations, forward_only, depth_alpha)
 
 
 class GaussianRasterizationSettings(NamedTuple):

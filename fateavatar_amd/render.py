@@ -59,11 +59,13 @@ def _activations(pc):
     return False, pc.get_opacity, pc.get_scaling, pc.get_rotation
 
 
-def _result(image, radii, screenspace_points, planes=None) -> dict:
+def _result(outs, screenspace_points) -> dict:
+    """render()'s dict from a view's autograd outputs: (image, radii), with `depth_alpha` (extension) also (depth, alpha)."""
+    image, radii, *planes = outs
     visible = getattr(radii, "_fr_visible", None)  # written by the preprocess kernel (same values as radii > 0)
     out = {"render": image, "viewspace_points": screenspace_points,
            "visibility_filter": visible if visible is not None else radii > 0, "radii": radii}
-    if planes is not None:   # (extension: depth_alpha=True)
+    if planes:
         out["depth"], out["alpha"] = planes
     return out
 
@@ -80,7 +82,7 @@ def render(viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, o
     out = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
                      scales=scales, rotations=rotations, cov3D_precomp=None, **({"raw_activations": True} if fused else {}),
                      **({"depth_alpha": True} if depth_alpha else {}))
-    return _result(out[0], out[1], screenspace_points, out[2:] if depth_alpha else None)
+    return _result(out, screenspace_points)
 
 
 def render_batch(viewpoint_cameras, pcs, bg_colors, scaling_modifier=1.0, slots=None, depth_alpha=False):
@@ -108,4 +110,4 @@ def render_batch(viewpoint_cameras, pcs, bg_colors, scaling_modifier=1.0, slots=
         tensors.append((means3D, sp, pc.get_features, empty, opacity, scales, rotations, empty))
         points.append(sp)
     res = rasterize_views_autograd(settings, tensors, raw_activations=fused, slots=slots, depth_alpha=depth_alpha)
-    return [_result(r[0], r[1], sp, r[2:] if depth_alpha else None) for r, sp in zip(res, points)]
+    return [_result(r, sp) for r, sp in zip(res, points)]

@@ -1430,3 +1430,89 @@ def test_batch_refuses_shared_handles_and_too_many_views(gpu_device):
         render_batch([cam, cam], pc, bg, slots=[1, 1])
     with pytest.raises(RuntimeError, match="1 .. 4 views"):
         render_batch([cam] * 5, pc, bg)
+
+
+def _raster_settings(s, dev, H=None, W=None):
+    import torch
+    from fateavatar_amd import rasterizer
+    c = s.camera
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
+    return rasterizer.GaussianRasterizationSettings(
+        image_height=c.image_height if H is None else H, image_width=c.image_width if W is None else W, tanfovx=c.tanfovx,
+        tanfovy=c.tanfovy, bg=t(s.bg), scale_modifier=1.0, viewmatrix=t(c.world_view_transform),
+        projmatrix=t(c.full_proj_transform), sh_degree=s.sh_degree, campos=t(c.camera_center), prefiltered=False, debug=False)
+
+
+@pytest.mark.parametrize("depth_alpha", [False, True])
+def test_a_frame_without_gaussians_renders_zeros_and_empty_gradients(gpu_device, depth_alpha):
+    """P == 0 through GaussianRasterizer: rasterize_points.cu:81 skips the rasterizer, so the image is the zeros it was
+    allocated as (not the background), and the backward hands every input an empty gradient of its own shape.  Nothing is
+    launched, so nothing can fail in a launch."""
+    import torch
+    from fateavatar_amd import rasterizer
+    s = scenes.random_scene(10, 40, 24, sh_degree=1, seed=0, bg=(0.2, 0.5, 0.9))
+    rs = _raster_settings(s, gpu_device)
+    H, W = rs.image_height, rs.image_width
+    leaf = lambda *shape: torch.zeros(shape, device=gpu_device, requires_grad=True)  # noqa: E731
+    shs = torch.zeros((0, 4, 3), device=gpu_device)
+    for colours in ("precomputed", "sh"):
+        means3D, means2D, opac, scales, rots, cols = leaf(0, 3), leaf(0, 3), leaf(0, 1), leaf(0, 3), leaf(0, 4), leaf(0, 3)
+        out = rasterizer.GaussianRasterizer(rs)(
+            means3D=means3D, means2D=means2D, opacities=opac, scales=scales, rotations=rots,
+            shs=shs if colours == "sh" else None, colors_precomp=cols if colours == "precomputed" else None,
+            **({"depth_alpha": True} if depth_alpha else {}))
+        assert len(out) == (4 if depth_alpha else 2)
+        color, radii = out[0], out[1]
+        assert color.shape == (3, H, W) and color.dtype == torch.float32 and not bool(color.detach().any())
+        assert radii.shape == (0,) and radii.dtype == torch.int32 and not radii.requires_grad
+        assert not hasattr(radii, "_fr_visible")
+        loss = (color * 2.0).sum()
+        if depth_alpha:
+            for plane in out[2:]:
+                assert plane.shape == (1, H, W) and plane.dtype == torch.float32 and not bool(plane.detach().any())
+                loss = loss + plane.sum()
+        assert color.requires_grad
+        loss.backward()
+        torch.cuda.synchronize()
+        wanted = [means3D, means2D, opac, scales, rots] + ([cols] if colours == "precomputed" else [])
+        for t in wanted:
+            assert t.grad is not None and t.grad.shape == t.shape and t.grad.dtype == torch.float32
+        if colours == "sh":
+            assert cols.grad is None
+
+
+def test_the_reference_call_of_the_autograd_function_with_nine_arguments(gpu_device):
+    """diff_gaussian_rasterization/__init__.py:32-41 calls `_RasterizeGaussians.apply` with exactly nine positional
+    arguments (tensors first, raster_settings ninth).  That call gives the image and radii of GaussianRasterizer bit for
+    bit, and the same gradients (to the summation order of the backward's atomics)."""
+    import torch
+    import diff_gaussian_rasterization as dgr
+    from fateavatar_amd import rasterizer
+    s = scenes.head_scene(P=4000, res=96, sh_degree=2, seed=5, opacity=0.4)
+    rs = _raster_settings(s, gpu_device)
+    rng = np.random.default_rng(11)
+    w = torch.from_numpy((rng.uniform(-1, 1, (3, rs.image_height, rs.image_width)) / 96 ** 2).astype(np.float32)).to(gpu_device)
+    empty = torch.Tensor([])
+
+    def run(how):
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(gpu_device).requires_grad_(True)  # noqa: E731
+        means3D, shs, opac, scales, rots = t(s.means3D), t(s.shs), t(s.opacities), t(s.scales), t(s.rotations)
+        means2D = torch.zeros_like(means3D, requires_grad=True)
+        if how == "apply":
+            out = dgr._RasterizeGaussians.apply(means3D, means2D, shs, empty, opac, scales, rots, empty, rs)
+        else:
+            out = rasterizer.GaussianRasterizer(rs)(means3D=means3D, means2D=means2D, shs=shs, opacities=opac, scales=scales,
+                                                    rotations=rots)
+        assert len(out) == 2
+        color, radii = out
+        (color * w).sum().backward()
+        torch.cuda.synchronize()
+        return color.detach(), radii, [x.grad for x in (means3D, means2D, shs, opac, scales, rots)]
+
+    ca, ra, ga = run("apply")
+    cm, rm, gm = run("module")
+    assert torch.equal(ca, cm) and torch.equal(ra, rm) and int((ra > 0).sum()) > 1000
+    for name, a, m in zip(("means3D", "means2D", "shs", "opacities", "scales", "rotations"), ga, gm):
+        # (the head scene's splats are isotropic: its rotation gradients are zero on both sides)
+        assert a is not None and a.shape == m.shape and (float(m.abs().max()) > 0 or name == "rotations"), name
+        assert util.rel_l2(a.cpu().numpy(), m.cpu().numpy()) < 1e-5, name
