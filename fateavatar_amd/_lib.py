@@ -62,6 +62,15 @@ class fr_adam_config(C.Structure):
                 ("skip", C.c_void_p * FR_ADAM_MAX_GRADS), ("n_skip", C.c_int32)]
 
 
+FR_TEX_MAX_LAYERS = 8
+FR_TEX_ACT_IDENTITY, FR_TEX_ACT_TANH_SCALE, FR_TEX_ACT_SOFTPLUS_CAP = 0, 1, 2
+
+
+class fr_tex_layer(C.Structure):
+    _fields_ = [("texture", C.c_void_p), ("out", C.c_void_p), ("d_out", C.c_void_p), ("d_texture", C.c_void_p),
+                ("channels", C.c_int32), ("activation", C.c_int32), ("a0", C.c_float), ("a1", C.c_float)]
+
+
 class fr_inputs(C.Structure):
     _fields_ = [(n, _fp) for n in ("background", "means3D", "shs", "colors_precomp", "opacities", "scales",
                                    "rotations", "cov3D_precomp", "viewmatrix", "projmatrix", "campos")]
@@ -80,7 +89,7 @@ class fr_counts(C.Structure):
 EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile_enable", "fr_profile_read", "fr_geometry_bytes", "fr_image_bytes",
            "fr_binning_bytes", "fr_planes_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
            "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
-           "fr_bind_forward", "fr_bind_backward"]
+           "fr_bind_forward", "fr_bind_backward", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward"]
 
 
 def build(force: bool = False) -> str:
@@ -166,6 +175,13 @@ def lib():
     L.fr_bind_forward.restype = C.c_int
     L.fr_bind_backward.argtypes = [C.POINTER(fr_binding), _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
     L.fr_bind_backward.restype = C.c_int
+    L.fr_texture_corners.argtypes = [C.c_int32, _fp, C.c_int32, C.c_int32, _fp, C.c_void_p]
+    L.fr_texture_corners.restype = C.c_int
+    L.fr_texture_lookup.argtypes = [C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(fr_tex_layer), C.c_void_p]
+    L.fr_texture_lookup.restype = C.c_int
+    L.fr_texture_lookup_backward.argtypes = [C.c_int32, _fp, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.POINTER(fr_tex_layer),
+                                             C.c_void_p]
+    L.fr_texture_lookup_backward.restype = C.c_int
     L.fr_adam_step.argtypes = [C.POINTER(fr_adam_config), _fp, _fp, _fp, _fp, C.c_uint64, _fp, C.c_void_p]
     L.fr_adam_step.restype = C.c_int
     L.fr_adam_step_multi.argtypes = [C.POINTER(fr_adam_config), _fp, C.POINTER(C.c_void_p), C.c_int32, _fp, _fp, C.c_uint64, _fp,

@@ -1,0 +1,291 @@
+"""Gaussian attributes looked up in UV attribute maps: the per-frame front end of a BAKED FateAvatar.
+
+reference: model/uv_decoder.py — `UVSampling._texture_look_up` (:179-202):
+    F.grid_sample(texture, 2 * uv - 1, mode="bilinear", padding_mode="border", align_corners=True)
+once per attribute map (colour 3, opacity 1, scaling 3, rotation 3 -> 4 after its activation, offset 1 channel; 512 x 512),
+behind the per-texture activations of :133-174, at the UV coordinates of the avatar's binding points.  Per frame that is
+five grid_sample launches, a dozen element-wise kernels and, in training, their autograd twins, which scatter every point's
+gradient into the textures with float atomics.
+
+Here the look-up of ALL textures is one HIP kernel (lane = point, output row-major [N,C]: the layout the rasterizer takes)
+with the colour / offset / scaling activations applied to the texels inside it, and the backward is one kernel with lane =
+TEXEL that gathers over a plan built once per UV set (`TexturePlan`) and stores every texel of every gradient: no zero
+fill, no float atomics, the same bits on every run (include/fr_rasterizer.h, csrc/fr_texture.hip).  The rotation activation
+(axis-angle -> quaternion) stays torch, on the texture (`rotation_activation`).
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+
+SH_C0 = 0.28209479177387814   # tools/gs_utils/sh_utils.py: C0
+
+# model/uv_decoder.py:225-245: the channel slices of the decoder's 11-channel output
+TEXTURE_CHANNELS = (("color", 3), ("opacity", 1), ("scaling", 3), ("rotation", 3), ("offset", 1))
+
+
+class Activation(NamedTuple):
+    """A per-texture activation the look-up kernels apply to the texel (include/fr_rasterizer.h, FR_TEX_ACT_*)."""
+    kind: int = _lib.FR_TEX_ACT_IDENTITY
+    a0: float = 0.0
+    a1: float = 0.0
+
+
+IDENTITY = Activation()
+
+
+def tanh_scale(scale: float) -> Activation:
+    """tanh(t) * scale."""
+    return Activation(_lib.FR_TEX_ACT_TANH_SCALE, float(scale), 0.0)
+
+
+def softplus_cap(mean: float, cap: float) -> Activation:
+    """cap - softplus(-(t + mean) + cap)."""
+    return Activation(_lib.FR_TEX_ACT_SOFTPLUS_CAP, float(mean), float(cap))
+
+
+COLOR_ACTIVATION = tanh_scale(0.5 / SH_C0)      # _color_activation, uv_decoder.py:134-138
+OFFSET_ACTIVATION = tanh_scale(1.0)             # _offset_activation, :152-156
+
+
+def scaling_activation(mean_scaling: float, max_scaling: float) -> Activation:
+    """_scaling_activation (uv_decoder.py:140-149): max - softplus(-(t + mean) + max)."""
+    return softplus_cap(mean_scaling, max_scaling)
+
+
+def _on_device(t: torch.Tensor, name: str) -> None:
+    if not t.is_cuda:
+        raise RuntimeError(f"texture_lookup: {name} must be on a HIP device (there is no CPU path)")
+
+
+def validate_textures(textures, H: int, W: int, activations=None):
+    """The argument checks of `texture_lookup`, in its order: layer count, shapes ([C,H,W] or [1,C,H,W], C <= 4, the plan's
+    H x W), activations, then devices.  -> (textures as a list, activations as a list of `Activation`)."""
+    textures = list(textures)
+    if not 1 <= len(textures) <= _lib.FR_TEX_MAX_LAYERS:
+        raise RuntimeError(f"texture_lookup: 1 .. {_lib.FR_TEX_MAX_LAYERS} textures per call, not {len(textures)}")
+    acts = [IDENTITY] * len(textures) if activations is None else [IDENTITY if a is None else Activation(*a) for a in activations]
+    if len(acts) != len(textures):
+        raise RuntimeError("texture_lookup: one activation (or None) per texture")
+    for i, t in enumerate(textures):
+        if not isinstance(t, torch.Tensor) or t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[0] != 1):
+            raise RuntimeError(f"texture_lookup: texture {i} must be a [C,H,W] or [1,C,H,W] tensor")
+        c, h, w = t.shape[-3:]
+        if not 1 <= c <= 4:
+            raise RuntimeError(f"texture_lookup: texture {i} has {c} channels (1 .. 4)")
+        if (h, w) != (H, W):
+            raise RuntimeError(f"texture_lookup: texture {i} is {h} x {w}, the plan was made for {H} x {W}")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"texture_lookup: texture {i} must be float32")
+    for a in acts:
+        if a.kind not in (_lib.FR_TEX_ACT_IDENTITY, _lib.FR_TEX_ACT_TANH_SCALE, _lib.FR_TEX_ACT_SOFTPLUS_CAP):
+            raise RuntimeError(f"texture_lookup: unknown activation {a.kind}")
+    for i, t in enumerate(textures):
+        _on_device(t, f"texture {i}")
+    return textures, acts
+
+
+class TexturePlan:
+    """The UV coordinates of a point set on H x W textures, and — built on the first backward — their inverse map: for
+    every texel the list of (point, corner) entries whose bilinear footprint touches it, as a CSR (`row_start` [H*W + 1]
+    int32, `entries` int32 = 4 * point + corner, stable in (point, corner) order).  Corners past the last row / column
+    (weight 0, never read) are EXCLUDED; in-range corners of weight 0 (a point exactly on a texel) are listed.  The UV
+    coordinates of a baked avatar do not change from step to step (the reference's are buffers, uv_decoder.py:310-325): a
+    new UV set simply means a new plan."""
+
+    def __init__(self, uv: torch.Tensor, H: int, W: int):
+        if uv.requires_grad:
+            raise RuntimeError("TexturePlan: uv gets no gradient (the look-up differentiates with respect to the textures only)")
+        if uv.dim() != 2 or uv.shape[1] != 2:
+            raise RuntimeError("TexturePlan: uv must be [N,2]")
+        if int(H) < 1 or int(W) < 1:
+            raise RuntimeError("TexturePlan: H and W must be positive")
+        _on_device(uv, "uv")
+        self.uv = uv.detach().to(torch.float32).contiguous()
+        self.H, self.W, self.N = int(H), int(W), int(uv.shape[0])
+        self._csr = None
+
+    @property
+    def device(self):
+        return self.uv.device
+
+    def corners(self) -> torch.Tensor:
+        """[N,4] int32: the texel index (y * W + x) of every point's four corners, -1 past the border (fr_texture_corners)."""
+        out = torch.empty((self.N, 4), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().fr_texture_corners(self.N, self.uv.data_ptr(), self.H, self.W, out.data_ptr(),
+                                               torch.cuda.current_stream(self.device).cuda_stream)
+        if rc != _lib.FR_OK:
+            raise RuntimeError(f"fr_texture_corners failed: {_lib.last_error()}")
+        return out
+
+    @property
+    def has_csr(self) -> bool:
+        return self._csr is not None
+
+    def csr(self):
+        """(row_start, entries), built once (a stable sort on the device; it synchronises, so not under stream capture)."""
+        if self._csr is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("TexturePlan: the inverse map does not exist yet and cannot be built while a stream is being "
+                                   "captured: call plan.csr() (or run one eager backward) first")
+            flat = self.corners().reshape(-1).long()                                  # index = 4 * point + corner
+            ids = torch.nonzero(flat >= 0).reshape(-1)
+            keys = flat[ids]
+            order = torch.argsort(keys, stable=True)                                  # stable: (point, corner) order per texel
+            counts = torch.bincount(keys, minlength=self.H * self.W)
+            row_start = torch.zeros(self.H * self.W + 1, dtype=torch.int64, device=self.device)
+            row_start[1:] = torch.cumsum(counts, 0)
+            self._csr = (row_start.to(torch.int32).contiguous(), ids[order].to(torch.int32).contiguous())
+        return self._csr
+
+
+def _layers(textures, acts, outs=None, d_outs=None, d_textures=None):
+    arr = (_lib.fr_tex_layer * len(textures))()
+    for i, (t, a) in enumerate(zip(textures, acts)):
+        arr[i].texture = t.data_ptr()
+        arr[i].out = outs[i].data_ptr() if outs is not None else None
+        arr[i].d_out = d_outs[i].data_ptr() if d_outs is not None else None
+        arr[i].d_texture = d_textures[i].data_ptr() if d_textures is not None else None
+        arr[i].channels, arr[i].activation, arr[i].a0, arr[i].a1 = int(t.shape[-3]), int(a.kind), float(a.a0), float(a.a1)
+    return arr
+
+
+class _TextureLookup(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan: TexturePlan, acts, *textures):
+        dev = plan.device
+        for i, t in enumerate(textures):
+            if t.device != dev:
+                raise RuntimeError(f"texture_lookup: texture {i} is on {t.device}, the plan on {dev}")
+        tex = [t.contiguous() for t in textures]
+        outs = [torch.empty((plan.N, t.shape[-3]), dtype=torch.float32, device=dev) for t in tex]
+        with torch.cuda.device(dev):
+            rc = _lib.lib().fr_texture_lookup(plan.N, plan.uv.data_ptr(), plan.H, plan.W, len(tex), _layers(tex, acts, outs=outs),
+                                              torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.FR_OK:
+            raise RuntimeError(f"fr_texture_lookup failed: {_lib.last_error()}")
+        ctx.plan, ctx.acts = plan, acts
+        ctx.save_for_backward(*tex)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *d_outs):
+        plan, tex, dev = ctx.plan, ctx.saved_tensors, ctx.plan.device
+        sel = [i for i, g in enumerate(d_outs) if g is not None and ctx.needs_input_grad[2 + i]]
+        grads = [None] * len(tex)
+        if sel:
+            row_start, entries = plan.csr()
+            g_in = [d_outs[i].to(torch.float32).contiguous() for i in sel]
+            d_tex = [torch.empty(tex[i].shape, dtype=torch.float32, device=dev) for i in sel]   # (planar [C,H,W], contiguous)
+            layers = _layers([tex[i] for i in sel], [ctx.acts[i] for i in sel], d_outs=g_in, d_textures=d_tex)
+            with torch.cuda.device(dev):
+                rc = _lib.lib().fr_texture_lookup_backward(plan.N, plan.uv.data_ptr(), plan.H, plan.W, row_start.data_ptr(),
+                                                           entries.data_ptr(), len(sel), layers,
+                                                           torch.cuda.current_stream(dev).cuda_stream)
+            if rc != _lib.FR_OK:
+                raise RuntimeError(f"fr_texture_lookup_backward failed: {_lib.last_error()}")
+            for i, d in zip(sel, d_tex):
+                grads[i] = d
+        return (None, None, *grads)
+
+
+def texture_lookup(textures, plan: TexturePlan, activations=None):
+    """`_texture_look_up` (uv_decoder.py:179-202) of up to 8 textures in one launch, differentiable with respect to the
+    textures.  `textures`: a list or a dict of [C,H,W] or [1,C,H,W] float32 device tensors (C <= 4, the plan's H x W);
+    `activations`: per texture (same container kind) None or an `Activation` the kernel applies to the texels — the result
+    is that of activating the whole texture first.  Returns, in the same container kind, one [N,C] tensor per texture.
+    Under torch.no_grad() no inverse map is needed (or built)."""
+    if isinstance(textures, dict):
+        names = list(textures)
+        acts = None if activations is None else [activations.get(n) for n in names]
+        return dict(zip(names, texture_lookup([textures[n] for n in names], plan, acts)))
+    tex, acts = validate_textures(textures, plan.H, plan.W, activations)
+    return list(_TextureLookup.apply(plan, acts, *tex))
+
+
+def rotation_activation(texture: torch.Tensor) -> torch.Tensor:
+    """`_rotation_activation` (uv_decoder.py:158-174) on a [3,H,W] or [1,3,H,W] texture -> [4,H,W] / [1,4,H,W]: plain torch
+    (any device), per texel over the channel axis:
+        a = tanh(t) * 2 pi                                       (axis-angle)
+        q = axis_angle_to_quaternion(a)                          (pytorch3d: REAL PART FIRST, (w, x, y, z))
+          = (cos(theta / 2), a * s),  theta = |a|,  s = sin(theta / 2) / theta,  and for theta < 1e-6 the Taylor series
+            s = 0.5 - theta^2 / 48
+        out = (q[3], q[0], q[1], q[2])                           (the reference's shuffle, :166: it is labelled
+                                                                 "xyzr -> rxyz" there, but applied to a real-first
+                                                                 quaternion it emits (z, w, x, y) — restated as it runs)
+    pytorch3d is not installed where this package is developed: like the other pytorch3d restatements this is pinned by
+    the formula of pytorch3d 0.7.7's transforms/rotation_conversions.py, not by running it.  (The reference takes the
+    no-permute branch when the LAST axis of the texture has length 3, i.e. for 3-texel-wide textures; that quirk is not
+    restated.)"""
+    if texture.dim() not in (3, 4) or texture.shape[-3] != 3:
+        raise RuntimeError("rotation_activation: a [3,H,W] or [1,3,H,W] texture")
+    a = torch.tanh(texture) * (2 * math.pi)
+    angles = torch.linalg.vector_norm(a, ord=2, dim=-3, keepdim=True)
+    half = angles * 0.5
+    small = angles.abs() < 1e-6
+    safe = torch.where(small, torch.ones_like(angles), angles)          # (the unselected branch must not divide by zero)
+    s = torch.where(small, 0.5 - (angles * angles) / 48, torch.sin(half) / safe)
+    q = torch.cat([torch.cos(half), a * s], dim=-3)                     # (w, x, y, z)
+    return torch.cat([q.narrow(-3, 3, 1), q.narrow(-3, 0, 3)], dim=-3).contiguous()
+
+
+def gather_attributes_from_texture_dict(texture_dict: dict, plan: TexturePlan, mean_scaling: float, max_scaling: float) -> dict:
+    """`_gather_attribute_from_texture_dict` (uv_decoder.py:109-131): {name: [N,C]} for every texture of the dictionary.
+    'scaling', 'offset' and 'rotation' are activated, 'color' is NOT (the reference activates it outside), any other name
+    is looked up as it is.  One launch."""
+    tex, acts = {}, {}
+    for name, t in texture_dict.items():
+        if name == "scaling":
+            tex[name], acts[name] = t, scaling_activation(mean_scaling, max_scaling)
+        elif name == "offset":
+            tex[name], acts[name] = t, OFFSET_ACTIVATION
+        elif name == "rotation":
+            tex[name], acts[name] = rotation_activation(t), None
+        else:
+            tex[name], acts[name] = t, None
+    return texture_lookup(tex, plan, acts)
+
+
+def gather_attributes(neural_texture: torch.Tensor, plan: TexturePlan, mean_scaling: float, max_scaling: float):
+    """`_gather_attribute` (uv_decoder.py:85-107) on the decoder's [1,11,H,W] output with the channel slices of :225-245:
+    colour 0:3 (tanh * 0.5 / C0), opacity 3:4, scaling 4:7, rotation 7:10, offset 10:11.  Returns (texture_dict, value_dict):
+    the raw slices and the looked-up [N,C] values; the activated textures are never materialised (except rotation's)."""
+    n_ch = sum(c for _, c in TEXTURE_CHANNELS)
+    if neural_texture.dim() != 4 or neural_texture.shape[0] != 1 or neural_texture.shape[1] != n_ch:
+        raise RuntimeError(f"gather_attributes: the decoder output must be [1,{n_ch},H,W]")
+    texture_dict, tex, acts, off = {}, {}, {}, 0
+    for name, c in TEXTURE_CHANNELS:
+        texture_dict[name] = neural_texture[:, off:off + c]
+        off += c
+    for name, t in texture_dict.items():
+        tex[name] = rotation_activation(t) if name == "rotation" else t
+        acts[name] = {"color": COLOR_ACTIVATION, "scaling": scaling_activation(mean_scaling, max_scaling),
+                      "offset": OFFSET_ACTIVATION}.get(name)
+    return texture_dict, texture_lookup(tex, plan, acts)
+
+
+def uv_of_binding(face_index, bary_coords, uv_layout: Optional[tuple] = None) -> torch.Tensor:
+    """`reweight_uvcoords_by_barycoords` (volume_rendering/mesh_sampling.py:202-234, first two columns): the UV coordinates
+    [N,2] float32 of binding points (face index, barycentrics) on a UV layout (verts_uvs [V',2], faces_uvs [F,3]) — by
+    default the shipped head template's (`scenes.head_uv()`).  Tensors in, a tensor on `bary_coords`' device out (numpy
+    arrays give a CPU tensor)."""
+    if uv_layout is None:
+        from . import scenes
+        uv_layout = scenes.head_uv()
+        if uv_layout is None:
+            raise RuntimeError("the head template's UV layout is not in fateavatar_amd/data/head_template_geom.npz")
+    bary = torch.as_tensor(np.asarray(bary_coords) if not isinstance(bary_coords, torch.Tensor) else bary_coords).to(torch.float32)
+    dev = bary.device
+    fi = torch.as_tensor(np.asarray(face_index) if not isinstance(face_index, torch.Tensor) else face_index).to(dev, torch.int64)
+    uvc = torch.as_tensor(np.asarray(uv_layout[0]) if not isinstance(uv_layout[0], torch.Tensor) else uv_layout[0]).to(dev, torch.float32)
+    uvf = torch.as_tensor(np.asarray(uv_layout[1]) if not isinstance(uv_layout[1], torch.Tensor) else uv_layout[1]).to(dev, torch.int64)
+    if bary.dim() != 2 or bary.shape[1] != 3 or fi.shape != (bary.shape[0],):
+        raise RuntimeError("uv_of_binding: face_index [N], bary_coords [N,3]")
+    corners = uvc[uvf[fi]]                                   # [N,3,2]
+    return (bary.unsqueeze(-1) * corners).sum(dim=-2).contiguous()

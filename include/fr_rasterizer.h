@@ -372,6 +372,48 @@ int fr_bind_forward(const fr_binding* b, float* xyz, float* rotation_out, float*
 int fr_bind_backward(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
                      float* d_verts, float* d_offset, float* d_rotation, float* d_scaling, void* hip_stream);
 
+/* ---- Gaussian attributes looked up in UV attribute maps: the per-frame front end of a BAKED FateAvatar (reference
+ * model/uv_decoder.py:179-202, `UVSampling._texture_look_up`: F.grid_sample(texture, 2 uv - 1, mode="bilinear",
+ * padding_mode="border", align_corners=True) once per attribute map, behind the per-texture activations of :133-156;
+ * callers `_gather_attribute` :85-107, `_gather_attribute_from_texture_dict` :109-131, `UVDecoder.forward` :387-542,
+ * `render_from_texture_dict` :564-690, `_export_avatar_model` :342-385).
+ * Up to FR_TEX_MAX_LAYERS planar [C,H,W] float textures of ONE common H x W, C <= 4 each, are sampled at uv [N,2] in one
+ * launch: out[n, c] = sum over the four corners of w * act(texture[c, y, x]), row-major [N,C].  u is x (width), v is y
+ * (height), no flip; coordinates outside [0,1] clip to the border.  The activation is applied to the TEXEL (what activating
+ * the whole texture and then sampling gives):
+ *   FR_TEX_ACT_IDENTITY      t
+ *   FR_TEX_ACT_TANH_SCALE    tanh(t) * a0                         (colour: a0 = 0.5 / C0, :134-138; offset: a0 = 1, :152-156)
+ *   FR_TEX_ACT_SOFTPLUS_CAP  a1 - softplus(-(t + a0) + a1)        (scaling: a0 = mean, a1 = max, :140-149; softplus with
+ *                                                                 torch's defaults: beta 1, linear above 20)
+ * All pointers are device pointers.  No call allocates or synchronises: each can be captured in a HIP graph. */
+#define FR_TEX_MAX_LAYERS 8
+#define FR_TEX_ACT_IDENTITY 0
+#define FR_TEX_ACT_TANH_SCALE 1
+#define FR_TEX_ACT_SOFTPLUS_CAP 2
+typedef struct fr_tex_layer {
+    const float* texture;   /* [C,H,W] raw (not activated) texture */
+    float* out;             /* forward:  [N,C] looked-up values */
+    const float* d_out;     /* backward: [N,C] gradient of `out` */
+    float* d_texture;       /* backward: [C,H,W] gradient of `texture`, every texel written */
+    int32_t channels;       /* C: 1 .. 4 */
+    int32_t activation;     /* FR_TEX_ACT_* */
+    float a0, a1;
+} fr_tex_layer;
+/* corners[n, k] = texel index (y * W + x) of corner k of point n (k = 0 .. 3: (y0,x0), (y0,x1), (y1,x0), (y1,x1), the order
+ * in which the look-up sums them), or -1 for a corner past the last row / column (weight 0, never read).  The plan of the
+ * backward is these indices inverted, once per UV set. */
+int fr_texture_corners(int32_t N, const float* uv, int32_t H, int32_t W, int32_t* corners, void* hip_stream);
+int fr_texture_lookup(int32_t N, const float* uv, int32_t H, int32_t W, int32_t n_layers, const fr_tex_layer* layers,
+                      void* hip_stream);
+/* The backward as a GATHER per texel.  row_start [H*W + 1] and entries [row_start[H*W]] are the CSR of the plan: the
+ * entries of texel t are entries[row_start[t] .. row_start[t+1]), each 4 * point + corner, for every corner
+ * fr_texture_corners reported on t.  d_texture[c, y, x] = act'(texture[c, y, x]) * sum over the texel's entries, in list
+ * order, of w(uv[point], corner) * d_out[point, c] — STORED for every texel of every layer (0 where no point lands): no
+ * zero fill beforehand, no float atomics, the same bits on every run.  `texture` may be NULL for an identity layer.  uv
+ * gets no gradient (the reference's coordinates are buffers). */
+int fr_texture_lookup_backward(int32_t N, const float* uv, int32_t H, int32_t W, const int32_t* row_start,
+                               const int32_t* entries, int32_t n_layers, const fr_tex_layer* layers, void* hip_stream);
+
 /* present[i] = view-space z of means3D[i] > 0.2 (auxiliary.h:154). */
 int fr_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                     uint8_t* present, void* hip_stream);
