@@ -8,6 +8,13 @@ pytorch3d's matrix_to_quaternion and quaternion_multiply, then
     gaussian._xyz      = position + face_normal * shell_len * tanh(_offset)      (:258)
 About forty PyTorch kernels (and their autograd twins) there; `bind_gaussians` is one HIP kernel forward and one
 backward, differentiable w.r.t. verts (the delta blendshapes train through it), offset, rotation and scaling.
+
+`bind_gaussians_face_local` is the same for GaussianAvatars' binding (model/baseline/gaussianavatars.py:144-171), the
+reference's headline baseline: every Gaussian lives in the local frame of one triangle,
+    gaussian._scaling  = _scaling + log(face_scaling[binding])
+    gaussian._rotation = quaternion_multiply(normalize(matrix_to_quaternion(face_orien_mat))[binding], _rotation)
+    gaussian._xyz      = (face_orien_mat[binding] @ _xyz) * face_scaling[binding] + face_center[binding]
+The same two kernels (fr_binding::mode), differentiable w.r.t. verts, the local position, rotation and scaling.
 """
 from __future__ import annotations
 
@@ -117,3 +124,73 @@ def bind_gaussians(verts, faces, face_index, bary_coords, face_scale_canonical, 
     gaussian._rotation / gaussian._scaling before render()."""
     return _Bind.apply(verts, offset, rotation, scaling, faces, face_index, bary_coords, face_scale_canonical, shell_len,
                        resize_scale)
+
+
+def _desc_local(verts, faces, binding, local_xyz, rotation, scaling):
+    b = _lib.fr_binding()   # (zero-filled: bary, offset, face_scale_canonical, shell_len, resize_scale are not read in this mode)
+    b.N, b.V, b.F = binding.shape[0], verts.shape[0], faces.shape[0]
+    b.verts, b.faces, b.face_index = verts.data_ptr(), faces.data_ptr(), binding.data_ptr()
+    b.rotation, b.scaling = rotation.data_ptr(), scaling.data_ptr()
+    b.mode, b.local_xyz = _lib.FR_BIND_FACE_LOCAL, local_xyz.data_ptr()
+    return b
+
+
+class _BindFaceLocal(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts, local_xyz, rotation, scaling, faces, binding):
+        verts, local_xyz = _chk(verts, torch.float32, "verts"), _chk(local_xyz, torch.float32, "local_xyz")
+        rotation, scaling = _chk(rotation, torch.float32, "rotation"), _chk(scaling, torch.float32, "scaling")
+        faces, binding = _chk(faces, torch.int32, "faces"), _chk(binding, torch.int32, "binding")
+        N, dev = binding.shape[0], verts.device
+        if verts.dim() != 2 or local_xyz.shape != (N, 3) or rotation.shape != (N, 4) or scaling.shape != (N, 3):
+            raise RuntimeError("bind_gaussians_face_local: verts [V,3], binding [N], local_xyz [N,3], rotation [N,4], scaling [N,3]")
+        xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        rot = torch.empty((N, 4), dtype=torch.float32, device=dev)
+        scl = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        b = _desc_local(verts, faces, binding, local_xyz, rotation, scaling)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().fr_bind_forward(C.byref(b), xyz.data_ptr(), rot.data_ptr(), scl.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.FR_OK:
+            raise RuntimeError(f"fr_bind_forward failed: {_lib.last_error()}")
+        ctx.save_for_backward(verts, local_xyz, rotation, scaling, faces, binding)
+        from .rasterizer import GradOut   # (the `_fr_grad_out` extension, as _Bind)
+        ctx.grad_slots = (GradOut.of(local_xyz), GradOut.of(rotation), GradOut.of(scaling))
+        return xyz, rot, scl
+
+    @staticmethod
+    def backward(ctx, g_xyz, g_rot, g_scl):
+        verts, local_xyz, rotation, scaling, faces, binding = ctx.saved_tensors
+        dev, N = verts.device, binding.shape[0]
+        need_v, need_l, need_r, need_s = ctx.needs_input_grad[:4]
+        c = lambda g: g.contiguous().float() if g is not None else None  # noqa: E731
+        g_xyz, g_rot, g_scl = c(g_xyz), c(g_rot), c(g_scl)
+        d_verts = torch.zeros_like(verts) if need_v else None
+
+        def out(need, slot, shape):
+            if not need:
+                return None
+            buf = slot.claim()[0] if slot is not None else None   # first backward of the step writes the slot in place
+            if buf is not None and buf.numel() == int(torch.Size(shape).numel()) and buf.is_contiguous():
+                return buf.view(shape)
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+
+        d_loc = out(need_l, ctx.grad_slots[0], (N, 3))
+        d_rot = out(need_r, ctx.grad_slots[1], (N, 4))
+        d_scl = out(need_s, ctx.grad_slots[2], (N, 3))
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        b = _desc_local(verts, faces, binding, local_xyz, rotation, scaling)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().fr_bind_backward_local(C.byref(b), p(g_xyz), p(g_rot), p(g_scl), p(d_verts), p(d_loc), p(d_rot),
+                                                   p(d_scl), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.FR_OK:
+            raise RuntimeError(f"fr_bind_backward_local failed: {_lib.last_error()}")
+        return d_verts, d_loc, d_rot, d_scl, None, None
+
+
+def bind_gaussians_face_local(verts, faces, binding, local_xyz, rotation, scaling):
+    """One frame of model/baseline/gaussianavatars.py:144-171.  verts [V,3] (posed), faces [F,3], binding [N] (the face of
+    every Gaussian), raw local_xyz [N,3] / rotation [N,4] / scaling [N,3].  Returns (xyz [N,3], rotation [N,4],
+    scaling [N,3]): the values the reference assigns to gaussian._xyz / gaussian._rotation / gaussian._scaling before
+    render()."""
+    return _BindFaceLocal.apply(verts, local_xyz, rotation, scaling, faces, binding)

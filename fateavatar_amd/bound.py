@@ -9,6 +9,9 @@ its own work (and stores them for the backward), and the per-Gaussian backward k
 the binding to offset / rotation / scaling (and the posed vertices).  Same expressions from one header
 (csrc/fr_bind_math.hpp), so the results are those of `bind_gaussians` followed by `render_batch`, bit for bit in the
 forward and to atomic-summation order in the backward.
+
+The same holds for GaussianAvatars' face-local binding (model/baseline/gaussianavatars.py:144-171,
+`binding.bind_gaussians_face_local`): hand `render_bound_batch` a `FaceLocalBinding` instead of a `MeshBinding`.
 """
 from __future__ import annotations
 
@@ -17,7 +20,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from .binding import _chk, _desc
+from .binding import _chk, _desc, _desc_local
 from .rasterizer import (_GRAD_NAMES, _any_grad, _backward_args, _forward_args, _forward_batch, _FrameGrads, _per_view_outputs,
                          _pick_forward_only, _SavedFrame, rasterize_gaussians_backward_batch)
 from .render import _result, _screenspace_points, _settings
@@ -34,9 +37,26 @@ class MeshBinding(NamedTuple):
     resize_scale: bool = True
 
 
+class FaceLocalBinding(NamedTuple):
+    """GaussianAvatars' binding (model/baseline/gaussianavatars.py:52-60,144-171): the mesh topology and the face of every
+    Gaussian.  The per-Gaussian position in that face's frame is a parameter (the holder's `_xyz`), not part of this."""
+    faces: torch.Tensor                   # [F,3] int32
+    face_index: torch.Tensor              # [N]   int32 (the reference's `binding`)
+
+
+def _descriptor(mb, verts, first, rotation, scaling):
+    """The fr_binding of one view; `first` is the binding's own per-Gaussian parameter: offset [N,1] (MeshBinding) or the
+    local position [N,3] (FaceLocalBinding)."""
+    if isinstance(mb, FaceLocalBinding):
+        return _desc_local(verts, mb.faces, mb.face_index, first, rotation, scaling)
+    return _desc(verts, mb.faces, mb.face_index, mb.bary_coords, mb.face_scale_canonical, first, rotation, scaling, mb.shell_len,
+                 mb.resize_scale)
+
+
 class _RasterizeBoundBatch(torch.autograd.Function):
     """Tensor arguments per view: (verts, offset, rotation, scaling, means2D, sh, opacities) — the RAW parameters, as
-    render() hands them over with `fused_activations`.  Outputs per view: those of `_SavedFrame`."""
+    render() hands them over with `fused_activations`; with a FaceLocalBinding the local position [N,3] stands where the
+    offset stands.  Outputs per view: those of `_SavedFrame`."""
     PER_VIEW = 7
 
     @staticmethod
@@ -53,13 +73,16 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             rotation, scaling = _chk(rotation, torch.float32, "rotation"), _chk(scaling, torch.float32, "scaling")
             checked.append((verts, offset, rotation, scaling))   # (what the descriptor points at: alive until the launch, saved for the backward)
             N, dev = mb.face_index.shape[0], verts.device
-            if verts.dim() != 2 or offset.numel() != N or rotation.shape != (N, 4) or scaling.shape != (N, 3) or \
-                    mb.bary_coords.shape != (N, 3):
-                raise RuntimeError("render_bound_batch: verts [V,3], offset [N,1], rotation [N,4], scaling [N,3], bary [N,3]")
-            if mb.resize_scale and (mb.face_scale_canonical is None or mb.face_scale_canonical.numel() != mb.faces.shape[0]):
-                raise RuntimeError("render_bound_batch: resize_scale needs face_scale_canonical [F,1]")
-            descs.append(_desc(verts, mb.faces, mb.face_index, mb.bary_coords, mb.face_scale_canonical, offset, rotation, scaling,
-                               mb.shell_len, mb.resize_scale))
+            if isinstance(mb, FaceLocalBinding):
+                if verts.dim() != 2 or offset.shape != (N, 3) or rotation.shape != (N, 4) or scaling.shape != (N, 3):
+                    raise RuntimeError("render_bound_batch: verts [V,3], _xyz [N,3], rotation [N,4], scaling [N,3]")
+            else:
+                if verts.dim() != 2 or offset.numel() != N or rotation.shape != (N, 4) or scaling.shape != (N, 3) or \
+                        mb.bary_coords.shape != (N, 3):
+                    raise RuntimeError("render_bound_batch: verts [V,3], offset [N,1], rotation [N,4], scaling [N,3], bary [N,3]")
+                if mb.resize_scale and (mb.face_scale_canonical is None or mb.face_scale_canonical.numel() != mb.faces.shape[0]):
+                    raise RuntimeError("render_bound_batch: resize_scale needs face_scale_canonical [F,1]")
+            descs.append(_descriptor(mb, verts, offset, rotation, scaling))
             # the bound values: written by the preprocess kernel, read again by the backward
             xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
             rot = torch.empty((N, 4), dtype=torch.float32, device=dev)
@@ -101,9 +124,11 @@ class _RasterizeBoundBatch(torch.autograd.Function):
                     return b.view(shape)
                 return torch.empty(shape, dtype=torch.float32, device=dev)
 
-            descs.append(_desc(verts, mb.faces, mb.face_index, mb.bary_coords, mb.face_scale_canonical, offset, rotation, scaling,
-                               mb.shell_len, mb.resize_scale))
-            bgrads.append({"d_verts": torch.zeros_like(verts) if need_v else None, "d_offset": buf(need_o, "d_offset", (N,)),
+            descs.append(_descriptor(mb, verts, offset, rotation, scaling))
+            # (the slot of the binding's own parameter is claimed as "d_offset" in both modes; the kernel's name differs)
+            first = {"d_local_xyz": buf(need_o, "d_offset", (N, 3))} if isinstance(mb, FaceLocalBinding) else \
+                {"d_offset": buf(need_o, "d_offset", (N,))}
+            bgrads.append({"d_verts": torch.zeros_like(verts) if need_v else None, **first,
                            "d_rotation": buf(need_r, "d_rotation", (N, 4)), "d_scaling": buf(need_s, "d_scaling", (N, 3))})
         res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=[f.grads.want for f in ctx.frames],
                                                  outs=outs, stats=[f.stats for f in ctx.frames], bindings=descs, bind_grads=bgrads,
@@ -111,14 +136,15 @@ class _RasterizeBoundBatch(torch.autograd.Function):
         flat = [None, None, None, None, None]
         for grads, b, offset_shape in zip(res, bgrads, ctx.offset_shapes):
             g = dict(zip(_GRAD_NAMES, grads))
-            d_off = b["d_offset"].view(offset_shape) if b["d_offset"] is not None else None
+            d_off = b["d_offset"] if "d_offset" in b else b["d_local_xyz"]
+            d_off = d_off.view(offset_shape) if d_off is not None else None
             # (fresh view objects: AccumulateGrad adopts a gradient without a copy only if nobody else references it)
             fresh = lambda t: t.view(t.shape) if t is not None else None  # noqa: E731
             flat += [b["d_verts"], d_off, fresh(b["d_rotation"]), fresh(b["d_scaling"]), g["dL_dmeans2D"], g["dL_dsh"], g["dL_dopacity"]]
         return tuple(flat)
 
 
-def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding: MeshBinding, bg_colors, scaling_modifier=1.0, slots=None,
+def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding, bg_colors, scaling_modifier=1.0, slots=None,
                        depth_alpha=False):
     """`bind_gaussians` + `render_batch` for K views in one launch chain without binding kernels.
 
@@ -128,25 +154,42 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding: MeshBinding
     (xyz, rotation, scaling) the reference assigns to the Gaussians before render() (model/fateavatar.py:256-258) as plain
     kernel OUTPUTS, DETACHED from autograd: gradients reach offset / rotation / scaling / verts through the image only.  A
     regulariser on the bound values themselves needs the differentiable stand-alone op (`binding.bind_gaussians`, what
-    `AvatarStep(fold_binding=False)` renders through).  `depth_alpha=True` (extension): "depth" and "alpha" as in render()."""
+    `AvatarStep(fold_binding=False)` renders through).  `depth_alpha=True` (extension): "depth" and "alpha" as in render().
+
+    `binding`: a `MeshBinding`, or a `FaceLocalBinding` (GaussianAvatars, model/baseline/gaussianavatars.py:144-171;
+    stand-alone op `binding.bind_gaussians_face_local`).  The holders then carry the local position `_xyz` [N,3] where
+    FateAvatar's carry `_offset`, and the frame is rendered with their `active_sh_degree` (the reference hands render() a
+    GaussianModel(sh_degree=active_sh_degree), :157) from `get_features` [N,M,3], M >= (active_sh_degree + 1)^2."""
     K = len(viewpoint_cameras)
     if not 1 <= K <= _lib.FR_MAX_BATCH:
         raise RuntimeError(f"render_bound_batch: 1 .. {_lib.FR_MAX_BATCH} views")
     if not isinstance(pcs, (list, tuple)):
         pcs = [pcs] * K
+    local = isinstance(binding, FaceLocalBinding)
+    if local:
+        for pc in pcs:
+            if getattr(pc, "_xyz", None) is None:
+                raise RuntimeError("render_bound_batch: a face-local binding (FaceLocalBinding) needs a holder with the local "
+                                   f"positions `_xyz` [N,3]; {type(pc).__name__} has none")
     if isinstance(bg_colors, torch.Tensor):
         bg_colors = [bg_colors] * K
     if isinstance(posed_verts, torch.Tensor):
         posed_verts = [posed_verts] * K
-    mb = MeshBinding(_chk(binding.faces, torch.int32, "faces"), _chk(binding.face_index, torch.int32, "face_index"),
-                     _chk(binding.bary_coords, torch.float32, "bary_coords"),
-                     _chk(binding.face_scale_canonical, torch.float32, "face_scale_canonical")
-                     if binding.face_scale_canonical is not None else None, float(binding.shell_len), bool(binding.resize_scale))
+    if local:
+        mb = FaceLocalBinding(_chk(binding.faces, torch.int32, "faces"), _chk(binding.face_index, torch.int32, "face_index"))
+    else:
+        mb = MeshBinding(_chk(binding.faces, torch.int32, "faces"), _chk(binding.face_index, torch.int32, "face_index"),
+                         _chk(binding.bary_coords, torch.float32, "bary_coords"),
+                         _chk(binding.face_scale_canonical, torch.float32, "face_scale_canonical")
+                         if binding.face_scale_canonical is not None else None, float(binding.shell_len), bool(binding.resize_scale))
     settings, tensors, points = [], [], []
     for cam, pc, bg, verts in zip(viewpoint_cameras, pcs, bg_colors, posed_verts):
         sp = _screenspace_points(pc._scaling, pc)
-        settings.append(_settings(cam, pc, bg, scaling_modifier))
-        tensors += [verts, pc._offset, pc._rotation, pc._scaling, sp, pc.get_features, pc._opacity]
+        rs = _settings(cam, pc, bg, scaling_modifier)
+        if local:
+            rs = rs._replace(sh_degree=int(getattr(pc, "active_sh_degree", pc.max_sh_degree)))
+        settings.append(rs)
+        tensors += [verts, pc._xyz if local else pc._offset, pc._rotation, pc._scaling, sp, pc.get_features, pc._opacity]
         points.append(sp)
     res = _RasterizeBoundBatch.apply(settings, [mb] * K, list(range(K)) if slots is None else list(slots),
                                      _pick_forward_only(tensors), bool(depth_alpha), *tensors)

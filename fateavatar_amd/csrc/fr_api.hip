@@ -22,6 +22,22 @@ int fail_msg(int code, const char* msg)
     return code;
 }
 
+// (also what a frame rendered from its binding is checked with, before anything is enqueued)
+static int check_binding(const fr_binding* b)
+{
+    if (!b || b->N < 0 || b->V < 0 || b->F < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: null or negative sizes");
+    if (b->mode != FR_BIND_SHELL && b->mode != FR_BIND_FACE_LOCAL)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: unknown mode (FR_BIND_SHELL or FR_BIND_FACE_LOCAL)");
+    if (b->N == 0) return FR_OK;
+    if (!b->verts || !b->faces || !b->face_index || !b->rotation || !b->scaling)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: missing array");
+    if (b->mode == FR_BIND_FACE_LOCAL) {
+        if (!b->local_xyz) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: FR_BIND_FACE_LOCAL needs local_xyz");
+    } else if (!b->bary || !b->offset || (b->resize_scale && !b->face_scale_canonical))
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: missing array");
+    return FR_OK;
+}
+
 static int check_frame(const fr_params* prm, const fr_inputs* in, bool forward)
 {
     if (!prm || !in) return fail_msg(FR_ERR_INVALID_ARGUMENT, "null params/inputs");
@@ -47,9 +63,9 @@ static int check_frame(const fr_params* prm, const fr_inputs* in, bool forward)
         const fr_binding& b = *prm->aux->binding;
         if (!(prm->flags & FR_FLAG_RAW_ACTIVATIONS) || !sr)
             return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_aux::binding needs FR_FLAG_RAW_ACTIVATIONS and scales + rotations");
-        if (b.N != prm->P || !b.verts || !b.faces || !b.face_index || !b.bary || !b.offset || !b.rotation || !b.scaling ||
-            (b.resize_scale && !b.face_scale_canonical))
-            return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_aux::binding: N must equal P and every array must be given");
+        if (b.N != prm->P) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_aux::binding: N must equal P");
+        const int rc = check_binding(&b);
+        if (rc) return rc;
     }
     return FR_OK;
 }
@@ -391,15 +407,6 @@ int fr_knn_nearest_dist2(int32_t P, const float* points, float* out, void* works
     return launch_knn(P, points, out, workspace, workspace_bytes, static_cast<hipStream_t>(stream), 1);
 }
 
-static int check_binding(const fr_binding* b)
-{
-    if (!b || b->N < 0 || b->V < 0 || b->F < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: null or negative sizes");
-    if (b->N > 0 && (!b->verts || !b->faces || !b->face_index || !b->bary || !b->offset || !b->rotation || !b->scaling ||
-                     (b->resize_scale && !b->face_scale_canonical)))
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: missing array");
-    return FR_OK;
-}
-
 int fr_face_scale(int32_t V, int32_t F, const float* verts, const int32_t* faces, float* out_scale, void* stream)
 {
     if (V < 0 || F < 0 || (F > 0 && (!verts || !faces || !out_scale))) return fail_msg(FR_ERR_INVALID_ARGUMENT, "bad argument");
@@ -419,7 +426,19 @@ int fr_bind_backward(const fr_binding* b, const float* g_xyz, const float* g_rot
 {
     int rc = check_binding(b);
     if (rc) return rc;
-    return launch_bind_backward(*b, g_xyz, g_rotation, g_scaling, d_verts, d_offset, d_rotation, d_scaling,
+    if (b->mode != FR_BIND_SHELL)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_bind_backward: a FR_BIND_FACE_LOCAL binding goes through fr_bind_backward_local");
+    return launch_bind_backward(*b, g_xyz, g_rotation, g_scaling, d_verts, d_offset, d_rotation, d_scaling, nullptr,
+                                static_cast<hipStream_t>(stream));
+}
+
+int fr_bind_backward_local(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
+                           float* d_verts, float* d_local_xyz, float* d_rotation, float* d_scaling, void* stream)
+{
+    int rc = check_binding(b);
+    if (rc) return rc;
+    if (b->mode != FR_BIND_FACE_LOCAL) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_bind_backward_local: the binding is not FR_BIND_FACE_LOCAL");
+    return launch_bind_backward(*b, g_xyz, g_rotation, g_scaling, d_verts, nullptr, d_rotation, d_scaling, d_local_xyz,
                                 static_cast<hipStream_t>(stream));
 }
 

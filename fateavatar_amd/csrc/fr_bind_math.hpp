@@ -6,6 +6,12 @@
 // reference: model/fateavatar.py:225-258 with volume_rendering/mesh_compute.py:27-59 and pytorch3d 0.7.7's
 // matrix_to_quaternion / quaternion_multiply / standardize_quaternion.  Every translation unit that includes this is
 // built with -ffp-contract=off: the expressions are in the oracle's operation order.
+//
+// Two bindings share the face frame and the quaternion code (BindArgs::mode, the same for every Gaussian of a launch):
+//   FR_BIND_SHELL       FateAvatar's own: barycentric point + shell offset along the face normal (bind_one_fwd / _bwd)
+//   FR_BIND_FACE_LOCAL  GaussianAvatars': a free position in the face's local frame (bind_local_fwd / _bwd;
+//                       model/baseline/gaussianavatars.py:144-171)
+// bind_fwd / bind_bwd pick by the mode; the kernels call those (and bind_bwd_zero for a Gaussian without a gradient).
 #pragma once
 #include "fr_common.hpp"
 
@@ -23,6 +29,8 @@ struct BindArgs {
     const float* offset;      // [N]
     const float* rotation;    // [N,4]
     const float* scaling;     // [N,3]
+    int mode;                 // FR_BIND_SHELL / FR_BIND_FACE_LOCAL (wave-uniform: a kernel argument)
+    const float* local_xyz;   // [N,3] FR_BIND_FACE_LOCAL: position in the face's frame (bary .. offset are not read)
 };
 
 struct Vec3 {
@@ -109,6 +117,107 @@ __device__ __forceinline__ QuatSel frame_to_quaternion(const FaceFrame& f)
     return s;
 }
 
+// pytorch3d quaternion_multiply: Hamilton product a (x) b with the real part made non-negative
+__device__ __forceinline__ void quat_multiply(const float a[4], const float b[4], float out[4])
+{
+    const float aw = a[0], ax = a[1], ay = a[2], az = a[3];
+    const float bw = b[0], bx = b[1], by = b[2], bz = b[3];
+    const float o[4] = {aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                        aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw};
+    const float sg = o[0] < 0.f ? -1.f : 1.f;
+    for (int k = 0; k < 4; k++) out[k] = sg * o[k];
+}
+// its gradient: dL/d(out) in, dL/da and dL/db out
+__device__ __forceinline__ void quat_multiply_bwd(const float a[4], const float b[4], const float g_out[4], float da[4], float db[4])
+{
+    const float aw = a[0], ax = a[1], ay = a[2], az = a[3];
+    const float bw = b[0], bx = b[1], by = b[2], bz = b[3];
+    const float ow = aw * bw - ax * bx - ay * by - az * bz;
+    const float sg = ow < 0.f ? -1.f : 1.f;
+    const float gw = sg * g_out[0], gx = sg * g_out[1], gy = sg * g_out[2], gz = sg * g_out[3];
+    db[0] = gw * aw + gx * ax + gy * ay + gz * az;
+    db[1] = -gw * ax + gx * aw + gy * az - gz * ay;
+    db[2] = -gw * ay - gx * az + gy * aw + gz * ax;
+    db[3] = -gw * az + gx * ay - gy * ax + gz * aw;
+    da[0] = gw * bw + gx * bx + gy * by + gz * bz;
+    da[1] = -gw * bx + gx * bw - gy * bz + gz * by;
+    da[2] = -gw * by + gx * bz + gy * bw - gz * bx;
+    da[3] = -gw * bz - gx * by + gy * bx + gz * bw;
+}
+
+// gradient of the face quaternion (frame_to_quaternion's q) on to the frame's axes: through standardize, the selected
+// candidate row and the matrix entries it reads.  `dq` is consumed.
+__device__ __forceinline__ void frame_to_quaternion_bwd(const QuatSel& qs, float dq[4], Vec3& da0, Vec3& da1, Vec3& da2)
+{
+    // through standardize + the selected candidate row: q_k = sgn * num_k / den
+    float dnum[4], dden = 0.f;
+    for (int k = 0; k < 4; k++) {
+        dq[k] *= qs.sgn;
+        dnum[k] = dq[k] / qs.den;
+        dden -= dq[k] * qs.num[k] / (qs.den * qs.den);
+    }
+    float dqa = (qs.qa > 0.1f) ? 2.0f * dden : 0.f;   // den = 2 max(qa, 0.1)
+    dqa += 2.0f * qs.qa * dnum[qs.sel];               // diagonal numerator qa^2
+    const float dx = qs.qa > 0.f ? dqa / (2.0f * qs.qa) : 0.f;   // qa = sqrt(x), zero subgradient at x <= 0
+    // x_sel = 1 +- m00 +- m11 +- m22
+    const float s00 = (qs.sel == 0 || qs.sel == 1) ? 1.f : -1.f;
+    const float s11 = (qs.sel == 0 || qs.sel == 2) ? 1.f : -1.f;
+    const float s22 = (qs.sel == 0 || qs.sel == 3) ? 1.f : -1.f;
+    float dm[3][3] = {{s00 * dx, 0, 0}, {0, s11 * dx, 0}, {0, 0, s22 * dx}};  // dm[r][c]
+    switch (qs.sel) {
+        case 0:  // num = (diag, m21 - m12, m02 - m20, m10 - m01)
+            dm[2][1] += dnum[1], dm[1][2] -= dnum[1], dm[0][2] += dnum[2], dm[2][0] -= dnum[2], dm[1][0] += dnum[3], dm[0][1] -= dnum[3];
+            break;
+        case 1:  // (m21 - m12, diag, m10 + m01, m02 + m20)
+            dm[2][1] += dnum[0], dm[1][2] -= dnum[0], dm[1][0] += dnum[2], dm[0][1] += dnum[2], dm[0][2] += dnum[3], dm[2][0] += dnum[3];
+            break;
+        case 2:  // (m02 - m20, m10 + m01, diag, m12 + m21)
+            dm[0][2] += dnum[0], dm[2][0] -= dnum[0], dm[1][0] += dnum[1], dm[0][1] += dnum[1], dm[1][2] += dnum[3], dm[2][1] += dnum[3];
+            break;
+        default:  // (m10 - m01, m20 + m02, m21 + m12, diag)
+            dm[1][0] += dnum[0], dm[0][1] -= dnum[0], dm[2][0] += dnum[1], dm[0][2] += dnum[1], dm[2][1] += dnum[2], dm[1][2] += dnum[2];
+            break;
+    }
+    // m[r][c] = a_c[r]
+    da0 = add(da0, Vec3{dm[0][0], dm[1][0], dm[2][0]});
+    da1 = add(da1, Vec3{dm[0][1], dm[1][1], dm[2][1]});
+    da2 = add(da2, Vec3{dm[0][2], dm[1][2], dm[2][2]});
+}
+
+// gradients of the frame's axes (and of length(e1), `dl1`) on to the two edges: mesh_compute.py:45-47, last to first
+__device__ __forceinline__ void face_frame_bwd(const FaceFrame& f, Vec3 da0, Vec3 da1, Vec3 da2, float dl1, Vec3& de1, Vec3& de2)
+{
+    {   // a2 = -normalize(c2), c2 = a1 x a0
+        const Vec3 y = {-f.a2.x, -f.a2.y, -f.a2.z};
+        const Vec3 dc2 = safe_normalize_bwd(Vec3{-da2.x, -da2.y, -da2.z}, y, f.lc2, f.kc2);
+        da1 = add(da1, cross3(f.a0, dc2));
+        da0 = add(da0, cross3(dc2, f.a1));
+    }
+    {   // a1 = normalize(c1), c1 = a0 x e2
+        const Vec3 dc1 = safe_normalize_bwd(da1, f.a1, f.lc1, f.kc1);
+        da0 = add(da0, cross3(f.e2, dc1));
+        de2 = add(de2, cross3(dc1, f.a0));
+    }
+    {   // a0 = normalize(e1); s0 = length(e1)
+        de1 = add(de1, safe_normalize_bwd(da0, f.a0, f.l1, f.k1));
+        if (!f.k1) de1 = add(de1, mul(f.a0, dl1));
+    }
+}
+
+// edge gradients on to the face's three vertices (e1 = v1 - v0, e2 = v2 - v0), then the float atomics of dL/dverts
+__device__ __forceinline__ void scatter_vertex_grads(float* d_verts, int i0, int i1, int i2, Vec3 dv0, Vec3 dv1, Vec3 dv2, Vec3 de1,
+                                                     Vec3 de2)
+{
+    dv1 = add(dv1, de1);
+    dv2 = add(dv2, de2);
+    dv0 = sub(dv0, add(de1, de2));
+    if (d_verts) {
+        atomic_add_f32(d_verts + 3 * i0, dv0.x), atomic_add_f32(d_verts + 3 * i0 + 1, dv0.y), atomic_add_f32(d_verts + 3 * i0 + 2, dv0.z);
+        atomic_add_f32(d_verts + 3 * i1, dv1.x), atomic_add_f32(d_verts + 3 * i1 + 1, dv1.y), atomic_add_f32(d_verts + 3 * i1 + 2, dv1.z);
+        atomic_add_f32(d_verts + 3 * i2, dv2.x), atomic_add_f32(d_verts + 3 * i2 + 1, dv2.y), atomic_add_f32(d_verts + 3 * i2 + 2, dv2.z);
+    }
+}
+
 // forward of one Gaussian: what the reference assigns to gaussian._xyz / _rotation / _scaling before render()
 __device__ __forceinline__ void bind_one_fwd(const BindArgs& a, int n, float xyz[3], float rot[4], float scl[3])
 {
@@ -126,12 +235,8 @@ __device__ __forceinline__ void bind_one_fwd(const BindArgs& a, int n, float xyz
     xyz[2] = pos.z + nrm.z * a.shell_len * t;
     // rotation: face quaternion (x) own quaternion, real part made non-negative
     const QuatSel qs = frame_to_quaternion(f);
-    const float aw = qs.q[0], ax = qs.q[1], ay = qs.q[2], az = qs.q[3];
-    const float bw = a.rotation[4 * n], bx = a.rotation[4 * n + 1], by = a.rotation[4 * n + 2], bz = a.rotation[4 * n + 3];
-    const float o[4] = {aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
-                        aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw};
-    const float sg = o[0] < 0.f ? -1.f : 1.f;
-    for (int k = 0; k < 4; k++) rot[k] = sg * o[k];
+    const float r[4] = {a.rotation[4 * n], a.rotation[4 * n + 1], a.rotation[4 * n + 2], a.rotation[4 * n + 3]};
+    quat_multiply(qs.q, r, rot);
     // scale: log of the face's stretch relative to the canonical mesh
     const float ls = a.resize_scale ? logf(f.scale / a.canon[fi]) : 0.f;
     for (int k = 0; k < 3; k++) scl[k] = a.scaling[3 * n + k] + ls;
@@ -143,12 +248,15 @@ struct BindGrads {
     float* d_offset;    // [N]   written
     float* d_rotation;  // [N,4] written
     float* d_scaling;   // [N,3] written
+    float* d_local_xyz; // [N,3] written (FR_BIND_FACE_LOCAL; d_offset is the shell mode's)
 };
 
 // a Gaussian without any gradient (culled by the frame): zero rows, nothing for the vertices
-__device__ __forceinline__ void bind_one_bwd_zero(int n, const BindGrads& o)
+__device__ __forceinline__ void bind_bwd_zero(int n, const BindGrads& o)
 {
     if (o.d_offset) o.d_offset[n] = 0.f;
+    if (o.d_local_xyz)
+        for (int k = 0; k < 3; k++) o.d_local_xyz[3 * n + k] = 0.f;
     if (o.d_rotation)
         for (int k = 0; k < 4; k++) o.d_rotation[4 * n + k] = 0.f;
     if (o.d_scaling)
@@ -193,81 +301,130 @@ __device__ __forceinline__ void bind_one_bwd(const BindArgs& a, int n, const flo
     const float b0 = a.bary[3 * n], b1 = a.bary[3 * n + 1], b2 = a.bary[3 * n + 2];
     Vec3 dv0 = mul(gx, b0), dv1 = mul(gx, b1), dv2 = mul(gx, b2);
 
-    // ---- rotation: out = sg * (qf (x) r)
+    // ---- rotation: out = standardize(qf (x) r)
     const QuatSel qs = frame_to_quaternion(f);
-    const float aw = qs.q[0], ax = qs.q[1], ay = qs.q[2], az = qs.q[3];
-    const float bw = a.rotation[4 * n], bx = a.rotation[4 * n + 1], by = a.rotation[4 * n + 2], bz = a.rotation[4 * n + 3];
-    const float ow = aw * bw - ax * bx - ay * by - az * bz;
-    const float sg = ow < 0.f ? -1.f : 1.f;
-    float g[4];
-    for (int k = 0; k < 4; k++) g[k] = sg * g_rot[k];
-    const float gw = g[0], gxq = g[1], gy = g[2], gz = g[3];
-    if (o.d_rotation) {
-        o.d_rotation[4 * n] = gw * aw + gxq * ax + gy * ay + gz * az;
-        o.d_rotation[4 * n + 1] = -gw * ax + gxq * aw + gy * az - gz * ay;
-        o.d_rotation[4 * n + 2] = -gw * ay - gxq * az + gy * aw + gz * ax;
-        o.d_rotation[4 * n + 3] = -gw * az + gxq * ay - gy * ax + gz * aw;
-    }
-    float dq[4] = {gw * bw + gxq * bx + gy * by + gz * bz, -gw * bx + gxq * bw - gy * bz + gz * by,
-                   -gw * by + gxq * bz + gy * bw - gz * bx, -gw * bz - gxq * by + gy * bx + gz * bw};
-    // through standardize + the selected candidate row: q_k = sgn * num_k / den
-    float dnum[4], dden = 0.f;
-    for (int k = 0; k < 4; k++) {
-        dq[k] *= qs.sgn;
-        dnum[k] = dq[k] / qs.den;
-        dden -= dq[k] * qs.num[k] / (qs.den * qs.den);
-    }
-    float dqa = (qs.qa > 0.1f) ? 2.0f * dden : 0.f;   // den = 2 max(qa, 0.1)
-    dqa += 2.0f * qs.qa * dnum[qs.sel];               // diagonal numerator qa^2
-    const float dx = qs.qa > 0.f ? dqa / (2.0f * qs.qa) : 0.f;   // qa = sqrt(x), zero subgradient at x <= 0
-    // x_sel = 1 +- m00 +- m11 +- m22
-    const float s00 = (qs.sel == 0 || qs.sel == 1) ? 1.f : -1.f;
-    const float s11 = (qs.sel == 0 || qs.sel == 2) ? 1.f : -1.f;
-    const float s22 = (qs.sel == 0 || qs.sel == 3) ? 1.f : -1.f;
-    float dm[3][3] = {{s00 * dx, 0, 0}, {0, s11 * dx, 0}, {0, 0, s22 * dx}};  // dm[r][c]
-    switch (qs.sel) {
-        case 0:  // num = (diag, m21 - m12, m02 - m20, m10 - m01)
-            dm[2][1] += dnum[1], dm[1][2] -= dnum[1], dm[0][2] += dnum[2], dm[2][0] -= dnum[2], dm[1][0] += dnum[3], dm[0][1] -= dnum[3];
-            break;
-        case 1:  // (m21 - m12, diag, m10 + m01, m02 + m20)
-            dm[2][1] += dnum[0], dm[1][2] -= dnum[0], dm[1][0] += dnum[2], dm[0][1] += dnum[2], dm[0][2] += dnum[3], dm[2][0] += dnum[3];
-            break;
-        case 2:  // (m02 - m20, m10 + m01, diag, m12 + m21)
-            dm[0][2] += dnum[0], dm[2][0] -= dnum[0], dm[1][0] += dnum[1], dm[0][1] += dnum[1], dm[1][2] += dnum[3], dm[2][1] += dnum[3];
-            break;
-        default:  // (m10 - m01, m20 + m02, m21 + m12, diag)
-            dm[1][0] += dnum[0], dm[0][1] -= dnum[0], dm[2][0] += dnum[1], dm[0][2] += dnum[1], dm[2][1] += dnum[2], dm[1][2] += dnum[2];
-            break;
-    }
-    // m[r][c] = a_c[r]
-    da0 = add(da0, Vec3{dm[0][0], dm[1][0], dm[2][0]});
-    da1 = add(da1, Vec3{dm[0][1], dm[1][1], dm[2][1]});
-    da2 = add(da2, Vec3{dm[0][2], dm[1][2], dm[2][2]});
+    const float r[4] = {a.rotation[4 * n], a.rotation[4 * n + 1], a.rotation[4 * n + 2], a.rotation[4 * n + 3]};
+    float dq[4], dr[4];
+    quat_multiply_bwd(qs.q, r, g_rot, dq, dr);
+    if (o.d_rotation)
+        for (int k = 0; k < 4; k++) o.d_rotation[4 * n + k] = dr[k];
+    frame_to_quaternion_bwd(qs, dq, da0, da1, da2);
+    face_frame_bwd(f, da0, da1, da2, dl1, de1, de2);
+    scatter_vertex_grads(o.d_verts, i0, i1, i2, dv0, dv1, dv2, de1, de2);
+}
 
-    // ---- face frame (mesh_compute.py:45-47), last to first
-    {   // a2 = -normalize(c2), c2 = a1 x a0
-        const Vec3 y = {-f.a2.x, -f.a2.y, -f.a2.z};
-        const Vec3 dc2 = safe_normalize_bwd(Vec3{-da2.x, -da2.y, -da2.z}, y, f.lc2, f.kc2);
-        da1 = add(da1, cross3(f.a0, dc2));
-        da0 = add(da0, cross3(dc2, f.a1));
+// ---------------------------------------------------------------------------------------------------------------------
+// FR_BIND_FACE_LOCAL — GaussianAvatars' binding (model/baseline/gaussianavatars.py:144-171): with R = [a0 a1 a2], s the
+// face scale and c the mean of the face's three vertices,
+//     xyz = (R local_xyz) * s + c;  rotation = standardize(normalize(q_face) (x) rotation);  scaling = scaling + log(s)
+// normalize = F.normalize: q / max(|q|, 1e-12).
+constexpr float kNormEps = 1e-12f;
+
+struct UnitQuat {
+    float q[4];
+    float len;      // max(|q|, eps)
+    bool clamped;   // the length did not depend on q
+};
+__device__ __forceinline__ UnitQuat normalize_quat(const float q[4])
+{
+    UnitQuat u;
+    const float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    u.clamped = !(n > kNormEps);
+    u.len = fmaxf(n, kNormEps);
+    for (int k = 0; k < 4; k++) u.q[k] = q[k] / u.len;
+    return u;
+}
+
+__device__ __forceinline__ void bind_local_fwd(const BindArgs& a, int n, float xyz[3], float rot[4], float scl[3])
+{
+    const int fi = a.face_index[n];
+    const int i0 = a.faces[3 * fi], i1 = a.faces[3 * fi + 1], i2 = a.faces[3 * fi + 2];
+    const Vec3 v0 = load3(a.verts, i0), v1 = load3(a.verts, i1), v2 = load3(a.verts, i2);
+    const FaceFrame f = face_frame(v0, v1, v2);
+    // position: the local point turned into the face's frame, stretched by the face scale, moved to the face centre
+    const Vec3 l = load3(a.local_xyz, n);
+    const Vec3 u = {f.a0.x * l.x + f.a1.x * l.y + f.a2.x * l.z, f.a0.y * l.x + f.a1.y * l.y + f.a2.y * l.z,
+                    f.a0.z * l.x + f.a1.z * l.y + f.a2.z * l.z};
+    xyz[0] = u.x * f.scale + (v0.x + v1.x + v2.x) / 3.0f;
+    xyz[1] = u.y * f.scale + (v0.y + v1.y + v2.y) / 3.0f;
+    xyz[2] = u.z * f.scale + (v0.z + v1.z + v2.z) / 3.0f;
+    // rotation: normalised face quaternion (x) own quaternion, real part made non-negative
+    const QuatSel qs = frame_to_quaternion(f);
+    const UnitQuat uq = normalize_quat(qs.q);
+    const float r[4] = {a.rotation[4 * n], a.rotation[4 * n + 1], a.rotation[4 * n + 2], a.rotation[4 * n + 3]};
+    quat_multiply(uq.q, r, rot);
+    // scale: log of the face scale itself
+    const float ls = logf(f.scale);
+    for (int k = 0; k < 3; k++) scl[k] = a.scaling[3 * n + k] + ls;
+}
+
+// gradients of local_xyz / rotation / scaling written, dL/dverts added: through the centre, R (position and normalised
+// quaternion), s and log s
+__device__ __forceinline__ void bind_local_bwd(const BindArgs& a, int n, const float g_xyz[3], const float g_rot[4],
+                                               const float g_scl[3], const BindGrads& o)
+{
+    const int fi = a.face_index[n];
+    const int i0 = a.faces[3 * fi], i1 = a.faces[3 * fi + 1], i2 = a.faces[3 * fi + 2];
+    const Vec3 v0 = load3(a.verts, i0), v1 = load3(a.verts, i1), v2 = load3(a.verts, i2);
+    const FaceFrame f = face_frame(v0, v1, v2);
+    Vec3 de1 = {0, 0, 0}, de2 = {0, 0, 0};
+
+    // ---- scaling: + log(s)
+    float gs = 0.f;
+    for (int k = 0; k < 3; k++) {
+        const float g = g_scl[k];
+        if (o.d_scaling) o.d_scaling[3 * n + k] = g;
+        gs += g;
     }
-    {   // a1 = normalize(c1), c1 = a0 x e2
-        const Vec3 dc1 = safe_normalize_bwd(da1, f.a1, f.lc1, f.kc1);
-        da0 = add(da0, cross3(f.e2, dc1));
-        de2 = add(de2, cross3(dc1, f.a0));
+    float dscale = gs / f.scale;
+
+    // ---- position: xyz = u * s + c, u = R l
+    const Vec3 gx = {g_xyz[0], g_xyz[1], g_xyz[2]};
+    const Vec3 l = load3(a.local_xyz, n);
+    const Vec3 u = {f.a0.x * l.x + f.a1.x * l.y + f.a2.x * l.z, f.a0.y * l.x + f.a1.y * l.y + f.a2.y * l.z,
+                    f.a0.z * l.x + f.a1.z * l.y + f.a2.z * l.z};
+    dscale += dot3(gx, u);
+    const Vec3 du = mul(gx, f.scale);
+    if (o.d_local_xyz) o.d_local_xyz[3 * n] = dot3(f.a0, du), o.d_local_xyz[3 * n + 1] = dot3(f.a1, du), o.d_local_xyz[3 * n + 2] = dot3(f.a2, du);
+    Vec3 da0 = mul(du, l.x), da1 = mul(du, l.y), da2 = mul(du, l.z);
+    const Vec3 dc = {gx.x / 3.0f, gx.y / 3.0f, gx.z / 3.0f};   // c = (v0 + v1 + v2) / 3
+
+    // ---- the face scale s = (length(e1) + |a2 . e2|) / 2
+    const float dl1 = 0.5f * dscale;
+    const float dd = 0.5f * dscale * (f.d < 0.f ? -1.f : (f.d > 0.f ? 1.f : 0.f));
+    da2 = add(da2, mul(f.e2, dd));
+    de2 = add(de2, mul(f.a2, dd));
+
+    // ---- rotation: out = standardize(normalize(qf) (x) r)
+    const QuatSel qs = frame_to_quaternion(f);
+    const UnitQuat uq = normalize_quat(qs.q);
+    const float r[4] = {a.rotation[4 * n], a.rotation[4 * n + 1], a.rotation[4 * n + 2], a.rotation[4 * n + 3]};
+    float dq[4], dr[4];
+    quat_multiply_bwd(uq.q, r, g_rot, dq, dr);
+    if (o.d_rotation)
+        for (int k = 0; k < 4; k++) o.d_rotation[4 * n + k] = dr[k];
+    if (!uq.clamped) {   // through q / |q|; a clamped length did not depend on q (as safe_normalize_bwd)
+        const float t = uq.q[0] * dq[0] + uq.q[1] * dq[1] + uq.q[2] * dq[2] + uq.q[3] * dq[3];
+        for (int k = 0; k < 4; k++) dq[k] = dq[k] - uq.q[k] * t;
     }
-    {   // a0 = normalize(e1); s0 = length(e1)
-        de1 = add(de1, safe_normalize_bwd(da0, f.a0, f.l1, f.k1));
-        if (!f.k1) de1 = add(de1, mul(f.a0, dl1));
-    }
-    dv1 = add(dv1, de1);
-    dv2 = add(dv2, de2);
-    dv0 = sub(dv0, add(de1, de2));
-    if (o.d_verts) {
-        atomic_add_f32(o.d_verts + 3 * i0, dv0.x), atomic_add_f32(o.d_verts + 3 * i0 + 1, dv0.y), atomic_add_f32(o.d_verts + 3 * i0 + 2, dv0.z);
-        atomic_add_f32(o.d_verts + 3 * i1, dv1.x), atomic_add_f32(o.d_verts + 3 * i1 + 1, dv1.y), atomic_add_f32(o.d_verts + 3 * i1 + 2, dv1.z);
-        atomic_add_f32(o.d_verts + 3 * i2, dv2.x), atomic_add_f32(o.d_verts + 3 * i2 + 1, dv2.y), atomic_add_f32(o.d_verts + 3 * i2 + 2, dv2.z);
-    }
+    for (int k = 0; k < 4; k++) dq[k] = dq[k] / uq.len;
+    frame_to_quaternion_bwd(qs, dq, da0, da1, da2);
+    face_frame_bwd(f, da0, da1, da2, dl1, de1, de2);
+    scatter_vertex_grads(o.d_verts, i0, i1, i2, dc, dc, dc, de1, de2);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// what the kernels call: the binding of BindArgs::mode (one value per launch, so the branch is wave-uniform)
+__device__ __forceinline__ void bind_fwd(const BindArgs& a, int n, float xyz[3], float rot[4], float scl[3])
+{
+    if (a.mode == FR_BIND_FACE_LOCAL) bind_local_fwd(a, n, xyz, rot, scl);
+    else bind_one_fwd(a, n, xyz, rot, scl);
+}
+__device__ __forceinline__ void bind_bwd(const BindArgs& a, int n, const float g_xyz[3], const float g_rot[4], const float g_scl[3],
+                                         const BindGrads& o)
+{
+    if (a.mode == FR_BIND_FACE_LOCAL) bind_local_bwd(a, n, g_xyz, g_rot, g_scl, o);
+    else bind_one_bwd(a, n, g_xyz, g_rot, g_scl, o);
 }
 
 }  // namespace fr

@@ -8,7 +8,8 @@
 // with the face frame / scale of volume_rendering/mesh_compute.py:36-59 and pytorch3d 0.7.7's quaternion conversion
 // and product.  The reference evaluates this as ~40 PyTorch kernels over [F] and [N] temporaries (plus their autograd
 // twins); here ONE kernel per direction, one thread per Gaussian, recomputing the ~150 flops of its face's frame
-// instead of gathering per-face temporaries.  The backward scatters dL/dverts with float atomics (a vertex is shared
+// instead of gathering per-face temporaries.  The same two kernels serve GaussianAvatars' face-local binding
+// (fr_binding::mode == FR_BIND_FACE_LOCAL, model/baseline/gaussianavatars.py:144-171): the mode is a kernel argument.  The backward scatters dL/dverts with float atomics (a vertex is shared
 // by the Gaussians of ~6 faces x ~10 Gaussians each).  Built without FMA contraction, in the oracle's operation order.
 #include "fr_bind_math.hpp"
 
@@ -19,7 +20,7 @@ __global__ void __launch_bounds__(256) k_bind_fwd(BindArgs a, float* xyz, float*
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= a.N) return;
     float p[3], q[4], s[3];
-    bind_one_fwd(a, n, p, q, s);
+    bind_fwd(a, n, p, q, s);
     for (int k = 0; k < 3; k++) xyz[3 * n + k] = p[k];
     for (int k = 0; k < 4; k++) rot_out[4 * n + k] = q[k];
     for (int k = 0; k < 3; k++) scale_out[3 * n + k] = s[k];
@@ -37,7 +38,7 @@ __global__ void __launch_bounds__(256) k_bind_bwd(BindArgs a, const float* g_xyz
         for (int k = 0; k < 4; k++) gq[k] = g_rot[4 * n + k];
     if (g_scale)
         for (int k = 0; k < 3; k++) gs[k] = g_scale[3 * n + k];
-    bind_one_bwd(a, n, gp, gq, gs, o);
+    bind_bwd(a, n, gp, gq, gs, o);
 }
 
 // per-face scale of a mesh (the canonical one, computed once): mesh_compute.py:51-56
@@ -55,6 +56,7 @@ BindArgs bind_args(const fr_binding& b)
     a.N = b.N, a.verts = b.verts, a.faces = b.faces, a.face_index = b.face_index, a.bary = b.bary;
     a.canon = b.face_scale_canonical, a.shell_len = b.shell_len, a.resize_scale = b.resize_scale;
     a.offset = b.offset, a.rotation = b.rotation, a.scaling = b.scaling;
+    a.mode = b.mode, a.local_xyz = b.local_xyz;
     return a;
 }
 
@@ -67,11 +69,11 @@ int launch_bind_forward(const fr_binding& b, float* xyz, float* rot, float* scal
 }
 
 int launch_bind_backward(const fr_binding& b, const float* g_xyz, const float* g_rot, const float* g_scale, float* d_verts,
-                         float* d_offset, float* d_rotation, float* d_scaling, hipStream_t s)
+                         float* d_offset, float* d_rotation, float* d_scaling, float* d_local_xyz, hipStream_t s)
 {
     if (b.N <= 0) return FR_OK;
     hipLaunchKernelGGL(k_bind_bwd, dim3((b.N + 255) / 256), dim3(256), 0, s, bind_args(b), g_xyz, g_rot, g_scale,
-                       BindGrads{d_verts, d_offset, d_rotation, d_scaling});
+                       BindGrads{d_verts, d_offset, d_rotation, d_scaling, d_local_xyz});
     FR_HIP(hipGetLastError());
     return FR_OK;
 }

@@ -455,7 +455,7 @@ struct BindArgs;
 BindArgs bind_args(const fr_binding& b);   // (fr_bind_math.hpp / fr_binding.hip)
 int launch_bind_forward(const fr_binding& b, float* xyz, float* rot, float* scale, hipStream_t s);
 int launch_bind_backward(const fr_binding& b, const float* g_xyz, const float* g_rot, const float* g_scale, float* d_verts,
-                         float* d_offset, float* d_rotation, float* d_scaling, hipStream_t s);
+                         float* d_offset, float* d_rotation, float* d_scaling, float* d_local_xyz, hipStream_t s);
 int launch_face_scale(int F, const float* verts, const int* faces, float* out, hipStream_t s);
 int launch_adam(const fr_adam_config& cfg, float* param, const float* const* grad_bufs, int n_grads, float* exp_avg,
                 float* exp_avg_sq, unsigned long long n, float* state, hipStream_t s);

@@ -238,7 +238,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
         // the frame comes straight from its mesh binding (model/fateavatar.py:225-258): position, rotation and log-scale
         // of this Gaussian are evaluated here (fr_bind_forward's expressions) and stored for the backward and the caller
         float bp[3];
-        bind_one_fwd(a.bind, li, bp, in_rot, in_sc);
+        bind_fwd(a.bind, li, bp, in_rot, in_sc);
         p_orig = make_float3(bp[0], bp[1], bp[2]);
         if (live) {
             float* m = const_cast<float*>(a.means3D) + 3 * (size_t)li;

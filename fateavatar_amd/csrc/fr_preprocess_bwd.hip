@@ -79,7 +79,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
         if (!adds(G_SCALES)) store3(a.out.dL_dscales, i, 0.f, 0.f, 0.f, false);
         if (a.out.dL_drotations && !adds(G_ROTATIONS))
             for (int k = 0; k < 4; k++) a.out.dL_drotations[4 * i + k] = 0.f;
-        if (a.bound) bind_one_bwd_zero(idx, a.bg);
+        if (a.bound) bind_bwd_zero(idx, a.bg);
         return;
     }
     // accumulating arrays: what they hold is requested NOW, so that the round trip runs under the arithmetic below
@@ -355,7 +355,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
             for (int k = 0; k < 4; k++) a.out.dL_drotations[4 * i + k] = 0.f;
     }
     // ---------------- through the mesh binding (model/fateavatar.py:225-258): fr_bind_backward's expressions
-    if (a.bound) bind_one_bwd(a.bind, idx, g_mean, g_rot, g_scl, a.bg);
+    if (a.bound) bind_bwd(a.bind, idx, g_mean, g_rot, g_scl, a.bg);
 }
 
 // A wave's [64][row_len] block of dL_dsh rows goes from LDS to HBM in coalesced 16-byte stores (the inverse of the
@@ -496,7 +496,7 @@ int launch_backward(int n, const BackwardCall* calls, hipStream_t s)
         a.bound = (prm.aux && prm.aux->binding) ? 1 : 0;
         if (a.bound) {
             a.bind = bind_args(*prm.aux->binding);
-            a.bg = BindGrads{prm.aux->d_verts, prm.aux->d_offset, prm.aux->d_rotation, prm.aux->d_scaling};
+            a.bg = BindGrads{prm.aux->d_verts, prm.aux->d_offset, prm.aux->d_rotation, prm.aux->d_scaling, prm.aux->d_local_xyz};
         } else {
             a.bind = BindArgs{};
             a.bg = BindGrads{};

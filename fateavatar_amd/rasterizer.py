@@ -168,7 +168,7 @@ def _stats3(stats):
 def _aux(visible=None, grad_accum=None, denom=None, binding=None, bind_grads=None, overflow_out=None, planes=None):
     """fr_aux (optional fused side inputs / outputs) from torch tensors, or None if nothing is asked for.  `binding`: an
     `_lib.fr_binding` descriptor (the frame is rendered straight from its mesh binding); `bind_grads`: dict with the
-    backward's d_verts / d_offset / d_rotation / d_scaling tensors (any may be None).  `planes` (FR_FLAG_DEPTH_ALPHA): dict
+    backward's d_verts / d_offset (a face-local binding: d_local_xyz) / d_rotation / d_scaling tensors (any may be None).  `planes` (FR_FLAG_DEPTH_ALPHA): dict
     of the out_depth / out_alpha / dL_ddepth / dL_dalpha tensors and the `planes` scratch (any may be None; the scratch of a
     forward is set by the launcher, which sizes it with the binning buffer)."""
     if visible is None and grad_accum is None and denom is None and binding is None and overflow_out is None and planes is None:
@@ -185,7 +185,7 @@ def _aux(visible=None, grad_accum=None, denom=None, binding=None, bind_grads=Non
     if binding is not None:
         aux._binding_keepalive = binding
         aux.binding = C.pointer(binding)
-        for n in ("d_verts", "d_offset", "d_rotation", "d_scaling"):
+        for n in ("d_verts", "d_offset", "d_rotation", "d_scaling", "d_local_xyz"):
             t = (bind_grads or {}).get(n)
             if t is not None:
                 if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:

@@ -17,7 +17,9 @@
  *                     (cuda_rasterizer/rasterizer.h:24-29, rasterizer_impl.cu:141-153),
  *                     called from markVisible (rasterize_points.cu:198-217)
  *   fr_bind_forward / fr_bind_backward / fr_face_scale replace the ~40 PyTorch kernels of the mesh
- *                     binding (model/fateavatar.py:225-258, volume_rendering/mesh_compute.py:27-59)
+ *                     binding (model/fateavatar.py:225-258, volume_rendering/mesh_compute.py:27-59);
+ *                     with FR_BIND_FACE_LOCAL, fr_bind_forward / fr_bind_backward_local replace those of
+ *                     GaussianAvatars' binding (model/baseline/gaussianavatars.py:144-171)
  *   fr_adam_step      replaces torch.optim.Adam.step() over the Gaussian groups (train/optim.py:11-37)
  *   fr_knn_mean_dist2 replaces SimpleKNN::knn (simple_knn.h, simple_knn.cu:186-222),
  *                     called from distCUDA2 (spatial.cu:14-25)
@@ -93,7 +95,9 @@ typedef struct fr_aux {
      * continues through the binding — fr_bind_backward's expressions on the gradients it would have written to
      * dL_dmeans3D / dL_drotations / dL_dscales (which may then be NULL) — and writes d_offset [P], d_rotation [P,4],
      * d_scaling [P,3] (every row; zeros for culled Gaussians) and ADDS dL/dverts into d_verts [V,3] (float atomics; the
-     * caller zeroes it).  FR_FLAG_ACCUMULATE does not apply to these four. */
+     * caller zeroes it).  FR_FLAG_ACCUMULATE does not apply to these four.
+     * A descriptor with mode FR_BIND_FACE_LOCAL (model/baseline/gaussianavatars.py:144-171) goes the same way; its backward
+     * writes d_local_xyz [P,3] (below) where the shell binding writes d_offset. */
     const fr_binding* binding;
     float* d_verts;
     float* d_offset;
@@ -106,6 +110,10 @@ typedef struct fr_aux {
      * every backward call: frames that feed one optimizer step need ONE WORD EACH (fr_adam_config::skip takes up to
      * FR_ADAM_MAX_GRADS of them); the views of one fr_backward_batch call must not share a word. */
     float* overflow_out;
+    /* fr_backward / fr_backward_batch out [P,3]: a binding with mode FR_BIND_FACE_LOCAL only, where it takes d_offset's
+     * place (every row written, zeros for culled Gaussians; d_offset is then not touched).  It sits behind the binding's
+     * other members: the members in front of it keep their offsets, the plane members below stay the struct's last. */
+    float* d_local_xyz;
     /* FR_FLAG_DEPTH_ALPHA only (appended: positional construction of the members above is unchanged; all unused without the
      * flag).  fr_forward / fr_forward_batch out [H,W], both required under the flag: out_depth = sum over the pixel's blended
      * Gaussians of z_i alpha_i T_i (z_i the view-space depth of the mean; 0 where nothing is blended), out_alpha = 1 - the final
@@ -351,7 +359,16 @@ int fr_multi_copy(int32_t n_segments, float* const* dst, const float* const* src
  * gaussian._xyz / _rotation / _scaling before render():
  *   xyz = sum_k bary_k v_k + (e1 x e2) * shell_len * tanh(offset);  rotation = standardize(q_face (x) rotation);
  *   scaling = scaling + log(face_scale / face_scale_canonical)   (resize_scale != 0; unchanged otherwise).
- * All pointers are device pointers; one frame per call. */
+ * All pointers are device pointers; one frame per call.
+ *
+ * fr_binding::mode selects the binding; a zeroed field is FR_BIND_SHELL, the one above.  FR_BIND_FACE_LOCAL is
+ * GaussianAvatars' (model/baseline/gaussianavatars.py:144-171): with R = [a0 a1 a2] the face's frame, s its scale and c
+ * the mean of its three vertices,
+ *   xyz = (R local_xyz) * s + c;  rotation = standardize(normalize(q_face) (x) rotation);  scaling = scaling + log(s)
+ * (normalize: q / max(|q|, 1e-12)).  bary, offset, face_scale_canonical, shell_len and resize_scale are then ignored and
+ * may be NULL / zero; local_xyz is required. */
+#define FR_BIND_SHELL 0
+#define FR_BIND_FACE_LOCAL 1
 struct fr_binding {
     int32_t N, V, F;
     const float* verts;                 /* [V,3] posed vertices */
@@ -364,6 +381,8 @@ struct fr_binding {
     const float* offset;                /* [N]   raw: tanh is applied here */
     const float* rotation;              /* [N,4] raw quaternion (r,x,y,z) */
     const float* scaling;               /* [N,3] raw log-scale */
+    int32_t mode;                       /* FR_BIND_* (appended: a descriptor that ends above, zero-filled, is a shell binding) */
+    const float* local_xyz;             /* [N,3] FR_BIND_FACE_LOCAL: position in the face's frame */
 };
 int fr_face_scale(int32_t V, int32_t F, const float* verts, const int32_t* faces, float* out_scale, void* hip_stream);
 int fr_bind_forward(const fr_binding* b, float* xyz, float* rotation_out, float* scaling_out, void* hip_stream);
@@ -371,6 +390,10 @@ int fr_bind_forward(const fr_binding* b, float* xyz, float* rotation_out, float*
  * ADDED into d_verts [V,3] with float atomics (the caller zeroes it).  Any of the seven arrays may be NULL. */
 int fr_bind_backward(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
                      float* d_verts, float* d_offset, float* d_rotation, float* d_scaling, void* hip_stream);
+/* The same for a FR_BIND_FACE_LOCAL binding (any other mode is FR_ERR_INVALID_ARGUMENT): d_local_xyz [N,3] where the shell
+ * binding has d_offset. */
+int fr_bind_backward_local(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
+                           float* d_verts, float* d_local_xyz, float* d_rotation, float* d_scaling, void* hip_stream);
 
 /* ---- Gaussian attributes looked up in UV attribute maps: the per-frame front end of a BAKED FateAvatar (reference
  * model/uv_decoder.py:179-202, `UVSampling._texture_look_up`: F.grid_sample(texture, 2 uv - 1, mode="bilinear",

@@ -8,6 +8,9 @@ Targets are renders of a hidden "ground-truth" Gaussian set on the head template
 weights are absent: declared stand-in for the INSTA sequence); the trained set starts from perturbed appearance and
 opacity.  Prints one JSON line: optimisation steps/s (render + L1 + backward + densification statistics + Adam, one
 frame per rank per step, one flat-gradient all-reduce when N > 1) and the loss before / after.
+
+    python tools/train_synthetic.py --rigged [--P 10006 --sh-degree 3 --binding-op]
+GaussianAvatars' step (fateavatar_amd/rigged.py): Gaussians rigged to the triangles of the posed template, one GPU.
 """
 import argparse
 import json
@@ -50,12 +53,17 @@ def main():
     ap.add_argument("--fateavatar", action="store_true",
                     help="FateAvatar's own loop: mesh-bound parameters (offset / rotation / scaling / colour / opacity), "
                          "synthetic INSTA-layout sequence with per-frame posed mesh, SH degree 0")
+    ap.add_argument("--rigged", action="store_true",
+                    help="GaussianAvatars' loop: Gaussians bound to the local frames of the template's faces (one per face, then "
+                         "random faces up to --P), rendered with --sh-degree active; --binding-op as for --fateavatar")
     a = ap.parse_args()
     rank, world, local = dp.init_from_env()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     if a.fateavatar:
         return main_fateavatar(a, rank, world, dev)
+    if a.rigged:
+        return main_rigged(a, rank, world, dev)
     truth = scenes.head_scene(P=a.P, res=a.res, sh_degree=a.sh_degree, seed=0, opacity=0.5)
     cams = [TorchCamera(scenes.head_scene(P=8, res=a.res, sh_degree=a.sh_degree, seed=0, view=v, n_views=a.views).camera, dev)
             for v in range(a.views)]
@@ -186,6 +194,76 @@ def main_fateavatar(a, rank, world, dev):
                           "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
+
+
+def rigged_setup(P, res, dev, views=8, sh_degree=3, use_graph=True, fold_binding=True):
+    """GaussianAvatars' optimisation step on the synthetic INSTA-layout sequence: P Gaussians rigged to the template's faces
+    (Gaussian i on face i for the first F = 10 006, the reference's initialisation; further ones on random faces, spread over
+    them), the step object, cameras, posed meshes and targets rendered from a hidden ground-truth set of the same binding."""
+    from fateavatar_amd import insta
+    from fateavatar_amd.binding import bind_gaussians_face_local
+    from fateavatar_amd.rigged import RiggedGaussians, RiggedStep, _RiggedFrame
+    n_frames = max(views, 8)
+    transform, posed, faces = insta.synthetic_sequence(n_frames, res, seed=0)
+    F = int(faces.shape[0])
+    rng = np.random.default_rng(0)
+    binding = np.arange(min(P, F), dtype=np.int32)
+    if P > F:
+        binding = np.concatenate([binding, rng.integers(0, F, P - F).astype(np.int32)])
+    cams = [TorchCamera(c, dev) for c in insta.camera_arrays(transform)]
+    posed_t, faces_t = torch.from_numpy(posed).to(dev), torch.from_numpy(faces).to(dev)
+    bg = torch.ones(3, device=dev)
+    g = torch.Generator().manual_seed(5)
+    spread = (0.3 * torch.randn(len(binding), 3, generator=g) * torch.tensor([1.0, 0.1, 1.0])).to(dev)
+    if P > F:   # several Gaussians per face: smaller, and not all on the face's centre
+        spread[:F] = 0
+    pc = RiggedGaussians(binding, dev)
+    gt = RiggedGaussians(binding, dev)
+    with torch.no_grad():
+        for m in (pc, gt):
+            if P > F:
+                m._xyz.copy_(spread)
+                m._scaling.fill_(float(np.log(max(F / P, 1e-3)) / 2))
+            m.active_sh_degree = int(sh_degree)
+        gt._features_dc.copy_((torch.rand(gt.P, 1, 3, generator=g) * 2.0 - 1.0).to(dev))
+        gt._features_rest.copy_((0.1 * torch.randn(gt.P, 15, 3, generator=g)).to(dev))
+        gt._opacity.fill_(float(np.log(0.6 / 0.4)))
+        gt._xyz.add_((0.1 * torch.randn(gt.P, 3, generator=g)).to(dev))
+    gts = []
+    with torch.no_grad():
+        for f in range(n_frames):
+            b = bind_gaussians_face_local(posed_t[f], faces_t.to(torch.int32), gt.binding, gt._xyz, gt._rotation, gt._scaling)
+            gts.append(render(cams[f], _RiggedFrame(gt, None, b), bg)["render"].clone())
+    st = RiggedStep(pc, faces_t, TorchCamera(insta.camera_arrays(transform)[0], dev), bg, posed_t[0], use_graph=use_graph,
+                    fold_binding=fold_binding)
+    return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames)
+
+
+def main_rigged(a, rank, world, dev):
+    if world > 1:
+        raise SystemExit("--rigged: data-parallel runs are not built")
+    su = rigged_setup(a.P, a.res, dev, views=a.views, sh_degree=a.sh_degree, use_graph=not a.no_graph, fold_binding=not a.binding_op)
+    st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
+    losses, warm = [], 10
+    for it in range(warm):
+        losses.append(st.step(cams[it % n_frames], posed_t[it % n_frames], gts[it % n_frames]).clone())
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(warm, warm + a.steps):
+        loss = st.step(cams[it % n_frames], posed_t[it % n_frames], gts[it % n_frames])
+        if it >= warm + a.steps - 4:
+            losses.append(loss.clone())
+    t_host = time.perf_counter() - t0
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    st.check()
+    l = [float(x) for x in losses]
+    print(json.dumps({"host_enqueue_ms_per_step": round(t_host / a.steps * 1e3, 4),
+                      "metric": "GaussianAvatars optimisation steps/s (bind + render + L1 + backward + stats + Adam)",
+                      "binding": "stand-alone kernels" if a.binding_op else "inside the per-Gaussian kernels (fr_aux::binding, face-local)",
+                      "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": st.pc.P, "res": a.res,
+                      "frames": n_frames, "sh_degree": st.pc.active_sh_degree, "graph": not a.no_graph, "overflows": st.overflows,
+                      "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
 
 
 if __name__ == "__main__":
