@@ -512,6 +512,17 @@ int fr_l1_loss_grad_batch(int32_t n_images, uint64_t n, const float* const* img,
     return launch_l1_loss_grad_batch(n_images, n, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
+size_t fr_regularise_workspace_bytes(void) { return regularise_workspace_bytes(); }
+
+int fr_gaussian_regularise(const fr_regularise_config* cfg, int32_t P, const float* scaling, const float* xyz, float* d_scaling,
+                           float* d_xyz, float* loss, void* workspace, void* stream)
+{
+    if (!cfg || P < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_gaussian_regularise: null configuration or negative P");
+    if (P > 0 && (!scaling || !xyz)) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_gaussian_regularise: null parameter array");
+    if (!workspace || !loss) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_gaussian_regularise: null workspace or loss");
+    return launch_gaussian_regularise(*cfg, P, scaling, xyz, d_scaling, d_xyz, loss, workspace, static_cast<hipStream_t>(stream));
+}
+
 int fr_multi_copy(int32_t n_segments, float* const* dst, const float* const* src, const uint64_t* count, void* stream)
 {
     if (n_segments < 0 || n_segments > FR_COPY_MAX_SEGMENTS || (n_segments > 0 && (!dst || !src || !count)))

@@ -358,4 +358,130 @@ int launch_scaled_sum(int n_src, const float* const* src, float* dst, unsigned l
     return FR_OK;
 }
 
+// ---------------------------------------------------------------- GaussianAvatars' scale / xyz regularisers, one launch
+// reference: GaussianAvatarsLoss.accumulate_gradients (train/loss.py:367-379) on the raw local parameters
+// (model/baseline/gaussianavatars.py:196-197):
+//     scale_loss = relu(exp(_scaling) - threshold_scale).norm(dim=1).mean()
+//     xyz_loss   = relu(_xyz.norm(dim=1) - threshold_xyz).mean()
+// in PyTorch a dozen launch-bound kernels and their autograd twins on every step.  Here lane = Gaussian: the row's two loss
+// terms, and weight x their gradients ADDED into the caller's gradient rows by the lane that owns the row (no atomics).
+// Sub-gradients are autograd's: relu passes a gradient where its input is > 0, norm's backward gives 0 at norm 0 — so a
+// component with exp(s) <= threshold, a row clipped to zero and a row with |xyz| <= threshold add nothing, and no division
+// by a zero norm is evaluated.  The loss sums are reduced as k_l1_loss_grad's: per-workgroup partials, added up in index
+// order by the workgroup that finishes last, which also puts the partials back to zero.
+constexpr unsigned kRegMaxBlocks = 1024;
+
+struct RegArgs {
+    const float* scaling;
+    const float* xyz;
+    float* d_scaling;     // null: no gradient traffic for the term (also what a zero weight gives)
+    float* d_xyz;
+    float* partial;       // [2][kRegMaxBlocks]
+    unsigned* counter;
+    float* loss;          // {scale_loss, xyz_loss}, unweighted
+    int P;
+    float g_scale, g_xyz; // weight / P
+    float thr_scale, thr_xyz, inv_P;
+};
+
+__global__ void __launch_bounds__(256) k_gaussian_regularise(RegArgs a)
+{
+    const float* __restrict__ scaling = a.scaling;
+    const float* __restrict__ xyz = a.xyz;
+    float* __restrict__ d_scaling = a.d_scaling;
+    float* __restrict__ d_xyz = a.d_xyz;
+    float* const partial = a.partial;
+    __shared__ float s_red[2][4];
+    __shared__ bool s_last;
+    const unsigned stride = gridDim.x * blockDim.x;
+    float acc_s = 0.f, acc_x = 0.f;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)a.P; i += stride) {
+        const size_t o = (size_t)i * 3;
+        const float e0 = act_exp(scaling[o]), e1 = act_exp(scaling[o + 1]), e2 = act_exp(scaling[o + 2]);
+        const float c0 = fmaxf(e0 - a.thr_scale, 0.f), c1 = fmaxf(e1 - a.thr_scale, 0.f), c2 = fmaxf(e2 - a.thr_scale, 0.f);
+        const float ns = sqrtf((c0 * c0 + c1 * c1) + c2 * c2);
+        acc_s += ns;
+        if (d_scaling && ns > 0.f) {       // (c_k == 0 where exp(s_k) <= threshold: that component adds an exact 0)
+            const float k = a.g_scale / ns;
+            d_scaling[o] += k * c0 * e0;
+            d_scaling[o + 1] += k * c1 * e1;
+            d_scaling[o + 2] += k * c2 * e2;
+        }
+        const float x = xyz[o], y = xyz[o + 1], z = xyz[o + 2];
+        const float nx = sqrtf((x * x + y * y) + z * z);
+        const float over = nx - a.thr_xyz;
+        acc_x += fmaxf(over, 0.f);
+        if (d_xyz && over > 0.f && nx > 0.f) {
+            const float k = a.g_xyz / nx;
+            d_xyz[o] += k * x;
+            d_xyz[o + 1] += k * y;
+            d_xyz[o + 2] += k * z;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        acc_s += __shfl_down(acc_s, off);
+        acc_x += __shfl_down(acc_x, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_red[0][threadIdx.x >> 6] = acc_s;
+        s_red[1][threadIdx.x >> 6] = acc_x;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        // write-through stores, wait for them, then count this workgroup in (as k_l1_loss_grad)
+        __hip_atomic_store(partial + blockIdx.x, (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(partial + kRegMaxBlocks + blockIdx.x, (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        s_last = last_workgroup(a.counter);
+    }
+    __syncthreads();
+    if (!s_last) return;
+    float ts = 0.f, tx = 0.f;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
+        ts += __hip_atomic_load(partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        tx += __hip_atomic_load(partial + kRegMaxBlocks + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(partial + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the workspace is left zeroed
+        __hip_atomic_store(partial + kRegMaxBlocks + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        ts += __shfl_down(ts, off);
+        tx += __shfl_down(tx, off);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        s_red[0][threadIdx.x >> 6] = ts;
+        s_red[1][threadIdx.x >> 6] = tx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a.loss[0] = ((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3])) * a.inv_P;
+        a.loss[1] = ((s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3])) * a.inv_P;
+    }
+}
+
+size_t regularise_workspace_bytes() { return (kDoneGroups + 1) * kDoneStride * sizeof(unsigned) + 2 * kRegMaxBlocks * sizeof(float); }
+
+int launch_gaussian_regularise(const fr_regularise_config& cfg, int P, const float* scaling, const float* xyz, float* d_scaling,
+                               float* d_xyz, float* loss, void* workspace, hipStream_t s)
+{
+    if (P <= 0) return FR_OK;
+    unsigned blocks = ((unsigned)P + 255u) / 256u;
+    blocks = blocks > kRegMaxBlocks ? kRegMaxBlocks : blocks;
+    RegArgs a;
+    a.scaling = scaling, a.xyz = xyz;
+    a.d_scaling = cfg.scale_weight != 0.f ? d_scaling : nullptr;   // a zero weight: the array is not touched
+    a.d_xyz = cfg.xyz_weight != 0.f ? d_xyz : nullptr;
+    a.counter = static_cast<unsigned*>(workspace);
+    a.partial = reinterpret_cast<float*>(a.counter + (kDoneGroups + 1) * kDoneStride);
+    a.loss = loss, a.P = P;
+    a.inv_P = (float)(1.0 / (double)P);
+    a.g_scale = (float)((double)cfg.scale_weight / (double)P), a.g_xyz = (float)((double)cfg.xyz_weight / (double)P);
+    a.thr_scale = cfg.threshold_scale, a.thr_xyz = cfg.threshold_xyz;
+    hipLaunchKernelGGL(k_gaussian_regularise, dim3(blocks), dim3(256), 0, s, a);
+    FR_HIP(hipGetLastError());
+    return FR_OK;
+}
+
 }  // namespace fr

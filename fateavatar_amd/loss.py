@@ -96,6 +96,60 @@ def l1_loss_and_grad_batch(imgs, gts, loss_outs, grad_outs, workspaces):
     return loss_outs, grad_outs
 
 
+_reg_workspace = {}   # (device index, stream handle) -> zeroed scratch of fr_gaussian_regularise (as _workspace above)
+
+
+def regulariser_workspace(dev: torch.device) -> torch.Tensor:
+    """A fresh zeroed workspace for `gaussian_regularisers(..., workspace=)`."""
+    return torch.zeros((_lib.lib().fr_regularise_workspace_bytes(),), dtype=torch.uint8, device=dev)
+
+
+def gaussian_regularisers(scaling: torch.Tensor, xyz: torch.Tensor, d_scaling: Optional[torch.Tensor],
+                          d_xyz: Optional[torch.Tensor], out: Optional[torch.Tensor] = None, weights=(1.0, 0.01),
+                          thresholds=(0.6, 1.0), workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """GaussianAvatars' scale and xyz regularisers (train/loss.py:367-379) on the raw `_scaling` / `_xyz` [P,3] in ONE launch
+    (`fr_gaussian_regularise`): returns `out` = (scale_loss, xyz_loss), UNWEIGHTED, a 2-element device tensor, and ADDS
+    `weights[0] * d scale_loss / d _scaling` into `d_scaling` and `weights[1] * d xyz_loss / d _xyz` into `d_xyz` ([P,3]
+    gradient buffers; None: that gradient is not wanted; a weight of 0 leaves its buffer untouched).  `thresholds`:
+    (threshold_scale, threshold_xyz).  `workspace`: scratch from `regulariser_workspace()`; by default one is kept per
+    (device, current stream) — launches that may overlap must not share one.  There is no CPU path."""
+    if not (scaling.is_cuda and xyz.is_cuda):
+        raise RuntimeError("gaussian_regularisers needs device tensors (there is no CPU path)")
+    dev = scaling.device
+    P = int(scaling.shape[0])
+    scaling, xyz = scaling.detach(), xyz.detach()
+    for t in (scaling, xyz, d_scaling, d_xyz):
+        if t is None:
+            continue
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (P, 3):
+            raise RuntimeError("gaussian_regularisers: contiguous float32 [P,3] tensors of one device")
+    loss = out if out is not None else torch.empty((2,), dtype=torch.float32, device=dev)
+    if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
+        raise RuntimeError("gaussian_regularisers: `out` is a contiguous 2-element float32 tensor on the parameters' device")
+    L = _lib.lib()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ws = workspace
+    if ws is None:
+        key = (dev.index, stream)
+        ws = _reg_workspace.get(key)
+        if ws is None:
+            if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
+                raise RuntimeError("gaussian_regularisers: first call on this stream happens inside a graph capture; call it "
+                                   "once eagerly on the stream first, or pass workspace=regulariser_workspace(device)")
+            ws = _reg_workspace[key] = regulariser_workspace(dev)
+    elif not (ws.is_cuda and ws.device == dev and ws.dtype == torch.uint8 and ws.numel() >= L.fr_regularise_workspace_bytes()):
+        raise RuntimeError("gaussian_regularisers: workspace must come from regulariser_workspace() on the parameters' device")
+    import ctypes as C
+    cfg = _lib.fr_regularise_config(float(weights[0]), float(weights[1]), float(thresholds[0]), float(thresholds[1]))
+    with torch.cuda.device(dev):
+        rc = L.fr_gaussian_regularise(C.byref(cfg), P, scaling.data_ptr(), xyz.data_ptr(),
+                                      d_scaling.data_ptr() if d_scaling is not None else None,
+                                      d_xyz.data_ptr() if d_xyz is not None else None, loss.data_ptr(), ws.data_ptr(), stream)
+    if rc != _lib.FR_OK:
+        raise RuntimeError(f"fr_gaussian_regularise failed: {_lib.last_error()}")
+    return loss
+
+
 _copy_calls = {}   # (dst ptr, src ptr, floats) per pair -> the prepared argument arrays of fr_multi_copy
 
 

@@ -13,19 +13,25 @@ reference:
 What is fused: the binding runs inside the rasterizer's per-Gaussian kernels (bound.render_bound_batch with a
 FaceLocalBinding; `fold_binding=False` keeps the stand-alone op as the A/B), activations and densification statistics run
 inside the rasterizer kernels, one L1 launch, one Adam launch over the flat buffer, the whole step ONE HIP graph.
-Not here: the clone / split densification with `binding_counter` and its guarded prune, the scale / xyz
-regularisers and the D-SSIM term, the position learning-rate schedule, a multi-lane batch step, data-parallel runs, FLAME.
+  * the scale / xyz regularisers — `GaussianAvatarsLoss.accumulate_gradients` (train/loss.py:367-379) with the weights and
+    thresholds of config/gaussianavatars.yaml: `RiggedStep(regularisers=...)`, one more launch inside the captured step
+    (`loss.gaussian_regularisers`) that adds their gradients in front of Adam
+  * density control — `_densify_and_prune`, `_clone_densify`, `_split_densify`, `_prune` with `binding_counter`,
+    `_reset_opacity` (gaussianavatars.py:278-495): `RiggedStep.densify_and_prune / prune / prune_low_opacity /
+    reset_opacity`, torch index surgery between steps
+Not here: the D-SSIM term and `rgb_weight` (the image term keeps weight 1), the position learning-rate schedule,
+`max_radii2D` (see `densify_and_prune`), a multi-lane batch step, data-parallel runs, FLAME.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from .binding import bind_gaussians_face_local
 from .bound import FaceLocalBinding, render_bound_batch
-from .loss import l1_loss_and_grad, l1_workspace
+from .loss import gaussian_regularisers, l1_loss_and_grad, l1_workspace, regulariser_workspace
 from .model import TorchCamera
 from .optim import FusedAdam
 from .rasterizer import GradOut
@@ -34,6 +40,28 @@ from .train import TrainStep
 
 # config/gaussianavatars.yaml:26-31 (group names of train/optim.py:73-80; position_lr_init: the schedule is out of scope)
 RIGGED_LRS = dict(xyz=0.005, opacity=0.05, feature_dc=0.0025, feature_rest=0.0025 / 20, rotation=0.001, scaling=0.017)
+
+
+class Regularisers(NamedTuple):
+    """The scale / xyz regularisers of GaussianAvatarsLoss (train/loss.py:367-379)."""
+    scale_weight: float
+    xyz_weight: float
+    threshold_scale: float
+    threshold_xyz: float
+
+
+# the reference's values (config/gaussianavatars.yaml:13-20)
+REFERENCE_REGULARISERS = Regularisers(scale_weight=1.0, xyz_weight=0.01, threshold_scale=0.6, threshold_xyz=1.0)
+PERCENT_DENSE = 0.01     # gaussianavatars.py:47
+
+
+def build_rotation(r: torch.Tensor) -> torch.Tensor:
+    """[n,4] raw quaternions (r, x, y, z) -> [n,3,3]: build_rotation (tools/gs_utils/general_utils.py:78-99)."""
+    q = r / torch.sqrt((r * r).sum(dim=1, keepdim=True))
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                        2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                        2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
 
 
 class RiggedGaussians(torch.nn.Module):
@@ -97,6 +125,42 @@ class RiggedGaussians(torch.nn.Module):
         for name, _ in self.FIELDS:
             getattr(self, name).grad = None
 
+    def grad_view(self, name: str) -> torch.Tensor:
+        """The run of the flat gradient buffer that belongs to the field `name`, as [P, width]."""
+        off = 0
+        for n, w in self.FIELDS:
+            if n == name:
+                return self.flat_grad[off:off + self.P * w].view(self.P, w)
+            off += self.P * w
+        raise KeyError(name)
+
+    @torch.no_grad()
+    def resize(self, keep_mask=None, new_rows=None, new_binding=None) -> torch.Tensor:
+        """Prune and / or append Gaussians (FlatGaussians.resize's contract): rows where `keep_mask` is False are dropped,
+        then `new_rows` — one raw tensor [n_new, ...] per field, in FIELDS order — are appended, bound to the faces
+        `new_binding` [n_new].  `binding` follows the rows.  The flat buffers are rebuilt and every parameter is a new
+        nn.Parameter; returns the row map `old_index` (int64 [P_new], -1 for appended rows)."""
+        dev = self.flat.device
+        P_old = self.P
+        keep = torch.ones(P_old, dtype=torch.bool, device=dev) if keep_mask is None else keep_mask.to(dev).bool().reshape(-1)
+        if keep.numel() != P_old:
+            raise ValueError("keep_mask must have one entry per Gaussian")
+        old_index = torch.nonzero(keep).reshape(-1)
+        raw = [getattr(self, name).detach()[old_index] for name, _ in self.FIELDS]
+        binding = self.binding[old_index]
+        n_new = 0
+        if new_rows is not None:
+            n_new = int(new_rows[0].shape[0])
+            if new_binding is None or int(new_binding.numel()) != n_new:
+                raise ValueError("new_binding must name one face per appended row")
+            for i, (r, add) in enumerate(zip(raw, new_rows)):
+                add = add.to(dev, torch.float32).reshape((n_new,) + tuple(r.shape[1:]))
+                raw[i] = torch.cat([r, add], dim=0)
+            binding = torch.cat([binding, new_binding.to(dev, torch.int32).reshape(-1)])
+        self.binding = binding.contiguous()
+        self._bind(raw)
+        return torch.cat([old_index, torch.full((n_new,), -1, dtype=torch.int64, device=dev)])
+
     def collect_grads(self) -> torch.Tensor:
         """Every parameter's gradient in the flat gradient buffer (most are written there by the kernels already; the two
         halves of the SH block come back from autograd's split of the concatenation)."""
@@ -132,11 +196,15 @@ class RiggedStep(TrainStep):
     bind in the frame -> render -> L1 -> backward -> densification statistics -> Adam."""
 
     def __init__(self, pc: RiggedGaussians, faces: torch.Tensor, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
-                 lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True):
+                 lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True,
+                 regularisers: Optional[Regularisers] = None):
         """`verts` [V,3]: any pose of the mesh (sizes the step's static vertex buffer and is its first content).
         `fold_binding` (default): the binding is evaluated inside the rasterizer's per-Gaussian kernels (fr_aux::binding with
         FR_BIND_FACE_LOCAL) — no binding launches.  False: the stand-alone `bind_gaussians_face_local` op in front of
-        render() (same results; the A/B and the op's own user)."""
+        render() (same results; the A/B and the op's own user).
+        `regularisers`: a `Regularisers` (REFERENCE_REGULARISERS holds the reference's values) adds the scale / xyz terms of
+        train/loss.py:367-379 to every step — one launch between the backward and Adam; `reg_loss` then holds the step's
+        unweighted (scale_loss, xyz_loss).  None (default): no such launch, `reg_loss` is None."""
         if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise RuntimeError("RiggedStep: data-parallel runs are not built (DESIGN.md)")
         self.pc, self.bg = pc, bg
@@ -154,10 +222,23 @@ class RiggedStep(TrainStep):
         self.loss = torch.zeros((), device=self.dev)
         self._dimage = torch.zeros_like(self.gt)   # dL/dimage of the step
         self._l1_ws = l1_workspace(self.dev)
+        self.regularisers = None if regularisers is None else Regularisers(*[float(x) for x in regularisers])
+        # the reference's out['scale_loss'] / out['xyz_loss'] of the step (unweighted), written by the regulariser launch
+        self.reg_loss = None if regularisers is None else torch.zeros(2, device=self.dev)
+        self._reg_ws = None if regularisers is None else regulariser_workspace(self.dev)
+        self.n_faces = int(self.faces.shape[0])
+        self._count_binding()
         self.out = None
         self.use_graph = bool(use_graph)
         self._graph, self._eager_steps, self.overflows = None, 0, 0
         self.host_steps = 0      # (TrainStep.skipped_steps)
+
+    def _count_binding(self):
+        """binding_counter [F] int32: Gaussians per face (gaussianavatars.py:66-69)."""
+        b = self.pc.binding.long()
+        if b.numel() and (int(b.min()) < 0 or int(b.max()) >= self.n_faces):
+            raise ValueError("RiggedStep: `binding` names a face the mesh does not have")
+        self.binding_counter = torch.bincount(b, minlength=self.n_faces).to(torch.int32)
 
     def adam_segments(self):
         """The optimizer groups (train/optim.py:73-80 with config/gaussianavatars.yaml:26-31) as runs of the flat buffer."""
@@ -184,6 +265,14 @@ class RiggedStep(TrainStep):
         _, g = l1_loss_and_grad(out["render"], self.gt, loss_out=self.loss, grad_out=self._dimage, workspace=self._l1_ws)   # see TrainStep
         out["render"].backward(g)
         pc.collect_grads()                                          # (the SH halves: see RiggedGaussians.collect_grads)
+        if self.regularisers is not None:
+            # train/loss.py:367-379: weight x the two regularisers' gradients are ADDED to the image term's, in front of Adam.
+            # A replay that overflowed its binning capacity back-propagated zeros and its Adam launch skips the step (the
+            # overflow word): what this launch added to the zeroed gradient is then never applied — harmless.
+            r = self.regularisers
+            gaussian_regularisers(pc._scaling, pc._xyz, pc.grad_view("_scaling"), pc.grad_view("_xyz"), out=self.reg_loss,
+                                  weights=(r.scale_weight, r.xyz_weight), thresholds=(r.threshold_scale, r.threshold_xyz),
+                                  workspace=self._reg_ws)
         self.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
 
     def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor) -> torch.Tensor:
@@ -202,12 +291,128 @@ class RiggedStep(TrainStep):
             self._graph = None
         return pc.active_sh_degree
 
-    # ---- the maintenance of TrainStep moves rows of a FlatGaussians; the rigged set's own (clone / split with
-    #      binding_counter, guarded prune) is not built
-    def _no_maintenance(self, *a, **k):
-        raise NotImplementedError("RiggedStep: GaussianAvatars' densification / prune / opacity reset are not built (DESIGN.md)")
+    # ---- GaussianAvatars' density control (gaussianavatars.py:278-495), with TrainStep's conventions: torch index surgery
+    #      under no_grad between step() calls, optimizer state through FusedAdam.remap_rows / zero_field_moments, the graph
+    #      dropped when the buffers move, host_steps untouched
+    @torch.no_grad()
+    def _after_resize(self, old_index, old_rows, stats=None):
+        """`stats`: the (xyz_gradient_accum, denom) the new rows continue with; None: they restart from zero."""
+        pc = self.pc
+        self.adam.remap_rows(pc.flat, pc.flat_grad, old_index, pc.widths(), old_rows)
+        acc, den = stats if stats is not None else (None, None)
+        self.xyz_gradient_accum = acc if acc is not None else torch.zeros((pc.P, 1), device=self.dev)
+        self.denom = den if den is not None else torch.zeros((pc.P, 1), device=self.dev)
+        self.adam.set_skip_words([pc.overflow_word])
+        self._graph, self._eager_steps = None, 0   # buffers moved: the captured step is stale
 
-    prune_low_opacity = densify_by_gradient = reset_opacity = _no_maintenance
+    @torch.no_grad()
+    def _append(self, rows, binding) -> int:
+        """Appends `rows` (FIELDS order) bound to `binding`; counts them into binding_counter (:313-315, :374-377); the
+        statistics restart from zero whether or not anything was appended (_densification_postfix always runs, :462-475)."""
+        n = int(binding.numel())
+        if n == 0:
+            self.xyz_gradient_accum.zero_()
+            self.denom.zero_()
+            return 0
+        pc = self.pc
+        self.binding_counter += torch.bincount(binding.long(), minlength=self.n_faces).to(torch.int32)
+        old_rows = pc.P
+        old_index = pc.resize(new_rows=rows, new_binding=binding)
+        self._after_resize(old_index, old_rows)
+        return n
+
+    @torch.no_grad()
+    def prune(self, mask: torch.Tensor) -> int:
+        """_prune (gaussianavatars.py:418-460): removes the Gaussians marked in `mask` [P] — but if a face would lose ALL of
+        its Gaussians none of its marked ones is removed (binding_counter guard, :420-424); otherwise all of them are.  The
+        statistics of the surviving rows are kept (:455-456).  Returns the number of Gaussians removed."""
+        pc = self.pc
+        mask = mask.to(self.dev).bool().reshape(-1).clone()
+        if mask.numel() != pc.P:
+            raise ValueError("prune: mask must have one entry per Gaussian")
+        b = pc.binding.long()
+        marked = torch.bincount(b[mask], minlength=self.n_faces).to(torch.int32)
+        redundant = (self.binding_counter - marked) > 0
+        mask &= redundant[b]
+        n = int(mask.sum())
+        if n == 0:
+            return 0
+        self.binding_counter -= torch.bincount(b[mask], minlength=self.n_faces).to(torch.int32)
+        keep = ~mask
+        stats = (self.xyz_gradient_accum[keep].contiguous(), self.denom[keep].contiguous())
+        old_rows = pc.P
+        old_index = pc.resize(keep_mask=keep)
+        self._after_resize(old_index, old_rows, stats)
+        return n
+
+    @torch.no_grad()
+    def prune_low_opacity(self, min_opacity: float = 0.005) -> int:
+        """`prune` with the opacity mask of _densify_and_prune (:287)."""
+        return self.prune((torch.sigmoid(self.pc._opacity) < min_opacity).reshape(-1))
+
+    @torch.no_grad()
+    def densify_and_prune(self, max_grad: float = 1e-4, min_opacity: float = 0.005, extent: float = 2.0,
+                          max_screen_size=None, generator: Optional[torch.Generator] = None):
+        """_densify_and_prune with _clone_densify and _split_densify (gaussianavatars.py:278-416); call it between step()
+        calls.  Returns (cloned, split, pruned) row counts.
+          * grads = xyz_gradient_accum / denom, NaN -> 0 (:281-282)
+          * clone (:297-351): rows with grads >= max_grad and max exp(_scaling) <= percent_dense * extent are appended as
+            they are, on the same face
+          * split (:353-416), over the set after the clone (the clones' padded gradient is 0), N = 2: rows with grads >=
+            max_grad and max exp(_scaling) > percent_dense * extent get two children at R(_rotation) . sample + _xyz, sample ~
+            N(0, exp(_scaling)) — ONE torch.normal(mean=zeros, std=stds, generator=generator) call of shape [2 n, 3], made
+            on the generator's device — with _scaling = log(exp(_scaling) / (0.8 N)), everything else repeated; the selected
+            originals are then removed through the guarded prune
+          * appended rows start with zero Adam moments, the step count is kept; the statistics restart from zero after the
+            clone and after the split, even when nothing was selected
+          * final prune (:287-293): sigmoid(_opacity) < min_opacity, and with a truthy `max_screen_size` also max exp(_scaling) >
+            0.1 * extent.  The reference also ORs in `max_radii2D > max_screen_size`; that test can never fire there
+            (_densification_postfix zeroes max_radii2D in clone and in split immediately before it), so max_radii2D is not
+            tracked here.
+        The reference calls this between backward() and optimizer.step(), where the new Parameters have no gradients; that
+        ordering is not copied."""
+        pc = self.pc
+        grads = self.xyz_gradient_accum / self.denom
+        grads[grads.isnan()] = 0.0
+        grads = torch.norm(grads, dim=-1)
+        fields = lambda sel: [getattr(pc, name).detach()[sel] for name, _ in pc.FIELDS]  # noqa: E731
+        largest = lambda: torch.exp(pc._scaling.detach()).max(dim=1).values  # noqa: E731
+        # ---- clone
+        sel = (grads >= max_grad) & (largest() <= PERCENT_DENSE * extent)
+        n_clone = self._append(fields(sel), pc.binding[sel])
+        # ---- split
+        N = 2
+        padded = torch.zeros(pc.P, device=self.dev)
+        padded[:grads.shape[0]] = grads
+        sel = (padded >= max_grad) & (largest() > PERCENT_DENSE * extent)
+        n_split = int(sel.sum())
+        rows = [r.repeat((N,) + (1,) * (r.dim() - 1)) for r in fields(sel)]
+        stds = torch.exp(rows[5])                               # exp(_scaling)[sel].repeat(N, 1)
+        gdev = generator.device if generator is not None else self.dev
+        samples = torch.normal(mean=torch.zeros((stds.shape[0], 3), device=gdev), std=stds.to(gdev), generator=generator).to(self.dev)
+        rows[0] = torch.bmm(build_rotation(rows[4]), samples.unsqueeze(-1)).squeeze(-1) + rows[0]
+        rows[5] = torch.log(stds / (0.8 * N))
+        self._append(rows, pc.binding[sel].repeat(N))
+        if n_split:
+            self.prune(torch.cat([sel, torch.zeros(N * n_split, dtype=torch.bool, device=self.dev)]))
+        # ---- prune
+        mask = (torch.sigmoid(pc._opacity.detach()) < min_opacity).reshape(-1)
+        if max_screen_size:
+            mask |= torch.exp(pc._scaling.detach()).max(dim=1).values > 0.1 * extent
+        return n_clone, n_split, self.prune(mask)
+
+    def densify_by_gradient(self, *a, **k):
+        raise NotImplementedError("RiggedStep: the rigged set densifies with densify_and_prune() (GaussianAvatars' clone / split)")
+
+    @torch.no_grad()
+    def reset_opacity(self) -> None:
+        """_reset_opacity (gaussianavatars.py:477-495): opacity <- inverse_sigmoid(min(sigmoid(opacity), 0.01)), its Adam
+        moments <- 0, IN PLACE: the captured graph keeps pointing at the same parameter and moment buffers."""
+        pc = self.pc
+        cur = torch.sigmoid(pc._opacity)
+        new = torch.minimum(cur, torch.full_like(cur, 0.01))
+        pc._opacity.data.copy_(torch.log(new / (1 - new)))
+        self.adam.zero_field_moments(pc.widths(), pc.P, fields=(1,))
 
     # ---- checkpoints: 'model' holds what GaussianAvatars.state_dict() holds of the Gaussians (the six parameters and the
     #      `binding` buffer); 'optimizer', 'densification' and 'active_sh_degree' are what a seamless resume needs on top
@@ -236,6 +441,7 @@ class RiggedStep(TrainStep):
         P = int(pc.binding.shape[0])
         pc._bind([g[name].to(self.dev, torch.float32).reshape((P,) + pc.SHAPES[name]) for name, _ in pc.FIELDS])
         pc.active_sh_degree = int(sd.get("active_sh_degree", pc.active_sh_degree))
+        self._count_binding()
         self._make_adam()                                  # fresh (zero) moments over the new buffers
         self._graph, self._eager_steps = None, 0           # buffers moved: the captured step is stale
         self.xyz_gradient_accum = torch.zeros((P, 1), device=self.dev)

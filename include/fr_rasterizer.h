@@ -343,6 +343,28 @@ int fr_l1_loss_grad(uint64_t n, const float* img, const float* gt, float* grad, 
 int fr_l1_loss_grad_batch(int32_t n_images, uint64_t n, const float* const* img, const float* const* gt, float* const* grad,
                           float* const* loss, void* const* workspace, void* hip_stream);
 
+/* ---- GaussianAvatars' two per-Gaussian regularisers and their gradients in ONE launch (reference:
+ * GaussianAvatarsLoss.accumulate_gradients, train/loss.py:367-379, on the raw local parameters,
+ * model/baseline/gaussianavatars.py:196-197):
+ *   scale_loss = relu(exp(_scaling) - threshold_scale).norm(dim=1).mean()
+ *   xyz_loss   = relu(_xyz.norm(dim=1) - threshold_xyz).mean()
+ * `scaling`, `xyz`: P rows of 3 raw floats.  The kernel ADDS scale_weight * d scale_loss / d _scaling into `d_scaling`
+ * [P,3] and xyz_weight * d xyz_loss / d _xyz into `d_xyz` [P,3] (read-modify-write by the lane that owns the row, no
+ * atomics) with autograd's sub-gradients: a component with exp(s) <= threshold, a row whose clipped vector has norm 0 and
+ * a row with |xyz| <= threshold add nothing; no division by a zero norm is evaluated.  A weight of 0 leaves that term's
+ * array untouched (no traffic); either gradient pointer may be NULL (loss only).  `loss`: two device floats,
+ * {scale_loss, xyz_loss}, UNWEIGHTED; bit-reproducible from launch to launch (per-workgroup partials summed in index order
+ * by the workgroup that finishes last).  `workspace`: fr_regularise_workspace_bytes() bytes of device memory, zeroed ONCE
+ * by the caller; the kernel leaves it zeroed; not to be shared by launches that can overlap on the device.  Nothing
+ * depends on the step: the call can be captured in a graph.  P == 0 launches nothing and leaves `loss` as it is. */
+typedef struct fr_regularise_config {
+    float scale_weight, xyz_weight;       /* reference: 1.0, 0.01 (config/gaussianavatars.yaml) */
+    float threshold_scale, threshold_xyz; /* reference: 0.6, 1.0 */
+} fr_regularise_config;
+size_t fr_regularise_workspace_bytes(void);
+int fr_gaussian_regularise(const fr_regularise_config* cfg, int32_t P, const float* scaling, const float* xyz,
+                           float* d_scaling, float* d_xyz, float* loss, void* workspace, void* hip_stream);
+
 /* ---- dst = scale * (src[0] + ... + src[n_src - 1]), n_src in 1 .. FR_ADAM_MAX_GRADS arrays of `count` floats, 16-byte
  * aligned: the mean of the gradient buffers of the views a rank rendered in flight together, written into the exchange
  * buffer of the data-parallel all-reduce in one pass.  dst may be one of the sources. */

@@ -11,6 +11,10 @@ frame per rank per step, one flat-gradient all-reduce when N > 1) and the loss b
 
     python tools/train_synthetic.py --rigged [--P 10006 --sh-degree 3 --binding-op]
 GaussianAvatars' step (fateavatar_amd/rigged.py): Gaussians rigged to the triangles of the posed template, one GPU.
+    python tools/train_synthetic.py --rigged --P 10006 --regularisers --densify-from 0.3 --densify-interval 0.1 --reset-interval 0.5
+the same with the reference's scale / xyz regularisers in the step and a compressed maintenance schedule (fractions of
+--steps: config/gaussianavatars.yaml:36-43 has 10 000 / 2 000 / 60 000 of 600 000 iterations); P and min(binding_counter)
+are printed after each densify.
 """
 import argparse
 import json
@@ -56,6 +60,17 @@ def main():
     ap.add_argument("--rigged", action="store_true",
                     help="GaussianAvatars' loop: Gaussians bound to the local frames of the template's faces (one per face, then "
                          "random faces up to --P), rendered with --sh-degree active; --binding-op as for --fateavatar")
+    ap.add_argument("--regularisers", action="store_true",
+                    help="--rigged: the reference's scale / xyz regularisers in every step (one more launch in the graph)")
+    ap.add_argument("--reg-weights", type=float, nargs=2, default=None, metavar=("SCALE", "XYZ"),
+                    help="--rigged: regulariser weights (default 1.0 0.01); implies --regularisers")
+    ap.add_argument("--reg-thresholds", type=float, nargs=2, default=None, metavar=("SCALE", "XYZ"),
+                    help="--rigged: regulariser thresholds (default 0.6 1.0); implies --regularisers")
+    ap.add_argument("--densify-from", type=float, default=0.0,
+                    help="--rigged: first densify_and_prune at this fraction of --steps (0: no densification)")
+    ap.add_argument("--densify-interval", type=float, default=0.1, help="--rigged: densify every this fraction of --steps")
+    ap.add_argument("--reset-interval", type=float, default=0.0,
+                    help="--rigged: reset_opacity every this fraction of --steps (0: never)")
     a = ap.parse_args()
     rank, world, local = dp.init_from_env()
     torch.cuda.set_device(local)
@@ -196,7 +211,7 @@ def main_fateavatar(a, rank, world, dev):
         torch.distributed.destroy_process_group()
 
 
-def rigged_setup(P, res, dev, views=8, sh_degree=3, use_graph=True, fold_binding=True):
+def rigged_setup(P, res, dev, views=8, sh_degree=3, use_graph=True, fold_binding=True, regularisers=None):
     """GaussianAvatars' optimisation step on the synthetic INSTA-layout sequence: P Gaussians rigged to the template's faces
     (Gaussian i on face i for the first F = 10 006, the reference's initialisation; further ones on random faces, spread over
     them), the step object, cameras, posed meshes and targets rendered from a hidden ground-truth set of the same binding."""
@@ -235,15 +250,25 @@ def rigged_setup(P, res, dev, views=8, sh_degree=3, use_graph=True, fold_binding
             b = bind_gaussians_face_local(posed_t[f], faces_t.to(torch.int32), gt.binding, gt._xyz, gt._rotation, gt._scaling)
             gts.append(render(cams[f], _RiggedFrame(gt, None, b), bg)["render"].clone())
     st = RiggedStep(pc, faces_t, TorchCamera(insta.camera_arrays(transform)[0], dev), bg, posed_t[0], use_graph=use_graph,
-                    fold_binding=fold_binding)
+                    fold_binding=fold_binding, regularisers=regularisers)
     return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames)
 
 
 def main_rigged(a, rank, world, dev):
     if world > 1:
         raise SystemExit("--rigged: data-parallel runs are not built")
-    su = rigged_setup(a.P, a.res, dev, views=a.views, sh_degree=a.sh_degree, use_graph=not a.no_graph, fold_binding=not a.binding_op)
+    from fateavatar_amd.rigged import REFERENCE_REGULARISERS, Regularisers
+    reg = None
+    if a.regularisers or a.reg_weights or a.reg_thresholds:
+        reg = Regularisers(*(a.reg_weights or REFERENCE_REGULARISERS[:2]), *(a.reg_thresholds or REFERENCE_REGULARISERS[2:]))
+    su = rigged_setup(a.P, a.res, dev, views=a.views, sh_degree=a.sh_degree, use_graph=not a.no_graph, fold_binding=not a.binding_op,
+                      regularisers=reg)
     st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
+    # the compressed maintenance schedule, in steps of the timed loop (train/iteration.py:158-177)
+    densify_from = int(round(a.densify_from * a.steps)) if a.densify_from > 0 else 0
+    densify_every = max(1, int(round(a.densify_interval * a.steps)))
+    reset_every = max(1, int(round(a.reset_interval * a.steps))) if a.reset_interval > 0 else 0
+    gen = torch.Generator().manual_seed(0)
     losses, warm = [], 10
     for it in range(warm):
         losses.append(st.step(cams[it % n_frames], posed_t[it % n_frames], gts[it % n_frames]).clone())
@@ -253,6 +278,13 @@ def main_rigged(a, rank, world, dev):
         loss = st.step(cams[it % n_frames], posed_t[it % n_frames], gts[it % n_frames])
         if it >= warm + a.steps - 4:
             losses.append(loss.clone())
+        k = it - warm + 1
+        if densify_from and k >= densify_from and k < a.steps and (k - densify_from) % densify_every == 0:
+            did = st.densify_and_prune(max_screen_size=20 if reset_every and k > reset_every else None, generator=gen)
+            print(f"step {k}: cloned / split / pruned {did}, P {st.pc.P}, min binding_counter {int(st.binding_counter.min())}",
+                  file=sys.stderr)
+        if reset_every and k < a.steps and k % reset_every == 0:
+            st.reset_opacity()
     t_host = time.perf_counter() - t0
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -263,6 +295,8 @@ def main_rigged(a, rank, world, dev):
                       "binding": "stand-alone kernels" if a.binding_op else "inside the per-Gaussian kernels (fr_aux::binding, face-local)",
                       "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": st.pc.P, "res": a.res,
                       "frames": n_frames, "sh_degree": st.pc.active_sh_degree, "graph": not a.no_graph, "overflows": st.overflows,
+                      "regularisers": list(reg) if reg else None,
+                      "reg_loss": [round(float(x), 6) for x in st.reg_loss] if reg else None,
                       "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
 
 
