@@ -512,6 +512,34 @@ int fr_l1_loss_grad_batch(int32_t n_images, uint64_t n, const float* const* img,
     return launch_l1_loss_grad_batch(n_images, n, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
+void fr_ssim_window(float out[11])
+{
+    if (out) ssim_window(out);
+}
+
+size_t fr_image_loss_workspace_bytes(int32_t C, int32_t H, int32_t W) { return image_loss_workspace_bytes(C, H, W); }
+
+int fr_image_loss_grad(const fr_image_loss_config* cfg, int32_t n_images, int32_t C, int32_t H, int32_t W, const float* const* img,
+                       const float* const* gt, float* const* grad, float* const* loss, void* const* workspace, void* stream)
+{
+    if (!cfg) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: null configuration");
+    if (n_images < 1 || n_images > kMaxBatch) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: 1 .. FR_MAX_BATCH images");
+    if (C < 1 || H < 1 || W < 1 || (int64_t)n_images * C > 65535 || H > (1 << 20) || W > (1 << 20))
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: C, H, W >= 1, n_images x C <= 65535, H, W <= 2^20");
+    if (!img || !gt || !loss || !workspace) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: null argument array");
+    for (int k = 0; k < n_images; k++) {
+        if (!img[k] || !gt[k] || !loss[k] || !workspace[k]) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: null array");
+        uintptr_t align = reinterpret_cast<uintptr_t>(workspace[k]);
+        // (the D-SSIM-free path is k_l1_loss_grad's float4 walk)
+        if (cfg->dssim_weight == 0.f)
+            align |= reinterpret_cast<uintptr_t>(img[k]) | reinterpret_cast<uintptr_t>(gt[k]) | (grad ? reinterpret_cast<uintptr_t>(grad[k]) : 0);
+        if (align & 15) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: arrays must be 16-byte aligned");
+        for (int j = 0; j < k; j++)
+            if (workspace[j] == workspace[k]) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: one workspace per image");
+    }
+    return launch_image_loss_grad(*cfg, n_images, C, H, W, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
+}
+
 size_t fr_regularise_workspace_bytes(void) { return regularise_workspace_bytes(); }
 
 int fr_gaussian_regularise(const fr_regularise_config* cfg, int32_t P, const float* scaling, const float* xyz, float* d_scaling,

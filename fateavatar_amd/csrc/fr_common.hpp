@@ -463,6 +463,15 @@ int launch_l1_loss_grad_batch(int n_images, unsigned long long n, const float* c
                               float* const* loss, void* const* workspace, hipStream_t s);
 int launch_l1_loss_grad(unsigned long long n, const float* img, const float* gt, float* grad, float* loss, void* workspace,
                         hipStream_t s);
+// the L1 term with fr_image_loss_grad's outputs (loss = {rgb_weight x l1, l1, 0}, gradient rgb_weight x sign / n): its path
+// for a D-SSIM weight of 0 (fr_optim.hip, k_l1_loss_grad's sums bit for bit)
+int launch_l1_loss_grad_terms(int n_images, unsigned long long n, float rgb_weight, const float* const* img, const float* const* gt,
+                              float* const* grad, float* const* loss, void* const* workspace, hipStream_t s);
+// L1 + D-SSIM image loss and its gradient (fr_ssim.hip)
+void ssim_window(float out[11]);
+size_t image_loss_workspace_bytes(int C, int H, int W);
+int launch_image_loss_grad(const fr_image_loss_config& cfg, int n_images, int C, int H, int W, const float* const* img,
+                           const float* const* gt, float* const* grad, float* const* loss, void* const* workspace, hipStream_t s);
 int launch_scaled_sum(int n_src, const float* const* src, float* dst, unsigned long long count, float scale, hipStream_t s);
 size_t regularise_workspace_bytes();
 int launch_gaussian_regularise(const fr_regularise_config& cfg, int P, const float* scaling, const float* xyz, float* d_scaling,
@@ -498,6 +507,21 @@ __device__ __forceinline__ void cov3d_from_scale_rot(float sc0, float sc1, float
     c3[3] = m10 * m10 + m11 * m11 + m12 * m12;
     c3[4] = m20 * m10 + m21 * m11 + m22 * m12;
     c3[5] = m20 * m20 + m21 * m21 + m22 * m22;
+}
+// "Which workgroup of this launch finishes last?" with TWO levels of wrapping counters: atomics on one address are
+// served one at a time (about 10 ns each on MI355X: a single counter costs 8 us for 768 workgroups, 75 us for 8192), so
+// a workgroup counts itself into one of kDoneGroups counters and only the last of each group into the final one.
+// The counters sit in separate 128-byte lines: the L2 serves atomics on one LINE one at a time, too.
+// `c`: (kDoneGroups + 1) x kDoneStride zeroed words, left zeroed.  `id` of `count`: the workgroup's index among those that
+// share the counters.  Call from one thread per workgroup.
+constexpr unsigned kDoneGroups = 16, kDoneStride = 32;
+__device__ __forceinline__ bool last_workgroup_of(unsigned* c, unsigned id, unsigned count)
+{
+    const unsigned groups = count < kDoneGroups ? count : kDoneGroups;
+    const unsigned g = id % groups;
+    const unsigned members = (count - g + groups - 1u) / groups;   // workgroups b with b % groups == g
+    if (atomicInc(c + g * kDoneStride, members - 1u) != members - 1u) return false;  // (wraps back to 0)
+    return atomicInc(c + kDoneGroups * kDoneStride, groups - 1u) == groups - 1u;
 }
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 

@@ -10,20 +10,8 @@
 
 namespace fr {
 
-// "Which workgroup of this launch finishes last?" with TWO levels of wrapping counters: atomics on one address are
-// served one at a time (about 10 ns each on MI355X: a single counter costs 8 us for 768 workgroups, 75 us for 8192), so
-// a workgroup counts itself into one of kDoneGroups counters and only the last of each group into the final one.
-// The counters sit in separate 128-byte lines: the L2 serves atomics on one LINE one at a time, too.
-// `c`: (kDoneGroups + 1) x kDoneStride zeroed words, left zeroed.  Call from one thread per workgroup.
-constexpr unsigned kDoneGroups = 16, kDoneStride = 32;
-__device__ __forceinline__ bool last_workgroup(unsigned* c)
-{
-    const unsigned groups = gridDim.x < kDoneGroups ? gridDim.x : kDoneGroups;
-    const unsigned g = blockIdx.x % groups;
-    const unsigned members = (gridDim.x - g + groups - 1u) / groups;   // workgroups b with b % groups == g
-    if (atomicInc(c + g * kDoneStride, members - 1u) != members - 1u) return false;  // (wraps back to 0)
-    return atomicInc(c + kDoneGroups * kDoneStride, groups - 1u) == groups - 1u;
-}
+// (last_workgroup_of, kDoneGroups, kDoneStride: fr_common.hpp)  Call from one thread per workgroup of a 1-D grid.
+__device__ __forceinline__ bool last_workgroup(unsigned* c) { return last_workgroup_of(c, blockIdx.x, gridDim.x); }
 
 struct AdamArgs {
     int n_seg;
@@ -183,7 +171,10 @@ struct L1View {   // one image of a (possibly batched) launch
     float* loss;
 };
 
-__device__ __forceinline__ void l1_loss_grad_body(const L1View& v, unsigned long long n, float inv_n)
+// kTerms (fr_image_loss_grad with a D-SSIM weight of 0): the gradient's magnitude is `g` = rgb_weight / n instead of 1 / n,
+// `loss` takes {rgb_weight x l1, l1, 0} and the partials are put back to zero; the sums are those of the plain kernel, bit for bit.
+template <bool kTerms>
+__device__ __forceinline__ void l1_loss_grad_body(const L1View& v, unsigned long long n, float inv_n, float g_mag, float rgb_weight)
 {
     const float* __restrict__ img = v.img;
     const float* __restrict__ gt = v.gt;
@@ -202,7 +193,7 @@ __device__ __forceinline__ void l1_loss_grad_body(const L1View& v, unsigned long
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             acc += fabsf(d[k]);
-            g[k] = d[k] > 0.f ? inv_n : (d[k] < 0.f ? -inv_n : 0.f);   // torch.sign: 0 at 0
+            g[k] = d[k] > 0.f ? g_mag : (d[k] < 0.f ? -g_mag : 0.f);   // torch.sign: 0 at 0
         }
         if (grad) reinterpret_cast<float4*>(grad)[i] = make_float4(g[0], g[1], g[2], g[3]);
     }
@@ -210,7 +201,7 @@ __device__ __forceinline__ void l1_loss_grad_body(const L1View& v, unsigned long
         const unsigned long long e = 4 * n4 + threadIdx.x;
         const float d = img[e] - gt[e];
         acc += fabsf(d);
-        if (grad) grad[e] = d > 0.f ? inv_n : (d < 0.f ? -inv_n : 0.f);
+        if (grad) grad[e] = d > 0.f ? g_mag : (d < 0.f ? -g_mag : 0.f);
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
@@ -224,20 +215,31 @@ __device__ __forceinline__ void l1_loss_grad_body(const L1View& v, unsigned long
     __syncthreads();
     if (!s_last) return;
     float t = 0.f;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x)
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
         t += __hip_atomic_load(partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (kTerms) __hip_atomic_store(partial + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = t;
     __syncthreads();
-    if (threadIdx.x == 0) *loss = ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) * inv_n;
+    if (threadIdx.x == 0) {
+        const float l1 = ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) * inv_n;
+        if (kTerms) loss[0] = rgb_weight * l1, loss[1] = l1, loss[2] = 0.f;
+        else *loss = l1;
+    }
 }
 
-__global__ void __launch_bounds__(256) k_l1_loss_grad(L1View v, unsigned long long n, float inv_n) { l1_loss_grad_body(v, n, inv_n); }
+__global__ void __launch_bounds__(256) k_l1_loss_grad(L1View v, unsigned long long n, float inv_n) { l1_loss_grad_body<false>(v, n, inv_n, inv_n, 1.f); }
 // the images of the frames of a batch (same size), one workspace each: grid (x, images)
 __global__ void __launch_bounds__(256) k_l1_loss_grad_batch(BatchOf<L1View> b, unsigned long long n, float inv_n)
 {
-    l1_loss_grad_body(b.v[blockIdx.y], n, inv_n);
+    l1_loss_grad_body<false>(b.v[blockIdx.y], n, inv_n, inv_n, 1.f);
+}
+// the L1 term alone behind fr_image_loss_grad (three loss words per image, weighted gradient)
+__global__ void __launch_bounds__(256) k_l1_loss_grad_terms(BatchOf<L1View> b, unsigned long long n, float inv_n, float g_mag, float rgb_weight)
+{
+    l1_loss_grad_body<true>(b.v[blockIdx.y], n, inv_n, g_mag, rgb_weight);
 }
 
 int launch_l1_loss_grad(unsigned long long n, const float* img, const float* gt, float* grad, float* loss, void* workspace,
@@ -268,6 +270,25 @@ int launch_l1_loss_grad_batch(int n_images, unsigned long long n, const float* c
                         counter, loss[j]};
     }
     hipLaunchKernelGGL(k_l1_loss_grad_batch, dim3((unsigned)blocks, (unsigned)n_images), dim3(256), 0, s, b, n, (float)(1.0 / (double)n));
+    FR_HIP(hipGetLastError());
+    return FR_OK;
+}
+
+int launch_l1_loss_grad_terms(int n_images, unsigned long long n, float rgb_weight, const float* const* img, const float* const* gt,
+                              float* const* grad, float* const* loss, void* const* workspace, hipStream_t s)
+{
+    if (n == 0 || n_images <= 0) return FR_OK;
+    unsigned long long blocks = (n / 4 + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks > kL1MaxBlocks ? kL1MaxBlocks : blocks);
+    BatchOf<L1View> b;
+    for (int k = 0; k < kMaxBatch; k++) {
+        const int j = k < n_images ? k : 0;
+        unsigned* counter = static_cast<unsigned*>(workspace[j]);
+        b.v[k] = L1View{img[j], gt[j], grad ? grad[j] : nullptr, reinterpret_cast<float*>(counter + (kDoneGroups + 1) * kDoneStride),
+                        counter, loss[j]};
+    }
+    hipLaunchKernelGGL(k_l1_loss_grad_terms, dim3((unsigned)blocks, (unsigned)n_images), dim3(256), 0, s, b, n, (float)(1.0 / (double)n),
+                       (float)((double)rgb_weight / (double)n), rgb_weight);
     FR_HIP(hipGetLastError());
     return FR_OK;
 }

@@ -4,10 +4,12 @@ reference: `nn.L1Loss(reduction='mean')` on the rendered image (model/loss.py:92
 launch-bound PyTorch kernels between the rasterizer's forward and its backward.  `l1_loss_and_grad` produces the loss
 and the gradient autograd would hand to the rasterizer (`sign(img - gt) / n`, for a unit upstream gradient) in one
 launch of the HIP library (`fr_l1_loss_grad`, include/fr_rasterizer.h); the caller continues with
-`render.backward(grad)`.  There is no CPU path."""
+`render.backward(grad)`.  `image_loss_and_grad` is the same for the weighted L1 + D-SSIM objective of GaussianAvatars and
+3DGS (train/loss.py:351-365, tools/loss_utils/dssim.py:28-56) in two launches (`fr_image_loss_grad`), and `d_ssim` the
+reference's function as an autograd op on those kernels.  There is no CPU path."""
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -213,3 +215,149 @@ def scaled_sum(dst: torch.Tensor, srcs, scale: float) -> torch.Tensor:
     if rc != _lib.FR_OK:
         raise RuntimeError(f"fr_scaled_sum failed: {_lib.last_error()}")
     return dst
+
+
+# ---- L1 + D-SSIM (GaussianAvatarsLoss, train/loss.py:351-365; d_ssim of tools/loss_utils/dssim.py:28-56): two launches of
+# the HIP library (`fr_image_loss_grad`) give the three loss scalars and the gradient autograd would hand to the rasterizer
+class ImageLoss(NamedTuple):
+    """Weights of the image term: loss = rgb_weight * L1 + dssim_weight * d_ssim (config/gaussianavatars.yaml:16-20 has
+    0.8 and 0.2, the original 3DGS mix)."""
+    rgb_weight: float
+    dssim_weight: float
+
+
+_image_workspace = {}   # (device index, stream handle) -> workspace of fr_image_loss_grad (as _workspace above), see _default_image_workspace
+
+
+def ssim_window() -> torch.Tensor:
+    """The eleven 1-D taps of d_ssim's window, `gaussian(11, 1.5)` of dssim.py:18-20 in its float32 arithmetic (CPU tensor)."""
+    import ctypes as C
+    out = (C.c_float * 11)()
+    _lib.lib().fr_ssim_window(out)
+    return torch.tensor(list(out), dtype=torch.float32)
+
+
+def image_loss_workspace(dev: torch.device, C: int, H: int, W: int) -> torch.Tensor:
+    """A fresh zeroed workspace for `image_loss_and_grad(..., workspace=)` on [C,H,W] images."""
+    if min(int(C), int(H), int(W)) < 1:
+        raise RuntimeError("image_loss_workspace: C, H, W >= 1")
+    return torch.zeros((_lib.lib().fr_image_loss_workspace_bytes(int(C), int(H), int(W)),), dtype=torch.uint8, device=dev)
+
+
+def _chw(t: torch.Tensor, what: str):
+    if t.dim() == 4 and t.shape[0] == 1:
+        return tuple(t.shape[1:])
+    if t.dim() != 3:
+        raise RuntimeError(f"{what}: images are [C,H,W] or [1,C,H,W], got {tuple(t.shape)}")
+    return tuple(t.shape)
+
+
+def image_loss_and_grad_batch(imgs, gts, weights, loss_outs, grad_outs, workspaces):
+    """`image_loss_and_grad` for the images of the 1 .. 4 frames of a batch in ONE launch pair (`fr_image_loss_grad`): lists of
+    equally-shaped contiguous float32 device tensors; every image has its own 3-element loss tensor, gradient buffer (an
+    entry may be None: losses only) and workspace (`image_loss_workspace()`).  Returns (loss_outs, grad_outs)."""
+    import ctypes as C
+    K = len(imgs)
+    if not (1 <= K <= _lib.FR_MAX_BATCH and len(gts) == len(loss_outs) == len(grad_outs) == len(workspaces) == K):
+        raise RuntimeError(f"image_loss_and_grad_batch: 1 .. {_lib.FR_MAX_BATCH} images, one gt / loss / grad / workspace each")
+    imgs = [i.detach() for i in imgs]
+    dev = imgs[0].device
+    tensors = list(imgs) + list(gts) + [g for g in grad_outs if g is not None]
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("image_loss_and_grad_batch needs device tensors (there is no CPU path)")
+    shape = _chw(imgs[0], "image_loss_and_grad_batch")
+    for t in tensors:
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or _chw(t, "image_loss_and_grad_batch") != shape:
+            raise RuntimeError("image_loss_and_grad_batch: contiguous float32 tensors of one device and one shape")
+    L = _lib.lib()
+    need = L.fr_image_loss_workspace_bytes(*shape)
+    for w, l in zip(workspaces, loss_outs):
+        if not (w.is_cuda and w.device == dev and w.dtype == torch.uint8 and w.numel() >= need):
+            raise RuntimeError(f"image_loss_and_grad_batch: workspace must come from image_loss_workspace() for this image shape "
+                               f"on the images' device ({need} bytes)")
+        if not (l.is_cuda and l.device == dev and l.dtype == torch.float32 and l.numel() == 3 and l.is_contiguous()):
+            raise RuntimeError("image_loss_and_grad_batch: contiguous 3-element float32 loss tensors on the images' device")
+    arr = lambda ts: (C.c_void_p * K)(*[None if t is None else t.data_ptr() for t in ts])  # noqa: E731
+    cfg = _lib.fr_image_loss_config(float(weights[0]), float(weights[1]))
+    with torch.cuda.device(dev):
+        rc = L.fr_image_loss_grad(C.byref(cfg), K, shape[0], shape[1], shape[2], arr(imgs), arr(gts), arr(grad_outs), arr(loss_outs),
+                                  arr(workspaces), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != _lib.FR_OK:
+        raise RuntimeError(f"fr_image_loss_grad failed: {_lib.last_error()}")
+    return loss_outs, grad_outs
+
+
+def _default_image_workspace(dev: torch.device, shape, what: str) -> torch.Tensor:
+    """The (device, current stream)'s own workspace, grown to the largest shape asked for (one buffer per stream, not one per
+    shape: the maps take 12 bytes per pixel and channel)."""
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    need = _lib.lib().fr_image_loss_workspace_bytes(*shape)
+    ws = _image_workspace.get(key)
+    if ws is None or ws.numel() < need:
+        if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
+            raise RuntimeError(f"{what}: the first call for this image size on this stream happens inside a graph capture; call it "
+                               "once eagerly on the stream first, or pass workspace=image_loss_workspace(device, C, H, W)")
+        ws = _image_workspace[key] = image_loss_workspace(dev, *shape)
+    return ws
+
+
+def image_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, weights, loss_out: Optional[torch.Tensor] = None,
+                        grad_out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`weights` = (rgb_weight, dssim_weight), e.g. an `ImageLoss`: returns the 3-element device tensor
+    (rgb_weight * l1 + dssim_weight * d_ssim, l1, d_ssim) — the last two unweighted — and the gradient of the first with
+    respect to `img`, of `img`'s shape.  `img`, `gt`: [C,H,W] or [1,C,H,W].  `loss_out` / `grad_out`: write into these
+    tensors instead of fresh ones (buffers of a captured step).  `workspace`: scratch from `image_loss_workspace()`; by
+    default one is kept per (device, current stream) — launches that may overlap must not share one.  The losses without the
+    gradient: `image_loss_and_grad_batch` with a None gradient entry."""
+    if not (img.is_cuda and gt.is_cuda):
+        raise RuntimeError("image_loss_and_grad needs device tensors (there is no CPU path)")
+    if img.shape != gt.shape:
+        raise RuntimeError(f"image_loss_and_grad: shapes differ: {tuple(img.shape)} vs {tuple(gt.shape)}")
+    shape = _chw(img, "image_loss_and_grad")
+    img = img.detach()
+    if img.dtype != torch.float32 or not img.is_contiguous():
+        img = img.float().contiguous()
+    if gt.dtype != torch.float32 or not gt.is_contiguous():
+        gt = gt.float().contiguous()
+    dev = img.device
+    grad = grad_out if grad_out is not None else torch.empty_like(img)
+    loss = loss_out if loss_out is not None else torch.empty((3,), dtype=torch.float32, device=dev)
+    if (grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != dev
+            or loss.numel() != 3 or loss.dtype != torch.float32 or loss.device != dev or not loss.is_contiguous()):
+        raise RuntimeError("image_loss_and_grad: bad output buffers (gradient of the image's shape, 3-element loss, float32, contiguous)")
+    ws = workspace if workspace is not None else _default_image_workspace(dev, shape, "image_loss_and_grad")
+    image_loss_and_grad_batch([img], [gt], weights, [loss], [grad], [ws])
+    return loss, grad
+
+
+class _DSsim(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img1, img2):
+        if not (img1.is_cuda and img2.is_cuda):
+            raise RuntimeError("d_ssim needs device tensors (there is no CPU path)")
+        if img1.shape != img2.shape:
+            raise RuntimeError(f"d_ssim: shapes differ: {tuple(img1.shape)} vs {tuple(img2.shape)}")
+        x, y = img1.detach().float().contiguous(), img2.detach().float().contiguous()
+        grad = torch.empty_like(x) if ctx.needs_input_grad[0] else None     # None: losses only, pass 2 is not launched
+        loss = torch.empty(3, dtype=torch.float32, device=x.device)
+        image_loss_and_grad_batch([x], [y], (0.0, 1.0), [loss], [grad], [_default_image_workspace(x.device, _chw(x, "d_ssim"), "d_ssim")])
+        if grad is not None:
+            ctx.save_for_backward(grad.view(img1.shape))
+        ctx.in_dtype = img1.dtype
+        return loss[2].clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        return (grad * grad_output).to(ctx.in_dtype), None
+
+
+def d_ssim(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
+    """`d_ssim` of the reference (tools/loss_utils/dssim.py:28-56; window 11, averaged): 1 - mean SSIM map as a 0-dim tensor,
+    differentiable with respect to `img1` (the fused kernels' gradient, scaled by the incoming one).  The target takes no
+    gradient: `img2.requires_grad` raises."""
+    if img2.requires_grad:
+        raise RuntimeError("d_ssim: the target (img2) takes no gradient; detach it")
+    return _DSsim.apply(img1, img2)

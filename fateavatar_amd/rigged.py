@@ -13,14 +13,16 @@ reference:
 What is fused: the binding runs inside the rasterizer's per-Gaussian kernels (bound.render_bound_batch with a
 FaceLocalBinding; `fold_binding=False` keeps the stand-alone op as the A/B), activations and densification statistics run
 inside the rasterizer kernels, one L1 launch, one Adam launch over the flat buffer, the whole step ONE HIP graph.
+  * the image term — `GaussianAvatarsLoss` (train/loss.py:351-365): rgb_weight x L1 + dssim_weight x d_ssim with the weights of
+    config/gaussianavatars.yaml:16-20: `RiggedStep(image_loss=REFERENCE_IMAGE_LOSS)`, two launches in the L1 launch's place
+    (`loss.image_loss_and_grad`)
   * the scale / xyz regularisers — `GaussianAvatarsLoss.accumulate_gradients` (train/loss.py:367-379) with the weights and
     thresholds of config/gaussianavatars.yaml: `RiggedStep(regularisers=...)`, one more launch inside the captured step
     (`loss.gaussian_regularisers`) that adds their gradients in front of Adam
   * density control — `_densify_and_prune`, `_clone_densify`, `_split_densify`, `_prune` with `binding_counter`,
     `_reset_opacity` (gaussianavatars.py:278-495): `RiggedStep.densify_and_prune / prune / prune_low_opacity /
     reset_opacity`, torch index surgery between steps
-Not here: the D-SSIM term and `rgb_weight` (the image term keeps weight 1), the position learning-rate schedule,
-`max_radii2D` (see `densify_and_prune`), a multi-lane batch step, data-parallel runs, FLAME.
+Not here: the position learning-rate schedule, `max_radii2D` (see `densify_and_prune`), a multi-lane batch step, data-parallel runs, FLAME.
 """
 from __future__ import annotations
 
@@ -31,7 +33,7 @@ import torch
 
 from .binding import bind_gaussians_face_local
 from .bound import FaceLocalBinding, render_bound_batch
-from .loss import gaussian_regularisers, l1_loss_and_grad, l1_workspace, regulariser_workspace
+from .loss import ImageLoss, gaussian_regularisers, l1_workspace, regulariser_workspace
 from .model import TorchCamera
 from .optim import FusedAdam
 from .rasterizer import GradOut
@@ -52,6 +54,8 @@ class Regularisers(NamedTuple):
 
 # the reference's values (config/gaussianavatars.yaml:13-20)
 REFERENCE_REGULARISERS = Regularisers(scale_weight=1.0, xyz_weight=0.01, threshold_scale=0.6, threshold_xyz=1.0)
+# rgb_weight, dssim_weight of the image term (config/gaussianavatars.yaml:16-20)
+REFERENCE_IMAGE_LOSS = ImageLoss(rgb_weight=0.8, dssim_weight=0.2)
 PERCENT_DENSE = 0.01     # gaussianavatars.py:47
 
 
@@ -197,14 +201,18 @@ class RiggedStep(TrainStep):
 
     def __init__(self, pc: RiggedGaussians, faces: torch.Tensor, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True,
-                 regularisers: Optional[Regularisers] = None):
+                 regularisers: Optional[Regularisers] = None, image_loss: Optional[ImageLoss] = None):
         """`verts` [V,3]: any pose of the mesh (sizes the step's static vertex buffer and is its first content).
         `fold_binding` (default): the binding is evaluated inside the rasterizer's per-Gaussian kernels (fr_aux::binding with
         FR_BIND_FACE_LOCAL) — no binding launches.  False: the stand-alone `bind_gaussians_face_local` op in front of
         render() (same results; the A/B and the op's own user).
         `regularisers`: a `Regularisers` (REFERENCE_REGULARISERS holds the reference's values) adds the scale / xyz terms of
         train/loss.py:367-379 to every step — one launch between the backward and Adam; `reg_loss` then holds the step's
-        unweighted (scale_loss, xyz_loss).  None (default): no such launch, `reg_loss` is None."""
+        unweighted (scale_loss, xyz_loss).  None (default): no such launch, `reg_loss` is None.
+        `image_loss`: an `ImageLoss` (REFERENCE_IMAGE_LOSS holds the reference's 0.8 / 0.2) makes the image term
+        rgb_weight x L1 + dssim_weight x d_ssim (train/loss.py:351-365) — two launches where the L1 launch is; `loss_terms`
+        then holds the step's (weighted image loss, l1, d_ssim) and `loss` is its first word.  None (default): the image
+        term is L1 with weight 1, `loss_terms` is None."""
         if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise RuntimeError("RiggedStep: data-parallel runs are not built (DESIGN.md)")
         self.pc, self.bg = pc, bg
@@ -222,6 +230,7 @@ class RiggedStep(TrainStep):
         self.loss = torch.zeros((), device=self.dev)
         self._dimage = torch.zeros_like(self.gt)   # dL/dimage of the step
         self._l1_ws = l1_workspace(self.dev)
+        self._init_image_loss(image_loss)
         self.regularisers = None if regularisers is None else Regularisers(*[float(x) for x in regularisers])
         # the reference's out['scale_loss'] / out['xyz_loss'] of the step (unweighted), written by the regulariser launch
         self.reg_loss = None if regularisers is None else torch.zeros(2, device=self.dev)
@@ -262,8 +271,7 @@ class RiggedStep(TrainStep):
         else:
             bound = bind_gaussians_face_local(self.verts, self.faces, pc.binding, pc._xyz, pc._rotation, pc._scaling)
             out = render(self.cam, _RiggedFrame(pc, stats, bound), self.bg)
-        _, g = l1_loss_and_grad(out["render"], self.gt, loss_out=self.loss, grad_out=self._dimage, workspace=self._l1_ws)   # see TrainStep
-        out["render"].backward(g)
+        out["render"].backward(self._image_loss_and_grad(out["render"]))   # see TrainStep
         pc.collect_grads()                                          # (the SH halves: see RiggedGaussians.collect_grads)
         if self.regularisers is not None:
             # train/loss.py:367-379: weight x the two regularisers' gradients are ADDED to the image term's, in front of Adam.

@@ -21,7 +21,7 @@ from typing import Optional
 import torch
 
 from . import dp
-from .loss import l1_loss_and_grad, l1_workspace, multi_copy
+from .loss import ImageLoss, image_loss_and_grad, image_loss_workspace, l1_loss_and_grad, l1_workspace, multi_copy
 from .model import FlatGaussians, TorchCamera
 from .optim import FusedAdam
 from .render import render
@@ -32,7 +32,11 @@ DEFAULT_LRS = dict(xyz=1.6e-4, feature_dc=2.5e-3, feature_rest=2.5e-3 / 20, opac
 
 class TrainStep:
     def __init__(self, pc: FlatGaussians, camera: TorchCamera, bg: torch.Tensor, lrs: Optional[dict] = None,
-                 use_graph: bool = True):
+                 use_graph: bool = True, image_loss: Optional[ImageLoss] = None):
+        """`image_loss`: an `ImageLoss(rgb_weight, dssim_weight)` makes the image term rgb_weight x L1 + dssim_weight x d_ssim
+        (the original 3DGS objective is ImageLoss(0.8, 0.2)): two launches of `loss.image_loss_and_grad` where the L1 launch
+        is; `loss_terms` then holds the step's (weighted total, l1, d_ssim) and `loss` is its first word.  None (default):
+        the plain L1 step, `loss_terms` is None."""
         if not pc.fused_activations:
             raise ValueError("TrainStep drives the fused path: build FlatGaussians(..., fused_activations=True)")
         self.pc, self.bg = pc, bg
@@ -66,6 +70,7 @@ class TrainStep:
         self.loss = torch.zeros((), device=self.dev)
         self._dimage = torch.zeros_like(self.gt)   # dL/dimage of the step
         self._l1_ws = l1_workspace(self.dev)       # scratch of this step's loss kernel (not shared with launches that may overlap)
+        self._init_image_loss(image_loss)
         self.out = None
         self.use_graph = bool(use_graph)
         self._graph = None       # render .. backward (.. Adam when world == 1)
@@ -73,14 +78,32 @@ class TrainStep:
         self.overflows = 0       # replayed frames that overflowed the captured binning capacity (see _poll_overflow)
         self.host_steps = 0      # step() calls; the device's own count of APPLIED updates is adam.step_count (skipped_steps)
 
+    def _init_image_loss(self, image_loss):
+        """The step's L1 + D-SSIM buffers (after self.gt / self.loss exist): `loss` becomes a view of loss_terms[0]."""
+        self.image_loss = None if image_loss is None else ImageLoss(*[float(x) for x in image_loss])
+        self.loss_terms, self._image_ws = None, None
+        if self.image_loss is not None:
+            self.loss_terms = torch.zeros(3, device=self.dev)
+            self.loss = self.loss_terms[0]
+            self._image_ws = image_loss_workspace(self.dev, *self.gt.shape)
+
+    def _image_loss_and_grad(self, image: torch.Tensor) -> torch.Tensor:
+        """dL/dimage of the step's image term, written into the step's buffers with the loss."""
+        if self.image_loss is None:
+            # nn.L1Loss(reduction='mean') (loss.py:92) + loss.backward(): the loss and the gradient autograd would hand to the
+            # rasterizer in one launch, written straight into the step's buffers
+            _, g = l1_loss_and_grad(image, self.gt, loss_out=self.loss, grad_out=self._dimage, workspace=self._l1_ws)
+        else:
+            _, g = image_loss_and_grad(image, self.gt, self.image_loss, loss_out=self.loss_terms, grad_out=self._dimage,
+                                       workspace=self._image_ws)
+        return g
+
     # -- the step body: everything between zero_grad and the gradient exchange
     def _forward_backward(self):
         self.pc.begin_step()                                   # zero_grad(set_to_none=True), iteration.py:48-49
         out = render(self.cam, self.pc, self.bg)               # activations + rasterizer (fused)
-        # nn.L1Loss(reduction='mean') (loss.py:92) + loss.backward(): the loss and the gradient autograd would hand to the
-        # rasterizer in one launch, written straight into the step's buffers; then the rasterizer backward (stats fused)
-        _, g = l1_loss_and_grad(out["render"], self.gt, loss_out=self.loss, grad_out=self._dimage, workspace=self._l1_ws)
-        out["render"].backward(g)
+        # the image term and its gradient (_image_loss_and_grad), then the rasterizer backward (stats fused)
+        out["render"].backward(self._image_loss_and_grad(out["render"]))
         # keep the step's outputs WITHOUT their autograd graph: a graph kept alive across steps keeps its
         # AccumulateGrad nodes (and the stream they were created on) alive, which breaks a later stream capture
         self.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}

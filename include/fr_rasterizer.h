@@ -343,6 +343,31 @@ int fr_l1_loss_grad(uint64_t n, const float* img, const float* gt, float* grad, 
 int fr_l1_loss_grad_batch(int32_t n_images, uint64_t n, const float* const* img, const float* const* gt, float* const* grad,
                           float* const* loss, void* const* workspace, void* hip_stream);
 
+/* ---- L1 + D-SSIM image loss and its gradient with respect to the rendered image in TWO launches (reference:
+ * GaussianAvatarsLoss, train/loss.py:351-365, with rgb_weight 0.8 and dssim_weight 0.2 of config/gaussianavatars.yaml:16-20 —
+ * the original 3DGS objective; d_ssim is tools/loss_utils/dssim.py:28-56: five grouped F.conv2d with an 11 x 11 Gaussian
+ * window of sigma 1.5, zero padding 5, a dozen elementwise kernels, and autograd's backward of all of them):
+ *   loss[0] = rgb_weight * loss[1] + dssim_weight * loss[2],  loss[1] = mean |img - gt|,  loss[2] = 1 - mean(ssim_map)
+ *   grad    = rgb_weight * sign(img - gt) / N + dssim_weight * d loss[2] / d img,         N = C H W
+ * for n_images (1 .. FR_MAX_BATCH) images of C x H x W floats each, every image with its own gt / grad / loss (3 device
+ * floats) / workspace (distinct).  `grad` may be NULL, or hold NULL entries: losses only for those images.  The first launch
+ * stores three derivative maps of the SSIM map in the workspace and reduces the two sums, the second convolves the maps and
+ * writes the gradient (one plain store per pixel); no float atomics, the results are bit-reproducible from launch to launch.
+ * A dssim_weight of 0 runs fr_l1_loss_grad's kernel alone: gradient and loss[1] are that entry's, bit for bit (for an
+ * rgb_weight of 1), loss[2] is 0; the image arrays must then be 16-byte aligned.
+ * `workspace`: fr_image_loss_workspace_bytes(C, H, W) bytes of device memory, 16-byte aligned: counters and per-workgroup
+ * partial sums, zeroed ONCE by the caller and left zeroed by the kernels, in front of 12 C H W bytes for the maps, which
+ * are written before they are read and need no initial value.  Not to be shared by launches that can overlap on the device.
+ * fr_ssim_window: the eleven 1-D taps in the reference's float32 arithmetic (dssim.py:18-20); host only, as is the size query. */
+typedef struct fr_image_loss_config {
+    float rgb_weight, dssim_weight;       /* reference: 0.8, 0.2 (config/gaussianavatars.yaml) */
+} fr_image_loss_config;
+void fr_ssim_window(float out[11]);
+size_t fr_image_loss_workspace_bytes(int32_t C, int32_t H, int32_t W);
+int fr_image_loss_grad(const fr_image_loss_config* cfg, int32_t n_images, int32_t C, int32_t H, int32_t W,
+                       const float* const* img, const float* const* gt, float* const* grad, float* const* loss,
+                       void* const* workspace, void* hip_stream);
+
 /* ---- GaussianAvatars' two per-Gaussian regularisers and their gradients in ONE launch (reference:
  * GaussianAvatarsLoss.accumulate_gradients, train/loss.py:367-379, on the raw local parameters,
  * model/baseline/gaussianavatars.py:196-197):

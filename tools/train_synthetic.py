@@ -15,6 +15,8 @@ GaussianAvatars' step (fateavatar_amd/rigged.py): Gaussians rigged to the triang
 the same with the reference's scale / xyz regularisers in the step and a compressed maintenance schedule (fractions of
 --steps: config/gaussianavatars.yaml:36-43 has 10 000 / 2 000 / 60 000 of 600 000 iterations); P and min(binding_counter)
 are printed after each densify.
+    python tools/train_synthetic.py --rigged --P 10006 --dssim [--regularisers]
+the reference's image term, 0.8 x L1 + 0.2 x d_ssim (--image-loss RGB DSSIM for other weights; also for the generic step).
 """
 import argparse
 import json
@@ -28,6 +30,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fateavatar_amd import dp, scenes  # noqa: E402
+from fateavatar_amd.loss import ImageLoss  # noqa: E402
 from fateavatar_amd.model import FlatGaussians, TorchCamera  # noqa: E402
 from fateavatar_amd.render import render  # noqa: E402
 from fateavatar_amd.train import TrainStep  # noqa: E402
@@ -66,6 +69,10 @@ def main():
                     help="--rigged: regulariser weights (default 1.0 0.01); implies --regularisers")
     ap.add_argument("--reg-thresholds", type=float, nargs=2, default=None, metavar=("SCALE", "XYZ"),
                     help="--rigged: regulariser thresholds (default 0.6 1.0); implies --regularisers")
+    ap.add_argument("--image-loss", type=float, nargs=2, default=None, metavar=("RGB", "DSSIM"),
+                    help="--rigged and the generic step: the image term is RGB x L1 + DSSIM x d_ssim (two launches where the L1 "
+                         "launch is); default: L1 with weight 1")
+    ap.add_argument("--dssim", action="store_true", help="shorthand for --image-loss 0.8 0.2 (GaussianAvatars' and 3DGS's mix)")
     ap.add_argument("--densify-from", type=float, default=0.0,
                     help="--rigged: first densify_and_prune at this fraction of --steps (0: no densification)")
     ap.add_argument("--densify-interval", type=float, default=0.1, help="--rigged: densify every this fraction of --steps")
@@ -75,7 +82,10 @@ def main():
     rank, world, local = dp.init_from_env()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
+    a.image_loss = ImageLoss(*a.image_loss) if a.image_loss else (ImageLoss(0.8, 0.2) if a.dssim else None)
     if a.fateavatar:
+        if a.image_loss:
+            raise SystemExit("--fateavatar: the D-SSIM term is not part of FateAvatar's objective (dssim_loss 0.0)")
         return main_fateavatar(a, rank, world, dev)
     if a.rigged:
         return main_rigged(a, rank, world, dev)
@@ -92,7 +102,7 @@ def main():
     pc = FlatGaussians(truth.means3D, shs0, truth.opacities * 0.6, truth.scales, truth.rotations, a.sh_degree, dev,
                        fused_activations=True)
     cam = TorchCamera(scenes.head_scene(P=8, res=a.res, sh_degree=a.sh_degree, seed=0, view=0, n_views=a.views).camera, dev)
-    ts = TrainStep(pc, cam, bg, use_graph=not a.no_graph)
+    ts = TrainStep(pc, cam, bg, use_graph=not a.no_graph, image_loss=a.image_loss)
     losses = []
     warm = 10
     for it in range(warm):
@@ -115,6 +125,7 @@ def main():
         print(json.dumps({"metric": "optimisation steps/s (render + L1 + backward + stats + Adam)", "value": round(a.steps / dt, 1),
                           "frames_per_s": round(world * a.steps / dt, 1), "n_gpus": world, "ms_per_step": round(dt / a.steps * 1e3, 4),
                           "P": a.P, "res": a.res, "views": a.views, "graph": not a.no_graph,
+                          "image_loss": list(a.image_loss) if a.image_loss else None,
                           "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
@@ -211,7 +222,7 @@ def main_fateavatar(a, rank, world, dev):
         torch.distributed.destroy_process_group()
 
 
-def rigged_setup(P, res, dev, views=8, sh_degree=3, use_graph=True, fold_binding=True, regularisers=None):
+def rigged_setup(P, res, dev, views=8, sh_degree=3, use_graph=True, fold_binding=True, regularisers=None, image_loss=None):
     """GaussianAvatars' optimisation step on the synthetic INSTA-layout sequence: P Gaussians rigged to the template's faces
     (Gaussian i on face i for the first F = 10 006, the reference's initialisation; further ones on random faces, spread over
     them), the step object, cameras, posed meshes and targets rendered from a hidden ground-truth set of the same binding."""
@@ -250,7 +261,7 @@ def rigged_setup(P, res, dev, views=8, sh_degree=3, use_graph=True, fold_binding
             b = bind_gaussians_face_local(posed_t[f], faces_t.to(torch.int32), gt.binding, gt._xyz, gt._rotation, gt._scaling)
             gts.append(render(cams[f], _RiggedFrame(gt, None, b), bg)["render"].clone())
     st = RiggedStep(pc, faces_t, TorchCamera(insta.camera_arrays(transform)[0], dev), bg, posed_t[0], use_graph=use_graph,
-                    fold_binding=fold_binding, regularisers=regularisers)
+                    fold_binding=fold_binding, regularisers=regularisers, image_loss=image_loss)
     return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames)
 
 
@@ -262,7 +273,7 @@ def main_rigged(a, rank, world, dev):
     if a.regularisers or a.reg_weights or a.reg_thresholds:
         reg = Regularisers(*(a.reg_weights or REFERENCE_REGULARISERS[:2]), *(a.reg_thresholds or REFERENCE_REGULARISERS[2:]))
     su = rigged_setup(a.P, a.res, dev, views=a.views, sh_degree=a.sh_degree, use_graph=not a.no_graph, fold_binding=not a.binding_op,
-                      regularisers=reg)
+                      regularisers=reg, image_loss=a.image_loss)
     st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
     # the compressed maintenance schedule, in steps of the timed loop (train/iteration.py:158-177)
     densify_from = int(round(a.densify_from * a.steps)) if a.densify_from > 0 else 0
@@ -296,6 +307,8 @@ def main_rigged(a, rank, world, dev):
                       "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": st.pc.P, "res": a.res,
                       "frames": n_frames, "sh_degree": st.pc.active_sh_degree, "graph": not a.no_graph, "overflows": st.overflows,
                       "regularisers": list(reg) if reg else None,
+                      "image_loss": list(a.image_loss) if a.image_loss else None,
+                      "loss_terms": [round(float(x), 6) for x in st.loss_terms] if a.image_loss else None,
                       "reg_loss": [round(float(x), 6) for x in st.reg_loss] if reg else None,
                       "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
 
