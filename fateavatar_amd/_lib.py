@@ -24,6 +24,7 @@ FR_FLAG_DEPTH_ALPHA = 8        # depth and alpha planes next to the image (fr_au
 FR_FLAG_ACCUMULATE_SHIFT = 8   # fr_backward: bit (8 + k) = add into the k-th array of fr_grads
 FR_BIND_SHELL = 0              # fr_binding::mode: FateAvatar's barycentric point + shell offset (a zeroed descriptor)
 FR_BIND_FACE_LOCAL = 1         # GaussianAvatars': a free position in the face's local frame (fr_binding::local_xyz)
+FR_BIND_PHONG = 2              # SplattingAvatar's: a point of the posed mesh's Phong surface (uvd travels in local_xyz)
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -33,6 +34,15 @@ class fr_binding(C.Structure):
                 ("face_index", C.c_void_p), ("bary", C.c_void_p), ("face_scale_canonical", C.c_void_p),
                 ("shell_len", C.c_float), ("resize_scale", C.c_int32), ("offset", C.c_void_p), ("rotation", C.c_void_p),
                 ("scaling", C.c_void_p), ("mode", C.c_int32), ("local_xyz", C.c_void_p)]
+
+
+class fr_binding_phong(C.Structure):
+    """A FR_BIND_PHONG descriptor: fr_binding with the mode's three arrays behind it.  `as_binding()` is the `base` member as
+    an fr_binding that SHARES this object's memory (and keeps it alive): what the entry points and fr_aux::binding take."""
+    _fields_ = [("base", fr_binding), ("vert_normals", C.c_void_p), ("vert_quats", C.c_void_p), ("face_ratio", C.c_void_p)]
+
+    def as_binding(self) -> fr_binding:
+        return fr_binding.from_buffer(self)
 
 
 class fr_aux(C.Structure):
@@ -101,7 +111,7 @@ class fr_counts(C.Structure):
 EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile_enable", "fr_profile_read", "fr_geometry_bytes", "fr_image_bytes",
            "fr_binning_bytes", "fr_planes_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
            "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
-           "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward"]
+           "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_phong_frame", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward"]
 
 
 def build(force: bool = False) -> str:
@@ -189,6 +199,10 @@ def lib():
     L.fr_bind_backward.restype = C.c_int
     L.fr_bind_backward_local.argtypes = [C.POINTER(fr_binding), _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
     L.fr_bind_backward_local.restype = C.c_int
+    L.fr_bind_backward_phong.argtypes = [C.POINTER(fr_binding), _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
+    L.fr_bind_backward_phong.restype = C.c_int
+    L.fr_phong_frame.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
+    L.fr_phong_frame.restype = C.c_int
     L.fr_texture_corners.argtypes = [C.c_int32, _fp, C.c_int32, C.c_int32, _fp, C.c_void_p]
     L.fr_texture_corners.restype = C.c_int
     L.fr_texture_lookup.argtypes = [C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(fr_tex_layer), C.c_void_p]

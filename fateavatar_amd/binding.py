@@ -15,10 +15,21 @@ reference's headline baseline: every Gaussian lives in the local frame of one tr
     gaussian._rotation = quaternion_multiply(normalize(matrix_to_quaternion(face_orien_mat))[binding], _rotation)
     gaussian._xyz      = (face_orien_mat[binding] @ _xyz) * face_scaling[binding] + face_center[binding]
 The same two kernels (fr_binding::mode), differentiable w.r.t. verts, the local position, rotation and scaling.
+
+`bind_gaussians_phong` is SplattingAvatar's binding (model/baseline/splattingavatar.py:203-246): every Gaussian is a point of
+the posed mesh's Phong surface,
+    gaussian._scaling  = _scaling * face_area_ratio[fidx]                                  (:244: the raw log-scale is multiplied)
+    gaussian._rotation = quaternion_multiply(sum_k bary_k per_vert_quat[face[k]], _rotation)   (:235, :245)
+    gaussian._xyz      = sum_k bary_k verts[face[k]] + normalize(sum_k bary_k vert_normal[face[k]]) * _uvd[:, 2]   (:224-233, :246)
+`phong_canonical` holds what the mesh fixes once, `phong_frame` is the per-frame mesh pass (vertex normals, per-vertex
+quaternions, face area ratios: ONE kernel without atomics where the reference runs pytorch3d's verts_normals_packed,
+torch.inverse, matrix_to_quaternion and six index_add calls).  Differentiable w.r.t. uvd, rotation and scaling; the mode has no
+gradient to the posed vertices.
 """
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import torch
 
@@ -194,3 +205,151 @@ def bind_gaussians_face_local(verts, faces, binding, local_xyz, rotation, scalin
     scaling [N,3]): the values the reference assigns to gaussian._xyz / gaussian._rotation / gaussian._scaling before
     render()."""
     return _BindFaceLocal.apply(verts, local_xyz, rotation, scaling, faces, binding)
+
+
+class PhongCanonical(NamedTuple):
+    """What SplattingAvatar's binding keeps per MESH (PerVertQuaternion.prepare_cano_per_vert,
+    model/baseline/splattingavatar.py:825-844) plus the vertex -> face incidence list `phong_frame` gathers by."""
+    cano_verts: torch.Tensor      # [V,3] float32
+    faces: torch.Tensor           # [F,3] int32
+    vf_offsets: torch.Tensor      # [V+1] int32: CSR rows, the faces of every vertex ...
+    vf_faces: torch.Tensor        # [3F]  int32: ... ascending within a row
+    face_area: torch.Tensor       # [F]   float32: calc_face_areas of the canonical mesh (:781-791)
+
+
+def phong_canonical(cano_verts: torch.Tensor, faces: torch.Tensor) -> PhongCanonical:
+    """The once-per-mesh side of the Phong-surface binding, in plain torch on the tensors' device (CPU tensors are fine; move
+    the result with `PhongCanonical(*[t.to(device) for t in c])`)."""
+    cano = cano_verts.detach().to(torch.float32).contiguous()
+    f = faces.detach().to(torch.int64)
+    V, F = int(cano.shape[0]), int(f.shape[0])
+    if cano.dim() != 2 or cano.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+        raise RuntimeError("phong_canonical: cano_verts [V,3], faces [F,3]")
+    if F and (int(f.min()) < 0 or int(f.max()) >= V):
+        raise ValueError("phong_canonical: `faces` names a vertex the mesh does not have")
+    # incidence list: the (vertex, face) pairs sorted by vertex, then by face (a face with a repeated corner is listed once
+    # per corner, as the reference's three index_add calls add it)
+    corner = f.reshape(-1)
+    face_of = torch.arange(F, device=f.device).repeat_interleave(3)
+    order = torch.argsort(corner * max(F, 1) + face_of)
+    offsets = torch.zeros(V + 1, dtype=torch.int64, device=f.device)
+    offsets[1:] = torch.cumsum(torch.bincount(corner, minlength=V), dim=0)
+    tri = cano[f]
+    area = torch.linalg.cross(tri[:, 2] - tri[:, 1], tri[:, 0] - tri[:, 1], dim=1).norm(dim=-1) / 2.0
+    return PhongCanonical(cano, f.to(torch.int32).contiguous(), offsets.to(torch.int32), face_of[order].to(torch.int32).contiguous(),
+                          area.contiguous())
+
+
+def phong_frame(canonical: PhongCanonical, verts: torch.Tensor):
+    """One frame of model/baseline/splattingavatar.py:203-215 for the posed `verts` [V,3]: (vert_normals [V,3],
+    vert_quats [V,4], face_ratio [F]) — one launch on the current stream, the same bits on every call.  Not differentiable."""
+    c = canonical
+    verts = _chk(verts.detach(), torch.float32, "verts")
+    V, F, dev = c.cano_verts.shape[0], c.faces.shape[0], verts.device
+    if verts.shape != (V, 3):
+        raise RuntimeError(f"phong_frame: verts must be [{V},3] like the canonical mesh")
+    cano, faces = _chk(c.cano_verts, torch.float32, "cano_verts"), _chk(c.faces, torch.int32, "faces")
+    off, ids = _chk(c.vf_offsets, torch.int32, "vf_offsets"), _chk(c.vf_faces, torch.int32, "vf_faces")
+    area = _chk(c.face_area, torch.float32, "face_area")
+    if off.numel() != V + 1 or ids.numel() != 3 * F or area.numel() != F:
+        raise RuntimeError("phong_frame: the canonical data does not belong to this mesh")
+    vn = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    vq = torch.empty((V, 4), dtype=torch.float32, device=dev)
+    ratio = torch.empty((F,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().fr_phong_frame(V, F, verts.data_ptr(), cano.data_ptr(), faces.data_ptr(), off.data_ptr(), ids.data_ptr(),
+                                       area.data_ptr(), vn.data_ptr(), vq.data_ptr(), ratio.data_ptr(),
+                                       torch.cuda.current_stream(dev).cuda_stream)
+    if rc != _lib.FR_OK:
+        raise RuntimeError(f"fr_phong_frame failed: {_lib.last_error()}")
+    return vn, vq, ratio
+
+
+def _desc_phong(verts, faces, face_index, bary, frame, uvd, rotation, scaling):
+    vn, vq, ratio = frame
+    p = _lib.fr_binding_phong()   # (zero-filled: offset, face_scale_canonical, shell_len, resize_scale are not read in this mode)
+    b = p.base
+    b.N, b.V, b.F = face_index.shape[0], verts.shape[0], faces.shape[0]
+    b.verts, b.faces, b.face_index, b.bary = verts.data_ptr(), faces.data_ptr(), face_index.data_ptr(), bary.data_ptr()
+    b.rotation, b.scaling = rotation.data_ptr(), scaling.data_ptr()
+    b.mode, b.local_xyz = _lib.FR_BIND_PHONG, uvd.data_ptr()
+    p.vert_normals, p.vert_quats, p.face_ratio = vn.data_ptr(), vq.data_ptr(), ratio.data_ptr()
+    return p.as_binding()   # (an fr_binding over the extended descriptor's memory: every caller passes it on as before)
+
+
+def _chk_phong_frame(frame, V, F, who):
+    vn, vq, ratio = (_chk(t, torch.float32, n) for t, n in zip(frame, ("vert_normals", "vert_quats", "face_ratio")))
+    if vn.shape != (V, 3) or vq.shape != (V, 4) or ratio.numel() != F:
+        raise RuntimeError(f"{who}: vert_normals [V,3], vert_quats [V,4], face_ratio [F] (`phong_frame` of the posed mesh)")
+    return vn, vq, ratio
+
+
+class _BindPhong(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, uvd, rotation, scaling, verts, faces, face_index, bary, vn, vq, ratio):
+        verts, uvd = _chk(verts, torch.float32, "verts"), _chk(uvd, torch.float32, "uvd")
+        rotation, scaling = _chk(rotation, torch.float32, "rotation"), _chk(scaling, torch.float32, "scaling")
+        faces, face_index = _chk(faces, torch.int32, "faces"), _chk(face_index, torch.int32, "face_index")
+        bary = _chk(bary, torch.float32, "bary_coords")
+        N, dev = face_index.shape[0], verts.device
+        if verts.dim() != 2 or uvd.shape != (N, 3) or rotation.shape != (N, 4) or scaling.shape != (N, 3) or bary.shape != (N, 3):
+            raise RuntimeError("bind_gaussians_phong: verts [V,3], face_index [N], bary [N,3], uvd [N,3], rotation [N,4], scaling [N,3]")
+        frame = _chk_phong_frame((vn, vq, ratio), verts.shape[0], faces.shape[0], "bind_gaussians_phong")
+        xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        rot = torch.empty((N, 4), dtype=torch.float32, device=dev)
+        scl = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        b = _desc_phong(verts, faces, face_index, bary, frame, uvd, rotation, scaling)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().fr_bind_forward(C.byref(b), xyz.data_ptr(), rot.data_ptr(), scl.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.FR_OK:
+            raise RuntimeError(f"fr_bind_forward failed: {_lib.last_error()}")
+        ctx.save_for_backward(verts, uvd, rotation, scaling, faces, face_index, bary, *frame)
+        from .rasterizer import GradOut   # (the `_fr_grad_out` extension, as _Bind)
+        ctx.grad_slots = (GradOut.of(uvd), GradOut.of(rotation), GradOut.of(scaling))
+        return xyz, rot, scl
+
+    @staticmethod
+    def backward(ctx, g_xyz, g_rot, g_scl):
+        verts, uvd, rotation, scaling, faces, face_index, bary, vn, vq, ratio = ctx.saved_tensors
+        dev, N = verts.device, face_index.shape[0]
+        need_u, need_r, need_s = ctx.needs_input_grad[:3]
+        c = lambda g: g.contiguous().float() if g is not None else None  # noqa: E731
+        g_xyz, g_rot, g_scl = c(g_xyz), c(g_rot), c(g_scl)
+
+        def out(need, slot, shape):
+            if not need:
+                return None
+            buf = slot.claim()[0] if slot is not None else None   # first backward of the step writes the slot in place
+            if buf is not None and buf.numel() == int(torch.Size(shape).numel()) and buf.is_contiguous():
+                return buf.view(shape)
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+
+        d_uvd = out(need_u, ctx.grad_slots[0], (N, 3))
+        d_rot = out(need_r, ctx.grad_slots[1], (N, 4))
+        d_scl = out(need_s, ctx.grad_slots[2], (N, 3))
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        b = _desc_phong(verts, faces, face_index, bary, (vn, vq, ratio), uvd, rotation, scaling)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().fr_bind_backward_phong(C.byref(b), p(g_xyz), p(g_rot), p(g_scl), None, p(d_uvd), p(d_rot), p(d_scl),
+                                                   torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.FR_OK:
+            raise RuntimeError(f"fr_bind_backward_phong failed: {_lib.last_error()}")
+        return d_uvd, d_rot, d_scl, None, None, None, None, None, None, None
+
+
+def _no_vertex_gradient(verts, who):
+    if isinstance(verts, torch.Tensor) and verts.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(f"{who}: the Phong-surface binding has no vertex gradient (the per-frame mesh pass is not "
+                           "differentiable); hand it `verts.detach()`")
+
+
+def bind_gaussians_phong(verts, faces, face_index, bary_coords, frame, uvd, rotation, scaling):
+    """One frame of model/baseline/splattingavatar.py:224-246.  verts [V,3] (posed), faces [F,3], face_index [N],
+    bary_coords [N,3], `frame` = `phong_frame(canonical, verts)` of the same posed mesh, raw uvd [N,3] / rotation [N,4] /
+    scaling [N,3].  Returns (xyz [N,3], rotation [N,4], scaling [N,3]): the values the reference assigns to gaussian._xyz /
+    gaussian._rotation / gaussian._scaling before render().  Only the third column of uvd is read; the first two columns of its
+    gradient are zeros (the reference's forward likewise: they only steer its CPU triangle walk)."""
+    _no_vertex_gradient(verts, "bind_gaussians_phong")
+    vn, vq, ratio = frame
+    return _BindPhong.apply(uvd, rotation, scaling, verts, faces, face_index, bary_coords, vn, vq, ratio)

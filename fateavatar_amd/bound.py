@@ -12,6 +12,10 @@ forward and to atomic-summation order in the backward.
 
 The same holds for GaussianAvatars' face-local binding (model/baseline/gaussianavatars.py:144-171,
 `binding.bind_gaussians_face_local`): hand `render_bound_batch` a `FaceLocalBinding` instead of a `MeshBinding`.
+
+And for SplattingAvatar's Phong-surface binding (model/baseline/splattingavatar.py:203-246, `binding.bind_gaussians_phong`):
+hand it a `PhongBinding`.  That mode's per-frame mesh pass (`binding.phong_frame`, one launch per view) runs in front of
+the launch chain; the per-Gaussian part is folded like the other two.
 """
 from __future__ import annotations
 
@@ -20,7 +24,8 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from .binding import _chk, _desc, _desc_local
+from .binding import (PhongCanonical, _chk, _chk_phong_frame, _desc, _desc_local, _desc_phong, _no_vertex_gradient,
+                      phong_frame)
 from .rasterizer import (_GRAD_NAMES, _any_grad, _backward_args, _forward_args, _forward_batch, _FrameGrads, _per_view_outputs,
                          _pick_forward_only, _SavedFrame, rasterize_gaussians_backward_batch)
 from .render import _result, _screenspace_points, _settings
@@ -44,19 +49,44 @@ class FaceLocalBinding(NamedTuple):
     face_index: torch.Tensor              # [N]   int32 (the reference's `binding`)
 
 
+class PhongBinding(NamedTuple):
+    """SplattingAvatar's binding (model/baseline/splattingavatar.py:128-145, :224-246): the mesh topology, every Gaussian's
+    face and barycentrics, and the once-per-mesh data of `binding.phong_canonical`.  The per-Gaussian `_uvd` is a parameter of
+    the holder, not part of this."""
+    faces: torch.Tensor                   # [F,3] int32
+    face_index: torch.Tensor              # [N]   int32 (the reference's `sample_fidxs`)
+    bary_coords: torch.Tensor             # [N,3]       (`sample_bary`)
+    canonical: PhongCanonical
+
+
+class _PhongView(NamedTuple):
+    """A PhongBinding of ONE view: with the outputs of that view's mesh pass in the canonical data's place."""
+    faces: torch.Tensor
+    face_index: torch.Tensor
+    bary_coords: torch.Tensor
+    frame: tuple                          # (vert_normals [V,3], vert_quats [V,4], face_ratio [F])
+
+
+def _has_own_xyz(mb) -> bool:
+    """The binding's own per-Gaussian parameter is an [N,3] array (its gradient goes to fr_aux::d_local_xyz), not the offset."""
+    return isinstance(mb, (FaceLocalBinding, _PhongView))
+
+
 def _descriptor(mb, verts, first, rotation, scaling):
-    """The fr_binding of one view; `first` is the binding's own per-Gaussian parameter: offset [N,1] (MeshBinding) or the
-    local position [N,3] (FaceLocalBinding)."""
+    """The fr_binding of one view; `first` is the binding's own per-Gaussian parameter: offset [N,1] (MeshBinding), the
+    local position [N,3] (FaceLocalBinding) or uvd [N,3] (PhongBinding)."""
     if isinstance(mb, FaceLocalBinding):
         return _desc_local(verts, mb.faces, mb.face_index, first, rotation, scaling)
+    if isinstance(mb, _PhongView):
+        return _desc_phong(verts, mb.faces, mb.face_index, mb.bary_coords, mb.frame, first, rotation, scaling)
     return _desc(verts, mb.faces, mb.face_index, mb.bary_coords, mb.face_scale_canonical, first, rotation, scaling, mb.shell_len,
                  mb.resize_scale)
 
 
 class _RasterizeBoundBatch(torch.autograd.Function):
     """Tensor arguments per view: (verts, offset, rotation, scaling, means2D, sh, opacities) — the RAW parameters, as
-    render() hands them over with `fused_activations`; with a FaceLocalBinding the local position [N,3] stands where the
-    offset stands.  Outputs per view: those of `_SavedFrame`."""
+    render() hands them over with `fused_activations`; with a FaceLocalBinding the local position [N,3] (with a PhongBinding:
+    uvd [N,3]) stands where the offset stands.  Outputs per view: those of `_SavedFrame`."""
     PER_VIEW = 7
 
     @staticmethod
@@ -76,6 +106,10 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             if isinstance(mb, FaceLocalBinding):
                 if verts.dim() != 2 or offset.shape != (N, 3) or rotation.shape != (N, 4) or scaling.shape != (N, 3):
                     raise RuntimeError("render_bound_batch: verts [V,3], _xyz [N,3], rotation [N,4], scaling [N,3]")
+            elif isinstance(mb, _PhongView):
+                if verts.dim() != 2 or offset.shape != (N, 3) or rotation.shape != (N, 4) or scaling.shape != (N, 3) or \
+                        mb.bary_coords.shape != (N, 3):
+                    raise RuntimeError("render_bound_batch: verts [V,3], _uvd [N,3], rotation [N,4], scaling [N,3], bary [N,3]")
             else:
                 if verts.dim() != 2 or offset.numel() != N or rotation.shape != (N, 4) or scaling.shape != (N, 3) or \
                         mb.bary_coords.shape != (N, 3):
@@ -126,7 +160,7 @@ class _RasterizeBoundBatch(torch.autograd.Function):
 
             descs.append(_descriptor(mb, verts, offset, rotation, scaling))
             # (the slot of the binding's own parameter is claimed as "d_offset" in both modes; the kernel's name differs)
-            first = {"d_local_xyz": buf(need_o, "d_offset", (N, 3))} if isinstance(mb, FaceLocalBinding) else \
+            first = {"d_local_xyz": buf(need_o, "d_offset", (N, 3))} if _has_own_xyz(mb) else \
                 {"d_offset": buf(need_o, "d_offset", (N,))}
             bgrads.append({"d_verts": torch.zeros_like(verts) if need_v else None, **first,
                            "d_rotation": buf(need_r, "d_rotation", (N, 4)), "d_scaling": buf(need_s, "d_scaling", (N, 3))})
@@ -156,7 +190,10 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding, bg_colors, 
     regulariser on the bound values themselves needs the differentiable stand-alone op (`binding.bind_gaussians`, what
     `AvatarStep(fold_binding=False)` renders through).  `depth_alpha=True` (extension): "depth" and "alpha" as in render().
 
-    `binding`: a `MeshBinding`, or a `FaceLocalBinding` (GaussianAvatars, model/baseline/gaussianavatars.py:144-171;
+    `binding`: a `MeshBinding`, a `PhongBinding` (SplattingAvatar, model/baseline/splattingavatar.py:203-246; stand-alone op
+    `binding.bind_gaussians_phong`; the holders carry `_uvd` [N,3] where FateAvatar's carry `_offset`, the posed vertices get no
+    gradient, and every view's mesh pass `binding.phong_frame` is launched here, in front of the frame's launch chain), or a
+    `FaceLocalBinding` (GaussianAvatars, model/baseline/gaussianavatars.py:144-171;
     stand-alone op `binding.bind_gaussians_face_local`).  The holders then carry the local position `_xyz` [N,3] where
     FateAvatar's carry `_offset`, and the frame is rendered with their `active_sh_degree` (the reference hands render() a
     GaussianModel(sh_degree=active_sh_degree), :157) from `get_features` [N,M,3], M >= (active_sh_degree + 1)^2."""
@@ -171,11 +208,27 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding, bg_colors, 
             if getattr(pc, "_xyz", None) is None:
                 raise RuntimeError("render_bound_batch: a face-local binding (FaceLocalBinding) needs a holder with the local "
                                    f"positions `_xyz` [N,3]; {type(pc).__name__} has none")
+    phong = isinstance(binding, PhongBinding)
+    if phong:
+        for pc in pcs:
+            if getattr(pc, "_uvd", None) is None:
+                raise RuntimeError("render_bound_batch: a Phong-surface binding (PhongBinding) needs a holder with the "
+                                   f"parameters `_uvd` [N,3]; {type(pc).__name__} has none")
     if isinstance(bg_colors, torch.Tensor):
         bg_colors = [bg_colors] * K
     if isinstance(posed_verts, torch.Tensor):
         posed_verts = [posed_verts] * K
-    if local:
+    if phong:
+        faces, fidx = _chk(binding.faces, torch.int32, "faces"), _chk(binding.face_index, torch.int32, "face_index")
+        bary = _chk(binding.bary_coords, torch.float32, "bary_coords")
+        V, frames, mbs = binding.canonical.cano_verts.shape[0], {}, []
+        for verts in posed_verts:
+            _no_vertex_gradient(verts, "render_bound_batch")
+            if id(verts) not in frames:   # (views of one pose share its mesh pass)
+                frames[id(verts)] = _chk_phong_frame(phong_frame(binding.canonical, verts), V, faces.shape[0], "render_bound_batch")
+            mbs.append(_PhongView(faces, fidx, bary, frames[id(verts)]))
+        posed_verts = [v.detach() for v in posed_verts]
+    elif local:
         mb = FaceLocalBinding(_chk(binding.faces, torch.int32, "faces"), _chk(binding.face_index, torch.int32, "face_index"))
     else:
         mb = MeshBinding(_chk(binding.faces, torch.int32, "faces"), _chk(binding.face_index, torch.int32, "face_index"),
@@ -189,9 +242,9 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding, bg_colors, 
         if local:
             rs = rs._replace(sh_degree=int(getattr(pc, "active_sh_degree", pc.max_sh_degree)))
         settings.append(rs)
-        tensors += [verts, pc._xyz if local else pc._offset, pc._rotation, pc._scaling, sp, pc.get_features, pc._opacity]
+        tensors += [verts, pc._uvd if phong else pc._xyz if local else pc._offset, pc._rotation, pc._scaling, sp, pc.get_features, pc._opacity]
         points.append(sp)
-    res = _RasterizeBoundBatch.apply(settings, [mb] * K, list(range(K)) if slots is None else list(slots),
+    res = _RasterizeBoundBatch.apply(settings, mbs if phong else [mb] * K, list(range(K)) if slots is None else list(slots),
                                      _pick_forward_only(tensors), bool(depth_alpha), *tensors)
     out = []
     for r, sp in zip(_per_view_outputs(res, K), points):

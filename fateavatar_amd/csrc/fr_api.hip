@@ -26,13 +26,18 @@ int fail_msg(int code, const char* msg)
 static int check_binding(const fr_binding* b)
 {
     if (!b || b->N < 0 || b->V < 0 || b->F < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: null or negative sizes");
-    if (b->mode != FR_BIND_SHELL && b->mode != FR_BIND_FACE_LOCAL)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: unknown mode (FR_BIND_SHELL or FR_BIND_FACE_LOCAL)");
+    if (b->mode != FR_BIND_SHELL && b->mode != FR_BIND_FACE_LOCAL && b->mode != FR_BIND_PHONG)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: unknown mode (FR_BIND_SHELL, FR_BIND_FACE_LOCAL or FR_BIND_PHONG)");
     if (b->N == 0) return FR_OK;
     if (!b->verts || !b->faces || !b->face_index || !b->rotation || !b->scaling)
         return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: missing array");
     if (b->mode == FR_BIND_FACE_LOCAL) {
         if (!b->local_xyz) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: FR_BIND_FACE_LOCAL needs local_xyz");
+    } else if (b->mode == FR_BIND_PHONG) {
+        const fr_binding_phong* p = reinterpret_cast<const fr_binding_phong*>(b);   // (this mode's descriptor: its `base` is *b)
+        if (!b->bary || !p->vert_normals || !p->vert_quats || !p->face_ratio || !b->local_xyz)
+            return fail_msg(FR_ERR_INVALID_ARGUMENT,
+                            "fr_binding: FR_BIND_PHONG needs bary, vert_normals, vert_quats, face_ratio and uvd (in local_xyz)");
     } else if (!b->bary || !b->offset || (b->resize_scale && !b->face_scale_canonical))
         return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: missing array");
     return FR_OK;
@@ -66,6 +71,8 @@ static int check_frame(const fr_params* prm, const fr_inputs* in, bool forward)
         if (b.N != prm->P) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_aux::binding: N must equal P");
         const int rc = check_binding(&b);
         if (rc) return rc;
+        if (!forward && b.mode == FR_BIND_PHONG && prm->aux->d_verts)
+            return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_aux::d_verts: a FR_BIND_PHONG binding has no vertex gradient");
     }
     return FR_OK;
 }
@@ -427,7 +434,8 @@ int fr_bind_backward(const fr_binding* b, const float* g_xyz, const float* g_rot
     int rc = check_binding(b);
     if (rc) return rc;
     if (b->mode != FR_BIND_SHELL)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_bind_backward: a FR_BIND_FACE_LOCAL binding goes through fr_bind_backward_local");
+        return fail_msg(FR_ERR_INVALID_ARGUMENT,
+                        "fr_bind_backward: the binding is not FR_BIND_SHELL (fr_bind_backward_local / fr_bind_backward_phong)");
     return launch_bind_backward(*b, g_xyz, g_rotation, g_scaling, d_verts, d_offset, d_rotation, d_scaling, nullptr,
                                 static_cast<hipStream_t>(stream));
 }
@@ -440,6 +448,30 @@ int fr_bind_backward_local(const fr_binding* b, const float* g_xyz, const float*
     if (b->mode != FR_BIND_FACE_LOCAL) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_bind_backward_local: the binding is not FR_BIND_FACE_LOCAL");
     return launch_bind_backward(*b, g_xyz, g_rotation, g_scaling, d_verts, nullptr, d_rotation, d_scaling, d_local_xyz,
                                 static_cast<hipStream_t>(stream));
+}
+
+int fr_bind_backward_phong(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
+                           float* d_verts, float* d_uvd, float* d_rotation, float* d_scaling, void* stream)
+{
+    int rc = check_binding(b);
+    if (rc) return rc;
+    if (b->mode != FR_BIND_PHONG) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_bind_backward_phong: the binding is not FR_BIND_PHONG");
+    if (d_verts) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_bind_backward_phong: a FR_BIND_PHONG binding has no vertex gradient");
+    return launch_bind_backward(*b, g_xyz, g_rotation, g_scaling, nullptr, nullptr, d_rotation, d_scaling, d_uvd,
+                                static_cast<hipStream_t>(stream));
+}
+
+int fr_phong_frame(int32_t V, int32_t F, const float* verts, const float* cano_verts, const int32_t* faces,
+                   const int32_t* vf_offsets, const int32_t* vf_faces, const float* face_area_canonical, float* vert_normals,
+                   float* vert_quats, float* face_ratio, void* stream)
+{
+    if (V < 0 || F < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_frame: negative sizes");
+    if ((V > 0 || F > 0) && (!verts || !cano_verts || !faces || !vf_offsets || !vf_faces || !face_area_canonical))
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_frame: null input");
+    if ((V > 0 && (!vert_normals || !vert_quats)) || (F > 0 && !face_ratio))
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_frame: null output");
+    return launch_phong_frame(V, F, verts, cano_verts, faces, vf_offsets, vf_faces, face_area_canonical, vert_normals, vert_quats,
+                              face_ratio, static_cast<hipStream_t>(stream));
 }
 
 int fr_adam_step(const fr_adam_config* cfg, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

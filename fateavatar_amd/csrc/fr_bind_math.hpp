@@ -7,10 +7,13 @@
 // matrix_to_quaternion / quaternion_multiply / standardize_quaternion.  Every translation unit that includes this is
 // built with -ffp-contract=off: the expressions are in the oracle's operation order.
 //
-// Two bindings share the face frame and the quaternion code (BindArgs::mode, the same for every Gaussian of a launch):
+// Three bindings share the quaternion code (BindArgs::mode, the same for every Gaussian of a launch):
 //   FR_BIND_SHELL       FateAvatar's own: barycentric point + shell offset along the face normal (bind_one_fwd / _bwd)
 //   FR_BIND_FACE_LOCAL  GaussianAvatars': a free position in the face's local frame (bind_local_fwd / _bwd;
 //                       model/baseline/gaussianavatars.py:144-171)
+//   FR_BIND_PHONG       SplattingAvatar's: a point of the posed mesh's Phong surface (bind_phong_fwd / _bwd;
+//                       model/baseline/splattingavatar.py:224-246) from the per-vertex normals / quaternions and per-face
+//                       area ratios that phong_vertex / phong_face_ratio (below; fr_phong_frame) compute once per frame
 // bind_fwd / bind_bwd pick by the mode; the kernels call those (and bind_bwd_zero for a Gaussian without a gradient).
 #pragma once
 #include "fr_common.hpp"
@@ -29,8 +32,12 @@ struct BindArgs {
     const float* offset;      // [N]
     const float* rotation;    // [N,4]
     const float* scaling;     // [N,3]
-    int mode;                 // FR_BIND_SHELL / FR_BIND_FACE_LOCAL (wave-uniform: a kernel argument)
-    const float* local_xyz;   // [N,3] FR_BIND_FACE_LOCAL: position in the face's frame (bary .. offset are not read)
+    int mode;                 // FR_BIND_SHELL / FR_BIND_FACE_LOCAL / FR_BIND_PHONG (wave-uniform: a kernel argument)
+    const float* local_xyz;   // [N,3] FR_BIND_FACE_LOCAL: position in the face's frame (bary .. offset are not read);
+                              //       FR_BIND_PHONG: uvd (only column 2, the offset along the normal, is read)
+    const float* vert_normals;  // [V,3] FR_BIND_PHONG (fr_binding_phong's tail): fr_phong_frame's outputs for the posed mesh
+    const float* vert_quats;    // [V,4]
+    const float* face_ratio;    // [F]
 };
 
 struct Vec3 {
@@ -89,11 +96,11 @@ struct QuatSel {
     int sel;
     float sgn;
 };
-__device__ __forceinline__ QuatSel frame_to_quaternion(const FaceFrame& f)
+__device__ __forceinline__ QuatSel frame_to_quaternion(Vec3 a0, Vec3 a1, Vec3 a2)
 {
-    const float m00 = f.a0.x, m10 = f.a0.y, m20 = f.a0.z;
-    const float m01 = f.a1.x, m11 = f.a1.y, m21 = f.a1.z;
-    const float m02 = f.a2.x, m12 = f.a2.y, m22 = f.a2.z;
+    const float m00 = a0.x, m10 = a0.y, m20 = a0.z;
+    const float m01 = a1.x, m11 = a1.y, m21 = a1.z;
+    const float m02 = a2.x, m12 = a2.y, m22 = a2.z;
     const float x[4] = {1.0f + m00 + m11 + m22, 1.0f + m00 - m11 - m22, 1.0f - m00 + m11 - m22, 1.0f - m00 - m11 + m22};
     float qa[4];
     int sel = 0;
@@ -116,6 +123,7 @@ __device__ __forceinline__ QuatSel frame_to_quaternion(const FaceFrame& f)
     for (int k = 0; k < 4; k++) s.q[k] *= s.sgn;
     return s;
 }
+__device__ __forceinline__ QuatSel frame_to_quaternion(const FaceFrame& f) { return frame_to_quaternion(f.a0, f.a1, f.a2); }
 
 // pytorch3d quaternion_multiply: Hamilton product a (x) b with the real part made non-negative
 __device__ __forceinline__ void quat_multiply(const float a[4], const float b[4], float out[4])
@@ -414,16 +422,162 @@ __device__ __forceinline__ void bind_local_bwd(const BindArgs& a, int n, const f
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// FR_BIND_PHONG — SplattingAvatar's binding (model/baseline/splattingavatar.py:203-246).  Two parts:
+//
+// (1) the per-frame mesh pass (fr_phong_frame): per face the area ratio of :899-902, per vertex the normal of pytorch3d's
+//     verts_normals_packed (:206) and the area-weighted mean of its faces' quaternions (PerVertQuaternion, :846-881).  The
+//     reference sums both with index_add (float atomics); here every vertex GATHERS its faces in the order of a CSR
+//     incidence list and recomputes each face's contribution (~250 flops) — no scratch, no atomics, the same bits every run.
+// (2) the per-Gaussian binding from those arrays (bind_phong_fwd / _bwd).  Nothing of it reaches the posed vertices
+//     (DESIGN.md).
+constexpr float kPhongDamping = 1e-4f;   // calc_face_area_change (:899)
+constexpr float kVertEps = 1e-6f;        // F.normalize(eps=1e-6) of the per-vertex sums (:879, verts_normals_packed)
+
+// F.normalize: x / max(|x|, eps)
+__device__ __forceinline__ Vec3 f_normalize(Vec3 x, float eps)
+{
+    const float n = fmaxf(sqrtf(dot3(x, x)), eps);
+    return {x.x / n, x.y / n, x.z / n};
+}
+
+// cross(v2 - v1, v0 - v1): calc_face_areas' (:781-791) and verts_normals_packed's face vector; |.| / 2 is the area
+__device__ __forceinline__ Vec3 phong_face_cross(Vec3 v0, Vec3 v1, Vec3 v2) { return cross3(sub(v2, v1), sub(v0, v1)); }
+
+__device__ __forceinline__ float phong_face_ratio(Vec3 p0, Vec3 p1, Vec3 p2, float area_cano)
+{
+    const Vec3 c = phong_face_cross(p0, p1, p2);
+    return (sqrtf(dot3(c, c)) / 2.0f + kPhongDamping) / (area_cano + kPhongDamping);
+}
+
+// tbn (:756-765): the columns X, Y, Z of a triangle's frame
+__device__ __forceinline__ void phong_tbn(Vec3 a, Vec3 b, Vec3 c, Vec3& X, Vec3& Y, Vec3& Z)
+{
+    const Vec3 d = sub(b, a);
+    const Vec3 n = f_normalize(cross3(d, sub(c, a)), kNormEps);
+    X = f_normalize(cross3(d, n), kNormEps);
+    Y = f_normalize(cross3(d, X), kNormEps);
+    Z = f_normalize(d, kNormEps);
+}
+
+// matrix_to_quaternion(R_posed R_cano^T) of one face (:795-802, :891-894; the rotation block of deform_Rt cano_Rt^-1: tbn
+// is orthonormal, so the inverse is the transpose)
+__device__ __forceinline__ void phong_face_quat(Vec3 p0, Vec3 p1, Vec3 p2, Vec3 c0, Vec3 c1, Vec3 c2, float q[4])
+{
+    Vec3 Xp, Yp, Zp, Xc, Yc, Zc;
+    phong_tbn(p0, p1, p2, Xp, Yp, Zp);
+    phong_tbn(c0, c1, c2, Xc, Yc, Zc);
+    // column j of M = R_p R_c^T:  X_p X_c[j] + Y_p Y_c[j] + Z_p Z_c[j]
+    const Vec3 m0 = add(add(mul(Xp, Xc.x), mul(Yp, Yc.x)), mul(Zp, Zc.x));
+    const Vec3 m1 = add(add(mul(Xp, Xc.y), mul(Yp, Yc.y)), mul(Zp, Zc.y));
+    const Vec3 m2 = add(add(mul(Xp, Xc.z), mul(Yp, Yc.z)), mul(Zp, Zc.z));
+    const QuatSel qs = frame_to_quaternion(m0, m1, m2);
+    for (int k = 0; k < 4; k++) q[k] = qs.q[k];
+}
+
+struct PhongFrameArgs {
+    int V, F;
+    const float* verts;       // [V,3] posed
+    const float* cano_verts;  // [V,3]
+    const int* faces;         // [F,3]
+    const int* vf_offsets;    // [V+1] CSR rows: the faces of every vertex ...
+    const int* vf_faces;      // [3F]  ... ascending within a row
+    const float* area_cano;   // [F]
+    float* vert_normals;      // [V,3] out
+    float* vert_quats;        // [V,4] out
+    float* face_ratio;        // [F]   out
+};
+
+__device__ __forceinline__ void phong_vertex(const PhongFrameArgs& a, int v)
+{
+    Vec3 ns = {0.f, 0.f, 0.f};
+    float qs[4] = {0.f, 0.f, 0.f, 0.f};
+    const int end = a.vf_offsets[v + 1];
+    for (int e = a.vf_offsets[v]; e < end; e++) {
+        const int fi = a.vf_faces[e];
+        const int i0 = a.faces[3 * fi], i1 = a.faces[3 * fi + 1], i2 = a.faces[3 * fi + 2];
+        const Vec3 p0 = load3(a.verts, i0), p1 = load3(a.verts, i1), p2 = load3(a.verts, i2);
+        ns = add(ns, phong_face_cross(p0, p1, p2));
+        float q[4];
+        phong_face_quat(p0, p1, p2, load3(a.cano_verts, i0), load3(a.cano_verts, i1), load3(a.cano_verts, i2), q);
+        const float w = a.area_cano[fi];
+        for (int k = 0; k < 4; k++) qs[k] = qs[k] + w * q[k];
+    }
+    const Vec3 n = f_normalize(ns, kVertEps);
+    a.vert_normals[3 * v] = n.x, a.vert_normals[3 * v + 1] = n.y, a.vert_normals[3 * v + 2] = n.z;
+    const float len = fmaxf(sqrtf(qs[0] * qs[0] + qs[1] * qs[1] + qs[2] * qs[2] + qs[3] * qs[3]), kVertEps);
+    for (int k = 0; k < 4; k++) a.vert_quats[4 * v + k] = qs[k] / len;
+}
+
+// xyz = sum_k b_k v_k + normalize(sum_k b_k n_k) * uvd.z;  rotation = standardize((sum_k b_k q_k) (x) rotation) — the sum is
+// NOT normalised (:235, :245);  scaling = scaling * face_ratio — the raw log-scale is MULTIPLIED (:244, kept as it is)
+__device__ __forceinline__ Vec3 phong_unit_normal(const BindArgs& a, int i0, int i1, int i2, float b0, float b1, float b2)
+{
+    const Vec3 n0 = load3(a.vert_normals, i0), n1 = load3(a.vert_normals, i1), n2 = load3(a.vert_normals, i2);
+    const Vec3 nb = {b0 * n0.x + b1 * n1.x + b2 * n2.x, b0 * n0.y + b1 * n1.y + b2 * n2.y, b0 * n0.z + b1 * n1.z + b2 * n2.z};
+    return f_normalize(nb, kNormEps);
+}
+__device__ __forceinline__ void phong_base_quat(const BindArgs& a, int i0, int i1, int i2, float b0, float b1, float b2, float q[4])
+{
+    for (int k = 0; k < 4; k++) q[k] = b0 * a.vert_quats[4 * i0 + k] + b1 * a.vert_quats[4 * i1 + k] + b2 * a.vert_quats[4 * i2 + k];
+}
+
+__device__ __forceinline__ void bind_phong_fwd(const BindArgs& a, int n, float xyz[3], float rot[4], float scl[3])
+{
+    const int fi = a.face_index[n];
+    const int i0 = a.faces[3 * fi], i1 = a.faces[3 * fi + 1], i2 = a.faces[3 * fi + 2];
+    const Vec3 v0 = load3(a.verts, i0), v1 = load3(a.verts, i1), v2 = load3(a.verts, i2);
+    const float b0 = a.bary[3 * n], b1 = a.bary[3 * n + 1], b2 = a.bary[3 * n + 2];
+    const Vec3 nh = phong_unit_normal(a, i0, i1, i2, b0, b1, b2);
+    const float d = a.local_xyz[3 * n + 2];
+    xyz[0] = (b0 * v0.x + b1 * v1.x + b2 * v2.x) + nh.x * d;
+    xyz[1] = (b0 * v0.y + b1 * v1.y + b2 * v2.y) + nh.y * d;
+    xyz[2] = (b0 * v0.z + b1 * v1.z + b2 * v2.z) + nh.z * d;
+    float qb[4];
+    phong_base_quat(a, i0, i1, i2, b0, b1, b2, qb);
+    const float r[4] = {a.rotation[4 * n], a.rotation[4 * n + 1], a.rotation[4 * n + 2], a.rotation[4 * n + 3]};
+    quat_multiply(qb, r, rot);
+    const float ratio = a.face_ratio[fi];
+    for (int k = 0; k < 3; k++) scl[k] = a.scaling[3 * n + k] * ratio;
+}
+
+// gradients of uvd (through its third column only) / rotation / scaling written; the posed mesh gets none
+__device__ __forceinline__ void bind_phong_bwd(const BindArgs& a, int n, const float g_xyz[3], const float g_rot[4],
+                                               const float g_scl[3], const BindGrads& o)
+{
+    const int fi = a.face_index[n];
+    const int i0 = a.faces[3 * fi], i1 = a.faces[3 * fi + 1], i2 = a.faces[3 * fi + 2];
+    const float b0 = a.bary[3 * n], b1 = a.bary[3 * n + 1], b2 = a.bary[3 * n + 2];
+    if (o.d_scaling) {
+        const float ratio = a.face_ratio[fi];
+        for (int k = 0; k < 3; k++) o.d_scaling[3 * n + k] = g_scl[k] * ratio;
+    }
+    if (o.d_local_xyz) {
+        const Vec3 nh = phong_unit_normal(a, i0, i1, i2, b0, b1, b2);
+        o.d_local_xyz[3 * n] = 0.f, o.d_local_xyz[3 * n + 1] = 0.f;
+        o.d_local_xyz[3 * n + 2] = dot3(Vec3{g_xyz[0], g_xyz[1], g_xyz[2]}, nh);
+    }
+    if (o.d_rotation) {
+        float qb[4], dq[4], dr[4];
+        phong_base_quat(a, i0, i1, i2, b0, b1, b2, qb);
+        const float r[4] = {a.rotation[4 * n], a.rotation[4 * n + 1], a.rotation[4 * n + 2], a.rotation[4 * n + 3]};
+        quat_multiply_bwd(qb, r, g_rot, dq, dr);
+        for (int k = 0; k < 4; k++) o.d_rotation[4 * n + k] = dr[k];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // what the kernels call: the binding of BindArgs::mode (one value per launch, so the branch is wave-uniform)
 __device__ __forceinline__ void bind_fwd(const BindArgs& a, int n, float xyz[3], float rot[4], float scl[3])
 {
     if (a.mode == FR_BIND_FACE_LOCAL) bind_local_fwd(a, n, xyz, rot, scl);
+    else if (a.mode == FR_BIND_PHONG) bind_phong_fwd(a, n, xyz, rot, scl);
     else bind_one_fwd(a, n, xyz, rot, scl);
 }
 __device__ __forceinline__ void bind_bwd(const BindArgs& a, int n, const float g_xyz[3], const float g_rot[4], const float g_scl[3],
                                          const BindGrads& o)
 {
     if (a.mode == FR_BIND_FACE_LOCAL) bind_local_bwd(a, n, g_xyz, g_rot, g_scl, o);
+    else if (a.mode == FR_BIND_PHONG) bind_phong_bwd(a, n, g_xyz, g_rot, g_scl, o);
     else bind_one_bwd(a, n, g_xyz, g_rot, g_scl, o);
 }
 

@@ -9,7 +9,9 @@
 // and product.  The reference evaluates this as ~40 PyTorch kernels over [F] and [N] temporaries (plus their autograd
 // twins); here ONE kernel per direction, one thread per Gaussian, recomputing the ~150 flops of its face's frame
 // instead of gathering per-face temporaries.  The same two kernels serve GaussianAvatars' face-local binding
-// (fr_binding::mode == FR_BIND_FACE_LOCAL, model/baseline/gaussianavatars.py:144-171): the mode is a kernel argument.  The backward scatters dL/dverts with float atomics (a vertex is shared
+// (fr_binding::mode == FR_BIND_FACE_LOCAL, model/baseline/gaussianavatars.py:144-171) and SplattingAvatar's Phong-surface
+// binding (FR_BIND_PHONG, model/baseline/splattingavatar.py:224-246; its per-frame mesh pass is k_phong_frame): the mode is a
+// kernel argument.  The backward scatters dL/dverts with float atomics (a vertex is shared
 // by the Gaussians of ~6 faces x ~10 Gaussians each).  Built without FMA contraction, in the oracle's operation order.
 #include "fr_bind_math.hpp"
 
@@ -50,6 +52,18 @@ __global__ void __launch_bounds__(256) k_face_scale(int F, const float* verts, c
     out[fi] = f.scale;
 }
 
+// SplattingAvatar's per-frame mesh pass (model/baseline/splattingavatar.py:203-215, PerVertQuaternion :819-902) in ONE launch:
+// thread i writes face i's area ratio (i < F) and gathers vertex i's normal and quaternion over its faces (i < V)
+__global__ void __launch_bounds__(256) k_phong_frame(PhongFrameArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.F) {
+        const int i0 = a.faces[3 * i], i1 = a.faces[3 * i + 1], i2 = a.faces[3 * i + 2];
+        a.face_ratio[i] = phong_face_ratio(load3(a.verts, i0), load3(a.verts, i1), load3(a.verts, i2), a.area_cano[i]);
+    }
+    if (i < a.V) phong_vertex(a, i);
+}
+
 BindArgs bind_args(const fr_binding& b)
 {
     BindArgs a;
@@ -57,6 +71,11 @@ BindArgs bind_args(const fr_binding& b)
     a.canon = b.face_scale_canonical, a.shell_len = b.shell_len, a.resize_scale = b.resize_scale;
     a.offset = b.offset, a.rotation = b.rotation, a.scaling = b.scaling;
     a.mode = b.mode, a.local_xyz = b.local_xyz;
+    a.vert_normals = a.vert_quats = a.face_ratio = nullptr;
+    if (b.mode == FR_BIND_PHONG) {   // (the descriptor is the `base` of a fr_binding_phong: include/fr_rasterizer.h)
+        const fr_binding_phong& p = reinterpret_cast<const fr_binding_phong&>(b);
+        a.vert_normals = p.vert_normals, a.vert_quats = p.vert_quats, a.face_ratio = p.face_ratio;
+    }
     return a;
 }
 
@@ -74,6 +93,18 @@ int launch_bind_backward(const fr_binding& b, const float* g_xyz, const float* g
     if (b.N <= 0) return FR_OK;
     hipLaunchKernelGGL(k_bind_bwd, dim3((b.N + 255) / 256), dim3(256), 0, s, bind_args(b), g_xyz, g_rot, g_scale,
                        BindGrads{d_verts, d_offset, d_rotation, d_scaling, d_local_xyz});
+    FR_HIP(hipGetLastError());
+    return FR_OK;
+}
+
+int launch_phong_frame(int V, int F, const float* verts, const float* cano_verts, const int* faces, const int* vf_offsets,
+                       const int* vf_faces, const float* area_cano, float* vert_normals, float* vert_quats, float* face_ratio,
+                       hipStream_t s)
+{
+    const int n = V > F ? V : F;
+    if (n <= 0) return FR_OK;
+    const PhongFrameArgs a = {V, F, verts, cano_verts, faces, vf_offsets, vf_faces, area_cano, vert_normals, vert_quats, face_ratio};
+    hipLaunchKernelGGL(k_phong_frame, dim3((n + 255) / 256), dim3(256), 0, s, a);
     FR_HIP(hipGetLastError());
     return FR_OK;
 }

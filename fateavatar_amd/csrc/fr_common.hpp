@@ -457,6 +457,9 @@ int launch_bind_forward(const fr_binding& b, float* xyz, float* rot, float* scal
 int launch_bind_backward(const fr_binding& b, const float* g_xyz, const float* g_rot, const float* g_scale, float* d_verts,
                          float* d_offset, float* d_rotation, float* d_scaling, float* d_local_xyz, hipStream_t s);
 int launch_face_scale(int F, const float* verts, const int* faces, float* out, hipStream_t s);
+int launch_phong_frame(int V, int F, const float* verts, const float* cano_verts, const int* faces, const int* vf_offsets,
+                       const int* vf_faces, const float* area_cano, float* vert_normals, float* vert_quats, float* face_ratio,
+                       hipStream_t s);
 int launch_adam(const fr_adam_config& cfg, float* param, const float* const* grad_bufs, int n_grads, float* exp_avg,
                 float* exp_avg_sq, unsigned long long n, float* state, hipStream_t s);
 int launch_l1_loss_grad_batch(int n_images, unsigned long long n, const float* const* img, const float* const* gt, float* const* grad,

@@ -1,0 +1,289 @@
+"""SplattingAvatar — the reference's Phong-surface baseline — on the fused path: Gaussians embedded in the posed mesh by
+(face, barycentrics, offset along the interpolated normal), SH degree 0, one optimisation step per call.
+
+reference:
+  * parameters — `_register_init_gaussian` (model/baseline/splattingavatar.py:147-183): `num_init_samples` (10 000,
+    config/splattingavatar.yaml:23) points sampled on the canonical mesh by `sample_bary_on_triangles` (:725-736), `_uvd` 0,
+    colour RGB2SH(0.5), log sqrt of the mean squared distance to the 3 nearest samples (distCUDA2, clamped at 1e-7), identity
+    rotation, opacity 0.1, `max_sh_degree` 0 (:217: `_features_rest` is [N,0,3])
+  * their Adam groups — `_uvd, _opacity, _features_dc, _features_rest, _rotation, _scaling` in that order (train/optim.py:106-117)
+    with the rates of config/splattingavatar.yaml:26-30, `_features_rest` at feature_dc_lr / 20
+  * a frame — `forward` :203-246: the per-frame mesh pass (vertex normals, per-vertex quaternions, face area ratios:
+    `binding.phong_frame`), every Gaussian placed on the Phong surface (`binding.bind_gaussians_phong`), then render()
+What is fused: the mesh pass is one launch, the per-Gaussian binding runs inside the rasterizer's per-Gaussian kernels
+(bound.render_bound_batch with a PhongBinding; `fold_binding=False` keeps the stand-alone op as the A/B), activations and
+densification statistics run inside the rasterizer kernels, one L1 launch, one Adam launch over the flat buffer, the whole
+step — mesh pass included — ONE HIP graph.
+
+NOT here:
+  * triangle walking and `update_corres_spt` (CPU C++ in submodules/simple_phongsurf, every `triangle_walk_interval` steps):
+    without it a Gaussian stays on its face and the `u, v` columns of `_uvd` only ever receive zero gradient — exactly as in
+    the reference's forward, which reads `_uvd[..., -1:]` alone
+  * SplattingAvatar's density control (:262-716) and opacity reset
+  * its MSE / scale / LPIPS loss terms (config/splattingavatar.yaml:13-20): the image term is L1 (`rgb_loss` 1.0)
+  * gradients to the posed vertices (the reference's tracking / deformer rates): the mesh pass is not differentiable
+  * data-parallel runs of the step
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .binding import PhongCanonical, bind_gaussians_phong, phong_canonical, phong_frame
+from .bound import PhongBinding, render_bound_batch
+from .gs_utils import RGB2SH
+from .loss import l1_workspace
+from .model import TorchCamera
+from .optim import FusedAdam
+from .rasterizer import GradOut
+from .render import render
+from .train import TrainStep
+
+# config/splattingavatar.yaml:26-30 (group names of train/optim.py:106-117)
+SPLATTING_LRS = dict(uvd=0.00016, opacity=0.05, feature_dc=0.0025, feature_rest=0.0025 / 20, rotation=0.001, scaling=0.005)
+NUM_INIT_SAMPLES = 10_000   # config/splattingavatar.yaml:23
+
+
+def sample_bary_on_triangles(num_faces: int, num_samples: int, generator: Optional[torch.Generator] = None):
+    """sample_bary_on_triangles (model/baseline/splattingavatar.py:725-736) with a seeded generator: (face of every sample
+    [n] int64, barycentrics [n,3] — u uniform, v uniform in the rest, w the remainder, then shuffled per row).  Faces are drawn
+    uniformly, not by area, as in the reference."""
+    bary = torch.zeros(num_samples, 3)
+    bary[:, 0] = torch.rand(num_samples, generator=generator)
+    bary[:, 1] = torch.rand(num_samples, generator=generator) * (1.0 - bary[:, 0])
+    bary[:, 2] = 1.0 - bary[:, 0] - bary[:, 1]
+    fidxs = torch.randint(0, num_faces, size=(num_samples,), generator=generator)
+    indices = torch.argsort(torch.rand(num_samples, 3, generator=generator), dim=-1)
+    return fidxs, torch.gather(bary, dim=-1, index=indices)
+
+
+class SplattingGaussians(torch.nn.Module):
+    """SplattingAvatar's Gaussian parameters in ONE flat buffer, in the order of the optimizer groups (train/optim.py:106-117).
+    `face_index` [P] / `bary_coords` [P,3] are every Gaussian's embedding (`sample_fidxs`, `sample_bary`); they stay fixed
+    (no triangle walk, see the module docstring)."""
+    max_sh_degree = 0        # :217
+    FIELDS = (("_uvd", 3), ("_opacity", 1), ("_features_dc", 3), ("_features_rest", 0), ("_rotation", 4), ("_scaling", 3))
+    SHAPES = {"_uvd": (3,), "_opacity": (1,), "_features_dc": (1, 3), "_features_rest": (0, 3), "_rotation": (4,),
+              "_scaling": (3,)}
+    fused_activations = True
+
+    def __init__(self, face_index, bary_coords, log_scale, device):
+        """_register_init_gaussian (:147-183) for Gaussians embedded at (`face_index` [P], `bary_coords` [P,3]); `log_scale`:
+        the initial `_scaling` value(s), a float or [P] (`log(sqrt(distCUDA2))` of the sampled points: `SplattingGaussians.sample`)."""
+        super().__init__()
+        self.face_index = torch.as_tensor(face_index).to(device, torch.int32).contiguous()
+        self.bary_coords = torch.as_tensor(bary_coords).to(device, torch.float32).contiguous()
+        P = int(self.face_index.shape[0])
+        if self.bary_coords.shape != (P, 3):
+            raise ValueError("SplattingGaussians: face_index [P], bary_coords [P,3]")
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)  # noqa: E731
+        dc = torch.full((P, 1, 3), float(RGB2SH(0.5)), dtype=torch.float32, device=device)          # :151-158
+        rot = z(P, 4)
+        rot[:, 0] = 1
+        op = torch.full((P, 1), float(np.log(0.1 / 0.9)), dtype=torch.float32, device=device)       # inverse_sigmoid(0.1)
+        scl = torch.as_tensor(log_scale, dtype=torch.float32).to(device).reshape(-1, 1).expand(P, 3)   # :164
+        self.active_sh_degree = 0
+        self._bind([z(P, 3), op, dc, z(P, 0, 3), rot, scl.contiguous()])
+
+    @classmethod
+    def sample(cls, cano_verts: torch.Tensor, faces: torch.Tensor, num_samples: int = NUM_INIT_SAMPLES,
+               generator: Optional[torch.Generator] = None) -> "SplattingGaussians":
+        """`_sample_initial_points` + `_register_init_gaussian` (:128-183) on the canonical mesh (device tensors): the samples
+        of `sample_bary_on_triangles`, scales from this project's `distCUDA2` of the sampled points."""
+        from .knn import distCUDA2
+        dev = cano_verts.device
+        fidxs, bary = sample_bary_on_triangles(int(faces.shape[0]), int(num_samples), generator)
+        tri = cano_verts.detach().float()[faces.long()][fidxs.to(dev)]
+        points = torch.einsum("nij,ni->nj", tri, bary.to(dev)).contiguous()                         # :136
+        dist2 = torch.clamp_min(distCUDA2(points), 0.0000001)                                       # :163
+        return cls(fidxs, bary, torch.log(torch.sqrt(dist2)), dev)
+
+    @property
+    def P(self) -> int:
+        return int(self.face_index.shape[0])
+
+    def widths(self):
+        return [w for _, w in self.FIELDS]
+
+    def _bind(self, raw):
+        P, dev = raw[0].shape[0], raw[0].device
+        sizes = [P * w for _, w in self.FIELDS]
+        self.flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        # (gradient buffer + the step's overflow word behind it: model.FlatGaussians._bind)
+        self._grad_store = torch.zeros(sum(sizes) + 4, dtype=torch.float32, device=dev)
+        self.flat_grad = self._grad_store[:sum(sizes)]
+        self.overflow_word = self._grad_store[sum(sizes):sum(sizes) + 1]
+        off = 0
+        for (name, w), n, r in zip(self.FIELDS, sizes, raw):
+            shp = (P,) + self.SHAPES[name]
+            self.flat[off:off + n].copy_(r.detach().reshape(-1))
+            p = torch.nn.Parameter(self.flat[off:off + n].view(shp))
+            p._fr_grad_out = GradOut(self.flat_grad[off:off + n].view(shp))   # (see AvatarGaussians._bind)
+            setattr(self, name, p)
+            off += n
+
+    @property
+    def get_features(self) -> torch.Tensor:
+        """[P,1,3]: GaussianModel.get_features (volume_rendering/gaussian_model.py:119-122) at SH degree 0."""
+        return torch.cat((self._features_dc, self._features_rest), dim=1)
+
+    def begin_step(self):
+        for name, _ in self.FIELDS:
+            getattr(self, name).grad = None
+
+    def collect_grads(self) -> torch.Tensor:
+        """Every parameter's gradient in the flat gradient buffer (most are written there by the kernels already; the SH
+        block comes back from autograd's split of the concatenation)."""
+        off = 0
+        for name, w in self.FIELDS:
+            n = self.P * w
+            g, view = getattr(self, name).grad, self.flat_grad[off:off + n]
+            if n == 0:
+                continue
+            if g is None:
+                view.zero_()
+            elif g.data_ptr() != view.data_ptr() or not g.is_contiguous():
+                view.view(g.shape).copy_(g)
+            off += n
+        return self.flat_grad
+
+
+class _SplattingFrame:
+    """What render() / render_bound_batch() read of a Gaussian holder for one frame."""
+    fused_activations = True
+    max_sh_degree = active_sh_degree = 0
+
+    def __init__(self, pc: SplattingGaussians, stats, bound=None):
+        self._opacity, self.get_features = pc._opacity, pc.get_features
+        if bound is None:     # raw parameters: the rasterizer evaluates the binding itself
+            self._uvd, self._rotation, self._scaling = pc._uvd, pc._rotation, pc._scaling
+        else:                 # the stand-alone op's outputs
+            self.get_xyz, self._rotation, self._scaling = bound
+        self.fused_densification_stats = stats
+
+
+class SplattingStep(TrainStep):
+    """One optimisation step of SplattingAvatar per call: `step(camera, posed_verts, gt_image)` —
+    mesh pass -> bind in the frame -> render -> L1 -> backward -> densification statistics -> Adam."""
+
+    def __init__(self, pc: SplattingGaussians, canonical: PhongCanonical, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
+                 lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True):
+        """`canonical`: `binding.phong_canonical(cano_verts, faces)`; `verts` [V,3]: any pose of the mesh (sizes the step's
+        static vertex buffer and is its first content).  `fold_binding` (default): the per-Gaussian binding is evaluated
+        inside the rasterizer's per-Gaussian kernels (fr_aux::binding with FR_BIND_PHONG).  False: the stand-alone
+        `bind_gaussians_phong` op in front of render() (same results; the A/B and the op's own user)."""
+        if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise RuntimeError("SplattingStep: data-parallel runs are not built (DESIGN.md)")
+        self.pc, self.bg = pc, bg
+        self.fold_binding = bool(fold_binding)
+        self.dev = pc.flat.device
+        self.world, self.exchange, self.exchange_in_graph = 1, False, False
+        self.lr = dict(SPLATTING_LRS, **(lrs or {}))
+        self.canonical = PhongCanonical(*[t.to(self.dev).contiguous() for t in canonical])
+        self.faces = self.canonical.faces
+        if pc.P and (int(pc.face_index.min()) < 0 or int(pc.face_index.max()) >= int(self.faces.shape[0])):
+            raise ValueError("SplattingStep: `face_index` names a face the mesh does not have")
+        self._make_adam()
+        self.xyz_gradient_accum = torch.zeros((pc.P, 1), device=self.dev)
+        self.denom = torch.zeros((pc.P, 1), device=self.dev)
+        self.cam = camera
+        self.verts = verts.detach().to(self.dev, torch.float32).clone().contiguous()   # static input of the captured step
+        self.gt = torch.zeros((3, camera.image_height, camera.image_width), device=self.dev)
+        self.loss = torch.zeros((), device=self.dev)
+        self._dimage = torch.zeros_like(self.gt)   # dL/dimage of the step
+        self._l1_ws = l1_workspace(self.dev)
+        self._init_image_loss(None)
+        self.out = None
+        self.use_graph = bool(use_graph)
+        self._graph, self._eager_steps, self.overflows = None, 0, 0
+        self.host_steps = 0      # (TrainStep.skipped_steps)
+
+    def adam_segments(self):
+        """The optimizer groups (train/optim.py:106-117 with config/splattingavatar.yaml:26-30) as runs of the flat buffer
+        (`_features_rest` is empty at SH degree 0: its group keeps its place and rate)."""
+        lr, P = self.lr, self.pc.P
+        return [(P * 3, lr["uvd"]), (P * 1, lr["opacity"]), (P * 3, lr["feature_dc"]), (P * 0, lr["feature_rest"]),
+                (P * 4, lr["rotation"]), (P * 3, lr["scaling"])]
+
+    def _make_adam(self):
+        pc = self.pc
+        self.adam = FusedAdam(pc.flat, pc.flat_grad, self.adam_segments())
+        self.adam.set_skip_words([pc.overflow_word])
+
+    def _forward_backward(self):
+        pc = self.pc
+        pc.begin_step()                                             # zero_grad(set_to_none=True)
+        stats = (self.xyz_gradient_accum, self.denom, pc.overflow_word)
+        if self.fold_binding:
+            from . import rasterizer
+            out = render_bound_batch([self.cam], [_SplattingFrame(pc, stats)], [self.verts],
+                                     PhongBinding(self.faces, pc.face_index, pc.bary_coords, self.canonical), self.bg,
+                                     slots=[rasterizer._slot])[0]
+        else:
+            frame = phong_frame(self.canonical, self.verts)
+            bound = bind_gaussians_phong(self.verts, self.faces, pc.face_index, pc.bary_coords, frame, pc._uvd, pc._rotation,
+                                         pc._scaling)
+            out = render(self.cam, _SplattingFrame(pc, stats, bound), self.bg)
+        out["render"].backward(self._image_loss_and_grad(out["render"]))   # see TrainStep
+        pc.collect_grads()
+        self.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
+
+    def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor) -> torch.Tensor:
+        self._extra_inputs = [(self.verts, posed_verts)]
+        return super().step(camera, gt_image)
+
+    def _load_inputs(self, camera, gt_image, extra=()):
+        super()._load_inputs(camera, gt_image, extra=self._extra_inputs)
+
+    # ---- SplattingAvatar's density control and opacity reset are out of scope (module docstring)
+    def _unsupported(self, *a, **k):
+        raise NotImplementedError("SplattingStep: SplattingAvatar's density control is not built (DESIGN.md)")
+
+    prune_low_opacity = densify_by_gradient = reset_opacity = reduce_densification_stats = _unsupported
+
+    # ---- checkpoints: 'model' holds the six parameters under the reference's names and the embedding buffers
+    GAUSSIAN_ATTRIBUTES = ["_uvd", "_opacity", "_features_dc", "_features_rest", "_rotation", "_scaling", "sample_fidxs",
+                           "sample_bary"]
+
+    def state_dict(self) -> dict:
+        pc = self.pc
+        model = {name: getattr(pc, name).detach().clone() for name, _ in pc.FIELDS}
+        model["sample_fidxs"], model["sample_bary"] = pc.face_index.clone(), pc.bary_coords.clone()
+        return {"global_step": self.adam.step_count, "model": model,
+                "optimizer": {"exp_avg": self.adam.exp_avg.clone(), "exp_avg_sq": self.adam.exp_avg_sq.clone(),
+                              "state": self.adam.state_words()},
+                "densification": {"xyz_gradient_accum": self.xyz_gradient_accum.clone(), "denom": self.denom.clone()}}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> list:
+        """Restores the Gaussians (any row count), the optimizer state and the statistics; returns the keys of sd['model'] it
+        did not use."""
+        model = dict(sd["model"])
+        missing = [k for k in self.GAUSSIAN_ATTRIBUTES if k not in model]
+        if missing:
+            raise KeyError(f"checkpoint lacks Gaussian attributes {missing}")
+        g = {k: model.pop(k) for k in self.GAUSSIAN_ATTRIBUTES}
+        pc = self.pc
+        pc.face_index = g["sample_fidxs"].to(self.dev, torch.int32).contiguous()
+        pc.bary_coords = g["sample_bary"].to(self.dev, torch.float32).contiguous()
+        P = int(pc.face_index.shape[0])
+        pc._bind([g[name].to(self.dev, torch.float32).reshape((P,) + pc.SHAPES[name]) for name, _ in pc.FIELDS])
+        self._make_adam()                                  # fresh (zero) moments over the new buffers
+        self._graph, self._eager_steps = None, 0           # buffers moved: the captured step is stale
+        self.xyz_gradient_accum = torch.zeros((P, 1), device=self.dev)
+        self.denom = torch.zeros((P, 1), device=self.dev)
+        opt, dens = sd.get("optimizer"), sd.get("densification")
+        if opt is not None:
+            self.adam.exp_avg.copy_(opt["exp_avg"])
+            self.adam.exp_avg_sq.copy_(opt["exp_avg_sq"])
+            self.adam.load_state_words(opt["state"])
+        self.host_steps = self.adam.step_count
+        if dens is not None:
+            self.xyz_gradient_accum.copy_(dens["xyz_gradient_accum"])
+            self.denom.copy_(dens["denom"])
+        return sorted(model.keys())
+
+
+__all__ = ["NUM_INIT_SAMPLES", "SPLATTING_LRS", "SplattingGaussians", "SplattingStep", "phong_canonical", "sample_bary_on_triangles"]

@@ -20,6 +20,9 @@
  *                     binding (model/fateavatar.py:225-258, volume_rendering/mesh_compute.py:27-59);
  *                     with FR_BIND_FACE_LOCAL, fr_bind_forward / fr_bind_backward_local replace those of
  *                     GaussianAvatars' binding (model/baseline/gaussianavatars.py:144-171)
+ *   fr_phong_frame    SplattingAvatar's per-frame mesh pass (model/baseline/splattingavatar.py:203-215, :819-902): vertex
+ *                     normals, per-vertex quaternions, face area ratios in one launch; with FR_BIND_PHONG, fr_bind_forward /
+ *                     fr_bind_backward_phong replace its Phong-surface binding (:224-246)
  *   fr_adam_step      replaces torch.optim.Adam.step() over the Gaussian groups (train/optim.py:11-37)
  *   fr_knn_mean_dist2 replaces SimpleKNN::knn (simple_knn.h, simple_knn.cu:186-222),
  *                     called from distCUDA2 (spatial.cu:14-25)
@@ -97,7 +100,8 @@ typedef struct fr_aux {
      * d_scaling [P,3] (every row; zeros for culled Gaussians) and ADDS dL/dverts into d_verts [V,3] (float atomics; the
      * caller zeroes it).  FR_FLAG_ACCUMULATE does not apply to these four.
      * A descriptor with mode FR_BIND_FACE_LOCAL (model/baseline/gaussianavatars.py:144-171) goes the same way; its backward
-     * writes d_local_xyz [P,3] (below) where the shell binding writes d_offset. */
+     * writes d_local_xyz [P,3] (below) where the shell binding writes d_offset.  So does one with mode FR_BIND_PHONG
+     * (model/baseline/splattingavatar.py:224-246): d_local_xyz receives d_uvd, and d_verts must be NULL. */
     const fr_binding* binding;
     float* d_verts;
     float* d_offset;
@@ -110,7 +114,7 @@ typedef struct fr_aux {
      * every backward call: frames that feed one optimizer step need ONE WORD EACH (fr_adam_config::skip takes up to
      * FR_ADAM_MAX_GRADS of them); the views of one fr_backward_batch call must not share a word. */
     float* overflow_out;
-    /* fr_backward / fr_backward_batch out [P,3]: a binding with mode FR_BIND_FACE_LOCAL only, where it takes d_offset's
+    /* fr_backward / fr_backward_batch out [P,3]: a binding with mode FR_BIND_FACE_LOCAL or FR_BIND_PHONG (d_uvd) only, where it takes d_offset's
      * place (every row written, zeros for culled Gaussians; d_offset is then not touched).  It sits behind the binding's
      * other members: the members in front of it keep their offsets, the plane members below stay the struct's last. */
     float* d_local_xyz;
@@ -413,9 +417,23 @@ int fr_multi_copy(int32_t n_segments, float* const* dst, const float* const* src
  * the mean of its three vertices,
  *   xyz = (R local_xyz) * s + c;  rotation = standardize(normalize(q_face) (x) rotation);  scaling = scaling + log(s)
  * (normalize: q / max(|q|, 1e-12)).  bary, offset, face_scale_canonical, shell_len and resize_scale are then ignored and
- * may be NULL / zero; local_xyz is required. */
+ * may be NULL / zero; local_xyz is required.
+ *
+ * FR_BIND_PHONG is SplattingAvatar's (model/baseline/splattingavatar.py:224-246): a point of the posed mesh's Phong surface.
+ * With b = bary and i_k the corners of the Gaussian's face f,
+ *   xyz = sum_k b_k verts[i_k] + normalize(sum_k b_k vert_normals[i_k]) * uvd[2]      (:224-233, :246; normalize: eps 1e-12)
+ *   rotation = standardize((sum_k b_k vert_quats[i_k]) (x) rotation)                   (:235, :245; the sum is not normalised)
+ *   scaling = scaling * face_ratio[f]                                                  (:237, :244: the raw log-scale is MULTIPLIED)
+ * vert_normals / vert_quats / face_ratio are fr_phong_frame's outputs for the posed mesh; they travel in struct fr_binding_phong
+ * (below), which extends the descriptor for this mode.  The per-Gaussian parameter uvd
+ * [N,3] travels in the `local_xyz` member (and its gradient in the backward's d_local_xyz slot): only its third column is
+ * read, and the first two columns of its gradient are written as zeros — walking a Gaussian over the mesh (the reference's
+ * CPU submodule simple_phongsurf) is outside this library.  face_index, bary, rotation, scaling, local_xyz and the three
+ * fr_phong_frame arrays are required; offset, face_scale_canonical, shell_len and resize_scale are ignored.  The mode has NO
+ * gradient to the posed vertices: a d_verts request is FR_ERR_INVALID_ARGUMENT. */
 #define FR_BIND_SHELL 0
 #define FR_BIND_FACE_LOCAL 1
+#define FR_BIND_PHONG 2
 struct fr_binding {
     int32_t N, V, F;
     const float* verts;                 /* [V,3] posed vertices */
@@ -429,8 +447,18 @@ struct fr_binding {
     const float* rotation;              /* [N,4] raw quaternion (r,x,y,z) */
     const float* scaling;               /* [N,3] raw log-scale */
     int32_t mode;                       /* FR_BIND_* (appended: a descriptor that ends above, zero-filled, is a shell binding) */
-    const float* local_xyz;             /* [N,3] FR_BIND_FACE_LOCAL: position in the face's frame */
+    const float* local_xyz;             /* [N,3] FR_BIND_FACE_LOCAL: position in the face's frame; FR_BIND_PHONG: uvd */
 };
+/* The descriptor of a FR_BIND_PHONG binding: fr_binding with the mode's three arrays behind it.  Wherever a `const fr_binding*`
+ * is taken (fr_bind_forward, fr_bind_backward_phong, fr_aux::binding) a descriptor whose mode is FR_BIND_PHONG MUST be the
+ * `base` member of one of these — the functions read the tail through that pointer.  fr_binding itself is unchanged: the two
+ * other modes neither carry nor read a tail. */
+typedef struct fr_binding_phong {
+    struct fr_binding base;             /* mode = FR_BIND_PHONG, bary, uvd in local_xyz */
+    const float* vert_normals;          /* [V,3] fr_phong_frame's outputs for the posed mesh */
+    const float* vert_quats;            /* [V,4] */
+    const float* face_ratio;            /* [F]   */
+} fr_binding_phong;
 int fr_face_scale(int32_t V, int32_t F, const float* verts, const int32_t* faces, float* out_scale, void* hip_stream);
 int fr_bind_forward(const fr_binding* b, float* xyz, float* rotation_out, float* scaling_out, void* hip_stream);
 /* Gradients of the three outputs in, gradients of offset / rotation / scaling out (fully written), and dL/dverts
@@ -441,6 +469,25 @@ int fr_bind_backward(const fr_binding* b, const float* g_xyz, const float* g_rot
  * binding has d_offset. */
 int fr_bind_backward_local(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
                            float* d_verts, float* d_local_xyz, float* d_rotation, float* d_scaling, void* hip_stream);
+/* The same for a FR_BIND_PHONG binding (any other mode is FR_ERR_INVALID_ARGUMENT): d_uvd [N,3] = (0, 0, g_xyz . n_hat),
+ * d_rotation through the quaternion product, d_scaling = g_scaling * face_ratio[f].  d_verts must be NULL (the argument keeps
+ * the three entry points' shape): the mode has no vertex gradient. */
+int fr_bind_backward_phong(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
+                           float* d_verts, float* d_uvd, float* d_rotation, float* d_scaling, void* hip_stream);
+/* SplattingAvatar's per-frame mesh pass (model/baseline/splattingavatar.py `forward` :203-215, `PerVertQuaternion` :819-902,
+ * `calc_face_areas` :781-791, `tbn` :756-765, `calc_per_face_Rt` :795-802) for FR_BIND_PHONG, from the posed verts [V,3], the
+ * canonical cano_verts [V,3], faces [F,3], the vertex -> face incidence list in CSR form (vf_offsets [V+1], vf_faces [3F],
+ * ascending within a row) and the canonical face areas face_area_canonical [F] (|cross(v2 - v1, v0 - v1)| / 2):
+ *   face_ratio [F]     = (area_posed + 1e-4) / (area_canonical + 1e-4)                                   (:899-902)
+ *   vert_normals [V,3] = normalize(sum over the vertex's faces of cross(v2 - v1, v0 - v1), eps 1e-6)     (:206, pytorch3d's
+ *                        verts_normals_packed)
+ *   vert_quats [V,4]   = normalize(sum of area_canonical[f] * q_f, eps 1e-6),  q_f = matrix_to_quaternion(R_posed,f R_cano,f^T)
+ *                        with R = tbn(triangle) (:846-881; the reference inverts [R|T] with torch.inverse: tbn is orthonormal)
+ * One launch on hip_stream, no allocation, no synchronisation (capturable), and no float atomics: every vertex gathers its
+ * faces in the list's order, so the result is the same bits on every run.  Not differentiable. */
+int fr_phong_frame(int32_t V, int32_t F, const float* verts, const float* cano_verts, const int32_t* faces,
+                   const int32_t* vf_offsets, const int32_t* vf_faces, const float* face_area_canonical, float* vert_normals,
+                   float* vert_quats, float* face_ratio, void* hip_stream);
 
 /* ---- Gaussian attributes looked up in UV attribute maps: the per-frame front end of a BAKED FateAvatar (reference
  * model/uv_decoder.py:179-202, `UVSampling._texture_look_up`: F.grid_sample(texture, 2 uv - 1, mode="bilinear",

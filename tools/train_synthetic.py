@@ -17,6 +17,10 @@ the same with the reference's scale / xyz regularisers in the step and a compres
 are printed after each densify.
     python tools/train_synthetic.py --rigged --P 10006 --dssim [--regularisers]
 the reference's image term, 0.8 x L1 + 0.2 x d_ssim (--image-loss RGB DSSIM for other weights; also for the generic step).
+
+    python tools/train_synthetic.py --splatting [--P 10000 --binding-op | --torch-binding]
+SplattingAvatar's step (fateavatar_amd/splatting.py): Gaussians on the Phong surface of the posed template, SH degree 0, one
+GPU.  --torch-binding binds with the stock-PyTorch restatement (tests/phong_ref.py) in front of render(): the A/B.
 """
 import argparse
 import json
@@ -63,6 +67,11 @@ def main():
     ap.add_argument("--rigged", action="store_true",
                     help="GaussianAvatars' loop: Gaussians bound to the local frames of the template's faces (one per face, then "
                          "random faces up to --P), rendered with --sh-degree active; --binding-op as for --fateavatar")
+    ap.add_argument("--splatting", action="store_true",
+                    help="SplattingAvatar's loop: --P Gaussians sampled on the template's Phong surface (default 10 000, the "
+                         "reference's num_init_samples), SH degree 0; --binding-op as for --fateavatar")
+    ap.add_argument("--torch-binding", action="store_true",
+                    help="--splatting: the mesh pass and the binding in stock PyTorch (tests/phong_ref.py) in front of render()")
     ap.add_argument("--regularisers", action="store_true",
                     help="--rigged: the reference's scale / xyz regularisers in every step (one more launch in the graph)")
     ap.add_argument("--reg-weights", type=float, nargs=2, default=None, metavar=("SCALE", "XYZ"),
@@ -89,6 +98,10 @@ def main():
         return main_fateavatar(a, rank, world, dev)
     if a.rigged:
         return main_rigged(a, rank, world, dev)
+    if a.splatting:
+        if a.image_loss:
+            raise SystemExit("--splatting: the image term is L1 (DESIGN.md)")
+        return main_splatting(a, rank, world, dev)
     truth = scenes.head_scene(P=a.P, res=a.res, sh_degree=a.sh_degree, seed=0, opacity=0.5)
     cams = [TorchCamera(scenes.head_scene(P=8, res=a.res, sh_degree=a.sh_degree, seed=0, view=v, n_views=a.views).camera, dev)
             for v in range(a.views)]
@@ -310,6 +323,87 @@ def main_rigged(a, rank, world, dev):
                       "image_loss": list(a.image_loss) if a.image_loss else None,
                       "loss_terms": [round(float(x), 6) for x in st.loss_terms] if a.image_loss else None,
                       "reg_loss": [round(float(x), 6) for x in st.reg_loss] if reg else None,
+                      "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
+
+
+def splatting_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_binding=False):
+    """SplattingAvatar's optimisation step on the synthetic INSTA-layout sequence (frame 0 is the canonical mesh): P Gaussians
+    sampled on the template as the reference samples them, the step object, cameras, posed meshes and targets rendered from a
+    hidden ground-truth set of the same embedding."""
+    from fateavatar_amd import insta
+    from fateavatar_amd.binding import bind_gaussians_phong, phong_canonical, phong_frame
+    from fateavatar_amd.splatting import SplattingGaussians, SplattingStep, _SplattingFrame
+    n_frames = max(views, 8)
+    transform, posed, faces = insta.synthetic_sequence(n_frames, res, seed=0)
+    cams = [TorchCamera(c, dev) for c in insta.camera_arrays(transform)]
+    posed_t, faces_t = torch.from_numpy(posed).to(dev), torch.from_numpy(faces).to(dev).to(torch.int32)
+    canonical = phong_canonical(posed_t[0], faces_t)
+    bg = torch.ones(3, device=dev)
+    pc = SplattingGaussians.sample(posed_t[0], faces_t, P, torch.Generator().manual_seed(0))
+    gt = SplattingGaussians(pc.face_index, pc.bary_coords, pc._scaling.detach()[:, 0], dev)
+    g = torch.Generator().manual_seed(5)
+    with torch.no_grad():
+        gt._features_dc.copy_((torch.rand(gt.P, 1, 3, generator=g) * 2.0 - 1.0).to(dev))
+        gt._opacity.fill_(float(np.log(0.6 / 0.4)))
+        gt._uvd[:, 2].copy_((0.002 * torch.randn(gt.P, generator=g)).to(dev))
+        gt._rotation.add_((0.3 * torch.randn(gt.P, 4, generator=g)).to(dev))
+        gt._scaling.add_((0.3 * torch.randn(gt.P, 3, generator=g)).to(dev))
+    gts = []
+    with torch.no_grad():
+        for f in range(n_frames):
+            b = bind_gaussians_phong(posed_t[f], faces_t, gt.face_index, gt.bary_coords, phong_frame(canonical, posed_t[f]),
+                                     gt._uvd, gt._rotation, gt._scaling)
+            gts.append(render(cams[f], _SplattingFrame(gt, None, b), bg)["render"].clone())
+    cls = SplattingStep
+    if torch_binding:
+        from tests import phong_ref
+
+        class TorchBoundStep(SplattingStep):
+            """The A/B: the reference's own route — mesh pass and binding as stock PyTorch kernels in front of render().
+            (R_posed R_cano^T instead of torch.inverse: the inverse does not capture into a graph.)"""
+            def _forward_backward(self):
+                pc, c = self.pc, self.canonical
+                pc.begin_step()
+                frame = phong_ref.mesh_frame(c.cano_verts, c.faces, self.verts, inverse=False)
+                bound = phong_ref.phong_bind(self.verts, c.faces, pc.face_index, pc.bary_coords, frame, pc._uvd, pc._rotation,
+                                             pc._scaling)
+                out = render(self.cam, _SplattingFrame(pc, (self.xyz_gradient_accum, self.denom, pc.overflow_word), bound), self.bg)
+                out["render"].backward(self._image_loss_and_grad(out["render"]))
+                pc.collect_grads()
+                self.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
+        cls = TorchBoundStep
+    st = cls(pc, canonical, TorchCamera(insta.camera_arrays(transform)[0], dev), bg, posed_t[0], use_graph=use_graph,
+             fold_binding=fold_binding)
+    return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames)
+
+
+def main_splatting(a, rank, world, dev):
+    if world > 1:
+        raise SystemExit("--splatting: data-parallel runs are not built")
+    P = a.P if "--P" in sys.argv else 10_000
+    su = splatting_setup(P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
+                         torch_binding=a.torch_binding)
+    st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
+    losses, warm = [], 10
+    for it in range(warm):
+        losses.append(st.step(cams[it % n_frames], posed_t[it % n_frames], gts[it % n_frames]).clone())
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(warm, warm + a.steps):
+        loss = st.step(cams[it % n_frames], posed_t[it % n_frames], gts[it % n_frames])
+        if it >= warm + a.steps - 4:
+            losses.append(loss.clone())
+    t_host = time.perf_counter() - t0
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    st.check()
+    l = [float(x) for x in losses]
+    how = "stock PyTorch in front of render()" if a.torch_binding else "stand-alone kernels" if a.binding_op else \
+        "mesh pass + inside the per-Gaussian kernels (fr_aux::binding, Phong surface)"
+    print(json.dumps({"host_enqueue_ms_per_step": round(t_host / a.steps * 1e3, 4),
+                      "metric": "SplattingAvatar optimisation steps/s (mesh pass + bind + render + L1 + backward + stats + Adam)",
+                      "binding": how, "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": st.pc.P,
+                      "res": a.res, "frames": n_frames, "graph": not a.no_graph, "overflows": st.overflows,
                       "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
 
 
