@@ -26,12 +26,11 @@ import torch
 from . import dp
 from .binding import bind_gaussians, face_scale
 from .bound import MeshBinding, render_bound_batch
+from .flat import FlatParams
 from .model import TorchCamera
-from .optim import FusedAdam
-from .rasterizer import GradOut
 from .render import render
 from .loss import l1_loss_and_grad, l1_workspace
-from .train import TrainStep
+from .train import BoundStep
 
 # config/fateavatar.yaml:34-39 (group names of train/optim.py:15-21)
 FATE_LRS = dict(opacity=0.05, offset=0.0016, color=0.0025, rotation=0.001, scaling=0.005)
@@ -40,11 +39,12 @@ FATE_MAINTAIN = dict(opacity_reset_interval=60000, densify_interval=3000, prune_
                      increase_num=1000, max_points_num=200000)
 
 
-class AvatarGaussians(torch.nn.Module):
+class AvatarGaussians(FlatParams):
     """The mesh-bound Gaussian parameters of FateAvatar (model/fateavatar.py:166-190) in ONE flat buffer, in the order
     of the optimizer groups.  `face_index` / `bary_coords` are the binding (model/fateavatar.py:120-164)."""
     FIELDS = (("_opacity", 1), ("_offset", 1), ("_features_dc", 3), ("_rotation", 4), ("_scaling", 3))
     SHAPES = {"_opacity": (1,), "_offset": (1,), "_features_dc": (1, 3), "_rotation": (4,), "_scaling": (3,)}
+    ROW_BUFFERS = (("face_index", torch.int32, "new_face_index"), ("bary_coords", torch.float32, "new_bary"))
     max_sh_degree = 0   # model/fateavatar.py:54,244
     fused_activations = True
 
@@ -90,99 +90,6 @@ class AvatarGaussians(torch.nn.Module):
         scale_init = float(init_scale_by_knn(torch.from_numpy(pts).to(device))[2])
         return cls(fi, bc, scale_init, device)
 
-    @property
-    def P(self):
-        return int(self.face_index.shape[0])
-
-    def widths(self):
-        return [w for _, w in self.FIELDS]
-
-    def _bind(self, raw):
-        P = raw[0].shape[0]
-        dev = raw[0].device
-        sizes = [P * w for _, w in self.FIELDS]
-        self.flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-        # (gradient buffer + the step's overflow word behind it: model.FlatGaussians._bind)
-        self._grad_store = torch.zeros(sum(sizes) + 4, dtype=torch.float32, device=dev)
-        self.flat_grad = self._grad_store[:sum(sizes)]
-        self.overflow_word = self._grad_store[sum(sizes):sum(sizes) + 1]
-        off = 0
-        for (name, w), n, r in zip(self.FIELDS, sizes, raw):
-            shp = (P,) + self.SHAPES[name]
-            self.flat[off:off + n].copy_(r.detach().reshape(-1))
-            p = torch.nn.Parameter(self.flat[off:off + n].view(shp))
-            # every parameter reaches a HIP kernel raw (the rasterizer or the binding op): its gradient is written straight
-            # into the flat gradient buffer
-            p._fr_grad_out = GradOut(self.flat_grad[off:off + n].view(shp))
-            setattr(self, name, p)
-            off += n
-
-    def lane(self) -> "AvatarGaussians":
-        """A second set of leaves over the SAME parameter storage with a gradient buffer of its own: what another view of
-        the batch, rendered in flight together with this one, back-propagates into (AvatarBatchStep)."""
-        o = AvatarGaussians.__new__(AvatarGaussians)
-        torch.nn.Module.__init__(o)
-        o.face_index, o.bary_coords, o.flat = self.face_index, self.bary_coords, self.flat
-        o._grad_store = torch.zeros_like(self._grad_store)
-        o.flat_grad = o._grad_store[:self.flat.numel()]
-        o.overflow_word = o._grad_store[self.flat.numel():self.flat.numel() + 1]
-        off = 0
-        for name, w in self.FIELDS:
-            n = self.P * w
-            shp = (self.P,) + self.SHAPES[name]
-            p = torch.nn.Parameter(self.flat[off:off + n].view(shp))
-            p._fr_grad_out = GradOut(o.flat_grad[off:off + n].view(shp))
-            setattr(o, name, p)
-            off += n
-        return o
-
-    def begin_step(self):
-        for name, _ in self.FIELDS:
-            getattr(self, name).grad = None
-
-    def exchange_buffer(self) -> torch.Tensor:
-        """`collect_grads()` + the overflow word behind it: what a data-parallel step all-reduces (SUM)."""
-        self.collect_grads()
-        return self._grad_store
-
-    def collect_grads(self) -> torch.Tensor:
-        off = 0
-        for name, w in self.FIELDS:
-            n = self.P * w
-            g, view = getattr(self, name).grad, self.flat_grad[off:off + n]
-            if g is None:
-                view.zero_()
-            elif g.data_ptr() != view.data_ptr():
-                view.copy_(g.reshape(-1))
-            off += n
-        return self.flat_grad
-
-    @torch.no_grad()
-    def resize(self, keep_mask=None, new_rows=None, new_face_index=None, new_bary=None, order=None):
-        """Drop the rows where keep_mask is False — or take the rows in the sequence `order` (row indices: a permutation
-        re-stores the set in another order) —, then append `new_rows` (one tensor per field) with their binding.
-        Returns the row map (old row of every new row, -1 for appended ones) the optimizer state has to follow."""
-        dev = self.flat.device
-        if order is not None:
-            if keep_mask is not None:
-                raise ValueError("resize: keep_mask or order, not both")
-            old_index = order.to(dev, torch.int64).reshape(-1)
-        else:
-            keep = torch.ones(self.P, dtype=torch.bool, device=dev) if keep_mask is None else keep_mask.reshape(-1).bool()
-            old_index = torch.nonzero(keep).reshape(-1)
-        raw = [getattr(self, name).detach()[old_index] for name, _ in self.FIELDS]
-        fi, bc = self.face_index[old_index], self.bary_coords[old_index]
-        n_new = 0
-        if new_rows is not None:
-            n_new = int(new_rows[0].shape[0])
-            raw = [torch.cat([r, a.to(dev, torch.float32).reshape((n_new,) + tuple(r.shape[1:]))]) for r, a in zip(raw, new_rows)]
-            fi = torch.cat([fi, new_face_index.to(dev, torch.int32)])
-            bc = torch.cat([bc, new_bary.to(dev, torch.float32)])
-        self.face_index, self.bary_coords = fi.contiguous(), bc.contiguous()
-        self._bind(raw)
-        return torch.cat([old_index, torch.full((n_new,), -1, dtype=torch.int64, device=dev)])
-
-
 class _BoundFrame:
     """What render() reads of a Gaussian holder (render_3dgs.py:19-63), for one frame's bound values."""
     max_sh_degree = 0
@@ -206,8 +113,11 @@ class _RawFrame:
         self.fused_densification_stats = stats
 
 
-class AvatarStep(TrainStep):
-    """One optimisation step of FateAvatar per call: `step(camera, posed_verts, gt_image)`."""
+class AvatarStep(BoundStep):
+    """One optimisation step of FateAvatar per call: `step(camera, posed_verts, gt_image)`.  The optimizer groups are those
+    of train/optim.py:15-21 with config/fateavatar.yaml:34-39."""
+    LRS = FATE_LRS
+    LR_KEYS = {"_opacity": "opacity", "_offset": "offset", "_features_dc": "color", "_rotation": "rotation", "_scaling": "scaling"}
 
     def __init__(self, pc: AvatarGaussians, faces: torch.Tensor, canonical_verts: torch.Tensor, camera: TorchCamera,
                  bg: torch.Tensor, lrs: Optional[dict] = None, shell_len: float = 0.05, resize_scale: bool = True,
@@ -220,42 +130,12 @@ class AvatarStep(TrainStep):
         `fold_binding` (default): the binding is evaluated inside the rasterizer's per-Gaussian kernels (bound.py,
         fr_aux::binding) — no binding launches, no bound arrays written by one kernel to be read by the next.  False: the
         stand-alone `bind_gaussians` op in front of `render()` (same results; kept as the A/B and as the op's own user)."""
-        self.pc, self.bg = pc, bg
-        self.fold_binding = bool(fold_binding)
         self.keep_coherent = bool(keep_coherent)
-        self.dev = pc.flat.device
-        self.world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
-        self.exchange = torch.distributed.is_initialized() and (self.world > 1 or dp.group_of_one())
-        self.exchange_in_graph = self.exchange and torch.distributed.get_backend() == "nccl"   # (see TrainStep)
-        self.lr = dict(FATE_LRS, **(lrs or {}))
-        self.faces = faces.to(self.dev, torch.int32).contiguous()
+        super().__init__(pc, faces, camera, bg, canonical_verts, lrs, use_graph, fold_binding)
         self.shell_len, self.resize_scale = float(shell_len), bool(resize_scale)
+        self.canon_verts = self.verts.clone()
         # compute_face_orientation(canonical verts, return_scale=True)[1] (model/fateavatar.py:84-85)
-        self.face_scale_canonical = face_scale(canonical_verts.to(self.dev, torch.float32), self.faces)
-        self._make_adam()
-        self.xyz_gradient_accum = torch.zeros((pc.P, 1), device=self.dev)
-        self.denom = torch.zeros((pc.P, 1), device=self.dev)
-        self.cam = camera
-        self.canon_verts = canonical_verts.to(self.dev, torch.float32).clone().contiguous()
-        self.verts = canonical_verts.to(self.dev, torch.float32).clone().contiguous()   # static input of the captured step
-        self.gt = torch.zeros((3, camera.image_height, camera.image_width), device=self.dev)
-        self.loss = torch.zeros((), device=self.dev)
-        self._dimage = torch.zeros_like(self.gt)   # dL/dimage of the step
-        self._l1_ws = l1_workspace(self.dev)       # scratch of this frame's loss kernel (one per lane: loss.py)
-        self.out = None
-        self.use_graph = bool(use_graph)
-        self._graph, self._eager_steps, self.overflows = None, 0, 0
-        self.host_steps = 0      # (TrainStep.skipped_steps)
-
-    def adam_segments(self):
-        """The optimizer groups (train/optim.py:15-21 with config/fateavatar.yaml:34-39) as runs of the flat buffer."""
-        lr, P = self.lr, self.pc.P
-        return [(P * 1, lr["opacity"]), (P * 1, lr["offset"]), (P * 3, lr["color"]), (P * 4, lr["rotation"]), (P * 3, lr["scaling"])]
-
-    def _make_adam(self):
-        pc = self.pc
-        self.adam = FusedAdam(pc.flat, pc.flat_grad, self.adam_segments(), grad_scale=1.0 / self.world)
-        self.adam.set_skip_words([pc.overflow_word])
+        self.face_scale_canonical = face_scale(self.canon_verts, self.faces)
 
     def _forward_backward(self):
         self._forward_backward_on(self)
@@ -276,17 +156,10 @@ class AvatarStep(TrainStep):
             out = render(L.cam, frame, self.bg)
         _, g = l1_loss_and_grad(out["render"], L.gt, loss_out=L.loss, grad_out=L._dimage, workspace=L._l1_ws)   # see TrainStep
         out["render"].backward(g)
-        L.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
+        L.out = self._kept(out)
 
     def _binding(self, pc: AvatarGaussians) -> MeshBinding:
         return MeshBinding(self.faces, pc.face_index, pc.bary_coords, self.face_scale_canonical, self.shell_len, self.resize_scale)
-
-    def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor) -> torch.Tensor:
-        self._extra_inputs = [(self.verts, posed_verts)]
-        return super().step(camera, gt_image)
-
-    def _load_inputs(self, camera, gt_image, extra=()):
-        super()._load_inputs(camera, gt_image, extra=self._extra_inputs)
 
     # ---- maintenance (train/iteration.py:62-86)
     def maintain(self, global_step: int, cfg: Optional[dict] = None) -> dict:
@@ -301,13 +174,6 @@ class AvatarStep(TrainStep):
             self.reset_opacity()
             did["opacity_reset"] = True
         return did
-
-    @torch.no_grad()
-    def _rebind_optimizer(self, old_index, old_rows):
-        pc = self.pc
-        self.adam.remap_rows(pc.flat, pc.flat_grad, old_index, pc.widths(), old_rows)
-        self.adam.set_skip_words([pc.overflow_word])
-        self._graph, self._eager_steps = None, 0   # buffers moved: the captured step is stale
 
     @torch.no_grad()
     def uv_densify(self, increase_num: int, generator: Optional[torch.Generator] = None) -> int:
@@ -327,13 +193,11 @@ class AvatarStep(TrainStep):
         dp.broadcast_(uvw)
         new_bary = uvw / uvw.sum(dim=-1, keepdim=True)
         rows = [getattr(pc, name).detach()[idx].clone() for name, _ in pc.FIELDS]
-        rows[4] = torch.log(torch.exp(rows[4]) * 0.75)          # new_scaling (:624)
+        i = self._field_index("_scaling")
+        rows[i] = torch.log(torch.exp(rows[i]) * 0.75)          # new_scaling (:624)
         old_rows = pc.P
         old_index = pc.resize(new_rows=rows, new_face_index=pc.face_index[idx], new_bary=new_bary)
-        self._rebind_optimizer(old_index, old_rows)
-        # statistics restart from zero (:667-669)
-        self.xyz_gradient_accum = torch.zeros((pc.P, 1), device=self.dev)
-        self.denom = torch.zeros((pc.P, 1), device=self.dev)
+        self._buffers_moved(old_index, old_rows, stats=None)    # statistics restart from zero (:667-669)
         self.last_densify = (idx, new_bary)
         if self.keep_coherent:
             AvatarStep.sort_coherent(self)     # (a subclass's lanes are rebuilt by its own uv_densify)
@@ -358,10 +222,9 @@ class AvatarStep(TrainStep):
         pc = self.pc
         order = self.coherent_order(cells)
         old_rows = pc.P
-        acc, den = self.xyz_gradient_accum[order], self.denom[order]
+        stats = (self.xyz_gradient_accum[order].contiguous(), self.denom[order].contiguous())
         old_index = pc.resize(order=order)
-        self._rebind_optimizer(old_index, old_rows)
-        self.xyz_gradient_accum, self.denom = acc.contiguous(), den.contiguous()
+        self._buffers_moved(old_index, old_rows, stats=stats)
         return order
 
     @torch.no_grad()
@@ -370,20 +233,10 @@ class AvatarStep(TrainStep):
         pc = self.pc
         keep = ~(torch.sigmoid(pc._opacity) < min_opacity).reshape(-1)
         old_rows = pc.P
-        acc, den = self.xyz_gradient_accum[keep], self.denom[keep]
+        stats = (self.xyz_gradient_accum[keep].contiguous(), self.denom[keep].contiguous())
         old_index = pc.resize(keep_mask=keep)
-        self._rebind_optimizer(old_index, old_rows)
-        self.xyz_gradient_accum, self.denom = acc.contiguous(), den.contiguous()
+        self._buffers_moved(old_index, old_rows, stats=stats)
         return old_rows - pc.P
-
-    @torch.no_grad()
-    def reset_opacity(self) -> None:
-        """_reset_opacity (model/fateavatar.py:713-731), in place (the captured graph stays valid)."""
-        pc = self.pc
-        cur = torch.sigmoid(pc._opacity)
-        new = torch.minimum(cur, torch.full_like(cur, 0.01))
-        pc._opacity.data.copy_(torch.log(new / (1 - new)))
-        self.adam.zero_field_moments(pc.widths(), pc.P, fields=(0,))
 
     # ---- checkpoints in the reference's layout (Trainer.save_checkpoint, train/trainer.py:396-435: a dict with 'epoch',
     #      'global_step' and 'model' = model.state_dict(), which for FateAvatar holds the six Gaussian parameters and the
@@ -397,10 +250,7 @@ class AvatarStep(TrainStep):
         model["_features_rest"] = torch.zeros((pc.P, 0, 3), device=self.dev)   # max_sh_degree 0: empty (fateavatar.py:172-183)
         model["face_index"], model["bary_coords"] = pc.face_index.clone(), pc.bary_coords.clone()
         # 'optimizer' and 'densification' are additions a seamless resume needs; the reference saves neither
-        return {"global_step": self.adam.step_count, "model": model,
-                "optimizer": {"exp_avg": self.adam.exp_avg.clone(), "exp_avg_sq": self.adam.exp_avg_sq.clone(),
-                              "state": self.adam.state_words()},
-                "densification": {"xyz_gradient_accum": self.xyz_gradient_accum.clone(), "denom": self.denom.clone()}}
+        return {"global_step": self.adam.step_count, "model": model, **self._training_state()}
 
     @torch.no_grad()
     def load_state_dict(self, sd: dict) -> list:
@@ -421,18 +271,9 @@ class AvatarStep(TrainStep):
         pc.bary_coords = g["bary_coords"].to(self.dev, torch.float32).contiguous()
         P = int(pc.face_index.shape[0])
         pc._bind([g[name].to(self.dev, torch.float32).reshape((P,) + pc.SHAPES[name]) for name, _ in pc.FIELDS])
-        self._rebind_optimizer(torch.full((P,), -1, dtype=torch.int64, device=self.dev), old_rows)   # fresh (zero) moments
-        self.xyz_gradient_accum = torch.zeros((P, 1), device=self.dev)
-        self.denom = torch.zeros((P, 1), device=self.dev)
-        opt, dens = sd.get("optimizer"), sd.get("densification")
-        if opt is not None:
-            self.adam.exp_avg.copy_(opt["exp_avg"])
-            self.adam.exp_avg_sq.copy_(opt["exp_avg_sq"])
-            self.adam.load_state_words(opt["state"])
-        self.host_steps = self.adam.step_count          # (skipped_steps counts from the restored state on)
-        if dens is not None:
-            self.xyz_gradient_accum.copy_(dens["xyz_gradient_accum"])
-            self.denom.copy_(dens["denom"])
+        # REMAPPED, not fresh: a checkpoint without an `optimizer` entry goes on from this step's count with zero moments
+        self._buffers_moved(torch.full((P,), -1, dtype=torch.int64, device=self.dev), old_rows, stats=None)
+        self._load_training_state(sd)
         return sorted(model.keys())
 
 
@@ -544,7 +385,7 @@ class AvatarBatchStep(AvatarStep):
         _, grads = l1_loss_and_grad_batch(images, [L.gt for L in self.lanes], [L.loss for L in self.lanes],
                                           [L._dimage for L in self.lanes], [L._l1_ws for L in self.lanes])
         for L, out in zip(self.lanes, outs):
-            L.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
+            L.out = self._kept(out)
         torch.autograd.backward(images, grad_tensors=grads)
         if self.exchange:                          # sum of the local lanes, then the sum over the ranks; Adam scales
             flat = [L.pc.exchange_buffer() for L in self.lanes]   # (gradients + overflow words: the words add up too)

@@ -11,23 +11,19 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .rasterizer import GradOut
+from .flat import FlatParams
 
 
-class FlatGaussians(torch.nn.Module):
+class FlatGaussians(FlatParams):
     FIELDS = (("_xyz", 3), ("_features", None), ("_opacity", 1), ("_scaling", 3), ("_rotation", 4))
 
     def __init__(self, means3D, shs, opacities, scales, rotations, sh_degree: int, device, fused_activations=False):
         """Arguments are ACTIVATED values (numpy): they are inverted into raw parameters like
         create_from_pcd does (gaussian_model.py:137-160)."""
         super().__init__()
-        P, M = means3D.shape[0], shs.shape[1]
-        self.max_sh_degree = sh_degree
-        self.P, self.M = P, M
+        self.max_sh_degree, self.M = sh_degree, shs.shape[1]
         # True: render() passes the raw parameters and the rasterizer kernels apply the activations themselves
         self.fused_activations = bool(fused_activations)
-        # one flat value buffer and one flat gradient buffer; every parameter (and its .grad) is a VIEW into
-        # them, so autograd accumulates in place and the data-parallel exchange is a single all-reduce
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)  # noqa: E731
         op = t(opacities).reshape(-1).clamp(1e-6, 1 - 1e-6)
         self._bind([t(means3D), t(shs), torch.log(op / (1 - op)).reshape(-1, 1), torch.log(t(scales)), t(rotations)])
@@ -58,60 +54,14 @@ class FlatGaussians(torch.nn.Module):
                             fused_activations)
 
     def widths(self):
-        """Floats per Gaussian of each field, in flat-buffer order."""
         return [3, self.M * 3, 1, 3, 4]
 
-    def _bind(self, raw):
-        """(Re)build the flat value / gradient buffers from one raw tensor per field ([P, ...] each) and make every
-        parameter, and its gradient slot, a view into them."""
-        P = raw[0].shape[0]
-        device = raw[0].device
-        self.P = P
-        sizes = [P * w for w in self.widths()]
-        shapes = [(P, 3), (P, self.M, 3), (P, 1), (P, 3), (P, 4)]
-        self.flat = torch.empty(sum(sizes), dtype=torch.float32, device=device)
-        # the gradient buffer, and behind it (same allocation, so that ONE all-reduce carries both) the step's OVERFLOW WORD:
-        # the rasterizer's backward sets it to 1 when its frame overflowed the binning capacity inside a replayed graph (all
-        # its gradients are zero then), and the fused Adam skips a step whose word — summed over lanes and ranks — is not 0
-        self._grad_store = torch.zeros(sum(sizes) + 4, dtype=torch.float32, device=device)
-        self.flat_grad = self._grad_store[:sum(sizes)]
-        self.overflow_word = self._grad_store[sum(sizes):sum(sizes) + 1]
-        self._grad_views = {}
-        off = 0
-        for (name, _), n, shp, r in zip(self.FIELDS, sizes, shapes, raw):
-            self.flat[off:off + n].copy_(r.detach().reshape(-1))
-            p = torch.nn.Parameter(self.flat[off:off + n].view(shp))
-            gv = self.flat_grad[off:off + n].view(shp)
-            self._grad_views[name] = gv
-            if name in ("_xyz", "_features") or self.fused_activations:
-                # these reach the rasterizer untouched: it writes their gradient straight into the flat
-                # buffer (rasterizer.py `_fr_grad_out`), no accumulation kernel, no zero-fill
-                p._fr_grad_out = GradOut(gv)
-            setattr(self, name, p)
-            off += n
+    def shapes(self):
+        return [(3,), (self.M, 3), (1,), (3,), (4,)]
 
-    @torch.no_grad()
-    def resize(self, keep_mask=None, new_rows=None):
-        """Prune and / or append Gaussians (reference: _prune_low_opacity_points / _uv_densify,
-        model/fateavatar.py:610-711): rows where `keep_mask` is False are dropped, then `new_rows` — one raw tensor
-        [n_new, ...] per field, in FIELDS order — are appended.  The flat buffers are rebuilt and every parameter is a
-        new nn.Parameter (as in the reference); returns the row map `old_index` (int64 [P_new], -1 for appended rows)
-        that optimizer state has to follow (FusedAdam.remap_rows)."""
-        dev = self.flat.device
-        P_old = self.P
-        keep = torch.ones(P_old, dtype=torch.bool, device=dev) if keep_mask is None else keep_mask.to(dev).bool().reshape(-1)
-        if keep.numel() != P_old:
-            raise ValueError("keep_mask must have one entry per Gaussian")
-        old_index = torch.nonzero(keep).reshape(-1)
-        raw = [getattr(self, name).detach()[old_index] for name, _ in self.FIELDS]
-        n_new = 0
-        if new_rows is not None:
-            n_new = int(new_rows[0].shape[0])
-            for i, (r, add) in enumerate(zip(raw, new_rows)):
-                add = add.to(dev, torch.float32).reshape((n_new,) + tuple(r.shape[1:]))
-                raw[i] = torch.cat([r, add], dim=0)
-        self._bind(raw)
-        return torch.cat([old_index, torch.full((n_new,), -1, dtype=torch.int64, device=dev)])
+    def _wants_slot(self, name):
+        # without fused activations only these two reach the rasterizer untouched (FlatParams._wants_slot)
+        return name in ("_xyz", "_features") or self.fused_activations
 
     def _p(self, name):
         return getattr(self, name)
@@ -141,10 +91,7 @@ class FlatGaussians(torch.nn.Module):
         return getattr(self, name).grad
 
     def begin_step(self):
-        """Drop the previous gradients (set_to_none, like the reference's zero_grad(set_to_none=True),
-        train/iteration.py:49): the next backward ASSIGNS instead of accumulating."""
-        for name, _ in self.FIELDS:
-            getattr(self, name).grad = None
+        super().begin_step()
         self.accumulate_into_kept_grads(False)
 
     def accumulate_into_kept_grads(self, on: bool = True) -> None:
@@ -156,22 +103,6 @@ class FlatGaussians(torch.nn.Module):
             slot = getattr(getattr(self, name), "_fr_grad_out", None)
             if slot is not None:
                 slot.add_to_kept = bool(on)
-
-    def exchange_buffer(self) -> torch.Tensor:
-        """`collect_grads()` + the overflow word behind it: what a data-parallel step all-reduces (SUM)."""
-        self.collect_grads()
-        return self._grad_store
-
-    def collect_grads(self) -> torch.Tensor:
-        """After backward: make `flat_grad` hold every parameter's gradient (xyz / features are already there;
-        the three activated parameters are copied in).  Returns the flat buffer for the data-parallel exchange."""
-        for name, _ in self.FIELDS:
-            g, view = getattr(self, name).grad, self._grad_views[name]
-            if g is None:
-                view.zero_()
-            elif g.data_ptr() != view.data_ptr():
-                view.copy_(g)
-        return self.flat_grad
 
 
 class TorchCamera:

@@ -33,12 +33,11 @@ import torch
 
 from .binding import bind_gaussians_face_local
 from .bound import FaceLocalBinding, render_bound_batch
-from .loss import ImageLoss, gaussian_regularisers, l1_workspace, regulariser_workspace
+from .flat import FlatParams
+from .loss import ImageLoss, gaussian_regularisers, regulariser_workspace
 from .model import TorchCamera
-from .optim import FusedAdam
-from .rasterizer import GradOut
 from .render import render
-from .train import TrainStep
+from .train import BoundStep
 
 # config/gaussianavatars.yaml:26-31 (group names of train/optim.py:73-80; position_lr_init: the schedule is out of scope)
 RIGGED_LRS = dict(xyz=0.005, opacity=0.05, feature_dc=0.0025, feature_rest=0.0025 / 20, rotation=0.001, scaling=0.017)
@@ -68,13 +67,14 @@ def build_rotation(r: torch.Tensor) -> torch.Tensor:
                         2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
 
 
-class RiggedGaussians(torch.nn.Module):
+class RiggedGaussians(FlatParams):
     """The face-bound Gaussian parameters of GaussianAvatars in ONE flat buffer, in the order of the optimizer groups
     (train/optim.py:73-80).  `binding` [P] is the face of every Gaussian (gaussianavatars.py:52-60)."""
     max_sh_degree = 3        # config/gaussianavatars.yaml:23
     FIELDS = (("_xyz", 3), ("_opacity", 1), ("_features_dc", 3), ("_features_rest", 45), ("_rotation", 4), ("_scaling", 3))
     SHAPES = {"_xyz": (3,), "_opacity": (1,), "_features_dc": (1, 3), "_features_rest": (15, 3), "_rotation": (4,),
               "_scaling": (3,)}
+    ROW_BUFFERS = (("binding", torch.int32, "new_binding"),)
     fused_activations = True
 
     def __init__(self, binding, device, rng: Optional[np.random.Generator] = None):
@@ -97,87 +97,9 @@ class RiggedGaussians(torch.nn.Module):
         return cls(np.arange(int(n_faces), dtype=np.int32), device, rng)
 
     @property
-    def P(self) -> int:
-        return int(self.binding.shape[0])
-
-    def widths(self):
-        return [w for _, w in self.FIELDS]
-
-    def _bind(self, raw):
-        P, dev = raw[0].shape[0], raw[0].device
-        sizes = [P * w for _, w in self.FIELDS]
-        self.flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-        # (gradient buffer + the step's overflow word behind it: model.FlatGaussians._bind)
-        self._grad_store = torch.zeros(sum(sizes) + 4, dtype=torch.float32, device=dev)
-        self.flat_grad = self._grad_store[:sum(sizes)]
-        self.overflow_word = self._grad_store[sum(sizes):sum(sizes) + 1]
-        off = 0
-        for (name, w), n, r in zip(self.FIELDS, sizes, raw):
-            shp = (P,) + self.SHAPES[name]
-            self.flat[off:off + n].copy_(r.detach().reshape(-1))
-            p = torch.nn.Parameter(self.flat[off:off + n].view(shp))
-            p._fr_grad_out = GradOut(self.flat_grad[off:off + n].view(shp))   # (see AvatarGaussians._bind)
-            setattr(self, name, p)
-            off += n
-
-    @property
     def get_features(self) -> torch.Tensor:
         """[P,16,3]: GaussianModel.get_features (volume_rendering/gaussian_model.py:119-122)."""
         return torch.cat((self._features_dc, self._features_rest), dim=1)
-
-    def begin_step(self):
-        for name, _ in self.FIELDS:
-            getattr(self, name).grad = None
-
-    def grad_view(self, name: str) -> torch.Tensor:
-        """The run of the flat gradient buffer that belongs to the field `name`, as [P, width]."""
-        off = 0
-        for n, w in self.FIELDS:
-            if n == name:
-                return self.flat_grad[off:off + self.P * w].view(self.P, w)
-            off += self.P * w
-        raise KeyError(name)
-
-    @torch.no_grad()
-    def resize(self, keep_mask=None, new_rows=None, new_binding=None) -> torch.Tensor:
-        """Prune and / or append Gaussians (FlatGaussians.resize's contract): rows where `keep_mask` is False are dropped,
-        then `new_rows` — one raw tensor [n_new, ...] per field, in FIELDS order — are appended, bound to the faces
-        `new_binding` [n_new].  `binding` follows the rows.  The flat buffers are rebuilt and every parameter is a new
-        nn.Parameter; returns the row map `old_index` (int64 [P_new], -1 for appended rows)."""
-        dev = self.flat.device
-        P_old = self.P
-        keep = torch.ones(P_old, dtype=torch.bool, device=dev) if keep_mask is None else keep_mask.to(dev).bool().reshape(-1)
-        if keep.numel() != P_old:
-            raise ValueError("keep_mask must have one entry per Gaussian")
-        old_index = torch.nonzero(keep).reshape(-1)
-        raw = [getattr(self, name).detach()[old_index] for name, _ in self.FIELDS]
-        binding = self.binding[old_index]
-        n_new = 0
-        if new_rows is not None:
-            n_new = int(new_rows[0].shape[0])
-            if new_binding is None or int(new_binding.numel()) != n_new:
-                raise ValueError("new_binding must name one face per appended row")
-            for i, (r, add) in enumerate(zip(raw, new_rows)):
-                add = add.to(dev, torch.float32).reshape((n_new,) + tuple(r.shape[1:]))
-                raw[i] = torch.cat([r, add], dim=0)
-            binding = torch.cat([binding, new_binding.to(dev, torch.int32).reshape(-1)])
-        self.binding = binding.contiguous()
-        self._bind(raw)
-        return torch.cat([old_index, torch.full((n_new,), -1, dtype=torch.int64, device=dev)])
-
-    def collect_grads(self) -> torch.Tensor:
-        """Every parameter's gradient in the flat gradient buffer (most are written there by the kernels already; the two
-        halves of the SH block come back from autograd's split of the concatenation)."""
-        off = 0
-        for name, w in self.FIELDS:
-            n = self.P * w
-            g, view = getattr(self, name).grad, self.flat_grad[off:off + n]
-            if g is None:
-                view.zero_()
-            elif g.data_ptr() != view.data_ptr() or not g.is_contiguous():
-                view.view(g.shape).copy_(g)
-            off += n
-        return self.flat_grad
 
 
 class _RiggedFrame:
@@ -195,9 +117,13 @@ class _RiggedFrame:
         self.fused_densification_stats = stats
 
 
-class RiggedStep(TrainStep):
+class RiggedStep(BoundStep):
     """One optimisation step of GaussianAvatars per call: `step(camera, posed_verts, gt_image)` —
-    bind in the frame -> render -> L1 -> backward -> densification statistics -> Adam."""
+    bind in the frame -> render -> L1 -> backward -> densification statistics -> Adam.  The optimizer groups are those of
+    train/optim.py:73-80 with config/gaussianavatars.yaml:26-31."""
+    LRS = RIGGED_LRS
+    LR_KEYS = {"_xyz": "xyz", "_opacity": "opacity", "_features_dc": "feature_dc", "_features_rest": "feature_rest",
+               "_rotation": "rotation", "_scaling": "scaling"}
 
     def __init__(self, pc: RiggedGaussians, faces: torch.Tensor, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True,
@@ -215,32 +141,13 @@ class RiggedStep(TrainStep):
         term is L1 with weight 1, `loss_terms` is None."""
         if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise RuntimeError("RiggedStep: data-parallel runs are not built (DESIGN.md)")
-        self.pc, self.bg = pc, bg
-        self.fold_binding = bool(fold_binding)
-        self.dev = pc.flat.device
-        self.world, self.exchange, self.exchange_in_graph = 1, False, False
-        self.lr = dict(RIGGED_LRS, **(lrs or {}))
-        self.faces = faces.to(self.dev, torch.int32).contiguous()
-        self._make_adam()
-        self.xyz_gradient_accum = torch.zeros((pc.P, 1), device=self.dev)
-        self.denom = torch.zeros((pc.P, 1), device=self.dev)
-        self.cam = camera
-        self.verts = verts.to(self.dev, torch.float32).clone().contiguous()   # static input of the captured step
-        self.gt = torch.zeros((3, camera.image_height, camera.image_width), device=self.dev)
-        self.loss = torch.zeros((), device=self.dev)
-        self._dimage = torch.zeros_like(self.gt)   # dL/dimage of the step
-        self._l1_ws = l1_workspace(self.dev)
-        self._init_image_loss(image_loss)
+        super().__init__(pc, faces, camera, bg, verts, lrs, use_graph, fold_binding, image_loss, data_parallel=False)
         self.regularisers = None if regularisers is None else Regularisers(*[float(x) for x in regularisers])
         # the reference's out['scale_loss'] / out['xyz_loss'] of the step (unweighted), written by the regulariser launch
         self.reg_loss = None if regularisers is None else torch.zeros(2, device=self.dev)
         self._reg_ws = None if regularisers is None else regulariser_workspace(self.dev)
         self.n_faces = int(self.faces.shape[0])
         self._count_binding()
-        self.out = None
-        self.use_graph = bool(use_graph)
-        self._graph, self._eager_steps, self.overflows = None, 0, 0
-        self.host_steps = 0      # (TrainStep.skipped_steps)
 
     def _count_binding(self):
         """binding_counter [F] int32: Gaussians per face (gaussianavatars.py:66-69)."""
@@ -248,17 +155,6 @@ class RiggedStep(TrainStep):
         if b.numel() and (int(b.min()) < 0 or int(b.max()) >= self.n_faces):
             raise ValueError("RiggedStep: `binding` names a face the mesh does not have")
         self.binding_counter = torch.bincount(b, minlength=self.n_faces).to(torch.int32)
-
-    def adam_segments(self):
-        """The optimizer groups (train/optim.py:73-80 with config/gaussianavatars.yaml:26-31) as runs of the flat buffer."""
-        lr, P = self.lr, self.pc.P
-        return [(P * 3, lr["xyz"]), (P * 1, lr["opacity"]), (P * 3, lr["feature_dc"]), (P * 45, lr["feature_rest"]),
-                (P * 4, lr["rotation"]), (P * 3, lr["scaling"])]
-
-    def _make_adam(self):
-        pc = self.pc
-        self.adam = FusedAdam(pc.flat, pc.flat_grad, self.adam_segments())
-        self.adam.set_skip_words([pc.overflow_word])
 
     def _forward_backward(self):
         pc = self.pc
@@ -272,7 +168,7 @@ class RiggedStep(TrainStep):
             bound = bind_gaussians_face_local(self.verts, self.faces, pc.binding, pc._xyz, pc._rotation, pc._scaling)
             out = render(self.cam, _RiggedFrame(pc, stats, bound), self.bg)
         out["render"].backward(self._image_loss_and_grad(out["render"]))   # see TrainStep
-        pc.collect_grads()                                          # (the SH halves: see RiggedGaussians.collect_grads)
+        pc.collect_grads()                                          # (the SH halves: see FlatParams.collect_grads)
         if self.regularisers is not None:
             # train/loss.py:367-379: weight x the two regularisers' gradients are ADDED to the image term's, in front of Adam.
             # A replay that overflowed its binning capacity back-propagated zeros and its Adam launch skips the step (the
@@ -281,14 +177,7 @@ class RiggedStep(TrainStep):
             gaussian_regularisers(pc._scaling, pc._xyz, pc.grad_view("_scaling"), pc.grad_view("_xyz"), out=self.reg_loss,
                                   weights=(r.scale_weight, r.xyz_weight), thresholds=(r.threshold_scale, r.threshold_xyz),
                                   workspace=self._reg_ws)
-        self.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
-
-    def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor) -> torch.Tensor:
-        self._extra_inputs = [(self.verts, posed_verts)]
-        return super().step(camera, gt_image)
-
-    def _load_inputs(self, camera, gt_image, extra=()):
-        super()._load_inputs(camera, gt_image, extra=self._extra_inputs)
+        self.out = self._kept(out)
 
     def update_sh_degree(self) -> int:
         """_update_sh_degree (gaussianavatars.py:497-499).  The degree is a launch argument of the captured kernels: the step
@@ -303,17 +192,6 @@ class RiggedStep(TrainStep):
     #      under no_grad between step() calls, optimizer state through FusedAdam.remap_rows / zero_field_moments, the graph
     #      dropped when the buffers move, host_steps untouched
     @torch.no_grad()
-    def _after_resize(self, old_index, old_rows, stats=None):
-        """`stats`: the (xyz_gradient_accum, denom) the new rows continue with; None: they restart from zero."""
-        pc = self.pc
-        self.adam.remap_rows(pc.flat, pc.flat_grad, old_index, pc.widths(), old_rows)
-        acc, den = stats if stats is not None else (None, None)
-        self.xyz_gradient_accum = acc if acc is not None else torch.zeros((pc.P, 1), device=self.dev)
-        self.denom = den if den is not None else torch.zeros((pc.P, 1), device=self.dev)
-        self.adam.set_skip_words([pc.overflow_word])
-        self._graph, self._eager_steps = None, 0   # buffers moved: the captured step is stale
-
-    @torch.no_grad()
     def _append(self, rows, binding) -> int:
         """Appends `rows` (FIELDS order) bound to `binding`; counts them into binding_counter (:313-315, :374-377); the
         statistics restart from zero whether or not anything was appended (_densification_postfix always runs, :462-475)."""
@@ -326,7 +204,7 @@ class RiggedStep(TrainStep):
         self.binding_counter += torch.bincount(binding.long(), minlength=self.n_faces).to(torch.int32)
         old_rows = pc.P
         old_index = pc.resize(new_rows=rows, new_binding=binding)
-        self._after_resize(old_index, old_rows)
+        self._buffers_moved(old_index, old_rows, stats=None)
         return n
 
     @torch.no_grad()
@@ -350,7 +228,7 @@ class RiggedStep(TrainStep):
         stats = (self.xyz_gradient_accum[keep].contiguous(), self.denom[keep].contiguous())
         old_rows = pc.P
         old_index = pc.resize(keep_mask=keep)
-        self._after_resize(old_index, old_rows, stats)
+        self._buffers_moved(old_index, old_rows, stats=stats)
         return n
 
     @torch.no_grad()
@@ -412,16 +290,6 @@ class RiggedStep(TrainStep):
     def densify_by_gradient(self, *a, **k):
         raise NotImplementedError("RiggedStep: the rigged set densifies with densify_and_prune() (GaussianAvatars' clone / split)")
 
-    @torch.no_grad()
-    def reset_opacity(self) -> None:
-        """_reset_opacity (gaussianavatars.py:477-495): opacity <- inverse_sigmoid(min(sigmoid(opacity), 0.01)), its Adam
-        moments <- 0, IN PLACE: the captured graph keeps pointing at the same parameter and moment buffers."""
-        pc = self.pc
-        cur = torch.sigmoid(pc._opacity)
-        new = torch.minimum(cur, torch.full_like(cur, 0.01))
-        pc._opacity.data.copy_(torch.log(new / (1 - new)))
-        self.adam.zero_field_moments(pc.widths(), pc.P, fields=(1,))
-
     # ---- checkpoints: 'model' holds what GaussianAvatars.state_dict() holds of the Gaussians (the six parameters and the
     #      `binding` buffer); 'optimizer', 'densification' and 'active_sh_degree' are what a seamless resume needs on top
     GAUSSIAN_ATTRIBUTES = ["_xyz", "_opacity", "_features_dc", "_features_rest", "_rotation", "_scaling", "binding"]
@@ -431,9 +299,7 @@ class RiggedStep(TrainStep):
         model = {name: getattr(pc, name).detach().clone() for name, _ in pc.FIELDS}
         model["binding"] = pc.binding.clone()
         return {"global_step": self.adam.step_count, "model": model, "active_sh_degree": int(pc.active_sh_degree),
-                "optimizer": {"exp_avg": self.adam.exp_avg.clone(), "exp_avg_sq": self.adam.exp_avg_sq.clone(),
-                              "state": self.adam.state_words()},
-                "densification": {"xyz_gradient_accum": self.xyz_gradient_accum.clone(), "denom": self.denom.clone()}}
+                **self._training_state()}
 
     @torch.no_grad()
     def load_state_dict(self, sd: dict) -> list:
@@ -450,17 +316,7 @@ class RiggedStep(TrainStep):
         pc._bind([g[name].to(self.dev, torch.float32).reshape((P,) + pc.SHAPES[name]) for name, _ in pc.FIELDS])
         pc.active_sh_degree = int(sd.get("active_sh_degree", pc.active_sh_degree))
         self._count_binding()
-        self._make_adam()                                  # fresh (zero) moments over the new buffers
-        self._graph, self._eager_steps = None, 0           # buffers moved: the captured step is stale
-        self.xyz_gradient_accum = torch.zeros((P, 1), device=self.dev)
-        self.denom = torch.zeros((P, 1), device=self.dev)
-        opt, dens = sd.get("optimizer"), sd.get("densification")
-        if opt is not None:
-            self.adam.exp_avg.copy_(opt["exp_avg"])
-            self.adam.exp_avg_sq.copy_(opt["exp_avg_sq"])
-            self.adam.load_state_words(opt["state"])
-        self.host_steps = self.adam.step_count
-        if dens is not None:
-            self.xyz_gradient_accum.copy_(dens["xyz_gradient_accum"])
-            self.denom.copy_(dens["denom"])
+        # FRESH, not remapped: a checkpoint without an `optimizer` entry starts the optimizer over, step count 0
+        self._buffers_moved(None, None, stats=None)
+        self._load_training_state(sd)
         return sorted(model.keys())

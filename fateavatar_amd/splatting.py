@@ -33,13 +33,11 @@ import torch
 
 from .binding import PhongCanonical, bind_gaussians_phong, phong_canonical, phong_frame
 from .bound import PhongBinding, render_bound_batch
+from .flat import FlatParams
 from .gs_utils import RGB2SH
-from .loss import l1_workspace
 from .model import TorchCamera
-from .optim import FusedAdam
-from .rasterizer import GradOut
 from .render import render
-from .train import TrainStep
+from .train import BoundStep
 
 # config/splattingavatar.yaml:26-30 (group names of train/optim.py:106-117)
 SPLATTING_LRS = dict(uvd=0.00016, opacity=0.05, feature_dc=0.0025, feature_rest=0.0025 / 20, rotation=0.001, scaling=0.005)
@@ -59,7 +57,7 @@ def sample_bary_on_triangles(num_faces: int, num_samples: int, generator: Option
     return fidxs, torch.gather(bary, dim=-1, index=indices)
 
 
-class SplattingGaussians(torch.nn.Module):
+class SplattingGaussians(FlatParams):
     """SplattingAvatar's Gaussian parameters in ONE flat buffer, in the order of the optimizer groups (train/optim.py:106-117).
     `face_index` [P] / `bary_coords` [P,3] are every Gaussian's embedding (`sample_fidxs`, `sample_bary`); they stay fixed
     (no triangle walk, see the module docstring)."""
@@ -67,6 +65,7 @@ class SplattingGaussians(torch.nn.Module):
     FIELDS = (("_uvd", 3), ("_opacity", 1), ("_features_dc", 3), ("_features_rest", 0), ("_rotation", 4), ("_scaling", 3))
     SHAPES = {"_uvd": (3,), "_opacity": (1,), "_features_dc": (1, 3), "_features_rest": (0, 3), "_rotation": (4,),
               "_scaling": (3,)}
+    ROW_BUFFERS = (("face_index", torch.int32, "new_face_index"), ("bary_coords", torch.float32, "new_bary"))
     fused_activations = True
 
     def __init__(self, face_index, bary_coords, log_scale, device):
@@ -101,53 +100,9 @@ class SplattingGaussians(torch.nn.Module):
         return cls(fidxs, bary, torch.log(torch.sqrt(dist2)), dev)
 
     @property
-    def P(self) -> int:
-        return int(self.face_index.shape[0])
-
-    def widths(self):
-        return [w for _, w in self.FIELDS]
-
-    def _bind(self, raw):
-        P, dev = raw[0].shape[0], raw[0].device
-        sizes = [P * w for _, w in self.FIELDS]
-        self.flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-        # (gradient buffer + the step's overflow word behind it: model.FlatGaussians._bind)
-        self._grad_store = torch.zeros(sum(sizes) + 4, dtype=torch.float32, device=dev)
-        self.flat_grad = self._grad_store[:sum(sizes)]
-        self.overflow_word = self._grad_store[sum(sizes):sum(sizes) + 1]
-        off = 0
-        for (name, w), n, r in zip(self.FIELDS, sizes, raw):
-            shp = (P,) + self.SHAPES[name]
-            self.flat[off:off + n].copy_(r.detach().reshape(-1))
-            p = torch.nn.Parameter(self.flat[off:off + n].view(shp))
-            p._fr_grad_out = GradOut(self.flat_grad[off:off + n].view(shp))   # (see AvatarGaussians._bind)
-            setattr(self, name, p)
-            off += n
-
-    @property
     def get_features(self) -> torch.Tensor:
         """[P,1,3]: GaussianModel.get_features (volume_rendering/gaussian_model.py:119-122) at SH degree 0."""
         return torch.cat((self._features_dc, self._features_rest), dim=1)
-
-    def begin_step(self):
-        for name, _ in self.FIELDS:
-            getattr(self, name).grad = None
-
-    def collect_grads(self) -> torch.Tensor:
-        """Every parameter's gradient in the flat gradient buffer (most are written there by the kernels already; the SH
-        block comes back from autograd's split of the concatenation)."""
-        off = 0
-        for name, w in self.FIELDS:
-            n = self.P * w
-            g, view = getattr(self, name).grad, self.flat_grad[off:off + n]
-            if n == 0:
-                continue
-            if g is None:
-                view.zero_()
-            elif g.data_ptr() != view.data_ptr() or not g.is_contiguous():
-                view.view(g.shape).copy_(g)
-            off += n
-        return self.flat_grad
 
 
 class _SplattingFrame:
@@ -164,9 +119,14 @@ class _SplattingFrame:
         self.fused_densification_stats = stats
 
 
-class SplattingStep(TrainStep):
+class SplattingStep(BoundStep):
     """One optimisation step of SplattingAvatar per call: `step(camera, posed_verts, gt_image)` —
-    mesh pass -> bind in the frame -> render -> L1 -> backward -> densification statistics -> Adam."""
+    mesh pass -> bind in the frame -> render -> L1 -> backward -> densification statistics -> Adam.  The optimizer groups are
+    those of train/optim.py:106-117 with config/splattingavatar.yaml:26-30 (`_features_rest` is empty at SH degree 0: its
+    group keeps its place and rate)."""
+    LRS = SPLATTING_LRS
+    LR_KEYS = {"_uvd": "uvd", "_opacity": "opacity", "_features_dc": "feature_dc", "_features_rest": "feature_rest",
+               "_rotation": "rotation", "_scaling": "scaling"}
 
     def __init__(self, pc: SplattingGaussians, canonical: PhongCanonical, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True):
@@ -176,41 +136,10 @@ class SplattingStep(TrainStep):
         `bind_gaussians_phong` op in front of render() (same results; the A/B and the op's own user)."""
         if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise RuntimeError("SplattingStep: data-parallel runs are not built (DESIGN.md)")
-        self.pc, self.bg = pc, bg
-        self.fold_binding = bool(fold_binding)
-        self.dev = pc.flat.device
-        self.world, self.exchange, self.exchange_in_graph = 1, False, False
-        self.lr = dict(SPLATTING_LRS, **(lrs or {}))
-        self.canonical = PhongCanonical(*[t.to(self.dev).contiguous() for t in canonical])
-        self.faces = self.canonical.faces
-        if pc.P and (int(pc.face_index.min()) < 0 or int(pc.face_index.max()) >= int(self.faces.shape[0])):
+        self.canonical = PhongCanonical(*[t.to(pc.flat.device).contiguous() for t in canonical])
+        if pc.P and (int(pc.face_index.min()) < 0 or int(pc.face_index.max()) >= int(self.canonical.faces.shape[0])):
             raise ValueError("SplattingStep: `face_index` names a face the mesh does not have")
-        self._make_adam()
-        self.xyz_gradient_accum = torch.zeros((pc.P, 1), device=self.dev)
-        self.denom = torch.zeros((pc.P, 1), device=self.dev)
-        self.cam = camera
-        self.verts = verts.detach().to(self.dev, torch.float32).clone().contiguous()   # static input of the captured step
-        self.gt = torch.zeros((3, camera.image_height, camera.image_width), device=self.dev)
-        self.loss = torch.zeros((), device=self.dev)
-        self._dimage = torch.zeros_like(self.gt)   # dL/dimage of the step
-        self._l1_ws = l1_workspace(self.dev)
-        self._init_image_loss(None)
-        self.out = None
-        self.use_graph = bool(use_graph)
-        self._graph, self._eager_steps, self.overflows = None, 0, 0
-        self.host_steps = 0      # (TrainStep.skipped_steps)
-
-    def adam_segments(self):
-        """The optimizer groups (train/optim.py:106-117 with config/splattingavatar.yaml:26-30) as runs of the flat buffer
-        (`_features_rest` is empty at SH degree 0: its group keeps its place and rate)."""
-        lr, P = self.lr, self.pc.P
-        return [(P * 3, lr["uvd"]), (P * 1, lr["opacity"]), (P * 3, lr["feature_dc"]), (P * 0, lr["feature_rest"]),
-                (P * 4, lr["rotation"]), (P * 3, lr["scaling"])]
-
-    def _make_adam(self):
-        pc = self.pc
-        self.adam = FusedAdam(pc.flat, pc.flat_grad, self.adam_segments())
-        self.adam.set_skip_words([pc.overflow_word])
+        super().__init__(pc, self.canonical.faces, camera, bg, verts, lrs, use_graph, fold_binding, data_parallel=False)
 
     def _forward_backward(self):
         pc = self.pc
@@ -228,14 +157,7 @@ class SplattingStep(TrainStep):
             out = render(self.cam, _SplattingFrame(pc, stats, bound), self.bg)
         out["render"].backward(self._image_loss_and_grad(out["render"]))   # see TrainStep
         pc.collect_grads()
-        self.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
-
-    def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor) -> torch.Tensor:
-        self._extra_inputs = [(self.verts, posed_verts)]
-        return super().step(camera, gt_image)
-
-    def _load_inputs(self, camera, gt_image, extra=()):
-        super()._load_inputs(camera, gt_image, extra=self._extra_inputs)
+        self.out = self._kept(out)
 
     # ---- SplattingAvatar's density control and opacity reset are out of scope (module docstring)
     def _unsupported(self, *a, **k):
@@ -251,10 +173,7 @@ class SplattingStep(TrainStep):
         pc = self.pc
         model = {name: getattr(pc, name).detach().clone() for name, _ in pc.FIELDS}
         model["sample_fidxs"], model["sample_bary"] = pc.face_index.clone(), pc.bary_coords.clone()
-        return {"global_step": self.adam.step_count, "model": model,
-                "optimizer": {"exp_avg": self.adam.exp_avg.clone(), "exp_avg_sq": self.adam.exp_avg_sq.clone(),
-                              "state": self.adam.state_words()},
-                "densification": {"xyz_gradient_accum": self.xyz_gradient_accum.clone(), "denom": self.denom.clone()}}
+        return {"global_step": self.adam.step_count, "model": model, **self._training_state()}
 
     @torch.no_grad()
     def load_state_dict(self, sd: dict) -> list:
@@ -270,19 +189,9 @@ class SplattingStep(TrainStep):
         pc.bary_coords = g["sample_bary"].to(self.dev, torch.float32).contiguous()
         P = int(pc.face_index.shape[0])
         pc._bind([g[name].to(self.dev, torch.float32).reshape((P,) + pc.SHAPES[name]) for name, _ in pc.FIELDS])
-        self._make_adam()                                  # fresh (zero) moments over the new buffers
-        self._graph, self._eager_steps = None, 0           # buffers moved: the captured step is stale
-        self.xyz_gradient_accum = torch.zeros((P, 1), device=self.dev)
-        self.denom = torch.zeros((P, 1), device=self.dev)
-        opt, dens = sd.get("optimizer"), sd.get("densification")
-        if opt is not None:
-            self.adam.exp_avg.copy_(opt["exp_avg"])
-            self.adam.exp_avg_sq.copy_(opt["exp_avg_sq"])
-            self.adam.load_state_words(opt["state"])
-        self.host_steps = self.adam.step_count
-        if dens is not None:
-            self.xyz_gradient_accum.copy_(dens["xyz_gradient_accum"])
-            self.denom.copy_(dens["denom"])
+        # FRESH, not remapped: a checkpoint without an `optimizer` entry starts the optimizer over, step count 0
+        self._buffers_moved(None, None, stats=None)
+        self._load_training_state(sd)
         return sorted(model.keys())
 
 

@@ -41,29 +41,41 @@ class TrainStep:
             raise ValueError("TrainStep drives the fused path: build FlatGaussians(..., fused_activations=True)")
         self.pc, self.bg = pc, bg
         self.dev = pc.flat.device
-        self.world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
-        # RCCL ("nccl") collectives can be captured into a HIP graph: the whole step — render, backward, all-reduce of
-        # the flat gradient buffer, Adam — is then ONE replay, with no host work between the backward and the update.
-        # (gloo cannot be captured: the CPU tests keep the eager exchange.)
-        self.exchange = torch.distributed.is_initialized() and (self.world > 1 or dp.group_of_one())
-        self.exchange_in_graph = self.exchange and torch.distributed.get_backend() == "nccl"
+        self._init_exchange()
         if use_graph and self.exchange and not self.exchange_in_graph:
             import warnings
             warnings.warn(f"TrainStep: the {torch.distributed.get_backend()} exchange cannot be captured; the all-reduce and Adam "
                           "run eagerly behind the captured frame")
-        lr = dict(DEFAULT_LRS, **(lrs or {}))
-        P, M = pc.P, pc.M
-        self.adam = FusedAdam(pc.flat, pc.flat_grad, [
-            (P * 3, lr["xyz"]),
-            (P * M * 3, lr["feature_dc"], M * 3, 3, lr["feature_rest"]),
-            (P, lr["opacity"]), (P * 3, lr["scaling"]), (P * 4, lr["rotation"])], grad_scale=1.0 / self.world)
+        self.lr = dict(DEFAULT_LRS, **(lrs or {}))
+        self._make_adam()
+        self._init_step_state(camera, use_graph, image_loss)
+
+    def _init_exchange(self, data_parallel: bool = True):
+        self.world = torch.distributed.get_world_size() if data_parallel and torch.distributed.is_initialized() else 1
+        # RCCL ("nccl") collectives can be captured into a HIP graph: the whole step — render, backward, all-reduce of
+        # the flat gradient buffer, Adam — is then ONE replay, with no host work between the backward and the update.
+        # (gloo cannot be captured: the CPU tests keep the eager exchange.)
+        self.exchange = data_parallel and torch.distributed.is_initialized() and (self.world > 1 or dp.group_of_one())
+        self.exchange_in_graph = self.exchange and torch.distributed.get_backend() == "nccl"
+
+    def adam_segments(self):
+        """The optimizer groups (train/optim.py:11-37) as runs of the flat buffer; the SH block is one run, DC at
+        feature_dc, the rest at feature_rest (FusedAdam's 5-tuple form)."""
+        lr, P, M = self.lr, self.pc.P, self.pc.M
+        return [(P * 3, lr["xyz"]), (P * M * 3, lr["feature_dc"], M * 3, 3, lr["feature_rest"]),
+                (P, lr["opacity"]), (P * 3, lr["scaling"]), (P * 4, lr["rotation"])]
+
+    def _make_adam(self):
+        """A FRESH optimizer over the holder's present buffers: zero moments, step count 0."""
+        pc = self.pc
+        self.adam = FusedAdam(pc.flat, pc.flat_grad, self.adam_segments(), grad_scale=1.0 / self.world)
         # a replayed frame that overflowed its binning capacity back-propagates zeros: the rasterizer's backward says so in
         # the word behind the gradient buffer (summed over ranks by the same all-reduce) and the update skips that step
         self.adam.set_skip_words([pc.overflow_word])
-        # _add_densification_stats accumulators (model/fateavatar.py:186-188,734-737), updated by the backward kernel
-        self.xyz_gradient_accum = torch.zeros((P, 1), device=self.dev)
-        self.denom = torch.zeros((P, 1), device=self.dev)
-        pc.fused_densification_stats = (self.xyz_gradient_accum, self.denom, pc.overflow_word)
+
+    def _init_step_state(self, camera: TorchCamera, use_graph: bool, image_loss: Optional[ImageLoss] = None):
+        """Everything the captured step reads and writes besides the parameters, and the bookkeeping of the capture."""
+        self._set_stats(None)
         # static inputs of the captured step
         self.cam = camera
         self.gt = torch.zeros((3, camera.image_height, camera.image_width), device=self.dev)
@@ -77,6 +89,17 @@ class TrainStep:
         self._eager_steps = 0
         self.overflows = 0       # replayed frames that overflowed the captured binning capacity (see _poll_overflow)
         self.host_steps = 0      # step() calls; the device's own count of APPLIED updates is adam.step_count (skipped_steps)
+
+    STATS_ON_HOLDER = True       # render() reads the statistics' buffers from the holder (a bound frame carries its own)
+
+    def _set_stats(self, stats):
+        """The _add_densification_stats accumulators (model/fateavatar.py:186-188,734-737), updated by the backward kernel:
+        `stats` = the (xyz_gradient_accum, denom) to go on with, or None: they restart from zero."""
+        if stats is None:
+            stats = (torch.zeros((self.pc.P, 1), device=self.dev), torch.zeros((self.pc.P, 1), device=self.dev))
+        self.xyz_gradient_accum, self.denom = stats
+        if self.STATS_ON_HOLDER:
+            self.pc.fused_densification_stats = (self.xyz_gradient_accum, self.denom, self.pc.overflow_word)
 
     def _init_image_loss(self, image_loss):
         """The step's L1 + D-SSIM buffers (after self.gt / self.loss exist): `loss` becomes a view of loss_terms[0]."""
@@ -104,9 +127,13 @@ class TrainStep:
         out = render(self.cam, self.pc, self.bg)               # activations + rasterizer (fused)
         # the image term and its gradient (_image_loss_and_grad), then the rasterizer backward (stats fused)
         out["render"].backward(self._image_loss_and_grad(out["render"]))
-        # keep the step's outputs WITHOUT their autograd graph: a graph kept alive across steps keeps its
-        # AccumulateGrad nodes (and the stream they were created on) alive, which breaks a later stream capture
-        self.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
+        self.out = self._kept(out)
+
+    @staticmethod
+    def _kept(out: dict) -> dict:
+        """The step's outputs WITHOUT their autograd graph: a graph kept alive across steps keeps its AccumulateGrad nodes
+        (and the stream they were created on) alive, which breaks a later stream capture."""
+        return {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
 
     def _exchange_and_update(self):
         dp.allreduce_sum_(self.pc.exchange_buffer())  # gradients + overflow word; Adam applies grad_scale = 1 / world
@@ -141,10 +168,11 @@ class TrainStep:
             torch.cuda.synchronize()
         self._graph = g
 
-    def step(self, camera: TorchCamera, gt_image: torch.Tensor) -> torch.Tensor:
-        """One optimisation step on this rank's frame.  Returns the (device) loss scalar of the step."""
+    def step(self, camera: TorchCamera, gt_image: torch.Tensor, _extra=()) -> torch.Tensor:
+        """One optimisation step on this rank's frame.  Returns the (device) loss scalar of the step.  (`_extra`: further
+        (static buffer, value) pairs a subclass loads with the frame's inputs.)"""
         self.host_steps += 1
-        self._load_inputs(camera, gt_image)
+        self._load_inputs(camera, gt_image, _extra)
         if self.use_graph and self._graph is None and self._eager_steps >= 2:
             self._capture()
         if self._graph is not None:
@@ -201,14 +229,18 @@ class TrainStep:
     # -- Gaussian maintenance (reference: train/iteration.py:62-86 -> model/fateavatar.py:610-731), generic-3DGS flavour:
     #    the FateAvatar versions additionally carry the mesh binding (face index, barycentrics) of every row
     @torch.no_grad()
-    def _after_resize(self, old_index, old_rows, zero_fields=()):
+    def _buffers_moved(self, old_index, old_rows, *, stats):
+        """After the holder rebuilt its buffers (resize, _bind): re-attach the optimizer, point the update at the new
+        overflow word and drop the captured step.  `old_index`: the row map the moments follow (FusedAdam.remap_rows: rows
+        mapped to -1 start with zero moments, the step count is KEPT) — or None for a FRESH optimizer (`_make_adam`: zero
+        moments, step count 0).  `stats`: see `_set_stats` — the caller says whether the statistics restart or are carried."""
         pc = self.pc
-        self.adam.remap_rows(pc.flat, pc.flat_grad, old_index, pc.widths(), old_rows, zero_fields)
-        # statistics restart from zero after a change of the point set (model/fateavatar.py:667-672)
-        self.xyz_gradient_accum = torch.zeros((pc.P, 1), device=self.dev)
-        self.denom = torch.zeros((pc.P, 1), device=self.dev)
-        pc.fused_densification_stats = (self.xyz_gradient_accum, self.denom, pc.overflow_word)
-        self.adam.set_skip_words([pc.overflow_word])
+        if old_index is None:
+            self._make_adam()
+        else:
+            self.adam.remap_rows(pc.flat, pc.flat_grad, old_index, pc.widths(), old_rows)
+            self.adam.set_skip_words([pc.overflow_word])
+        self._set_stats(stats)
         self._graph, self._eager_steps = None, 0   # buffers moved: the captured step is stale
 
     @torch.no_grad()
@@ -218,7 +250,8 @@ class TrainStep:
         keep = ~(torch.sigmoid(pc._opacity) < min_opacity).reshape(-1)
         old_rows = pc.P
         old_index = pc.resize(keep_mask=keep)
-        self._after_resize(old_index, old_rows)
+        # statistics restart from zero after a change of the point set (model/fateavatar.py:667-672)
+        self._buffers_moved(old_index, old_rows, stats=None)
         return old_rows - pc.P
 
     @torch.no_grad()
@@ -238,10 +271,11 @@ class TrainStep:
             idx = torch.multinomial(w, increase_num, replacement=True, generator=generator)   # (`generator`: rank 0's only)
         dp.broadcast_(idx)
         rows = [getattr(pc, name).detach()[idx].clone() for name, _ in pc.FIELDS]
-        rows[3] = torch.log(torch.exp(rows[3]) * 0.75)   # _scaling
+        i = self._field_index("_scaling")
+        rows[i] = torch.log(torch.exp(rows[i]) * 0.75)
         old_rows = pc.P
         old_index = pc.resize(new_rows=rows)
-        self._after_resize(old_index, old_rows)
+        self._buffers_moved(old_index, old_rows, stats=None)
         return idx
 
     @torch.no_grad()
@@ -252,7 +286,10 @@ class TrainStep:
         new = torch.minimum(cur, torch.full_like(cur, 0.01))
         pc._opacity.data.copy_(torch.log(new / (1 - new)))
         # in place: the captured graph keeps pointing at the same parameter and moment buffers
-        self.adam.zero_field_moments(pc.widths(), pc.P, fields=(2,))
+        self.adam.zero_field_moments(pc.widths(), pc.P, fields=(self._field_index("_opacity"),))
+
+    def _field_index(self, name: str) -> int:
+        return [n for n, _ in self.pc.FIELDS].index(name)
 
     # -- checkpoint / resume (reference layout: Trainer.save_checkpoint, train/trainer.py:396-435 — a dict with
     #    'global_step' and 'model' = the Gaussian parameters under the GaussianModel names and shapes; the reference
@@ -264,10 +301,27 @@ class TrainStep:
         model = {"_xyz": pc._xyz.detach().clone(), "_features_dc": f[:, :1, :].clone(), "_features_rest": f[:, 1:, :].clone(),
                  "_opacity": pc._opacity.detach().clone(), "_scaling": pc._scaling.detach().clone(),
                  "_rotation": pc._rotation.detach().clone()}
-        return {"global_step": self.adam.step_count, "model": model,
-                "optimizer": {"exp_avg": self.adam.exp_avg.clone(), "exp_avg_sq": self.adam.exp_avg_sq.clone(),
+        return {"global_step": self.adam.step_count, "model": model, **self._training_state()}
+
+    def _training_state(self) -> dict:
+        """The `optimizer` and `densification` entries of a checkpoint."""
+        return {"optimizer": {"exp_avg": self.adam.exp_avg.clone(), "exp_avg_sq": self.adam.exp_avg_sq.clone(),
                               "state": self.adam.state_words()},
                 "densification": {"xyz_gradient_accum": self.xyz_gradient_accum.clone(), "denom": self.denom.clone()}}
+
+    @torch.no_grad()
+    def _load_training_state(self, sd: dict) -> None:
+        """Restores what `_training_state` wrote, after `_buffers_moved(.., stats=None)` re-attached the optimizer: an entry
+        the checkpoint lacks leaves what that call made (zero moments and zero statistics; the step count as it chose)."""
+        opt, dens = sd.get("optimizer"), sd.get("densification")
+        if opt is not None:
+            self.adam.exp_avg.copy_(opt["exp_avg"])
+            self.adam.exp_avg_sq.copy_(opt["exp_avg_sq"])
+            self.adam.load_state_words(opt["state"])
+        self.host_steps = self.adam.step_count          # (skipped_steps counts from the restored state on)
+        if dens is not None:
+            self.xyz_gradient_accum.copy_(dens["xyz_gradient_accum"])
+            self.denom.copy_(dens["denom"])
 
     @torch.no_grad()
     def load_state_dict(self, sd: dict) -> None:
@@ -278,18 +332,9 @@ class TrainStep:
             raise ValueError("checkpoint holds a different number of SH coefficients")
         old_rows = pc.P
         pc._bind([r.to(self.dev, torch.float32) for r in rows])
-        # rebind the optimizer to the new buffers (row map irrelevant: every moment is overwritten below)
-        self._after_resize(torch.full((pc.P,), -1, dtype=torch.int64, device=self.dev), old_rows)
-        opt = sd.get("optimizer")
-        if opt is not None:
-            self.adam.exp_avg.copy_(opt["exp_avg"])
-            self.adam.exp_avg_sq.copy_(opt["exp_avg_sq"])
-            self.adam.load_state_words(opt["state"])
-        self.host_steps = self.adam.step_count          # (skipped_steps counts from the restored state on)
-        dens = sd.get("densification")
-        if dens is not None:
-            self.xyz_gradient_accum.copy_(dens["xyz_gradient_accum"])
-            self.denom.copy_(dens["denom"])
+        # REMAPPED, not fresh: a checkpoint without an `optimizer` entry goes on from this step's count with zero moments
+        self._buffers_moved(torch.full((pc.P,), -1, dtype=torch.int64, device=self.dev), old_rows, stats=None)
+        self._load_training_state(sd)
 
     def check(self) -> None:
         """After synchronising: raise if a captured (no-wait) frame overflowed its binning capacity."""
@@ -304,3 +349,36 @@ class TrainStep:
             dp.allreduce_sum_(acc)
             dp.allreduce_sum_(den)
         return acc, den
+
+
+class BoundStep(TrainStep):
+    """What the steps of the mesh-bound models share on top of TrainStep: `step(camera, posed_verts, gt_image)` — the posed
+    vertices are one more static input of the captured step —, the choice between the binding folded into the rasterizer's
+    per-Gaussian kernels and the stand-alone binding op, and one Adam group per field of the holder.  A subclass names its
+    rates (`LRS`, `LR_KEYS`) and writes `_forward_backward`."""
+    LRS: dict = {}            # the model's learning rates by the reference's group names
+    LR_KEYS: dict = {}        # field of the holder -> its key in LRS
+    STATS_ON_HOLDER = False   # every frame carries the statistics' buffers itself
+
+    def __init__(self, pc, faces: torch.Tensor, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
+                 lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True,
+                 image_loss: Optional[ImageLoss] = None, data_parallel: bool = True):
+        """`verts` [V,3]: any pose of the mesh (sizes the step's static vertex buffer and is its first content)."""
+        self.pc, self.bg = pc, bg
+        self.fold_binding = bool(fold_binding)
+        self.dev = pc.flat.device
+        self._init_exchange(data_parallel)
+        self.lr = dict(self.LRS, **(lrs or {}))
+        self.faces = faces.to(self.dev, torch.int32).contiguous()
+        self._make_adam()
+        self.verts = verts.detach().to(self.dev, torch.float32).clone().contiguous()   # static input of the captured step
+        self._init_step_state(camera, use_graph, image_loss)
+
+    def adam_segments(self):
+        """The optimizer groups (train/optim.py, one per parameter in the holder's order) as runs of the flat buffer; an
+        empty field keeps its place and rate."""
+        P = self.pc.P
+        return [(P * w, self.lr[self.LR_KEYS[name]]) for name, w in self.pc.FIELDS]
+
+    def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor) -> torch.Tensor:
+        return super().step(camera, gt_image, [(self.verts, posed_verts)])
