@@ -532,18 +532,25 @@ __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
 
 // The frame's camera (view 4x4, projection 4x4, position) as wave-uniform values: every lane fetches ONE of the 35
-// floats (one memory round trip, issued together with the kernel's other input loads) and v_readlane broadcasts
-// them to scalar registers.  Reading the matrices through their pointers instead cost the per-Gaussian kernels a
-// dependent global load (= a serialised round trip) at every use.
+// floats and v_readlane broadcasts them to scalar registers.  Reading the matrices through their pointers instead cost
+// the per-Gaussian kernels a dependent global load (= a serialised round trip) at every use.
+// The fetch is ONE load instruction for the wave: each lane selects its ADDRESS (view + lane, proj + lane - 16,
+// campos + lane - 32) and lanes 0..34 load from it.  (As three loads in three divergent branches that wrote one register
+// the compiler waited for each before it issued the next: three round trips.)  camera_request issues the load,
+// camera_broadcast is its first use: a kernel puts its other input loads between the two (or in front of both) so that
+// the wait in front of the broadcast covers all of them.
 struct CameraRegs {
     float view[16], proj[16], campos[3];
 };
-__device__ __forceinline__ CameraRegs load_camera(const float* view, const float* proj, const float* campos, int lane)
+__device__ __forceinline__ float camera_request(const float* view, const float* proj, const float* campos, int lane)
 {
+    const float* p = lane < 16 ? view + lane : (lane < 32 ? proj + (lane - 16) : campos + (lane - 32));
     float x = 0.f;
-    if (lane < 16) x = view[lane];
-    else if (lane < 32) x = proj[lane - 16];
-    else if (lane < 35) x = campos[lane - 32];
+    if (lane < 35) x = *p;   // (lanes 35..63 hold an address past campos and do not load)
+    return x;
+}
+__device__ __forceinline__ CameraRegs camera_broadcast(float x)
+{
     const int xi = __float_as_int(x);
     CameraRegs c;
 #pragma unroll
@@ -554,6 +561,10 @@ __device__ __forceinline__ CameraRegs load_camera(const float* view, const float
 #pragma unroll
     for (int k = 0; k < 3; k++) c.campos[k] = __int_as_float(__builtin_amdgcn_readlane(xi, 32 + k));
     return c;
+}
+__device__ __forceinline__ CameraRegs load_camera(const float* view, const float* proj, const float* campos, int lane)
+{
+    return camera_broadcast(camera_request(view, proj, campos, lane));
 }
 
 // reference auxiliary.h:58-77 — matrices are indexed column-major

@@ -227,9 +227,11 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
     if ((int)(blockIdx.x * kPreWG) >= a.P) return;   // (a batched launch's grid is the largest view's; P > 0: block 0 stays)
     const int M3 = a.M * 3;
     PRE_TR_DECL;
-    // every input of this thread is requested up front (camera, mean, scale, rotation, opacity — and the SH block
-    // below), so that the kernel pays one memory round trip for its inputs instead of one per use
-    const CameraRegs cam = load_camera(a.view, a.proj, a.campos, lane);
+    // every input of this thread is requested up front (camera, mean, scale, rotation, opacity), so that the kernel pays
+    // one memory round trip for them instead of one per use; the SH block's copy goes out right behind them and lands
+    // under the geometry.  The camera is only REQUESTED here: its broadcast, the first use of a loaded value, comes behind
+    // the thread's other requests (fr_common.hpp)
+    const float cam_x = camera_request(a.view, a.proj, a.campos, lane);
     const bool live = idx < a.P;
     const int li = live ? idx : 0;
     float3 p_orig;
@@ -259,6 +261,11 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
     // (requested with the other inputs: a load issued behind the counting atomics would come back behind them)
     float in_col[3] = {0.f, 0.f, 0.f};
     if (a.colors_precomp) in_col[0] = a.colors_precomp[3 * li], in_col[1] = a.colors_precomp[3 * li + 1], in_col[2] = a.colors_precomp[3 * li + 2];
+    // (the camera was requested first and loads come back in order: this waits for the camera alone, with the thread's
+    // inputs in flight right behind it.  In front of the SH block's copy, not behind it: the compiler does not count the
+    // copy's pieces, so a counted wait behind them would also wait for most of the block, and the geometry below would no
+    // longer run while the block arrives.)
+    const CameraRegs cam = camera_broadcast(cam_x);
     // one LDS region per wave: the SH rows of its Gaussians, then the tables of its counting pass —
     // nothing in it is shared between waves, so the kernel needs no workgroup barrier for it
     float* const wave_lds = s_sh + (size_t)wave * (pre_wave_lds_bytes(M3) / 4);   // (launch_forward sizes it the same way)

@@ -55,18 +55,119 @@ __device__ __forceinline__ void store3(float* p, size_t i, float a, float b, flo
     p[3 * i] = a, p[3 * i + 1] = b, p[3 * i + 2] = c;
 }
 
-// Everything for ONE Gaussian.  `row` (LDS, may be null) receives this Gaussian's dL_dsh row (the kernel writes the rows
-// of a wave through LDS for coalesced HBM access).  PLANES (a backward with a depth gradient, FR_FLAG_DEPTH_ALPHA): the
+// Row stride (floats) of a wave's [64][M3] block of dL_dsh rows in LDS.  M3 a multiple of 4 (M = 4, 16): the rows are
+// written and read in 16-byte pieces, so the stride is a multiple of 4 — and stride / 4 is odd: a lane's ds_write_b128 goes
+// to bank (stride * lane + 4 k) mod 32, and over the 8 consecutive lanes that share an LDS cycle an odd stride / 4 gives 8
+// different 4-bank slots (52 floats at M3 = 48: 20 * lane mod 32 = 0, 20, 8, 28, 16, 4, 24, 12).  unstage_rows reads consecutive
+// 16-byte pieces, one row's 12 behind the other: a 16-lane group of its ds_read_b128 crosses at most two 4-word row gaps,
+// so at most one slot of the 64-bank row is asked twice (5 LDS cycles instead of 4); at M3 = 12 the stride IS the row
+// length and the reads are contiguous.  Other row lengths (M = 1, 9) go word by word with an odd stride.
+__host__ __device__ constexpr bool prebwd_rows_by16(int M3) { return M3 % 4 == 0 && M3 <= 48; }
+__host__ __device__ constexpr int prebwd_row_stride(int M3)
+{
+    return prebwd_rows_by16(M3) ? (((M3 / 4) & 1) ? M3 : M3 + 4) : (M3 | 1);
+}
+
+// What k_preprocess_bwd reads for ONE Gaussian, all of it requested by preprocess_bwd_fetch before anything is used or
+// stored: the kernel pays one memory round trip for its inputs.  (Read where they are used, the inputs cost a wave seven
+// dependent round trips: nothing here is __restrict__, so no load could move up over the stores in front of it, and on
+// gfx9 an s_waitcnt vmcnt counts the stores, too.)
+struct PreBwdIn {
+    int radius;
+    float mean[3], q[4], sc[3], c3[6];   // q / sc: with `scales`;  c3: with `cov3D_precomp`
+    float opacity;
+    uint32_t cl;                         // with `shs`: clamped bits, d colour / d direction
+    float dd[9];
+    float4 r0, r1, r2;                   // the accumulator row
+    uint32_t overflow;                   // DeviceCounts::overflow of the frame (wave-uniform)
+    float ga, dn;                        // grad_accum / denom, where the call has them
+    float old_m3[3], old_sc[3], old_q[4], old_op;   // accumulating arrays: what they hold
+};
+
+// (a pointer that went through an asm operand has lost its address space: named again, or every load through it is a FLAT one)
+template <class T> using GlobalPtr = const __attribute__((address_space(1))) T*;
+template <class T> __device__ __forceinline__ GlobalPtr<T> as_global(const T* p) { return (GlobalPtr<T>)p; }
+typedef float PreBwdF4 __attribute__((ext_vector_type(4)));
+
+// `li`: the Gaussian's index, clamped to P - 1 for the lanes past the end (they load like everyone and store nothing).
+// Optional inputs are wave-uniform null tests.  The row of a culled Gaussian is loaded like any other: its dcolor_ddir and
+// opacity_act may be scratch the forward never wrote — preprocess_bwd_one uses none of it on that path.
+__device__ __forceinline__ void preprocess_bwd_fetch(const PreBwdArgs& a, const int li, PreBwdIn& in)
+{
+    const size_t i = (size_t)li;
+    const auto adds = [&](int k) { return ((a.acc >> k) & 1u) != 0u; };
+    // the pointers first, all of them before the first request: read where they are used, each was a scalar load of the
+    // kernel-argument block with a wait of its own between two requests
+    const int* radii_ = a.radii;
+    const DeviceCounts* counts_ = a.counts;
+    const float *accum_ = a.g.accum, *means3D_ = a.means3D, *scales_ = a.scales, *rotations_ = a.rotations, *cov3D_ = a.cov3D_precomp;
+    const float *opacity_act_ = a.g.opacity_act, *dcolor_ddir_ = a.g.dcolor_ddir, *shs = a.shs;
+    const uint8_t* clamped_ = a.g.clamped;
+    const float *grad_accum_ = a.grad_accum, *denom_ = a.denom;
+    asm volatile("" : "+s"(radii_), "+s"(counts_), "+s"(accum_), "+s"(means3D_), "+s"(scales_), "+s"(rotations_), "+s"(cov3D_),
+                 "+s"(opacity_act_), "+s"(dcolor_ddir_), "+s"(shs), "+s"(clamped_), "+s"(grad_accum_), "+s"(denom_));
+    const auto radii = as_global(radii_);
+    const auto counts = as_global(counts_);
+    const auto accum = as_global(accum_), means3D = as_global(means3D_), scales = as_global(scales_), rotations = as_global(rotations_);
+    const auto cov3D = as_global(cov3D_), opacity_act = as_global(opacity_act_), dcolor_ddir = as_global(dcolor_ddir_);
+    const auto clamped = as_global(clamped_);
+    const auto grad_accum = as_global(grad_accum_), denom = as_global(denom_);
+    in.radius = radii[li];
+    in.overflow = counts->overflow;
+    const GlobalPtr<PreBwdF4> row4 = (GlobalPtr<PreBwdF4>)(accum + i * kAccumStride);
+    const PreBwdF4 r0 = row4[0], r1 = row4[1], r2 = row4[2];
+    in.r0 = make_float4(r0.x, r0.y, r0.z, r0.w), in.r1 = make_float4(r1.x, r1.y, r1.z, r1.w), in.r2 = make_float4(r2.x, r2.y, r2.z, r2.w);
+    for (int k = 0; k < 3; k++) in.mean[k] = means3D[3 * i + k];
+    for (int k = 0; k < 4; k++) in.q[k] = 0.f;
+    for (int k = 0; k < 3; k++) in.sc[k] = 0.f;
+    for (int k = 0; k < 6; k++) in.c3[k] = 0.f;
+    if (scales) {
+        for (int k = 0; k < 4; k++) in.q[k] = rotations[4 * i + k];
+        for (int k = 0; k < 3; k++) in.sc[k] = scales[3 * i + k];
+    }
+    if (cov3D)
+        for (int k = 0; k < 6; k++) in.c3[k] = cov3D[6 * i + k];
+    in.opacity = opacity_act[li];
+    in.cl = 0u;
+    for (int k = 0; k < 9; k++) in.dd[k] = 0.f;
+    if (shs) {
+        in.cl = clamped[li];
+        for (int k = 0; k < 9; k++) in.dd[k] = dcolor_ddir[i * 9 + k];
+    }
+    in.ga = in.dn = 0.f;
+    if (grad_accum) in.ga = grad_accum[i];
+    if (denom) in.dn = denom[i];
+    for (int k = 0; k < 3; k++) in.old_m3[k] = 0.f, in.old_sc[k] = 0.f;
+    for (int k = 0; k < 4; k++) in.old_q[k] = 0.f;
+    in.old_op = 0.f;
+    if (a.acc) {
+        if (adds(G_MEANS3D) && a.out.dL_dmeans3D)
+            for (int k = 0; k < 3; k++) in.old_m3[k] = a.out.dL_dmeans3D[3 * i + k];
+        if (adds(G_SCALES) && a.out.dL_dscales)
+            for (int k = 0; k < 3; k++) in.old_sc[k] = a.out.dL_dscales[3 * i + k];
+        if (adds(G_ROTATIONS) && a.out.dL_drotations)
+            for (int k = 0; k < 4; k++) in.old_q[k] = a.out.dL_drotations[4 * i + k];
+        if (adds(G_OPACITY) && a.out.dL_dopacity) in.old_op = a.out.dL_dopacity[i];
+    }
+}
+
+// Everything for ONE Gaussian, from what preprocess_bwd_fetch brought: arithmetic and stores, no input load.  `row` (LDS,
+// may be null) receives this Gaussian's dL_dsh row (the kernel writes the rows of a wave through LDS for coalesced HBM
+// access), in 16-byte pieces if `by16`.  PLANES (a backward with a depth gradient, FR_FLAG_DEPTH_ALPHA): the
 // accumulated dL/dz of the view-space depth (ACC_Z) joins dL/dmean3D through z = view[2] x + view[6] y + view[10] z + view[14].
 template <bool PLANES>
-__device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const CameraRegs& cam, const int radius,
-                                                   const int idx, float* row)
+__device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const CameraRegs& cam, const PreBwdIn& in,
+                                                   const int idx, float* row, const bool by16)
 {
     const size_t i = (size_t)idx;
     const int Mc = a.M;
+    const int radius = in.radius;
     const auto adds = [&](int k) { return ((a.acc >> k) & 1u) != 0u; };
     if (!(radius > 0)) {   // no gradient: zeros where the arrays are overwritten, nothing where they accumulate
-        if (row)
+        if (row && by16) {
+            float4* r4 = reinterpret_cast<float4*>(row);
+            for (int k = 0; k < (Mc * 3) / 4; k++) r4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else if (row)
             for (int k = 0; k < Mc * 3; k++) row[k] = 0.f;
         if (!adds(G_MEANS2D)) store3(a.out.dL_dmeans2D, i, 0.f, 0.f, 0.f, false);
         if (!adds(G_COLORS)) store3(a.out.dL_dcolors, i, 0.f, 0.f, 0.f, false);
@@ -82,37 +183,29 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
         if (a.bound) bind_bwd_zero(idx, a.bg);
         return;
     }
-    // accumulating arrays: what they hold is requested NOW, so that the round trip runs under the arithmetic below
-    // (a load next to its store would sit behind the stores in front of it)
-    float old_m3[3] = {0.f, 0.f, 0.f}, old_sc[3] = {0.f, 0.f, 0.f}, old_q[4] = {0.f, 0.f, 0.f, 0.f}, old_op = 0.f;
-    if (a.acc) {
-        if (adds(G_MEANS3D) && a.out.dL_dmeans3D)
-            for (int k = 0; k < 3; k++) old_m3[k] = a.out.dL_dmeans3D[3 * i + k];
-        if (adds(G_SCALES) && a.out.dL_dscales)
-            for (int k = 0; k < 3; k++) old_sc[k] = a.out.dL_dscales[3 * i + k];
-        if (adds(G_ROTATIONS) && a.out.dL_drotations)
-            for (int k = 0; k < 4; k++) old_q[k] = a.out.dL_drotations[4 * i + k];
-        if (adds(G_OPACITY) && a.out.dL_dopacity) old_op = a.out.dL_dopacity[i];
-    }
-    // read the accumulator row and leave it zeroed for the next backward (the rows are zero between backward
-    // passes: no zeroing launch, and no zeroing writes in the forward)
+    // (accumulating arrays: what they hold came with the other inputs — a load next to its store would sit behind the
+    // stores in front of it)
+    const float old_m3[3] = {in.old_m3[0], in.old_m3[1], in.old_m3[2]}, old_sc[3] = {in.old_sc[0], in.old_sc[1], in.old_sc[2]};
+    const float old_q[4] = {in.old_q[0], in.old_q[1], in.old_q[2], in.old_q[3]}, old_op = in.old_op;
+    // the accumulator row, left zeroed for the next backward (the rows are zero between backward passes: no zeroing
+    // launch, and no zeroing writes in the forward).  These are the kernel's first stores: every input load is in front of them
     float acc[12];
     {
         float4* row4 = reinterpret_cast<float4*>(a.g.accum + i * kAccumStride);
-        const float4 r0 = row4[0], r1 = row4[1], r2 = row4[2];
+        const float4 r0 = in.r0, r1 = in.r1, r2 = in.r2;
         row4[0] = row4[1] = row4[2] = make_float4(0.f, 0.f, 0.f, 0.f);
         acc[0] = r0.x, acc[1] = r0.y, acc[2] = r0.z, acc[3] = r0.w, acc[4] = r1.x, acc[5] = r1.y, acc[6] = r1.z,
         acc[7] = r1.w, acc[8] = r2.x, acc[9] = r2.y, acc[10] = r2.z, acc[11] = r2.w;
     }
-    const float3 mean = make_float3(a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]);
+    const float3 mean = make_float3(in.mean[0], in.mean[1], in.mean[2]);
     const float* vm = cam.view;
     // Sigma3D: the caller's, or computed again from the scales and rotations (the same function and bits as the forward)
     float q_r = 0.f, q_x = 0.f, q_y = 0.f, q_z = 0.f, rot_inv = 1.0f;
     float sc[3] = {0.f, 0.f, 0.f};
     float c3[6];
     if (a.scales) {
-        q_r = a.rotations[4 * idx], q_x = a.rotations[4 * idx + 1], q_y = a.rotations[4 * idx + 2], q_z = a.rotations[4 * idx + 3];
-        sc[0] = a.scales[3 * idx], sc[1] = a.scales[3 * idx + 1], sc[2] = a.scales[3 * idx + 2];
+        q_r = in.q[0], q_x = in.q[1], q_y = in.q[2], q_z = in.q[3];
+        sc[0] = in.sc[0], sc[1] = in.sc[1], sc[2] = in.sc[2];
         if (a.raw) {
             sc[0] = act_exp(sc[0]), sc[1] = act_exp(sc[1]), sc[2] = act_exp(sc[2]);
             rot_inv = act_rot_inv_norm(q_r, q_x, q_y, q_z);
@@ -120,7 +213,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
         }
     }
     if (a.cov3D_precomp) {
-        for (int k = 0; k < 6; k++) c3[k] = a.cov3D_precomp[6 * i + k];
+        for (int k = 0; k < 6; k++) c3[k] = in.c3[k];
     } else {
         cov3d_from_scale_rot(sc[0], sc[1], sc[2], q_r, q_x, q_y, q_z, a.scale_modifier, c3);
     }
@@ -159,7 +252,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
     // The conic is not read back: it is the inverse of the 2D covariance this kernel has just computed again, with the
     // forward's expressions (forward.cu:74-113, 207-219) — the same bits; only the activated opacity comes from the state.
     const float det_inv = 1.f / denom;
-    const float4 co = make_float4(cc * det_inv, -cb * det_inv, ca * det_inv, a.g.opacity_act[idx]);
+    const float4 co = make_float4(cc * det_inv, -cb * det_inv, ca * det_inv, in.opacity);
     // (ACC_MX / ACC_MY arrive combined with the conic per pixel: sum of q * dG/d(centre) / G, fr_common.hpp)
     const float g2x = acc[ACC_MX] * (0.5f * a.W);
     const float g2y = acc[ACC_MY] * (0.5f * a.H);
@@ -169,9 +262,9 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
     store3(a.out.dL_dmeans2D, i, g2x, g2y, 0.f, adds(G_MEANS2D));
     // fused _add_densification_stats (model/fateavatar.py:734-737); this branch is radii > 0
     // (a replayed frame that overflowed its captured binning capacity back-propagates zeros: it must not count as a view)
-    if (!a.counts->overflow) {
-        if (a.grad_accum) a.grad_accum[i] += sqrtf(g2x * g2x + g2y * g2y);
-        if (a.denom) a.denom[i] += 1.0f;
+    if (!in.overflow) {
+        if (a.grad_accum) a.grad_accum[i] = in.ga + sqrtf(g2x * g2x + g2y * g2y);
+        if (a.denom) a.denom[i] = in.dn + 1.0f;
     }
     store3(a.out.dL_dcolors, i, dcol[0], dcol[1], dcol[2], adds(G_COLORS));
     // raw-parameter mode: d sigmoid = o (1 - o); co.w is the activated opacity the forward stored
@@ -236,10 +329,10 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
         const float x = dox / len, y = doy / len, z = doz / len;
         // (the derivative of the colour with respect to the direction comes from the forward, GeomView::dcolor_ddir: this
         // kernel does not read the SH coefficients at all; `row`, if staged, only collects the dL_dsh row)
-        const uint8_t cl = a.g.clamped[idx];
+        const uint32_t cl = in.cl;
         float dRGB[3];
         for (int c = 0; c < 3; c++) dRGB[c] = dcol[c] * (((cl >> c) & 1) ? 0 : 1);
-        const float* dd = a.g.dcolor_ddir + i * 9;
+        const float* dd = in.dd;
         const float dRGBdx[3] = {dd[0], dd[1], dd[2]}, dRGBdy[3] = {dd[3], dd[4], dd[5]}, dRGBdz[3] = {dd[6], dd[7], dd[8]};
         const int deg = a.D;
         const int used = (deg + 1) * (deg + 1);
@@ -279,7 +372,43 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
                 for (int k = used; k < Mc; k++) dsh[k * 3] = 0.f, dsh[k * 3 + 1] = 0.f, dsh[k * 3 + 2] = 0.f;
 #undef DSH
         };
-        if (row) write_row(row, false);                                   // (added to the array by unstage_rows)
+        // The LDS row in 16-byte pieces (M3 a multiple of 4): the same products — the direction factor of coefficient k,
+        // evaluated with write_row's expression, times dRGB[c] — four of them per ds_write_b128 instead of one per store.
+        auto write_row_by16 = [&](float* dsh) {
+            float f[16] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            f[0] = bSH_C0;
+            if (deg > 0) {
+                f[1] = -bSH_C1 * y, f[2] = bSH_C1 * z, f[3] = -bSH_C1 * x;
+                if (deg > 1) {
+                    const float xx = x * x, yy = y * y, zz = z * z;
+                    const float xy = x * y, yz = y * z, xz = x * z;
+                    f[4] = bSH_C2[0] * xy, f[5] = bSH_C2[1] * yz, f[6] = bSH_C2[2] * (2.f * zz - xx - yy);
+                    f[7] = bSH_C2[3] * xz, f[8] = bSH_C2[4] * (xx - yy);
+                    if (deg > 2) {
+                        f[9] = bSH_C3[0] * y * (3.f * xx - yy), f[10] = bSH_C3[1] * xy * z;
+                        f[11] = bSH_C3[2] * y * (4.f * zz - xx - yy), f[12] = bSH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy);
+                        f[13] = bSH_C3[4] * x * (4.f * zz - xx - yy), f[14] = bSH_C3[5] * z * (xx - yy);
+                        f[15] = bSH_C3[6] * x * (xx - 3.f * yy);
+                    }
+                }
+            }
+            float4* d4 = reinterpret_cast<float4*>(dsh);
+            const int pieces = (Mc * 3) / 4;
+#pragma unroll
+            for (int j = 0; j < 12; j++) {
+                if (j >= pieces) break;   // (wave-uniform; rows longer than 48 floats do not exist: M <= 16)
+                float v[4];
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const int k = (4 * j + t) / 3, c = (4 * j + t) % 3;
+                    // (coefficients above the active degree: a literal zero, as write_row stores)
+                    v[t] = k < used ? f[k] * dRGB[c] : 0.f;
+                }
+                d4[j] = make_float4(v[0], v[1], v[2], v[3]);
+            }
+        };
+        if (row && by16) write_row_by16(row);                              // (added to the array by unstage_rows)
+        else if (row) write_row(row, false);
         else if (a.out.dL_dsh) write_row(a.out.dL_dsh + i * Mc * 3, adds(G_SH));
         const float ddx = dRGBdx[0] * dRGB[0] + dRGBdx[1] * dRGB[1] + dRGBdx[2] * dRGB[2];
         const float ddy = dRGBdy[0] * dRGB[0] + dRGBdy[1] * dRGB[1] + dRGBdy[2] * dRGB[2];
@@ -402,11 +531,45 @@ __device__ __forceinline__ void unstage_rows_t(float* __restrict__ dst, const fl
         }
     }
 }
+// The same for rows of whole 16-byte pieces (row_len and stride multiples of 4): a piece never crosses a row, so every
+// 16-byte store is ONE ds_read_b128 behind ONE division (instead of four word reads, four divisions and four selects).
+template <bool ADD>
+__device__ __forceinline__ void unstage_rows_by16_t(float* __restrict__ dst, const float* src, int stride, int rows, int row_len, int lane)
+{
+    const int total = rows * row_len;   // (a multiple of 4)
+    const unsigned magic = (unsigned)((0x100000000ull + (unsigned)row_len - 1u) / (unsigned)row_len);
+    constexpr int kBatch = ADD ? 6 : 1;
+    for (int base = lane * 4; base < total; base += 64 * 4 * kBatch) {
+        float4 o[kBatch];
+        if (ADD) {
+#pragma unroll
+            for (int u = 0; u < kBatch; u++) {
+                const int c = base + u * 64 * 4;
+                o[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (c < total) o[u] = *reinterpret_cast<const float4*>(dst + c);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kBatch; u++) {
+            const int c = base + u * 64 * 4;
+            if (c >= total) break;
+            const int r = (int)__umulhi((unsigned)c, magic);  // c / row_len (exact: c < 2^16)
+            float4 v = *reinterpret_cast<const float4*>(src + r * stride + (c - r * row_len));
+            if (ADD) v.x += o[u].x, v.y += o[u].y, v.z += o[u].z, v.w += o[u].w;
+            *reinterpret_cast<float4*>(dst + c) = v;
+        }
+    }
+}
 __device__ __forceinline__ void unstage_rows(float* __restrict__ dst, const float* src, int stride, int rows, int row_len, int lane,
                                              bool add)
 {
-    if (add) unstage_rows_t<true>(dst, src, stride, rows, row_len, lane);
-    else unstage_rows_t<false>(dst, src, stride, rows, row_len, lane);
+    if (prebwd_rows_by16(row_len)) {
+        if (add) unstage_rows_by16_t<true>(dst, src, stride, rows, row_len, lane);
+        else unstage_rows_by16_t<false>(dst, src, stride, rows, row_len, lane);
+    } else {
+        if (add) unstage_rows_t<true>(dst, src, stride, rows, row_len, lane);
+        else unstage_rows_t<false>(dst, src, stride, rows, row_len, lane);
+    }
 }
 
 #ifndef FR_PREBWD_WAVES
@@ -421,17 +584,26 @@ __device__ __forceinline__ void preprocess_bwd_body(const PreBwdArgs& a)
     if ((int)(blockIdx.x * blockDim.x) >= a.P) return;   // (a batched launch's grid is the largest view's)
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // (fr_aux::overflow_out: the step's optimizer kernel reads it — fr_adam_config::skip)
-    if (a.overflow_out && blockIdx.x == 0 && threadIdx.x == 0) *a.overflow_out = a.counts->overflow ? 1.0f : 0.0f;
-    const int M3 = a.M * 3, stride = M3 | 1;
+    const int M3 = a.M * 3, stride = prebwd_row_stride(M3);
     const int wave_first = blockIdx.x * (64 * kPreBwdWaves) + wave * 64;
     const int rows = min(64, a.P - wave_first);
     const bool staged = a.shs != nullptr && a.out.dL_dsh != nullptr;
     float* w_rows = s_rows + (size_t)wave * 64 * stride;
-    // camera and radius are requested before the SH block is staged: one round trip for all of them
-    const CameraRegs cam = load_camera(a.view, a.proj, a.campos, lane);
-    const int radius = idx < a.P ? a.radii[idx] : 0;
-    if (idx < a.P) preprocess_bwd_one<PLANES>(a, cam, radius, idx, staged ? w_rows + lane * stride : nullptr);
+    // Every input of the thread, then the camera, are requested before anything is used or stored: one round trip for all
+    // of them.  The camera goes LAST: loads come back in order, so the wait in front of its broadcast — the first use of
+    // anything — is the kernel's one wait for its inputs.  (The compiler's barrier: without it the loads that only the
+    // visible Gaussians use sink into their branch, behind the wait for the radius.)
+    PreBwdIn in;
+    preprocess_bwd_fetch(a, min(idx, a.P - 1), in);
+    const float cam_x = camera_request(a.view, a.proj, a.campos, lane);
+    asm volatile("" ::: "memory");
+    const CameraRegs cam = camera_broadcast(cam_x);
+    // (... and the first arithmetic on a loaded value — ~clamped, denom + 1 — is hoisted to its load otherwise, with a wait
+    // of its own in the middle of the requests)
+    asm volatile("" : "+v"(in.cl), "+v"(in.ga), "+v"(in.dn), "+v"(in.opacity), "+v"(in.radius));
+    // (fr_aux::overflow_out: the step's optimizer kernel reads it — fr_adam_config::skip)
+    if (a.overflow_out && blockIdx.x == 0 && threadIdx.x == 0) *a.overflow_out = in.overflow ? 1.0f : 0.0f;
+    if (idx < a.P) preprocess_bwd_one<PLANES>(a, cam, in, idx, staged ? w_rows + lane * stride : nullptr, prebwd_rows_by16(M3));
     __syncthreads();
     if (staged && rows > 0) unstage_rows(a.out.dL_dsh + (size_t)wave_first * M3, w_rows, stride, rows, M3, lane, ((a.acc >> G_SH) & 1u) != 0u);
 }
@@ -501,7 +673,7 @@ int launch_backward(int n, const BackwardCall* calls, hipStream_t s)
             a.bind = BindArgs{};
             a.bg = BindGrads{};
         }
-        const size_t l = (in.shs && calls[k].grads->dL_dsh) ? (size_t)kPreBwdWaves * 64 * ((prm.M * 3) | 1) * sizeof(float) : 0;
+        const size_t l = (in.shs && calls[k].grads->dL_dsh) ? (size_t)kPreBwdWaves * 64 * prebwd_row_stride(prm.M * 3) * sizeof(float) : 0;
         lds = l > lds ? l : lds;
         blocks = max(blocks, (uint32_t)((P + wg - 1) / wg));
     }
