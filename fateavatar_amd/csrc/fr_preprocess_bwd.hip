@@ -55,17 +55,91 @@ __device__ __forceinline__ void store3(float* p, size_t i, float a, float b, flo
     p[3 * i] = a, p[3 * i + 1] = b, p[3 * i + 2] = c;
 }
 
-// Row stride (floats) of a wave's [64][M3] block of dL_dsh rows in LDS.  M3 a multiple of 4 (M = 4, 16): the rows are
+// Rows of a wave's dL_dsh block in LDS on the 16-byte path: the wave's 64 rows go through a [R][stride] block in 64 / R
+// passes of R consecutive Gaussians each (64: one pass, the whole wave's rows at once).  Fewer rows per pass = less LDS per
+// wave = more resident waves per CU; every pass still stores one contiguous run of R rows.
+#ifndef FR_PREBWD_STAGE_ROWS
+#define FR_PREBWD_STAGE_ROWS 32
+#endif
+constexpr int kPreBwdStageRows = FR_PREBWD_STAGE_ROWS;
+static_assert(kPreBwdStageRows == 64 || kPreBwdStageRows == 32 || kPreBwdStageRows == 16, "FR_PREBWD_STAGE_ROWS: 64, 32 or 16");
+
+// Row stride (floats) of a wave's block of dL_dsh rows in LDS.  M3 a multiple of 4 (M = 4, 16): the rows are
 // written and read in 16-byte pieces, so the stride is a multiple of 4 — and stride / 4 is odd: a lane's ds_write_b128 goes
-// to bank (stride * lane + 4 k) mod 32, and over the 8 consecutive lanes that share an LDS cycle an odd stride / 4 gives 8
-// different 4-bank slots (52 floats at M3 = 48: 20 * lane mod 32 = 0, 20, 8, 28, 16, 4, 24, 12).  unstage_rows reads consecutive
-// 16-byte pieces, one row's 12 behind the other: a 16-lane group of its ds_read_b128 crosses at most two 4-word row gaps,
-// so at most one slot of the 64-bank row is asked twice (5 LDS cycles instead of 4); at M3 = 12 the stride IS the row
-// length and the reads are contiguous.  Other row lengths (M = 1, 9) go word by word with an odd stride.
+// to bank (stride * row + 4 k) mod 32, and over the 8 consecutive lanes that share an LDS cycle an odd stride / 4 gives 8
+// different 4-bank slots (52 floats at M3 = 48: 20 * row mod 32 = 0, 20, 8, 28, 16, 4, 24, 12).  A pass's writers are R
+// consecutive lanes on rows 0 .. R - 1, R a multiple of 8: the same residues in every group of 8, whatever R is.
+// unstage_rows reads consecutive 16-byte pieces, one row's 12 behind the other: a 16-lane group of its ds_read_b128
+// crosses at most two 4-word row gaps, so at most one slot of the 64-bank row is asked twice (5 LDS cycles instead of 4) —
+// a property of 16 consecutive pieces, not of how many rows the block has; at M3 = 12 the stride IS the row length and the
+// reads are contiguous.  Other row lengths (M = 1, 9) go word by word with an odd stride, all 64 rows in one block.
 __host__ __device__ constexpr bool prebwd_rows_by16(int M3) { return M3 % 4 == 0 && M3 <= 48; }
 __host__ __device__ constexpr int prebwd_row_stride(int M3)
 {
     return prebwd_rows_by16(M3) ? (((M3 / 4) & 1) ? M3 : M3 + 4) : (M3 | 1);
+}
+// rows of a wave's LDS block
+__host__ __device__ constexpr int prebwd_block_rows(int M3) { return prebwd_rows_by16(M3) ? kPreBwdStageRows : 64; }
+
+// A Gaussian's dL_dsh row on the 16-byte path, kept until its pass: the row is a function of the unit view direction and
+// of dRGB alone, so six floats and a flag stand in for its 48.
+struct PreBwdRow {
+    float x, y, z, dRGB[3];
+    bool visible;   // false: the row is zeros (culled, or past the end)
+};
+
+// The LDS row in 16-byte pieces (M3 a multiple of 4): write_row's products — the direction factor of coefficient k,
+// evaluated with write_row's expression, times dRGB[c] — four of them per ds_write_b128 instead of one per store.
+__device__ __forceinline__ void write_row_by16(float* dsh, const PreBwdRow& r, const int deg, const int Mc)
+{
+    const float x = r.x, y = r.y, z = r.z;
+    const int used = (deg + 1) * (deg + 1);
+    float f[16] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    f[0] = bSH_C0;
+    if (deg > 0) {
+        f[1] = -bSH_C1 * y, f[2] = bSH_C1 * z, f[3] = -bSH_C1 * x;
+        if (deg > 1) {
+            const float xx = x * x, yy = y * y, zz = z * z;
+            const float xy = x * y, yz = y * z, xz = x * z;
+            f[4] = bSH_C2[0] * xy, f[5] = bSH_C2[1] * yz, f[6] = bSH_C2[2] * (2.f * zz - xx - yy);
+            f[7] = bSH_C2[3] * xz, f[8] = bSH_C2[4] * (xx - yy);
+            if (deg > 2) {
+                f[9] = bSH_C3[0] * y * (3.f * xx - yy), f[10] = bSH_C3[1] * xy * z;
+                f[11] = bSH_C3[2] * y * (4.f * zz - xx - yy), f[12] = bSH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy);
+                f[13] = bSH_C3[4] * x * (4.f * zz - xx - yy), f[14] = bSH_C3[5] * z * (xx - yy);
+                f[15] = bSH_C3[6] * x * (xx - 3.f * yy);
+            }
+        }
+    }
+    float4* d4 = reinterpret_cast<float4*>(dsh);
+    const int pieces = (Mc * 3) / 4;
+#pragma unroll
+    for (int j = 0; j < 12; j++) {
+        if (j < pieces) {   // (wave-uniform; rows longer than 48 floats do not exist: M <= 16)
+            float v[4];
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int k = (4 * j + t) / 3, c = (4 * j + t) % 3;
+                // (coefficients above the active degree: a literal zero, as write_row stores)
+                v[t] = k < used ? f[k] * r.dRGB[c] : 0.f;
+            }
+            d4[j] = make_float4(v[0], v[1], v[2], v[3]);
+        }
+    }
+}
+__device__ __forceinline__ void zero_row_by16(float* dsh, const int Mc)
+{
+    float4* d4 = reinterpret_cast<float4*>(dsh);
+    for (int k = 0; k < (Mc * 3) / 4; k++) d4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// Orders a wave's own LDS accesses for the compiler: the hardware executes them in program order, so a lane reads what
+// another lane of its wave wrote in front of this point.  No instruction, no waiting for other waves.
+__device__ __forceinline__ void wave_lds_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // What k_preprocess_bwd reads for ONE Gaussian, all of it requested by preprocess_bwd_fetch before anything is used or
@@ -151,23 +225,21 @@ __device__ __forceinline__ void preprocess_bwd_fetch(const PreBwdArgs& a, const 
     }
 }
 
-// Everything for ONE Gaussian, from what preprocess_bwd_fetch brought: arithmetic and stores, no input load.  `row` (LDS,
-// may be null) receives this Gaussian's dL_dsh row (the kernel writes the rows of a wave through LDS for coalesced HBM
-// access), in 16-byte pieces if `by16`.  PLANES (a backward with a depth gradient, FR_FLAG_DEPTH_ALPHA): the
+// Everything for ONE Gaussian, from what preprocess_bwd_fetch brought: arithmetic and stores, no input load.  The kernel
+// writes the dL_dsh rows of a wave through LDS for coalesced HBM access: `row` (LDS, may be null) receives this Gaussian's
+// row word by word; or, with `defer` (the 16-byte path), `deferred` receives what the row is made from and the caller writes it
+// in the Gaussian's pass (`deferred.visible` stays false for a culled Gaussian).  PLANES (a backward with a depth gradient, FR_FLAG_DEPTH_ALPHA): the
 // accumulated dL/dz of the view-space depth (ACC_Z) joins dL/dmean3D through z = view[2] x + view[6] y + view[10] z + view[14].
 template <bool PLANES>
 __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const CameraRegs& cam, const PreBwdIn& in,
-                                                   const int idx, float* row, const bool by16)
+                                                   const int idx, float* row, const bool defer, PreBwdRow& deferred)
 {
     const size_t i = (size_t)idx;
     const int Mc = a.M;
     const int radius = in.radius;
     const auto adds = [&](int k) { return ((a.acc >> k) & 1u) != 0u; };
     if (!(radius > 0)) {   // no gradient: zeros where the arrays are overwritten, nothing where they accumulate
-        if (row && by16) {
-            float4* r4 = reinterpret_cast<float4*>(row);
-            for (int k = 0; k < (Mc * 3) / 4; k++) r4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else if (row)
+        if (row)
             for (int k = 0; k < Mc * 3; k++) row[k] = 0.f;
         if (!adds(G_MEANS2D)) store3(a.out.dL_dmeans2D, i, 0.f, 0.f, 0.f, false);
         if (!adds(G_COLORS)) store3(a.out.dL_dcolors, i, 0.f, 0.f, 0.f, false);
@@ -175,7 +247,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
         if (!adds(G_MEANS3D)) store3(a.out.dL_dmeans3D, i, 0.f, 0.f, 0.f, false);
         if (a.out.dL_dcov3D && !adds(G_COV3D))
             for (int k = 0; k < 6; k++) a.out.dL_dcov3D[6 * i + k] = 0.f;
-        if (a.out.dL_dsh && !row && !adds(G_SH))
+        if (a.out.dL_dsh && !row && !defer && !adds(G_SH))
             for (int k = 0; k < Mc * 3; k++) a.out.dL_dsh[i * Mc * 3 + k] = 0.f;
         if (!adds(G_SCALES)) store3(a.out.dL_dscales, i, 0.f, 0.f, 0.f, false);
         if (a.out.dL_drotations && !adds(G_ROTATIONS))
@@ -372,43 +444,11 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
                 for (int k = used; k < Mc; k++) dsh[k * 3] = 0.f, dsh[k * 3 + 1] = 0.f, dsh[k * 3 + 2] = 0.f;
 #undef DSH
         };
-        // The LDS row in 16-byte pieces (M3 a multiple of 4): the same products — the direction factor of coefficient k,
-        // evaluated with write_row's expression, times dRGB[c] — four of them per ds_write_b128 instead of one per store.
-        auto write_row_by16 = [&](float* dsh) {
-            float f[16] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            f[0] = bSH_C0;
-            if (deg > 0) {
-                f[1] = -bSH_C1 * y, f[2] = bSH_C1 * z, f[3] = -bSH_C1 * x;
-                if (deg > 1) {
-                    const float xx = x * x, yy = y * y, zz = z * z;
-                    const float xy = x * y, yz = y * z, xz = x * z;
-                    f[4] = bSH_C2[0] * xy, f[5] = bSH_C2[1] * yz, f[6] = bSH_C2[2] * (2.f * zz - xx - yy);
-                    f[7] = bSH_C2[3] * xz, f[8] = bSH_C2[4] * (xx - yy);
-                    if (deg > 2) {
-                        f[9] = bSH_C3[0] * y * (3.f * xx - yy), f[10] = bSH_C3[1] * xy * z;
-                        f[11] = bSH_C3[2] * y * (4.f * zz - xx - yy), f[12] = bSH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy);
-                        f[13] = bSH_C3[4] * x * (4.f * zz - xx - yy), f[14] = bSH_C3[5] * z * (xx - yy);
-                        f[15] = bSH_C3[6] * x * (xx - 3.f * yy);
-                    }
-                }
-            }
-            float4* d4 = reinterpret_cast<float4*>(dsh);
-            const int pieces = (Mc * 3) / 4;
-#pragma unroll
-            for (int j = 0; j < 12; j++) {
-                if (j >= pieces) break;   // (wave-uniform; rows longer than 48 floats do not exist: M <= 16)
-                float v[4];
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const int k = (4 * j + t) / 3, c = (4 * j + t) % 3;
-                    // (coefficients above the active degree: a literal zero, as write_row stores)
-                    v[t] = k < used ? f[k] * dRGB[c] : 0.f;
-                }
-                d4[j] = make_float4(v[0], v[1], v[2], v[3]);
-            }
-        };
-        if (row && by16) write_row_by16(row);                              // (added to the array by unstage_rows)
-        else if (row) write_row(row, false);
+        if (defer) {                                                       // (written in its pass, by the caller)
+            deferred.x = x, deferred.y = y, deferred.z = z;
+            deferred.dRGB[0] = dRGB[0], deferred.dRGB[1] = dRGB[1], deferred.dRGB[2] = dRGB[2];
+            deferred.visible = true;
+        } else if (row) write_row(row, false);                             // (added to the array by unstage_rows)
         else if (a.out.dL_dsh) write_row(a.out.dL_dsh + i * Mc * 3, adds(G_SH));
         const float ddx = dRGBdx[0] * dRGB[0] + dRGBdx[1] * dRGB[1] + dRGBdx[2] * dRGB[2];
         const float ddy = dRGBdy[0] * dRGB[0] + dRGBdy[1] * dRGB[1] + dRGBdy[2] * dRGB[2];
@@ -419,7 +459,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
         dmx += ((+sum2 - dox * dox) * ddx - doy * dox * ddy - doz * dox * ddz) * invsum32;
         dmy += (-dox * doy * ddx + (sum2 - doy * doy) * ddy - doz * doy * ddz) * invsum32;
         dmz += (-dox * doz * ddx - doy * doz * ddy + (sum2 - doz * doz) * ddz) * invsum32;
-    } else if (a.out.dL_dsh && !row && !adds(G_SH)) {
+    } else if (a.out.dL_dsh && !row && !defer && !adds(G_SH)) {
         for (int k = 0; k < Mc * 3; k++) a.out.dL_dsh[i * Mc * 3 + k] = 0.f;
     }
     if (PLANES) {
@@ -487,7 +527,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
     if (a.bound) bind_bwd(a.bind, idx, g_mean, g_rot, g_scl, a.bg);
 }
 
-// A wave's [64][row_len] block of dL_dsh rows goes from LDS to HBM in coalesced 16-byte stores (the inverse of the
+// A wave's [rows][row_len] block of dL_dsh rows goes from LDS to HBM in coalesced 16-byte stores (the inverse of the
 // forward's staging, fr_preprocess.hip).
 template <bool ADD>
 __device__ __forceinline__ void unstage_rows_t(float* __restrict__ dst, const float* src, int stride, int rows, int row_len, int lane)
@@ -560,17 +600,6 @@ __device__ __forceinline__ void unstage_rows_by16_t(float* __restrict__ dst, con
         }
     }
 }
-__device__ __forceinline__ void unstage_rows(float* __restrict__ dst, const float* src, int stride, int rows, int row_len, int lane,
-                                             bool add)
-{
-    if (prebwd_rows_by16(row_len)) {
-        if (add) unstage_rows_by16_t<true>(dst, src, stride, rows, row_len, lane);
-        else unstage_rows_by16_t<false>(dst, src, stride, rows, row_len, lane);
-    } else {
-        if (add) unstage_rows_t<true>(dst, src, stride, rows, row_len, lane);
-        else unstage_rows_t<false>(dst, src, stride, rows, row_len, lane);
-    }
-}
 
 #ifndef FR_PREBWD_WAVES
 #define FR_PREBWD_WAVES 4
@@ -588,7 +617,8 @@ __device__ __forceinline__ void preprocess_bwd_body(const PreBwdArgs& a)
     const int wave_first = blockIdx.x * (64 * kPreBwdWaves) + wave * 64;
     const int rows = min(64, a.P - wave_first);
     const bool staged = a.shs != nullptr && a.out.dL_dsh != nullptr;
-    float* w_rows = s_rows + (size_t)wave * 64 * stride;
+    const bool by16 = prebwd_rows_by16(M3);
+    float* w_rows = s_rows + (size_t)wave * prebwd_block_rows(M3) * stride;   // this wave's block: no other wave touches it
     // Every input of the thread, then the camera, are requested before anything is used or stored: one round trip for all
     // of them.  The camera goes LAST: loads come back in order, so the wait in front of its broadcast — the first use of
     // anything — is the kernel's one wait for its inputs.  (The compiler's barrier: without it the loads that only the
@@ -603,9 +633,38 @@ __device__ __forceinline__ void preprocess_bwd_body(const PreBwdArgs& a)
     asm volatile("" : "+v"(in.cl), "+v"(in.ga), "+v"(in.dn), "+v"(in.opacity), "+v"(in.radius));
     // (fr_aux::overflow_out: the step's optimizer kernel reads it — fr_adam_config::skip)
     if (a.overflow_out && blockIdx.x == 0 && threadIdx.x == 0) *a.overflow_out = in.overflow ? 1.0f : 0.0f;
-    if (idx < a.P) preprocess_bwd_one<PLANES>(a, cam, in, idx, staged ? w_rows + lane * stride : nullptr, prebwd_rows_by16(M3));
-    __syncthreads();
-    if (staged && rows > 0) unstage_rows(a.out.dL_dsh + (size_t)wave_first * M3, w_rows, stride, rows, M3, lane, ((a.acc >> G_SH) & 1u) != 0u);
+    PreBwdRow mine;
+    mine.x = mine.y = mine.z = mine.dRGB[0] = mine.dRGB[1] = mine.dRGB[2] = 0.f, mine.visible = false;
+    if (idx < a.P)
+        preprocess_bwd_one<PLANES>(a, cam, in, idx, staged && !by16 ? w_rows + lane * stride : nullptr, staged && by16, mine);
+    // The whole wave is here, converged (nothing returns inside preprocess_bwd_one's caller), and the waves of a workgroup
+    // go their own ways: each unstages only its own block, so there is nothing to wait for another wave for.
+    if (!staged || rows <= 0) return;
+    float* dst = a.out.dL_dsh + (size_t)wave_first * M3;
+    const bool add = ((a.acc >> G_SH) & 1u) != 0u;
+    if (!by16) {
+        wave_lds_fence();
+        if (add) unstage_rows_t<true>(dst, w_rows, stride, rows, M3, lane);
+        else unstage_rows_t<false>(dst, w_rows, stride, rows, M3, lane);
+        return;
+    }
+    // pass p: the Gaussians [p R, p R + R) of the wave write their rows (culled: zeros), the wave stores them.  (Unrolled:
+    // as a loop the passes cost the single-view kernels 9 more VGPRs, 103 instead of 94, and a wave per SIMD with them.)
+    constexpr int R = kPreBwdStageRows;
+#pragma unroll
+    for (int first = 0; first < 64; first += R) {
+        if (first >= rows) break;   // (wave-uniform)
+        if (lane >= first && lane < first + R) {
+            float* row = w_rows + (lane - first) * stride;
+            if (mine.visible) write_row_by16(row, mine, a.D, a.M);
+            else zero_row_by16(row, a.M);
+        }
+        wave_lds_fence();
+        const int n = min(R, rows - first);
+        if (add) unstage_rows_by16_t<true>(dst + (size_t)first * M3, w_rows, stride, n, M3, lane);
+        else unstage_rows_by16_t<false>(dst + (size_t)first * M3, w_rows, stride, n, M3, lane);
+        wave_lds_fence();   // (the next pass overwrites what this one read)
+    }
 }
 
 __global__ void __launch_bounds__(64 * kPreBwdWaves) k_preprocess_bwd(PreBwdArgs a) { preprocess_bwd_body<false>(a); }
@@ -673,7 +732,7 @@ int launch_backward(int n, const BackwardCall* calls, hipStream_t s)
             a.bind = BindArgs{};
             a.bg = BindGrads{};
         }
-        const size_t l = (in.shs && calls[k].grads->dL_dsh) ? (size_t)kPreBwdWaves * 64 * prebwd_row_stride(prm.M * 3) * sizeof(float) : 0;
+        const size_t l = (in.shs && calls[k].grads->dL_dsh) ? (size_t)kPreBwdWaves * prebwd_block_rows(prm.M * 3) * prebwd_row_stride(prm.M * 3) * sizeof(float) : 0;
         lds = l > lds ? l : lds;
         blocks = max(blocks, (uint32_t)((P + wg - 1) / wg));
     }
