@@ -265,6 +265,21 @@ def last_error() -> str:
     return lib().fr_last_error().decode("utf-8", "replace")
 
 
+def check(rc: int, name: str) -> None:
+    if rc != FR_OK:
+        raise RuntimeError(f"{name} failed (code {rc}): {last_error()}")
+
+
+def launch(name: str, device, *args) -> None:
+    """The entry point `name` on `device`'s current stream (its last argument), checked: how every stream-ordered call of
+    the package reaches the library."""
+    import torch
+
+    with torch.cuda.device(device):
+        rc = getattr(lib(), name)(*args, torch.cuda.current_stream(device).cuda_stream)
+    check(rc, name)
+
+
 _handles: dict = {}
 
 

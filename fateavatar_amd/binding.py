@@ -34,6 +34,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
+from .rasterizer import GradOut
 
 
 def _chk(t, dtype, name):
@@ -47,164 +48,8 @@ def face_scale(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     the canonical mesh (model/fateavatar.py:84-85)."""
     verts, faces = _chk(verts, torch.float32, "verts"), _chk(faces, torch.int32, "faces")
     out = torch.empty((faces.shape[0], 1), dtype=torch.float32, device=verts.device)
-    with torch.cuda.device(verts.device):
-        rc = _lib.lib().fr_face_scale(verts.shape[0], faces.shape[0], verts.data_ptr(), faces.data_ptr(), out.data_ptr(),
-                                      torch.cuda.current_stream(verts.device).cuda_stream)
-    if rc != _lib.FR_OK:
-        raise RuntimeError(f"fr_face_scale failed: {_lib.last_error()}")
+    _lib.launch("fr_face_scale", verts.device, verts.shape[0], faces.shape[0], verts.data_ptr(), faces.data_ptr(), out.data_ptr())
     return out
-
-
-def _desc(verts, faces, face_index, bary, canon, offset, rotation, scaling, shell_len, resize_scale):
-    b = _lib.fr_binding()
-    b.N, b.V, b.F = face_index.shape[0], verts.shape[0], faces.shape[0]
-    b.verts, b.faces, b.face_index, b.bary = verts.data_ptr(), faces.data_ptr(), face_index.data_ptr(), bary.data_ptr()
-    b.face_scale_canonical = canon.data_ptr() if canon is not None else None
-    b.shell_len, b.resize_scale = float(shell_len), int(bool(resize_scale))
-    b.offset, b.rotation, b.scaling = offset.data_ptr(), rotation.data_ptr(), scaling.data_ptr()
-    return b
-
-
-class _Bind(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, verts, offset, rotation, scaling, faces, face_index, bary, canon, shell_len, resize_scale):
-        verts, offset = _chk(verts, torch.float32, "verts"), _chk(offset, torch.float32, "offset")
-        rotation, scaling = _chk(rotation, torch.float32, "rotation"), _chk(scaling, torch.float32, "scaling")
-        faces, face_index = _chk(faces, torch.int32, "faces"), _chk(face_index, torch.int32, "face_index")
-        bary = _chk(bary, torch.float32, "bary_coords")
-        canon = _chk(canon, torch.float32, "face_scale_canonical") if canon is not None else None
-        N, dev = face_index.shape[0], verts.device
-        if verts.dim() != 2 or offset.numel() != N or rotation.shape != (N, 4) or scaling.shape != (N, 3) or bary.shape != (N, 3):
-            raise RuntimeError("bind_gaussians: verts [V,3], offset [N,1], rotation [N,4], scaling [N,3], bary [N,3]")
-        if resize_scale and (canon is None or canon.numel() != faces.shape[0]):
-            raise RuntimeError("bind_gaussians: resize_scale needs face_scale_canonical [F,1]")
-        xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
-        rot = torch.empty((N, 4), dtype=torch.float32, device=dev)
-        scl = torch.empty((N, 3), dtype=torch.float32, device=dev)
-        b = _desc(verts, faces, face_index, bary, canon, offset, rotation, scaling, shell_len, resize_scale)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().fr_bind_forward(C.byref(b), xyz.data_ptr(), rot.data_ptr(), scl.data_ptr(),
-                                            torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.FR_OK:
-            raise RuntimeError(f"fr_bind_forward failed: {_lib.last_error()}")
-        ctx.save_for_backward(verts, offset, rotation, scaling, faces, face_index, bary, canon)
-        ctx.consts = (float(shell_len), bool(resize_scale), offset.shape)
-        # optional extension (see rasterizer.GradOut): a raw parameter may carry `_fr_grad_out`, a slot whose preallocated
-        # buffer (a view into a flat gradient buffer) receives its gradient without a copy
-        from .rasterizer import GradOut
-        ctx.grad_slots = (GradOut.of(offset), GradOut.of(rotation), GradOut.of(scaling))
-        return xyz, rot, scl
-
-    @staticmethod
-    def backward(ctx, g_xyz, g_rot, g_scl):
-        verts, offset, rotation, scaling, faces, face_index, bary, canon = ctx.saved_tensors
-        shell_len, resize_scale, offset_shape = ctx.consts
-        dev, N = verts.device, face_index.shape[0]
-        need_v, need_o, need_r, need_s = ctx.needs_input_grad[:4]
-        c = lambda g: g.contiguous().float() if g is not None else None  # noqa: E731
-        g_xyz, g_rot, g_scl = c(g_xyz), c(g_rot), c(g_scl)
-        d_verts = torch.zeros_like(verts) if need_v else None
-
-        def out(need, slot, shape):
-            if not need:
-                return None
-            buf = slot.claim()[0] if slot is not None else None   # first backward of the step writes the slot in place
-            if buf is not None and buf.numel() == int(torch.Size(shape).numel()) and buf.is_contiguous():
-                return buf.view(shape)
-            return torch.empty(shape, dtype=torch.float32, device=dev)
-
-        d_off = out(need_o, ctx.grad_slots[0], (N,))
-        d_rot = out(need_r, ctx.grad_slots[1], (N, 4))
-        d_scl = out(need_s, ctx.grad_slots[2], (N, 3))
-        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        b = _desc(verts, faces, face_index, bary, canon, offset, rotation, scaling, shell_len, resize_scale)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().fr_bind_backward(C.byref(b), p(g_xyz), p(g_rot), p(g_scl), p(d_verts), p(d_off), p(d_rot), p(d_scl),
-                                             torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.FR_OK:
-            raise RuntimeError(f"fr_bind_backward failed: {_lib.last_error()}")
-        return (d_verts, d_off.view(offset_shape) if d_off is not None else None, d_rot, d_scl, None, None, None, None, None,
-                None)
-
-
-def bind_gaussians(verts, faces, face_index, bary_coords, face_scale_canonical, offset, rotation, scaling,
-                   shell_len: float, resize_scale: bool = True):
-    """One frame of model/fateavatar.py:225-258.  verts [V,3] (posed), faces [F,3], face_index [N], bary_coords [N,3],
-    face_scale_canonical [F,1] (`face_scale` of the canonical mesh), raw offset [N,1] / rotation [N,4] / scaling [N,3].
-    Returns (xyz [N,3], rotation [N,4], scaling [N,3]): the values the reference assigns to gaussian._xyz /
-    gaussian._rotation / gaussian._scaling before render()."""
-    return _Bind.apply(verts, offset, rotation, scaling, faces, face_index, bary_coords, face_scale_canonical, shell_len,
-                       resize_scale)
-
-
-def _desc_local(verts, faces, binding, local_xyz, rotation, scaling):
-    b = _lib.fr_binding()   # (zero-filled: bary, offset, face_scale_canonical, shell_len, resize_scale are not read in this mode)
-    b.N, b.V, b.F = binding.shape[0], verts.shape[0], faces.shape[0]
-    b.verts, b.faces, b.face_index = verts.data_ptr(), faces.data_ptr(), binding.data_ptr()
-    b.rotation, b.scaling = rotation.data_ptr(), scaling.data_ptr()
-    b.mode, b.local_xyz = _lib.FR_BIND_FACE_LOCAL, local_xyz.data_ptr()
-    return b
-
-
-class _BindFaceLocal(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, verts, local_xyz, rotation, scaling, faces, binding):
-        verts, local_xyz = _chk(verts, torch.float32, "verts"), _chk(local_xyz, torch.float32, "local_xyz")
-        rotation, scaling = _chk(rotation, torch.float32, "rotation"), _chk(scaling, torch.float32, "scaling")
-        faces, binding = _chk(faces, torch.int32, "faces"), _chk(binding, torch.int32, "binding")
-        N, dev = binding.shape[0], verts.device
-        if verts.dim() != 2 or local_xyz.shape != (N, 3) or rotation.shape != (N, 4) or scaling.shape != (N, 3):
-            raise RuntimeError("bind_gaussians_face_local: verts [V,3], binding [N], local_xyz [N,3], rotation [N,4], scaling [N,3]")
-        xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
-        rot = torch.empty((N, 4), dtype=torch.float32, device=dev)
-        scl = torch.empty((N, 3), dtype=torch.float32, device=dev)
-        b = _desc_local(verts, faces, binding, local_xyz, rotation, scaling)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().fr_bind_forward(C.byref(b), xyz.data_ptr(), rot.data_ptr(), scl.data_ptr(),
-                                            torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.FR_OK:
-            raise RuntimeError(f"fr_bind_forward failed: {_lib.last_error()}")
-        ctx.save_for_backward(verts, local_xyz, rotation, scaling, faces, binding)
-        from .rasterizer import GradOut   # (the `_fr_grad_out` extension, as _Bind)
-        ctx.grad_slots = (GradOut.of(local_xyz), GradOut.of(rotation), GradOut.of(scaling))
-        return xyz, rot, scl
-
-    @staticmethod
-    def backward(ctx, g_xyz, g_rot, g_scl):
-        verts, local_xyz, rotation, scaling, faces, binding = ctx.saved_tensors
-        dev, N = verts.device, binding.shape[0]
-        need_v, need_l, need_r, need_s = ctx.needs_input_grad[:4]
-        c = lambda g: g.contiguous().float() if g is not None else None  # noqa: E731
-        g_xyz, g_rot, g_scl = c(g_xyz), c(g_rot), c(g_scl)
-        d_verts = torch.zeros_like(verts) if need_v else None
-
-        def out(need, slot, shape):
-            if not need:
-                return None
-            buf = slot.claim()[0] if slot is not None else None   # first backward of the step writes the slot in place
-            if buf is not None and buf.numel() == int(torch.Size(shape).numel()) and buf.is_contiguous():
-                return buf.view(shape)
-            return torch.empty(shape, dtype=torch.float32, device=dev)
-
-        d_loc = out(need_l, ctx.grad_slots[0], (N, 3))
-        d_rot = out(need_r, ctx.grad_slots[1], (N, 4))
-        d_scl = out(need_s, ctx.grad_slots[2], (N, 3))
-        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        b = _desc_local(verts, faces, binding, local_xyz, rotation, scaling)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().fr_bind_backward_local(C.byref(b), p(g_xyz), p(g_rot), p(g_scl), p(d_verts), p(d_loc), p(d_rot),
-                                                   p(d_scl), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.FR_OK:
-            raise RuntimeError(f"fr_bind_backward_local failed: {_lib.last_error()}")
-        return d_verts, d_loc, d_rot, d_scl, None, None
-
-
-def bind_gaussians_face_local(verts, faces, binding, local_xyz, rotation, scaling):
-    """One frame of model/baseline/gaussianavatars.py:144-171.  verts [V,3] (posed), faces [F,3], binding [N] (the face of
-    every Gaussian), raw local_xyz [N,3] / rotation [N,4] / scaling [N,3].  Returns (xyz [N,3], rotation [N,4],
-    scaling [N,3]): the values the reference assigns to gaussian._xyz / gaussian._rotation / gaussian._scaling before
-    render()."""
-    return _BindFaceLocal.apply(verts, local_xyz, rotation, scaling, faces, binding)
 
 
 class PhongCanonical(NamedTuple):
@@ -256,25 +101,9 @@ def phong_frame(canonical: PhongCanonical, verts: torch.Tensor):
     vn = torch.empty((V, 3), dtype=torch.float32, device=dev)
     vq = torch.empty((V, 4), dtype=torch.float32, device=dev)
     ratio = torch.empty((F,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().fr_phong_frame(V, F, verts.data_ptr(), cano.data_ptr(), faces.data_ptr(), off.data_ptr(), ids.data_ptr(),
-                                       area.data_ptr(), vn.data_ptr(), vq.data_ptr(), ratio.data_ptr(),
-                                       torch.cuda.current_stream(dev).cuda_stream)
-    if rc != _lib.FR_OK:
-        raise RuntimeError(f"fr_phong_frame failed: {_lib.last_error()}")
+    _lib.launch("fr_phong_frame", dev, V, F, verts.data_ptr(), cano.data_ptr(), faces.data_ptr(), off.data_ptr(), ids.data_ptr(),
+                area.data_ptr(), vn.data_ptr(), vq.data_ptr(), ratio.data_ptr())
     return vn, vq, ratio
-
-
-def _desc_phong(verts, faces, face_index, bary, frame, uvd, rotation, scaling):
-    vn, vq, ratio = frame
-    p = _lib.fr_binding_phong()   # (zero-filled: offset, face_scale_canonical, shell_len, resize_scale are not read in this mode)
-    b = p.base
-    b.N, b.V, b.F = face_index.shape[0], verts.shape[0], faces.shape[0]
-    b.verts, b.faces, b.face_index, b.bary = verts.data_ptr(), faces.data_ptr(), face_index.data_ptr(), bary.data_ptr()
-    b.rotation, b.scaling = rotation.data_ptr(), scaling.data_ptr()
-    b.mode, b.local_xyz = _lib.FR_BIND_PHONG, uvd.data_ptr()
-    p.vert_normals, p.vert_quats, p.face_ratio = vn.data_ptr(), vq.data_ptr(), ratio.data_ptr()
-    return p.as_binding()   # (an fr_binding over the extended descriptor's memory: every caller passes it on as before)
 
 
 def _chk_phong_frame(frame, V, F, who):
@@ -284,64 +113,168 @@ def _chk_phong_frame(frame, V, F, who):
     return vn, vq, ratio
 
 
-class _BindPhong(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, uvd, rotation, scaling, verts, faces, face_index, bary, vn, vq, ratio):
-        verts, uvd = _chk(verts, torch.float32, "verts"), _chk(uvd, torch.float32, "uvd")
-        rotation, scaling = _chk(rotation, torch.float32, "rotation"), _chk(scaling, torch.float32, "scaling")
-        faces, face_index = _chk(faces, torch.int32, "faces"), _chk(face_index, torch.int32, "face_index")
-        bary = _chk(bary, torch.float32, "bary_coords")
-        N, dev = face_index.shape[0], verts.device
-        if verts.dim() != 2 or uvd.shape != (N, 3) or rotation.shape != (N, 4) or scaling.shape != (N, 3) or bary.shape != (N, 3):
-            raise RuntimeError("bind_gaussians_phong: verts [V,3], face_index [N], bary [N,3], uvd [N,3], rotation [N,4], scaling [N,3]")
-        frame = _chk_phong_frame((vn, vq, ratio), verts.shape[0], faces.shape[0], "bind_gaussians_phong")
-        xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
-        rot = torch.empty((N, 4), dtype=torch.float32, device=dev)
-        scl = torch.empty((N, 3), dtype=torch.float32, device=dev)
-        b = _desc_phong(verts, faces, face_index, bary, frame, uvd, rotation, scaling)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().fr_bind_forward(C.byref(b), xyz.data_ptr(), rot.data_ptr(), scl.data_ptr(),
-                                            torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.FR_OK:
-            raise RuntimeError(f"fr_bind_forward failed: {_lib.last_error()}")
-        ctx.save_for_backward(verts, uvd, rotation, scaling, faces, face_index, bary, *frame)
-        from .rasterizer import GradOut   # (the `_fr_grad_out` extension, as _Bind)
-        ctx.grad_slots = (GradOut.of(uvd), GradOut.of(rotation), GradOut.of(scaling))
-        return xyz, rot, scl
-
-    @staticmethod
-    def backward(ctx, g_xyz, g_rot, g_scl):
-        verts, uvd, rotation, scaling, faces, face_index, bary, vn, vq, ratio = ctx.saved_tensors
-        dev, N = verts.device, face_index.shape[0]
-        need_u, need_r, need_s = ctx.needs_input_grad[:3]
-        c = lambda g: g.contiguous().float() if g is not None else None  # noqa: E731
-        g_xyz, g_rot, g_scl = c(g_xyz), c(g_rot), c(g_scl)
-
-        def out(need, slot, shape):
-            if not need:
-                return None
-            buf = slot.claim()[0] if slot is not None else None   # first backward of the step writes the slot in place
-            if buf is not None and buf.numel() == int(torch.Size(shape).numel()) and buf.is_contiguous():
-                return buf.view(shape)
-            return torch.empty(shape, dtype=torch.float32, device=dev)
-
-        d_uvd = out(need_u, ctx.grad_slots[0], (N, 3))
-        d_rot = out(need_r, ctx.grad_slots[1], (N, 4))
-        d_scl = out(need_s, ctx.grad_slots[2], (N, 3))
-        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        b = _desc_phong(verts, faces, face_index, bary, (vn, vq, ratio), uvd, rotation, scaling)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().fr_bind_backward_phong(C.byref(b), p(g_xyz), p(g_rot), p(g_scl), None, p(d_uvd), p(d_rot), p(d_scl),
-                                                   torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.FR_OK:
-            raise RuntimeError(f"fr_bind_backward_phong failed: {_lib.last_error()}")
-        return d_uvd, d_rot, d_scl, None, None, None, None, None, None, None
-
-
 def _no_vertex_gradient(verts, who):
     if isinstance(verts, torch.Tensor) and verts.requires_grad and torch.is_grad_enabled():
         raise RuntimeError(f"{who}: the Phong-surface binding has no vertex gradient (the per-frame mesh pass is not "
                            "differentiable); hand it `verts.detach()`")
+
+
+class BindMode(NamedTuple):
+    """Everything the host knows about ONE value of fr_binding::mode.  The device code holds the modes as one thing
+    (csrc/fr_bind_math.hpp, one bind_fwd / bind_bwd switch); this is its counterpart: the descriptor builder, the autograd
+    Function below and bound.py read a record and never ask which mode they are in."""
+    value: int            # FR_BIND_*
+    op: str               # the public stand-alone op (error messages)
+    own: str              # the mode's own per-Gaussian parameter: as the op names it, ...
+    attr: str             # ... the holder attribute that carries it, ...
+    own_cols: int         # ... its shape: [N,3], or with 1 anything of N elements ([N,1]), ...
+    field: str            # ... the fr_binding member it travels in ...
+    grad: str             # ... and the fr_aux member its gradient is written through
+    backward: str         # the stand-alone backward's entry point
+    reads_bary: bool      # fr_binding::bary is read
+    verts_grad: bool      # the posed vertices get a gradient
+    active_sh: bool       # render_bound_batch renders the frame at the holder's active_sh_degree
+    shapes: str           # the shape error of the op ...
+    frame_shapes: str     # ... and of render_bound_batch
+    holder: str           # what render_bound_batch tells a holder without `attr`
+
+    def grad_shape(self, N):
+        """The shape the kernel writes the own parameter's gradient in."""
+        return (N, 3) if self.own_cols == 3 else (N,)
+
+
+SHELL = BindMode(_lib.FR_BIND_SHELL, "bind_gaussians", "offset", "_offset", 1, "offset", "d_offset", "fr_bind_backward",
+                 reads_bary=True, verts_grad=True, active_sh=False,
+                 shapes="verts [V,3], offset [N,1], rotation [N,4], scaling [N,3], bary [N,3]",
+                 frame_shapes="verts [V,3], offset [N,1], rotation [N,4], scaling [N,3], bary [N,3]",
+                 holder="a shell binding (MeshBinding) needs a holder with the offsets `_offset` [N,1]")
+FACE_LOCAL = BindMode(_lib.FR_BIND_FACE_LOCAL, "bind_gaussians_face_local", "local_xyz", "_xyz", 3, "local_xyz", "d_local_xyz",
+                      "fr_bind_backward_local", reads_bary=False, verts_grad=True, active_sh=True,
+                      shapes="verts [V,3], binding [N], local_xyz [N,3], rotation [N,4], scaling [N,3]",
+                      frame_shapes="verts [V,3], _xyz [N,3], rotation [N,4], scaling [N,3]",
+                      holder="a face-local binding (FaceLocalBinding) needs a holder with the local positions `_xyz` [N,3]")
+PHONG = BindMode(_lib.FR_BIND_PHONG, "bind_gaussians_phong", "uvd", "_uvd", 3, "local_xyz", "d_local_xyz", "fr_bind_backward_phong",
+                 reads_bary=True, verts_grad=False, active_sh=False,
+                 shapes="verts [V,3], face_index [N], bary [N,3], uvd [N,3], rotation [N,4], scaling [N,3]",
+                 frame_shapes="verts [V,3], _uvd [N,3], rotation [N,4], scaling [N,3], bary [N,3]",
+                 holder="a Phong-surface binding (PhongBinding) needs a holder with the parameters `_uvd` [N,3]")
+
+
+def _describe(mode, verts, faces, face_index, own, rotation, scaling, bary=None, canon=None, shell_len=0.0, resize_scale=False,
+              frame=None):
+    """The fr_binding of one frame in `mode`; `own` is the mode's own per-Gaussian parameter.  What a mode does not read is
+    not handed over and stays zero.  `frame` (`phong_frame` of the posed mesh) makes it the `base` of an fr_binding_phong
+    with the three arrays behind it: an fr_binding over the extended descriptor's memory, passed on like any other.  The
+    descriptor holds raw pointers: the caller keeps the tensors alive until the launch."""
+    phong = _lib.fr_binding_phong() if frame is not None else None
+    b = phong.base if phong is not None else _lib.fr_binding()
+    b.N, b.V, b.F, b.mode = face_index.shape[0], verts.shape[0], faces.shape[0], mode.value
+    b.verts, b.faces, b.face_index = verts.data_ptr(), faces.data_ptr(), face_index.data_ptr()
+    b.bary = bary.data_ptr() if bary is not None else None
+    b.face_scale_canonical = canon.data_ptr() if canon is not None else None
+    b.shell_len, b.resize_scale = float(shell_len), int(bool(resize_scale))
+    b.rotation, b.scaling = rotation.data_ptr(), scaling.data_ptr()
+    setattr(b, mode.field, own.data_ptr())
+    if phong is None:
+        return b
+    phong.vert_normals, phong.vert_quats, phong.face_ratio = (t.data_ptr() for t in frame)
+    return phong.as_binding()
+
+
+def _check_shapes(who, text, mode, verts, faces, face_index, own, rotation, scaling, bary=None, canon=None, shell_len=0.0,
+                  resize_scale=False, frame=None):
+    """`_describe`'s arguments behind the name of the caller and its shape error (`BindMode.shapes` / `.frame_shapes`)."""
+    N = face_index.shape[0]
+    own_ok = own.shape == (N, 3) if mode.own_cols == 3 else own.numel() == N
+    if verts.dim() != 2 or not own_ok or rotation.shape != (N, 4) or scaling.shape != (N, 3) or \
+            (mode.reads_bary and bary.shape != (N, 3)):
+        raise RuntimeError(f"{who}: {text}")
+    if resize_scale and (canon is None or canon.numel() != faces.shape[0]):
+        raise RuntimeError(f"{who}: resize_scale needs face_scale_canonical [F,1]")
+
+
+def _grad_buffer(need, claimed, shape, device):
+    """Where a backward writes one gradient: nothing if it is not needed; `claimed`, the buffer of the parameter's GradOut slot
+    (the first backward of a step writes the slot in place), if it has the right size and is contiguous; else a fresh tensor."""
+    if not need:
+        return None
+    if claimed is not None and claimed.numel() == int(torch.Size(shape).numel()) and claimed.is_contiguous():
+        return claimed.view(shape)
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
+class _Bind(torch.autograd.Function):
+    """The stand-alone binding op of every mode: fr_bind_forward, and the mode's backward entry point."""
+
+    @staticmethod
+    def forward(ctx, mode, verts, own, rotation, scaling, faces, face_index, bary, canon, shell_len, resize_scale, frame):
+        own_shape = own.shape
+        verts, own = _chk(verts, torch.float32, "verts"), _chk(own, torch.float32, mode.own)
+        rotation, scaling = _chk(rotation, torch.float32, "rotation"), _chk(scaling, torch.float32, "scaling")
+        faces, face_index = _chk(faces, torch.int32, "faces"), _chk(face_index, torch.int32, "face_index")
+        bary = _chk(bary, torch.float32, "bary_coords") if mode.reads_bary else None
+        canon = _chk(canon, torch.float32, "face_scale_canonical") if canon is not None else None
+        args = (mode, verts, faces, face_index, own, rotation, scaling, bary, canon, float(shell_len), bool(resize_scale))
+        _check_shapes(mode.op, mode.shapes, *args)
+        if frame is not None:
+            frame = _chk_phong_frame(frame, verts.shape[0], faces.shape[0], mode.op)
+        N, dev = face_index.shape[0], verts.device
+        xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        rot = torch.empty((N, 4), dtype=torch.float32, device=dev)
+        scl = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        b = _describe(*args, frame)
+        _lib.launch("fr_bind_forward", dev, C.byref(b), xyz.data_ptr(), rot.data_ptr(), scl.data_ptr())
+        ctx.save_for_backward(verts, faces, face_index, own, rotation, scaling, bary, canon, *(frame or ()))
+        ctx.consts = (mode, float(shell_len), bool(resize_scale), own_shape)
+        # optional extension (see rasterizer.GradOut): a raw parameter may carry `_fr_grad_out`, a slot whose preallocated
+        # buffer (a view into a flat gradient buffer) receives its gradient without a copy
+        ctx.grad_slots = (GradOut.of(own), GradOut.of(rotation), GradOut.of(scaling))
+        return xyz, rot, scl
+
+    @staticmethod
+    def backward(ctx, g_xyz, g_rot, g_scl):
+        saved = ctx.saved_tensors
+        *tensors, bary, canon = saved[:8]
+        mode, shell_len, resize_scale, own_shape = ctx.consts
+        verts, dev, N = tensors[0], tensors[0].device, tensors[2].shape[0]
+        need_v, need_o, need_r, need_s = ctx.needs_input_grad[1:5]
+        c = lambda g: g.contiguous().float() if g is not None else None  # noqa: E731
+        g_xyz, g_rot, g_scl = c(g_xyz), c(g_rot), c(g_scl)
+        claim = lambda need, slot: slot.claim()[0] if need and slot is not None else None  # noqa: E731
+        d_verts = torch.zeros_like(verts) if need_v and mode.verts_grad else None
+        d_own = _grad_buffer(need_o, claim(need_o, ctx.grad_slots[0]), mode.grad_shape(N), dev)
+        d_rot = _grad_buffer(need_r, claim(need_r, ctx.grad_slots[1]), (N, 4), dev)
+        d_scl = _grad_buffer(need_s, claim(need_s, ctx.grad_slots[2]), (N, 3), dev)
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        b = _describe(mode, *tensors, bary, canon, shell_len, resize_scale, saved[8:] or None)
+        _lib.launch(mode.backward, dev, C.byref(b), p(g_xyz), p(g_rot), p(g_scl), p(d_verts), p(d_own), p(d_rot), p(d_scl))
+        return (None, d_verts, d_own.view(own_shape) if d_own is not None else None, d_rot, d_scl, None, None, None, None, None,
+                None, None)
+
+
+def _bind(mode, verts, own, rotation, scaling, faces, face_index, bary=None, canon=None, shell_len=0.0, resize_scale=False,
+          frame=None):
+    if not mode.verts_grad:
+        _no_vertex_gradient(verts, mode.op)   # (before any other argument is touched)
+    return _Bind.apply(mode, verts, own, rotation, scaling, faces, face_index, bary, canon, shell_len, resize_scale, frame)
+
+
+def bind_gaussians(verts, faces, face_index, bary_coords, face_scale_canonical, offset, rotation, scaling,
+                   shell_len: float, resize_scale: bool = True):
+    """One frame of model/fateavatar.py:225-258.  verts [V,3] (posed), faces [F,3], face_index [N], bary_coords [N,3],
+    face_scale_canonical [F,1] (`face_scale` of the canonical mesh), raw offset [N,1] / rotation [N,4] / scaling [N,3].
+    Returns (xyz [N,3], rotation [N,4], scaling [N,3]): the values the reference assigns to gaussian._xyz /
+    gaussian._rotation / gaussian._scaling before render()."""
+    return _bind(SHELL, verts, offset, rotation, scaling, faces, face_index, bary_coords, face_scale_canonical, shell_len,
+                 resize_scale)
+
+
+def bind_gaussians_face_local(verts, faces, binding, local_xyz, rotation, scaling):
+    """One frame of model/baseline/gaussianavatars.py:144-171.  verts [V,3] (posed), faces [F,3], binding [N] (the face of
+    every Gaussian), raw local_xyz [N,3] / rotation [N,4] / scaling [N,3].  Returns (xyz [N,3], rotation [N,4],
+    scaling [N,3]): the values the reference assigns to gaussian._xyz / gaussian._rotation / gaussian._scaling before
+    render()."""
+    return _bind(FACE_LOCAL, verts, local_xyz, rotation, scaling, faces, binding)
 
 
 def bind_gaussians_phong(verts, faces, face_index, bary_coords, frame, uvd, rotation, scaling):
@@ -350,6 +283,4 @@ def bind_gaussians_phong(verts, faces, face_index, bary_coords, frame, uvd, rota
     scaling [N,3].  Returns (xyz [N,3], rotation [N,4], scaling [N,3]): the values the reference assigns to gaussian._xyz /
     gaussian._rotation / gaussian._scaling before render().  Only the third column of uvd is read; the first two columns of its
     gradient are zeros (the reference's forward likewise: they only steer its CPU triangle walk)."""
-    _no_vertex_gradient(verts, "bind_gaussians_phong")
-    vn, vq, ratio = frame
-    return _BindPhong.apply(uvd, rotation, scaling, verts, faces, face_index, bary_coords, vn, vq, ratio)
+    return _bind(PHONG, verts, uvd, rotation, scaling, faces, face_index, bary_coords, frame=frame)

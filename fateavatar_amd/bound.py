@@ -24,13 +24,16 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from .binding import (PhongCanonical, _chk, _chk_phong_frame, _desc, _desc_local, _desc_phong, _no_vertex_gradient,
-                      phong_frame)
+from .binding import (FACE_LOCAL, PHONG, SHELL, PhongCanonical, _check_shapes, _chk, _chk_phong_frame, _describe, _grad_buffer,
+                      _no_vertex_gradient, phong_frame)
 from .rasterizer import (_GRAD_NAMES, _any_grad, _backward_args, _forward_args, _forward_batch, _FrameGrads, _per_view_outputs,
                          _pick_forward_only, _SavedFrame, rasterize_gaussians_backward_batch)
 from .render import _result, _screenspace_points, _settings
 
 
+# Every binding class names its mode's record (`mode`, binding.BindMode) and has two methods: `describe_args()`, what
+# `binding._describe` takes behind the per-Gaussian parameters (nothing it does not read), and `per_view(posed_verts)`,
+# render_bound_batch's preparation: (the checked binding of every view, the vertices the views are rendered from).
 class MeshBinding(NamedTuple):
     """What does not change from frame to frame: model/fateavatar.py:120-164 (face_index, bary_coords), :84-85
     (face_scale_canonical), the mesh topology and the two configuration values of :256-258."""
@@ -41,12 +44,46 @@ class MeshBinding(NamedTuple):
     shell_len: float
     resize_scale: bool = True
 
+    mode = SHELL
+
+    def describe_args(self):
+        return self.bary_coords, self.face_scale_canonical, self.shell_len, self.resize_scale
+
+    def per_view(self, posed_verts):
+        mb = MeshBinding(_chk(self.faces, torch.int32, "faces"), _chk(self.face_index, torch.int32, "face_index"),
+                         _chk(self.bary_coords, torch.float32, "bary_coords"),
+                         _chk(self.face_scale_canonical, torch.float32, "face_scale_canonical")
+                         if self.face_scale_canonical is not None else None, float(self.shell_len), bool(self.resize_scale))
+        return [mb] * len(posed_verts), posed_verts
+
 
 class FaceLocalBinding(NamedTuple):
     """GaussianAvatars' binding (model/baseline/gaussianavatars.py:52-60,144-171): the mesh topology and the face of every
     Gaussian.  The per-Gaussian position in that face's frame is a parameter (the holder's `_xyz`), not part of this."""
     faces: torch.Tensor                   # [F,3] int32
     face_index: torch.Tensor              # [N]   int32 (the reference's `binding`)
+
+    mode = FACE_LOCAL
+
+    def describe_args(self):
+        return ()
+
+    def per_view(self, posed_verts):
+        mb = FaceLocalBinding(_chk(self.faces, torch.int32, "faces"), _chk(self.face_index, torch.int32, "face_index"))
+        return [mb] * len(posed_verts), posed_verts
+
+
+class _PhongView(NamedTuple):
+    """A PhongBinding of ONE view: with the outputs of that view's mesh pass in the canonical data's place."""
+    faces: torch.Tensor
+    face_index: torch.Tensor
+    bary_coords: torch.Tensor
+    frame: tuple                          # (vert_normals [V,3], vert_quats [V,4], face_ratio [F])
+
+    mode = PHONG
+
+    def describe_args(self):
+        return self.bary_coords, None, 0.0, False, self.frame
 
 
 class PhongBinding(NamedTuple):
@@ -58,65 +95,44 @@ class PhongBinding(NamedTuple):
     bary_coords: torch.Tensor             # [N,3]       (`sample_bary`)
     canonical: PhongCanonical
 
+    mode = PHONG
 
-class _PhongView(NamedTuple):
-    """A PhongBinding of ONE view: with the outputs of that view's mesh pass in the canonical data's place."""
-    faces: torch.Tensor
-    face_index: torch.Tensor
-    bary_coords: torch.Tensor
-    frame: tuple                          # (vert_normals [V,3], vert_quats [V,4], face_ratio [F])
-
-
-def _has_own_xyz(mb) -> bool:
-    """The binding's own per-Gaussian parameter is an [N,3] array (its gradient goes to fr_aux::d_local_xyz), not the offset."""
-    return isinstance(mb, (FaceLocalBinding, _PhongView))
-
-
-def _descriptor(mb, verts, first, rotation, scaling):
-    """The fr_binding of one view; `first` is the binding's own per-Gaussian parameter: offset [N,1] (MeshBinding), the
-    local position [N,3] (FaceLocalBinding) or uvd [N,3] (PhongBinding)."""
-    if isinstance(mb, FaceLocalBinding):
-        return _desc_local(verts, mb.faces, mb.face_index, first, rotation, scaling)
-    if isinstance(mb, _PhongView):
-        return _desc_phong(verts, mb.faces, mb.face_index, mb.bary_coords, mb.frame, first, rotation, scaling)
-    return _desc(verts, mb.faces, mb.face_index, mb.bary_coords, mb.face_scale_canonical, first, rotation, scaling, mb.shell_len,
-                 mb.resize_scale)
+    def per_view(self, posed_verts):
+        """One `binding.phong_frame` per distinct posed mesh, in front of the frame's launch chain; the vertices detached."""
+        faces, fidx = _chk(self.faces, torch.int32, "faces"), _chk(self.face_index, torch.int32, "face_index")
+        bary = _chk(self.bary_coords, torch.float32, "bary_coords")
+        V, frames, mbs = self.canonical.cano_verts.shape[0], {}, []
+        for verts in posed_verts:
+            _no_vertex_gradient(verts, "render_bound_batch")
+            if id(verts) not in frames:   # (views of one pose share its mesh pass)
+                frames[id(verts)] = _chk_phong_frame(phong_frame(self.canonical, verts), V, faces.shape[0], "render_bound_batch")
+            mbs.append(_PhongView(faces, fidx, bary, frames[id(verts)]))
+        return mbs, [v.detach() for v in posed_verts]
 
 
 class _RasterizeBoundBatch(torch.autograd.Function):
-    """Tensor arguments per view: (verts, offset, rotation, scaling, means2D, sh, opacities) — the RAW parameters, as
-    render() hands them over with `fused_activations`; with a FaceLocalBinding the local position [N,3] (with a PhongBinding:
-    uvd [N,3]) stands where the offset stands.  Outputs per view: those of `_SavedFrame`."""
+    """Tensor arguments per view: (verts, own, rotation, scaling, means2D, sh, opacities) — the RAW parameters, as render()
+    hands them over with `fused_activations`; `own` is the binding's own per-Gaussian parameter (offset [N,1], the local
+    position [N,3], uvd [N,3]: `BindMode.attr` of the holder).  Outputs per view: those of `_SavedFrame`."""
     PER_VIEW = 7
 
     @staticmethod
     def forward(ctx, settings, bindings, slots, forward_only, depth_alpha, *tensors):
         K, n = len(settings), _RasterizeBoundBatch.PER_VIEW
         assert len(tensors) == n * K and len(bindings) == K
-        ctx.bindings, ctx.slots, ctx.offset_shapes = bindings, slots, []
+        ctx.bindings, ctx.slots, ctx.own_shapes = bindings, slots, []
         empty = torch.Tensor([])
         views, viss, descs, bound, checked = [], [], [], [], []
         for k, (rs, mb) in enumerate(zip(settings, bindings)):
-            verts, offset, rotation, scaling, means2D, sh, opacities = tensors[n * k:n * k + n]
-            ctx.offset_shapes.append(tuple(offset.shape))
-            verts, offset = _chk(verts, torch.float32, "verts"), _chk(offset, torch.float32, "offset")
+            verts, own, rotation, scaling, means2D, sh, opacities = tensors[n * k:n * k + n]
+            ctx.own_shapes.append(tuple(own.shape))
+            verts, own = _chk(verts, torch.float32, "verts"), _chk(own, torch.float32, mb.mode.own)
             rotation, scaling = _chk(rotation, torch.float32, "rotation"), _chk(scaling, torch.float32, "scaling")
-            checked.append((verts, offset, rotation, scaling))   # (what the descriptor points at: alive until the launch, saved for the backward)
+            checked.append((verts, own, rotation, scaling))   # (what the descriptor points at: alive until the launch, saved for the backward)
             N, dev = mb.face_index.shape[0], verts.device
-            if isinstance(mb, FaceLocalBinding):
-                if verts.dim() != 2 or offset.shape != (N, 3) or rotation.shape != (N, 4) or scaling.shape != (N, 3):
-                    raise RuntimeError("render_bound_batch: verts [V,3], _xyz [N,3], rotation [N,4], scaling [N,3]")
-            elif isinstance(mb, _PhongView):
-                if verts.dim() != 2 or offset.shape != (N, 3) or rotation.shape != (N, 4) or scaling.shape != (N, 3) or \
-                        mb.bary_coords.shape != (N, 3):
-                    raise RuntimeError("render_bound_batch: verts [V,3], _uvd [N,3], rotation [N,4], scaling [N,3], bary [N,3]")
-            else:
-                if verts.dim() != 2 or offset.numel() != N or rotation.shape != (N, 4) or scaling.shape != (N, 3) or \
-                        mb.bary_coords.shape != (N, 3):
-                    raise RuntimeError("render_bound_batch: verts [V,3], offset [N,1], rotation [N,4], scaling [N,3], bary [N,3]")
-                if mb.resize_scale and (mb.face_scale_canonical is None or mb.face_scale_canonical.numel() != mb.faces.shape[0]):
-                    raise RuntimeError("render_bound_batch: resize_scale needs face_scale_canonical [F,1]")
-            descs.append(_descriptor(mb, verts, offset, rotation, scaling))
+            args = (mb.mode, verts, mb.faces, mb.face_index, own, rotation, scaling, *mb.describe_args())
+            _check_shapes("render_bound_batch", mb.mode.frame_shapes, *args)
+            descs.append(_describe(*args))
             # the bound values: written by the preprocess kernel, read again by the backward
             xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
             rot = torch.empty((N, 4), dtype=torch.float32, device=dev)
@@ -127,8 +143,8 @@ class _RasterizeBoundBatch(torch.autograd.Function):
         res = _forward_batch(views, slots, True, viss, descs, forward_only, depth_alpha)
         frames = []
         for k, rs in enumerate(settings):
-            verts, offset, rotation, scaling, means2D, sh, opacities = tensors[n * k:n * k + n]
-            grads = _FrameGrads({"dL_dsh": sh if sh.numel() else None, "dL_dopacity": opacities, "d_offset": offset,
+            verts, own, rotation, scaling, means2D, sh, opacities = tensors[n * k:n * k + n]
+            grads = _FrameGrads({"dL_dsh": sh if sh.numel() else None, "dL_dopacity": opacities, "d_own": own,
                                  "d_rotation": rotation, "d_scaling": scaling}, sh, bound=True)
             frames.append(_SavedFrame(rs, res[k], viss[k], means2D, grads, (*checked[k], sh, *bound[k])))
             res[k].radii._fr_bound = bound[k]           # (xyz, rotation, scaling) as bind_gaussians returns them
@@ -141,40 +157,31 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             return (None,) * (5 + n * K)
         empty = torch.Tensor([])
         views, outs, descs, bgrads, planes = [], [], [], [], []
-        for k, (f, own, fw, g, pl) in enumerate(_SavedFrame.load(ctx, grad_outs)):
-            (verts, offset, rotation, scaling, sh, xyz, rot, scl), mb = own, ctx.bindings[k]
+        for k, (f, saved, fw, g, pl) in enumerate(_SavedFrame.load(ctx, grad_outs)):
+            (verts, own, rotation, scaling, sh, xyz, rot, scl), mb = saved, ctx.bindings[k]
             dev, N = verts.device, xyz.shape[0]
             views.append(_backward_args(f.rs, (empty, xyz, scl, rot, empty, sh), fw, g))
             planes.append(pl)
             claimed = f.grads.claim(accumulate=False)[0]
             outs.append({m: b for m, b in claimed.items() if m.startswith("dL_")})
             need_v, need_o, need_r, need_s = ctx.needs_input_grad[5 + n * k:5 + n * k + 4]   # (after the 5 non-tensor arguments)
-
-            def buf(need, name, shape):
-                if not need:
-                    return None
-                b = claimed.get(name)
-                if b is not None and b.numel() == int(torch.Size(shape).numel()) and b.is_contiguous():
-                    return b.view(shape)
-                return torch.empty(shape, dtype=torch.float32, device=dev)
-
-            descs.append(_descriptor(mb, verts, offset, rotation, scaling))
-            # (the slot of the binding's own parameter is claimed as "d_offset" in both modes; the kernel's name differs)
-            first = {"d_local_xyz": buf(need_o, "d_offset", (N, 3))} if _has_own_xyz(mb) else \
-                {"d_offset": buf(need_o, "d_offset", (N,))}
-            bgrads.append({"d_verts": torch.zeros_like(verts) if need_v else None, **first,
-                           "d_rotation": buf(need_r, "d_rotation", (N, 4)), "d_scaling": buf(need_s, "d_scaling", (N, 3))})
+            descs.append(_describe(mb.mode, verts, mb.faces, mb.face_index, own, rotation, scaling, *mb.describe_args()))
+            # (the own parameter's gradient goes to the kernel under the name its mode has in fr_aux)
+            bgrads.append({"d_verts": torch.zeros_like(verts) if need_v else None,
+                           mb.mode.grad: _grad_buffer(need_o, claimed.get("d_own"), mb.mode.grad_shape(N), dev),
+                           "d_rotation": _grad_buffer(need_r, claimed.get("d_rotation"), (N, 4), dev),
+                           "d_scaling": _grad_buffer(need_s, claimed.get("d_scaling"), (N, 3), dev)})
         res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=[f.grads.want for f in ctx.frames],
                                                  outs=outs, stats=[f.stats for f in ctx.frames], bindings=descs, bind_grads=bgrads,
                                                  planes=planes if ctx.frames[0].has_planes else None)
         flat = [None, None, None, None, None]
-        for grads, b, offset_shape in zip(res, bgrads, ctx.offset_shapes):
+        for grads, b, mb, own_shape in zip(res, bgrads, ctx.bindings, ctx.own_shapes):
             g = dict(zip(_GRAD_NAMES, grads))
-            d_off = b["d_offset"] if "d_offset" in b else b["d_local_xyz"]
-            d_off = d_off.view(offset_shape) if d_off is not None else None
+            d_own = b[mb.mode.grad]
+            d_own = d_own.view(own_shape) if d_own is not None else None
             # (fresh view objects: AccumulateGrad adopts a gradient without a copy only if nobody else references it)
             fresh = lambda t: t.view(t.shape) if t is not None else None  # noqa: E731
-            flat += [b["d_verts"], d_off, fresh(b["d_rotation"]), fresh(b["d_scaling"]), g["dL_dmeans2D"], g["dL_dsh"], g["dL_dopacity"]]
+            flat += [b["d_verts"], d_own, fresh(b["d_rotation"]), fresh(b["d_scaling"]), g["dL_dmeans2D"], g["dL_dsh"], g["dL_dopacity"]]
         return tuple(flat)
 
 
@@ -202,49 +209,25 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding, bg_colors, 
         raise RuntimeError(f"render_bound_batch: 1 .. {_lib.FR_MAX_BATCH} views")
     if not isinstance(pcs, (list, tuple)):
         pcs = [pcs] * K
-    local = isinstance(binding, FaceLocalBinding)
-    if local:
-        for pc in pcs:
-            if getattr(pc, "_xyz", None) is None:
-                raise RuntimeError("render_bound_batch: a face-local binding (FaceLocalBinding) needs a holder with the local "
-                                   f"positions `_xyz` [N,3]; {type(pc).__name__} has none")
-    phong = isinstance(binding, PhongBinding)
-    if phong:
-        for pc in pcs:
-            if getattr(pc, "_uvd", None) is None:
-                raise RuntimeError("render_bound_batch: a Phong-surface binding (PhongBinding) needs a holder with the "
-                                   f"parameters `_uvd` [N,3]; {type(pc).__name__} has none")
+    mode = binding.mode
+    for pc in pcs:
+        if getattr(pc, mode.attr, None) is None:
+            raise RuntimeError(f"render_bound_batch: {mode.holder}; {type(pc).__name__} has none")
     if isinstance(bg_colors, torch.Tensor):
         bg_colors = [bg_colors] * K
     if isinstance(posed_verts, torch.Tensor):
         posed_verts = [posed_verts] * K
-    if phong:
-        faces, fidx = _chk(binding.faces, torch.int32, "faces"), _chk(binding.face_index, torch.int32, "face_index")
-        bary = _chk(binding.bary_coords, torch.float32, "bary_coords")
-        V, frames, mbs = binding.canonical.cano_verts.shape[0], {}, []
-        for verts in posed_verts:
-            _no_vertex_gradient(verts, "render_bound_batch")
-            if id(verts) not in frames:   # (views of one pose share its mesh pass)
-                frames[id(verts)] = _chk_phong_frame(phong_frame(binding.canonical, verts), V, faces.shape[0], "render_bound_batch")
-            mbs.append(_PhongView(faces, fidx, bary, frames[id(verts)]))
-        posed_verts = [v.detach() for v in posed_verts]
-    elif local:
-        mb = FaceLocalBinding(_chk(binding.faces, torch.int32, "faces"), _chk(binding.face_index, torch.int32, "face_index"))
-    else:
-        mb = MeshBinding(_chk(binding.faces, torch.int32, "faces"), _chk(binding.face_index, torch.int32, "face_index"),
-                         _chk(binding.bary_coords, torch.float32, "bary_coords"),
-                         _chk(binding.face_scale_canonical, torch.float32, "face_scale_canonical")
-                         if binding.face_scale_canonical is not None else None, float(binding.shell_len), bool(binding.resize_scale))
+    mbs, posed_verts = binding.per_view(posed_verts)
     settings, tensors, points = [], [], []
     for cam, pc, bg, verts in zip(viewpoint_cameras, pcs, bg_colors, posed_verts):
         sp = _screenspace_points(pc._scaling, pc)
         rs = _settings(cam, pc, bg, scaling_modifier)
-        if local:
+        if mode.active_sh:
             rs = rs._replace(sh_degree=int(getattr(pc, "active_sh_degree", pc.max_sh_degree)))
         settings.append(rs)
-        tensors += [verts, pc._uvd if phong else pc._xyz if local else pc._offset, pc._rotation, pc._scaling, sp, pc.get_features, pc._opacity]
+        tensors += [verts, getattr(pc, mode.attr), pc._rotation, pc._scaling, sp, pc.get_features, pc._opacity]
         points.append(sp)
-    res = _RasterizeBoundBatch.apply(settings, mbs if phong else [mb] * K, list(range(K)) if slots is None else list(slots),
+    res = _RasterizeBoundBatch.apply(settings, mbs, list(range(K)) if slots is None else list(slots),
                                      _pick_forward_only(tensors), bool(depth_alpha), *tensors)
     out = []
     for r, sp in zip(_per_view_outputs(res, K), points):

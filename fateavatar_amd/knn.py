@@ -15,14 +15,9 @@ def _knn(points: torch.Tensor, fn_name: str) -> torch.Tensor:
     means = torch.full((P,), 0.0, dtype=torch.float32, device=points.device)
     if P == 0:
         return means
-    L = _lib.lib()
-    ws_bytes = L.fr_knn_workspace_bytes(P)
+    ws_bytes = _lib.lib().fr_knn_workspace_bytes(P)
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=points.device)
-    with torch.cuda.device(dev):
-        rc = getattr(L, fn_name)(P, pts.data_ptr(), means.data_ptr(), ws.data_ptr(), ws_bytes,
-                                 torch.cuda.current_stream(dev).cuda_stream)
-    if rc != _lib.FR_OK:
-        raise RuntimeError(f"{fn_name} failed (code {rc}): {_lib.last_error()}")
+    _lib.launch(fn_name, dev, P, pts.data_ptr(), means.data_ptr(), ws.data_ptr(), ws_bytes)
     return means
 
 

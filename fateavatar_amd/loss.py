@@ -49,10 +49,9 @@ def l1_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, loss_out: Optional[tor
     if grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or loss.numel() != 1:
         raise RuntimeError("l1_loss_and_grad: bad output buffers")
     L = _lib.lib()
-    stream = torch.cuda.current_stream(dev).cuda_stream
     ws = workspace
     if ws is None:
-        key = (dev.index, stream)
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
         ws = _workspace.get(key)
         if ws is None:
             # (allocated on a side stream-independent path: torch.zeros inside a capture would become part of the graph)
@@ -62,11 +61,7 @@ def l1_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, loss_out: Optional[tor
             ws = _workspace[key] = l1_workspace(dev)
     elif not (ws.is_cuda and ws.device == dev and ws.dtype == torch.uint8 and ws.numel() >= L.fr_l1_workspace_bytes()):
         raise RuntimeError("l1_loss_and_grad: workspace must come from l1_workspace() on the image's device")
-    with torch.cuda.device(dev):
-        rc = L.fr_l1_loss_grad(img.numel(), img.data_ptr(), gt.data_ptr(), grad.data_ptr(), loss.data_ptr(), ws.data_ptr(),
-                               stream)
-    if rc != _lib.FR_OK:
-        raise RuntimeError(f"fr_l1_loss_grad failed: {_lib.last_error()}")
+    _lib.launch("fr_l1_loss_grad", dev, img.numel(), img.data_ptr(), gt.data_ptr(), grad.data_ptr(), loss.data_ptr(), ws.data_ptr())
     return loss, grad
 
 
@@ -90,11 +85,7 @@ def l1_loss_and_grad_batch(imgs, gts, loss_outs, grad_outs, workspaces):
         if not (w.is_cuda and w.device == dev and w.dtype == torch.uint8 and w.numel() >= L.fr_l1_workspace_bytes()) or l.numel() != 1:
             raise RuntimeError("l1_loss_and_grad_batch: workspaces from l1_workspace(), one-element loss tensors")
     arr = lambda ts: (C.c_void_p * K)(*[t.data_ptr() for t in ts])  # noqa: E731
-    with torch.cuda.device(dev):
-        rc = L.fr_l1_loss_grad_batch(K, n, arr(imgs), arr(gts), arr(grad_outs), arr(loss_outs), arr(workspaces),
-                                     torch.cuda.current_stream(dev).cuda_stream)
-    if rc != _lib.FR_OK:
-        raise RuntimeError(f"fr_l1_loss_grad_batch failed: {_lib.last_error()}")
+    _lib.launch("fr_l1_loss_grad_batch", dev, K, n, arr(imgs), arr(gts), arr(grad_outs), arr(loss_outs), arr(workspaces))
     return loss_outs, grad_outs
 
 
@@ -129,10 +120,9 @@ def gaussian_regularisers(scaling: torch.Tensor, xyz: torch.Tensor, d_scaling: O
     if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
         raise RuntimeError("gaussian_regularisers: `out` is a contiguous 2-element float32 tensor on the parameters' device")
     L = _lib.lib()
-    stream = torch.cuda.current_stream(dev).cuda_stream
     ws = workspace
     if ws is None:
-        key = (dev.index, stream)
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
         ws = _reg_workspace.get(key)
         if ws is None:
             if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
@@ -143,12 +133,9 @@ def gaussian_regularisers(scaling: torch.Tensor, xyz: torch.Tensor, d_scaling: O
         raise RuntimeError("gaussian_regularisers: workspace must come from regulariser_workspace() on the parameters' device")
     import ctypes as C
     cfg = _lib.fr_regularise_config(float(weights[0]), float(weights[1]), float(thresholds[0]), float(thresholds[1]))
-    with torch.cuda.device(dev):
-        rc = L.fr_gaussian_regularise(C.byref(cfg), P, scaling.data_ptr(), xyz.data_ptr(),
-                                      d_scaling.data_ptr() if d_scaling is not None else None,
-                                      d_xyz.data_ptr() if d_xyz is not None else None, loss.data_ptr(), ws.data_ptr(), stream)
-    if rc != _lib.FR_OK:
-        raise RuntimeError(f"fr_gaussian_regularise failed: {_lib.last_error()}")
+    _lib.launch("fr_gaussian_regularise", dev, C.byref(cfg), P, scaling.data_ptr(), xyz.data_ptr(),
+                d_scaling.data_ptr() if d_scaling is not None else None, d_xyz.data_ptr() if d_xyz is not None else None,
+                loss.data_ptr(), ws.data_ptr())
     return loss
 
 
@@ -184,8 +171,8 @@ def multi_copy(pairs) -> None:
             _copy_calls.clear()
         _copy_calls[key] = call
     n, dst, src, cnt = call
-    # (the raw handle of the device's current stream without building a torch.cuda.Stream object: 5 us of a host path that
-    # has to stay under the step's 130 us)
+    # (not `_lib.launch`: the raw handle of the device's current stream without building a torch.cuda.Stream object, and no
+    # device guard where the device is current: 5 us of a host path that has to stay under the step's 130 us)
     raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
     stream = raw(dev.index) if raw is not None else torch.cuda.current_stream(dev).cuda_stream
     if torch.cuda.current_device() == dev.index:
@@ -193,8 +180,7 @@ def multi_copy(pairs) -> None:
     else:
         with torch.cuda.device(dev):
             rc = _lib.lib().fr_multi_copy(n, dst, src, cnt, stream)
-    if rc != _lib.FR_OK:
-        raise RuntimeError(f"fr_multi_copy failed: {_lib.last_error()}")
+    _lib.check(rc, "fr_multi_copy")
 
 
 def scaled_sum(dst: torch.Tensor, srcs, scale: float) -> torch.Tensor:
@@ -209,11 +195,7 @@ def scaled_sum(dst: torch.Tensor, srcs, scale: float) -> torch.Tensor:
         if not t.is_cuda or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != dst.numel():
             raise RuntimeError("scaled_sum: contiguous float32 tensors of one device and one size")
     ptrs = (C.c_void_p * len(srcs))(*[t.data_ptr() for t in srcs])
-    with torch.cuda.device(dev):
-        rc = _lib.lib().fr_scaled_sum(len(srcs), ptrs, dst.data_ptr(), dst.numel(), float(scale),
-                                      torch.cuda.current_stream(dev).cuda_stream)
-    if rc != _lib.FR_OK:
-        raise RuntimeError(f"fr_scaled_sum failed: {_lib.last_error()}")
+    _lib.launch("fr_scaled_sum", dev, len(srcs), ptrs, dst.data_ptr(), dst.numel(), float(scale))
     return dst
 
 
@@ -280,11 +262,8 @@ def image_loss_and_grad_batch(imgs, gts, weights, loss_outs, grad_outs, workspac
             raise RuntimeError("image_loss_and_grad_batch: contiguous 3-element float32 loss tensors on the images' device")
     arr = lambda ts: (C.c_void_p * K)(*[None if t is None else t.data_ptr() for t in ts])  # noqa: E731
     cfg = _lib.fr_image_loss_config(float(weights[0]), float(weights[1]))
-    with torch.cuda.device(dev):
-        rc = L.fr_image_loss_grad(C.byref(cfg), K, shape[0], shape[1], shape[2], arr(imgs), arr(gts), arr(grad_outs), arr(loss_outs),
-                                  arr(workspaces), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != _lib.FR_OK:
-        raise RuntimeError(f"fr_image_loss_grad failed: {_lib.last_error()}")
+    _lib.launch("fr_image_loss_grad", dev, C.byref(cfg), K, shape[0], shape[1], shape[2], arr(imgs), arr(gts), arr(grad_outs),
+                arr(loss_outs), arr(workspaces))
     return loss_outs, grad_outs
 
 

@@ -119,22 +119,16 @@ class FusedAdam:
         parameters), on their SUM: the views of a batch back-propagate into a buffer each, and grad_scale makes the sum
         the batch mean."""
         dev = self.param.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if grads is None:
-                rc = _lib.lib().fr_adam_step(C.byref(self.cfg), self.param.data_ptr(), self.grad.data_ptr(),
-                                             self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.param.numel(),
-                                             self.state.data_ptr(), stream)
-            else:
-                for g in grads:
-                    if g.shape != self.param.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev:
-                        raise RuntimeError("FusedAdam.step: gradient buffers must look like the parameter buffer")
-                ptrs = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
-                rc = _lib.lib().fr_adam_step_multi(C.byref(self.cfg), self.param.data_ptr(), ptrs, len(grads),
-                                                   self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.param.numel(),
-                                                   self.state.data_ptr(), stream)
-        if rc != _lib.FR_OK:
-            raise RuntimeError(f"fr_adam_step failed: {_lib.last_error()}")
+        if grads is None:
+            _lib.launch("fr_adam_step", dev, C.byref(self.cfg), self.param.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
+                        self.exp_avg_sq.data_ptr(), self.param.numel(), self.state.data_ptr())
+        else:
+            for g in grads:
+                if g.shape != self.param.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev:
+                    raise RuntimeError("FusedAdam.step: gradient buffers must look like the parameter buffer")
+            ptrs = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+            _lib.launch("fr_adam_step_multi", dev, C.byref(self.cfg), self.param.data_ptr(), ptrs, len(grads), self.exp_avg.data_ptr(),
+                        self.exp_avg_sq.data_ptr(), self.param.numel(), self.state.data_ptr())
 
     STATE_WORDS = 8   # what a checkpoint has to carry: the step, the float corrections and the doubles behind them
 

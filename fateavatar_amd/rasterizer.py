@@ -45,11 +45,6 @@ def _ptrs(*tensors) -> list:
     return [0 if t is None or t.numel() == 0 else t.data_ptr() for t in tensors]
 
 
-def _check(rc: int, what: str):
-    if rc != _lib.FR_OK:
-        raise RuntimeError(f"{what} failed (code {rc}): {_lib.last_error()}")
-
-
 # When True, forwards never wait for their instance counts (graph-capturable, zero host syncs): the binning
 # capacity is the current high-water mark and overflow is only detected by `check_async_overflow()`.
 _no_wait = False
@@ -133,7 +128,7 @@ class handle_slot:
 def read_counts(device_index: int = 0, slot: int | None = None):
     """fr_counts of the most recent frame on this device (synchronise first)."""
     c = _lib.fr_counts()
-    _check(_lib.lib().fr_read_counts(_lib.handle(device_index, _slot if slot is None else slot), C.byref(c)), "fr_read_counts")
+    _lib.check(_lib.lib().fr_read_counts(_lib.handle(device_index, _slot if slot is None else slot), C.byref(c)), "fr_read_counts")
     return c
 
 
@@ -343,7 +338,7 @@ def _launch_forward(views, slots, batch):
             for v, c in zip(views, counts):
                 if c.overflow:
                     v["cap"] = int(c.num_instances * 1.25) + 1024
-    _check(rc, "fr_forward_batch" if batch else "fr_forward")
+    _lib.check(rc, "fr_forward_batch" if batch else "fr_forward")
     out = []
     last_forward_only[dev] = bool(views[0]["prm"].flags & _lib.FR_FLAG_FORWARD_ONLY)
     for v, c in zip(views, counts):
@@ -372,7 +367,7 @@ def _launch_backward(views, slots, batch):
             rc = L.fr_backward(_lib.handle(dev, slots[0]), C.byref(v["prm"]), C.byref(v["inp"]), v["radii"].data_ptr(),
                                v["geom"].data_ptr(), v["img"].data_ptr(), v["binning"].data_ptr(), v["dpix"].data_ptr(),
                                C.byref(v["grads"]), stream)
-    _check(rc, "fr_backward_batch" if batch else "fr_backward")
+    _lib.check(rc, "fr_backward_batch" if batch else "fr_backward")
     return [tuple(v["g"].values()) for v in views]
 
 
@@ -538,10 +533,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     present = torch.zeros((P,), dtype=torch.bool, device=means3D.device)
     if P != 0:
         means3D, viewmatrix, projmatrix = _f32c(means3D, viewmatrix, projmatrix)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().fr_mark_visible(P, means3D.data_ptr(), viewmatrix.data_ptr(), projmatrix.data_ptr(),
-                                            present.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        _check(rc, "fr_mark_visible")
+        _lib.launch("fr_mark_visible", dev, P, means3D.data_ptr(), viewmatrix.data_ptr(), projmatrix.data_ptr(), present.data_ptr())
     return present
 
 

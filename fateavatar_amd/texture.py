@@ -117,11 +117,7 @@ class TexturePlan:
     def corners(self) -> torch.Tensor:
         """[N,4] int32: the texel index (y * W + x) of every point's four corners, -1 past the border (fr_texture_corners)."""
         out = torch.empty((self.N, 4), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().fr_texture_corners(self.N, self.uv.data_ptr(), self.H, self.W, out.data_ptr(),
-                                               torch.cuda.current_stream(self.device).cuda_stream)
-        if rc != _lib.FR_OK:
-            raise RuntimeError(f"fr_texture_corners failed: {_lib.last_error()}")
+        _lib.launch("fr_texture_corners", self.device, self.N, self.uv.data_ptr(), self.H, self.W, out.data_ptr())
         return out
 
     @property
@@ -165,11 +161,7 @@ class _TextureLookup(torch.autograd.Function):
                 raise RuntimeError(f"texture_lookup: texture {i} is on {t.device}, the plan on {dev}")
         tex = [t.contiguous() for t in textures]
         outs = [torch.empty((plan.N, t.shape[-3]), dtype=torch.float32, device=dev) for t in tex]
-        with torch.cuda.device(dev):
-            rc = _lib.lib().fr_texture_lookup(plan.N, plan.uv.data_ptr(), plan.H, plan.W, len(tex), _layers(tex, acts, outs=outs),
-                                              torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.FR_OK:
-            raise RuntimeError(f"fr_texture_lookup failed: {_lib.last_error()}")
+        _lib.launch("fr_texture_lookup", dev, plan.N, plan.uv.data_ptr(), plan.H, plan.W, len(tex), _layers(tex, acts, outs=outs))
         ctx.plan, ctx.acts = plan, acts
         ctx.save_for_backward(*tex)
         return tuple(outs)
@@ -184,12 +176,8 @@ class _TextureLookup(torch.autograd.Function):
             g_in = [d_outs[i].to(torch.float32).contiguous() for i in sel]
             d_tex = [torch.empty(tex[i].shape, dtype=torch.float32, device=dev) for i in sel]   # (planar [C,H,W], contiguous)
             layers = _layers([tex[i] for i in sel], [ctx.acts[i] for i in sel], d_outs=g_in, d_textures=d_tex)
-            with torch.cuda.device(dev):
-                rc = _lib.lib().fr_texture_lookup_backward(plan.N, plan.uv.data_ptr(), plan.H, plan.W, row_start.data_ptr(),
-                                                           entries.data_ptr(), len(sel), layers,
-                                                           torch.cuda.current_stream(dev).cuda_stream)
-            if rc != _lib.FR_OK:
-                raise RuntimeError(f"fr_texture_lookup_backward failed: {_lib.last_error()}")
+            _lib.launch("fr_texture_lookup_backward", dev, plan.N, plan.uv.data_ptr(), plan.H, plan.W, row_start.data_ptr(),
+                        entries.data_ptr(), len(sel), layers)
             for i, d in zip(sel, d_tex):
                 grads[i] = d
         return (None, None, *grads)

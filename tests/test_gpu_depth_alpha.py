@@ -407,7 +407,7 @@ def _bound_frames(apc, mb, acams, posed, slots, depth_alpha):
     import torch
     from fateavatar_amd import rasterizer
     from fateavatar_amd.avatar import _RawFrame
-    from fateavatar_amd.binding import _chk, _desc
+    from fateavatar_amd.binding import SHELL, _chk, _describe
     from fateavatar_amd.render import _settings
     bg = torch.ones(3, device=apc._offset.device)
     views, viss, descs, bound, keep = [], [], [], [], []
@@ -416,11 +416,11 @@ def _bound_frames(apc, mb, acams, posed, slots, depth_alpha):
         xyz, rot, scl = (torch.empty((N, c), device=dev) for c in (3, 4, 3))
         # (the descriptor holds raw pointers: every tensor it names stays referenced until the launch)
         t = [_chk(posed[k], torch.float32, "verts"), _chk(mb.faces, torch.int32, "faces"), _chk(mb.face_index, torch.int32, "fi"),
-             _chk(mb.bary_coords, torch.float32, "bary"), _chk(mb.face_scale_canonical, torch.float32, "canon"),
              _chk(apc._offset.detach(), torch.float32, "offset"), _chk(apc._rotation.detach(), torch.float32, "rotation"),
-             _chk(apc._scaling.detach(), torch.float32, "scaling")]
+             _chk(apc._scaling.detach(), torch.float32, "scaling"),
+             _chk(mb.bary_coords, torch.float32, "bary"), _chk(mb.face_scale_canonical, torch.float32, "canon")]
         keep.append(t)
-        descs.append(_desc(*t, mb.shell_len, mb.resize_scale))
+        descs.append(_describe(SHELL, *t, mb.shell_len, mb.resize_scale))
         rs = _settings(cam, _RawFrame(apc, None), bg, 1.0)
         views.append(rasterizer._forward_args(rs, xyz, None, apc._features_dc.detach(), torch.empty(0), apc._opacity.detach(), scl,
                                               rot, torch.empty(0)))

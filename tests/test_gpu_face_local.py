@@ -384,7 +384,7 @@ def test_zeroed_mode_field_is_the_shell_binding(gpu_device):
     import torch
     from fateavatar_amd import _lib, mesh_sampling, rasterizer, scenes
     from fateavatar_amd.avatar import AvatarGaussians, _BoundFrame
-    from fateavatar_amd.binding import _desc, bind_gaussians, face_scale
+    from fateavatar_amd.binding import SHELL, _describe, bind_gaussians, face_scale
     from fateavatar_amd.render import _screenspace_points, _settings, render
     dev = gpu_device
     S = _template(dev, 128, 2)
@@ -401,8 +401,8 @@ def test_zeroed_mode_field_is_the_shell_binding(gpu_device):
     empty = torch.Tensor([])
 
     def frame(write_mode):
-        b = _desc(verts, S["faces"], pc.face_index, pc.bary_coords, canon, pc._offset.detach(), pc._rotation.detach(),
-                  pc._scaling.detach(), 0.05, True)
+        b = _describe(SHELL, verts, S["faces"], pc.face_index, pc._offset.detach(), pc._rotation.detach(), pc._scaling.detach(),
+                      pc.bary_coords, canon, 0.05, True)
         if write_mode:
             b.mode = _lib.FR_BIND_SHELL
         assert b.mode == 0 and not b.local_xyz

@@ -410,7 +410,7 @@ def test_plain_descriptor_is_the_shell_binding_and_face_local_frames_keep_their_
     import torch
     from fateavatar_amd import _lib, mesh_sampling, rasterizer, scenes
     from fateavatar_amd.avatar import AvatarGaussians, _BoundFrame
-    from fateavatar_amd.binding import _desc, bind_gaussians, face_scale
+    from fateavatar_amd.binding import SHELL, _describe, bind_gaussians, face_scale
     from fateavatar_amd.bound import FaceLocalBinding, PhongBinding, render_bound_batch
     from fateavatar_amd.render import _screenspace_points, _settings, render
     from fateavatar_amd.rigged import RiggedGaussians, _RiggedFrame
@@ -428,8 +428,8 @@ def test_plain_descriptor_is_the_shell_binding_and_face_local_frames_keep_their_
     verts, cam, bg = S["posed"][1].contiguous(), S["cams"][1], torch.ones(3, device=dev)
     rs = _settings(cam, pc, bg, 1.0)
     empty = torch.Tensor([])
-    b = _desc(verts, S["faces"], pc.face_index, pc.bary_coords, canon, pc._offset.detach(), pc._rotation.detach(),
-              pc._scaling.detach(), 0.05, True)
+    b = _describe(SHELL, verts, S["faces"], pc.face_index, pc._offset.detach(), pc._rotation.detach(), pc._scaling.detach(),
+                  pc.bary_coords, canon, 0.05, True)
     assert type(b) is _lib.fr_binding and b.mode == _lib.FR_BIND_SHELL and not b.local_xyz      # no Phong tail at all
     xyz, rot, scl = (torch.empty((pc.P, k), device=dev) for k in (3, 4, 3))
     sp = _screenspace_points(xyz, pc)
