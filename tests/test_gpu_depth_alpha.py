@@ -4,7 +4,10 @@ The reference is the project's own pinned path: the depth plane is what a frame 
 channel 0 with colors_precomp = (z, 0, 0) (z: the view-space depth, computed in torch) over bg = (0, 1, 0), and the alpha
 plane is 1 - channel 1 of that frame.  Gradients of <gC, C> + <gD, D> + <gA, A> from ONE planes frame are compared with the
 sum over the plain frame (gC) and that composite frame (gD on channel 0, -gA on channel 1), dL/dz carried into means3D in
-torch.  Frames with planes leave every plain output as it was, bit for bit."""
+torch.  Frames with planes leave every plain output as it was, bit for bit.
+
+Where the planes meet the CPU oracle directly (long tile lists, every sort tier, dead trailing units, one plane gradient at a
+time): tests/test_gpu_planes_long_lists.py, with the reference of tests/planes_ref.py."""
 import os
 import subprocess
 import sys

@@ -151,11 +151,11 @@ def test_planes_instance_across_a_boundary(gpu_device):
     pixels whose blend sequence flipped against the oracle get no gradient."""
     import torch
     from fateavatar_amd import rasterizer
-    from oracle import oracle
+    from tests.planes_ref import PlanesRef
     P = 97
     s = _scene(P, 0.5)
-    c = s.camera
-    o = util.oracle_forward(s)
+    ref = PlanesRef(s)   # (the oracle's plain and composite frames; asserts that their radii agree)
+    o = ref.o
     _has_both(o, P)
     v = util._Frame()
     v._upload(s, gpu_device)
@@ -175,25 +175,9 @@ def test_planes_instance_across_a_boundary(gpu_device):
         got = rasterizer.rasterize_gaussians_backward(*v._backward_args(t(gC)), _planes=(res[8], t(gD), t(gA)))
         torch.cuda.synchronize()
     got = {k: a.cpu().numpy() for k, a in zip(util.GRAD_NAMES, got)}
-    m = c.world_view_transform.astype(np.float32).reshape(-1)
-    z = (s.means3D[:, 0] * m[2] + s.means3D[:, 1] * m[6] + s.means3D[:, 2] * m[10] + m[14]).astype(np.float32)
-    comp = oracle.forward(bg=np.array([0.0, 1.0, 0.0], np.float32), means3D=s.means3D, opacities=s.opacities,
-                          viewmatrix=c.world_view_transform, projmatrix=c.full_proj_transform, campos=c.camera_center,
-                          tanfovx=c.tanfovx, tanfovy=c.tanfovy, H=64, W=64, sh_degree=s.sh_degree,
-                          colors_precomp=np.stack([z, np.zeros_like(z), np.zeros_like(z)], 1), scales=s.scales, rotations=s.rotations)
-    assert np.array_equal(comp.radii, o.radii)
-    b_plain = oracle.backward(o, gC)
-    b_comp = oracle.backward(comp, np.stack([gD, -gA, np.zeros_like(gD)]))
-    dz = b_comp.dL_dcolors[:, 0:1]
+    want = ref.sum_gradients(gC, np.stack([gD, -gA, np.zeros_like(gD)]))
     culled = o.radii <= 0
     for k in util.GRAD_NAMES:
-        a, b = getattr(b_plain, k), getattr(b_comp, k)
-        if k in ("dL_dcolors", "dL_dsh"):
-            want = a                                   # (the composite colours are not the frame's parameters)
-        elif k == "dL_dmeans3D":
-            want = a + b + dz * m[[2, 6, 10]].reshape(1, 3)
-        else:
-            want = a + b
         assert np.isfinite(got[k]).all(), k
-        assert util.rel_l2(got[k], want) <= 1e-4, (k, util.rel_l2(got[k], want))
+        assert util.rel_l2(got[k], want[k]) <= 1e-4, (k, util.rel_l2(got[k], want[k]))
         assert np.all(got[k][culled] == 0.0), k
