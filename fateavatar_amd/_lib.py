@@ -111,7 +111,7 @@ class fr_counts(C.Structure):
 EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile_enable", "fr_profile_read", "fr_geometry_bytes", "fr_image_bytes",
            "fr_binning_bytes", "fr_planes_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
            "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
-           "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_phong_frame", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward"]
+           "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_phong_frame", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward"]
 
 
 def build(force: bool = False) -> str:
@@ -203,6 +203,12 @@ def lib():
     L.fr_bind_backward_phong.restype = C.c_int
     L.fr_phong_frame.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
     L.fr_phong_frame.restype = C.c_int
+    # (the stream is the FIRST argument of these two: `launch_first`)
+    L.fr_triwalk.argtypes = [C.c_void_p, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int32, C.c_float, _fp]
+    L.fr_triwalk.restype = C.c_int
+    L.fr_phong_fit.argtypes = [C.c_void_p, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int32, C.c_int32,
+                               C.c_float, _fp, _fp, _fp]
+    L.fr_phong_fit.restype = C.c_int
     L.fr_texture_corners.argtypes = [C.c_int32, _fp, C.c_int32, C.c_int32, _fp, C.c_void_p]
     L.fr_texture_corners.restype = C.c_int
     L.fr_texture_lookup.argtypes = [C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(fr_tex_layer), C.c_void_p]
@@ -277,6 +283,15 @@ def launch(name: str, device, *args) -> None:
 
     with torch.cuda.device(device):
         rc = getattr(lib(), name)(*args, torch.cuda.current_stream(device).cuda_stream)
+    check(rc, name)
+
+
+def launch_first(name: str, device, *args) -> None:
+    """`launch` for an entry point whose stream is its FIRST argument (fr_triwalk, fr_phong_fit)."""
+    import torch
+
+    with torch.cuda.device(device):
+        rc = getattr(lib(), name)(torch.cuda.current_stream(device).cuda_stream, *args)
     check(rc, name)
 
 

@@ -85,6 +85,33 @@ def phong_canonical(cano_verts: torch.Tensor, faces: torch.Tensor) -> PhongCanon
                           area.contiguous())
 
 
+def triangle_neighbours(faces: torch.Tensor) -> torch.Tensor:
+    """The edge neighbour table of the walk on the mesh (initTriangleNeighbor, submodules/simple_phongsurf/simple_phongsurf/
+    src/triangle_walk.cpp:176-237), once per mesh, in plain torch on the tensor's device: int32 [F,3]; entry [f, j] describes
+    the directed edge faces[f,j] -> faces[f,(j+1)%3] and holds 4 g + k of the face g and edge k that carry the reversed
+    directed edge, or -1 if there is none (a boundary edge).  Defined for meshes in which every directed edge occurs at most
+    once: ValueError otherwise (the reference's std::map silently keeps the last duplicate)."""
+    f = faces.detach().to(torch.int64)
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise RuntimeError("triangle_neighbours: faces [F,3]")
+    F = int(f.shape[0])
+    if F == 0:
+        return torch.zeros((0, 3), dtype=torch.int32, device=f.device)
+    if int(f.min()) < 0:
+        raise ValueError("triangle_neighbours: negative vertex index")
+    a, b = f.reshape(-1), f.roll(-1, dims=1).reshape(-1)          # edge 3 f + j runs a -> b
+    V = int(f.max()) + 1
+    key, rev = a * V + b, b * V + a
+    skey, order = torch.sort(key)
+    if bool((skey[1:] == skey[:-1]).any()):
+        raise ValueError("triangle_neighbours: a directed edge occurs more than once (the mesh is not an oriented manifold)")
+    pos = torch.searchsorted(skey, rev).clamp(max=3 * F - 1)
+    found = skey[pos] == rev
+    other = order[pos]                                            # = 3 g + k
+    out = torch.where(found, 4 * (other // 3) + other % 3, torch.full_like(other, -1))
+    return out.reshape(F, 3).to(torch.int32).contiguous()
+
+
 def phong_frame(canonical: PhongCanonical, verts: torch.Tensor):
     """One frame of model/baseline/splattingavatar.py:203-215 for the posed `verts` [V,3]: (vert_normals [V,3],
     vert_quats [V,4], face_ratio [F]) — one launch on the current stream, the same bits on every call.  Not differentiable."""

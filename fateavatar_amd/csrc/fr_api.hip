@@ -474,6 +474,27 @@ int fr_phong_frame(int32_t V, int32_t F, const float* verts, const float* cano_v
                               face_ratio, static_cast<hipStream_t>(stream));
 }
 
+int fr_triwalk(void* stream, const int32_t* faces_nbr, int32_t F, int32_t n, int32_t* face_index, float* bary, const float* delta,
+               int32_t delta_stride, float decay, int32_t* status)
+{
+    if (n < 0 || F < 0 || delta_stride < 2) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_triwalk: negative size, or delta_stride < 2");
+    if (n > 0 && (!faces_nbr || !face_index || !bary || !delta || !status)) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_triwalk: null array");
+    return launch_triwalk(faces_nbr, F, n, face_index, bary, delta, delta_stride, decay, status, static_cast<hipStream_t>(stream));
+}
+
+int fr_phong_fit(void* stream, const float* cano_verts, const float* cano_normals, const int32_t* faces, const int32_t* faces_nbr,
+                 int32_t V, int32_t F, int32_t n, const float* query, int32_t* face_index, float* bary, int32_t outer_loop,
+                 int32_t inner_loop, float decay, int32_t* work, int32_t* status, float* delta_out)
+{
+    if (n < 0 || F < 0 || V < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_fit: negative size");
+    if (inner_loop < 1 || inner_loop > 512) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_fit: inner_loop must be 1 .. 512");
+    if (outer_loop < 1 || outer_loop > 8) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_fit: outer_loop must be 1 .. 8");
+    if (n > 0 && (!cano_verts || !cano_normals || !faces || !faces_nbr || !query || !face_index || !bary || !work || !status))
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_fit: null array");
+    return launch_phong_fit(cano_verts, cano_normals, faces, faces_nbr, V, F, n, query, face_index, bary, outer_loop, inner_loop, decay,
+                            work, status, delta_out, static_cast<hipStream_t>(stream));
+}
+
 int fr_adam_step(const fr_adam_config* cfg, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                  uint64_t n, float* state, void* stream)
 {

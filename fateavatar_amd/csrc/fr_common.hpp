@@ -460,6 +460,12 @@ int launch_face_scale(int F, const float* verts, const int* faces, float* out, h
 int launch_phong_frame(int V, int F, const float* verts, const float* cano_verts, const int* faces, const int* vf_offsets,
                        const int* vf_faces, const float* area_cano, float* vert_normals, float* vert_quats, float* face_ratio,
                        hipStream_t s);
+// the walk on the triangle mesh and the Phong-surface fit (fr_phongsurf.hip)
+int launch_triwalk(const int* nbr, int F, int n, int* face_index, float* bary, const float* delta, int delta_stride, float decay,
+                   int* status, hipStream_t s);
+int launch_phong_fit(const float* verts, const float* normals, const int* faces, const int* nbr, int V, int F, int n, const float* query,
+                     int* face_index, float* bary, int outer_loop, int inner_loop, float decay, int* work, int* status, float* delta_out,
+                     hipStream_t s);
 int launch_adam(const fr_adam_config& cfg, float* param, const float* const* grad_bufs, int n_grads, float* exp_avg,
                 float* exp_avg_sq, unsigned long long n, float* state, hipStream_t s);
 int launch_l1_loss_grad_batch(int n_images, unsigned long long n, const float* const* img, const float* const* gt, float* const* grad,

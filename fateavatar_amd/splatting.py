@@ -15,14 +15,21 @@ What is fused: the mesh pass is one launch, the per-Gaussian binding runs inside
 densification statistics run inside the rasterizer kernels, one L1 launch, one Adam launch over the flat buffer, the whole
 step — mesh pass included — ONE HIP graph.
 
+  * density control and the triangle walk — `_densify_and_prune`, `_clone_densify`, `_split_densify`, `_prune`,
+    `_walking_on_triangles`, `_reset_opacity` (:386-715): `SplattingStep.densify_and_prune / prune / prune_low_opacity /
+    walk_on_triangles / reset_opacity`, between step() calls.  The reference's schedule (config/splattingavatar.yaml:35-44,
+    train/iteration.py:271-298) densifies every 100 steps from 600, resets opacity every 3 500 and walks every 100.  What the
+    reference keeps on the CPU for this (submodules/simple_phongsurf: the C++ walk, and `update_corres_spt`'s ~100 x 40 small
+    launches and four blocking copies per densification) is two HIP kernels here (`phongsurf.PhongSurface`): the walk moves
+    the embedding in place, so the captured step survives it.  With the reference's forward, which reads `_uvd[..., -1:]`
+    alone, the `u, v` columns of `_uvd` only ever hold zeros and the walk leaves every interior Gaussian where it is — exactly
+    as in the reference.
+
 NOT here:
-  * triangle walking and `update_corres_spt` (CPU C++ in submodules/simple_phongsurf, every `triangle_walk_interval` steps):
-    without it a Gaussian stays on its face and the `u, v` columns of `_uvd` only ever receive zero gradient — exactly as in
-    the reference's forward, which reads `_uvd[..., -1:]` alone
-  * SplattingAvatar's density control (:262-716) and opacity reset
   * its MSE / scale / LPIPS loss terms (config/splattingavatar.yaml:13-20): the image term is L1 (`rgb_loss` 1.0)
   * gradients to the posed vertices (the reference's tracking / deformer rates): the mesh pass is not differentiable
-  * data-parallel runs of the step
+  * data-parallel runs of the step (`reduce_densification_stats`)
+  * `max_radii2D` (see `densify_and_prune`)
 """
 from __future__ import annotations
 
@@ -36,10 +43,13 @@ from .bound import PhongBinding, render_bound_batch
 from .flat import FlatParams
 from .gs_utils import RGB2SH
 from .model import TorchCamera
+from .phongsurf import PhongSurface, triwalk
 from .render import render
+from .rigged import build_rotation
 from .train import BoundStep
 
 # config/splattingavatar.yaml:26-30 (group names of train/optim.py:106-117)
+PERCENT_DENSE = 0.01        # splattingavatar.py: percent_dense
 SPLATTING_LRS = dict(uvd=0.00016, opacity=0.05, feature_dc=0.0025, feature_rest=0.0025 / 20, rotation=0.001, scaling=0.005)
 NUM_INIT_SAMPLES = 10_000   # config/splattingavatar.yaml:23
 
@@ -59,8 +69,8 @@ def sample_bary_on_triangles(num_faces: int, num_samples: int, generator: Option
 
 class SplattingGaussians(FlatParams):
     """SplattingAvatar's Gaussian parameters in ONE flat buffer, in the order of the optimizer groups (train/optim.py:106-117).
-    `face_index` [P] / `bary_coords` [P,3] are every Gaussian's embedding (`sample_fidxs`, `sample_bary`); they stay fixed
-    (no triangle walk, see the module docstring)."""
+    `face_index` [P] / `bary_coords` [P,3] are every Gaussian's embedding (`sample_fidxs`, `sample_bary`): moved in place by
+    `SplattingStep.walk_on_triangles`, rebuilt with the rows by the density control."""
     max_sh_degree = 0        # :217
     FIELDS = (("_uvd", 3), ("_opacity", 1), ("_features_dc", 3), ("_features_rest", 0), ("_rotation", 4), ("_scaling", 3))
     SHAPES = {"_uvd": (3,), "_opacity": (1,), "_features_dc": (1, 3), "_features_rest": (0, 3), "_rotation": (4,),
@@ -159,11 +169,141 @@ class SplattingStep(BoundStep):
         pc.collect_grads()
         self.out = self._kept(out)
 
-    # ---- SplattingAvatar's density control and opacity reset are out of scope (module docstring)
-    def _unsupported(self, *a, **k):
-        raise NotImplementedError("SplattingStep: SplattingAvatar's density control is not built (DESIGN.md)")
+    # ---- SplattingAvatar's density control, triangle walk and opacity reset (:386-715), with RiggedStep's conventions: torch
+    #      index surgery under no_grad between step() calls, optimizer state through FusedAdam.remap_rows, the graph dropped
+    #      when the buffers move; `reset_opacity` is TrainStep's (:697-715 is the same rule), in place
+    @property
+    def phongsurf(self) -> PhongSurface:
+        """The canonical mesh's Phong surface as the reference constructs it (:122-125: outer_loop 2, inner_loop 50, 'uvd'), with
+        the canonical vertex normals `phong_frame(canonical, cano_verts)[0]`.  Made on first use."""
+        if getattr(self, "_phongsurf", None) is None:
+            c = self.canonical
+            self._phongsurf = PhongSurface(c.cano_verts, c.faces, phong_frame(c, c.cano_verts)[0], outer_loop=2, inner_loop=50,
+                                           method="uvd")
+        return self._phongsurf
 
-    prune_low_opacity = densify_by_gradient = reset_opacity = reduce_densification_stats = _unsupported
+    @torch.no_grad()
+    def walk_on_triangles(self) -> None:
+        """_walking_on_triangles (:668-695): every Gaussian walks over the mesh by `_uvd[:, :2]` (one launch, in place: the
+        embedding buffers, the parameters and the moments keep their addresses, so the captured step and the step count are
+        kept), then those two columns and the matching columns of both Adam moments are zeroed."""
+        pc, surf = self.pc, self.phongsurf
+        triwalk(surf.faces_nbr, pc.face_index, pc.bary_coords, pc._uvd.detach(), surf.status, surf.decay)
+        pc._uvd.data[:, :2] = 0
+        i, P = self._field_index("_uvd"), pc.P
+        off = P * sum(pc.widths()[:i])
+        for m in (self.adam.exp_avg, self.adam.exp_avg_sq):
+            m[off:off + 3 * P].view(P, 3)[:, :2] = 0
+
+    @torch.no_grad()
+    def _append(self, rows, face_index, bary) -> int:
+        """Appends `rows` (FIELDS order) embedded at (`face_index`, `bary`) with zero moments; the statistics restart from zero
+        whether or not anything was appended (_densification_postfix always runs, :577-603)."""
+        n = int(face_index.numel())
+        if n == 0:
+            self.xyz_gradient_accum.zero_()
+            self.denom.zero_()
+            return 0
+        pc = self.pc
+        old_rows = pc.P
+        old_index = pc.resize(new_rows=rows, new_face_index=face_index, new_bary=bary)
+        self._buffers_moved(old_index, old_rows, stats=None)
+        return n
+
+    @torch.no_grad()
+    def prune(self, mask: torch.Tensor) -> int:
+        """_prune (:606-665): removes the Gaussians marked in `mask` [P]; the surviving rows keep their statistics and moments.
+        Returns the number of Gaussians removed."""
+        pc = self.pc
+        mask = mask.to(self.dev).bool().reshape(-1)
+        if mask.numel() != pc.P:
+            raise ValueError("prune: mask must have one entry per Gaussian")
+        n = int(mask.sum())
+        if n == 0:
+            return 0
+        keep = ~mask
+        stats = (self.xyz_gradient_accum[keep].contiguous(), self.denom[keep].contiguous())
+        old_rows = pc.P
+        old_index = pc.resize(keep_mask=keep)
+        self._buffers_moved(old_index, old_rows, stats=stats)
+        return n
+
+    @torch.no_grad()
+    def prune_low_opacity(self, min_opacity: float = 0.005) -> int:
+        """`prune` with the opacity mask of _densify_and_prune (:395-397)."""
+        return self.prune((torch.sigmoid(self.pc._opacity) < min_opacity).reshape(-1))
+
+    @torch.no_grad()
+    def densify_and_prune(self, max_grad: float = 2e-4, min_opacity: float = 0.005, extent: float = 2.0, max_screen_size=None,
+                          generator: Optional[torch.Generator] = None):
+        """_densify_and_prune with _clone_densify and _split_densify (:386-574); call it between step() calls.  Returns (cloned,
+        split, pruned) row counts.
+          * grads = xyz_gradient_accum / denom, NaN -> 0 (:389-390)
+          * clone (:407-470): rows with grads >= max_grad and max exp(_scaling) <= percent_dense * extent are appended as they
+            are, with their face_index / bary_coords
+          * split (:473-574), over the set after the clone (the clones' padded gradient is 0), N = 2: rows with grads >= max_grad
+            and max exp(_scaling) > percent_dense * extent get two children at R(_rotation) . sample + xyz_cano, sample ~
+            N(0, exp(_scaling)) — ONE torch.normal call of shape [2 n, 3], made on the generator's device.  `xyz_cano` is the
+            reference's MIXTURE (:490-502), kept: the barycentric point on the step's CURRENT POSED vertices (the last frame's)
+            plus the CANONICAL interpolated normal times `_uvd[:, 2]`.  The children are re-embedded on the canonical mesh by
+            `PhongSurface.update_corres_spt` (:517) starting from the parent's face and (u, v): bary = (u, v, 1 - u - v),
+            `_uvd` = (0, 0, the parent's d) — the fitted d is discarded, as in the reference —, _scaling = log(exp(_scaling) /
+            (0.8 N)), everything else repeated; the selected originals are then removed
+          * appended rows start with zero Adam moments, the step count is kept; the statistics restart from zero after the
+            clone and after the split, even when nothing was selected
+          * final prune (:395-404): sigmoid(_opacity) < min_opacity, and with a truthy `max_screen_size` also max exp(_scaling) >
+            0.1 * extent.  The reference also ORs in `max_radii2D > max_screen_size`; that test can never fire there
+            (_densification_postfix zeroes max_radii2D in clone and in split immediately before it), so max_radii2D is not
+            tracked here.
+        `self.last_fit_iterations` holds the fit's iteration count per outer round (empty if nothing was split)."""
+        pc = self.pc
+        grads = self.xyz_gradient_accum / self.denom
+        grads[grads.isnan()] = 0.0
+        grads = torch.norm(grads, dim=-1)
+        fields = lambda sel: [getattr(pc, name).detach()[sel] for name, _ in pc.FIELDS]  # noqa: E731
+        largest = lambda: torch.exp(pc._scaling.detach()).max(dim=1).values  # noqa: E731
+        # ---- clone
+        sel = (grads >= max_grad) & (largest() <= PERCENT_DENSE * extent)
+        n_clone = self._append(fields(sel), pc.face_index[sel], pc.bary_coords[sel])
+        # ---- split
+        N = 2
+        padded = torch.zeros(pc.P, device=self.dev)
+        padded[:grads.shape[0]] = grads
+        sel = (padded >= max_grad) & (largest() > PERCENT_DENSE * extent)
+        n_split = int(sel.sum())
+        self.last_fit_iterations = []
+        rows = [r.repeat((N,) + (1,) * (r.dim() - 1)) for r in fields(sel)]
+        i_uvd, i_rot, i_scl = (self._field_index(n) for n in ("_uvd", "_rotation", "_scaling"))
+        stds = torch.exp(rows[i_scl])                           # exp(_scaling)[sel].repeat(N, 1)
+        gdev = generator.device if generator is not None else self.dev
+        samples = torch.normal(mean=torch.zeros((stds.shape[0], 3), device=gdev), std=stds.to(gdev), generator=generator).to(self.dev)
+        fidx, bary = pc.face_index[sel].repeat(N), pc.bary_coords[sel].repeat(N, 1)
+        if n_split:
+            surf = self.phongsurf
+            corners = self.faces.long()[fidx.long()]
+            base_xyz = torch.einsum("nij,ni->nj", self.verts[corners], bary)                                   # :490-493
+            base_normal = torch.nn.functional.normalize(torch.einsum("nij,ni->nj", surf.N[corners], bary), dim=-1)
+            xyz_cano = base_xyz + base_normal * rows[i_uvd][:, 2:]
+            new_xyz = torch.bmm(build_rotation(rows[i_rot]), samples.unsqueeze(-1)).squeeze(-1) + xyz_cano
+            fidx, uv = surf.update_corres_spt(new_xyz, None, fidx, bary[:, :2].contiguous())                   # :517
+            bary = torch.cat([uv, 1.0 - uv[:, 0:1] - uv[:, 1:2]], dim=-1)
+            self.last_fit_iterations = surf.fit_iterations()
+        rows[i_uvd] = torch.cat([torch.zeros_like(rows[i_uvd][:, :2]), rows[i_uvd][:, 2:]], dim=-1)
+        rows[i_scl] = torch.log(stds / (0.8 * N))
+        self._append(rows, fidx, bary)
+        if n_split:
+            self.prune(torch.cat([sel, torch.zeros(N * n_split, dtype=torch.bool, device=self.dev)]))
+        # ---- prune
+        mask = (torch.sigmoid(pc._opacity.detach()) < min_opacity).reshape(-1)
+        if max_screen_size:
+            mask |= torch.exp(pc._scaling.detach()).max(dim=1).values > 0.1 * extent
+        return n_clone, n_split, self.prune(mask)
+
+    def densify_by_gradient(self, *a, **k):
+        raise NotImplementedError("SplattingStep: the set densifies with densify_and_prune() (SplattingAvatar's clone / split)")
+
+    def reduce_densification_stats(self, *a, **k):
+        raise NotImplementedError("SplattingStep: data-parallel runs are not built (DESIGN.md)")
 
     # ---- checkpoints: 'model' holds the six parameters under the reference's names and the embedding buffers
     GAUSSIAN_ATTRIBUTES = ["_uvd", "_opacity", "_features_dc", "_features_rest", "_rotation", "_scaling", "sample_fidxs",

@@ -23,6 +23,9 @@
  *   fr_phong_frame    SplattingAvatar's per-frame mesh pass (model/baseline/splattingavatar.py:203-215, :819-902): vertex
  *                     normals, per-vertex quaternions, face area ratios in one launch; with FR_BIND_PHONG, fr_bind_forward /
  *                     fr_bind_backward_phong replace its Phong-surface binding (:224-246)
+ *   fr_triwalk / fr_phong_fit replace SplattingAvatar's CPU submodule (submodules/simple_phongsurf/simple_phongsurf/):
+ *                     Triwalk::updateSurfacePointsImpl (src/triangle_walk_py.cpp:62-79) around walkSurfacePoint
+ *                     (src/triangle_walk.cpp:240-386), and PhongSurfacePy3d.update_corres_spt (phongsurf_py3d.py:151-185)
  *   fr_adam_step      replaces torch.optim.Adam.step() over the Gaussian groups (train/optim.py:11-37)
  *   fr_knn_mean_dist2 replaces SimpleKNN::knn (simple_knn.h, simple_knn.cu:186-222),
  *                     called from distCUDA2 (spatial.cu:14-25)
@@ -488,6 +491,37 @@ int fr_bind_backward_phong(const fr_binding* b, const float* g_xyz, const float*
 int fr_phong_frame(int32_t V, int32_t F, const float* verts, const float* cano_verts, const int32_t* faces,
                    const int32_t* vf_offsets, const int32_t* vf_faces, const float* face_area_canonical, float* vert_normals,
                    float* vert_quats, float* face_ratio, void* hip_stream);
+
+/* ---- SplattingAvatar's walk on the triangle mesh and Phong-surface fit (the reference's CPU submodule
+ * submodules/simple_phongsurf/simple_phongsurf/).  All pointers are device pointers; no call allocates, synchronises or copies
+ * to the host (capturable); no float atomics: the same inputs give the same bits on every run.  NOTE the stream comes FIRST.
+ *
+ * faces_nbr [F,3]: entry [f, j] describes the directed edge faces[f,j] -> faces[f,(j+1)%3]: 4 g + k of the face g and edge k that
+ * carry the reversed edge, or -1 (initTriangleNeighbor, src/triangle_walk.cpp:176-237).
+ *
+ * fr_triwalk: Triwalk::updateSurfacePointsImpl (src/triangle_walk_py.cpp:62-79) around walkSurfacePoint / walkCrossEdge /
+ * walkToNeighbor / finalize (src/triangle_walk.cpp:240-386), one thread per point: point i starts on face face_index[i] at
+ * (u, v) = bary[i, :2] and is shifted by (delta[i * delta_stride], delta[i * delta_stride + 1]) barycentric units, crossing into
+ * neighbouring faces with the remaining shift multiplied by `decay` (cross_triangle_decay, 0.9) per crossing.  face_index and
+ * bary are updated in place; bary[i, 2] = 1 - u - v.  Precisions, tolerances and the `t12[0] <= 1.0` typo of :72 are the
+ * reference's.  Where the reference's recursion would not end, the loop does, and counts it in status [4] (ADDED to; the
+ * caller zeroes it): status[0] points stopped after 256 crossings; status[1] points whose resetBaryToInside (:165-173) did not
+ * settle in two passes and were clamped; status[2] points left exactly as they were because their delta or barycentrics were
+ * not finite or their face was out of range.
+ *
+ * fr_phong_fit: PhongSurfacePy3d.update_corres_spt (phongsurf_py3d.py:151-185) with method 'uvd', N = None, max_dist = inf:
+ * outer_loop (1 .. 8) rounds of solve_delta_vwd (:256-309; at most inner_loop, 1 .. 512, iterations of torch.optim.Adam at
+ * lr 0.01 on mean((10 V(uv + d) + 10 n_hat(uv + d) d_d - 10 q)^2), ended after the first iteration in which no point of the
+ * batch moved by more than 5e-4) followed by the walk by d_uv.  Two launches per round: the first runs every trajectory and
+ * counts the moving points per iteration into work[round * inner_loop + it], the second takes the stopping iteration from the
+ * counters, runs the trajectories again up to it and walks.  work: int32 [outer_loop * inner_loop + 4], zeroed by the call
+ * (the last four words are reserved); status[3] = the iteration count of the last round; status[0..2] as fr_triwalk.
+ * delta_out [n,3] (may be NULL): the last round's (d_u, d_v, d_d), for tests. */
+int fr_triwalk(void* hip_stream, const int32_t* faces_nbr, int32_t F, int32_t n, int32_t* face_index, float* bary,
+               const float* delta, int32_t delta_stride, float decay, int32_t* status);
+int fr_phong_fit(void* hip_stream, const float* cano_verts, const float* cano_normals, const int32_t* faces,
+                 const int32_t* faces_nbr, int32_t V, int32_t F, int32_t n, const float* query, int32_t* face_index, float* bary,
+                 int32_t outer_loop, int32_t inner_loop, float decay, int32_t* work, int32_t* status, float* delta_out);
 
 /* ---- Gaussian attributes looked up in UV attribute maps: the per-frame front end of a BAKED FateAvatar (reference
  * model/uv_decoder.py:179-202, `UVSampling._texture_look_up`: F.grid_sample(texture, 2 uv - 1, mode="bilinear",

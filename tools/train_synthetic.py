@@ -19,6 +19,7 @@ are printed after each densify.
 the reference's image term, 0.8 x L1 + 0.2 x d_ssim (--image-loss RGB DSSIM for other weights; also for the generic step).
 
     python tools/train_synthetic.py --splatting [--P 10000 --binding-op | --torch-binding]
+    python tools/train_synthetic.py --splatting --densify-from 0.3 --densify-interval 0.1 --reset-interval 0.5 --walk-interval 0.1
 SplattingAvatar's step (fateavatar_amd/splatting.py): Gaussians on the Phong surface of the posed template, SH degree 0, one
 GPU.  --torch-binding binds with the stock-PyTorch restatement (tests/phong_ref.py) in front of render(): the A/B.
 """
@@ -83,10 +84,12 @@ def main():
                          "launch is); default: L1 with weight 1")
     ap.add_argument("--dssim", action="store_true", help="shorthand for --image-loss 0.8 0.2 (GaussianAvatars' and 3DGS's mix)")
     ap.add_argument("--densify-from", type=float, default=0.0,
-                    help="--rigged: first densify_and_prune at this fraction of --steps (0: no densification)")
-    ap.add_argument("--densify-interval", type=float, default=0.1, help="--rigged: densify every this fraction of --steps")
+                    help="--rigged / --splatting: first densify_and_prune at this fraction of --steps (0: no densification)")
+    ap.add_argument("--densify-interval", type=float, default=0.1, help="--rigged / --splatting: densify every this fraction of --steps")
+    ap.add_argument("--walk-interval", type=float, default=0.0,
+                    help="--splatting: walk_on_triangles every this fraction of --steps (0: never)")
     ap.add_argument("--reset-interval", type=float, default=0.0,
-                    help="--rigged: reset_opacity every this fraction of --steps (0: never)")
+                    help="--rigged / --splatting: reset_opacity every this fraction of --steps (0: never)")
     a = ap.parse_args()
     rank, world, local = dp.init_from_env()
     torch.cuda.set_device(local)
@@ -384,6 +387,13 @@ def main_splatting(a, rank, world, dev):
     su = splatting_setup(P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
                          torch_binding=a.torch_binding)
     st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
+    # the compressed maintenance schedule, in steps of the timed loop (config/splattingavatar.yaml:35-44,
+    # train/iteration.py:271-298: densify every 100 steps from 600, reset opacity every 3 500, walk every 100)
+    densify_from = int(round(a.densify_from * a.steps)) if a.densify_from > 0 else 0
+    densify_every = max(1, int(round(a.densify_interval * a.steps)))
+    reset_every = max(1, int(round(a.reset_interval * a.steps))) if a.reset_interval > 0 else 0
+    walk_every = max(1, int(round(a.walk_interval * a.steps))) if a.walk_interval > 0 else 0
+    gen = torch.Generator().manual_seed(0)
     losses, warm = [], 10
     for it in range(warm):
         losses.append(st.step(cams[it % n_frames], posed_t[it % n_frames], gts[it % n_frames]).clone())
@@ -393,6 +403,15 @@ def main_splatting(a, rank, world, dev):
         loss = st.step(cams[it % n_frames], posed_t[it % n_frames], gts[it % n_frames])
         if it >= warm + a.steps - 4:
             losses.append(loss.clone())
+        k = it - warm + 1
+        if densify_from and k >= densify_from and k < a.steps and (k - densify_from) % densify_every == 0:
+            did = st.densify_and_prune(max_screen_size=20 if reset_every and k > reset_every else None, generator=gen)
+            print(f"step {k}: cloned / split / pruned {did}, P {st.pc.P}, split {did[1]}, fit iterations {st.last_fit_iterations}",
+                  file=sys.stderr)
+        if walk_every and k < a.steps and k % walk_every == 0:
+            st.walk_on_triangles()
+        if reset_every and k < a.steps and k % reset_every == 0:
+            st.reset_opacity()
     t_host = time.perf_counter() - t0
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
