@@ -178,26 +178,12 @@ class AvatarStep(BoundStep):
     @torch.no_grad()
     def uv_densify(self, increase_num: int, generator: Optional[torch.Generator] = None) -> int:
         """_uv_densify (model/fateavatar.py:610-672).  The two random draws (multinomial over xyz_gradient_accum, with
-        replacement; uniform barycentrics) are made on rank 0 from the statistics summed over all ranks and broadcast."""
-        pc = self.pc
-        acc, _ = self.reduce_densification_stats()
-        w = acc.reshape(-1)
-        idx = torch.zeros(increase_num, dtype=torch.int64, device=self.dev)
-        uvw = torch.zeros((increase_num, 3), dtype=torch.float32, device=self.dev)
-        if float(w.sum()) <= 0:       # (the summed statistics are identical on every rank: all of them raise, none is left
-            raise RuntimeError("no densification statistics accumulated yet")   # waiting in the broadcast below)
-        if not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0:
-            idx = torch.multinomial(w, increase_num, replacement=True, generator=generator)   # (`generator`: rank 0's only)
-            uvw = torch.rand((increase_num, 3), device=self.dev, generator=generator)
-        dp.broadcast_(idx)
-        dp.broadcast_(uvw)
+        replacement; then uniform barycentrics) are `_draw_by_gradient`'s: made on rank 0 from the statistics summed over all
+        ranks and broadcast."""
+        idx, uvw, rows = self._draw_by_gradient(increase_num, generator, uniforms=3)
         new_bary = uvw / uvw.sum(dim=-1, keepdim=True)
-        rows = [getattr(pc, name).detach()[idx].clone() for name, _ in pc.FIELDS]
-        i = self._field_index("_scaling")
-        rows[i] = torch.log(torch.exp(rows[i]) * 0.75)          # new_scaling (:624)
-        old_rows = pc.P
-        old_index = pc.resize(new_rows=rows, new_face_index=pc.face_index[idx], new_bary=new_bary)
-        self._buffers_moved(old_index, old_rows, stats=None)    # statistics restart from zero (:667-669)
+        # appended rows start with zero Adam moments, the statistics restart from zero (:667-669)
+        self._resize(carry_stats=False, new_rows=rows, new_face_index=self.pc.face_index[idx], new_bary=new_bary)
         self.last_densify = (idx, new_bary)
         if self.keep_coherent:
             AvatarStep.sort_coherent(self)     # (a subclass's lanes are rebuilt by its own uv_densify)
@@ -219,62 +205,30 @@ class AvatarStep(BoundStep):
     def sort_coherent(self, cells: int = 32) -> torch.Tensor:
         """Re-store the Gaussians (parameters, binding, Adam moments, densification statistics) in `coherent_order`.
         Returns the order applied (old row of every new row)."""
-        pc = self.pc
         order = self.coherent_order(cells)
-        old_rows = pc.P
-        stats = (self.xyz_gradient_accum[order].contiguous(), self.denom[order].contiguous())
-        old_index = pc.resize(order=order)
-        self._buffers_moved(old_index, old_rows, stats=stats)
+        self._resize(carry_stats=True, order=order)
         return order
 
     @torch.no_grad()
     def prune_low_opacity(self, min_opacity: float = 0.005) -> int:
         """_prune_low_opacity_points (model/fateavatar.py:674-711): the statistics of the surviving rows are kept."""
-        pc = self.pc
-        keep = ~(torch.sigmoid(pc._opacity) < min_opacity).reshape(-1)
-        old_rows = pc.P
-        stats = (self.xyz_gradient_accum[keep].contiguous(), self.denom[keep].contiguous())
-        old_index = pc.resize(keep_mask=keep)
-        self._buffers_moved(old_index, old_rows, stats=stats)
-        return old_rows - pc.P
+        old_rows = self.pc.P
+        self._resize(carry_stats=True, keep_mask=~(torch.sigmoid(self.pc._opacity) < min_opacity).reshape(-1))
+        return old_rows - self.pc.P
 
     # ---- checkpoints in the reference's layout (Trainer.save_checkpoint, train/trainer.py:396-435: a dict with 'epoch',
     #      'global_step' and 'model' = model.state_dict(), which for FateAvatar holds the six Gaussian parameters and the
     #      two binding buffers next to the FLAME / blendshape entries)
     GAUSSIAN_ATTRIBUTES = ['_offset', '_features_dc', '_features_rest', '_scaling', '_rotation', '_opacity', 'face_index',
                            'bary_coords']   # train/deserialize.py:10-12
+    RESUME_REMAPPED = True      # a checkpoint without an `optimizer` entry goes on from this step's count with zero moments
 
-    def state_dict(self) -> dict:
-        pc = self.pc
-        model = {name: getattr(pc, name).detach().clone() for name, _ in pc.FIELDS}
-        model["_features_rest"] = torch.zeros((pc.P, 0, 3), device=self.dev)   # max_sh_degree 0: empty (fateavatar.py:172-183)
-        model["face_index"], model["bary_coords"] = pc.face_index.clone(), pc.bary_coords.clone()
-        # 'optimizer' and 'densification' are additions a seamless resume needs; the reference saves neither
-        return {"global_step": self.adam.step_count, "model": model, **self._training_state()}
+    def _save_extras(self, sd: dict) -> None:
+        sd["model"]["_features_rest"] = torch.zeros((self.pc.P, 0, 3), device=self.dev)   # max_sh_degree 0: empty (fateavatar.py:172-183)
 
-    @torch.no_grad()
-    def load_state_dict(self, sd: dict) -> list:
-        """deserialize_checkpoints_fateavatar (train/deserialize.py:7-40): the Gaussian attributes are POPPED from
-        sd['model'] (their row count differs from the freshly built model's), re-attached as parameters / buffers, and the
-        per-point statistics restart from zero; whatever else 'model' holds (FLAME, blendshape deltas: outside this
-        path) is returned as the list of ignored keys.  A checkpoint written by the reference itself loads the same way."""
-        model = dict(sd["model"])
-        missing = [k for k in self.GAUSSIAN_ATTRIBUTES if k not in model]
-        if missing:
-            raise KeyError(f"checkpoint lacks Gaussian attributes {missing}")
-        g = {k: model.pop(k) for k in self.GAUSSIAN_ATTRIBUTES}
+    def _load_extras(self, sd: dict, g: dict) -> None:
         if int(g["_features_rest"].shape[1]) != 0:
             raise ValueError("FateAvatar renders SH degree 0: _features_rest must be empty")
-        pc = self.pc
-        old_rows = pc.P
-        pc.face_index = g["face_index"].to(self.dev, torch.int32).contiguous()
-        pc.bary_coords = g["bary_coords"].to(self.dev, torch.float32).contiguous()
-        P = int(pc.face_index.shape[0])
-        pc._bind([g[name].to(self.dev, torch.float32).reshape((P,) + pc.SHAPES[name]) for name, _ in pc.FIELDS])
-        # REMAPPED, not fresh: a checkpoint without an `optimizer` entry goes on from this step's count with zero moments
-        self._buffers_moved(torch.full((P,), -1, dtype=torch.int64, device=self.dev), old_rows, stats=None)
-        self._load_training_state(sd)
-        return sorted(model.keys())
 
 
 class _Lane:
@@ -531,32 +485,29 @@ class AvatarBatchStep(AvatarStep):
         self._fold_stats()
         return super().reduce_densification_stats()
 
-    def uv_densify(self, increase_num: int, generator=None) -> int:
+    def _maintenance(self, op, *args, fold: bool = True, rebuild: bool = True):
+        """One of AvatarStep's maintenance calls on the batch: wait for the lanes, fold their statistics (`fold`), run it,
+        rebuild the lanes over the new buffers (`rebuild`)."""
         torch.cuda.synchronize()
-        n = super().uv_densify(increase_num, generator)
-        self._build_lanes()
-        return n
+        if fold:
+            self._fold_stats()
+        out = op(*args)
+        if rebuild:
+            self._build_lanes()
+        return out
+
+    def uv_densify(self, increase_num: int, generator=None) -> int:
+        return self._maintenance(super().uv_densify, increase_num, generator, fold=False)   # (folds in reduce_densification_stats)
 
     def prune_low_opacity(self, min_opacity: float = 0.005) -> int:
-        torch.cuda.synchronize()
-        self._fold_stats()
-        n = super().prune_low_opacity(min_opacity)
-        self._build_lanes()
-        return n
+        return self._maintenance(super().prune_low_opacity, min_opacity)
 
     def reset_opacity(self) -> None:
-        torch.cuda.synchronize()
-        super().reset_opacity()          # in place: the lanes' leaves see it (shared storage), their graphs stay valid
+        # in place: the lanes' leaves see it (shared storage), their graphs stay valid
+        self._maintenance(super().reset_opacity, fold=False, rebuild=False)
 
     def sort_coherent(self, cells: int = 32):
-        torch.cuda.synchronize()
-        self._fold_stats()
-        order = super().sort_coherent(cells)
-        self._build_lanes()
-        return order
+        return self._maintenance(super().sort_coherent, cells)
 
     def load_state_dict(self, sd: dict) -> list:
-        torch.cuda.synchronize()
-        ignored = super().load_state_dict(sd)
-        self._build_lanes()
-        return ignored
+        return self._maintenance(super().load_state_dict, sd, fold=False)               # (the checkpoint brings the statistics)

@@ -1,11 +1,14 @@
 """The small helpers the reference's Gaussian callers take from tools/gs_utils (sh_utils.py:114-118,
 general_utils.py:18-19,29-62, graphics_utils.py:38-49), for callers that use this package instead: colour <-> SH DC
 term, inverse sigmoid, the exponential learning-rate schedule (GaussianModel.training_setup of the 3DGS baselines) and
-the world-to-view matrix with the scene translate / scale.  Each is pinned on the reference's own function
-(tests/golden/golden_misc.npz, tests/test_oracle_golden.py)."""
+the world-to-view matrix with the scene translate / scale.  Each of these is pinned on the reference's own function
+(tests/golden/golden_misc.npz, tests/test_oracle_golden.py).  `build_rotation` (general_utils.py:78-99: raw quaternion ->
+rotation matrix, used by the density control's split) is pinned on the restatement of tests/rigged_density_ref.py
+(tests/test_rigged_density_host.py)."""
 from __future__ import annotations
 
 import numpy as np
+import torch
 
 C0 = 0.28209479177387814
 
@@ -20,6 +23,15 @@ def SH2RGB(sh):
 
 def inverse_sigmoid(x):
     return np.log(x / (1 - x)) if isinstance(x, (np.ndarray, float)) else (x / (1 - x)).log()
+
+
+def build_rotation(r: torch.Tensor) -> torch.Tensor:
+    """[n,4] raw quaternions (r, x, y, z) -> [n,3,3]: build_rotation (tools/gs_utils/general_utils.py:78-99)."""
+    q = r / torch.sqrt((r * r).sum(dim=1, keepdim=True))
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                        2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                        2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
 
 
 def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000):

@@ -37,7 +37,8 @@ from .flat import FlatParams
 from .loss import ImageLoss, gaussian_regularisers, regulariser_workspace
 from .model import TorchCamera
 from .render import render
-from .train import BoundStep
+from .gs_utils import build_rotation
+from .train import CloneSplitStep
 
 # config/gaussianavatars.yaml:26-31 (group names of train/optim.py:73-80; position_lr_init: the schedule is out of scope)
 RIGGED_LRS = dict(xyz=0.005, opacity=0.05, feature_dc=0.0025, feature_rest=0.0025 / 20, rotation=0.001, scaling=0.017)
@@ -55,16 +56,6 @@ class Regularisers(NamedTuple):
 REFERENCE_REGULARISERS = Regularisers(scale_weight=1.0, xyz_weight=0.01, threshold_scale=0.6, threshold_xyz=1.0)
 # rgb_weight, dssim_weight of the image term (config/gaussianavatars.yaml:16-20)
 REFERENCE_IMAGE_LOSS = ImageLoss(rgb_weight=0.8, dssim_weight=0.2)
-PERCENT_DENSE = 0.01     # gaussianavatars.py:47
-
-
-def build_rotation(r: torch.Tensor) -> torch.Tensor:
-    """[n,4] raw quaternions (r, x, y, z) -> [n,3,3]: build_rotation (tools/gs_utils/general_utils.py:78-99)."""
-    q = r / torch.sqrt((r * r).sum(dim=1, keepdim=True))
-    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
-    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
-                        2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-                        2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
 
 
 class RiggedGaussians(FlatParams):
@@ -117,7 +108,7 @@ class _RiggedFrame:
         self.fused_densification_stats = stats
 
 
-class RiggedStep(BoundStep):
+class RiggedStep(CloneSplitStep):
     """One optimisation step of GaussianAvatars per call: `step(camera, posed_verts, gt_image)` —
     bind in the frame -> render -> L1 -> backward -> densification statistics -> Adam.  The optimizer groups are those of
     train/optim.py:73-80 with config/gaussianavatars.yaml:26-31."""
@@ -139,22 +130,29 @@ class RiggedStep(BoundStep):
         rgb_weight x L1 + dssim_weight x d_ssim (train/loss.py:351-365) — two launches where the L1 launch is; `loss_terms`
         then holds the step's (weighted image loss, l1, d_ssim) and `loss` is its first word.  None (default): the image
         term is L1 with weight 1, `loss_terms` is None."""
-        if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            raise RuntimeError("RiggedStep: data-parallel runs are not built (DESIGN.md)")
         super().__init__(pc, faces, camera, bg, verts, lrs, use_graph, fold_binding, image_loss, data_parallel=False)
         self.regularisers = None if regularisers is None else Regularisers(*[float(x) for x in regularisers])
         # the reference's out['scale_loss'] / out['xyz_loss'] of the step (unweighted), written by the regulariser launch
         self.reg_loss = None if regularisers is None else torch.zeros(2, device=self.dev)
         self._reg_ws = None if regularisers is None else regulariser_workspace(self.dev)
         self.n_faces = int(self.faces.shape[0])
+        self._check_binding(pc.binding)
         self._count_binding()
 
-    def _count_binding(self):
-        """binding_counter [F] int32: Gaussians per face (gaussianavatars.py:66-69)."""
-        b = self.pc.binding.long()
-        if b.numel() and (int(b.min()) < 0 or int(b.max()) >= self.n_faces):
+    def _check_binding(self, binding: torch.Tensor) -> None:
+        """Refuses a `binding` out of the mesh's range (reads device state: the constructor and load_state_dict only)."""
+        if binding.numel() and (int(binding.min()) < 0 or int(binding.max()) >= self.n_faces):
             raise ValueError("RiggedStep: `binding` names a face the mesh does not have")
-        self.binding_counter = torch.bincount(b, minlength=self.n_faces).to(torch.int32)
+
+    def _count_binding(self) -> None:
+        """binding_counter [F] int32: Gaussians per face (gaussianavatars.py:66-69)."""
+        self.binding_counter = torch.bincount(self.pc.binding.long(), minlength=self.n_faces).to(torch.int32)
+
+    def _buffers_moved(self, old_index, old_rows, *, stats):
+        """... and the rows with them: binding_counter is counted again — THE place that keeps it equal to bincount(binding)
+        (the reference adds to it in clone and split, :313-315, :374-377, and subtracts in _prune)."""
+        super()._buffers_moved(old_index, old_rows, stats=stats)
+        self._count_binding()
 
     def _forward_backward(self):
         pc = self.pc
@@ -188,104 +186,26 @@ class RiggedStep(BoundStep):
             self._graph = None
         return pc.active_sh_degree
 
-    # ---- GaussianAvatars' density control (gaussianavatars.py:278-495), with TrainStep's conventions: torch index surgery
-    #      under no_grad between step() calls, optimizer state through FusedAdam.remap_rows / zero_field_moments, the graph
-    #      dropped when the buffers move, host_steps untouched
-    @torch.no_grad()
-    def _append(self, rows, binding) -> int:
-        """Appends `rows` (FIELDS order) bound to `binding`; counts them into binding_counter (:313-315, :374-377); the
-        statistics restart from zero whether or not anything was appended (_densification_postfix always runs, :462-475)."""
-        n = int(binding.numel())
-        if n == 0:
-            self.xyz_gradient_accum.zero_()
-            self.denom.zero_()
-            return 0
-        pc = self.pc
-        self.binding_counter += torch.bincount(binding.long(), minlength=self.n_faces).to(torch.int32)
-        old_rows = pc.P
-        old_index = pc.resize(new_rows=rows, new_binding=binding)
-        self._buffers_moved(old_index, old_rows, stats=None)
-        return n
-
-    @torch.no_grad()
-    def prune(self, mask: torch.Tensor) -> int:
-        """_prune (gaussianavatars.py:418-460): removes the Gaussians marked in `mask` [P] — but if a face would lose ALL of
-        its Gaussians none of its marked ones is removed (binding_counter guard, :420-424); otherwise all of them are.  The
-        statistics of the surviving rows are kept (:455-456).  Returns the number of Gaussians removed."""
-        pc = self.pc
-        mask = mask.to(self.dev).bool().reshape(-1).clone()
-        if mask.numel() != pc.P:
-            raise ValueError("prune: mask must have one entry per Gaussian")
-        b = pc.binding.long()
+    # ---- GaussianAvatars' density control (gaussianavatars.py:278-495): CloneSplitStep's, with the binding_counter guard
+    def _prune_guard(self, mask: torch.Tensor) -> torch.Tensor:
+        """If a face would lose ALL of its Gaussians none of its marked ones is removed (binding_counter guard,
+        gaussianavatars.py:420-424); otherwise all of them are."""
+        b = self.pc.binding.long()
         marked = torch.bincount(b[mask], minlength=self.n_faces).to(torch.int32)
-        redundant = (self.binding_counter - marked) > 0
-        mask &= redundant[b]
-        n = int(mask.sum())
-        if n == 0:
-            return 0
-        self.binding_counter -= torch.bincount(b[mask], minlength=self.n_faces).to(torch.int32)
-        keep = ~mask
-        stats = (self.xyz_gradient_accum[keep].contiguous(), self.denom[keep].contiguous())
-        old_rows = pc.P
-        old_index = pc.resize(keep_mask=keep)
-        self._buffers_moved(old_index, old_rows, stats=stats)
-        return n
+        return mask & ((self.binding_counter - marked) > 0)[b]
 
-    @torch.no_grad()
-    def prune_low_opacity(self, min_opacity: float = 0.005) -> int:
-        """`prune` with the opacity mask of _densify_and_prune (:287)."""
-        return self.prune((torch.sigmoid(self.pc._opacity) < min_opacity).reshape(-1))
+    def _split_children(self, rows, sel, samples, N):
+        """Children at R(_rotation) . sample + _xyz on the parent's face, everything else repeated (:353-416)."""
+        i_xyz, i_rot = self._field_index("_xyz"), self._field_index("_rotation")
+        rows[i_xyz] = torch.bmm(build_rotation(rows[i_rot]), samples.unsqueeze(-1)).squeeze(-1) + rows[i_xyz]
+        return rows, dict(new_binding=self.pc.binding[sel].repeat(N))
 
-    @torch.no_grad()
     def densify_and_prune(self, max_grad: float = 1e-4, min_opacity: float = 0.005, extent: float = 2.0,
                           max_screen_size=None, generator: Optional[torch.Generator] = None):
-        """_densify_and_prune with _clone_densify and _split_densify (gaussianavatars.py:278-416); call it between step()
-        calls.  Returns (cloned, split, pruned) row counts.
-          * grads = xyz_gradient_accum / denom, NaN -> 0 (:281-282)
-          * clone (:297-351): rows with grads >= max_grad and max exp(_scaling) <= percent_dense * extent are appended as
-            they are, on the same face
-          * split (:353-416), over the set after the clone (the clones' padded gradient is 0), N = 2: rows with grads >=
-            max_grad and max exp(_scaling) > percent_dense * extent get two children at R(_rotation) . sample + _xyz, sample ~
-            N(0, exp(_scaling)) — ONE torch.normal(mean=zeros, std=stds, generator=generator) call of shape [2 n, 3], made
-            on the generator's device — with _scaling = log(exp(_scaling) / (0.8 N)), everything else repeated; the selected
-            originals are then removed through the guarded prune
-          * appended rows start with zero Adam moments, the step count is kept; the statistics restart from zero after the
-            clone and after the split, even when nothing was selected
-          * final prune (:287-293): sigmoid(_opacity) < min_opacity, and with a truthy `max_screen_size` also max exp(_scaling) >
-            0.1 * extent.  The reference also ORs in `max_radii2D > max_screen_size`; that test can never fire there
-            (_densification_postfix zeroes max_radii2D in clone and in split immediately before it), so max_radii2D is not
-            tracked here.
-        The reference calls this between backward() and optimizer.step(), where the new Parameters have no gradients; that
-        ordering is not copied."""
-        pc = self.pc
-        grads = self.xyz_gradient_accum / self.denom
-        grads[grads.isnan()] = 0.0
-        grads = torch.norm(grads, dim=-1)
-        fields = lambda sel: [getattr(pc, name).detach()[sel] for name, _ in pc.FIELDS]  # noqa: E731
-        largest = lambda: torch.exp(pc._scaling.detach()).max(dim=1).values  # noqa: E731
-        # ---- clone
-        sel = (grads >= max_grad) & (largest() <= PERCENT_DENSE * extent)
-        n_clone = self._append(fields(sel), pc.binding[sel])
-        # ---- split
-        N = 2
-        padded = torch.zeros(pc.P, device=self.dev)
-        padded[:grads.shape[0]] = grads
-        sel = (padded >= max_grad) & (largest() > PERCENT_DENSE * extent)
-        n_split = int(sel.sum())
-        rows = [r.repeat((N,) + (1,) * (r.dim() - 1)) for r in fields(sel)]
-        stds = torch.exp(rows[5])                               # exp(_scaling)[sel].repeat(N, 1)
-        gdev = generator.device if generator is not None else self.dev
-        samples = torch.normal(mean=torch.zeros((stds.shape[0], 3), device=gdev), std=stds.to(gdev), generator=generator).to(self.dev)
-        rows[0] = torch.bmm(build_rotation(rows[4]), samples.unsqueeze(-1)).squeeze(-1) + rows[0]
-        rows[5] = torch.log(stds / (0.8 * N))
-        self._append(rows, pc.binding[sel].repeat(N))
-        if n_split:
-            self.prune(torch.cat([sel, torch.zeros(N * n_split, dtype=torch.bool, device=self.dev)]))
-        # ---- prune
-        mask = (torch.sigmoid(pc._opacity.detach()) < min_opacity).reshape(-1)
-        if max_screen_size:
-            mask |= torch.exp(pc._scaling.detach()).max(dim=1).values > 0.1 * extent
-        return n_clone, n_split, self.prune(mask)
+        """_densify_and_prune with _clone_densify and _split_densify (gaussianavatars.py:278-416): CloneSplitStep's, which
+        states the rule — grads :281-282, clone :297-351 (on the same face), split :353-416 (`_split_children`; the selected
+        originals go through the guarded prune), final prune :287-293.  Returns (cloned, split, pruned) row counts."""
+        return super().densify_and_prune(max_grad, min_opacity, extent, max_screen_size, generator)
 
     def densify_by_gradient(self, *a, **k):
         raise NotImplementedError("RiggedStep: the rigged set densifies with densify_and_prune() (GaussianAvatars' clone / split)")
@@ -293,30 +213,11 @@ class RiggedStep(BoundStep):
     # ---- checkpoints: 'model' holds what GaussianAvatars.state_dict() holds of the Gaussians (the six parameters and the
     #      `binding` buffer); 'optimizer', 'densification' and 'active_sh_degree' are what a seamless resume needs on top
     GAUSSIAN_ATTRIBUTES = ["_xyz", "_opacity", "_features_dc", "_features_rest", "_rotation", "_scaling", "binding"]
+    RESUME_REMAPPED = False     # resumes FRESH
 
-    def state_dict(self) -> dict:
-        pc = self.pc
-        model = {name: getattr(pc, name).detach().clone() for name, _ in pc.FIELDS}
-        model["binding"] = pc.binding.clone()
-        return {"global_step": self.adam.step_count, "model": model, "active_sh_degree": int(pc.active_sh_degree),
-                **self._training_state()}
+    def _save_extras(self, sd: dict) -> None:
+        sd["active_sh_degree"] = int(self.pc.active_sh_degree)
 
-    @torch.no_grad()
-    def load_state_dict(self, sd: dict) -> list:
-        """Restores the Gaussians (any row count), the optimizer state and the statistics; returns the keys of sd['model'] it
-        did not use."""
-        model = dict(sd["model"])
-        missing = [k for k in self.GAUSSIAN_ATTRIBUTES if k not in model]
-        if missing:
-            raise KeyError(f"checkpoint lacks Gaussian attributes {missing}")
-        g = {k: model.pop(k) for k in self.GAUSSIAN_ATTRIBUTES}
-        pc = self.pc
-        pc.binding = g["binding"].to(self.dev, torch.int32).contiguous()
-        P = int(pc.binding.shape[0])
-        pc._bind([g[name].to(self.dev, torch.float32).reshape((P,) + pc.SHAPES[name]) for name, _ in pc.FIELDS])
-        pc.active_sh_degree = int(sd.get("active_sh_degree", pc.active_sh_degree))
-        self._count_binding()
-        # FRESH, not remapped: a checkpoint without an `optimizer` entry starts the optimizer over, step count 0
-        self._buffers_moved(None, None, stats=None)
-        self._load_training_state(sd)
-        return sorted(model.keys())
+    def _load_extras(self, sd: dict, g: dict) -> None:
+        self._check_binding(g["binding"])
+        self.pc.active_sh_degree = int(sd.get("active_sh_degree", self.pc.active_sh_degree))   # (the recount: _buffers_moved)

@@ -41,15 +41,13 @@ import torch
 from .binding import PhongCanonical, bind_gaussians_phong, phong_canonical, phong_frame
 from .bound import PhongBinding, render_bound_batch
 from .flat import FlatParams
-from .gs_utils import RGB2SH
+from .gs_utils import RGB2SH, build_rotation
 from .model import TorchCamera
 from .phongsurf import PhongSurface, triwalk
 from .render import render
-from .rigged import build_rotation
-from .train import BoundStep
+from .train import CloneSplitStep
 
 # config/splattingavatar.yaml:26-30 (group names of train/optim.py:106-117)
-PERCENT_DENSE = 0.01        # splattingavatar.py: percent_dense
 SPLATTING_LRS = dict(uvd=0.00016, opacity=0.05, feature_dc=0.0025, feature_rest=0.0025 / 20, rotation=0.001, scaling=0.005)
 NUM_INIT_SAMPLES = 10_000   # config/splattingavatar.yaml:23
 
@@ -129,7 +127,7 @@ class _SplattingFrame:
         self.fused_densification_stats = stats
 
 
-class SplattingStep(BoundStep):
+class SplattingStep(CloneSplitStep):
     """One optimisation step of SplattingAvatar per call: `step(camera, posed_verts, gt_image)` —
     mesh pass -> bind in the frame -> render -> L1 -> backward -> densification statistics -> Adam.  The optimizer groups are
     those of train/optim.py:106-117 with config/splattingavatar.yaml:26-30 (`_features_rest` is empty at SH degree 0: its
@@ -144,8 +142,6 @@ class SplattingStep(BoundStep):
         static vertex buffer and is its first content).  `fold_binding` (default): the per-Gaussian binding is evaluated
         inside the rasterizer's per-Gaussian kernels (fr_aux::binding with FR_BIND_PHONG).  False: the stand-alone
         `bind_gaussians_phong` op in front of render() (same results; the A/B and the op's own user)."""
-        if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            raise RuntimeError("SplattingStep: data-parallel runs are not built (DESIGN.md)")
         self.canonical = PhongCanonical(*[t.to(pc.flat.device).contiguous() for t in canonical])
         if pc.P and (int(pc.face_index.min()) < 0 or int(pc.face_index.max()) >= int(self.canonical.faces.shape[0])):
             raise ValueError("SplattingStep: `face_index` names a face the mesh does not have")
@@ -169,9 +165,8 @@ class SplattingStep(BoundStep):
         pc.collect_grads()
         self.out = self._kept(out)
 
-    # ---- SplattingAvatar's density control, triangle walk and opacity reset (:386-715), with RiggedStep's conventions: torch
-    #      index surgery under no_grad between step() calls, optimizer state through FusedAdam.remap_rows, the graph dropped
-    #      when the buffers move; `reset_opacity` is TrainStep's (:697-715 is the same rule), in place
+    # ---- SplattingAvatar's density control, triangle walk and opacity reset (:386-715): the density control is CloneSplitStep's
+    #      with the children re-embedded on the canonical mesh; `reset_opacity` is TrainStep's (:697-715 is the same rule), in place
     @property
     def phongsurf(self) -> PhongSurface:
         """The canonical mesh's Phong surface as the reference constructs it (:122-125: outer_loop 2, inner_loop 50, 'uvd'), with
@@ -195,90 +190,18 @@ class SplattingStep(BoundStep):
         for m in (self.adam.exp_avg, self.adam.exp_avg_sq):
             m[off:off + 3 * P].view(P, 3)[:, :2] = 0
 
-    @torch.no_grad()
-    def _append(self, rows, face_index, bary) -> int:
-        """Appends `rows` (FIELDS order) embedded at (`face_index`, `bary`) with zero moments; the statistics restart from zero
-        whether or not anything was appended (_densification_postfix always runs, :577-603)."""
-        n = int(face_index.numel())
-        if n == 0:
-            self.xyz_gradient_accum.zero_()
-            self.denom.zero_()
-            return 0
+    def _split_children(self, rows, sel, samples, N):
+        """Children at R(_rotation) . sample + xyz_cano (:473-574).  `xyz_cano` is the reference's MIXTURE (:490-502), kept: the
+        barycentric point on the step's CURRENT POSED vertices (the last frame's) plus the CANONICAL interpolated normal times
+        `_uvd[:, 2]`.  The children are re-embedded on the canonical mesh by `PhongSurface.update_corres_spt` (:517) starting
+        from the parent's face and (u, v): bary = (u, v, 1 - u - v), `_uvd` = (0, 0, the parent's d) — the fitted d is
+        discarded, as in the reference —, everything else repeated.  `self.last_fit_iterations` holds the fit's iteration count
+        per outer round (empty if nothing was split)."""
         pc = self.pc
-        old_rows = pc.P
-        old_index = pc.resize(new_rows=rows, new_face_index=face_index, new_bary=bary)
-        self._buffers_moved(old_index, old_rows, stats=None)
-        return n
-
-    @torch.no_grad()
-    def prune(self, mask: torch.Tensor) -> int:
-        """_prune (:606-665): removes the Gaussians marked in `mask` [P]; the surviving rows keep their statistics and moments.
-        Returns the number of Gaussians removed."""
-        pc = self.pc
-        mask = mask.to(self.dev).bool().reshape(-1)
-        if mask.numel() != pc.P:
-            raise ValueError("prune: mask must have one entry per Gaussian")
-        n = int(mask.sum())
-        if n == 0:
-            return 0
-        keep = ~mask
-        stats = (self.xyz_gradient_accum[keep].contiguous(), self.denom[keep].contiguous())
-        old_rows = pc.P
-        old_index = pc.resize(keep_mask=keep)
-        self._buffers_moved(old_index, old_rows, stats=stats)
-        return n
-
-    @torch.no_grad()
-    def prune_low_opacity(self, min_opacity: float = 0.005) -> int:
-        """`prune` with the opacity mask of _densify_and_prune (:395-397)."""
-        return self.prune((torch.sigmoid(self.pc._opacity) < min_opacity).reshape(-1))
-
-    @torch.no_grad()
-    def densify_and_prune(self, max_grad: float = 2e-4, min_opacity: float = 0.005, extent: float = 2.0, max_screen_size=None,
-                          generator: Optional[torch.Generator] = None):
-        """_densify_and_prune with _clone_densify and _split_densify (:386-574); call it between step() calls.  Returns (cloned,
-        split, pruned) row counts.
-          * grads = xyz_gradient_accum / denom, NaN -> 0 (:389-390)
-          * clone (:407-470): rows with grads >= max_grad and max exp(_scaling) <= percent_dense * extent are appended as they
-            are, with their face_index / bary_coords
-          * split (:473-574), over the set after the clone (the clones' padded gradient is 0), N = 2: rows with grads >= max_grad
-            and max exp(_scaling) > percent_dense * extent get two children at R(_rotation) . sample + xyz_cano, sample ~
-            N(0, exp(_scaling)) — ONE torch.normal call of shape [2 n, 3], made on the generator's device.  `xyz_cano` is the
-            reference's MIXTURE (:490-502), kept: the barycentric point on the step's CURRENT POSED vertices (the last frame's)
-            plus the CANONICAL interpolated normal times `_uvd[:, 2]`.  The children are re-embedded on the canonical mesh by
-            `PhongSurface.update_corres_spt` (:517) starting from the parent's face and (u, v): bary = (u, v, 1 - u - v),
-            `_uvd` = (0, 0, the parent's d) — the fitted d is discarded, as in the reference —, _scaling = log(exp(_scaling) /
-            (0.8 N)), everything else repeated; the selected originals are then removed
-          * appended rows start with zero Adam moments, the step count is kept; the statistics restart from zero after the
-            clone and after the split, even when nothing was selected
-          * final prune (:395-404): sigmoid(_opacity) < min_opacity, and with a truthy `max_screen_size` also max exp(_scaling) >
-            0.1 * extent.  The reference also ORs in `max_radii2D > max_screen_size`; that test can never fire there
-            (_densification_postfix zeroes max_radii2D in clone and in split immediately before it), so max_radii2D is not
-            tracked here.
-        `self.last_fit_iterations` holds the fit's iteration count per outer round (empty if nothing was split)."""
-        pc = self.pc
-        grads = self.xyz_gradient_accum / self.denom
-        grads[grads.isnan()] = 0.0
-        grads = torch.norm(grads, dim=-1)
-        fields = lambda sel: [getattr(pc, name).detach()[sel] for name, _ in pc.FIELDS]  # noqa: E731
-        largest = lambda: torch.exp(pc._scaling.detach()).max(dim=1).values  # noqa: E731
-        # ---- clone
-        sel = (grads >= max_grad) & (largest() <= PERCENT_DENSE * extent)
-        n_clone = self._append(fields(sel), pc.face_index[sel], pc.bary_coords[sel])
-        # ---- split
-        N = 2
-        padded = torch.zeros(pc.P, device=self.dev)
-        padded[:grads.shape[0]] = grads
-        sel = (padded >= max_grad) & (largest() > PERCENT_DENSE * extent)
-        n_split = int(sel.sum())
-        self.last_fit_iterations = []
-        rows = [r.repeat((N,) + (1,) * (r.dim() - 1)) for r in fields(sel)]
-        i_uvd, i_rot, i_scl = (self._field_index(n) for n in ("_uvd", "_rotation", "_scaling"))
-        stds = torch.exp(rows[i_scl])                           # exp(_scaling)[sel].repeat(N, 1)
-        gdev = generator.device if generator is not None else self.dev
-        samples = torch.normal(mean=torch.zeros((stds.shape[0], 3), device=gdev), std=stds.to(gdev), generator=generator).to(self.dev)
+        i_uvd, i_rot = self._field_index("_uvd"), self._field_index("_rotation")
         fidx, bary = pc.face_index[sel].repeat(N), pc.bary_coords[sel].repeat(N, 1)
-        if n_split:
+        self.last_fit_iterations = []
+        if fidx.numel():
             surf = self.phongsurf
             corners = self.faces.long()[fidx.long()]
             base_xyz = torch.einsum("nij,ni->nj", self.verts[corners], bary)                                   # :490-493
@@ -289,15 +212,14 @@ class SplattingStep(BoundStep):
             bary = torch.cat([uv, 1.0 - uv[:, 0:1] - uv[:, 1:2]], dim=-1)
             self.last_fit_iterations = surf.fit_iterations()
         rows[i_uvd] = torch.cat([torch.zeros_like(rows[i_uvd][:, :2]), rows[i_uvd][:, 2:]], dim=-1)
-        rows[i_scl] = torch.log(stds / (0.8 * N))
-        self._append(rows, fidx, bary)
-        if n_split:
-            self.prune(torch.cat([sel, torch.zeros(N * n_split, dtype=torch.bool, device=self.dev)]))
-        # ---- prune
-        mask = (torch.sigmoid(pc._opacity.detach()) < min_opacity).reshape(-1)
-        if max_screen_size:
-            mask |= torch.exp(pc._scaling.detach()).max(dim=1).values > 0.1 * extent
-        return n_clone, n_split, self.prune(mask)
+        return rows, dict(new_face_index=fidx, new_bary=bary)
+
+    def densify_and_prune(self, max_grad: float = 2e-4, min_opacity: float = 0.005, extent: float = 2.0, max_screen_size=None,
+                          generator: Optional[torch.Generator] = None):
+        """_densify_and_prune with _clone_densify and _split_densify (:386-574): CloneSplitStep's, which states the rule — grads
+        :389-390, clone :407-470 (with their face_index / bary_coords), split :473-574 (`_split_children`), final prune
+        :395-404.  Returns (cloned, split, pruned) row counts."""
+        return super().densify_and_prune(max_grad, min_opacity, extent, max_screen_size, generator)
 
     def densify_by_gradient(self, *a, **k):
         raise NotImplementedError("SplattingStep: the set densifies with densify_and_prune() (SplattingAvatar's clone / split)")
@@ -308,31 +230,8 @@ class SplattingStep(BoundStep):
     # ---- checkpoints: 'model' holds the six parameters under the reference's names and the embedding buffers
     GAUSSIAN_ATTRIBUTES = ["_uvd", "_opacity", "_features_dc", "_features_rest", "_rotation", "_scaling", "sample_fidxs",
                            "sample_bary"]
-
-    def state_dict(self) -> dict:
-        pc = self.pc
-        model = {name: getattr(pc, name).detach().clone() for name, _ in pc.FIELDS}
-        model["sample_fidxs"], model["sample_bary"] = pc.face_index.clone(), pc.bary_coords.clone()
-        return {"global_step": self.adam.step_count, "model": model, **self._training_state()}
-
-    @torch.no_grad()
-    def load_state_dict(self, sd: dict) -> list:
-        """Restores the Gaussians (any row count), the optimizer state and the statistics; returns the keys of sd['model'] it
-        did not use."""
-        model = dict(sd["model"])
-        missing = [k for k in self.GAUSSIAN_ATTRIBUTES if k not in model]
-        if missing:
-            raise KeyError(f"checkpoint lacks Gaussian attributes {missing}")
-        g = {k: model.pop(k) for k in self.GAUSSIAN_ATTRIBUTES}
-        pc = self.pc
-        pc.face_index = g["sample_fidxs"].to(self.dev, torch.int32).contiguous()
-        pc.bary_coords = g["sample_bary"].to(self.dev, torch.float32).contiguous()
-        P = int(pc.face_index.shape[0])
-        pc._bind([g[name].to(self.dev, torch.float32).reshape((P,) + pc.SHAPES[name]) for name, _ in pc.FIELDS])
-        # FRESH, not remapped: a checkpoint without an `optimizer` entry starts the optimizer over, step count 0
-        self._buffers_moved(None, None, stats=None)
-        self._load_training_state(sd)
-        return sorted(model.keys())
+    ROW_BUFFER_KEYS = {"face_index": "sample_fidxs", "bary_coords": "sample_bary"}
+    RESUME_REMAPPED = False     # resumes FRESH
 
 
 __all__ = ["NUM_INIT_SAMPLES", "SPLATTING_LRS", "SplattingGaussians", "SplattingStep", "phong_canonical", "sample_bary_on_triangles"]

@@ -28,6 +28,7 @@ from .render import render
 
 # config/fateavatar.yaml:34-39 (+ the generic 3DGS position rate; FateAvatar optimises a mesh offset instead)
 DEFAULT_LRS = dict(xyz=1.6e-4, feature_dc=2.5e-3, feature_rest=2.5e-3 / 20, opacity=0.05, scaling=5e-3, rotation=1e-3)
+PERCENT_DENSE = 0.01     # clone / split threshold as a share of the scene extent (gaussianavatars.py:47, splattingavatar.py)
 
 
 class TrainStep:
@@ -244,38 +245,63 @@ class TrainStep:
         self._graph, self._eager_steps = None, 0   # buffers moved: the captured step is stale
 
     @torch.no_grad()
-    def prune_low_opacity(self, min_opacity: float = 0.005) -> int:
-        """_prune_low_opacity_points (model/fateavatar.py:674-711).  Returns the number of Gaussians removed."""
+    def _resize(self, *, carry_stats: bool, **resize_kw) -> torch.Tensor:
+        """THE way a step changes its point set between step() calls: `pc.resize(**resize_kw)`, then `_buffers_moved` along
+        the row map it returned — the moments follow their rows, appended rows start with zero moments, the step count is
+        kept, the captured step is dropped.  `carry_stats`: the statistics follow their rows too (a prune, a re-ordering;
+        no caller appends and carries, so a map with appended rows is refused); False: they restart from zero, as after
+        every change of the point set in model/fateavatar.py:667-672.  Returns the row map."""
         pc = self.pc
-        keep = ~(torch.sigmoid(pc._opacity) < min_opacity).reshape(-1)
         old_rows = pc.P
-        old_index = pc.resize(keep_mask=keep)
-        # statistics restart from zero after a change of the point set (model/fateavatar.py:667-672)
-        self._buffers_moved(old_index, old_rows, stats=None)
-        return old_rows - pc.P
+        old_index = pc.resize(**resize_kw)
+        stats = None
+        if carry_stats:
+            if bool((old_index < 0).any()):
+                raise ValueError("_resize: appended rows have no statistics to carry")
+            stats = (self.xyz_gradient_accum[old_index].contiguous(), self.denom[old_index].contiguous())
+        self._buffers_moved(old_index, old_rows, stats=stats)
+        return old_index
 
     @torch.no_grad()
-    def densify_by_gradient(self, increase_num: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
-        """The sampling and cloning rule of _uv_densify (model/fateavatar.py:610-672) without the mesh re-binding:
-        `increase_num` rows drawn with probability proportional to xyz_gradient_accum (multinomial, with
-        replacement), cloned with their scale multiplied by 0.75; appended rows start with zero Adam moments.
-        Data-parallel: the statistics are per-view sums (model/fateavatar.py:734-737), so the draw is made on rank 0 from
-        the sum over all ranks and broadcast — every replica appends the same rows.  Returns the sampled row indices."""
+    def prune_low_opacity(self, min_opacity: float = 0.005) -> int:
+        """_prune_low_opacity_points (model/fateavatar.py:674-711); generic 3DGS: the statistics restart from zero after a change
+        of the point set (:667-672).  Returns the number of Gaussians removed."""
+        old_rows = self.pc.P
+        self._resize(carry_stats=False, keep_mask=~(torch.sigmoid(self.pc._opacity) < min_opacity).reshape(-1))
+        return old_rows - self.pc.P
+
+    @torch.no_grad()
+    def _draw_by_gradient(self, increase_num: int, generator: Optional[torch.Generator], uniforms: int = 0):
+        """The draw of _uv_densify (model/fateavatar.py:610-624): `increase_num` rows with probability proportional to
+        xyz_gradient_accum (multinomial, with replacement), then `uniforms` uniform numbers per drawn row.  Data-parallel: the
+        statistics are per-view sums (model/fateavatar.py:734-737), so both draws are made on rank 0 (`generator`: rank 0's
+        only) from the sum over all ranks and broadcast — every replica appends the same rows.  Returns (the row indices,
+        the uniforms [increase_num, uniforms], the drawn rows' values in FIELDS order with their scale multiplied by 0.75)."""
         pc = self.pc
         acc, _ = self.reduce_densification_stats()
         w = acc.reshape(-1)
         idx = torch.zeros(increase_num, dtype=torch.int64, device=self.dev)
+        u = torch.zeros((increase_num, uniforms), dtype=torch.float32, device=self.dev)
         if float(w.sum()) <= 0:       # (the summed statistics are identical on every rank: all of them raise, none is left
             raise RuntimeError("no densification statistics accumulated yet")   # waiting in the broadcast below)
         if not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0:
-            idx = torch.multinomial(w, increase_num, replacement=True, generator=generator)   # (`generator`: rank 0's only)
+            idx = torch.multinomial(w, increase_num, replacement=True, generator=generator)
+            if uniforms:
+                u = torch.rand((increase_num, uniforms), device=self.dev, generator=generator)
         dp.broadcast_(idx)
+        if uniforms:
+            dp.broadcast_(u)
         rows = [getattr(pc, name).detach()[idx].clone() for name, _ in pc.FIELDS]
         i = self._field_index("_scaling")
-        rows[i] = torch.log(torch.exp(rows[i]) * 0.75)
-        old_rows = pc.P
-        old_index = pc.resize(new_rows=rows)
-        self._buffers_moved(old_index, old_rows, stats=None)
+        rows[i] = torch.log(torch.exp(rows[i]) * 0.75)          # new_scaling (:624)
+        return idx, u, rows
+
+    @torch.no_grad()
+    def densify_by_gradient(self, increase_num: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """The sampling and cloning rule of _uv_densify (model/fateavatar.py:610-672) without the mesh re-binding
+        (`_draw_by_gradient`); appended rows start with zero Adam moments.  Returns the sampled row indices."""
+        idx, _, rows = self._draw_by_gradient(increase_num, generator)
+        self._resize(carry_stats=False, new_rows=rows)
         return idx
 
     @torch.no_grad()
@@ -354,16 +380,22 @@ class TrainStep:
 class BoundStep(TrainStep):
     """What the steps of the mesh-bound models share on top of TrainStep: `step(camera, posed_verts, gt_image)` — the posed
     vertices are one more static input of the captured step —, the choice between the binding folded into the rasterizer's
-    per-Gaussian kernels and the stand-alone binding op, and one Adam group per field of the holder.  A subclass names its
-    rates (`LRS`, `LR_KEYS`) and writes `_forward_backward`."""
+    per-Gaussian kernels and the stand-alone binding op, one Adam group per field of the holder, and the checkpoint pair.  A
+    subclass names its rates (`LRS`, `LR_KEYS`) and its checkpoint layout (`GAUSSIAN_ATTRIBUTES`, `ROW_BUFFER_KEYS`,
+    `RESUME_REMAPPED`) and writes `_forward_backward`."""
     LRS: dict = {}            # the model's learning rates by the reference's group names
     LR_KEYS: dict = {}        # field of the holder -> its key in LRS
     STATS_ON_HOLDER = False   # every frame carries the statistics' buffers itself
+    GAUSSIAN_ATTRIBUTES: list = []   # what a checkpoint's 'model' must hold of the Gaussians
+    ROW_BUFFER_KEYS: dict = {}       # row buffer of the holder -> its name in 'model' (default: the attribute's own)
+    RESUME_REMAPPED = False          # load_state_dict without an `optimizer` entry: the step count goes on, or (False) restarts
 
     def __init__(self, pc, faces: torch.Tensor, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True,
                  image_loss: Optional[ImageLoss] = None, data_parallel: bool = True):
         """`verts` [V,3]: any pose of the mesh (sizes the step's static vertex buffer and is its first content)."""
+        if not data_parallel and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise RuntimeError(f"{type(self).__name__}: data-parallel runs are not built (DESIGN.md)")
         self.pc, self.bg = pc, bg
         self.fold_binding = bool(fold_binding)
         self.dev = pc.flat.device
@@ -382,3 +414,147 @@ class BoundStep(TrainStep):
 
     def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor) -> torch.Tensor:
         return super().step(camera, gt_image, [(self.verts, posed_verts)])
+
+    # ---- checkpoints in the reference's layout (Trainer.save_checkpoint, train/trainer.py:396-435: a dict with 'global_step'
+    #      and 'model' = model.state_dict(), which holds the Gaussian parameters and the binding buffers under the model's
+    #      own names next to whatever else the model owns); 'optimizer' and 'densification' are additions a seamless
+    #      resume needs, the reference saves neither
+    def _save_extras(self, sd: dict) -> None:
+        """What the model's checkpoint holds beyond the holder's fields and row buffers: written into `sd`."""
+
+    def _load_extras(self, sd: dict, g: dict) -> None:
+        """The model's own checks and entries; `g` = the popped Gaussian attributes.  Runs before anything is changed."""
+
+    @torch.no_grad()
+    def state_dict(self) -> dict:
+        pc = self.pc
+        model = {name: getattr(pc, name).detach().clone() for name, _ in pc.FIELDS}
+        model.update({self.ROW_BUFFER_KEYS.get(attr, attr): getattr(pc, attr).clone() for attr, _, _ in pc.ROW_BUFFERS})
+        sd = {"global_step": self.adam.step_count, "model": model}
+        self._save_extras(sd)
+        return {**sd, **self._training_state()}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> list:
+        """deserialize_checkpoints_fateavatar (train/deserialize.py:7-40): the Gaussian attributes are POPPED from
+        sd['model'] (their row count differs from the freshly built model's), re-attached as parameters / buffers — any row
+        count —, and the per-point statistics restart from zero unless the checkpoint brings them; whatever else 'model'
+        holds (FLAME, blendshape deltas: outside this path) is returned as the list of ignored keys.  A checkpoint written by
+        the reference itself loads the same way."""
+        model = dict(sd["model"])
+        missing = [k for k in self.GAUSSIAN_ATTRIBUTES if k not in model]
+        if missing:
+            raise KeyError(f"checkpoint lacks Gaussian attributes {missing}")
+        g = {k: model.pop(k) for k in self.GAUSSIAN_ATTRIBUTES}
+        self._load_extras(sd, g)
+        pc = self.pc
+        old_rows, P = pc.P, int(g[pc.FIELDS[0][0]].shape[0])
+        for attr, dtype, _ in pc.ROW_BUFFERS:
+            setattr(pc, attr, g[self.ROW_BUFFER_KEYS.get(attr, attr)].to(self.dev, dtype).contiguous())
+        pc._bind([g[name].to(self.dev, torch.float32).reshape((P,) + pc.SHAPES[name]) for name, _ in pc.FIELDS])
+        if self.RESUME_REMAPPED:   # a checkpoint without an `optimizer` entry goes on from this step's count with zero moments
+            self._buffers_moved(torch.full((P,), -1, dtype=torch.int64, device=self.dev), old_rows, stats=None)
+        else:                      # ... or starts the optimizer over: FRESH, step count 0
+            self._buffers_moved(None, None, stats=None)
+        self._load_training_state(sd)
+        return sorted(model.keys())
+
+
+class CloneSplitStep(BoundStep):
+    """The density control the 3DGS-style bound models share — GaussianAvatars' and SplattingAvatar's `_densify_and_prune`,
+    `_clone_densify`, `_split_densify`, `_prune` (model/baseline/gaussianavatars.py:278-475, splattingavatar.py:386-665) — with
+    TrainStep's conventions (`_resize`): torch index surgery under no_grad between step() calls, the moments follow their rows,
+    the graph is dropped when the buffers move, host_steps is untouched.  A model says where a split child goes
+    (`_split_children`) and which marked rows a prune may not take (`_prune_guard`)."""
+
+    def _split_children(self, rows, sel, samples, N):
+        """`rows`: the selected parents' values (FIELDS order) repeated N times, `sel` [P] bool: the parents, `samples` [N n, 3]
+        ~ N(0, exp(_scaling)).  Returns (the children's rows — their `_scaling` is set by the caller —, their row buffers under
+        resize()'s keywords)."""
+        raise NotImplementedError
+
+    def _prune_guard(self, mask: torch.Tensor) -> torch.Tensor:
+        """The rows of `mask` a prune may remove: all of them, unless the model says otherwise."""
+        return mask
+
+    @torch.no_grad()
+    def _append(self, rows, **row_buffers) -> int:
+        """Appends `rows` (FIELDS order) with their row buffers and zero moments; the statistics restart from zero whether or
+        not anything was appended (_densification_postfix always runs, gaussianavatars.py:462-475, splattingavatar.py:577-603)."""
+        n = int(rows[0].shape[0])
+        if n == 0:
+            self.xyz_gradient_accum.zero_()
+            self.denom.zero_()
+            return 0
+        self._resize(carry_stats=False, new_rows=rows, **row_buffers)
+        return n
+
+    @torch.no_grad()
+    def prune(self, mask: torch.Tensor) -> int:
+        """_prune (gaussianavatars.py:418-460, splattingavatar.py:606-665): removes the Gaussians marked in `mask` [P] that
+        `_prune_guard` lets go; the surviving rows keep their statistics (:455-456) and moments.  Returns the number of
+        Gaussians removed."""
+        mask = mask.to(self.dev).bool().reshape(-1)
+        if mask.numel() != self.pc.P:
+            raise ValueError("prune: mask must have one entry per Gaussian")
+        mask = self._prune_guard(mask)
+        n = int(mask.sum())
+        if n:
+            self._resize(carry_stats=True, keep_mask=~mask)
+        return n
+
+    @torch.no_grad()
+    def prune_low_opacity(self, min_opacity: float = 0.005) -> int:
+        """`prune` with the opacity mask of _densify_and_prune (gaussianavatars.py:287, splattingavatar.py:395-397)."""
+        return self.prune((torch.sigmoid(self.pc._opacity) < min_opacity).reshape(-1))
+
+    @torch.no_grad()
+    def densify_and_prune(self, max_grad: float, min_opacity: float = 0.005, extent: float = 2.0, max_screen_size=None,
+                          generator: Optional[torch.Generator] = None):
+        """_densify_and_prune with _clone_densify and _split_densify; call it between step() calls.  Returns (cloned, split,
+        pruned) row counts.
+          * grads = xyz_gradient_accum / denom, NaN -> 0
+          * clone: rows with grads >= max_grad and max exp(_scaling) <= percent_dense * extent are appended as they are, with
+            their row buffers
+          * split, over the set after the clone (the clones' padded gradient is 0), N = 2: rows with grads >= max_grad and max
+            exp(_scaling) > percent_dense * extent get two children placed by `_split_children` from sample ~ N(0,
+            exp(_scaling)) — ONE torch.normal(mean=zeros, std=stds, generator=generator) call of shape [2 n, 3], made on the
+            generator's device, also when nothing is selected — with _scaling = log(exp(_scaling) / (0.8 N)); the selected
+            originals are then removed through `prune`
+          * appended rows start with zero Adam moments, the step count is kept; the statistics restart from zero after the
+            clone and after the split, even when nothing was selected (and then nothing is resized: the captured step stays)
+          * final prune: sigmoid(_opacity) < min_opacity, and with a truthy `max_screen_size` also max exp(_scaling) >
+            0.1 * extent.  The reference also ORs in `max_radii2D > max_screen_size`; that test can never fire there
+            (_densification_postfix zeroes max_radii2D in clone and in split immediately before it), so max_radii2D is not
+            tracked here.
+        The reference calls this between backward() and optimizer.step(), where the new Parameters have no gradients; that
+        ordering is not copied."""
+        pc = self.pc
+        grads = self.xyz_gradient_accum / self.denom
+        grads[grads.isnan()] = 0.0
+        grads = torch.norm(grads, dim=-1)
+        fields = lambda sel: [getattr(pc, name).detach()[sel] for name, _ in pc.FIELDS]  # noqa: E731
+        largest = lambda: torch.exp(pc._scaling.detach()).max(dim=1).values  # noqa: E731
+        # ---- clone
+        sel = (grads >= max_grad) & (largest() <= PERCENT_DENSE * extent)
+        n_clone = self._append(fields(sel), **{key: getattr(pc, attr)[sel] for attr, _, key in pc.ROW_BUFFERS})
+        # ---- split
+        N = 2
+        padded = torch.zeros(pc.P, device=self.dev)
+        padded[:grads.shape[0]] = grads
+        sel = (padded >= max_grad) & (largest() > PERCENT_DENSE * extent)
+        n_split = int(sel.sum())
+        rows = [r.repeat((N,) + (1,) * (r.dim() - 1)) for r in fields(sel)]
+        stds = torch.exp(rows[self._field_index("_scaling")])   # exp(_scaling)[sel].repeat(N, 1)
+        gdev = generator.device if generator is not None else self.dev
+        samples = torch.normal(mean=torch.zeros((stds.shape[0], 3), device=gdev), std=stds.to(gdev), generator=generator).to(self.dev)
+        rows, row_buffers = self._split_children(rows, sel, samples, N)
+        rows[self._field_index("_scaling")] = torch.log(stds / (0.8 * N))
+        self._append(rows, **row_buffers)
+        if n_split:
+            self.prune(torch.cat([sel, torch.zeros(N * n_split, dtype=torch.bool, device=self.dev)]))
+        # ---- prune
+        mask = (torch.sigmoid(pc._opacity.detach()) < min_opacity).reshape(-1)
+        if max_screen_size:
+            mask |= torch.exp(pc._scaling.detach()).max(dim=1).values > 0.1 * extent
+        return n_clone, n_split, self.prune(mask)

@@ -166,3 +166,20 @@ def test_rigged_gaussians_resize_carries_the_binding_and_returns_the_row_map():
     assert pc._xyz[:3].tolist() == [[0, 1, 2], [6, 7, 8], [9, 10, 11]] and bool((pc._xyz[3:] == 7).all())
     assert pc.flat.numel() == 5 * sum(pc.widths()) == pc.flat_grad.numel()
     assert pc.grad_view("_scaling").data_ptr() == pc.flat_grad[5 * 56:].data_ptr() and pc.grad_view("_xyz").shape == (5, 3)
+
+
+def test_build_rotation_is_the_restatements_matrix_and_a_rotation():
+    """`gs_utils.build_rotation` against tests/rigged_density_ref.build_rotation (general_utils.py:78-99 restated entry by entry) on
+    257 raw, unnormalised float64 quaternions.  The two differ only in how the norm's four squares are summed and in the order of
+    the products: every entry is <= 1 in magnitude and is reached in fewer than 16 roundings, so |got - want| <= 16 x 2^-52;
+    R R^T = I and det R = 1 to the same count times the three terms of a row product."""
+    from fateavatar_amd.gs_utils import build_rotation
+    from tests.rigged_density_ref import build_rotation as want_rotation
+    q = torch.randn(257, 4, dtype=torch.float64, generator=torch.Generator().manual_seed(12)) * 3.0
+    got, want = build_rotation(q), want_rotation(q)
+    eps = 2.0 ** -52
+    assert got.shape == (257, 3, 3) and got.dtype == torch.float64
+    assert float((got - want).abs().max()) <= 16 * eps
+    assert float((got @ got.transpose(1, 2) - torch.eye(3, dtype=torch.float64)).abs().max()) <= 48 * eps
+    assert float((torch.linalg.det(got) - 1).abs().max()) <= 48 * eps
+    assert torch.equal(build_rotation(torch.tensor([[2.0, 0.0, 0.0, 0.0]])), torch.eye(3).unsqueeze(0))
