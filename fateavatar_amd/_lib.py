@@ -89,6 +89,10 @@ class fr_regularise_config(C.Structure):
                 ("threshold_xyz", C.c_float)]
 
 
+class fr_mesh_terms_config(C.Structure):
+    _fields_ = [("laplacian_weight", C.c_float), ("flame_weight", C.c_float)]
+
+
 class fr_image_loss_config(C.Structure):
     _fields_ = [("rgb_weight", C.c_float), ("dssim_weight", C.c_float)]
 
@@ -110,7 +114,7 @@ class fr_counts(C.Structure):
 
 EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile_enable", "fr_profile_read", "fr_geometry_bytes", "fr_image_bytes",
            "fr_binning_bytes", "fr_planes_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
-           "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
+           "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_mesh_terms_workspace_bytes", "fr_mesh_terms", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
            "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_phong_frame", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward"]
 
 
@@ -231,6 +235,10 @@ def lib():
     L.fr_regularise_workspace_bytes.restype = C.c_size_t
     L.fr_gaussian_regularise.argtypes = [C.POINTER(fr_regularise_config), C.c_int32, _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p]
     L.fr_gaussian_regularise.restype = C.c_int
+    L.fr_mesh_terms_workspace_bytes.argtypes = []
+    L.fr_mesh_terms_workspace_bytes.restype = C.c_size_t
+    L.fr_mesh_terms.argtypes = [C.POINTER(fr_mesh_terms_config), C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p]
+    L.fr_mesh_terms.restype = C.c_int
     L.fr_ssim_window.argtypes = [C.POINTER(C.c_float)]
     L.fr_ssim_window.restype = None
     L.fr_image_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

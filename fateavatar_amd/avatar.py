@@ -29,7 +29,7 @@ from .bound import MeshBinding, render_bound_batch
 from .flat import FlatParams
 from .model import TorchCamera
 from .render import render
-from .loss import l1_loss_and_grad, l1_workspace
+from .loss import MeshTerms, l1_loss_and_grad, l1_workspace, mesh_terms_and_grad, mesh_terms_workspace
 from .train import BoundStep
 
 # config/fateavatar.yaml:34-39 (group names of train/optim.py:15-21)
@@ -115,13 +115,17 @@ class _RawFrame:
 
 class AvatarStep(BoundStep):
     """One optimisation step of FateAvatar per call: `step(camera, posed_verts, gt_image)`.  The optimizer groups are those
-    of train/optim.py:15-21 with config/fateavatar.yaml:34-39."""
+    of train/optim.py:15-21 with config/fateavatar.yaml:34-39 (the `gs` group).  The other half of the model — the mesh
+    under the Gaussians, learnt through FLAME's `delta_shapedirs` / `delta_posedirs` / `delta_vertex`
+    (model/fateavatar.py:87-94,212-223, the `bs` group) — stays the caller's, in stock PyTorch: `vertex_grad` / `mesh_terms`
+    hand it this step's dLoss/dposed_verts."""
     LRS = FATE_LRS
     LR_KEYS = {"_opacity": "opacity", "_offset": "offset", "_features_dc": "color", "_rotation": "rotation", "_scaling": "scaling"}
 
     def __init__(self, pc: AvatarGaussians, faces: torch.Tensor, canonical_verts: torch.Tensor, camera: TorchCamera,
                  bg: torch.Tensor, lrs: Optional[dict] = None, shell_len: float = 0.05, resize_scale: bool = True,
-                 use_graph: bool = True, fold_binding: bool = True, keep_coherent: bool = False):
+                 use_graph: bool = True, fold_binding: bool = True, keep_coherent: bool = False, vertex_grad: bool = False,
+                 mesh_terms: Optional[MeshTerms] = None):
         """`keep_coherent`: after every `uv_densify` the rows are re-stored in a spatially coherent order (`sort_coherent`):
         the reference appends the new rows at the end (model/fateavatar.py:640-665), so a set that started in UV-raster
         order (mesh_sampling.py:86-138: neighbours in storage are neighbours on the mesh) grows an unordered tail; the
@@ -129,9 +133,25 @@ class AvatarStep(BoundStep):
         row i as in the reference.
         `fold_binding` (default): the binding is evaluated inside the rasterizer's per-Gaussian kernels (bound.py,
         fr_aux::binding) — no binding launches, no bound arrays written by one kernel to be read by the next.  False: the
-        stand-alone `bind_gaussians` op in front of `render()` (same results; kept as the A/B and as the op's own user)."""
+        stand-alone `bind_gaussians` op in front of `render()` (same results; kept as the A/B and as the op's own user).
+        `vertex_grad`: `d_verts` [V,3] holds every step's dLoss/dposed_verts (BoundStep).
+        `mesh_terms`: a `MeshTerms` (REFERENCE_MESH_TERMS holds the reference's 1e5 / 0) adds FateAvatar's Laplacian-smoothing
+        and FLAME-distance terms (train/loss.py:112-121,166-180,192-197) to every step: `step(..., verts_orig=)` takes the
+        mesh the posed one is held to (the reference's `verts_orig`: the FLAME mesh without the learnt deltas, same pose) as
+        one more static input, and ONE launch behind the rasterizer's backward (`loss.mesh_terms_and_grad`) adds the terms'
+        weighted gradient into `d_verts`; `mesh_loss` then holds the step's unweighted (laplacian_loss, flame_loss), `loss`
+        stays the image term.  Implies `vertex_grad`.  None (default): no such launch, `mesh_loss` is None."""
         self.keep_coherent = bool(keep_coherent)
-        super().__init__(pc, faces, camera, bg, canonical_verts, lrs, use_graph, fold_binding)
+        self.mesh_terms = None if mesh_terms is None else MeshTerms(*[float(x) for x in mesh_terms])
+        super().__init__(pc, faces, camera, bg, canonical_verts, lrs, use_graph, fold_binding,
+                         vertex_grad=bool(vertex_grad) or mesh_terms is not None)
+        self.mesh_loss = self.verts_orig = self.laplacian = self._mesh_ws = None
+        if self.mesh_terms is not None:
+            from .binding import mesh_laplacian
+            self.laplacian = mesh_laplacian(self.faces, int(self.verts.shape[0]))
+            self.verts_orig = self.verts.clone()       # static input of the captured step
+            self.mesh_loss = torch.zeros(2, device=self.dev)
+            self._mesh_ws = mesh_terms_workspace(self.dev)
         self.shell_len, self.resize_scale = float(shell_len), bool(resize_scale)
         self.canon_verts = self.verts.clone()
         # compute_face_orientation(canonical verts, return_scale=True)[1] (model/fateavatar.py:84-85)
@@ -145,18 +165,32 @@ class AvatarStep(BoundStep):
         _dimage, xyz_gradient_accum, denom, out: this object itself, or one lane of an AvatarBatchStep."""
         pc = L.pc
         pc.begin_step()                                             # zero_grad(set_to_none=True), iteration.py:48-49
+        verts = self._vertex_leaf(L.verts)
         if self.fold_binding:
             from . import rasterizer
-            out = render_bound_batch([L.cam], [_RawFrame(pc, (L.xyz_gradient_accum, L.denom, pc.overflow_word))], [L.verts], self._binding(pc),
+            out = render_bound_batch([L.cam], [_RawFrame(pc, (L.xyz_gradient_accum, L.denom, pc.overflow_word))], [verts], self._binding(pc),
                                      self.bg, slots=[rasterizer._slot])[0]
         else:
-            xyz, rot, scl = bind_gaussians(L.verts, self.faces, pc.face_index, pc.bary_coords, self.face_scale_canonical,
+            xyz, rot, scl = bind_gaussians(verts, self.faces, pc.face_index, pc.bary_coords, self.face_scale_canonical,
                                            pc._offset, pc._rotation, pc._scaling, self.shell_len, self.resize_scale)
             frame = _BoundFrame(xyz, pc, rot, scl, (L.xyz_gradient_accum, L.denom, pc.overflow_word))
             out = render(L.cam, frame, self.bg)
         _, g = l1_loss_and_grad(out["render"], L.gt, loss_out=L.loss, grad_out=L._dimage, workspace=L._l1_ws)   # see TrainStep
         out["render"].backward(g)
+        self._keep_vertex_grad(verts)
+        if self.mesh_terms is not None:
+            # train/loss.py:112-121: weight x the mesh terms' gradient is ADDED to the image term's dL/dposed_verts.  A replay
+            # that overflowed its binning capacity back-propagated zeros: d_verts then holds the mesh terms alone.
+            mesh_terms_and_grad(L.verts, self.verts_orig, self.laplacian, self.mesh_terms, d_verts=self.d_verts, out=self.mesh_loss,
+                                workspace=self._mesh_ws)
         L.out = self._kept(out)
+
+    def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor,
+             verts_orig: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`verts_orig` [V,3]: the mesh the mesh terms hold `posed_verts` to — required with `mesh_terms`, refused without."""
+        if (verts_orig is None) != (self.mesh_terms is None):
+            raise ValueError("AvatarStep.step: `verts_orig` goes with `mesh_terms` (required with them, refused without)")
+        return super().step(camera, posed_verts, gt_image, () if verts_orig is None else [(self.verts_orig, verts_orig.detach())])
 
     def _binding(self, pc: AvatarGaussians) -> MeshBinding:
         return MeshBinding(self.faces, pc.face_index, pc.bary_coords, self.face_scale_canonical, self.shell_len, self.resize_scale)
@@ -256,6 +290,9 @@ class AvatarBatchStep(AvatarStep):
         from . import _lib
         if not 1 <= int(views_per_step) <= _lib.FR_ADAM_MAX_GRADS:
             raise ValueError(f"views_per_step must be 1..{_lib.FR_ADAM_MAX_GRADS}")
+        if kw.get("vertex_grad") or kw.get("mesh_terms") is not None:
+            raise NotImplementedError("AvatarBatchStep: `vertex_grad` / `mesh_terms` are not built for the batch step (two step "
+                                      "bodies, and its twelve multi_copy segments are used up at K = 4): use AvatarStep")
         self.K = int(views_per_step)
         self.chain = bool(chain)
         self._chain_graph = None

@@ -25,6 +25,9 @@ the posed mesh's Phong surface,
 quaternions, face area ratios: ONE kernel without atomics where the reference runs pytorch3d's verts_normals_packed,
 torch.inverse, matrix_to_quaternion and six index_add calls).  Differentiable w.r.t. uvd, rotation and scaling; the mode has no
 gradient to the posed vertices.
+
+`mesh_laplacian` is the once-per-mesh side of FateAvatar's Laplacian-smoothing term (train/loss.py:112-121,166-180): pytorch3d's
+`Meshes.laplacian_packed()` as a CSR adjacency for `loss.mesh_terms_and_grad` / `loss.laplacian_smoothing_loss`.
 """
 from __future__ import annotations
 
@@ -110,6 +113,51 @@ def triangle_neighbours(faces: torch.Tensor) -> torch.Tensor:
     other = order[pos]                                            # = 3 g + k
     out = torch.where(found, 4 * (other // 3) + other % 3, torch.full_like(other, -1))
     return out.reshape(F, 3).to(torch.int32).contiguous()
+
+
+class MeshLaplacian(NamedTuple):
+    """The uniform Laplacian of a mesh as a CSR adjacency (`mesh_laplacian`): row i lists the neighbours of vertex i in
+    ascending order; L[i,j] = 1 / deg(i) for a neighbour j, L[i,i] = -1 for every vertex."""
+    row_ptr: torch.Tensor         # [V+1] int32
+    col: torch.Tensor             # [nnz] int32
+    V: int
+
+    def to_dense(self, dtype=torch.float32) -> torch.Tensor:
+        """The V x V matrix the reference applies (`meshes.laplacian_packed().to_dense()`), on the arrays' device."""
+        rp, V = self.row_ptr.long(), int(self.V)
+        deg = rp[1:] - rp[:-1]
+        row = torch.repeat_interleave(torch.arange(V, device=rp.device), deg)
+        L = torch.zeros((V, V), dtype=dtype, device=rp.device)
+        L[row, self.col.long()] = (1.0 / deg.to(dtype))[row]
+        L[torch.arange(V), torch.arange(V)] = -1.0
+        return L
+
+
+def mesh_laplacian(faces: torch.Tensor, V: int) -> MeshLaplacian:
+    """pytorch3d 0.7.7's `Meshes.laplacian_packed()` (`pytorch3d.ops.laplacian`, the uniform Laplacian the reference's
+    get_laplacian_smoothing_loss densifies, train/loss.py:166-180) as a CSR adjacency, once per mesh, in plain torch on the
+    faces' device.  The edges are the UNIQUE undirected pairs {a, b}, a != b, among the faces' three sides (a face listed
+    twice or in both windings adds nothing; a side with a repeated corner is no edge), deg(i) the number of distinct
+    neighbours of vertex i; a vertex no face uses has an empty row.  `faces` naming a vertex outside 0 .. V-1: ValueError —
+    the kernel that reads the result (`loss.mesh_terms_and_grad`) cannot check it."""
+    f = faces.detach().to(torch.int64)
+    V = int(V)
+    if f.dim() != 2 or f.shape[1] != 3 or V < 0:
+        raise RuntimeError("mesh_laplacian: faces [F,3], V >= 0")
+    if f.numel() and (int(f.min()) < 0 or int(f.max()) >= V):
+        raise ValueError("mesh_laplacian: `faces` names a vertex the mesh does not have")
+    a, b = f.reshape(-1), f.roll(-1, dims=1).reshape(-1)
+    keep = a != b
+    lo, hi = torch.minimum(a, b)[keep], torch.maximum(a, b)[keep]
+    key = torch.unique(lo * max(V, 1) + hi)                       # the undirected edges, once each
+    lo, hi = key // max(V, 1), key % max(V, 1)
+    both = torch.sort(torch.cat([lo * max(V, 1) + hi, hi * max(V, 1) + lo])).values   # (row, col) ascending
+    row, col = both // max(V, 1), both % max(V, 1)
+    if both.numel() >= 2 ** 31:
+        raise ValueError("mesh_laplacian: more than 2^31 - 1 non-zeros")
+    row_ptr = torch.zeros(V + 1, dtype=torch.int64, device=f.device)
+    row_ptr[1:] = torch.cumsum(torch.bincount(row, minlength=V), dim=0)
+    return MeshLaplacian(row_ptr.to(torch.int32).contiguous(), col.to(torch.int32).contiguous(), V)
 
 
 def phong_frame(canonical: PhongCanonical, verts: torch.Tensor):

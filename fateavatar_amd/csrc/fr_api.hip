@@ -604,6 +604,18 @@ int fr_gaussian_regularise(const fr_regularise_config* cfg, int32_t P, const flo
     return launch_gaussian_regularise(*cfg, P, scaling, xyz, d_scaling, d_xyz, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
+size_t fr_mesh_terms_workspace_bytes(void) { return mesh_terms_workspace_bytes(); }
+
+int fr_mesh_terms(const fr_mesh_terms_config* cfg, int32_t V, const float* verts, const float* verts_orig, const int32_t* row_ptr,
+                  const int32_t* col, float* d_verts, float* loss, void* workspace, void* stream)
+{
+    if (!cfg || V < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_mesh_terms: null configuration or negative V");
+    if (!verts || !verts_orig || !row_ptr) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_mesh_terms: null verts, verts_orig or row_ptr");
+    if (V > 0 && !col) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_mesh_terms: null col");
+    if (!workspace || !loss) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_mesh_terms: null workspace or loss");
+    return launch_mesh_terms(*cfg, V, verts, verts_orig, row_ptr, col, d_verts, loss, workspace, static_cast<hipStream_t>(stream));
+}
+
 int fr_multi_copy(int32_t n_segments, float* const* dst, const float* const* src, const uint64_t* count, void* stream)
 {
     if (n_segments < 0 || n_segments > FR_COPY_MAX_SEGMENTS || (n_segments > 0 && (!dst || !src || !count)))

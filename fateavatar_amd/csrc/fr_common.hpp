@@ -485,6 +485,9 @@ int launch_scaled_sum(int n_src, const float* const* src, float* dst, unsigned l
 size_t regularise_workspace_bytes();
 int launch_gaussian_regularise(const fr_regularise_config& cfg, int P, const float* scaling, const float* xyz, float* d_scaling,
                                float* d_xyz, float* loss, void* workspace, hipStream_t s);
+size_t mesh_terms_workspace_bytes();
+int launch_mesh_terms(const fr_mesh_terms_config& cfg, int V, const float* verts, const float* verts_orig, const int* row_ptr,
+                      const int* col, float* d_verts, float* loss, void* workspace, hipStream_t s);
 int launch_multi_copy(int n_seg, float* const* dst, const float* const* src, const unsigned long long* count, hipStream_t s);
 int launch_selftest_reduce(const float* in, float* out, hipStream_t s);
 

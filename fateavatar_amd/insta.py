@@ -46,7 +46,21 @@ def _rot(axis, ang):
 
 
 def synthetic_sequence(n_frames: int = 32, res: int = 512, seed: int = 0):
-    """(transform dict in INSTA layout, posed vertices [n_frames, V, 3] float32, faces [F, 3] int32).
+    return _synthetic(n_frames, res, seed)[:3]
+
+
+def synthetic_pose_maps(n_frames: int = 32, seed: int = 0):
+    """The mesh motion of `synthetic_sequence(n_frames, ., seed)` as the per-vertex LINEAR map it applies to a displacement of
+    the template: (jaw weight wj [V], jaw rotations Rj [n_frames,3,3], rigid rotations Rg [n_frames,3,3]), float32.  The
+    sequence poses a vertex v as Rg ((1 - wj) v + wj (Rj (v - hinge) + hinge) - neck) + neck + t with the template's own
+    wj, so a template displaced by delta is posed at `posed[f] + ((1 - wj) delta + wj delta Rj^T) Rg^T` — what a trainer that
+    learns such a delta in front of the motion (FateAvatar's `delta_vertex`, model/fateavatar.py:212-223) differentiates."""
+    wj, Rj, Rg = _synthetic(n_frames, 8, seed)[3]
+    return wj.astype(np.float32), np.stack(Rj).astype(np.float32), np.stack(Rg).astype(np.float32)
+
+
+def _synthetic(n_frames: int, res: int, seed: int):
+    """(transform dict in INSTA layout, posed vertices [n_frames, V, 3] float32, faces [F, 3] int32), (wj, [Rj], [Rg]).
 
     Camera: the config-2 camera (R = diag(1,-1,-1), T = (0, 1.47, 0.98), tan(fov/2) = 0.2) orbiting the head by up to
     +-12 degrees, written as camera-to-world matrices.  Mesh: the head template under a rigid nod / turn of a few
@@ -57,7 +71,7 @@ def synthetic_sequence(n_frames: int = 32, res: int = 512, seed: int = 0):
     V = verts.astype(np.float64)
     ctr = np.array([0.0, 1.47, 0.0])
     fl = 0.5 * res / 0.2
-    frames = []
+    frames, jaws, rigids = [], [], []
     posed = np.zeros((n_frames, V.shape[0], 3), np.float32)
     # jaw-like weight: below the mouth line and towards the front of the face
     y, z = V[:, 1], V[:, 2]
@@ -85,5 +99,7 @@ def synthetic_sequence(n_frames: int = 32, res: int = 512, seed: int = 0):
         Rg = _rot((0, 1, 0), math.radians(4.0) * math.sin(2 * math.pi * t + 0.7)) @ _rot((1, 0, 0), math.radians(2.5) * math.cos(2 * math.pi * t))
         P = (P - neck) @ Rg.T + neck + np.array([0.002, 0.001, 0.0]) * math.sin(4 * math.pi * t)
         posed[f] = P.astype(np.float32)
+        jaws.append(Rj)
+        rigids.append(Rg)
     transform = {"fl_x": fl, "fl_y": fl, "cx": res / 2, "cy": res / 2, "w": res, "h": res, "frames": frames}
-    return transform, posed, faces.astype(np.int32)
+    return transform, posed, faces.astype(np.int32), (wj, jaws, rigids)

@@ -139,6 +139,101 @@ def gaussian_regularisers(scaling: torch.Tensor, xyz: torch.Tensor, d_scaling: O
     return loss
 
 
+# ---- FateAvatar's mesh terms (FateAvatarLoss, train/loss.py:112-121, :166-180, :192-197): ONE launch (`fr_mesh_terms`) gives
+# both unweighted losses and adds their weighted gradient into dL/dposed_verts
+class MeshTerms(NamedTuple):
+    """Weights of FateAvatar's two mesh terms: config/fateavatar.yaml:23 has laplacian_loss 100000.0, flame_loss 0."""
+    laplacian_weight: float = 1e5
+    flame_weight: float = 0.0
+
+
+REFERENCE_MESH_TERMS = MeshTerms()
+
+_mesh_workspace = {}   # (device index, stream handle) -> zeroed scratch of fr_mesh_terms (as _workspace above)
+
+
+def mesh_terms_workspace(dev: torch.device) -> torch.Tensor:
+    """A fresh zeroed workspace for `mesh_terms_and_grad(..., workspace=)`."""
+    return torch.zeros((_lib.lib().fr_mesh_terms_workspace_bytes(),), dtype=torch.uint8, device=dev)
+
+
+def mesh_terms_and_grad(verts: torch.Tensor, verts_orig: torch.Tensor, lap, terms=REFERENCE_MESH_TERMS,
+                        d_verts: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                        workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """FateAvatar's Laplacian-smoothing and FLAME-distance terms of the mesh `verts` [V,3] against `verts_orig` [V,3] in ONE
+    launch (`fr_mesh_terms`): returns `out` = (laplacian_loss, flame_loss), UNWEIGHTED, a 2-element device tensor, and ADDS
+    terms.laplacian_weight * d laplacian_loss / d verts + terms.flame_weight * d flame_loss / d verts into `d_verts` [V,3]
+    (None: losses only; a weight of 0 skips its term, both 0 leave the buffer untouched).  `lap`: the mesh's
+    `binding.mesh_laplacian(faces, V)` on the vertices' device.  `workspace`: scratch from `mesh_terms_workspace()`; by
+    default one is kept per (device, current stream) — launches that may overlap must not share one.  There is no CPU path."""
+    if not (verts.is_cuda and verts_orig.is_cuda):
+        raise RuntimeError("mesh_terms_and_grad needs device tensors (there is no CPU path)")
+    dev = verts.device
+    V = int(lap.V)
+    verts, verts_orig = verts.detach(), verts_orig.detach()
+    for t in (verts, verts_orig, d_verts):
+        if t is None:
+            continue
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (V, 3):
+            raise RuntimeError("mesh_terms_and_grad: contiguous float32 [V,3] tensors of one device, V that of the Laplacian")
+    for t, n in ((lap.row_ptr, V + 1), (lap.col, None)):
+        if t.device != dev or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1 or (n is not None and t.numel() != n):
+            raise RuntimeError("mesh_terms_and_grad: `lap` is a binding.mesh_laplacian() on the vertices' device")
+    loss = out if out is not None else torch.empty((2,), dtype=torch.float32, device=dev)
+    if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
+        raise RuntimeError("mesh_terms_and_grad: `out` is a contiguous 2-element float32 tensor on the vertices' device")
+    L = _lib.lib()
+    ws = workspace
+    if ws is None:
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        ws = _mesh_workspace.get(key)
+        if ws is None:
+            if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
+                raise RuntimeError("mesh_terms_and_grad: first call on this stream happens inside a graph capture; call it "
+                                   "once eagerly on the stream first, or pass workspace=mesh_terms_workspace(device)")
+            ws = _mesh_workspace[key] = mesh_terms_workspace(dev)
+    elif not (ws.is_cuda and ws.device == dev and ws.dtype == torch.uint8 and ws.numel() >= L.fr_mesh_terms_workspace_bytes()):
+        raise RuntimeError("mesh_terms_and_grad: workspace must come from mesh_terms_workspace() on the vertices' device")
+    import ctypes as C
+    cfg = _lib.fr_mesh_terms_config(float(terms[0]), float(terms[1]))
+    # (a mesh without edges has an empty `col` nobody reads; the entry point refuses NULL, and an empty tensor has no address)
+    col = lap.col if lap.col.numel() else lap.row_ptr
+    nz = lambda t: t.data_ptr() if t.numel() else ws.data_ptr()   # noqa: E731  (V == 0: nothing is launched)
+    _lib.launch("fr_mesh_terms", dev, C.byref(cfg), V, nz(verts), nz(verts_orig), lap.row_ptr.data_ptr(), col.data_ptr(),
+                d_verts.data_ptr() if d_verts is not None else None, loss.data_ptr(), ws.data_ptr())
+    return loss
+
+
+class _LaplacianSmoothing(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts, verts_orig, lap):
+        shape = verts.shape
+        v = verts.detach().float().reshape(-1, 3).contiguous()
+        o = verts_orig.detach().float().reshape(-1, 3).contiguous()
+        grad = torch.zeros_like(v) if ctx.needs_input_grad[0] else None     # None: the loss only
+        loss = mesh_terms_and_grad(v, o, lap, MeshTerms(1.0, 0.0), d_verts=grad)
+        if grad is not None:
+            ctx.save_for_backward(grad.view(shape))
+        ctx.in_dtype = verts.dtype
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        return (grad * grad_output).to(ctx.in_dtype), None, None
+
+
+def laplacian_smoothing_loss(verts_orig: torch.Tensor, verts: torch.Tensor, lap) -> torch.Tensor:
+    """`FateAvatarLoss.get_laplacian_smoothing_loss(verts_orig, verts)` (train/loss.py:166-180), the reference's argument
+    order, with the mesh's `binding.mesh_laplacian` where the reference builds the dense matrix: ((L verts - L verts_orig)^2)
+    .sum(-1, keepdim=True).mean() as a 0-dim tensor, differentiable with respect to `verts` (the fused kernel's gradient,
+    scaled by the incoming one).  [V,3] or [1,V,3].  `verts_orig` takes no gradient (the reference detaches it)."""
+    for t in (verts, verts_orig):
+        if not (t.dim() == 2 or (t.dim() == 3 and t.shape[0] == 1)) or t.shape[-1] != 3:
+            raise RuntimeError(f"laplacian_smoothing_loss: vertices are [V,3] or [1,V,3], got {tuple(t.shape)}")
+    return _LaplacianSmoothing.apply(verts, verts_orig.detach(), lap)
+
+
 _copy_calls = {}   # (dst ptr, src ptr, floats) per pair -> the prepared argument arrays of fr_multi_copy
 
 

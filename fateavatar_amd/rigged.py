@@ -118,7 +118,7 @@ class RiggedStep(CloneSplitStep):
 
     def __init__(self, pc: RiggedGaussians, faces: torch.Tensor, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True,
-                 regularisers: Optional[Regularisers] = None, image_loss: Optional[ImageLoss] = None):
+                 regularisers: Optional[Regularisers] = None, image_loss: Optional[ImageLoss] = None, vertex_grad: bool = False):
         """`verts` [V,3]: any pose of the mesh (sizes the step's static vertex buffer and is its first content).
         `fold_binding` (default): the binding is evaluated inside the rasterizer's per-Gaussian kernels (fr_aux::binding with
         FR_BIND_FACE_LOCAL) — no binding launches.  False: the stand-alone `bind_gaussians_face_local` op in front of
@@ -129,8 +129,10 @@ class RiggedStep(CloneSplitStep):
         `image_loss`: an `ImageLoss` (REFERENCE_IMAGE_LOSS holds the reference's 0.8 / 0.2) makes the image term
         rgb_weight x L1 + dssim_weight x d_ssim (train/loss.py:351-365) — two launches where the L1 launch is; `loss_terms`
         then holds the step's (weighted image loss, l1, d_ssim) and `loss` is its first word.  None (default): the image
-        term is L1 with weight 1, `loss_terms` is None."""
-        super().__init__(pc, faces, camera, bg, verts, lrs, use_graph, fold_binding, image_loss, data_parallel=False)
+        term is L1 with weight 1, `loss_terms` is None.
+        `vertex_grad`: `d_verts` [V,3] holds every step's dLoss/dposed_verts (BoundStep)."""
+        super().__init__(pc, faces, camera, bg, verts, lrs, use_graph, fold_binding, image_loss, data_parallel=False,
+                         vertex_grad=vertex_grad)
         self.regularisers = None if regularisers is None else Regularisers(*[float(x) for x in regularisers])
         # the reference's out['scale_loss'] / out['xyz_loss'] of the step (unweighted), written by the regulariser launch
         self.reg_loss = None if regularisers is None else torch.zeros(2, device=self.dev)
@@ -158,14 +160,16 @@ class RiggedStep(CloneSplitStep):
         pc = self.pc
         pc.begin_step()                                             # zero_grad(set_to_none=True)
         stats = (self.xyz_gradient_accum, self.denom, pc.overflow_word)
+        verts = self._vertex_leaf(self.verts)
         if self.fold_binding:
             from . import rasterizer
-            out = render_bound_batch([self.cam], [_RiggedFrame(pc, stats)], [self.verts], FaceLocalBinding(self.faces, pc.binding),
+            out = render_bound_batch([self.cam], [_RiggedFrame(pc, stats)], [verts], FaceLocalBinding(self.faces, pc.binding),
                                      self.bg, slots=[rasterizer._slot])[0]
         else:
-            bound = bind_gaussians_face_local(self.verts, self.faces, pc.binding, pc._xyz, pc._rotation, pc._scaling)
+            bound = bind_gaussians_face_local(verts, self.faces, pc.binding, pc._xyz, pc._rotation, pc._scaling)
             out = render(self.cam, _RiggedFrame(pc, stats, bound), self.bg)
         out["render"].backward(self._image_loss_and_grad(out["render"]))   # see TrainStep
+        self._keep_vertex_grad(verts)
         pc.collect_grads()                                          # (the SH halves: see FlatParams.collect_grads)
         if self.regularisers is not None:
             # train/loss.py:367-379: weight x the two regularisers' gradients are ADDED to the image term's, in front of Adam.

@@ -133,19 +133,24 @@ class SplattingStep(CloneSplitStep):
     those of train/optim.py:106-117 with config/splattingavatar.yaml:26-30 (`_features_rest` is empty at SH degree 0: its
     group keeps its place and rate)."""
     LRS = SPLATTING_LRS
+    VERTEX_GRAD = False
+    VERTEX_GRAD_MISSING = ("the Phong-surface binding has no vertex gradient (its per-frame mesh pass is not differentiable, "
+                           "and fr_backward refuses fr_aux::d_verts in that mode)")
     LR_KEYS = {"_uvd": "uvd", "_opacity": "opacity", "_features_dc": "feature_dc", "_features_rest": "feature_rest",
                "_rotation": "rotation", "_scaling": "scaling"}
 
     def __init__(self, pc: SplattingGaussians, canonical: PhongCanonical, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
-                 lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True):
+                 lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True, vertex_grad: bool = False):
         """`canonical`: `binding.phong_canonical(cano_verts, faces)`; `verts` [V,3]: any pose of the mesh (sizes the step's
         static vertex buffer and is its first content).  `fold_binding` (default): the per-Gaussian binding is evaluated
         inside the rasterizer's per-Gaussian kernels (fr_aux::binding with FR_BIND_PHONG).  False: the stand-alone
-        `bind_gaussians_phong` op in front of render() (same results; the A/B and the op's own user)."""
+        `bind_gaussians_phong` op in front of render() (same results; the A/B and the op's own user).
+        `vertex_grad=True` raises: the Phong-surface binding has no gradient to the posed vertices."""
         self.canonical = PhongCanonical(*[t.to(pc.flat.device).contiguous() for t in canonical])
         if pc.P and (int(pc.face_index.min()) < 0 or int(pc.face_index.max()) >= int(self.canonical.faces.shape[0])):
             raise ValueError("SplattingStep: `face_index` names a face the mesh does not have")
-        super().__init__(pc, self.canonical.faces, camera, bg, verts, lrs, use_graph, fold_binding, data_parallel=False)
+        super().__init__(pc, self.canonical.faces, camera, bg, verts, lrs, use_graph, fold_binding, data_parallel=False,
+                         vertex_grad=vertex_grad)
 
     def _forward_backward(self):
         pc = self.pc

@@ -389,11 +389,22 @@ class BoundStep(TrainStep):
     GAUSSIAN_ATTRIBUTES: list = []   # what a checkpoint's 'model' must hold of the Gaussians
     ROW_BUFFER_KEYS: dict = {}       # row buffer of the holder -> its name in 'model' (default: the attribute's own)
     RESUME_REMAPPED = False          # load_state_dict without an `optimizer` entry: the step count goes on, or (False) restarts
+    VERTEX_GRAD = True               # the model's binding has a gradient to the posed vertices (`vertex_grad=True`) ...
+    VERTEX_GRAD_MISSING = ""         # ... or why it has none
 
     def __init__(self, pc, faces: torch.Tensor, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True,
-                 image_loss: Optional[ImageLoss] = None, data_parallel: bool = True):
-        """`verts` [V,3]: any pose of the mesh (sizes the step's static vertex buffer and is its first content)."""
+                 image_loss: Optional[ImageLoss] = None, data_parallel: bool = True, vertex_grad: bool = False):
+        """`verts` [V,3]: any pose of the mesh (sizes the step's static vertex buffer and is its first content).
+        `vertex_grad`: after every `step()`, `d_verts` [V,3] holds THIS step's dLoss/dposed_verts (the binding's backward
+        scatters it; zeroed by the step itself, never accumulated over steps; one storage across the replays of a captured
+        step, like `out`) — the caller goes on with `posed_verts.backward(step.d_verts)` into whatever made the mesh (FLAME
+        and its blendshape deltas: stock PyTorch) and its own optimizer.  It is this rank's frame's gradient: the caller's
+        mesh parameters need their own all-reduce.  A replay that overflowed its binning capacity back-propagated zeros.
+        False (default): no such buffer, `d_verts` is None and the kernels are handed no vertex-gradient array."""
+        if vertex_grad and not self.VERTEX_GRAD:
+            raise NotImplementedError(f"{type(self).__name__}(vertex_grad=True): {self.VERTEX_GRAD_MISSING}")
+        self.vertex_grad, self.d_verts = bool(vertex_grad), None
         if not data_parallel and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise RuntimeError(f"{type(self).__name__}: data-parallel runs are not built (DESIGN.md)")
         self.pc, self.bg = pc, bg
@@ -412,8 +423,21 @@ class BoundStep(TrainStep):
         P = self.pc.P
         return [(P * w, self.lr[self.LR_KEYS[name]]) for name, w in self.pc.FIELDS]
 
-    def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor) -> torch.Tensor:
-        return super().step(camera, gt_image, [(self.verts, posed_verts)])
+    def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor, _extra=()) -> torch.Tensor:
+        if self.vertex_grad:
+            posed_verts = posed_verts.detach()     # (the caller's mesh usually hangs on its autograd graph: only the values are loaded)
+        return super().step(camera, gt_image, [(self.verts, posed_verts), *_extra])
+
+    def _vertex_leaf(self, verts: torch.Tensor) -> torch.Tensor:
+        """What a frame hands its binding as the posed mesh: the static buffer `verts` itself, or with `vertex_grad` a leaf
+        over the same storage (no copy), whose gradient `_keep_vertex_grad` picks up after the backward."""
+        return verts.detach().requires_grad_(True) if self.vertex_grad else verts
+
+    def _keep_vertex_grad(self, leaf: torch.Tensor) -> None:
+        """After the frame's backward: `d_verts` = the leaf's gradient — the buffer the binding's backward zeroed and
+        scattered into (inside a captured step: graph-owned storage, the same on every replay)."""
+        if self.vertex_grad:
+            self.d_verts = leaf.grad
 
     # ---- checkpoints in the reference's layout (Trainer.save_checkpoint, train/trainer.py:396-435: a dict with 'global_step'
     #      and 'model' = model.state_dict(), which holds the Gaussian parameters and the binding buffers under the model's

@@ -397,6 +397,31 @@ size_t fr_regularise_workspace_bytes(void);
 int fr_gaussian_regularise(const fr_regularise_config* cfg, int32_t P, const float* scaling, const float* xyz,
                            float* d_scaling, float* d_xyz, float* loss, void* workspace, void* hip_stream);
 
+/* ---- FateAvatar's two mesh terms and their gradient with respect to the posed vertices in ONE launch (reference:
+ * FateAvatarLoss.get_laplacian_smoothing_loss and flame_loss, train/loss.py:112-121, :166-180, :192-197, where the uniform
+ * Laplacian is a dense V x V matrix applied with bmm).  `row_ptr` [V+1], `col` [row_ptr[V]]: the mesh's adjacency in CSR
+ * form, every row ascending and duplicate-free, symmetric (j in row i <=> i in row j), no self-edges; L[i,i] = -1 for every
+ * vertex, L[i,j] = 1 / deg(i) for a neighbour j (pytorch3d's Meshes.laplacian_packed()).  With d = verts - verts_orig
+ * ([V,3] floats each) and r = L d:
+ *   loss[0] = (1/V) sum_i |r_i|^2      ((L verts - L verts_orig)^2 .sum(-1, keepdim=True).mean())
+ *   loss[1] = mean over the 3 V entries of d^2
+ * both UNWEIGHTED, and the kernel ADDS into `d_verts` [V,3]
+ *   laplacian_weight * (2/V) * (-r_i + sum_{j in N(i)} r_j / deg(j)) + flame_weight * (2/(3V)) * d_i
+ * by a read-modify-write of the lane that owns the row (it recomputes its neighbours' r_j: no atomics, no second launch).
+ * A weight of 0 skips that term's gradient arithmetic; with both weights 0 `d_verts` is not touched; `d_verts` may be NULL
+ * (losses only).  An empty row (a vertex no face uses) has r_i = -d_i and divides by nothing.  The losses are
+ * bit-reproducible from launch to launch (per-workgroup partials summed in index order by the workgroup that finishes last).
+ * `workspace`: fr_mesh_terms_workspace_bytes() bytes of device memory, zeroed ONCE by the caller; the kernel leaves it
+ * zeroed; not to be shared by launches that can overlap on the device.  The call can be captured in a graph.  V == 0
+ * launches nothing and leaves `loss` as it is.  The kernel cannot validate the CSR arrays: that is the caller's side
+ * (binding.mesh_laplacian). */
+typedef struct fr_mesh_terms_config {
+    float laplacian_weight, flame_weight; /* reference: 1e5, 0 (config/fateavatar.yaml:23) */
+} fr_mesh_terms_config;
+size_t fr_mesh_terms_workspace_bytes(void);
+int fr_mesh_terms(const fr_mesh_terms_config* cfg, int32_t V, const float* verts, const float* verts_orig,
+                  const int32_t* row_ptr, const int32_t* col, float* d_verts, float* loss, void* workspace, void* hip_stream);
+
 /* ---- dst = scale * (src[0] + ... + src[n_src - 1]), n_src in 1 .. FR_ADAM_MAX_GRADS arrays of `count` floats, 16-byte
  * aligned: the mean of the gradient buffers of the views a rank rendered in flight together, written into the exchange
  * buffer of the data-parallel all-reduce in one pass.  dst may be one of the sources. */

@@ -9,6 +9,13 @@ weights are absent: declared stand-in for the INSTA sequence); the trained set s
 opacity.  Prints one JSON line: optimisation steps/s (render + L1 + backward + densification statistics + Adam, one
 frame per rank per step, one flat-gradient all-reduce when N > 1) and the loss before / after.
 
+    python tools/train_synthetic.py --fateavatar --train-mesh [--mesh-terms LAP FLAME --mesh-lr 1e-4]
+FateAvatar's step with the OTHER half of the model: the targets come from a template displaced by a seeded smooth bump, a
+torch `delta_vertex` leaf [V,3] is added to the template in front of the sequence's rigid and jaw motion and trained by
+torch.optim.Adam through `step.d_verts` (the step's dLoss/dposed_verts, the reference's mesh terms already in it; `verts_orig`
+is the undisplaced posed mesh).  Prints steps/s, the image loss, both mesh terms and |delta - bump| at start and end.
+--vertex-grad alone: the plain loop with the vertex gradient switched on (what that option costs).
+
     python tools/train_synthetic.py --rigged [--P 10006 --sh-degree 3 --binding-op]
 GaussianAvatars' step (fateavatar_amd/rigged.py): Gaussians rigged to the triangles of the posed template, one GPU.
     python tools/train_synthetic.py --rigged --P 10006 --regularisers --densify-from 0.3 --densify-interval 0.1 --reset-interval 0.5
@@ -65,6 +72,13 @@ def main():
     ap.add_argument("--fateavatar", action="store_true",
                     help="FateAvatar's own loop: mesh-bound parameters (offset / rotation / scaling / colour / opacity), "
                          "synthetic INSTA-layout sequence with per-frame posed mesh, SH degree 0")
+    ap.add_argument("--vertex-grad", action="store_true",
+                    help="--fateavatar: AvatarStep(vertex_grad=True): every step leaves dLoss/dposed_verts in step.d_verts")
+    ap.add_argument("--train-mesh", action="store_true",
+                    help="--fateavatar: train a torch delta_vertex leaf under the Gaussians through step.d_verts, with the mesh terms")
+    ap.add_argument("--mesh-terms", type=float, nargs=2, default=None, metavar=("LAP", "FLAME"),
+                    help="--train-mesh: weights of the Laplacian and FLAME-distance terms (default: the reference's 1e5 0)")
+    ap.add_argument("--mesh-lr", type=float, default=1e-4, help="--train-mesh: Adam rate of delta_vertex (train/optim.py:30)")
     ap.add_argument("--rigged", action="store_true",
                     help="GaussianAvatars' loop: Gaussians bound to the local frames of the template's faces (one per face, then "
                          "random faces up to --P), rendered with --sh-degree active; --binding-op as for --fateavatar")
@@ -95,6 +109,8 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     a.image_loss = ImageLoss(*a.image_loss) if a.image_loss else (ImageLoss(0.8, 0.2) if a.dssim else None)
+    if (a.train_mesh or a.vertex_grad or a.mesh_terms) and not (a.fateavatar and a.views_per_step == 1):
+        raise SystemExit("--train-mesh / --vertex-grad / --mesh-terms go with --fateavatar at one frame per step")
     if a.fateavatar:
         if a.image_loss:
             raise SystemExit("--fateavatar: the D-SSIM term is not part of FateAvatar's objective (dssim_loss 0.0)")
@@ -148,10 +164,12 @@ def main():
 
 
 def fateavatar_setup(P, res, dev, views=8, views_per_step=1, use_graph=True, chain=True, fold_binding=True, order="uv",
-                     keep_coherent=False):
+                     keep_coherent=False, vertex_grad=False, mesh_terms=None, target_delta=None):
     """FateAvatar's optimisation step on the synthetic INSTA-layout sequence: the mesh-bound Gaussian
     set, its step object (AvatarStep, or AvatarBatchStep for K > 1 frames per step), cameras, posed meshes and targets
     rendered from a hidden ground-truth set.  Used by this script and by bench.py's `avatar` mode.
+    `vertex_grad`, `mesh_terms`: AvatarStep's options (K = 1).  `target_delta` [V,3] (numpy): the targets are rendered from
+    the template displaced by it (`pose`, also returned, poses a displaced template differentiably).
     `order="uv"`: the reference's own initialisation — `uniform_sampling_barycoords(P, ...)` on the template's UV raster
     (model/fateavatar.py:128-133), rows in row-major texel order; `order="random"`: the area-weighted draw as drawn (the A/B)."""
     from fateavatar_amd import insta
@@ -166,6 +184,12 @@ def fateavatar_setup(P, res, dev, views=8, views_per_step=1, use_graph=True, cha
     cams = [TorchCamera(c, dev) for c in insta.camera_arrays(transform)]
     posed_t, faces_t, canon = torch.from_numpy(posed).to(dev), torch.from_numpy(faces).to(dev), torch.from_numpy(verts).to(dev)
     bg = torch.ones(3, device=dev)
+    wj, Rj, Rg = (torch.from_numpy(x).to(dev) for x in insta.synthetic_pose_maps(n_frames, seed=0))
+
+    def pose(f, delta):
+        """Frame f of the sequence for the template displaced by `delta` [V,3] (insta.synthetic_pose_maps): differentiable."""
+        return posed_t[f] + ((1.0 - wj)[:, None] * delta + wj[:, None] * (delta @ Rj[f].T)) @ Rg[f].T
+
     # hidden ground truth: same binding, other appearance
     gt = AvatarGaussians(fi, bc, scale_init, dev)
     g = torch.Generator().manual_seed(5)
@@ -177,29 +201,103 @@ def fateavatar_setup(P, res, dev, views=8, views_per_step=1, use_graph=True, cha
     gts = []
     with torch.no_grad():
         for f in range(n_frames):
-            xyz, rot, scl = bind_gaussians(posed_t[f], ref.faces, gt.face_index, gt.bary_coords, ref.face_scale_canonical, gt._offset,
+            shown = posed_t[f] if target_delta is None else pose(f, torch.from_numpy(target_delta).to(dev)).contiguous()
+            xyz, rot, scl = bind_gaussians(shown, ref.faces, gt.face_index, gt.bary_coords, ref.face_scale_canonical, gt._offset,
                                            gt._rotation, gt._scaling, ref.shell_len, True)
             gts.append(render(cams[f], _BoundFrame(xyz, gt, rot, scl, None), bg)["render"].clone())
     K = max(1, views_per_step)
     cam0 = TorchCamera(insta.camera_arrays(transform)[0], dev)
     if K == 1:
-        st = AvatarStep(pc, faces_t, canon, cam0, bg, use_graph=use_graph, fold_binding=fold_binding, keep_coherent=keep_coherent)
+        extra = {}          # (only what is asked for: a plain run constructs the step exactly as before)
+        if vertex_grad:
+            extra["vertex_grad"] = True
+        if mesh_terms is not None:
+            extra["mesh_terms"] = mesh_terms
+        st = AvatarStep(pc, faces_t, canon, cam0, bg, use_graph=use_graph, fold_binding=fold_binding, keep_coherent=keep_coherent,
+                        **extra)
     else:   # the reference's batch of K frames per step (model/fateavatar.py:251-276), in flight together
         from fateavatar_amd.avatar import AvatarBatchStep
         st = AvatarBatchStep(pc, faces_t, canon, cam0, bg, views_per_step=K, use_graph=use_graph, chain=chain,
                              fold_binding=fold_binding, keep_coherent=keep_coherent)
-    return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames, K=K)
+    return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames, K=K, pose=pose, canon=canon)
+
+
+def smooth_bump(verts, seed=0, height=0.004, width=0.03):
+    """A seeded smooth displacement of the template [V,3] (numpy): three Gaussian bumps of `height` m and `width` m standard
+    deviation around randomly chosen vertices of the face's front, along +z."""
+    rng = np.random.default_rng(seed)
+    front = np.flatnonzero((verts[:, 2] > 0.05) & (verts[:, 1] > 1.43))
+    out = np.zeros_like(verts, dtype=np.float32)
+    for c in verts[rng.choice(front, 3, replace=False)]:
+        out[:, 2] += height * np.exp(-((verts - c) ** 2).sum(1) / (2 * width * width))
+    return out
+
+
+def main_train_mesh(a, rank, world, dev):
+    """The demonstration of `step.d_verts`: FateAvatar's Gaussians by the fused step, its mesh by the caller's own Adam."""
+    if world > 1 or a.views_per_step != 1:
+        raise SystemExit("--train-mesh: one GPU, one frame per step (DESIGN.md)")
+    from fateavatar_amd.loss import MeshTerms, REFERENCE_MESH_TERMS
+    terms = MeshTerms(*a.mesh_terms) if a.mesh_terms else REFERENCE_MESH_TERMS
+    verts, _, _ = scenes.head_geometry()
+    bump = smooth_bump(np.asarray(verts, dtype=np.float32))
+    su = fateavatar_setup(a.P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
+                           order="random" if a.random_order else "uv", mesh_terms=terms, target_delta=bump)
+    st, cams, posed_t, gts, n_frames, pose = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"], su["pose"]
+    bump_t = torch.from_numpy(bump).to(dev)
+    delta = torch.zeros_like(bump_t, requires_grad=True)           # the reference's delta_vertex (model/fateavatar.py:93-94)
+    opt = torch.optim.Adam([delta], lr=a.mesh_lr)                  # its `bs` group: the caller's, stock PyTorch
+
+    def one_step(it):
+        f = it % n_frames
+        opt.zero_grad(set_to_none=True)
+        posed = pose(f, delta)
+        st.step(cams[f], posed, gts[f], verts_orig=posed_t[f])
+        posed.backward(st.d_verts)                                 # dLoss/dposed_verts -> dLoss/ddelta through the motion
+        opt.step()
+
+    def report():
+        torch.cuda.synchronize()
+        return dict(image_loss=round(float(st.loss), 6), laplacian_loss=float(st.mesh_loss[0]), flame_loss=float(st.mesh_loss[1]),
+                    delta_minus_bump=round(float((delta.detach() - bump_t).norm()), 6))
+
+    warm = 10
+    one_step(0)
+    first = report()
+    for it in range(1, warm):
+        one_step(it)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(warm, warm + a.steps):
+        one_step(it)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    st.check()
+    print(json.dumps({"metric": "FateAvatar optimisation steps/s with the mesh trained (fused step + mesh terms + torch Adam on delta_vertex)",
+                      "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": a.P, "res": a.res,
+                      "frames": n_frames, "graph": not a.no_graph, "overflows": st.overflows, "mesh_terms": list(terms),
+                      "mesh_lr": a.mesh_lr, "bump_norm": round(float(bump_t.norm()), 6), "first": first, "last": report()}))
 
 
 def main_fateavatar(a, rank, world, dev):
+    if a.train_mesh:
+        return main_train_mesh(a, rank, world, dev)
+    mesh_terms = moved = None
+    if a.mesh_terms:       # the mesh terms in the plain loop (what the launch costs): a fixed displaced mesh held to the posed one
+        from fateavatar_amd.loss import MeshTerms
+        mesh_terms = MeshTerms(*a.mesh_terms)
     su = fateavatar_setup(a.P, a.res, dev, views=a.views, views_per_step=a.views_per_step, use_graph=not a.no_graph, chain=a.chain,
-                           fold_binding=not a.binding_op, order="random" if a.random_order else "uv", keep_coherent=a.keep_coherent)
+                           fold_binding=not a.binding_op, order="random" if a.random_order else "uv", keep_coherent=a.keep_coherent,
+                           vertex_grad=a.vertex_grad, mesh_terms=mesh_terms)
     st, cams, posed_t, gts, n_frames, K = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"], su["K"]
+    if mesh_terms is not None:
+        bump = torch.from_numpy(smooth_bump(np.asarray(scenes.head_geometry()[0], dtype=np.float32))).to(dev)
+        moved = [su["pose"](f, bump).contiguous() for f in range(n_frames)]
 
     def one_step(it, keep=True):
         if K == 1:
             f = (it * world + rank) % n_frames
-            loss = st.step(cams[f], posed_t[f], gts[f])
+            loss = st.step(cams[f], posed_t[f], gts[f]) if moved is None else st.step(cams[f], moved[f], gts[f], verts_orig=posed_t[f])
         else:
             fs = [((it * world + rank) * K + k) % n_frames for k in range(K)]
             loss = st.step([cams[f] for f in fs], [posed_t[f] for f in fs], [gts[f] for f in fs])[0]   # (first lane's loss)
@@ -232,7 +330,9 @@ def main_fateavatar(a, rank, world, dev):
                           "value": round(a.steps / dt, 1), "frames_per_s": round(world * K * a.steps / dt, 1), "n_gpus": world,
                           "views_per_step": K, "launch_chain": bool(a.chain) if K > 1 else None,
                           "ms_per_step": round(dt / a.steps * 1e3, 4), "P": a.P, "res": a.res, "frames": n_frames, "sh_degree": 0,
-                          "graph": not a.no_graph, "overflows": st.overflows,
+                          "graph": not a.no_graph, "overflows": st.overflows, "vertex_grad": bool(st.vertex_grad) if K == 1 else False,
+                          "mesh_terms": list(mesh_terms) if mesh_terms else None,
+                          "mesh_loss": [float(x) for x in st.mesh_loss] if mesh_terms else None,
                           "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
