@@ -25,6 +25,7 @@ FR_FLAG_ACCUMULATE_SHIFT = 8   # fr_backward: bit (8 + k) = add into the k-th ar
 FR_BIND_SHELL = 0              # fr_binding::mode: FateAvatar's barycentric point + shell offset (a zeroed descriptor)
 FR_BIND_FACE_LOCAL = 1         # GaussianAvatars': a free position in the face's local frame (fr_binding::local_xyz)
 FR_BIND_PHONG = 2              # SplattingAvatar's: a point of the posed mesh's Phong surface (uvd travels in local_xyz)
+FR_BIND_DEFORM = 4             # FlashAvatar's: barycentric point + the MLP's ten outputs (deform [N,10] travels in local_xyz); 3 is unassigned
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -97,6 +98,10 @@ class fr_image_loss_config(C.Structure):
     _fields_ = [("rgb_weight", C.c_float), ("dssim_weight", C.c_float)]
 
 
+class fr_huber_config(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("mask_weight", C.c_float)]
+
+
 class fr_inputs(C.Structure):
     _fields_ = [(n, _fp) for n in ("background", "means3D", "shs", "colors_precomp", "opacities", "scales",
                                    "rotations", "cov3D_precomp", "viewmatrix", "projmatrix", "campos")]
@@ -114,8 +119,8 @@ class fr_counts(C.Structure):
 
 EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile_enable", "fr_profile_read", "fr_geometry_bytes", "fr_image_bytes",
            "fr_binning_bytes", "fr_planes_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
-           "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_mesh_terms_workspace_bytes", "fr_mesh_terms", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
-           "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_phong_frame", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward"]
+           "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_huber_workspace_bytes", "fr_huber_loss_grad", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_mesh_terms_workspace_bytes", "fr_mesh_terms", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
+           "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_bind_backward_deform", "fr_phong_frame", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward"]
 
 
 def build(force: bool = False) -> str:
@@ -205,6 +210,8 @@ def lib():
     L.fr_bind_backward_local.restype = C.c_int
     L.fr_bind_backward_phong.argtypes = [C.POINTER(fr_binding), _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
     L.fr_bind_backward_phong.restype = C.c_int
+    L.fr_bind_backward_deform.argtypes = [C.POINTER(fr_binding), _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
+    L.fr_bind_backward_deform.restype = C.c_int
     L.fr_phong_frame.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
     L.fr_phong_frame.restype = C.c_int
     # (the stream is the FIRST argument of these two: `launch_first`)
@@ -231,6 +238,11 @@ def lib():
     L.fr_l1_loss_grad.restype = C.c_int
     L.fr_l1_loss_grad_batch.argtypes = [C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fr_l1_loss_grad_batch.restype = C.c_int
+    L.fr_huber_workspace_bytes.argtypes = []
+    L.fr_huber_workspace_bytes.restype = C.c_size_t
+    L.fr_huber_loss_grad.argtypes = [C.POINTER(fr_huber_config), C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, C.c_void_p,
+                                     C.c_void_p]
+    L.fr_huber_loss_grad.restype = C.c_int
     L.fr_regularise_workspace_bytes.argtypes = []
     L.fr_regularise_workspace_bytes.restype = C.c_size_t
     L.fr_gaussian_regularise.argtypes = [C.POINTER(fr_regularise_config), C.c_int32, _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p]

@@ -26,6 +26,13 @@ quaternions, face area ratios: ONE kernel without atomics where the reference ru
 torch.inverse, matrix_to_quaternion and six index_add calls).  Differentiable w.r.t. uvd, rotation and scaling; the mode has no
 gradient to the posed vertices.
 
+`bind_gaussians_deform` is FlashAvatar's binding (model/baseline/flashavatar.py:242-276): the barycentric point moved, turned and
+stretched by the ten outputs of a deformation MLP, with t = tanh(deform),
+    gaussian._scaling  = _scaling * exp(t[:, 7:10])                                        (:272: the raw log-scale is multiplied)
+    gaussian._rotation = quatProduct_batch(_rotation, (exp(t[:, 3]), t[:, 4:7]))           (:273, :380-390: no sign standardisation)
+    gaussian._xyz      = sum_k bary_k verts[face[k]] + t[:, 0:3]                           (:262-267, :274)
+The MLP stays the caller's stock PyTorch; the op is differentiable w.r.t. verts, deform, rotation and scaling.
+
 `mesh_laplacian` is the once-per-mesh side of FateAvatar's Laplacian-smoothing term (train/loss.py:112-121,166-180): pytorch3d's
 `Meshes.laplacian_packed()` as a CSR adjacency for `loss.mesh_terms_and_grad` / `loss.laplacian_smoothing_loss`.
 """
@@ -202,7 +209,7 @@ class BindMode(NamedTuple):
     op: str               # the public stand-alone op (error messages)
     own: str              # the mode's own per-Gaussian parameter: as the op names it, ...
     attr: str             # ... the holder attribute that carries it, ...
-    own_cols: int         # ... its shape: [N,3], or with 1 anything of N elements ([N,1]), ...
+    own_cols: int         # ... its shape: [N,own_cols], or with 1 anything of N elements ([N,1]), ...
     field: str            # ... the fr_binding member it travels in ...
     grad: str             # ... and the fr_aux member its gradient is written through
     backward: str         # the stand-alone backward's entry point
@@ -215,7 +222,7 @@ class BindMode(NamedTuple):
 
     def grad_shape(self, N):
         """The shape the kernel writes the own parameter's gradient in."""
-        return (N, 3) if self.own_cols == 3 else (N,)
+        return (N,) if self.own_cols == 1 else (N, self.own_cols)
 
 
 SHELL = BindMode(_lib.FR_BIND_SHELL, "bind_gaussians", "offset", "_offset", 1, "offset", "d_offset", "fr_bind_backward",
@@ -233,6 +240,11 @@ PHONG = BindMode(_lib.FR_BIND_PHONG, "bind_gaussians_phong", "uvd", "_uvd", 3, "
                  shapes="verts [V,3], face_index [N], bary [N,3], uvd [N,3], rotation [N,4], scaling [N,3]",
                  frame_shapes="verts [V,3], _uvd [N,3], rotation [N,4], scaling [N,3], bary [N,3]",
                  holder="a Phong-surface binding (PhongBinding) needs a holder with the parameters `_uvd` [N,3]")
+DEFORM = BindMode(_lib.FR_BIND_DEFORM, "bind_gaussians_deform", "deform", "_deform", 10, "local_xyz", "d_local_xyz",
+                  "fr_bind_backward_deform", reads_bary=True, verts_grad=True, active_sh=False,
+                  shapes="verts [V,3], face_index [N], bary [N,3], deform [N,10], rotation [N,4], scaling [N,3]",
+                  frame_shapes="verts [V,3], _deform [N,10], rotation [N,4], scaling [N,3], bary [N,3]",
+                  holder="an MLP-deformed binding (DeformBinding) needs a holder with this frame's MLP outputs `_deform` [N,10]")
 
 
 def _describe(mode, verts, faces, face_index, own, rotation, scaling, bary=None, canon=None, shell_len=0.0, resize_scale=False,
@@ -260,7 +272,7 @@ def _check_shapes(who, text, mode, verts, faces, face_index, own, rotation, scal
                   resize_scale=False, frame=None):
     """`_describe`'s arguments behind the name of the caller and its shape error (`BindMode.shapes` / `.frame_shapes`)."""
     N = face_index.shape[0]
-    own_ok = own.shape == (N, 3) if mode.own_cols == 3 else own.numel() == N
+    own_ok = own.numel() == N if mode.own_cols == 1 else own.shape == (N, mode.own_cols)
     if verts.dim() != 2 or not own_ok or rotation.shape != (N, 4) or scaling.shape != (N, 3) or \
             (mode.reads_bary and bary.shape != (N, 3)):
         raise RuntimeError(f"{who}: {text}")
@@ -359,3 +371,11 @@ def bind_gaussians_phong(verts, faces, face_index, bary_coords, frame, uvd, rota
     gaussian._rotation / gaussian._scaling before render().  Only the third column of uvd is read; the first two columns of its
     gradient are zeros (the reference's forward likewise: they only steer its CPU triangle walk)."""
     return _bind(PHONG, verts, uvd, rotation, scaling, faces, face_index, bary_coords, frame=frame)
+
+
+def bind_gaussians_deform(verts, faces, face_index, bary_coords, deform, rotation, scaling):
+    """One frame of model/baseline/flashavatar.py:242-276.  verts [V,3] (posed), faces [F,3], face_index [N], bary_coords [N,3],
+    deform [N,10] (the RAW outputs of the deformation MLP for this frame: tanh is applied here), raw rotation [N,4] /
+    scaling [N,3].  Returns (xyz [N,3], rotation [N,4], scaling [N,3]): the values the reference assigns to gaussian._xyz /
+    gaussian._rotation / gaussian._scaling before render().  Differentiable w.r.t. verts, deform, rotation and scaling."""
+    return _bind(DEFORM, verts, deform, rotation, scaling, faces, face_index, bary_coords)

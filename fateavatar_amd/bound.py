@@ -16,6 +16,9 @@ The same holds for GaussianAvatars' face-local binding (model/baseline/gaussiana
 And for SplattingAvatar's Phong-surface binding (model/baseline/splattingavatar.py:203-246, `binding.bind_gaussians_phong`):
 hand it a `PhongBinding`.  That mode's per-frame mesh pass (`binding.phong_frame`, one launch per view) runs in front of
 the launch chain; the per-Gaussian part is folded like the other two.
+
+And for FlashAvatar's MLP-deformed binding (model/baseline/flashavatar.py:242-276, `binding.bind_gaussians_deform`): hand it a
+`DeformBinding`; the holders carry the MLP's outputs for their view as `_deform` [N,10].
 """
 from __future__ import annotations
 
@@ -24,7 +27,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from .binding import (FACE_LOCAL, PHONG, SHELL, PhongCanonical, _check_shapes, _chk, _chk_phong_frame, _describe, _grad_buffer,
+from .binding import (DEFORM, FACE_LOCAL, PHONG, SHELL, PhongCanonical, _check_shapes, _chk, _chk_phong_frame, _describe, _grad_buffer,
                       _no_vertex_gradient, phong_frame)
 from .rasterizer import (_GRAD_NAMES, _any_grad, _backward_args, _forward_args, _forward_batch, _FrameGrads, _per_view_outputs,
                          _pick_forward_only, _SavedFrame, rasterize_gaussians_backward_batch)
@@ -110,10 +113,28 @@ class PhongBinding(NamedTuple):
         return mbs, [v.detach() for v in posed_verts]
 
 
+class DeformBinding(NamedTuple):
+    """FlashAvatar's binding (model/baseline/flashavatar.py:159-164, :262-274): the mesh topology and every Gaussian's face and
+    barycentrics.  The ten outputs of the deformation MLP are per frame: the holder's `_deform` [N,10], not part of this."""
+    faces: torch.Tensor                   # [F,3] int32
+    face_index: torch.Tensor              # [N]   int32
+    bary_coords: torch.Tensor             # [N,3]
+
+    mode = DEFORM
+
+    def describe_args(self):
+        return (self.bary_coords,)
+
+    def per_view(self, posed_verts):
+        mb = DeformBinding(_chk(self.faces, torch.int32, "faces"), _chk(self.face_index, torch.int32, "face_index"),
+                           _chk(self.bary_coords, torch.float32, "bary_coords"))
+        return [mb] * len(posed_verts), posed_verts
+
+
 class _RasterizeBoundBatch(torch.autograd.Function):
     """Tensor arguments per view: (verts, own, rotation, scaling, means2D, sh, opacities) — the RAW parameters, as render()
     hands them over with `fused_activations`; `own` is the binding's own per-Gaussian parameter (offset [N,1], the local
-    position [N,3], uvd [N,3]: `BindMode.attr` of the holder).  Outputs per view: those of `_SavedFrame`."""
+    position [N,3], uvd [N,3], the MLP's outputs [N,10]: `BindMode.attr` of the holder).  Outputs per view: those of `_SavedFrame`."""
     PER_VIEW = 7
 
     @staticmethod
@@ -203,7 +224,10 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding, bg_colors, 
     `FaceLocalBinding` (GaussianAvatars, model/baseline/gaussianavatars.py:144-171;
     stand-alone op `binding.bind_gaussians_face_local`).  The holders then carry the local position `_xyz` [N,3] where
     FateAvatar's carry `_offset`, and the frame is rendered with their `active_sh_degree` (the reference hands render() a
-    GaussianModel(sh_degree=active_sh_degree), :157) from `get_features` [N,M,3], M >= (active_sh_degree + 1)^2."""
+    GaussianModel(sh_degree=active_sh_degree), :157) from `get_features` [N,M,3], M >= (active_sh_degree + 1)^2.
+    Or a `DeformBinding` (FlashAvatar, model/baseline/flashavatar.py:242-276; stand-alone op `binding.bind_gaussians_deform`): the
+    holders carry `_deform` [N,10], the RAW outputs of the caller's deformation MLP for THEIR view (every view has its own
+    expression, so one holder per view), which takes a gradient like a parameter; the posed vertices get one too."""
     K = len(viewpoint_cameras)
     if not 1 <= K <= _lib.FR_MAX_BATCH:
         raise RuntimeError(f"render_bound_batch: 1 .. {_lib.FR_MAX_BATCH} views")

@@ -26,9 +26,13 @@ int fail_msg(int code, const char* msg)
 static int check_binding(const fr_binding* b)
 {
     if (!b || b->N < 0 || b->V < 0 || b->F < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: null or negative sizes");
-    if (b->mode != FR_BIND_SHELL && b->mode != FR_BIND_FACE_LOCAL && b->mode != FR_BIND_PHONG)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: unknown mode (FR_BIND_SHELL, FR_BIND_FACE_LOCAL or FR_BIND_PHONG)");
+    if (b->mode != FR_BIND_SHELL && b->mode != FR_BIND_FACE_LOCAL && b->mode != FR_BIND_PHONG && b->mode != FR_BIND_DEFORM)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT,
+                        "fr_binding: unknown mode (FR_BIND_SHELL, FR_BIND_FACE_LOCAL, FR_BIND_PHONG or FR_BIND_DEFORM)");
     if (b->N == 0) return FR_OK;
+    if (b->mode == FR_BIND_DEFORM && (!b->face_index || !b->bary || !b->local_xyz || !b->rotation || !b->scaling))
+        return fail_msg(FR_ERR_INVALID_ARGUMENT,
+                        "fr_binding: FR_BIND_DEFORM needs face_index, bary, deform [N,10] (in local_xyz), rotation and scaling");
     if (!b->verts || !b->faces || !b->face_index || !b->rotation || !b->scaling)
         return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: missing array");
     if (b->mode == FR_BIND_FACE_LOCAL) {
@@ -38,6 +42,8 @@ static int check_binding(const fr_binding* b)
         if (!b->bary || !p->vert_normals || !p->vert_quats || !p->face_ratio || !b->local_xyz)
             return fail_msg(FR_ERR_INVALID_ARGUMENT,
                             "fr_binding: FR_BIND_PHONG needs bary, vert_normals, vert_quats, face_ratio and uvd (in local_xyz)");
+    } else if (b->mode == FR_BIND_DEFORM) {
+        // (its own arrays were checked above; offset, face_scale_canonical, shell_len and resize_scale are not read)
     } else if (!b->bary || !b->offset || (b->resize_scale && !b->face_scale_canonical))
         return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_binding: missing array");
     return FR_OK;
@@ -435,7 +441,7 @@ int fr_bind_backward(const fr_binding* b, const float* g_xyz, const float* g_rot
     if (rc) return rc;
     if (b->mode != FR_BIND_SHELL)
         return fail_msg(FR_ERR_INVALID_ARGUMENT,
-                        "fr_bind_backward: the binding is not FR_BIND_SHELL (fr_bind_backward_local / fr_bind_backward_phong)");
+                        "fr_bind_backward: the binding is not FR_BIND_SHELL (fr_bind_backward_local / _phong / _deform)");
     return launch_bind_backward(*b, g_xyz, g_rotation, g_scaling, d_verts, d_offset, d_rotation, d_scaling, nullptr,
                                 static_cast<hipStream_t>(stream));
 }
@@ -458,6 +464,16 @@ int fr_bind_backward_phong(const fr_binding* b, const float* g_xyz, const float*
     if (b->mode != FR_BIND_PHONG) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_bind_backward_phong: the binding is not FR_BIND_PHONG");
     if (d_verts) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_bind_backward_phong: a FR_BIND_PHONG binding has no vertex gradient");
     return launch_bind_backward(*b, g_xyz, g_rotation, g_scaling, nullptr, nullptr, d_rotation, d_scaling, d_uvd,
+                                static_cast<hipStream_t>(stream));
+}
+
+int fr_bind_backward_deform(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
+                            float* d_verts, float* d_deform, float* d_rotation, float* d_scaling, void* stream)
+{
+    int rc = check_binding(b);
+    if (rc) return rc;
+    if (b->mode != FR_BIND_DEFORM) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_bind_backward_deform: the binding is not FR_BIND_DEFORM");
+    return launch_bind_backward(*b, g_xyz, g_rotation, g_scaling, d_verts, nullptr, d_rotation, d_scaling, d_deform,
                                 static_cast<hipStream_t>(stream));
 }
 
@@ -563,6 +579,21 @@ int fr_l1_loss_grad_batch(int32_t n_images, uint64_t n, const float* const* img,
             if (workspace[j] == workspace[k]) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_l1_loss_grad_batch: one workspace per image");
     }
     return launch_l1_loss_grad_batch(n_images, n, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
+}
+
+size_t fr_huber_workspace_bytes(void) { return huber_workspace_bytes(); }
+
+int fr_huber_loss_grad(const fr_huber_config* cfg, int32_t C, int32_t H, int32_t W, const float* img, const float* gt,
+                       const float* mask, float* grad, float* loss, void* workspace, void* stream)
+{
+    if (!cfg || !img || !gt || !loss || !workspace)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_huber_loss_grad: null configuration, img, gt, loss or workspace");
+    if (!(cfg->alpha > 0.f)) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_huber_loss_grad: alpha must be > 0");
+    if (C < 0 || H < 0 || W < 0 || (int64_t)H * W >= (1ll << 31))
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_huber_loss_grad: C, H, W >= 0, H x W < 2^31");
+    if ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(grad)) & 15)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_huber_loss_grad: img, gt and grad must be 16-byte aligned");
+    return launch_huber_loss_grad(*cfg, C, H, W, img, gt, mask, grad, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
 void fr_ssim_window(float out[11])

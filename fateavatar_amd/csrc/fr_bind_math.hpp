@@ -7,14 +7,17 @@
 // matrix_to_quaternion / quaternion_multiply / standardize_quaternion.  Every translation unit that includes this is
 // built with -ffp-contract=off: the expressions are in the oracle's operation order.
 //
-// Three bindings share the quaternion code (BindArgs::mode, the same for every Gaussian of a launch):
+// Four bindings share the quaternion code (BindArgs::mode, the same for every Gaussian of a launch):
 //   FR_BIND_SHELL       FateAvatar's own: barycentric point + shell offset along the face normal (bind_one_fwd / _bwd)
 //   FR_BIND_FACE_LOCAL  GaussianAvatars': a free position in the face's local frame (bind_local_fwd / _bwd;
 //                       model/baseline/gaussianavatars.py:144-171)
 //   FR_BIND_PHONG       SplattingAvatar's: a point of the posed mesh's Phong surface (bind_phong_fwd / _bwd;
 //                       model/baseline/splattingavatar.py:224-246) from the per-vertex normals / quaternions and per-face
 //                       area ratios that phong_vertex / phong_face_ratio (below; fr_phong_frame) compute once per frame
-// bind_fwd / bind_bwd pick by the mode; the kernels call those (and bind_bwd_zero for a Gaussian without a gradient).
+//   FR_BIND_DEFORM      FlashAvatar's: barycentric point + the ten outputs of the caller's deformation MLP for this frame
+//                       (bind_deform_fwd / _bwd; model/baseline/flashavatar.py:242-276, :380-390): no face frame at all
+// bind_fwd / bind_bwd pick by the mode; the kernels call those (and bind_bwd_zero for a Gaussian without a gradient, which
+// learns the width of the mode's own gradient row from bind_own_cols).
 #pragma once
 #include "fr_common.hpp"
 
@@ -32,9 +35,10 @@ struct BindArgs {
     const float* offset;      // [N]
     const float* rotation;    // [N,4]
     const float* scaling;     // [N,3]
-    int mode;                 // FR_BIND_SHELL / FR_BIND_FACE_LOCAL / FR_BIND_PHONG (wave-uniform: a kernel argument)
+    int mode;                 // FR_BIND_SHELL / _FACE_LOCAL / _PHONG / _DEFORM (wave-uniform: a kernel argument)
     const float* local_xyz;   // [N,3] FR_BIND_FACE_LOCAL: position in the face's frame (bary .. offset are not read);
-                              //       FR_BIND_PHONG: uvd (only column 2, the offset along the normal, is read)
+                              //       FR_BIND_PHONG: uvd (only column 2, the offset along the normal, is read);
+                              // [N,10] FR_BIND_DEFORM: the RAW outputs of the deformation MLP (canon .. offset are not read)
     const float* vert_normals;  // [V,3] FR_BIND_PHONG (fr_binding_phong's tail): fr_phong_frame's outputs for the posed mesh
     const float* vert_quats;    // [V,4]
     const float* face_ratio;    // [F]
@@ -125,24 +129,21 @@ __device__ __forceinline__ QuatSel frame_to_quaternion(Vec3 a0, Vec3 a1, Vec3 a2
 }
 __device__ __forceinline__ QuatSel frame_to_quaternion(const FaceFrame& f) { return frame_to_quaternion(f.a0, f.a1, f.a2); }
 
-// pytorch3d quaternion_multiply: Hamilton product a (x) b with the real part made non-negative
-__device__ __forceinline__ void quat_multiply(const float a[4], const float b[4], float out[4])
+// the Hamilton product a (x) b as it comes, sign kept: the sixteen products every binding's rotation is made of
+// (FlashAvatar's quatProduct_batch, model/baseline/flashavatar.py:380-390, is exactly this)
+__device__ __forceinline__ void quat_product(const float a[4], const float b[4], float o[4])
 {
     const float aw = a[0], ax = a[1], ay = a[2], az = a[3];
     const float bw = b[0], bx = b[1], by = b[2], bz = b[3];
-    const float o[4] = {aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
-                        aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw};
-    const float sg = o[0] < 0.f ? -1.f : 1.f;
-    for (int k = 0; k < 4; k++) out[k] = sg * o[k];
+    o[0] = aw * bw - ax * bx - ay * by - az * bz, o[1] = aw * bx + ax * bw + ay * bz - az * by;
+    o[2] = aw * by - ax * bz + ay * bw + az * bx, o[3] = aw * bz + ax * by - ay * bx + az * bw;
 }
-// its gradient: dL/d(out) in, dL/da and dL/db out
-__device__ __forceinline__ void quat_multiply_bwd(const float a[4], const float b[4], const float g_out[4], float da[4], float db[4])
+// its gradient: dL/d(o) in, dL/da and dL/db out
+__device__ __forceinline__ void quat_product_bwd(const float a[4], const float b[4], const float g[4], float da[4], float db[4])
 {
     const float aw = a[0], ax = a[1], ay = a[2], az = a[3];
     const float bw = b[0], bx = b[1], by = b[2], bz = b[3];
-    const float ow = aw * bw - ax * bx - ay * by - az * bz;
-    const float sg = ow < 0.f ? -1.f : 1.f;
-    const float gw = sg * g_out[0], gx = sg * g_out[1], gy = sg * g_out[2], gz = sg * g_out[3];
+    const float gw = g[0], gx = g[1], gy = g[2], gz = g[3];
     db[0] = gw * aw + gx * ax + gy * ay + gz * az;
     db[1] = -gw * ax + gx * aw + gy * az - gz * ay;
     db[2] = -gw * ay - gx * az + gy * aw + gz * ax;
@@ -151,6 +152,23 @@ __device__ __forceinline__ void quat_multiply_bwd(const float a[4], const float 
     da[1] = -gw * bx + gx * bw - gy * bz + gz * by;
     da[2] = -gw * by + gx * bz + gy * bw - gz * bx;
     da[3] = -gw * bz - gx * by + gy * bx + gz * bw;
+}
+// pytorch3d quaternion_multiply: the product with the real part made non-negative
+__device__ __forceinline__ void quat_multiply(const float a[4], const float b[4], float out[4])
+{
+    float o[4];
+    quat_product(a, b, o);
+    const float sg = o[0] < 0.f ? -1.f : 1.f;
+    for (int k = 0; k < 4; k++) out[k] = sg * o[k];
+}
+// its gradient: dL/d(out) in, dL/da and dL/db out
+__device__ __forceinline__ void quat_multiply_bwd(const float a[4], const float b[4], const float g_out[4], float da[4], float db[4])
+{
+    float o[4];
+    quat_product(a, b, o);   // (for the sign of its real part)
+    const float sg = o[0] < 0.f ? -1.f : 1.f;
+    const float g[4] = {sg * g_out[0], sg * g_out[1], sg * g_out[2], sg * g_out[3]};
+    quat_product_bwd(a, b, g, da, db);
 }
 
 // gradient of the face quaternion (frame_to_quaternion's q) on to the frame's axes: through standardize, the selected
@@ -256,15 +274,21 @@ struct BindGrads {
     float* d_offset;    // [N]   written
     float* d_rotation;  // [N,4] written
     float* d_scaling;   // [N,3] written
-    float* d_local_xyz; // [N,3] written (FR_BIND_FACE_LOCAL; d_offset is the shell mode's)
+    float* d_local_xyz; // [N,3] written (FR_BIND_FACE_LOCAL, FR_BIND_PHONG; d_offset is the shell mode's); [N,10] FR_BIND_DEFORM
 };
 
+constexpr int kDeformCols = 10;   // FR_BIND_DEFORM: position 3, rotation 4 (log of the real part first), log-scale factor 3
+// floats per row of the mode's own parameter in BindArgs::local_xyz, and of its gradient in BindGrads::d_local_xyz
+__device__ __forceinline__ int bind_own_cols(int mode) { return mode == FR_BIND_DEFORM ? kDeformCols : 3; }
+
 // a Gaussian without any gradient (culled by the frame): zero rows, nothing for the vertices
-__device__ __forceinline__ void bind_bwd_zero(int n, const BindGrads& o)
+__device__ __forceinline__ void bind_bwd_zero(const BindArgs& a, int n, const BindGrads& o)
 {
     if (o.d_offset) o.d_offset[n] = 0.f;
-    if (o.d_local_xyz)
-        for (int k = 0; k < 3; k++) o.d_local_xyz[3 * n + k] = 0.f;
+    if (o.d_local_xyz) {
+        const int cols = bind_own_cols(a.mode);
+        for (int k = 0; k < cols; k++) o.d_local_xyz[(size_t)cols * n + k] = 0.f;
+    }
     if (o.d_rotation)
         for (int k = 0; k < 4; k++) o.d_rotation[4 * n + k] = 0.f;
     if (o.d_scaling)
@@ -566,11 +590,66 @@ __device__ __forceinline__ void bind_phong_bwd(const BindArgs& a, int n, const f
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// FR_BIND_DEFORM — FlashAvatar's binding (model/baseline/flashavatar.py:242-276): with t = tanh(deform) of the ten RAW outputs
+// of the deformation MLP for this Gaussian in this frame,
+//     xyz = sum_k b_k v_k + t[0:3];  rotation = rotation (x) (exp(t[3]), t[4], t[5], t[6]);  scaling = scaling * exp(t[7:10])
+// The product is quatProduct_batch (:380-390): the PARAMETER is the first factor and the sign is kept.  The raw log-scale is
+// MULTIPLIED (:272, kept as it is, as in the Phong mode).  Nothing is normalised here: the rasterizer does that.
+__device__ __forceinline__ void bind_deform_fwd(const BindArgs& a, int n, float xyz[3], float rot[4], float scl[3])
+{
+    const int fi = a.face_index[n];
+    const int i0 = a.faces[3 * fi], i1 = a.faces[3 * fi + 1], i2 = a.faces[3 * fi + 2];
+    const Vec3 v0 = load3(a.verts, i0), v1 = load3(a.verts, i1), v2 = load3(a.verts, i2);
+    const float b0 = a.bary[3 * n], b1 = a.bary[3 * n + 1], b2 = a.bary[3 * n + 2];
+    float t[kDeformCols];
+    for (int k = 0; k < kDeformCols; k++) t[k] = tanhf(a.local_xyz[(size_t)kDeformCols * n + k]);
+    xyz[0] = (b0 * v0.x + b1 * v1.x + b2 * v2.x) + t[0];
+    xyz[1] = (b0 * v0.y + b1 * v1.y + b2 * v2.y) + t[1];
+    xyz[2] = (b0 * v0.z + b1 * v1.z + b2 * v2.z) + t[2];
+    const float r[4] = {a.rotation[4 * n], a.rotation[4 * n + 1], a.rotation[4 * n + 2], a.rotation[4 * n + 3]};
+    const float delta[4] = {expf(t[3]), t[4], t[5], t[6]};
+    quat_product(r, delta, rot);
+    for (int k = 0; k < 3; k++) scl[k] = a.scaling[3 * n + k] * expf(t[7 + k]);
+}
+
+// gradients of deform (all ten columns) / rotation / scaling written, dL/dverts added: b_k g_xyz to the face's three corners
+__device__ __forceinline__ void bind_deform_bwd(const BindArgs& a, int n, const float g_xyz[3], const float g_rot[4],
+                                                const float g_scl[3], const BindGrads& o)
+{
+    float t[kDeformCols], gt[kDeformCols];
+    for (int k = 0; k < kDeformCols; k++) t[k] = tanhf(a.local_xyz[(size_t)kDeformCols * n + k]);
+    for (int k = 0; k < 3; k++) gt[k] = g_xyz[k];
+    const float r[4] = {a.rotation[4 * n], a.rotation[4 * n + 1], a.rotation[4 * n + 2], a.rotation[4 * n + 3]};
+    const float e3 = expf(t[3]);
+    const float delta[4] = {e3, t[4], t[5], t[6]};
+    float dr[4], dd[4];
+    quat_product_bwd(r, delta, g_rot, dr, dd);
+    if (o.d_rotation)
+        for (int k = 0; k < 4; k++) o.d_rotation[4 * n + k] = dr[k];
+    gt[3] = dd[0] * e3, gt[4] = dd[1], gt[5] = dd[2], gt[6] = dd[3];
+    for (int k = 0; k < 3; k++) {
+        const float e = expf(t[7 + k]);
+        gt[7 + k] = g_scl[k] * a.scaling[3 * n + k] * e;
+        if (o.d_scaling) o.d_scaling[3 * n + k] = g_scl[k] * e;
+    }
+    if (o.d_local_xyz)
+        for (int k = 0; k < kDeformCols; k++) o.d_local_xyz[(size_t)kDeformCols * n + k] = gt[k] * (1.0f - t[k] * t[k]);
+    if (o.d_verts) {
+        const int fi = a.face_index[n];
+        const int i0 = a.faces[3 * fi], i1 = a.faces[3 * fi + 1], i2 = a.faces[3 * fi + 2];
+        const float b0 = a.bary[3 * n], b1 = a.bary[3 * n + 1], b2 = a.bary[3 * n + 2];
+        const Vec3 gx = {g_xyz[0], g_xyz[1], g_xyz[2]}, z = {0.f, 0.f, 0.f};
+        scatter_vertex_grads(o.d_verts, i0, i1, i2, mul(gx, b0), mul(gx, b1), mul(gx, b2), z, z);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // what the kernels call: the binding of BindArgs::mode (one value per launch, so the branch is wave-uniform)
 __device__ __forceinline__ void bind_fwd(const BindArgs& a, int n, float xyz[3], float rot[4], float scl[3])
 {
     if (a.mode == FR_BIND_FACE_LOCAL) bind_local_fwd(a, n, xyz, rot, scl);
     else if (a.mode == FR_BIND_PHONG) bind_phong_fwd(a, n, xyz, rot, scl);
+    else if (a.mode == FR_BIND_DEFORM) bind_deform_fwd(a, n, xyz, rot, scl);
     else bind_one_fwd(a, n, xyz, rot, scl);
 }
 __device__ __forceinline__ void bind_bwd(const BindArgs& a, int n, const float g_xyz[3], const float g_rot[4], const float g_scl[3],
@@ -578,6 +657,7 @@ __device__ __forceinline__ void bind_bwd(const BindArgs& a, int n, const float g
 {
     if (a.mode == FR_BIND_FACE_LOCAL) bind_local_bwd(a, n, g_xyz, g_rot, g_scl, o);
     else if (a.mode == FR_BIND_PHONG) bind_phong_bwd(a, n, g_xyz, g_rot, g_scl, o);
+    else if (a.mode == FR_BIND_DEFORM) bind_deform_bwd(a, n, g_xyz, g_rot, g_scl, o);
     else bind_one_bwd(a, n, g_xyz, g_rot, g_scl, o);
 }
 

@@ -10,7 +10,8 @@
 // twins); here ONE kernel per direction, one thread per Gaussian, recomputing the ~150 flops of its face's frame
 // instead of gathering per-face temporaries.  The same two kernels serve GaussianAvatars' face-local binding
 // (fr_binding::mode == FR_BIND_FACE_LOCAL, model/baseline/gaussianavatars.py:144-171) and SplattingAvatar's Phong-surface
-// binding (FR_BIND_PHONG, model/baseline/splattingavatar.py:224-246; its per-frame mesh pass is k_phong_frame): the mode is a
+// binding (FR_BIND_PHONG, model/baseline/splattingavatar.py:224-246; its per-frame mesh pass is k_phong_frame) and FlashAvatar's
+// MLP-deformed binding (FR_BIND_DEFORM, model/baseline/flashavatar.py:242-276; no face frame): the mode is a
 // kernel argument.  The backward scatters dL/dverts with float atomics (a vertex is shared
 // by the Gaussians of ~6 faces x ~10 Gaussians each).  Built without FMA contraction, in the oracle's operation order.
 #include "fr_bind_math.hpp"

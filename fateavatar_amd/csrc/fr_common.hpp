@@ -476,6 +476,10 @@ int launch_l1_loss_grad(unsigned long long n, const float* img, const float* gt,
 // for a D-SSIM weight of 0 (fr_optim.hip, k_l1_loss_grad's sums bit for bit)
 int launch_l1_loss_grad_terms(int n_images, unsigned long long n, float rgb_weight, const float* const* img, const float* const* gt,
                               float* const* grad, float* const* loss, void* const* workspace, hipStream_t s);
+// FlashAvatar's Huber image term and its gradient (fr_optim.hip)
+size_t huber_workspace_bytes();
+int launch_huber_loss_grad(const fr_huber_config& cfg, int C, int H, int W, const float* img, const float* gt, const float* mask,
+                           float* grad, float* loss, void* workspace, hipStream_t s);
 // L1 + D-SSIM image loss and its gradient (fr_ssim.hip)
 void ssim_window(float out[11]);
 size_t image_loss_workspace_bytes(int C, int H, int W);

@@ -293,6 +293,135 @@ int launch_l1_loss_grad_terms(int n_images, unsigned long long n, float rgb_weig
     return FR_OK;
 }
 
+// ---------------------------------------------------------------- Huber image term and its gradient, one launch
+// reference: FlashAvatarLoss.get_huber_loss (train/loss.py:217-221) on the image and, with a mouth mask, once more on the
+// masked image and target at weight 40 (:231-239), followed by loss.backward(): about thirty launch-bound elementwise /
+// reduction kernels with autograd's twins.  Here k_l1_loss_grad's scheme with TWO sums: float4 pieces plus a tail,
+// per-workgroup partials, the workgroup that finishes last adds them up in index order and puts the workspace back to zero.
+//   h(x) = 0.5 x^2 if |x| < alpha else alpha (|x| - 0.5 alpha);  h'(x) = x if |x| < alpha else alpha sign(x)
+struct HuberArgs {
+    const float* img;
+    const float* gt;
+    const float* mask;   // [HW] or null
+    float* grad;         // or null
+    float* partial;      // [2][kL1MaxBlocks]
+    unsigned* counter;
+    float* loss;         // {huber + mask_weight x mouth, huber, mouth}
+    unsigned long long n;
+    unsigned hw;
+    float alpha, mask_weight, inv_n;
+};
+
+// h and h' of one difference x: the value is added to `acc`, the derivative returned
+__device__ __forceinline__ float huber_term(float x, float alpha, float& acc)
+{
+    const float ax = fabsf(x);
+    if (ax < alpha) {
+        acc += 0.5f * x * x;
+        return x;
+    }
+    acc += alpha * (ax - 0.5f * alpha);
+    return x < 0.f ? -alpha : alpha;
+}
+
+// element e of the image: both terms' sums, and the gradient word
+__device__ __forceinline__ float huber_one(const HuberArgs& a, unsigned long long e, float d, float& acc_h, float& acc_m)
+{
+    float g = huber_term(d, a.alpha, acc_h);
+    if (a.mask) {
+        const float m = a.mask[e % a.hw];   // [1,H,W] broadcast over the channels
+        g += a.mask_weight * m * huber_term(m * d, a.alpha, acc_m);
+    }
+    return g * a.inv_n;
+}
+
+__global__ void __launch_bounds__(256) k_huber_loss_grad(HuberArgs a)
+{
+    const float* __restrict__ img = a.img;
+    const float* __restrict__ gt = a.gt;
+    float* __restrict__ grad = a.grad;
+    float* const partial = a.partial;
+    __shared__ float s_red[2][4];
+    __shared__ bool s_last;
+    const unsigned long long n = a.n, n4 = n / 4, stride = (unsigned long long)gridDim.x * blockDim.x;
+    float acc_h = 0.f, acc_m = 0.f;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const float4 x = reinterpret_cast<const float4*>(img)[i], y = reinterpret_cast<const float4*>(gt)[i];
+        const float d[4] = {x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w};
+        float g[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) g[k] = huber_one(a, 4 * i + k, d[k], acc_h, acc_m);
+        if (grad) reinterpret_cast<float4*>(grad)[i] = make_float4(g[0], g[1], g[2], g[3]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n - 4 * n4)) {   // tail of a length that is not a multiple of 4
+        const unsigned long long e = 4 * n4 + threadIdx.x;
+        const float g = huber_one(a, e, img[e] - gt[e], acc_h, acc_m);
+        if (grad) grad[e] = g;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        acc_h += __shfl_down(acc_h, off);
+        acc_m += __shfl_down(acc_m, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_red[0][threadIdx.x >> 6] = acc_h;
+        s_red[1][threadIdx.x >> 6] = acc_m;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        // write-through stores, wait for them, then count this workgroup in (as k_l1_loss_grad)
+        __hip_atomic_store(partial + blockIdx.x, (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(partial + kL1MaxBlocks + blockIdx.x, (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        s_last = last_workgroup_of(a.counter, blockIdx.x, gridDim.x);
+    }
+    __syncthreads();
+    if (!s_last) return;
+    float th = 0.f, tm = 0.f;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
+        th += __hip_atomic_load(partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        tm += __hip_atomic_load(partial + kL1MaxBlocks + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(partial + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the workspace is left zeroed
+        __hip_atomic_store(partial + kL1MaxBlocks + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        th += __shfl_down(th, off);
+        tm += __shfl_down(tm, off);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        s_red[0][threadIdx.x >> 6] = th;
+        s_red[1][threadIdx.x >> 6] = tm;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float huber = ((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3])) * a.inv_n;
+        const float mouth = ((s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3])) * a.inv_n;
+        a.loss[0] = huber + a.mask_weight * mouth, a.loss[1] = huber, a.loss[2] = mouth;
+    }
+}
+
+size_t huber_workspace_bytes() { return (kDoneGroups + 1) * kDoneStride * sizeof(unsigned) + 2 * kL1MaxBlocks * sizeof(float); }
+
+int launch_huber_loss_grad(const fr_huber_config& cfg, int C, int H, int W, const float* img, const float* gt, const float* mask,
+                           float* grad, float* loss, void* workspace, hipStream_t s)
+{
+    const unsigned long long hw = (unsigned long long)H * (unsigned long long)W, n = hw * (unsigned long long)C;
+    if (n == 0) return FR_OK;
+    unsigned long long blocks = (n / 4 + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks > kL1MaxBlocks ? kL1MaxBlocks : blocks);
+    HuberArgs a;
+    a.img = img, a.gt = gt, a.mask = mask, a.grad = grad, a.loss = loss;
+    a.counter = static_cast<unsigned*>(workspace);
+    a.partial = reinterpret_cast<float*>(a.counter + (kDoneGroups + 1) * kDoneStride);
+    a.n = n, a.hw = (unsigned)hw;
+    a.alpha = cfg.alpha, a.mask_weight = mask ? cfg.mask_weight : 0.f, a.inv_n = (float)(1.0 / (double)n);
+    hipLaunchKernelGGL(k_huber_loss_grad, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    FR_HIP(hipGetLastError());
+    return FR_OK;
+}
+
 // ---------------------------------------------------------------- several small device-to-device copies, one launch
 // The per-frame inputs of a captured step (camera block, posed vertices, target image) are copied into the buffers the
 // graph was captured with: as separate copies each is a launch-bound 5 us dispatch.

@@ -252,7 +252,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
         if (!adds(G_SCALES)) store3(a.out.dL_dscales, i, 0.f, 0.f, 0.f, false);
         if (a.out.dL_drotations && !adds(G_ROTATIONS))
             for (int k = 0; k < 4; k++) a.out.dL_drotations[4 * i + k] = 0.f;
-        if (a.bound) bind_bwd_zero(idx, a.bg);
+        if (a.bound) bind_bwd_zero(a.bind, idx, a.bg);
         return;
     }
     // (accumulating arrays: what they hold came with the other inputs — a load next to its store would sit behind the

@@ -6,7 +6,8 @@ and the gradient autograd would hand to the rasterizer (`sign(img - gt) / n`, fo
 launch of the HIP library (`fr_l1_loss_grad`, include/fr_rasterizer.h); the caller continues with
 `render.backward(grad)`.  `image_loss_and_grad` is the same for the weighted L1 + D-SSIM objective of GaussianAvatars and
 3DGS (train/loss.py:351-365, tools/loss_utils/dssim.py:28-56) in two launches (`fr_image_loss_grad`), and `d_ssim` the
-reference's function as an autograd op on those kernels.  There is no CPU path."""
+reference's function as an autograd op on those kernels.  `huber_loss_and_grad` is FlashAvatar's Huber term with its optional
+mouth-mask term (train/loss.py:217-221, :231-239) in one launch (`fr_huber_loss_grad`).  There is no CPU path."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional, Tuple
@@ -87,6 +88,79 @@ def l1_loss_and_grad_batch(imgs, gts, loss_outs, grad_outs, workspaces):
     arr = lambda ts: (C.c_void_p * K)(*[t.data_ptr() for t in ts])  # noqa: E731
     _lib.launch("fr_l1_loss_grad_batch", dev, K, n, arr(imgs), arr(gts), arr(grad_outs), arr(loss_outs), arr(workspaces))
     return loss_outs, grad_outs
+
+
+# ---- FlashAvatar's Huber image term (FlashAvatarLoss, train/loss.py:217-221, :231-239): ONE launch (`fr_huber_loss_grad`) gives the
+# three loss words and the gradient autograd would hand to the rasterizer
+class HuberLoss(NamedTuple):
+    """The Huber term's threshold and the weight of its mouth-mask term: the reference has 0.1 and 40 (train/loss.py:231-239)."""
+    alpha: float = 0.1
+    mask_weight: float = 40.0
+
+
+REFERENCE_HUBER_LOSS = HuberLoss(0.1, 40.0)
+
+_huber_workspace = {}   # (device index, stream handle) -> zeroed scratch of fr_huber_loss_grad (as _workspace above)
+
+
+def huber_workspace(dev: torch.device) -> torch.Tensor:
+    """A fresh zeroed workspace for `huber_loss_and_grad(..., workspace=)`."""
+    return torch.zeros((_lib.lib().fr_huber_workspace_bytes(),), dtype=torch.uint8, device=dev)
+
+
+def huber_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, terms=REFERENCE_HUBER_LOSS, mask: Optional[torch.Tensor] = None,
+                        loss_out: Optional[torch.Tensor] = None, grad_out: Optional[torch.Tensor] = None,
+                        workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """FlashAvatar's image term of `img` against `gt` ([C,H,W] or [1,C,H,W]) in ONE launch: returns the 3-element device tensor
+    (huber + terms.mask_weight * mouth, huber, mouth) and the gradient of its first word with respect to `img`, of `img`'s
+    shape.  huber = mean h(img - gt) with h(x) = 0.5 x^2 below |x| = terms.alpha and alpha (|x| - alpha / 2) from there on;
+    mouth = mean h(mask * (img - gt)) for a `mask` [1,H,W] or [H,W] with values in [0,1], broadcast over the channels (None: no
+    mouth term, the word is 0).  `loss_out` / `grad_out`: write into these tensors instead of fresh ones (buffers of a captured
+    step).  `workspace`: scratch from `huber_workspace()`; by default one is kept per (device, current stream) — launches that
+    may overlap must not share one.  The losses without the gradient: `grad_out=False`.  There is no CPU path."""
+    if not (img.is_cuda and gt.is_cuda):
+        raise RuntimeError("huber_loss_and_grad needs device tensors (there is no CPU path)")
+    if img.shape != gt.shape:
+        raise RuntimeError(f"huber_loss_and_grad: shapes differ: {tuple(img.shape)} vs {tuple(gt.shape)}")
+    Cn, H, W = _chw(img, "huber_loss_and_grad")
+    alpha, mask_weight = float(terms[0]), float(terms[1])
+    if not alpha > 0.0:
+        raise ValueError("huber_loss_and_grad: alpha must be > 0")
+    img = img.detach()
+    if img.dtype != torch.float32 or not img.is_contiguous():
+        img = img.float().contiguous()
+    if gt.dtype != torch.float32 or not gt.is_contiguous():
+        gt = gt.float().contiguous()
+    dev = img.device
+    if mask is not None:
+        if not mask.is_cuda or mask.device != dev or mask.numel() != H * W or tuple(mask.shape[-2:]) != (H, W):
+            raise RuntimeError(f"huber_loss_and_grad: the mask is [1,{H},{W}] or [{H},{W}] on the image's device")
+        mask = mask.detach()
+        if mask.dtype != torch.float32 or not mask.is_contiguous():
+            mask = mask.float().contiguous()
+    grad = None if grad_out is False else (grad_out if grad_out is not None else torch.empty_like(img))
+    loss = loss_out if loss_out is not None else torch.empty((3,), dtype=torch.float32, device=dev)
+    if (grad is not None and (grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != dev)) \
+            or loss.numel() != 3 or loss.dtype != torch.float32 or loss.device != dev or not loss.is_contiguous():
+        raise RuntimeError("huber_loss_and_grad: bad output buffers (gradient of the image's shape, 3-element loss, float32, contiguous)")
+    L = _lib.lib()
+    ws = workspace
+    if ws is None:
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        ws = _huber_workspace.get(key)
+        if ws is None:
+            if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
+                raise RuntimeError("huber_loss_and_grad: first call on this stream happens inside a graph capture; call it once "
+                                   "eagerly on the stream first, or pass workspace=huber_workspace(device)")
+            ws = _huber_workspace[key] = huber_workspace(dev)
+    elif not (ws.is_cuda and ws.device == dev and ws.dtype == torch.uint8 and ws.numel() >= L.fr_huber_workspace_bytes()):
+        raise RuntimeError("huber_loss_and_grad: workspace must come from huber_workspace() on the image's device")
+    import ctypes as C
+    cfg = _lib.fr_huber_config(alpha, mask_weight)
+    _lib.launch("fr_huber_loss_grad", dev, C.byref(cfg), Cn, H, W, img.data_ptr(), gt.data_ptr(),
+                mask.data_ptr() if mask is not None else None, grad.data_ptr() if grad is not None else None, loss.data_ptr(),
+                ws.data_ptr())
+    return loss, grad
 
 
 _reg_workspace = {}   # (device index, stream handle) -> zeroed scratch of fr_gaussian_regularise (as _workspace above)

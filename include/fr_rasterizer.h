@@ -104,7 +104,9 @@ typedef struct fr_aux {
      * caller zeroes it).  FR_FLAG_ACCUMULATE does not apply to these four.
      * A descriptor with mode FR_BIND_FACE_LOCAL (model/baseline/gaussianavatars.py:144-171) goes the same way; its backward
      * writes d_local_xyz [P,3] (below) where the shell binding writes d_offset.  So does one with mode FR_BIND_PHONG
-     * (model/baseline/splattingavatar.py:224-246): d_local_xyz receives d_uvd, and d_verts must be NULL. */
+     * (model/baseline/splattingavatar.py:224-246): d_local_xyz receives d_uvd, and d_verts must be NULL.  And one with mode
+     * FR_BIND_DEFORM (model/baseline/flashavatar.py:242-276): d_local_xyz receives d_deform, TEN floats per row, and d_verts
+     * takes b_k g_xyz at the face's three corners. */
     const fr_binding* binding;
     float* d_verts;
     float* d_offset;
@@ -117,7 +119,8 @@ typedef struct fr_aux {
      * every backward call: frames that feed one optimizer step need ONE WORD EACH (fr_adam_config::skip takes up to
      * FR_ADAM_MAX_GRADS of them); the views of one fr_backward_batch call must not share a word. */
     float* overflow_out;
-    /* fr_backward / fr_backward_batch out [P,3]: a binding with mode FR_BIND_FACE_LOCAL or FR_BIND_PHONG (d_uvd) only, where it takes d_offset's
+    /* fr_backward / fr_backward_batch out [P,3]: a binding with mode FR_BIND_FACE_LOCAL or FR_BIND_PHONG (d_uvd), or out [P,10]:
+     * one with mode FR_BIND_DEFORM (d_deform) — only those three modes —, where it takes d_offset's
      * place (every row written, zeros for culled Gaussians; d_offset is then not touched).  It sits behind the binding's
      * other members: the members in front of it keep their offsets, the plane members below stay the struct's last. */
     float* d_local_xyz;
@@ -375,6 +378,26 @@ int fr_image_loss_grad(const fr_image_loss_config* cfg, int32_t n_images, int32_
                        const float* const* img, const float* const* gt, float* const* grad, float* const* loss,
                        void* const* workspace, void* hip_stream);
 
+/* ---- FlashAvatar's Huber image term and its gradient with respect to the rendered image in ONE launch (reference:
+ * FlashAvatarLoss.get_huber_loss and accumulate_gradients, train/loss.py:217-221, :231-239, with alpha 0.1 and the mouth term's
+ * weight 40).  With d = img - gt over the n = C H W floats of an image and
+ *   h(x) = 0.5 x^2 if |x| < alpha else alpha (|x| - 0.5 alpha),     h'(x) = x if |x| < alpha else alpha sign(x)
+ * and `mask` [H*W] (any values in [0,1]; broadcast over the C channels; NULL: no mouth term):
+ *   loss[1] = mean_n h(d),   loss[2] = mean_n h(mask * d)  (0 without a mask),   loss[0] = loss[1] + mask_weight * loss[2]
+ *   grad    = (h'(d) + mask_weight * mask * h'(mask * d)) / n          (`grad` may be NULL: losses only)
+ * h is C1, so nothing flips at |x| = alpha.  One launch of float4 pieces plus a tail, two per-workgroup partial sums added up in
+ * index order by the workgroup that finishes last: no float atomics, the same bits on every run.  `workspace`:
+ * fr_huber_workspace_bytes() bytes of device memory, zeroed ONCE by the caller and left zeroed by the kernel; not to be shared
+ * by launches that can overlap on the device.  No allocation, no synchronisation: the call can be captured in a graph.  img, gt
+ * and grad must be 16-byte aligned (mask need not be).  n == 0 launches nothing and leaves `loss` as it is.  A NULL cfg / img /
+ * gt / loss / workspace, or alpha <= 0, is FR_ERR_INVALID_ARGUMENT.  `loss`: three device floats. */
+typedef struct fr_huber_config {
+    float alpha, mask_weight;             /* reference: 0.1, 40 (train/loss.py:231-239) */
+} fr_huber_config;
+size_t fr_huber_workspace_bytes(void);
+int fr_huber_loss_grad(const fr_huber_config* cfg, int32_t C, int32_t H, int32_t W, const float* img, const float* gt,
+                       const float* mask, float* grad, float* loss, void* workspace, void* hip_stream);
+
 /* ---- GaussianAvatars' two per-Gaussian regularisers and their gradients in ONE launch (reference:
  * GaussianAvatarsLoss.accumulate_gradients, train/loss.py:367-379, on the raw local parameters,
  * model/baseline/gaussianavatars.py:196-197):
@@ -458,10 +481,24 @@ int fr_multi_copy(int32_t n_segments, float* const* dst, const float* const* src
  * read, and the first two columns of its gradient are written as zeros — walking a Gaussian over the mesh (the reference's
  * CPU submodule simple_phongsurf) is outside this library.  face_index, bary, rotation, scaling, local_xyz and the three
  * fr_phong_frame arrays are required; offset, face_scale_canonical, shell_len and resize_scale are ignored.  The mode has NO
- * gradient to the posed vertices: a d_verts request is FR_ERR_INVALID_ARGUMENT. */
+ * gradient to the posed vertices: a d_verts request is FR_ERR_INVALID_ARGUMENT.
+ *
+ * FR_BIND_DEFORM is FlashAvatar's (model/baseline/flashavatar.py:242-276, :380-390): the barycentric point moved, turned and
+ * stretched by the ten outputs of the caller's deformation MLP for this Gaussian in this frame.  With t = tanh(deform[n]),
+ *   xyz = sum_k b_k verts[i_k] + t[0:3]
+ *   rotation = rotation (x) (exp(t[3]), t[4], t[5], t[6])      (the Hamilton product as it comes: the PARAMETER is the first
+ *                                                               factor and the sign is NOT standardised, quatProduct_batch)
+ *   scaling = scaling * exp(t[7:10])                            (the raw log-scale is MULTIPLIED, as in FR_BIND_PHONG)
+ * The RAW deform array [N,10] travels in the `local_xyz` member, and its gradient [N,10] in the backward's d_local_xyz slot
+ * (fr_aux::d_local_xyz, fr_bind_backward_deform's d_deform): all ten columns are read and written.  face_index, bary,
+ * local_xyz, rotation and scaling are required; offset, face_scale_canonical, shell_len and resize_scale are ignored.  The
+ * mode HAS a vertex gradient: d_verts[i_k] += b_k g_xyz.
+ *
+ * The value 3 is unassigned: a descriptor that carries it is refused like any other unknown mode. */
 #define FR_BIND_SHELL 0
 #define FR_BIND_FACE_LOCAL 1
 #define FR_BIND_PHONG 2
+#define FR_BIND_DEFORM 4
 struct fr_binding {
     int32_t N, V, F;
     const float* verts;                 /* [V,3] posed vertices */
@@ -475,7 +512,8 @@ struct fr_binding {
     const float* rotation;              /* [N,4] raw quaternion (r,x,y,z) */
     const float* scaling;               /* [N,3] raw log-scale */
     int32_t mode;                       /* FR_BIND_* (appended: a descriptor that ends above, zero-filled, is a shell binding) */
-    const float* local_xyz;             /* [N,3] FR_BIND_FACE_LOCAL: position in the face's frame; FR_BIND_PHONG: uvd */
+    const float* local_xyz;             /* [N,3] FR_BIND_FACE_LOCAL: position in the face's frame; FR_BIND_PHONG: uvd;
+                                         * [N,10] FR_BIND_DEFORM: the raw outputs of the deformation MLP */
 };
 /* The descriptor of a FR_BIND_PHONG binding: fr_binding with the mode's three arrays behind it.  Wherever a `const fr_binding*`
  * is taken (fr_bind_forward, fr_bind_backward_phong, fr_aux::binding) a descriptor whose mode is FR_BIND_PHONG MUST be the
@@ -502,6 +540,11 @@ int fr_bind_backward_local(const fr_binding* b, const float* g_xyz, const float*
  * the three entry points' shape): the mode has no vertex gradient. */
 int fr_bind_backward_phong(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
                            float* d_verts, float* d_uvd, float* d_rotation, float* d_scaling, void* hip_stream);
+/* The same for a FR_BIND_DEFORM binding (any other mode is FR_ERR_INVALID_ARGUMENT): d_deform [N,10] through tanh, the
+ * quaternion product and the two exponentials, d_rotation through the product, d_scaling = g_scaling * exp(t[7:10]), and
+ * b_k g_xyz ADDED into d_verts [V,3] at the face's three corners. */
+int fr_bind_backward_deform(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
+                            float* d_verts, float* d_deform, float* d_rotation, float* d_scaling, void* hip_stream);
 /* SplattingAvatar's per-frame mesh pass (model/baseline/splattingavatar.py `forward` :203-215, `PerVertQuaternion` :819-902,
  * `calc_face_areas` :781-791, `tbn` :756-765, `calc_per_face_Rt` :795-802) for FR_BIND_PHONG, from the posed verts [V,3], the
  * canonical cano_verts [V,3], faces [F,3], the vertex -> face incidence list in CSR form (vf_offsets [V+1], vf_faces [3F],

@@ -29,6 +29,12 @@ the reference's image term, 0.8 x L1 + 0.2 x d_ssim (--image-loss RGB DSSIM for 
     python tools/train_synthetic.py --splatting --densify-from 0.3 --densify-interval 0.1 --reset-interval 0.5 --walk-interval 0.1
 SplattingAvatar's step (fateavatar_amd/splatting.py): Gaussians on the Phong surface of the posed template, SH degree 0, one
 GPU.  --torch-binding binds with the stock-PyTorch restatement (tests/phong_ref.py) in front of render(): the A/B.
+
+    python tools/train_synthetic.py --flash [--P 16384 --binding-op | --torch-binding] [--mouth-mask] [--vertex-grad]
+FlashAvatar's step (fateavatar_amd/flash.py): Gaussians at fixed barycentric points of the posed template, moved per frame by a
+small torch deformation network (positional encoding of the canonical point + a per-frame condition, six hidden layers of 256,
+ten outputs; torch.optim.Adam at 1e-4) that is trained through `step.d_deform`; Huber image term, SH degree 0, one GPU.
+--torch-binding: binding and Huber as the stock-PyTorch restatement (tests/flash_ref.py) with autograd in front of render().
 """
 import argparse
 import json
@@ -86,7 +92,13 @@ def main():
                     help="SplattingAvatar's loop: --P Gaussians sampled on the template's Phong surface (default 10 000, the "
                          "reference's num_init_samples), SH degree 0; --binding-op as for --fateavatar")
     ap.add_argument("--torch-binding", action="store_true",
-                    help="--splatting: the mesh pass and the binding in stock PyTorch (tests/phong_ref.py) in front of render()")
+                    help="--splatting: the mesh pass and the binding in stock PyTorch (tests/phong_ref.py) in front of render(); "
+                         "--flash: the binding and the Huber term in stock PyTorch (tests/flash_ref.py)")
+    ap.add_argument("--flash", action="store_true",
+                    help="FlashAvatar's loop: --P Gaussians (default 16 384, tex_size 128 squared) at fixed points of the template, "
+                         "deformed per frame by a torch MLP trained through step.d_deform; Huber loss; --binding-op as for --fateavatar")
+    ap.add_argument("--mouth-mask", action="store_true",
+                    help="--flash: every frame brings a mouth mask (the Huber term's second sum, weight 40)")
     ap.add_argument("--regularisers", action="store_true",
                     help="--rigged: the reference's scale / xyz regularisers in every step (one more launch in the graph)")
     ap.add_argument("--reg-weights", type=float, nargs=2, default=None, metavar=("SCALE", "XYZ"),
@@ -109,6 +121,12 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     a.image_loss = ImageLoss(*a.image_loss) if a.image_loss else (ImageLoss(0.8, 0.2) if a.dssim else None)
+    if a.flash:
+        if a.image_loss or a.train_mesh or a.mesh_terms or a.fateavatar or a.rigged or a.splatting:
+            raise SystemExit("--flash: FlashAvatar's step has its own image term (Huber) and no mesh terms; one model per run")
+        return main_flash(a, rank, world, dev)
+    if a.mouth_mask:
+        raise SystemExit("--mouth-mask goes with --flash")
     if (a.train_mesh or a.vertex_grad or a.mesh_terms) and not (a.fateavatar and a.views_per_step == 1):
         raise SystemExit("--train-mesh / --vertex-grad / --mesh-terms go with --fateavatar at one frame per step")
     if a.fateavatar:
@@ -523,6 +541,140 @@ def main_splatting(a, rank, world, dev):
                       "metric": "SplattingAvatar optimisation steps/s (mesh pass + bind + render + L1 + backward + stats + Adam)",
                       "binding": how, "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": st.pc.P,
                       "res": a.res, "frames": n_frames, "graph": not a.no_graph, "overflows": st.overflows,
+                      "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
+
+
+class DeformNet(torch.nn.Module):
+    """A deformation network of FlashAvatar's kind: the canonical point, identity plus sin / cos at the eight octave-spaced
+    frequencies 2^0 .. 2^7 (3 + 48 inputs), concatenated with the frame's condition vector; six hidden layers of 256 with ReLU;
+    ten outputs (the step applies tanh).  The last layer starts small, so the first frames are the undeformed avatar."""
+
+    def __init__(self, points: torch.Tensor, cond_dim: int, hidden: int = 256, layers: int = 6):
+        super().__init__()
+        freqs = 2.0 ** torch.arange(8, dtype=torch.float32, device=points.device)
+        ang = points[:, None, :] * freqs[None, :, None]                                   # [N,8,3]
+        self.register_buffer("embedded", torch.cat([points, torch.sin(ang).flatten(1), torch.cos(ang).flatten(1)], dim=1))
+        dims = [self.embedded.shape[1] + cond_dim] + [hidden] * layers
+        mods = []
+        for i, o in zip(dims[:-1], dims[1:]):
+            mods += [torch.nn.Linear(i, o), torch.nn.ReLU()]
+        self.net = torch.nn.Sequential(*mods, torch.nn.Linear(hidden, 10))
+        with torch.no_grad():
+            self.net[-1].weight.mul_(0.01)
+            self.net[-1].bias.zero_()
+
+    def forward(self, cond: torch.Tensor) -> torch.Tensor:
+        return self.net(torch.cat([self.embedded, cond.expand(self.embedded.shape[0], -1)], dim=1))
+
+
+def flash_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_binding=False, mouth_mask=False, vertex_grad=False):
+    """FlashAvatar's optimisation step on the synthetic INSTA-layout sequence: P Gaussians at fixed points of the template (the
+    reference's UV-raster sampling when P is its row count, else uniform faces), the step object, the deformation network with
+    its per-frame conditions (the frame's jaw and rigid rotations, from the sequence), cameras, posed meshes, mouth masks and
+    targets rendered from a hidden ground-truth set at the same places with a per-frame deformation of its own."""
+    from fateavatar_amd import insta
+    from fateavatar_amd.binding import bind_gaussians_deform
+    from fateavatar_amd.flash import FlashGaussians, FlashStep, _FlashFrame
+    from fateavatar_amd.knn import init_scale_by_knn
+    from fateavatar_amd.splatting import sample_bary_on_triangles
+    n_frames = max(views, 8)
+    transform, posed, faces = insta.synthetic_sequence(n_frames, res, seed=0)
+    cams = [TorchCamera(c, dev) for c in insta.camera_arrays(transform)]
+    posed_t, faces_t = torch.from_numpy(posed).to(dev), torch.from_numpy(faces).to(dev).to(torch.int32)
+    canon = torch.from_numpy(np.asarray(scenes.head_geometry()[0], dtype=np.float32)).to(dev)
+    bg = torch.ones(3, device=dev)
+    g = torch.Generator().manual_seed(0)
+    fi, bary = sample_bary_on_triangles(int(faces.shape[0]), P, g)
+    pts = torch.einsum("nij,ni->nj", canon[faces_t.long()][fi.to(dev)], bary.to(dev)).contiguous()
+    scale_init = float(init_scale_by_knn(pts)[2])
+    pc, gt = FlashGaussians(fi, bary, scale_init, dev), FlashGaussians(fi, bary, scale_init, dev)
+    g = torch.Generator().manual_seed(5)
+    with torch.no_grad():
+        gt._features_dc.copy_((torch.rand(P, 1, 3, generator=g) * 2.0 - 1.0).to(dev))
+        gt._opacity.fill_(float(np.log(0.6 / 0.4)))
+        gt._rotation.add_((0.3 * torch.randn(P, 4, generator=g)).to(dev))
+    _, Rj, Rg = insta.synthetic_pose_maps(n_frames, seed=0)
+    conds = [torch.from_numpy(np.concatenate([Rj[f].reshape(-1), Rg[f].reshape(-1)])).to(dev) for f in range(n_frames)]
+    # the hidden avatar's own deformation: smooth in the canonical point, different per frame
+    gts, masks = [], []
+    yy, xx = torch.meshgrid(torch.arange(res, device=dev), torch.arange(res, device=dev), indexing="ij")
+    width = torch.tensor([0.002] * 3 + [0.3] * 4 + [0.2] * 3, device=dev)
+    with torch.no_grad():
+        for f in range(n_frames):
+            phase = torch.linspace(0.0, 3.0, 10, device=dev) + f
+            hidden = torch.sin(40.0 * pts.sum(1, keepdim=True) + phase) * width
+            b = bind_gaussians_deform(posed_t[f], faces_t, gt.face_index, gt.bary_coords, hidden, gt._rotation, gt._scaling)
+            gts.append(render(cams[f], _FlashFrame(gt, None, bound=b), bg)["render"].clone())
+            masks.append((((yy - 0.62 * res) / (0.10 * res)) ** 2 + ((xx - 0.5 * res) / (0.16 * res)) ** 2 < 1).float()[None].contiguous())
+    net = DeformNet(pc.canonical_points(canon, faces_t), conds[0].numel()).to(dev)
+    cls = FlashStep
+    if torch_binding:
+        from tests import flash_ref
+
+        class TorchBoundStep(FlashStep):
+            """The A/B: the reference's own route — binding and Huber term as stock PyTorch kernels with autograd around render()."""
+            def _forward_backward(self):
+                pc = self.pc
+                pc.begin_step()
+                verts = self._vertex_leaf(self.verts)
+                deform = self.deform.detach().requires_grad_(True)
+                bound = flash_ref.deform_bind(verts, self.faces, pc.face_index, pc.bary_coords, deform, pc._rotation, pc._scaling)
+                out = render(self.cam, _FlashFrame(pc, (self.xyz_gradient_accum, self.denom, pc.overflow_word), bound=bound), self.bg)
+                terms = flash_ref.huber_loss(out["render"], self.gt, self.mask, self.huber.alpha, self.huber.mask_weight)
+                self.loss_terms.copy_(torch.stack([t.detach() for t in terms]))
+                terms[0].backward()
+                pc.collect_grads()
+                self._keep_vertex_grad(verts)
+                self.d_deform = deform.grad
+                self.out = self._kept(out)
+        cls = TorchBoundStep
+    st = cls(pc, faces_t, TorchCamera(insta.camera_arrays(transform)[0], dev), bg, posed_t[0], use_graph=use_graph,
+             fold_binding=fold_binding, mouth_mask=mouth_mask, vertex_grad=vertex_grad)
+    return dict(st=st, net=net, conds=conds, cams=cams, posed=posed_t, gts=gts, masks=masks, n_frames=n_frames)
+
+
+def main_flash(a, rank, world, dev):
+    if world > 1:
+        raise SystemExit("--flash: data-parallel runs are not built")
+    P = a.P if "--P" in sys.argv else 16_384
+    su = flash_setup(P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
+                     torch_binding=a.torch_binding, mouth_mask=a.mouth_mask, vertex_grad=a.vertex_grad)
+    st, net, conds, cams, posed_t, gts, masks, n_frames = (su[k] for k in ("st", "net", "conds", "cams", "posed", "gts", "masks", "n_frames"))
+    opt = torch.optim.Adam(net.parameters(), lr=1e-4)      # the reference's `deformer` group (train/optim.py:55-59)
+    first = [p.detach().clone() for p in net.parameters()]
+
+    def one_step(it):
+        f = it % n_frames
+        deform = net(conds[f])
+        loss = st.step(cams[f], posed_t[f], deform, gts[f], masks[f] if a.mouth_mask else None)
+        opt.zero_grad(set_to_none=True)
+        deform.backward(st.d_deform)                       # dLoss/d(deform) -> the network's weights: stock PyTorch
+        opt.step()
+        return loss
+
+    losses, warm = [], 10
+    for it in range(warm):
+        losses.append(one_step(it).clone())
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(warm, warm + a.steps):
+        loss = one_step(it)
+        if it >= warm + a.steps - 4:
+            losses.append(loss.clone())
+    t_host = time.perf_counter() - t0
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    st.check()
+    l = [float(x) for x in losses]
+    how = "stock PyTorch (binding + Huber + autograd) around render()" if a.torch_binding else "stand-alone kernels" if a.binding_op else \
+        "inside the per-Gaussian kernels (fr_aux::binding, MLP-deformed)"
+    moved = max(float((p.detach() - q).abs().max()) for p, q in zip(net.parameters(), first))
+    print(json.dumps({"host_enqueue_ms_per_step": round(t_host / a.steps * 1e3, 4),
+                      "metric": "FlashAvatar optimisation steps/s (torch MLP + bind + render + Huber + backward + stats + Adam + MLP backward / Adam)",
+                      "binding": how, "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": st.pc.P,
+                      "res": a.res, "frames": n_frames, "graph": not a.no_graph, "overflows": st.overflows,
+                      "mouth_mask": bool(a.mouth_mask), "vertex_grad": bool(st.vertex_grad),
+                      "loss_terms": [round(float(x), 6) for x in st.loss_terms], "mlp_weights_moved": moved,
                       "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
 
 
