@@ -647,6 +647,55 @@ int fr_mesh_terms(const fr_mesh_terms_config* cfg, int32_t V, const float* verts
     return launch_mesh_terms(*cfg, V, verts, verts_orig, row_ptr, col, d_verts, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
+static const char* point_lbs_invalid(const fr_point_lbs* d)
+{
+    if (!d || d->N < 0) return "fr_point_lbs: null descriptor or negative N";
+    if (d->E < 1 || d->E > FR_LBS_MAX_E || d->J < 1 || d->J > FR_LBS_MAX_J) return "fr_point_lbs: E outside 1 .. FR_LBS_MAX_E or J outside 1 .. FR_LBS_MAX_J";
+    if (d->N > 0 && (!d->points || !d->shapedirs || !d->posedirs || !d->weights)) return "fr_point_lbs: null per-point array";
+    for (const fr_pose_state* p : {&d->canonical, &d->frame})
+        if (!p->betas || !p->pose_feature || !p->transforms) return "fr_point_lbs: null pose state array";
+    return nullptr;
+}
+
+int fr_point_lbs_forward(const fr_point_lbs* lbs, float* xyz, void* stream)
+{
+    if (const char* why = point_lbs_invalid(lbs)) return fail_msg(FR_ERR_INVALID_ARGUMENT, why);
+    if (lbs->N > 0 && !xyz) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_point_lbs_forward: null xyz");
+    return launch_point_lbs_forward(*lbs, xyz, static_cast<hipStream_t>(stream));
+}
+
+int fr_point_lbs_backward(const fr_point_lbs* lbs, const float* g_xyz, float* d_points, float* d_shapedirs, float* d_posedirs,
+                          float* d_weights, void* stream)
+{
+    if (const char* why = point_lbs_invalid(lbs)) return fail_msg(FR_ERR_INVALID_ARGUMENT, why);
+    if (lbs->N > 0 && !g_xyz) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_point_lbs_backward: null g_xyz");
+    return launch_point_lbs_backward(*lbs, g_xyz, d_points, d_shapedirs, d_posedirs, d_weights, static_cast<hipStream_t>(stream));
+}
+
+int fr_nearest_vertex(int32_t N, const float* points, int32_t V, const float* verts, int32_t* index, float* dist2, void* stream)
+{
+    if (N < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_nearest_vertex: negative N");
+    if (V <= 0 || V > FR_NEAREST_MAX_V) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_nearest_vertex: V outside 1 .. FR_NEAREST_MAX_V");
+    if (!verts || (N > 0 && (!points || !index))) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_nearest_vertex: null points, verts or index");
+    return launch_nearest_vertex(N, points, V, verts, index, dist2, static_cast<hipStream_t>(stream));
+}
+
+size_t fr_lbs_terms_workspace_bytes(void) { return lbs_terms_workspace_bytes(); }
+
+int fr_lbs_terms(const fr_lbs_terms_config* cfg, int32_t N, int32_t V, int32_t E, int32_t J, const int32_t* index, const float* weights,
+                 const float* posedirs, const float* shapedirs, const float* gt_weights, const float* gt_posedirs,
+                 const float* gt_shapedirs, float* d_weights, float* d_posedirs, float* d_shapedirs, float* loss, void* workspace,
+                 void* stream)
+{
+    if (!cfg || N < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_lbs_terms: null configuration or negative N");
+    if (V < 1 || E < 1 || J < 1) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_lbs_terms: V, E and J are at least 1");
+    if (N > 0 && (!index || !weights || !posedirs || !shapedirs)) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_lbs_terms: null index or predicted array");
+    if (!gt_weights || !gt_posedirs || !gt_shapedirs) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_lbs_terms: null ground-truth table");
+    if (!workspace || !loss) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_lbs_terms: null workspace or loss");
+    return launch_lbs_terms(*cfg, N, V, E, J, index, weights, posedirs, shapedirs, gt_weights, gt_posedirs, gt_shapedirs, d_weights,
+                            d_posedirs, d_shapedirs, loss, workspace, static_cast<hipStream_t>(stream));
+}
+
 int fr_multi_copy(int32_t n_segments, float* const* dst, const float* const* src, const uint64_t* count, void* stream)
 {
     if (n_segments < 0 || n_segments > FR_COPY_MAX_SEGMENTS || (n_segments > 0 && (!dst || !src || !count)))

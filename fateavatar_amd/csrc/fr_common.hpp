@@ -492,6 +492,15 @@ int launch_gaussian_regularise(const fr_regularise_config& cfg, int P, const flo
 size_t mesh_terms_workspace_bytes();
 int launch_mesh_terms(const fr_mesh_terms_config& cfg, int V, const float* verts, const float* verts_orig, const int* row_ptr,
                       const int* col, float* d_verts, float* loss, void* workspace, hipStream_t s);
+int launch_point_lbs_forward(const fr_point_lbs& lbs, float* xyz, hipStream_t s);
+int launch_point_lbs_backward(const fr_point_lbs& lbs, const float* g_xyz, float* d_points, float* d_shapedirs, float* d_posedirs,
+                              float* d_weights, hipStream_t s);
+int launch_nearest_vertex(int N, const float* points, int V, const float* verts, int* index, float* dist2, hipStream_t s);
+size_t lbs_terms_workspace_bytes();
+int launch_lbs_terms(const fr_lbs_terms_config& cfg, int N, int V, int E, int J, const int* index, const float* weights,
+                     const float* posedirs, const float* shapedirs, const float* gt_weights, const float* gt_posedirs,
+                     const float* gt_shapedirs, float* d_weights, float* d_posedirs, float* d_shapedirs, float* loss, void* workspace,
+                     hipStream_t s);
 int launch_multi_copy(int n_seg, float* const* dst, const float* const* src, const unsigned long long* count, hipStream_t s);
 int launch_selftest_reduce(const float* in, float* out, hipStream_t s);
 

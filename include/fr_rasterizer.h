@@ -673,6 +673,70 @@ int fr_knn_mean_dist2(int32_t P, const float* points, float* out, void* workspac
 int fr_knn_nearest_dist2(int32_t P, const float* points, float* out, void* workspace, size_t workspace_bytes,
                          void* hip_stream);
 
+/* ---- MonoGaussianAvatar's point deformation: every point carries its own blendshapes and skinning weights and is moved by
+ * FLAME's linear blend skinning (reference: FLAME.forward_pts, flame/FLAME.py:207-237, over flame/lbs.py:103-188; the caller
+ * is model/baseline/monogaussianavatar.py:345-359).  One launch per direction where the reference expands the expression
+ * vector, the pose feature and the bone transforms per point, inverts N 4x4 matrices and differentiates the lot forward-mode.
+ * Per point, with h = (p, 1), a pose state (betas [E], pose_feature [36], transforms [J,16] row-major 4x4) for the canonical
+ * pose (c) and one for the frame:
+ *   T_c = sum_j w_j A^c_j                  z = T_c^-1 h                (a 4-vector: z[3] = 1 / sum_j w_j)
+ *   x   = z[:3] + S (beta - beta_c) + P^T (phi - phi_c)                (S = shapedirs [3,E], P = posedirs [36,3] of the point)
+ *   xyz = (sum_j w_j A_j (x, 1))[:3]                                   (no division by the homogeneous coordinate)
+ * PRECONDITION, not checked on the device: every bone matrix has the last row (0, 0, 0, 1).  The weights are taken as given:
+ * they need not sum to 1.  The backward takes g_xyz [N,3] and writes EVERY row of d_points [N,3], d_shapedirs [N,3,E],
+ * d_posedirs [N,36,3] and d_weights [N,J]; any of them may be NULL, and what is written does not depend on which are.  The
+ * pose states get no gradient.  All pointers are device pointers; no call allocates, synchronises or uses float atomics:
+ * the same bits on every launch, and both calls can be captured in a graph (the pose states are read at run time).
+ * N == 0 launches nothing.  E outside 1 .. FR_LBS_MAX_E or J outside 1 .. FR_LBS_MAX_J is FR_ERR_INVALID_ARGUMENT. */
+#define FR_LBS_MAX_E 64
+#define FR_LBS_MAX_J 8
+#define FR_LBS_POSE_FEATURES 36
+typedef struct fr_pose_state {
+    const float* betas;        /* [E] expression coefficients */
+    const float* pose_feature; /* [FR_LBS_POSE_FEATURES] */
+    const float* transforms;   /* [J,16] */
+} fr_pose_state;
+typedef struct fr_point_lbs {
+    int32_t N, E, J;
+    const float* points;    /* [N,3] */
+    const float* shapedirs; /* [N,3,E] */
+    const float* posedirs;  /* [N,FR_LBS_POSE_FEATURES,3] */
+    const float* weights;   /* [N,J] */
+    fr_pose_state canonical, frame;
+} fr_point_lbs;
+int fr_point_lbs_forward(const fr_point_lbs* lbs, float* xyz, void* hip_stream);
+int fr_point_lbs_backward(const fr_point_lbs* lbs, const float* g_xyz, float* d_points, float* d_shapedirs, float* d_posedirs,
+                          float* d_weights, void* hip_stream);
+
+/* ---- index[i] = the vertex nearest to points[i], brute force against V <= FR_NEAREST_MAX_V vertices held in LDS (reference:
+ * pytorch3d's knn_points(p, verts, K=1), train/loss.py:231-233).  The squared distance is (dx*dx + dy*dy) + dz*dz in float32
+ * without contraction, d = point - vertex; ties go to the LOWEST index.  `dist2` [N] may be NULL.  V <= 0 or
+ * V > FR_NEAREST_MAX_V is FR_ERR_INVALID_ARGUMENT; N == 0 launches nothing. */
+#define FR_NEAREST_MAX_V 8192
+int fr_nearest_vertex(int32_t N, const float* points, int32_t V, const float* verts, int32_t* index, float* dist2,
+                      void* hip_stream);
+
+/* ---- the three blendshape terms of MonoGaussianAvatarLoss in ONE launch (reference: train/loss.py:418-445, :472-515): with
+ * v = index[i] (clamped to 0 .. V-1) the plain mean squared errors
+ *   loss[0] = mean (weights [N,J]     - gt_weights [V,J][v])^2
+ *   loss[1] = mean (posedirs [N,36,3] - gt_posedirs [V,36,3][v])^2
+ *   loss[2] = mean (shapedirs [N,3,E] - gt_shapedirs [V,3,E][v])^2
+ * UNWEIGHTED, and the kernel ADDS weight_k * 2 (pred - gt) / count_k into d_weights / d_posedirs / d_shapedirs by a
+ * read-modify-write of the lane that owns the element (so that it lands on what fr_point_lbs_backward wrote; no atomics).  A
+ * weight of 0 leaves that array untouched; a NULL gradient pointer means that term's loss only.  The caller pads the ghost
+ * bone's column and transposes FLAME's [36, 3V] pose basis.  Sums and workspace as fr_gaussian_regularise: per-workgroup
+ * partials summed in index order by the workgroup that finishes last (the same bits on every launch); `workspace`:
+ * fr_lbs_terms_workspace_bytes() bytes, zeroed ONCE by the caller, left zeroed, not shared by launches that can overlap.
+ * `loss`: three device floats.  N == 0 launches nothing and leaves `loss` as it is. */
+typedef struct fr_lbs_terms_config {
+    float weights_weight, posedirs_weight, shapedirs_weight;
+} fr_lbs_terms_config;
+size_t fr_lbs_terms_workspace_bytes(void);
+int fr_lbs_terms(const fr_lbs_terms_config* cfg, int32_t N, int32_t V, int32_t E, int32_t J, const int32_t* index,
+                 const float* weights, const float* posedirs, const float* shapedirs, const float* gt_weights,
+                 const float* gt_posedirs, const float* gt_shapedirs, float* d_weights, float* d_posedirs, float* d_shapedirs,
+                 float* loss, void* workspace, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,15 @@ FlashAvatar's step (fateavatar_amd/flash.py): Gaussians at fixed barycentric poi
 small torch deformation network (positional encoding of the canonical point + a per-frame condition, six hidden layers of 256,
 ten outputs; torch.optim.Adam at 1e-4) that is trained through `step.d_deform`; Huber image term, SH degree 0, one GPU.
 --torch-binding: binding and Huber as the stock-PyTorch restatement (tests/flash_ref.py) with autograd in front of render().
+
+    python tools/train_synthetic.py --mono [--P 100000] [--torch-lbs]
+MonoGaussianAvatar's loop (fateavatar_amd/mono.py): --P free points (default 100 000, the reference's max_points) with a torch
+deformer network (four hidden layers of 128: expression basis, pose-corrective basis and skinning weights per point), a geometry
+network (seven of 256) and a Gaussian network (two of 64), moved by a synthetic bone sequence through
+deform_points -> splat_attributes -> render_points and trained on L1 + the three blendshape terms against per-vertex tables of
+the template (nearest_vertex, lbs_terms_and_grad); torch.optim.Adam at 1e-4.  --torch-lbs: deformation, nearest vertex and the
+three terms as the stock-PyTorch restatement (tests/mono_ref.py) with autograd and torch gathers: the A/B.  Like --torch-binding,
+it imports the restatement from the test tree: run it from a checkout that has tests/, not from an installed package alone.
 """
 import argparse
 import json
@@ -97,6 +106,12 @@ def main():
     ap.add_argument("--flash", action="store_true",
                     help="FlashAvatar's loop: --P Gaussians (default 16 384, tex_size 128 squared) at fixed points of the template, "
                          "deformed per frame by a torch MLP trained through step.d_deform; Huber loss; --binding-op as for --fateavatar")
+    ap.add_argument("--mono", action="store_true",
+                    help="MonoGaussianAvatar's loop: --P free points (default 100 000) deformed by learned per-point linear blend "
+                         "skinning, colours from a torch network, L1 + the three blendshape terms")
+    ap.add_argument("--torch-lbs", action="store_true",
+                    help="--mono: deformation, nearest vertex and blendshape terms in stock PyTorch (tests/mono_ref.py: needs the "
+                         "checkout's tests/ next to tools/)")
     ap.add_argument("--mouth-mask", action="store_true",
                     help="--flash: every frame brings a mouth mask (the Huber term's second sum, weight 40)")
     ap.add_argument("--regularisers", action="store_true",
@@ -121,6 +136,12 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     a.image_loss = ImageLoss(*a.image_loss) if a.image_loss else (ImageLoss(0.8, 0.2) if a.dssim else None)
+    if a.mono:
+        if a.image_loss or a.train_mesh or a.mesh_terms or a.fateavatar or a.rigged or a.splatting or a.flash:
+            raise SystemExit("--mono: the image term is L1 and there are no mesh terms; one model per run")
+        return main_mono(a, rank, world, dev)
+    if a.torch_lbs:
+        raise SystemExit("--torch-lbs goes with --mono")
     if a.flash:
         if a.image_loss or a.train_mesh or a.mesh_terms or a.fateavatar or a.rigged or a.splatting:
             raise SystemExit("--flash: FlashAvatar's step has its own image term (Huber) and no mesh terms; one model per run")
@@ -675,6 +696,116 @@ def main_flash(a, rank, world, dev):
                       "res": a.res, "frames": n_frames, "graph": not a.no_graph, "overflows": st.overflows,
                       "mouth_mask": bool(a.mouth_mask), "vertex_grad": bool(st.vertex_grad),
                       "loss_terms": [round(float(x), 6) for x in st.loss_terms], "mlp_weights_moved": moved,
+                      "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
+
+
+def _mlp(d_in, hidden, d_out):
+    layers, d = [], d_in
+    for h in hidden:
+        layers += [torch.nn.Linear(d, h), torch.nn.Softplus(beta=100)]
+        d = h
+    return torch.nn.Sequential(*layers, torch.nn.Linear(d, d_out))
+
+
+def main_mono(a, rank, world, dev):
+    if world > 1:
+        raise SystemExit("--mono: data-parallel runs are not built")
+    from fateavatar_amd import mono
+    if a.torch_lbs:
+        from tests import mono_ref
+    N, E, J, n_frames = a.P, 50, 6, a.views
+    torch.manual_seed(0)
+    gen = torch.Generator().manual_seed(0)
+    rn = lambda *sh: torch.randn(sh, generator=gen)  # noqa: E731
+    truth = scenes.head_scene(P=N, res=a.res, sh_degree=0, seed=0, opacity=0.5)
+    cam = TorchCamera(truth.camera, dev)
+    bg = torch.zeros(3, device=dev)
+    # per-vertex tables of the template in fr_lbs_terms' layouts (FLAME's own are absent: smooth functions of the vertex)
+    verts = torch.from_numpy(np.asarray(scenes.head_geometry()[0], np.float32))
+    V, centre = verts.shape[0], verts.mean(0)
+    rel = (verts - centre) / 0.15
+    proj = lambda d: rel @ rn(3, d)  # noqa: E731
+    gt_w = torch.softmax(2 * proj(J), 1)
+    gt_P, gt_S = 0.003 * torch.tanh(proj(108)).reshape(V, 36, 3), 0.003 * torch.tanh(proj(3 * E)).reshape(V, 3, E)
+    verts, gt_w, gt_P, gt_S = (t.contiguous().to(dev) for t in (verts, gt_w, gt_P, gt_S))
+
+    def bones(angle):                     # rigid motions about the head's centre; bone 0 (the ghost bone) the identity
+        r = angle * rn(J, 3)
+        th = r.norm(dim=1).clamp_min(1e-12)
+        k = r / th[:, None]
+        K = torch.zeros(J, 3, 3)
+        K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -k[:, 2], k[:, 1], k[:, 2], -k[:, 0], -k[:, 1], k[:, 0]
+        R = torch.eye(3)[None] + torch.sin(th)[:, None, None] * K + (1 - torch.cos(th))[:, None, None] * (K @ K)
+        A = torch.eye(4).repeat(J, 1, 1)
+        A[:, :3, :3], A[:, :3, 3] = R, 0.004 * rn(J, 3) + centre - R @ centre
+        A[0] = torch.eye(4)
+        return A
+
+    state = lambda angle, amp: mono.PoseState(*[t.to(dev) for t in (amp * rn(E), 0.3 * amp * rn(36), bones(angle))])  # noqa: E731
+    canonical = state(0.02, 0.0)
+    frames = [state(0.12, 0.5) for _ in range(n_frames)]
+    # targets: the hidden points carry their nearest vertex' table rows and fixed attributes
+    pts_true = torch.from_numpy(np.asarray(truth.means3D, np.float32)).to(dev)
+    feats_true = torch.cat([rn(N, 3), rn(N, 3) - 1.0, rn(N, 4), rn(N, 1)], 1).to(dev)
+    radius = 0.002
+    with torch.no_grad():
+        idx = mono.nearest_vertex(pts_true, verts)[0].long()
+        attrs = mono.splat_attributes(feats_true, torch.zeros_like(feats_true), radius, scene_scale=4.0)
+        gts = [mono.render_points(cam, mono.deform_points(pts_true, gt_S[idx], gt_P[idx], gt_w[idx], canonical, f), *attrs, bg)[0].clone()
+               for f in frames]
+    points = (pts_true + 0.002 * rn(N, 3).to(dev)).requires_grad_(True)
+    deformer, geometry, gaussian = _mlp(3, [128] * 4, 3 * E + 108 + J).to(dev), _mlp(3, [256] * 7, 11).to(dev), _mlp(3, [64, 64], 11).to(dev)
+    nets = (deformer, geometry, gaussian)
+    opt = torch.optim.Adam([points] + [p for n in nets for p in n.parameters()], lr=1e-4)
+    terms = mono.reference_lbs_weights(10.0)
+    lbs = torch.zeros(3, device=dev)
+
+    def one_step(it):
+        frame = frames[it % n_frames]
+        opt.zero_grad(set_to_none=True)
+        q = deformer((points.detach() - centre.to(dev)) / 0.15)
+        S, P, w = 0.01 * q[:, :3 * E].reshape(N, 3, E), 0.01 * q[:, 3 * E:3 * E + 108].reshape(N, 36, 3), torch.softmax(q[:, 3 * E + 108:], 1)
+        if a.torch_lbs:
+            xyz = mono_ref.deform_points(points, S, P, w, canonical, frame)
+        else:
+            leaves = [t.detach().requires_grad_(True) for t in (S, P, w)]
+            xyz = mono.deform_points(points, *leaves, canonical, frame)
+        feats = geometry((points.detach() - centre.to(dev)) / 0.15)
+        offs = gaussian((xyz.detach() - points.detach()) / 0.15)
+        rgb, opacity, scales, rotations = mono.splat_attributes(feats, offs, radius, scene_scale=4.0)
+        image = mono.render_points(cam, xyz, rgb, opacity, scales, rotations, bg)[0]
+        loss = (image - gts[it % n_frames]).abs().mean()
+        if a.torch_lbs:
+            index = mono_ref.nearest_vertex(points.detach(), verts)[0]
+            three = mono_ref.lbs_terms(index, w, P, S, gt_w, gt_P, gt_S)
+            (loss + (three * torch.tensor(tuple(terms), device=dev)).sum()).backward()
+            lbs.copy_(three.detach())
+        else:
+            loss.backward()                # image term -> points, the two attribute networks and the three leaves
+            index = mono.nearest_vertex(points.detach(), verts)[0]
+            mono.lbs_terms_and_grad(index, leaves[2], leaves[1], leaves[0], gt_w, gt_P, gt_S, terms, leaves[2].grad, leaves[1].grad,
+                                    leaves[0].grad, out=lbs)
+            torch.autograd.backward([S, P, w], [t.grad for t in leaves])      # -> the deformer's weights: stock PyTorch
+        opt.step()
+        return loss.detach()
+
+    losses, warm = [], 5
+    for it in range(warm):
+        losses.append(one_step(it).clone())
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(warm, warm + a.steps):
+        loss = one_step(it)
+        if it >= warm + a.steps - 4:
+            losses.append(loss.clone())
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    l = [float(x) for x in losses]
+    print(json.dumps({"metric": "MonoGaussianAvatar optimisation steps/s (three torch MLPs + LBS + render + L1 + blendshape terms + "
+                                "backward + Adam)",
+                      "lbs": "stock PyTorch (tests/mono_ref.py)" if a.torch_lbs else "fused (fr_point_lbs, fr_nearest_vertex, fr_lbs_terms)",
+                      "value": round(a.steps / dt, 2), "ms_per_step": round(dt / a.steps * 1e3, 3), "P": N, "V": V, "res": a.res,
+                      "frames": n_frames, "lbs_terms": [float(x) for x in lbs],
                       "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
 
 
