@@ -331,10 +331,16 @@ def _huber_case(shape, seed):
     return img, gt, mask
 
 
+HUBER_GRID_CAP = 1024 * 256 * 4    # floats one trip of k_huber_loss_grad's float4 sweep covers at the launch's cap (kL1MaxBlocks, fr_optim.hip)
+
+
 @pytest.mark.parametrize("masked", [False, True])
-@pytest.mark.parametrize("shape", [(3, 37, 41), (3, 128, 128), (3, 512, 512)])
+@pytest.mark.parametrize("shape", [(3, 37, 41), (3, 128, 128), (3, 512, 512), (3, 593, 591), (4, 512, 512), (4, 65, 4033)])
 def test_huber_loss_and_grad_matches_the_restatement(gpu_device, shape, masked):
-    """The three loss words within 1e-6 relative of the float64 restatement (test_l1_loss_and_grad_matches_autograd's bound), the
+    """(3 x 593 x 591 = 1 051 389 floats: past HUBER_GRID_CAP, so some lanes make a second trip; n % 4 = 1, so there is a scalar
+    tail; H W is odd, so float4 pieces straddle the channel boundary of the mask's broadcast.  4 x 512 x 512 is HUBER_GRID_CAP exactly:
+    every lane of the capped grid makes one trip; 4 x 65 x 4033 is one float4 more: one lane makes a second.)
+    The three loss words within 1e-6 relative of the float64 restatement (test_l1_loss_and_grad_matches_autograd's bound), the
     gradient within rtol 1e-6 of the float32 restatement's autograd (a handful of roundings of same-signed terms, no
     cancellation; exactly 0 where d = 0); three repeated calls give identical bits (the workspace comes back zeroed, the sums
     are reproducible); without a gradient buffer the loss is still written."""
@@ -342,6 +348,10 @@ def test_huber_loss_and_grad_matches_the_restatement(gpu_device, shape, masked):
     from fateavatar_amd.loss import huber_loss_and_grad, huber_workspace
     dev = gpu_device
     img, gt, mask = _huber_case(shape, seed=shape[1])
+    if shape[1] > 512:
+        assert img.numel() > HUBER_GRID_CAP and img.numel() % 4 == 1 and (shape[1] * shape[2]) % 4 != 0
+    if shape[0] == 4:
+        assert img.numel() == HUBER_GRID_CAP + (0 if shape[1] == 512 else 4)
     m = mask if masked else None
     want = [float(x) for x in R.huber_loss(img.double(), gt.double(), None if m is None else m.double())]
     leaf = img.clone().requires_grad_(True)

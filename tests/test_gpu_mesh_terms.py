@@ -7,13 +7,19 @@ of config/fateavatar.yaml:23; the restatement the kernel is held to is tests/mes
 import numpy as np
 import pytest
 
-from tests.mesh_terms_ref import displaced, flame_distance, float64_terms, laplacian_dense, laplacian_smoothing, random_mesh
+from tests.mesh_terms_ref import (displaced, flame_distance, float64_terms, float64_terms_sparse, laplacian_dense, laplacian_smoothing,
+                                  random_mesh, random_mesh_drawn_at_once)
 
 pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -24
-N_RED = 21     # roundings of a loss sum behind its terms: see test_mesh_terms_kernel_matches_float64
+N_RED = 21     # roundings of a loss sum behind its terms up to 8 192 vertices: see test_mesh_terms_kernel_matches_float64
+MESH_GRID_CAP = 1024 * 32   # vertices one sweep of k_mesh_terms covers: kMeshMaxBlocks x (kMeshThreads / kMeshGroup), fr_mesh_terms.hip
 SIZES = [1, 3, 4, 63, 64, 65, 257]
+# past the cap (an exactly full sweep, one vertex in a second sweep, a partial third sweep): meshes drawn at once, held to the
+# sparse float64 restatement (V x V doubles would be 8.6 GB and more)
+BIG_SIZES = [MESH_GRID_CAP, MESH_GRID_CAP + 1, 2 * MESH_GRID_CAP + 9]
 SEED = {1: 101, 3: 103, 4: 104, 63: 115, 64: 105, 65: 101, 257: 102}   # (63 .. 257: draws that leave a vertex without a face)
+SEED.update({V: 200 + k for k, V in enumerate(BIG_SIZES)})
 _cache = {}
 
 
@@ -25,20 +31,28 @@ def _mesh(V):
             vo, faces, _ = scenes.head_geometry()
             vo, faces, seed = np.ascontiguousarray(vo, dtype=np.float32), np.asarray(faces, dtype=np.int64), 7
         else:
-            vo, faces = random_mesh(V, SEED[V])
+            vo, faces = (random_mesh_drawn_at_once if V in BIG_SIZES else random_mesh)(V, SEED[V])
             seed = SEED[V]
         _cache[V] = (vo, displaced(vo, seed), faces)
     return _cache[V]
 
 
 def _truth(V, weights):
-    """float64_terms of a case, computed once per (case, weights) and left unchanged."""
+    """float64_terms of a case (past the cap: its sparse form), computed once per (case, weights) and left unchanged."""
     import torch
     key = (V, tuple(weights))
     if key not in _cache:
         vo, v, faces = _mesh(V)
-        _cache[key] = float64_terms(faces, vo.shape[0], torch.from_numpy(vo), torch.from_numpy(v), *weights)
+        terms = float64_terms_sparse if V in BIG_SIZES else float64_terms
+        _cache[key] = terms(faces, vo.shape[0], torch.from_numpy(vo), torch.from_numpy(v), *weights)
     return _cache[key]
+
+
+def _n_red(V):
+    """N_RED, plus one rounding per further partial a lane of the last workgroup adds up (past 8 192 vertices) and one per
+    further vertex a group of lanes visits (past MESH_GRID_CAP), as csrc/fr_mesh_terms.hip's header spells out."""
+    blocks = min(-(-V // 32), MESH_GRID_CAP // 32)
+    return N_RED + (-(-blocks // 256) - 1) + (-(-V // (32 * blocks)) - 1)
 
 
 def _grad_bound(t, weights, V, want):
@@ -50,8 +64,8 @@ def _grad_bound(t, weights, V, want):
 
 def _loss_bounds(t, V):
     r_err = (t["deg"][:, None].double() + 3.0) * EPS * t["Mr"]
-    lap = float((2.0 * t["r"].abs() * r_err).sum()) / V + N_RED * EPS * t["lap"]
-    flame = float((2.0 * t["d"].abs() * EPS * t["d"].abs()).sum()) / (3.0 * V) + N_RED * EPS * t["flame"]
+    lap = float((2.0 * t["r"].abs() * r_err).sum()) / V + _n_red(V) * EPS * t["lap"]
+    flame = float((2.0 * t["d"].abs() * EPS * t["d"].abs()).sum()) / (3.0 * V) + _n_red(V) * EPS * t["flame"]
     return lap, flame
 
 
@@ -68,11 +82,15 @@ def test_drawn_meshes_have_empty_rows():
     empty = {V: int((_truth(V, (1e5, 0.0))["deg"] == 0).sum()) for V in SIZES}
     assert empty[1] == 1 and min(empty[63], empty[64], empty[65], empty[257]) >= 1 and empty[3] == empty[4] == 0, empty
     assert int(_truth(257, (1e5, 0.0))["deg"].max()) > int(_truth(257, (1e5, 0.0))["deg"].min()) + 4      # irregular degrees
+    for V in BIG_SIZES:
+        deg = _truth(V, (1e5, 0.0))["deg"]
+        assert deg.shape == (V,) and int((deg == 0).sum()) >= 8 and int(deg.max()) > int(deg.min()) + 16, V
+    assert [_n_red(V) for V in (1, 5023, 8192, 8193, MESH_GRID_CAP, MESH_GRID_CAP + 1, 2 * MESH_GRID_CAP + 9)] == [21, 21, 21, 22, 24, 25, 26]
 
 
 # ------------------------------------------------------------------ 4. the kernel against float64
 @pytest.mark.parametrize("weights", [(1e5, 0.0), (1e5, 0.3)])
-@pytest.mark.parametrize("V", SIZES + ["template"])
+@pytest.mark.parametrize("V", SIZES + ["template"] + BIG_SIZES)
 def test_mesh_terms_kernel_matches_float64(gpu_device, V, weights):
     """`mesh_terms_and_grad` against float64 autograd of w_lap x laplacian + w_flame x flame on the dense restatement, added
     to a gradient array pre-filled with the gradient's own sign: expected = before + grad, no entry exempt.  eps = 2^-24.
@@ -89,8 +107,11 @@ def test_mesh_terms_kernel_matches_float64(gpu_device, V, weights):
     Loss scalars: |dloss| <= sum_i 2 |r_i| bound(r_i) / V + N_RED eps loss (flame: d, bound eps |d|, 3 V) with N_RED = 21: the
     squares and the row's two additions 3, the wave's shuffle tree 6, the workgroup's four waves 2, in the last workgroup
     its shuffle tree 6 and four waves 2 (one partial per lane: 157 workgroups of 32 vertices on the template), the rounded
-    1 / V and the product 2; a group of lanes visits one vertex up to 32 768 vertices.
-    Achieved maxima (MI355X): see profiles/r15_mesh_terms.md."""
+    1 / V and the product 2; a group of lanes visits one vertex up to 32 768 vertices.  Past 8 192 vertices a lane of the last
+    workgroup adds up ceil(B / 256) partials (B = min(ceil(V / 32), 1024) workgroups) and past MESH_GRID_CAP a group visits
+    ceil(V / 32 B) vertices, a rounding more for each further one (`_n_red`): 24, 25, 26 at BIG_SIZES, whose meshes are drawn at
+    once and held to the SPARSE float64 restatement (tests/test_mesh_terms_host.py pins it to the dense one).
+    Achieved maxima (MI355X): see profiles/r15_mesh_terms.md, past the cap profiles/r18_grid_caps.md."""
     import torch
     from fateavatar_amd.loss import MeshTerms, mesh_terms_and_grad, mesh_terms_workspace
     dev = gpu_device

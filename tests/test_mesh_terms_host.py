@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.mesh_terms_ref import flame_distance, laplacian_dense, laplacian_smoothing
+from tests.mesh_terms_ref import (displaced, flame_distance, float64_terms, float64_terms_sparse, laplacian_dense, laplacian_smoothing,
+                                  random_mesh, random_mesh_drawn_at_once)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "fr_rasterizer.h")
@@ -94,6 +95,32 @@ def test_restated_losses_on_the_tetrahedron_by_hand():
     assert torch.allclose(v.grad[0], torch.tensor([2.0, -2.0 / 3.0, -2.0 / 3.0], dtype=torch.float64), atol=1e-12)
     # a constant shift of the whole mesh is in the Laplacian's null space
     assert abs(float(laplacian_smoothing(L, vo, vo + 0.25))) < 1e-24
+
+
+@pytest.mark.parametrize("weights", [(1e5, 0.0), (1e5, 0.3)])
+def test_sparse_restatement_is_the_dense_one(weights):
+    """`float64_terms_sparse` (what the GPU test is held to where V x V does not fit) against `float64_terms` on the drawn meshes
+    of tests/test_gpu_mesh_terms.py, a mesh drawn at once and the hand-written cases: `grad`, `lap`, `flame` (and the
+    magnitudes the bounds are written in) to 1e-12 relative, `deg` exactly."""
+    from tests.test_gpu_mesh_terms import SEED, SIZES
+    meshes = [random_mesh(V, SEED[V]) + (SEED[V],) for V in SIZES] + [random_mesh_drawn_at_once(300, 5) + (5,)]
+    meshes += [(0.1 * np.random.default_rng(3).standard_normal((V, 3)).astype(np.float32), np.asarray(faces, np.int64), 9)
+               for V, faces, _ in CASES.values()]
+    empty = 0
+    for vo, faces, seed in meshes:
+        V = vo.shape[0]
+        vo_t, v_t = torch.from_numpy(vo), torch.from_numpy(displaced(vo, seed))
+        dense, sparse = float64_terms(faces, V, vo_t, v_t, *weights), float64_terms_sparse(faces, V, vo_t, v_t, *weights)
+        assert sorted(dense) == sorted(sparse)
+        assert sparse["deg"].dtype == dense["deg"].dtype and torch.equal(sparse["deg"], dense["deg"])
+        empty += int((sparse["deg"] == 0).sum())
+        for k in ("lap", "flame"):
+            assert dense[k] > 0 and abs(sparse[k] - dense[k]) <= 1e-12 * dense[k], (V, k)
+        for k in ("grad", "r", "d", "Mr", "Mg"):
+            assert sparse[k].shape == dense[k].shape and sparse[k].dtype == torch.float64
+            assert float((sparse[k] - dense[k]).norm()) <= 1e-12 * float(dense[k].norm()), (V, k)
+            assert float((sparse[k] - dense[k]).abs().max()) <= 1e-12 * float(dense[k].abs().max()), (V, k)
+    assert empty >= 5                                # rows without a neighbour were among them
 
 
 def test_new_entries_are_declared_exported_and_listed():

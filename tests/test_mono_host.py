@@ -71,6 +71,38 @@ def test_the_recipe_has_the_rows_the_design_asks_for():
             assert float(torch.linalg.cond(T_c / w.sum(1)[:, None, None]).max()) < 1.5
 
 
+def _recipe_digest(*args, **kw):
+    """sha256 (first 16 hex digits) over every tensor of the recipe, rounded to float32 (the values the GPU tests feed)."""
+    import hashlib
+    p, S, P, w, c, f, g = R.recipe(*args, **kw)
+    h = hashlib.sha256()
+    for t in (p, S, P, w, *c, *f, g):
+        h.update(t.float().contiguous().numpy().tobytes())
+    return h.hexdigest()[:16]
+
+
+def test_the_recipe_keeps_its_values_and_is_valid_for_one_bone():
+    """The digests were taken BEFORE the recipe learnt J = 1 (the rows without bone 0 are skipped there: with one bone the row would
+    be 0 / 0, and the points are drawn smaller): every (N, E, J) in use then gives the same float32 bits now.  With J = 1 every
+    tensor is finite, the weights are the softmax's 1 apart from the scaled block, and the deformation and its gradients are
+    finite."""
+    want = {(1, 50, 6): "0b22257940740a6f", (63, 7, 5): "f6eb026b67683433", (65, 50, 6): "a190ca7814dbc539",
+            (4099, 50, 6): "a1770f02762c83a1", (4099, 7, 5): "d6b26c3fa37bd498", (33, 7, 5): "ee731b9948b4b382"}
+    assert {k: _recipe_digest(*k) for k in want} == want
+    assert _recipe_digest(40, 7, 5, seed=1) == "f65b7b9d4e7cf8c7" and _recipe_digest(5, 4, 3, seed=3) == "dc6d99d20b22d751"
+    for N, E in ((1, 1), (30, 3), (4099, 1), (4099, 16)):
+        p, S, P, w, c, f, g = R.recipe(N, E, 1)
+        assert w.shape == (N, 1) and all(bool(torch.isfinite(t).all()) for t in (p, S, P, w, *c, *f, g)), (N, E)
+        s = w[:, 0]
+        assert bool((s[:8] == 1).all()) and bool((s[24:] == 1).all())
+        if N > 24:
+            assert float(s[8:24].min()) >= 0.5 and float(s[8:24].max()) <= 2.0 and float((s[8:24] - 1).abs().max()) > 0.05
+        leaves = [t.clone().requires_grad_(True) for t in (p, S, P, w)]
+        xyz = R.deform_points(*leaves, c, f)
+        grads = torch.autograd.grad(xyz, leaves, g)
+        assert bool(torch.isfinite(xyz).all()) and all(bool(torch.isfinite(t).all()) and float(t.abs().max()) > 0 for t in grads)
+
+
 def test_gradcheck_of_the_restatement():
     p, S, P, w, c, f, _ = R.recipe(5, 4, 3, seed=3)
     leaves = [t.clone().requires_grad_(True) for t in (p, S, P, w)]
@@ -105,6 +137,16 @@ def test_lbs_terms_restatement():
     idx = torch.tensor([3, 3, 0, 6])
     out = R.lbs_terms(idx, gw[idx] + 1.0, gP[idx] * 0 + gP[idx] - 2.0, gS[idx], gw, gP, gS)
     assert torch.allclose(out, torch.tensor([1.0, 4.0, 0.0]))
+
+
+def test_the_counted_roundings_of_the_lbs_terms():
+    """The formula the GPU test bounds the three losses with (tests/test_gpu_mono.py), on the sizes its docstring names."""
+    from tests.test_gpu_mono import TERMS_GRID_CAP, _terms_roundings
+    assert TERMS_GRID_CAP == 16384
+    assert _terms_roundings(1027, 50, 6) == [1 + 1 + 1 + 18, 7 + 1 + 1 + 18, 10 + 1 + 1 + 18]
+    assert _terms_roundings(TERMS_GRID_CAP, 50, 6)[2] == 10 + 1 + 4 + 18 and _terms_roundings(TERMS_GRID_CAP + 1, 64, 8)[2] == 12 + 2 + 4 + 18
+    assert _terms_roundings(3 * TERMS_GRID_CAP + 5, 50, 6) == [1 + 4 + 4 + 18, 7 + 4 + 4 + 18, 36]
+    assert _terms_roundings(1027, 1, 1) == [21, 27, 21]
 
 
 def test_reference_lbs_weights():
