@@ -140,7 +140,7 @@ EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile
            "fr_binning_bytes", "fr_planes_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
            "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_huber_workspace_bytes", "fr_huber_loss_grad", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_mesh_terms_workspace_bytes", "fr_mesh_terms", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
            "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_bind_backward_deform", "fr_phong_frame", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward",
-           "fr_point_lbs_forward", "fr_point_lbs_backward", "fr_nearest_vertex", "fr_lbs_terms_workspace_bytes", "fr_lbs_terms"]
+           "fr_point_lbs_forward", "fr_point_lbs_backward", "fr_point_lbs_pose_workspace_bytes", "fr_point_lbs_backward_pose", "fr_nearest_vertex", "fr_lbs_terms_workspace_bytes", "fr_lbs_terms"]
 
 
 def build(force: bool = False) -> str:
@@ -275,6 +275,10 @@ def lib():
     L.fr_point_lbs_forward.restype = C.c_int
     L.fr_point_lbs_backward.argtypes = [C.POINTER(fr_point_lbs), _fp, _fp, _fp, _fp, _fp, C.c_void_p]
     L.fr_point_lbs_backward.restype = C.c_int
+    L.fr_point_lbs_pose_workspace_bytes.argtypes = []
+    L.fr_point_lbs_pose_workspace_bytes.restype = C.c_size_t
+    L.fr_point_lbs_backward_pose.argtypes = [C.POINTER(fr_point_lbs), _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p]
+    L.fr_point_lbs_backward_pose.restype = C.c_int
     L.fr_nearest_vertex.argtypes = [C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, C.c_void_p]
     L.fr_nearest_vertex.restype = C.c_int
     L.fr_lbs_terms_workspace_bytes.argtypes = []

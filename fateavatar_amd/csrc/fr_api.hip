@@ -672,6 +672,18 @@ int fr_point_lbs_backward(const fr_point_lbs* lbs, const float* g_xyz, float* d_
     return launch_point_lbs_backward(*lbs, g_xyz, d_points, d_shapedirs, d_posedirs, d_weights, static_cast<hipStream_t>(stream));
 }
 
+size_t fr_point_lbs_pose_workspace_bytes(void) { return point_lbs_pose_workspace_bytes(); }
+
+int fr_point_lbs_backward_pose(const fr_point_lbs* lbs, const float* g_xyz, float* d_betas, float* d_pose_feature, float* d_transforms,
+                               void* workspace, void* stream)
+{
+    if (const char* why = point_lbs_invalid(lbs)) return fail_msg(FR_ERR_INVALID_ARGUMENT, why);
+    if (lbs->N > 0 && !g_xyz) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_point_lbs_backward_pose: null g_xyz");
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u))
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_point_lbs_backward_pose: null workspace, or one that is not 16-byte aligned");
+    return launch_point_lbs_backward_pose(*lbs, g_xyz, d_betas, d_pose_feature, d_transforms, workspace, static_cast<hipStream_t>(stream));
+}
+
 int fr_nearest_vertex(int32_t N, const float* points, int32_t V, const float* verts, int32_t* index, float* dist2, void* stream)
 {
     if (N < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_nearest_vertex: negative N");

@@ -495,6 +495,9 @@ int launch_mesh_terms(const fr_mesh_terms_config& cfg, int V, const float* verts
 int launch_point_lbs_forward(const fr_point_lbs& lbs, float* xyz, hipStream_t s);
 int launch_point_lbs_backward(const fr_point_lbs& lbs, const float* g_xyz, float* d_points, float* d_shapedirs, float* d_posedirs,
                               float* d_weights, hipStream_t s);
+size_t point_lbs_pose_workspace_bytes();
+int launch_point_lbs_backward_pose(const fr_point_lbs& lbs, const float* g_xyz, float* d_betas, float* d_pose_feature,
+                                   float* d_transforms, void* workspace, hipStream_t s);
 int launch_nearest_vertex(int N, const float* points, int V, const float* verts, int* index, float* dist2, hipStream_t s);
 size_t lbs_terms_workspace_bytes();
 int launch_lbs_terms(const fr_lbs_terms_config& cfg, int N, int V, int E, int J, const int* index, const float* weights,

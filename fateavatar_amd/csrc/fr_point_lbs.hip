@@ -1,5 +1,5 @@
-// MonoGaussianAvatar's per-point passes (include/fr_rasterizer.h): fr_point_lbs_forward / _backward, fr_nearest_vertex and
-// fr_lbs_terms.
+// MonoGaussianAvatar's per-point passes (include/fr_rasterizer.h): fr_point_lbs_forward / _backward / _backward_pose,
+// fr_nearest_vertex and fr_lbs_terms.
 //
 // reference: FLAME.forward_pts (flame/FLAME.py:207-237) over flame/lbs.py:103-188 — per point an expression basis S [3,E], a
 // pose-corrective basis P [36,3] and skinning weights w [J] the deformer MLP predicted:
@@ -24,6 +24,24 @@
 //     u3 = R^-T d_x,  u4 = -(t . u3) / s   (u = T_c^-T (d_x, 0))                        d_p = u3
 //     d_w_j = g . (R_j x + t_j) - (u3 . (R^c_j z3 + t^c_j z4) + u4 z4)
 // d_weights is the only output that needs x, i.e. S and P again: a backward without it reads 36 B per point.
+//
+// fr_point_lbs_backward_pose (k_point_lbs_pose_bwd): the gradient to the FRAME's pose state is a reduction over the points,
+//     d_beta[l] = sum_n sum_k S_n[k,l] d_x_n[k]      d_phi[i] = sum_n sum_k P_n[i,k] d_x_n[k]      d_A[j,r,c] = sum_n w_nj g_n[r] (x_n, 1)[c]
+// (E + 36 + 12 J sums; the bones' last rows are constants: 0).  The same sixteen-lane groups, lbs_stage and lbs_point; d_x needs
+// w, p and g only, so ONE pass over the point's S and P rows feeds both the blendshape offset (lbs_offset's sums in its order:
+// x has the forward's bits) and the running sums a lane keeps for the slots it owns: columns sub, sub + 16, ... of S, elements
+// sub, sub + 16, ... of P (folded three to a pose feature at the very end) and, in lane j < J, the twelve products of bone j.
+// A dead group adds exact zeros and stays with its wave.  After the sweep: the wave's four groups in index order (shuffles), the
+// workgroup's waves in index order (LDS), one row of 272 partials per workgroup stored write-through, and the workgroup that
+// finishes last (last_workgroup_of, as k_lbs_terms) adds the rows up in workgroup-index order (fifteen runs of consecutive rows
+// side by side, then the runs in order), writes the three outputs and leaves the workspace zeroed: no float atomics, the same
+// bits on every launch.  Workgroups of 1 024 threads, at most one per CU (256): the last workgroup's serial read grows with the
+// number of rows, not with N.  Compiler (gfx950): 123 VGPRs, no scratch, 18 580 B of LDS, four waves per SIMD = the one
+// resident workgroup.  Measured on the MI355X at N = 100 000, E = 50, J = 6 (profiles/r19_mono_pose.md): 0.072 ms a launch,
+// i.e. the 1 080 B a point's S, P, w, p and g rows hold are read at 1.50 TB/s = 24 % of the achievable HBM rate, 45 x faster
+// than the float32 torch backward to the frame state.  The same code as 512 workgroups of 256 threads (two waves per SIMD, 512
+// rows for the last workgroup) took 0.121 ms: what bounds the launch is memory latency at the waves in flight its registers
+// allow (and the last workgroup's serial pass), not the HBM rate; how the 0.072 ms split between the two was not measured.
 //
 // fr_nearest_vertex: one lane per point against the vertices in LDS (struct of arrays, 4 096 vertices = 48 KB at a time, every
 // lane of a wave reads the same address: broadcast reads, four vertices per ds_read_b128), strict `<` in ascending order.
@@ -262,6 +280,185 @@ int launch_point_lbs_backward(const fr_point_lbs& d, const float* g_xyz, float* 
     LbsArgs a = lbs_args(d);
     a.g = g_xyz, a.d_points = d_points, a.d_shapedirs = d_shapedirs, a.d_posedirs = d_posedirs, a.d_weights = d_weights;
     hipLaunchKernelGGL(k_point_lbs_bwd, dim3(lbs_blocks(d.N)), dim3(kLbsThreads), 0, s, a);
+    FR_HIP(hipGetLastError());
+    return FR_OK;
+}
+
+// ---- gradients to the frame's pose state: a reduction over the points
+// (workgroups of 1 024 threads, one per CU: the last workgroup reads one row of partials per workgroup, and four waves per SIMD
+// from 256 rows cost it a quarter of what they cost from 1 024 workgroups of 256 threads)
+constexpr unsigned kPoseThreads = 1024, kPoseWaves = kPoseThreads / 64;
+constexpr unsigned kPoseMaxBlocks = 256;
+constexpr unsigned kPoseS = (FR_LBS_MAX_E + kLbsGroup - 1) / kLbsGroup;      // 4 columns of S per lane
+constexpr unsigned kPoseP = (kLbsPose * 3 + kLbsGroup - 1) / kLbsGroup;      // 7 elements of P per lane
+constexpr unsigned kPoseAcc = kPoseS + kPoseP + 12;                          // a lane's running sums
+constexpr unsigned kPoseOffP = kPoseS * kLbsGroup;                           // slot of P's element 0 (64)
+constexpr unsigned kPoseOffT = kPoseOffP + kPoseP * kLbsGroup;               // slot of the bones' sums (176), [12][FR_LBS_MAX_J]
+constexpr unsigned kPoseSlots = kPoseOffT + 12 * FR_LBS_MAX_J;               // 272 floats = 68 float4 per workgroup
+constexpr unsigned kPoseChunks = kPoseThreads / (kPoseSlots / 4);            // 15 runs of rows in the last workgroup
+static_assert(kPoseSlots % 4 == 0 && kPoseChunks >= 1 && kPoseChunks < kPoseWaves, "one float4 column per thread of the last "
+              "workgroup; the runs' sums and their total share the waves' rows of LDS");
+static_assert(((kDoneGroups + 1) * kDoneStride * sizeof(unsigned)) % 16 == 0, "the partials are read sixteen bytes at a time");
+
+struct LbsPoseOut {
+    float *d_betas, *d_phi, *d_A;   // [E], [36], [J,16]; any may be null
+    float* partial;                 // [kPoseMaxBlocks][kPoseSlots]
+    unsigned* counter;
+};
+
+// where running sum `acc` of lane `sub` lives in a row of partials (sub < FR_LBS_MAX_J for the bones' sums)
+__device__ __forceinline__ unsigned pose_slot(unsigned acc, unsigned sub)
+{
+    return acc < kPoseS + kPoseP ? acc * kLbsGroup + sub : kPoseOffT + (acc - (kPoseS + kPoseP)) * FR_LBS_MAX_J + sub;
+}
+
+__global__ void __launch_bounds__(kPoseThreads) k_point_lbs_pose_bwd(LbsArgs a, LbsPoseOut out)
+{
+    __shared__ LbsShared s;
+    __shared__ float s_red[kPoseWaves][kPoseSlots];
+    __shared__ bool s_last;
+    lbs_stage(a, s);
+    const unsigned sub = threadIdx.x & (kLbsGroup - 1);
+    const unsigned group = (blockIdx.x * blockDim.x + threadIdx.x) / kLbsGroup, n_groups = gridDim.x * blockDim.x / kLbsGroup;
+    const unsigned E = (unsigned)a.E;
+    float acc[kPoseAcc];
+#pragma unroll
+    for (unsigned t = 0; t < kPoseAcc; t++) acc[t] = 0.f;
+    for (unsigned base = 0; base < (unsigned)a.N; base += n_groups) {
+        const size_t i = (size_t)base + group;
+        const bool live = i < (size_t)a.N;
+        float wl, p[3];
+        lbs_load_point(a, i, sub, live, wl, p);
+        LbsPoint q;
+        lbs_point(s, wl, a.J, p, q);
+        const float g0 = live ? a.g[i * 3u] : 0.f, g1 = live ? a.g[i * 3u + 1] : 0.f, g2 = live ? a.g[i * 3u + 2] : 0.f;
+        const float dx0 = (q.T[0] * g0 + q.T[4] * g1) + q.T[8] * g2;
+        const float dx1 = (q.T[1] * g0 + q.T[5] * g1) + q.T[9] * g2;
+        const float dx2 = (q.T[2] * g0 + q.T[6] * g1) + q.T[10] * g2;
+        // ONE pass over the point's S and P rows serves the blendshape offset (lbs_offset's sums, in its order: x has the
+        // forward's bits) and the sums of d_betas / d_pose_feature, which need d_x but not x
+        float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+        if (live) {
+            const float* __restrict__ S = a.shapedirs + i * 3u * (size_t)E;
+            const float* __restrict__ P = a.posedirs + i * (size_t)(kLbsPose * 3);
+#pragma unroll
+            for (unsigned t = 0; t < kPoseS; t++) {
+                const unsigned l = sub + t * kLbsGroup;
+                if (l < E) {
+                    const float b = s.dbeta[l], S0 = S[l], S1 = S[E + l], S2 = S[2u * E + l];
+                    o0 += S0 * b, o1 += S1 * b, o2 += S2 * b;
+                    acc[t] += (S0 * dx0 + S1 * dx1) + S2 * dx2;
+                }
+            }
+#pragma unroll
+            for (unsigned t = 0; t < kPoseP; t++) {
+                const unsigned m = sub + t * kLbsGroup;
+                if (m < (unsigned)(kLbsPose * 3)) {
+                    const float Pm = P[m], v = Pm * s.dphi[m / 3u];
+                    const unsigned k = m % 3u;
+                    o0 += k == 0u ? v : 0.f, o1 += k == 1u ? v : 0.f, o2 += k == 2u ? v : 0.f;
+                    acc[kPoseS + t] += Pm * (k == 0u ? dx0 : (k == 1u ? dx1 : dx2));
+                }
+            }
+        }
+        o0 = group_sum(o0), o1 = group_sum(o1), o2 = group_sum(o2);
+        // (the sweep's last shuffle is behind us; a dead group adds nothing: exact zeros)
+        if (live && sub < (unsigned)a.J) {
+            const float x0 = q.z[0] + o0, x1 = q.z[1] + o1, x2 = q.z[2] + o2;
+            const float wg[3] = {wl * g0, wl * g1, wl * g2};
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                float* t = acc + kPoseS + kPoseP + r * 4;
+                t[0] += wg[r] * x0, t[1] += wg[r] * x1, t[2] += wg[r] * x2, t[3] += wg[r];
+            }
+        }
+    }
+    // the wave's four groups in index order, then the workgroup's waves through LDS in index order
+    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+#pragma unroll
+    for (unsigned t = 0; t < kPoseAcc; t++) {
+        const float v0 = __shfl(acc[t], (int)sub), v1 = __shfl(acc[t], (int)(sub + 16u)), v2 = __shfl(acc[t], (int)(sub + 32u)),
+                    v3 = __shfl(acc[t], (int)(sub + 48u));
+        const float v = ((v0 + v1) + v2) + v3;
+        if (lane < kLbsGroup && (t < kPoseS + kPoseP || sub < (unsigned)FR_LBS_MAX_J)) s_red[wave][pose_slot(t, sub)] = v;
+    }
+    __syncthreads();
+    // write-through stores, every storing wave waits for its own, then ONE thread counts the workgroup in (as k_lbs_terms)
+    float* const row = out.partial + (size_t)blockIdx.x * kPoseSlots;
+    if (threadIdx.x < kPoseSlots) {
+        float v = s_red[0][threadIdx.x];
+#pragma unroll
+        for (unsigned w = 1; w < kPoseWaves; w++) v += s_red[w][threadIdx.x];
+        __hip_atomic_store(row + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const bool last = last_workgroup_of(out.counter, blockIdx.x, gridDim.x);
+        if (last) {
+            // the last workgroup reads the others' rows with plain loads: drop this CU's L1 lines first, and hold the barrier for it
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        s_last = last;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    // rows in workgroup-index order: kPoseChunks runs of consecutive rows side by side, one float4 column per thread, then the
+    // runs in order; every row is left zeroed
+    constexpr unsigned cols = kPoseSlots / 4;
+    const unsigned chunk = threadIdx.x / cols, col = threadIdx.x % cols;
+    const unsigned per = (gridDim.x + kPoseChunks - 1) / kPoseChunks;
+    if (chunk < kPoseChunks) {
+        const unsigned b0 = chunk * per < gridDim.x ? chunk * per : gridDim.x, b1 = b0 + per < gridDim.x ? b0 + per : gridDim.x;
+        float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 8
+        for (unsigned b = b0; b < b1; b++) {
+            float* at = out.partial + (size_t)b * kPoseSlots + col * 4u;
+            const float4 v = *reinterpret_cast<const float4*>(at);
+            tot.x += v.x, tot.y += v.y, tot.z += v.z, tot.w += v.w;
+#pragma unroll
+            for (int k = 0; k < 4; k++) __hip_atomic_store(at + k, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        float* dst = &s_red[chunk][col * 4u];           // (the waves' rows: their earlier content has been read)
+        dst[0] = tot.x, dst[1] = tot.y, dst[2] = tot.z, dst[3] = tot.w;
+    }
+    __syncthreads();
+    if (threadIdx.x < kPoseSlots) {
+        float v = s_red[0][threadIdx.x];
+#pragma unroll
+        for (unsigned c = 1; c < kPoseChunks; c++) v += s_red[c][threadIdx.x];
+        s_red[kPoseChunks][threadIdx.x] = v;
+    }
+    __syncthreads();
+    const float* fin = s_red[kPoseChunks];
+    const unsigned t = threadIdx.x;
+    if (out.d_betas && t < E) out.d_betas[t] = fin[t];
+    if (out.d_phi && t < (unsigned)kLbsPose) out.d_phi[t] = (fin[kPoseOffP + 3u * t] + fin[kPoseOffP + 3u * t + 1u]) + fin[kPoseOffP + 3u * t + 2u];
+    if (out.d_A && t < (unsigned)a.J * 16u) {
+        const unsigned j = t / 16u, e = t % 16u;
+        out.d_A[t] = e < 12u ? fin[kPoseOffT + e * FR_LBS_MAX_J + j] : 0.f;      // (the bones' last rows are constants)
+    }
+}
+
+size_t point_lbs_pose_workspace_bytes()
+{
+    return (kDoneGroups + 1) * kDoneStride * sizeof(unsigned) + (size_t)kPoseMaxBlocks * kPoseSlots * sizeof(float);
+}
+
+int launch_point_lbs_backward_pose(const fr_point_lbs& d, const float* g_xyz, float* d_betas, float* d_pose_feature, float* d_transforms,
+                                   void* workspace, hipStream_t s)
+{
+    if (d.N <= 0) return FR_OK;
+    LbsArgs a = lbs_args(d);
+    a.g = g_xyz;
+    LbsPoseOut out;
+    out.d_betas = d_betas, out.d_phi = d_pose_feature, out.d_A = d_transforms;
+    out.counter = static_cast<unsigned*>(workspace);
+    out.partial = reinterpret_cast<float*>(out.counter + (kDoneGroups + 1) * kDoneStride);
+    constexpr unsigned per_block = kPoseThreads / kLbsGroup;
+    const unsigned want = ((unsigned)d.N + per_block - 1u) / per_block, blocks = want > kPoseMaxBlocks ? kPoseMaxBlocks : want;
+    hipLaunchKernelGGL(k_point_lbs_pose_bwd, dim3(blocks), dim3(kPoseThreads), 0, s, a, out);
     FR_HIP(hipGetLastError());
     return FR_OK;
 }

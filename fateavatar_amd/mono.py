@@ -6,7 +6,10 @@ their own, `fateavatar_amd/csrc/fr_point_lbs.hip`.
 reference (model/baseline/monogaussianavatar.py, flame/FLAME.py, flame/lbs.py, train/loss.py):
   * the deformation — `FLAME.forward_pts` (flame/FLAME.py:207-237) over flame/lbs.py:103-188, called per point under
     vmap(jacfwd(...)) (:345-359) with the expression vector, the pose feature and the [J,4,4] transforms expanded to one copy per
-    point (:180-186) and a batched torch.inverse (flame/lbs.py:174): `deform_points`, one launch per direction
+    point (:180-186) and a batched torch.inverse (flame/lbs.py:174): `deform_points`, one launch per direction, and with
+    `frame_grad=True` one more that sums the gradients to the FRAME's pose state over the points
+    (`fr_point_lbs_backward_pose`): what the reference's tracking optimisation of `expression` and `flame_pose`
+    (train/base.py:113-156, :198-228) receives through the caller's FLAME
   * the nearest FLAME vertex of every canonical point — pytorch3d's knn_points(p, verts, K=1) (train/loss.py:231-233):
     `nearest_vertex`
   * the three blendshape terms — get_gt_blendshape / get_lbs_loss (train/loss.py:418-445, :472-515), three [N, .] gathers and
@@ -16,8 +19,8 @@ reference (model/baseline/monogaussianavatar.py, flame/FLAME.py, flame/lbs.py, t
   * the point cloud and its schedule (PointCloud :524-565, `_register_points` :132-148, `_upsample_points` :430-467): `MonoPoints`
 The MLPs (geometry, deformer, rendering and Gaussian networks) and FLAME stay the caller's stock PyTorch, as in flash.py.
 
-NOT here: gradients to the pose states (the reference's tracking optimisation of expression and pose through this
-path), the VGG term, a captured whole step, data-parallel runs.
+NOT here: the canonical pose state's gradient (a constant buffer in the reference), camera-pose gradients, the VGG
+term, a captured whole step, data-parallel runs.
 """
 from __future__ import annotations
 
@@ -61,8 +64,41 @@ def _one_device(who, *tensors):
 
 def _no_pose_gradient(state, which):
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in state):
-        raise RuntimeError(f"deform_points: the {which} pose state requires grad, and the pose states get no gradient here (the "
-                           "tracking optimisation of expression and pose is not built, DESIGN.md); hand it detached tensors")
+        why = "it is a constant buffer in the reference" if which == "canonical" else \
+            "the frame's state gets one only from deform_points(..., frame_grad=True)"
+        raise RuntimeError(f"deform_points: the {which} pose state requires grad, and the pose states get no gradient here ({why}); "
+                           "hand it detached tensors")
+
+
+_pose_workspace = {}    # (device index, stream handle) -> zeroed scratch of fr_point_lbs_backward_pose
+
+
+def pose_workspace(dev) -> torch.Tensor:
+    """A fresh zeroed workspace for `deform_points(..., frame_grad=True, workspace=)`."""
+    if not isinstance(dev, (torch.device, str, int)):
+        raise RuntimeError(f"pose_workspace: a device, not {type(dev).__name__}")
+    dev = torch.device("cuda", dev) if isinstance(dev, int) else torch.device(dev)
+    if dev.type != "cuda":
+        raise RuntimeError(f"pose_workspace: a HIP device, not {dev} (there is no CPU path)")
+    return torch.zeros((_lib.lib().fr_point_lbs_pose_workspace_bytes(),), dtype=torch.uint8, device=dev)
+
+
+def _pose_workspace_for(dev, workspace):
+    """`workspace` checked, or the one kept for (device, current stream): made on the first call, which must not be captured."""
+    who = "deform_points"
+    if workspace is not None:
+        if not (workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+                and workspace.numel() >= _lib.lib().fr_point_lbs_pose_workspace_bytes()):
+            raise RuntimeError(f"{who}: workspace must come from pose_workspace() on the points' device")
+        return workspace
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _pose_workspace.get(key)
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
+            raise RuntimeError(f"{who}: first call with frame_grad=True on this stream happens inside a graph capture; call it once "
+                               "eagerly on the stream first, or pass workspace=pose_workspace(device)")
+        ws = _pose_workspace[key] = pose_workspace(dev)
+    return ws
 
 
 def _pose(state, E, J, which):
@@ -83,10 +119,10 @@ def _describe(points, S, P, w, canonical, frame):
 
 
 class _Deform(torch.autograd.Function):
-    """fr_point_lbs_forward / fr_point_lbs_backward."""
+    """fr_point_lbs_forward / fr_point_lbs_backward, and fr_point_lbs_backward_pose where the frame's state asks for it."""
 
     @staticmethod
-    def forward(ctx, points, shapedirs, posedirs, weights, *pose):
+    def forward(ctx, workspace, points, shapedirs, posedirs, weights, *pose):
         who = "deform_points"
         points, S, P, w = (_f32(t, n, who) for t, n in zip((points, shapedirs, posedirs, weights),
                                                             ("points", "shapedirs", "posedirs", "lbs_weights")))
@@ -99,6 +135,9 @@ class _Deform(torch.autograd.Function):
             raise RuntimeError(f"{who}: E in 1 .. {_lib.FR_LBS_MAX_E} and J in 1 .. {_lib.FR_LBS_MAX_J}, not E = {E}, J = {J}")
         canonical, frame = _pose(pose[:3], E, J, "canonical"), _pose(pose[3:], E, J, "frame")
         dev = _one_device(who, points, S, P, w, *canonical, *frame)
+        # (the workspace is settled here, where the caller called, not on the backward's thread)
+        ctx.workspace = _pose_workspace_for(dev, workspace) if any(ctx.needs_input_grad[8:11]) else None
+        ctx.frame_shapes = tuple(tuple(t.shape) for t in pose[3:])
         xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
         d = _describe(points, S, P, w, canonical, frame)
         _lib.launch("fr_point_lbs_forward", dev, C.byref(d), xyz.data_ptr())
@@ -112,28 +151,47 @@ class _Deform(torch.autograd.Function):
         dev = points.device
         g_xyz = g_xyz.contiguous().float()
         outs = []
-        for need, slot, like in zip(ctx.needs_input_grad[:4], ctx.grad_slots, (points, S, P, w)):
+        for need, slot, like in zip(ctx.needs_input_grad[1:5], ctx.grad_slots, (points, S, P, w)):
             claimed = slot.claim()[0] if need and slot is not None else None
             outs.append(_grad_buffer(need, claimed, tuple(like.shape), dev))
         p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
         d = _describe(points, S, P, w, pose[:3], pose[3:])
         _lib.launch("fr_point_lbs_backward", dev, C.byref(d), g_xyz.data_ptr() if g_xyz.numel() else None, *[p(t) for t in outs])
-        return (*outs, None, None, None, None, None, None)
+        frame = [None, None, None]
+        if ctx.workspace is not None:
+            make = torch.empty if points.shape[0] else torch.zeros      # (N == 0 launches nothing: sums over no points)
+            frame = [make(shape, dtype=torch.float32, device=dev) if need else None
+                     for need, shape in zip(ctx.needs_input_grad[8:11], ctx.frame_shapes)]
+            _lib.launch("fr_point_lbs_backward_pose", dev, C.byref(d), g_xyz.data_ptr() if g_xyz.numel() else None,
+                        *[t.data_ptr() if t is not None else None for t in frame], ctx.workspace.data_ptr())
+        return (None, *outs, None, None, None, *frame)
 
 
-def deform_points(points, shapedirs, posedirs, lbs_weights, canonical: PoseState, frame: PoseState) -> torch.Tensor:
+def deform_points(points, shapedirs, posedirs, lbs_weights, canonical: PoseState, frame: PoseState, *, frame_grad: bool = False,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`FLAME.forward_pts` (flame/FLAME.py:207-237) for N points in one launch: points [N,3] (canonical), shapedirs [N,3,E],
     posedirs [N,36,3], lbs_weights [N,J] (the deformer's outputs for the points), and the canonical and the frame's `PoseState`.
     Per point, with h = (p, 1):
         T_c = sum_j w_j A^c_j,  z = T_c^-1 h,  x = z[:3] - S beta_c - P^T phi_c + S beta + P^T phi,  xyz = (sum_j w_j A_j (x, 1))[:3]
     Returns xyz [N,3].  Differentiable w.r.t. the first four arguments (`GradOut` slots on them are honoured); a pose state that
-    requires grad is refused.  The weights are taken as given (they need not sum to 1).  There is no CPU path."""
+    requires grad is refused, unless `frame_grad=True`: then the FRAME's betas, pose_feature and transforms may require grad, and
+    the backward makes one more launch (only if one of them does) that sums, with g = dL/dxyz, T = sum_j w_j A_j, d_x = T[:3,:3]^T g,
+        d_betas[l] = sum_n sum_k S_n[k,l] d_x_n[k],  d_pose_feature[i] = sum_n sum_k P_n[i,k] d_x_n[k],
+        d_transforms[j,r,c] = sum_n w_nj g_n[r] (x_n, 1)[c]   (rows 0 .. 2; the bones' constant last rows get 0)
+    in the inputs' shapes (N == 0: zeros): what a trainer's `expression` / `flame_pose` receive through its own FLAME.  The four
+    per-point gradients keep their bits either way.  The canonical state is refused in both modes (a constant buffer in the
+    reference).  `workspace`: that launch's scratch from `pose_workspace()`; by default one is kept per (device, current
+    stream) — launches that may overlap must not share one.  The weights are taken as given (they need not sum to 1).  There is
+    no CPU path."""
     for state in (canonical, frame):
         if not isinstance(state, (tuple, list)) or len(state) != 3:
             raise RuntimeError("deform_points: a pose state is (betas, pose_feature, transforms)")
     _no_pose_gradient(canonical, "canonical")
-    _no_pose_gradient(frame, "frame")
-    return _Deform.apply(points, shapedirs, posedirs, lbs_weights, *canonical, *frame)
+    if not frame_grad:
+        _no_pose_gradient(frame, "frame")
+    if workspace is not None and not isinstance(workspace, torch.Tensor):
+        raise RuntimeError("deform_points: workspace must come from pose_workspace() on the points' device")
+    return _Deform.apply(workspace, points, shapedirs, posedirs, lbs_weights, *canonical, *frame)
 
 
 def nearest_vertex(points: torch.Tensor, verts: torch.Tensor):
@@ -347,4 +405,4 @@ class MonoPoints:
 
 
 __all__ = ["LbsWeights", "MonoPoints", "POSE_FEATURES", "PoseState", "deform_points", "lbs_terms_and_grad", "lbs_terms_workspace",
-           "nearest_vertex", "radius_factor", "reference_lbs_weights", "render_points", "splat_attributes", "upsample_target"]
+           "nearest_vertex", "pose_workspace", "radius_factor", "reference_lbs_weights", "render_points", "splat_attributes", "upsample_target"]

@@ -708,6 +708,24 @@ int fr_point_lbs_forward(const fr_point_lbs* lbs, float* xyz, void* hip_stream);
 int fr_point_lbs_backward(const fr_point_lbs* lbs, const float* g_xyz, float* d_points, float* d_shapedirs, float* d_posedirs,
                           float* d_weights, void* hip_stream);
 
+/* ---- the gradient of the same deformation to the FRAME's pose state (the reference's tracking optimisation of `expression`
+ * and `flame_pose` reaches the image only through it, model/baseline/monogaussianavatar.py:162-186): one launch that sums over
+ * the points, with g = g_xyz, T = sum_j w_j A_j, d_x = T[:3,:3]^T g and x as above,
+ *   d_betas[l]          = sum_n sum_k S_n[k,l] d_x_n[k]                       (E sums)
+ *   d_pose_feature[i]   = sum_n sum_k P_n[i,k] d_x_n[k]                       (36 sums)
+ *   d_transforms[j,r,c] = sum_n w_nj g_n[r] (x_n, 1)[c],  r < 3, c < 4        (12 J sums; the last row of every bone is written 0)
+ * PRECONDITION as above: every bone matrix has the last row (0, 0, 0, 1) — it is a constant, so its gradient is 0 and nothing
+ * else is computed for it.  The canonical state gets no gradient (it is a constant buffer in the reference).  Any of the three
+ * outputs may be NULL, what the others receive does not depend on which are, and EVERY element of a non-NULL output is
+ * written.  Sums as fr_lbs_terms: per-workgroup partials added up in workgroup-index order by the workgroup that finishes
+ * last, no float atomics, the same bits on every launch; it can be captured in a graph.  `workspace`:
+ * fr_point_lbs_pose_workspace_bytes() bytes, 16-byte aligned, zeroed ONCE by the caller, left zeroed, not shared by launches
+ * that can overlap.  N == 0 launches nothing (the outputs are left as they are).  The descriptor is checked as by
+ * fr_point_lbs_backward; a NULL g_xyz with N > 0 or a NULL workspace is FR_ERR_INVALID_ARGUMENT. */
+size_t fr_point_lbs_pose_workspace_bytes(void);
+int fr_point_lbs_backward_pose(const fr_point_lbs* lbs, const float* g_xyz, float* d_betas, float* d_pose_feature,
+                               float* d_transforms, void* workspace, void* hip_stream);
+
 /* ---- index[i] = the vertex nearest to points[i], brute force against V <= FR_NEAREST_MAX_V vertices held in LDS (reference:
  * pytorch3d's knn_points(p, verts, K=1), train/loss.py:231-233).  The squared distance is (dx*dx + dy*dy) + dz*dz in float32
  * without contraction, d = point - vertex; ties go to the LOWEST index.  `dist2` [N] may be NULL.  V <= 0 or

@@ -44,6 +44,11 @@ deform_points -> splat_attributes -> render_points and trained on L1 + the three
 the template (nearest_vertex, lbs_terms_and_grad); torch.optim.Adam at 1e-4.  --torch-lbs: deformation, nearest vertex and the
 three terms as the stock-PyTorch restatement (tests/mono_ref.py) with autograd and torch gathers: the A/B.  Like --torch-binding,
 it imports the restatement from the test tree: run it from a checkout that has tests/, not from an installed package alone.
+    python tools/train_synthetic.py --mono --track [--torch-lbs]
+the same loop with the reference's tracking optimisation next to it (train/base.py:113-156): every frame's bones come from torch
+leaves (axis-angle per bone -> Rodrigues -> `transforms` and `pose_feature`) and an expression vector, which start perturbed from
+the truth and are trained by torch.optim.Adam(lr=5e-4) through deform_points(frame_grad=True); the JSON line gains the RMS error
+of the axis-angles and of the expression against the truth at the start and at the end.
 """
 import argparse
 import json
@@ -112,6 +117,9 @@ def main():
     ap.add_argument("--torch-lbs", action="store_true",
                     help="--mono: deformation, nearest vertex and blendshape terms in stock PyTorch (tests/mono_ref.py: needs the "
                          "checkout's tests/ next to tools/)")
+    ap.add_argument("--track", action="store_true",
+                    help="--mono: the frames' bones and expression are torch leaves (axis-angle per bone, an expression vector) that "
+                         "start perturbed and are trained by Adam at 5e-4 through deform_points(frame_grad=True)")
     ap.add_argument("--mouth-mask", action="store_true",
                     help="--flash: every frame brings a mouth mask (the Huber term's second sum, weight 40)")
     ap.add_argument("--regularisers", action="store_true",
@@ -140,8 +148,8 @@ def main():
         if a.image_loss or a.train_mesh or a.mesh_terms or a.fateavatar or a.rigged or a.splatting or a.flash:
             raise SystemExit("--mono: the image term is L1 and there are no mesh terms; one model per run")
         return main_mono(a, rank, world, dev)
-    if a.torch_lbs:
-        raise SystemExit("--torch-lbs goes with --mono")
+    if a.torch_lbs or a.track:
+        raise SystemExit("--torch-lbs and --track go with --mono")
     if a.flash:
         if a.image_loss or a.train_mesh or a.mesh_terms or a.fateavatar or a.rigged or a.splatting:
             raise SystemExit("--flash: FlashAvatar's step has its own image term (Huber) and no mesh terms; one model per run")
@@ -743,7 +751,32 @@ def main_mono(a, rank, world, dev):
 
     state = lambda angle, amp: mono.PoseState(*[t.to(dev) for t in (amp * rn(E), 0.3 * amp * rn(36), bones(angle))])  # noqa: E731
     canonical = state(0.02, 0.0)
-    frames = [state(0.12, 0.5) for _ in range(n_frames)]
+    if a.track:
+        # a frame's pose state as a differentiable function of its leaves: bone 0 the identity, bones 1 .. 4 give the pose feature
+        centre_d, eye3 = centre.to(dev), torch.eye(3, device=dev)
+        last_row = torch.tensor([0.0, 0.0, 0.0, 1.0], device=dev).expand(J, 1, 4)
+
+        def frame_state(r, expr, trans):
+            th = r.norm(dim=1).clamp_min(1e-12)
+            k, zero = r / th[:, None], torch.zeros_like(th)
+            K = torch.stack([zero, -k[:, 2], k[:, 1], k[:, 2], zero, -k[:, 0], -k[:, 1], k[:, 0], zero], 1).reshape(J, 3, 3)
+            R = eye3[None] + torch.sin(th)[:, None, None] * K + (1 - torch.cos(th))[:, None, None] * (K @ K)
+            R = torch.cat([eye3[None], R[1:]], 0)
+            t = torch.cat([torch.zeros((1, 3), device=dev), (trans + centre_d - R @ centre_d)[1:]], 0)
+            A = torch.cat([torch.cat([R, t[:, :, None]], 2), last_row], 1)
+            return mono.PoseState(expr, (R[1:5] - eye3[None]).reshape(36), A)
+
+        r_true, expr_true, trans = (t.to(dev) for t in (0.12 * rn(n_frames, J, 3), 0.5 * rn(n_frames, E), 0.004 * rn(n_frames, J, 3)))
+        with torch.no_grad():
+            frames = [mono.PoseState(*[t.contiguous() for t in frame_state(r_true[f], expr_true[f], trans[f])]) for f in range(n_frames)]
+        r_leaf = (r_true + 0.02 * rn(n_frames, J, 3).to(dev)).requires_grad_(True)
+        expr_leaf = (expr_true + 0.1 * rn(n_frames, E).to(dev)).requires_grad_(True)
+        opt_track = torch.optim.Adam([r_leaf, expr_leaf], lr=5e-4)       # tracking_lr (train/base.py:113-156)
+        rms = lambda d: float(d.detach().pow(2).mean().sqrt())  # noqa: E731
+        track_err = lambda: (rms((r_leaf - r_true)[:, 1:]), rms(expr_leaf - expr_true))  # noqa: E731
+        err_first = track_err()
+    else:
+        frames = [state(0.12, 0.5) for _ in range(n_frames)]
     # targets: the hidden points carry their nearest vertex' table rows and fixed attributes
     pts_true = torch.from_numpy(np.asarray(truth.means3D, np.float32)).to(dev)
     feats_true = torch.cat([rn(N, 3), rn(N, 3) - 1.0, rn(N, 4), rn(N, 1)], 1).to(dev)
@@ -763,13 +796,17 @@ def main_mono(a, rank, world, dev):
     def one_step(it):
         frame = frames[it % n_frames]
         opt.zero_grad(set_to_none=True)
+        if a.track:
+            opt_track.zero_grad(set_to_none=True)
+            f = it % n_frames
+            frame = frame_state(r_leaf[f], expr_leaf[f], trans[f])
         q = deformer((points.detach() - centre.to(dev)) / 0.15)
         S, P, w = 0.01 * q[:, :3 * E].reshape(N, 3, E), 0.01 * q[:, 3 * E:3 * E + 108].reshape(N, 36, 3), torch.softmax(q[:, 3 * E + 108:], 1)
         if a.torch_lbs:
             xyz = mono_ref.deform_points(points, S, P, w, canonical, frame)
         else:
             leaves = [t.detach().requires_grad_(True) for t in (S, P, w)]
-            xyz = mono.deform_points(points, *leaves, canonical, frame)
+            xyz = mono.deform_points(points, *leaves, canonical, frame, frame_grad=a.track)
         feats = geometry((points.detach() - centre.to(dev)) / 0.15)
         offs = gaussian((xyz.detach() - points.detach()) / 0.15)
         rgb, opacity, scales, rotations = mono.splat_attributes(feats, offs, radius, scene_scale=4.0)
@@ -787,6 +824,8 @@ def main_mono(a, rank, world, dev):
                                     leaves[0].grad, out=lbs)
             torch.autograd.backward([S, P, w], [t.grad for t in leaves])      # -> the deformer's weights: stock PyTorch
         opt.step()
+        if a.track:
+            opt_track.step()
         return loss.detach()
 
     losses, warm = [], 5
@@ -801,7 +840,15 @@ def main_mono(a, rank, world, dev):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     l = [float(x) for x in losses]
-    print(json.dumps({"metric": "MonoGaussianAvatar optimisation steps/s (three torch MLPs + LBS + render + L1 + blendshape terms + "
+    tracked = {}
+    if a.track:
+        err_last = track_err()
+        tracked = {"track": "axis-angle and expression leaves, torch.optim.Adam(lr=5e-4) through " +
+                            ("autograd" if a.torch_lbs else "fr_point_lbs_backward_pose"),
+                   "pose_err_first": err_first[0], "pose_err_last": err_last[0], "expression_err_first": err_first[1],
+                   "expression_err_last": err_last[1]}
+    print(json.dumps({**tracked,
+                      "metric": "MonoGaussianAvatar optimisation steps/s (three torch MLPs + LBS + render + L1 + blendshape terms + "
                                 "backward + Adam)",
                       "lbs": "stock PyTorch (tests/mono_ref.py)" if a.torch_lbs else "fused (fr_point_lbs, fr_nearest_vertex, fr_lbs_terms)",
                       "value": round(a.steps / dt, 2), "ms_per_step": round(dt / a.steps * 1e3, 3), "P": N, "V": V, "res": a.res,
