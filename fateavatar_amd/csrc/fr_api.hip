@@ -555,7 +555,7 @@ int fr_adam_step_multi(const fr_adam_config* cfg, float* param, const float* con
     return launch_adam(*cfg, param, grads, n_grads, exp_avg, exp_avg_sq, n, state, static_cast<hipStream_t>(stream));
 }
 
-size_t fr_l1_workspace_bytes(void) { return 17 * 128 + 1024 * sizeof(float); }
+size_t fr_l1_workspace_bytes(void) { return l1_workspace_bytes(); }
 
 int fr_l1_loss_grad(uint64_t n, const float* img, const float* gt, float* grad, float* loss, void* workspace, void* stream)
 {

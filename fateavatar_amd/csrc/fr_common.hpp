@@ -468,6 +468,7 @@ int launch_phong_fit(const float* verts, const float* normals, const int* faces,
                      hipStream_t s);
 int launch_adam(const fr_adam_config& cfg, float* param, const float* const* grad_bufs, int n_grads, float* exp_avg,
                 float* exp_avg_sq, unsigned long long n, float* state, hipStream_t s);
+size_t l1_workspace_bytes();
 int launch_l1_loss_grad_batch(int n_images, unsigned long long n, const float* const* img, const float* const* gt, float* const* grad,
                               float* const* loss, void* const* workspace, hipStream_t s);
 int launch_l1_loss_grad(unsigned long long n, const float* img, const float* gt, float* grad, float* loss, void* workspace,
@@ -550,6 +551,94 @@ __device__ __forceinline__ bool last_workgroup_of(unsigned* c, unsigned id, unsi
     const unsigned members = (count - g + groups - 1u) / groups;   // workgroups b with b % groups == g
     if (atomicInc(c + g * kDoneStride, members - 1u) != members - 1u) return false;  // (wraps back to 0)
     return atomicInc(c + kDoneGroups * kDoneStride, groups - 1u) == groups - 1u;
+}
+
+// A launch's sums without float atomics: per-workgroup partials, added up by the workgroup that finishes last.  Its workspace
+// is the counters of last_workgroup_of followed by the partials, all zero before the first launch.
+constexpr size_t done_workspace_bytes(size_t partial_floats)
+{
+    return (kDoneGroups + 1) * kDoneStride * sizeof(unsigned) + partial_floats * sizeof(float);
+}
+struct DoneWorkspace {
+    unsigned* counter;
+    float* partial;
+};
+static inline DoneWorkspace done_workspace(void* workspace)
+{
+    return DoneWorkspace{static_cast<unsigned*>(workspace), reinterpret_cast<float*>(static_cast<char*>(workspace) + done_workspace_bytes(0))};
+}
+// workgroups for `n` items at `per_block` items each: at least one, at most `cap` (the kernels stride over the rest)
+static inline unsigned capped_blocks(unsigned long long n, unsigned per_block, unsigned cap)
+{
+    const unsigned long long blocks = (n + per_block - 1) / per_block;
+    return blocks < 1 ? 1u : (blocks > cap ? cap : (unsigned)blocks);
+}
+
+// acc[k]: this thread's running sums.  Returns true in thread 0 of the workgroup that finishes last, with acc[k] = the launch's
+// totals; false everywhere else (acc is then undefined).  Call from every thread of a workgroup of kSumThreads, outside
+// divergent control flow.  `partial`: K rows `row_stride` floats apart, slot `id` of `count` (as last_workgroup_of) in each.
+// Every sum has a fixed shape — lanes by shuffle, the four waves as (0 + 1) + (2 + 3), the partials in workgroup-index order
+// dealt out to the last workgroup's threads, then that tree again — so a launch gives the same bits every time, whichever
+// workgroup happens to be last.  kZero: the partials are put back to zero (the counters always are).
+// Why the last workgroup sees the others' partials (cdna_hip_programming.md Guideline 16, the form without an acquire): a
+// partial is stored by ONE thread with a relaxed agent-scope atomic store, which writes through to where every compute unit
+// of the device reads; that thread's wave waits until the store has completed (s_waitcnt vmcnt(0)) and only then counts the
+// workgroup in, with an atomic of its own.  So whoever draws the last ticket drew it after every partial had landed.  The
+// reader, in turn, fetches EVERY partial with a relaxed agent-scope atomic load, which bypasses its compute unit's L1: no plain
+// load of a handed-off word, hence no stale line to invalidate and no acquire fence.  The verdict reaches the workgroup's other
+// threads through LDS and a barrier, which also keeps their loads behind the election.  A plain load added to the loop below
+// would need that fence (k_point_lbs_pose_bwd has one); a second storing wave would have to wait for its own stores too.
+constexpr unsigned kSumThreads = 256;
+template <int K, bool kZero = true>
+__device__ __forceinline__ bool sum_over_workgroups(float (&acc)[K], float* partial, unsigned row_stride, unsigned* counter,
+                                                    unsigned id, unsigned count)
+{
+    static_assert(K >= 1 && kSumThreads == 4 * kWave, "four waves: the (0 + 1) + (2 + 3) tree below");
+    __shared__ float s_red[K][kSumThreads / kWave];
+    __shared__ bool s_last;
+    const unsigned wave = threadIdx.x >> 6;
+    const bool lead = (threadIdx.x & 63) == 0;
+#pragma unroll
+    for (int k = 0; k < K; k++)
+        for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off);
+    if (lead) {
+#pragma unroll
+        for (int k = 0; k < K; k++) s_red[k][wave] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < K; k++)
+            __hip_atomic_store(partial + k * row_stride + id, (s_red[k][0] + s_red[k][1]) + (s_red[k][2] + s_red[k][3]),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        s_last = last_workgroup_of(counter, id, count);
+    }
+    __syncthreads();
+    if (!s_last) return false;
+#pragma unroll
+    for (int k = 0; k < K; k++) acc[k] = 0.f;
+    for (unsigned b = threadIdx.x; b < count; b += kSumThreads) {
+#pragma unroll
+        for (int k = 0; k < K; k++) acc[k] += __hip_atomic_load(partial + k * row_stride + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (kZero) {
+#pragma unroll
+            for (int k = 0; k < K; k++) __hip_atomic_store(partial + k * row_stride + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++)
+        for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off);
+    __syncthreads();   // (thread 0 has read the first round's s_red)
+    if (lead) {
+#pragma unroll
+        for (int k = 0; k < K; k++) s_red[k][wave] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return false;
+#pragma unroll
+    for (int k = 0; k < K; k++) acc[k] = (s_red[k][0] + s_red[k][1]) + (s_red[k][2] + s_red[k][3]);
+    return true;
 }
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 

@@ -20,7 +20,7 @@
 // writes row i (a read-modify-write, no float atomics).  (One lane per vertex is the same arithmetic as ONE dependent chain
 // of 6 x 32 gathers at a pole, and the launch waits for its slowest lane: 61 us on the MI355X against 100 ns of traffic.)
 // The two loss sums go through per-workgroup partials added up in index order by the workgroup that finishes last
-// (k_gaussian_regularise's pattern): the same bits on every launch and every replay.
+// (sum_over_workgroups, fr_common.hpp): the same bits on every launch and every replay.
 //
 // Roundings (what tests/test_gpu_mesh_terms.py holds the kernel to; eps = 2^-24, first order):
 //     r_k: d_j 1, the sum's deg - 1 additions, 1 / deg 1, the product 1, the subtraction 1         -> (deg_k + 3) eps M^r_k
@@ -37,7 +37,7 @@
 namespace fr {
 
 constexpr unsigned kMeshMaxBlocks = 1024;
-constexpr unsigned kMeshThreads = 256;
+constexpr unsigned kMeshThreads = kSumThreads;   // (sum_over_workgroups' workgroup)
 constexpr unsigned kMeshGroup = 8;           // lanes per vertex (a power of two that divides the wave)
 
 struct MeshTermsArgs {
@@ -89,13 +89,10 @@ __global__ void __launch_bounds__(kMeshThreads) k_mesh_terms(MeshTermsArgs a)
     const int* __restrict__ row_ptr = a.row_ptr;
     const int* __restrict__ col = a.col;
     float* const d_verts = a.d_verts;
-    float* const partial = a.partial;
-    __shared__ float s_red[2][kMeshThreads / 64];
-    __shared__ bool s_last;
     const unsigned sub = threadIdx.x & (kMeshGroup - 1);
     const unsigned group = (blockIdx.x * blockDim.x + threadIdx.x) / kMeshGroup, n_groups = gridDim.x * blockDim.x / kMeshGroup;
     const bool lap_grad = d_verts && a.c_lap != 0.f;
-    float acc_l = 0.f, acc_f = 0.f;
+    float acc[2] = {0.f, 0.f};   // laplacian, flame
     // (the trip count is the same for every lane of the launch: the shuffles below run with whole waves)
     for (unsigned base = 0; base < (unsigned)a.V; base += n_groups) {
         const unsigned i = base + group;
@@ -109,8 +106,8 @@ __global__ void __launch_bounds__(kMeshThreads) k_mesh_terms(MeshTermsArgs a)
                     d = mesh_diff(verts, orig, (int)i);
                     float inv_i;
                     const Vec3 r = mesh_row(verts, orig, row_ptr, col, (int)i, d, inv_i);
-                    acc_l += (r.x * r.x + r.y * r.y) + r.z * r.z;
-                    acc_f += (d.x * d.x + d.y * d.y) + d.z * d.z;
+                    acc[0] += (r.x * r.x + r.y * r.y) + r.z * r.z;
+                    acc[1] += (d.x * d.x + d.y * d.y) + d.z * d.z;
                     gx -= r.x, gy -= r.y, gz -= r.z;
                 } else {
                     const int j = col[b + (int)m - 1];
@@ -135,64 +132,24 @@ __global__ void __launch_bounds__(kMeshThreads) k_mesh_terms(MeshTermsArgs a)
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        acc_l += __shfl_down(acc_l, off);
-        acc_f += __shfl_down(acc_f, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_red[0][threadIdx.x >> 6] = acc_l;
-        s_red[1][threadIdx.x >> 6] = acc_f;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // write-through stores, wait for them, then count this workgroup in (as k_l1_loss_grad)
-        __hip_atomic_store(partial + blockIdx.x, (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(partial + kMeshMaxBlocks + blockIdx.x, (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = last_workgroup_of(a.counter, blockIdx.x, gridDim.x);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    float tl = 0.f, tf = 0.f;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
-        tl += __hip_atomic_load(partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tf += __hip_atomic_load(partial + kMeshMaxBlocks + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(partial + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the workspace is left zeroed
-        __hip_atomic_store(partial + kMeshMaxBlocks + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        tl += __shfl_down(tl, off);
-        tf += __shfl_down(tf, off);
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        s_red[0][threadIdx.x >> 6] = tl;
-        s_red[1][threadIdx.x >> 6] = tf;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a.loss[0] = ((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3])) * a.inv_V;
-        a.loss[1] = ((s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3])) * a.inv_3V;
-    }
+    if (!sum_over_workgroups(acc, a.partial, kMeshMaxBlocks, a.counter, blockIdx.x, gridDim.x)) return;
+    a.loss[0] = acc[0] * a.inv_V;
+    a.loss[1] = acc[1] * a.inv_3V;
 }
 
-size_t mesh_terms_workspace_bytes() { return (kDoneGroups + 1) * kDoneStride * sizeof(unsigned) + 2 * kMeshMaxBlocks * sizeof(float); }
+size_t mesh_terms_workspace_bytes() { return done_workspace_bytes(2 * kMeshMaxBlocks); }
 
 int launch_mesh_terms(const fr_mesh_terms_config& cfg, int V, const float* verts, const float* verts_orig, const int* row_ptr,
                       const int* col, float* d_verts, float* loss, void* workspace, hipStream_t s)
 {
     if (V <= 0) return FR_OK;
-    constexpr unsigned per_block = kMeshThreads / kMeshGroup;
-    unsigned blocks = ((unsigned)V + per_block - 1u) / per_block;
-    blocks = blocks > kMeshMaxBlocks ? kMeshMaxBlocks : blocks;
+    const unsigned blocks = capped_blocks((unsigned)V, kMeshThreads / kMeshGroup, kMeshMaxBlocks);
+    const DoneWorkspace ws = done_workspace(workspace);
     MeshTermsArgs a;
     a.verts = verts, a.orig = verts_orig, a.row_ptr = row_ptr, a.col = col;
     // both weights 0: the gradient array is not touched at all
     a.d_verts = (cfg.laplacian_weight != 0.f || cfg.flame_weight != 0.f) ? d_verts : nullptr;
-    a.counter = static_cast<unsigned*>(workspace);
-    a.partial = reinterpret_cast<float*>(a.counter + (kDoneGroups + 1) * kDoneStride);
+    a.counter = ws.counter, a.partial = ws.partial;
     a.loss = loss, a.V = V;
     a.c_lap = (float)((double)cfg.laplacian_weight * 2.0 / (double)V);
     a.c_flame = (float)((double)cfg.flame_weight * 2.0 / (3.0 * (double)V));

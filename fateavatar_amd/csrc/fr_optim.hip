@@ -10,9 +10,6 @@
 
 namespace fr {
 
-// (last_workgroup_of, kDoneGroups, kDoneStride: fr_common.hpp)  Call from one thread per workgroup of a 1-D grid.
-__device__ __forceinline__ bool last_workgroup(unsigned* c) { return last_workgroup_of(c, blockIdx.x, gridDim.x); }
-
 struct AdamArgs {
     int n_seg;
     unsigned long long seg_end[FR_ADAM_MAX_SEGMENTS];
@@ -34,7 +31,7 @@ struct AdamArgs {
 // DOUBLE, with beta and 1 - beta as the doubles the configuration holds (1 - 0.999f alone is off by 1.3e-5): accumulated
 // error at most 2^-53 / (1 - beta) = 1.1e-13 at any step count, far inside the float32 rounding of the value the update uses.  Words 1 and 2 keep
 // the corrections rounded to float for readers of the state.  Every workgroup of k_adam derives this step's corrections
-// from the OLD state; the workgroup that finishes last (last_workgroup) stores the new one — no launch of its own.
+// from the OLD state; the workgroup that finishes last (last_workgroup_of) stores the new one — no launch of its own.
 __device__ __forceinline__ float adam_one(float& p, float g, float& m, float& v, float lr_over_bc1, float inv_sqrt_bc2,
                                           const AdamArgs& a)
 {
@@ -117,7 +114,7 @@ __global__ void __launch_bounds__(256) k_adam(AdamArgs a, float4* __restrict__ p
     // knows that all have
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (last_workgroup(reinterpret_cast<unsigned*>(state + 32))) {
+        if (last_workgroup_of(reinterpret_cast<unsigned*>(state + 32), blockIdx.x, gridDim.x)) {
             double* const carry = reinterpret_cast<double*>(state + 4);
             state[0] = step_new, state[1] = bc1, state[2] = bc2, carry[0] = bc1_d, carry[1] = bc2_d;
         }
@@ -159,7 +156,8 @@ int launch_adam(const fr_adam_config& cfg, float* param, const float* const* gra
 // reference: nn.L1Loss(reduction='mean') on the rendered image (model/loss.py:92) followed by loss.backward() — in
 // PyTorch eight launch-bound elementwise / reduction kernels (sub, abs, mean, fill, sign, mul, ...: 41 us of a 205 us
 // optimisation step at 512 x 512).  Here: grad = sign(img - gt) / n and per-workgroup partial sums of |img - gt| in one
-// pass; the workgroup that finishes last adds the partials up in index order (deterministic) and stores the loss.
+// pass; the workgroup that finishes last adds the partials up in index order (deterministic) and stores the loss
+// (sum_over_workgroups, fr_common.hpp: every fused loss kernel of the library ends with it).
 constexpr unsigned kL1MaxBlocks = 1024;
 
 struct L1View {   // one image of a (possibly batched) launch
@@ -179,20 +177,16 @@ __device__ __forceinline__ void l1_loss_grad_body(const L1View& v, unsigned long
     const float* __restrict__ img = v.img;
     const float* __restrict__ gt = v.gt;
     float* __restrict__ grad = v.grad;
-    float* const partial = v.partial;
-    unsigned* const counter = v.counter;
     float* __restrict__ loss = v.loss;
-    __shared__ float s_red[4];
-    __shared__ bool s_last;
     const unsigned long long n4 = n / 4, stride = (unsigned long long)gridDim.x * blockDim.x;
-    float acc = 0.f;
+    float acc[1] = {0.f};
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const float4 a = reinterpret_cast<const float4*>(img)[i], b = reinterpret_cast<const float4*>(gt)[i];
         const float d[4] = {a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w};
         float g[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            acc += fabsf(d[k]);
+            acc[0] += fabsf(d[k]);
             g[k] = d[k] > 0.f ? g_mag : (d[k] < 0.f ? -g_mag : 0.f);   // torch.sign: 0 at 0
         }
         if (grad) reinterpret_cast<float4*>(grad)[i] = make_float4(g[0], g[1], g[2], g[3]);
@@ -200,57 +194,54 @@ __device__ __forceinline__ void l1_loss_grad_body(const L1View& v, unsigned long
     if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n - 4 * n4)) {   // tail of a length that is not a multiple of 4
         const unsigned long long e = 4 * n4 + threadIdx.x;
         const float d = img[e] - gt[e];
-        acc += fabsf(d);
+        acc[0] += fabsf(d);
         if (grad) grad[e] = d > 0.f ? g_mag : (d < 0.f ? -g_mag : 0.f);
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // write-through store, wait for it, then count this workgroup in (see k_unit_blend_chained on the hand-off)
-        __hip_atomic_store(partial + blockIdx.x, (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = last_workgroup(counter);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    float t = 0.f;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
-        t += __hip_atomic_load(partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (kTerms) __hip_atomic_store(partial + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float l1 = ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) * inv_n;
-        if (kTerms) loss[0] = rgb_weight * l1, loss[1] = l1, loss[2] = 0.f;
-        else *loss = l1;
-    }
+    if (!sum_over_workgroups<1, kTerms>(acc, v.partial, 0u, v.counter, blockIdx.x, gridDim.x)) return;
+    const float l1 = acc[0] * inv_n;
+    if (kTerms) loss[0] = rgb_weight * l1, loss[1] = l1, loss[2] = 0.f;
+    else *loss = l1;
 }
 
-__global__ void __launch_bounds__(256) k_l1_loss_grad(L1View v, unsigned long long n, float inv_n) { l1_loss_grad_body<false>(v, n, inv_n, inv_n, 1.f); }
+__global__ void __launch_bounds__(kSumThreads) k_l1_loss_grad(L1View v, unsigned long long n, float inv_n) { l1_loss_grad_body<false>(v, n, inv_n, inv_n, 1.f); }
 // the images of the frames of a batch (same size), one workspace each: grid (x, images)
-__global__ void __launch_bounds__(256) k_l1_loss_grad_batch(BatchOf<L1View> b, unsigned long long n, float inv_n)
+__global__ void __launch_bounds__(kSumThreads) k_l1_loss_grad_batch(BatchOf<L1View> b, unsigned long long n, float inv_n)
 {
     l1_loss_grad_body<false>(b.v[blockIdx.y], n, inv_n, inv_n, 1.f);
 }
 // the L1 term alone behind fr_image_loss_grad (three loss words per image, weighted gradient)
-__global__ void __launch_bounds__(256) k_l1_loss_grad_terms(BatchOf<L1View> b, unsigned long long n, float inv_n, float g_mag, float rgb_weight)
+__global__ void __launch_bounds__(kSumThreads) k_l1_loss_grad_terms(BatchOf<L1View> b, unsigned long long n, float inv_n, float g_mag, float rgb_weight)
 {
     l1_loss_grad_body<true>(b.v[blockIdx.y], n, inv_n, g_mag, rgb_weight);
+}
+
+size_t l1_workspace_bytes() { return done_workspace_bytes(kL1MaxBlocks); }
+
+// a float4 per thread and sweep: what the L1 and Huber kernels take per workgroup
+static unsigned l1_blocks(unsigned long long n) { return capped_blocks(n / 4, kSumThreads, kL1MaxBlocks); }
+
+static L1View l1_view(const float* img, const float* gt, float* grad, float* loss, void* workspace)
+{
+    const DoneWorkspace ws = done_workspace(workspace);
+    return L1View{img, gt, grad, ws.partial, ws.counter, loss};
+}
+
+static BatchOf<L1View> l1_views(int n_images, const float* const* img, const float* const* gt, float* const* grad, float* const* loss,
+                                void* const* workspace)
+{
+    BatchOf<L1View> b;
+    for (int k = 0; k < kMaxBatch; k++) {
+        const int j = k < n_images ? k : 0;   // (unused entries: never indexed, blockIdx.y < n_images)
+        b.v[k] = l1_view(img[j], gt[j], grad ? grad[j] : nullptr, loss[j], workspace[j]);
+    }
+    return b;
 }
 
 int launch_l1_loss_grad(unsigned long long n, const float* img, const float* gt, float* grad, float* loss, void* workspace,
                         hipStream_t s)
 {
     if (n == 0) return FR_OK;
-    unsigned long long blocks = (n / 4 + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > kL1MaxBlocks ? kL1MaxBlocks : blocks);
-    unsigned* counter = static_cast<unsigned*>(workspace);
-    float* partial = reinterpret_cast<float*>(counter + (kDoneGroups + 1) * kDoneStride);
-    hipLaunchKernelGGL(k_l1_loss_grad, dim3((unsigned)blocks), dim3(256), 0, s, L1View{img, gt, grad, partial, counter, loss}, n,
+    hipLaunchKernelGGL(k_l1_loss_grad, dim3(l1_blocks(n)), dim3(kSumThreads), 0, s, l1_view(img, gt, grad, loss, workspace), n,
                        (float)(1.0 / (double)n));
     FR_HIP(hipGetLastError());
     return FR_OK;
@@ -260,16 +251,8 @@ int launch_l1_loss_grad_batch(int n_images, unsigned long long n, const float* c
                               float* const* loss, void* const* workspace, hipStream_t s)
 {
     if (n == 0 || n_images <= 0) return FR_OK;
-    unsigned long long blocks = (n / 4 + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > kL1MaxBlocks ? kL1MaxBlocks : blocks);
-    BatchOf<L1View> b;
-    for (int k = 0; k < kMaxBatch; k++) {
-        const int j = k < n_images ? k : 0;   // (unused entries: never indexed, blockIdx.y < n_images)
-        unsigned* counter = static_cast<unsigned*>(workspace[j]);
-        b.v[k] = L1View{img[j], gt[j], grad ? grad[j] : nullptr, reinterpret_cast<float*>(counter + (kDoneGroups + 1) * kDoneStride),
-                        counter, loss[j]};
-    }
-    hipLaunchKernelGGL(k_l1_loss_grad_batch, dim3((unsigned)blocks, (unsigned)n_images), dim3(256), 0, s, b, n, (float)(1.0 / (double)n));
+    hipLaunchKernelGGL(k_l1_loss_grad_batch, dim3(l1_blocks(n), (unsigned)n_images), dim3(kSumThreads), 0, s,
+                       l1_views(n_images, img, gt, grad, loss, workspace), n, (float)(1.0 / (double)n));
     FR_HIP(hipGetLastError());
     return FR_OK;
 }
@@ -278,16 +261,8 @@ int launch_l1_loss_grad_terms(int n_images, unsigned long long n, float rgb_weig
                               float* const* grad, float* const* loss, void* const* workspace, hipStream_t s)
 {
     if (n == 0 || n_images <= 0) return FR_OK;
-    unsigned long long blocks = (n / 4 + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > kL1MaxBlocks ? kL1MaxBlocks : blocks);
-    BatchOf<L1View> b;
-    for (int k = 0; k < kMaxBatch; k++) {
-        const int j = k < n_images ? k : 0;
-        unsigned* counter = static_cast<unsigned*>(workspace[j]);
-        b.v[k] = L1View{img[j], gt[j], grad ? grad[j] : nullptr, reinterpret_cast<float*>(counter + (kDoneGroups + 1) * kDoneStride),
-                        counter, loss[j]};
-    }
-    hipLaunchKernelGGL(k_l1_loss_grad_terms, dim3((unsigned)blocks, (unsigned)n_images), dim3(256), 0, s, b, n, (float)(1.0 / (double)n),
+    hipLaunchKernelGGL(k_l1_loss_grad_terms, dim3(l1_blocks(n), (unsigned)n_images), dim3(kSumThreads), 0, s,
+                       l1_views(n_images, img, gt, grad, loss, workspace), n, (float)(1.0 / (double)n),
                        (float)((double)rgb_weight / (double)n), rgb_weight);
     FR_HIP(hipGetLastError());
     return FR_OK;
@@ -340,84 +315,40 @@ __global__ void __launch_bounds__(256) k_huber_loss_grad(HuberArgs a)
     const float* __restrict__ img = a.img;
     const float* __restrict__ gt = a.gt;
     float* __restrict__ grad = a.grad;
-    float* const partial = a.partial;
-    __shared__ float s_red[2][4];
-    __shared__ bool s_last;
     const unsigned long long n = a.n, n4 = n / 4, stride = (unsigned long long)gridDim.x * blockDim.x;
-    float acc_h = 0.f, acc_m = 0.f;
+    float acc[2] = {0.f, 0.f};   // huber, mouth
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const float4 x = reinterpret_cast<const float4*>(img)[i], y = reinterpret_cast<const float4*>(gt)[i];
         const float d[4] = {x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w};
         float g[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) g[k] = huber_one(a, 4 * i + k, d[k], acc_h, acc_m);
+        for (int k = 0; k < 4; k++) g[k] = huber_one(a, 4 * i + k, d[k], acc[0], acc[1]);
         if (grad) reinterpret_cast<float4*>(grad)[i] = make_float4(g[0], g[1], g[2], g[3]);
     }
     if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n - 4 * n4)) {   // tail of a length that is not a multiple of 4
         const unsigned long long e = 4 * n4 + threadIdx.x;
-        const float g = huber_one(a, e, img[e] - gt[e], acc_h, acc_m);
+        const float g = huber_one(a, e, img[e] - gt[e], acc[0], acc[1]);
         if (grad) grad[e] = g;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        acc_h += __shfl_down(acc_h, off);
-        acc_m += __shfl_down(acc_m, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_red[0][threadIdx.x >> 6] = acc_h;
-        s_red[1][threadIdx.x >> 6] = acc_m;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // write-through stores, wait for them, then count this workgroup in (as k_l1_loss_grad)
-        __hip_atomic_store(partial + blockIdx.x, (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(partial + kL1MaxBlocks + blockIdx.x, (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = last_workgroup_of(a.counter, blockIdx.x, gridDim.x);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    float th = 0.f, tm = 0.f;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
-        th += __hip_atomic_load(partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tm += __hip_atomic_load(partial + kL1MaxBlocks + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(partial + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the workspace is left zeroed
-        __hip_atomic_store(partial + kL1MaxBlocks + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        th += __shfl_down(th, off);
-        tm += __shfl_down(tm, off);
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        s_red[0][threadIdx.x >> 6] = th;
-        s_red[1][threadIdx.x >> 6] = tm;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float huber = ((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3])) * a.inv_n;
-        const float mouth = ((s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3])) * a.inv_n;
-        a.loss[0] = huber + a.mask_weight * mouth, a.loss[1] = huber, a.loss[2] = mouth;
-    }
+    if (!sum_over_workgroups(acc, a.partial, kL1MaxBlocks, a.counter, blockIdx.x, gridDim.x)) return;
+    const float huber = acc[0] * a.inv_n, mouth = acc[1] * a.inv_n;
+    a.loss[0] = huber + a.mask_weight * mouth, a.loss[1] = huber, a.loss[2] = mouth;
 }
 
-size_t huber_workspace_bytes() { return (kDoneGroups + 1) * kDoneStride * sizeof(unsigned) + 2 * kL1MaxBlocks * sizeof(float); }
+size_t huber_workspace_bytes() { return done_workspace_bytes(2 * kL1MaxBlocks); }
 
 int launch_huber_loss_grad(const fr_huber_config& cfg, int C, int H, int W, const float* img, const float* gt, const float* mask,
                            float* grad, float* loss, void* workspace, hipStream_t s)
 {
     const unsigned long long hw = (unsigned long long)H * (unsigned long long)W, n = hw * (unsigned long long)C;
     if (n == 0) return FR_OK;
-    unsigned long long blocks = (n / 4 + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > kL1MaxBlocks ? kL1MaxBlocks : blocks);
+    const DoneWorkspace ws = done_workspace(workspace);
     HuberArgs a;
     a.img = img, a.gt = gt, a.mask = mask, a.grad = grad, a.loss = loss;
-    a.counter = static_cast<unsigned*>(workspace);
-    a.partial = reinterpret_cast<float*>(a.counter + (kDoneGroups + 1) * kDoneStride);
+    a.counter = ws.counter, a.partial = ws.partial;
     a.n = n, a.hw = (unsigned)hw;
     a.alpha = cfg.alpha, a.mask_weight = mask ? cfg.mask_weight : 0.f, a.inv_n = (float)(1.0 / (double)n);
-    hipLaunchKernelGGL(k_huber_loss_grad, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_huber_loss_grad, dim3(l1_blocks(n)), dim3(kSumThreads), 0, s, a);
     FR_HIP(hipGetLastError());
     return FR_OK;
 }
@@ -540,17 +471,14 @@ __global__ void __launch_bounds__(256) k_gaussian_regularise(RegArgs a)
     const float* __restrict__ xyz = a.xyz;
     float* __restrict__ d_scaling = a.d_scaling;
     float* __restrict__ d_xyz = a.d_xyz;
-    float* const partial = a.partial;
-    __shared__ float s_red[2][4];
-    __shared__ bool s_last;
     const unsigned stride = gridDim.x * blockDim.x;
-    float acc_s = 0.f, acc_x = 0.f;
+    float acc[2] = {0.f, 0.f};   // scale, xyz
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)a.P; i += stride) {
         const size_t o = (size_t)i * 3;
         const float e0 = act_exp(scaling[o]), e1 = act_exp(scaling[o + 1]), e2 = act_exp(scaling[o + 2]);
         const float c0 = fmaxf(e0 - a.thr_scale, 0.f), c1 = fmaxf(e1 - a.thr_scale, 0.f), c2 = fmaxf(e2 - a.thr_scale, 0.f);
         const float ns = sqrtf((c0 * c0 + c1 * c1) + c2 * c2);
-        acc_s += ns;
+        acc[0] += ns;
         if (d_scaling && ns > 0.f) {       // (c_k == 0 where exp(s_k) <= threshold: that component adds an exact 0)
             const float k = a.g_scale / ns;
             d_scaling[o] += k * c0 * e0;
@@ -560,7 +488,7 @@ __global__ void __launch_bounds__(256) k_gaussian_regularise(RegArgs a)
         const float x = xyz[o], y = xyz[o + 1], z = xyz[o + 2];
         const float nx = sqrtf((x * x + y * y) + z * z);
         const float over = nx - a.thr_xyz;
-        acc_x += fmaxf(over, 0.f);
+        acc[1] += fmaxf(over, 0.f);
         if (d_xyz && over > 0.f && nx > 0.f) {
             const float k = a.g_xyz / nx;
             d_xyz[o] += k * x;
@@ -568,63 +496,24 @@ __global__ void __launch_bounds__(256) k_gaussian_regularise(RegArgs a)
             d_xyz[o + 2] += k * z;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        acc_s += __shfl_down(acc_s, off);
-        acc_x += __shfl_down(acc_x, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_red[0][threadIdx.x >> 6] = acc_s;
-        s_red[1][threadIdx.x >> 6] = acc_x;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // write-through stores, wait for them, then count this workgroup in (as k_l1_loss_grad)
-        __hip_atomic_store(partial + blockIdx.x, (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(partial + kRegMaxBlocks + blockIdx.x, (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = last_workgroup(a.counter);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    float ts = 0.f, tx = 0.f;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
-        ts += __hip_atomic_load(partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tx += __hip_atomic_load(partial + kRegMaxBlocks + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(partial + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the workspace is left zeroed
-        __hip_atomic_store(partial + kRegMaxBlocks + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        ts += __shfl_down(ts, off);
-        tx += __shfl_down(tx, off);
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        s_red[0][threadIdx.x >> 6] = ts;
-        s_red[1][threadIdx.x >> 6] = tx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a.loss[0] = ((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3])) * a.inv_P;
-        a.loss[1] = ((s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3])) * a.inv_P;
-    }
+    if (!sum_over_workgroups(acc, a.partial, kRegMaxBlocks, a.counter, blockIdx.x, gridDim.x)) return;
+    a.loss[0] = acc[0] * a.inv_P;
+    a.loss[1] = acc[1] * a.inv_P;
 }
 
-size_t regularise_workspace_bytes() { return (kDoneGroups + 1) * kDoneStride * sizeof(unsigned) + 2 * kRegMaxBlocks * sizeof(float); }
+size_t regularise_workspace_bytes() { return done_workspace_bytes(2 * kRegMaxBlocks); }
 
 int launch_gaussian_regularise(const fr_regularise_config& cfg, int P, const float* scaling, const float* xyz, float* d_scaling,
                                float* d_xyz, float* loss, void* workspace, hipStream_t s)
 {
     if (P <= 0) return FR_OK;
-    unsigned blocks = ((unsigned)P + 255u) / 256u;
-    blocks = blocks > kRegMaxBlocks ? kRegMaxBlocks : blocks;
+    const unsigned blocks = capped_blocks((unsigned)P, kSumThreads, kRegMaxBlocks);
+    const DoneWorkspace ws = done_workspace(workspace);
     RegArgs a;
     a.scaling = scaling, a.xyz = xyz;
     a.d_scaling = cfg.scale_weight != 0.f ? d_scaling : nullptr;   // a zero weight: the array is not touched
     a.d_xyz = cfg.xyz_weight != 0.f ? d_xyz : nullptr;
-    a.counter = static_cast<unsigned*>(workspace);
-    a.partial = reinterpret_cast<float*>(a.counter + (kDoneGroups + 1) * kDoneStride);
+    a.counter = ws.counter, a.partial = ws.partial;
     a.loss = loss, a.P = P;
     a.inv_P = (float)(1.0 / (double)P);
     a.g_scale = (float)((double)cfg.scale_weight / (double)P), a.g_xyz = (float)((double)cfg.xyz_weight / (double)P);

@@ -33,7 +33,7 @@
 // sub, sub + 16, ... of P (folded three to a pose feature at the very end) and, in lane j < J, the twelve products of bone j.
 // A dead group adds exact zeros and stays with its wave.  After the sweep: the wave's four groups in index order (shuffles), the
 // workgroup's waves in index order (LDS), one row of 272 partials per workgroup stored write-through, and the workgroup that
-// finishes last (last_workgroup_of, as k_lbs_terms) adds the rows up in workgroup-index order (fifteen runs of consecutive rows
+// finishes last (last_workgroup_of, as sum_over_workgroups) adds the rows up in workgroup-index order (fifteen runs of consecutive rows
 // side by side, then the runs in order), writes the three outputs and leaves the workspace zeroed: no float atomics, the same
 // bits on every launch.  Workgroups of 1 024 threads, at most one per CU (256): the last workgroup's serial read grows with the
 // number of rows, not with N.  Compiler (gfx950): 123 VGPRs, no scratch, 18 580 B of LDS, four waves per SIMD = the one
@@ -46,7 +46,7 @@
 // fr_nearest_vertex: one lane per point against the vertices in LDS (struct of arrays, 4 096 vertices = 48 KB at a time, every
 // lane of a wave reads the same address: broadcast reads, four vertices per ds_read_b128), strict `<` in ascending order.
 // fr_lbs_terms: the same sixteen-lane groups over (pred row, gathered ground-truth row); the three sums go through
-// per-workgroup partials added up in index order by the workgroup that finishes last (k_gaussian_regularise's pattern).
+// per-workgroup partials added up in index order by the workgroup that finishes last (sum_over_workgroups, fr_common.hpp).
 // Built with the STRICT flags: the nearest vertex's expression order is part of its contract.
 #include "fr_common.hpp"
 
@@ -246,12 +246,7 @@ __global__ void __launch_bounds__(kLbsThreads) k_point_lbs_bwd(LbsArgs a)
     }
 }
 
-static unsigned lbs_blocks(int N)
-{
-    constexpr unsigned per_block = kLbsThreads / kLbsGroup;
-    const unsigned blocks = ((unsigned)N + per_block - 1u) / per_block;
-    return blocks > kLbsMaxBlocks ? kLbsMaxBlocks : blocks;
-}
+static unsigned lbs_blocks(int N) { return capped_blocks((unsigned)N, kLbsThreads / kLbsGroup, kLbsMaxBlocks); }
 
 static LbsArgs lbs_args(const fr_point_lbs& d)
 {
@@ -298,7 +293,7 @@ constexpr unsigned kPoseSlots = kPoseOffT + 12 * FR_LBS_MAX_J;               // 
 constexpr unsigned kPoseChunks = kPoseThreads / (kPoseSlots / 4);            // 15 runs of rows in the last workgroup
 static_assert(kPoseSlots % 4 == 0 && kPoseChunks >= 1 && kPoseChunks < kPoseWaves, "one float4 column per thread of the last "
               "workgroup; the runs' sums and their total share the waves' rows of LDS");
-static_assert(((kDoneGroups + 1) * kDoneStride * sizeof(unsigned)) % 16 == 0, "the partials are read sixteen bytes at a time");
+static_assert(done_workspace_bytes(0) % 16 == 0, "the partials are read sixteen bytes at a time");
 
 struct LbsPoseOut {
     float *d_betas, *d_phi, *d_A;   // [E], [36], [J,16]; any may be null
@@ -383,7 +378,7 @@ __global__ void __launch_bounds__(kPoseThreads) k_point_lbs_pose_bwd(LbsArgs a, 
         if (lane < kLbsGroup && (t < kPoseS + kPoseP || sub < (unsigned)FR_LBS_MAX_J)) s_red[wave][pose_slot(t, sub)] = v;
     }
     __syncthreads();
-    // write-through stores, every storing wave waits for its own, then ONE thread counts the workgroup in (as k_lbs_terms)
+    // write-through stores, every storing wave waits for its own, then ONE thread counts the workgroup in (as sum_over_workgroups)
     float* const row = out.partial + (size_t)blockIdx.x * kPoseSlots;
     if (threadIdx.x < kPoseSlots) {
         float v = s_red[0][threadIdx.x];
@@ -443,7 +438,7 @@ __global__ void __launch_bounds__(kPoseThreads) k_point_lbs_pose_bwd(LbsArgs a, 
 
 size_t point_lbs_pose_workspace_bytes()
 {
-    return (kDoneGroups + 1) * kDoneStride * sizeof(unsigned) + (size_t)kPoseMaxBlocks * kPoseSlots * sizeof(float);
+    return done_workspace_bytes((size_t)kPoseMaxBlocks * kPoseSlots);
 }
 
 int launch_point_lbs_backward_pose(const fr_point_lbs& d, const float* g_xyz, float* d_betas, float* d_pose_feature, float* d_transforms,
@@ -454,10 +449,9 @@ int launch_point_lbs_backward_pose(const fr_point_lbs& d, const float* g_xyz, fl
     a.g = g_xyz;
     LbsPoseOut out;
     out.d_betas = d_betas, out.d_phi = d_pose_feature, out.d_A = d_transforms;
-    out.counter = static_cast<unsigned*>(workspace);
-    out.partial = reinterpret_cast<float*>(out.counter + (kDoneGroups + 1) * kDoneStride);
-    constexpr unsigned per_block = kPoseThreads / kLbsGroup;
-    const unsigned want = ((unsigned)d.N + per_block - 1u) / per_block, blocks = want > kPoseMaxBlocks ? kPoseMaxBlocks : want;
+    const DoneWorkspace ws = done_workspace(workspace);
+    out.counter = ws.counter, out.partial = ws.partial;
+    const unsigned blocks = capped_blocks((unsigned)d.N, kPoseThreads / kLbsGroup, kPoseMaxBlocks);
     hipLaunchKernelGGL(k_point_lbs_pose_bwd, dim3(blocks), dim3(kPoseThreads), 0, s, a, out);
     FR_HIP(hipGetLastError());
     return FR_OK;
@@ -550,9 +544,7 @@ __device__ __forceinline__ float terms_row(const float* __restrict__ pred, const
 
 __global__ void __launch_bounds__(kLbsThreads) k_lbs_terms(LbsTermsArgs a)
 {
-    __shared__ float s_red[3][kLbsThreads / 64];
-    __shared__ bool s_last;
-    float* const partial = a.partial;
+    static_assert(kLbsThreads == kSumThreads, "sum_over_workgroups' workgroup");
     const unsigned sub = threadIdx.x & (kLbsGroup - 1);
     const unsigned group = (blockIdx.x * blockDim.x + threadIdx.x) / kLbsGroup, n_groups = gridDim.x * blockDim.x / kLbsGroup;
     const unsigned J = (unsigned)a.J, lenP = (unsigned)(kLbsPose * 3), lenS = 3u * (unsigned)a.E;
@@ -565,50 +557,13 @@ __global__ void __launch_bounds__(kLbsThreads) k_lbs_terms(LbsTermsArgs a)
         acc[2] += terms_row(a.S + i * lenS, a.gS + (size_t)v * lenS, a.d_S ? a.d_S + i * lenS : nullptr, lenS, sub, a.c_S);
     }
     // (every lane of the workgroup arrives here: the loop above holds no shuffle)
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-        for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) s_red[k][threadIdx.x >> 6] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // write-through stores, wait for them, then count this workgroup in (as k_mesh_terms)
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-            __hip_atomic_store(partial + k * kTermsMaxBlocks + blockIdx.x, (s_red[k][0] + s_red[k][1]) + (s_red[k][2] + s_red[k][3]),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = last_workgroup_of(a.counter, blockIdx.x, gridDim.x);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    float tot[3] = {0.f, 0.f, 0.f};
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            tot[k] += __hip_atomic_load(partial + k * kTermsMaxBlocks + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(partial + k * kTermsMaxBlocks + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // left zeroed
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-        for (int off = 32; off > 0; off >>= 1) tot[k] += __shfl_down(tot[k], off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) s_red[k][threadIdx.x >> 6] = tot[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a.loss[0] = ((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3])) * a.inv_w;
-        a.loss[1] = ((s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3])) * a.inv_P;
-        a.loss[2] = ((s_red[2][0] + s_red[2][1]) + (s_red[2][2] + s_red[2][3])) * a.inv_S;
-    }
+    if (!sum_over_workgroups(acc, a.partial, kTermsMaxBlocks, a.counter, blockIdx.x, gridDim.x)) return;
+    a.loss[0] = acc[0] * a.inv_w;
+    a.loss[1] = acc[1] * a.inv_P;
+    a.loss[2] = acc[2] * a.inv_S;
 }
 
-size_t lbs_terms_workspace_bytes() { return (kDoneGroups + 1) * kDoneStride * sizeof(unsigned) + 3 * kTermsMaxBlocks * sizeof(float); }
+size_t lbs_terms_workspace_bytes() { return done_workspace_bytes(3 * kTermsMaxBlocks); }
 
 int launch_lbs_terms(const fr_lbs_terms_config& cfg, int N, int V, int E, int J, const int* index, const float* weights,
                      const float* posedirs, const float* shapedirs, const float* gt_weights, const float* gt_posedirs,
@@ -622,14 +577,14 @@ int launch_lbs_terms(const fr_lbs_terms_config& cfg, int N, int V, int E, int J,
     a.d_w = cfg.weights_weight != 0.f ? d_weights : nullptr;
     a.d_P = cfg.posedirs_weight != 0.f ? d_posedirs : nullptr;
     a.d_S = cfg.shapedirs_weight != 0.f ? d_shapedirs : nullptr;
-    a.counter = static_cast<unsigned*>(workspace);
-    a.partial = reinterpret_cast<float*>(a.counter + (kDoneGroups + 1) * kDoneStride);
+    const DoneWorkspace ws = done_workspace(workspace);
+    a.counter = ws.counter, a.partial = ws.partial;
     a.loss = loss, a.N = N, a.V = V, a.E = E, a.J = J;
     const double n_w = (double)N * J, n_P = (double)N * (kLbsPose * 3), n_S = (double)N * 3.0 * E;
     a.c_w = (float)((double)cfg.weights_weight * 2.0 / n_w), a.inv_w = (float)(1.0 / n_w);
     a.c_P = (float)((double)cfg.posedirs_weight * 2.0 / n_P), a.inv_P = (float)(1.0 / n_P);
     a.c_S = (float)((double)cfg.shapedirs_weight * 2.0 / n_S), a.inv_S = (float)(1.0 / n_S);
-    hipLaunchKernelGGL(k_lbs_terms, dim3(lbs_blocks(N) > kTermsMaxBlocks ? kTermsMaxBlocks : lbs_blocks(N)), dim3(kLbsThreads), 0, s, a);
+    hipLaunchKernelGGL(k_lbs_terms, dim3(capped_blocks((unsigned)N, kLbsThreads / kLbsGroup, kTermsMaxBlocks)), dim3(kLbsThreads), 0, s, a);
     FR_HIP(hipGetLastError());
     return FR_OK;
 }

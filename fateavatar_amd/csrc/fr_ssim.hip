@@ -21,7 +21,7 @@
 // different banks) and 40 for the horizontal results (a wave reads columns 0 .. 31 of rows r and r + 4: 4 x 40 = 160 = 32
 // mod 64, the two halves of the wave use the two halves of the 64 banks).  48 KB (pass 1) and 42 KB (pass 2) of LDS per
 // workgroup: three workgroups per CU.  No float atomics: every output has one owner, and the loss sums go through
-// per-workgroup partials that the workgroup finishing last adds up in index order (k_l1_loss_grad's scheme) — results are
+// per-workgroup partials that the workgroup finishing last adds up in index order (sum_over_workgroups, fr_common.hpp) — results are
 // bit-reproducible.  Built with FMA contraction (Makefile).
 #include "fr_common.hpp"
 
@@ -33,7 +33,7 @@ constexpr int kSsimTile = 32, kRad = 5, kTaps = 2 * kRad + 1, kHalo = kSsimTile 
 constexpr int kInStride = 43, kRowStride = 40;
 constexpr int kRowsPerThread = 4, kThreads = kSsimTile * kSsimTile / kRowsPerThread;   // 256
 constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
-static_assert(kThreads == 256 && (kRowsPerThread * kRowStride) % 64 == 32 && kRowStride >= kSsimTile && kInStride >= kHalo, "tile geometry");
+static_assert(kThreads == kSumThreads && (kRowsPerThread * kRowStride) % 64 == 32 && kRowStride >= kSsimTile && kInStride >= kHalo, "tile geometry");
 
 struct SsimView {   // one image of a launch
     const float* img;
@@ -69,8 +69,6 @@ __global__ void __launch_bounds__(256) k_image_loss_maps(SsimArgs a)
 {
     __shared__ float s_x[kHalo * kInStride], s_y[kHalo * kInStride];
     __shared__ float s_h[5][kHalo * kRowStride];
-    __shared__ float s_red[2][4];
-    __shared__ bool s_last;
     const SsimView& v = a.b.v[blockIdx.z / (unsigned)a.C];
     const int ch = blockIdx.z % (unsigned)a.C;
     const int H = a.H, W = a.W, x0 = blockIdx.x * kSsimTile, y0 = blockIdx.y * kSsimTile;
@@ -115,7 +113,7 @@ __global__ void __launch_bounds__(256) k_image_loss_maps(SsimArgs a)
             }
         }
     }
-    float sum_d = 0.f, sum_l1 = 0.f;
+    float sums[2] = {0.f, 0.f};   // 1 - S, |x - y|
     const int x = x0 + tx;
     float* const maps = v.maps + ch * plane;
     const size_t map_stride = (size_t)a.C * plane;
@@ -131,53 +129,21 @@ __global__ void __launch_bounds__(256) k_image_loss_maps(SsimArgs a)
             const float S = A * B * inv;
             const float dS12 = 2.f * A * inv, dS11 = -S / D;
             const float dM = 2.f * mu2 * B * inv - 2.f * mu1 * (S / Cc) - 2.f * mu1 * dS11 - mu2 * dS12;
-            sum_d += 1.f - S;
+            sums[0] += 1.f - S;
             const int li = (r0 + o + kRad) * kInStride + tx + kRad;
-            sum_l1 += fabsf(s_x[li] - s_y[li]);
+            sums[1] += fabsf(s_x[li] - s_y[li]);
             if (v.grad) {
                 const size_t p = (size_t)y * W + x;
                 maps[p] = dM, maps[map_stride + p] = dS11, maps[2 * map_stride + p] = dS12;
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        sum_d += __shfl_down(sum_d, off);
-        sum_l1 += __shfl_down(sum_l1, off);
-    }
-    if ((threadIdx.x & 63) == 0) s_red[0][threadIdx.x >> 6] = sum_d, s_red[1][threadIdx.x >> 6] = sum_l1;
-    __syncthreads();
     const unsigned n_wg = (unsigned)a.C * a.tiles_x * a.tiles_y;
-    if (threadIdx.x == 0) {
-        const unsigned id = ((unsigned)ch * a.tiles_y + blockIdx.y) * a.tiles_x + blockIdx.x;
-        // write-through stores, wait for them, then count this workgroup in (as k_l1_loss_grad)
-        __hip_atomic_store(v.partial + id, (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(v.partial + n_wg + id, (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = last_workgroup_of(v.counter, id, n_wg);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    float td = 0.f, tl = 0.f;
-    for (unsigned b = threadIdx.x; b < n_wg; b += kThreads) {
-        td += __hip_atomic_load(v.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tl += __hip_atomic_load(v.partial + n_wg + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(v.partial + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // left zeroed
-        __hip_atomic_store(v.partial + n_wg + b, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        td += __shfl_down(td, off);
-        tl += __shfl_down(tl, off);
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[0][threadIdx.x >> 6] = td, s_red[1][threadIdx.x >> 6] = tl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float d = ((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3])) * a.inv_n;
-        const float l1 = ((s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3])) * a.inv_n;
-        v.loss[0] = a.rgb_weight * l1 + a.dssim_weight * d, v.loss[1] = l1, v.loss[2] = d;
-    }
+    const unsigned id = ((unsigned)ch * a.tiles_y + blockIdx.y) * a.tiles_x + blockIdx.x;
+    if (!sum_over_workgroups(sums, v.partial, n_wg, v.counter, id, n_wg)) return;
+    const float d = sums[0] * a.inv_n, l1 = sums[1] * a.inv_n;
+    // (spelt out: which of the two products the compiler folds into the addition is its choice, and it shows in the last bit)
+    v.loss[0] = __builtin_fmaf(a.dssim_weight, d, a.rgb_weight * l1), v.loss[1] = l1, v.loss[2] = d;
 }
 
 __global__ void __launch_bounds__(256) k_image_loss_grad(SsimArgs a)
@@ -259,13 +225,11 @@ void ssim_window(float out[11])
 }
 
 static inline size_t n_tiles(int n) { return ((size_t)n + kSsimTile - 1) / kSsimTile; }
-// counters | partials (at least the 1024 floats k_l1_loss_grad uses: the D-SSIM-free path runs that kernel) | maps
+// counters | partials (at least what k_l1_loss_grad_terms uses: the D-SSIM-free path runs that kernel) | maps
 static inline size_t maps_offset(int C, int H, int W)
 {
-    size_t partials = 2 * (size_t)C * n_tiles(H) * n_tiles(W);
-    partials = partials < 1024 ? 1024 : partials;
-    const size_t bytes = (kDoneGroups + 1) * kDoneStride * sizeof(unsigned) + partials * sizeof(float);
-    return (bytes + 255) / 256 * 256;
+    const size_t bytes = done_workspace_bytes(2 * (size_t)C * n_tiles(H) * n_tiles(W));
+    return align_up(bytes < l1_workspace_bytes() ? l1_workspace_bytes() : bytes, 256);
 }
 
 size_t image_loss_workspace_bytes(int C, int H, int W)
@@ -284,10 +248,9 @@ int launch_image_loss_grad(const fr_image_loss_config& cfg, int n_images, int C,
     const size_t off = maps_offset(C, H, W);
     for (int k = 0; k < kMaxBatch; k++) {
         const int j = k < n_images ? k : 0;   // (unused entries are never indexed: blockIdx.z < n_images x C)
-        char* ws = static_cast<char*>(workspace[j]);
-        unsigned* counter = reinterpret_cast<unsigned*>(ws);
-        a.b.v[k] = SsimView{img[j], gt[j], grad ? grad[j] : nullptr, loss[j], counter,
-                            reinterpret_cast<float*>(counter + (kDoneGroups + 1) * kDoneStride), reinterpret_cast<float*>(ws + off)};
+        const DoneWorkspace ws = done_workspace(workspace[j]);
+        a.b.v[k] = SsimView{img[j], gt[j], grad ? grad[j] : nullptr, loss[j], ws.counter, ws.partial,
+                            reinterpret_cast<float*>(static_cast<char*>(workspace[j]) + off)};
         any_grad = any_grad || a.b.v[k].grad != nullptr;
     }
     a.C = C, a.H = H, a.W = W;

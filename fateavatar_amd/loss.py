@@ -15,18 +15,19 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
+from .workspace import StreamWorkspace
 
-# (device index, stream handle) -> zeroed scratch (the kernel leaves it zeroed).  One workspace PER STREAM: the kernel
-# elects its last workgroup through counters in the workspace and sums per-workgroup partials left there, so two launches
-# that overlap on the device — the lanes of AvatarBatchStep run on their own streams, each from its own captured graph —
-# must not share one (the loss scalars would mix; include/fr_rasterizer.h says the same of fr_l1_loss_grad).
-_workspace = {}
+# one workspace per op and (device, stream): workspace.py says why
+_l1_ws = StreamWorkspace("l1_workspace", lambda: _lib.lib().fr_l1_workspace_bytes(), "image's")
+_huber_ws = StreamWorkspace("huber_workspace", lambda: _lib.lib().fr_huber_workspace_bytes(), "image's")
+_reg_ws = StreamWorkspace("regulariser_workspace", lambda: _lib.lib().fr_regularise_workspace_bytes(), "parameters'")
+_mesh_ws = StreamWorkspace("mesh_terms_workspace", lambda: _lib.lib().fr_mesh_terms_workspace_bytes(), "vertices'")
 
 
 def l1_workspace(dev: torch.device) -> torch.Tensor:
     """A fresh zeroed workspace for `l1_loss_and_grad(..., workspace=)`: for callers that launch from several streams or
     graphs at once and want to own the scratch explicitly."""
-    return torch.zeros((_lib.lib().fr_l1_workspace_bytes(),), dtype=torch.uint8, device=dev)
+    return _l1_ws.fresh(dev)
 
 
 def l1_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, loss_out: Optional[torch.Tensor] = None,
@@ -49,19 +50,7 @@ def l1_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, loss_out: Optional[tor
     loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float32, device=dev)
     if grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or loss.numel() != 1:
         raise RuntimeError("l1_loss_and_grad: bad output buffers")
-    L = _lib.lib()
-    ws = workspace
-    if ws is None:
-        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        ws = _workspace.get(key)
-        if ws is None:
-            # (allocated on a side stream-independent path: torch.zeros inside a capture would become part of the graph)
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("l1_loss_and_grad: first call on this stream happens inside a graph capture; call it once "
-                                   "eagerly on the stream first, or pass workspace=l1_workspace(device)")
-            ws = _workspace[key] = l1_workspace(dev)
-    elif not (ws.is_cuda and ws.device == dev and ws.dtype == torch.uint8 and ws.numel() >= L.fr_l1_workspace_bytes()):
-        raise RuntimeError("l1_loss_and_grad: workspace must come from l1_workspace() on the image's device")
+    ws = _l1_ws.resolve(dev, workspace, "l1_loss_and_grad")
     _lib.launch("fr_l1_loss_grad", dev, img.numel(), img.data_ptr(), gt.data_ptr(), grad.data_ptr(), loss.data_ptr(), ws.data_ptr())
     return loss, grad
 
@@ -100,12 +89,9 @@ class HuberLoss(NamedTuple):
 
 REFERENCE_HUBER_LOSS = HuberLoss(0.1, 40.0)
 
-_huber_workspace = {}   # (device index, stream handle) -> zeroed scratch of fr_huber_loss_grad (as _workspace above)
-
-
 def huber_workspace(dev: torch.device) -> torch.Tensor:
     """A fresh zeroed workspace for `huber_loss_and_grad(..., workspace=)`."""
-    return torch.zeros((_lib.lib().fr_huber_workspace_bytes(),), dtype=torch.uint8, device=dev)
+    return _huber_ws.fresh(dev)
 
 
 def huber_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, terms=REFERENCE_HUBER_LOSS, mask: Optional[torch.Tensor] = None,
@@ -143,18 +129,7 @@ def huber_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, terms=REFERENCE_HUB
     if (grad is not None and (grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != dev)) \
             or loss.numel() != 3 or loss.dtype != torch.float32 or loss.device != dev or not loss.is_contiguous():
         raise RuntimeError("huber_loss_and_grad: bad output buffers (gradient of the image's shape, 3-element loss, float32, contiguous)")
-    L = _lib.lib()
-    ws = workspace
-    if ws is None:
-        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        ws = _huber_workspace.get(key)
-        if ws is None:
-            if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
-                raise RuntimeError("huber_loss_and_grad: first call on this stream happens inside a graph capture; call it once "
-                                   "eagerly on the stream first, or pass workspace=huber_workspace(device)")
-            ws = _huber_workspace[key] = huber_workspace(dev)
-    elif not (ws.is_cuda and ws.device == dev and ws.dtype == torch.uint8 and ws.numel() >= L.fr_huber_workspace_bytes()):
-        raise RuntimeError("huber_loss_and_grad: workspace must come from huber_workspace() on the image's device")
+    ws = _huber_ws.resolve(dev, workspace, "huber_loss_and_grad")
     import ctypes as C
     cfg = _lib.fr_huber_config(alpha, mask_weight)
     _lib.launch("fr_huber_loss_grad", dev, C.byref(cfg), Cn, H, W, img.data_ptr(), gt.data_ptr(),
@@ -163,12 +138,9 @@ def huber_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, terms=REFERENCE_HUB
     return loss, grad
 
 
-_reg_workspace = {}   # (device index, stream handle) -> zeroed scratch of fr_gaussian_regularise (as _workspace above)
-
-
 def regulariser_workspace(dev: torch.device) -> torch.Tensor:
     """A fresh zeroed workspace for `gaussian_regularisers(..., workspace=)`."""
-    return torch.zeros((_lib.lib().fr_regularise_workspace_bytes(),), dtype=torch.uint8, device=dev)
+    return _reg_ws.fresh(dev)
 
 
 def gaussian_regularisers(scaling: torch.Tensor, xyz: torch.Tensor, d_scaling: Optional[torch.Tensor],
@@ -193,18 +165,7 @@ def gaussian_regularisers(scaling: torch.Tensor, xyz: torch.Tensor, d_scaling: O
     loss = out if out is not None else torch.empty((2,), dtype=torch.float32, device=dev)
     if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
         raise RuntimeError("gaussian_regularisers: `out` is a contiguous 2-element float32 tensor on the parameters' device")
-    L = _lib.lib()
-    ws = workspace
-    if ws is None:
-        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        ws = _reg_workspace.get(key)
-        if ws is None:
-            if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
-                raise RuntimeError("gaussian_regularisers: first call on this stream happens inside a graph capture; call it "
-                                   "once eagerly on the stream first, or pass workspace=regulariser_workspace(device)")
-            ws = _reg_workspace[key] = regulariser_workspace(dev)
-    elif not (ws.is_cuda and ws.device == dev and ws.dtype == torch.uint8 and ws.numel() >= L.fr_regularise_workspace_bytes()):
-        raise RuntimeError("gaussian_regularisers: workspace must come from regulariser_workspace() on the parameters' device")
+    ws = _reg_ws.resolve(dev, workspace, "gaussian_regularisers")
     import ctypes as C
     cfg = _lib.fr_regularise_config(float(weights[0]), float(weights[1]), float(thresholds[0]), float(thresholds[1]))
     _lib.launch("fr_gaussian_regularise", dev, C.byref(cfg), P, scaling.data_ptr(), xyz.data_ptr(),
@@ -223,12 +184,9 @@ class MeshTerms(NamedTuple):
 
 REFERENCE_MESH_TERMS = MeshTerms()
 
-_mesh_workspace = {}   # (device index, stream handle) -> zeroed scratch of fr_mesh_terms (as _workspace above)
-
-
 def mesh_terms_workspace(dev: torch.device) -> torch.Tensor:
     """A fresh zeroed workspace for `mesh_terms_and_grad(..., workspace=)`."""
-    return torch.zeros((_lib.lib().fr_mesh_terms_workspace_bytes(),), dtype=torch.uint8, device=dev)
+    return _mesh_ws.fresh(dev)
 
 
 def mesh_terms_and_grad(verts: torch.Tensor, verts_orig: torch.Tensor, lap, terms=REFERENCE_MESH_TERMS,
@@ -256,18 +214,7 @@ def mesh_terms_and_grad(verts: torch.Tensor, verts_orig: torch.Tensor, lap, term
     loss = out if out is not None else torch.empty((2,), dtype=torch.float32, device=dev)
     if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
         raise RuntimeError("mesh_terms_and_grad: `out` is a contiguous 2-element float32 tensor on the vertices' device")
-    L = _lib.lib()
-    ws = workspace
-    if ws is None:
-        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        ws = _mesh_workspace.get(key)
-        if ws is None:
-            if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
-                raise RuntimeError("mesh_terms_and_grad: first call on this stream happens inside a graph capture; call it "
-                                   "once eagerly on the stream first, or pass workspace=mesh_terms_workspace(device)")
-            ws = _mesh_workspace[key] = mesh_terms_workspace(dev)
-    elif not (ws.is_cuda and ws.device == dev and ws.dtype == torch.uint8 and ws.numel() >= L.fr_mesh_terms_workspace_bytes()):
-        raise RuntimeError("mesh_terms_and_grad: workspace must come from mesh_terms_workspace() on the vertices' device")
+    ws = _mesh_ws.resolve(dev, workspace, "mesh_terms_and_grad")
     import ctypes as C
     cfg = _lib.fr_mesh_terms_config(float(terms[0]), float(terms[1]))
     # (a mesh without edges has an empty `col` nobody reads; the entry point refuses NULL, and an empty tensor has no address)
@@ -377,7 +324,17 @@ class ImageLoss(NamedTuple):
     dssim_weight: float
 
 
-_image_workspace = {}   # (device index, stream handle) -> workspace of fr_image_loss_grad (as _workspace above), see _default_image_workspace
+def _image_bytes(C: int, H: int, W: int) -> int:
+    if min(int(C), int(H), int(W)) < 1:
+        raise RuntimeError("image_loss_workspace: C, H, W >= 1")
+    return _lib.lib().fr_image_loss_workspace_bytes(int(C), int(H), int(W))
+
+
+# (its size depends on the image: the stream's own is grown to the largest shape asked for — one buffer per stream, not one per
+# shape: the maps take 12 bytes per pixel and channel)
+_image_ws = StreamWorkspace("image_loss_workspace", _image_bytes, "images'", first="the first call for this image size",
+                            maker_args="device, C, H, W")
+_image_workspace = _image_ws.kept   # (device index, stream handle) -> workspace of fr_image_loss_grad
 
 
 def ssim_window() -> torch.Tensor:
@@ -390,9 +347,8 @@ def ssim_window() -> torch.Tensor:
 
 def image_loss_workspace(dev: torch.device, C: int, H: int, W: int) -> torch.Tensor:
     """A fresh zeroed workspace for `image_loss_and_grad(..., workspace=)` on [C,H,W] images."""
-    if min(int(C), int(H), int(W)) < 1:
-        raise RuntimeError("image_loss_workspace: C, H, W >= 1")
-    return torch.zeros((_lib.lib().fr_image_loss_workspace_bytes(int(C), int(H), int(W)),), dtype=torch.uint8, device=dev)
+    _image_bytes(C, H, W)   # (the shape is refused before the device)
+    return _image_ws.fresh(dev, C, H, W)
 
 
 def _chw(t: torch.Tensor, what: str):
@@ -436,20 +392,6 @@ def image_loss_and_grad_batch(imgs, gts, weights, loss_outs, grad_outs, workspac
     return loss_outs, grad_outs
 
 
-def _default_image_workspace(dev: torch.device, shape, what: str) -> torch.Tensor:
-    """The (device, current stream)'s own workspace, grown to the largest shape asked for (one buffer per stream, not one per
-    shape: the maps take 12 bytes per pixel and channel)."""
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    need = _lib.lib().fr_image_loss_workspace_bytes(*shape)
-    ws = _image_workspace.get(key)
-    if ws is None or ws.numel() < need:
-        if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
-            raise RuntimeError(f"{what}: the first call for this image size on this stream happens inside a graph capture; call it "
-                               "once eagerly on the stream first, or pass workspace=image_loss_workspace(device, C, H, W)")
-        ws = _image_workspace[key] = image_loss_workspace(dev, *shape)
-    return ws
-
-
 def image_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, weights, loss_out: Optional[torch.Tensor] = None,
                         grad_out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None
                         ) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -475,7 +417,8 @@ def image_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, weights, loss_out: 
     if (grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != dev
             or loss.numel() != 3 or loss.dtype != torch.float32 or loss.device != dev or not loss.is_contiguous()):
         raise RuntimeError("image_loss_and_grad: bad output buffers (gradient of the image's shape, 3-element loss, float32, contiguous)")
-    ws = workspace if workspace is not None else _default_image_workspace(dev, shape, "image_loss_and_grad")
+    # (a caller's workspace is checked by image_loss_and_grad_batch, which names the bytes this shape takes)
+    ws = workspace if workspace is not None else _image_ws.resolve(dev, None, "image_loss_and_grad", need=shape)
     image_loss_and_grad_batch([img], [gt], weights, [loss], [grad], [ws])
     return loss, grad
 
@@ -490,7 +433,7 @@ class _DSsim(torch.autograd.Function):
         x, y = img1.detach().float().contiguous(), img2.detach().float().contiguous()
         grad = torch.empty_like(x) if ctx.needs_input_grad[0] else None     # None: losses only, pass 2 is not launched
         loss = torch.empty(3, dtype=torch.float32, device=x.device)
-        image_loss_and_grad_batch([x], [y], (0.0, 1.0), [loss], [grad], [_default_image_workspace(x.device, _chw(x, "d_ssim"), "d_ssim")])
+        image_loss_and_grad_batch([x], [y], (0.0, 1.0), [loss], [grad], [_image_ws.resolve(x.device, None, "d_ssim", need=_chw(x, "d_ssim"))])
         if grad is not None:
             ctx.save_for_backward(grad.view(img1.shape))
         ctx.in_dtype = img1.dtype

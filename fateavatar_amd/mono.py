@@ -33,6 +33,7 @@ import torch
 from . import _lib
 from .binding import _grad_buffer
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, GradOut
+from .workspace import StreamWorkspace
 
 POSE_FEATURES = _lib.FR_LBS_POSE_FEATURES
 
@@ -70,35 +71,14 @@ def _no_pose_gradient(state, which):
                            "hand it detached tensors")
 
 
-_pose_workspace = {}    # (device index, stream handle) -> zeroed scratch of fr_point_lbs_backward_pose
+_pose_ws = StreamWorkspace("pose_workspace", lambda: _lib.lib().fr_point_lbs_pose_workspace_bytes(), "points'",
+                           first="first call with frame_grad=True")
+_terms_ws = StreamWorkspace("lbs_terms_workspace", lambda: _lib.lib().fr_lbs_terms_workspace_bytes(), "predictions'")
 
 
 def pose_workspace(dev) -> torch.Tensor:
     """A fresh zeroed workspace for `deform_points(..., frame_grad=True, workspace=)`."""
-    if not isinstance(dev, (torch.device, str, int)):
-        raise RuntimeError(f"pose_workspace: a device, not {type(dev).__name__}")
-    dev = torch.device("cuda", dev) if isinstance(dev, int) else torch.device(dev)
-    if dev.type != "cuda":
-        raise RuntimeError(f"pose_workspace: a HIP device, not {dev} (there is no CPU path)")
-    return torch.zeros((_lib.lib().fr_point_lbs_pose_workspace_bytes(),), dtype=torch.uint8, device=dev)
-
-
-def _pose_workspace_for(dev, workspace):
-    """`workspace` checked, or the one kept for (device, current stream): made on the first call, which must not be captured."""
-    who = "deform_points"
-    if workspace is not None:
-        if not (workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
-                and workspace.numel() >= _lib.lib().fr_point_lbs_pose_workspace_bytes()):
-            raise RuntimeError(f"{who}: workspace must come from pose_workspace() on the points' device")
-        return workspace
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _pose_workspace.get(key)
-    if ws is None:
-        if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
-            raise RuntimeError(f"{who}: first call with frame_grad=True on this stream happens inside a graph capture; call it once "
-                               "eagerly on the stream first, or pass workspace=pose_workspace(device)")
-        ws = _pose_workspace[key] = pose_workspace(dev)
-    return ws
+    return _pose_ws.fresh(dev)
 
 
 def _pose(state, E, J, which):
@@ -136,7 +116,7 @@ class _Deform(torch.autograd.Function):
         canonical, frame = _pose(pose[:3], E, J, "canonical"), _pose(pose[3:], E, J, "frame")
         dev = _one_device(who, points, S, P, w, *canonical, *frame)
         # (the workspace is settled here, where the caller called, not on the backward's thread)
-        ctx.workspace = _pose_workspace_for(dev, workspace) if any(ctx.needs_input_grad[8:11]) else None
+        ctx.workspace = _pose_ws.resolve(dev, workspace, "deform_points") if any(ctx.needs_input_grad[8:11]) else None
         ctx.frame_shapes = tuple(tuple(t.shape) for t in pose[3:])
         xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
         d = _describe(points, S, P, w, canonical, frame)
@@ -234,12 +214,9 @@ def reference_lbs_weights(lbs_weight: float = 10.0, var_expression=None) -> LbsW
     return LbsWeights(0.1 * w, 1000.0 * w, 1000.0 * w * float((1.0 / var).mean()) / 50.0)
 
 
-_terms_workspace = {}   # (device index, stream handle) -> zeroed scratch of fr_lbs_terms
-
-
 def lbs_terms_workspace(dev: torch.device) -> torch.Tensor:
     """A fresh zeroed workspace for `lbs_terms_and_grad(..., workspace=)`."""
-    return torch.zeros((_lib.lib().fr_lbs_terms_workspace_bytes(),), dtype=torch.uint8, device=dev)
+    return _terms_ws.fresh(dev)
 
 
 def lbs_terms_and_grad(index, lbs_weights, posedirs, shapedirs, gt_weights, gt_posedirs, gt_shapedirs,
@@ -277,18 +254,7 @@ def lbs_terms_and_grad(index, lbs_weights, posedirs, shapedirs, gt_weights, gt_p
     loss = out if out is not None else (torch.empty if N else torch.zeros)((3,), dtype=torch.float32, device=dev)
     if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != 3 or not loss.is_contiguous():
         raise RuntimeError(f"{who}: `out` is a contiguous 3-element float32 tensor on the predictions' device")
-    L = _lib.lib()
-    ws = workspace
-    if ws is None:
-        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        ws = _terms_workspace.get(key)
-        if ws is None:
-            if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
-                raise RuntimeError(f"{who}: first call on this stream happens inside a graph capture; call it once eagerly on "
-                                   "the stream first, or pass workspace=lbs_terms_workspace(device)")
-            ws = _terms_workspace[key] = lbs_terms_workspace(dev)
-    elif not (ws.is_cuda and ws.device == dev and ws.dtype == torch.uint8 and ws.numel() >= L.fr_lbs_terms_workspace_bytes()):
-        raise RuntimeError(f"{who}: workspace must come from lbs_terms_workspace() on the predictions' device")
+    ws = _terms_ws.resolve(dev, workspace, who)
     if N == 0:
         return loss
     cfg = _lib.fr_lbs_terms_config(*[float(x) for x in terms])

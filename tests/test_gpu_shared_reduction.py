@@ -1,0 +1,121 @@
+"""The fused loss kernels end with ONE reduction (sum_over_workgroups, csrc/fr_common.hpp): per-workgroup partials, added up by
+the workgroup that finishes last, which leaves the workspace as it found it.  Every user of it is run here at the workgroup
+counts where that tail changes its path: 1, 15, 16 and 17 (last_workgroup_of's counter groups fill up at 16), the op's grid cap
+(four partials per thread of the last workgroup) and one past it (the grid stays at the cap and sweeps twice).  Everything
+asserted is exact: equal bits from launch to launch and from a fresh workspace, and a zero workspace afterwards.  The values
+against float64 are held by the ops' own tests."""
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+CAP = 1024                      # kL1MaxBlocks = kRegMaxBlocks = kMeshMaxBlocks = kTermsMaxBlocks
+COUNTS = (1, 15, 16, 17, CAP, CAP + 1)
+COUNTER_BYTES = 17 * 128        # (kDoneGroups + 1) counters, one 128-byte line each
+# [C,H,W] -> C x ceil(H / 32) x ceil(W / 32) workgroups; the image loss has no cap
+IMAGE_SHAPES = {1: (1, 32, 32), 15: (3, 32, 160), 16: (1, 128, 128), 17: (1, 32, 544)}
+
+
+def _rand(gen, *shape):
+    import torch
+    return torch.rand(*shape, generator=gen, dtype=torch.float32)
+
+
+def _l1(b, dev, gen):
+    from fateavatar_amd.loss import l1_loss_and_grad, l1_workspace
+    n = 1024 * b + 3
+    x, y = _rand(gen, n).to(dev), _rand(gen, n).to(dev)
+    return (lambda ws: list(l1_loss_and_grad(x, y, workspace=ws))), (lambda: l1_workspace(dev))
+
+
+def _l1_terms(b, dev, gen):
+    """fr_image_loss_grad with a D-SSIM weight of 0: the L1 kernel's instance that zeroes its partials.  1024 b + 2 floats as
+    two rows (the entry point takes rows of up to 2^20 pixels): b workgroups and a tail of two."""
+    from fateavatar_amd.loss import image_loss_and_grad, image_loss_workspace
+    shape = (1, 2, 512 * b + 1)
+    x, y = _rand(gen, *shape).to(dev), _rand(gen, *shape).to(dev)
+    return (lambda ws: list(image_loss_and_grad(x, y, (0.8, 0.0), workspace=ws))), (lambda: image_loss_workspace(dev, *shape))
+
+
+def _huber(b, dev, gen):
+    from fateavatar_amd.loss import huber_loss_and_grad, huber_workspace
+    n = 1024 * b + 3
+    x, y, m = _rand(gen, 1, 1, n).to(dev), _rand(gen, 1, 1, n).to(dev), _rand(gen, 1, n).to(dev)
+    return (lambda ws: list(huber_loss_and_grad(x, y, mask=m, workspace=ws))), (lambda: huber_workspace(dev))
+
+
+def _regulariser(b, dev, gen):
+    import torch
+    from fateavatar_amd.loss import gaussian_regularisers, regulariser_workspace
+    P = 256 * b
+    scaling, xyz = (_rand(gen, P, 3) - 0.7).to(dev), (2.0 * _rand(gen, P, 3)).to(dev)      # both sides of both thresholds
+
+    def run(ws):
+        d_s, d_x = torch.zeros_like(scaling), torch.zeros_like(xyz)
+        return [gaussian_regularisers(scaling, xyz, d_s, d_x, workspace=ws).clone(), d_s, d_x]
+    return run, (lambda: regulariser_workspace(dev))
+
+
+def _mesh(b, dev, gen):
+    import torch
+    from fateavatar_amd.binding import mesh_laplacian
+    from fateavatar_amd.loss import MeshTerms, mesh_terms_and_grad, mesh_terms_workspace
+    V = 32 * b
+    i = torch.arange(V)
+    lap = mesh_laplacian(torch.stack([i, (i + 1) % V, (i + 2) % V], dim=1).to(dev), V)     # a closed ring: neighbours i +- 1, i +- 2
+    verts, orig = _rand(gen, V, 3).to(dev), _rand(gen, V, 3).to(dev)
+
+    def run(ws):
+        d = torch.zeros_like(verts)
+        return [mesh_terms_and_grad(verts, orig, lap, MeshTerms(1e3, 0.3), d_verts=d, workspace=ws).clone(), d]
+    return run, (lambda: mesh_terms_workspace(dev))
+
+
+def _lbs(b, dev, gen):
+    import torch
+    from fateavatar_amd.mono import LbsWeights, lbs_terms_and_grad, lbs_terms_workspace
+    N, V, E, J = 16 * b, 5, 1, 1
+    index = torch.randint(0, V, (N,), generator=gen, dtype=torch.int32).to(dev)
+    pred = [_rand(gen, N, J).to(dev), _rand(gen, N, 36, 3).to(dev), _rand(gen, N, 3, E).to(dev)]
+    gt = [_rand(gen, V, J).to(dev), _rand(gen, V, 36, 3).to(dev), _rand(gen, V, 3, E).to(dev)]
+
+    def run(ws):
+        bufs = [torch.zeros_like(t) for t in pred]
+        return [lbs_terms_and_grad(index, *pred, *gt, LbsWeights(0.5, 2.0, 3.0), *bufs, workspace=ws).clone()] + bufs
+    return run, (lambda: lbs_terms_workspace(dev))
+
+
+def _image(b, dev, gen):
+    from fateavatar_amd.loss import image_loss_and_grad, image_loss_workspace
+    shape = IMAGE_SHAPES[b]
+    x, y = _rand(gen, *shape).to(dev), _rand(gen, *shape).to(dev)
+    return (lambda ws: list(image_loss_and_grad(x, y, (0.8, 0.2), workspace=ws))), (lambda: image_loss_workspace(dev, *shape))
+
+
+# op -> (case builder, partial floats the kernel promises to leave zeroed; None: no promise), with the counts it is run at
+OPS = {"l1": (_l1, None), "l1_terms": (_l1_terms, CAP), "huber": (_huber, 2 * CAP), "regulariser": (_regulariser, 2 * CAP),
+       "mesh": (_mesh, 2 * CAP), "lbs": (_lbs, 3 * CAP), "image": (_image, 0)}
+CASES = [(op, b) for op in OPS for b in (IMAGE_SHAPES if op == "image" else COUNTS)]
+
+
+@pytest.mark.parametrize("op,b", CASES, ids=[f"{op}-{b}" for op, b in CASES])
+def test_same_bits_on_every_launch_and_the_workspace_left_zeroed(gpu_device, op, b):
+    import torch
+    dev = gpu_device
+    build, partial_floats = OPS[op]
+    run, fresh = build(b, dev, torch.Generator().manual_seed(1000 + b))
+    if op == "image":
+        partial_floats = 2 * b
+
+    def launch(ws):
+        outs = run(ws)
+        torch.cuda.synchronize()
+        assert int(ws[:COUNTER_BYTES].count_nonzero()) == 0, "counters"
+        if partial_floats is not None:
+            assert int(ws[COUNTER_BYTES:COUNTER_BYTES + 4 * partial_floats].count_nonzero()) == 0, "partials"
+        return [o.clone() for o in outs]
+
+    ws = fresh()
+    first, second, other = launch(ws), launch(ws), launch(fresh())
+    assert float(first[0].abs().max()) > 0                     # (the sums saw data)
+    for a, s, o in zip(first, second, other):
+        assert torch.equal(a.view(torch.int32), s.view(torch.int32)) and torch.equal(a.view(torch.int32), o.view(torch.int32))
