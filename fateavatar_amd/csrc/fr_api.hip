@@ -1,6 +1,6 @@
 // extern "C" entry points declared in include/fr_rasterizer.h.  Argument checking, handle
-// lifetime, error strings; the work is in fr_preprocess.hip / fr_blend.hip /
-// fr_preprocess_bwd.hip / fr_knn.hip.
+// lifetime, error strings; the work is in fr_preprocess.hip / fr_tile_sort.hip / fr_blend_fwd.hip /
+// fr_blend_bwd.hip / fr_preprocess_bwd.hip / fr_knn.hip.
 #include "fr_common.hpp"
 #include <cstdio>
 #include <cstdlib>

@@ -70,7 +70,7 @@ __host__ __device__ static inline T* carve(char*& p, size_t count)
 struct GeomView {
     float4* rec_tmpl;       // [P*3] the 48-byte splat RECORD the blend kernels gather for every (tile, Gaussian) instance:
                             // (x, y, a', b'), (c', opacity, r, g), (b, id, depth, 0) with the pixel-space centre, the
-                            // conic as (a', b', c') = (-0.5 a, -b, -0.5 c) (fr_blend.hip: pair_power) and the colour fed to the blend (SH result or
+                            // conic as (a', b', c') = (-0.5 a, -b, -0.5 c) (fr_tile.hpp: pair_power) and the colour fed to the blend (SH result or
                             // colors_precomp) — ONE 48-byte gather per instance, not three
     float* opacity_act;     // [P] the activated opacity (the backward's API does not take the opacities; the conic is NOT stored:
                             // k_preprocess_bwd computes the 2D covariance again anyway and inverts it with the forward's expressions)
@@ -412,7 +412,7 @@ struct BackwardCall {
 // (grid, n) launch.  Every view has its own handle and buffers; the views' frames are independent of each other.
 int launch_forward(int n, const ForwardCall* calls, hipStream_t s);
 int launch_backward(int n, const BackwardCall* calls, hipStream_t s);
-// what launch_forward has prepared per view when it hands over to the sort + blend launches (fr_blend.hip)
+// what launch_forward has prepared per view when it hands over to launch_tile_sort and launch_blend_forward
 struct FrameView {
     fr_handle_impl* h;
     const fr_params* prm;
@@ -426,6 +426,20 @@ struct FrameView {
     float* out_depth;
     float* out_alpha;
 };
+// The per-tile stages of n views: the depth sort of every tile's list (fr_tile_sort.hip), then the forward blend
+// (fr_blend_fwd.hip); and the blend backward (fr_blend_bwd.hip; the views' accumulators in g[k].accum; `planes`: the views'
+// plane gradients, fr_aux::dL_ddepth / dL_dalpha, go in too).
+int launch_tile_sort(int n, const FrameView* f, hipStream_t s, bool debug);
+int launch_blend_forward(int n, const FrameView* f, hipStream_t s, bool debug);
+int launch_blend_backward(int n, const BackwardCall* calls, const GeomView* g, const ImageView* v, bool planes, hipStream_t s, bool debug);
+// after a stage of a debug frame (fr_params::debug): wait for it, so that a fault is reported under the stage's name
+static inline int debug_sync(bool debug, hipStream_t s, const char* stage)
+{
+    if (!debug) return FR_OK;
+    hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail_hip(e, stage, __FILE__, __LINE__);
+    return FR_OK;
+}
 // kernel for one view, its *_batch twin for several: the twin takes BatchOf<A> and a (gx, n) grid
 template <typename A, typename KS, typename KB>
 static inline void launch_views(KS single, KB batch, int n, const A* args, uint32_t gx, uint32_t threads, size_t lds, hipStream_t s)

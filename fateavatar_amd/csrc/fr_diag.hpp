@@ -1,4 +1,4 @@
-// Development-only instrumentation of the blend kernels, compiled out of the product build.
+// Development-only instrumentation of the blend backward (fr_blend_bwd.hip), compiled out of the product build.
 //   -DFR_DIAG_STATS   per-launch iteration accounting of k_unit_blend_bwd_sparse in DeviceCounts::pair_hist
 //                     (tools/diag/bwd_stats.sh builds and reads it)
 // The product translation units only ever see the empty forms of these macros.
@@ -61,20 +61,5 @@ extern "C" int fr_diag_read_trace(void* dst, size_t bytes)
 #define FR_ABLATE(k) false
 #endif
 
-//   -DFR_DIAG_FWD_TRACE   per-unit time stamps of k_unit_blend_chained's phases (tools/diag/fwd_trace.py)
-#ifdef FR_DIAG_FWD_TRACE
-namespace fr {
-__device__ unsigned long long g_fwd_trace[16384 * 16];
-}
-extern "C" int fr_debug_read_fwd_trace(void* dst, size_t bytes)
-{
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(fr::g_fwd_trace), bytes < sizeof(fr::g_fwd_trace) ? bytes : sizeof(fr::g_fwd_trace));
-}
-#define FW_STAMP(K) do { if (lane == 0 && u < 16384u) ::fr::g_fwd_trace[(size_t)u * 16 + (K)] = __builtin_readcyclecounter(); } while (0)
-#define FW_STAMPV(K, V) do { if (lane == 0 && u < 16384u) ::fr::g_fwd_trace[(size_t)u * 16 + (K)] = (unsigned long long)(V); } while (0)
-#else
-#define FW_STAMP(K) do { } while (0)
-#define FW_STAMPV(K, V) do { } while (0)
-#endif
-
-// (fr_preprocess.hip has its own timing-experiment switch, -DFR_DIAG_PRE_ABLATE=mask, defined at its head)
+// (the switches of the other units are defined at their heads, so that each trace buffer and its reader exist once in the
+// library: -DFR_DIAG_FWD_TRACE in fr_blend_fwd.hip, -DFR_DIAG_PRE_ABLATE=mask in fr_preprocess.hip)

@@ -864,17 +864,6 @@ int launch_mark_visible(int P, const float* means3D, const float* view, uint8_t*
     return FR_OK;
 }
 
-// implemented in fr_blend.hip
-int launch_sort_and_blend(int n, const FrameView* f, hipStream_t s, bool debug);
-
-static int debug_sync(bool debug, hipStream_t s, const char* stage)
-{
-    if (!debug) return FR_OK;
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail_hip(e, stage, __FILE__, __LINE__);
-    return FR_OK;
-}
-
 // The handle's buffers (gradient accumulators, per-tile counters, key buckets) grow with the scene and the tile grid.
 // Growing means hipMalloc (and freeing or retiring the old buffer), which a capturing stream does not allow — and trying
 // would invalidate the caller's capture.  Asked for EVERY view of a call before any of them touches the stream or a handle.
@@ -1022,7 +1011,8 @@ int launch_forward(int n, const ForwardCall* calls, hipStream_t s)
     }
     FR_HIP(hipGetLastError());
     if ((rc = debug_sync(debug, s, "scan_tiles"))) return rc;
-    if ((rc = launch_sort_and_blend(n, f, s, debug))) return rc;
+    if ((rc = launch_tile_sort(n, f, s, debug))) return rc;
+    if ((rc = launch_blend_forward(n, f, s, debug))) return rc;
     for (int k = 0; k < n; k++) {
         fr_handle_impl* h = calls[k].h;
         h->counters_clean = true;

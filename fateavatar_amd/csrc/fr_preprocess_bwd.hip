@@ -673,10 +673,6 @@ __global__ void __launch_bounds__(64 * kPreBwdWaves) k_preprocess_bwd_batch(Batc
 __global__ void __launch_bounds__(64 * kPreBwdWaves) k_preprocess_bwd_planes(PreBwdArgs a) { preprocess_bwd_body<true>(a); }
 __global__ void __launch_bounds__(64 * kPreBwdWaves) k_preprocess_bwd_planes_batch(BatchOf<PreBwdArgs> b) { preprocess_bwd_body<true>(b.v[blockIdx.y]); }
 
-// implemented in fr_blend.hip: the blend backward of n views (their accumulators in g[k].accum); `planes`: the views'
-// plane gradients (fr_aux::dL_ddepth / dL_dalpha) go in too
-int launch_blend_backward(int n, const BackwardCall* calls, const GeomView* g, const ImageView* v, bool planes, hipStream_t s, bool debug);
-
 int launch_backward(int n, const BackwardCall* calls, hipStream_t s)
 {
     GeomView g[kMaxBatch];

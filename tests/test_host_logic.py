@@ -229,7 +229,7 @@ def test_handle_slot_is_scoped():
 
 
 def test_backward_work_list_stripe_assignment_is_exact():
-    """The blend backward's work list (fateavatar_amd/csrc/fr_blend.hip, k_unit_blend_chained: "Which stripe?") deals the
+    """The blend backward's work list (fateavatar_amd/csrc/fr_blend_fwd.hip, k_unit_blend_chained: "Which stripe?") deals the
     units out to 64 stripes so that the eight stripes whose slots run on XCD x hold a CONTIGUOUS run of units, and fills
     every stripe exactly: stripe j owns slots j, j + 64, ... < nu, and the two-ended cursors only work if exactly that
     many units are sent to it.  The arithmetic, restated here, must be a perfect deal for every unit count."""
