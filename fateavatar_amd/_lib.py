@@ -21,6 +21,7 @@ FR_FLAG_NO_WAIT = 1
 FR_FLAG_RAW_ACTIVATIONS = 2
 FR_FLAG_FORWARD_ONLY = 4       # fr_forward: a frame no backward follows (no backward hand-off is written)
 FR_FLAG_DEPTH_ALPHA = 8        # depth and alpha planes next to the image (fr_aux::out_depth / out_alpha, their gradients)
+FR_FLAG_CAMERA_GRAD = 16       # fr_backward: also dL/d(viewmatrix, projmatrix, campos) (fr_aux_camera::d_viewmatrix / d_projmatrix / d_campos)
 FR_FLAG_ACCUMULATE_SHIFT = 8   # fr_backward: bit (8 + k) = add into the k-th array of fr_grads
 FR_BIND_SHELL = 0              # fr_binding::mode: FateAvatar's barycentric point + shell offset (a zeroed descriptor)
 FR_BIND_FACE_LOCAL = 1         # GaussianAvatars': a free position in the face's local frame (fr_binding::local_xyz)
@@ -53,6 +54,16 @@ class fr_aux(C.Structure):
                 ("d_local_xyz", C.c_void_p),
                 ("out_depth", C.c_void_p), ("out_alpha", C.c_void_p), ("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p),
                 ("planes", C.c_void_p)]
+
+
+class fr_aux_camera(C.Structure):
+    """The side block of a backward with FR_FLAG_CAMERA_GRAD: fr_aux with the camera's members behind it.  `as_aux()` is the
+    `base` member as an fr_aux that SHARES this object's memory (and keeps it alive): what fr_params::aux points at."""
+    _fields_ = [("base", fr_aux), ("d_viewmatrix", C.c_void_p), ("d_projmatrix", C.c_void_p), ("d_campos", C.c_void_p),
+                ("camera_workspace", C.c_void_p)]
+
+    def as_aux(self) -> fr_aux:
+        return fr_aux.from_buffer(self)
 
 
 class fr_params(C.Structure):
@@ -137,7 +148,7 @@ class fr_counts(C.Structure):
 
 
 EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile_enable", "fr_profile_read", "fr_geometry_bytes", "fr_image_bytes",
-           "fr_binning_bytes", "fr_planes_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
+           "fr_binning_bytes", "fr_planes_bytes", "fr_camera_grad_workspace_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
            "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_huber_workspace_bytes", "fr_huber_loss_grad", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_mesh_terms_workspace_bytes", "fr_mesh_terms", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
            "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_bind_backward_deform", "fr_phong_frame", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward",
            "fr_point_lbs_forward", "fr_point_lbs_backward", "fr_point_lbs_pose_workspace_bytes", "fr_point_lbs_backward_pose", "fr_nearest_vertex", "fr_lbs_terms_workspace_bytes", "fr_lbs_terms"]
@@ -186,6 +197,8 @@ def lib():
     L.fr_binning_bytes.restype = C.c_size_t
     L.fr_planes_bytes.argtypes = [C.c_uint64, C.c_int32, C.c_int32]
     L.fr_planes_bytes.restype = C.c_size_t
+    L.fr_camera_grad_workspace_bytes.argtypes = []
+    L.fr_camera_grad_workspace_bytes.restype = C.c_size_t
     L.fr_forward.argtypes = [C.c_void_p, C.POINTER(fr_params), C.POINTER(fr_inputs), _fp, _fp, _fp, _fp, _fp,
                              C.c_uint64, C.POINTER(fr_counts), C.c_void_p]
     L.fr_forward.restype = C.c_int

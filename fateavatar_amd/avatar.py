@@ -121,11 +121,12 @@ class AvatarStep(BoundStep):
     hand it this step's dLoss/dposed_verts."""
     LRS = FATE_LRS
     LR_KEYS = {"_opacity": "opacity", "_offset": "offset", "_features_dc": "color", "_rotation": "rotation", "_scaling": "scaling"}
+    CAMERA_GRAD = True
 
     def __init__(self, pc: AvatarGaussians, faces: torch.Tensor, canonical_verts: torch.Tensor, camera: TorchCamera,
                  bg: torch.Tensor, lrs: Optional[dict] = None, shell_len: float = 0.05, resize_scale: bool = True,
                  use_graph: bool = True, fold_binding: bool = True, keep_coherent: bool = False, vertex_grad: bool = False,
-                 mesh_terms: Optional[MeshTerms] = None):
+                 mesh_terms: Optional[MeshTerms] = None, camera_grad: bool = False):
         """`keep_coherent`: after every `uv_densify` the rows are re-stored in a spatially coherent order (`sort_coherent`):
         the reference appends the new rows at the end (model/fateavatar.py:640-665), so a set that started in UV-raster
         order (mesh_sampling.py:86-138: neighbours in storage are neighbours on the mesh) grows an unordered tail; the
@@ -140,11 +141,13 @@ class AvatarStep(BoundStep):
         mesh the posed one is held to (the reference's `verts_orig`: the FLAME mesh without the learnt deltas, same pose) as
         one more static input, and ONE launch behind the rasterizer's backward (`loss.mesh_terms_and_grad`) adds the terms'
         weighted gradient into `d_verts`; `mesh_loss` then holds the step's unweighted (laplacian_loss, flame_loss), `loss`
-        stays the image term.  Implies `vertex_grad`.  None (default): no such launch, `mesh_loss` is None."""
+        stays the image term.  Implies `vertex_grad`.  None (default): no such launch, `mesh_loss` is None.
+        `camera_grad`: `d_view` / `d_proj` / `d_campos` hold every step's dLoss/d(camera) (BoundStep): what a per-frame camera
+        embedding (the reference's `cam_pose`, train/base.py:123,142) trains on."""
         self.keep_coherent = bool(keep_coherent)
         self.mesh_terms = None if mesh_terms is None else MeshTerms(*[float(x) for x in mesh_terms])
         super().__init__(pc, faces, camera, bg, canonical_verts, lrs, use_graph, fold_binding,
-                         vertex_grad=bool(vertex_grad) or mesh_terms is not None)
+                         vertex_grad=bool(vertex_grad) or mesh_terms is not None, camera_grad=camera_grad)
         self.mesh_loss = self.verts_orig = self.laplacian = self._mesh_ws = None
         if self.mesh_terms is not None:
             from .binding import mesh_laplacian
@@ -165,19 +168,20 @@ class AvatarStep(BoundStep):
         _dimage, xyz_gradient_accum, denom, out: this object itself, or one lane of an AvatarBatchStep."""
         pc = L.pc
         pc.begin_step()                                             # zero_grad(set_to_none=True), iteration.py:48-49
-        verts = self._vertex_leaf(L.verts)
+        verts, cam = self._vertex_leaf(L.verts), self._camera_leaf(L.cam)
         if self.fold_binding:
             from . import rasterizer
-            out = render_bound_batch([L.cam], [_RawFrame(pc, (L.xyz_gradient_accum, L.denom, pc.overflow_word))], [verts], self._binding(pc),
+            out = render_bound_batch([cam], [_RawFrame(pc, (L.xyz_gradient_accum, L.denom, pc.overflow_word))], [verts], self._binding(pc),
                                      self.bg, slots=[rasterizer._slot])[0]
         else:
             xyz, rot, scl = bind_gaussians(verts, self.faces, pc.face_index, pc.bary_coords, self.face_scale_canonical,
                                            pc._offset, pc._rotation, pc._scaling, self.shell_len, self.resize_scale)
             frame = _BoundFrame(xyz, pc, rot, scl, (L.xyz_gradient_accum, L.denom, pc.overflow_word))
-            out = render(L.cam, frame, self.bg)
+            out = render(cam, frame, self.bg)
         _, g = l1_loss_and_grad(out["render"], L.gt, loss_out=L.loss, grad_out=L._dimage, workspace=L._l1_ws)   # see TrainStep
         out["render"].backward(g)
         self._keep_vertex_grad(verts)
+        self._keep_camera_grad(cam)
         if self.mesh_terms is not None:
             # train/loss.py:112-121: weight x the mesh terms' gradient is ADDED to the image term's dL/dposed_verts.  A replay
             # that overflowed its binning capacity back-propagated zeros: d_verts then holds the mesh terms alone.
@@ -290,6 +294,8 @@ class AvatarBatchStep(AvatarStep):
         from . import _lib
         if not 1 <= int(views_per_step) <= _lib.FR_ADAM_MAX_GRADS:
             raise ValueError(f"views_per_step must be 1..{_lib.FR_ADAM_MAX_GRADS}")
+        if kw.get("camera_grad"):
+            raise NotImplementedError("AvatarBatchStep: `camera_grad` is not built for the batch step: use AvatarStep")
         if kw.get("vertex_grad") or kw.get("mesh_terms") is not None:
             raise NotImplementedError("AvatarBatchStep: `vertex_grad` / `mesh_terms` are not built for the batch step (two step "
                                       "bodies, and its twelve multi_copy segments are used up at K = 4): use AvatarStep")

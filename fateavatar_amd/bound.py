@@ -29,8 +29,8 @@ import torch
 from . import _lib
 from .binding import (DEFORM, FACE_LOCAL, PHONG, SHELL, PhongCanonical, _check_shapes, _chk, _chk_phong_frame, _describe, _grad_buffer,
                       _no_vertex_gradient, phong_frame)
-from .rasterizer import (_GRAD_NAMES, _any_grad, _backward_args, _forward_args, _forward_batch, _FrameGrads, _per_view_outputs,
-                         _pick_forward_only, _SavedFrame, rasterize_gaussians_backward_batch)
+from .rasterizer import (_GRAD_NAMES, _any_grad, _backward_args, _camera_grads, _camera_inputs_of, _forward_args, _forward_batch,
+                         _FrameGrads, _per_view_outputs, _pick_forward_only, _SavedFrame, rasterize_gaussians_backward_batch)
 from .render import _result, _screenspace_points, _settings
 
 
@@ -134,14 +134,16 @@ class DeformBinding(NamedTuple):
 class _RasterizeBoundBatch(torch.autograd.Function):
     """Tensor arguments per view: (verts, own, rotation, scaling, means2D, sh, opacities) — the RAW parameters, as render()
     hands them over with `fused_activations`; `own` is the binding's own per-Gaussian parameter (offset [N,1], the local
-    position [N,3], uvd [N,3], the MLP's outputs [N,10]: `BindMode.attr` of the holder).  Outputs per view: those of `_SavedFrame`."""
+    position [N,3], uvd [N,3], the MLP's outputs [N,10]: `BindMode.attr` of the holder); then — optionally — per view its settings'
+    (viewmatrix, projmatrix, campos), which then receive gradients (`rasterizer._camera_inputs`).  Outputs per view: those of
+    `_SavedFrame`."""
     PER_VIEW = 7
 
     @staticmethod
     def forward(ctx, settings, bindings, slots, forward_only, depth_alpha, *tensors):
         K, n = len(settings), _RasterizeBoundBatch.PER_VIEW
-        assert len(tensors) == n * K and len(bindings) == K
-        ctx.bindings, ctx.slots, ctx.own_shapes = bindings, slots, []
+        assert len(tensors) in (n * K, (n + 3) * K) and len(bindings) == K
+        ctx.bindings, ctx.slots, ctx.own_shapes, ctx.camera = bindings, slots, [], len(tensors) == (n + 3) * K
         empty = torch.Tensor([])
         views, viss, descs, bound, checked = [], [], [], [], []
         for k, (rs, mb) in enumerate(zip(settings, bindings)):
@@ -175,7 +177,7 @@ class _RasterizeBoundBatch(torch.autograd.Function):
     def backward(ctx, *grad_outs):
         K, n = len(ctx.frames), _RasterizeBoundBatch.PER_VIEW
         if not _any_grad(grad_outs):
-            return (None,) * (5 + n * K)
+            return (None,) * (5 + (n + 3 if ctx.camera else n) * K)
         empty = torch.Tensor([])
         views, outs, descs, bgrads, planes = [], [], [], [], []
         for k, (f, saved, fw, g, pl) in enumerate(_SavedFrame.load(ctx, grad_outs)):
@@ -194,15 +196,17 @@ class _RasterizeBoundBatch(torch.autograd.Function):
                            "d_scaling": _grad_buffer(need_s, claimed.get("d_scaling"), (N, 3), dev)})
         res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=[f.grads.want for f in ctx.frames],
                                                  outs=outs, stats=[f.stats for f in ctx.frames], bindings=descs, bind_grads=bgrads,
-                                                 planes=planes if ctx.frames[0].has_planes else None)
+                                                 planes=planes if ctx.frames[0].has_planes else None, camera=ctx.camera)
         flat = [None, None, None, None, None]
         for grads, b, mb, own_shape in zip(res, bgrads, ctx.bindings, ctx.own_shapes):
-            g = dict(zip(_GRAD_NAMES, grads))
+            g = dict(zip(_GRAD_NAMES, grads))   # (the eight per-Gaussian arrays; camera gradients, if any, come behind them)
             d_own = b[mb.mode.grad]
             d_own = d_own.view(own_shape) if d_own is not None else None
             # (fresh view objects: AccumulateGrad adopts a gradient without a copy only if nobody else references it)
             fresh = lambda t: t.view(t.shape) if t is not None else None  # noqa: E731
             flat += [b["d_verts"], d_own, fresh(b["d_rotation"]), fresh(b["d_scaling"]), g["dL_dmeans2D"], g["dL_dsh"], g["dL_dopacity"]]
+        if ctx.camera:
+            flat += [t for f, grads in zip(ctx.frames, res) for t in _camera_grads(f.rs, grads)]
         return tuple(flat)
 
 
@@ -251,6 +255,7 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding, bg_colors, 
         settings.append(rs)
         tensors += [verts, getattr(pc, mode.attr), pc._rotation, pc._scaling, sp, pc.get_features, pc._opacity]
         points.append(sp)
+    tensors += _camera_inputs_of(settings)
     res = _RasterizeBoundBatch.apply(settings, mbs, list(range(K)) if slots is None else list(slots),
                                      _pick_forward_only(tensors), bool(depth_alpha), *tensors)
     out = []

@@ -230,6 +230,8 @@ size_t fr_binning_bytes(uint64_t capacity, int32_t W, int32_t H)
     return BinningView::bytes((size_t)capacity, (size_t)v.tiles_x * v.tiles_y);
 }
 
+size_t fr_camera_grad_workspace_bytes(void) { return camera_grad_workspace_bytes(); }
+
 size_t fr_planes_bytes(uint64_t capacity, int32_t W, int32_t H)
 {
     ImageView v = ImageView::make(nullptr, W, H);
@@ -313,6 +315,12 @@ static int check_backward(const BackwardCall& c, bool batched)
                             "a depth or alpha gradient for a frame rendered without FR_FLAG_DEPTH_ALPHA: it has no planes to differentiate");
         if (!aux->planes) return fail_msg(FR_ERR_INVALID_ARGUMENT, "FR_FLAG_DEPTH_ALPHA with a plane gradient needs fr_aux::planes");
     }
+    if (c.prm->flags & FR_FLAG_CAMERA_GRAD) {
+        const fr_aux_camera* cam = reinterpret_cast<const fr_aux_camera*>(aux);   // (under the flag, aux is an fr_aux_camera's base)
+        if (!cam || (!cam->d_viewmatrix && !cam->d_projmatrix && !cam->d_campos))
+            return fail_msg(FR_ERR_INVALID_ARGUMENT, "FR_FLAG_CAMERA_GRAD needs one of fr_aux_camera::d_viewmatrix, d_projmatrix, d_campos");
+        if (!cam->camera_workspace) return fail_msg(FR_ERR_INVALID_ARGUMENT, "FR_FLAG_CAMERA_GRAD needs fr_aux_camera::camera_workspace");
+    }
     return FR_OK;
 }
 
@@ -342,6 +350,12 @@ int fr_backward_batch(int32_t n_views, fr_handle* const* handles, const fr_param
         if (rc) return rc;
         if ((prm[k]->flags ^ prm[0]->flags) & FR_FLAG_DEPTH_ALPHA)
             return fail_msg(FR_ERR_INVALID_ARGUMENT, "the views of a batch must agree on FR_FLAG_DEPTH_ALPHA");
+        if ((prm[k]->flags ^ prm[0]->flags) & FR_FLAG_CAMERA_GRAD)
+            return fail_msg(FR_ERR_INVALID_ARGUMENT, "the views of a batch must agree on FR_FLAG_CAMERA_GRAD");
+        for (int j = 0; j < k; j++)
+            if ((prm[k]->flags & FR_FLAG_CAMERA_GRAD) && reinterpret_cast<const fr_aux_camera*>(prm[j]->aux)->camera_workspace ==
+                                                             reinterpret_cast<const fr_aux_camera*>(prm[k]->aux)->camera_workspace)
+                return fail_msg(FR_ERR_INVALID_ARGUMENT, "the views of a batch need a camera_workspace each");
     }
     return launch_backward(n_views, c, static_cast<hipStream_t>(stream));
 }

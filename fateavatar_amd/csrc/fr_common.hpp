@@ -432,6 +432,10 @@ struct FrameView {
 int launch_tile_sort(int n, const FrameView* f, hipStream_t s, bool debug);
 int launch_blend_forward(int n, const FrameView* f, hipStream_t s, bool debug);
 int launch_blend_backward(int n, const BackwardCall* calls, const GeomView* g, const ImageView* v, bool planes, hipStream_t s, bool debug);
+// the camera-pose gradients of n views (fr_camera_bwd.hip; FR_FLAG_CAMERA_GRAD): reads the accumulator rows the blend backward
+// filled, so it goes between that and the per-Gaussian backward, which re-zeroes them
+int launch_camera_backward(int n, const BackwardCall* calls, const GeomView* g, const ImageView* v, hipStream_t s);
+size_t camera_grad_workspace_bytes();
 // after a stage of a debug frame (fr_params::debug): wait for it, so that a fault is reported under the stage's name
 static inline int debug_sync(bool debug, hipStream_t s, const char* stage)
 {

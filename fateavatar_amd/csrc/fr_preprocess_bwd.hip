@@ -735,6 +735,13 @@ int launch_backward(int n, const BackwardCall* calls, hipStream_t s)
     // g.accum is all zero here: zeroed when allocated, and again by k_preprocess_bwd after every backward
     int rc = launch_blend_backward(n, calls, g, v, planes, s, debug);
     if (rc) return rc;
+    // camera-pose gradients (FR_FLAG_CAMERA_GRAD, the views agree on it): they read the accumulator rows k_preprocess_bwd zeroes
+    if (calls[0].prm->flags & FR_FLAG_CAMERA_GRAD) {
+        rc = launch_camera_backward(n, calls, g, v, s);
+        if (rc) return rc;
+        rc = debug_sync(debug, s, "camera backward");
+        if (rc) return rc;
+    }
     {
         StageScope sc(calls[0].h, ST_PREPROCESS_BWD, s);
         if (planes) launch_views(k_preprocess_bwd_planes, k_preprocess_bwd_planes_batch, n, args, blocks, (uint32_t)wg, lds, s);

@@ -5,7 +5,9 @@
 //     rasterize_gaussians            RasterizeGaussiansCUDA            rasterize_points.cu:35-115
 //     rasterize_gaussians_backward   RasterizeGaussiansBackwardCUDA    rasterize_points.cu:117-196
 //     mark_visible                   markVisible                       rasterize_points.cu:198-217
-// plus distCUDA2 (simple-knn ext.cpp / spatial.cu:14-25).  The bodies are torch glue only — allocate the outputs and
+// plus distCUDA2 (simple-knn ext.cpp / spatial.cu:14-25) and ONE name the reference does not have,
+//     rasterize_gaussians_backward_camera   rasterize_gaussians_backward + dL/d(viewmatrix, projmatrix, campos)
+// (FR_FLAG_CAMERA_GRAD: the reference's binding returns nothing for the camera).  The bodies are torch glue only — allocate the outputs and
 // the three opaque byte buffers with the caching allocator, pass data pointers and the current HIP stream to
 // libfr_hip.so.  Where the reference calls CudaRasterizer::Rasterizer::{forward,backward,markVisible} this calls
 // fr_forward / fr_backward / fr_mark_visible.  Built by __graft_entry__.build() (torch.utils.cpp_extension, host
@@ -24,6 +26,7 @@ namespace {
 struct DeviceState {
     fr_handle* handle = nullptr;
     uint64_t capacity = 0;  // high-water mark of the binning capacity (instances)
+    torch::Tensor camera_ws;  // fr_aux_camera::camera_workspace of this handle's backward passes: zeroed once, left zeroed by the kernel
 };
 
 std::mutex g_mutex;
@@ -97,14 +100,18 @@ RasterizeGaussiansCUDA(const torch::Tensor& background, const torch::Tensor& mea
     return std::make_tuple((int)counts.num_rendered, out_color, radii, geom, binning, img);
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
-RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
-                               const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
-                               const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
-                               const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
-                               const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree,
-                               const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
-                               const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug)
+namespace {
+using Grads8 = std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>;
+
+// camera: non-null = the (d_viewmatrix [4,4], d_projmatrix [4,4], d_campos [3]) tensors the call fills (FR_FLAG_CAMERA_GRAD)
+Grads8 backward_impl(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
+                     const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
+                     const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+                     const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                     const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree,
+                     const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
+                     const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug,
+                     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>* camera)
 {
     (void)R;  // the binning layout is re-derived from the counts the forward left in the image buffer
     TORCH_CHECK(means3D.is_cuda(), "fateavatar_amd rasterizer: tensors must be on a HIP device (torch device 'cuda'); there is no CPU path");
@@ -126,6 +133,14 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
         const torch::Tensor rad = radii.contiguous();
         DeviceState& st = state_of(means3D.get_device());
         fr_params prm{P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, 0, debug ? 1 : 0, 0, nullptr};
+        fr_aux_camera aux{};
+        if (camera) {
+            if (!st.camera_ws.defined())
+                st.camera_ws = torch::zeros({(int64_t)fr_camera_grad_workspace_bytes()}, means3D.options().dtype(torch::kByte));
+            aux.d_viewmatrix = std::get<0>(*camera).data_ptr<float>(), aux.d_projmatrix = std::get<1>(*camera).data_ptr<float>();
+            aux.d_campos = std::get<2>(*camera).data_ptr<float>(), aux.camera_workspace = st.camera_ws.data_ptr();
+            prm.flags |= FR_FLAG_CAMERA_GRAD, prm.aux = &aux.base;
+        }
         fr_inputs in{fptr(bg), fptr(m3), fptr(shs), fptr(col), nullptr, fptr(sc), fptr(rot), fptr(cov), fptr(view), fptr(proj), fptr(cam)};
         fr_grads g{dL_dmeans2D.data_ptr<float>(), dL_dcolors.data_ptr<float>(), dL_dopacity.data_ptr<float>(),
                    dL_dmeans3D.data_ptr<float>(), dL_dcov3D.data_ptr<float>(), M ? dL_dsh.data_ptr<float>() : nullptr,
@@ -136,6 +151,41 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
         TORCH_CHECK(rc == FR_OK, "fr_backward failed (code ", rc, "): ", fr_last_error());
     }
     return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations);
+}
+}  // namespace
+
+Grads8 RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
+                                      const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
+                                      const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+                                      const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                                      const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree,
+                                      const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
+                                      const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug)
+{
+    return backward_impl(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+                         tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, nullptr);
+}
+
+// The same call with the camera's gradients behind the eight arrays: (d_viewmatrix [4,4], d_projmatrix [4,4], d_campos [3]),
+// the gradients of the three camera arguments as the kernels read them (zeros for P == 0).
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor, torch::Tensor>
+RasterizeGaussiansBackwardCameraCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
+                                     const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
+                                     const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+                                     const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                                     const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree,
+                                     const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
+                                     const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug)
+{
+    TORCH_CHECK(means3D.is_cuda(), "fateavatar_amd rasterizer: tensors must be on a HIP device (torch device 'cuda'); there is no CPU path");
+    c10::DeviceGuard guard(means3D.device());
+    auto f32 = means3D.options().dtype(torch::kFloat32);
+    auto cam = std::make_tuple(torch::zeros({4, 4}, f32), torch::zeros({4, 4}, f32), torch::zeros({3}, f32));
+    return std::tuple_cat(backward_impl(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                                        projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
+                                        imageBuffer, debug, &cam),
+                          cam);
 }
 
 torch::Tensor markVisible(torch::Tensor& means3D, torch::Tensor& viewmatrix, torch::Tensor& projmatrix)
@@ -175,6 +225,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.def("rasterize_gaussians", &RasterizeGaussiansCUDA);
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackwardCUDA);
+    m.def("rasterize_gaussians_backward_camera", &RasterizeGaussiansBackwardCameraCUDA);
     m.def("mark_visible", &markVisible);
     m.def("distCUDA2", &distCUDA2);
 }

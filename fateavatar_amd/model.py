@@ -138,3 +138,32 @@ class TorchCamera:
         if (other.image_height, other.image_width, other.FoVx, other.FoVy) != \
                 (self.image_height, self.image_width, self.FoVx, self.FoVy):
             raise ValueError("copy_from needs a camera with the same image size and field of view")
+
+
+class PoseCamera:
+    """The reference's `Camera` (volume_rendering/camera_3dgs.py:22-72 around getWorld2View2_torch, tools/gs_utils/
+    graphics_utils.py:51-62) built IN TORCH on the device of `R` / `T`, with the attribute names render() reads: gradients
+    reach `R` [3,3] (camera-to-world rotation) and `T` [3] (world-to-view translation) through `world_view_transform`,
+    `full_proj_transform` and `camera_center`.  The reference builds these three from its `cam_pose` embedding
+    (model/fateavatar.py:198-204) and then loses the gradient inside its rasterizer; here `render(PoseCamera(R, T, ...), ...)`
+    followed by `.backward()` fills `R.grad` / `T.grad`.
+
+    view = R^T x + T, so world_view_transform is [[R, 0], [T, 1]] (the transposed, row-vector storage) and the camera centre is
+    -R T; getWorld2View2_torch's two matrix inversions (the identity for translate = 0, scale = 1) and the reference's
+    `world_view_transform.inverse()[3, :3]` are left out: they need R orthonormal and agree with this to float32 rounding."""
+
+    def __init__(self, R, T, FoVx, FoVy, img_res, znear: float = 0.01, zfar: float = 100.0):
+        from .scenes import projection_matrix
+        R, T = R.squeeze(0), T.squeeze(0)
+        if R.shape != (3, 3) or T.shape != (3,):
+            raise ValueError("PoseCamera: R is [3,3] (or [1,3,3]), T is [3] (or [1,3])")
+        self.R, self.T = R, T
+        self.FoVx, self.FoVy = float(FoVx), float(FoVy)
+        self.image_height, self.image_width = int(img_res[0]), int(img_res[1])
+        self.znear, self.zfar = znear, zfar
+        last = torch.tensor([[0.0], [0.0], [0.0], [1.0]], dtype=R.dtype, device=R.device)
+        self.world_view_transform = torch.cat([torch.cat([R, T.reshape(1, 3).to(R.dtype)], 0), last], 1)
+        self.projection_matrix = torch.from_numpy(projection_matrix(znear, zfar, self.FoVx, self.FoVy).T.copy()).to(
+            device=R.device, dtype=R.dtype)
+        self.full_proj_transform = self.world_view_transform @ self.projection_matrix
+        self.camera_center = -(R @ T.to(R.dtype))

@@ -160,18 +160,61 @@ def _stats3(stats):
     return stats[0], stats[1], (stats[2] if len(stats) > 2 else None)
 
 
-def _aux(visible=None, grad_accum=None, denom=None, binding=None, bind_grads=None, overflow_out=None, planes=None):
+_camera_ws: dict = {}   # (device index, handle slot) -> the zeroed scratch of that handle's camera-gradient launches
+
+
+def camera_workspace(dev: int, slot: int) -> torch.Tensor:
+    """fr_aux_camera::camera_workspace of the backward passes of handle `slot` on device `dev`: zeroed once, left zeroed by the kernel.
+    One per handle — backward passes of one handle are ordered, those of different handles (the views of a batch, frames in
+    flight on several streams) may overlap and must not share one."""
+    ws = _camera_ws.get((dev, slot))
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():    # (torch.zeros inside a capture would become part of the graph)
+            raise RuntimeError(f"camera gradients: the workspace of handle slot {slot} does not exist yet and cannot be made while a "
+                               "stream is being captured: run one eager backward with camera gradients through it first")
+        ws = _camera_ws[(dev, slot)] = torch.zeros((_lib.lib().fr_camera_grad_workspace_bytes(),), dtype=torch.uint8,
+                                                   device=torch.device("cuda", dev))
+    return ws
+
+
+def _camera_outputs(camera, device):
+    """The (d_viewmatrix [4,4], d_projmatrix [4,4], d_campos [3]) tensors of a backward with `_camera`: True — fresh ones —
+    or the caller's three buffers (any may be None: not wanted), written in place."""
+    if camera is True:
+        return tuple(torch.empty(sh, dtype=torch.float32, device=device) for sh in ((4, 4), (4, 4), (3,)))
+    out = tuple(camera)
+    if len(out) != 3 or all(t is None for t in out):
+        raise RuntimeError("_camera: True, or (d_viewmatrix [4,4], d_projmatrix [4,4], d_campos [3]) buffers, not all of them None")
+    for t, n in zip(out, (16, 16, 3)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+            raise RuntimeError("_camera: the buffers are contiguous float32 device tensors of 16, 16 and 3 elements")
+    return out
+
+
+def _aux(visible=None, grad_accum=None, denom=None, binding=None, bind_grads=None, overflow_out=None, planes=None, camera=None):
     """fr_aux (optional fused side inputs / outputs) from torch tensors, or None if nothing is asked for.  `binding`: an
     `_lib.fr_binding` descriptor (the frame is rendered straight from its mesh binding); `bind_grads`: dict with the
     backward's d_verts / d_offset (a face-local binding: d_local_xyz) / d_rotation / d_scaling tensors (any may be None).  `planes` (FR_FLAG_DEPTH_ALPHA): dict
     of the out_depth / out_alpha / dL_ddepth / dL_dalpha tensors and the `planes` scratch (any may be None; the scratch of a
-    forward is set by the launcher, which sizes it with the binning buffer)."""
-    if visible is None and grad_accum is None and denom is None and binding is None and overflow_out is None and planes is None:
+    forward is set by the launcher, which sizes it with the binning buffer).  `camera` (FR_FLAG_CAMERA_GRAD): dict of the
+    d_viewmatrix / d_projmatrix / d_campos tensors (any may be None) and the camera_workspace: the block returned is then the
+    `base` of an `_lib.fr_aux_camera` that carries them."""
+    if visible is None and grad_accum is None and denom is None and binding is None and overflow_out is None and planes is None \
+            and camera is None:
         return None
     for t, dt in ((visible, (torch.bool, torch.uint8)), (grad_accum, (torch.float32,)), (denom, (torch.float32,))):
         if t is not None and (t.dtype not in dt or not t.is_contiguous() or not t.is_cuda):
             raise RuntimeError("fused side outputs must be contiguous device tensors (bool/uint8 mask, float32 stats)")
-    aux = _lib.fr_aux(*(t.data_ptr() if t is not None else None for t in (visible, grad_accum, denom)))
+    if camera is not None:     # (FR_FLAG_CAMERA_GRAD: the block is the `base` of an fr_aux_camera, which it keeps alive)
+        ext = _lib.fr_aux_camera()
+        aux = ext.as_aux()
+        for n, t in camera.items():
+            if t is not None:
+                setattr(ext, n, t.data_ptr())
+        aux._camera_keepalive = (ext, camera)
+        aux.visible, aux.grad_accum, aux.denom = (t.data_ptr() if t is not None else None for t in (visible, grad_accum, denom))
+    else:
+        aux = _lib.fr_aux(*(t.data_ptr() if t is not None else None for t in (visible, grad_accum, denom)))
     if overflow_out is not None:
         if not (overflow_out.is_cuda and overflow_out.dtype == torch.float32 and overflow_out.numel() >= 1 and overflow_out.is_contiguous()):
             raise RuntimeError("the overflow word must be a contiguous float32 device tensor")
@@ -257,11 +300,13 @@ def _forward_view(args, raw=False, visible=None, binding=None, forward_only=Fals
 
 
 def _backward_view(args, raw=False, want=None, out=None, stats=None, accumulate=(), binding=None, bind_grads=None,
-                   what="rasterize_gaussians_backward", planes=None) -> dict:
+                   what="rasterize_gaussians_backward", planes=None, camera=None, slot=0) -> dict:
     """One view of a backward, from the positional arguments of `rasterize_gaussians_backward` and its keyword
     arguments: the gradient tensors it returns, its inputs as the kernels read them (kept alive in the view), and its
     fr_params / fr_inputs / fr_grads.  `planes` (FR_FLAG_DEPTH_ALPHA): (planesBuffer, dL_ddepth, dL_dalpha) of a frame
-    rendered with depth and alpha planes; either gradient may be None (zero)."""
+    rendered with depth and alpha planes; either gradient may be None (zero).  `camera` (FR_FLAG_CAMERA_GRAD): True or three
+    buffers (`_camera_outputs`); the view's result then ends with (d_viewmatrix, d_projmatrix, d_campos), and the launch takes
+    the scratch of the device's handle `slot`."""
     (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
      tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug) = args
     dev = _dev_index(means3D)
@@ -290,10 +335,16 @@ def _backward_view(args, raw=False, want=None, out=None, stats=None, accumulate=
         pl = dict(planes=buf, dL_ddepth=None if dz is None else _f32c(dz.reshape(H, W))[0],
                   dL_dalpha=None if da is None else _f32c(da.reshape(H, W))[0])
         acc_flags |= _lib.FR_FLAG_DEPTH_ALPHA
-    if stats is not None or binding is not None or pl is not None:
+    cam_out, cm = (), None
+    if camera is not None and camera is not False and P != 0:
+        cam_out = _camera_outputs(camera, means3D.device)
+        cm = dict(zip(("d_viewmatrix", "d_projmatrix", "d_campos"), cam_out), camera_workspace=camera_workspace(dev, slot))
+        acc_flags |= _lib.FR_FLAG_CAMERA_GRAD
+    if stats is not None or binding is not None or pl is not None or cm is not None:
         grad_accum, denom, overflow_out = _stats3(stats)
-        aux = _aux(grad_accum=grad_accum, denom=denom, overflow_out=overflow_out, binding=binding, bind_grads=bind_grads, planes=pl)
-    return dict(dev=dev, g=g, keep=keep, inp=_inputs(*keep), grads=_lib.fr_grads(*_ptrs(*g.values())),
+        aux = _aux(grad_accum=grad_accum, denom=denom, overflow_out=overflow_out, binding=binding, bind_grads=bind_grads, planes=pl,
+                   camera=cm)
+    return dict(dev=dev, g=g, cam=cam_out, keep=keep, inp=_inputs(*keep), grads=_lib.fr_grads(*_ptrs(*g.values())),
                 prm=_params(P, degree, M, W, H, tan_fovx, tan_fovy, scale_modifier, False, debug, raw, aux, acc_flags),
                 radii=radii.contiguous(), geom=geomBuffer, img=imageBuffer, binning=binningBuffer, dpix=dpix)
 
@@ -368,7 +419,7 @@ def _launch_backward(views, slots, batch):
                                v["geom"].data_ptr(), v["img"].data_ptr(), v["binning"].data_ptr(), v["dpix"].data_ptr(),
                                C.byref(v["grads"]), stream)
     _lib.check(rc, "fr_backward_batch" if batch else "fr_backward")
-    return [tuple(v["g"].values()) for v in views]
+    return [tuple(v["g"].values()) + v["cam"] for v in views]
 
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
@@ -397,7 +448,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                  geomBuffer, R, binningBuffer, imageBuffer, debug, _want=None, _out=None, _raw=False,
-                                 _stats=None, _accumulate=(), _planes=None):
+                                 _stats=None, _accumulate=(), _planes=None, _camera=False):
     """`_C.rasterize_gaussians_backward` (rasterize_points.cu:117-196).
 
     Returns (dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dsh[P,M,3],
@@ -406,13 +457,18 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     `_want` (extension): the names of the gradients to compute (the others come back as None); `_out`: caller-provided
     gradient buffers, written in place; `_accumulate`: names of `_out` buffers the frame's gradient is ADDED to
     (FR_FLAG_ACCUMULATE); `_planes=(planesBuffer, dL_ddepth, dL_dalpha)` (FR_FLAG_DEPTH_ALPHA): the gradients of the depth
-    and alpha planes of a frame rendered with `_depth_alpha` (either may be None)."""
+    and alpha planes of a frame rendered with `_depth_alpha` (either may be None).
+    `_camera=True` (extension, FR_FLAG_CAMERA_GRAD): three more results, (d_viewmatrix [4,4], d_projmatrix [4,4], d_campos [3]) —
+    the gradients of the three camera inputs, which the reference leaves at None; or three buffers of those sizes, written in
+    place (any may be None).  Entries the kernels do not read (viewmatrix column 3, projmatrix column 2) are 0."""
     v = _backward_view((background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                         projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                        imageBuffer, debug), _raw, _want, _out, _stats, _accumulate, planes=_planes)
+                        imageBuffer, debug), _raw, _want, _out, _stats, _accumulate, planes=_planes, camera=_camera, slot=_slot)
     if v["prm"].P == 0:
+        cam = () if not _camera else tuple(None if t is None else t.zero_() for t in (
+            _camera_outputs(_camera, means3D.device)))
         return tuple((_out[k] if k in _accumulate else torch.zeros(s, device=means3D.device, dtype=torch.float32))
-                     for k, s in _grad_shapes(0, v["prm"].M).items())
+                     for k, s in _grad_shapes(0, v["prm"].M).items()) + cam
     return _launch_backward([v], [_slot], batch=False)[0]
 
 
@@ -453,21 +509,25 @@ def _forward_batch(views, slots, raw, visibles, bindings, forward_only, depth_al
 
 
 def rasterize_gaussians_backward_batch(views, slots=None, raw=False, wants=None, outs=None, stats=None, accumulates=None,
-                                       bindings=None, bind_grads=None, planes=None):
+                                       bindings=None, bind_grads=None, planes=None, camera=None):
     """`rasterize_gaussians_backward` for K views in ONE launch chain (fr_backward_batch): `views` is a list of its
     positional argument tuples (background ... debug); `wants` / `outs` / `stats` / `accumulates`: per-view lists of the
     corresponding keyword arguments.  Returns the list of gradient tuples.  `bindings` / `bind_grads` (extension,
     fr_aux::binding): per view the descriptor the forward was given and a dict of the d_verts / d_offset / d_rotation /
     d_scaling tensors the kernel writes (d_verts: adds).  `planes` (FR_FLAG_DEPTH_ALPHA): per view the `_planes` tuple of
-    `rasterize_gaussians_backward`; the views must agree on having one."""
+    `rasterize_gaussians_backward`; the views must agree on having one.  `camera` (FR_FLAG_CAMERA_GRAD): True, or per view
+    the `_camera` argument of `rasterize_gaussians_backward`; all views or none."""
     K = len(views)
     if not 1 <= K <= _lib.FR_MAX_BATCH:
         raise RuntimeError(f"rasterize_gaussians_backward_batch: 1 .. {_lib.FR_MAX_BATCH} views")
     slots = list(range(K)) if slots is None else [int(x) for x in slots]
     wants, outs, stats, accumulates, bindings, bind_grads, planes = (x or [None] * K for x in (wants, outs, stats, accumulates,
                                                                                               bindings, bind_grads, planes))
+    cameras = [camera] * K if camera is None or isinstance(camera, bool) else list(camera)
+    if len(set(bool(c is not None and c is not False) for c in cameras)) != 1:
+        raise RuntimeError("rasterize_gaussians_backward_batch: the views of a batch must agree on camera gradients")
     st = [_backward_view(a, raw, wants[k], outs[k], stats[k], tuple(accumulates[k] or ()), bindings[k], bind_grads[k],
-                         "rasterize_gaussians_backward_batch", planes[k]) for k, a in enumerate(views)]
+                         "rasterize_gaussians_backward_batch", planes[k], cameras[k], slots[k]) for k, a in enumerate(views)]
     # fr_aux::overflow_out is OVERWRITTEN (0 or 1) by every backward: views of one launch that shared a word would race, and a
     # view that did not overflow could clear the flag of one that did (the optimizer would step on a partly zero gradient)
     words = [int(_stats3(stats[k])[2].data_ptr()) for k in range(K) if _stats3(stats[k])[2] is not None]
@@ -479,13 +539,14 @@ def rasterize_gaussians_backward_batch(views, slots=None, raw=False, wants=None,
 
 class _RasterizeGaussiansBatch(torch.autograd.Function):
     """`_RasterizeGaussians` for K views rendered together.  Tensor arguments: per view the eight of `_RasterizeGaussians`
-    (means3D ... cov3Ds_precomp); outputs: per view those of `_SavedFrame`."""
+    (means3D ... cov3Ds_precomp), then — optionally — per view its settings' (viewmatrix, projmatrix, campos), which then
+    receive gradients (`_camera_inputs`); outputs: per view those of `_SavedFrame`."""
 
     @staticmethod
     def forward(ctx, settings, raw_activations, slots, forward_only, depth_alpha, *tensors):
         K = len(settings)
-        assert len(tensors) == 8 * K
-        ctx.raw, ctx.slots = bool(raw_activations), slots
+        assert len(tensors) in (8 * K, 11 * K)
+        ctx.raw, ctx.slots, ctx.camera = bool(raw_activations), slots, len(tensors) == 11 * K
         per_view = [tensors[8 * k:8 * k + 8] for k in range(K)]
         viss = [torch.empty((t[0].shape[0],), dtype=torch.bool, device=t[0].device) for t in per_view]
         res = _forward_batch([_forward_args(rs, *t) for rs, t in zip(settings, per_view)], slots, ctx.raw, viss, None,
@@ -500,7 +561,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grad_outs):
         if not _any_grad(grad_outs):
-            return (None,) * (5 + 8 * len(ctx.frames))
+            return (None,) * (5 + (11 if ctx.camera else 8) * len(ctx.frames))
         views, outs, planes = [], [], []
         for f, own, fw, g, pl in _SavedFrame.load(ctx, grad_outs):
             views.append(_backward_args(f.rs, own, fw, g))
@@ -510,8 +571,9 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             outs.append(f.grads.claim(accumulate=False)[0])
         res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=ctx.raw, wants=[f.grads.want for f in ctx.frames],
                                                  outs=outs, stats=[f.stats for f in ctx.frames],
-                                                 planes=planes if ctx.frames[0].has_planes else None)
-        return (None,) * 5 + tuple(t for grads in res for t in _input_grads(grads))
+                                                 planes=planes if ctx.frames[0].has_planes else None, camera=ctx.camera)
+        return (None,) * 5 + tuple(t for grads in res for t in _input_grads(grads)) + \
+            (tuple(t for f, grads in zip(ctx.frames, res) for t in _camera_grads(f.rs, grads)) if ctx.camera else ())
 
 
 def rasterize_views_autograd(settings, per_view_tensors, raw_activations=False, slots=None, depth_alpha=False):
@@ -520,7 +582,7 @@ def rasterize_views_autograd(settings, per_view_tensors, raw_activations=False, 
     empty tensors for what a view does not use.  Returns [(color, radii), ...], with `depth_alpha` (extension,
     FR_FLAG_DEPTH_ALPHA) [(color, radii, depth [1,H,W], alpha [1,H,W]), ...] (both planes differentiable)."""
     K = len(settings)
-    flat = [t for v in per_view_tensors for t in v]
+    flat = [t for v in per_view_tensors for t in v] + _camera_inputs_of(settings)
     out = _RasterizeGaussiansBatch.apply(list(settings), bool(raw_activations), list(range(K)) if slots is None else list(slots),
                                          _pick_forward_only(flat), bool(depth_alpha), *flat)
     return _per_view_outputs(out, K)
@@ -676,6 +738,27 @@ _INPUT_GRADS = [(k, _GRAD_NAMES.index(k)) for k in ("dL_dmeans3D", "dL_dmeans2D"
                                                      "dL_dscales", "dL_drotations", "dL_dcov3D")]
 
 
+def _camera_inputs(rs) -> tuple:
+    """The settings' (viewmatrix, projmatrix, campos) as TENSOR inputs of the frame's autograd Function — only when autograd
+    records and one of them requires grad (a `model.PoseCamera` built from leaves, a pose being refined); () otherwise, and the
+    frame is then exactly the reference's: no flag, no extra launch."""
+    cam = (rs.viewmatrix, rs.projmatrix, rs.campos)
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam):
+        return cam
+    return ()
+
+
+def _camera_inputs_of(settings) -> list:
+    """`_camera_inputs` for the views of a batch, which share one launch chain: every view's three, or none."""
+    cams = [_camera_inputs(rs) for rs in settings]
+    return [t for rs in settings for t in (rs.viewmatrix, rs.projmatrix, rs.campos)] if any(cams) else []
+
+
+def _camera_grads(rs, grads) -> tuple:
+    """The last three results of a backward with `_camera` as the gradients of the settings' camera tensors."""
+    return tuple(g.reshape(t.shape).to(t.dtype) for g, t in zip(grads[-3:], (rs.viewmatrix, rs.projmatrix, rs.campos)))
+
+
 def _input_grads(grads, added=()):
     """The results of `rasterize_gaussians_backward` in the order of the frame's tensor inputs (means3D, means2D, sh,
     colors_precomp, opacities, scales, rotations, cov3Ds_precomp); None for the names in `added`, whose gradient is
@@ -746,13 +829,16 @@ def _per_view_outputs(outs, K) -> list:
 
 class _RasterizeGaussians(torch.autograd.Function):
     """diff_gaussian_rasterization/__init__.py:44-155.  Tensor arguments: (means3D, means2D, sh, colors_precomp, opacities,
-    scales, rotations, cov3Ds_precomp), then raster_settings; outputs: those of `_SavedFrame`."""
+    scales, rotations, cov3Ds_precomp), then raster_settings; outputs: those of `_SavedFrame`.  Optional trailing tensor
+    inputs (extension): the settings' (viewmatrix, projmatrix, campos), which then receive gradients (`_camera_inputs`)."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, raw_activations=False, forward_only=False, depth_alpha=False):
+                raster_settings, raw_activations=False, forward_only=False, depth_alpha=False, viewmatrix=None,
+                projmatrix=None, campos=None):
         rs = raster_settings
         ctx.raw = bool(raw_activations)
+        ctx.camera = viewmatrix is not None   # (the three are rs.viewmatrix / projmatrix / campos: all or none)
         ctx.fr_slot = _slot   # the backward goes through the handle the forward used
         args = _forward_args(rs, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         vis = torch.empty((means3D.shape[0],), dtype=torch.bool, device=means3D.device) if means3D.is_cuda else None
@@ -766,24 +852,25 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grad_outs):
         if not _any_grad(grad_outs):
-            return (None,) * 12
+            return (None,) * 15
         (f, own, fw, grad_out_color, planes), = _SavedFrame.load(ctx, grad_outs)
         out, added = ({}, ()) if f.rs.debug else f.grads.claim()   # (debug mode claims no GradOut slot)
         with handle_slot(ctx.fr_slot):
             grads = _snapshot_on_error(
                 f.rs.debug, "snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n",
                 rasterize_gaussians_backward, _backward_args(f.rs, own, fw, grad_out_color), _out=out, _raw=ctx.raw,
-                _stats=f.stats, _want=f.grads.want, _accumulate=added, _planes=planes)
+                _stats=f.stats, _want=f.grads.want, _accumulate=added, _planes=planes, _camera=ctx.camera)
         # (autograd drops the surplus trailing None of a call with the reference's nine arguments)
-        return _input_grads(grads, added) + (None,) * 4
+        return _input_grads(grads, added) + (None,) * 4 + (_camera_grads(f.rs, grads) if ctx.camera else (None,) * 3)
 
 
 def rasterize_gaussians_autograd(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                  raster_settings, raw_activations=False, depth_alpha=False):
     """`depth_alpha` (extension, FR_FLAG_DEPTH_ALPHA): (color, radii, depth, alpha) instead of (color, radii)."""
-    forward_only = _pick_forward_only((means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp))
+    cam = _camera_inputs(raster_settings)
+    forward_only = _pick_forward_only((means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, *cam))
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                     raster_settings, raw_activations, forward_only, depth_alpha)
+                                     raster_settings, raw_activations, forward_only, depth_alpha, *cam)
 
 
 class GaussianRasterizationSettings(NamedTuple):

@@ -16,6 +16,7 @@ when they are needed.
 """
 from __future__ import annotations
 
+import copy
 from typing import Optional
 
 import torch
@@ -391,17 +392,29 @@ class BoundStep(TrainStep):
     RESUME_REMAPPED = False          # load_state_dict without an `optimizer` entry: the step count goes on, or (False) restarts
     VERTEX_GRAD = True               # the model's binding has a gradient to the posed vertices (`vertex_grad=True`) ...
     VERTEX_GRAD_MISSING = ""         # ... or why it has none
+    CAMERA_GRAD = False              # the step keeps the frame's camera gradients (`camera_grad=True`): AvatarStep
 
     def __init__(self, pc, faces: torch.Tensor, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True,
-                 image_loss: Optional[ImageLoss] = None, data_parallel: bool = True, vertex_grad: bool = False):
+                 image_loss: Optional[ImageLoss] = None, data_parallel: bool = True, vertex_grad: bool = False,
+                 camera_grad: bool = False):
         """`verts` [V,3]: any pose of the mesh (sizes the step's static vertex buffer and is its first content).
         `vertex_grad`: after every `step()`, `d_verts` [V,3] holds THIS step's dLoss/dposed_verts (the binding's backward
         scatters it; zeroed by the step itself, never accumulated over steps; one storage across the replays of a captured
         step, like `out`) — the caller goes on with `posed_verts.backward(step.d_verts)` into whatever made the mesh (FLAME
         and its blendshape deltas: stock PyTorch) and its own optimizer.  It is this rank's frame's gradient: the caller's
         mesh parameters need their own all-reduce.  A replay that overflowed its binning capacity back-propagated zeros.
-        False (default): no such buffer, `d_verts` is None and the kernels are handed no vertex-gradient array."""
+        False (default): no such buffer, `d_verts` is None and the kernels are handed no vertex-gradient array.
+        `camera_grad`: after every `step()`, `d_view` [4,4], `d_proj` [4,4] and `d_campos` [3] hold THIS step's dLoss/d(the
+        camera's world_view_transform, full_proj_transform, camera_center) — what the reference's `cam_pose` tracking embedding
+        (train/base.py:123,142) needs and its rasterizer does not return; the caller chains them through its own camera
+        construction (`model.PoseCamera`: `wvt.backward(step.d_view)` ...) into its own optimizer.  Like `d_verts`: this step's,
+        this rank's, one storage across the replays of a captured step, zeros after a replay that overflowed.  False
+        (default): no such buffers, no extra launch."""
+        if camera_grad and not self.CAMERA_GRAD:
+            raise NotImplementedError(f"{type(self).__name__}(camera_grad=True): camera gradients are built for AvatarStep only "
+                                      "(render through a model.PoseCamera for any other model)")
+        self.camera_grad, self.d_view, self.d_proj, self.d_campos = bool(camera_grad), None, None, None
         if vertex_grad and not self.VERTEX_GRAD:
             raise NotImplementedError(f"{type(self).__name__}(vertex_grad=True): {self.VERTEX_GRAD_MISSING}")
         self.vertex_grad, self.d_verts = bool(vertex_grad), None
@@ -438,6 +451,21 @@ class BoundStep(TrainStep):
         scattered into (inside a captured step: graph-owned storage, the same on every replay)."""
         if self.vertex_grad:
             self.d_verts = leaf.grad
+
+    def _camera_leaf(self, cam):
+        """What a frame is rendered through: the static camera `cam` itself, or with `camera_grad` a camera whose three tensors
+        are leaves over the same storage (no copy), whose gradients `_keep_camera_grad` picks up after the backward."""
+        if not self.camera_grad:
+            return cam
+        leaf = copy.copy(cam)
+        for n in ("world_view_transform", "full_proj_transform", "camera_center"):
+            setattr(leaf, n, getattr(cam, n).detach().requires_grad_(True))
+        return leaf
+
+    def _keep_camera_grad(self, leaf) -> None:
+        if self.camera_grad:
+            self.d_view, self.d_proj, self.d_campos = (leaf.world_view_transform.grad, leaf.full_proj_transform.grad,
+                                                       leaf.camera_center.grad)
 
     # ---- checkpoints in the reference's layout (Trainer.save_checkpoint, train/trainer.py:396-435: a dict with 'global_step'
     #      and 'model' = model.state_dict(), which holds the Gaussian parameters and the binding buffers under the model's

@@ -141,6 +141,22 @@ typedef struct fr_aux {
     void* planes;
 } fr_aux;
 
+/* The side block of a backward with FR_FLAG_CAMERA_GRAD: fr_aux with the camera's members behind it.  With the flag set,
+ * fr_params::aux MUST point at the `base` member of one of these — fr_backward / fr_backward_batch read the tail through that
+ * pointer (as fr_binding_phong extends fr_binding).  fr_aux itself is unchanged, size and layout: callers without the flag
+ * neither carry nor read a tail. */
+typedef struct fr_aux_camera {
+    fr_aux base;
+    /* out: dL/d(viewmatrix) [16], dL/d(projmatrix) [16] and dL/d(campos) [3] of fr_inputs, in the storage the kernels read,
+     * OVERWRITTEN.  Any of the three may be NULL (not wanted), not all of them. */
+    float* d_viewmatrix;
+    float* d_projmatrix;
+    float* d_campos;
+    /* fr_camera_grad_workspace_bytes() bytes of device memory, 16-byte aligned, required: zeroed ONCE by the caller and left
+     * zeroed by the kernel.  Launches that may overlap on the device (the views of a batch, other handles) need one each. */
+    void* camera_workspace;
+} fr_aux_camera;
+
 /* Frame parameters: the scalar arguments of Rasterizer::forward/backward. */
 typedef struct fr_params {
     int32_t P;            /* number of Gaussians */
@@ -191,6 +207,28 @@ typedef struct fr_params {
  * FR_ERR_INVALID_ARGUMENT and enqueues nothing.  All views of a batch must agree on the flag.  Scratch sizes of frames without
  * the flag are unchanged; a frame with it needs fr_planes_bytes() more. */
 #define FR_FLAG_DEPTH_ALPHA 8
+
+/* fr_backward / fr_backward_batch: also return the gradient of the loss with respect to the frame's CAMERA — the three camera
+ * inputs of fr_inputs, viewmatrix [16], projmatrix [16] and campos [3], as independent variables in the storage the kernels
+ * read (view-space mean c = sum_r viewmatrix[c + 4 r] m_r + viewmatrix[c + 12]) — in fr_aux_camera::d_viewmatrix /
+ * d_projmatrix / d_campos (fr_params::aux then points at an fr_aux_camera's `base`).  The reference's rasterizer returns None for them (diff_gaussian_rasterization/__init__.py:143-153), so its
+ * per-frame camera embedding (train/base.py:123,142) never trains.  One more launch between the blend backward and the
+ * per-Gaussian backward sums, over the Gaussians with radii > 0,
+ *   d viewmatrix[c + 4 r] = dL/dt_c m_r (m = (mean, 1); dL/dt the per-Gaussian backward's, with the reference's stop-gradient
+ *                           on guard-band-clamped x / y; + the depth plane's dL/dz for c = 2) + the part through the rotation
+ *                           inside the 2D covariance's T = J W,
+ *   d projmatrix          through ndc = hom.xy / (hom.w + 1e-7) from dL_dmeans2D,
+ *   d campos              = minus the SH colour's share of dL_dmeans3D (0 for a frame with colors_precomp).
+ * Entries no kernel reads are written as 0: flat indices 3, 7, 11, 15 of viewmatrix and 2, 6, 10, 14 of projmatrix.  The
+ * discrete decisions (culling, tile lists, depth order) get no gradient, and neither do tan_fovx / tan_fovy.  A frame that
+ * overflowed its binning capacity writes zeros; fr_backward with P == 0 enqueues nothing and leaves them as they are.  No float atomics: per-workgroup partial sums are added up in index order by
+ * the workgroup that finishes last, so the same inputs give the same bits on every call; nothing allocates or synchronises
+ * (the call stays capturable).  The fr_grads arrays are those of the same call without the flag, bit for bit, and a call
+ * without the flag launches exactly what it did before.  Needs an fr_aux_camera with camera_workspace and at least one of the three
+ * outputs (FR_ERR_INVALID_ARGUMENT otherwise); all views of a batch must agree on the flag.  Combines with
+ * FR_FLAG_RAW_ACTIVATIONS, FR_FLAG_DEPTH_ALPHA, FR_FLAG_ACCUMULATE (which does not apply to the three arrays) and
+ * fr_aux::binding (the bound means3D / scales / rotations the forward wrote come back in fr_inputs).  fr_forward ignores it. */
+#define FR_FLAG_CAMERA_GRAD 16
 
 /* fr_backward only: FR_FLAG_ACCUMULATE(k) makes the k-th array of fr_grads (k = position of the pointer in the
  * struct: 0 = dL_dmeans2D ... 7 = dL_drotations) ACCUMULATE: the frame's gradient is added to what the array holds
@@ -262,6 +300,8 @@ size_t fr_binning_bytes(uint64_t capacity, int32_t W, int32_t H);
 /* fr_aux::planes of a frame with FR_FLAG_DEPTH_ALPHA whose binning buffer holds `capacity` instances: 512 bytes per blend
  * unit (capacity / 64 + tiles + 1 of them), plus alignment.  Regrow it with the binning buffer. */
 size_t fr_planes_bytes(uint64_t capacity, int32_t W, int32_t H);
+/* fr_aux_camera::camera_workspace of a backward with FR_FLAG_CAMERA_GRAD (a constant: counters and per-workgroup partial sums). */
+size_t fr_camera_grad_workspace_bytes(void);
 
 /* out_color [3,H,W], radii [P] (reference semantics: ceil(3*sigma_max), 0 if culled).
  * Returns FR_OK, or FR_ERR_BINNING_CAPACITY with counts->num_instances = capacity required

@@ -15,6 +15,12 @@ torch `delta_vertex` leaf [V,3] is added to the template in front of the sequenc
 torch.optim.Adam through `step.d_verts` (the step's dLoss/dposed_verts, the reference's mesh terms already in it; `verts_orig`
 is the undisplaced posed mesh).  Prints steps/s, the image loss, both mesh terms and |delta - bump| at start and end.
 --vertex-grad alone: the plain loop with the vertex gradient switched on (what that option costs).
+    python tools/train_synthetic.py --fateavatar --track-camera [--track-offset 0.005]
+FateAvatar's step with the reference's camera tracking next to it (train/base.py:123,142: one translation per frame in an
+embedding, at `tracking_lr`): every frame's camera translation is a torch leaf that starts --track-offset metres (RMS per axis)
+from the truth; each step the frame's camera is built from it as `model.PoseCamera` builds it, rendered by
+AvatarStep(camera_grad=True), and `step.d_view / d_proj / d_campos` are chained back through that construction into
+torch.optim.Adam(lr=5e-4).  Prints steps/s, the image loss and the RMS translation error before and after.
 
     python tools/train_synthetic.py --rigged [--P 10006 --sh-degree 3 --binding-op]
 GaussianAvatars' step (fateavatar_amd/rigged.py): Gaussians rigged to the triangles of the posed template, one GPU.
@@ -99,6 +105,10 @@ def main():
     ap.add_argument("--mesh-terms", type=float, nargs=2, default=None, metavar=("LAP", "FLAME"),
                     help="--train-mesh: weights of the Laplacian and FLAME-distance terms (default: the reference's 1e5 0)")
     ap.add_argument("--mesh-lr", type=float, default=1e-4, help="--train-mesh: Adam rate of delta_vertex (train/optim.py:30)")
+    ap.add_argument("--track-camera", action="store_true",
+                    help="--fateavatar: train a per-frame camera translation leaf through AvatarStep(camera_grad=True)")
+    ap.add_argument("--track-offset", type=float, default=0.005, help="--track-camera: RMS start error of the translations, per axis (m)")
+    ap.add_argument("--track-lr", type=float, default=5e-4, help="--track-camera: Adam rate (config/fateavatar.yaml:50 tracking_lr)")
     ap.add_argument("--rigged", action="store_true",
                     help="GaussianAvatars' loop: Gaussians bound to the local frames of the template's faces (one per face, then "
                          "random faces up to --P), rendered with --sh-degree active; --binding-op as for --fateavatar")
@@ -156,8 +166,8 @@ def main():
         return main_flash(a, rank, world, dev)
     if a.mouth_mask:
         raise SystemExit("--mouth-mask goes with --flash")
-    if (a.train_mesh or a.vertex_grad or a.mesh_terms) and not (a.fateavatar and a.views_per_step == 1):
-        raise SystemExit("--train-mesh / --vertex-grad / --mesh-terms go with --fateavatar at one frame per step")
+    if (a.train_mesh or a.vertex_grad or a.mesh_terms or a.track_camera) and not (a.fateavatar and a.views_per_step == 1):
+        raise SystemExit("--train-mesh / --vertex-grad / --mesh-terms / --track-camera go with --fateavatar at one frame per step")
     if a.fateavatar:
         if a.image_loss:
             raise SystemExit("--fateavatar: the D-SSIM term is not part of FateAvatar's objective (dssim_loss 0.0)")
@@ -211,11 +221,11 @@ def main():
 
 
 def fateavatar_setup(P, res, dev, views=8, views_per_step=1, use_graph=True, chain=True, fold_binding=True, order="uv",
-                     keep_coherent=False, vertex_grad=False, mesh_terms=None, target_delta=None):
+                     keep_coherent=False, vertex_grad=False, mesh_terms=None, target_delta=None, camera_grad=False):
     """FateAvatar's optimisation step on the synthetic INSTA-layout sequence: the mesh-bound Gaussian
     set, its step object (AvatarStep, or AvatarBatchStep for K > 1 frames per step), cameras, posed meshes and targets
     rendered from a hidden ground-truth set.  Used by this script and by bench.py's `avatar` mode.
-    `vertex_grad`, `mesh_terms`: AvatarStep's options (K = 1).  `target_delta` [V,3] (numpy): the targets are rendered from
+    `vertex_grad`, `mesh_terms`, `camera_grad`: AvatarStep's options (K = 1).  `target_delta` [V,3] (numpy): the targets are rendered from
     the template displaced by it (`pose`, also returned, poses a displaced template differentiably).
     `order="uv"`: the reference's own initialisation — `uniform_sampling_barycoords(P, ...)` on the template's UV raster
     (model/fateavatar.py:128-133), rows in row-major texel order; `order="random"`: the area-weighted draw as drawn (the A/B)."""
@@ -260,13 +270,16 @@ def fateavatar_setup(P, res, dev, views=8, views_per_step=1, use_graph=True, cha
             extra["vertex_grad"] = True
         if mesh_terms is not None:
             extra["mesh_terms"] = mesh_terms
+        if camera_grad:
+            extra["camera_grad"] = True
         st = AvatarStep(pc, faces_t, canon, cam0, bg, use_graph=use_graph, fold_binding=fold_binding, keep_coherent=keep_coherent,
                         **extra)
     else:   # the reference's batch of K frames per step (model/fateavatar.py:251-276), in flight together
         from fateavatar_amd.avatar import AvatarBatchStep
         st = AvatarBatchStep(pc, faces_t, canon, cam0, bg, views_per_step=K, use_graph=use_graph, chain=chain,
                              fold_binding=fold_binding, keep_coherent=keep_coherent)
-    return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames, K=K, pose=pose, canon=canon)
+    return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames, K=K, pose=pose, canon=canon,
+                camera_arrays=insta.camera_arrays(transform))
 
 
 def smooth_bump(verts, seed=0, height=0.004, width=0.03):
@@ -326,7 +339,61 @@ def main_train_mesh(a, rank, world, dev):
                       "mesh_lr": a.mesh_lr, "bump_norm": round(float(bump_t.norm()), 6), "first": first, "last": report()}))
 
 
+def main_track_camera(a, rank, world, dev):
+    """The demonstration of `step.d_view / d_proj / d_campos`: FateAvatar's Gaussians by the fused step, every frame's camera
+    translation by the caller's own Adam (the reference's `train_cam_pose` embedding, which its rasterizer never moves)."""
+    if world > 1 or a.train_mesh or a.mesh_terms:
+        raise SystemExit("--track-camera: one GPU, without --train-mesh / --mesh-terms")
+    from fateavatar_amd.model import PoseCamera
+    su = fateavatar_setup(a.P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
+                           order="random" if a.random_order else "uv", camera_grad=True)
+    st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
+    arrays = su["camera_arrays"]
+    # world_view_transform = [[R, 0], [T, 1]] (model.PoseCamera): the truth's rotation and translation of every frame
+    Rs = [torch.from_numpy(np.ascontiguousarray(c.world_view_transform[:3, :3])).to(dev) for c in arrays]
+    T_true = torch.from_numpy(np.stack([c.world_view_transform[3, :3] for c in arrays])).to(dev)
+    g = torch.Generator().manual_seed(9)
+    T = (T_true + a.track_offset * torch.randn(T_true.shape, generator=g).to(dev)).requires_grad_(True)   # the embedding's rows
+    opt = torch.optim.Adam([T], lr=a.track_lr)
+    shown = [c.clone() for c in cams]                                # per frame the camera block the step is handed
+
+    def one_step(it):
+        f = it % n_frames
+        opt.zero_grad(set_to_none=True)
+        c = arrays[f]
+        cam = PoseCamera(Rs[f], T[f], c.FoVx, c.FoVy, (c.image_height, c.image_width))
+        packed = torch.cat([cam.world_view_transform.reshape(-1), cam.full_proj_transform.reshape(-1), cam.camera_center])
+        shown[f]._packed.copy_(packed.detach())
+        st.step(shown[f], posed_t[f], gts[f])
+        packed.backward(torch.cat([st.d_view.reshape(-1), st.d_proj.reshape(-1), st.d_campos]))
+        opt.step()
+
+    def report():
+        torch.cuda.synchronize()
+        return dict(image_loss=round(float(st.loss), 6), translation_rms_error=float((T.detach() - T_true).pow(2).mean().sqrt()))
+
+    warm = 10
+    one_step(0)
+    first = report()
+    for it in range(1, warm):
+        one_step(it)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(warm, warm + a.steps):
+        one_step(it)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    st.check()
+    print(json.dumps({"metric": "FateAvatar optimisation steps/s with the camera translations tracked (fused step with camera "
+                                "gradients + torch Adam on the per-frame translation)",
+                      "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": a.P, "res": a.res,
+                      "frames": n_frames, "graph": not a.no_graph, "overflows": st.overflows, "track_lr": a.track_lr,
+                      "track_offset": a.track_offset, "first": first, "last": report()}))
+
+
 def main_fateavatar(a, rank, world, dev):
+    if a.track_camera:
+        return main_track_camera(a, rank, world, dev)
     if a.train_mesh:
         return main_train_mesh(a, rank, world, dev)
     mesh_terms = moved = None
