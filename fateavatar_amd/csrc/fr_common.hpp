@@ -73,7 +73,7 @@ struct GeomView {
                             // conic as (a', b', c') = (-0.5 a, -b, -0.5 c) (fr_tile.hpp: pair_power) and the colour fed to the blend (SH result or
                             // colors_precomp) — ONE 48-byte gather per instance, not three
     float* opacity_act;     // [P] the activated opacity (the backward's API does not take the opacities; the conic is NOT stored:
-                            // k_preprocess_bwd computes the 2D covariance again anyway and inverts it with the forward's expressions)
+                            // k_preprocess_bwd computes the 2D covariance again anyway, by the forward's function: fr_project_math.hpp)
     uint8_t* clamped;       // [P] bit c set if SH colour channel c was clamped at 0
     float* dcolor_ddir;     // [P*9] d(SH colour)/d(view direction): (dR,dG,dB)/dx, /dy, /dz — computed by the forward, which has
                             // the 48 coefficients in LDS anyway, so that the backward reads 36 bytes per Gaussian instead
@@ -456,6 +456,19 @@ static inline void launch_views(KS single, KB batch, int n, const A* args, uint3
         hipLaunchKernelGGL(batch, dim3(gx, (uint32_t)n), dim3(threads), lds, s, b);
     }
 }
+// What the per-Gaussian kernels' argument structs (PreArgs, PreBwdArgs, CamBwdArgs) have in common: the frame's sizes, the
+// camera's intrinsics (focal lengths in pixels: rasterizer_impl.cu:222-223) and the inputs the projection reads.
+template <typename A>
+static inline void fill_projection_args(A& a, const fr_params& prm, const fr_inputs& in)
+{
+    a.P = prm.P, a.W = prm.W, a.H = prm.H;
+    a.raw = (prm.flags & FR_FLAG_RAW_ACTIVATIONS) ? 1 : 0;
+    a.tan_fovx = prm.tan_fovx, a.tan_fovy = prm.tan_fovy;
+    a.focal_y = prm.H / (2.0f * prm.tan_fovy), a.focal_x = prm.W / (2.0f * prm.tan_fovx);
+    a.scale_modifier = prm.scale_modifier;
+    a.means3D = in.means3D, a.scales = in.scales, a.rotations = in.rotations, a.cov3D_precomp = in.cov3D_precomp;
+    a.view = in.viewmatrix, a.proj = in.projmatrix, a.campos = in.campos;
+}
 int launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 int launch_knn(int P, const float* points, float* out, void* ws, size_t ws_bytes, hipStream_t s, int mode);
 size_t knn_workspace_bytes(int P);
@@ -537,24 +550,6 @@ __device__ __forceinline__ float act_rot_inv_norm(float r, float x, float y, flo
     return 1.0f / fmaxf(sqrtf(r * r + x * x + y * y + z * z), 1e-12f);  // torch.nn.functional.normalize, eps 1e-12
 }
 
-// Sigma3D = R S^2 R^T as its 6 upper-triangular floats (forward.cu:118-152) from the ACTIVATED scale and unit quaternion.
-// Both per-Gaussian kernels call this: the forward does not store the matrix (24 bytes per Gaussian written and read
-// back), the backward computes the same bits again from the scales and rotations it reads anyway.
-__device__ __forceinline__ void cov3d_from_scale_rot(float sc0, float sc1, float sc2, float r, float x, float y, float z,
-                                                     float scale_modifier, float (&c3)[6])
-{
-    const float s0 = scale_modifier * sc0, s1 = scale_modifier * sc1, s2 = scale_modifier * sc2;
-    // rows of the rotation matrix, each entry scaled by the scale of its COLUMN index
-    const float m00 = s0 * (1.f - 2.f * (y * y + z * z)), m01 = s1 * (2.f * (x * y - r * z)), m02 = s2 * (2.f * (x * z + r * y));
-    const float m10 = s0 * (2.f * (x * y + r * z)), m11 = s1 * (1.f - 2.f * (x * x + z * z)), m12 = s2 * (2.f * (y * z - r * x));
-    const float m20 = s0 * (2.f * (x * z - r * y)), m21 = s1 * (2.f * (y * z + r * x)), m22 = s2 * (1.f - 2.f * (x * x + y * y));
-    c3[0] = m00 * m00 + m01 * m01 + m02 * m02;
-    c3[1] = m10 * m00 + m11 * m01 + m12 * m02;
-    c3[2] = m20 * m00 + m21 * m01 + m22 * m02;
-    c3[3] = m10 * m10 + m11 * m11 + m12 * m12;
-    c3[4] = m20 * m10 + m21 * m11 + m22 * m12;
-    c3[5] = m20 * m20 + m21 * m21 + m22 * m22;
-}
 // "Which workgroup of this launch finishes last?" with TWO levels of wrapping counters: atomics on one address are
 // served one at a time (about 10 ns each on MI355X: a single counter costs 8 us for 768 workgroups, 75 us for 8192), so
 // a workgroup counts itself into one of kDoneGroups counters and only the last of each group into the final one.

@@ -6,6 +6,7 @@
 // pixel centres, conics, depths and colours are bit-comparable with the CPU oracle.  These
 // kernels are bandwidth-trivial; the missing FMAs cost nothing measurable.
 #include "fr_bind_math.hpp"
+#include "fr_project_math.hpp"
 
 // Development only, compiled out of the product build: -DFR_DIAG_PRE_ABLATE=mask — timing experiments on k_preprocess_fwd (results are WRONG): bit 0 no SH colour (no SH loads), bit 1
 //                     no counting pass, bit 2 the counting pass without its key stores, bit 3 without its global atomics, bit 4
@@ -312,52 +313,22 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
             if (p_view.z <= 0.2f) break;
             if (FR_PRE_ABLATE(5) && in_opacity > -1e30f) break;
 
-            const float4 p_hom = xform4x4(p_orig, cam.proj);
-            const float p_w = 1.0f / (p_hom.w + 0.0000001f);
+            float p_w;
+            const float4 p_hom = project_mean(p_orig, cam.proj, p_w);
             const float p_proj_x = p_hom.x * p_w, p_proj_y = p_hom.y * p_w;
 
-            // ---- Sigma3D = R S^2 R^T, 6 upper-triangular floats (forward.cu:118-152)
-            float c3[6];
-            if (a.cov3D_precomp) {
-                for (int k = 0; k < 6; k++) c3[k] = a.cov3D_precomp[6 * (size_t)idx + k];
-            } else {
-                float sc0 = in_sc[0], sc1 = in_sc[1], sc2 = in_sc[2];
-                float r = in_rot[0], x = in_rot[1], y = in_rot[2], z = in_rot[3];
-                if (a.raw) {
-                    sc0 = act_exp(sc0), sc1 = act_exp(sc1), sc2 = act_exp(sc2);
-                    const float inv = act_rot_inv_norm(r, x, y, z);
-                    r *= inv, x *= inv, y *= inv, z *= inv;
-                }
-                cov3d_from_scale_rot(sc0, sc1, sc2, r, x, y, z, a.scale_modifier, c3);   // (not stored: k_preprocess_bwd computes it again)
-            }
+            // ---- Sigma3D = R S^2 R^T, 6 upper-triangular floats (forward.cu:118-152).  Not stored: k_preprocess_bwd and
+            // k_camera_bwd compute it again, with the function called here (fr_project_math.hpp)
+            const bool precomp = a.cov3D_precomp != nullptr;
+            float in_c3[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            if (precomp)
+                for (int k = 0; k < 6; k++) in_c3[k] = a.cov3D_precomp[6 * (size_t)idx + k];
+            const Sigma3D sig = sigma3d_from_inputs(!precomp, a.raw != 0, in_sc, in_rot, a.scale_modifier, precomp, in_c3);
 
-            // ---- EWA projection to a 2D covariance (forward.cu:74-113)
-            float3 t = p_view;  // transformPoint4x3(mean, viewmatrix) again in the reference; same value
-            const float limx = 1.3f * a.tan_fovx, limy = 1.3f * a.tan_fovy;
-            const float txtz = t.x / t.z, tytz = t.y / t.z;
-            t.x = fminf(limx, fmaxf(-limx, txtz)) * t.z;
-            t.y = fminf(limy, fmaxf(-limy, tytz)) * t.z;
-            const float j00 = a.focal_x / t.z, j02 = -(a.focal_x * t.x) / (t.z * t.z);
-            const float j11 = a.focal_y / t.z, j12 = -(a.focal_y * t.y) / (t.z * t.z);
-            const float* vm = cam.view;
-            // T = J * W (2x3): row 0 and row 1; the zero products are kept so the sums round identically
-            float T0[3], T1[3];
-            for (int w = 0; w < 3; w++) {
-                const float W0 = vm[4 * w], W1 = vm[4 * w + 1], W2 = vm[4 * w + 2];
-                T0[w] = W0 * j00 + W1 * 0.0f + W2 * j02;
-                T1[w] = W0 * 0.0f + W1 * j11 + W2 * j12;
-            }
-            const float V[3][3] = {{c3[0], c3[1], c3[2]}, {c3[1], c3[3], c3[4]}, {c3[2], c3[4], c3[5]}};
-            float A0[3], A1[3];  // (T * Sigma) rows
-            for (int c = 0; c < 3; c++) {
-                A0[c] = T0[0] * V[0][c] + T0[1] * V[1][c] + T0[2] * V[2][c];
-                A1[c] = T1[0] * V[0][c] + T1[1] * V[1][c] + T1[2] * V[2][c];
-            }
-            float cov_a = A0[0] * T0[0] + A0[1] * T0[1] + A0[2] * T0[2];
-            const float cov_b = A1[0] * T0[0] + A1[1] * T0[1] + A1[2] * T0[2];
-            float cov_c = A1[0] * T1[0] + A1[1] * T1[1] + A1[2] * T1[2];
-            cov_a += 0.3f;
-            cov_c += 0.3f;
+            // ---- EWA projection to a 2D covariance (forward.cu:74-113); t = transformPoint4x3(mean, viewmatrix) again in
+            // the reference: the same value as p_view
+            const Ewa e = ewa_project(p_view, cam.view, sig.c3, a.tan_fovx, a.tan_fovy, a.focal_x, a.focal_y);
+            const float cov_a = e.cov_a, cov_b = e.cov_b, cov_c = e.cov_c;
 
             const float det = (cov_a * cov_c - cov_b * cov_b);
             if (det == 0.0f) break;
@@ -935,15 +906,9 @@ static int prepare_forward(const ForwardCall& c, hipStream_t s, bool capturing, 
         v.buckets = h->key_buckets, v.bucket_cap = h->bucket_cap;
     }
 
-    a.P = P, a.D = prm.D, a.M = prm.M, a.W = W, a.H = H;
-    a.raw = (prm.flags & FR_FLAG_RAW_ACTIVATIONS) ? 1 : 0;
-    a.tan_fovx = prm.tan_fovx, a.tan_fovy = prm.tan_fovy;
-    a.focal_y = H / (2.0f * prm.tan_fovy);  // rasterizer_impl.cu:222-223
-    a.focal_x = W / (2.0f * prm.tan_fovx);
-    a.scale_modifier = prm.scale_modifier;
-    a.means3D = in.means3D, a.scales = in.scales, a.rotations = in.rotations, a.opacities = in.opacities;
-    a.shs = in.shs, a.cov3D_precomp = in.cov3D_precomp, a.colors_precomp = in.colors_precomp;
-    a.view = in.viewmatrix, a.proj = in.projmatrix, a.campos = in.campos;
+    fill_projection_args(a, prm, in);
+    a.D = prm.D, a.M = prm.M;
+    a.opacities = in.opacities, a.shs = in.shs, a.colors_precomp = in.colors_precomp;
     a.visible = prm.aux ? prm.aux->visible : nullptr;
     a.bound = (prm.aux && prm.aux->binding) ? 1 : 0;
     if (a.bound) a.bind = bind_args(*prm.aux->binding);

@@ -8,6 +8,7 @@
 // need not pre-zero anything — or, per array, ADDED to what the array holds (FR_FLAG_ACCUMULATE:
 // gradient accumulation over the frames of a batch without a second buffer and an add kernel).
 #include "fr_bind_math.hpp"
+#include "fr_project_math.hpp"
 
 namespace fr {
 
@@ -271,65 +272,22 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
     }
     const float3 mean = make_float3(in.mean[0], in.mean[1], in.mean[2]);
     const float* vm = cam.view;
-    // Sigma3D: the caller's, or computed again from the scales and rotations (the same function and bits as the forward)
-    float q_r = 0.f, q_x = 0.f, q_y = 0.f, q_z = 0.f, rot_inv = 1.0f;
-    float sc[3] = {0.f, 0.f, 0.f};
-    float c3[6];
-    if (a.scales) {
-        q_r = in.q[0], q_x = in.q[1], q_y = in.q[2], q_z = in.q[3];
-        sc[0] = in.sc[0], sc[1] = in.sc[1], sc[2] = in.sc[2];
-        if (a.raw) {
-            sc[0] = act_exp(sc[0]), sc[1] = act_exp(sc[1]), sc[2] = act_exp(sc[2]);
-            rot_inv = act_rot_inv_norm(q_r, q_x, q_y, q_z);
-            q_r *= rot_inv, q_x *= rot_inv, q_y *= rot_inv, q_z *= rot_inv;
-        }
-    }
-    if (a.cov3D_precomp) {
-        for (int k = 0; k < 6; k++) c3[k] = in.c3[k];
-    } else {
-        cov3d_from_scale_rot(sc[0], sc[1], sc[2], q_r, q_x, q_y, q_z, a.scale_modifier, c3);
-    }
+    // Sigma3D: the caller's, or computed again from the scales and rotations — by the function the forward calls
+    // (fr_project_math.hpp): the same bits
+    const Sigma3D sig = sigma3d_from_inputs(a.scales != nullptr, a.raw != 0, in.sc, in.q, a.scale_modifier, a.cov3D_precomp != nullptr, in.c3);
 
     // ---------------- conic -> Sigma2D -> Sigma3D and mean (backward.cu:144-274)
-    float3 t = xform4x3(mean, vm);
-    const float limx = 1.3f * a.tan_fovx, limy = 1.3f * a.tan_fovy;
-    const float txtz = t.x / t.z, tytz = t.y / t.z;
-    t.x = fminf(limx, fmaxf(-limx, txtz)) * t.z;
-    t.y = fminf(limy, fmaxf(-limy, tytz)) * t.z;
-    const float x_grad_mul = txtz < -limx || txtz > limx ? 0 : 1;
-    const float y_grad_mul = tytz < -limy || tytz > limy ? 0 : 1;
-    const float h_x = a.focal_x, h_y = a.focal_y;
-    const float j00 = h_x / t.z, j02 = -(h_x * t.x) / (t.z * t.z);
-    const float j11 = h_y / t.z, j12 = -(h_y * t.y) / (t.z * t.z);
-    float T0[3], T1[3];  // T0[w] = T[0][w], T1[w] = T[1][w] of the reference's column-major T
-    for (int w = 0; w < 3; w++) {
-        const float W0 = vm[4 * w], W1 = vm[4 * w + 1], W2 = vm[4 * w + 2];
-        T0[w] = W0 * j00 + W1 * 0.0f + W2 * j02;
-        T1[w] = W0 * 0.0f + W1 * j11 + W2 * j12;
-    }
-    const float V[3][3] = {{c3[0], c3[1], c3[2]}, {c3[1], c3[3], c3[4]}, {c3[2], c3[4], c3[5]}};
-    float A0[3], A1[3];
-    for (int c = 0; c < 3; c++) {
-        A0[c] = T0[0] * V[0][c] + T0[1] * V[1][c] + T0[2] * V[2][c];
-        A1[c] = T1[0] * V[0][c] + T1[1] * V[1][c] + T1[2] * V[2][c];
-    }
-    float ca = A0[0] * T0[0] + A0[1] * T0[1] + A0[2] * T0[2];
-    const float cb = A1[0] * T0[0] + A1[1] * T0[1] + A1[2] * T0[2];
-    float cc = A1[0] * T1[0] + A1[1] * T1[1] + A1[2] * T1[2];
-    ca += 0.3f;
-    cc += 0.3f;
-    const float denom = ca * cc - cb * cb;
+    const Ewa e = ewa_project(xform4x3(mean, vm), vm, sig.c3, a.tan_fovx, a.tan_fovy, a.focal_x, a.focal_y);
     // moments of q = dL/dG * G accumulated by the blend backward -> the reference's per-Gaussian sums
     // (backward.cu:538-554): dG/ddelx = -G*(dx*A + dy*B), dG/ddely = -G*(dy*C + dx*B)
-    // The conic is not read back: it is the inverse of the 2D covariance this kernel has just computed again, with the
-    // forward's expressions (forward.cu:74-113, 207-219) — the same bits; only the activated opacity comes from the state.
-    const float det_inv = 1.f / denom;
-    const float4 co = make_float4(cc * det_inv, -cb * det_inv, ca * det_inv, in.opacity);
+    // Neither the conic nor the 2D covariance is read back: ewa_project is what the forward called (forward.cu:74-113,
+    // 207-219) — the same bits; only the activated opacity comes from the state.
+    const float opacity = in.opacity;
     // (ACC_MX / ACC_MY arrive combined with the conic per pixel: sum of q * dG/d(centre) / G, fr_common.hpp)
     const float g2x = acc[ACC_MX] * (0.5f * a.W);
     const float g2y = acc[ACC_MY] * (0.5f * a.H);
     const float dcx = -0.5f * acc[ACC_CA], dcy = -0.5f * acc[ACC_CB], dcz = -0.5f * acc[ACC_CC];
-    const float dop = (co.w != 0.f) ? acc[ACC_OP] / co.w : 0.f;
+    const float dop = (opacity != 0.f) ? acc[ACC_OP] / opacity : 0.f;
     float dcol[3] = {acc[ACC_R], acc[ACC_G], acc[ACC_B]};
     store3(a.out.dL_dmeans2D, i, g2x, g2y, 0.f, adds(G_MEANS2D));
     // fused _add_densification_stats (model/fateavatar.py:734-737); this branch is radii > 0
@@ -339,16 +297,14 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
         if (a.denom) a.denom[i] = in.dn + 1.0f;
     }
     store3(a.out.dL_dcolors, i, dcol[0], dcol[1], dcol[2], adds(G_COLORS));
-    // raw-parameter mode: d sigmoid = o (1 - o); co.w is the activated opacity the forward stored
-    if (a.out.dL_dopacity) a.out.dL_dopacity[i] = old_op + (a.raw ? dop * co.w * (1.0f - co.w) : dop);
+    // raw-parameter mode: d sigmoid = o (1 - o); `opacity` is the activated opacity the forward stored
+    if (a.out.dL_dopacity) a.out.dL_dopacity[i] = old_op + (a.raw ? dop * opacity * (1.0f - opacity) : dop);
 
-    float dL_da = 0, dL_db = 0, dL_dc = 0;
-    const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+    const CovGrad cg = conic_bwd(e, dcx, dcy, dcz);
+    const float dL_da = cg.dL_da, dL_db = cg.dL_db, dL_dc = cg.dL_dc;
+    const float(&T0)[3] = e.T0, (&T1)[3] = e.T1;
     float dcov[6] = {0, 0, 0, 0, 0, 0};
-    if (denom2inv != 0) {
-        dL_da = denom2inv * (-cc * cc * dcx + 2 * cb * cc * dcy + (denom - ca * cc) * dcz);
-        dL_dc = denom2inv * (-ca * ca * dcz + 2 * ca * cb * dcy + (denom - ca * cc) * dcx);
-        dL_db = denom2inv * 2 * (cb * cc * dcx - (denom + 2 * cb * cb) * dcy + ca * cb * dcz);
+    if (cg.live) {   // (conic_bwd's guard: not from zeros)
         dcov[0] = (T0[0] * T0[0] * dL_da + T0[0] * T1[0] * dL_db + T1[0] * T1[0] * dL_dc);
         dcov[3] = (T0[1] * T0[1] * dL_da + T0[1] * T1[1] * dL_db + T1[1] * T1[1] * dL_dc);
         dcov[5] = (T0[2] * T0[2] * dL_da + T0[2] * T1[2] * dL_db + T1[2] * T1[2] * dL_dc);
@@ -359,24 +315,9 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
     if (a.out.dL_dcov3D)
         for (int k = 0; k < 6; k++) put(a.out.dL_dcov3D + 6 * i + k, dcov[k], adds(G_COV3D));
 
-    // dL/dT (upper 2x3), backward.cu:237-248.  Vrk[c][r] is symmetric.
-    float dT0[3], dT1[3];
-    for (int c = 0; c < 3; c++) {
-        const float tv0 = T0[0] * V[c][0] + T0[1] * V[c][1] + T0[2] * V[c][2];
-        const float tv1 = T1[0] * V[c][0] + T1[1] * V[c][1] + T1[2] * V[c][2];
-        dT0[c] = 2 * tv0 * dL_da + tv1 * dL_db;
-        dT1[c] = 2 * tv1 * dL_dc + tv0 * dL_db;
-    }
-    // dL/dJ, backward.cu:252-255 (W[c][r] = vm[c + 4r])
-    const float dL_dJ00 = vm[0] * dT0[0] + vm[4] * dT0[1] + vm[8] * dT0[2];
-    const float dL_dJ02 = vm[2] * dT0[0] + vm[6] * dT0[1] + vm[10] * dT0[2];
-    const float dL_dJ11 = vm[1] * dT1[0] + vm[5] * dT1[1] + vm[9] * dT1[2];
-    const float dL_dJ12 = vm[2] * dT1[0] + vm[6] * dT1[1] + vm[10] * dT1[2];
-    const float tz = 1.f / t.z, tz2 = tz * tz, tz3 = tz2 * tz;
-    // NB the clamped t.x / t.y are treated as constants here (stop-gradient quirk of the reference)
-    const float dL_dtx = x_grad_mul * -h_x * tz2 * dL_dJ02;
-    const float dL_dty = y_grad_mul * -h_y * tz2 * dL_dJ12;
-    const float dL_dtz = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * t.x) * tz3 * dL_dJ02 + (2 * h_y * t.y) * tz3 * dL_dJ12;
+    // dL/dT -> dL/dJ -> dL/dt (backward.cu:237-270)
+    const EwaGrad eg = ewa_bwd(e, vm, sig.c3, cg, a.focal_x, a.focal_y);
+    const float dL_dtx = eg.dL_dtx, dL_dty = eg.dL_dty, dL_dtz = eg.dL_dtz;
     float dmx = vm[0] * dL_dtx + vm[1] * dL_dty + vm[2] * dL_dtz;
     float dmy = vm[4] * dL_dtx + vm[5] * dL_dty + vm[6] * dL_dtz;
     float dmz = vm[8] * dL_dtx + vm[9] * dL_dty + vm[10] * dL_dtz;
@@ -384,8 +325,8 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
     // ---------------- projection part of dL/dmean3D (backward.cu:370-387)
     {
         const float* proj = cam.proj;
-        const float4 m_hom = xform4x4(mean, proj);
-        const float m_w = 1.0f / (m_hom.w + 0.0000001f);
+        float m_w;
+        project_mean(mean, proj, m_w);
         const float mul1 = (proj[0] * mean.x + proj[4] * mean.y + proj[8] * mean.z + proj[12]) * m_w * m_w;
         const float mul2 = (proj[1] * mean.x + proj[5] * mean.y + proj[9] * mean.z + proj[13]) * m_w * m_w;
         const float px = (proj[0] * m_w - proj[3] * mul1) * g2x + (proj[1] * m_w - proj[3] * mul2) * g2y;
@@ -396,16 +337,13 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
 
     // ---------------- SH backward (backward.cu:20-139)
     if (a.shs) {
-        const float dox = mean.x - cam.campos[0], doy = mean.y - cam.campos[1], doz = mean.z - cam.campos[2];
-        const float len = sqrtf(dox * dox + doy * doy + doz * doz);
-        const float x = dox / len, y = doy / len, z = doz / len;
         // (the derivative of the colour with respect to the direction comes from the forward, GeomView::dcolor_ddir: this
         // kernel does not read the SH coefficients at all; `row`, if staged, only collects the dL_dsh row)
-        const uint32_t cl = in.cl;
-        float dRGB[3];
-        for (int c = 0; c < 3; c++) dRGB[c] = dcol[c] * (((cl >> c) & 1) ? 0 : 1);
-        const float* dd = in.dd;
-        const float dRGBdx[3] = {dd[0], dd[1], dd[2]}, dRGBdy[3] = {dd[3], dd[4], dd[5]}, dRGBdz[3] = {dd[6], dd[7], dd[8]};
+        const ShDirGrad sd = sh_dir_bwd(mean, cam.campos, in.cl, dcol, in.dd);
+        const float dox = sd.dox, doy = sd.doy, doz = sd.doz;
+        const float len = sqrtf(dox * dox + doy * doy + doz * doz);
+        const float x = dox / len, y = doy / len, z = doz / len;
+        const float(&dRGB)[3] = sd.dRGB;
         const int deg = a.D;
         const int used = (deg + 1) * (deg + 1);
         // the dL_dsh row: into the wave's LDS block (coalesced to HBM afterwards) or straight into the array.  One body,
@@ -450,15 +388,7 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
             deferred.visible = true;
         } else if (row) write_row(row, false);                             // (added to the array by unstage_rows)
         else if (a.out.dL_dsh) write_row(a.out.dL_dsh + i * Mc * 3, adds(G_SH));
-        const float ddx = dRGBdx[0] * dRGB[0] + dRGBdx[1] * dRGB[1] + dRGBdx[2] * dRGB[2];
-        const float ddy = dRGBdy[0] * dRGB[0] + dRGBdy[1] * dRGB[1] + dRGBdy[2] * dRGB[2];
-        const float ddz = dRGBdz[0] * dRGB[0] + dRGBdz[1] * dRGB[1] + dRGBdz[2] * dRGB[2];
-        // dnormvdv (auxiliary.h:107-117)
-        const float sum2 = dox * dox + doy * doy + doz * doz;
-        const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-        dmx += ((+sum2 - dox * dox) * ddx - doy * dox * ddy - doz * dox * ddz) * invsum32;
-        dmy += (-dox * doy * ddx + (sum2 - doy * doy) * ddy - doz * doy * ddz) * invsum32;
-        dmz += (-dox * doz * ddx - doy * doz * ddy + (sum2 - doz * doz) * ddz) * invsum32;
+        dmx += sd.d[0], dmy += sd.d[1], dmz += sd.d[2];
     } else if (a.out.dL_dsh && !row && !defer && !adds(G_SH)) {
         for (int k = 0; k < Mc * 3; k++) a.out.dL_dsh[i * Mc * 3 + k] = 0.f;
     }
@@ -472,7 +402,9 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
 
     // ---------------- Sigma3D -> scale, quaternion (backward.cu:278-341)
     if (a.scales) {
-        const float r = q_r, x = q_x, y = q_y, z = q_z;   // (read and activated above, for Sigma3D)
+        const float r = sig.q[0], x = sig.q[1], y = sig.q[2], z = sig.q[3];   // (activated above, for Sigma3D)
+        const float(&sc)[3] = sig.sc;
+        const float rot_inv = sig.rot_inv;
         const float s[3] = {a.scale_modifier * sc[0], a.scale_modifier * sc[1], a.scale_modifier * sc[2]};
         // Rc[c][w]: the reference's column-major R (its column c is row c of the usual rotation matrix)
         const float Rc[3][3] = {{1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y)},
@@ -706,14 +638,8 @@ int launch_backward(int n, const BackwardCall* calls, hipStream_t s)
         v[k] = ImageView::make(const_cast<void*>(calls[k].image), prm.W, prm.H);
         debug = debug || prm.debug != 0;
         PreBwdArgs& a = args[k];
-        a.P = P, a.D = prm.D, a.M = prm.M, a.W = prm.W, a.H = prm.H;
-        a.raw = (prm.flags & FR_FLAG_RAW_ACTIVATIONS) ? 1 : 0;
-        a.tan_fovx = prm.tan_fovx, a.tan_fovy = prm.tan_fovy;
-        a.focal_y = prm.H / (2.0f * prm.tan_fovy);
-        a.focal_x = prm.W / (2.0f * prm.tan_fovx);
-        a.scale_modifier = prm.scale_modifier;
-        a.means3D = in.means3D, a.scales = in.scales, a.rotations = in.rotations, a.shs = in.shs;
-        a.cov3D_precomp = in.cov3D_precomp, a.view = in.viewmatrix, a.proj = in.projmatrix, a.campos = in.campos;
+        fill_projection_args(a, prm, in);
+        a.D = prm.D, a.M = prm.M, a.shs = in.shs;
         a.radii = calls[k].radii, a.g = g[k], a.out = *calls[k].grads;
         a.grad_accum = prm.aux ? prm.aux->grad_accum : nullptr;
         a.denom = prm.aux ? prm.aux->denom : nullptr;
