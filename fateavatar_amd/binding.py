@@ -23,8 +23,9 @@ the posed mesh's Phong surface,
     gaussian._xyz      = sum_k bary_k verts[face[k]] + normalize(sum_k bary_k vert_normal[face[k]]) * _uvd[:, 2]   (:224-233, :246)
 `phong_canonical` holds what the mesh fixes once, `phong_frame` is the per-frame mesh pass (vertex normals, per-vertex
 quaternions, face area ratios: ONE kernel without atomics where the reference runs pytorch3d's verts_normals_packed,
-torch.inverse, matrix_to_quaternion and six index_add calls).  Differentiable w.r.t. uvd, rotation and scaling; the mode has no
-gradient to the posed vertices.
+torch.inverse, matrix_to_quaternion and six index_add calls).  Differentiable w.r.t. uvd, rotation and scaling; and, on a frame
+made with `phong_frame(..., differentiable=True)`, w.r.t. the posed vertices through all four routes of the reference's forward
+(`phong_frame_backward`, `phong_scatter_frame_grads`, `PhongGradBuffers`; with a detached frame a vertex gradient is refused).
 
 `bind_gaussians_deform` is FlashAvatar's binding (model/baseline/flashavatar.py:242-276): the barycentric point moved, turned and
 stretched by the ten outputs of a deformation MLP, with t = tanh(deform),
@@ -167,9 +168,98 @@ def mesh_laplacian(faces: torch.Tensor, V: int) -> MeshLaplacian:
     return MeshLaplacian(row_ptr.to(torch.int32).contiguous(), col.to(torch.int32).contiguous(), V)
 
 
-def phong_frame(canonical: PhongCanonical, verts: torch.Tensor):
+def _phong_mesh_args(c, V, who):
+    """The canonical data as `fr_phong_frame` / `fr_phong_frame_backward` take it, checked against the mesh's sizes."""
+    F = c.faces.shape[0]
+    cano, faces = _chk(c.cano_verts, torch.float32, "cano_verts"), _chk(c.faces, torch.int32, "faces")
+    off, ids = _chk(c.vf_offsets, torch.int32, "vf_offsets"), _chk(c.vf_faces, torch.int32, "vf_faces")
+    area = _chk(c.face_area, torch.float32, "face_area")
+    if cano.shape != (V, 3) or off.numel() != V + 1 or ids.numel() != 3 * F or area.numel() != F:
+        raise RuntimeError(f"{who}: the canonical data does not belong to this mesh")
+    return cano, faces, off, ids, area
+
+
+def phong_frame_backward(canonical: PhongCanonical, verts, d_vert_normals, d_vert_quats, d_face_ratio, d_verts, workspace=None):
+    """The backward of `phong_frame` (`fr_phong_frame_backward`): dLoss/dverts of the mesh pass ADDED onto `d_verts` [V,3]
+    (float32, contiguous, on the device) from the gradients of its three outputs (each may be None: zero).  Two launches on
+    the current stream, no float atomics: the same bits on every call and graph replay.  `workspace`: a preallocated uint8
+    buffer of `phong_frame_backward_workspace_bytes(V, F)` bytes (for a captured step), or None."""
+    V, F, dev = canonical.cano_verts.shape[0], canonical.faces.shape[0], d_verts.device
+    verts = _chk(verts.detach(), torch.float32, "verts")
+    if verts.shape != (V, 3) or d_verts.shape != (V, 3) or d_verts.dtype != torch.float32 or not d_verts.is_contiguous():
+        raise RuntimeError(f"phong_frame_backward: verts and d_verts must be [{V},3] float32 like the canonical mesh")
+    cano, faces, off, ids, area = _phong_mesh_args(canonical, V, "phong_frame_backward")
+    ups = []
+    for t, shape, name in ((d_vert_normals, (V, 3), "d_vert_normals"), (d_vert_quats, (V, 4), "d_vert_quats"),
+                           (d_face_ratio, (F,), "d_face_ratio")):
+        if t is not None:
+            t = _chk(t.detach(), torch.float32, name)
+            if t.numel() != int(torch.Size(shape).numel()):
+                raise RuntimeError(f"phong_frame_backward: {name} must be {list(shape)}")
+        ups.append(t)
+    need = phong_frame_backward_workspace_bytes(V, F)
+    if workspace is None:
+        workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < need or not workspace.is_cuda:
+        raise RuntimeError(f"phong_frame_backward: the workspace must hold {need} bytes on the device")
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.launch("fr_phong_frame_backward", dev, V, F, verts.data_ptr(), cano.data_ptr(), faces.data_ptr(), off.data_ptr(),
+                ids.data_ptr(), area.data_ptr(), p(ups[0]), p(ups[1]), p(ups[2]), d_verts.data_ptr(), workspace.data_ptr())
+    return d_verts
+
+
+def phong_frame_backward_workspace_bytes(V: int, F: int) -> int:
+    return int(_lib.lib().fr_phong_frame_backward_workspace_bytes(int(V), int(F)))
+
+
+class PhongGradBuffers:
+    """What the vertex gradient of ONE posed mesh is formed in, allocated once: d_verts [V,3], the gradients of `phong_frame`'s
+    three arrays (d_vert_normals [V,3], d_vert_quats [V,4], d_face_ratio [F]) as views of one flat buffer — one zeroing launch
+    — and the workspace of `phong_frame_backward`.  A captured step keeps one; hung on a posed-vertex tensor as
+    `_fr_phong_grad`, `render_bound_batch` with a `PosedPhongBinding` uses it instead of allocating."""
+
+    def __init__(self, V: int, F: int, device, zeroed: bool = False):
+        self.V, self.F = int(V), int(F)
+        n = [3 * self.V, 3 * self.V, 4 * self.V, self.F]
+        self.flat = (torch.zeros if zeroed else torch.empty)((sum(n),), dtype=torch.float32, device=device)
+        a, b, c, d = torch.split(self.flat, n)
+        self.d_verts, self.d_vert_normals, self.d_vert_quats, self.d_face_ratio = a.view(V, 3), b.view(V, 3), c.view(V, 4), d
+        self.workspace = torch.empty((max(phong_frame_backward_workspace_bytes(V, F), 1),), dtype=torch.uint8, device=device)
+
+    def zero_(self):
+        self.flat.zero_()
+
+    def check(self, V, F, device):
+        if (self.V, self.F) != (int(V), int(F)) or self.flat.device != torch.device(device):
+            raise RuntimeError(f"PhongGradBuffers: made for V = {self.V}, F = {self.F} on {self.flat.device}")
+
+
+class _PhongFrame(torch.autograd.Function):
+    """`phong_frame(differentiable=True)`: fr_phong_frame, and fr_phong_frame_backward for the posed vertices."""
+
+    @staticmethod
+    def forward(ctx, verts, *canonical):
+        c = PhongCanonical(*canonical)
+        out = phong_frame(c, verts)
+        ctx.save_for_backward(verts, *canonical)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_vn, d_vq, d_ratio):
+        verts, *canonical = ctx.saved_tensors
+        d_verts = torch.zeros(verts.shape, dtype=torch.float32, device=verts.device)
+        phong_frame_backward(PhongCanonical(*canonical), verts, d_vn, d_vq, d_ratio, d_verts)
+        return (d_verts.to(verts.dtype), *([None] * len(canonical)))
+
+
+def phong_frame(canonical: PhongCanonical, verts: torch.Tensor, differentiable: bool = False):
     """One frame of model/baseline/splattingavatar.py:203-215 for the posed `verts` [V,3]: (vert_normals [V,3],
-    vert_quats [V,4], face_ratio [F]) — one launch on the current stream, the same bits on every call.  Not differentiable."""
+    vert_quats [V,4], face_ratio [F]) — one launch on the current stream, the same bits on every call.  By default the
+    outputs are detached from `verts`.  `differentiable=True`: the same values on autograd; their backward is
+    `phong_frame_backward` (the reference's autograd through verts_normals_packed, PerVertQuaternion and
+    calc_face_area_change), and `bind_gaussians_phong` on them carries dLoss/dverts."""
+    if differentiable:
+        return _PhongFrame.apply(verts, *canonical)
     c = canonical
     verts = _chk(verts.detach(), torch.float32, "verts")
     V, F, dev = c.cano_verts.shape[0], c.faces.shape[0], verts.device
@@ -364,12 +454,84 @@ def bind_gaussians_face_local(verts, faces, binding, local_xyz, rotation, scalin
     return _bind(FACE_LOCAL, verts, local_xyz, rotation, scaling, faces, binding)
 
 
+def phong_scatter_frame_grads(verts, faces, face_index, bary, frame, uvd, rotation, scaling, g_xyz, g_rotation, g_scaling,
+                              d_verts=None, d_vert_normals=None, d_vert_quats=None, d_face_ratio=None):
+    """`fr_bind_backward_phong_frame`: the gradients of the bound values (any may be None: zero) ADDED with float atomics onto
+    d_verts [V,3] and onto the gradients of `phong_frame`'s three arrays (d_vert_normals [V,3], d_vert_quats [V,4],
+    d_face_ratio [F]; the caller zeroed them, any may be None).  All tensors float32 / int32, contiguous, on the device; one
+    launch on the current stream."""
+    b = _describe(PHONG, verts, faces, face_index, uvd, rotation, scaling, bary, frame=frame)
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.launch("fr_bind_backward_phong_frame", verts.device, C.byref(b), p(g_xyz), p(g_rotation), p(g_scaling), p(d_verts),
+                p(d_vert_normals), p(d_vert_quats), p(d_face_ratio))
+
+
+class _BindPhongFrame(torch.autograd.Function):
+    """`bind_gaussians_phong` on a differentiable frame: `_Bind`'s two launches (the same bits for uvd / rotation / scaling),
+    and fr_bind_backward_phong_frame for the posed vertices and the frame's three arrays."""
+
+    @staticmethod
+    def forward(ctx, verts, vn, vq, ratio, own, rotation, scaling, faces, face_index, bary):
+        mode, own_shape = PHONG, own.shape
+        verts, own = _chk(verts, torch.float32, "verts"), _chk(own, torch.float32, mode.own)
+        rotation, scaling = _chk(rotation, torch.float32, "rotation"), _chk(scaling, torch.float32, "scaling")
+        faces, face_index = _chk(faces, torch.int32, "faces"), _chk(face_index, torch.int32, "face_index")
+        bary = _chk(bary, torch.float32, "bary_coords")
+        args = (mode, verts, faces, face_index, own, rotation, scaling, bary, None, 0.0, False)
+        _check_shapes(mode.op, mode.shapes, *args)
+        frame = _chk_phong_frame((vn, vq, ratio), verts.shape[0], faces.shape[0], mode.op)
+        N, dev = face_index.shape[0], verts.device
+        xyz = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        rot = torch.empty((N, 4), dtype=torch.float32, device=dev)
+        scl = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        b = _describe(*args, frame)
+        _lib.launch("fr_bind_forward", dev, C.byref(b), xyz.data_ptr(), rot.data_ptr(), scl.data_ptr())
+        ctx.save_for_backward(verts, faces, face_index, own, rotation, scaling, bary, *frame)
+        ctx.own_shape = own_shape
+        ctx.grad_slots = (GradOut.of(own), GradOut.of(rotation), GradOut.of(scaling))
+        return xyz, rot, scl
+
+    @staticmethod
+    def backward(ctx, g_xyz, g_rot, g_scl):
+        verts, faces, face_index, own, rotation, scaling, bary, *frame = ctx.saved_tensors
+        mode, dev, N = PHONG, verts.device, face_index.shape[0]
+        need_v, need_vn, need_vq, need_ratio, need_o, need_r, need_s = ctx.needs_input_grad[:7]
+        c = lambda g: g.contiguous().float() if g is not None else None  # noqa: E731
+        g_xyz, g_rot, g_scl = c(g_xyz), c(g_rot), c(g_scl)
+        claim = lambda need, slot: slot.claim()[0] if need and slot is not None else None  # noqa: E731
+        d_own = _grad_buffer(need_o, claim(need_o, ctx.grad_slots[0]), mode.grad_shape(N), dev)
+        d_rot = _grad_buffer(need_r, claim(need_r, ctx.grad_slots[1]), (N, 4), dev)
+        d_scl = _grad_buffer(need_s, claim(need_s, ctx.grad_slots[2]), (N, 3), dev)
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        b = _describe(mode, verts, faces, face_index, own, rotation, scaling, bary, frame=frame)
+        if need_o or need_r or need_s:
+            _lib.launch(mode.backward, dev, C.byref(b), p(g_xyz), p(g_rot), p(g_scl), None, p(d_own), p(d_rot), p(d_scl))
+        zeros = lambda need, t: torch.zeros_like(t) if need else None  # noqa: E731
+        d_verts, d_vn, d_vq, d_ratio = (zeros(n, t) for n, t in zip((need_v, need_vn, need_vq, need_ratio), (verts, *frame)))
+        _lib.launch("fr_bind_backward_phong_frame", dev, C.byref(b), p(g_xyz), p(g_rot), p(g_scl), p(d_verts), p(d_vn), p(d_vq),
+                    p(d_ratio))
+        return (d_verts, d_vn, d_vq, d_ratio, d_own.view(ctx.own_shape) if d_own is not None else None, d_rot, d_scl, None, None,
+                None)
+
+
+def _frame_on_autograd(frame):
+    return torch.is_grad_enabled() and isinstance(frame, (tuple, list)) and len(frame) == 3 and \
+        all(isinstance(t, torch.Tensor) and t.requires_grad for t in frame)
+
+
 def bind_gaussians_phong(verts, faces, face_index, bary_coords, frame, uvd, rotation, scaling):
     """One frame of model/baseline/splattingavatar.py:224-246.  verts [V,3] (posed), faces [F,3], face_index [N],
     bary_coords [N,3], `frame` = `phong_frame(canonical, verts)` of the same posed mesh, raw uvd [N,3] / rotation [N,4] /
     scaling [N,3].  Returns (xyz [N,3], rotation [N,4], scaling [N,3]): the values the reference assigns to gaussian._xyz /
     gaussian._rotation / gaussian._scaling before render().  Only the third column of uvd is read; the first two columns of its
-    gradient are zeros (the reference's forward likewise: they only steer its CPU triangle walk)."""
+    gradient are zeros (the reference's forward likewise: they only steer its CPU triangle walk).
+
+    With a `frame` whose three tensors require grad — `phong_frame(canonical, verts, differentiable=True)` — the op also hands
+    gradients to `verts` (the barycentric point) and to the three frame arrays, and through them dLoss/dverts of the whole
+    path is what the reference's autograd gives.  With a detached frame a `verts` that requires grad is refused: the result
+    would silently lack the mesh pass's part."""
+    if _frame_on_autograd(frame):
+        return _BindPhongFrame.apply(verts, *frame, uvd, rotation, scaling, faces, face_index, bary_coords)
     return _bind(PHONG, verts, uvd, rotation, scaling, faces, face_index, bary_coords, frame=frame)
 
 

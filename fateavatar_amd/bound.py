@@ -27,8 +27,8 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from .binding import (DEFORM, FACE_LOCAL, PHONG, SHELL, PhongCanonical, _check_shapes, _chk, _chk_phong_frame, _describe, _grad_buffer,
-                      _no_vertex_gradient, phong_frame)
+from .binding import (DEFORM, FACE_LOCAL, PHONG, SHELL, PhongCanonical, PhongGradBuffers, _check_shapes, _chk, _chk_phong_frame,
+                      _describe, _grad_buffer, _no_vertex_gradient, phong_frame, phong_frame_backward, phong_scatter_frame_grads)
 from .rasterizer import (_GRAD_NAMES, _any_grad, _backward_args, _camera_grads, _camera_inputs_of, _forward_args, _forward_batch,
                          _FrameGrads, _per_view_outputs, _pick_forward_only, _SavedFrame, rasterize_gaussians_backward_batch)
 from .render import _result, _screenspace_points, _settings
@@ -113,6 +113,53 @@ class PhongBinding(NamedTuple):
         return mbs, [v.detach() for v in posed_verts]
 
 
+class _PosedPhongView(NamedTuple):
+    """A PosedPhongBinding of ONE view: `_PhongView` and what the vertex gradient needs — the canonical data, which of the
+    batch's distinct posed meshes the view is rendered from, and that mesh's preallocated buffers (or None)."""
+    faces: torch.Tensor
+    face_index: torch.Tensor
+    bary_coords: torch.Tensor
+    frame: tuple
+    canonical: PhongCanonical
+    group: int
+    buffers: Optional[PhongGradBuffers]
+
+    mode = PHONG
+    # what the frame's backward stores on top of the parameters' gradients: the gradients of the bound values
+    bound_grads = ("dL_dmeans3D", "dL_drotations", "dL_dscales")
+
+    def describe_args(self):
+        return self.bary_coords, None, 0.0, False, self.frame
+
+
+class PosedPhongBinding(NamedTuple):
+    """`PhongBinding` whose posed vertices take a gradient: `render_bound_batch` returns dLoss/dposed_verts per view for it
+    (the reference's autograd through splattingavatar.py:203-246).  The frame is `PhongBinding`'s, bit for bit — image, bound
+    values and every parameter gradient; its backward also stores the gradients of the bound values, and behind the frame's
+    launch chain `fr_bind_backward_phong_frame` scatters them per view and `fr_phong_frame_backward` runs once per distinct
+    posed mesh: views that share a mesh (the same tensor object) share one mesh pass forward, and their gradients are summed
+    into that mesh's one d_verts.  A mesh tensor may carry `_fr_phong_grad`, a `binding.PhongGradBuffers`: its gradient is then
+    formed in those preallocated buffers (zeroed by the backward itself)."""
+    faces: torch.Tensor                   # [F,3] int32
+    face_index: torch.Tensor              # [N]   int32
+    bary_coords: torch.Tensor             # [N,3]
+    canonical: PhongCanonical
+
+    mode = PHONG
+
+    def per_view(self, posed_verts):
+        faces, fidx = _chk(self.faces, torch.int32, "faces"), _chk(self.face_index, torch.int32, "face_index")
+        bary = _chk(self.bary_coords, torch.float32, "bary_coords")
+        V, frames, mbs = self.canonical.cano_verts.shape[0], {}, []
+        for verts in posed_verts:
+            if id(verts) not in frames:   # (views of one pose share its mesh pass, forward and backward)
+                frame = _chk_phong_frame(phong_frame(self.canonical, verts), V, faces.shape[0], "render_bound_batch")
+                frames[id(verts)] = (frame, len(frames))
+            frame, group = frames[id(verts)]
+            mbs.append(_PosedPhongView(faces, fidx, bary, frame, self.canonical, group, getattr(verts, "_fr_phong_grad", None)))
+        return mbs, list(posed_verts)
+
+
 class DeformBinding(NamedTuple):
     """FlashAvatar's binding (model/baseline/flashavatar.py:159-164, :262-274): the mesh topology and every Gaussian's face and
     barycentrics.  The ten outputs of the deformation MLP are per frame: the holder's `_deform` [N,10], not part of this."""
@@ -179,7 +226,7 @@ class _RasterizeBoundBatch(torch.autograd.Function):
         if not _any_grad(grad_outs):
             return (None,) * (5 + (n + 3 if ctx.camera else n) * K)
         empty = torch.Tensor([])
-        views, outs, descs, bgrads, planes = [], [], [], [], []
+        views, outs, descs, bgrads, planes, wants, posed = [], [], [], [], [], [], {}
         for k, (f, saved, fw, g, pl) in enumerate(_SavedFrame.load(ctx, grad_outs)):
             (verts, own, rotation, scaling, sh, xyz, rot, scl), mb = saved, ctx.bindings[k]
             dev, N = verts.device, xyz.shape[0]
@@ -188,15 +235,23 @@ class _RasterizeBoundBatch(torch.autograd.Function):
             claimed = f.grads.claim(accumulate=False)[0]
             outs.append({m: b for m, b in claimed.items() if m.startswith("dL_")})
             need_v, need_o, need_r, need_s = ctx.needs_input_grad[5 + n * k:5 + n * k + 4]   # (after the 5 non-tensor arguments)
+            want = f.grads.want
+            if need_v and isinstance(mb, _PosedPhongView):
+                # (the kernel is handed no d_verts in this mode: it stores the bound values' gradients, and the two calls
+                # of the Phong vertex gradient follow the launch chain below)
+                posed[k], need_v, want = (verts, own, rotation, scaling), False, want | set(mb.bound_grads)
+            wants.append(want)
             descs.append(_describe(mb.mode, verts, mb.faces, mb.face_index, own, rotation, scaling, *mb.describe_args()))
             # (the own parameter's gradient goes to the kernel under the name its mode has in fr_aux)
             bgrads.append({"d_verts": torch.zeros_like(verts) if need_v else None,
                            mb.mode.grad: _grad_buffer(need_o, claimed.get("d_own"), mb.mode.grad_shape(N), dev),
                            "d_rotation": _grad_buffer(need_r, claimed.get("d_rotation"), (N, 4), dev),
                            "d_scaling": _grad_buffer(need_s, claimed.get("d_scaling"), (N, 3), dev)})
-        res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=[f.grads.want for f in ctx.frames],
+        res = rasterize_gaussians_backward_batch(views, slots=ctx.slots, raw=True, wants=wants,
                                                  outs=outs, stats=[f.stats for f in ctx.frames], bindings=descs, bind_grads=bgrads,
                                                  planes=planes if ctx.frames[0].has_planes else None, camera=ctx.camera)
+        if posed:
+            _phong_vertex_grads(ctx.bindings, posed, res, bgrads)
         flat = [None, None, None, None, None]
         for grads, b, mb, own_shape in zip(res, bgrads, ctx.bindings, ctx.own_shapes):
             g = dict(zip(_GRAD_NAMES, grads))   # (the eight per-Gaussian arrays; camera gradients, if any, come behind them)
@@ -208,6 +263,32 @@ class _RasterizeBoundBatch(torch.autograd.Function):
         if ctx.camera:
             flat += [t for f, grads in zip(ctx.frames, res) for t in _camera_grads(f.rs, grads)]
         return tuple(flat)
+
+
+def _phong_vertex_grads(bindings, posed, res, bgrads):
+    """dLoss/dposed_verts of the views `posed` (view -> its checked verts, uvd, rotation, scaling) of a PosedPhongBinding, from
+    the gradients of the bound values their frame's backward stored in `res`: one scatter launch per view into its mesh's four
+    arrays, then the mesh pass's backward once per distinct mesh.  The mesh's d_verts becomes the gradient of the FIRST view
+    rendered from it (`bgrads[k]["d_verts"]`); autograd adds nothing for the others."""
+    meshes = {}
+    for k, (verts, own, rotation, scaling) in posed.items():
+        mb = bindings[k]
+        if mb.group not in meshes:
+            buf = mb.buffers
+            if buf is None:
+                buf = PhongGradBuffers(verts.shape[0], mb.faces.shape[0], verts.device, zeroed=True)
+            else:
+                buf.check(verts.shape[0], mb.faces.shape[0], verts.device)
+                buf.zero_()
+            meshes[mb.group] = (buf, verts, mb.canonical)
+            bgrads[k]["d_verts"] = buf.d_verts
+        buf = meshes[mb.group][0]
+        g = dict(zip(_GRAD_NAMES, res[k]))
+        phong_scatter_frame_grads(verts, mb.faces, mb.face_index, mb.bary_coords, mb.frame, own, rotation, scaling,
+                                  g["dL_dmeans3D"], g["dL_drotations"], g["dL_dscales"], buf.d_verts, buf.d_vert_normals,
+                                  buf.d_vert_quats, buf.d_face_ratio)
+    for buf, verts, canonical in meshes.values():
+        phong_frame_backward(canonical, verts, buf.d_vert_normals, buf.d_vert_quats, buf.d_face_ratio, buf.d_verts, buf.workspace)
 
 
 def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding, bg_colors, scaling_modifier=1.0, slots=None,
@@ -224,7 +305,8 @@ def render_bound_batch(viewpoint_cameras, pcs, posed_verts, binding, bg_colors, 
 
     `binding`: a `MeshBinding`, a `PhongBinding` (SplattingAvatar, model/baseline/splattingavatar.py:203-246; stand-alone op
     `binding.bind_gaussians_phong`; the holders carry `_uvd` [N,3] where FateAvatar's carry `_offset`, the posed vertices get no
-    gradient, and every view's mesh pass `binding.phong_frame` is launched here, in front of the frame's launch chain), or a
+    gradient, and every view's mesh pass `binding.phong_frame` is launched here, in front of the frame's launch chain), a
+    `PosedPhongBinding` (the same frame, and dLoss/dposed_verts behind it: the class's docstring), or a
     `FaceLocalBinding` (GaussianAvatars, model/baseline/gaussianavatars.py:144-171;
     stand-alone op `binding.bind_gaussians_face_local`).  The holders then carry the local position `_xyz` [N,3] where
     FateAvatar's carry `_offset`, and the frame is rendered with their `active_sh_degree` (the reference hands render() a

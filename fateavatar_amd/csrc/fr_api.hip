@@ -504,6 +504,39 @@ int fr_phong_frame(int32_t V, int32_t F, const float* verts, const float* cano_v
                               face_ratio, static_cast<hipStream_t>(stream));
 }
 
+int fr_bind_backward_phong_frame(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
+                                 float* d_verts, float* d_vert_normals, float* d_vert_quats, float* d_face_ratio, void* stream)
+{
+    int rc = check_binding(b);
+    if (rc) return rc;
+    if (b->mode != FR_BIND_PHONG)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_bind_backward_phong_frame: the binding is not FR_BIND_PHONG");
+    return launch_bind_backward_phong_frame(*b, g_xyz, g_rotation, g_scaling, d_verts, d_vert_normals, d_vert_quats, d_face_ratio,
+                                            static_cast<hipStream_t>(stream));
+}
+
+size_t fr_phong_frame_backward_workspace_bytes(int32_t V, int32_t F)
+{
+    (void)F;
+    return phong_frame_backward_workspace_bytes(V);
+}
+
+int fr_phong_frame_backward(int32_t V, int32_t F, const float* verts, const float* cano_verts, const int32_t* faces,
+                            const int32_t* vf_offsets, const int32_t* vf_faces, const float* face_area_canonical,
+                            const float* d_vert_normals, const float* d_vert_quats, const float* d_face_ratio, float* d_verts,
+                            void* workspace, void* stream)
+{
+    if (V < 0 || F < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_frame_backward: negative sizes");
+    if (V > 0 && F > 0) {
+        if (!verts || !cano_verts || !faces || !vf_offsets || !vf_faces || !face_area_canonical)
+            return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_frame_backward: null mesh array");
+        if (!d_verts) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_frame_backward: null d_verts");
+        if (!workspace) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_phong_frame_backward: null workspace (fr_phong_frame_backward_workspace_bytes)");
+    }
+    return launch_phong_frame_backward(V, F, verts, cano_verts, faces, vf_offsets, vf_faces, face_area_canonical, d_vert_normals,
+                                       d_vert_quats, d_face_ratio, d_verts, workspace, static_cast<hipStream_t>(stream));
+}
+
 int fr_triwalk(void* stream, const int32_t* faces_nbr, int32_t F, int32_t n, int32_t* face_index, float* bary, const float* delta,
                int32_t delta_stride, float decay, int32_t* status)
 {

@@ -589,6 +589,226 @@ __device__ __forceinline__ void bind_phong_bwd(const BindArgs& a, int n, const f
     }
 }
 
+// ---- the vertex gradient of the Phong mode (fr_phong_grad.hip).  bind_phong_bwd above is untouched: these are separate
+// launches behind it.
+//
+// (a) per Gaussian: the gradients of the bound values on to the posed vertices (the barycentric point) and on to the three
+//     arrays of the mesh pass, ADDED with float atomics at the face's three corners (as scatter_vertex_grads); any output may
+//     be null.
+struct PhongFrameGrads {
+    float* d_verts;         // [V,3]
+    float* d_vert_normals;  // [V,3]
+    float* d_vert_quats;    // [V,4]
+    float* d_face_ratio;    // [F]
+};
+
+__device__ __forceinline__ void bind_phong_frame_bwd(const BindArgs& a, int n, const float g_xyz[3], const float g_rot[4],
+                                                     const float g_scl[3], const PhongFrameGrads& o)
+{
+    const int fi = a.face_index[n];
+    const int ix[3] = {a.faces[3 * fi], a.faces[3 * fi + 1], a.faces[3 * fi + 2]};
+    const float b[3] = {a.bary[3 * n], a.bary[3 * n + 1], a.bary[3 * n + 2]};
+    const Vec3 gx = {g_xyz[0], g_xyz[1], g_xyz[2]};
+    if (o.d_verts)
+        for (int k = 0; k < 3; k++) {
+            atomic_add_f32(o.d_verts + 3 * ix[k], b[k] * gx.x), atomic_add_f32(o.d_verts + 3 * ix[k] + 1, b[k] * gx.y);
+            atomic_add_f32(o.d_verts + 3 * ix[k] + 2, b[k] * gx.z);
+        }
+    if (o.d_vert_normals) {   // xyz = .. + nb / max(|nb|, eps) * d
+        const Vec3 n0 = load3(a.vert_normals, ix[0]), n1 = load3(a.vert_normals, ix[1]), n2 = load3(a.vert_normals, ix[2]);
+        const Vec3 nb = {b[0] * n0.x + b[1] * n1.x + b[2] * n2.x, b[0] * n0.y + b[1] * n1.y + b[2] * n2.y,
+                         b[0] * n0.z + b[1] * n1.z + b[2] * n2.z};
+        const float raw = sqrtf(dot3(nb, nb)), len = fmaxf(raw, kNormEps);
+        const Vec3 nh = {nb.x / len, nb.y / len, nb.z / len};
+        const float d = a.local_xyz[3 * n + 2];
+        const float t = raw > kNormEps ? dot3(nh, gx) : 0.f;   // a clamped length did not depend on nb
+        const Vec3 dnb = {d * (gx.x - nh.x * t) / len, d * (gx.y - nh.y * t) / len, d * (gx.z - nh.z * t) / len};
+        for (int k = 0; k < 3; k++) {
+            atomic_add_f32(o.d_vert_normals + 3 * ix[k], b[k] * dnb.x), atomic_add_f32(o.d_vert_normals + 3 * ix[k] + 1, b[k] * dnb.y);
+            atomic_add_f32(o.d_vert_normals + 3 * ix[k] + 2, b[k] * dnb.z);
+        }
+    }
+    if (o.d_vert_quats) {   // rotation = standardize(qb (x) r), qb = sum_k b_k vq[i_k]
+        float qb[4], dq[4], dr[4];
+        phong_base_quat(a, ix[0], ix[1], ix[2], b[0], b[1], b[2], qb);
+        const float r[4] = {a.rotation[4 * n], a.rotation[4 * n + 1], a.rotation[4 * n + 2], a.rotation[4 * n + 3]};
+        quat_multiply_bwd(qb, r, g_rot, dq, dr);
+        for (int k = 0; k < 3; k++)
+            for (int c = 0; c < 4; c++) atomic_add_f32(o.d_vert_quats + 4 * ix[k] + c, b[k] * dq[c]);
+    }
+    if (o.d_face_ratio)   // scaling = scaling * face_ratio[f]
+        atomic_add_f32(o.d_face_ratio + fi, g_scl[0] * a.scaling[3 * n] + g_scl[1] * a.scaling[3 * n + 1] + g_scl[2] * a.scaling[3 * n + 2]);
+}
+
+// (b) the backward of the mesh pass.  gradient of y = x / max(|x|, eps) w.r.t. x: `len` is the clamped length
+__device__ __forceinline__ Vec3 f_normalize_bwd(Vec3 g, Vec3 y, float len, float eps)
+{
+    const float t = len > eps ? dot3(y, g) : 0.f;
+    return {(g.x - y.x * t) / len, (g.y - y.y * t) / len, (g.z - y.z * t) / len};
+}
+
+// phong_tbn with what its backward needs: the same expressions in the same order
+struct PhongTbn {
+    Vec3 d, e, n, X, Y, Z;
+    float l0, l1, l2, ld;   // the clamped lengths of cross(d, e), cross(d, n), cross(d, X), d
+};
+__device__ __forceinline__ Vec3 f_normalize_len(Vec3 x, float eps, float& len)
+{
+    len = fmaxf(sqrtf(dot3(x, x)), eps);
+    return {x.x / len, x.y / len, x.z / len};
+}
+__device__ __forceinline__ PhongTbn phong_tbn_full(Vec3 a, Vec3 b, Vec3 c)
+{
+    PhongTbn t;
+    t.d = sub(b, a), t.e = sub(c, a);
+    t.n = f_normalize_len(cross3(t.d, t.e), kNormEps, t.l0);
+    t.X = f_normalize_len(cross3(t.d, t.n), kNormEps, t.l1);
+    t.Y = f_normalize_len(cross3(t.d, t.X), kNormEps, t.l2);
+    t.Z = f_normalize_len(t.d, kNormEps, t.ld);
+    return t;
+}
+// gradients of X, Y, Z on to the triangle's corners (z = x cross y: dx = y cross g, dy = g cross x), last to first
+__device__ __forceinline__ void phong_tbn_bwd(const PhongTbn& t, Vec3 dX, Vec3 dY, Vec3 dZ, Vec3& da, Vec3& db, Vec3& dc)
+{
+    Vec3 dd = f_normalize_bwd(dZ, t.Z, t.ld, kNormEps);
+    const Vec3 dc2 = f_normalize_bwd(dY, t.Y, t.l2, kNormEps);     // Y = normalize(d x X)
+    dd = add(dd, cross3(t.X, dc2));
+    dX = add(dX, cross3(dc2, t.d));
+    const Vec3 dc1 = f_normalize_bwd(dX, t.X, t.l1, kNormEps);     // X = normalize(d x n)
+    dd = add(dd, cross3(t.n, dc1));
+    const Vec3 dn = cross3(dc1, t.d);
+    const Vec3 dc0 = f_normalize_bwd(dn, t.n, t.l0, kNormEps);     // n = normalize(d x e)
+    dd = add(dd, cross3(t.e, dc0));
+    const Vec3 de = cross3(dc0, t.d);
+    db = add(db, dd), dc = add(dc, de), da = sub(da, add(dd, de));
+}
+
+struct PhongFrameBwdArgs {
+    int V, F;
+    const float* verts;           // [V,3] posed
+    const float* cano_verts;      // [V,3]
+    const int* faces;             // [F,3]
+    const int* vf_offsets;        // [V+1]
+    const int* vf_faces;          // [3F]
+    const float* area_cano;       // [F]
+    const float* d_vert_normals;  // [V,3] upstream, may be null (zero)
+    const float* d_vert_quats;    // [V,4] upstream, may be null
+    const float* d_face_ratio;    // [F]   upstream, may be null
+    float* sums;                  // [V,7] workspace: the gradients of the unnormalised sums ns_u (3) and qs_u (4)
+    float* d_verts;               // [V,3] added to
+};
+
+// first launch, vertex v: ns_v and qs_v again from the expressions phong_vertex forms them with, then the upstream gradients
+// through the two F.normalize(eps=1e-6).  The row is walked by `stride` lanes (lane `first` takes the entries first,
+// first + stride, ...; the kernel adds the lanes' partial sums in a fixed butterfly order): a head mesh's rows hold 1 .. 32
+// faces, and one lane per vertex makes its whole wave wait for the longest row.
+__device__ __forceinline__ void phong_vertex_sums_partial(const PhongFrameBwdArgs& a, int v, int first, int stride, Vec3& ns, float qs[4])
+{
+    const int end = a.vf_offsets[v + 1];
+    for (int e = a.vf_offsets[v] + first; e < end; e += stride) {
+        const int fi = a.vf_faces[e];
+        const int i0 = a.faces[3 * fi], i1 = a.faces[3 * fi + 1], i2 = a.faces[3 * fi + 2];
+        const Vec3 p0 = load3(a.verts, i0), p1 = load3(a.verts, i1), p2 = load3(a.verts, i2);
+        ns = add(ns, phong_face_cross(p0, p1, p2));
+        float q[4];
+        phong_face_quat(p0, p1, p2, load3(a.cano_verts, i0), load3(a.cano_verts, i1), load3(a.cano_verts, i2), q);
+        const float w = a.area_cano[fi];
+        for (int k = 0; k < 4; k++) qs[k] = qs[k] + w * q[k];
+    }
+}
+__device__ __forceinline__ void phong_vertex_sums_finish(const PhongFrameBwdArgs& a, int v, Vec3 ns, const float qs[4])
+{
+    float* out = a.sums + 7 * (size_t)v;
+    {
+        float len;
+        const Vec3 y = f_normalize_len(ns, kVertEps, len);
+        const Vec3 g = a.d_vert_normals ? load3(a.d_vert_normals, v) : Vec3{0.f, 0.f, 0.f};
+        const Vec3 d = f_normalize_bwd(g, y, len, kVertEps);
+        out[0] = d.x, out[1] = d.y, out[2] = d.z;
+    }
+    {
+        const float len = fmaxf(sqrtf(qs[0] * qs[0] + qs[1] * qs[1] + qs[2] * qs[2] + qs[3] * qs[3]), kVertEps);
+        float g[4] = {0.f, 0.f, 0.f, 0.f}, t = 0.f;
+        if (a.d_vert_quats)
+            for (int k = 0; k < 4; k++) g[k] = a.d_vert_quats[4 * v + k];
+        if (len > kVertEps)
+            for (int k = 0; k < 4; k++) t += (qs[k] / len) * g[k];
+        for (int k = 0; k < 4; k++) out[3 + k] = (g[k] - (qs[k] / len) * t) / len;
+    }
+}
+
+// what face fi hands to its three corners: through the face cross product (vertex normals, area ratio) and through the face
+// quaternion (matrix_to_quaternion of M = R_p R_c^T, tbn of the posed triangle; the canonical mesh is constant)
+__device__ __forceinline__ void phong_face_bwd(const PhongFrameBwdArgs& a, int fi, Vec3& dv0, Vec3& dv1, Vec3& dv2)
+{
+    const int i0 = a.faces[3 * fi], i1 = a.faces[3 * fi + 1], i2 = a.faces[3 * fi + 2];
+    const Vec3 p0 = load3(a.verts, i0), p1 = load3(a.verts, i1), p2 = load3(a.verts, i2);
+    const float* s0 = a.sums + 7 * (size_t)i0;
+    const float* s1 = a.sums + 7 * (size_t)i1;
+    const float* s2 = a.sums + 7 * (size_t)i2;
+    const float area = a.area_cano[fi];
+    dv0 = dv1 = dv2 = Vec3{0.f, 0.f, 0.f};
+    {   // c = (p2 - p1) x (p0 - p1): every corner's ns takes c; ratio = (|c| / 2 + damping) / (A + damping)
+        const Vec3 u = sub(p2, p1), w = sub(p0, p1);
+        const Vec3 c = cross3(u, w);
+        Vec3 gc = {(s0[0] + s1[0]) + s2[0], (s0[1] + s1[1]) + s2[1], (s0[2] + s1[2]) + s2[2]};
+        const float len = sqrtf(dot3(c, c));
+        if (a.d_face_ratio && len > 0.f) gc = add(gc, mul(c, a.d_face_ratio[fi] / (2.0f * len * (area + kPhongDamping))));
+        const Vec3 du = cross3(w, gc), dw = cross3(gc, u);
+        dv2 = add(dv2, du), dv0 = add(dv0, dw), dv1 = sub(dv1, add(du, dw));
+    }
+    {   // every corner's qs takes A q_f
+        float gq[4];
+        for (int k = 0; k < 4; k++) gq[k] = area * ((s0[3 + k] + s1[3 + k]) + s2[3 + k]);
+        const PhongTbn tp = phong_tbn_full(p0, p1, p2);
+        Vec3 Xc, Yc, Zc;
+        phong_tbn(load3(a.cano_verts, i0), load3(a.cano_verts, i1), load3(a.cano_verts, i2), Xc, Yc, Zc);
+        const Vec3 m0 = add(add(mul(tp.X, Xc.x), mul(tp.Y, Yc.x)), mul(tp.Z, Zc.x));
+        const Vec3 m1 = add(add(mul(tp.X, Xc.y), mul(tp.Y, Yc.y)), mul(tp.Z, Zc.y));
+        const Vec3 m2 = add(add(mul(tp.X, Xc.z), mul(tp.Y, Yc.z)), mul(tp.Z, Zc.z));
+        const QuatSel qs = frame_to_quaternion(m0, m1, m2);
+        Vec3 dm0 = {0.f, 0.f, 0.f}, dm1 = {0.f, 0.f, 0.f}, dm2 = {0.f, 0.f, 0.f};
+        frame_to_quaternion_bwd(qs, gq, dm0, dm1, dm2);
+        // column j of M = X_p X_c[j] + Y_p Y_c[j] + Z_p Z_c[j]
+        const Vec3 dX = add(add(mul(dm0, Xc.x), mul(dm1, Xc.y)), mul(dm2, Xc.z));
+        const Vec3 dY = add(add(mul(dm0, Yc.x), mul(dm1, Yc.y)), mul(dm2, Yc.z));
+        const Vec3 dZ = add(add(mul(dm0, Zc.x), mul(dm1, Zc.y)), mul(dm2, Zc.z));
+        phong_tbn_bwd(tp, dX, dY, dZ, dv0, dv1, dv2);
+    }
+}
+
+// second launch, vertex v: the sum over its incidence row of what every face hands to THIS corner, the row walked by `stride`
+// lanes as above.  A face with a repeated corner is in the row once per corner (phong_canonical): the k-th of its entries
+// takes the k-th matching corner.
+__device__ __forceinline__ Vec3 phong_vertex_gather_partial(const PhongFrameBwdArgs& a, int v, int first, int stride)
+{
+    Vec3 acc = {0.f, 0.f, 0.f};
+    const int begin = a.vf_offsets[v], end = a.vf_offsets[v + 1];
+    for (int e = begin + first; e < end; e += stride) {
+        const int fi = a.vf_faces[e];
+        int occ = 0;
+        if (e - 1 >= begin && a.vf_faces[e - 1] == fi) occ++;
+        if (e - 2 >= begin && a.vf_faces[e - 2] == fi) occ++;
+        Vec3 dv0, dv1, dv2;
+        phong_face_bwd(a, fi, dv0, dv1, dv2);
+        int seen = 0;
+        Vec3 mine = {0.f, 0.f, 0.f};
+        if (a.faces[3 * fi] == v && seen++ == occ) mine = dv0;
+        if (a.faces[3 * fi + 1] == v && seen++ == occ) mine = dv1;
+        if (a.faces[3 * fi + 2] == v && seen++ == occ) mine = dv2;
+        acc = add(acc, mine);
+    }
+    return acc;
+}
+// the owning lane's plain read-add-store; a vertex without a face is not touched
+__device__ __forceinline__ void phong_vertex_gather_finish(const PhongFrameBwdArgs& a, int v, Vec3 acc)
+{
+    if (a.vf_offsets[v + 1] > a.vf_offsets[v]) {
+        a.d_verts[3 * v] = a.d_verts[3 * v] + acc.x, a.d_verts[3 * v + 1] = a.d_verts[3 * v + 1] + acc.y;
+        a.d_verts[3 * v + 2] = a.d_verts[3 * v + 2] + acc.z;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // FR_BIND_DEFORM — FlashAvatar's binding (model/baseline/flashavatar.py:242-276): with t = tanh(deform) of the ten RAW outputs
 // of the deformation MLP for this Gaussian in this frame,

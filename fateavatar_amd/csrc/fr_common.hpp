@@ -491,6 +491,13 @@ int launch_face_scale(int F, const float* verts, const int* faces, float* out, h
 int launch_phong_frame(int V, int F, const float* verts, const float* cano_verts, const int* faces, const int* vf_offsets,
                        const int* vf_faces, const float* area_cano, float* vert_normals, float* vert_quats, float* face_ratio,
                        hipStream_t s);
+// the vertex gradient of the Phong-surface binding (fr_phong_grad.hip)
+int launch_bind_backward_phong_frame(const fr_binding& b, const float* g_xyz, const float* g_rot, const float* g_scale, float* d_verts,
+                                     float* d_vert_normals, float* d_vert_quats, float* d_face_ratio, hipStream_t s);
+size_t phong_frame_backward_workspace_bytes(int V);
+int launch_phong_frame_backward(int V, int F, const float* verts, const float* cano_verts, const int* faces, const int* vf_offsets,
+                                const int* vf_faces, const float* area_cano, const float* d_vert_normals, const float* d_vert_quats,
+                                const float* d_face_ratio, float* d_verts, void* workspace, hipStream_t s);
 // the walk on the triangle mesh and the Phong-surface fit (fr_phongsurf.hip)
 int launch_triwalk(const int* nbr, int F, int n, int* face_index, float* bary, const float* delta, int delta_stride, float decay,
                    int* status, hipStream_t s);

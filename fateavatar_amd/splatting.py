@@ -27,7 +27,8 @@ step — mesh pass included — ONE HIP graph.
 
 NOT here:
   * its MSE / scale / LPIPS loss terms (config/splattingavatar.yaml:13-20): the image term is L1 (`rgb_loss` 1.0)
-  * gradients to the posed vertices (the reference's tracking / deformer rates): the mesh pass is not differentiable
+  * camera gradients for this step (render through a model.PoseCamera), and FLAME itself: `SplattingStep(mesh_grad=True)` hands
+    dLoss/dposed_verts back (`d_verts`), the mesh's own parameters and their optimizer stay the caller's torch
   * data-parallel runs of the step (`reduce_densification_stats`)
   * `max_radii2D` (see `densify_and_prune`)
 """
@@ -38,8 +39,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .binding import PhongCanonical, bind_gaussians_phong, phong_canonical, phong_frame
-from .bound import PhongBinding, render_bound_batch
+from .binding import PhongCanonical, PhongGradBuffers, bind_gaussians_phong, phong_canonical, phong_frame
+from .bound import PhongBinding, PosedPhongBinding, render_bound_batch
 from .flat import FlatParams
 from .gs_utils import RGB2SH, build_rotation
 from .model import TorchCamera
@@ -134,39 +135,62 @@ class SplattingStep(CloneSplitStep):
     group keeps its place and rate)."""
     LRS = SPLATTING_LRS
     VERTEX_GRAD = False
-    VERTEX_GRAD_MISSING = ("the Phong-surface binding has no vertex gradient (its per-frame mesh pass is not differentiable, "
-                           "and fr_backward refuses fr_aux::d_verts in that mode)")
+    VERTEX_GRAD_MISSING = ("the Phong-surface binding has no vertex gradient under this name (fr_backward refuses "
+                           "fr_aux::d_verts in that mode); its vertex gradient is two calls of its own behind the frame: "
+                           "ask for it with `mesh_grad=True`")
     LR_KEYS = {"_uvd": "uvd", "_opacity": "opacity", "_features_dc": "feature_dc", "_features_rest": "feature_rest",
                "_rotation": "rotation", "_scaling": "scaling"}
 
     def __init__(self, pc: SplattingGaussians, canonical: PhongCanonical, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
-                 lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True, vertex_grad: bool = False):
+                 lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True, vertex_grad: bool = False,
+                 mesh_grad: bool = False):
         """`canonical`: `binding.phong_canonical(cano_verts, faces)`; `verts` [V,3]: any pose of the mesh (sizes the step's
         static vertex buffer and is its first content).  `fold_binding` (default): the per-Gaussian binding is evaluated
         inside the rasterizer's per-Gaussian kernels (fr_aux::binding with FR_BIND_PHONG).  False: the stand-alone
         `bind_gaussians_phong` op in front of render() (same results; the A/B and the op's own user).
-        `vertex_grad=True` raises: the Phong-surface binding has no gradient to the posed vertices."""
+        `mesh_grad`: after every `step()`, `d_verts` [V,3] holds THIS step's dLoss/dposed_verts — through the barycentric
+        point, the vertex normals, the per-vertex quaternions and the face area ratios, as the reference's autograd forms it
+        (splattingavatar.py:203-246) — like `AvatarStep(vertex_grad=True)`: the caller goes on with
+        `posed_verts.backward(step.d_verts)` into whatever made the mesh.  One preallocated buffer (`PhongGradBuffers`, per
+        mesh, not per Gaussian: density control leaves it alone); its zeroing, the per-Gaussian scatter and the mesh pass's
+        backward are launches of the step, inside its captured graph.  Parameters and moments are what they are without it.
+        `vertex_grad=True` raises: that name stays the refusal it was; the gradient is asked for as `mesh_grad`."""
+        self.mesh_grad = bool(mesh_grad)
         self.canonical = PhongCanonical(*[t.to(pc.flat.device).contiguous() for t in canonical])
         if pc.P and (int(pc.face_index.min()) < 0 or int(pc.face_index.max()) >= int(self.canonical.faces.shape[0])):
             raise ValueError("SplattingStep: `face_index` names a face the mesh does not have")
         super().__init__(pc, self.canonical.faces, camera, bg, verts, lrs, use_graph, fold_binding, data_parallel=False,
                          vertex_grad=vertex_grad)
+        if self.mesh_grad:
+            self._mesh_buffers = PhongGradBuffers(self.verts.shape[0], self.faces.shape[0], self.dev, zeroed=True)
+            self.d_verts = self._mesh_buffers.d_verts
+
+    def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor, _extra=()) -> torch.Tensor:
+        if self.mesh_grad:
+            posed_verts = posed_verts.detach()     # (as BoundStep.step with vertex_grad: only the values are loaded)
+        return super().step(camera, posed_verts, gt_image, _extra)
 
     def _forward_backward(self):
         pc = self.pc
         pc.begin_step()                                             # zero_grad(set_to_none=True)
         stats = (self.xyz_gradient_accum, self.denom, pc.overflow_word)
+        verts, binding = self.verts, PhongBinding
+        if self.mesh_grad:     # a leaf over the static buffer's storage (no copy) that carries the step's gradient buffers
+            verts, binding = self.verts.detach().requires_grad_(True), PosedPhongBinding
+            verts._fr_phong_grad = self._mesh_buffers
         if self.fold_binding:
             from . import rasterizer
-            out = render_bound_batch([self.cam], [_SplattingFrame(pc, stats)], [self.verts],
-                                     PhongBinding(self.faces, pc.face_index, pc.bary_coords, self.canonical), self.bg,
+            out = render_bound_batch([self.cam], [_SplattingFrame(pc, stats)], [verts],
+                                     binding(self.faces, pc.face_index, pc.bary_coords, self.canonical), self.bg,
                                      slots=[rasterizer._slot])[0]
         else:
-            frame = phong_frame(self.canonical, self.verts)
-            bound = bind_gaussians_phong(self.verts, self.faces, pc.face_index, pc.bary_coords, frame, pc._uvd, pc._rotation,
+            frame = phong_frame(self.canonical, verts, differentiable=self.mesh_grad)
+            bound = bind_gaussians_phong(verts, self.faces, pc.face_index, pc.bary_coords, frame, pc._uvd, pc._rotation,
                                          pc._scaling)
             out = render(self.cam, _SplattingFrame(pc, stats, bound), self.bg)
         out["render"].backward(self._image_loss_and_grad(out["render"]))   # see TrainStep
+        if self.mesh_grad and not self.fold_binding:     # (the ops' backward allocates its own: copied into the step's buffer)
+            self.d_verts.copy_(verts.grad)
         pc.collect_grads()
         self.out = self._kept(out)
 

@@ -520,8 +520,10 @@ int fr_multi_copy(int32_t n_segments, float* const* dst, const float* const* src
  * [N,3] travels in the `local_xyz` member (and its gradient in the backward's d_local_xyz slot): only its third column is
  * read, and the first two columns of its gradient are written as zeros — walking a Gaussian over the mesh (the reference's
  * CPU submodule simple_phongsurf) is outside this library.  face_index, bary, rotation, scaling, local_xyz and the three
- * fr_phong_frame arrays are required; offset, face_scale_canonical, shell_len and resize_scale are ignored.  The mode has NO
- * gradient to the posed vertices: a d_verts request is FR_ERR_INVALID_ARGUMENT.
+ * fr_phong_frame arrays are required; offset, face_scale_canonical, shell_len and resize_scale are ignored.  fr_backward and
+ * fr_bind_backward_phong hand NO gradient to the posed vertices in this mode: a d_verts request there is
+ * FR_ERR_INVALID_ARGUMENT.  The vertex gradient is two calls of its own, fr_bind_backward_phong_frame and
+ * fr_phong_frame_backward (below).
  *
  * FR_BIND_DEFORM is FlashAvatar's (model/baseline/flashavatar.py:242-276, :380-390): the barycentric point moved, turned and
  * stretched by the ten outputs of the caller's deformation MLP for this Gaussian in this frame.  With t = tanh(deform[n]),
@@ -595,10 +597,39 @@ int fr_bind_backward_deform(const fr_binding* b, const float* g_xyz, const float
  *   vert_quats [V,4]   = normalize(sum of area_canonical[f] * q_f, eps 1e-6),  q_f = matrix_to_quaternion(R_posed,f R_cano,f^T)
  *                        with R = tbn(triangle) (:846-881; the reference inverts [R|T] with torch.inverse: tbn is orthonormal)
  * One launch on hip_stream, no allocation, no synchronisation (capturable), and no float atomics: every vertex gathers its
- * faces in the list's order, so the result is the same bits on every run.  Not differentiable. */
+ * faces in the list's order, so the result is the same bits on every run.  Its backward is fr_phong_frame_backward (below). */
 int fr_phong_frame(int32_t V, int32_t F, const float* verts, const float* cano_verts, const int32_t* faces,
                    const int32_t* vf_offsets, const int32_t* vf_faces, const float* face_area_canonical, float* vert_normals,
                    float* vert_quats, float* face_ratio, void* hip_stream);
+
+/* ---- The vertex gradient of the FR_BIND_PHONG path: two separate calls behind the ones above, which stay as they are
+ * (fr_bind_backward_phong and fr_backward with fr_aux::d_verts keep refusing a d_verts request in that mode: the gradient
+ * toward the posed mesh is asked for HERE).  The reference has it from autograd through splattingavatar.py:203-246.
+ *
+ * fr_bind_backward_phong_frame: per Gaussian n on face f with corners i_k, barycentrics b_k, d = uvd[n,2],
+ * nb = sum_k b_k vert_normals[i_k], n_hat = nb / max(|nb|, 1e-12), from the gradients of the bound values:
+ *   d_verts[i_k]        += b_k g_xyz
+ *   d_vert_normals[i_k] += b_k d (g_xyz - n_hat (n_hat . g_xyz)) / max(|nb|, 1e-12)
+ *   d_vert_quats[i_k]   += b_k dq,   dq = the gradient of the quaternion product w.r.t. its first factor sum_k b_k vert_quats[i_k]
+ *   d_face_ratio[f]     += sum_c g_scaling[n,c] scaling[n,c]
+ * ADDED with float atomics into arrays the caller zeroed ([V,3], [V,3], [V,4], [F]).  Any g_* may be NULL (zero), any output
+ * may be NULL.  `b` is the `base` of an fr_binding_phong; any other mode is FR_ERR_INVALID_ARGUMENT.  One launch.
+ *
+ * fr_phong_frame_backward: the backward of fr_phong_frame.  It takes that call's inputs and the gradients of its three outputs
+ * (each may be NULL: zero) and ADDS dL/dverts onto d_verts [V,3] — the thread that owns a vertex reads, adds and stores, so it
+ * composes with the call above on the same stream.  Through F.normalize(eps=1e-6) of the per-vertex sums, the face cross
+ * product (vertex normals and area ratio), matrix_to_quaternion's selected candidate, M = R_posed R_cano^T and tbn of the posed
+ * triangle; the canonical mesh is constant.  Two launches: per vertex the gradients of the two unnormalised sums into
+ * `workspace` (fr_phong_frame_backward_workspace_bytes(V, F) bytes, 7 floats per vertex), then per vertex a gather over its
+ * incidence row.  No float atomics: the same bits on every launch and graph replay.  A vertex that belongs to no face is not
+ * touched.  Neither call allocates, synchronises or copies (capturable). */
+int fr_bind_backward_phong_frame(const fr_binding* b, const float* g_xyz, const float* g_rotation, const float* g_scaling,
+                                 float* d_verts, float* d_vert_normals, float* d_vert_quats, float* d_face_ratio, void* hip_stream);
+size_t fr_phong_frame_backward_workspace_bytes(int32_t V, int32_t F);
+int fr_phong_frame_backward(int32_t V, int32_t F, const float* verts, const float* cano_verts, const int32_t* faces,
+                            const int32_t* vf_offsets, const int32_t* vf_faces, const float* face_area_canonical,
+                            const float* d_vert_normals, const float* d_vert_quats, const float* d_face_ratio, float* d_verts,
+                            void* workspace, void* hip_stream);
 
 /* ---- SplattingAvatar's walk on the triangle mesh and Phong-surface fit (the reference's CPU submodule
  * submodules/simple_phongsurf/simple_phongsurf/).  All pointers are device pointers; no call allocates, synchronises or copies

@@ -42,6 +42,12 @@ small torch deformation network (positional encoding of the canonical point + a 
 ten outputs; torch.optim.Adam at 1e-4) that is trained through `step.d_deform`; Huber image term, SH degree 0, one GPU.
 --torch-binding: binding and Huber as the stock-PyTorch restatement (tests/flash_ref.py) with autograd in front of render().
 
+    python tools/train_synthetic.py --splatting --track-mesh [--track-offset 0.005 --track-lr 5e-4] [--binding-op | --torch-binding]
+SplattingAvatar's step with the reference's tracking optimisation next to it (train/base.py:113-156), reduced to a rigid pose: every
+frame's posed mesh gets an axis-angle and translation correction, a torch leaf of six numbers that starts --track-offset away
+from the truth (zero) and is trained by torch Adam through `posed.backward(step.d_verts)` (`SplattingStep(mesh_grad=True)`).
+Prints the mean pose error (vertex displacement) at the start and the end, and steps/s.
+
     python tools/train_synthetic.py --mono [--P 100000] [--torch-lbs]
 MonoGaussianAvatar's loop (fateavatar_amd/mono.py): --P free points (default 100 000, the reference's max_points) with a torch
 deformer network (four hidden layers of 128: expression basis, pose-corrective basis and skinning weights per point), a geometry
@@ -109,6 +115,10 @@ def main():
                     help="--fateavatar: train a per-frame camera translation leaf through AvatarStep(camera_grad=True)")
     ap.add_argument("--track-offset", type=float, default=0.005, help="--track-camera: RMS start error of the translations, per axis (m)")
     ap.add_argument("--track-lr", type=float, default=5e-4, help="--track-camera: Adam rate (config/fateavatar.yaml:50 tracking_lr)")
+    ap.add_argument("--track-mesh", action="store_true",
+                    help="--splatting: every frame's posed mesh gets a rigid correction (axis-angle + translation, a torch leaf of "
+                         "six numbers that starts --track-offset away), trained by torch Adam at --track-lr through "
+                         "SplattingStep(mesh_grad=True)'s d_verts; with --torch-binding the same through stock PyTorch autograd")
     ap.add_argument("--rigged", action="store_true",
                     help="GaussianAvatars' loop: Gaussians bound to the local frames of the template's faces (one per face, then "
                          "random faces up to --P), rendered with --sh-degree active; --binding-op as for --fateavatar")
@@ -168,6 +178,8 @@ def main():
         raise SystemExit("--mouth-mask goes with --flash")
     if (a.train_mesh or a.vertex_grad or a.mesh_terms or a.track_camera) and not (a.fateavatar and a.views_per_step == 1):
         raise SystemExit("--train-mesh / --vertex-grad / --mesh-terms / --track-camera go with --fateavatar at one frame per step")
+    if a.track_mesh and not a.splatting:
+        raise SystemExit("--track-mesh goes with --splatting")
     if a.fateavatar:
         if a.image_loss:
             raise SystemExit("--fateavatar: the D-SSIM term is not part of FateAvatar's objective (dssim_loss 0.0)")
@@ -543,7 +555,7 @@ def main_rigged(a, rank, world, dev):
                       "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
 
 
-def splatting_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_binding=False):
+def splatting_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_binding=False, mesh_grad=False):
     """SplattingAvatar's optimisation step on the synthetic INSTA-layout sequence (frame 0 is the canonical mesh): P Gaussians
     sampled on the template as the reference samples them, the step object, cameras, posed meshes and targets rendered from a
     hidden ground-truth set of the same embedding."""
@@ -581,22 +593,93 @@ def splatting_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, tor
             def _forward_backward(self):
                 pc, c = self.pc, self.canonical
                 pc.begin_step()
-                frame = phong_ref.mesh_frame(c.cano_verts, c.faces, self.verts, inverse=False)
-                bound = phong_ref.phong_bind(self.verts, c.faces, pc.face_index, pc.bary_coords, frame, pc._uvd, pc._rotation,
+                verts = self.verts.detach().requires_grad_(True) if self.mesh_grad else self.verts
+                frame = phong_ref.mesh_frame(c.cano_verts, c.faces, verts, inverse=False)
+                bound = phong_ref.phong_bind(verts, c.faces, pc.face_index, pc.bary_coords, frame, pc._uvd, pc._rotation,
                                              pc._scaling)
                 out = render(self.cam, _SplattingFrame(pc, (self.xyz_gradient_accum, self.denom, pc.overflow_word), bound), self.bg)
                 out["render"].backward(self._image_loss_and_grad(out["render"]))
+                if self.mesh_grad:     # (float32 autograd through the restatement: the A/B of the two fused calls)
+                    self.d_verts.copy_(verts.grad)
                 pc.collect_grads()
                 self.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
         cls = TorchBoundStep
     st = cls(pc, canonical, TorchCamera(insta.camera_arrays(transform)[0], dev), bg, posed_t[0], use_graph=use_graph,
-             fold_binding=fold_binding)
+             fold_binding=fold_binding, mesh_grad=mesh_grad)
     return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames)
+
+
+def main_track_mesh(a, rank, world, dev):
+    """The demonstration of `SplattingStep(mesh_grad=True)`: SplattingAvatar's Gaussians by the fused step, every frame's rigid
+    mesh correction by the caller's own Adam (the reference's per-frame tracking embeddings, train/base.py:113-156, reduced to a
+    rigid pose: FLAME itself stays the caller's torch)."""
+    if a.densify_from or a.walk_interval or a.reset_interval:
+        raise SystemExit("--track-mesh: without the maintenance schedule (--densify-from / --walk-interval / --reset-interval)")
+    P = a.P if "--P" in sys.argv else 10_000
+    # (the restatement's matrix_to_quaternion indexes by a boolean mask while autograd records, as pytorch3d's does: a host
+    # synchronisation, so the stock-PyTorch A/B cannot be captured and runs eagerly; compare it with --track-mesh --no-graph)
+    use_graph = not a.no_graph and not a.torch_binding
+    su = splatting_setup(P, a.res, dev, views=a.views, use_graph=use_graph, fold_binding=not a.binding_op,
+                         torch_binding=a.torch_binding, mesh_grad=True)
+    st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
+    g = torch.Generator().manual_seed(9)
+    # per frame (axis-angle [rad], translation [m]) about the mesh's centroid; the truth is zero
+    leaves = [(a.track_offset * torch.randn(6, generator=g)).to(dev).requires_grad_(True) for _ in range(n_frames)]
+    opt = torch.optim.Adam(leaves, lr=a.track_lr)
+    centres = posed_t.mean(dim=1, keepdim=True)
+
+    def pose(f):
+        w = leaves[f][:3]
+        zero = w.new_zeros(())
+        K = torch.stack([torch.stack([zero, -w[2], w[1]]), torch.stack([w[2], zero, -w[0]]), torch.stack([-w[1], w[0], zero])])
+        return (posed_t[f] - centres[f]) @ torch.linalg.matrix_exp(K).T + centres[f] + leaves[f][3:]
+
+    def one_step(it):
+        f = it % n_frames
+        opt.zero_grad(set_to_none=True)          # (a frame's leaf moves only in its own steps: Adam skips a leaf without a gradient)
+        posed = pose(f)
+        loss = st.step(cams[f], posed, gts[f])
+        posed.backward(st.d_verts)
+        opt.step()
+        return loss
+
+    def report():
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            all_leaves = torch.stack([l.detach() for l in leaves])
+            err = torch.stack([(pose(f) - posed_t[f]).norm(dim=1).mean() for f in range(n_frames)]).mean()
+        return dict(image_loss=round(float(st.loss), 6), mean_vertex_error_m=float(err),
+                    rotation_rms_rad=float(all_leaves[:, :3].pow(2).mean().sqrt()),
+                    translation_rms_m=float(all_leaves[:, 3:].pow(2).mean().sqrt()))
+
+    first = dict(report(), image_loss=None)
+    warm = 10
+    for it in range(warm):
+        one_step(it)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(warm, warm + a.steps):
+        one_step(it)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    st.check()
+    how = "stock PyTorch autograd (tests/phong_ref.py) in front of render()" if a.torch_binding else \
+        "differentiable stand-alone ops" if a.binding_op else "fr_bind_backward_phong_frame + fr_phong_frame_backward behind the folded frame"
+    last = report()
+    print(f"mean pose error (vertex displacement): start {first['mean_vertex_error_m']:.6f} m, end {last['mean_vertex_error_m']:.6f} m; "
+          f"{a.steps / dt:.1f} steps/s", file=sys.stderr)
+    print(json.dumps({"metric": "SplattingAvatar optimisation steps/s with every frame's rigid mesh pose tracked (fused step with "
+                                "mesh gradients + torch Adam on six numbers per frame)",
+                      "vertex_gradient": how, "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4),
+                      "P": st.pc.P, "res": a.res, "frames": n_frames, "graph": use_graph, "overflows": st.overflows,
+                      "track_lr": a.track_lr, "track_offset": a.track_offset, "first": first, "last": last}))
 
 
 def main_splatting(a, rank, world, dev):
     if world > 1:
         raise SystemExit("--splatting: data-parallel runs are not built")
+    if a.track_mesh:
+        return main_track_mesh(a, rank, world, dev)
     P = a.P if "--P" in sys.argv else 10_000
     su = splatting_setup(P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
                          torch_binding=a.torch_binding)
