@@ -295,6 +295,15 @@ __device__ __forceinline__ void bind_bwd_zero(const BindArgs& a, int n, const Bi
         for (int k = 0; k < 3; k++) o.d_scaling[3 * n + k] = 0.f;
 }
 
+// the upstream rows of a Gaussian the frame gave no gradient: all ten exactly zero (a NaN row is not)
+__device__ __forceinline__ bool bind_rows_all_zero(const float g_xyz[3], const float g_rot[4], const float g_scl[3])
+{
+    bool z = true;
+    for (int k = 0; k < 3; k++) z = z && g_xyz[k] == 0.f && g_scl[k] == 0.f;
+    for (int k = 0; k < 4; k++) z = z && g_rot[k] == 0.f;
+    return z;
+}
+
 // backward of one Gaussian: gradients of its three bound values in, gradients of offset / rotation / scaling written,
 // dL/dverts of its face's three vertices added
 __device__ __forceinline__ void bind_one_bwd(const BindArgs& a, int n, const float g_xyz[3], const float g_rot[4],

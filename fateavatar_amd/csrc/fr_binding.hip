@@ -41,6 +41,12 @@ __global__ void __launch_bounds__(256) k_bind_bwd(BindArgs a, const float* g_xyz
         for (int k = 0; k < 4; k++) gq[k] = g_rot[4 * n + k];
     if (g_scale)
         for (int k = 0; k < 3; k++) gs[k] = g_scale[3 * n + k];
+    // a Gaussian the frame dropped (culled, or non-finite: INTEGRATION.md) arrives with zero rows: zero rows out and nothing
+    // for the vertices, as preprocess_bwd_one does inside the frame — 0 x its own NaN or inf must not reach d_verts
+    if (bind_rows_all_zero(gp, gq, gs)) {
+        bind_bwd_zero(a, n, o);
+        return;
+    }
     bind_bwd(a, n, gp, gq, gs, o);
 }
 

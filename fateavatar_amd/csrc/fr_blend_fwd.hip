@@ -315,7 +315,7 @@ __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, u
     const size_t pix = (size_t)py * W + px, HW = (size_t)H * W;
     float Cr = 0.f, Cg = 0.f, Cb = 0.f, Cd = 0.f, Tf = 1.0f;
     uint32_t ncon = 0;
-    if (nu <= (uint32_t)R) {   // short tile: one round of loads, the image front to back, the suffix pass on the registers
+    if (nu <= (uint32_t)R) {   // short tile: one round of loads; the image is the suffix pass's last sum
         float cr[R], cg[R], cb[R], cd[R], To[R];
         uint32_t lw[R];
 #pragma unroll
@@ -331,8 +331,6 @@ __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, u
         for (int k = 0; k < R; k++) {
             if ((uint32_t)k < nu) {
                 const bool dead = (lw[k] & kDeadBit) != 0u;
-                Cr += cr[k], Cg += cg[k], Cb += cb[k];   // (a dead pixel's contribution is stored as 0)
-                if (PLANES) Cd += cd[k];
                 if (!dead) {
                     Tf = To[k];
                     if (lw[k] & ~kDeadBit) ncon = lw[k] & ~kDeadBit;
@@ -349,10 +347,14 @@ __device__ __forceinline__ void gather_tile(const ImageView& v, uint32_t tile, u
                     unit_state[(size_t)(u0 + (uint32_t)k) * kUnit + lane] = make_float4(Sr * inv, Sg * inv, Sb * inv, To[k]);
                     if (PLANES) pl.depth_state[(size_t)(u0 + (uint32_t)k) * kUnit + lane] = Sd * inv;
                 }
-                Sr += cr[k], Sg += cg[k], Sb += cb[k];
+                Sr += cr[k], Sg += cg[k], Sb += cb[k];   // (a dead pixel's contribution is stored as 0)
                 if (PLANES) Sd += cd[k];
             }
         }
+        // the rows are added BACK TO FRONT here as in the long tile below: units that contribute exactly 0 to every pixel behind
+        // the real ones (the instances of Gaussians dropped for a non-finite colour) may move a tile from one
+        // branch to the other, and the image must not change by a summation order
+        Cr = Sr, Cg = Sg, Cb = Sb, Cd = Sd;
     } else {
         // long tile: ONE pass over the rows, back to front, eight units per round of loads — a unit's entry state is the sum
         // of the rows behind it, the image the sum of all of them (in this order), the final transmittance and contributor

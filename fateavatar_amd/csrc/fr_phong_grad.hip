@@ -37,6 +37,9 @@ __global__ void __launch_bounds__(256) k_bind_phong_frame_bwd(BindArgs a, const 
         for (int k = 0; k < 4; k++) gq[k] = g_rot[4 * n + k];
     if (g_scale)
         for (int k = 0; k < 3; k++) gs[k] = g_scale[3 * n + k];
+    // a Gaussian the frame dropped (culled, or non-finite: INTEGRATION.md) arrives with zero rows and adds nothing — its own
+    // values may be NaN or inf, and 0 x NaN would reach every vertex of the face's two-ring through the atomics below
+    if (bind_rows_all_zero(gp, gq, gs)) return;
     bind_phong_frame_bwd(a, n, gp, gq, gs, o);
 }
 

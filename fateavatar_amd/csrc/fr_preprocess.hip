@@ -349,8 +349,6 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
             const int rx1 = min(a.ref_gx, max(0, (int)((pix_x + mr + kRefTile - 1) / kRefTile)));
             const int ry1 = min(a.ref_gy, max(0, (int)((pix_y + mr + kRefTile - 1) / kRefTile)));
             if ((rx1 - rx0) * (ry1 - ry0) == 0) break;
-            ref_tiles = (uint32_t)((rx1 - rx0) * (ry1 - ry0));
-
 
             const float opacity = a.raw ? act_sigmoid(in_opacity) : in_opacity;
             // Contract: a Gaussian whose projected state is not finite (NaN / inf position, scale,
@@ -362,6 +360,9 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
                 if (!(fabsf(chk) < 3.0e38f)) break;
             }
             alive = true;
+            // (num_rendered counts the Gaussians that end with radii > 0, as the reference's sum over radii > 0 does: set behind
+            // the finite test, cleared again where the colour turns out dead)
+            ref_tiles = (uint32_t)((rx1 - rx0) * (ry1 - ry0));
             mr_out = mr;
             rec_ca = conic_a, rec_cb = conic_b, rec_cc = conic_c, rec_op = opacity, rec_z = p_view.z;
             ctr = make_float2(pix_x, pix_y);
@@ -612,6 +613,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
             }
             PRE_TR(3);   // colour
             dead_colour = !(fabsf(raw_sum) < 3.0e38f);
+            if (dead_colour) ref_tiles = 0u;
             if (!dead_colour) {
                 radius_out = mr_out;
                 if (!FWD_ONLY) {

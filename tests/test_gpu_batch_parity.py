@@ -489,6 +489,7 @@ def test_non_finite_view_leaves_the_other_views_alone(gpu_device):
     b2 = util.HipBatch([others[0], clean, others[1]], dev)
     g2 = b2.backward_all(dpixs)
     assert (b1[1].radii.cpu().numpy()[bad] == 0).all()
+    assert b1[1].num_rendered == b2[1].num_rendered, (b1[1].num_rendered, b2[1].num_rendered)
     assert np.isfinite(b1[1].color.cpu().numpy()).all()
     assert np.array_equal(b1[1].color.cpu().numpy(), b2[1].color.cpu().numpy())
     assert np.array_equal(b1[1].final_T.cpu().numpy(), b2[1].final_T.cpu().numpy())

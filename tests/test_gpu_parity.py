@@ -1289,8 +1289,11 @@ def test_long_lists_without_the_big_sorter_launch(gpu_device):
 
 def test_non_finite_gaussians_are_dropped_not_propagated(gpu_device):
     """Contract: a Gaussian with a non-finite opacity, scale, position or SH coefficient is dropped — no
-    instance, no contribution, radius 0, zero gradient rows — instead of poisoning the image as the reference's
-    arithmetic would; every other Gaussian renders exactly as if the bad ones were not there."""
+    contribution, radius 0, zero gradient rows, not counted in num_rendered — instead of poisoning the image as the
+    reference's arithmetic would; every other Gaussian renders exactly as if the bad ones were not there.  (A Gaussian
+    whose geometry is finite and whose COLOUR is not does leave instances behind — it was binned before its colour was known —
+    with depth +inf and opacity 0: only `fr_counts::num_instances` sees them.  tests/test_gpu_nonfinite.py holds the contract
+    for every field, input form and frame path.)"""
     s = scenes.random_scene(1500, 64, 80, sh_degree=1, seed=31)
     bad = np.zeros(s.P, bool)
     bad[[3, 400, 777, 1200, 55, 910]] = True
@@ -1305,6 +1308,7 @@ def test_non_finite_gaussians_are_dropped_not_propagated(gpu_device):
     h = util.HipFrame(s, gpu_device)
     hc = util.HipFrame(clean, gpu_device)
     assert (h.radii.cpu().numpy()[bad] == 0).all()
+    assert h.num_rendered == hc.num_rendered, (h.num_rendered, hc.num_rendered)
     col = h.color.cpu().numpy()
     assert np.isfinite(col).all()
     np.testing.assert_array_equal(col, hc.color.cpu().numpy())
