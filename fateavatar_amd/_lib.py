@@ -124,6 +124,18 @@ class fr_point_lbs(C.Structure):
                 ("posedirs", C.c_void_p), ("weights", C.c_void_p), ("canonical", fr_pose_state), ("frame", fr_pose_state)]
 
 
+FR_MLP_WIDTH = 256
+FR_MLP_MAX_LAYERS = 8
+FR_MLP_MAX_OUT = 16
+FR_MLP_POINT_TILE = 128        # points per workgroup of the MLP's forward and backward-data products
+FR_MLP_CHUNK = 256             # points per split-N partial of the MLP's weight gradients
+
+
+class fr_mlp(C.Structure):
+    _fields_ = [("N", C.c_int32), ("L", C.c_int32), ("De", C.c_int32), ("Dc", C.c_int32), ("D_out", C.c_int32),
+                ("E", C.c_void_p), ("cond", C.c_void_p), ("weights", C.c_void_p)]
+
+
 class fr_image_loss_config(C.Structure):
     _fields_ = [("rgb_weight", C.c_float), ("dssim_weight", C.c_float)]
 
@@ -151,7 +163,8 @@ EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile
            "fr_binning_bytes", "fr_planes_bytes", "fr_camera_grad_workspace_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
            "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_huber_workspace_bytes", "fr_huber_loss_grad", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_mesh_terms_workspace_bytes", "fr_mesh_terms", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
            "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_bind_backward_deform", "fr_phong_frame", "fr_bind_backward_phong_frame", "fr_phong_frame_backward_workspace_bytes", "fr_phong_frame_backward", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward",
-           "fr_point_lbs_forward", "fr_point_lbs_backward", "fr_point_lbs_pose_workspace_bytes", "fr_point_lbs_backward_pose", "fr_nearest_vertex", "fr_lbs_terms_workspace_bytes", "fr_lbs_terms"]
+           "fr_point_lbs_forward", "fr_point_lbs_backward", "fr_point_lbs_pose_workspace_bytes", "fr_point_lbs_backward_pose", "fr_nearest_vertex", "fr_lbs_terms_workspace_bytes", "fr_lbs_terms",
+           "fr_mlp_workspace_bytes", "fr_mlp_forward", "fr_mlp_backward"]
 
 
 def build(force: bool = False) -> str:
@@ -305,6 +318,12 @@ def lib():
     L.fr_lbs_terms.argtypes = [C.POINTER(fr_lbs_terms_config), C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_fp] * 11 + \
         [C.c_void_p, C.c_void_p]
     L.fr_lbs_terms.restype = C.c_int
+    L.fr_mlp_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.fr_mlp_workspace_bytes.restype = C.c_size_t
+    L.fr_mlp_forward.argtypes = [C.POINTER(fr_mlp), _fp, _fp, C.c_void_p]
+    L.fr_mlp_forward.restype = C.c_int
+    L.fr_mlp_backward.argtypes = [C.POINTER(fr_mlp), _fp, _fp, _fp, _fp, C.c_void_p]
+    L.fr_mlp_backward.restype = C.c_int
     L.fr_ssim_window.argtypes = [C.POINTER(C.c_float)]
     L.fr_ssim_window.restype = None
     L.fr_image_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

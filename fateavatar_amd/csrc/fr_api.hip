@@ -780,4 +780,46 @@ int fr_scaled_sum(int32_t n_src, const float* const* src, float* dst, uint64_t c
     return launch_scaled_sum(n_src, src, dst, count, scale, static_cast<hipStream_t>(stream));
 }
 
+size_t fr_mlp_workspace_bytes(int32_t N, int32_t L)
+{
+    if (N < 0 || L < 1 || L > FR_MLP_MAX_LAYERS) return 0;
+    return mlp_workspace_bytes(N, L);
+}
+
+static int mlp_check(const fr_mlp* m, const void* workspace, const char*& why)
+{
+    why = nullptr;
+    if (!m) why = "null descriptor";
+    else if (m->N < 0) why = "negative N";
+    else if (m->L < 1 || m->L > FR_MLP_MAX_LAYERS) why = "1 <= L <= FR_MLP_MAX_LAYERS";
+    else if (m->De < 1 || m->Dc < 0 || m->De + m->Dc > FR_MLP_WIDTH) why = "De >= 1, Dc >= 0, De + Dc <= FR_MLP_WIDTH";
+    else if (m->D_out < 1 || m->D_out > FR_MLP_MAX_OUT) why = "1 <= D_out <= FR_MLP_MAX_OUT";
+    else if (!workspace) why = "null workspace";
+    else if (reinterpret_cast<uintptr_t>(workspace) & 255) why = "the workspace must be 256-byte aligned";
+    else if (m->N > 0 && (!m->E || !m->weights || (m->Dc > 0 && !m->cond))) why = "null E, weights or cond";
+    return why ? FR_ERR_INVALID_ARGUMENT : FR_OK;
+}
+
+int fr_mlp_forward(const fr_mlp* mlp, float* out, void* workspace, void* stream)
+{
+    const char* why;
+    if (mlp_check(mlp, workspace, why) != FR_OK) {
+        snprintf(g_err, sizeof(g_err), "fr_mlp_forward: %s", why);
+        return FR_ERR_INVALID_ARGUMENT;
+    }
+    if (mlp->N > 0 && !out) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_mlp_forward: null out");
+    return launch_mlp_forward(*mlp, out, workspace, static_cast<hipStream_t>(stream));
+}
+
+int fr_mlp_backward(const fr_mlp* mlp, const float* d_out, float* d_weights, float* d_cond, void* workspace, void* stream)
+{
+    const char* why;
+    if (mlp_check(mlp, workspace, why) != FR_OK) {
+        snprintf(g_err, sizeof(g_err), "fr_mlp_backward: %s", why);
+        return FR_ERR_INVALID_ARGUMENT;
+    }
+    if (!d_weights || (mlp->N > 0 && !d_out)) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_mlp_backward: null d_out or d_weights");
+    return launch_mlp_backward(*mlp, d_out, d_weights, d_cond, workspace, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

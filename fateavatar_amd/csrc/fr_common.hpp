@@ -543,6 +543,10 @@ int launch_lbs_terms(const fr_lbs_terms_config& cfg, int N, int V, int E, int J,
                      const float* posedirs, const float* shapedirs, const float* gt_weights, const float* gt_posedirs,
                      const float* gt_shapedirs, float* d_weights, float* d_posedirs, float* d_shapedirs, float* loss, void* workspace,
                      hipStream_t s);
+// FlashAvatar's deformation MLP on f32 MFMA (fr_mlp.hip)
+size_t mlp_workspace_bytes(int N, int L);
+int launch_mlp_forward(const fr_mlp& m, float* out, void* workspace, hipStream_t s);
+int launch_mlp_backward(const fr_mlp& m, const float* d_out, float* d_weights, float* d_cond, void* workspace, hipStream_t s);
 int launch_multi_copy(int n_seg, float* const* dst, const float* const* src, const unsigned long long* count, hipStream_t s);
 int launch_selftest_reduce(const float* in, float* out, hipStream_t s);
 

@@ -17,8 +17,11 @@ reference:
 What is fused: the binding runs inside the rasterizer's per-Gaussian kernels (bound.render_bound_batch with a DeformBinding;
 `fold_binding=False` keeps the stand-alone op `binding.bind_gaussians_deform` as the A/B), activations and densification
 statistics run inside the rasterizer kernels, one Huber launch, one Adam launch over the flat buffer, the whole step ONE HIP
-graph.  The MLP stays the caller's stock PyTorch, as FLAME does: the step takes this frame's `deform` [N,10] as one more static
-input and hands back `d_deform`, the caller goes on with `deform.backward(step.d_deform)` and its own optimizer.
+graph.  By default the MLP stays the caller's stock PyTorch, as FLAME does: the step takes this frame's `deform` [N,10] as one
+more static input and hands back `d_deform`, the caller goes on with `deform.backward(step.d_deform)` and its own optimizer.
+With `FlashStep(deformer=DeformMLP(...))` the network is part of the captured step (mlp.py, csrc/fr_mlp.hip): the step takes the
+frame's condition vector instead, runs the MLP's forward into its `deform` buffer and its backward from `d_deform`, and a
+second FusedAdam launch updates the network's flat buffer — still ONE graph, nothing eager between replays.
 
 The reference renders SH degree 0 (:256), so `_features_rest` is never read and only ever gets a zero gradient.  The frame hands
 the rasterizer `_features_dc` alone (M = 1), as AvatarGaussians' frames do: the image is the same; `_features_rest` keeps its
@@ -40,7 +43,9 @@ from .binding import bind_gaussians_deform
 from .bound import DeformBinding, render_bound_batch
 from .flat import FlatParams
 from .loss import REFERENCE_HUBER_LOSS, HuberLoss, huber_loss_and_grad, huber_workspace
+from .mlp import PREFIX as DEFORM_PREFIX, DeformMLP
 from .model import TorchCamera
+from .optim import FusedAdam
 from .render import render
 from .train import BoundStep
 
@@ -121,7 +126,8 @@ class FlashStep(BoundStep):
 
     def __init__(self, pc: FlashGaussians, faces: torch.Tensor, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True,
-                 huber: HuberLoss = REFERENCE_HUBER_LOSS, mouth_mask: bool = False, vertex_grad: bool = False):
+                 huber: HuberLoss = REFERENCE_HUBER_LOSS, mouth_mask: bool = False, vertex_grad: bool = False,
+                 deformer: Optional[DeformMLP] = None, deformer_lr: float = 1e-4):
         """`verts` [V,3]: any pose of the mesh (sizes the step's static vertex buffer and is its first content).
         `fold_binding` (default): the binding is evaluated inside the rasterizer's per-Gaussian kernels (fr_aux::binding with
         FR_BIND_DEFORM).  False: the stand-alone `bind_gaussians_deform` op in front of render() (same results; the A/B and the
@@ -130,7 +136,24 @@ class FlashStep(BoundStep):
         it refuses one.  `vertex_grad`: `d_verts` [V,3] holds every step's dLoss/dposed_verts (BoundStep; the reference's
         tracking optimisation, train/base.py:76-113, reaches the FLAME coefficients through it).
         After every `step()`, `d_deform` [N,10] holds THIS step's dLoss/d(deform), with the lifetime and the zeroing rules of
-        `d_verts`; `loss_terms` holds (huber + mask_weight x mouth, huber, mouth) and `loss` is its first word."""
+        `d_verts`; `loss_terms` holds (huber + mask_weight x mouth, huber, mouth) and `loss` is its first word.
+        `deformer`: a `mlp.DeformMLP` over the holder's P points makes the network part of the step:
+        `step(camera, posed_verts, cond, gt_image, mouth_mask=None)` then takes the frame's condition [Dc] where it took
+        `deform`, and the captured body is MLP forward -> frame -> MLP backward -> the Gaussians' Adam -> an Adam of the
+        network's flat buffer at `deformer_lr` (train/optim.py:55-59), skipped by the same overflow word.  `d_cond` [Dc] holds
+        THIS step's dLoss/d(cond) (the reference's tracking optimisation of expression and pose), with the lifetime rules of
+        `d_verts`.  None (default): the MLP is the caller's, nothing here changes."""
+        if deformer is not None:
+            if not isinstance(deformer, DeformMLP):
+                raise TypeError("FlashStep: `deformer` must be a mlp.DeformMLP")
+            if deformer.N != pc.P or deformer.out_dim != DEFORM_COLS:
+                raise ValueError(f"FlashStep: the deformer maps {deformer.N} points to {deformer.out_dim} columns, the step needs "
+                                 f"[{pc.P},{DEFORM_COLS}]")
+            if deformer.flat.device != pc.flat.device:
+                raise ValueError("FlashStep: the deformer and the Gaussians live on different devices")
+            if not float(deformer_lr) > 0.0:
+                raise ValueError("FlashStep: deformer_lr must be positive")
+        self.deformer, self.deformer_lr, self.deformer_adam = deformer, float(deformer_lr), None
         if int(pc.face_index.shape[0]) and (int(pc.face_index.min()) < 0 or int(pc.face_index.max()) >= int(faces.shape[0])):
             raise ValueError("FlashStep: `face_index` names a face the mesh does not have")
         self.huber = HuberLoss(*[float(x) for x in huber])
@@ -142,9 +165,27 @@ class FlashStep(BoundStep):
         self.deform = torch.zeros((pc.P, DEFORM_COLS), device=self.dev)
         self.mask = torch.zeros((1, camera.image_height, camera.image_width), device=self.dev) if mouth_mask else None
         self.d_deform = None
+        # with a deformer: the frame's condition, one more static input, and its gradient
+        self.cond = self.d_cond = None
+        if deformer is not None:
+            self.cond = torch.zeros(deformer.cond_dim, device=self.dev)
+            self.d_cond = torch.zeros(deformer.cond_dim, device=self.dev)
+
+    def _make_adam(self):
+        """The Gaussians' optimizer and, with a deformer, a FRESH one over its flat buffer; both skip on the holder's present
+        overflow word."""
+        super()._make_adam()
+        if self.deformer is not None:
+            d = self.deformer
+            self.deformer_adam = FusedAdam(d.flat.detach(), d.flat_grad, [(d.flat.numel(), self.deformer_lr)])
+            self.deformer_adam.set_skip_words([self.pc.overflow_word])
 
     def _buffers_moved(self, old_index, old_rows, *, stats):
         super()._buffers_moved(old_index, old_rows, stats=stats)
+        if self.deformer is not None:
+            if self.deformer.N != self.pc.P:
+                raise ValueError(f"FlashStep: the deformer is built over {self.deformer.N} points, the Gaussians now have {self.pc.P}")
+            self.deformer_adam.set_skip_words([self.pc.overflow_word])   # (a remapped optimizer: the word may have moved)
         if getattr(self, "deform", None) is not None and self.deform.shape[0] != self.pc.P:   # (a checkpoint with another row count)
             self.deform = torch.zeros((self.pc.P, DEFORM_COLS), device=self.dev)
             self.d_deform = None
@@ -154,6 +195,8 @@ class FlashStep(BoundStep):
         pc.begin_step()                                             # zero_grad(set_to_none=True)
         stats = (self.xyz_gradient_accum, self.denom, pc.overflow_word)
         verts = self._vertex_leaf(self.verts)
+        if self.deformer is not None:
+            self.deformer.forward_into(self.cond, self.deform)
         deform = self.deform.detach().requires_grad_(True)         # a leaf over the static buffer (no copy), as `_vertex_leaf`
         if self.fold_binding:
             from . import rasterizer
@@ -167,18 +210,31 @@ class FlashStep(BoundStep):
         out["render"].backward(g)
         self._keep_vertex_grad(verts)
         self.d_deform = deform.grad      # (inside a captured step: graph-owned storage, the same on every replay)
+        if self.deformer is not None:
+            self.deformer.backward_from(self.d_deform, self.cond, self.d_cond)
         self.out = self._kept(out)
+
+    def _body(self):
+        super()._body()
+        if self.deformer is not None:
+            self.deformer_adam.step()
 
     def step(self, camera: TorchCamera, posed_verts: torch.Tensor, deform: torch.Tensor, gt_image: torch.Tensor,
              mouth_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`deform` [N,10]: the deformation MLP's RAW outputs for this frame (only the values are loaded: it usually hangs on
-        the MLP's autograd graph).  `mouth_mask` [1,H,W] or [H,W]: required if the step was built with `mouth_mask=True`,
-        refused otherwise."""
+        the MLP's autograd graph) — or, for a step built with a `deformer`, the frame's condition vector [Dc].  `mouth_mask`
+        [1,H,W] or [H,W]: required if the step was built with `mouth_mask=True`, refused otherwise."""
         if (mouth_mask is None) != (self.mask is None):
             raise ValueError("FlashStep.step: `mouth_mask` goes with FlashStep(mouth_mask=True) (required with it, refused without)")
-        if tuple(deform.shape) != tuple(self.deform.shape):
+        if self.deformer is not None:
+            if tuple(deform.shape) != tuple(self.cond.shape):
+                raise ValueError(f"FlashStep.step: a step with a deformer takes the frame's condition [{self.cond.shape[0]}] "
+                                 f"where it took `deform`, not a tensor of shape {tuple(deform.shape)}")
+            extra = [(self.cond, deform.detach())]
+        elif tuple(deform.shape) != tuple(self.deform.shape):
             raise ValueError(f"FlashStep.step: deform must be [{self.pc.P},{DEFORM_COLS}]")
-        extra = [(self.deform, deform.detach())]
+        else:
+            extra = [(self.deform, deform.detach())]
         if mouth_mask is not None:
             extra.append((self.mask, mouth_mask.detach().reshape(self.mask.shape)))
         return super().step(camera, posed_verts.detach(), gt_image, extra)
@@ -198,6 +254,37 @@ class FlashStep(BoundStep):
     #      the deformation MLP's and FLAME's entries, which are returned as ignored keys)
     GAUSSIAN_ATTRIBUTES = ["_opacity", "_features_dc", "_features_rest", "_rotation", "_scaling", "face_index", "bary_coords"]
     RESUME_REMAPPED = False     # resumes FRESH
+
+    # with a deformer the checkpoint's 'model' also carries the network under the reference's `deformNet.*` names, and
+    # `deformer_optimizer` (an addition, like `optimizer`) its Adam state
+    def _save_extras(self, sd: dict) -> None:
+        if self.deformer is not None:
+            sd["model"].update(self.deformer.state_dict(DEFORM_PREFIX))
+            a = self.deformer_adam
+            sd["deformer_optimizer"] = {"exp_avg": a.exp_avg.clone(), "exp_avg_sq": a.exp_avg_sq.clone(), "state": a.state_words()}
+
+    def _load_extras(self, sd: dict, g: dict) -> None:
+        if self.deformer is not None:
+            self.deformer.check_state_dict(sd["model"], DEFORM_PREFIX)
+            if int(g["_opacity"].shape[0]) != self.deformer.N:
+                raise ValueError(f"FlashStep: the checkpoint holds {int(g['_opacity'].shape[0])} Gaussians, the deformer is built "
+                                 f"over {self.deformer.N} points")
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> list:
+        """BoundStep.load_state_dict; with a deformer the `deformNet.*` entries are LOADED (in place) instead of being returned
+        as ignored, and `deformer_optimizer`, if the checkpoint has one, restores the network's Adam (else it starts fresh)."""
+        ignored = super().load_state_dict(sd)
+        if self.deformer is None:
+            return ignored
+        self.deformer.load_state_dict(sd["model"], DEFORM_PREFIX)
+        opt = sd.get("deformer_optimizer")
+        if opt is not None:
+            self.deformer_adam.exp_avg.copy_(opt["exp_avg"])
+            self.deformer_adam.exp_avg_sq.copy_(opt["exp_avg_sq"])
+            self.deformer_adam.load_state_words(opt["state"])
+        mine = set(self.deformer.state_dict(DEFORM_PREFIX))
+        return [k for k in ignored if k not in mine]
 
 
 __all__ = ["DEFORM_COLS", "FLASH_LRS", "FlashGaussians", "FlashStep"]

@@ -826,6 +826,46 @@ int fr_lbs_terms(const fr_lbs_terms_config* cfg, int32_t N, int32_t V, int32_t E
                  const float* gt_posedirs, const float* gt_shapedirs, float* d_weights, float* d_posedirs, float* d_shapedirs,
                  float* loss, void* workspace, void* hip_stream);
 
+/* ---- FlashAvatar's deformation MLP (reference: `MLP`, model/baseline/flashavatar.py:434-464, fed by :238-240): L hidden ReLU
+ * layers (1 <= L <= FR_MLP_MAX_LAYERS) of width FR_MLP_WIDTH and a linear output layer of D_out <= FR_MLP_MAX_OUT columns, all
+ * float32: the products are exact-f32 MFMA (a k-ordered fmaf chain), everything else plain f32.
+ *   input row of point n = [E[n, 0:De] | cond[0:Dc]]   (E: a per-point constant; cond: ONE vector per frame; De >= 1, Dc >= 0,
+ *                                                       De + Dc <= FR_MLP_WIDTH)
+ * The broadcast half is never materialised: layer 0 is relu(E W0[:, :De]^T + (W0[:, De:] cond + b0)).
+ * `weights`: ONE flat buffer in torch's nn.Linear layout — per layer `weight` [out, in] row-major then `bias` [out], layers in
+ * order (in = De + Dc for layer 0, FR_MLP_WIDTH after it; out = FR_MLP_WIDTH, D_out for the last): a checkpoint's
+ * deformNet.fcs.{i}.weight/bias and deformNet.output_linear.* copy in and out without a transpose.  `d_weights` has the same
+ * layout.
+ * fr_mlp_forward writes the RAW outputs `out` [N, D_out] (no tanh) and saves every hidden layer's post-ReLU activations in the
+ * workspace.  fr_mlp_backward (after a forward with the same descriptor and workspace) computes, last layer first,
+ *   dZ_l = dH_l * [H_l > 0],  dH_{l-1} = dZ_l W_l,  dW_l = dZ_l^T H_{l-1},  db_l = sum_n dZ_l,
+ *   dW_0[:, De:] = db_0 (x) cond,  d_cond = W_0[:, De:]^T db_0     (`d_cond` [Dc] may be NULL)
+ * and OVERWRITES d_weights (every element; nothing is accumulated).  E gets no gradient (a registered buffer in the reference).
+ * The sums over n run in chunks of FR_MLP_CHUNK points, each a k-ordered chain, and a second launch adds the chunks' partials
+ * in chunk order: no float atomics, the same bits on every launch and every graph replay.  Ragged sizes (N against the
+ * FR_MLP_POINT_TILE-point tile, De against the MFMA's K step, D_out, the last chunk) are handled inside the kernels.
+ * N == 0 launches no kernel: the forward writes nothing, the backward zeroes d_weights and d_cond.  Sizes outside the limits,
+ * a NULL workspace, or a NULL array that N > 0 needs are FR_ERR_INVALID_ARGUMENT.
+ * `workspace`: fr_mlp_workspace_bytes(N, L) bytes, 256-byte aligned, the caller's, not shared by launches that can overlap:
+ *     (L + 2) * r256(N * FR_MLP_WIDTH * 4)                             the saved activations and two dZ buffers
+ *   + r256(ceil(N / FR_MLP_CHUNK) * (FR_MLP_WIDTH + 1) * FR_MLP_WIDTH * 4)   one layer's split-N partials (weight and bias)
+ *   + r256(FR_MLP_WIDTH * 4)                                           layer 0's bias with the condition folded in
+ * with r256 = round up to 256 (151.1 MB at N = 16 384, L = 6). */
+#define FR_MLP_WIDTH 256
+#define FR_MLP_MAX_LAYERS 8
+#define FR_MLP_MAX_OUT 16
+#define FR_MLP_POINT_TILE 128
+#define FR_MLP_CHUNK 256
+typedef struct fr_mlp {
+    int32_t N, L, De, Dc, D_out;
+    const float* E;       /* [N, De] */
+    const float* cond;    /* [Dc] (may be NULL if Dc == 0) */
+    const float* weights; /* flat, as above */
+} fr_mlp;
+size_t fr_mlp_workspace_bytes(int32_t N, int32_t L);
+int fr_mlp_forward(const fr_mlp* mlp, float* out, void* workspace, void* hip_stream);
+int fr_mlp_backward(const fr_mlp* mlp, const float* d_out, float* d_weights, float* d_cond, void* workspace, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,9 @@ FlashAvatar's step (fateavatar_amd/flash.py): Gaussians at fixed barycentric poi
 small torch deformation network (positional encoding of the canonical point + a per-frame condition, six hidden layers of 256,
 ten outputs; torch.optim.Adam at 1e-4) that is trained through `step.d_deform`; Huber image term, SH degree 0, one GPU.
 --torch-binding: binding and Huber as the stock-PyTorch restatement (tests/flash_ref.py) with autograd in front of render().
+    python tools/train_synthetic.py --flash --fused-mlp [--P 16384] [--mouth-mask] [--vertex-grad]
+The same loop with the deformation network INSIDE the captured step (fateavatar_amd/mlp.py: `FlashStep(deformer=DeformMLP(...))`,
+the reference's embedding order and network shape, f32-MFMA kernels, a second fused Adam at 1e-4): one graph replay per step.
 
     python tools/train_synthetic.py --splatting --track-mesh [--track-offset 0.005 --track-lr 5e-4] [--binding-op | --torch-binding]
 SplattingAvatar's step with the reference's tracking optimisation next to it (train/base.py:113-156), reduced to a rigid pose: every
@@ -131,6 +134,9 @@ def main():
     ap.add_argument("--flash", action="store_true",
                     help="FlashAvatar's loop: --P Gaussians (default 16 384, tex_size 128 squared) at fixed points of the template, "
                          "deformed per frame by a torch MLP trained through step.d_deform; Huber loss; --binding-op as for --fateavatar")
+    ap.add_argument("--fused-mlp", action="store_true",
+                    help="--flash: the deformation MLP runs inside the captured step (mlp.DeformMLP, fr_mlp_forward / _backward and "
+                         "a second fused Adam) instead of stock PyTorch around it")
     ap.add_argument("--mono", action="store_true",
                     help="MonoGaussianAvatar's loop: --P free points (default 100 000) deformed by learned per-point linear blend "
                          "skinning, colours from a torch network, L1 + the three blendshape terms")
@@ -173,9 +179,11 @@ def main():
     if a.flash:
         if a.image_loss or a.train_mesh or a.mesh_terms or a.fateavatar or a.rigged or a.splatting:
             raise SystemExit("--flash: FlashAvatar's step has its own image term (Huber) and no mesh terms; one model per run")
+        if a.fused_mlp and a.torch_binding:
+            raise SystemExit("--fused-mlp: the fused step has no stock-PyTorch binding variant (drop --torch-binding)")
         return main_flash(a, rank, world, dev)
-    if a.mouth_mask:
-        raise SystemExit("--mouth-mask goes with --flash")
+    if a.mouth_mask or a.fused_mlp:
+        raise SystemExit("--mouth-mask and --fused-mlp go with --flash")
     if (a.train_mesh or a.vertex_grad or a.mesh_terms or a.track_camera) and not (a.fateavatar and a.views_per_step == 1):
         raise SystemExit("--train-mesh / --vertex-grad / --mesh-terms / --track-camera go with --fateavatar at one frame per step")
     if a.track_mesh and not a.splatting:
@@ -746,11 +754,14 @@ class DeformNet(torch.nn.Module):
         return self.net(torch.cat([self.embedded, cond.expand(self.embedded.shape[0], -1)], dim=1))
 
 
-def flash_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_binding=False, mouth_mask=False, vertex_grad=False):
+def flash_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_binding=False, mouth_mask=False, vertex_grad=False,
+                fused_mlp=False):
     """FlashAvatar's optimisation step on the synthetic INSTA-layout sequence: P Gaussians at fixed points of the template (the
     reference's UV-raster sampling when P is its row count, else uniform faces), the step object, the deformation network with
     its per-frame conditions (the frame's jaw and rigid rotations, from the sequence), cameras, posed meshes, mouth masks and
-    targets rendered from a hidden ground-truth set at the same places with a per-frame deformation of its own."""
+    targets rendered from a hidden ground-truth set at the same places with a per-frame deformation of its own.
+    `fused_mlp`: `net` is a mlp.DeformMLP (the reference's embedding order; six hidden layers of 256; the last layer starts small
+    like DeformNet's) and part of the step."""
     from fateavatar_amd import insta
     from fateavatar_amd.binding import bind_gaussians_deform
     from fateavatar_amd.flash import FlashGaussians, FlashStep, _FlashFrame
@@ -785,7 +796,16 @@ def flash_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_b
             b = bind_gaussians_deform(posed_t[f], faces_t, gt.face_index, gt.bary_coords, hidden, gt._rotation, gt._scaling)
             gts.append(render(cams[f], _FlashFrame(gt, None, bound=b), bg)["render"].clone())
             masks.append((((yy - 0.62 * res) / (0.10 * res)) ** 2 + ((xx - 0.5 * res) / (0.16 * res)) ** 2 < 1).float()[None].contiguous())
-    net = DeformNet(pc.canonical_points(canon, faces_t), conds[0].numel()).to(dev)
+    extra = {}
+    if fused_mlp:
+        from fateavatar_amd.mlp import DeformMLP, embed_points
+        net = DeformMLP(embed_points(pc.canonical_points(canon, faces_t)).contiguous(), conds[0].numel(), layers=6)
+        with torch.no_grad():
+            net.weight(net.layers).mul_(0.01)
+            net.bias(net.layers).zero_()
+        extra = dict(deformer=net, deformer_lr=1e-4)
+    else:
+        net = DeformNet(pc.canonical_points(canon, faces_t), conds[0].numel()).to(dev)
     cls = FlashStep
     if torch_binding:
         from tests import flash_ref
@@ -808,7 +828,7 @@ def flash_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_b
                 self.out = self._kept(out)
         cls = TorchBoundStep
     st = cls(pc, faces_t, TorchCamera(insta.camera_arrays(transform)[0], dev), bg, posed_t[0], use_graph=use_graph,
-             fold_binding=fold_binding, mouth_mask=mouth_mask, vertex_grad=vertex_grad)
+             fold_binding=fold_binding, mouth_mask=mouth_mask, vertex_grad=vertex_grad, **extra)
     return dict(st=st, net=net, conds=conds, cams=cams, posed=posed_t, gts=gts, masks=masks, n_frames=n_frames)
 
 
@@ -817,13 +837,16 @@ def main_flash(a, rank, world, dev):
         raise SystemExit("--flash: data-parallel runs are not built")
     P = a.P if "--P" in sys.argv else 16_384
     su = flash_setup(P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
-                     torch_binding=a.torch_binding, mouth_mask=a.mouth_mask, vertex_grad=a.vertex_grad)
+                     torch_binding=a.torch_binding, mouth_mask=a.mouth_mask, vertex_grad=a.vertex_grad, fused_mlp=a.fused_mlp)
     st, net, conds, cams, posed_t, gts, masks, n_frames = (su[k] for k in ("st", "net", "conds", "cams", "posed", "gts", "masks", "n_frames"))
-    opt = torch.optim.Adam(net.parameters(), lr=1e-4)      # the reference's `deformer` group (train/optim.py:55-59)
+    # the reference's `deformer` group (train/optim.py:55-59); with --fused-mlp the step's own second Adam
+    opt = None if a.fused_mlp else torch.optim.Adam(net.parameters(), lr=1e-4)
     first = [p.detach().clone() for p in net.parameters()]
 
     def one_step(it):
         f = it % n_frames
+        if a.fused_mlp:                                    # everything is in the step: one graph replay
+            return st.step(cams[f], posed_t[f], conds[f], gts[f], masks[f] if a.mouth_mask else None)
         deform = net(conds[f])
         loss = st.step(cams[f], posed_t[f], deform, gts[f], masks[f] if a.mouth_mask else None)
         opt.zero_grad(set_to_none=True)
@@ -849,8 +872,10 @@ def main_flash(a, rank, world, dev):
         "inside the per-Gaussian kernels (fr_aux::binding, MLP-deformed)"
     moved = max(float((p.detach() - q).abs().max()) for p, q in zip(net.parameters(), first))
     print(json.dumps({"host_enqueue_ms_per_step": round(t_host / a.steps * 1e3, 4),
-                      "metric": "FlashAvatar optimisation steps/s (torch MLP + bind + render + Huber + backward + stats + Adam + MLP backward / Adam)",
-                      "binding": how, "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": st.pc.P,
+                      "metric": "FlashAvatar optimisation steps/s (fused MLP + bind + render + Huber + backward + stats + Adam + MLP backward + MLP Adam, one graph)"
+                      if a.fused_mlp else
+                      "FlashAvatar optimisation steps/s (torch MLP + bind + render + Huber + backward + stats + Adam + MLP backward / Adam)",
+                      "mlp": "fused (fr_mlp, inside the step)" if a.fused_mlp else "stock PyTorch", "binding": how, "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": st.pc.P,
                       "res": a.res, "frames": n_frames, "graph": not a.no_graph, "overflows": st.overflows,
                       "mouth_mask": bool(a.mouth_mask), "vertex_grad": bool(st.vertex_grad),
                       "loss_terms": [round(float(x), 6) for x in st.loss_terms], "mlp_weights_moved": moved,
