@@ -643,6 +643,32 @@ int fr_huber_loss_grad(const fr_huber_config* cfg, int32_t C, int32_t H, int32_t
     return launch_huber_loss_grad(*cfg, C, H, W, img, gt, mask, grad, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
+size_t fr_pixel_loss_workspace_bytes(void) { return pixel_loss_workspace_bytes(); }
+
+int fr_pixel_loss_grad(const fr_pixel_loss_config* cfg, int32_t C, int32_t H, int32_t W, const float* img, const float* gt,
+                       float* grad, float* loss, void* workspace, void* stream)
+{
+    if (!cfg || !img || !gt || !loss || !workspace)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_pixel_loss_grad: null configuration, img, gt, loss or workspace");
+    if (C < 0 || H < 0 || W < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_pixel_loss_grad: C, H, W >= 0");
+    if ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(grad)) & 15)
+        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_pixel_loss_grad: img, gt and grad must be 16-byte aligned");
+    return launch_pixel_loss_grad(*cfg, C, H, W, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
+}
+
+size_t fr_scale_term_workspace_bytes(void) { return scale_term_workspace_bytes(); }
+
+int fr_scale_term(const fr_scale_term_config* cfg, int32_t P, const float* scaling, float* d_scaling, float* loss, void* workspace,
+                  void* stream)
+{
+    if (!cfg || P < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_scale_term: null configuration or negative P");
+    // (the selected rows are counted in floats: exact below 2^24)
+    if (P >= (1 << 24)) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_scale_term: P < 2^24");
+    if (P > 0 && !scaling) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_scale_term: null parameter array");
+    if (!workspace || !loss) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_scale_term: null workspace or loss");
+    return launch_scale_term(*cfg, P, scaling, d_scaling, loss, workspace, static_cast<hipStream_t>(stream));
+}
+
 void fr_ssim_window(float out[11])
 {
     if (out) ssim_window(out);

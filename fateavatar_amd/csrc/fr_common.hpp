@@ -519,6 +519,13 @@ int launch_l1_loss_grad_terms(int n_images, unsigned long long n, float rgb_weig
 size_t huber_workspace_bytes();
 int launch_huber_loss_grad(const fr_huber_config& cfg, int C, int H, int W, const float* img, const float* gt, const float* mask,
                            float* grad, float* loss, void* workspace, hipStream_t s);
+// SplattingAvatar's L1 + MSE image term and its gradient, and its scale term (fr_optim.hip)
+size_t pixel_loss_workspace_bytes();
+int launch_pixel_loss_grad(const fr_pixel_loss_config& cfg, int C, int H, int W, const float* img, const float* gt, float* grad,
+                           float* loss, void* workspace, hipStream_t s);
+size_t scale_term_workspace_bytes();
+int launch_scale_term(const fr_scale_term_config& cfg, int P, const float* scaling, float* d_scaling, float* loss, void* workspace,
+                      hipStream_t s);
 // L1 + D-SSIM image loss and its gradient (fr_ssim.hip)
 void ssim_window(float out[11]);
 size_t image_loss_workspace_bytes(int C, int H, int W);

@@ -353,6 +353,76 @@ int launch_huber_loss_grad(const fr_huber_config& cfg, int C, int H, int W, cons
     return FR_OK;
 }
 
+// ---------------------------------------------------------------- SplattingAvatar's L1 + MSE image term and its gradient, one launch
+// reference: SplattingAvatarLoss.accumulate_gradients (train/loss.py:288-323; get_rgb_loss / get_mse_loss :279-283) with
+// rgb_loss 1.0 and mse_loss 10.0 of config/splattingavatar.yaml:13-20, followed by loss.backward(): two mean reductions with
+// their elementwise kernels and autograd's twins.  Here the Huber kernel's scheme: float4 pieces plus a tail, TWO sums.  The
+// L1 sum has its own accumulator and takes its addends in k_l1_loss_grad's order, on k_l1_loss_grad's grid, through the same
+// tree: loss[1] is fr_l1_loss_grad's loss, bit for bit.
+struct PixelArgs {
+    const float* img;
+    const float* gt;
+    float* grad;         // or null
+    float* partial;      // [2][kL1MaxBlocks]
+    unsigned* counter;
+    float* loss;         // {rgb_weight x l1 + mse_weight x mse, l1, mse}
+    unsigned long long n;
+    float rgb_weight, mse_weight, inv_n;
+    float g_l1, g_mse;   // rgb_weight / n, 2 mse_weight / n
+};
+
+// one difference d: both sums, and the gradient word  rgb_weight sign(d) / n + mse_weight 2 d / n  (torch.sign: 0 at 0)
+__device__ __forceinline__ float pixel_one(const PixelArgs& a, float d, float& acc_l1, float& acc_mse)
+{
+    acc_l1 += fabsf(d);
+    acc_mse += d * d;
+    return (d > 0.f ? a.g_l1 : (d < 0.f ? -a.g_l1 : 0.f)) + a.g_mse * d;
+}
+
+__global__ void __launch_bounds__(kSumThreads) k_pixel_loss_grad(PixelArgs a)
+{
+    const float* __restrict__ img = a.img;
+    const float* __restrict__ gt = a.gt;
+    float* __restrict__ grad = a.grad;
+    const unsigned long long n = a.n, n4 = n / 4, stride = (unsigned long long)gridDim.x * blockDim.x;
+    float acc[2] = {0.f, 0.f};   // l1, mse
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const float4 x = reinterpret_cast<const float4*>(img)[i], y = reinterpret_cast<const float4*>(gt)[i];
+        const float d[4] = {x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w};
+        float g[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) g[k] = pixel_one(a, d[k], acc[0], acc[1]);
+        if (grad) reinterpret_cast<float4*>(grad)[i] = make_float4(g[0], g[1], g[2], g[3]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n - 4 * n4)) {   // tail of a length that is not a multiple of 4
+        const unsigned long long e = 4 * n4 + threadIdx.x;
+        const float g = pixel_one(a, img[e] - gt[e], acc[0], acc[1]);
+        if (grad) grad[e] = g;
+    }
+    if (!sum_over_workgroups(acc, a.partial, kL1MaxBlocks, a.counter, blockIdx.x, gridDim.x)) return;
+    const float l1 = acc[0] * a.inv_n, mse = acc[1] * a.inv_n;
+    a.loss[0] = a.rgb_weight * l1 + a.mse_weight * mse, a.loss[1] = l1, a.loss[2] = mse;
+}
+
+size_t pixel_loss_workspace_bytes() { return done_workspace_bytes(2 * kL1MaxBlocks); }
+
+int launch_pixel_loss_grad(const fr_pixel_loss_config& cfg, int C, int H, int W, const float* img, const float* gt, float* grad,
+                           float* loss, void* workspace, hipStream_t s)
+{
+    const unsigned long long n = (unsigned long long)H * (unsigned long long)W * (unsigned long long)C;
+    if (n == 0) return FR_OK;
+    const DoneWorkspace ws = done_workspace(workspace);
+    PixelArgs a;
+    a.img = img, a.gt = gt, a.grad = grad, a.loss = loss;
+    a.counter = ws.counter, a.partial = ws.partial;
+    a.n = n;
+    a.rgb_weight = cfg.rgb_weight, a.mse_weight = cfg.mse_weight, a.inv_n = (float)(1.0 / (double)n);
+    a.g_l1 = (float)((double)cfg.rgb_weight / (double)n), a.g_mse = (float)(2.0 * (double)cfg.mse_weight / (double)n);
+    hipLaunchKernelGGL(k_pixel_loss_grad, dim3(l1_blocks(n)), dim3(kSumThreads), 0, s, a);
+    FR_HIP(hipGetLastError());
+    return FR_OK;
+}
+
 // ---------------------------------------------------------------- several small device-to-device copies, one launch
 // The per-frame inputs of a captured step (camera block, posed vertices, target image) are copied into the buffers the
 // graph was captured with: as separate copies each is a launch-bound 5 us dispatch.
@@ -520,6 +590,98 @@ int launch_gaussian_regularise(const fr_regularise_config& cfg, int P, const flo
     a.thr_scale = cfg.threshold_scale, a.thr_xyz = cfg.threshold_xyz;
     hipLaunchKernelGGL(k_gaussian_regularise, dim3(blocks), dim3(256), 0, s, a);
     FR_HIP(hipGetLastError());
+    return FR_OK;
+}
+
+// ---------------------------------------------------------------- SplattingAvatar's scale term, two launches
+// reference: SplattingAvatarLoss.get_scale_loss (train/loss.py:307-315) on get_scaling = exp(_scaling)
+// (model/baseline/splattingavatar.py:270):
+//     smax, smin = scale.max(-1), scale.min(-1)
+//     sel        = (smax > max_scaling) & (smax / smin > scale_threshold)
+//     scale_loss = smax[sel].mean() if sel.any() else 0
+// The mean's denominator is the number of SELECTED rows, known only once every row has been seen: the first launch reduces
+// the sum and the count (k_gaussian_regularise's tail) and stores {scale_loss, count}; the second recomputes every row's
+// selection with the same function (scale_row) and ADDS  weight x smax / count  (d smax / d _scaling[argmax] = smax) to the
+// row's largest component, by the lane that owns the row.  The count travels as a float: every addend is 0 or 1 and every
+// partial result an integer <= P < 2^24 (the entry point refuses more), so it is exact.  No float atomics; with nothing
+// selected the second launch returns at once and no 0 / 0 is evaluated.
+struct ScaleRow {
+    float smax;      // the row's largest activated scale ...
+    int arg;         // ... and its component: the FIRST of equal ones (torch.max's gradient goes to one index)
+    bool selected;
+};
+
+// THE selection of both launches.  Every comparison with a NaN is false and torch.max / torch.min propagate a NaN: a row
+// that holds one is not selected (arg and smax are then not used).
+__device__ __forceinline__ ScaleRow scale_row(const float* __restrict__ scaling, unsigned i, float max_scaling, float scale_threshold)
+{
+    const size_t o = (size_t)i * 3;
+    const float e0 = act_exp(scaling[o]), e1 = act_exp(scaling[o + 1]), e2 = act_exp(scaling[o + 2]);
+    ScaleRow r;
+    r.smax = e0, r.arg = 0;
+    if (e1 > r.smax) r.smax = e1, r.arg = 1;
+    if (e2 > r.smax) r.smax = e2, r.arg = 2;
+    const float smin = fminf(e0, fminf(e1, e2));
+    const bool numbers = e0 == e0 && e1 == e1 && e2 == e2;
+    r.selected = numbers && r.smax > max_scaling && r.smax / smin > scale_threshold;
+    return r;
+}
+
+struct ScaleTermArgs {
+    const float* scaling;
+    float* d_scaling;     // the second launch's; never null there
+    float* partial;       // [2][kRegMaxBlocks]
+    unsigned* counter;
+    float* loss;          // {scale_loss, selected rows}
+    int P;
+    float weight, scale_threshold, max_scaling;
+};
+
+__global__ void __launch_bounds__(kSumThreads) k_scale_term_sum(ScaleTermArgs a)
+{
+    const unsigned stride = gridDim.x * blockDim.x;
+    float acc[2] = {0.f, 0.f};   // sum of smax over the selected rows, their number
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)a.P; i += stride) {
+        const ScaleRow r = scale_row(a.scaling, i, a.max_scaling, a.scale_threshold);
+        if (r.selected) acc[0] += r.smax, acc[1] += 1.f;
+    }
+    if (!sum_over_workgroups(acc, a.partial, kRegMaxBlocks, a.counter, blockIdx.x, gridDim.x)) return;
+    a.loss[0] = acc[1] > 0.f ? acc[0] / acc[1] : 0.f;
+    a.loss[1] = acc[1];
+}
+
+__global__ void __launch_bounds__(kSumThreads) k_scale_term_grad(ScaleTermArgs a)
+{
+    float* __restrict__ d_scaling = a.d_scaling;
+    const float count = a.loss[1];      // (the launch in front of this one stored it)
+    if (!(count > 0.f)) return;
+    const float g = a.weight / count;
+    const unsigned stride = gridDim.x * blockDim.x;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)a.P; i += stride) {
+        const ScaleRow r = scale_row(a.scaling, i, a.max_scaling, a.scale_threshold);
+        if (r.selected) d_scaling[(size_t)i * 3 + r.arg] += g * r.smax;
+    }
+}
+
+size_t scale_term_workspace_bytes() { return done_workspace_bytes(2 * kRegMaxBlocks); }
+
+int launch_scale_term(const fr_scale_term_config& cfg, int P, const float* scaling, float* d_scaling, float* loss, void* workspace,
+                      hipStream_t s)
+{
+    if (P <= 0) return FR_OK;
+    const unsigned blocks = capped_blocks((unsigned)P, kSumThreads, kRegMaxBlocks);
+    const DoneWorkspace ws = done_workspace(workspace);
+    ScaleTermArgs a;
+    a.scaling = scaling, a.d_scaling = d_scaling;
+    a.counter = ws.counter, a.partial = ws.partial;
+    a.loss = loss, a.P = P;
+    a.weight = cfg.weight, a.scale_threshold = cfg.scale_threshold, a.max_scaling = cfg.max_scaling;
+    hipLaunchKernelGGL(k_scale_term_sum, dim3(blocks), dim3(kSumThreads), 0, s, a);
+    FR_HIP(hipGetLastError());
+    if (d_scaling && cfg.weight != 0.f) {   // (a zero weight, a null array: no gradient traffic)
+        hipLaunchKernelGGL(k_scale_term_grad, dim3(blocks), dim3(kSumThreads), 0, s, a);
+        FR_HIP(hipGetLastError());
+    }
     return FR_OK;
 }
 

@@ -7,7 +7,9 @@ launch of the HIP library (`fr_l1_loss_grad`, include/fr_rasterizer.h); the call
 `render.backward(grad)`.  `image_loss_and_grad` is the same for the weighted L1 + D-SSIM objective of GaussianAvatars and
 3DGS (train/loss.py:351-365, tools/loss_utils/dssim.py:28-56) in two launches (`fr_image_loss_grad`), and `d_ssim` the
 reference's function as an autograd op on those kernels.  `huber_loss_and_grad` is FlashAvatar's Huber term with its optional
-mouth-mask term (train/loss.py:217-221, :231-239) in one launch (`fr_huber_loss_grad`).  There is no CPU path."""
+mouth-mask term (train/loss.py:217-221, :231-239) in one launch (`fr_huber_loss_grad`).  `pixel_loss_and_grad` is
+SplattingAvatar's L1 + MSE image term (train/loss.py:279-283, :288-304) in one launch (`fr_pixel_loss_grad`) and
+`scale_term_and_grad` its scale term (:307-315) in two (`fr_scale_term`).  There is no CPU path."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional, Tuple
@@ -20,6 +22,8 @@ from .workspace import StreamWorkspace
 # one workspace per op and (device, stream): workspace.py says why
 _l1_ws = StreamWorkspace("l1_workspace", lambda: _lib.lib().fr_l1_workspace_bytes(), "image's")
 _huber_ws = StreamWorkspace("huber_workspace", lambda: _lib.lib().fr_huber_workspace_bytes(), "image's")
+_pixel_ws = StreamWorkspace("pixel_loss_workspace", lambda: _lib.lib().fr_pixel_loss_workspace_bytes(), "image's")
+_scale_ws = StreamWorkspace("scale_term_workspace", lambda: _lib.lib().fr_scale_term_workspace_bytes(), "parameters'")
 _reg_ws = StreamWorkspace("regulariser_workspace", lambda: _lib.lib().fr_regularise_workspace_bytes(), "parameters'")
 _mesh_ws = StreamWorkspace("mesh_terms_workspace", lambda: _lib.lib().fr_mesh_terms_workspace_bytes(), "vertices'")
 
@@ -136,6 +140,100 @@ def huber_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, terms=REFERENCE_HUB
                 mask.data_ptr() if mask is not None else None, grad.data_ptr() if grad is not None else None, loss.data_ptr(),
                 ws.data_ptr())
     return loss, grad
+
+
+# ---- SplattingAvatar's image term (SplattingAvatarLoss, train/loss.py:279-283, :288-304): ONE launch (`fr_pixel_loss_grad`) gives the
+# three loss words and the gradient autograd would hand to the rasterizer
+class PixelLoss(NamedTuple):
+    """Weights of SplattingAvatar's image term: loss = rgb_weight * L1 + mse_weight * MSE (config/splattingavatar.yaml:13-20 has
+    1.0 and 10.0)."""
+    rgb_weight: float = 1.0
+    mse_weight: float = 10.0
+
+
+def pixel_loss_workspace(dev: torch.device) -> torch.Tensor:
+    """A fresh zeroed workspace for `pixel_loss_and_grad(..., workspace=)`."""
+    return _pixel_ws.fresh(dev)
+
+
+def pixel_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, weights=PixelLoss(), loss_out: Optional[torch.Tensor] = None,
+                        grad_out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """SplattingAvatar's image term of `img` against `gt` ([C,H,W] or [1,C,H,W]) in ONE launch: `weights` = (rgb_weight,
+    mse_weight), e.g. a `PixelLoss`; returns the 3-element device tensor (rgb_weight * l1 + mse_weight * mse, l1, mse) — the last
+    two unweighted means over all C H W values — and the gradient of its first word with respect to `img`, of `img`'s shape:
+    rgb_weight * sign(img - gt) / n + mse_weight * 2 (img - gt) / n.  The l1 word is `l1_loss_and_grad`'s loss, bit for bit.
+    `loss_out` / `grad_out`: write into these tensors instead of fresh ones (buffers of a captured step).  `workspace`: scratch
+    from `pixel_loss_workspace()`; by default one is kept per (device, current stream) — launches that may overlap must not
+    share one.  The losses without the gradient: `grad_out=False`.  There is no CPU path."""
+    if not (img.is_cuda and gt.is_cuda):
+        raise RuntimeError("pixel_loss_and_grad needs device tensors (there is no CPU path)")
+    if img.shape != gt.shape:
+        raise RuntimeError(f"pixel_loss_and_grad: shapes differ: {tuple(img.shape)} vs {tuple(gt.shape)}")
+    Cn, H, W = _chw(img, "pixel_loss_and_grad")
+    rgb_weight, mse_weight = float(weights[0]), float(weights[1])
+    img = img.detach()
+    if img.dtype != torch.float32 or not img.is_contiguous():
+        img = img.float().contiguous()
+    if gt.dtype != torch.float32 or not gt.is_contiguous():
+        gt = gt.float().contiguous()
+    dev = img.device
+    grad = None if grad_out is False else (grad_out if grad_out is not None else torch.empty_like(img))
+    loss = loss_out if loss_out is not None else torch.empty((3,), dtype=torch.float32, device=dev)
+    if (grad is not None and (grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != dev)) \
+            or loss.numel() != 3 or loss.dtype != torch.float32 or loss.device != dev or not loss.is_contiguous():
+        raise RuntimeError("pixel_loss_and_grad: bad output buffers (gradient of the image's shape, 3-element loss, float32, contiguous)")
+    ws = _pixel_ws.resolve(dev, workspace, "pixel_loss_and_grad")
+    import ctypes as C
+    cfg = _lib.fr_pixel_loss_config(rgb_weight, mse_weight)
+    _lib.launch("fr_pixel_loss_grad", dev, C.byref(cfg), Cn, H, W, img.data_ptr(), gt.data_ptr(),
+                grad.data_ptr() if grad is not None else None, loss.data_ptr(), ws.data_ptr())
+    return loss, grad
+
+
+# ---- SplattingAvatar's scale term (SplattingAvatarLoss, train/loss.py:307-315): two launches (`fr_scale_term`) give the unweighted
+# loss with the number of selected rows and add the weighted gradient into dL/d_scaling
+class ScaleTerm(NamedTuple):
+    """SplattingAvatar's scale term: its weight and the two gates of its row selection (config/splattingavatar.yaml:13-20 has
+    scale_loss 1.0, scale_threshold 10.0, max_scaling 0.008)."""
+    weight: float = 1.0
+    scale_threshold: float = 10.0
+    max_scaling: float = 0.008
+
+
+def scale_term_workspace(dev: torch.device) -> torch.Tensor:
+    """A fresh zeroed workspace for `scale_term_and_grad(..., workspace=)`."""
+    return _scale_ws.fresh(dev)
+
+
+def scale_term_and_grad(scaling: torch.Tensor, d_scaling: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
+                        terms=ScaleTerm(), workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SplattingAvatar's scale term (train/loss.py:307-315) on the raw `_scaling` [P,3] (`fr_scale_term`): with scale =
+    exp(scaling), a row is selected if its largest component is > terms.max_scaling and more than terms.scale_threshold times
+    its smallest; returns `out` = (mean of the largest component over the selected rows — 0 if there is none —, the number
+    of selected rows), UNWEIGHTED, a 2-element device tensor, and ADDS terms.weight * d scale_loss / d _scaling into `d_scaling`
+    ([P,3] gradient buffer: one entry per selected row, its largest component's; None, or a weight of 0: no gradient traffic).
+    A row with a NaN is not selected.  `workspace`: scratch from `scale_term_workspace()`; by default one is kept per (device,
+    current stream) — launches that may overlap must not share one.  There is no CPU path."""
+    if not scaling.is_cuda:
+        raise RuntimeError("scale_term_and_grad needs device tensors (there is no CPU path)")
+    dev = scaling.device
+    P = int(scaling.shape[0])
+    scaling = scaling.detach()
+    for t in (scaling, d_scaling):
+        if t is None:
+            continue
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (P, 3):
+            raise RuntimeError("scale_term_and_grad: contiguous float32 [P,3] tensors of one device")
+    loss = out if out is not None else torch.zeros((2,), dtype=torch.float32, device=dev)   # (P == 0 launches nothing)
+    if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
+        raise RuntimeError("scale_term_and_grad: `out` is a contiguous 2-element float32 tensor on the parameters' device")
+    ws = _scale_ws.resolve(dev, workspace, "scale_term_and_grad")
+    import ctypes as C
+    cfg = _lib.fr_scale_term_config(float(terms[0]), float(terms[1]), float(terms[2]))
+    _lib.launch("fr_scale_term", dev, C.byref(cfg), P, scaling.data_ptr() if P else None,
+                d_scaling.data_ptr() if d_scaling is not None and P else None, loss.data_ptr(), ws.data_ptr())
+    return loss
 
 
 def regulariser_workspace(dev: torch.device) -> torch.Tensor:

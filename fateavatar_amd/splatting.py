@@ -15,6 +15,12 @@ What is fused: the mesh pass is one launch, the per-Gaussian binding runs inside
 densification statistics run inside the rasterizer kernels, one L1 launch, one Adam launch over the flat buffer, the whole
 step — mesh pass included — ONE HIP graph.
 
+  * the objective — `SplattingAvatarLoss.accumulate_gradients` (train/loss.py:288-323) with config/splattingavatar.yaml:13-20:
+    1.0 x L1 + 10.0 x MSE + 1.0 x the scale term (+ 0.01 x LPIPS, not built).  `SplattingStep(image_loss=REFERENCE_IMAGE_LOSS)`:
+    one launch in the L1 launch's place (`loss.pixel_loss_and_grad`); `SplattingStep(scale_term=REFERENCE_SCALE_TERM)`: two more
+    launches inside the captured step (`loss.scale_term_and_grad`) that add the term's gradient in front of Adam.  Both are opt-in:
+    the default step optimises L1 alone
+
   * density control and the triangle walk — `_densify_and_prune`, `_clone_densify`, `_split_densify`, `_prune`,
     `_walking_on_triangles`, `_reset_opacity` (:386-715): `SplattingStep.densify_and_prune / prune / prune_low_opacity /
     walk_on_triangles / reset_opacity`, between step() calls.  The reference's schedule (config/splattingavatar.yaml:35-44,
@@ -26,7 +32,7 @@ step — mesh pass included — ONE HIP graph.
     as in the reference.
 
 NOT here:
-  * its MSE / scale / LPIPS loss terms (config/splattingavatar.yaml:13-20): the image term is L1 (`rgb_loss` 1.0)
+  * its LPIPS loss term (config/splattingavatar.yaml:13-20, weight 0.01): it needs pretrained VGG weights
   * camera gradients for this step (render through a model.PoseCamera), and FLAME itself: `SplattingStep(mesh_grad=True)` hands
     dLoss/dposed_verts back (`d_verts`), the mesh's own parameters and their optimizer stay the caller's torch
   * data-parallel runs of the step (`reduce_densification_stats`)
@@ -43,6 +49,7 @@ from .binding import PhongCanonical, PhongGradBuffers, bind_gaussians_phong, pho
 from .bound import PhongBinding, PosedPhongBinding, render_bound_batch
 from .flat import FlatParams
 from .gs_utils import RGB2SH, build_rotation
+from .loss import PixelLoss, ScaleTerm, scale_term_and_grad, scale_term_workspace
 from .model import TorchCamera
 from .phongsurf import PhongSurface, triwalk
 from .render import render
@@ -51,6 +58,9 @@ from .train import CloneSplitStep
 # config/splattingavatar.yaml:26-30 (group names of train/optim.py:106-117)
 SPLATTING_LRS = dict(uvd=0.00016, opacity=0.05, feature_dc=0.0025, feature_rest=0.0025 / 20, rotation=0.001, scaling=0.005)
 NUM_INIT_SAMPLES = 10_000   # config/splattingavatar.yaml:23
+# config/splattingavatar.yaml:13-20 (SplattingAvatarLoss.Params, train/loss.py:261-268)
+REFERENCE_IMAGE_LOSS = PixelLoss(rgb_weight=1.0, mse_weight=10.0)
+REFERENCE_SCALE_TERM = ScaleTerm(weight=1.0, scale_threshold=10.0, max_scaling=0.008)
 
 
 def sample_bary_on_triangles(num_faces: int, num_samples: int, generator: Optional[torch.Generator] = None):
@@ -143,7 +153,7 @@ class SplattingStep(CloneSplitStep):
 
     def __init__(self, pc: SplattingGaussians, canonical: PhongCanonical, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True, vertex_grad: bool = False,
-                 mesh_grad: bool = False):
+                 mesh_grad: bool = False, image_loss=None, scale_term: Optional[ScaleTerm] = None):
         """`canonical`: `binding.phong_canonical(cano_verts, faces)`; `verts` [V,3]: any pose of the mesh (sizes the step's
         static vertex buffer and is its first content).  `fold_binding` (default): the per-Gaussian binding is evaluated
         inside the rasterizer's per-Gaussian kernels (fr_aux::binding with FR_BIND_PHONG).  False: the stand-alone
@@ -154,13 +164,27 @@ class SplattingStep(CloneSplitStep):
         `posed_verts.backward(step.d_verts)` into whatever made the mesh.  One preallocated buffer (`PhongGradBuffers`, per
         mesh, not per Gaussian: density control leaves it alone); its zeroing, the per-Gaussian scatter and the mesh pass's
         backward are launches of the step, inside its captured graph.  Parameters and moments are what they are without it.
-        `vertex_grad=True` raises: that name stays the refusal it was; the gradient is asked for as `mesh_grad`."""
+        `vertex_grad=True` raises: that name stays the refusal it was; the gradient is asked for as `mesh_grad`.
+        `image_loss`: a `PixelLoss` (REFERENCE_IMAGE_LOSS holds the reference's 1.0 / 10.0) makes the image term
+        rgb_weight x L1 + mse_weight x MSE (train/loss.py:288-304) — one launch where the L1 launch is; `loss_terms` then holds
+        the step's (weighted image loss, l1, mse) and `loss` is its first word.  (An `ImageLoss` gives L1 + D-SSIM, as in every
+        step.)  None (default): the image term is L1 with weight 1, `loss_terms` is None.
+        `scale_term`: a `ScaleTerm` (REFERENCE_SCALE_TERM holds the reference's values) adds the scale term of
+        train/loss.py:307-315 to every step — two launches between the backward and Adam; `reg_loss` then holds the step's
+        unweighted scale_loss and the number of rows it selected.  None (default): no such launch, `reg_loss` is None."""
+        if scale_term is not None and not isinstance(scale_term, ScaleTerm):
+            raise TypeError(f"SplattingStep: `scale_term` is a ScaleTerm or None, not {type(scale_term).__name__}")
         self.mesh_grad = bool(mesh_grad)
         self.canonical = PhongCanonical(*[t.to(pc.flat.device).contiguous() for t in canonical])
         if pc.P and (int(pc.face_index.min()) < 0 or int(pc.face_index.max()) >= int(self.canonical.faces.shape[0])):
             raise ValueError("SplattingStep: `face_index` names a face the mesh does not have")
-        super().__init__(pc, self.canonical.faces, camera, bg, verts, lrs, use_graph, fold_binding, data_parallel=False,
+        super().__init__(pc, self.canonical.faces, camera, bg, verts, lrs, use_graph, fold_binding, image_loss, data_parallel=False,
                          vertex_grad=vertex_grad)
+        self.scale_term = None if scale_term is None else ScaleTerm(*[float(x) for x in scale_term])
+        # the reference's out['scale_loss'] of the step (unweighted) and the rows it averaged over, written by the term's launch;
+        # the scratch is the step's own and its size does not depend on P: density control leaves both alone
+        self.reg_loss = None if scale_term is None else torch.zeros(2, device=self.dev)
+        self._scale_ws = None if scale_term is None else scale_term_workspace(self.dev)
         if self.mesh_grad:
             self._mesh_buffers = PhongGradBuffers(self.verts.shape[0], self.faces.shape[0], self.dev, zeroed=True)
             self.d_verts = self._mesh_buffers.d_verts
@@ -192,6 +216,12 @@ class SplattingStep(CloneSplitStep):
         if self.mesh_grad and not self.fold_binding:     # (the ops' backward allocates its own: copied into the step's buffer)
             self.d_verts.copy_(verts.grad)
         pc.collect_grads()
+        if self.scale_term is not None:
+            # train/loss.py:307-315: weight x the scale term's gradient is ADDED to the image term's, in front of Adam.
+            # A replay that overflowed its binning capacity back-propagated zeros and its Adam launch skips the step (the
+            # overflow word): what this launch added to the zeroed gradient is then never applied — harmless.
+            scale_term_and_grad(pc._scaling, pc.grad_view("_scaling"), out=self.reg_loss, terms=self.scale_term,
+                                workspace=self._scale_ws)
         self.out = self._kept(out)
 
     # ---- SplattingAvatar's density control, triangle walk and opacity reset (:386-715): the density control is CloneSplitStep's
@@ -263,4 +293,4 @@ class SplattingStep(CloneSplitStep):
     RESUME_REMAPPED = False     # resumes FRESH
 
 
-__all__ = ["NUM_INIT_SAMPLES", "SPLATTING_LRS", "SplattingGaussians", "SplattingStep", "phong_canonical", "sample_bary_on_triangles"]
+__all__ = ["NUM_INIT_SAMPLES", "REFERENCE_IMAGE_LOSS", "REFERENCE_SCALE_TERM", "SPLATTING_LRS", "SplattingGaussians", "SplattingStep", "phong_canonical", "sample_bary_on_triangles"]

@@ -22,7 +22,8 @@ from typing import Optional
 import torch
 
 from . import dp
-from .loss import ImageLoss, image_loss_and_grad, image_loss_workspace, l1_loss_and_grad, l1_workspace, multi_copy
+from .loss import (ImageLoss, PixelLoss, image_loss_and_grad, image_loss_workspace, l1_loss_and_grad, l1_workspace, multi_copy,
+                   pixel_loss_and_grad, pixel_loss_workspace)
 from .model import FlatGaussians, TorchCamera
 from .optim import FusedAdam
 from .render import render
@@ -37,7 +38,9 @@ class TrainStep:
                  use_graph: bool = True, image_loss: Optional[ImageLoss] = None):
         """`image_loss`: an `ImageLoss(rgb_weight, dssim_weight)` makes the image term rgb_weight x L1 + dssim_weight x d_ssim
         (the original 3DGS objective is ImageLoss(0.8, 0.2)): two launches of `loss.image_loss_and_grad` where the L1 launch
-        is; `loss_terms` then holds the step's (weighted total, l1, d_ssim) and `loss` is its first word.  None (default):
+        is; `loss_terms` then holds the step's (weighted total, l1, d_ssim) and `loss` is its first word.  A
+        `PixelLoss(rgb_weight, mse_weight)` makes it rgb_weight x L1 + mse_weight x MSE (SplattingAvatar's image term): ONE launch
+        of `loss.pixel_loss_and_grad` where the L1 launch is; `loss_terms` then holds (weighted total, l1, mse).  None (default):
         the plain L1 step, `loss_terms` is None."""
         if not pc.fused_activations:
             raise ValueError("TrainStep drives the fused path: build FlatGaussians(..., fused_activations=True)")
@@ -104,13 +107,18 @@ class TrainStep:
             self.pc.fused_densification_stats = (self.xyz_gradient_accum, self.denom, self.pc.overflow_word)
 
     def _init_image_loss(self, image_loss):
-        """The step's L1 + D-SSIM buffers (after self.gt / self.loss exist): `loss` becomes a view of loss_terms[0]."""
-        self.image_loss = None if image_loss is None else ImageLoss(*[float(x) for x in image_loss])
+        """The buffers of the step's L1 + D-SSIM (an `ImageLoss`) or L1 + MSE (a `PixelLoss`) image term (after self.gt /
+        self.loss exist): `loss` becomes a view of loss_terms[0]."""
+        if image_loss is not None and not isinstance(image_loss, (ImageLoss, PixelLoss)):
+            raise TypeError(f"{type(self).__name__}: `image_loss` is an ImageLoss (L1 + D-SSIM), a PixelLoss (L1 + MSE) or None, "
+                            f"not {type(image_loss).__name__}")
+        self.image_loss = None if image_loss is None else type(image_loss)(*[float(x) for x in image_loss])
         self.loss_terms, self._image_ws = None, None
         if self.image_loss is not None:
             self.loss_terms = torch.zeros(3, device=self.dev)
             self.loss = self.loss_terms[0]
-            self._image_ws = image_loss_workspace(self.dev, *self.gt.shape)
+            self._image_ws = pixel_loss_workspace(self.dev) if isinstance(self.image_loss, PixelLoss) else \
+                image_loss_workspace(self.dev, *self.gt.shape)
 
     def _image_loss_and_grad(self, image: torch.Tensor) -> torch.Tensor:
         """dL/dimage of the step's image term, written into the step's buffers with the loss."""
@@ -118,6 +126,9 @@ class TrainStep:
             # nn.L1Loss(reduction='mean') (loss.py:92) + loss.backward(): the loss and the gradient autograd would hand to the
             # rasterizer in one launch, written straight into the step's buffers
             _, g = l1_loss_and_grad(image, self.gt, loss_out=self.loss, grad_out=self._dimage, workspace=self._l1_ws)
+        elif isinstance(self.image_loss, PixelLoss):
+            _, g = pixel_loss_and_grad(image, self.gt, self.image_loss, loss_out=self.loss_terms, grad_out=self._dimage,
+                                       workspace=self._image_ws)
         else:
             _, g = image_loss_and_grad(image, self.gt, self.image_loss, loss_out=self.loss_terms, grad_out=self._dimage,
                                        workspace=self._image_ws)

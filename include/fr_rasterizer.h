@@ -438,6 +438,47 @@ size_t fr_huber_workspace_bytes(void);
 int fr_huber_loss_grad(const fr_huber_config* cfg, int32_t C, int32_t H, int32_t W, const float* img, const float* gt,
                        const float* mask, float* grad, float* loss, void* workspace, void* hip_stream);
 
+/* ---- SplattingAvatar's L1 + MSE image term and its gradient with respect to the rendered image in ONE launch (reference:
+ * SplattingAvatarLoss.accumulate_gradients, train/loss.py:288-323, with get_rgb_loss / get_mse_loss :279-283 and rgb_loss 1.0,
+ * mse_loss 10.0 of config/splattingavatar.yaml:13-20).  With d = img - gt over the n = C H W floats of an image:
+ *   loss[1] = mean_n |d|,   loss[2] = mean_n d^2,   loss[0] = rgb_weight * loss[1] + mse_weight * loss[2]
+ *   grad    = rgb_weight * sign(d) / n + mse_weight * 2 d / n     (sign(0) = 0; `grad` may be NULL: losses only)
+ * One launch of float4 pieces plus a tail, two per-workgroup partial sums added up in index order by the workgroup that
+ * finishes last: no float atomics, the same bits on every run.  The L1 sum takes its addends in fr_l1_loss_grad's order:
+ * loss[1] is that entry's loss, bit for bit.  `workspace`: fr_pixel_loss_workspace_bytes() bytes of device memory, zeroed ONCE
+ * by the caller and left zeroed by the kernel; not to be shared by launches that can overlap on the device.  No allocation, no
+ * synchronisation: the call can be captured in a graph.  img, gt and grad must be 16-byte aligned.  n == 0 launches nothing and
+ * leaves `loss` as it is.  A NULL cfg / img / gt / loss / workspace is FR_ERR_INVALID_ARGUMENT.  `loss`: three device floats. */
+typedef struct fr_pixel_loss_config {
+    float rgb_weight, mse_weight;         /* reference: 1.0, 10.0 (config/splattingavatar.yaml:13-20) */
+} fr_pixel_loss_config;
+size_t fr_pixel_loss_workspace_bytes(void);
+int fr_pixel_loss_grad(const fr_pixel_loss_config* cfg, int32_t C, int32_t H, int32_t W, const float* img, const float* gt,
+                       float* grad, float* loss, void* workspace, void* hip_stream);
+
+/* ---- SplattingAvatar's scale term and its gradient in TWO launches (reference: SplattingAvatarLoss.get_scale_loss,
+ * train/loss.py:307-315, on get_scaling = exp(_scaling), model/baseline/splattingavatar.py:270).  `scaling`: P rows of 3 raw
+ * floats.  With scale = exp(scaling), smax / smin a row's largest / smallest component:
+ *   selected   = smax > max_scaling  and  smax / smin > scale_threshold
+ *   loss[0]    = mean of smax over the selected rows (0 if there is none),   loss[1] = their number (an exact integer)
+ * both UNWEIGHTED, and `weight * smax / loss[1]` is ADDED to d_scaling[row][argmax] of every selected row (read-modify-write
+ * by the lane that owns the row, no atomics; the first of equal components takes it).  The first launch reduces sum and
+ * count (per-workgroup partials summed in index order by the workgroup that finishes last: the same bits on every run) and
+ * stores `loss`; the second recomputes the selection with the same device function and reads the stored count.  A row with
+ * a NaN scale is not selected and its gradient row not touched; with no row selected `d_scaling` is not touched and no 0 / 0
+ * is evaluated.  `d_scaling` NULL or a weight of 0: the second launch is not made (no gradient traffic).  `workspace`:
+ * fr_scale_term_workspace_bytes() bytes of device memory, zeroed ONCE by the caller; the kernel leaves it zeroed; not to be
+ * shared by launches that can overlap on the device.  No allocation, no synchronisation: the call can be captured in a graph.
+ * P == 0 launches nothing and leaves `loss` as it is; P >= 2^24 is FR_ERR_INVALID_ARGUMENT (the count is summed in floats,
+ * exact below that).  `loss`: two device floats. */
+typedef struct fr_scale_term_config {
+    float weight;                         /* reference: 1.0 (scale_loss, config/splattingavatar.yaml:13-20) */
+    float scale_threshold, max_scaling;   /* reference: 10.0, 0.008 */
+} fr_scale_term_config;
+size_t fr_scale_term_workspace_bytes(void);
+int fr_scale_term(const fr_scale_term_config* cfg, int32_t P, const float* scaling, float* d_scaling, float* loss,
+                  void* workspace, void* hip_stream);
+
 /* ---- GaussianAvatars' two per-Gaussian regularisers and their gradients in ONE launch (reference:
  * GaussianAvatarsLoss.accumulate_gradients, train/loss.py:367-379, on the raw local parameters,
  * model/baseline/gaussianavatars.py:196-197):

@@ -31,7 +31,7 @@ are printed after each densify.
     python tools/train_synthetic.py --rigged --P 10006 --dssim [--regularisers]
 the reference's image term, 0.8 x L1 + 0.2 x d_ssim (--image-loss RGB DSSIM for other weights; also for the generic step).
 
-    python tools/train_synthetic.py --splatting [--P 10000 --binding-op | --torch-binding]
+    python tools/train_synthetic.py --splatting [--P 10000 --binding-op | --torch-binding] [--reference-loss]
     python tools/train_synthetic.py --splatting --densify-from 0.3 --densify-interval 0.1 --reset-interval 0.5 --walk-interval 0.1
 SplattingAvatar's step (fateavatar_amd/splatting.py): Gaussians on the Phong surface of the posed template, SH degree 0, one
 GPU.  --torch-binding binds with the stock-PyTorch restatement (tests/phong_ref.py) in front of render(): the A/B.
@@ -128,6 +128,9 @@ def main():
     ap.add_argument("--splatting", action="store_true",
                     help="SplattingAvatar's loop: --P Gaussians sampled on the template's Phong surface (default 10 000, the "
                          "reference's num_init_samples), SH degree 0; --binding-op as for --fateavatar")
+    ap.add_argument("--reference-loss", action="store_true",
+                    help="--splatting: the reference's objective without LPIPS, 1.0 x L1 + 10.0 x MSE + 1.0 x the scale term "
+                         "(SplattingStep(image_loss=REFERENCE_IMAGE_LOSS, scale_term=REFERENCE_SCALE_TERM)); default: L1 alone")
     ap.add_argument("--torch-binding", action="store_true",
                     help="--splatting: the mesh pass and the binding in stock PyTorch (tests/phong_ref.py) in front of render(); "
                          "--flash: the binding and the Huber term in stock PyTorch (tests/flash_ref.py)")
@@ -170,6 +173,8 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     a.image_loss = ImageLoss(*a.image_loss) if a.image_loss else (ImageLoss(0.8, 0.2) if a.dssim else None)
+    if a.reference_loss and (not a.splatting or a.torch_binding):
+        raise SystemExit("--reference-loss goes with --splatting (and its fused terms: not with --torch-binding)")
     if a.mono:
         if a.image_loss or a.train_mesh or a.mesh_terms or a.fateavatar or a.rigged or a.splatting or a.flash:
             raise SystemExit("--mono: the image term is L1 and there are no mesh terms; one model per run")
@@ -196,7 +201,7 @@ def main():
         return main_rigged(a, rank, world, dev)
     if a.splatting:
         if a.image_loss:
-            raise SystemExit("--splatting: the image term is L1 (DESIGN.md)")
+            raise SystemExit("--splatting: the image term is L1, or with --reference-loss the reference's L1 + MSE (DESIGN.md)")
         return main_splatting(a, rank, world, dev)
     truth = scenes.head_scene(P=a.P, res=a.res, sh_degree=a.sh_degree, seed=0, opacity=0.5)
     cams = [TorchCamera(scenes.head_scene(P=8, res=a.res, sh_degree=a.sh_degree, seed=0, view=v, n_views=a.views).camera, dev)
@@ -563,13 +568,15 @@ def main_rigged(a, rank, world, dev):
                       "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
 
 
-def splatting_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_binding=False, mesh_grad=False):
+def splatting_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_binding=False, mesh_grad=False,
+                    reference_loss=False):
     """SplattingAvatar's optimisation step on the synthetic INSTA-layout sequence (frame 0 is the canonical mesh): P Gaussians
     sampled on the template as the reference samples them, the step object, cameras, posed meshes and targets rendered from a
-    hidden ground-truth set of the same embedding."""
+    hidden ground-truth set of the same embedding.  `reference_loss`: the step optimises the reference's L1 + MSE + scale term."""
     from fateavatar_amd import insta
     from fateavatar_amd.binding import bind_gaussians_phong, phong_canonical, phong_frame
-    from fateavatar_amd.splatting import SplattingGaussians, SplattingStep, _SplattingFrame
+    from fateavatar_amd.splatting import (REFERENCE_IMAGE_LOSS, REFERENCE_SCALE_TERM, SplattingGaussians, SplattingStep,
+                                          _SplattingFrame)
     n_frames = max(views, 8)
     transform, posed, faces = insta.synthetic_sequence(n_frames, res, seed=0)
     cams = [TorchCamera(c, dev) for c in insta.camera_arrays(transform)]
@@ -613,7 +620,8 @@ def splatting_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, tor
                 self.out = {"render": out["render"].detach(), "radii": out["radii"], "visibility_filter": out["visibility_filter"]}
         cls = TorchBoundStep
     st = cls(pc, canonical, TorchCamera(insta.camera_arrays(transform)[0], dev), bg, posed_t[0], use_graph=use_graph,
-             fold_binding=fold_binding, mesh_grad=mesh_grad)
+             fold_binding=fold_binding, mesh_grad=mesh_grad, image_loss=REFERENCE_IMAGE_LOSS if reference_loss else None,
+             scale_term=REFERENCE_SCALE_TERM if reference_loss else None)
     return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames)
 
 
@@ -628,7 +636,7 @@ def main_track_mesh(a, rank, world, dev):
     # synchronisation, so the stock-PyTorch A/B cannot be captured and runs eagerly; compare it with --track-mesh --no-graph)
     use_graph = not a.no_graph and not a.torch_binding
     su = splatting_setup(P, a.res, dev, views=a.views, use_graph=use_graph, fold_binding=not a.binding_op,
-                         torch_binding=a.torch_binding, mesh_grad=True)
+                         torch_binding=a.torch_binding, mesh_grad=True, reference_loss=a.reference_loss)
     st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
     g = torch.Generator().manual_seed(9)
     # per frame (axis-angle [rad], translation [m]) about the mesh's centroid; the truth is zero
@@ -690,7 +698,7 @@ def main_splatting(a, rank, world, dev):
         return main_track_mesh(a, rank, world, dev)
     P = a.P if "--P" in sys.argv else 10_000
     su = splatting_setup(P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
-                         torch_binding=a.torch_binding)
+                         torch_binding=a.torch_binding, reference_loss=a.reference_loss)
     st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
     # the compressed maintenance schedule, in steps of the timed loop (config/splattingavatar.yaml:35-44,
     # train/iteration.py:271-298: densify every 100 steps from 600, reset opacity every 3 500, walk every 100)
@@ -724,8 +732,15 @@ def main_splatting(a, rank, world, dev):
     l = [float(x) for x in losses]
     how = "stock PyTorch in front of render()" if a.torch_binding else "stand-alone kernels" if a.binding_op else \
         "mesh pass + inside the per-Gaussian kernels (fr_aux::binding, Phong surface)"
+    terms = {}
+    if a.reference_loss:     # the last step's words: (weighted image loss, l1, mse) and (scale_loss, rows it averaged over)
+        lt, rl = [float(x) for x in st.loss_terms], [float(x) for x in st.reg_loss]
+        terms = {"l1": round(lt[1], 6), "mse": round(lt[2], 6), "scale_loss": round(rl[0], 6), "scale_selected": int(rl[1])}
+        print(f"last step: l1 {lt[1]:.6f}, mse {lt[2]:.6f}, scale_loss {rl[0]:.6f} over {int(rl[1])} selected rows", file=sys.stderr)
+    objective = "L1 + MSE + scale term" if a.reference_loss else "L1"
     print(json.dumps({"host_enqueue_ms_per_step": round(t_host / a.steps * 1e3, 4),
-                      "metric": "SplattingAvatar optimisation steps/s (mesh pass + bind + render + L1 + backward + stats + Adam)",
+                      "metric": f"SplattingAvatar optimisation steps/s (mesh pass + bind + render + {objective} + backward + stats + Adam)",
+                      "reference_loss": bool(a.reference_loss), **terms,
                       "binding": how, "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": st.pc.P,
                       "res": a.res, "frames": n_frames, "graph": not a.no_graph, "overflows": st.overflows,
                       "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
