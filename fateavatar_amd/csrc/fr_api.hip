@@ -390,7 +390,7 @@ const void* fr_debug_geometry_field(const void* geometry, int32_t P, int32_t fie
         case 6: return g.clamped;
         case 7: return nullptr;   // (the gradient accumulators moved into the handle)
         case 8: return g.rec_tmpl;   // [P][12]: x, y, a', b', c', opacity, r, g, b, id bits, depth, 0
-        case 9: return g.dcolor_ddir;   // [P][9]
+        case 9: return g.dcolor_ddir;   // [9][P], planar
         case 10: return g.opacity_act;
         default: return nullptr;
     }

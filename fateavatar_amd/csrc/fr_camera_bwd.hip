@@ -87,7 +87,7 @@ __device__ __forceinline__ void camera_bwd_fetch(const CamBwdArgs& a, const size
     for (int k = 0; k < 9; k++) in.dd[k] = 0.f;
     if (a.dcolor_ddir) {
         in.cl = a.clamped[i];
-        for (int k = 0; k < 9; k++) in.dd[k] = a.dcolor_ddir[i * 9 + k];
+        for (int k = 0; k < 9; k++) in.dd[k] = a.dcolor_ddir[ddir_index(k, i, (size_t)a.P)];   // (planar [9][P])
     }
 }
 

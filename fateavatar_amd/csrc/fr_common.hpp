@@ -66,6 +66,12 @@ __host__ __device__ static inline T* carve(char*& p, size_t count)
     return r;
 }
 
+// Where component k of Gaussian i of GeomView::dcolor_ddir sits.  (FR_DDIR_PLANAR 0: the [P][9] rows it had, for an A/B.)
+#ifndef FR_DDIR_PLANAR
+#define FR_DDIR_PLANAR 1
+#endif
+__host__ __device__ static inline size_t ddir_index(int k, size_t i, size_t P) { return FR_DDIR_PLANAR ? (size_t)k * P + i : i * 9 + (size_t)k; }
+
 // Per-Gaussian state written by the forward preprocess and read by every later stage.
 struct GeomView {
     float4* rec_tmpl;       // [P*3] the 48-byte splat RECORD the blend kernels gather for every (tile, Gaussian) instance:
@@ -75,9 +81,10 @@ struct GeomView {
     float* opacity_act;     // [P] the activated opacity (the backward's API does not take the opacities; the conic is NOT stored:
                             // k_preprocess_bwd computes the 2D covariance again anyway, by the forward's function: fr_project_math.hpp)
     uint8_t* clamped;       // [P] bit c set if SH colour channel c was clamped at 0
-    float* dcolor_ddir;     // [P*9] d(SH colour)/d(view direction): (dR,dG,dB)/dx, /dy, /dz — computed by the forward, which has
-                            // the 48 coefficients in LDS anyway, so that the backward reads 36 bytes per Gaussian instead
-                            // of its 192-byte SH row (the largest array of the frame) a second time
+    float* dcolor_ddir;     // [9][P], PLANAR (component k of Gaussian i at k * P + i): d(SH colour)/d(view direction): (dR,dG,dB)/dx,
+                            // /dy, /dz — computed by the forward, which has the 48 coefficients in LDS anyway, so that the backward
+                            // reads 36 bytes per Gaussian instead of its 192-byte SH row (the largest array of the frame) a second
+                            // time.  Planar so that every one of a wave's nine stores and loads is one contiguous 256-byte run
     float* accum;           // [P*kAccumStride] gradient accumulators of the blend backward.  NOT part of the geometry
                             // buffer: they belong to the handle (fr_handle_impl::accum), are all zero between
                             // backward passes (k_preprocess_bwd zeroes each row after reading it) and so cost the

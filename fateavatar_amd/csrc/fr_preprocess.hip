@@ -203,6 +203,10 @@ __device__ __forceinline__ void dma16_to_lds(const void* g, uint32_t lds_byte_ad
 #ifndef FR_PRE_ROWS_IN_REGS
 #define FR_PRE_ROWS_IN_REGS 1
 #endif
+// FR_PRE_STAGE_RECS: a wave's blend records leave through its LDS region as whole lines (0: every thread stores its own, for an A/B)
+#ifndef FR_PRE_STAGE_RECS
+#define FR_PRE_STAGE_RECS 1
+#endif
 __host__ __device__ constexpr int pre_wave_lds_bytes(int M3)
 {
     // the SH block (it has to be there BEFORE the counting atomics are issued and is read while they are in flight: loads
@@ -565,6 +569,14 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
     };
     const bool counting = total > 0u && !FR_PRE_ABLATE(1);
     if (counting) count_issue(0u);
+    // The wave's blend records (GeomView::rec_tmpl) are 64 x 48 = 3 072 contiguous bytes: staged in the wave's LDS region and
+    // stored as whole lines behind the colour stage.  With the rows in registers (M = 16) the bytes behind the counting
+    // tables are free; otherwise the SH block in front of the tables is dead once the colours have been evaluated.  Where
+    // neither has the room (M < 4: SH degree 0, precomputed colours without SH) every thread stores its own record.
+    constexpr int kRecStageBytes = 64 * 48;
+    static_assert(!FR_PRE_ROWS_IN_REGS || 256 * 48 - kCountLdsBytes >= kRecStageBytes, "no room for the records behind the counting tables");
+    const bool stage_recs = FR_PRE_STAGE_RECS && (rows_in_regs || 256 * M3 >= kRecStageBytes);   // (wave-uniform)
+    float4* const rec_stage = reinterpret_cast<float4*>(reinterpret_cast<char*>(wave_lds) + (rows_in_regs ? kCountLdsBytes : 0));
 
     // ---- colour (forward.cu:20-71), with the atomics above in flight
     bool dead_colour = false;
@@ -618,9 +630,11 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
                 radius_out = mr_out;
                 if (!FWD_ONLY) {
                     if (from_sh) {
-                        float* o = a.g.dcolor_ddir + (size_t)idx * 9;
+                        // planar, [9][P]: the wave's store of component k is one contiguous 256-byte run (as [P][9] rows it
+                        // touched 36 64-byte lines and filled none)
+                        float* o = a.g.dcolor_ddir;
                         if (!FR_PRE_ABLATE(6))
-                            for (int k = 0; k < 9; k++) o[k] = dd[k];
+                            for (int k = 0; k < 9; k++) o[ddir_index(k, (size_t)idx, (size_t)a.P)] = dd[k];
                         else asm volatile("" ::"v"(dd[0]), "v"(dd[1]), "v"(dd[2]), "v"(dd[3]), "v"(dd[4]), "v"(dd[5]), "v"(dd[6]), "v"(dd[7]), "v"(dd[8]));
                     }
                     a.g.opacity_act[idx] = rec_op;
@@ -632,16 +646,41 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs& a)
                 // loops get the reference's power = a'dx^2 + c'dy^2 + b'dxdy (forward.cu:340) in three multiply-adds, and the
                 // blend backward the reference's conic itself.  A Gaussian whose colour is not finite leaves a record of
                 // opacity 0 and colour 0 behind its counted instances: no pixel passes its alpha test
-                float4* t = a.g.rec_tmpl + (size_t)idx * 3;
+                // Staged (rec_stage): the row goes into the wave's LDS block and leaves it below, with the rows of the wave's
+                // other Gaussians, in coalesced 16-byte stores; otherwise straight to memory (three 16-byte stores at a
+                // 48-byte stride across the wave: 3 x 48 part lines)
                 if (!FR_PRE_ABLATE(7)) {
-                    t[0] = make_float4(ctr.x, ctr.y, rec_ca * -0.5f, -rec_cb);
-                    t[1] = make_float4(rec_cc * -0.5f, dead_colour ? 0.f : rec_op, dead_colour ? 0.f : col[0], dead_colour ? 0.f : col[1]);
-                    t[2] = make_float4(dead_colour ? 0.f : col[2], __uint_as_float((uint32_t)idx), rec_z, 0.f);   // (.z: view-space depth, for diagnostics)
+                    const float4 t0 = make_float4(ctr.x, ctr.y, rec_ca * -0.5f, -rec_cb);
+                    const float4 t1 = make_float4(rec_cc * -0.5f, dead_colour ? 0.f : rec_op, dead_colour ? 0.f : col[0], dead_colour ? 0.f : col[1]);
+                    const float4 t2 = make_float4(dead_colour ? 0.f : col[2], __uint_as_float((uint32_t)idx), rec_z, 0.f);   // (.z: view-space depth, for diagnostics)
+                    if (stage_recs) {
+                        // (every lane of this branch has read its SH row: the block's space may be written)
+                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                        rec_stage[lane * 3] = t0, rec_stage[lane * 3 + 1] = t1, rec_stage[lane * 3 + 2] = t2;
+                    } else {
+                        float4* t = a.g.rec_tmpl + (size_t)idx * 3;
+                        t[0] = t0, t[1] = t1, t[2] = t2;
+                    }
                 } else asm volatile("" ::"v"(col[0]), "v"(col[1]), "v"(col[2]));
             }
         }
         a.radii[idx] = radius_out;
         if (a.visible) a.visible[idx] = radius_out > 0 ? 1 : 0;
+    }
+    if (stage_recs && !FR_PRE_ABLATE(7)) {
+        // the staged records leave as the wave's contiguous run: 16-byte piece j of the run belongs to Gaussian j / 3, lane
+        // l stores pieces l, l + 64, l + 128 — of the Gaussians that wrote a record only (culled ones and the lanes past P
+        // have none: their 48 bytes of the array stay what they were)
+        const unsigned long long wrote = __ballot(alive);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        float4* run = a.g.rec_tmpl + (size_t)wave_first * 3;
+#pragma unroll
+        for (int t = 0; t < 3; t++) {
+            const int j = lane + 64 * t;
+            const int owner_lane = (j * 171) >> 9;   // j / 3 for j < 192
+            if ((wrote >> owner_lane) & 1ull) run[j] = rec_stage[j];
+        }
     }
     PRE_TR(4);   // record stores (and the wave's reconvergence)
     const unsigned long long dead = __ballot(dead_colour);

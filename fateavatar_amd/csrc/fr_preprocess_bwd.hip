@@ -63,6 +63,11 @@ __device__ __forceinline__ void store3(float* p, size_t i, float a, float b, flo
 #define FR_PREBWD_STAGE_ROWS 32
 #endif
 constexpr int kPreBwdStageRows = FR_PREBWD_STAGE_ROWS;
+// FR_PREBWD_ZERO_RUN: a wave re-zeroes its accumulator rows as ONE contiguous run of whole lines (0: every visible Gaussian
+// its own row, for an A/B)
+#ifndef FR_PREBWD_ZERO_RUN
+#define FR_PREBWD_ZERO_RUN 1
+#endif
 static_assert(kPreBwdStageRows == 64 || kPreBwdStageRows == 32 || kPreBwdStageRows == 16, "FR_PREBWD_STAGE_ROWS: 64, 32 or 16");
 
 // Row stride (floats) of a wave's block of dL_dsh rows in LDS.  M3 a multiple of 4 (M = 4, 16): the rows are
@@ -207,7 +212,7 @@ __device__ __forceinline__ void preprocess_bwd_fetch(const PreBwdArgs& a, const 
     for (int k = 0; k < 9; k++) in.dd[k] = 0.f;
     if (shs) {
         in.cl = clamped[li];
-        for (int k = 0; k < 9; k++) in.dd[k] = dcolor_ddir[i * 9 + k];
+        for (int k = 0; k < 9; k++) in.dd[k] = dcolor_ddir[ddir_index(k, i, (size_t)a.P)];   // (planar [9][P]: a wave's load is one run)
     }
     in.ga = in.dn = 0.f;
     if (grad_accum) in.ga = grad_accum[i];
@@ -260,13 +265,14 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreBwdArgs& a, const Ca
     // stores in front of it)
     const float old_m3[3] = {in.old_m3[0], in.old_m3[1], in.old_m3[2]}, old_sc[3] = {in.old_sc[0], in.old_sc[1], in.old_sc[2]};
     const float old_q[4] = {in.old_q[0], in.old_q[1], in.old_q[2], in.old_q[3]}, old_op = in.old_op;
-    // the accumulator row, left zeroed for the next backward (the rows are zero between backward passes: no zeroing
-    // launch, and no zeroing writes in the forward).  These are the kernel's first stores: every input load is in front of them
+    // the accumulator row (the caller has left the wave's rows zeroed for the next backward)
     float acc[12];
     {
-        float4* row4 = reinterpret_cast<float4*>(a.g.accum + i * kAccumStride);
         const float4 r0 = in.r0, r1 = in.r1, r2 = in.r2;
-        row4[0] = row4[1] = row4[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!FR_PREBWD_ZERO_RUN) {   // (every visible Gaussian the used part of its own row)
+            float4* row4 = reinterpret_cast<float4*>(a.g.accum + i * kAccumStride);
+            row4[0] = row4[1] = row4[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         acc[0] = r0.x, acc[1] = r0.y, acc[2] = r0.z, acc[3] = r0.w, acc[4] = r1.x, acc[5] = r1.y, acc[6] = r1.z,
         acc[7] = r1.w, acc[8] = r2.x, acc[9] = r2.y, acc[10] = r2.z, acc[11] = r2.w;
     }
@@ -563,6 +569,21 @@ __device__ __forceinline__ void preprocess_bwd_body(const PreBwdArgs& a)
     // (... and the first arithmetic on a loaded value — ~clamped, denom + 1 — is hoisted to its load otherwise, with a wait
     // of its own in the middle of the requests)
     asm volatile("" : "+v"(in.cl), "+v"(in.ga), "+v"(in.dn), "+v"(in.opacity), "+v"(in.radius));
+    // The wave's accumulator rows, left zeroed for the next backward (the rows are zero between backward passes: no zeroing
+    // launch, and no zeroing writes in the forward): ONE contiguous run of `rows` 64-byte rows, four coalesced 16-byte stores
+    // per lane, whole lines.  (Each visible Gaussian zeroing the 48 used bytes of its own row asked for 3 x 64 part lines per
+    // wave.)  The rows of culled Gaussians and the tail of every row are zero already: writing zeros there changes nothing.
+    // These are the kernel's first stores, behind its one wait: the zero they store is made to depend on the camera's
+    // broadcast, whose wait covers every load in front of it — the rows are in registers by now.  The wave is converged.
+    if (FR_PREBWD_ZERO_RUN) {
+        float zero = 0.f;
+        asm volatile("" : "+v"(zero) : "s"(cam.campos[2]) : "memory");
+        float4* z4 = reinterpret_cast<float4*>(a.g.accum + (size_t)max(wave_first, 0) * kAccumStride);
+        const int pieces = rows * (kAccumStride / 4);   // (<= 0 for a wave past the end)
+#pragma unroll
+        for (int t = 0; t < kAccumStride / 4; t++)
+            if (lane + 64 * t < pieces) z4[lane + 64 * t] = make_float4(zero, zero, zero, zero);
+    }
     // (fr_aux::overflow_out: the step's optimizer kernel reads it — fr_adam_config::skip)
     if (a.overflow_out && blockIdx.x == 0 && threadIdx.x == 0) *a.overflow_out = in.overflow ? 1.0f : 0.0f;
     PreBwdRow mine;
