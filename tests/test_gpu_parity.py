@@ -38,7 +38,8 @@ def _scene_list():
 SCENES = _scene_list()
 
 
-def _check_forward(o, h, name):
+def _check_forward_state(o, h, name):
+    """The state half of `_check_forward`: num_rendered, radii and the per-Gaussian forward state, bit-equal to the oracle's."""
     assert h.num_rendered == o.num_rendered, name
     np.testing.assert_array_equal(h.radii.cpu().numpy(), o.radii)
     vis = o.radii > 0
@@ -54,6 +55,10 @@ def _check_forward(o, h, name):
                                   else o._inputs["colors_precomp"][vis])
     # (Sigma3D itself is no longer stored: both per-Gaussian kernels compute it with one function, and the conic above,
     # bit-equal to the oracle's, is a function of it; the backward's copy is covered by the gradient comparisons)
+
+
+def _check_forward(o, h, name):
+    _check_forward_state(o, h, name)
     col = h.color.cpu().numpy()
     fT = h.final_T.cpu().numpy()
     fc = util.frac_close(col, o.color, 1e-4, 1e-5)
