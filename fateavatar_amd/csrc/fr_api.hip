@@ -558,74 +558,86 @@ int fr_phong_fit(void* stream, const float* cano_verts, const float* cano_normal
                             work, status, delta_out, static_cast<hipStream_t>(stream));
 }
 
+// Checks that several entry points share: each caller names itself (`who`) in the message, "<who>: <what>"
+static int fail_in(const char* who, const char* what)
+{
+    snprintf(g_err, sizeof(g_err), "%s: %s", who, what);
+    return FR_ERR_INVALID_ARGUMENT;
+}
+static uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+
+// What the two Adam entry points ask, in the order they ask it.  `multi`: the gradients are a list with checks and messages of
+// its own; otherwise grads[0] is one of the arrays, checked with them.
+static int check_adam(const char* who, bool multi, const fr_adam_config* cfg, const float* param, const float* const* grads, int n_grads,
+                      const float* exp_avg, const float* exp_avg_sq, const float* state, uint64_t n)
+{
+    if (!cfg || cfg->n_segments < 1 || cfg->n_segments > FR_ADAM_MAX_SEGMENTS) return fail_in(who, "1..FR_ADAM_MAX_SEGMENTS segments");
+    if (multi && (!grads || n_grads < 1 || n_grads > FR_ADAM_MAX_GRADS)) return fail_in(who, "1..FR_ADAM_MAX_GRADS gradient buffers");
+    for (int k = 0; multi && k < n_grads; k++)
+        if (n > 0 && (!grads[k] || (addr(grads[k]) & 15))) return fail_in(who, "null or misaligned gradient buffer");
+    const float* const grad = multi ? param : grads[0];   // (multi: checked above, `param` stands in)
+    if (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq || !state)) return fail_in(who, "null array");
+    uint64_t prev = 0;
+    for (int i = 0; i < cfg->n_segments; i++) {
+        if (cfg->segment_end[i] < prev) return fail_in(who, "segment ends must ascend");
+        prev = cfg->segment_end[i];
+    }
+    if (prev != n) return fail_in(who, "the last segment must end at n");
+    if ((addr(param) | addr(grad) | addr(exp_avg) | addr(exp_avg_sq)) & 15) return fail_in(who, "arrays must be 16-byte aligned");
+    if (addr(state) & 7) return fail_in(who, "state must be 8-byte aligned");
+    return FR_OK;
+}
+
 int fr_adam_step(const fr_adam_config* cfg, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                  uint64_t n, float* state, void* stream)
 {
-    if (!cfg || cfg->n_segments < 1 || cfg->n_segments > FR_ADAM_MAX_SEGMENTS)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step: 1..FR_ADAM_MAX_SEGMENTS segments");
-    if (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq || !state))
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step: null array");
-    uint64_t prev = 0;
-    for (int i = 0; i < cfg->n_segments; i++) {
-        if (cfg->segment_end[i] < prev) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step: segment ends must ascend");
-        prev = cfg->segment_end[i];
-    }
-    if (prev != n) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step: the last segment must end at n");
-    if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-         reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step: arrays must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(state) & 7) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step: state must be 8-byte aligned");
     const float* one[1] = {grad};
-    return launch_adam(*cfg, param, one, 1, exp_avg, exp_avg_sq, n, state, static_cast<hipStream_t>(stream));
+    const int rc = check_adam("fr_adam_step", false, cfg, param, one, 1, exp_avg, exp_avg_sq, state, n);
+    return rc ? rc : launch_adam(*cfg, param, one, 1, exp_avg, exp_avg_sq, n, state, static_cast<hipStream_t>(stream));
 }
 
 int fr_adam_step_multi(const fr_adam_config* cfg, float* param, const float* const* grads, int32_t n_grads, float* exp_avg,
                        float* exp_avg_sq, uint64_t n, float* state, void* stream)
 {
-    if (!cfg || cfg->n_segments < 1 || cfg->n_segments > FR_ADAM_MAX_SEGMENTS)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: 1..FR_ADAM_MAX_SEGMENTS segments");
-    if (!grads || n_grads < 1 || n_grads > FR_ADAM_MAX_GRADS)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: 1..FR_ADAM_MAX_GRADS gradient buffers");
-    for (int k = 0; k < n_grads; k++)
-        if (n > 0 && (!grads[k] || (reinterpret_cast<uintptr_t>(grads[k]) & 15)))
-            return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: null or misaligned gradient buffer");
-    if (n > 0 && (!param || !exp_avg || !exp_avg_sq || !state)) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: null array");
-    uint64_t prev = 0;
-    for (int i = 0; i < cfg->n_segments; i++) {
-        if (cfg->segment_end[i] < prev) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: segment ends must ascend");
-        prev = cfg->segment_end[i];
+    const int rc = check_adam("fr_adam_step_multi", true, cfg, param, grads, n_grads, exp_avg, exp_avg_sq, state, n);
+    return rc ? rc : launch_adam(*cfg, param, grads, n_grads, exp_avg, exp_avg_sq, n, state, static_cast<hipStream_t>(stream));
+}
+
+// One image of a per-pixel term (fr_optim.hip's sweep): is it there, and can it be read as float4 (grad: or null)?  Two questions and
+// not one check: the entry points with a configuration ask about that in between.
+static bool image_null(const float* img, const float* gt, const float* loss, const void* workspace) { return !img || !gt || !loss || !workspace; }
+static bool image_misaligned(const float* img, const float* gt, const float* grad) { return ((addr(img) | addr(gt) | addr(grad)) & 15) != 0; }
+// The images of a batched image term, image by image: there (`need`: they are read), aligned (`walk4`: img, gt and grad are
+// read as float4; `ws16`: the workspace holds float4 maps), and no workspace met before.
+static int check_images(const char* who, int n_images, bool need, bool walk4, bool ws16, const float* const* img, const float* const* gt,
+                        float* const* grad, float* const* loss, void* const* workspace)
+{
+    if (!img || !gt || !loss || !workspace) return fail_in(who, "null argument array");
+    for (int k = 0; k < n_images; k++) {
+        if (need && image_null(img[k], gt[k], loss[k], workspace[k])) return fail_in(who, "null array");
+        if ((walk4 && image_misaligned(img[k], gt[k], grad ? grad[k] : nullptr)) || (ws16 && (addr(workspace[k]) & 15)))
+            return fail_in(who, "arrays must be 16-byte aligned");
+        for (int j = 0; j < k; j++)
+            if (workspace[j] == workspace[k]) return fail_in(who, "one workspace per image");
     }
-    if (prev != n) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: the last segment must end at n");
-    if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: arrays must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(state) & 7) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_adam_step_multi: state must be 8-byte aligned");
-    return launch_adam(*cfg, param, grads, n_grads, exp_avg, exp_avg_sq, n, state, static_cast<hipStream_t>(stream));
+    return FR_OK;
 }
 
 size_t fr_l1_workspace_bytes(void) { return l1_workspace_bytes(); }
 
 int fr_l1_loss_grad(uint64_t n, const float* img, const float* gt, float* grad, float* loss, void* workspace, void* stream)
 {
-    if (n > 0 && (!img || !gt || !loss || !workspace)) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_l1_loss_grad: null array");
-    if ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(grad)) & 15)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_l1_loss_grad: arrays must be 16-byte aligned");
+    if (n > 0 && image_null(img, gt, loss, workspace)) return fail_in("fr_l1_loss_grad", "null array");
+    if (image_misaligned(img, gt, grad)) return fail_in("fr_l1_loss_grad", "arrays must be 16-byte aligned");
     return launch_l1_loss_grad(n, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
 int fr_l1_loss_grad_batch(int32_t n_images, uint64_t n, const float* const* img, const float* const* gt, float* const* grad,
                           float* const* loss, void* const* workspace, void* stream)
 {
-    if (n_images < 1 || n_images > kMaxBatch) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_l1_loss_grad_batch: 1 .. FR_MAX_BATCH images");
-    if (!img || !gt || !loss || !workspace) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_l1_loss_grad_batch: null argument array");
-    for (int k = 0; k < n_images; k++) {
-        if (n > 0 && (!img[k] || !gt[k] || !loss[k] || !workspace[k]))
-            return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_l1_loss_grad_batch: null array");
-        if ((reinterpret_cast<uintptr_t>(img[k]) | reinterpret_cast<uintptr_t>(gt[k]) | (grad ? reinterpret_cast<uintptr_t>(grad[k]) : 0)) & 15)
-            return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_l1_loss_grad_batch: arrays must be 16-byte aligned");
-        for (int j = 0; j < k; j++)
-            if (workspace[j] == workspace[k]) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_l1_loss_grad_batch: one workspace per image");
-    }
-    return launch_l1_loss_grad_batch(n_images, n, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
+    if (n_images < 1 || n_images > kMaxBatch) return fail_in("fr_l1_loss_grad_batch", "1 .. FR_MAX_BATCH images");
+    const int rc = check_images("fr_l1_loss_grad_batch", n_images, n > 0, true, false, img, gt, grad, loss, workspace);
+    return rc ? rc : launch_l1_loss_grad_batch(n_images, n, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
 size_t fr_huber_workspace_bytes(void) { return huber_workspace_bytes(); }
@@ -633,13 +645,10 @@ size_t fr_huber_workspace_bytes(void) { return huber_workspace_bytes(); }
 int fr_huber_loss_grad(const fr_huber_config* cfg, int32_t C, int32_t H, int32_t W, const float* img, const float* gt,
                        const float* mask, float* grad, float* loss, void* workspace, void* stream)
 {
-    if (!cfg || !img || !gt || !loss || !workspace)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_huber_loss_grad: null configuration, img, gt, loss or workspace");
-    if (!(cfg->alpha > 0.f)) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_huber_loss_grad: alpha must be > 0");
-    if (C < 0 || H < 0 || W < 0 || (int64_t)H * W >= (1ll << 31))
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_huber_loss_grad: C, H, W >= 0, H x W < 2^31");
-    if ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(grad)) & 15)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_huber_loss_grad: img, gt and grad must be 16-byte aligned");
+    if (!cfg || image_null(img, gt, loss, workspace)) return fail_in("fr_huber_loss_grad", "null configuration, img, gt, loss or workspace");
+    if (!(cfg->alpha > 0.f)) return fail_in("fr_huber_loss_grad", "alpha must be > 0");
+    if (C < 0 || H < 0 || W < 0 || (int64_t)H * W >= (1ll << 31)) return fail_in("fr_huber_loss_grad", "C, H, W >= 0, H x W < 2^31");
+    if (image_misaligned(img, gt, grad)) return fail_in("fr_huber_loss_grad", "img, gt and grad must be 16-byte aligned");
     return launch_huber_loss_grad(*cfg, C, H, W, img, gt, mask, grad, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
@@ -648,11 +657,9 @@ size_t fr_pixel_loss_workspace_bytes(void) { return pixel_loss_workspace_bytes()
 int fr_pixel_loss_grad(const fr_pixel_loss_config* cfg, int32_t C, int32_t H, int32_t W, const float* img, const float* gt,
                        float* grad, float* loss, void* workspace, void* stream)
 {
-    if (!cfg || !img || !gt || !loss || !workspace)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_pixel_loss_grad: null configuration, img, gt, loss or workspace");
-    if (C < 0 || H < 0 || W < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_pixel_loss_grad: C, H, W >= 0");
-    if ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(grad)) & 15)
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_pixel_loss_grad: img, gt and grad must be 16-byte aligned");
+    if (!cfg || image_null(img, gt, loss, workspace)) return fail_in("fr_pixel_loss_grad", "null configuration, img, gt, loss or workspace");
+    if (C < 0 || H < 0 || W < 0) return fail_in("fr_pixel_loss_grad", "C, H, W >= 0");
+    if (image_misaligned(img, gt, grad)) return fail_in("fr_pixel_loss_grad", "img, gt and grad must be 16-byte aligned");
     return launch_pixel_loss_grad(*cfg, C, H, W, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
@@ -679,22 +686,13 @@ size_t fr_image_loss_workspace_bytes(int32_t C, int32_t H, int32_t W) { return i
 int fr_image_loss_grad(const fr_image_loss_config* cfg, int32_t n_images, int32_t C, int32_t H, int32_t W, const float* const* img,
                        const float* const* gt, float* const* grad, float* const* loss, void* const* workspace, void* stream)
 {
-    if (!cfg) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: null configuration");
-    if (n_images < 1 || n_images > kMaxBatch) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: 1 .. FR_MAX_BATCH images");
+    if (!cfg) return fail_in("fr_image_loss_grad", "null configuration");
+    if (n_images < 1 || n_images > kMaxBatch) return fail_in("fr_image_loss_grad", "1 .. FR_MAX_BATCH images");
     if (C < 1 || H < 1 || W < 1 || (int64_t)n_images * C > 65535 || H > (1 << 20) || W > (1 << 20))
-        return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: C, H, W >= 1, n_images x C <= 65535, H, W <= 2^20");
-    if (!img || !gt || !loss || !workspace) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: null argument array");
-    for (int k = 0; k < n_images; k++) {
-        if (!img[k] || !gt[k] || !loss[k] || !workspace[k]) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: null array");
-        uintptr_t align = reinterpret_cast<uintptr_t>(workspace[k]);
-        // (the D-SSIM-free path is k_l1_loss_grad's float4 walk)
-        if (cfg->dssim_weight == 0.f)
-            align |= reinterpret_cast<uintptr_t>(img[k]) | reinterpret_cast<uintptr_t>(gt[k]) | (grad ? reinterpret_cast<uintptr_t>(grad[k]) : 0);
-        if (align & 15) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: arrays must be 16-byte aligned");
-        for (int j = 0; j < k; j++)
-            if (workspace[j] == workspace[k]) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_image_loss_grad: one workspace per image");
-    }
-    return launch_image_loss_grad(*cfg, n_images, C, H, W, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
+        return fail_in("fr_image_loss_grad", "C, H, W >= 1, n_images x C <= 65535, H, W <= 2^20");
+    // (the D-SSIM-free path is k_l1_loss_grad's float4 walk)
+    const int rc = check_images("fr_image_loss_grad", n_images, true, cfg->dssim_weight == 0.f, true, img, gt, grad, loss, workspace);
+    return rc ? rc : launch_image_loss_grad(*cfg, n_images, C, H, W, img, gt, grad, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
 size_t fr_regularise_workspace_bytes(void) { return regularise_workspace_bytes(); }

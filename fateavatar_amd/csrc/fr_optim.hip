@@ -152,275 +152,212 @@ int launch_adam(const fr_adam_config& cfg, float* param, const float* const* gra
     return FR_OK;
 }
 
-// ---------------------------------------------------------------- L1 image loss and its gradient, one launch
-// reference: nn.L1Loss(reduction='mean') on the rendered image (model/loss.py:92) followed by loss.backward() — in
-// PyTorch eight launch-bound elementwise / reduction kernels (sub, abs, mean, fill, sign, mul, ...: 41 us of a 205 us
-// optimisation step at 512 x 512).  Here: grad = sign(img - gt) / n and per-workgroup partial sums of |img - gt| in one
-// pass; the workgroup that finishes last adds the partials up in index order (deterministic) and stores the loss
-// (sum_over_workgroups, fr_common.hpp: every fused loss kernel of the library ends with it).
+// ---------------------------------------------------------------- the per-pixel image terms and their gradients, one launch each
+// Four objectives on the differences d = img - gt.  The reference follows each with loss.backward(): in PyTorch eight (L1: sub,
+// abs, mean, fill, sign, mul, ...: 41 us of a 205 us optimisation step at 512 x 512) to about thirty (Huber) launch-bound
+// elementwise / reduction kernels with autograd's twins.  Here one pass gives the loss words and the gradient autograd would
+// hand to the rasterizer:
+//   L1Term       nn.L1Loss(reduction='mean') on the rendered image (model/loss.py:92): mean |d|, gradient sign(d) / n
+//   L1WordsTerm  the same with fr_image_loss_grad's outputs, its path for a D-SSIM weight of 0: gradient rgb_weight sign(d) / n
+//   HuberTerm    FlashAvatarLoss.get_huber_loss (train/loss.py:217-221) on the image and, with a mouth mask, once more on the
+//                masked image and target at weight 40 (:231-239)
+//   PixelTerm    SplattingAvatarLoss.accumulate_gradients (train/loss.py:288-304; get_rgb_loss / get_mse_loss :279-283) with
+//                rgb_loss 1.0 and mse_loss 10.0 of config/splattingavatar.yaml:13-20: L1 + MSE
+// image_term_sweep is the pass they share: float4 pieces on a grid capped at kL1MaxBlocks, a tail in workgroup 0, per-workgroup
+// partial sums, and the workgroup that finishes last adds the partials up in index order (deterministic) and hands the totals
+// to the term (sum_over_workgroups, fr_common.hpp: every fused loss kernel of the library ends with it).  A term says what one
+// difference adds to which of its kSums sums and which gradient word it gives (`one`), what the totals mean (`finish`), and
+// whether the partials are put back to zero (kZero: all but the plain L1, whose one row every launch overwrites).  The terms
+// whose first sum takes fabsf(d) run the plain L1 kernel's sweep on its grid with its first accumulator: the same addends in
+// the same order through the same tree, so loss[1] of L1WordsTerm and of PixelTerm is fr_l1_loss_grad's loss, bit for bit.
 constexpr unsigned kL1MaxBlocks = 1024;
 
-struct L1View {   // one image of a (possibly batched) launch
+struct LossView {   // one image of a (possibly batched) launch
     const float* img;
     const float* gt;
-    float* grad;
-    float* partial;
+    float* grad;         // or null
+    float* partial;      // [kSums][kL1MaxBlocks]
     unsigned* counter;
     float* loss;
 };
 
-// kTerms (fr_image_loss_grad with a D-SSIM weight of 0): the gradient's magnitude is `g` = rgb_weight / n instead of 1 / n,
-// `loss` takes {rgb_weight x l1, l1, 0} and the partials are put back to zero; the sums are those of the plain kernel, bit for bit.
-template <bool kTerms>
-__device__ __forceinline__ void l1_loss_grad_body(const L1View& v, unsigned long long n, float inv_n, float g_mag, float rgb_weight)
+template <typename Term>
+__device__ __forceinline__ void image_term_sweep(const LossView& v, unsigned long long n, const Term& t)
 {
     const float* __restrict__ img = v.img;
     const float* __restrict__ gt = v.gt;
     float* __restrict__ grad = v.grad;
-    float* __restrict__ loss = v.loss;
-    const unsigned long long n4 = n / 4, stride = (unsigned long long)gridDim.x * blockDim.x;
-    float acc[1] = {0.f};
-    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    // (kSumThreads is blockDim.x: the launcher's block size, and the one sum_over_workgroups asks for)
+    const unsigned long long n4 = n / 4, stride = (unsigned long long)gridDim.x * kSumThreads;
+    float acc[Term::kSums] = {};
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kSumThreads + threadIdx.x; i < n4; i += stride) {
         const float4 a = reinterpret_cast<const float4*>(img)[i], b = reinterpret_cast<const float4*>(gt)[i];
         const float d[4] = {a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w};
         float g[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            acc[0] += fabsf(d[k]);
-            g[k] = d[k] > 0.f ? g_mag : (d[k] < 0.f ? -g_mag : 0.f);   // torch.sign: 0 at 0
-        }
+        for (int k = 0; k < 4; k++) g[k] = t.one(4 * i + k, d[k], acc);
         if (grad) reinterpret_cast<float4*>(grad)[i] = make_float4(g[0], g[1], g[2], g[3]);
     }
     if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n - 4 * n4)) {   // tail of a length that is not a multiple of 4
         const unsigned long long e = 4 * n4 + threadIdx.x;
-        const float d = img[e] - gt[e];
-        acc[0] += fabsf(d);
-        if (grad) grad[e] = d > 0.f ? g_mag : (d < 0.f ? -g_mag : 0.f);
+        const float g = t.one(e, img[e] - gt[e], acc);
+        if (grad) grad[e] = g;
     }
-    if (!sum_over_workgroups<1, kTerms>(acc, v.partial, 0u, v.counter, blockIdx.x, gridDim.x)) return;
-    const float l1 = acc[0] * inv_n;
-    if (kTerms) loss[0] = rgb_weight * l1, loss[1] = l1, loss[2] = 0.f;
-    else *loss = l1;
+    if (!sum_over_workgroups<Term::kSums, Term::kZero>(acc, v.partial, kL1MaxBlocks, v.counter, blockIdx.x, gridDim.x)) return;
+    t.finish(acc, v.loss);
 }
 
-__global__ void __launch_bounds__(kSumThreads) k_l1_loss_grad(L1View v, unsigned long long n, float inv_n) { l1_loss_grad_body<false>(v, n, inv_n, inv_n, 1.f); }
-// the images of the frames of a batch (same size), one workspace each: grid (x, images)
-__global__ void __launch_bounds__(kSumThreads) k_l1_loss_grad_batch(BatchOf<L1View> b, unsigned long long n, float inv_n)
-{
-    l1_loss_grad_body<false>(b.v[blockIdx.y], n, inv_n, inv_n, 1.f);
-}
-// the L1 term alone behind fr_image_loss_grad (three loss words per image, weighted gradient)
-__global__ void __launch_bounds__(kSumThreads) k_l1_loss_grad_terms(BatchOf<L1View> b, unsigned long long n, float inv_n, float g_mag, float rgb_weight)
-{
-    l1_loss_grad_body<true>(b.v[blockIdx.y], n, inv_n, g_mag, rgb_weight);
-}
+__device__ __forceinline__ float sign_times(float d, float g) { return d > 0.f ? g : (d < 0.f ? -g : 0.f); }   // torch.sign: 0 at 0
+
+struct L1Term {
+    static constexpr int kSums = 1;
+    static constexpr bool kZero = false;
+    float inv_n;
+    __device__ __forceinline__ float one(unsigned long long, float d, float (&acc)[1]) const
+    {
+        acc[0] += fabsf(d);
+        return sign_times(d, inv_n);
+    }
+    __device__ __forceinline__ void finish(const float (&acc)[1], float* loss) const { *loss = acc[0] * inv_n; }
+};
+
+struct L1WordsTerm {   // loss = {rgb_weight x l1, l1, 0}
+    static constexpr int kSums = 1;
+    static constexpr bool kZero = true;
+    float inv_n, g_mag, rgb_weight;   // g_mag = rgb_weight / n
+    __device__ __forceinline__ float one(unsigned long long, float d, float (&acc)[1]) const
+    {
+        acc[0] += fabsf(d);
+        return sign_times(d, g_mag);
+    }
+    __device__ __forceinline__ void finish(const float (&acc)[1], float* loss) const
+    {
+        const float l1 = acc[0] * inv_n;
+        loss[0] = rgb_weight * l1, loss[1] = l1, loss[2] = 0.f;
+    }
+};
+
+//   h(x) = 0.5 x^2 if |x| < alpha else alpha (|x| - 0.5 alpha);  h'(x) = x if |x| < alpha else alpha sign(x)
+struct HuberTerm {   // sums: huber, mouth; loss = {huber + mask_weight x mouth, huber, mouth}
+    static constexpr int kSums = 2;
+    static constexpr bool kZero = true;
+    const float* mask;   // [HW] or null
+    unsigned hw;
+    float alpha, mask_weight, inv_n;
+    // h and h' of one difference x: the value is added to `acc`, the derivative returned
+    __device__ __forceinline__ float h(float x, float& acc) const
+    {
+        const float ax = fabsf(x);
+        if (ax < alpha) {
+            acc += 0.5f * x * x;
+            return x;
+        }
+        acc += alpha * (ax - 0.5f * alpha);
+        return x < 0.f ? -alpha : alpha;
+    }
+    __device__ __forceinline__ float one(unsigned long long e, float d, float (&acc)[2]) const
+    {
+        float g = h(d, acc[0]);
+        if (mask) {
+            const float m = mask[e % hw];   // [1,H,W] broadcast over the channels
+            g += mask_weight * m * h(m * d, acc[1]);
+        }
+        return g * inv_n;
+    }
+    __device__ __forceinline__ void finish(const float (&acc)[2], float* loss) const
+    {
+        const float huber = acc[0] * inv_n, mouth = acc[1] * inv_n;
+        loss[0] = huber + mask_weight * mouth, loss[1] = huber, loss[2] = mouth;
+    }
+};
+
+struct PixelTerm {   // sums: l1, mse; loss = {rgb_weight x l1 + mse_weight x mse, l1, mse}
+    static constexpr int kSums = 2;
+    static constexpr bool kZero = true;
+    float rgb_weight, mse_weight, inv_n;
+    float g_l1, g_mse;   // rgb_weight / n, 2 mse_weight / n
+    // the gradient word  rgb_weight sign(d) / n + mse_weight 2 d / n
+    __device__ __forceinline__ float one(unsigned long long, float d, float (&acc)[2]) const
+    {
+        acc[0] += fabsf(d);
+        acc[1] += d * d;
+        return sign_times(d, g_l1) + g_mse * d;
+    }
+    __device__ __forceinline__ void finish(const float (&acc)[2], float* loss) const
+    {
+        const float l1 = acc[0] * inv_n, mse = acc[1] * inv_n;
+        loss[0] = rgb_weight * l1 + mse_weight * mse, loss[1] = l1, loss[2] = mse;
+    }
+};
+
+// (the *_batch and *_terms kernels: the images of the frames of a batch, same size, one workspace each: grid (x, images))
+__global__ void __launch_bounds__(kSumThreads) k_l1_loss_grad(LossView v, unsigned long long n, L1Term t) { image_term_sweep(v, n, t); }
+__global__ void __launch_bounds__(kSumThreads) k_l1_loss_grad_batch(BatchOf<LossView> b, unsigned long long n, L1Term t) { image_term_sweep(b.v[blockIdx.y], n, t); }
+__global__ void __launch_bounds__(kSumThreads) k_l1_loss_grad_terms(BatchOf<LossView> b, unsigned long long n, L1WordsTerm t) { image_term_sweep(b.v[blockIdx.y], n, t); }
+__global__ void __launch_bounds__(kSumThreads) k_huber_loss_grad(LossView v, unsigned long long n, HuberTerm t) { image_term_sweep(v, n, t); }
+__global__ void __launch_bounds__(kSumThreads) k_pixel_loss_grad(LossView v, unsigned long long n, PixelTerm t) { image_term_sweep(v, n, t); }
 
 size_t l1_workspace_bytes() { return done_workspace_bytes(kL1MaxBlocks); }
+size_t huber_workspace_bytes() { return done_workspace_bytes(HuberTerm::kSums * kL1MaxBlocks); }
+size_t pixel_loss_workspace_bytes() { return done_workspace_bytes(PixelTerm::kSums * kL1MaxBlocks); }
 
-// a float4 per thread and sweep: what the L1 and Huber kernels take per workgroup
+// a float4 per thread and sweep: what the sweep takes per workgroup
 static unsigned l1_blocks(unsigned long long n) { return capped_blocks(n / 4, kSumThreads, kL1MaxBlocks); }
+static float over_n(double x, unsigned long long n) { return n ? (float)(x / (double)n) : 0.f; }   // (n == 0 launches nothing)
 
-static L1View l1_view(const float* img, const float* gt, float* grad, float* loss, void* workspace)
+// `kernel` takes one LossView (n_images = 1) or a BatchOf<> of them
+template <typename Views, typename Term>
+static int launch_image_term(void (*kernel)(Views, unsigned long long, Term), int n_images, unsigned long long n, const float* const* img,
+                             const float* const* gt, float* const* grad, float* const* loss, void* const* workspace, const Term& t,
+                             hipStream_t s)
 {
-    const DoneWorkspace ws = done_workspace(workspace);
-    return L1View{img, gt, grad, ws.partial, ws.counter, loss};
-}
-
-static BatchOf<L1View> l1_views(int n_images, const float* const* img, const float* const* gt, float* const* grad, float* const* loss,
-                                void* const* workspace)
-{
-    BatchOf<L1View> b;
+    if (n == 0 || n_images <= 0) return FR_OK;
+    BatchOf<LossView> b;
     for (int k = 0; k < kMaxBatch; k++) {
         const int j = k < n_images ? k : 0;   // (unused entries: never indexed, blockIdx.y < n_images)
-        b.v[k] = l1_view(img[j], gt[j], grad ? grad[j] : nullptr, loss[j], workspace[j]);
+        const DoneWorkspace ws = done_workspace(workspace[j]);
+        b.v[k] = LossView{img[j], gt[j], grad ? grad[j] : nullptr, ws.partial, ws.counter, loss[j]};
     }
-    return b;
+    const dim3 grid(l1_blocks(n), (unsigned)n_images);
+    if constexpr (std::is_same<Views, LossView>::value) hipLaunchKernelGGL(kernel, grid, dim3(kSumThreads), 0, s, b.v[0], n, t);
+    else hipLaunchKernelGGL(kernel, grid, dim3(kSumThreads), 0, s, b, n, t);
+    FR_HIP(hipGetLastError());
+    return FR_OK;
 }
 
 int launch_l1_loss_grad(unsigned long long n, const float* img, const float* gt, float* grad, float* loss, void* workspace,
                         hipStream_t s)
 {
-    if (n == 0) return FR_OK;
-    hipLaunchKernelGGL(k_l1_loss_grad, dim3(l1_blocks(n)), dim3(kSumThreads), 0, s, l1_view(img, gt, grad, loss, workspace), n,
-                       (float)(1.0 / (double)n));
-    FR_HIP(hipGetLastError());
-    return FR_OK;
+    return launch_image_term(k_l1_loss_grad, 1, n, &img, &gt, &grad, &loss, &workspace, L1Term{over_n(1.0, n)}, s);
 }
 
 int launch_l1_loss_grad_batch(int n_images, unsigned long long n, const float* const* img, const float* const* gt, float* const* grad,
                               float* const* loss, void* const* workspace, hipStream_t s)
 {
-    if (n == 0 || n_images <= 0) return FR_OK;
-    hipLaunchKernelGGL(k_l1_loss_grad_batch, dim3(l1_blocks(n), (unsigned)n_images), dim3(kSumThreads), 0, s,
-                       l1_views(n_images, img, gt, grad, loss, workspace), n, (float)(1.0 / (double)n));
-    FR_HIP(hipGetLastError());
-    return FR_OK;
+    return launch_image_term(k_l1_loss_grad_batch, n_images, n, img, gt, grad, loss, workspace, L1Term{over_n(1.0, n)}, s);
 }
 
 int launch_l1_loss_grad_terms(int n_images, unsigned long long n, float rgb_weight, const float* const* img, const float* const* gt,
                               float* const* grad, float* const* loss, void* const* workspace, hipStream_t s)
 {
-    if (n == 0 || n_images <= 0) return FR_OK;
-    hipLaunchKernelGGL(k_l1_loss_grad_terms, dim3(l1_blocks(n), (unsigned)n_images), dim3(kSumThreads), 0, s,
-                       l1_views(n_images, img, gt, grad, loss, workspace), n, (float)(1.0 / (double)n),
-                       (float)((double)rgb_weight / (double)n), rgb_weight);
-    FR_HIP(hipGetLastError());
-    return FR_OK;
+    const L1WordsTerm t{over_n(1.0, n), over_n(rgb_weight, n), rgb_weight};
+    return launch_image_term(k_l1_loss_grad_terms, n_images, n, img, gt, grad, loss, workspace, t, s);
 }
-
-// ---------------------------------------------------------------- Huber image term and its gradient, one launch
-// reference: FlashAvatarLoss.get_huber_loss (train/loss.py:217-221) on the image and, with a mouth mask, once more on the
-// masked image and target at weight 40 (:231-239), followed by loss.backward(): about thirty launch-bound elementwise /
-// reduction kernels with autograd's twins.  Here k_l1_loss_grad's scheme with TWO sums: float4 pieces plus a tail,
-// per-workgroup partials, the workgroup that finishes last adds them up in index order and puts the workspace back to zero.
-//   h(x) = 0.5 x^2 if |x| < alpha else alpha (|x| - 0.5 alpha);  h'(x) = x if |x| < alpha else alpha sign(x)
-struct HuberArgs {
-    const float* img;
-    const float* gt;
-    const float* mask;   // [HW] or null
-    float* grad;         // or null
-    float* partial;      // [2][kL1MaxBlocks]
-    unsigned* counter;
-    float* loss;         // {huber + mask_weight x mouth, huber, mouth}
-    unsigned long long n;
-    unsigned hw;
-    float alpha, mask_weight, inv_n;
-};
-
-// h and h' of one difference x: the value is added to `acc`, the derivative returned
-__device__ __forceinline__ float huber_term(float x, float alpha, float& acc)
-{
-    const float ax = fabsf(x);
-    if (ax < alpha) {
-        acc += 0.5f * x * x;
-        return x;
-    }
-    acc += alpha * (ax - 0.5f * alpha);
-    return x < 0.f ? -alpha : alpha;
-}
-
-// element e of the image: both terms' sums, and the gradient word
-__device__ __forceinline__ float huber_one(const HuberArgs& a, unsigned long long e, float d, float& acc_h, float& acc_m)
-{
-    float g = huber_term(d, a.alpha, acc_h);
-    if (a.mask) {
-        const float m = a.mask[e % a.hw];   // [1,H,W] broadcast over the channels
-        g += a.mask_weight * m * huber_term(m * d, a.alpha, acc_m);
-    }
-    return g * a.inv_n;
-}
-
-__global__ void __launch_bounds__(256) k_huber_loss_grad(HuberArgs a)
-{
-    const float* __restrict__ img = a.img;
-    const float* __restrict__ gt = a.gt;
-    float* __restrict__ grad = a.grad;
-    const unsigned long long n = a.n, n4 = n / 4, stride = (unsigned long long)gridDim.x * blockDim.x;
-    float acc[2] = {0.f, 0.f};   // huber, mouth
-    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const float4 x = reinterpret_cast<const float4*>(img)[i], y = reinterpret_cast<const float4*>(gt)[i];
-        const float d[4] = {x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w};
-        float g[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) g[k] = huber_one(a, 4 * i + k, d[k], acc[0], acc[1]);
-        if (grad) reinterpret_cast<float4*>(grad)[i] = make_float4(g[0], g[1], g[2], g[3]);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n - 4 * n4)) {   // tail of a length that is not a multiple of 4
-        const unsigned long long e = 4 * n4 + threadIdx.x;
-        const float g = huber_one(a, e, img[e] - gt[e], acc[0], acc[1]);
-        if (grad) grad[e] = g;
-    }
-    if (!sum_over_workgroups(acc, a.partial, kL1MaxBlocks, a.counter, blockIdx.x, gridDim.x)) return;
-    const float huber = acc[0] * a.inv_n, mouth = acc[1] * a.inv_n;
-    a.loss[0] = huber + a.mask_weight * mouth, a.loss[1] = huber, a.loss[2] = mouth;
-}
-
-size_t huber_workspace_bytes() { return done_workspace_bytes(2 * kL1MaxBlocks); }
 
 int launch_huber_loss_grad(const fr_huber_config& cfg, int C, int H, int W, const float* img, const float* gt, const float* mask,
                            float* grad, float* loss, void* workspace, hipStream_t s)
 {
     const unsigned long long hw = (unsigned long long)H * (unsigned long long)W, n = hw * (unsigned long long)C;
-    if (n == 0) return FR_OK;
-    const DoneWorkspace ws = done_workspace(workspace);
-    HuberArgs a;
-    a.img = img, a.gt = gt, a.mask = mask, a.grad = grad, a.loss = loss;
-    a.counter = ws.counter, a.partial = ws.partial;
-    a.n = n, a.hw = (unsigned)hw;
-    a.alpha = cfg.alpha, a.mask_weight = mask ? cfg.mask_weight : 0.f, a.inv_n = (float)(1.0 / (double)n);
-    hipLaunchKernelGGL(k_huber_loss_grad, dim3(l1_blocks(n)), dim3(kSumThreads), 0, s, a);
-    FR_HIP(hipGetLastError());
-    return FR_OK;
+    const HuberTerm t{mask, (unsigned)hw, cfg.alpha, mask ? cfg.mask_weight : 0.f, over_n(1.0, n)};
+    return launch_image_term(k_huber_loss_grad, 1, n, &img, &gt, &grad, &loss, &workspace, t, s);
 }
-
-// ---------------------------------------------------------------- SplattingAvatar's L1 + MSE image term and its gradient, one launch
-// reference: SplattingAvatarLoss.accumulate_gradients (train/loss.py:288-323; get_rgb_loss / get_mse_loss :279-283) with
-// rgb_loss 1.0 and mse_loss 10.0 of config/splattingavatar.yaml:13-20, followed by loss.backward(): two mean reductions with
-// their elementwise kernels and autograd's twins.  Here the Huber kernel's scheme: float4 pieces plus a tail, TWO sums.  The
-// L1 sum has its own accumulator and takes its addends in k_l1_loss_grad's order, on k_l1_loss_grad's grid, through the same
-// tree: loss[1] is fr_l1_loss_grad's loss, bit for bit.
-struct PixelArgs {
-    const float* img;
-    const float* gt;
-    float* grad;         // or null
-    float* partial;      // [2][kL1MaxBlocks]
-    unsigned* counter;
-    float* loss;         // {rgb_weight x l1 + mse_weight x mse, l1, mse}
-    unsigned long long n;
-    float rgb_weight, mse_weight, inv_n;
-    float g_l1, g_mse;   // rgb_weight / n, 2 mse_weight / n
-};
-
-// one difference d: both sums, and the gradient word  rgb_weight sign(d) / n + mse_weight 2 d / n  (torch.sign: 0 at 0)
-__device__ __forceinline__ float pixel_one(const PixelArgs& a, float d, float& acc_l1, float& acc_mse)
-{
-    acc_l1 += fabsf(d);
-    acc_mse += d * d;
-    return (d > 0.f ? a.g_l1 : (d < 0.f ? -a.g_l1 : 0.f)) + a.g_mse * d;
-}
-
-__global__ void __launch_bounds__(kSumThreads) k_pixel_loss_grad(PixelArgs a)
-{
-    const float* __restrict__ img = a.img;
-    const float* __restrict__ gt = a.gt;
-    float* __restrict__ grad = a.grad;
-    const unsigned long long n = a.n, n4 = n / 4, stride = (unsigned long long)gridDim.x * blockDim.x;
-    float acc[2] = {0.f, 0.f};   // l1, mse
-    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const float4 x = reinterpret_cast<const float4*>(img)[i], y = reinterpret_cast<const float4*>(gt)[i];
-        const float d[4] = {x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w};
-        float g[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) g[k] = pixel_one(a, d[k], acc[0], acc[1]);
-        if (grad) reinterpret_cast<float4*>(grad)[i] = make_float4(g[0], g[1], g[2], g[3]);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n - 4 * n4)) {   // tail of a length that is not a multiple of 4
-        const unsigned long long e = 4 * n4 + threadIdx.x;
-        const float g = pixel_one(a, img[e] - gt[e], acc[0], acc[1]);
-        if (grad) grad[e] = g;
-    }
-    if (!sum_over_workgroups(acc, a.partial, kL1MaxBlocks, a.counter, blockIdx.x, gridDim.x)) return;
-    const float l1 = acc[0] * a.inv_n, mse = acc[1] * a.inv_n;
-    a.loss[0] = a.rgb_weight * l1 + a.mse_weight * mse, a.loss[1] = l1, a.loss[2] = mse;
-}
-
-size_t pixel_loss_workspace_bytes() { return done_workspace_bytes(2 * kL1MaxBlocks); }
 
 int launch_pixel_loss_grad(const fr_pixel_loss_config& cfg, int C, int H, int W, const float* img, const float* gt, float* grad,
                            float* loss, void* workspace, hipStream_t s)
 {
     const unsigned long long n = (unsigned long long)H * (unsigned long long)W * (unsigned long long)C;
-    if (n == 0) return FR_OK;
-    const DoneWorkspace ws = done_workspace(workspace);
-    PixelArgs a;
-    a.img = img, a.gt = gt, a.grad = grad, a.loss = loss;
-    a.counter = ws.counter, a.partial = ws.partial;
-    a.n = n;
-    a.rgb_weight = cfg.rgb_weight, a.mse_weight = cfg.mse_weight, a.inv_n = (float)(1.0 / (double)n);
-    a.g_l1 = (float)((double)cfg.rgb_weight / (double)n), a.g_mse = (float)(2.0 * (double)cfg.mse_weight / (double)n);
-    hipLaunchKernelGGL(k_pixel_loss_grad, dim3(l1_blocks(n)), dim3(kSumThreads), 0, s, a);
-    FR_HIP(hipGetLastError());
-    return FR_OK;
+    const PixelTerm t{cfg.rgb_weight, cfg.mse_weight, over_n(1.0, n), over_n(cfg.rgb_weight, n), over_n(2.0 * cfg.mse_weight, n)};
+    return launch_image_term(k_pixel_loss_grad, 1, n, &img, &gt, &grad, &loss, &workspace, t, s);
 }
 
 // ---------------------------------------------------------------- several small device-to-device copies, one launch

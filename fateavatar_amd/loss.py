@@ -12,6 +12,7 @@ SplattingAvatar's L1 + MSE image term (train/loss.py:279-283, :288-304) in one l
 `scale_term_and_grad` its scale term (:307-315) in two (`fr_scale_term`).  There is no CPU path."""
 from __future__ import annotations
 
+import ctypes as C
 from typing import NamedTuple, Optional, Tuple
 
 import torch
@@ -28,6 +29,71 @@ _reg_ws = StreamWorkspace("regulariser_workspace", lambda: _lib.lib().fr_regular
 _mesh_ws = StreamWorkspace("mesh_terms_workspace", lambda: _lib.lib().fr_mesh_terms_workspace_bytes(), "vertices'")
 
 
+# ---- what the wrappers below ask of their arguments, said once; `who`: the wrapper's name, for the message
+def _f32c(t: torch.Tensor) -> torch.Tensor:
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+
+
+def _image_pair(img: torch.Tensor, gt: torch.Tensor, who: str):
+    """The image (detached) and its target as contiguous float32, and their device."""
+    if not (img.is_cuda and gt.is_cuda):
+        raise RuntimeError(f"{who} needs device tensors (there is no CPU path)")
+    if img.shape != gt.shape:
+        raise RuntimeError(f"{who}: shapes differ: {tuple(img.shape)} vs {tuple(gt.shape)}")
+    return _f32c(img.detach()), _f32c(gt), img.device
+
+
+def _outputs(img: torch.Tensor, k: int, grad_out, loss_out, who: str):
+    """The gradient buffer (None for `grad_out=False`) and the k-word loss tensor of an image term on the prepared `img`: the
+    caller's, checked, or fresh ones.  (k = 1 is `l1_loss_and_grad`, whose contract is older and asks less.)"""
+    dev = img.device
+    grad = None if grad_out is False else (grad_out if grad_out is not None else torch.empty_like(img))
+    loss = loss_out if loss_out is not None else torch.empty(() if k == 1 else (k,), dtype=torch.float32, device=dev)
+    bad = (grad is not None and (grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous())) or loss.numel() != k
+    if k == 1:
+        what = ""
+    else:
+        bad = bad or (grad is not None and grad.device != dev) or loss.dtype != torch.float32 or loss.device != dev or not loss.is_contiguous()
+        what = f" (gradient of the image's shape, {k}-element loss, float32, contiguous)"
+    if bad:
+        raise RuntimeError(f"{who}: bad output buffers{what}")
+    return grad, loss
+
+
+def _check_rows3(who: str, dev: torch.device, rows: int, tensors, what: str) -> None:
+    """Every tensor (None: skipped) is contiguous float32 [rows,3] on `dev`."""
+    for t in tensors:
+        if t is not None and (t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (rows, 3)):
+            raise RuntimeError(f"{who}: contiguous float32 {what}")
+
+
+def _out_words(who: str, out: Optional[torch.Tensor], k: int, dev: torch.device, whose: str, fresh=torch.empty) -> torch.Tensor:
+    """The k-word loss tensor of a term: the caller's `out`, checked, or a fresh one."""
+    loss = out if out is not None else fresh((k,), dtype=torch.float32, device=dev)
+    if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != k or not loss.is_contiguous():
+        raise RuntimeError(f"{who}: `out` is a contiguous {k}-element float32 tensor on the {whose} device")
+    return loss
+
+
+def _ptrs(tensors):
+    """The tensors' addresses as a C pointer array (None: NULL)."""
+    return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _image_lists(who: str, imgs, gts, loss_outs, grad_outs, workspaces):
+    """The lists of a batched image term: 1 .. FR_MAX_BATCH images with one of everything each, on a device.  Returns the
+    detached images, every tensor the kernel walks (images, targets, the gradient buffers that are not None) and the device."""
+    K = len(imgs)
+    if not (1 <= K <= _lib.FR_MAX_BATCH and len(gts) == len(loss_outs) == len(grad_outs) == len(workspaces) == K):
+        raise RuntimeError(f"{who}: 1 .. {_lib.FR_MAX_BATCH} images, one gt / loss / grad / workspace each")
+    imgs = [i.detach() for i in imgs]
+    tensors = list(imgs) + list(gts) + [g for g in grad_outs if g is not None]
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who} needs device tensors (there is no CPU path)")
+    return imgs, tensors, imgs[0].device
+
+
 def l1_workspace(dev: torch.device) -> torch.Tensor:
     """A fresh zeroed workspace for `l1_loss_and_grad(..., workspace=)`: for callers that launch from several streams or
     graphs at once and want to own the scratch explicitly."""
@@ -40,21 +106,10 @@ def l1_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, loss_out: Optional[tor
     """mean |img - gt| (0-dim device tensor) and its gradient with respect to `img`.  `loss_out` / `grad_out`: write into
     these tensors instead of fresh ones (buffers of a captured step).  `workspace`: scratch from `l1_workspace()`; by
     default one is kept per (device, current stream) — launches that may overlap must not share one."""
-    if not (img.is_cuda and gt.is_cuda):
-        raise RuntimeError("l1_loss_and_grad needs device tensors (there is no CPU path)")
-    if img.shape != gt.shape:
-        raise RuntimeError(f"l1_loss_and_grad: shapes differ: {tuple(img.shape)} vs {tuple(gt.shape)}")
-    img = img.detach()
-    if img.dtype != torch.float32 or not img.is_contiguous():
-        img = img.float().contiguous()
-    if gt.dtype != torch.float32 or not gt.is_contiguous():
-        gt = gt.float().contiguous()
-    dev = img.device
-    grad = grad_out if grad_out is not None else torch.empty_like(img)
-    loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float32, device=dev)
-    if grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or loss.numel() != 1:
-        raise RuntimeError("l1_loss_and_grad: bad output buffers")
-    ws = _l1_ws.resolve(dev, workspace, "l1_loss_and_grad")
+    who = "l1_loss_and_grad"
+    img, gt, dev = _image_pair(img, gt, who)
+    grad, loss = _outputs(img, 1, grad_out, loss_out, who)
+    ws = _l1_ws.resolve(dev, workspace, who)
     _lib.launch("fr_l1_loss_grad", dev, img.numel(), img.data_ptr(), gt.data_ptr(), grad.data_ptr(), loss.data_ptr(), ws.data_ptr())
     return loss, grad
 
@@ -63,23 +118,17 @@ def l1_loss_and_grad_batch(imgs, gts, loss_outs, grad_outs, workspaces):
     """`l1_loss_and_grad` for the images of the 1 .. 4 frames of a batch in ONE launch (`fr_l1_loss_grad_batch`): lists of
     equally-sized contiguous float32 device tensors; every image has its own loss scalar, gradient buffer and workspace
     (`l1_workspace()`).  Returns (loss_outs, grad_outs)."""
-    import ctypes as C
-    K = len(imgs)
-    if not (1 <= K <= _lib.FR_MAX_BATCH and len(gts) == len(loss_outs) == len(grad_outs) == len(workspaces) == K):
-        raise RuntimeError(f"l1_loss_and_grad_batch: 1 .. {_lib.FR_MAX_BATCH} images, one gt / loss / grad / workspace each")
-    imgs = [i.detach() for i in imgs]
-    dev, n = imgs[0].device, imgs[0].numel()
-    for t in list(imgs) + list(gts) + list(grad_outs):
-        if not t.is_cuda:
-            raise RuntimeError("l1_loss_and_grad_batch needs device tensors (there is no CPU path)")
+    who = "l1_loss_and_grad_batch"
+    imgs, tensors, dev = _image_lists(who, imgs, gts, loss_outs, grad_outs, workspaces)
+    n = imgs[0].numel()
+    for t in tensors:
         if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
-            raise RuntimeError("l1_loss_and_grad_batch: contiguous float32 tensors of one device and one size")
-    L = _lib.lib()
+            raise RuntimeError(f"{who}: contiguous float32 tensors of one device and one size")
+    need = _lib.lib().fr_l1_workspace_bytes()
     for w, l in zip(workspaces, loss_outs):
-        if not (w.is_cuda and w.device == dev and w.dtype == torch.uint8 and w.numel() >= L.fr_l1_workspace_bytes()) or l.numel() != 1:
-            raise RuntimeError("l1_loss_and_grad_batch: workspaces from l1_workspace(), one-element loss tensors")
-    arr = lambda ts: (C.c_void_p * K)(*[t.data_ptr() for t in ts])  # noqa: E731
-    _lib.launch("fr_l1_loss_grad_batch", dev, K, n, arr(imgs), arr(gts), arr(grad_outs), arr(loss_outs), arr(workspaces))
+        if not (w.is_cuda and w.device == dev and w.dtype == torch.uint8 and w.numel() >= need) or l.numel() != 1:
+            raise RuntimeError(f"{who}: workspaces from l1_workspace(), one-element loss tensors")
+    _lib.launch("fr_l1_loss_grad_batch", dev, len(imgs), n, _ptrs(imgs), _ptrs(gts), _ptrs(grad_outs), _ptrs(loss_outs), _ptrs(workspaces))
     return loss_outs, grad_outs
 
 
@@ -108,33 +157,18 @@ def huber_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, terms=REFERENCE_HUB
     mouth term, the word is 0).  `loss_out` / `grad_out`: write into these tensors instead of fresh ones (buffers of a captured
     step).  `workspace`: scratch from `huber_workspace()`; by default one is kept per (device, current stream) — launches that
     may overlap must not share one.  The losses without the gradient: `grad_out=False`.  There is no CPU path."""
-    if not (img.is_cuda and gt.is_cuda):
-        raise RuntimeError("huber_loss_and_grad needs device tensors (there is no CPU path)")
-    if img.shape != gt.shape:
-        raise RuntimeError(f"huber_loss_and_grad: shapes differ: {tuple(img.shape)} vs {tuple(gt.shape)}")
-    Cn, H, W = _chw(img, "huber_loss_and_grad")
+    who = "huber_loss_and_grad"
+    img, gt, dev = _image_pair(img, gt, who)
+    Cn, H, W = _chw(img, who)
     alpha, mask_weight = float(terms[0]), float(terms[1])
     if not alpha > 0.0:
-        raise ValueError("huber_loss_and_grad: alpha must be > 0")
-    img = img.detach()
-    if img.dtype != torch.float32 or not img.is_contiguous():
-        img = img.float().contiguous()
-    if gt.dtype != torch.float32 or not gt.is_contiguous():
-        gt = gt.float().contiguous()
-    dev = img.device
+        raise ValueError(f"{who}: alpha must be > 0")
     if mask is not None:
         if not mask.is_cuda or mask.device != dev or mask.numel() != H * W or tuple(mask.shape[-2:]) != (H, W):
-            raise RuntimeError(f"huber_loss_and_grad: the mask is [1,{H},{W}] or [{H},{W}] on the image's device")
-        mask = mask.detach()
-        if mask.dtype != torch.float32 or not mask.is_contiguous():
-            mask = mask.float().contiguous()
-    grad = None if grad_out is False else (grad_out if grad_out is not None else torch.empty_like(img))
-    loss = loss_out if loss_out is not None else torch.empty((3,), dtype=torch.float32, device=dev)
-    if (grad is not None and (grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != dev)) \
-            or loss.numel() != 3 or loss.dtype != torch.float32 or loss.device != dev or not loss.is_contiguous():
-        raise RuntimeError("huber_loss_and_grad: bad output buffers (gradient of the image's shape, 3-element loss, float32, contiguous)")
-    ws = _huber_ws.resolve(dev, workspace, "huber_loss_and_grad")
-    import ctypes as C
+            raise RuntimeError(f"{who}: the mask is [1,{H},{W}] or [{H},{W}] on the image's device")
+        mask = _f32c(mask.detach())
+    grad, loss = _outputs(img, 3, grad_out, loss_out, who)
+    ws = _huber_ws.resolve(dev, workspace, who)
     cfg = _lib.fr_huber_config(alpha, mask_weight)
     _lib.launch("fr_huber_loss_grad", dev, C.byref(cfg), Cn, H, W, img.data_ptr(), gt.data_ptr(),
                 mask.data_ptr() if mask is not None else None, grad.data_ptr() if grad is not None else None, loss.data_ptr(),
@@ -166,26 +200,12 @@ def pixel_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, weights=PixelLoss()
     `loss_out` / `grad_out`: write into these tensors instead of fresh ones (buffers of a captured step).  `workspace`: scratch
     from `pixel_loss_workspace()`; by default one is kept per (device, current stream) — launches that may overlap must not
     share one.  The losses without the gradient: `grad_out=False`.  There is no CPU path."""
-    if not (img.is_cuda and gt.is_cuda):
-        raise RuntimeError("pixel_loss_and_grad needs device tensors (there is no CPU path)")
-    if img.shape != gt.shape:
-        raise RuntimeError(f"pixel_loss_and_grad: shapes differ: {tuple(img.shape)} vs {tuple(gt.shape)}")
-    Cn, H, W = _chw(img, "pixel_loss_and_grad")
-    rgb_weight, mse_weight = float(weights[0]), float(weights[1])
-    img = img.detach()
-    if img.dtype != torch.float32 or not img.is_contiguous():
-        img = img.float().contiguous()
-    if gt.dtype != torch.float32 or not gt.is_contiguous():
-        gt = gt.float().contiguous()
-    dev = img.device
-    grad = None if grad_out is False else (grad_out if grad_out is not None else torch.empty_like(img))
-    loss = loss_out if loss_out is not None else torch.empty((3,), dtype=torch.float32, device=dev)
-    if (grad is not None and (grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != dev)) \
-            or loss.numel() != 3 or loss.dtype != torch.float32 or loss.device != dev or not loss.is_contiguous():
-        raise RuntimeError("pixel_loss_and_grad: bad output buffers (gradient of the image's shape, 3-element loss, float32, contiguous)")
-    ws = _pixel_ws.resolve(dev, workspace, "pixel_loss_and_grad")
-    import ctypes as C
-    cfg = _lib.fr_pixel_loss_config(rgb_weight, mse_weight)
+    who = "pixel_loss_and_grad"
+    img, gt, dev = _image_pair(img, gt, who)
+    Cn, H, W = _chw(img, who)
+    cfg = _lib.fr_pixel_loss_config(float(weights[0]), float(weights[1]))
+    grad, loss = _outputs(img, 3, grad_out, loss_out, who)
+    ws = _pixel_ws.resolve(dev, workspace, who)
     _lib.launch("fr_pixel_loss_grad", dev, C.byref(cfg), Cn, H, W, img.data_ptr(), gt.data_ptr(),
                 grad.data_ptr() if grad is not None else None, loss.data_ptr(), ws.data_ptr())
     return loss, grad
@@ -220,16 +240,9 @@ def scale_term_and_grad(scaling: torch.Tensor, d_scaling: Optional[torch.Tensor]
     dev = scaling.device
     P = int(scaling.shape[0])
     scaling = scaling.detach()
-    for t in (scaling, d_scaling):
-        if t is None:
-            continue
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (P, 3):
-            raise RuntimeError("scale_term_and_grad: contiguous float32 [P,3] tensors of one device")
-    loss = out if out is not None else torch.zeros((2,), dtype=torch.float32, device=dev)   # (P == 0 launches nothing)
-    if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
-        raise RuntimeError("scale_term_and_grad: `out` is a contiguous 2-element float32 tensor on the parameters' device")
+    _check_rows3("scale_term_and_grad", dev, P, (scaling, d_scaling), "[P,3] tensors of one device")
+    loss = _out_words("scale_term_and_grad", out, 2, dev, "parameters'", fresh=torch.zeros)   # (P == 0 launches nothing)
     ws = _scale_ws.resolve(dev, workspace, "scale_term_and_grad")
-    import ctypes as C
     cfg = _lib.fr_scale_term_config(float(terms[0]), float(terms[1]), float(terms[2]))
     _lib.launch("fr_scale_term", dev, C.byref(cfg), P, scaling.data_ptr() if P else None,
                 d_scaling.data_ptr() if d_scaling is not None and P else None, loss.data_ptr(), ws.data_ptr())
@@ -255,16 +268,9 @@ def gaussian_regularisers(scaling: torch.Tensor, xyz: torch.Tensor, d_scaling: O
     dev = scaling.device
     P = int(scaling.shape[0])
     scaling, xyz = scaling.detach(), xyz.detach()
-    for t in (scaling, xyz, d_scaling, d_xyz):
-        if t is None:
-            continue
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (P, 3):
-            raise RuntimeError("gaussian_regularisers: contiguous float32 [P,3] tensors of one device")
-    loss = out if out is not None else torch.empty((2,), dtype=torch.float32, device=dev)
-    if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
-        raise RuntimeError("gaussian_regularisers: `out` is a contiguous 2-element float32 tensor on the parameters' device")
+    _check_rows3("gaussian_regularisers", dev, P, (scaling, xyz, d_scaling, d_xyz), "[P,3] tensors of one device")
+    loss = _out_words("gaussian_regularisers", out, 2, dev, "parameters'")
     ws = _reg_ws.resolve(dev, workspace, "gaussian_regularisers")
-    import ctypes as C
     cfg = _lib.fr_regularise_config(float(weights[0]), float(weights[1]), float(thresholds[0]), float(thresholds[1]))
     _lib.launch("fr_gaussian_regularise", dev, C.byref(cfg), P, scaling.data_ptr(), xyz.data_ptr(),
                 d_scaling.data_ptr() if d_scaling is not None else None, d_xyz.data_ptr() if d_xyz is not None else None,
@@ -301,19 +307,12 @@ def mesh_terms_and_grad(verts: torch.Tensor, verts_orig: torch.Tensor, lap, term
     dev = verts.device
     V = int(lap.V)
     verts, verts_orig = verts.detach(), verts_orig.detach()
-    for t in (verts, verts_orig, d_verts):
-        if t is None:
-            continue
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (V, 3):
-            raise RuntimeError("mesh_terms_and_grad: contiguous float32 [V,3] tensors of one device, V that of the Laplacian")
+    _check_rows3("mesh_terms_and_grad", dev, V, (verts, verts_orig, d_verts), "[V,3] tensors of one device, V that of the Laplacian")
     for t, n in ((lap.row_ptr, V + 1), (lap.col, None)):
         if t.device != dev or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1 or (n is not None and t.numel() != n):
             raise RuntimeError("mesh_terms_and_grad: `lap` is a binding.mesh_laplacian() on the vertices' device")
-    loss = out if out is not None else torch.empty((2,), dtype=torch.float32, device=dev)
-    if loss.device != dev or loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
-        raise RuntimeError("mesh_terms_and_grad: `out` is a contiguous 2-element float32 tensor on the vertices' device")
+    loss = _out_words("mesh_terms_and_grad", out, 2, dev, "vertices'")
     ws = _mesh_ws.resolve(dev, workspace, "mesh_terms_and_grad")
-    import ctypes as C
     cfg = _lib.fr_mesh_terms_config(float(terms[0]), float(terms[1]))
     # (a mesh without edges has an empty `col` nobody reads; the entry point refuses NULL, and an empty tensor has no address)
     col = lap.col if lap.col.numel() else lap.row_ptr
@@ -362,7 +361,6 @@ def multi_copy(pairs) -> None:
     same few sets of tensors over and over (its static buffers, the frames of a resident sequence): the ctypes argument
     arrays of a set are made once and looked up by the tensors' addresses afterwards — this call is on the host's critical
     path of a 130 us step."""
-    import ctypes as C
     pairs = [(d, s) for d, s in pairs if d.numel()]
     if not pairs:
         return
@@ -400,7 +398,6 @@ def multi_copy(pairs) -> None:
 def scaled_sum(dst: torch.Tensor, srcs, scale: float) -> torch.Tensor:
     """dst = scale * sum(srcs) for 1 .. 4 contiguous float32 device tensors of dst's size, in ONE pass (`fr_scaled_sum`):
     the mean of the gradient buffers of the views a rank rendered in flight together."""
-    import ctypes as C
     srcs = list(srcs)
     if not 1 <= len(srcs) <= _lib.FR_ADAM_MAX_GRADS:
         raise RuntimeError(f"scaled_sum: 1..{_lib.FR_ADAM_MAX_GRADS} sources")
@@ -408,8 +405,7 @@ def scaled_sum(dst: torch.Tensor, srcs, scale: float) -> torch.Tensor:
     for t in [dst] + srcs:
         if not t.is_cuda or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != dst.numel():
             raise RuntimeError("scaled_sum: contiguous float32 tensors of one device and one size")
-    ptrs = (C.c_void_p * len(srcs))(*[t.data_ptr() for t in srcs])
-    _lib.launch("fr_scaled_sum", dev, len(srcs), ptrs, dst.data_ptr(), dst.numel(), float(scale))
+    _lib.launch("fr_scaled_sum", dev, len(srcs), _ptrs(srcs), dst.data_ptr(), dst.numel(), float(scale))
     return dst
 
 
@@ -437,7 +433,6 @@ _image_workspace = _image_ws.kept   # (device index, stream handle) -> workspace
 
 def ssim_window() -> torch.Tensor:
     """The eleven 1-D taps of d_ssim's window, `gaussian(11, 1.5)` of dssim.py:18-20 in its float32 arithmetic (CPU tensor)."""
-    import ctypes as C
     out = (C.c_float * 11)()
     _lib.lib().fr_ssim_window(out)
     return torch.tensor(list(out), dtype=torch.float32)
@@ -461,32 +456,22 @@ def image_loss_and_grad_batch(imgs, gts, weights, loss_outs, grad_outs, workspac
     """`image_loss_and_grad` for the images of the 1 .. 4 frames of a batch in ONE launch pair (`fr_image_loss_grad`): lists of
     equally-shaped contiguous float32 device tensors; every image has its own 3-element loss tensor, gradient buffer (an
     entry may be None: losses only) and workspace (`image_loss_workspace()`).  Returns (loss_outs, grad_outs)."""
-    import ctypes as C
-    K = len(imgs)
-    if not (1 <= K <= _lib.FR_MAX_BATCH and len(gts) == len(loss_outs) == len(grad_outs) == len(workspaces) == K):
-        raise RuntimeError(f"image_loss_and_grad_batch: 1 .. {_lib.FR_MAX_BATCH} images, one gt / loss / grad / workspace each")
-    imgs = [i.detach() for i in imgs]
-    dev = imgs[0].device
-    tensors = list(imgs) + list(gts) + [g for g in grad_outs if g is not None]
+    who = "image_loss_and_grad_batch"
+    imgs, tensors, dev = _image_lists(who, imgs, gts, loss_outs, grad_outs, workspaces)
+    shape = _chw(imgs[0], who)
     for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError("image_loss_and_grad_batch needs device tensors (there is no CPU path)")
-    shape = _chw(imgs[0], "image_loss_and_grad_batch")
-    for t in tensors:
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or _chw(t, "image_loss_and_grad_batch") != shape:
-            raise RuntimeError("image_loss_and_grad_batch: contiguous float32 tensors of one device and one shape")
-    L = _lib.lib()
-    need = L.fr_image_loss_workspace_bytes(*shape)
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or _chw(t, who) != shape:
+            raise RuntimeError(f"{who}: contiguous float32 tensors of one device and one shape")
+    need = _lib.lib().fr_image_loss_workspace_bytes(*shape)
     for w, l in zip(workspaces, loss_outs):
         if not (w.is_cuda and w.device == dev and w.dtype == torch.uint8 and w.numel() >= need):
-            raise RuntimeError(f"image_loss_and_grad_batch: workspace must come from image_loss_workspace() for this image shape "
+            raise RuntimeError(f"{who}: workspace must come from image_loss_workspace() for this image shape "
                                f"on the images' device ({need} bytes)")
         if not (l.is_cuda and l.device == dev and l.dtype == torch.float32 and l.numel() == 3 and l.is_contiguous()):
-            raise RuntimeError("image_loss_and_grad_batch: contiguous 3-element float32 loss tensors on the images' device")
-    arr = lambda ts: (C.c_void_p * K)(*[None if t is None else t.data_ptr() for t in ts])  # noqa: E731
+            raise RuntimeError(f"{who}: contiguous 3-element float32 loss tensors on the images' device")
     cfg = _lib.fr_image_loss_config(float(weights[0]), float(weights[1]))
-    _lib.launch("fr_image_loss_grad", dev, C.byref(cfg), K, shape[0], shape[1], shape[2], arr(imgs), arr(gts), arr(grad_outs),
-                arr(loss_outs), arr(workspaces))
+    _lib.launch("fr_image_loss_grad", dev, C.byref(cfg), len(imgs), shape[0], shape[1], shape[2], _ptrs(imgs), _ptrs(gts),
+                _ptrs(grad_outs), _ptrs(loss_outs), _ptrs(workspaces))
     return loss_outs, grad_outs
 
 
@@ -499,22 +484,9 @@ def image_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, weights, loss_out: 
     tensors instead of fresh ones (buffers of a captured step).  `workspace`: scratch from `image_loss_workspace()`; by
     default one is kept per (device, current stream) — launches that may overlap must not share one.  The losses without the
     gradient: `image_loss_and_grad_batch` with a None gradient entry."""
-    if not (img.is_cuda and gt.is_cuda):
-        raise RuntimeError("image_loss_and_grad needs device tensors (there is no CPU path)")
-    if img.shape != gt.shape:
-        raise RuntimeError(f"image_loss_and_grad: shapes differ: {tuple(img.shape)} vs {tuple(gt.shape)}")
+    img, gt, dev = _image_pair(img, gt, "image_loss_and_grad")
     shape = _chw(img, "image_loss_and_grad")
-    img = img.detach()
-    if img.dtype != torch.float32 or not img.is_contiguous():
-        img = img.float().contiguous()
-    if gt.dtype != torch.float32 or not gt.is_contiguous():
-        gt = gt.float().contiguous()
-    dev = img.device
-    grad = grad_out if grad_out is not None else torch.empty_like(img)
-    loss = loss_out if loss_out is not None else torch.empty((3,), dtype=torch.float32, device=dev)
-    if (grad.shape != img.shape or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != dev
-            or loss.numel() != 3 or loss.dtype != torch.float32 or loss.device != dev or not loss.is_contiguous()):
-        raise RuntimeError("image_loss_and_grad: bad output buffers (gradient of the image's shape, 3-element loss, float32, contiguous)")
+    grad, loss = _outputs(img, 3, grad_out, loss_out, "image_loss_and_grad")
     # (a caller's workspace is checked by image_loss_and_grad_batch, which names the bytes this shape takes)
     ws = workspace if workspace is not None else _image_ws.resolve(dev, None, "image_loss_and_grad", need=shape)
     image_loss_and_grad_batch([img], [gt], weights, [loss], [grad], [ws])
@@ -524,11 +496,7 @@ def image_loss_and_grad(img: torch.Tensor, gt: torch.Tensor, weights, loss_out: 
 class _DSsim(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img1, img2):
-        if not (img1.is_cuda and img2.is_cuda):
-            raise RuntimeError("d_ssim needs device tensors (there is no CPU path)")
-        if img1.shape != img2.shape:
-            raise RuntimeError(f"d_ssim: shapes differ: {tuple(img1.shape)} vs {tuple(img2.shape)}")
-        x, y = img1.detach().float().contiguous(), img2.detach().float().contiguous()
+        x, y, _ = _image_pair(img1, img2, "d_ssim")
         grad = torch.empty_like(x) if ctx.needs_input_grad[0] else None     # None: losses only, pass 2 is not launched
         loss = torch.empty(3, dtype=torch.float32, device=x.device)
         image_loss_and_grad_batch([x], [y], (0.0, 1.0), [loss], [grad], [_image_ws.resolve(x.device, None, "d_ssim", need=_chw(x, "d_ssim"))])

@@ -27,6 +27,20 @@ def _l1(b, dev, gen):
     return (lambda ws: list(l1_loss_and_grad(x, y, workspace=ws))), (lambda: l1_workspace(dev))
 
 
+def _l1_batch(b, dev, gen):
+    """Two images in one launch (grid (b, 2)), a workspace each: both are checked."""
+    import torch
+    from fateavatar_amd.loss import l1_loss_and_grad_batch, l1_workspace
+    n = 1024 * b + 3
+    xs, ys = [_rand(gen, n).to(dev) for _ in range(2)], [_rand(gen, n).to(dev) for _ in range(2)]
+
+    def run(wss):
+        losses, grads = [torch.empty((), dtype=torch.float32, device=dev) for _ in xs], [torch.empty_like(x) for x in xs]
+        l1_loss_and_grad_batch(xs, ys, losses, grads, list(wss))
+        return losses + grads
+    return run, (lambda: (l1_workspace(dev), l1_workspace(dev)))
+
+
 def _l1_terms(b, dev, gen):
     """fr_image_loss_grad with a D-SSIM weight of 0: the L1 kernel's instance that zeroes its partials.  1024 b + 2 floats as
     two rows (the entry point takes rows of up to 2^20 pixels): b workgroups and a tail of two."""
@@ -41,6 +55,37 @@ def _huber(b, dev, gen):
     n = 1024 * b + 3
     x, y, m = _rand(gen, 1, 1, n).to(dev), _rand(gen, 1, 1, n).to(dev), _rand(gen, 1, n).to(dev)
     return (lambda ws: list(huber_loss_and_grad(x, y, mask=m, workspace=ws))), (lambda: huber_workspace(dev))
+
+
+def _pixel(b, dev, gen):
+    from fateavatar_amd.loss import pixel_loss_and_grad, pixel_loss_workspace
+    n = 1024 * b + 3
+    x, y = _rand(gen, 1, 1, n).to(dev), _rand(gen, 1, 1, n).to(dev)
+    return (lambda ws: list(pixel_loss_and_grad(x, y, workspace=ws))), (lambda: pixel_loss_workspace(dev))
+
+
+def _scale_term(b, dev, gen):
+    """The reference's gates on rows drawn around them (tests/splatting_loss_ref.py): in float64, here on the CPU, rows lie on
+    both sides of both gates and the selection is neither empty nor everything, so the loss word is a sum of positive terms."""
+    import torch
+    from fateavatar_amd.loss import ScaleTerm, scale_term_and_grad, scale_term_workspace
+    from tests import splatting_loss_ref as R
+    P = 256 * b
+    ref = R.REFERENCE
+    cpu = R.draw_scaling(P, gen)
+    scale = torch.exp(cpu.double())
+    smax, smin = scale.max(dim=1).values, scale.min(dim=1).values
+    for gate in (smax > ref["max_scaling"], smax / smin > ref["scale_threshold"]):
+        assert bool(gate.any()) and not bool(gate.all())
+    count = R.scale_term(cpu, ref["scale_weight"], ref["scale_threshold"], ref["max_scaling"])[1]
+    assert 0 < count < P, count
+    scaling = cpu.to(dev)
+
+    def run(ws):
+        d = torch.zeros_like(scaling)
+        terms = ScaleTerm(ref["scale_weight"], ref["scale_threshold"], ref["max_scaling"])
+        return [scale_term_and_grad(scaling, d, terms=terms, workspace=ws).clone(), d]
+    return run, (lambda: scale_term_workspace(dev))
 
 
 def _regulariser(b, dev, gen):
@@ -92,7 +137,8 @@ def _image(b, dev, gen):
 
 
 # op -> (case builder, partial floats the kernel promises to leave zeroed; None: no promise), with the counts it is run at
-OPS = {"l1": (_l1, None), "l1_terms": (_l1_terms, CAP), "huber": (_huber, 2 * CAP), "regulariser": (_regulariser, 2 * CAP),
+OPS = {"l1": (_l1, None), "l1_batch": (_l1_batch, None), "l1_terms": (_l1_terms, CAP), "huber": (_huber, 2 * CAP),
+       "pixel": (_pixel, 2 * CAP), "scale_term": (_scale_term, 2 * CAP), "regulariser": (_regulariser, 2 * CAP),
        "mesh": (_mesh, 2 * CAP), "lbs": (_lbs, 3 * CAP), "image": (_image, 0)}
 CASES = [(op, b) for op in OPS for b in (IMAGE_SHAPES if op == "image" else COUNTS)]
 
@@ -109,9 +155,10 @@ def test_same_bits_on_every_launch_and_the_workspace_left_zeroed(gpu_device, op,
     def launch(ws):
         outs = run(ws)
         torch.cuda.synchronize()
-        assert int(ws[:COUNTER_BYTES].count_nonzero()) == 0, "counters"
-        if partial_floats is not None:
-            assert int(ws[COUNTER_BYTES:COUNTER_BYTES + 4 * partial_floats].count_nonzero()) == 0, "partials"
+        for w in (ws if isinstance(ws, tuple) else (ws,)):     # (l1_batch: one workspace per image)
+            assert int(w[:COUNTER_BYTES].count_nonzero()) == 0, "counters"
+            if partial_floats is not None:
+                assert int(w[COUNTER_BYTES:COUNTER_BYTES + 4 * partial_floats].count_nonzero()) == 0, "partials"
         return [o.clone() for o in outs]
 
     ws = fresh()
