@@ -136,6 +136,18 @@ class fr_mlp(C.Structure):
                 ("E", C.c_void_p), ("cond", C.c_void_p), ("weights", C.c_void_p)]
 
 
+FR_FLAME_MAX_E = 128
+FR_FLAME_JOINTS = 5
+FR_FLAME_POSE_FEATURES = 36
+
+
+class fr_flame(C.Structure):
+    _fields_ = [("V", C.c_int32), ("NS", C.c_int32), ("NE", C.c_int32), ("parents", C.c_void_p), ("v_template", C.c_void_p),
+                ("shapedirs", C.c_void_p), ("posedirs", C.c_void_p), ("J_regressor", C.c_void_p), ("lbs_weights", C.c_void_p),
+                ("delta_exp", C.c_void_p), ("delta_posedirs", C.c_void_p), ("delta_vertex", C.c_void_p), ("expression", C.c_void_p),
+                ("pose", C.c_void_p)]
+
+
 class fr_image_loss_config(C.Structure):
     _fields_ = [("rgb_weight", C.c_float), ("dssim_weight", C.c_float)]
 
@@ -172,7 +184,8 @@ EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile
            "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_huber_workspace_bytes", "fr_huber_loss_grad", "fr_pixel_loss_workspace_bytes", "fr_pixel_loss_grad", "fr_scale_term_workspace_bytes", "fr_scale_term", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_mesh_terms_workspace_bytes", "fr_mesh_terms", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
            "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_bind_backward_deform", "fr_phong_frame", "fr_bind_backward_phong_frame", "fr_phong_frame_backward_workspace_bytes", "fr_phong_frame_backward", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward",
            "fr_point_lbs_forward", "fr_point_lbs_backward", "fr_point_lbs_pose_workspace_bytes", "fr_point_lbs_backward_pose", "fr_nearest_vertex", "fr_lbs_terms_workspace_bytes", "fr_lbs_terms",
-           "fr_mlp_workspace_bytes", "fr_mlp_forward", "fr_mlp_backward"]
+           "fr_mlp_workspace_bytes", "fr_mlp_forward", "fr_mlp_backward",
+           "fr_flame_workspace_bytes", "fr_flame_workspace_zeroed_bytes", "fr_flame_forward", "fr_flame_backward"]
 
 
 def build(force: bool = False) -> str:
@@ -341,6 +354,14 @@ def lib():
     L.fr_mlp_forward.restype = C.c_int
     L.fr_mlp_backward.argtypes = [C.POINTER(fr_mlp), _fp, _fp, _fp, _fp, C.c_void_p]
     L.fr_mlp_backward.restype = C.c_int
+    L.fr_flame_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.fr_flame_workspace_bytes.restype = C.c_size_t
+    L.fr_flame_workspace_zeroed_bytes.argtypes = []
+    L.fr_flame_workspace_zeroed_bytes.restype = C.c_size_t
+    L.fr_flame_forward.argtypes = [C.POINTER(fr_flame), _fp, _fp, _fp, _fp, _fp, C.c_void_p]
+    L.fr_flame_forward.restype = C.c_int
+    L.fr_flame_backward.argtypes = [C.POINTER(fr_flame), _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
+    L.fr_flame_backward.restype = C.c_int
     L.fr_ssim_window.argtypes = [C.POINTER(C.c_float)]
     L.fr_ssim_window.restype = None
     L.fr_image_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

@@ -26,11 +26,13 @@ import torch
 from . import dp
 from .binding import bind_gaussians, face_scale
 from .bound import MeshBinding, render_bound_batch
+from .flame import REFERENCE_FLAME_LRS, FlameFrame, FlameMesh
 from .flat import FlatParams
 from .model import TorchCamera
+from .optim import FusedAdam
 from .render import render
 from .loss import MeshTerms, l1_loss_and_grad, l1_workspace, mesh_terms_and_grad, mesh_terms_workspace
-from .train import BoundStep
+from .train import BoundStep, TrainStep
 
 # config/fateavatar.yaml:34-39 (group names of train/optim.py:15-21)
 FATE_LRS = dict(opacity=0.05, offset=0.0016, color=0.0025, rotation=0.001, scaling=0.005)
@@ -117,8 +119,9 @@ class AvatarStep(BoundStep):
     """One optimisation step of FateAvatar per call: `step(camera, posed_verts, gt_image)`.  The optimizer groups are those
     of train/optim.py:15-21 with config/fateavatar.yaml:34-39 (the `gs` group).  The other half of the model — the mesh
     under the Gaussians, learnt through FLAME's `delta_shapedirs` / `delta_posedirs` / `delta_vertex`
-    (model/fateavatar.py:87-94,212-223, the `bs` group) — stays the caller's, in stock PyTorch: `vertex_grad` / `mesh_terms`
-    hand it this step's dLoss/dposed_verts."""
+    (model/fateavatar.py:87-94,212-223, the `bs` group) — stays the caller's, in stock PyTorch, by default: `vertex_grad` /
+    `mesh_terms` hand it this step's dLoss/dposed_verts.  With `flame=FlameMesh(...)` the mesh is part of the captured step too
+    (flame.py, csrc/fr_flame.hip): `step(camera, FlameFrame(expression, pose), gt_image)`."""
     LRS = FATE_LRS
     LR_KEYS = {"_opacity": "opacity", "_offset": "offset", "_features_dc": "color", "_rotation": "rotation", "_scaling": "scaling"}
     CAMERA_GRAD = True
@@ -126,7 +129,8 @@ class AvatarStep(BoundStep):
     def __init__(self, pc: AvatarGaussians, faces: torch.Tensor, canonical_verts: torch.Tensor, camera: TorchCamera,
                  bg: torch.Tensor, lrs: Optional[dict] = None, shell_len: float = 0.05, resize_scale: bool = True,
                  use_graph: bool = True, fold_binding: bool = True, keep_coherent: bool = False, vertex_grad: bool = False,
-                 mesh_terms: Optional[MeshTerms] = None, camera_grad: bool = False):
+                 mesh_terms: Optional[MeshTerms] = None, camera_grad: bool = False, flame: Optional[FlameMesh] = None,
+                 flame_lrs: Optional[dict] = None):
         """`keep_coherent`: after every `uv_densify` the rows are re-stored in a spatially coherent order (`sort_coherent`):
         the reference appends the new rows at the end (model/fateavatar.py:640-665), so a set that started in UV-raster
         order (mesh_sampling.py:86-138: neighbours in storage are neighbours on the mesh) grows an unordered tail; the
@@ -143,11 +147,38 @@ class AvatarStep(BoundStep):
         weighted gradient into `d_verts`; `mesh_loss` then holds the step's unweighted (laplacian_loss, flame_loss), `loss`
         stays the image term.  Implies `vertex_grad`.  None (default): no such launch, `mesh_loss` is None.
         `camera_grad`: `d_view` / `d_proj` / `d_campos` hold every step's dLoss/d(camera) (BoundStep): what a per-frame camera
-        embedding (the reference's `cam_pose`, train/base.py:123,142) trains on."""
+        embedding (the reference's `cam_pose`, train/base.py:123,142) trains on.
+        `flame`: a `flame.FlameMesh` over the mesh's V vertices makes FLAME and its three learnt deltas part of the step:
+        `step(camera, FlameFrame(expression, pose), gt_image)` then takes the frame's coefficients where it took the posed
+        vertices (a vertex tensor or a `verts_orig` argument is refused), and the captured body is FLAME forward (into the
+        step's vertex buffer and, with `mesh_terms`, into `verts_orig`: the reference's second, delta-free forward) -> the
+        frame -> the mesh terms -> FLAME backward from `d_verts` -> the Gaussians' Adam -> an Adam of the mesh's flat buffer
+        with the three groups of train/optim.py:27-33 at `flame_lrs` (default REFERENCE_FLAME_LRS: 1e-5, 1e-5, 1e-4), skipped by
+        the same overflow word.  `d_expression` [n_exp] and `d_pose` [15] hold THIS step's dLoss/d(expression, pose) — what the
+        reference's tracking optimisation (tracking_lr) trains on — with the lifetime rules of `d_verts`.  Implies
+        `vertex_grad`.  None (default): the mesh is the caller's, nothing here changes."""
         self.keep_coherent = bool(keep_coherent)
         self.mesh_terms = None if mesh_terms is None else MeshTerms(*[float(x) for x in mesh_terms])
+        if flame is not None:
+            if not isinstance(flame, FlameMesh):
+                raise TypeError("AvatarStep: `flame` must be a flame.FlameMesh")
+            if flame.V != int(canonical_verts.shape[0]):
+                raise ValueError(f"AvatarStep: the FLAME model has {flame.V} vertices, the mesh {int(canonical_verts.shape[0])}")
+            if flame.device != pc.flat.device:
+                raise ValueError("AvatarStep: the FLAME model and the Gaussians live on different devices")
+            if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                raise NotImplementedError("AvatarStep(flame=...): data-parallel runs of the fused mesh are not built (its gradient "
+                                          "has no all-reduce): use the caller's FLAME with `vertex_grad`")
+            self._flame_segments = flame.adam_segments(flame_lrs)
+            flame._ensure_workspace()              # (allocates: outside any capture)
+        self.flame, self.flame_adam = flame, None
         super().__init__(pc, faces, camera, bg, canonical_verts, lrs, use_graph, fold_binding,
-                         vertex_grad=bool(vertex_grad) or mesh_terms is not None, camera_grad=camera_grad)
+                         vertex_grad=bool(vertex_grad) or mesh_terms is not None or flame is not None, camera_grad=camera_grad)
+        # with a FLAME model: the frame's coefficients, two more static inputs, and their gradients
+        self.expression = self.pose = self.d_expression = self.d_pose = None
+        if flame is not None:
+            self.expression, self.pose = torch.zeros(flame.n_exp, device=self.dev), torch.zeros(15, device=self.dev)
+            self.d_expression, self.d_pose = torch.zeros(flame.n_exp, device=self.dev), torch.zeros(15, device=self.dev)
         self.mesh_loss = self.verts_orig = self.laplacian = self._mesh_ws = None
         if self.mesh_terms is not None:
             from .binding import mesh_laplacian
@@ -160,14 +191,35 @@ class AvatarStep(BoundStep):
         # compute_face_orientation(canonical verts, return_scale=True)[1] (model/fateavatar.py:84-85)
         self.face_scale_canonical = face_scale(self.canon_verts, self.faces)
 
+    def _make_adam(self):
+        """The Gaussians' optimizer; the mesh's is made ONCE (a change of the point set does not touch the mesh: its moments
+        and step count go on) and skips on the holder's present overflow word."""
+        super()._make_adam()
+        if self.flame is not None:
+            if self.flame_adam is None:
+                self.flame_adam = FusedAdam(self.flame.flat.detach(), self.flame.flat_grad, self._flame_segments)
+            self.flame_adam.set_skip_words([self.pc.overflow_word])
+
+    def _buffers_moved(self, old_index, old_rows, *, stats):
+        super()._buffers_moved(old_index, old_rows, stats=stats)
+        if self.flame is not None:
+            self.flame_adam.set_skip_words([self.pc.overflow_word])   # (a remapped optimizer: the word may have moved)
+
     def _forward_backward(self):
         self._forward_backward_on(self)
+
+    def _body(self):
+        super()._body()
+        if self.flame is not None:
+            self.flame_adam.step()
 
     def _forward_backward_on(self, L):
         """Bind, render, L1, backward for one frame.  `L` holds what the frame reads and writes — pc, verts, cam, gt, loss,
         _dimage, xyz_gradient_accum, denom, out: this object itself, or one lane of an AvatarBatchStep."""
         pc = L.pc
         pc.begin_step()                                             # zero_grad(set_to_none=True), iteration.py:48-49
+        if self.flame is not None:     # model/fateavatar.py:212-223: both FLAME forwards, two launches
+            self.flame.forward_into(self.expression, self.pose, L.verts, self.verts_orig)
         verts, cam = self._vertex_leaf(L.verts), self._camera_leaf(L.cam)
         if self.fold_binding:
             from . import rasterizer
@@ -187,11 +239,25 @@ class AvatarStep(BoundStep):
             # that overflowed its binning capacity back-propagated zeros: d_verts then holds the mesh terms alone.
             mesh_terms_and_grad(L.verts, self.verts_orig, self.laplacian, self.mesh_terms, d_verts=self.d_verts, out=self.mesh_loss,
                                 workspace=self._mesh_ws)
+        if self.flame is not None:     # d_verts -> the deltas' flat gradient, d_expression, d_pose: two launches
+            self.flame.backward_from(self.d_verts, self.expression, self.pose, self.d_expression, self.d_pose)
         L.out = self._kept(out)
 
-    def step(self, camera: TorchCamera, posed_verts: torch.Tensor, gt_image: torch.Tensor,
+    def step(self, camera: TorchCamera, posed_verts, gt_image: torch.Tensor,
              verts_orig: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """`verts_orig` [V,3]: the mesh the mesh terms hold `posed_verts` to — required with `mesh_terms`, refused without."""
+        """`verts_orig` [V,3]: the mesh the mesh terms hold `posed_verts` to — required with `mesh_terms`, refused without.
+        A step built with `flame` takes a `FlameFrame(expression [n_exp], pose [15])` where it took `posed_verts` and makes
+        both meshes itself: a vertex tensor or a `verts_orig` is refused."""
+        if self.flame is not None:
+            if verts_orig is not None or not isinstance(posed_verts, FlameFrame):
+                raise ValueError("AvatarStep.step: a step with a FLAME model takes FlameFrame(expression, pose) where it took the "
+                                 "posed vertices, and no `verts_orig` (it makes both meshes itself)")
+            e, p = posed_verts
+            if tuple(e.shape) != tuple(self.expression.shape) or tuple(p.shape) != (15,):
+                raise ValueError(f"AvatarStep.step: FlameFrame(expression [{self.expression.shape[0]}], pose [15]), not "
+                                 f"{tuple(e.shape)} and {tuple(p.shape)}")
+            # (BoundStep.step would load the vertex buffer: here the kernels write it)
+            return TrainStep.step(self, camera, gt_image, [(self.expression, e.detach()), (self.pose, p.detach())])
         if (verts_orig is None) != (self.mesh_terms is None):
             raise ValueError("AvatarStep.step: `verts_orig` goes with `mesh_terms` (required with them, refused without)")
         return super().step(camera, posed_verts, gt_image, () if verts_orig is None else [(self.verts_orig, verts_orig.detach())])
@@ -261,12 +327,36 @@ class AvatarStep(BoundStep):
                            'bary_coords']   # train/deserialize.py:10-12
     RESUME_REMAPPED = True      # a checkpoint without an `optimizer` entry goes on from this step's count with zero moments
 
+    # with a FLAME model the checkpoint's 'model' also carries delta_shapedirs [V,3,L], delta_posedirs [36,3V] and
+    # delta_vertex [V,3] under the reference's names (model/fateavatar.py:87-94), and `flame_optimizer` (an addition, like
+    # `optimizer`) their Adam state
     def _save_extras(self, sd: dict) -> None:
         sd["model"]["_features_rest"] = torch.zeros((self.pc.P, 0, 3), device=self.dev)   # max_sh_degree 0: empty (fateavatar.py:172-183)
+        if self.flame is not None:
+            sd["model"].update(self.flame.state_dict())
+            a = self.flame_adam
+            sd["flame_optimizer"] = {"exp_avg": a.exp_avg.clone(), "exp_avg_sq": a.exp_avg_sq.clone(), "state": a.state_words()}
 
     def _load_extras(self, sd: dict, g: dict) -> None:
         if int(g["_features_rest"].shape[1]) != 0:
             raise ValueError("FateAvatar renders SH degree 0: _features_rest must be empty")
+        if self.flame is not None:
+            self.flame.check_state_dict(sd["model"])
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> list:
+        """BoundStep.load_state_dict; with a FLAME model the three `delta_*` entries are LOADED (in place) instead of being
+        returned as ignored, and `flame_optimizer`, if the checkpoint has one, restores their Adam (else it goes on as it is)."""
+        ignored = super().load_state_dict(sd)
+        if self.flame is None:
+            return ignored
+        self.flame.load_state_dict(sd["model"])
+        opt = sd.get("flame_optimizer")
+        if opt is not None:
+            self.flame_adam.exp_avg.copy_(opt["exp_avg"])
+            self.flame_adam.exp_avg_sq.copy_(opt["exp_avg_sq"])
+            self.flame_adam.load_state_words(opt["state"])
+        return [k for k in ignored if k not in ("delta_shapedirs", "delta_posedirs", "delta_vertex")]
 
 
 class _Lane:
@@ -296,6 +386,9 @@ class AvatarBatchStep(AvatarStep):
             raise ValueError(f"views_per_step must be 1..{_lib.FR_ADAM_MAX_GRADS}")
         if kw.get("camera_grad"):
             raise NotImplementedError("AvatarBatchStep: `camera_grad` is not built for the batch step: use AvatarStep")
+        if kw.get("flame") is not None:
+            raise NotImplementedError("AvatarBatchStep: `flame` is not built for the batch step (one FLAME state per step, like "
+                                      "`vertex_grad`): use AvatarStep")
         if kw.get("vertex_grad") or kw.get("mesh_terms") is not None:
             raise NotImplementedError("AvatarBatchStep: `vertex_grad` / `mesh_terms` are not built for the batch step (two step "
                                       "bodies, and its twelve multi_copy segments are used up at K = 4): use AvatarStep")

@@ -846,4 +846,40 @@ int fr_mlp_backward(const fr_mlp* mlp, const float* d_out, float* d_weights, flo
     return launch_mlp_backward(*mlp, d_out, d_weights, d_cond, workspace, static_cast<hipStream_t>(stream));
 }
 
+size_t fr_flame_workspace_bytes(int32_t V, int32_t NE)
+{
+    if (V < 0 || NE < 1 || NE > FR_FLAME_MAX_E) return 0;
+    return flame_workspace_bytes(V, NE);
+}
+
+size_t fr_flame_workspace_zeroed_bytes(void) { return flame_workspace_zeroed_bytes(); }
+
+static const char* flame_invalid(const fr_flame* f, const void* workspace)
+{
+    if (!f || f->V < 0 || f->NS < 0) return "fr_flame: null descriptor, or negative V or NS";
+    if (f->NE < 1 || f->NE > FR_FLAME_MAX_E) return "fr_flame: NE outside 1 .. FR_FLAME_MAX_E";
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u)) return "fr_flame: null workspace, or one that is not 16-byte aligned";
+    if (!f->parents || !f->expression || !f->pose) return "fr_flame: null parents, expression or pose";
+    if (f->V > 0 && (!f->v_template || !f->shapedirs || !f->posedirs || !f->J_regressor || !f->lbs_weights))
+        return "fr_flame: null model array";
+    return nullptr;
+}
+
+int fr_flame_forward(const fr_flame* flame, float* verts, float* verts_orig, float* pose_feature, float* transforms, void* workspace,
+                     void* stream)
+{
+    if (const char* why = flame_invalid(flame, workspace)) return fail_msg(FR_ERR_INVALID_ARGUMENT, why);
+    if (flame->V > 0 && !verts) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_flame_forward: null verts");
+    return launch_flame_forward(*flame, verts, verts_orig, pose_feature, transforms, workspace, static_cast<hipStream_t>(stream));
+}
+
+int fr_flame_backward(const fr_flame* flame, const float* g_verts, float* d_delta_exp, float* d_delta_posedirs, float* d_delta_vertex,
+                      float* d_expression, float* d_pose, void* workspace, void* stream)
+{
+    if (const char* why = flame_invalid(flame, workspace)) return fail_msg(FR_ERR_INVALID_ARGUMENT, why);
+    if (flame->V > 0 && !g_verts) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_flame_backward: null g_verts");
+    return launch_flame_backward(*flame, g_verts, d_delta_exp, d_delta_posedirs, d_delta_vertex, d_expression, d_pose, workspace,
+                                 static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

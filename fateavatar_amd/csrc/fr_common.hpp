@@ -561,6 +561,13 @@ int launch_lbs_terms(const fr_lbs_terms_config& cfg, int N, int V, int E, int J,
 size_t mlp_workspace_bytes(int N, int L);
 int launch_mlp_forward(const fr_mlp& m, float* out, void* workspace, hipStream_t s);
 int launch_mlp_backward(const fr_mlp& m, const float* d_out, float* d_weights, float* d_cond, void* workspace, hipStream_t s);
+// FLAME's linear blend skinning with FateAvatar's deltas (fr_flame.hip)
+size_t flame_workspace_bytes(int V, int NE);
+size_t flame_workspace_zeroed_bytes();
+int launch_flame_forward(const fr_flame& f, float* verts, float* verts_orig, float* pose_feature, float* transforms, void* workspace,
+                         hipStream_t s);
+int launch_flame_backward(const fr_flame& f, const float* g_verts, float* d_delta_exp, float* d_delta_posedirs, float* d_delta_vertex,
+                          float* d_expression, float* d_pose, void* workspace, hipStream_t s);
 int launch_multi_copy(int n_seg, float* const* dst, const float* const* src, const unsigned long long* count, hipStream_t s);
 int launch_selftest_reduce(const float* in, float* out, hipStream_t s);
 

@@ -907,6 +907,57 @@ size_t fr_mlp_workspace_bytes(int32_t N, int32_t L);
 int fr_mlp_forward(const fr_mlp* mlp, float* out, void* workspace, void* hip_stream);
 int fr_mlp_backward(const fr_mlp* mlp, const float* d_out, float* d_weights, float* d_cond, void* workspace, void* hip_stream);
 
+/* ---- FLAME's linear blend skinning with FateAvatar's personalised deltas, for ONE frame (reference:
+ * FLAME.forward_with_delta_blendshape, flame/FLAME.py:156-204, over lbs(), flame/lbs.py:24-101; the caller is
+ * model/fateavatar.py:212-223 with the `bs` optimizer group of train/optim.py:27-33).  V vertices, NS shape and NE expression
+ * columns (L = NS + NE), FR_FLAME_JOINTS joints with parents[i] < i (parents[0] is not read), FR_FLAME_POSE_FEATURES pose
+ * features:
+ *   v_shaped = (v_template + delta_vertex) + (shapedirs[:, :, NS:] + delta_exp) expression
+ *   Jnt      = J_regressor v_shaped
+ *   R_j      = batch_rodrigues(pose[3j : 3j + 3])         (angle = |r + 1e-8|, dir = r / angle, as the reference)
+ *   phi      = (R_1 .. R_4 - I).flatten()
+ *   v_posed  = v_shaped + phi (posedirs + delta_posedirs)
+ *   A        = batch_rigid_transform(R, Jnt, parents)
+ *   verts    = (sum_j w_vj A_j) (v_posed, 1)
+ * The reference multiplies the NS shape columns by exact zeros: they are not read, their gradient is exactly 0, and the trained
+ * part of `delta_shapedirs` [V,3,L] is its expression slice `delta_exp` [V,3,NE] alone.  Any of the three deltas may be NULL:
+ * zeros.  fr_flame_forward writes `verts` [V,3], `pose_feature` [36] and `transforms` [5,16] (row-major 4x4, last rows
+ * (0,0,0,1); these two may be NULL) and, if `verts_orig` is not NULL, the mesh WITHOUT the deltas (joint sums of its own) there.
+ * fr_flame_backward (after a forward with the same descriptor and workspace) takes g_verts [V,3] = dLoss/dverts and writes
+ * EVERY element of d_delta_exp [V,3,NE], d_delta_posedirs [36,3V], d_delta_vertex [V,3], d_expression [NE] and d_pose [15]
+ * (stored, not accumulated); any of them may be NULL, and what the others receive does not depend on which are.
+ * Two launches per call.  The sums over the vertices (the joints; d_A, d_phi; d_expression) are per-workgroup partials added up
+ * in workgroup-index order by the workgroup that finishes last: no float atomics, the same bits on every launch and every graph
+ * replay.  Nothing allocates or synchronises; both calls can be captured.  V == 0 launches nothing.  NE outside
+ * 1 .. FR_FLAME_MAX_E, negative V or NS, a NULL required pointer or a NULL / misaligned workspace is FR_ERR_INVALID_ARGUMENT.
+ * Inputs are assumed finite.
+ * `workspace`: fr_flame_workspace_bytes(V, NE) bytes, 16-byte aligned, not shared by launches that can overlap.  Its first
+ * fr_flame_workspace_zeroed_bytes() bytes (counters and partials) are zeroed ONCE by the caller and left zeroed by every call;
+ * the rest is the frame's state (phi, A, the chain, v_posed, d_v_posed), which a forward overwrites and the backward reads. */
+#define FR_FLAME_MAX_E 128
+#define FR_FLAME_JOINTS 5
+#define FR_FLAME_POSE_FEATURES 36
+typedef struct fr_flame {
+    int32_t V, NS, NE;
+    const int32_t* parents;      /* [5], device */
+    const float* v_template;     /* [V,3] */
+    const float* shapedirs;      /* [V,3,NS+NE] */
+    const float* posedirs;       /* [36,3V] */
+    const float* J_regressor;    /* [5,V] */
+    const float* lbs_weights;    /* [V,5] */
+    const float* delta_exp;      /* [V,3,NE] or NULL */
+    const float* delta_posedirs; /* [36,3V] or NULL */
+    const float* delta_vertex;   /* [V,3] or NULL */
+    const float* expression;     /* [NE] */
+    const float* pose;           /* [15] */
+} fr_flame;
+size_t fr_flame_workspace_bytes(int32_t V, int32_t NE);
+size_t fr_flame_workspace_zeroed_bytes(void);
+int fr_flame_forward(const fr_flame* flame, float* verts, float* verts_orig, float* pose_feature, float* transforms,
+                     void* workspace, void* hip_stream);
+int fr_flame_backward(const fr_flame* flame, const float* g_verts, float* d_delta_exp, float* d_delta_posedirs,
+                      float* d_delta_vertex, float* d_expression, float* d_pose, void* workspace, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,15 @@ torch `delta_vertex` leaf [V,3] is added to the template in front of the sequenc
 torch.optim.Adam through `step.d_verts` (the step's dLoss/dposed_verts, the reference's mesh terms already in it; `verts_orig`
 is the undisplaced posed mesh).  Prints steps/s, the image loss, both mesh terms and |delta - bump| at start and end.
 --vertex-grad alone: the plain loop with the vertex gradient switched on (what that option costs).
+    python tools/train_synthetic.py --fateavatar --fused-flame [--flame-shape 100 --flame-exp 50 --mesh-terms LAP FLAME]
+    python tools/train_synthetic.py --fateavatar --torch-flame [...]
+FateAvatar's WHOLE iteration: a synthetic FLAME over the (centred) template (fateavatar_amd/flame.py: `synthetic_flame`), per
+frame an expression and a pose, targets from the mesh with a seeded smooth bump as the true `delta_vertex`.  --fused-flame:
+`AvatarStep(flame=FlameMesh, mesh_terms=...)` — FLAME forward (both meshes), frame, mesh terms, FLAME backward and both Adams in
+ONE replayed graph.  --torch-flame: the A/B, the same loop with FLAME as the stock-PyTorch restatement (tests/flame_ref.py: needs
+the checkout's tests/ next to tools/) run twice in front of the step, `posed.backward(step.d_verts)` and torch.optim.Adam over the
+reference's three groups (delta_shapedirs at its full [V,3,L]).  Prints steps/s, the image loss, both mesh terms and
+|delta_vertex - bump| at start and end.
     python tools/train_synthetic.py --fateavatar --track-camera [--track-offset 0.005]
 FateAvatar's step with the reference's camera tracking next to it (train/base.py:123,142: one translation per frame in an
 embedding, at `tracking_lr`): every frame's camera translation is a torch leaf that starts --track-offset metres (RMS per axis)
@@ -114,6 +123,14 @@ def main():
     ap.add_argument("--mesh-terms", type=float, nargs=2, default=None, metavar=("LAP", "FLAME"),
                     help="--train-mesh: weights of the Laplacian and FLAME-distance terms (default: the reference's 1e5 0)")
     ap.add_argument("--mesh-lr", type=float, default=1e-4, help="--train-mesh: Adam rate of delta_vertex (train/optim.py:30)")
+    ap.add_argument("--fused-flame", action="store_true",
+                    help="--fateavatar: FLAME and its learnt deltas inside the captured step (AvatarStep(flame=FlameMesh), "
+                         "fr_flame_forward / _backward and a second fused Adam), with the mesh terms")
+    ap.add_argument("--torch-flame", action="store_true",
+                    help="--fateavatar: the A/B of --fused-flame: the same loop with FLAME in stock PyTorch (tests/flame_ref.py) around "
+                         "the step and torch.optim.Adam over the three deltas")
+    ap.add_argument("--flame-shape", type=int, default=100, help="--fused-flame / --torch-flame: shape columns of the synthetic FLAME")
+    ap.add_argument("--flame-exp", type=int, default=50, help="--fused-flame / --torch-flame: expression columns (1 .. 128)")
     ap.add_argument("--track-camera", action="store_true",
                     help="--fateavatar: train a per-frame camera translation leaf through AvatarStep(camera_grad=True)")
     ap.add_argument("--track-offset", type=float, default=0.005, help="--track-camera: RMS start error of the translations, per axis (m)")
@@ -191,6 +208,10 @@ def main():
         raise SystemExit("--mouth-mask and --fused-mlp go with --flash")
     if (a.train_mesh or a.vertex_grad or a.mesh_terms or a.track_camera) and not (a.fateavatar and a.views_per_step == 1):
         raise SystemExit("--train-mesh / --vertex-grad / --mesh-terms / --track-camera go with --fateavatar at one frame per step")
+    if a.fused_flame or a.torch_flame:
+        if not (a.fateavatar and a.views_per_step == 1) or (a.fused_flame and a.torch_flame) or a.train_mesh or a.track_camera:
+            raise SystemExit("--fused-flame / --torch-flame: one of the two, with --fateavatar at one frame per step, without "
+                             "--train-mesh / --track-camera")
     if a.track_mesh and not a.splatting:
         raise SystemExit("--track-mesh goes with --splatting")
     if a.fateavatar:
@@ -364,6 +385,100 @@ def main_train_mesh(a, rank, world, dev):
                       "mesh_lr": a.mesh_lr, "bump_norm": round(float(bump_t.norm()), 6), "first": first, "last": report()}))
 
 
+def main_flame(a, rank, world, dev):
+    """FateAvatar's whole iteration — the Gaussians AND the FLAME mesh under them with its three learnt deltas — with FLAME inside
+    the captured step (--fused-flame) or as stock PyTorch around it (--torch-flame)."""
+    if world > 1:
+        raise SystemExit("--fused-flame / --torch-flame: one GPU (DESIGN.md)")
+    from fateavatar_amd import flame
+    from fateavatar_amd.avatar import AvatarGaussians, AvatarStep, _BoundFrame
+    from fateavatar_amd.binding import bind_gaussians
+    from fateavatar_amd.loss import MeshTerms, REFERENCE_MESH_TERMS
+    terms = MeshTerms(*a.mesh_terms) if a.mesh_terms else REFERENCE_MESH_TERMS
+    verts0, faces, _ = scenes.head_geometry()
+    bump = smooth_bump(np.asarray(verts0, dtype=np.float32))
+    verts = (verts0 - verts0.mean(0)).astype(np.float32)          # FLAME's own template sits at the origin
+    n_frames = max(a.views, 8)
+    fm = flame.synthetic_flame(verts, seed=0, n_shape=a.flame_shape, n_exp=a.flame_exp, device=dev)
+    g = torch.Generator().manual_seed(3)
+    frames = [flame.FlameFrame((0.5 * torch.randn(fm.n_exp, generator=g)).to(dev), (0.1 * torch.randn(15, generator=g)).to(dev))
+              for _ in range(n_frames)]
+    rng = np.random.default_rng(0)
+    cams = []
+    for _ in range(n_frames):
+        eye = np.array([0.25 * rng.uniform(-1, 1), 0.15 * rng.uniform(-1, 1), 0.8 + 0.1 * rng.uniform(-1, 1)], np.float32)
+        cams.append(TorchCamera(scenes.look_at_camera(eye, np.zeros(3), (0, 1, 0), 0.5, 0.5, a.res, a.res), dev))
+    pc = AvatarGaussians.from_template(dev, num_points=a.P, sampling="random" if a.random_order else "uv", rng=np.random.default_rng(0))
+    faces_t, canon, bg = torch.from_numpy(faces).to(dev), torch.from_numpy(verts).to(dev), torch.ones(3, device=dev)
+    bump_t = torch.from_numpy(bump).to(dev)
+    tables = (fm.v_template, fm.shapedirs, fm.posedirs, fm.J_regressor, fm.parents.cpu(), fm.lbs_weights, fm.n_shape)
+    # hidden ground truth: same binding, other appearance, on the mesh whose delta_vertex is the bump
+    gt = AvatarGaussians(pc.face_index.cpu().numpy(), pc.bary_coords.cpu().numpy(), float(pc._scaling.detach()[0, 0]), dev)
+    with torch.no_grad():
+        gt._features_dc.copy_((torch.rand(gt.P, 1, 3, generator=g) * 2.0 - 1.0).to(dev))
+        gt._opacity.fill_(float(np.log(0.6 / 0.4)))
+        gt._offset.copy_((0.3 * torch.randn(gt.P, 1, generator=g)).to(dev))
+    ref = AvatarStep(gt, faces_t, canon, cams[0].clone(), bg, use_graph=False)
+    gts = []
+    # (the targets are posed by the restatement in both modes, so that both train on the same images)
+    from tests import flame_ref
+    with torch.no_grad():
+        for f in range(n_frames):
+            shown = flame_ref.lbs(frames[f].expression, frames[f].pose, *tables, None, None, bump_t)[0].contiguous()
+            xyz, rot, scl = bind_gaussians(shown, ref.faces, gt.face_index, gt.bary_coords, ref.face_scale_canonical, gt._offset,
+                                           gt._rotation, gt._scaling, ref.shell_len, True)
+            gts.append(render(cams[f], _BoundFrame(xyz, gt, rot, scl, None), bg)["render"].clone())
+    common = dict(use_graph=not a.no_graph, fold_binding=not a.binding_op, mesh_terms=terms)
+    if a.fused_flame:
+        st = AvatarStep(pc, faces_t, canon, cams[0].clone(), bg, flame=fm, **common)
+        delta_vertex = lambda: fm.delta_vertex  # noqa: E731
+
+        def one_step(it):
+            f = it % n_frames
+            st.step(cams[f], frames[f], gts[f])
+    else:
+        st = AvatarStep(pc, faces_t, canon, cams[0].clone(), bg, **common)
+        sd = fm.state_dict()
+        leaves = [sd[k].clone().requires_grad_(True) for k in flame.DELTA_KEYS]      # delta_shapedirs at its full [V,3,L]
+        lrs = flame.REFERENCE_FLAME_LRS
+        opt = torch.optim.Adam([{"params": [t], "lr": lrs[k]} for t, k in zip(leaves, flame.DELTA_KEYS)], lr=0.0)   # train/optim.py:27-33
+        delta_vertex = lambda: leaves[2].detach()  # noqa: E731
+
+        def one_step(it):
+            f = it % n_frames
+            opt.zero_grad(set_to_none=True)
+            posed = flame_ref.lbs(frames[f].expression, frames[f].pose, *tables, *leaves)[0]     # model/fateavatar.py:212-218
+            with torch.no_grad():
+                orig = flame_ref.lbs(frames[f].expression, frames[f].pose, *tables)[0]           # :220-223
+            st.step(cams[f], posed, gts[f], verts_orig=orig)
+            posed.backward(st.d_verts)
+            opt.step()
+
+    def report():
+        torch.cuda.synchronize()
+        return dict(image_loss=round(float(st.loss), 6), laplacian_loss=float(st.mesh_loss[0]), flame_loss=float(st.mesh_loss[1]),
+                    delta_minus_bump=round(float((delta_vertex() - bump_t).norm()), 6))
+
+    warm = 10
+    one_step(0)
+    first = report()
+    for it in range(1, warm):
+        one_step(it)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(warm, warm + a.steps):
+        one_step(it)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    st.check()
+    how = "FLAME and both Adams inside the captured step" if a.fused_flame else "torch FLAME and torch Adam around the fused step"
+    print(json.dumps({"metric": f"FateAvatar optimisation steps/s, Gaussians and FLAME deltas trained ({how})",
+                      "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": a.P, "res": a.res,
+                      "V": fm.V, "n_shape": fm.n_shape, "n_exp": fm.n_exp, "frames": n_frames, "graph": not a.no_graph,
+                      "fused_flame": bool(a.fused_flame), "overflows": st.overflows, "mesh_terms": list(terms),
+                      "bump_norm": round(float(bump_t.norm()), 6), "first": first, "last": report()}))
+
+
 def main_track_camera(a, rank, world, dev):
     """The demonstration of `step.d_view / d_proj / d_campos`: FateAvatar's Gaussians by the fused step, every frame's camera
     translation by the caller's own Adam (the reference's `train_cam_pose` embedding, which its rasterizer never moves)."""
@@ -421,6 +536,8 @@ def main_fateavatar(a, rank, world, dev):
         return main_track_camera(a, rank, world, dev)
     if a.train_mesh:
         return main_train_mesh(a, rank, world, dev)
+    if a.fused_flame or a.torch_flame:
+        return main_flame(a, rank, world, dev)
     mesh_terms = moved = None
     if a.mesh_terms:       # the mesh terms in the plain loop (what the launch costs): a fixed displaced mesh held to the posed one
         from fateavatar_amd.loss import MeshTerms
