@@ -2,9 +2,12 @@
 (FR_BIND_DEFORM) and the Huber launch are tested against.
 
 reference: model/baseline/flashavatar.py:242-276 (`forward`), :380-390 (`quatProduct_batch`), train/loss.py:217-221, :231-239
-(`get_huber_loss`, the mouth term).  Written from the arithmetic, not from the reference's program text, which cannot be
-imported here (it needs pytorch3d); tests/test_flash_host.py pins it by hand cases, by gradcheck and by the written backward
-formulas."""
+(`get_huber_loss`, the mouth term).  Written from the arithmetic, not from the reference's program text;
+tests/test_flash_host.py pins it by hand cases, by gradcheck and by the written backward formulas, and
+tests/test_reference_runs_host.py pins `huber_loss` and `quat_product` to recorded runs of the reference's own
+`FlashAvatarLoss.accumulate_gradients` and `FlashAvatar.quatProduct_batch` (tests/golden/reference_image_terms.npz cases
+`huber_plain` / `huber_mouth`, tests/golden/reference_mlp*.npz case `quat`; the module imports with stand-ins for pytorch3d).
+`deform_bind` stays builder-pinned: `forward` runs the CUDA rasterizer."""
 import torch
 
 ALPHA, MASK_WEIGHT = 0.1, 40.0

@@ -1,13 +1,16 @@
 """A torch restatement of the L1 + D-SSIM image loss, written from its formulas (not from the library's code):
 
-    window  w = g g^T, g = the 11 taps exp(-(i - 5)^2 / (2 x 1.5^2)) rounded to float32, divided by their float32 sum
+    window  w = g g^T rounded to float32, g = the 11 taps exp(-(i - 5)^2 / (2 x 1.5^2)) rounded to float32, divided by their
+            float32 sum
     conv    = correlation with w per channel, zero padding 5
     mu1 = conv(x), mu2 = conv(y), s11 = conv(x x) - mu1^2, s22 = conv(y y) - mu2^2, s12 = conv(x y) - mu1 mu2
     S = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2)),  C1 = 1e-4, C2 = 9e-4
     d_ssim = 1 - mean(S),  l1 = mean |x - y|,  loss = rgb_weight l1 + dssim_weight d_ssim
 
 evaluated in float64 (the reference of the tests) or in float32 (the yardstick for what float32 arithmetic reaches on the
-same inputs), the gradients with respect to x from autograd.  CPU only; results are cached per input."""
+same inputs), the gradients with respect to x from autograd.  CPU only; results are cached per input.
+`d_ssim_of` is pinned to recorded runs of the reference's own `d_ssim` (tools/loss_utils/dssim.py) by
+tests/test_reference_runs_host.py (tests/golden/reference_image_terms.npz, cases `dssim_*` and `ga`)."""
 import functools
 from math import exp
 
@@ -34,8 +37,11 @@ def window_taps() -> torch.Tensor:
 def d_ssim_of(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """1 - mean SSIM map of [C,H,W] images in their own dtype (differentiable)."""
     C = x.shape[0]
-    g = window_taps().to(x.dtype)
-    w = (g[:, None] * g[None, :]).expand(C, 1, 11, 11).contiguous()
+    g = window_taps()
+    # the 121 products are rounded to float32 BEFORE the window takes the images' dtype (`create_window` multiplies the taps in
+    # float32, `d_ssim` casts the result): in float64 the float64 products of the taps are another window, 2e-6 of d_ssim away
+    # from the recorded run (tests/golden/reference_image_terms.npz, tests/test_reference_runs_host.py)
+    w = (g[:, None] * g[None, :]).to(x.dtype).expand(C, 1, 11, 11).contiguous()
     conv = lambda t: F.conv2d(t[None], w, padding=5, groups=C)[0]  # noqa: E731
     mu1, mu2 = conv(x), conv(y)
     s11, s22, s12 = conv(x * x) - mu1 * mu1, conv(y * y) - mu2 * mu2, conv(x * y) - mu1 * mu2

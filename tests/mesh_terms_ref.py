@@ -5,7 +5,10 @@ the kernel tests are held to, float32 what the step tests add to the image term)
     the edges are the unique undirected pairs {a, b}, a != b, among the faces' sides; L[i,j] = 1 / deg(i) for a neighbour j,
     L[i,i] = -1 for EVERY vertex.  pytorch3d is not installed here: the rule is pinned by the hand-written matrices of
     tests/test_mesh_terms_host.py, not by a run of pytorch3d.
-  * `laplacian_smoothing`, `flame_distance` — the expressions of FateAvatarLoss (train/loss.py:112-121, :192-197).
+  * `laplacian_smoothing`, `flame_distance` — the expressions of FateAvatarLoss (train/loss.py:112-121, :192-197), pinned by
+    tests/test_reference_runs_host.py to recorded runs of the class's own `get_laplacian_smoothing_loss` and
+    `accumulate_gradients` with `laplacian_matrix` preset to `laplacian_dense` (tests/golden/reference_image_terms.npz, case
+    `fate`): what the reference does WITH the matrix is recorded, the matrix rule is not.
   * what the GPU tests need around them: float64 values / gradients / rounding magnitudes, and the seeded inputs;
   * `float64_terms_sparse` — the same dictionary from gathers and `index_add_` over the edge list, for meshes whose V x V matrix
     does not fit (pinned to `float64_terms` by tests/test_mesh_terms_host.py), and `random_mesh_drawn_at_once` for such meshes."""

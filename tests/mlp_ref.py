@@ -1,6 +1,8 @@
 """The torch restatement of FlashAvatar's point embedding and deformation MLP (model/baseline/flashavatar.py:396-464, fed as in
 :238-240): the reference of every comparison in tests/test_mlp_host.py and tests/test_gpu_mlp.py.  It runs in whatever dtype its
-inputs have (float64 for the ground truth, float32 on the CPU for the measured error bound)."""
+inputs have (float64 for the ground truth, float32 on the CPU for the measured error bound).  `embed` and `run` are pinned to
+recorded runs of the reference's own `Embedder(8)` and `MLP(110, 10, 256, 2)` by tests/test_reference_runs_host.py
+(tests/golden/reference_mlp*.npz, cases `embed` and `mlp`)."""
 import torch
 
 

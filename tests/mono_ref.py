@@ -1,6 +1,11 @@
 """MonoGaussianAvatar's per-point arithmetic restated in plain torch (any dtype, any device): the yardstick of
 fateavatar_amd/mono.py's fused calls.  Written from the arithmetic of include/fr_rasterizer.h (fr_point_lbs, fr_nearest_vertex,
-fr_lbs_terms), with torch.inverse and einsums where the kernels have closed forms; differentiable by autograd."""
+fr_lbs_terms), with torch.inverse and einsums where the kernels have closed forms; differentiable by autograd.
+Pinned to the reference's own Python by tests/test_reference_runs_host.py: `deform_points` (with its seven gradients, the frame's
+pose state included) to recorded runs of `FLAME.forward_pts` over flame/lbs.py's `inverse_pts` / `forward_pts`
+(tests/golden/reference_skinning.npz), `lbs_terms` times `fateavatar_amd.mono.reference_lbs_weights` to
+`MonoGaussianAvatarLoss.accumulate_gradients` with and without a `var_expression` (tests/golden/reference_mono_terms*.npz).
+`nearest_vertex` stays builder-pinned (pytorch3d's knn_points is absent)."""
 from __future__ import annotations
 
 import math

@@ -7,6 +7,9 @@ reference:
   * `binding_counter` — gaussianavatars.py:66-69
   * `_densify_and_prune` :278-295, `_clone_densify` :297-351, `_split_densify` :353-416, `_prune` :418-460,
     `_densification_postfix` :462-475, `_reset_opacity` :477-495; `build_rotation` tools/gs_utils/general_utils.py:78-99
+The regularisers are pinned to a recorded run of `GaussianAvatarsLoss.accumulate_gradients` itself (the full loss, with the
+D-SSIM image term) by tests/test_reference_runs_host.py (tests/golden/reference_image_terms.npz, case `ga`); the density-control
+surgery stays builder-pinned (it needs a live optimiser and a rasterized frame).
 `max_radii2D` is left out: `_densification_postfix` zeroes it in clone and in split immediately before the only test that
 reads it (:289), so that test never fires."""
 import torch

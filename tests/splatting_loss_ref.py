@@ -3,8 +3,10 @@ on hand-computed cases by tests/test_splatting_loss_host.py.
 
 reference: `SplattingAvatarLoss` (train/loss.py:259-323) — `get_rgb_loss` / `get_mse_loss` (:279-283: nn.L1Loss and nn.MSELoss,
 reduction 'mean') and the scale term of `accumulate_gradients` (:307-315) on `model_outputs['scale']` = exp(_scaling)
-(model/baseline/splattingavatar.py:270), with the weights and gates of config/splattingavatar.yaml:13-20.  The class itself
-cannot be imported (its constructor builds lpips.LPIPS): this is a restatement, written anew."""
+(model/baseline/splattingavatar.py:270), with the weights and gates of config/splattingavatar.yaml:13-20.  A restatement, written
+anew — and pinned to the class itself: `SplattingAvatarLoss.accumulate_gradients` (made without its constructor, which builds
+lpips.LPIPS) was run on recorded inputs, and tests/test_reference_runs_host.py holds `pixel_terms`, `scale_term` and `REFERENCE`
+to its float64 results and `Params` (tests/golden/reference_image_terms.npz, case `splat`)."""
 import math
 
 import torch

@@ -126,15 +126,23 @@ def test_steps_take_the_image_loss_argument():
 def test_restatement_agrees_with_the_closed_form_gradient(kind):
     """The reference of the GPU tests pinned on the CPU: float64 autograd of the restatement against the closed form
         d d_ssim / dx = -(1/N) [conv(dM) + 2 x conv(dS11) + y conv(dS12)]
-    written out with separable 1-D convolutions (another evaluation order than the restatement's 2-D window)."""
+    written out with the window applied as 121 shifted, weighted copies of the padded map (another evaluation than the
+    restatement's conv2d).  The window is the reference's: the taps' products ROUNDED TO float32 (`create_window` multiplies in
+    float32), which a separable pair of float64 1-D passes is not — that form, which this test used before the restatement was
+    held to a recorded run of the reference's d_ssim, is 5.6e-9 of d_ssim away."""
     import torch.nn.functional as F
     x, y, t64, t32 = ref.case((3, 33, 47), kind)
     l1, ds, g1, gs = t64
     X, Y = x.double(), y.double()
-    g = ref.window_taps().double()
-    Cn = X.shape[0]
-    kh, kv = g.view(1, 1, 1, 11).expand(Cn, 1, 1, 11).contiguous(), g.view(1, 1, 11, 1).expand(Cn, 1, 11, 1).contiguous()
-    conv = lambda t: F.conv2d(F.conv2d(t[None], kh, padding=(0, 5), groups=Cn), kv, padding=(5, 0), groups=Cn)[0]  # noqa: E731
+    g = ref.window_taps()
+    w2 = (g[:, None] * g[None, :]).double()            # float32 products, then the images' dtype
+    assert w2.dtype == torch.float64 and torch.equal(w2, w2.float().double()) and torch.equal(w2, w2.T)
+    H, W = X.shape[1:]
+
+    def conv(t):
+        p = F.pad(t, (5, 5, 5, 5))
+        return sum(w2[i, j] * p[:, i:i + H, j:j + W] for i in range(11) for j in range(11))
+
     mu1, mu2 = conv(X), conv(Y)
     s11, s22, s12 = conv(X * X) - mu1 ** 2, conv(Y * Y) - mu2 ** 2, conv(X * Y) - mu1 * mu2
     A, B, Cc, D = 2 * mu1 * mu2 + ref.C1, 2 * s12 + ref.C2, mu1 ** 2 + mu2 ** 2 + ref.C1, s11 + s22 + ref.C2
