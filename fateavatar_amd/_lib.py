@@ -148,6 +148,23 @@ class fr_flame(C.Structure):
                 ("pose", C.c_void_p)]
 
 
+FR_VGG_MAX_LAYERS = 16
+FR_VGG_LOSS_BLOCKS = 1024
+FR_VGG_REDUCE_BYTES = (16 + 1) * 32 * 4 + FR_VGG_LOSS_BLOCKS * 4
+FR_VGG_TILE_AUTO, FR_VGG_TILE_64, FR_VGG_TILE_128 = 0, 1, 2
+FR_VGG_NO_SPLIT = 4
+
+
+class fr_vgg_layer(C.Structure):
+    _fields_ = [("c_in", C.c_int32), ("c_out", C.c_int32), ("pool_before", C.c_int32), ("tap_after", C.c_int32)]
+
+
+class fr_vgg(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("size_h", C.c_int32), ("size_w", C.c_int32),
+                ("tile", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("layers", fr_vgg_layer * FR_VGG_MAX_LAYERS),
+                ("weights_fwd", C.c_void_p), ("weights_bwd", C.c_void_p), ("image", C.c_void_p), ("target", C.c_void_p)]
+
+
 class fr_image_loss_config(C.Structure):
     _fields_ = [("rgb_weight", C.c_float), ("dssim_weight", C.c_float)]
 
@@ -185,7 +202,8 @@ EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile
            "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_bind_backward_deform", "fr_phong_frame", "fr_bind_backward_phong_frame", "fr_phong_frame_backward_workspace_bytes", "fr_phong_frame_backward", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward",
            "fr_point_lbs_forward", "fr_point_lbs_backward", "fr_point_lbs_pose_workspace_bytes", "fr_point_lbs_backward_pose", "fr_nearest_vertex", "fr_lbs_terms_workspace_bytes", "fr_lbs_terms",
            "fr_mlp_workspace_bytes", "fr_mlp_forward", "fr_mlp_backward",
-           "fr_flame_workspace_bytes", "fr_flame_workspace_zeroed_bytes", "fr_flame_forward", "fr_flame_backward"]
+           "fr_flame_workspace_bytes", "fr_flame_workspace_zeroed_bytes", "fr_flame_forward", "fr_flame_backward",
+           "fr_vgg_workspace_bytes", "fr_vgg_loss_grad"]
 
 
 def build(force: bool = False) -> str:
@@ -362,6 +380,10 @@ def lib():
     L.fr_flame_forward.restype = C.c_int
     L.fr_flame_backward.argtypes = [C.POINTER(fr_flame), _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
     L.fr_flame_backward.restype = C.c_int
+    L.fr_vgg_workspace_bytes.argtypes = [C.POINTER(fr_vgg)]
+    L.fr_vgg_workspace_bytes.restype = C.c_size_t
+    L.fr_vgg_loss_grad.argtypes = [C.POINTER(fr_vgg), C.c_float, C.c_int, _fp, _fp, C.c_void_p, C.c_void_p]
+    L.fr_vgg_loss_grad.restype = C.c_int
     L.fr_ssim_window.argtypes = [C.POINTER(C.c_float)]
     L.fr_ssim_window.restype = None
     L.fr_image_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

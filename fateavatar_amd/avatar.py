@@ -30,6 +30,7 @@ from .flame import REFERENCE_FLAME_LRS, FlameFrame, FlameMesh
 from .flat import FlatParams
 from .model import TorchCamera
 from .optim import FusedAdam
+from .perceptual import Perceptual
 from .render import render
 from .loss import MeshTerms, l1_loss_and_grad, l1_workspace, mesh_terms_and_grad, mesh_terms_workspace
 from .train import BoundStep, TrainStep
@@ -130,7 +131,7 @@ class AvatarStep(BoundStep):
                  bg: torch.Tensor, lrs: Optional[dict] = None, shell_len: float = 0.05, resize_scale: bool = True,
                  use_graph: bool = True, fold_binding: bool = True, keep_coherent: bool = False, vertex_grad: bool = False,
                  mesh_terms: Optional[MeshTerms] = None, camera_grad: bool = False, flame: Optional[FlameMesh] = None,
-                 flame_lrs: Optional[dict] = None):
+                 flame_lrs: Optional[dict] = None, perceptual: Optional[Perceptual] = None):
         """`keep_coherent`: after every `uv_densify` the rows are re-stored in a spatially coherent order (`sort_coherent`):
         the reference appends the new rows at the end (model/fateavatar.py:640-665), so a set that started in UV-raster
         order (mesh_sampling.py:86-138: neighbours in storage are neighbours on the mesh) grows an unordered tail; the
@@ -156,8 +157,19 @@ class AvatarStep(BoundStep):
         with the three groups of train/optim.py:27-33 at `flame_lrs` (default REFERENCE_FLAME_LRS: 1e-5, 1e-5, 1e-4), skipped by
         the same overflow word.  `d_expression` [n_exp] and `d_pose` [15] hold THIS step's dLoss/d(expression, pose) — what the
         reference's tracking optimisation (tracking_lr) trains on — with the lifetime rules of `d_verts`.  Implies
-        `vertex_grad`.  None (default): the mesh is the caller's, nothing here changes."""
+        `vertex_grad`.  None (default): the mesh is the caller's, nothing here changes.
+        `perceptual`: a `perceptual.Perceptual` adds FateAvatar's VGG term (train/loss.py:123-199, weight 0.1) to every step:
+        ONE call directly behind the L1 launch (csrc/fr_vgg.hip) ADDS weight x its gradient to the L1 gradient in the step's
+        image-gradient buffer, before the rasterizer's backward; `perceptual_loss` [1 + T] then holds the step's unweighted
+        sum of the tap terms and the terms, `loss` stays the L1 term (the reference's total is
+        loss + perceptual.weight * perceptual_loss[0] + ...).  None (default): not one launch changes."""
         self.keep_coherent = bool(keep_coherent)
+        if perceptual is not None:
+            if not isinstance(perceptual, Perceptual):
+                raise TypeError("AvatarStep: `perceptual` must be a perceptual.Perceptual")
+            if perceptual.features.device != pc.flat.device:
+                raise ValueError("AvatarStep: the perceptual term and the Gaussians live on different devices")
+        self.perceptual = perceptual
         self.mesh_terms = None if mesh_terms is None else MeshTerms(*[float(x) for x in mesh_terms])
         if flame is not None:
             if not isinstance(flame, FlameMesh):
@@ -179,6 +191,8 @@ class AvatarStep(BoundStep):
         if flame is not None:
             self.expression, self.pose = torch.zeros(flame.n_exp, device=self.dev), torch.zeros(15, device=self.dev)
             self.d_expression, self.d_pose = torch.zeros(flame.n_exp, device=self.dev), torch.zeros(15, device=self.dev)
+        # (the term's workspace is its own, allocated with it: outside any capture)
+        self.perceptual_loss = None if perceptual is None else torch.zeros(1 + perceptual.n_terms, device=self.dev)
         self.mesh_loss = self.verts_orig = self.laplacian = self._mesh_ws = None
         if self.mesh_terms is not None:
             from .binding import mesh_laplacian
@@ -231,6 +245,8 @@ class AvatarStep(BoundStep):
             frame = _BoundFrame(xyz, pc, rot, scl, (L.xyz_gradient_accum, L.denom, pc.overflow_word))
             out = render(cam, frame, self.bg)
         _, g = l1_loss_and_grad(out["render"], L.gt, loss_out=L.loss, grad_out=L._dimage, workspace=L._l1_ws)   # see TrainStep
+        if self.perceptual is not None:     # weight x the VGG term's gradient, ADDED to the L1 gradient in place
+            self.perceptual.loss_and_grad(out["render"], L.gt, loss_out=self.perceptual_loss, grad_out=g, accumulate=True)
         out["render"].backward(g)
         self._keep_vertex_grad(verts)
         self._keep_camera_grad(cam)
@@ -389,6 +405,9 @@ class AvatarBatchStep(AvatarStep):
         if kw.get("flame") is not None:
             raise NotImplementedError("AvatarBatchStep: `flame` is not built for the batch step (one FLAME state per step, like "
                                       "`vertex_grad`): use AvatarStep")
+        if kw.get("perceptual") is not None:
+            raise NotImplementedError("AvatarBatchStep: `perceptual` is not built for the batch step (one workspace per lane): "
+                                      "use AvatarStep")
         if kw.get("vertex_grad") or kw.get("mesh_terms") is not None:
             raise NotImplementedError("AvatarBatchStep: `vertex_grad` / `mesh_terms` are not built for the batch step (two step "
                                       "bodies, and its twelve multi_copy segments are used up at K = 4): use AvatarStep")

@@ -882,4 +882,25 @@ int fr_flame_backward(const fr_flame* flame, const float* g_verts, float* d_delt
                                  static_cast<hipStream_t>(stream));
 }
 
+size_t fr_vgg_workspace_bytes(const fr_vgg* vgg) { return vgg_invalid(vgg) ? 0 : vgg_workspace_bytes(*vgg); }
+
+int fr_vgg_loss_grad(const fr_vgg* vgg, float weight, int accumulate, float* loss_out, float* d_image, void* workspace, void* stream)
+{
+    const char* why = vgg_invalid(vgg);
+    if (!why && (!vgg->weights_fwd || !vgg->weights_bwd || !vgg->image || !vgg->target)) why = "null weights, image or target";
+    if (!why && !loss_out) why = "null loss_out";
+    if (!why && !workspace) why = "null workspace";
+    if (!why && (reinterpret_cast<uintptr_t>(workspace) & 255)) why = "the workspace must be 256-byte aligned";
+    if (!why && ((reinterpret_cast<uintptr_t>(vgg->weights_fwd) | reinterpret_cast<uintptr_t>(vgg->weights_bwd)) & 15))
+        why = "the packed weights must be 16-byte aligned";
+    if (!why && ((reinterpret_cast<uintptr_t>(vgg->image) | reinterpret_cast<uintptr_t>(vgg->target) |
+                  reinterpret_cast<uintptr_t>(loss_out) | reinterpret_cast<uintptr_t>(d_image)) & 3))
+        why = "float arrays must be 4-byte aligned";
+    if (why) {
+        snprintf(g_err, sizeof(g_err), "fr_vgg_loss_grad: %s", why);
+        return FR_ERR_INVALID_ARGUMENT;
+    }
+    return launch_vgg_loss_grad(*vgg, weight, accumulate, loss_out, d_image, workspace, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

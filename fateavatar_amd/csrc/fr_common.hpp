@@ -568,6 +568,10 @@ int launch_flame_forward(const fr_flame& f, float* verts, float* verts_orig, flo
                          hipStream_t s);
 int launch_flame_backward(const fr_flame& f, const float* g_verts, float* d_delta_exp, float* d_delta_posedirs, float* d_delta_vertex,
                           float* d_expression, float* d_pose, void* workspace, hipStream_t s);
+// FateAvatar's VGG perceptual term: a conv stack on f32 MFMA (fr_vgg.hip)
+const char* vgg_invalid(const fr_vgg* v);      // nullptr, or why the descriptor is refused
+size_t vgg_workspace_bytes(const fr_vgg& v);
+int launch_vgg_loss_grad(const fr_vgg& v, float weight, int accumulate, float* loss_out, float* d_image, void* workspace, hipStream_t s);
 int launch_multi_copy(int n_seg, float* const* dst, const float* const* src, const unsigned long long* count, hipStream_t s);
 int launch_selftest_reduce(const float* in, float* out, hipStream_t s);
 

@@ -958,6 +958,74 @@ int fr_flame_forward(const fr_flame* flame, float* verts, float* verts_orig, flo
 int fr_flame_backward(const fr_flame* flame, const float* g_verts, float* d_delta_exp, float* d_delta_posedirs,
                       float* d_delta_vertex, float* d_expression, float* d_pose, void* workspace, void* hip_stream);
 
+/* ---- FateAvatar's VGG perceptual term (reference: VGGPerceptualLoss.forward, tools/loss_utils/vgg_feature.py:24-47, at
+ * weight 0.1 in train/loss.py): a frozen stack of 3 x 3 convolutions run on the rendered image and on its target, and the
+ * mean absolute difference of chosen layer outputs, with the gradient to the rendered image.  The stack is a descriptor, not
+ * VGG-16 hard-wired: n_layers <= FR_VGG_MAX_LAYERS layers, each conv3x3(c_in -> c_out, padding 1) + bias + ReLU with
+ *   pool_before  a 2 x 2 / stride 2 max-pool on the layer's input (not on layer 0),
+ *   tap_after    the layer's output is a feature the loss compares (the LAST layer must be one: nothing else reaches it).
+ * Layer 0 has c_in = 3; every later c_in equals the previous c_out and is a multiple of 32; every c_out is a multiple of 64;
+ * size_h and size_w are divisible by 2^(number of pools) and at most 32767.  Anything else is FR_ERR_INVALID_ARGUMENT.
+ *   x      = resize((image - mean) / std),  x_gt = the same of `target`      image, target: [3,H,W] planar, size: size_h x size_w
+ *   a_l    = relu(conv(pool?(a_{l-1}), W_l) + b_l)                            for both images
+ *   term_t = mean |a_l - a_l_gt| over the layer's c_out h_l w_l elements      for the t-th layer with tap_after
+ * The resize is F.interpolate(mode='bilinear', align_corners=False): source coordinate (o + 0.5) in / out - 0.5 clamped at 0,
+ * upper tap clamped at the edge, no antialiasing; size == (H, W) is the exact identity.  The max-pool's gradient goes to the
+ * first maximum of the window in row-major order (torch's rule); sign(0) = 0 in the terms' gradient.
+ * Every activation is NHWC with the two images stacked: row m = (image i, y, x) = i h w + y w + x, channels contiguous; image 0
+ * is the rendered one, image 1 the target.
+ * Weights are packed ONCE by the caller (the network is frozen; fateavatar_amd/perceptual.py does it with torch permutes):
+ *   weights_fwd   per layer, in order: [9 c_in][c_out] with row k = (3 ky + kx) c_in + ci holding W[co, ci, ky, kx], then the
+ *                 bias [c_out]                                         (the GEMM's B operand: K tap-major, channel-minor)
+ *   weights_bwd   per layer, in order: [9 c_out][c_in] with row k = (3 ky + kx) c_out + co holding W[co, ci, 2 - ky, 2 - kx]
+ *                 (taps flipped, c_in / c_out exchanged: the data gradient is the same gathered GEMM over this packing)
+ * fr_vgg_loss_grad writes loss_out[0] = the unweighted sum of the terms and loss_out[1 .. T] = the terms, and, unless d_image
+ * is NULL (forward only), d_image [3,H,W] = weight * dLoss/dimage: stored when `accumulate` is 0, added to what is there when
+ * it is 1.  The products are exact-f32 MFMA (layer 0 and its gradient: plain f32); no float atomics anywhere: the same bits on
+ * every launch and every graph replay.  Nothing allocates or synchronises.
+ * A GEMM of M rows (the pixels: of both images forward, of image 0 in the gradient) and N columns (c_out forward, c_in in the
+ * gradient) whose grid of 64 x 64 tiles is too small for the device is SPLIT over the nine taps into s planes — with
+ * t = ceil(M / 64) ceil(N / 64): s = 1 if t >= 256, else 3 if 3 t >= 256, else 9 — whose partial products a second launch adds
+ * in plane order before the epilogue.  s depends on the shape alone.
+ * `tile`: FR_VGG_TILE_AUTO (the GEMM's tile is the library's choice: 64 x 64), FR_VGG_TILE_64 or FR_VGG_TILE_128 (128 x 64
+ * forced; the results do not depend on the tile, bit for bit), optionally + FR_VGG_NO_SPLIT (no GEMM is split: another
+ * summation order, so other low bits).  For measurement and tests.
+ * `workspace`: fr_vgg_workspace_bytes() bytes (0 for an invalid descriptor), 256-byte aligned, the caller's, not shared by
+ * launches that can overlap.  With r256 = round up to 256 and h_l x w_l layer l's OUTPUT extent, in this order:
+ *     r256(FR_VGG_REDUCE_BYTES)                         counters and partials of the terms' sums: ZERO before the first call,
+ *                                                       left zeroed by every call
+ *   + r256(2 size_h size_w 3 * 4)                       x: the normalised, resized images
+ *   + sum over l of r256(2 h_l w_l c_out_l * 4)         a_l: every layer's post-ReLU output, both images (what the backward's
+ *                                                       masks, argmaxes and signs are read from)
+ *   + r256(max over pooled l of 2 h_l w_l c_in_l * 4)   the pooled input of the layer being computed
+ *   + 2 r256(max over l of h_l w_l c_out_l * 4)         two gradient buffers (image 0 only), used alternately
+ *   + r256(max over pooled l of h_l w_l c_in_l * 4)     a pooled layer's input gradient before it is routed to the argmaxes
+ *   + r256(max over the split GEMMs of s M N * 4)       the planes of the GEMM being computed (layers l >= 1: forward
+ *                                                       M = 2 h_l w_l, N = c_out_l; gradient M = h_l w_l, N = c_in_l)
+ * (152.1 MB for VGG-16 at 224^2.)  `weights_fwd` and `weights_bwd` are 16-byte aligned. */
+#define FR_VGG_MAX_LAYERS 16
+#define FR_VGG_LOSS_BLOCKS 1024
+#define FR_VGG_REDUCE_BYTES ((16 + 1) * 32 * 4 + FR_VGG_LOSS_BLOCKS * 4)
+#define FR_VGG_TILE_AUTO 0
+#define FR_VGG_TILE_64 1
+#define FR_VGG_TILE_128 2
+#define FR_VGG_NO_SPLIT 4
+typedef struct fr_vgg_layer {
+    int32_t c_in, c_out, pool_before, tap_after;
+} fr_vgg_layer;
+typedef struct fr_vgg {
+    int32_t n_layers, H, W, size_h, size_w, tile;
+    float mean[3], std[3];
+    fr_vgg_layer layers[FR_VGG_MAX_LAYERS];
+    const float* weights_fwd; /* packed, as above */
+    const float* weights_bwd;
+    const float* image;       /* [3,H,W] */
+    const float* target;      /* [3,H,W] */
+} fr_vgg;
+size_t fr_vgg_workspace_bytes(const fr_vgg* vgg);
+int fr_vgg_loss_grad(const fr_vgg* vgg, float weight, int accumulate, float* loss_out, float* d_image, void* workspace,
+                     void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,12 @@ ONE replayed graph.  --torch-flame: the A/B, the same loop with FLAME as the sto
 the checkout's tests/ next to tools/) run twice in front of the step, `posed.backward(step.d_verts)` and torch.optim.Adam over the
 reference's three groups (delta_shapedirs at its full [V,3,L]).  Prints steps/s, the image loss, both mesh terms and
 |delta_vertex - bump| at start and end.
+    python tools/train_synthetic.py --fateavatar --perceptual [--fused-flame] [--vgg-weights FILE] [--perceptual-size 224]
+    python tools/train_synthetic.py --fateavatar --torch-perceptual [...]
+FateAvatar's VGG perceptual term at weight 0.1 in the step: `AvatarStep(perceptual=Perceptual(VggFeatures.vgg16()))` — one call
+behind the L1 launch adds its gradient to the L1 gradient (csrc/fr_vgg.hip).  Seeded He-normal weights unless --vgg-weights names
+a torch-saved state dict in torchvision's naming.  --torch-perceptual: the A/B, the same term at the same place through
+F.conv2d and autograd.  The report gains `perceptual_loss` (the sum of the tap terms, then the terms).
     python tools/train_synthetic.py --fateavatar --track-camera [--track-offset 0.005]
 FateAvatar's step with the reference's camera tracking next to it (train/base.py:123,142: one translation per frame in an
 embedding, at `tracking_lr`): every frame's camera translation is a torch leaf that starts --track-offset metres (RMS per axis)
@@ -131,6 +137,16 @@ def main():
                          "the step and torch.optim.Adam over the three deltas")
     ap.add_argument("--flame-shape", type=int, default=100, help="--fused-flame / --torch-flame: shape columns of the synthetic FLAME")
     ap.add_argument("--flame-exp", type=int, default=50, help="--fused-flame / --torch-flame: expression columns (1 .. 128)")
+    ap.add_argument("--perceptual", action="store_true",
+                    help="--fateavatar (plain loop, --fused-flame or --torch-flame): FateAvatar's VGG perceptual term at weight 0.1 inside "
+                         "the step (AvatarStep(perceptual=Perceptual(VggFeatures.vgg16())), csrc/fr_vgg.hip); seeded random weights "
+                         "unless --vgg-weights is given")
+    ap.add_argument("--torch-perceptual", action="store_true",
+                    help="the A/B of --perceptual: the same term at the same place of the same loop through F.conv2d and autograd "
+                         "(the reference's route, tools/loss_utils/vgg_feature.py)")
+    ap.add_argument("--vgg-weights", default=None, metavar="FILE",
+                    help="--perceptual / --torch-perceptual: a torch-saved state dict in torchvision's naming (vgg16().state_dict())")
+    ap.add_argument("--perceptual-size", type=int, default=224, help="what both images are resized to (the reference: 224)")
     ap.add_argument("--track-camera", action="store_true",
                     help="--fateavatar: train a per-frame camera translation leaf through AvatarStep(camera_grad=True)")
     ap.add_argument("--track-offset", type=float, default=0.005, help="--track-camera: RMS start error of the translations, per axis (m)")
@@ -212,6 +228,10 @@ def main():
         if not (a.fateavatar and a.views_per_step == 1) or (a.fused_flame and a.torch_flame) or a.train_mesh or a.track_camera:
             raise SystemExit("--fused-flame / --torch-flame: one of the two, with --fateavatar at one frame per step, without "
                              "--train-mesh / --track-camera")
+    if a.perceptual or a.torch_perceptual:
+        if not (a.fateavatar and a.views_per_step == 1) or (a.perceptual and a.torch_perceptual) or a.train_mesh or a.track_camera:
+            raise SystemExit("--perceptual / --torch-perceptual: one of the two, with --fateavatar at one frame per step, without "
+                             "--train-mesh / --track-camera")
     if a.track_mesh and not a.splatting:
         raise SystemExit("--track-mesh goes with --splatting")
     if a.fateavatar:
@@ -266,8 +286,52 @@ def main():
         torch.distributed.destroy_process_group()
 
 
+def make_perceptual(a, dev):
+    """The step's perceptual term for --perceptual / --torch-perceptual (None without either): VGG-16's stack at weight 0.1 with
+    the caller's weights (--vgg-weights) or seeded He-normal ones; --torch-perceptual: the same object with its one call
+    replaced by the reference's route — stock convolutions and autograd — so that both variants sit at the same place of the
+    same step."""
+    if not (a.perceptual or a.torch_perceptual):
+        return None
+    import torch.nn.functional as F
+    from fateavatar_amd.perceptual import Perceptual, VggFeatures
+    size = (a.perceptual_size, a.perceptual_size)
+    if a.vgg_weights:
+        feats = VggFeatures.from_state_dict(torch.load(a.vgg_weights, map_location="cpu"), size=size, device=dev)
+    else:
+        rng = torch.get_rng_state()
+        torch.manual_seed(0)
+        feats = VggFeatures.vgg16(size=size, device=dev)
+        torch.set_rng_state(rng)
+    if a.perceptual:
+        return Perceptual(feats, weight=0.1)
+
+    m = torch.tensor(feats.mean, device=dev).view(1, 3, 1, 1)      # (made here: a captured step cannot copy from the host)
+    s = torch.tensor(feats.std, device=dev).view(1, 3, 1, 1)
+
+    class TorchPerceptual(Perceptual):
+        def loss_and_grad(self, img, gt, loss_out=None, grad_out=None, accumulate=False, weight=None):
+            f = self.features
+            with torch.enable_grad():
+                x = img.detach().requires_grad_(True)
+                h = F.interpolate((torch.stack([x, gt]) - m) / s, mode="bilinear", size=f.size, align_corners=False)
+                terms = []
+                for y, w, b in zip(f.layers, f.weights, f.biases):
+                    if y.pool_before:
+                        h = F.max_pool2d(h, 2, 2)
+                    h = F.relu(F.conv2d(h, w, b, padding=1))
+                    if y.tap_after:
+                        terms.append(F.l1_loss(h[0:1], h[1:2].detach()))
+                total = torch.stack(terms).sum()
+                (g,) = torch.autograd.grad(total, x)
+            loss_out.copy_(torch.cat([total.detach().reshape(1), torch.stack(terms).detach()]))
+            grad_out.add_(g, alpha=self.weight if weight is None else weight) if accumulate else grad_out.copy_(g * self.weight)
+            return loss_out, grad_out
+    return TorchPerceptual(feats, weight=0.1)
+
+
 def fateavatar_setup(P, res, dev, views=8, views_per_step=1, use_graph=True, chain=True, fold_binding=True, order="uv",
-                     keep_coherent=False, vertex_grad=False, mesh_terms=None, target_delta=None, camera_grad=False):
+                     keep_coherent=False, vertex_grad=False, mesh_terms=None, target_delta=None, camera_grad=False, perceptual=None):
     """FateAvatar's optimisation step on the synthetic INSTA-layout sequence: the mesh-bound Gaussian
     set, its step object (AvatarStep, or AvatarBatchStep for K > 1 frames per step), cameras, posed meshes and targets
     rendered from a hidden ground-truth set.  Used by this script and by bench.py's `avatar` mode.
@@ -318,6 +382,8 @@ def fateavatar_setup(P, res, dev, views=8, views_per_step=1, use_graph=True, cha
             extra["mesh_terms"] = mesh_terms
         if camera_grad:
             extra["camera_grad"] = True
+        if perceptual is not None:
+            extra["perceptual"] = perceptual
         st = AvatarStep(pc, faces_t, canon, cam0, bg, use_graph=use_graph, fold_binding=fold_binding, keep_coherent=keep_coherent,
                         **extra)
     else:   # the reference's batch of K frames per step (model/fateavatar.py:251-276), in flight together
@@ -429,6 +495,8 @@ def main_flame(a, rank, world, dev):
                                            gt._rotation, gt._scaling, ref.shell_len, True)
             gts.append(render(cams[f], _BoundFrame(xyz, gt, rot, scl, None), bg)["render"].clone())
     common = dict(use_graph=not a.no_graph, fold_binding=not a.binding_op, mesh_terms=terms)
+    if a.perceptual or a.torch_perceptual:
+        common["perceptual"] = make_perceptual(a, dev)
     if a.fused_flame:
         st = AvatarStep(pc, faces_t, canon, cams[0].clone(), bg, flame=fm, **common)
         delta_vertex = lambda: fm.delta_vertex  # noqa: E731
@@ -476,6 +544,8 @@ def main_flame(a, rank, world, dev):
                       "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": a.P, "res": a.res,
                       "V": fm.V, "n_shape": fm.n_shape, "n_exp": fm.n_exp, "frames": n_frames, "graph": not a.no_graph,
                       "fused_flame": bool(a.fused_flame), "overflows": st.overflows, "mesh_terms": list(terms),
+                      "perceptual": None if st.perceptual is None else ("torch" if a.torch_perceptual else "fused"),
+                      "perceptual_loss": None if st.perceptual is None else [round(float(x), 6) for x in st.perceptual_loss],
                       "bump_norm": round(float(bump_t.norm()), 6), "first": first, "last": report()}))
 
 
@@ -544,7 +614,7 @@ def main_fateavatar(a, rank, world, dev):
         mesh_terms = MeshTerms(*a.mesh_terms)
     su = fateavatar_setup(a.P, a.res, dev, views=a.views, views_per_step=a.views_per_step, use_graph=not a.no_graph, chain=a.chain,
                            fold_binding=not a.binding_op, order="random" if a.random_order else "uv", keep_coherent=a.keep_coherent,
-                           vertex_grad=a.vertex_grad, mesh_terms=mesh_terms)
+                           vertex_grad=a.vertex_grad, mesh_terms=mesh_terms, perceptual=make_perceptual(a, dev))
     st, cams, posed_t, gts, n_frames, K = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"], su["K"]
     if mesh_terms is not None:
         bump = torch.from_numpy(smooth_bump(np.asarray(scenes.head_geometry()[0], dtype=np.float32))).to(dev)
@@ -589,6 +659,8 @@ def main_fateavatar(a, rank, world, dev):
                           "graph": not a.no_graph, "overflows": st.overflows, "vertex_grad": bool(st.vertex_grad) if K == 1 else False,
                           "mesh_terms": list(mesh_terms) if mesh_terms else None,
                           "mesh_loss": [float(x) for x in st.mesh_loss] if mesh_terms else None,
+                          "perceptual": None if st.perceptual is None else ("torch" if a.torch_perceptual else "fused"),
+                          "perceptual_loss": None if st.perceptual is None else [round(float(x), 6) for x in st.perceptual_loss],
                           "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
