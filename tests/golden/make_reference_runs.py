@@ -1,5 +1,5 @@
-"""Generate tests/golden/reference_*.npz: runs of the reference's OWN Python for the avatar losses, the point skinning and the
-deformation MLP, recorded as plain data.
+"""Generate tests/golden/reference_*.npz: runs of the reference's OWN Python for the avatar losses, the point skinning, the
+deformation MLP and the perceptual term, recorded as plain data.
 
 Runs ONLY in the build container (needs /root/reference); the fixtures it writes hold arrays, scalars and a `notes` string and
 are committed.  No test imports this file.  Run as
@@ -14,12 +14,15 @@ except where `both(..., default64=True)` says why not):
                                       .accumulate_gradients, FateAvatarLoss.get_laplacian_smoothing_loss / .accumulate_gradients
   flame/FLAME.py over flame/lbs.py    FLAME.forward_pts (inverse_pts, forward_pts)
   model/baseline/flashavatar.py       Embedder, MLP, FlashAvatar.quatProduct_batch
+  tools/loss_utils/vgg_feature.py     VGGPerceptualLoss (constructor and forward)
 None of their text is in this file.  The work-arounds, all of them:
   * stand-in modules for what is not installed (pytorch3d.*, lpips, torchvision, plyfile, igl, simple_knn,
     diff_gaussian_rasterization, simple_phongsurf, matplotlib, PIL) through a meta-path finder APPENDED to sys.meta_path: a
     module that really is installed wins.  A stand-in module hands out one inert placeholder class for every name; nothing that
-    computes is replaced.  (FateAvatarLoss.accumulate_gradients constructs a pytorch3d `Meshes` it never reads once
-    `laplacian_matrix` is set: that object is the placeholder.)
+    computes is replaced — but for `torchvision.models.vgg16` and `VGG16_Weights`, which are made to work (below, at their
+    definition: a narrow VGG-16 in torchvision's layout with seeded weights; the layout is builder-pinned).
+    (FateAvatarLoss.accumulate_gradients constructs a pytorch3d `Meshes` it never reads once `laplacian_matrix` is set: that
+    object is the placeholder.)
   * objects made with `__new__` + `nn.Module.__init__` and only the attributes the called method reads (the constructors
     build LPIPS / VGG networks or read the FLAME pickle);
   * `Tensor.cuda` returns the tensor itself while MonoGaussianAvatarLoss.get_gt_blendshape runs with a ghost bone (its one
@@ -95,13 +98,51 @@ class StandInFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
 # repository's own `simple_knn` / `diff_gaussian_rasterization` drop-ins must not be what the reference's imports find
 sys.path.insert(0, REF)
 sys.meta_path.append(StandInFinder())
+
+
+# torchvision is not installed, and VGGPerceptualLoss's constructor asks it for a pretrained VGG-16 four times.  Two names of the
+# stand-in are therefore made to WORK before the reference's module is imported: `models.vgg16(weights=...)` returns an object whose
+# `.features` is an nn.Sequential in torchvision's configuration-D layout (conv, ReLU(inplace), conv, ReLU, MaxPool2d(2, 2), ...
+# through index 22, the last the reference slices), every width 64 (tests/vgg_ref.NARROW), with tests/vgg_ref.he_weights'
+# weights — the same on every call — and `models.VGG16_Weights.DEFAULT` exists.  The LAYOUT is this file's reading of
+# torchvision, not torchvision's own code: it stays builder-pinned.
+VGG_SEED = 29
+
+
+class NarrowVgg16Weights:
+    DEFAULT = "DEFAULT"
+
+
+def narrow_vgg16(weights=None):
+    from tests import vgg_ref
+    assert weights is NarrowVgg16Weights.DEFAULT
+    W, B = vgg_ref.he_weights(vgg_ref.NARROW, VGG_SEED)
+    mods = []
+    for (ci, co, pool, tap), w, b in zip(vgg_ref.NARROW, W, B):
+        if pool:
+            mods.append(torch.nn.MaxPool2d(kernel_size=2, stride=2))
+        conv = torch.nn.Conv2d(ci, co, kernel_size=3, padding=1)
+        with torch.no_grad():
+            conv.weight.copy_(w)
+            conv.bias.copy_(b)
+        mods += [conv, torch.nn.ReLU(inplace=True)]
+    holder = torch.nn.Module()
+    holder.features = torch.nn.Sequential(*mods)
+    return holder
+
+
+import torchvision.models  # noqa: E402
+assert isinstance(torchvision.models, StandIn), "torchvision is installed: record with its own vgg16 layout and say so in DESIGN.md"
+torchvision.models.vgg16, torchvision.models.VGG16_Weights = narrow_vgg16, NarrowVgg16Weights
+
 from flame.FLAME import FLAME  # noqa: E402
 from model.baseline.flashavatar import MLP, Embedder, FlashAvatar  # noqa: E402
 from tools.loss_utils.dssim import d_ssim  # noqa: E402
+from tools.loss_utils.vgg_feature import VGGPerceptualLoss  # noqa: E402
 from train import loss as ref_loss  # noqa: E402
 
 sys.path.insert(1, ROOT)
-from tests import image_loss_ref, mesh_terms_ref, mono_ref, rigged_density_ref, splatting_loss_ref  # noqa: E402
+from tests import image_loss_ref, mesh_terms_ref, mono_ref, rigged_density_ref, splatting_loss_ref, vgg_ref  # noqa: E402
 from tests.test_gpu_mlp import SEED_MARGIN, _keeps_clear_of_zero  # noqa: E402
 from tests.test_gpu_mono import _row_metric  # noqa: E402
 from tests.test_gpu_mono_pose import _element_metric  # noqa: E402
@@ -438,6 +479,37 @@ def case_mlp(out, case="mlp"):
     record(out, "quat", dict(q1=q1, q2=q2), *both(lambda dt: dict(product=FlashAvatar.quatProduct_batch(q1.to(dt), q2.to(dt)))))
 
 
+# ---------------------------------------------------------------- FateAvatar's perceptual term
+def case_vgg(out, case="vgg"):
+    """VGGPerceptualLoss()(img[None], gt[None]) as it is — its own normalisation, its resize to 224^2, its four slices of the
+    (narrow, stand-in) vgg16 — and its autograd gradient."""
+    H, W = 37, 53
+    img, gt = vgg_ref.images(H, W, seed=1000 * H + W)
+    Wt, B = vgg_ref.he_weights(vgg_ref.NARROW, VGG_SEED)
+
+    def run(dt):
+        net = VGGPerceptualLoss().to(dt)
+        assert len(net.blocks) == 4 and sum(len(b) for b in net.blocks) == 23 and net.mean.dtype == dt
+        x = leaf(img[None], dt)
+        loss = net(x, gt[None].to(dt))
+        (g,) = torch.autograd.grad(loss, x)
+        return dict(loss=loss.detach(), d_img=g[0])
+
+    r32, r64 = both(run)
+    inputs = dict(img=img, gt=gt)
+    for i, (w, b) in enumerate(zip(Wt, B)):
+        inputs[f"weight_{i}"], inputs[f"bias_{i}"] = w, b
+    record(out, case, inputs, dict(loss=r32["loss"]), dict(loss=r64["loss"]))
+    out[f"{case}_loss32"] = r32["loss"].numpy()
+    out[f"{case}_d_img"] = r64["d_img"].numpy()
+    NOTES.append(f"{case}: torchvision.models.vgg16 is this script's stand-in (configuration D's layout through features[22], every width "
+                 f"64, tests/vgg_ref.he_weights(NARROW, {VGG_SEED})): the layout is builder-pinned, everything the reference does with it is "
+                 f"recorded.  {case}_d_img is the float64 gradient; NO float32 gradient error is recorded or to be held: at 224^2 the "
+                 f"reference's own float32 gradient is {rel(r32['d_img'], r64['d_img']):.1e} rel-L2 from its float64 one (ReLU masks, pool "
+                 "argmaxes and tap signs that float32 rounding carries across their thresholds), which is no yardstick for a kernel — "
+                 "the pinned backward of tests/vgg_ref.py at the device's own decisions is")
+
+
 # ---------------------------------------------------------------- files
 def split(group, arrays):
     """[(file name, dict)]: the arrays in order, a new file whenever the next one would carry the file over FILE_BYTES."""
@@ -486,6 +558,9 @@ def main(check):
     o = group("mlp")
     case_mlp(o)
     groups["mlp"] = (o, list(NOTES))
+    o = group("vgg")
+    case_vgg(o)
+    groups["vgg"] = (o, list(NOTES))
 
     wanted = set()
     for name, (arrays, notes) in groups.items():

@@ -256,6 +256,53 @@ def test_deform_points_against_the_recorded_run(gpu_device, name):
     assert bool((grads[6][:, 3, :] == 0).all())
 
 
+# ------------------------------------------------------------------ FateAvatar's perceptual term
+def test_perceptual_against_the_recorded_run(gpu_device):
+    """`Perceptual` on the recorded images at the reference's own 224 x 224 (a narrow VGG-16: every width 64): the loss against
+    what VGGPerceptualLoss computed in float64, at test_gpu_vgg's bound with the RECORDED e32; the gradient against the pinned
+    float64 backward at the device's own saved activations, at the same bound with the float32 restatement's error (the
+    reference's own float32 gradient is 2.7e-3 from its float64 one at this size — decisions that flip — and no yardstick:
+    the fixture's notes).  Also the first test at the production extent: 100 352 rows, unsplit plans, k_vgg_tap_loss's
+    grid-stride loop looping (802 816 float4 against FR_VGG_LOSS_BLOCKS workgroups), a 6-fold upsampling with clamped rows."""
+    import torch
+    from fateavatar_amd import _lib
+    from fateavatar_amd.perceptual import Perceptual, VggFeatures
+    from tests import vgg_ref
+    from tests.test_gpu_vgg import FLOOR, _bound, _rel
+    from tests.test_reference_runs_host import VGG_SIZE
+    dev = gpu_device
+    c = Case("vgg")
+    W, B = mlp_weights(c)
+    layers = vgg_ref.NARROW
+    img, gt = c.inp("img"), c.inp("gt")
+    H, Wd = img.shape[1:]
+    p = Perceptual(VggFeatures(layers, W, B, size=VGG_SIZE, device=dev))
+    assert VGG_SIZE[0] * VGG_SIZE[1] * 64 // 4 > _lib.FR_VGG_LOSS_BLOCKS * 256          # (the terms' loop does loop)
+    loss = torch.full((1 + p.n_terms,), float("nan"), device=dev)
+    grad = torch.full((3, H, Wd), float("nan"), device=dev)
+    p.loss_and_grad(img.to(dev), gt.to(dev), loss_out=loss, grad_out=grad, weight=1.0)
+    torch.cuda.synchronize()
+    loss, grad = loss.cpu(), grad.cpu()
+    saved = [vgg_ref.nchw(a) for a in p.saved_activations()]
+    assert bool(torch.isfinite(loss).all()) and bool(torch.isfinite(grad).all()) and p.n_terms == 4
+    want = c.out("loss").reshape(1)
+    err = _rel(loss[0:1], want)
+    _say(c, "loss", err, "relative error")
+    assert err <= _bound(c.e32("loss")), (err, c.e32("loss"))
+    # the sum of the terms, added in order in float32 as the kernel adds them
+    s = torch.zeros((), dtype=torch.float32)
+    for t in loss[1:]:
+        s = s + t
+    assert torch.equal(s, loss[0]) and bool((loss[1:] > 0).all())
+    pin64 = vgg_ref.pinned_backward(W, layers, saved, (H, Wd), VGG_SIZE, torch.float64)
+    pin32 = vgg_ref.pinned_backward(W, layers, saved, (H, Wd), VGG_SIZE, torch.float32)
+    e32, err = _rel(pin32, pin64), _rel(grad, pin64)
+    print(f"vgg d_img (pinned, 224 x 224): kernel {err:.3e}  float32 restatement {e32:.3e}  ratio {err / max(e32, FLOOR):.2f}")
+    # (for scale only: against the reference's recorded float64 gradient, decisions and all)
+    print(f"vgg d_img against the recorded float64 gradient, end to end: {_rel(grad, c.out('d_img')):.3e}")
+    assert float(pin64.abs().max()) > 0 and err <= _bound(e32), (err, e32)
+
+
 # ------------------------------------------------------------------ FlashAvatar's embedding and MLP
 def test_embed_points_against_the_recorded_run(gpu_device):
     """`embed_points` on the device (plain torch): test_gpu_mlp's FACTOR x e32.  The arguments x 2^k are exact, so the error is the

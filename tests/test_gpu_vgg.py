@@ -10,7 +10,12 @@ scalar losses only, where the restatement's error can come out near zero by chan
 The forward is continuous and is compared directly.  The backward is not (a ReLU mask, a pool argmax or a tap sign that float32
 rounding carries across its threshold moves the gradient by far more than rounding), so it is compared twice: against the PINNED
 float64 backward evaluated at the device's own saved activations, on every shape; and against float64 autograd end to end on
-inputs drawn until the float64 network keeps every decision clear of its threshold."""
+inputs drawn until the float64 network keeps every decision clear of its threshold.
+
+Noise images at 24 x 24 leave two things out, which have cases of their own: decisions that land EXACTLY on their thresholds —
+flat image regions (vgg_ref.patchwork) and identical images, where the first-maximum rule of the pool's backward and
+sign(0) = 0 decide the gradient — and the plans of the GEMM split over the taps that sizes above 24 x 24 take under the library's
+own flags (WIDE_CASES: one and three planes; tests/test_vgg_host.py asserts that the cases take them)."""
 import functools
 
 import pytest
@@ -22,7 +27,7 @@ pytestmark = pytest.mark.gpu
 FACTOR, CEILING, FLOOR = 4.0, 2e-4, 2.0 ** -24
 MASK_Z = 1e-5            # a decision that differs from float64's lies within MASK_Z x the layer's RMS pre-activation of its threshold
 CLEAR = 2e-5             # the end-to-end inputs keep every float64 decision this x RMS clear of its threshold
-STACKS = {"vgg16": vgg_ref.VGG16, "small": vgg_ref.SMALL}
+STACKS = {"vgg16": vgg_ref.VGG16, "small": vgg_ref.SMALL, "wide": vgg_ref.WIDE, "narrow": vgg_ref.NARROW}
 # (stack, H, W, size_h, size_w)
 CASES = [("vgg16", 37, 53, 24, 24),       # non-integer downsampling, ragged M in every block
          ("vgg16", 13, 17, 24, 24),       # upsampling, the clamped source coordinates
@@ -31,6 +36,15 @@ CASES = [("vgg16", 37, 53, 24, 24),       # non-integer downsampling, ragged M i
          ("vgg16", 20, 40, 16, 32),       # non-square
          ("small", 24, 24, 24, 24)]       # descriptor generality: 3 -> 64, 64 -> 64 tap, pool, 64 -> 128 tap
 END_TO_END = [CASES[0], CASES[2], CASES[3]]
+# vgg_ref.patchwork's flat regions, at resizes that keep them bit-flat (tests/test_vgg_host.py holds what the inputs do to float64)
+PATCHWORK = [("small", 24, 24, 24, 24),   # identity
+             ("vgg16", 48, 48, 24, 24),   # exact halving: 0.5 v + 0.5 v
+             ("vgg16", 32, 32, 32, 32)]   # identity
+# vgg_ref.WIDE at the sizes where its GEMMs (layers 1 to 3) take each plan of the split over the taps UNDER THE DEFAULT FLAGS —
+# CASES' sizes split every GEMM into nine planes.  Plans by perceptual.gemm_splits, forward / gradient, layers 1, 2, 3:
+WIDE_CASES = [("wide", 31, 39, 26, 30),   # 3 3 3 / 9 3 3: three planes (VGG-16's block 4 at 224^2), ragged M = 1560 / 780
+              ("wide", 32, 32, 32, 32),   # 1 1 1 / 9 3 3: the forward exactly at tiles == 256
+              ("wide", 40, 24, 64, 32)]   # 1 1 1 / 9 1 1: the gradient unsplit too (at tiles == 256), SEED and MASK epilogues in-kernel
 
 
 def _rel(a, b):
@@ -47,11 +61,11 @@ def _weights(stack):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(stack, H, W, sh, sw):
+def _case(stack, H, W, sh, sw, patchwork=False):
     """Weights, images and both restatements' forwards on the CPU: computed once, shared, never modified."""
     import torch
     Wt, B = _weights(stack)
-    img, gt = vgg_ref.images(H, W, seed=1000 * H + W)
+    img, gt = (vgg_ref.patchwork if patchwork else vgg_ref.images)(H, W, seed=1000 * H + W)
     r64 = vgg_ref.forward(Wt, B, STACKS[stack], img, gt, (sh, sw), torch.float64)
     r32 = vgg_ref.forward(Wt, B, STACKS[stack], img, gt, (sh, sw), torch.float32)
     return dict(W=Wt, B=B, img=img, gt=gt, r64=r64, r32=r32)
@@ -94,15 +108,17 @@ def _ids(c):
     return f"{c[0]}-{c[1]}x{c[2]}-to-{c[3]}x{c[4]}"
 
 
-@pytest.mark.parametrize("case", CASES, ids=_ids)
-def test_forward_and_pinned_backward_against_float64(gpu_device, case):
+def _held_to_float64(dev, case, c, tile=None):
+    """The held set of a case: the forward quantities against float64, the decisions inside the band, the gradient against the
+    pinned float64 backward at the device's own saved activations — each at the module's bound, each with its ratio line.
+    `c`: weights, images and both restatements' forwards (of `_case`).  Returns (losses, gradient, saved activations, object)."""
     import torch
-    dev = gpu_device
     stack, H, W, sh, sw = case
     layers = STACKS[stack]
-    c = _case(*case)
     r64, r32 = c["r64"], c["r32"]
     p = _perceptual(stack, (sh, sw), dev)
+    if tile is not None:
+        p.tile = tile
     T = sum(1 for y in layers if y[3])
     loss = torch.full((1 + T,), float("nan"), device=dev)
     grad = torch.full((3, H, W), float("nan"), device=dev)      # every element is to be OVERWRITTEN
@@ -151,6 +167,116 @@ def test_forward_and_pinned_backward_against_float64(gpu_device, case):
     pin64 = vgg_ref.pinned_backward(c["W"], layers, saved, (H, W), (sh, sw), torch.float64)
     pin32 = vgg_ref.pinned_backward(c["W"], layers, saved, (H, W), (sh, sw), torch.float32)
     held("d_image (pinned)", grad, pin64, pin32)
+    return loss, grad, saved, p
+
+
+@pytest.mark.parametrize("case", CASES, ids=_ids)
+def test_forward_and_pinned_backward_against_float64(gpu_device, case):
+    _held_to_float64(gpu_device, case, _case(*case))
+
+
+def _background_interior(layers, H, W, sh, sw):
+    """(rows, columns) of the shared-background quadrant (top-left, both images 1.0) that NO unit with a view out of the quadrant
+    reaches: a unit whose receptive field lies inside the quadrant computes the same number for both images (the same chain on
+    the same values), so its tap difference is exactly 0 and it seeds no gradient; a source pixel gets a gradient only from
+    units whose field holds it, and one more than vgg_ref.receptive_margin(layers) resized pixels away from the quadrant's
+    inner edges lies in no field that crosses them.  (The image's own border is no edge: the padding is the same for both.)"""
+    fy, fx = H // sh, W // sw
+    assert (fy * sh, fx * sw) == (H, W) and fy in (1, 2) and fx in (1, 2)       # source pixel P blends into resized pixel P // f only
+    margin = vgg_ref.receptive_margin(layers)
+    return fy * max(sh // 2 - margin, 0), fx * max(sw // 2 - margin, 0)
+
+
+@pytest.mark.parametrize("case", PATCHWORK, ids=_ids)
+def test_flat_regions_against_float64(gpu_device, case):
+    """The held set on images with flat regions, where thousands of live pool windows are exact ties and thousands of live tap
+    differences exactly 0 (tests/test_vgg_host.py shows that either rule's opposite moves this gradient by 0.17 to 0.80 rel-L2):
+    k_vgg_unpool's first-maximum rule and sign_of(0) == 0 decide the gradient here.  The device keeps the ties — every output
+    element of a layer is the same chain of operations, so equal inputs give equal bits — and the interior of the shared
+    background takes a gradient of exactly 0.  (The interior is empty for VGG-16 at these sizes: its receptive field, 91 resized
+    pixels, is wider than the quadrant; test_shared_background_takes_no_gradient_at_production_size has the room.)"""
+    stack, H, W, sh, sw = case
+    layers = STACKS[stack]
+    c = _case(*case, patchwork=True)
+    loss, grad, saved, p = _held_to_float64(gpu_device, case, c)
+    ties64, zeros64 = vgg_ref.live_ties(c["r64"]["a"], layers)
+    ties, zeros = vgg_ref.live_ties(saved, layers)
+    print(f"{_ids(case)} patchwork: live tied windows {ties} on the device (float64: {ties64}), live zero tap differences {zeros} "
+          f"(float64: {zeros64})")
+    assert ties64 >= 1000 and zeros64 >= 1000
+    assert 2 * ties >= ties64 and 2 * zeros >= zeros64
+    rows, cols = _background_interior(layers, H, W, sh, sw)
+    print(f"{_ids(case)} patchwork: shared-background interior {rows} x {cols} pixels")
+    assert bool((grad[:, :rows, :cols] == 0).all())
+    assert float(grad[:, H // 2:, :].abs().max()) > 0
+
+
+def test_shared_background_takes_no_gradient_at_production_size(gpu_device):
+    """VGG-16 at 224^2 (identity), where the background quadrant (112 pixels) is wider than the stack's receptive field: its
+    interior's gradient is exactly 0, through the unsplit and the three-plane GEMMs of that size.  No reference is computed."""
+    import torch
+    dev = gpu_device
+    H = W = 224
+    rows, cols = _background_interior(vgg_ref.VGG16, H, W, H, W)
+    assert rows == cols == 112 - 91
+    img, gt = vgg_ref.patchwork(H, W, seed=5)
+    p = _perceptual("vgg16", (H, W), dev)
+    grad = torch.full((3, H, W), float("nan"), device=dev)
+    loss, _ = p.loss_and_grad(img.to(dev), gt.to(dev), grad_out=grad, weight=1.0)
+    torch.cuda.synchronize()
+    grad = grad.cpu()
+    assert bool(torch.isfinite(loss).all()) and bool(torch.isfinite(grad).all()) and float(loss[0]) > 0
+    assert bool((grad[:, :rows, :cols] == 0).all())
+    assert float(grad[:, H // 2:, :].abs().max()) > 0 and float(grad[:, :, W // 2:].abs().max()) > 0
+    # inside the quadrant the two images' activations are the same bits, layer by layer
+    for (h, w), a in zip(p.features.extents(), p.saved_activations()):
+        s = H // h
+        k = (112 - 91) // s
+        if k:
+            assert torch.equal(a[0, :k, :k], a[1, :k, :k])
+
+
+@pytest.mark.parametrize("stack,hw,size,patchwork", [("small", (24, 24), (24, 24), False), ("small", (24, 24), (24, 24), True),
+                                                     ("vgg16", (37, 53), (24, 24), False), ("vgg16", (48, 48), (24, 24), True)],
+                         ids=["small-noise", "small-patchwork", "vgg16-noise", "vgg16-patchwork"])
+def test_identical_images_give_exact_zeros(gpu_device, stack, hw, size, patchwork):
+    """loss_and_grad(x, x): both branches run the same chain on the same values, so every term is exactly 0.0, every tap sign
+    is sign_of(0) = 0 and the gradient is exactly 0.0 everywhere; accumulating it leaves a buffer's bits alone."""
+    import torch
+    dev = gpu_device
+    x = (vgg_ref.patchwork if patchwork else vgg_ref.images)(*hw, seed=9)[0].to(dev)
+    p = _perceptual(stack, size, dev)
+    loss = torch.full((1 + p.n_terms,), float("nan"), device=dev)
+    grad = torch.full_like(x, float("nan"))
+    p.loss_and_grad(x, x.clone(), loss_out=loss, grad_out=grad, weight=1.0)
+    torch.cuda.synchronize()
+    assert bool((loss == 0).all()) and bool((grad == 0).all())
+    assert all(float(a.abs().max()) > 0 for a in p.saved_activations())                 # (the network is not dead)
+    X = torch.randn(x.shape, generator=torch.Generator().manual_seed(2)).to(dev)
+    buf = X.clone()
+    p.loss_and_grad(x, x.clone(), grad_out=buf, accumulate=True)
+    torch.cuda.synchronize()
+    assert torch.equal(buf, X)
+
+
+@pytest.mark.parametrize("case", WIDE_CASES, ids=_ids)
+def test_every_split_plan_against_float64(gpu_device, case):
+    """The held set under the library's own flags at sizes whose GEMMs take the one-plane and three-plane plans (WIDE_CASES;
+    tests/test_vgg_host.py asserts which), and the larger tile changes no bit at any of them — at 26 x 30 M is ragged
+    against 128 rows as well."""
+    import torch
+    from fateavatar_amd import _lib
+    dev = gpu_device
+    c = _case(*case)
+    loss, grad, saved, p = _held_to_float64(dev, case, c, tile=_lib.FR_VGG_TILE_AUTO)
+    img, gt = c["img"].to(dev), c["gt"].to(dev)
+    acts = [a.clone() for a in p.saved_activations()]
+    for tile in (_lib.FR_VGG_TILE_64, _lib.FR_VGG_TILE_128):
+        p.tile = tile
+        loss_t, g_t = p.loss_and_grad(img, gt, weight=1.0)
+        torch.cuda.synchronize()
+        assert torch.equal(loss_t.cpu(), loss) and torch.equal(g_t.cpu(), grad), tile
+        assert all(torch.equal(a, b) for a, b in zip(p.saved_activations(), acts)), tile
 
 
 @pytest.mark.parametrize("case", END_TO_END, ids=_ids)

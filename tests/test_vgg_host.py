@@ -315,3 +315,97 @@ def test_restatement_pinned_backward_at_its_own_decisions_is_autograd():
         assert float(g.abs().max()) > 0 and float(loss) == float(r["loss"])
         assert float((pinned - g).norm() / g.norm()) < 1e-12
         assert vgg_ref.decisions_clear(r, layers, 0.0) and not vgg_ref.decisions_clear(r, layers, 1.0)
+
+
+def test_restatement_normalises_with_float32_statistics():
+    """The reference's mean and std are float32 buffers that take the image's dtype afterwards (recorded run `vgg`,
+    tests/test_reference_runs_host.py); the kernel's descriptor holds them as float."""
+    from fateavatar_amd.perceptual import IMAGENET_MEAN, IMAGENET_STD
+    assert (vgg_ref.MEAN, vgg_ref.STD) == (IMAGENET_MEAN, IMAGENET_STD)
+    x = torch.rand(1, 3, 4, 5, generator=torch.Generator().manual_seed(0))
+    m32, s32 = torch.tensor(vgg_ref.MEAN).double().view(1, 3, 1, 1), torch.tensor(vgg_ref.STD).double().view(1, 3, 1, 1)
+    assert torch.equal(vgg_ref.preprocess(x, (4, 5), torch.float64), (x.double() - m32) / s32)
+    assert not torch.equal(m32.view(3), torch.tensor(vgg_ref.MEAN, dtype=torch.float64))
+
+
+def test_receptive_margin_counted_by_hand():
+    # conv: 1 + 1; conv, conv: 2 + 2; SMALL: s 1 -> (1,1) -> (2,2), pool -> hi 3, s 2, conv -> (4,5)
+    assert vgg_ref.receptive_margin(((3, 64, False, True),)) == 2
+    assert vgg_ref.receptive_margin(vgg_ref.SMALL[:2]) == 4 and vgg_ref.receptive_margin(vgg_ref.SMALL) == 9
+    assert vgg_ref.receptive_margin(vgg_ref.VGG16) == 42 + 49
+    # the rule itself, on SMALL: an input pixel reaches exactly the deepest units whose field holds it
+    W, B = vgg_ref.he_weights(vgg_ref.SMALL, 1)
+    leaf = torch.rand(1, 3, 24, 24, dtype=torch.float64, generator=torch.Generator().manual_seed(1)).requires_grad_(True)
+    h = leaf
+    for (ci, co, pool, tap), w in zip(vgg_ref.SMALL, W):
+        h = F.conv2d(F.max_pool2d(h, 2) if pool else h, w.double().abs(), padding=1)     # (positive weights: nothing cancels)
+    for unit in (0, 3, 11):
+        (g,) = torch.autograd.grad(h[0, 0, unit, unit], leaf, retain_graph=True)
+        cols = g[0].abs().sum((0, 1)).nonzero().view(-1)
+        assert int(cols.max()) - int(cols.min()) <= vgg_ref.receptive_margin(vgg_ref.SMALL)
+        if unit == 3:       # (clear of both borders: the whole field)
+            assert int(cols.max()) - int(cols.min()) == vgg_ref.receptive_margin(vgg_ref.SMALL)
+
+
+def test_wide_cases_take_every_split_plan():
+    """tests/test_gpu_vgg.py's WIDE_CASES between them run every plan of the split over the taps that a GEMM kind can take —
+    under the library's own flags.  Should vgg_splits (restated by perceptual.gemm_splits, which
+    test_workspace_bytes_is_the_documented_formula holds to the library) change, this fails instead of the coverage going."""
+    from fateavatar_amd.perceptual import VggFeatures, gemm_splits
+    from tests.test_gpu_vgg import STACKS, WIDE_CASES
+    from tests.test_gpu_vgg import CASES
+
+    def plans(stack, sh, sw):
+        """(forward plans, gradient plans) of layers 1 .. L-1 (layer 0 and its gradient are no GEMMs)."""
+        layers = STACKS[stack]
+        extents = VggFeatures(layers, *vgg_ref.he_weights(layers, 0), size=(sh, sw)).extents()
+        return ([gemm_splits(2 * h * w, co) for (ci, co, _, _), (h, w) in list(zip(layers, extents))[1:]],
+                [gemm_splits(h * w, ci) for (ci, co, _, _), (h, w) in list(zip(layers, extents))[1:]])
+
+    wide = {(sh, sw): plans(stack, sh, sw) for stack, H, W, sh, sw in WIDE_CASES}
+    assert wide == {(26, 30): ([3, 3, 3], [9, 3, 3]), (32, 32): ([1, 1, 1], [9, 3, 3]), (64, 32): ([1, 1, 1], [9, 1, 1])}
+    forward = {s for fw, _ in wide.values() for s in fw}
+    gradient = {s for _, bw in wide.values() for s in bw[:-1]}          # with a stored dZ as its operand
+    seed = {bw[-1] for _, bw in wide.values()}                          # the last layer's: dZ computed in the fetch (SEED)
+    assert forward == {1, 3} and gradient == {1, 3, 9} and seed == {1, 3}
+    # nine planes forward (and nine on a SEED gradient): every GEMM of the older cases
+    older = [plans(stack, sh, sw) for stack, H, W, sh, sw in CASES]
+    assert all(set(fw) | set(bw) == {9} for fw, bw in older)
+    # the boundary itself: a grid of exactly 256 tiles is not split, one of 255 is
+    assert -(-2 * 32 * 32 // 64) * (512 // 64) == 256 and -(-64 * 32 // 64) * (512 // 64) == 256
+    assert [gemm_splits(m, 512) for m in (2048 - 64, 2048)] == [3, 1] and [gemm_splits(m, 64) for m in (85 * 64, 85 * 64 + 1)] == [9, 3]
+
+
+# (stack, H, W, size_h, size_w): resizes that keep a flat region bit-flat — the identity and an exact halving
+PATCHWORK_CASES = [("small", 24, 24, 24, 24), ("vgg16", 48, 48, 24, 24), ("vgg16", 32, 32, 32, 32)]
+PATCHWORK_STACKS = {"small": vgg_ref.SMALL, "vgg16": vgg_ref.VGG16}
+
+
+@pytest.mark.parametrize("case", PATCHWORK_CASES, ids=lambda c: f"{c[0]}-{c[1]}x{c[2]}-to-{c[3]}x{c[4]}")
+def test_patchwork_puts_live_decisions_on_their_thresholds(case):
+    """The patchwork images do what noise cannot: thousands of LIVE pool windows are exact ties and thousands of LIVE tap
+    differences exactly 0, so that the two rules the kernel's comments state — the first maximum takes a window's gradient,
+    sign(0) = 0 — decide a large part of the gradient.  Shown by mutation: the pinned backward with either rule replaced by
+    its opposite moves by more than 0.1 rel-L2 (on the suite's noise images: by exactly 0)."""
+    stack, H, Wd, sh, sw = case
+    layers = PATCHWORK_STACKS[stack]
+    W, B = vgg_ref.he_weights(layers, seed=11 + len(layers))
+    img, gt = vgg_ref.patchwork(H, Wd, seed=1000 * H + Wd)
+    assert bool((img[:, :H // 2, :Wd // 2] == 1).all()) and bool((gt[:, :H // 2, :Wd // 2] == 1).all())
+    assert torch.equal(img[:, H // 2:, Wd // 2:], vgg_ref.images(H, Wd, seed=1000 * H + Wd)[0][:, H // 2:, Wd // 2:])
+    r = vgg_ref.forward(W, B, layers, img, gt, (sh, sw))
+    ties, zeros = vgg_ref.live_ties(r["a"], layers)
+    print(f"{case}: live tied windows {ties}, live zero tap differences {zeros}")
+    assert ties >= 1000 and zeros >= 1000
+    loss, g = vgg_ref.autograd_gradient(W, B, layers, img, gt, (sh, sw))
+    pinned = vgg_ref.pinned_backward(W, layers, r["a"], (H, Wd), (sh, sw))
+    rel = lambda a, b: float((a - b).norm() / b.norm())  # noqa: E731
+    assert float(g.abs().max()) > 0 and rel(pinned, g) <= 1e-12
+    last = vgg_ref.pinned_backward(W, layers, r["a"], (H, Wd), (sh, sw), one_hot=lambda a: vgg_ref._window_one_hot(a, last=True))
+    plus = vgg_ref.pinned_backward(W, layers, r["a"], (H, Wd), (sh, sw), sign=vgg_ref.sign_plus_at_zero)
+    print(f"{case}: last maximum moves the gradient by {rel(last, pinned):.3f}, sign(0) = +1 by {rel(plus, pinned):.3f}")
+    assert rel(last, pinned) > 0.1 and rel(plus, pinned) > 0.1
+    # and noise has none of it: the same mutations change no bit there
+    img, gt = vgg_ref.images(H, Wd, seed=1000 * H + Wd)
+    r = vgg_ref.forward(W, B, layers, img, gt, (sh, sw))
+    assert vgg_ref.live_ties(r["a"], layers) == (0, 0)
