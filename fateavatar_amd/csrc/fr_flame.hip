@@ -5,7 +5,7 @@
 // their autograd backward.  Here, with e = expression [NE], r = pose [15], L = NS + NE:
 //     v_shaped = (v_template + delta_vertex) + (S + dS)[:, :, NS:] e          (the NS shape columns meet exact zeros: not read)
 //     Jnt      = J_regressor v_shaped                                          (5 x 3 sums over ALL vertices)
-//     R_j      = rodrigues(r[3j : 3j + 3]),  phi = (R_1 .. R_4 - I).flatten()
+//     R_j      = rodrigues(r[3j : 3j + 3]),  phi = (R_1 .. R_4 - I).flatten()   (taken before I is added: fl_rodrigues)
 //     v_posed  = v_shaped + phi (P + dP)
 //     A        = the chain of (R_j, Jnt_j - Jnt_parent) with G_j[:3,:3] Jnt_j taken off the translation
 //     verts    = (sum_j w_vj A_j) (v_posed, 1)
@@ -142,15 +142,20 @@ struct FlRod {
     float K[9], KK[9];
 };
 
-// batch_rodrigues (flame/lbs.py:238-269), mirrored: angle = |r + 1e-8|, dir = r / angle
-__device__ __forceinline__ void fl_rodrigues(const float* r, FlRod& q, float* R)
+// batch_rodrigues (flame/lbs.py:238-269): angle = |r + 1e-8|, dir = r / angle, R = I + D with D = sin K + (1 - cos) K K.
+// Unlike the reference's float32, 1 - cos is taken as 2 sin^2(angle / 2) and D = R - I is handed out as it is summed, before I
+// is added: below 2.4e-4 rad float32's cos rounds to 1 and 1 - cos is 0, and (I + D) - I rounds D to the spacing of 1 — up to
+// 1.2e-4 relative in the pose feature and in d_pose at the rotations a tracked neck and eyes have.  So the kernel departs from
+// the reference's float32 rounding TOWARDS its float64 value; the derivative below is unchanged (d(1 - cos) / d angle = sin).
+__device__ __forceinline__ void fl_rodrigues(const float* r, FlRod& q, float* R, float* D)
 {
 #pragma unroll
     for (int k = 0; k < 3; k++) q.a[k] = r[k] + 1e-8f;
     q.angle = sqrtf((q.a[0] * q.a[0] + q.a[1] * q.a[1]) + q.a[2] * q.a[2]);
 #pragma unroll
     for (int k = 0; k < 3; k++) q.d[k] = r[k] / q.angle;
-    q.s = sinf(q.angle), q.cosv = cosf(q.angle), q.c1 = 1.0f - q.cosv;
+    const float sh = sinf(0.5f * q.angle);
+    q.s = sinf(q.angle), q.cosv = cosf(q.angle), q.c1 = 2.0f * sh * sh;
     const float x = q.d[0], y = q.d[1], z = q.d[2];
     const float K[9] = {0.f, -z, y, z, 0.f, -x, -y, x, 0.f};
 #pragma unroll
@@ -160,15 +165,18 @@ __device__ __forceinline__ void fl_rodrigues(const float* r, FlRod& q, float* R)
 #pragma unroll
         for (int j = 0; j < 3; j++) q.KK[i * 3 + j] = (K[i * 3] * K[j] + K[i * 3 + 1] * K[3 + j]) + K[i * 3 + 2] * K[6 + j];
 #pragma unroll
-    for (int e = 0; e < 9; e++) R[e] = ((e % 4 == 0 ? 1.f : 0.f) + q.s * q.K[e]) + q.c1 * q.KK[e];
+    for (int e = 0; e < 9; e++) {
+        D[e] = q.s * q.K[e] + q.c1 * q.KK[e];
+        R[e] = (e % 4 == 0 ? 1.f : 0.f) + D[e];
+    }
 }
 
 // dLoss/dr from dLoss/dR
 __device__ __forceinline__ void fl_rodrigues_bwd(const float* r, const float* dR, float* dr)
 {
     FlRod q;
-    float R[9];
-    fl_rodrigues(r, q, R);
+    float R[9], D[9];
+    fl_rodrigues(r, q, R, D);
     float ds = 0.f, dc1 = 0.f;
 #pragma unroll
     for (int e = 0; e < 9; e++) ds += dR[e] * q.K[e], dc1 += dR[e] * q.KK[e];
@@ -191,7 +199,7 @@ __device__ __forceinline__ void fl_rodrigues_bwd(const float* r, const float* dR
 }
 
 struct FlChain {
-    float R[kFlJ][9], GR[kFlJ][9], Gt[kFlJ][3], J[kFlJ][3];
+    float R[kFlJ][9], D[kFlJ][9], GR[kFlJ][9], Gt[kFlJ][3], J[kFlJ][3];      // D = R - I, summed without I
     float dGR[kFlJ][9], dGt[kFlJ][3], dJ[kFlJ][3], dR[9], d_pose[3 * kFlJ];
     int parent[kFlJ];
 };
@@ -211,7 +219,7 @@ __device__ __forceinline__ void fl_chain_forward(const FlameArgs& a, const float
     fl_parents(a.parents, c);
     FlRod q;
     for (int j = 0; j < kFlJ; j++) {
-        fl_rodrigues(a.pose + 3 * j, q, c.R[j]);
+        fl_rodrigues(a.pose + 3 * j, q, c.R[j], c.D[j]);
         for (int k = 0; k < 3; k++) c.J[j][k] = Jnt[j * 3 + k];
     }
     for (int e = 0; e < 9; e++) c.GR[0][e] = c.R[0][e];
@@ -368,7 +376,7 @@ __global__ void __launch_bounds__(kFlThreads) k_flame_shape(FlameArgs a)
         for (int k = 0; k < 3; k++) a.state[kStJ + j * 3 + k] = c.J[j][k];
     }
     for (int i = 0; i < kFlPhi; i++) {
-        const float phi = c.R[1 + i / 9][i % 9] - (i % 9 % 4 == 0 ? 1.f : 0.f);
+        const float phi = c.D[1 + i / 9][i % 9];
         a.state[kStPhi + i] = phi;
         if (a.pose_feature) a.pose_feature[i] = phi;
     }

@@ -7,14 +7,29 @@ import torch
 JOINTS, POSE_FEATURES = 5, 36
 
 
-def rodrigues(r: torch.Tensor) -> torch.Tensor:
-    """batch_rodrigues (flame/lbs.py:238-269) for r [J,3]: angle = |r + 1e-8|, direction = r / angle, R = I + sin K + (1 - cos) K K."""
+def _angle_and_generator(r: torch.Tensor):
     angle = (r + 1e-8).norm(dim=1, keepdim=True)
     d = r / angle
     x, y, z = d[:, 0], d[:, 1], d[:, 2]
     o = torch.zeros_like(x)
-    K = torch.stack([o, -z, y, z, o, -x, -y, x, o], dim=1).view(-1, 3, 3)
+    return angle, torch.stack([o, -z, y, z, o, -x, -y, x, o], dim=1).view(-1, 3, 3)
+
+
+def rotation_offset(r: torch.Tensor) -> torch.Tensor:
+    """R - I for r [J,3] WITHOUT the detour through I: sin K + 2 sin^2(angle / 2) K K, the same angle and direction as
+    `rodrigues`.  In floating point 1 - cos(angle) loses every digit once cos rounds to 1 (float32: below 2.4e-4 rad) and
+    (I + x) - I rounds x to the spacing of 1; this form keeps full relative precision at any angle."""
+    angle, K = _angle_and_generator(r)
+    return torch.sin(angle)[:, :, None] * K + (2 * torch.sin(angle / 2) ** 2)[:, :, None] * (K @ K)
+
+
+def rodrigues(r: torch.Tensor, stable_rotation: bool = False) -> torch.Tensor:
+    """batch_rodrigues (flame/lbs.py:238-269) for r [J,3]: angle = |r + 1e-8|, direction = r / angle, R = I + sin K + (1 - cos) K K;
+    `stable_rotation`: I + rotation_offset(r), the same matrix in exact arithmetic."""
     eye = torch.eye(3, dtype=r.dtype, device=r.device)
+    if stable_rotation:
+        return eye + rotation_offset(r)
+    angle, K = _angle_and_generator(r)
     return eye + torch.sin(angle)[:, :, None] * K + (1 - torch.cos(angle))[:, :, None] * (K @ K)
 
 
@@ -34,16 +49,21 @@ def rigid_chain(R: torch.Tensor, joints: torch.Tensor, parents) -> torch.Tensor:
 
 
 def lbs(expression, pose, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, n_shape,
-        delta_shapedirs=None, delta_posedirs=None, delta_vertex=None):
-    """`(verts [V,3], pose_feature [36], A [5,4,4])` of FLAME.forward_with_delta_blendshape (None deltas: FLAME.forward)."""
+        delta_shapedirs=None, delta_posedirs=None, delta_vertex=None, stable_rotation=False):
+    """`(verts [V,3], pose_feature [36], A [5,4,4])` of FLAME.forward_with_delta_blendshape (None deltas: FLAME.forward).
+    `stable_rotation` (default off: the reference's own form): R and the pose feature from `rotation_offset`."""
     S = shapedirs if delta_shapedirs is None else shapedirs + delta_shapedirs
     P = posedirs if delta_posedirs is None else posedirs + delta_posedirs
     vt = v_template if delta_vertex is None else v_template + delta_vertex
     betas = torch.cat([torch.zeros(n_shape, dtype=expression.dtype, device=expression.device), expression])
     v_shaped = vt + S @ betas
     joints = J_regressor @ v_shaped
-    R = rodrigues(pose.view(-1, 3))
-    phi = (R[1:] - torch.eye(3, dtype=R.dtype, device=R.device)).reshape(-1)
+    if stable_rotation:
+        D = rotation_offset(pose.view(-1, 3))
+        R, phi = torch.eye(3, dtype=D.dtype, device=D.device) + D, D[1:].reshape(-1)
+    else:
+        R = rodrigues(pose.view(-1, 3))
+        phi = (R[1:] - torch.eye(3, dtype=R.dtype, device=R.device)).reshape(-1)
     v_posed = v_shaped + (phi @ P).view(-1, 3)
     A = rigid_chain(R, joints, parents)
     T = (lbs_weights @ A.view(A.shape[0], 16)).view(-1, 4, 4)
@@ -70,7 +90,7 @@ def random_model(V, n_shape, n_exp, seed, dtype=torch.float32):
     return m
 
 
-def run(m, dtype, with_deltas=True):
+def run(m, dtype, with_deltas=True, stable_rotation=False):
     """Forward and backward of `lbs` on the model dict `m` in `dtype` for dLoss/dverts = m['g']: a dict with `verts`,
     `pose_feature`, `A` and the gradients `d_delta_shapedirs`, `d_delta_posedirs`, `d_delta_vertex`, `d_expression`, `d_pose`."""
     c = lambda k: m[k].detach().to(dtype)  # noqa: E731
@@ -78,7 +98,7 @@ def run(m, dtype, with_deltas=True):
     e, p = leaf("expression"), leaf("pose")
     dS, dP, dV = (leaf(k) if with_deltas else None for k in ("delta_shapedirs", "delta_posedirs", "delta_vertex"))
     verts, phi, A = lbs(e, p, c("v_template"), c("shapedirs"), c("posedirs"), c("J_regressor"), m["parents"], c("lbs_weights"),
-                        m["n_shape"], dS, dP, dV)
+                        m["n_shape"], dS, dP, dV, stable_rotation=stable_rotation)
     verts.backward(c("g"))
     out = dict(verts=verts.detach(), pose_feature=phi.detach(), A=A.detach(), d_expression=e.grad, d_pose=p.grad)
     if with_deltas:

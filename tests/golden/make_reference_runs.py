@@ -1,5 +1,5 @@
 """Generate tests/golden/reference_*.npz: runs of the reference's OWN Python for the avatar losses, the point skinning, the
-deformation MLP and the perceptual term, recorded as plain data.
+deformation MLP, the perceptual term and FLAME's posing with FateAvatar's deltas, recorded as plain data.
 
 Runs ONLY in the build container (needs /root/reference); the fixtures it writes hold arrays, scalars and a `notes` string and
 are committed.  No test imports this file.  Run as
@@ -13,6 +13,7 @@ except where `both(..., default64=True)` says why not):
   train/loss.py                       SplattingAvatarLoss / FlashAvatarLoss / GaussianAvatarsLoss / MonoGaussianAvatarLoss
                                       .accumulate_gradients, FateAvatarLoss.get_laplacian_smoothing_loss / .accumulate_gradients
   flame/FLAME.py over flame/lbs.py    FLAME.forward_pts (inverse_pts, forward_pts)
+  flame/lbs.py                        lbs, with the arguments FLAME.forward_with_delta_blendshape hands it
   model/baseline/flashavatar.py       Embedder, MLP, FlashAvatar.quatProduct_batch
   tools/loss_utils/vgg_feature.py     VGGPerceptualLoss (constructor and forward)
 None of their text is in this file.  The work-arounds, all of them:
@@ -136,13 +137,14 @@ assert isinstance(torchvision.models, StandIn), "torchvision is installed: recor
 torchvision.models.vgg16, torchvision.models.VGG16_Weights = narrow_vgg16, NarrowVgg16Weights
 
 from flame.FLAME import FLAME  # noqa: E402
+from flame.lbs import lbs as ref_lbs  # noqa: E402
 from model.baseline.flashavatar import MLP, Embedder, FlashAvatar  # noqa: E402
 from tools.loss_utils.dssim import d_ssim  # noqa: E402
 from tools.loss_utils.vgg_feature import VGGPerceptualLoss  # noqa: E402
 from train import loss as ref_loss  # noqa: E402
 
 sys.path.insert(1, ROOT)
-from tests import image_loss_ref, mesh_terms_ref, mono_ref, rigged_density_ref, splatting_loss_ref, vgg_ref  # noqa: E402
+from tests import flame_ref, image_loss_ref, mesh_terms_ref, mono_ref, rigged_density_ref, splatting_loss_ref, vgg_ref  # noqa: E402
 from tests.test_gpu_mlp import SEED_MARGIN, _keeps_clear_of_zero  # noqa: E402
 from tests.test_gpu_mono import _row_metric  # noqa: E402
 from tests.test_gpu_mono_pose import _element_metric  # noqa: E402
@@ -510,6 +512,52 @@ def case_vgg(out, case="vgg"):
                  "the pinned backward of tests/vgg_ref.py at the device's own decisions is")
 
 
+# ---------------------------------------------------------------- FLAME with FateAvatar's deltas
+FLAME_SHAPE, FLAME_SEED = (65, 2, 5), 131
+
+
+def flame_poses():
+    """{case: (parents, pose [15] float32)}: joint trees other than FLAME's own, and the pose regimes a track has — exact zeros,
+    rotations where float32's cos rounds to 1, rotations near pi and near 2 pi."""
+    g = torch.Generator().manual_seed(FLAME_SEED + 1)
+    rn = lambda *s: torch.randn(s, generator=g, dtype=torch.float64)  # noqa: E731
+    axes = torch.nn.functional.normalize(rn(5, 3), dim=1)
+    rest = 0.3 * rn(5, 3)
+    rest[[1, 3, 4]] = 0.0
+    large = 3.1 * axes
+    large[2] = 6.2 * axes[2]
+    flame = (-1, 0, 1, 1, 1)
+    cases = dict(flame_chain=((-1, 0, 1, 2, 3), 0.3 * rn(5, 3)), flame_star=((-1, 0, 0, 0, 0), 0.3 * rn(5, 3)),
+                 flame_tree_small=((-1, 0, 0, 1, 2), 2e-4 * axes), flame_zero=(flame, torch.zeros(5, 3, dtype=torch.float64)),
+                 flame_rest=(flame, rest), flame_large=(flame, large))
+    return {k: (p, r.reshape(15).float()) for k, (p, r) in cases.items()}
+
+
+def case_flame(out, case, m, parents, pose, store_tables):
+    """lbs() as FLAME.forward_with_delta_blendshape calls it — betas = (zeros [1, NS], expression), the deltas added to the
+    tables — on the tables of tests/flame_ref.random_model, and the gradients of sum(verts * g)."""
+    NS = m["n_shape"]
+    par = torch.tensor(parents, dtype=torch.long)
+
+    def run(dt):
+        c = lambda k: m[k].to(dt)  # noqa: E731
+        dS, dP, dV, e, p = (leaf(t, dt) for t in (m["delta_shapedirs"], m["delta_posedirs"], m["delta_vertex"], m["expression"], pose))
+        betas = torch.cat([torch.zeros(1, NS, dtype=dt), e[None]], dim=1)
+        verts, phi, A = ref_lbs(betas, p[None], (c("v_template") + dV)[None], c("shapedirs") + dS, c("posedirs") + dP,
+                                c("J_regressor"), par, c("lbs_weights"), dtype=dt)
+        grads = torch.autograd.grad((verts[0] * c("g")).sum(), (dS, dP, dV, e, p))
+        # the shape columns meet exact zeros: their gradient is exactly zero, and only that is recorded of them
+        assert int(grads[0][:, :, :NS].count_nonzero()) == 0
+        return dict(verts=verts[0].detach(), pose_feature=phi[0].detach(), A=A[0].detach(), d_delta_exp=grads[0][:, :, NS:].contiguous(),
+                    d_delta_posedirs=grads[1], d_delta_vertex=grads[2], d_expression=grads[3], d_pose=grads[4])
+
+    inputs = dict(parents=np.asarray(parents, dtype=np.int64), pose=pose)
+    if store_tables:
+        inputs.update({k: m[k] for k in ("v_template", "shapedirs", "posedirs", "J_regressor", "lbs_weights", "delta_shapedirs",
+                                          "delta_posedirs", "delta_vertex", "expression", "g")})
+    record(out, case, inputs, *both(run), dict(n_shape=NS, n_exp=m["n_exp"]))
+
+
 # ---------------------------------------------------------------- files
 def split(group, arrays):
     """[(file name, dict)]: the arrays in order, a new file whenever the next one would carry the file over FILE_BYTES."""
@@ -561,6 +609,15 @@ def main(check):
     o = group("vgg")
     case_vgg(o)
     groups["vgg"] = (o, list(NOTES))
+    o = group("flame")
+    m = flame_ref.random_model(*FLAME_SHAPE, seed=FLAME_SEED)
+    for i, (name, (parents, pose)) in enumerate(flame_poses().items()):
+        case_flame(o, name, m, parents, pose, store_tables=i == 0)
+    NOTES.append("flame_*: every case reads flame_chain's tables, deltas, expression and g (`flame_chain_in_*`) and its own "
+                 "`_in_parents` and `_in_pose`; d_delta_exp is the expression columns of the gradient of delta_shapedirs, whose shape "
+                 "columns were asserted exactly zero; flame_zero's pose_feature and d_delta_posedirs are exactly zero (their e32 is "
+                 "the plain norm of the float32 run)")
+    groups["flame"] = (o, list(NOTES))
 
     wanted = set()
     for name, (arrays, notes) in groups.items():

@@ -3,7 +3,12 @@ float64 restatement of tests/flame_ref.py with a bound MEASURED on the float32 r
 graph replay, the autograd op, and AvatarStep(flame=...) against the existing route (torch FLAME outside the step).
 
 The bound (as tests/test_gpu_mlp.py): the float32 restatement on the CPU has a rel-L2 error e32 against float64 for each output;
-the kernels may have at most FACTOR x e32 (another summation order) and never more than the project's gradient ceiling 1e-4."""
+the kernels may have at most FACTOR x e32 (another summation order) and never more than the project's gradient ceiling 1e-4.
+
+The pose regimes (test_pose_regimes, test_trees_and_tables) are held to the float64 truth with the float32 run of the STABLE form
+of the rotation as the yardstick (flame_ref.rotation_offset): below 3e-4 rad the reference's own float32 form loses up to four
+digits of R - I (cos rounds to 1), sits at the ceiling itself and cannot bound a correct kernel.  Every comparison is also made
+BLOCK BY BLOCK (_check_blocks): a whole-array rel-L2 lets one joint of d_pose or one row of d_delta_posedirs hide."""
 import ctypes
 import functools
 
@@ -17,12 +22,131 @@ pytestmark = pytest.mark.gpu
 FACTOR, CEILING = 4.0, 1e-4
 # (V, n_shape, n_exp): one vertex, an odd size below one skinning tile, the golden file's, a ragged size at the widest expression,
 # FLAME's own vertex count, and one vertex past each grid cap (256 workgroups of 16 and of 64 vertices) at n_exp = 1
-SHAPES = [(1, 0, 1), (63, 0, 5), (300, 3, 7), (257, 2, 128), (5023, 100, 50), (4097, 0, 1), (16385, 0, 1)]
+# and the sizes on either side of a lane group (16 lanes per vertex, 16 expression columns per sweep) and of a skinning tile (64)
+SHAPES = [(1, 0, 1), (63, 0, 5), (300, 3, 7), (257, 2, 128), (5023, 100, 50), (4097, 0, 1), (16385, 0, 1),
+          (16, 0, 15), (17, 0, 16), (64, 1, 17), (65, 0, 127)]
 OUTPUTS = ("verts", "verts_orig", "pose_feature", "A", "d_delta_exp", "d_delta_posedirs", "d_delta_vertex", "d_expression", "d_pose")
+
+
+ROW_FACTOR = 16             # tests/test_gpu_mono.py's: a block may miss float64 by this many times the float32 restatement's worst block
+EPS = 2.0 ** -24
+YARDSTICK_SHAPE = (4099, 3, 7)
+FLAME_TREE = (-1, 0, 1, 1, 1)
+SWEEP = (0.0, 1e-6, 5e-5, 1e-4, 2e-4, 2.4e-4, 3e-4, 1e-3, 3.1)
 
 
 def _rel(a, b):
     return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-300))
+
+
+# ------------------------------------------------------------------ pose recipes, models, references
+def _axes():
+    import torch
+    g = torch.Generator().manual_seed(77)
+    return torch.nn.functional.normalize(torch.randn(5, 3, generator=g, dtype=torch.float64), dim=1)
+
+
+def _pose(recipe, own):
+    """A pose [15] (float32) by recipe: "randn" — the model's own 0.3 randn; ("theta", t) — five seeded unit axes x t; "rest" —
+    joints 1, 3, 4 exactly zero, the model's own rotations at 0 and 2; "large" — the axes x 3.1, joint 2 x 6.2."""
+    if recipe == "randn":
+        return own.clone()
+    if recipe == "rest":
+        p = own.clone().view(5, 3)
+        p[[1, 3, 4]] = 0.0
+        return p.reshape(15)
+    a = _axes()
+    if recipe == "large":
+        a = 3.1 * a
+        a[2] = 2.0 * a[2]
+        return a.reshape(15).float()
+    assert recipe[0] == "theta"
+    return (recipe[1] * a).reshape(15).float()
+
+
+def _references(m):
+    """The float64 truth (the reference's form), the float32 run of the reference's form and the float32 run of the stable form
+    for the model dict `m`, each with `d_delta_exp` and `verts_orig`."""
+    import torch
+    out = {}
+    for name, dtype, stable in (("r64", torch.float64, False), ("r32", torch.float32, False), ("r32s", torch.float32, True)):
+        r = flame_ref.run(m, dtype, stable_rotation=stable)
+        r["d_delta_exp"] = r.pop("d_delta_shapedirs")[:, :, m["n_shape"]:].contiguous()
+        r["verts_orig"] = flame_ref.run(m, dtype, with_deltas=False, stable_rotation=stable)["verts"]
+        out[name] = r
+    return out
+
+
+def _blocks(name, t, n_exp):
+    """The array `name` as [blocks, -1], or None for an output that is held as a whole only."""
+    if name in ("d_pose", "A", "pose_feature"):
+        t = t[:, :3, :] if name == "A" else t
+        return t.reshape(5 if name != "pose_feature" else 4, -1)
+    if name == "d_delta_posedirs":
+        return t.reshape(36, -1)
+    if name == "d_delta_exp":
+        return t.reshape(-1, n_exp).t()
+    if name == "d_delta_vertex":
+        return t.reshape(-1, 3)
+    return None
+
+
+BLOCKED = ("d_pose", "A", "pose_feature", "d_delta_posedirs", "d_delta_exp", "d_delta_vertex")
+
+
+@functools.lru_cache(maxsize=None)
+def _yardstick(recipe):
+    """{output: the worst block (tests/test_gpu_mono._row_metric) of the float32 STABLE restatement against float64} at
+    YARDSTICK_SHAPE with the pose recipe: on the CPU, computed once.  (A maximum over the few blocks of a small case is no
+    yardstick — tests/test_gpu_mono.py.)"""
+    import torch
+    from tests.test_gpu_mono import _row_metric
+    V, NS, NE = YARDSTICK_SHAPE
+    m = flame_ref.random_model(V, NS, NE, seed=4099, dtype=torch.float32)
+    m["pose"] = _pose(recipe, m["pose"])
+    r = _references(m)
+    return {n: float(_row_metric(_blocks(n, r["r32s"][n], NE), _blocks(n, r["r64"][n], NE)).max()) for n in BLOCKED}
+
+
+def _check_blocks(got, r64, n_exp, recipe, label):
+    """Every block of every blocked output within ROW_FACTOR x the recipe's yardstick, and never above CEILING."""
+    import torch
+    from tests.test_gpu_mono import _row_metric
+    yard, missed = _yardstick(recipe), []
+    for n in BLOCKED:
+        ref = _blocks(n, r64[n], n_exp)
+        if float(ref.abs().max()) == 0:         # (zero pose: the caller has held the kernel's values to exact zeros)
+            assert recipe == ("theta", 0.0) and n in ("pose_feature", "d_delta_posedirs"), n
+            continue
+        m = _row_metric(_blocks(n, got[n].cpu(), n_exp), ref)
+        worst, at = float(m.max()), int(m.argmax())
+        print(f"{label} {n}: worst block {worst:.3e} (block {at} of {m.numel()}), yardstick {yard[n]:.3e}, "
+              f"ratio {worst / yard[n]:.2f} of the {ROW_FACTOR} allowed")
+        assert 0 < yard[n] <= 2e-6, (n, yard[n])
+        if not (bool(torch.isfinite(m).all()) and worst <= min(ROW_FACTOR * yard[n], CEILING)):
+            missed.append((label, n, at, worst, yard[n]))
+    assert not missed, missed             # (after every output's line is printed)
+
+
+def _check_stable(got, refs, label, zero_pose=False):
+    """Every output against the float64 truth: at most FACTOR x the STABLE float32 run's error — and no less than FACTOR float32
+    roundings, for an e32s that is accidentally nothing where another order of the joint sums alone moves a rounding — and
+    never above CEILING.  `zero_pose`: pose_feature and d_delta_posedirs are exactly zero in float64, and here."""
+    import torch
+    r64, r32, r32s, missed = refs["r64"], refs["r32"], refs["r32s"], []
+    for name in OUTPUTS:
+        v, ref64 = got[name].cpu().reshape(-1), r64[name].reshape(-1)
+        assert bool(torch.isfinite(v).all()), name
+        if zero_pose and name in ("pose_feature", "d_delta_posedirs"):
+            assert float(ref64.abs().max()) == 0 and int(v.count_nonzero()) == 0, name
+            print(f"{label} {name}: exactly zero, as in float64")
+            continue
+        err, e32, e32s = _rel(v, ref64), _rel(r32[name].reshape(-1), ref64), _rel(r32s[name].reshape(-1), ref64)
+        print(f"{label} {name}: kernel {err:.3e}  float32 reference form {e32:.3e}  float32 stable form {e32s:.3e}")
+        assert float(ref64.abs().max()) > 0, name
+        if not (err <= max(FACTOR * e32s, FACTOR * EPS) and err <= CEILING):
+            missed.append((label, name, err, e32s))
+    assert not missed, missed             # (after every output's line is printed)
 
 
 @functools.lru_cache(maxsize=None)
@@ -82,6 +206,7 @@ def test_forward_and_backward_against_float64(gpu_device, shape):
         assert float(ref64.abs().max()) > 0
         assert err <= FACTOR * e32, (name, err, e32)
         assert err <= CEILING, (name, err)
+    _check_blocks(got, r64, shape[2], "randn", f"V={shape[0]} NS={shape[1]} NE={shape[2]}")
     # without verts_orig, and with some outputs NULL: what the others receive are the same bits
     alone = _run(fm, m, dev, orig=False)
     for name in OUTPUTS:
@@ -172,6 +297,128 @@ def test_autograd_op_hands_out_the_same_gradients(gpu_device):
         fm(torch.zeros(6, device=dev), p)
     with pytest.raises(TypeError, match="float32"):
         fm(e.detach(), torch.zeros(15, device=dev, dtype=torch.float64))
+
+
+# ------------------------------------------------------------------ pose regimes, joint trees, tables
+@functools.lru_cache(maxsize=None)
+def _regime(recipe, parents=FLAME_TREE, tables="random"):
+    """The (300, 3, 7) model with the pose of `recipe`, the joint tree `parents` and `tables`: "random" — flame_ref.random_model's;
+    "onehot" — every vertex skinned to ONE joint (FLAME's own weights hold exact 0 and 1) and a regressor of four non-zeros per
+    joint; "onehot_no_4" — the same with no vertex on joint 4.  With its references, computed once."""
+    import torch
+    m = flame_ref.random_model(300, 3, 7, seed=5, dtype=torch.float32)
+    m["pose"] = _pose(recipe, m["pose"])
+    m["parents"] = torch.tensor(parents)
+    if tables != "random":
+        g = torch.Generator().manual_seed(9)
+        used = 5 if tables == "onehot" else 4
+        joint = torch.randint(0, used, (300,), generator=g)
+        joint[:used] = torch.arange(used)                       # every joint in use owns a vertex
+        m["lbs_weights"] = torch.nn.functional.one_hot(joint, 5).float()
+        Jr = torch.zeros(5, 300, dtype=torch.float64)
+        for j in range(5):
+            w = torch.rand(4, generator=g, dtype=torch.float64) + 0.1
+            Jr[j, torch.randperm(300, generator=g)[:4]] = w / w.sum()
+        m["J_regressor"] = Jr.float()
+        assert int((m["lbs_weights"][:, 4] != 0).sum()) == (0 if tables == "onehot_no_4" else int((joint == 4).sum()))
+        assert bool(((m["J_regressor"] != 0).sum(1) == 4).all())
+    return dict(m=m, **_references(m))
+
+
+REGIMES = [("theta", t) for t in SWEEP] + ["rest"]
+
+
+@pytest.mark.parametrize("recipe", REGIMES, ids=lambda r: r if isinstance(r, str) else f"theta={r[1]:g}")
+def test_pose_regimes_against_float64(gpu_device, recipe):
+    """Five seeded unit axes x theta from exact zero through the band where float32's cos rounds to 1 (below 2.4e-4 rad) to 3.1,
+    and a pose with three joints exactly at rest: what real tracks hold (neck and eyes at zero, rotations of 1e-5 .. 1e-3).
+    The truth is float64; the bound is the float32 run of the stable form (see the module's docstring)."""
+    import torch
+    c = _regime(recipe)
+    fm = _mesh(c["m"], gpu_device)
+    got = _run(fm, c["m"], gpu_device)
+    torch.cuda.synchronize()
+    assert int(fm.workspace_zeroed_part().count_nonzero()) == 0
+    label = recipe if isinstance(recipe, str) else f"theta={recipe[1]:g}"
+    _check_stable(got, c, label, zero_pose=recipe == ("theta", 0.0))
+    _check_blocks(got, c["r64"], 7, recipe, label)
+
+
+TREES = {"chain": (-1, 0, 1, 2, 3), "star": (-1, 0, 0, 0, 0), "mixed": (-1, 0, 0, 1, 2)}
+
+
+@pytest.mark.parametrize("which", list(TREES) + ["onehot", "onehot_no_4"])
+def test_trees_and_tables_against_float64(gpu_device, which):
+    """Joint trees other than FLAME's own (a chain four deep, a star, a mixed tree: fl_parents / fl_chain_forward / _backward are
+    written for any parents[i] < i) and tables with exact zeros and ones, at rotations of a few tenths of a radian."""
+    import torch
+    c = _regime("randn", TREES.get(which, FLAME_TREE), "random" if which in TREES else which)
+    fm = _mesh(c["m"], gpu_device)
+    assert fm.parents.tolist() == list(TREES.get(which, FLAME_TREE))
+    got = _run(fm, c["m"], gpu_device)
+    torch.cuda.synchronize()
+    _check_stable(got, c, which)
+    _check_blocks(got, c["r64"], 7, "randn", which)
+    # (the tree matters: FLAME's own gives another mesh)
+    if which in TREES:
+        assert _rel(c["r64"]["verts"], _regime("randn")["r64"]["verts"]) > 1e-3
+
+
+# ------------------------------------------------------------------ NULL delta inputs (include/fr_rasterizer.h: "NULL: zeros")
+def _raw(fm, m, dev, null=()):
+    """One forward and backward through the C entry points with the descriptor's delta pointers named in `null` set to NULL,
+    into poisoned outputs (the gradients of all three deltas are still asked for)."""
+    import torch
+    from fateavatar_amd import _lib
+    full = lambda *s: torch.full(s, float("nan"), device=dev)  # noqa: E731
+    e, p, g = m["expression"].to(dev), m["pose"].to(dev), m["g"].to(dev)
+    d = fm._desc(e, p)
+    for k in null:
+        assert getattr(d, k) is not None
+        setattr(d, k, None)
+        assert getattr(d, k) is None
+    o = dict(verts=full(fm.V, 3), verts_orig=full(fm.V, 3), pose_feature=full(36), A=full(5, 4, 4), d_expression=full(fm.n_exp),
+             d_pose=full(15))
+    fm.flat_grad.fill_(float("nan"))
+    ws = fm._workspace.data_ptr()
+    _lib.launch("fr_flame_forward", dev, ctypes.byref(d), o["verts"].data_ptr(), o["verts_orig"].data_ptr(), o["pose_feature"].data_ptr(),
+                o["A"].data_ptr(), ws)
+    _lib.launch("fr_flame_backward", dev, ctypes.byref(d), g.data_ptr(), fm.grad_delta_exp.data_ptr(), fm.grad_delta_posedirs.data_ptr(),
+                fm.grad_delta_vertex.data_ptr(), o["d_expression"].data_ptr(), o["d_pose"].data_ptr(), ws)
+    o.update(d_delta_exp=fm.grad_delta_exp.clone(), d_delta_posedirs=fm.grad_delta_posedirs.clone(),
+             d_delta_vertex=fm.grad_delta_vertex.clone())
+    torch.cuda.synchronize()
+    assert int(fm.workspace_zeroed_part().count_nonzero()) == 0
+    return o
+
+
+def test_null_delta_inputs_are_zeros_bit_for_bit(gpu_device):
+    import torch
+    dev = gpu_device
+    m = _case(300, 3, 7)["m"]
+    fm = _mesh(m, dev)
+    with_deltas = _raw(fm, m, dev)
+    assert torch.equal(with_deltas["verts"], _run(fm, m, dev)["verts"])
+    # ---- all three NULL: the plain mesh, and the bits of a FlameMesh whose flat buffer is all zeros
+    zeros = _mesh(m, dev)
+    with torch.no_grad():
+        zeros.flat.zero_()
+    want = _raw(zeros, m, dev)
+    got = _raw(fm, m, dev, null=("delta_exp", "delta_posedirs", "delta_vertex"))
+    assert torch.equal(got["verts"], with_deltas["verts_orig"]) and torch.equal(got["verts_orig"], with_deltas["verts_orig"])
+    assert not torch.equal(got["verts"], with_deltas["verts"])
+    for name in OUTPUTS:
+        assert bool(torch.isfinite(got[name]).all()) and torch.equal(got[name], want[name]), name
+    # ---- each single NULL: the bits of that delta set to zeros
+    for k, view in (("delta_exp", "delta_exp"), ("delta_posedirs", "delta_posedirs"), ("delta_vertex", "delta_vertex")):
+        one = _mesh(m, dev)
+        with torch.no_grad():
+            getattr(one, view).zero_()
+        assert int(one.flat.count_nonzero()) > 0
+        want, got = _raw(one, m, dev), _raw(fm, m, dev, null=(k,))
+        for name in OUTPUTS:
+            assert torch.equal(got[name], want[name]), (k, name)
+        assert not torch.equal(got["verts"], with_deltas["verts"]), k
 
 
 # ------------------------------------------------------------------ the step

@@ -3,7 +3,7 @@ reference's own Python computed on them in float64 (tests/golden/make_reference_
 
 The bound of each output is the one its module's own GPU test states, imported from that test: image_loss_ref.LOSS_ATOL /
 GRAD_REL_L2 / GRAD_ENTRY; FACTOR x e32 under CEILING (test_gpu_mlp, test_gpu_splatting_loss); ROW_FACTOR / ELEMENT_FACTOR
-(test_gpu_mono, test_gpu_mono_pose); the counted 2^-24 bounds of the splatting, Huber, regulariser, blendshape-term and mesh-term
+(test_gpu_mono, test_gpu_mono_pose, and test_gpu_flame's blocks); the counted 2^-24 bounds of the splatting, Huber, regulariser, blendshape-term and mesh-term
 tests.  e32 — the reference's own float32 error — and the row / element yardsticks come from the fixture.  Inputs that meet a gate
 were drawn clear of it (the margins are in the fixture): no element is left out of any comparison.  The achieved error and the
 recorded e32 are printed per output.  Reads tests/golden/ only."""
@@ -14,7 +14,8 @@ from tests.reference_runs import EPS, Case, rel
 from tests.test_gpu_mlp import CEILING, FACTOR
 from tests.test_gpu_mono import ROW_FACTOR, _row_metric, _terms_roundings
 from tests.test_gpu_mono_pose import ELEMENT_FACTOR, _element_metric
-from tests.test_reference_runs_host import SKIN_OUTPUTS, mlp_weights, mono_tables, mono_var, skinning_inputs
+from tests.test_reference_runs_host import FLAME_CASES, FLAME_OUTPUTS, SKIN_OUTPUTS, flame_model, mlp_weights, mono_tables, mono_var, \
+    skinning_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -301,6 +302,43 @@ def test_perceptual_against_the_recorded_run(gpu_device):
     # (for scale only: against the reference's recorded float64 gradient, decisions and all)
     print(f"vgg d_img against the recorded float64 gradient, end to end: {_rel(grad, c.out('d_img')):.3e}")
     assert float(pin64.abs().max()) > 0 and err <= _bound(e32), (err, e32)
+
+
+# ------------------------------------------------------------------ FLAME with FateAvatar's deltas
+# the pose recipe (tests/test_gpu_flame._pose) whose block yardstick a recorded case is held to
+FLAME_RECIPES = dict(flame_chain="randn", flame_star="randn", flame_tree_small=("theta", 2e-4), flame_zero=("theta", 0.0),
+                     flame_rest="rest", flame_large="large")
+
+
+@pytest.mark.parametrize("name", FLAME_CASES)
+def test_flame_against_the_recorded_run(gpu_device, name):
+    """`FlameMesh.forward_into` / `backward_from` on what lbs() itself computed in float64 on a chain, a star and a mixed tree
+    and at zero, tiny, partly zero and near-pi / near-2-pi rotations: test_gpu_flame's FACTOR x e32 under CEILING with the
+    RECORDED e32, and its block-by-block bound.  At zero pose pose_feature and d_delta_posedirs are exactly zero in the record
+    and must be here."""
+    import torch
+    from tests.test_gpu_flame import _check_blocks, _mesh, _run
+    dev = gpu_device
+    c = Case(name, inputs_of="flame_chain")
+    m = flame_model(c)
+    fm = _mesh(m, dev)
+    got = _run(fm, m, dev)
+    torch.cuda.synchronize()
+    assert int(fm.workspace_zeroed_part().count_nonzero()) == 0 and fm.parents.tolist() == m["parents"].tolist()
+    r64 = {n: c.out(n) for n in FLAME_OUTPUTS}
+    for n in FLAME_OUTPUTS:
+        t, want = got[n].cpu(), r64[n]
+        assert t.shape == want.shape and bool(torch.isfinite(t).all()), n
+        if float(want.abs().max()) == 0:
+            assert name == "flame_zero" and n in ("pose_feature", "d_delta_posedirs") and c.e32(n) == 0, n
+            assert int(t.count_nonzero()) == 0, n
+            print(f"{name} {n}: exactly zero, as recorded")
+            continue
+        e = rel(t, want)
+        _say(c, n, e)
+        assert e <= FACTOR * c.e32(n), (n, e, c.e32(n))
+        assert e <= CEILING, (n, e)
+    _check_blocks(got, r64, m["n_exp"], FLAME_RECIPES[name], name)
 
 
 # ------------------------------------------------------------------ FlashAvatar's embedding and MLP

@@ -1,7 +1,7 @@
 """CPU: the torch restatements the kernel tests are held to, against RECORDED runs of the reference's own Python
 (tests/golden/reference_*.npz, written by tests/golden/make_reference_runs.py from the reference's unmodified functions).
 
-The restatements (image_loss_ref, splatting_loss_ref, flash_ref, mlp_ref, rigged_density_ref, mono_ref, mesh_terms_ref) were
+The restatements (image_loss_ref, splatting_loss_ref, flash_ref, mlp_ref, rigged_density_ref, mono_ref, mesh_terms_ref, flame_ref) were
 written by whoever wrote the kernels, from the same reading of the reference: a misread coefficient, gate or order of
 subtraction would be wrong on both sides of every kernel test.  Here each of them runs on the fixture's float32 inputs
   * in float64 and reproduces the reference's float64 result to rel-L2 <= 1e-12 (rounding differences are a few 1e-16; a
@@ -15,7 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests import flash_ref, image_loss_ref, mesh_terms_ref, mlp_ref, mono_ref, rigged_density_ref, splatting_loss_ref, vgg_ref
+from tests import flame_ref, flash_ref, image_loss_ref, mesh_terms_ref, mlp_ref, mono_ref, rigged_density_ref, splatting_loss_ref, vgg_ref
 from tests.reference_runs import Case, everything, float32_allowance, rel
 
 FLOAT64_BOUND = 1e-12
@@ -242,6 +242,51 @@ def test_point_skinning_restatement(name):
         assert 0 < c.scalar(f"d_{n}_row32") <= 2e-6
     for n in SKIN_OUTPUTS[4:]:
         assert 0 < c.scalar(f"d_{n}_element32") <= 2e-5
+
+
+# ------------------------------------------------------------------ FLAME with FateAvatar's deltas
+FLAME_CASES = ("flame_chain", "flame_star", "flame_tree_small", "flame_zero", "flame_rest", "flame_large")
+FLAME_OUTPUTS = ("verts", "pose_feature", "A", "d_delta_exp", "d_delta_posedirs", "d_delta_vertex", "d_expression", "d_pose")
+FLAME_TABLES = ("v_template", "shapedirs", "posedirs", "J_regressor", "lbs_weights", "delta_shapedirs", "delta_posedirs", "delta_vertex",
+                "expression", "g")
+
+
+def flame_model(c):
+    """The model dict of tests/flame_ref.run from a recorded FLAME case (float32 tensors, as every run read them)."""
+    m = {k: c.inp(k) for k in FLAME_TABLES + ("pose",)}
+    m["parents"] = c.inp("parents")
+    m["n_shape"], m["n_exp"] = int(c.param("n_shape")), int(c.param("n_exp"))
+    return m
+
+
+@pytest.mark.parametrize("name", FLAME_CASES)
+def test_flame_restatement_on_other_trees_and_pose_regimes(name):
+    """tests/flame_ref.py in float64 against lbs() itself on a chain, a star and a mixed tree, at zero, tiny, partly zero and
+    near-pi / near-2-pi rotations: 1e-12 of the largest magnitude (tests/test_flame_host.py's bound); what is exactly zero in
+    the record is exactly zero here."""
+    c = Case(name, inputs_of="flame_chain")
+    m = flame_model(c)
+    assert sorted(c.outputs()) == sorted(FLAME_OUTPUTS) and m["v_template"].shape == (65, 3) and (m["n_shape"], m["n_exp"]) == (2, 5)
+    assert all(0 <= int(m["parents"][i]) < i for i in range(1, 5)) and int(m["parents"][0]) == -1
+    r = flame_ref.run(m, torch.float64)
+    assert int(r["d_delta_shapedirs"][:, :, :m["n_shape"]].count_nonzero()) == 0
+    r["d_delta_exp"] = r.pop("d_delta_shapedirs")[:, :, m["n_shape"]:]
+    zero = ("pose_feature", "d_delta_posedirs") if name == "flame_zero" else ()
+    for k in FLAME_OUTPUTS:
+        want = c.out(k)
+        scale, worst = float(want.abs().max()), float((r[k] - want).abs().max())
+        print(f"{name} {k}: float64 restatement max |d| {worst:.3e} of max |want| {scale:.3e}; reference's own float32 run {c.e32(k):.3e}")
+        assert r[k].dtype == torch.float64 and r[k].shape == want.shape
+        assert (scale == 0) == (k in zero), k
+        assert worst <= FLOAT64_BOUND * scale, (k, worst, scale)
+    # the stable form of the rotation is the same function: it differs from the reference's form by float64 rounding alone
+    s = flame_ref.run(m, torch.float64, stable_rotation=True)
+    for k in ("verts", "pose_feature", "A", "d_delta_posedirs", "d_pose"):
+        want = c.out(k)
+        assert float((s[k] - want).abs().max()) <= 1e-9 * max(float(want.abs().max()), 1e-30) or k in zero, k
+    if name == "flame_tree_small":
+        # what the regime is recorded for: the reference's own float32 run loses four digits here, on exactly these outputs
+        assert c.e32("pose_feature") > 2e-5 and c.e32("d_pose") > 2e-5 and c.e32("verts") < 1e-6
 
 
 # ------------------------------------------------------------------ FlashAvatar's embedding, MLP and quaternion product
