@@ -623,20 +623,51 @@ static inline unsigned capped_blocks(unsigned long long n, unsigned per_block, u
     return blocks < 1 ? 1u : (blocks > cap ? cap : (unsigned)blocks);
 }
 
+// ---- shuffle sums of a fixed shape: the same operand order, hence the same bits, on every launch
+// the xor butterfly over G consecutive lanes (G / 2, .., 2, 1): every lane of the group gets the group's sum
+template <int G>
+__device__ __forceinline__ float group_sum(float v)
+{
+#pragma unroll
+    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
+    return v;
+}
+// the wave's four 16-lane groups in index order; every lane gets the sum of the lanes with its `sub` (= lane & 15)
+__device__ __forceinline__ float groups_sum16(float x, unsigned sub)
+{
+    const float v0 = __shfl(x, (int)sub), v1 = __shfl(x, (int)(sub + 16u)), v2 = __shfl(x, (int)(sub + 32u)), v3 = __shfl(x, (int)(sub + 48u));
+    return ((v0 + v1) + v2) + v3;
+}
+// the wave's 64 lanes as a __shfl_down tree (32, .., 2, 1): lane 0's value is the sum
+__device__ __forceinline__ float wave_sum(float x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
+    return x;
+}
+
+// ---- a launch's sums across its workgroups: sum_over_workgroups (a few scalars) and sum_rows_over_workgroups (a row)
+// Both leave per-workgroup partials in the workspace and let the workgroup that finishes last add them up in workgroup-index
+// order: no float atomics, and the same bits on every launch, whichever workgroup happens to be last.
+// Why the last workgroup sees the others' partials (cdna_hip_programming.md Guideline 16, write-through payload and a counter):
+// a partial is stored with a relaxed agent-scope atomic store, which writes through to where every compute unit of the device
+// reads; EVERY storing wave waits until its stores have completed (s_waitcnt vmcnt(0)), a barrier follows where more than one
+// thread stored, and only then ONE thread counts the workgroup in, with an atomic of its own: whoever draws the last ticket
+// drew it after every partial had landed.  What is left is the reader's own L1, which no other compute unit's store refreshes:
+//   - EVERY load of a handed-off word is a relaxed agent-scope atomic load, which bypasses the L1: no stale line, no acquire
+//     fence (sum_over_workgroups; sum_rows_over_workgroups with kVec == 1).  ONE plain load added there would need the fence;
+//   - or the electing thread of the last workgroup issues an agent-scope acquire fence, which drops the compute unit's L1 lines,
+//     and waits for it (s_waitcnt vmcnt(0)) BEFORE it publishes the verdict; the loads behind it may then be plain — the one
+//     form there is for a 16-byte load (sum_rows_over_workgroups with kVec == 4).
+// Either way the verdict reaches the workgroup's other threads through LDS and a barrier, which keeps their loads behind it.
+
 // acc[k]: this thread's running sums.  Returns true in thread 0 of the workgroup that finishes last, with acc[k] = the launch's
 // totals; false everywhere else (acc is then undefined).  Call from every thread of a workgroup of kSumThreads, outside
 // divergent control flow.  `partial`: K rows `row_stride` floats apart, slot `id` of `count` (as last_workgroup_of) in each.
 // Every sum has a fixed shape — lanes by shuffle, the four waves as (0 + 1) + (2 + 3), the partials in workgroup-index order
-// dealt out to the last workgroup's threads, then that tree again — so a launch gives the same bits every time, whichever
-// workgroup happens to be last.  kZero: the partials are put back to zero (the counters always are).
-// Why the last workgroup sees the others' partials (cdna_hip_programming.md Guideline 16, the form without an acquire): a
-// partial is stored by ONE thread with a relaxed agent-scope atomic store, which writes through to where every compute unit
-// of the device reads; that thread's wave waits until the store has completed (s_waitcnt vmcnt(0)) and only then counts the
-// workgroup in, with an atomic of its own.  So whoever draws the last ticket drew it after every partial had landed.  The
-// reader, in turn, fetches EVERY partial with a relaxed agent-scope atomic load, which bypasses its compute unit's L1: no plain
-// load of a handed-off word, hence no stale line to invalidate and no acquire fence.  The verdict reaches the workgroup's other
-// threads through LDS and a barrier, which also keeps their loads behind the election.  A plain load added to the loop below
-// would need that fence (k_point_lbs_pose_bwd has one); a second storing wave would have to wait for its own stores too.
+// dealt out to the last workgroup's threads, then that tree again.  kZero: the partials are put back to zero (the counters
+// always are).  The hand-off is the first form above: ONE thread stores the workgroup's K partials, waits for them and counts
+// the workgroup in, and every load of a partial below is atomic — no fence.
 constexpr unsigned kSumThreads = 256;
 template <int K, bool kZero = true>
 __device__ __forceinline__ bool sum_over_workgroups(float (&acc)[K], float* partial, unsigned row_stride, unsigned* counter,
@@ -648,8 +679,7 @@ __device__ __forceinline__ bool sum_over_workgroups(float (&acc)[K], float* part
     const unsigned wave = threadIdx.x >> 6;
     const bool lead = (threadIdx.x & 63) == 0;
 #pragma unroll
-    for (int k = 0; k < K; k++)
-        for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off);
+    for (int k = 0; k < K; k++) acc[k] = wave_sum(acc[k]);
     if (lead) {
 #pragma unroll
         for (int k = 0; k < K; k++) s_red[k][wave] = acc[k];
@@ -676,8 +706,7 @@ __device__ __forceinline__ bool sum_over_workgroups(float (&acc)[K], float* part
         }
     }
 #pragma unroll
-    for (int k = 0; k < K; k++)
-        for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off);
+    for (int k = 0; k < K; k++) acc[k] = wave_sum(acc[k]);
     __syncthreads();   // (thread 0 has read the first round's s_red)
     if (lead) {
 #pragma unroll
@@ -687,6 +716,88 @@ __device__ __forceinline__ bool sum_over_workgroups(float (&acc)[K], float* part
     if (threadIdx.x != 0) return false;
 #pragma unroll
     for (int k = 0; k < K; k++) acc[k] = (s_red[k][0] + s_red[k][1]) + (s_red[k][2] + s_red[k][3]);
+    return true;
+}
+
+// The same for a whole ROW of kSlots sums per workgroup of kThreads.  The LDS it works in is the caller's to declare (and to
+// overlay with what it no longer needs): `row` is read before anything else of it is written.
+template <unsigned kThreads, unsigned kSlots, unsigned kVec, unsigned kDepth>
+struct RowSums {
+    static constexpr unsigned kCols = kSlots / kVec;          // columns of kVec floats: one per reading thread
+    static constexpr unsigned kChunks = kThreads / kCols;     // runs of consecutive rows the last workgroup adds side by side
+    static_assert((kVec == 1 || kVec == 4) && kSlots % kVec == 0 && kChunks >= 1, "whole columns, one run at least");
+    static_assert(kVec == 1 || (done_workspace_bytes(0) % 16 == 0 && kSlots % 4 == 0), "the partials are read sixteen bytes at a time");
+    float row[kSlots];             // in: this workgroup's sums; out, in the last workgroup: the launch's totals
+    float run[kChunks][kSlots];
+    bool last;
+};
+// On entry `s.row` holds this workgroup's sums, behind a barrier.  Returns true in EVERY thread of the workgroup that finishes
+// last, with the launch's totals in `s.row`; false in all the others.  Call from every thread of the workgroup, outside
+// divergent control flow.  `partial`: gridDim.x rows of kSlots floats behind `counter` (done_workspace); rows and counters are
+// left zeroed.  The order of the additions is fixed: run c of kChunks covers rows [c per, (c + 1) per) with per =
+// ceil(gridDim.x / kChunks), a thread adds its column's rows in ascending order from 0, then the runs are added left to right.
+// The hand-off: threads < kSlots store, so every wave waits and a barrier precedes the ticket; the last workgroup reads kVec
+// floats a load, kDepth rows in flight per thread (they miss every cache: a round trip apiece if issued one by one).  kVec == 4:
+// plain float4 loads behind the fence.  kVec == 1: atomic loads and no fence — with the fence, FLAME's forward + backward pair
+// (V = 5 023, three such tails) took 0.0830 ms against 0.0827 ms, and a 4-byte load gains nothing from being plain.
+template <unsigned kThreads, unsigned kSlots, unsigned kVec, unsigned kDepth>
+__device__ __forceinline__ bool sum_rows_over_workgroups(RowSums<kThreads, kSlots, kVec, kDepth>& s, float* partial, unsigned* counter)
+{
+    using Lds = RowSums<kThreads, kSlots, kVec, kDepth>;
+    if (threadIdx.x < kSlots)
+        __hip_atomic_store(partial + (size_t)blockIdx.x * kSlots + threadIdx.x, s.row[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const bool last = last_workgroup_of(counter, blockIdx.x, gridDim.x);
+        if (kVec == 4 && last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (holds the barrier below for the invalidate)
+        }
+        s.last = last;
+    }
+    __syncthreads();
+    if (!s.last) return false;
+    const unsigned chunk = threadIdx.x / Lds::kCols, col = threadIdx.x % Lds::kCols;
+    if (chunk < Lds::kChunks) {
+        const unsigned per = (gridDim.x + Lds::kChunks - 1) / Lds::kChunks;
+        const unsigned b0 = chunk * per < gridDim.x ? chunk * per : gridDim.x, b1 = b0 + per < gridDim.x ? b0 + per : gridDim.x;
+        float* const column = partial + col * kVec;
+        float tot[kVec];
+#pragma unroll
+        for (unsigned i = 0; i < kVec; i++) tot[i] = 0.f;
+        for (unsigned b = b0; b < b1; b += kDepth) {
+            float v[kDepth][kVec];
+#pragma unroll
+            for (unsigned k = 0; k < kDepth; k++) {
+                const float* at = column + (size_t)(b + k) * kSlots;
+                if constexpr (kVec == 4) {
+                    const float4 x = b + k < b1 ? *reinterpret_cast<const float4*>(at) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    v[k][0] = x.x, v[k][1] = x.y, v[k][2] = x.z, v[k][3] = x.w;
+                } else {
+                    v[k][0] = b + k < b1 ? __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+                }
+            }
+#pragma unroll
+            for (unsigned k = 0; k < kDepth; k++)
+#pragma unroll
+                for (unsigned i = 0; i < kVec; i++) tot[i] += v[k][i];      // (a row past the run adds +0: no bit moves)
+        }
+        for (unsigned b = b0; b < b1; b++)
+#pragma unroll
+            for (unsigned i = 0; i < kVec; i++)
+                __hip_atomic_store(column + (size_t)b * kSlots + i, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (unsigned i = 0; i < kVec; i++) s.run[chunk][col * kVec + i] = tot[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < kSlots) {
+        float v = s.run[0][threadIdx.x];
+#pragma unroll
+        for (unsigned c = 1; c < Lds::kChunks; c++) v += s.run[c][threadIdx.x];
+        s.row[threadIdx.x] = v;
+    }
+    __syncthreads();
     return true;
 }
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }

@@ -12,8 +12,8 @@
 // and `verts_orig`, the same with every delta zero (its v_shaped differs, so it has joint sums and a chain of its own).
 //
 // FOUR LAUNCHES, two per direction; every sum over the vertices goes through per-workgroup partials that the workgroup which
-// finishes last adds up in workgroup-index order (flame_sum_rows: last_workgroup_of and the write-through hand-off of
-// sum_over_workgroups, fr_common.hpp): no float atomics, the same bits on every launch and every graph replay.
+// finishes last adds up in workgroup-index order (sum_rows_over_workgroups, fr_common.hpp: kFlThreads / slots runs of consecutive
+// rows side by side, then the runs in order): no float atomics, the same bits on every launch and every graph replay.
 //   k_flame_shape      a group of sixteen lanes per vertex walks the vertex's three [NE] rows of S and dS (contiguous along l) and
 //                      a butterfly adds them up (fr_point_lbs.hip's layout); lane j < 5 of the group keeps joint j's three sums.
 //                      The last workgroup runs Rodrigues and the chain (one thread per mesh) and leaves phi, A, and what the
@@ -46,7 +46,8 @@ constexpr int kFlJ = FR_FLAME_JOINTS;
 constexpr int kFlPhi = FR_FLAME_POSE_FEATURES;
 constexpr unsigned kFlAccE = FR_FLAME_MAX_E / kFlGroup;   // columns of S a lane owns in k_flame_bwd_shape
 static_assert(kFlJ == 5 && kFlPhi == 9 * (kFlJ - 1), "the slot layouts below");
-static_assert(FR_FLAME_MAX_E == kFlRow && kFlThreads == kSumThreads && kFlThreads % kFlRow == 0, "one slot per expression column");
+static_assert(FR_FLAME_MAX_E == kFlRow && kFlThreads == kSumThreads && kFlThreads % kFlRow == 0 && kFlThreads % 32 == 0,
+              "one slot per expression column; whole runs of rows in the last workgroup");
 static_assert(kFlSkinElems <= kFlThreads && kFlGroup >= kFlJ, "one lane per element / per joint");
 
 // the state block (floats)
@@ -71,70 +72,9 @@ __device__ __forceinline__ float* fl_vshaped_orig(const FlameArgs& a) { return a
 __device__ __forceinline__ float* fl_vposed(const FlameArgs& a) { return a.state + kStateHead + 2 * a.plane; }
 __device__ __forceinline__ float* fl_dvposed(const FlameArgs& a) { return a.state + kStateHead + 3 * a.plane; }
 
-__device__ __forceinline__ float fl_group_sum(float v)
-{
-    for (int off = kFlGroup / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kFlGroup);
-    return v;
-}
-
-// the wave's four groups in index order; every lane gets the sum of the lanes with its `sub`
-__device__ __forceinline__ float fl_groups_sum(float x, unsigned sub)
-{
-    const float v0 = __shfl(x, (int)sub), v1 = __shfl(x, (int)(sub + 16u)), v2 = __shfl(x, (int)(sub + 32u)), v3 = __shfl(x, (int)(sub + 48u));
-    return ((v0 + v1) + v2) + v3;
-}
-
-__device__ __forceinline__ float fl_wave_sum(float x)
-{
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
-    return x;     // (lane 0's)
-}
-
-// The launch's sums of kSlots values: `s_row` [kSlots] holds this workgroup's (in LDS, behind a barrier).  Returns true in every
-// thread of the workgroup that finishes last, with the totals in `s_tot` [kSlots]; false in all the others.  The rows are added
-// in workgroup-index order — kFlThreads / kSlots runs of consecutive rows side by side, then the runs in order — and left
-// zeroed.  The hand-off is sum_over_workgroups' (fr_common.hpp): write-through stores, every storing wave waits for its own,
-// a barrier, ONE thread counts the workgroup in; the reader fetches every partial with an agent-scope atomic load, which does
-// not go through its compute unit's L1, so there is no stale line to drop.
+// a launch's sums of kSlots <= kFlRow values, one row per workgroup: kFlThreads / kSlots whole runs of rows, 32 rows in flight
 template <unsigned kSlots>
-__device__ __forceinline__ bool flame_sum_rows(const float* s_row, float* s_tot, float* s_chunk, bool* s_last, float* partial,
-                                               unsigned* counter)
-{
-    static_assert(kSlots <= kFlRow && kFlThreads % kSlots == 0, "whole runs");
-    constexpr unsigned kChunks = kFlThreads / kSlots;
-    if (threadIdx.x < kSlots)
-        __hip_atomic_store(partial + (size_t)blockIdx.x * kSlots + threadIdx.x, s_row[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) *s_last = last_workgroup_of(counter, blockIdx.x, gridDim.x);
-    __syncthreads();
-    if (!*s_last) return false;
-    const unsigned chunk = threadIdx.x / kSlots, col = threadIdx.x % kSlots;
-    const unsigned per = (gridDim.x + kChunks - 1) / kChunks;
-    const unsigned b0 = chunk * per < gridDim.x ? chunk * per : gridDim.x, b1 = b0 + per < gridDim.x ? b0 + per : gridDim.x;
-    // kDepth loads in flight per thread (they miss every cache: a round trip apiece if issued one by one), added in row order
-    constexpr unsigned kDepth = 32;
-    float tot = 0.f;
-    for (unsigned b = b0; b < b1; b += kDepth) {
-        float v[kDepth];
-#pragma unroll
-        for (unsigned k = 0; k < kDepth; k++)
-            v[k] = b + k < b1 ? __hip_atomic_load(partial + (size_t)(b + k) * kSlots + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-#pragma unroll
-        for (unsigned k = 0; k < kDepth; k++) tot += v[k];
-    }
-    for (unsigned b = b0; b < b1; b++) __hip_atomic_store(partial + (size_t)b * kSlots + col, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_chunk[threadIdx.x] = tot;
-    __syncthreads();
-    if (threadIdx.x < kSlots) {
-        float v = s_chunk[threadIdx.x];
-#pragma unroll
-        for (unsigned c = 1; c < kChunks; c++) v += s_chunk[c * kSlots + threadIdx.x];
-        s_tot[threadIdx.x] = v;
-    }
-    __syncthreads();
-    return true;
-}
+using FlRowSums = RowSums<kFlThreads, kSlots, 1, 32>;
 
 // ---- Rodrigues and the chain, by ONE thread (their arrays live in LDS: the parents are run-time indices)
 struct FlRod {
@@ -295,8 +235,7 @@ __global__ void __launch_bounds__(kFlThreads) k_flame_shape(FlameArgs a)
 {
     __shared__ float s_e[FR_FLAME_MAX_E];
     __shared__ float s_red[kFlThreads / 64][32];
-    __shared__ float s_row[32], s_tot[32], s_chunk[kFlThreads];
-    __shared__ bool s_last;
+    __shared__ FlRowSums<32> s_sum;
     __shared__ FlChain s_chain[2];
     __shared__ float s_A[2][kFlJ * 12];
     const bool orig = a.verts_orig != nullptr;
@@ -327,10 +266,10 @@ __global__ void __launch_bounds__(kFlThreads) k_flame_shape(FlameArgs a)
             }
         }
 #pragma unroll
-        for (int k = 0; k < 3; k++) d[k] = fl_group_sum(d[k]);
+        for (int k = 0; k < 3; k++) d[k] = group_sum<kFlGroup>(d[k]);
         if (orig) {
 #pragma unroll
-            for (int k = 0; k < 3; k++) o[k] = fl_group_sum(o[k]);
+            for (int k = 0; k < 3; k++) o[k] = group_sum<kFlGroup>(o[k]);
         }
         // (the sweep's last shuffle is behind us; a dead group adds nothing)
         if (live) {
@@ -356,18 +295,18 @@ __global__ void __launch_bounds__(kFlThreads) k_flame_shape(FlameArgs a)
     const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        const float x = fl_groups_sum(aj[k], sub), y = fl_groups_sum(ao[k], sub);
+        const float x = groups_sum16(aj[k], sub), y = groups_sum16(ao[k], sub);
         if (lane < (unsigned)kFlJ) s_red[wave][lane * 3u + k] = x, s_red[wave][15u + lane * 3u + k] = orig ? y : 0.f;
     }
     if (lane >= 30u && lane < 32u) s_red[wave][lane] = 0.f;
     __syncthreads();
-    if (threadIdx.x < 32u) s_row[threadIdx.x] = ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
+    if (threadIdx.x < 32u) s_sum.row[threadIdx.x] = ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
     __syncthreads();
-    if (!flame_sum_rows<32>(s_row, s_tot, s_chunk, &s_last, a.partial, a.counter)) return;
+    if (!sum_rows_over_workgroups(s_sum, a.partial, a.counter)) return;
     const unsigned which = threadIdx.x >> 6;       // wave 0's first lane: the delta mesh; wave 1's: the plain one
     if (lane != 0u || which > (orig ? 1u : 0u)) return;
     FlChain& c = s_chain[which];
-    fl_chain_forward(a, s_tot + 15u * which, c, s_A[which]);
+    fl_chain_forward(a, s_sum.row + 15u * which, c, s_A[which]);
     float* const A_out = a.state + (which ? kStAo : kStA);
     for (int e = 0; e < kFlJ * 12; e++) A_out[e] = s_A[which][e];
     if (which) return;
@@ -454,8 +393,7 @@ __global__ void __launch_bounds__(kFlThreads) k_flame_bwd_pose(FlameArgs a)
     __shared__ float s_A[kFlJ * 12];
     __shared__ float s_dvp[kFlSkinElems];
     __shared__ float s_red[kFlThreads / 64][kFlPhi];
-    __shared__ float s_row[kFlRow], s_tot[kFlRow], s_chunk[kFlThreads];
-    __shared__ bool s_last;
+    __shared__ FlRowSums<kFlRow> s_sum;
     __shared__ FlChain s_chain;
     const unsigned t = threadIdx.x;
     if (t < (unsigned)kFlPhi) s_phi[t] = a.state[kStPhi + t];
@@ -513,20 +451,20 @@ __global__ void __launch_bounds__(kFlThreads) k_flame_bwd_pose(FlameArgs a)
     const unsigned wave = t >> 6, lane = t & 63u;
 #pragma unroll
     for (int e = 0; e < kFlJ * 12; e++) {
-        const float x = fl_wave_sum(accA[e]);
-        if (t == 0u) s_row[e] = x;
+        const float x = wave_sum(accA[e]);
+        if (t == 0u) s_sum.row[e] = x;
     }
 #pragma unroll
     for (int i = 0; i < kFlPhi; i++) {
-        const float x = fl_wave_sum(accP[i]);
+        const float x = wave_sum(accP[i]);
         if (lane == 0u) s_red[wave][i] = x;
     }
-    if (t >= 96u && t < kFlRow) s_row[t] = 0.f;
+    if (t >= 96u && t < kFlRow) s_sum.row[t] = 0.f;
     __syncthreads();
-    if (t < (unsigned)kFlPhi) s_row[60u + t] = ((s_red[0][t] + s_red[1][t]) + s_red[2][t]) + s_red[3][t];
+    if (t < (unsigned)kFlPhi) s_sum.row[60u + t] = ((s_red[0][t] + s_red[1][t]) + s_red[2][t]) + s_red[3][t];
     __syncthreads();
-    if (!flame_sum_rows<kFlRow>(s_row, s_tot, s_chunk, &s_last, a.partial, a.counter)) return;
-    if (t == 0u) fl_chain_backward(a, s_tot, s_chain);
+    if (!sum_rows_over_workgroups(s_sum, a.partial, a.counter)) return;
+    if (t == 0u) fl_chain_backward(a, s_sum.row, s_chain);
 }
 
 // ---- backward, launch two: d_v_shaped, d_delta_vertex, d_delta_exp and the sums of d_expression
@@ -535,8 +473,7 @@ __global__ void __launch_bounds__(kFlThreads) k_flame_bwd_shape(FlameArgs a)
     __shared__ float s_e[FR_FLAME_MAX_E];
     __shared__ float s_dJ[kFlJ * 3];
     __shared__ float s_red[kFlThreads / 64][kFlRow];
-    __shared__ float s_row[kFlRow], s_tot[kFlRow], s_chunk[kFlThreads];
-    __shared__ bool s_last;
+    __shared__ FlRowSums<kFlRow> s_sum;
     for (unsigned t = threadIdx.x; t < (unsigned)FR_FLAME_MAX_E; t += blockDim.x) s_e[t] = t < (unsigned)a.NE ? a.expr[t] : 0.f;
     if (threadIdx.x < (unsigned)kFlJ * 3u) s_dJ[threadIdx.x] = a.state[kStDJ + threadIdx.x];
     __syncthreads();
@@ -577,15 +514,15 @@ __global__ void __launch_bounds__(kFlThreads) k_flame_bwd_shape(FlameArgs a)
     const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
 #pragma unroll
     for (unsigned q = 0; q < kFlAccE; q++) {
-        const float x = fl_groups_sum(acc[q], sub);
+        const float x = groups_sum16(acc[q], sub);
         if (lane < kFlGroup) s_red[wave][q * kFlGroup + sub] = x;
     }
     __syncthreads();
     if (threadIdx.x < kFlRow)
-        s_row[threadIdx.x] = ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
+        s_sum.row[threadIdx.x] = ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
     __syncthreads();
-    if (!flame_sum_rows<kFlRow>(s_row, s_tot, s_chunk, &s_last, a.partial, a.counter)) return;
-    if (a.d_expr && threadIdx.x < NE) a.d_expr[threadIdx.x] = s_tot[threadIdx.x];
+    if (!sum_rows_over_workgroups(s_sum, a.partial, a.counter)) return;
+    if (a.d_expr && threadIdx.x < NE) a.d_expr[threadIdx.x] = s_sum.row[threadIdx.x];
 }
 
 // ---- host side

@@ -44,17 +44,10 @@ __global__ void __launch_bounds__(256) k_bind_phong_frame_bwd(BindArgs a, const 
 }
 
 // kRowLanes consecutive lanes share a vertex: lane l of the group takes the row's entries l, l + kRowLanes, ...; the partial
-// sums meet in an xor butterfly (4, 2, 1), the same order on every launch, and lane 0 of the group finishes.  Every lane of a
+// sums meet in an xor butterfly (group_sum: 4, 2, 1), the same order on every launch, and lane 0 of the group finishes.  Every lane of a
 // wave reaches the shuffles (a group past V walks an empty row).
 constexpr int kRowLanes = 8;
 constexpr int kVertsPerBlock = 256 / kRowLanes;
-
-__device__ __forceinline__ float row_sum(float x)
-{
-#pragma unroll
-    for (int m = kRowLanes / 2; m > 0; m >>= 1) x += __shfl_xor(x, m, kRowLanes);
-    return x;
-}
 
 __global__ void __launch_bounds__(256) k_phong_sums_bwd(PhongFrameBwdArgs a)
 {
@@ -62,9 +55,9 @@ __global__ void __launch_bounds__(256) k_phong_sums_bwd(PhongFrameBwdArgs a)
     Vec3 ns = {0.f, 0.f, 0.f};
     float qs[4] = {0.f, 0.f, 0.f, 0.f};
     if (v < a.V) phong_vertex_sums_partial(a, v, lane, kRowLanes, ns, qs);
-    ns.x = row_sum(ns.x), ns.y = row_sum(ns.y), ns.z = row_sum(ns.z);
+    ns.x = group_sum<kRowLanes>(ns.x), ns.y = group_sum<kRowLanes>(ns.y), ns.z = group_sum<kRowLanes>(ns.z);
 #pragma unroll
-    for (int k = 0; k < 4; k++) qs[k] = row_sum(qs[k]);
+    for (int k = 0; k < 4; k++) qs[k] = group_sum<kRowLanes>(qs[k]);
     if (v < a.V && lane == 0) phong_vertex_sums_finish(a, v, ns, qs);
 }
 
@@ -73,7 +66,7 @@ __global__ void __launch_bounds__(256) k_phong_gather_bwd(PhongFrameBwdArgs a)
     const int v = blockIdx.x * kVertsPerBlock + threadIdx.x / kRowLanes, lane = threadIdx.x % kRowLanes;
     Vec3 acc = {0.f, 0.f, 0.f};
     if (v < a.V) acc = phong_vertex_gather_partial(a, v, lane, kRowLanes);
-    acc.x = row_sum(acc.x), acc.y = row_sum(acc.y), acc.z = row_sum(acc.z);
+    acc.x = group_sum<kRowLanes>(acc.x), acc.y = group_sum<kRowLanes>(acc.y), acc.z = group_sum<kRowLanes>(acc.z);
     if (v < a.V && lane == 0) phong_vertex_gather_finish(a, v, acc);
 }
 

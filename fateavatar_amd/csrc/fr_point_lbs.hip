@@ -32,11 +32,11 @@
 // x has the forward's bits) and the running sums a lane keeps for the slots it owns: columns sub, sub + 16, ... of S, elements
 // sub, sub + 16, ... of P (folded three to a pose feature at the very end) and, in lane j < J, the twelve products of bone j.
 // A dead group adds exact zeros and stays with its wave.  After the sweep: the wave's four groups in index order (shuffles), the
-// workgroup's waves in index order (LDS), one row of 272 partials per workgroup stored write-through, and the workgroup that
-// finishes last (last_workgroup_of, as sum_over_workgroups) adds the rows up in workgroup-index order (fifteen runs of consecutive rows
-// side by side, then the runs in order), writes the three outputs and leaves the workspace zeroed: no float atomics, the same
-// bits on every launch.  Workgroups of 1 024 threads, at most one per CU (256): the last workgroup's serial read grows with the
-// number of rows, not with N.  Compiler (gfx950): 123 VGPRs, no scratch, 18 580 B of LDS, four waves per SIMD = the one
+// workgroup's waves in index order (LDS), one row of 272 partials per workgroup, and the workgroup that finishes last adds the
+// rows up in workgroup-index order (sum_rows_over_workgroups, fr_common.hpp: fifteen runs of consecutive rows side by side, one
+// float4 column per thread, then the runs in order), writes the three outputs and leaves the workspace zeroed: no float atomics,
+// the same bits on every launch.  Workgroups of 1 024 threads, at most one per CU (256): the last workgroup's serial read grows with the
+// number of rows, not with N.  Compiler (gfx950): 123 VGPRs, no scratch, 18 592 B of LDS, four waves per SIMD = the one
 // resident workgroup.  Measured on the MI355X at N = 100 000, E = 50, J = 6 (profiles/r19_mono_pose.md): 0.072 ms a launch,
 // i.e. the 1 080 B a point's S, P, w, p and g rows hold are read at 1.50 TB/s = 24 % of the achievable HBM rate, 45 x faster
 // than the float32 torch backward to the frame state.  The same code as 512 workgroups of 256 threads (two waves per SIMD, 512
@@ -86,12 +86,6 @@ __device__ __forceinline__ void lbs_stage(const LbsArgs& a, LbsShared& s)
     __syncthreads();
 }
 
-__device__ __forceinline__ float group_sum(float v)
-{
-    for (int off = kLbsGroup / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kLbsGroup);
-    return v;
-}
-
 // the blendshape offset S (beta - beta_c) + P^T (phi - phi_c) of point i, in every lane of its group
 __device__ __forceinline__ void lbs_offset(const LbsArgs& a, const LbsShared& s, size_t i, unsigned sub, bool live, float o[3])
 {
@@ -110,7 +104,7 @@ __device__ __forceinline__ void lbs_offset(const LbsArgs& a, const LbsShared& s,
             acc0 += k == 0u ? v : 0.f, acc1 += k == 1u ? v : 0.f, acc2 += k == 2u ? v : 0.f;
         }
     }
-    o[0] = group_sum(acc0), o[1] = group_sum(acc1), o[2] = group_sum(acc2);
+    o[0] = group_sum<kLbsGroup>(acc0), o[1] = group_sum<kLbsGroup>(acc1), o[2] = group_sum<kLbsGroup>(acc2);
 }
 
 struct LbsPoint {
@@ -290,10 +284,14 @@ constexpr unsigned kPoseAcc = kPoseS + kPoseP + 12;                          // 
 constexpr unsigned kPoseOffP = kPoseS * kLbsGroup;                           // slot of P's element 0 (64)
 constexpr unsigned kPoseOffT = kPoseOffP + kPoseP * kLbsGroup;               // slot of the bones' sums (176), [12][FR_LBS_MAX_J]
 constexpr unsigned kPoseSlots = kPoseOffT + 12 * FR_LBS_MAX_J;               // 272 floats = 68 float4 per workgroup
-constexpr unsigned kPoseChunks = kPoseThreads / (kPoseSlots / 4);            // 15 runs of rows in the last workgroup
-static_assert(kPoseSlots % 4 == 0 && kPoseChunks >= 1 && kPoseChunks < kPoseWaves, "one float4 column per thread of the last "
-              "workgroup; the runs' sums and their total share the waves' rows of LDS");
-static_assert(done_workspace_bytes(0) % 16 == 0, "the partials are read sixteen bytes at a time");
+// the waves' rows of sums, then — their content read — the workgroup's row and the last workgroup's runs in the same LDS
+using PoseRowSums = RowSums<kPoseThreads, kPoseSlots, 4, 8>;
+union PoseLds {
+    float red[kPoseWaves][kPoseSlots];
+    PoseRowSums sum;
+};
+static_assert(PoseRowSums::kChunks == 15 && PoseRowSums::kChunks < kPoseWaves && offsetof(PoseRowSums, row) == 0,
+              "the row lies over wave 0's slots, the runs over the other waves'");
 
 struct LbsPoseOut {
     float *d_betas, *d_phi, *d_A;   // [E], [36], [J,16]; any may be null
@@ -310,8 +308,7 @@ __device__ __forceinline__ unsigned pose_slot(unsigned acc, unsigned sub)
 __global__ void __launch_bounds__(kPoseThreads) k_point_lbs_pose_bwd(LbsArgs a, LbsPoseOut out)
 {
     __shared__ LbsShared s;
-    __shared__ float s_red[kPoseWaves][kPoseSlots];
-    __shared__ bool s_last;
+    __shared__ PoseLds lds;
     lbs_stage(a, s);
     const unsigned sub = threadIdx.x & (kLbsGroup - 1);
     const unsigned group = (blockIdx.x * blockDim.x + threadIdx.x) / kLbsGroup, n_groups = gridDim.x * blockDim.x / kLbsGroup;
@@ -356,7 +353,7 @@ __global__ void __launch_bounds__(kPoseThreads) k_point_lbs_pose_bwd(LbsArgs a, 
                 }
             }
         }
-        o0 = group_sum(o0), o1 = group_sum(o1), o2 = group_sum(o2);
+        o0 = group_sum<kLbsGroup>(o0), o1 = group_sum<kLbsGroup>(o1), o2 = group_sum<kLbsGroup>(o2);
         // (the sweep's last shuffle is behind us; a dead group adds nothing: exact zeros)
         if (live && sub < (unsigned)a.J) {
             const float x0 = q.z[0] + o0, x1 = q.z[1] + o1, x2 = q.z[2] + o2;
@@ -372,61 +369,21 @@ __global__ void __launch_bounds__(kPoseThreads) k_point_lbs_pose_bwd(LbsArgs a, 
     const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
 #pragma unroll
     for (unsigned t = 0; t < kPoseAcc; t++) {
-        const float v0 = __shfl(acc[t], (int)sub), v1 = __shfl(acc[t], (int)(sub + 16u)), v2 = __shfl(acc[t], (int)(sub + 32u)),
-                    v3 = __shfl(acc[t], (int)(sub + 48u));
-        const float v = ((v0 + v1) + v2) + v3;
-        if (lane < kLbsGroup && (t < kPoseS + kPoseP || sub < (unsigned)FR_LBS_MAX_J)) s_red[wave][pose_slot(t, sub)] = v;
+        const float v = groups_sum16(acc[t], sub);
+        if (lane < kLbsGroup && (t < kPoseS + kPoseP || sub < (unsigned)FR_LBS_MAX_J)) lds.red[wave][pose_slot(t, sub)] = v;
     }
     __syncthreads();
-    // write-through stores, every storing wave waits for its own, then ONE thread counts the workgroup in (as sum_over_workgroups)
-    float* const row = out.partial + (size_t)blockIdx.x * kPoseSlots;
+    // the row: the waves in index order.  (It lies over wave 0's slots, which thread t alone reads, and reads first.)
     if (threadIdx.x < kPoseSlots) {
-        float v = s_red[0][threadIdx.x];
+        float v = lds.red[0][threadIdx.x];
 #pragma unroll
-        for (unsigned w = 1; w < kPoseWaves; w++) v += s_red[w][threadIdx.x];
-        __hip_atomic_store(row + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const bool last = last_workgroup_of(out.counter, blockIdx.x, gridDim.x);
-        if (last) {
-            // the last workgroup reads the others' rows with plain loads: drop this CU's L1 lines first, and hold the barrier for it
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        s_last = last;
+        for (unsigned w = 1; w < kPoseWaves; w++) v += lds.red[w][threadIdx.x];
+        lds.sum.row[threadIdx.x] = v;
     }
     __syncthreads();
-    if (!s_last) return;
-    // rows in workgroup-index order: kPoseChunks runs of consecutive rows side by side, one float4 column per thread, then the
-    // runs in order; every row is left zeroed
-    constexpr unsigned cols = kPoseSlots / 4;
-    const unsigned chunk = threadIdx.x / cols, col = threadIdx.x % cols;
-    const unsigned per = (gridDim.x + kPoseChunks - 1) / kPoseChunks;
-    if (chunk < kPoseChunks) {
-        const unsigned b0 = chunk * per < gridDim.x ? chunk * per : gridDim.x, b1 = b0 + per < gridDim.x ? b0 + per : gridDim.x;
-        float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 8
-        for (unsigned b = b0; b < b1; b++) {
-            float* at = out.partial + (size_t)b * kPoseSlots + col * 4u;
-            const float4 v = *reinterpret_cast<const float4*>(at);
-            tot.x += v.x, tot.y += v.y, tot.z += v.z, tot.w += v.w;
-#pragma unroll
-            for (int k = 0; k < 4; k++) __hip_atomic_store(at + k, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        float* dst = &s_red[chunk][col * 4u];           // (the waves' rows: their earlier content has been read)
-        dst[0] = tot.x, dst[1] = tot.y, dst[2] = tot.z, dst[3] = tot.w;
-    }
-    __syncthreads();
-    if (threadIdx.x < kPoseSlots) {
-        float v = s_red[0][threadIdx.x];
-#pragma unroll
-        for (unsigned c = 1; c < kPoseChunks; c++) v += s_red[c][threadIdx.x];
-        s_red[kPoseChunks][threadIdx.x] = v;
-    }
-    __syncthreads();
-    const float* fin = s_red[kPoseChunks];
+    // the launch's sums: fifteen runs of rows, one float4 column per thread, eight rows in flight
+    if (!sum_rows_over_workgroups(lds.sum, out.partial, out.counter)) return;
+    const float* fin = lds.sum.row;
     const unsigned t = threadIdx.x;
     if (out.d_betas && t < E) out.d_betas[t] = fin[t];
     if (out.d_phi && t < (unsigned)kLbsPose) out.d_phi[t] = (fin[kPoseOffP + 3u * t] + fin[kPoseOffP + 3u * t + 1u]) + fin[kPoseOffP + 3u * t + 2u];

@@ -1,15 +1,20 @@
-"""The fused loss kernels end with ONE reduction (sum_over_workgroups, csrc/fr_common.hpp): per-workgroup partials, added up by
-the workgroup that finishes last, which leaves the workspace as it found it.  Every user of it is run here at the workgroup
-counts where that tail changes its path: 1, 15, 16 and 17 (last_workgroup_of's counter groups fill up at 16), the op's grid cap
-(four partials per thread of the last workgroup) and one past it (the grid stays at the cap and sweeps twice).  Everything
-asserted is exact: equal bits from launch to launch and from a fresh workspace, and a zero workspace afterwards.  The values
-against float64 are held by the ops' own tests."""
+"""A launch's sums across its workgroups have ONE protocol in two helpers (csrc/fr_common.hpp): per-workgroup partials, added up
+by the workgroup that finishes last, which leaves the workspace as it found it.  sum_over_workgroups adds a few scalars (every
+fused loss kernel ends with it), sum_rows_over_workgroups a whole row of sums (FLAME's three reducing kernels, the point
+deformation's backward to the frame's pose).  Every user of either is run here at the workgroup counts where that tail changes
+its path: 1, 15, 16 and 17 (last_workgroup_of's counter groups fill up at 16; the pose backward's fifteen runs of rows go from
+one row each to two, with empty trailing runs), the op's grid cap (1024: four partials per thread of the scalar helper's last
+workgroup; 256 for the row helper's users) and one past it (the grid stays at the cap and sweeps twice).  Everything asserted is
+exact: equal bits from launch to launch and from a fresh workspace, and a zero workspace afterwards.  The values against
+float64 are held by the ops' own tests."""
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 CAP = 1024                      # kL1MaxBlocks = kRegMaxBlocks = kMeshMaxBlocks = kTermsMaxBlocks
 COUNTS = (1, 15, 16, 17, CAP, CAP + 1)
+ROW_CAP = 256                   # kFlMaxBlocks = kPoseMaxBlocks: the grid cap of sum_rows_over_workgroups' users
+ROW_COUNTS = (1, 15, 16, 17, ROW_CAP, ROW_CAP + 1)
 COUNTER_BYTES = 17 * 128        # (kDoneGroups + 1) counters, one 128-byte line each
 # [C,H,W] -> C x ceil(H / 32) x ceil(W / 32) workgroups; the image loss has no cap
 IMAGE_SHAPES = {1: (1, 32, 32), 15: (3, 32, 160), 16: (1, 128, 128), 17: (1, 32, 544)}
@@ -136,18 +141,77 @@ def _image(b, dev, gen):
     return (lambda ws: list(image_loss_and_grad(x, y, (0.8, 0.2), workspace=ws))), (lambda: image_loss_workspace(dev, *shape))
 
 
-# op -> (case builder, partial floats the kernel promises to leave zeroed; None: no promise), with the counts it is run at
-OPS = {"l1": (_l1, None), "l1_batch": (_l1_batch, None), "l1_terms": (_l1_terms, CAP), "huber": (_huber, 2 * CAP),
-       "pixel": (_pixel, 2 * CAP), "scale_term": (_scale_term, 2 * CAP), "regulariser": (_regulariser, 2 * CAP),
-       "mesh": (_mesh, 2 * CAP), "lbs": (_lbs, 3 * CAP), "image": (_image, 0)}
-CASES = [(op, b) for op in OPS for b in (IMAGE_SHAPES if op == "image" else COUNTS)]
+def _mono_pose(b, dev, gen):
+    """deform_points' backward to the frame's pose state: a workgroup of 1024 threads takes 64 points, a row is 272 sums."""
+    import torch
+    from fateavatar_amd.mono import PoseState, deform_points, pose_workspace
+    from tests import mono_ref
+    p, S, P, w, c, f, g = mono_ref.recipe(64 * b, 3, 2, seed=int(gen.initial_seed()))
+    x = [t.float().to(dev).contiguous() for t in (p, S, P, w)]
+    c, f, g = PoseState(*(t.float().to(dev) for t in c)), [t.float().to(dev) for t in f], g.float().to(dev)
+
+    def run(ws):
+        frame = [t.clone().requires_grad_(True) for t in f]
+        xyz = deform_points(*x, c, PoseState(*frame), frame_grad=True, workspace=ws)
+        return list(torch.autograd.grad(xyz, frame, g))                  # d_betas, d_pose_feature, d_transforms
+    return run, (lambda: pose_workspace(dev))
+
+
+class _FlameWorkspace:
+    """A FlameMesh owns its workspace: a fresh one is a fresh mesh over the same tables."""
+
+    def __init__(self, make):
+        self.fm = make()
+        self.zeroed = self.fm.workspace_zeroed_part()
+        assert self.zeroed.numel() == COUNTER_BYTES + 4 * ROW_CAP * 128       # (the promise covers all of it)
+
+
+def _flame(b, dev, gen):
+    """FLAME forward and backward on two meshes, a workspace each: V = 16 b (the two sixteen-lanes-per-vertex kernels run b
+    workgroups) and V = 64 b (the two 64-vertices-per-workgroup kernels do).  Rows of 32, 128 and 128 sums."""
+    import torch
+    from fateavatar_amd.flame import synthetic_flame
+    cases = []
+    for V in (16 * b, 64 * b):
+        template = _rand(gen, V, 3).numpy()
+        deltas = 1e-3 * (_rand(gen, V * 3 * 3 + 36 * 3 * V + 3 * V) - 0.5)
+        e, p, g = (_rand(gen, 3) - 0.5).to(dev), (0.2 * (_rand(gen, 15) - 0.5)).to(dev), (_rand(gen, V, 3) - 0.5).to(dev)
+
+        def make(template=template, deltas=deltas):
+            fm = synthetic_flame(template, seed=1, n_shape=1, n_exp=3, device=dev)
+            with torch.no_grad():
+                fm.flat.copy_(deltas)
+            return fm
+        cases.append((make, e, p, g))
+
+    def run(wss):
+        outs = []
+        for (_, e, p, g), ws in zip(cases, wss):
+            fm = ws.fm
+            verts, orig = torch.empty_like(g), torch.empty_like(g)
+            phi, A = torch.empty(36, device=dev), torch.empty(5, 4, 4, device=dev)
+            d_e, d_p = torch.empty_like(e), torch.empty_like(p)
+            fm.forward_into(e, p, verts, orig, phi, A)
+            fm.backward_from(g, e, p, d_e, d_p)
+            outs += [verts, orig, phi, A, fm.flat_grad, d_e, d_p]
+        return outs
+    return run, (lambda: tuple(_FlameWorkspace(make) for make, *_ in cases))
+
+
+# op -> (case builder, partial floats the kernel promises to leave zeroed (None: no promise), the counts it is run at)
+OPS = {"l1": (_l1, None, COUNTS), "l1_batch": (_l1_batch, None, COUNTS), "l1_terms": (_l1_terms, CAP, COUNTS),
+       "huber": (_huber, 2 * CAP, COUNTS), "pixel": (_pixel, 2 * CAP, COUNTS), "scale_term": (_scale_term, 2 * CAP, COUNTS),
+       "regulariser": (_regulariser, 2 * CAP, COUNTS), "mesh": (_mesh, 2 * CAP, COUNTS), "lbs": (_lbs, 3 * CAP, COUNTS),
+       "image": (_image, 0, tuple(IMAGE_SHAPES)), "mono_pose": (_mono_pose, ROW_CAP * 272, ROW_COUNTS),
+       "flame": (_flame, ROW_CAP * 128, ROW_COUNTS)}
+CASES = [(op, b) for op, (_, _, counts) in OPS.items() for b in counts]
 
 
 @pytest.mark.parametrize("op,b", CASES, ids=[f"{op}-{b}" for op, b in CASES])
 def test_same_bits_on_every_launch_and_the_workspace_left_zeroed(gpu_device, op, b):
     import torch
     dev = gpu_device
-    build, partial_floats = OPS[op]
+    build, partial_floats, _ = OPS[op]
     run, fresh = build(b, dev, torch.Generator().manual_seed(1000 + b))
     if op == "image":
         partial_floats = 2 * b
@@ -155,7 +219,8 @@ def test_same_bits_on_every_launch_and_the_workspace_left_zeroed(gpu_device, op,
     def launch(ws):
         outs = run(ws)
         torch.cuda.synchronize()
-        for w in (ws if isinstance(ws, tuple) else (ws,)):     # (l1_batch: one workspace per image)
+        for w in (ws if isinstance(ws, tuple) else (ws,)):     # (l1_batch: one workspace per image; flame: one per mesh)
+            w = w.zeroed if isinstance(w, _FlameWorkspace) else w
             assert int(w[:COUNTER_BYTES].count_nonzero()) == 0, "counters"
             if partial_floats is not None:
                 assert int(w[COUNTER_BYTES:COUNTER_BYTES + 4 * partial_floats].count_nonzero()) == 0, "partials"
