@@ -203,7 +203,7 @@ EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile
            "fr_point_lbs_forward", "fr_point_lbs_backward", "fr_point_lbs_pose_workspace_bytes", "fr_point_lbs_backward_pose", "fr_nearest_vertex", "fr_lbs_terms_workspace_bytes", "fr_lbs_terms",
            "fr_mlp_workspace_bytes", "fr_mlp_forward", "fr_mlp_backward",
            "fr_flame_workspace_bytes", "fr_flame_workspace_zeroed_bytes", "fr_flame_forward", "fr_flame_backward",
-           "fr_vgg_workspace_bytes", "fr_vgg_loss_grad"]
+           "fr_vgg_workspace_bytes", "fr_vgg_loss_grad", "fr_lpips_workspace_bytes", "fr_lpips_loss_grad"]
 
 
 def build(force: bool = False) -> str:
@@ -384,6 +384,10 @@ def lib():
     L.fr_vgg_workspace_bytes.restype = C.c_size_t
     L.fr_vgg_loss_grad.argtypes = [C.POINTER(fr_vgg), C.c_float, C.c_int, _fp, _fp, C.c_void_p, C.c_void_p]
     L.fr_vgg_loss_grad.restype = C.c_int
+    L.fr_lpips_workspace_bytes.argtypes = [C.POINTER(fr_vgg)]
+    L.fr_lpips_workspace_bytes.restype = C.c_size_t
+    L.fr_lpips_loss_grad.argtypes = [C.POINTER(fr_vgg), _fp, C.c_float, C.c_int, _fp, _fp, C.c_void_p, C.c_void_p]
+    L.fr_lpips_loss_grad.restype = C.c_int
     L.fr_ssim_window.argtypes = [C.POINTER(C.c_float)]
     L.fr_ssim_window.restype = None
     L.fr_image_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

@@ -903,4 +903,27 @@ int fr_vgg_loss_grad(const fr_vgg* vgg, float weight, int accumulate, float* los
     return launch_vgg_loss_grad(*vgg, weight, accumulate, loss_out, d_image, workspace, static_cast<hipStream_t>(stream));
 }
 
+size_t fr_lpips_workspace_bytes(const fr_vgg* vgg) { return lpips_invalid(vgg) ? 0 : lpips_workspace_bytes(*vgg); }
+
+int fr_lpips_loss_grad(const fr_vgg* vgg, const float* lin, float weight, int accumulate, float* loss_out, float* d_image, void* workspace,
+                       void* stream)
+{
+    const char* why = lpips_invalid(vgg);
+    if (!why && (!vgg->weights_fwd || !vgg->weights_bwd || !vgg->image || !vgg->target)) why = "null weights, image or target";
+    if (!why && !lin) why = "null lin";
+    if (!why && !loss_out) why = "null loss_out";
+    if (!why && !workspace) why = "null workspace";
+    if (!why && (reinterpret_cast<uintptr_t>(workspace) & 255)) why = "the workspace must be 256-byte aligned";
+    if (!why && ((reinterpret_cast<uintptr_t>(vgg->weights_fwd) | reinterpret_cast<uintptr_t>(vgg->weights_bwd) | reinterpret_cast<uintptr_t>(lin)) & 15))
+        why = "the packed weights and lin must be 16-byte aligned";
+    if (!why && ((reinterpret_cast<uintptr_t>(vgg->image) | reinterpret_cast<uintptr_t>(vgg->target) |
+                  reinterpret_cast<uintptr_t>(loss_out) | reinterpret_cast<uintptr_t>(d_image)) & 3))
+        why = "float arrays must be 4-byte aligned";
+    if (why) {
+        snprintf(g_err, sizeof(g_err), "fr_lpips_loss_grad: %s", why);
+        return FR_ERR_INVALID_ARGUMENT;
+    }
+    return launch_lpips_loss_grad(*vgg, lin, weight, accumulate, loss_out, d_image, workspace, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

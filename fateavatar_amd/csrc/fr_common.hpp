@@ -572,6 +572,11 @@ int launch_flame_backward(const fr_flame& f, const float* g_verts, float* d_delt
 const char* vgg_invalid(const fr_vgg* v);      // nullptr, or why the descriptor is refused
 size_t vgg_workspace_bytes(const fr_vgg& v);
 int launch_vgg_loss_grad(const fr_vgg& v, float weight, int accumulate, float* loss_out, float* d_image, void* workspace, hipStream_t s);
+// the LPIPS term over the same stack (fr_vgg.hip): the workspace is the VGG layout with the taps' per-pixel scalars and a seed buffer behind it
+const char* lpips_invalid(const fr_vgg* v);
+size_t lpips_workspace_bytes(const fr_vgg& v);
+int launch_lpips_loss_grad(const fr_vgg& v, const float* lin, float weight, int accumulate, float* loss_out, float* d_image, void* workspace,
+                           hipStream_t s);
 int launch_multi_copy(int n_seg, float* const* dst, const float* const* src, const unsigned long long* count, hipStream_t s);
 int launch_selftest_reduce(const float* in, float* out, hipStream_t s);
 

@@ -30,6 +30,8 @@
 // of their own.  The terms' sums go through sum_over_workgroups: per-workgroup partials added by the last workgroup in index
 // order.  The resize's backward is a gather per SOURCE pixel over the output pixels that blend it.  No float atomics.
 // FAST flags (FMA contraction): the products are MFMA either way.
+// The LPIPS term (fr_lpips_loss_grad) runs the same forward and the same gradient GEMMs with another term kind
+// (VGG_TERM_LPIPS): its tap kernels and what they cost are described where they stand, below the L1 term's.
 #include "fr_common.hpp"
 #include "fr_vgg_math.hpp"
 
@@ -43,6 +45,10 @@ constexpr int kVggFullGrid = 256;   // workgroups that fill the device's compute
 static_assert(FR_VGG_REDUCE_BYTES == done_workspace_bytes(FR_VGG_LOSS_BLOCKS), "the header's size of the reduction scratch");
 
 enum { VGG_EPI_BIAS_RELU = 0, VGG_EPI_PLAIN = 1, VGG_EPI_MASK = 2 };
+// What a tap contributes to the gradient in the backward's epilogues, a compile-time kind.  L1: sign(a - a_gt) * tap_scale,
+// computed in place from the two saved activations.  LPIPS: the tap's seed READ from a buffer the seed kernel has filled
+// (`act_gt` then points at it; see the LPIPS section below).  The L1 instantiations contain no trace of the other kind.
+enum { VGG_TERM_L1 = 0, VGG_TERM_LPIPS = 1 };
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -57,7 +63,7 @@ struct VggGemmArgs {
     float* C;              // [M, N]
     const float* bias;     // BIAS_RELU: [N]
     const float* act;      // MASK: the rendered image's saved output of the layer in front, [M, N]
-    const float* act_gt;   // MASK with a tap on that layer: the target's
+    const float* act_gt;   // MASK with a tap on that layer: the target's (L1), or the tap's seed [M, N] (LPIPS)
     float seed_scale;      // SEED: 1 / numel of the last layer's term
     float tap_scale;       // MASK: 1 / numel of that layer's term, 0 without a tap
     int M, N, ca;
@@ -101,7 +107,7 @@ __device__ __forceinline__ void vgg_fetch_a(float (&r)[BM / 8], const VggGemmArg
     }
 }
 
-template <int TM, bool SEED, int EPI>
+template <int TM, bool SEED, int EPI, int KIND = VGG_TERM_L1>
 __global__ void __launch_bounds__(kVggThreads) k_vgg_gemm(VggGemmArgs g)
 {
     constexpr int BM = 64 * TM, BN = 64;
@@ -185,7 +191,7 @@ __global__ void __launch_bounds__(kVggThreads) k_vgg_gemm(VggGemmArgs g)
             if (EPI == VGG_EPI_BIAS_RELU) v = fmaxf(v + bias, 0.f);
             if (EPI == VGG_EPI_MASK) {
                 const float a = g.act[o];
-                if (g.tap_scale != 0.f) v += sign_of(a - g.act_gt[o]) * g.tap_scale;
+                if (g.tap_scale != 0.f) v += KIND == VGG_TERM_LPIPS ? g.act_gt[o] : sign_of(a - g.act_gt[o]) * g.tap_scale;
                 v = a > 0.f ? v : 0.f;
             }
             C[o] = v;
@@ -195,7 +201,7 @@ __global__ void __launch_bounds__(kVggThreads) k_vgg_gemm(VggGemmArgs g)
 
 // A GEMM split over the taps: the planes' partial products added in plane order, then the epilogue the unsplit kernel would have
 // applied.  One thread per four consecutive columns of a row (N is a multiple of 4).
-template <int EPI>
+template <int EPI, int KIND = VGG_TERM_L1>
 __global__ void __launch_bounds__(kVggThreads) k_vgg_split_reduce(VggGemmArgs g, const float* __restrict__ partial, int planes)
 {
     const unsigned i = blockIdx.x * kVggThreads + threadIdx.x, n4 = (unsigned)g.M * (unsigned)g.N / 4u;
@@ -218,7 +224,7 @@ __global__ void __launch_bounds__(kVggThreads) k_vgg_split_reduce(VggGemmArgs g,
             const float4 t4 = reinterpret_cast<const float4*>(g.act_gt)[i];
             const float t[4] = {t4.x, t4.y, t4.z, t4.w};
 #pragma unroll
-            for (int c = 0; c < 4; c++) v[c] += sign_of(a[c] - t[c]) * g.tap_scale;
+            for (int c = 0; c < 4; c++) v[c] += KIND == VGG_TERM_LPIPS ? t[c] : sign_of(a[c] - t[c]) * g.tap_scale;
         }
 #pragma unroll
         for (int c = 0; c < 4; c++) v[c] = a[c] > 0.f ? v[c] : 0.f;
@@ -366,6 +372,7 @@ __global__ void __launch_bounds__(kVggThreads) k_vgg_pool(const float* __restric
 
 // the pool's backward with the layer in front's tap gradient and ReLU mask: dZ[window] of image 0 from the pooled gradient.
 // The gradient goes to the FIRST maximum of the window in row-major order (torch's rule).
+template <int KIND = VGG_TERM_L1>
 __global__ void __launch_bounds__(kVggThreads) k_vgg_unpool(const float* __restrict__ d_pooled, const float* __restrict__ act,
                                                          const float* __restrict__ act_gt, float tap_scale, float* __restrict__ dz, int h,
                                                          int w, int c)
@@ -388,7 +395,7 @@ __global__ void __launch_bounds__(kVggThreads) k_vgg_unpool(const float* __restr
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         float v = k == best ? g : 0.f;
-        if (tap_scale != 0.f) v += sign_of(a[k] - act_gt[at[k]]) * tap_scale;
+        if (tap_scale != 0.f) v += KIND == VGG_TERM_LPIPS ? act_gt[at[k]] : sign_of(a[k] - act_gt[at[k]]) * tap_scale;
         dz[at[k]] = a[k] > 0.f ? v : 0.f;
     }
 }
@@ -413,12 +420,109 @@ __global__ void __launch_bounds__(kSumThreads) k_vgg_tap_loss(const float* __res
     }
 }
 
+// ---- the LPIPS term (fr_lpips_loss_grad): per tap, with a / b the rendered / target feature [h,w,C] and w_c the learnt weights,
+//     n_a(p) = sqrt(sum_c a_c(p)^2),  r_a = 1 / (n_a + 1e-10),  a^ = a r_a        (the same for b)
+//     term   = (1 / (h w)) sum_p sum_c w_c (a^_c - b^_c)^2
+//     dterm/da_c = r_a g_c - a^_c T / n_a,   g_c = 2 w_c (a^_c - b^_c) / (h w),   T = sum_c g_c a^_c
+// A pixel with n == 0 has r = 0 (its hat vector is 0, it contributes sum_c w_c b^_c^2) and T / n_a = 0 (its gradient is exactly
+// 0): stock autograd gives NaN there (sqrt's backward at 0); every unit behind such a pixel is a ReLU at 0 that passes nothing.
+// One wave takes one pixel at a time: lane i holds channels i, 64 + i, .. (C / 64 <= 8 values per image, in registers), the sums
+// over the channels are a per-lane chain in channel order and then the xor butterfly (the same bits in every lane).  The
+// pixels' contributions stay per lane and go through sum_over_workgroups: a fixed grid, fixed orders, no float atomics.
+// It leaves px[p] = (r_a, r_b, T / n_a) for the backward.
+constexpr int kLpipsMaxPerLane = 8;     // C <= 512
+constexpr float kLpipsEps = 1e-10f;
+
+// a r_a - b r_b with both unit values rounded on their own: this unit compiles with -ffp-contract=fast, under which the
+// back end fuses a product into the difference whatever the source says (a contract(off) pragma and __fmul_rn were both
+// tried: the ISA kept v_fma), and the fused form leaves the other product's rounding error behind — identical images must
+// give exactly 0.  The empty asm makes both products opaque to the combiner; it emits no instruction.
+__device__ __forceinline__ float lpips_unit_diff(float a, float r_a, float b, float r_b, float& ah)
+{
+    ah = a * r_a;
+    float bh = b * r_b;
+    asm volatile("" : "+v"(ah), "+v"(bh));
+    return ah - bh;
+}
+
+__global__ void __launch_bounds__(kSumThreads) k_lpips_tap(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ lin,
+                                                         float* __restrict__ px, unsigned P, int C, float* partial, unsigned* counter,
+                                                         float* loss_out, int term, int total_terms)
+{
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int nv = C / 64;
+    float wl[kLpipsMaxPerLane];
+#pragma unroll
+    for (int j = 0; j < kLpipsMaxPerLane; j++) wl[j] = j < nv ? lin[j * 64 + (int)lane] : 0.f;
+    const float two_inv = 2.f / (float)P;
+    float acc[1] = {0.f};
+    for (unsigned p = blockIdx.x * 4u + wave; p < P; p += gridDim.x * 4u) {     // (uniform over the wave)
+        const float* __restrict__ ra = a + (size_t)p * C + lane;
+        const float* __restrict__ rb = b + (size_t)p * C + lane;
+        float va[kLpipsMaxPerLane], vb[kLpipsMaxPerLane];
+        float sa = 0.f, sb = 0.f;
+#pragma unroll
+        for (int j = 0; j < kLpipsMaxPerLane; j++) {
+            va[j] = j < nv ? ra[j * 64] : 0.f, vb[j] = j < nv ? rb[j * 64] : 0.f;
+            sa = fmaf(va[j], va[j], sa), sb = fmaf(vb[j], vb[j], sb);
+        }
+        const float na = sqrtf(group_sum<64>(sa)), nb = sqrtf(group_sum<64>(sb));
+        const float r_a = na > 0.f ? 1.f / (na + kLpipsEps) : 0.f, r_b = nb > 0.f ? 1.f / (nb + kLpipsEps) : 0.f;
+        float s = 0.f, t = 0.f;
+#pragma unroll
+        for (int j = 0; j < kLpipsMaxPerLane; j++) {
+            float ah;
+            const float d = lpips_unit_diff(va[j], r_a, vb[j], r_b, ah), wd = wl[j] * d;
+            s = fmaf(wd, d, s), t = fmaf(wd, ah, t);
+        }
+        acc[0] += s;
+        t = group_sum<64>(t) * two_inv;
+        if (lane == 0) {
+            float* o = px + (size_t)p * 3;
+            o[0] = r_a, o[1] = r_b, o[2] = na > 0.f ? t / na : 0.f;
+        }
+    }
+    if (!sum_over_workgroups(acc, partial, kVggLossBlocks, counter, blockIdx.x, gridDim.x)) return;
+    loss_out[1 + term] = acc[0] / (float)P;
+    if (term + 1 == total_terms) {
+        float s = 0.f;
+        for (int k = 0; k < total_terms; k++) s += loss_out[1 + k];
+        loss_out[0] = s;
+    }
+}
+
+// A tap's gradient seed, already behind the layer's ReLU mask: seed(p, c) = [a > 0] (r_a (2 w_c / (h w)) (a r_a - b r_b) - a r_a T/n_a).
+// One thread per four channels of a pixel.  The LAST tap's seed is that layer's dZ and is written to a gradient buffer; an
+// earlier tap's goes to the seed buffer, which the epilogue that leaves the layer behind it adds (VGG_TERM_LPIPS).
+__global__ void __launch_bounds__(kVggThreads) k_lpips_seed(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ lin,
+                                                          const float* __restrict__ px, float* __restrict__ out, unsigned P, int C)
+{
+    const unsigned c4n = (unsigned)C / 4u, i = blockIdx.x * kVggThreads + threadIdx.x;
+    if (i >= P * c4n) return;
+    const unsigned p = i / c4n, c4 = i - p * c4n;
+    const float r_a = px[(size_t)p * 3], r_b = px[(size_t)p * 3 + 1], tn = px[(size_t)p * 3 + 2];
+    const float two_inv = 2.f / (float)P;
+    const float4 u = reinterpret_cast<const float4*>(a)[i], v = reinterpret_cast<const float4*>(b)[i], w4 = reinterpret_cast<const float4*>(lin)[c4];
+    const float ua[4] = {u.x, u.y, u.z, u.w}, ub[4] = {v.x, v.y, v.z, v.w}, w[4] = {w4.x, w4.y, w4.z, w4.w};
+    float o[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        float ah;
+        const float d = lpips_unit_diff(ua[c], r_a, ub[c], r_b, ah);
+        o[c] = ua[c] > 0.f ? r_a * (two_inv * w[c]) * d - ah * tn : 0.f;
+    }
+    reinterpret_cast<float4*>(out)[i] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
 // ---- host side
 struct VggPlan {
     int n_layers, terms;
     int h[FR_VGG_MAX_LAYERS], w[FR_VGG_MAX_LAYERS];     // layer l's output extent
     size_t wf[FR_VGG_MAX_LAYERS], wb[FR_VGG_MAX_LAYERS];  // float offsets of its packed weights
     size_t off_x, off_act[FR_VGG_MAX_LAYERS], off_pool, off_grad[2], off_raw, off_split, bytes;
+    // LPIPS only, appended BEHIND the layout above (which keeps its offsets): every tap's per-pixel scalars, one seed buffer
+    size_t lin[FR_VGG_MAX_LAYERS];      // float offset of a tapped layer's weights inside `lin`
+    size_t off_px[FR_VGG_MAX_LAYERS], off_seed, lpips_bytes;
 };
 
 // Into how many groups of taps a GEMM of M rows and N columns is split: a grid of 64 x 64 tiles that would leave compute units
@@ -489,14 +593,33 @@ static VggPlan vgg_plan(const fr_vgg& v)
     p.off_raw = o, o += align_up(pool_max * sizeof(float), 256);
     p.off_split = o, o += align_up(split_max * sizeof(float), 256);
     p.bytes = o;
+    size_t lin = 0, seed_max = 0;
+    for (int l = 0; l < v.n_layers; l++) {
+        if (!v.layers[l].tap_after) continue;
+        const size_t px = (size_t)p.h[l] * p.w[l];
+        p.lin[l] = lin, lin += v.layers[l].c_out;
+        p.off_px[l] = o, o += align_up(px * 3 * sizeof(float), 256);
+        if (l + 1 < v.n_layers) seed_max = seed_max > px * v.layers[l].c_out ? seed_max : px * v.layers[l].c_out;
+    }
+    p.off_seed = o, o += align_up(seed_max * sizeof(float), 256);
+    p.lpips_bytes = o;
     return p;
 }
 
 size_t vgg_workspace_bytes(const fr_vgg& v) { return vgg_plan(v).bytes; }
+size_t lpips_workspace_bytes(const fr_vgg& v) { return vgg_plan(v).lpips_bytes; }
+
+const char* lpips_invalid(const fr_vgg* v)
+{
+    if (const char* why = vgg_invalid(v)) return why;
+    for (int l = 0; l < v->n_layers; l++)
+        if (v->layers[l].tap_after && v->layers[l].c_out > 64 * kLpipsMaxPerLane) return "a tapped layer of the LPIPS term has c_out <= 512";
+    return nullptr;
+}
 
 static unsigned vgg_blocks(size_t n) { return (unsigned)((n + kVggThreads - 1) / kVggThreads); }
 
-template <bool SEED, int EPI>
+template <bool SEED, int EPI, int KIND = VGG_TERM_L1>
 static void vgg_gemm(VggGemmArgs g, int tile, float* split_space, hipStream_t s)
 {
     const unsigned ny = (unsigned)((g.N + 63) / 64);
@@ -505,8 +628,8 @@ static void vgg_gemm(VggGemmArgs g, int tile, float* split_space, hipStream_t s)
     const unsigned planes = (tile & FR_VGG_NO_SPLIT) ? 1u : (unsigned)vgg_splits(g.M, g.N);
     g.taps = 9 / (int)planes, g.plane = 0;
     if (planes == 1) {
-        if (big) hipLaunchKernelGGL((k_vgg_gemm<2, SEED, EPI>), dim3(nx128, ny), dim3(kVggThreads), 0, s, g);
-        else hipLaunchKernelGGL((k_vgg_gemm<1, SEED, EPI>), dim3(nx64, ny), dim3(kVggThreads), 0, s, g);
+        if (big) hipLaunchKernelGGL((k_vgg_gemm<2, SEED, EPI, KIND>), dim3(nx128, ny), dim3(kVggThreads), 0, s, g);
+        else hipLaunchKernelGGL((k_vgg_gemm<1, SEED, EPI, KIND>), dim3(nx64, ny), dim3(kVggThreads), 0, s, g);
         return;
     }
     VggGemmArgs part = g;
@@ -514,10 +637,11 @@ static void vgg_gemm(VggGemmArgs g, int tile, float* split_space, hipStream_t s)
     if (big) hipLaunchKernelGGL((k_vgg_gemm<2, SEED, VGG_EPI_PLAIN>), dim3(nx128, ny, planes), dim3(kVggThreads), 0, s, part);
     else hipLaunchKernelGGL((k_vgg_gemm<1, SEED, VGG_EPI_PLAIN>), dim3(nx64, ny, planes), dim3(kVggThreads), 0, s, part);
     g.plane = part.plane;
-    hipLaunchKernelGGL((k_vgg_split_reduce<EPI>), dim3(vgg_blocks((size_t)g.M * g.N / 4)), dim3(kVggThreads), 0, s, g, split_space, (int)planes);
+    hipLaunchKernelGGL((k_vgg_split_reduce<EPI, KIND>), dim3(vgg_blocks((size_t)g.M * g.N / 4)), dim3(kVggThreads), 0, s, g, split_space, (int)planes);
 }
 
-int launch_vgg_loss_grad(const fr_vgg& v, float weight, int accumulate, float* loss_out, float* d_image, void* workspace, hipStream_t s)
+template <int KIND>
+static int vgg_run(const fr_vgg& v, const float* lin, float weight, int accumulate, float* loss_out, float* d_image, void* workspace, hipStream_t s)
 {
     const VggPlan p = vgg_plan(v);
     char* base = static_cast<char*>(workspace);
@@ -563,8 +687,14 @@ int launch_vgg_loss_grad(const fr_vgg& v, float weight, int accumulate, float* l
         inv_n[l] = (float)(1.0 / (double)n);
         if (!v.layers[l].tap_after) continue;
         const float* a = at(p.off_act[l]);
-        hipLaunchKernelGGL(k_vgg_tap_loss, dim3(capped_blocks(n / 4, kSumThreads, kVggLossBlocks)), dim3(kSumThreads), 0, s, a, a + n, (unsigned)n,
-                           done.partial, done.counter, loss_out, term, p.terms);
+        if (KIND == VGG_TERM_LPIPS) {
+            const unsigned P = (unsigned)(p.h[l] * p.w[l]);
+            hipLaunchKernelGGL(k_lpips_tap, dim3(capped_blocks(P, 4, kVggLossBlocks)), dim3(kSumThreads), 0, s, a, a + n, lin + p.lin[l], at(p.off_px[l]),
+                               P, v.layers[l].c_out, done.partial, done.counter, loss_out, term, p.terms);
+        } else {
+            hipLaunchKernelGGL(k_vgg_tap_loss, dim3(capped_blocks(n / 4, kSumThreads, kVggLossBlocks)), dim3(kSumThreads), 0, s, a, a + n, (unsigned)n,
+                               done.partial, done.counter, loss_out, term, p.terms);
+        }
         term++;
     }
     if (!d_image) {
@@ -575,6 +705,18 @@ int launch_vgg_loss_grad(const fr_vgg& v, float weight, int accumulate, float* l
     // ---- the data gradient of the rendered branch, last layer first.  `cur`: dZ of the layer being left (none yet for the last)
     int side = 0;
     const float* cur = nullptr;
+    // LPIPS: a tap's seed from its two activations, the pixels' scalars and its weights
+    auto lpips_seed = [&](int l, float* out) {
+        const unsigned P = (unsigned)(p.h[l] * p.w[l]);
+        const int C = v.layers[l].c_out;
+        const float* a = at(p.off_act[l]);
+        hipLaunchKernelGGL(k_lpips_seed, dim3(vgg_blocks((size_t)P * C / 4)), dim3(kVggThreads), 0, s, a, a + (size_t)P * C, lin + p.lin[l],
+                           at(p.off_px[l]), out, P, C);
+    };
+    if (KIND == VGG_TERM_LPIPS) {       // the last layer's dZ is materialised: the plain (non-SEED) fetch from the start
+        lpips_seed(L - 1, at(p.off_grad[0]));
+        cur = at(p.off_grad[0]), side = 1;
+    }
     for (int l = L - 1; l >= 1; l--) {
         const fr_vgg_layer& y = v.layers[l];
         const fr_vgg_layer& front = v.layers[l - 1];
@@ -588,6 +730,19 @@ int launch_vgg_loss_grad(const fr_vgg& v, float weight, int accumulate, float* l
         g.M = M, g.N = y.c_in, g.ca = y.c_out, g.h = h, g.w = w;
         g.C = y.pool_before ? at(p.off_raw) : next;
         g.act = act, g.act_gt = act_gt, g.tap_scale = tap_scale;
+        if (KIND == VGG_TERM_LPIPS) {
+            if (front.tap_after) lpips_seed(l - 1, at(p.off_seed)), g.act_gt = at(p.off_seed);
+            g.A = cur;
+            if (y.pool_before) {
+                vgg_gemm<false, VGG_EPI_PLAIN>(g, v.tile, at(p.off_split), s);
+                hipLaunchKernelGGL((k_vgg_unpool<VGG_TERM_LPIPS>), dim3(vgg_blocks((size_t)M * y.c_in)), dim3(kVggThreads), 0, s, at(p.off_raw), act,
+                                   g.act_gt, tap_scale, next, 2 * h, 2 * w, y.c_in);
+            } else {
+                vgg_gemm<false, VGG_EPI_MASK, VGG_TERM_LPIPS>(g, v.tile, at(p.off_split), s);
+            }
+            cur = next, side ^= 1;
+            continue;
+        }
         if (cur) {
             g.A = cur;
             if (y.pool_before) vgg_gemm<false, VGG_EPI_PLAIN>(g, v.tile, at(p.off_split), s);
@@ -598,7 +753,7 @@ int launch_vgg_loss_grad(const fr_vgg& v, float weight, int accumulate, float* l
             else vgg_gemm<true, VGG_EPI_MASK>(g, v.tile, at(p.off_split), s);
         }
         if (y.pool_before)
-            hipLaunchKernelGGL(k_vgg_unpool, dim3(vgg_blocks((size_t)M * y.c_in)), dim3(kVggThreads), 0, s, at(p.off_raw), act, act_gt, tap_scale,
+            hipLaunchKernelGGL((k_vgg_unpool<VGG_TERM_L1>), dim3(vgg_blocks((size_t)M * y.c_in)), dim3(kVggThreads), 0, s, at(p.off_raw), act, act_gt, tap_scale,
                                next, 2 * h, 2 * w, y.c_in);
         cur = next, side ^= 1;
     }
@@ -614,6 +769,17 @@ int launch_vgg_loss_grad(const fr_vgg& v, float weight, int accumulate, float* l
     }
     FR_HIP(hipGetLastError());
     return FR_OK;
+}
+
+int launch_vgg_loss_grad(const fr_vgg& v, float weight, int accumulate, float* loss_out, float* d_image, void* workspace, hipStream_t s)
+{
+    return vgg_run<VGG_TERM_L1>(v, nullptr, weight, accumulate, loss_out, d_image, workspace, s);
+}
+
+int launch_lpips_loss_grad(const fr_vgg& v, const float* lin, float weight, int accumulate, float* loss_out, float* d_image, void* workspace,
+                           hipStream_t s)
+{
+    return vgg_run<VGG_TERM_LPIPS>(v, lin, weight, accumulate, loss_out, d_image, workspace, s);
 }
 
 }  // namespace fr

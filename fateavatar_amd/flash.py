@@ -13,7 +13,9 @@ reference:
     rotation = quatProduct_batch(_rotation, (exp(t[3]), t[4:7])), scaling = _scaling * exp(t[7:10]), rendered with
     GaussianModel(sh_degree=0)
   * the loss — FlashAvatarLoss (train/loss.py:203-255): Huber with alpha 0.1, plus 40 x the same on the mouth region if the
-    frame brings a mouth mask
+    frame brings a mouth mask, plus 0.05 x LPIPS once `cur_step > 15000` (config/flashavatar.yaml:16):
+    `FlashStep(lpips=Lpips(..., weight=REFERENCE_LPIPS_WEIGHT), lpips_start=REFERENCE_LPIPS_START)`, opt-in; the term's weights
+    are the caller's to load (`perceptual.Lpips.from_state_dicts`), none are shipped
 What is fused: the binding runs inside the rasterizer's per-Gaussian kernels (bound.render_bound_batch with a DeformBinding;
 `fold_binding=False` keeps the stand-alone op `binding.bind_gaussians_deform` as the A/B), activations and densification
 statistics run inside the rasterizer kernels, one Huber launch, one Adam launch over the flat buffer, the whole step ONE HIP
@@ -28,7 +30,6 @@ the rasterizer `_features_dc` alone (M = 1), as AvatarGaussians' frames do: the 
 place in the flat buffer, its rate and its checkpoint key, and stays exactly 0.
 
 NOT here:
-  * the LPIPS term the reference switches on after 15 000 steps (no VGG)
   * density control (the reference has none for this model) and data-parallel runs of the step
   * batch steps (several frames per update)
 """
@@ -52,6 +53,7 @@ from .train import BoundStep
 # config/flashavatar.yaml:22-25 (group names of train/optim.py:45-51)
 FLASH_LRS = dict(opacity=0.05, feature_dc=0.0025, feature_rest=0.0025 / 20, rotation=0.001, scaling=0.005)
 DEFORM_COLS = 10     # position 3, rotation 4, scale 3 (:247-254)
+REFERENCE_LPIPS_WEIGHT, REFERENCE_LPIPS_START = 0.05, 15_000     # config/flashavatar.yaml:16, train/loss.py:203-255
 
 
 class FlashGaussians(FlatParams):
@@ -127,7 +129,8 @@ class FlashStep(BoundStep):
     def __init__(self, pc: FlashGaussians, faces: torch.Tensor, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True,
                  huber: HuberLoss = REFERENCE_HUBER_LOSS, mouth_mask: bool = False, vertex_grad: bool = False,
-                 deformer: Optional[DeformMLP] = None, deformer_lr: float = 1e-4):
+                 deformer: Optional[DeformMLP] = None, deformer_lr: float = 1e-4, lpips=None,
+                 lpips_start: int = REFERENCE_LPIPS_START):
         """`verts` [V,3]: any pose of the mesh (sizes the step's static vertex buffer and is its first content).
         `fold_binding` (default): the binding is evaluated inside the rasterizer's per-Gaussian kernels (fr_aux::binding with
         FR_BIND_DEFORM).  False: the stand-alone `bind_gaussians_deform` op in front of render() (same results; the A/B and the
@@ -142,7 +145,18 @@ class FlashStep(BoundStep):
         `deform`, and the captured body is MLP forward -> frame -> MLP backward -> the Gaussians' Adam -> an Adam of the
         network's flat buffer at `deformer_lr` (train/optim.py:55-59), skipped by the same overflow word.  `d_cond` [Dc] holds
         THIS step's dLoss/d(cond) (the reference's tracking optimisation of expression and pose), with the lifetime rules of
-        `d_verts`.  None (default): the MLP is the caller's, nothing here changes."""
+        `d_verts`.  None (default): the MLP is the caller's, nothing here changes.
+        `lpips`: a `perceptual.Lpips` adds the LPIPS term from step `lpips_start` + 1 on (the reference multiplies it by 0 until
+        `cur_step > 15000`; here it is not launched before): ONE call behind the Huber launch adds weight x its gradient to the
+        step's image-gradient buffer, in front of the rasterizer's backward.  `lpips_loss` [1 + T] holds the step's UNWEIGHTED
+        terms and stays zero until then; `loss` and `loss_terms` keep their meaning.  The step's number is `host_steps` (step()
+        calls, restored from the Adam count by a checkpoint): no device word is read.  At the crossing the captured graph is
+        dropped ONCE (`lpips_switches` counts it) and the step re-captured with the launch in it, as after an overflow.
+        None (default): not one launch changes."""
+        self._init_lpips(lpips, pc)
+        if int(lpips_start) < 0:
+            raise ValueError("FlashStep: lpips_start is a step count, >= 0")
+        self.lpips_start, self._lpips_on, self.lpips_switches, self.captures = int(lpips_start), False, 0, 0
         if deformer is not None:
             if not isinstance(deformer, DeformMLP):
                 raise TypeError("FlashStep: `deformer` must be a mlp.DeformMLP")
@@ -207,6 +221,8 @@ class FlashStep(BoundStep):
             out = render(self.cam, _FlashFrame(pc, stats, bound=bound), self.bg)
         _, g = huber_loss_and_grad(out["render"], self.gt, self.huber, mask=self.mask, loss_out=self.loss_terms,
                                    grad_out=self._dimage, workspace=self._huber_ws)
+        if self._lpips_on:
+            self._add_lpips(out["render"], g)
         out["render"].backward(g)
         self._keep_vertex_grad(verts)
         self.d_deform = deform.grad      # (inside a captured step: graph-owned storage, the same on every replay)
@@ -218,6 +234,10 @@ class FlashStep(BoundStep):
         super()._body()
         if self.deformer is not None:
             self.deformer_adam.step()
+
+    def _capture(self):
+        self.captures += 1
+        super()._capture()
 
     def step(self, camera: TorchCamera, posed_verts: torch.Tensor, deform: torch.Tensor, gt_image: torch.Tensor,
              mouth_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -237,6 +257,12 @@ class FlashStep(BoundStep):
             extra = [(self.deform, deform.detach())]
         if mouth_mask is not None:
             extra.append((self.mask, mouth_mask.detach().reshape(self.mask.shape)))
+        on = self.lpips is not None and self.host_steps + 1 > self.lpips_start
+        if on != self._lpips_on:       # the schedule's crossing: the captured step does not hold the launch (or holds it: a restored count)
+            self._lpips_on, self._graph, self._eager_steps = on, None, 0
+            self.lpips_switches += 1
+            if not on:
+                self.lpips_loss.zero_()
         return super().step(camera, posed_verts.detach(), gt_image, extra)
 
     # ---- FlashAvatar has no density control, and the step no data-parallel form
@@ -287,4 +313,4 @@ class FlashStep(BoundStep):
         return [k for k in ignored if k not in mine]
 
 
-__all__ = ["DEFORM_COLS", "FLASH_LRS", "FlashGaussians", "FlashStep"]
+__all__ = ["DEFORM_COLS", "FLASH_LRS", "FlashGaussians", "FlashStep", "REFERENCE_LPIPS_START", "REFERENCE_LPIPS_WEIGHT"]

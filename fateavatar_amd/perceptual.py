@@ -42,6 +42,24 @@ VGG16_LAYERS = (ConvLayer(3, 64), ConvLayer(64, 64, tap_after=True),
                 ConvLayer(256, 512, pool_before=True), ConvLayer(512, 512), ConvLayer(512, 512, tap_after=True))
 
 
+# lpips.LPIPS(net='vgg')'s trunk, vgg16.features[:30]: thirteen convolutions, four pools, taps at relu1_2, relu2_2, relu3_3,
+# relu4_3 and relu5_3
+LPIPS_VGG16_LAYERS = VGG16_LAYERS + (ConvLayer(512, 512, pool_before=True), ConvLayer(512, 512), ConvLayer(512, 512, tap_after=True))
+# lpips' ScalingLayer: (x - shift) / scale on an input in [-1, 1]; `normalize=True` maps [0, 1] there first (2 x - 1)
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+LPIPS_MAX_TAP_WIDTH = 512       # a tapped layer's c_out: eight values a lane (include/fr_rasterizer.h)
+
+
+def lpips_mean_std(normalize: bool = True):
+    """(mean, std) with which `(x - mean) / std` is LPIPS's input layer: for `normalize=True` (images in [0, 1], the
+    reference's calls) (2 x - 1 - shift) / scale = (x - (1 + shift) / 2) / (scale / 2), which is the ImageNet statistics;
+    for `normalize=False` (images in [-1, 1]) shift and scale themselves."""
+    if normalize:
+        return tuple((1.0 + s) / 2.0 for s in LPIPS_SHIFT), tuple(s / 2.0 for s in LPIPS_SCALE)
+    return LPIPS_SHIFT, LPIPS_SCALE
+
+
 def as_layers(layers) -> Tuple[ConvLayer, ...]:
     """ConvLayer records from records or plain (c_in, c_out[, pool_before[, tap_after]]) tuples."""
     return tuple(ConvLayer(int(y[0]), int(y[1]), bool(y[2]) if len(y) > 2 else False, bool(y[3]) if len(y) > 3 else False) for y in layers)
@@ -186,17 +204,19 @@ class Perceptual:
     """The perceptual term of one training loop: `features` on a device, the term's `weight` in the objective, and the
     workspace (allocated HERE, outside any capture; one per object: calls that may overlap use different objects)."""
 
+    _NAME, _BYTES, _ENTRY = "Perceptual", "fr_vgg_workspace_bytes", "fr_vgg_loss_grad"
+
     def __init__(self, features: VggFeatures, weight: float = 0.1):
         if not isinstance(features, VggFeatures):
-            raise TypeError("Perceptual: `features` must be a VggFeatures")
+            raise TypeError(f"{self._NAME}: `features` must be a VggFeatures")
         if features.device.type != "cuda":
-            raise RuntimeError("Perceptual needs device tensors (there is no CPU path): VggFeatures(..., device=)")
+            raise RuntimeError(f"{self._NAME} needs device tensors (there is no CPU path): VggFeatures(..., device=)")
         self.features, self.weight = features, float(weight)
         self.tile = _lib.FR_VGG_TILE_AUTO
         self.n_terms = len(features.taps)
-        need = int(_lib.lib().fr_vgg_workspace_bytes(C.byref(features.describe(1, 1))))
+        need = int(getattr(_lib.lib(), self._BYTES)(C.byref(features.describe(1, 1))))
         if need == 0:
-            raise RuntimeError("Perceptual: the library refuses the layer table (fr_vgg_workspace_bytes returned 0)")
+            raise RuntimeError(f"{self._NAME}: the library refuses the layer table ({self._BYTES} returned 0)")
         # zeroed: the head of the workspace (counters and partials of the terms' sums) must be, and every call leaves it so
         self._workspace = torch.zeros(need, dtype=torch.uint8, device=features.device)
 
@@ -204,7 +224,7 @@ class Perceptual:
         dev = self.features.device
         if t.dtype != torch.float32 or t.dim() != 3 or t.shape[0] != 3 or not t.is_contiguous() or t.device != dev or \
                 (shape is not None and tuple(t.shape) != tuple(shape)) or t.shape[1] * t.shape[2] == 0:
-            raise ValueError(f"Perceptual: {what} must be a contiguous float32 [3,H,W] tensor on {dev}"
+            raise ValueError(f"{self._NAME}: {what} must be a contiguous float32 [3,H,W] tensor on {dev}"
                              + (f" of shape {tuple(shape)}" if shape is not None else ""))
 
     @torch.no_grad()
@@ -220,19 +240,23 @@ class Perceptual:
         dev = self.features.device
         loss = loss_out if loss_out is not None else torch.empty(1 + self.n_terms, dtype=torch.float32, device=dev)
         if loss.dtype != torch.float32 or loss.numel() != 1 + self.n_terms or not loss.is_contiguous() or loss.device != dev:
-            raise ValueError(f"Perceptual: loss_out must be a contiguous float32 [{1 + self.n_terms}] tensor on {dev}")
+            raise ValueError(f"{self._NAME}: loss_out must be a contiguous float32 [{1 + self.n_terms}] tensor on {dev}")
         grad = None
         if grad_out is not False:
             if grad_out is None:
                 if accumulate:
-                    raise ValueError("Perceptual: `accumulate` needs the `grad_out` to add to")
+                    raise ValueError(f"{self._NAME}: `accumulate` needs the `grad_out` to add to")
                 grad_out = torch.empty_like(img)
             self._check_image(grad_out, "grad_out", img.shape)
             grad = grad_out
         d = self.features.describe(img.shape[1], img.shape[2], img, gt, self.tile)
-        _lib.launch("fr_vgg_loss_grad", dev, C.byref(d), C.c_float(self.weight if weight is None else float(weight)),
+        _lib.launch(self._ENTRY, dev, C.byref(d), *self._term_args(), C.c_float(self.weight if weight is None else float(weight)),
                     int(bool(accumulate)), loss.data_ptr(), None if grad is None else grad.data_ptr(), self._workspace.data_ptr())
         return loss, grad
+
+    def _term_args(self) -> tuple:
+        """What the entry point takes between the descriptor and the weight."""
+        return ()
 
     def _view(self, offset: int, shape) -> torch.Tensor:
         n = 4 * math.prod(shape)
@@ -255,6 +279,89 @@ class Perceptual:
 
     def __call__(self, img: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
         return vgg_perceptual_loss(img, gt, self)
+
+
+# Where the `lpips` package keeps a tap's learnt weights in its state dict: `lin{k}.model.1.weight`, [1,C,1,1] (model.0 is a
+# Dropout).  Written from memory of the package: it is not installed where this was written and the reference does not vendor
+# it, so the names could not be checked against it.  They live in this one table.
+LPIPS_LIN_KEYS = tuple(f"lin{k}.model.1.weight" for k in range(5))
+
+
+class Lpips(Perceptual):
+    """The LPIPS term of one training loop (or the metric): `features` — the trunk, by default to be built with
+    `Lpips.trunk()` — the taps' learnt `lin` weights (per tap a [c_out] tensor; default: uniform 1 / c_out, a stand-in as the
+    trunk's default weights are) and the term's `weight` in the objective (FlashAvatar 0.05, SplattingAvatar 0.01).  The
+    calls, buffers and saved-state views are `Perceptual`'s; `loss_and_grad(..., grad_out=False)` is the metric.
+    A pixel whose feature vector is all zero contributes with a zero unit vector and takes a gradient of exactly 0, where stock
+    autograd gives NaN (include/fr_rasterizer.h)."""
+    _NAME, _BYTES, _ENTRY = "Lpips", "fr_lpips_workspace_bytes", "fr_lpips_loss_grad"
+
+    def __init__(self, features: VggFeatures, lin: Optional[Sequence[torch.Tensor]] = None, weight: float = 0.05):
+        if isinstance(features, VggFeatures):
+            for i in features.taps:
+                if features.layers[i].c_out > LPIPS_MAX_TAP_WIDTH:
+                    raise ValueError(f"Lpips: layer {i} is a tap of {features.layers[i].c_out} channels, more than {LPIPS_MAX_TAP_WIDTH}")
+        super().__init__(features, weight)
+        widths = [features.layers[i].c_out for i in features.taps]
+        if lin is None:
+            lin = [torch.full((c,), 1.0 / c) for c in widths]
+        if len(lin) != len(widths) or any(w.numel() != c for w, c in zip(lin, widths)):
+            raise ValueError(f"Lpips: `lin` is one vector per tap, of {widths} elements")
+        self.lin = [w.detach().reshape(-1).to(features.device, torch.float32).contiguous() for w in lin]
+        self.packed_lin = torch.cat(self.lin).contiguous()
+
+    def _term_args(self) -> tuple:
+        return (self.packed_lin.data_ptr(),)
+
+    @staticmethod
+    def trunk(size: Tuple[int, int], normalize: bool = True, **kw) -> VggFeatures:
+        """The 13-layer trunk at `size` (LPIPS does not resize: the frame's (H, W)) with LPIPS's input statistics."""
+        mean, std = lpips_mean_std(normalize)
+        return VggFeatures(LPIPS_VGG16_LAYERS, size=size, mean=mean, std=std, **kw)
+
+    def saved_pixel_scalars(self) -> List[torch.Tensor]:
+        """Per tap [h, w, 3]: (1 / (n_a + 1e-10), 1 / (n_b + 1e-10), T / n_a) of the last call, all 0 at a dead pixel: views."""
+        f = self.features
+        o, out = workspace_bytes(f), []
+        for i, (h, w) in enumerate(f.extents()):
+            if f.layers[i].tap_after:
+                out.append(self._view(o, (h, w, 3)))
+                o += _r256(h * w * 3 * 4)
+        return out
+
+    def lin_state_dict(self) -> dict:
+        return {LPIPS_LIN_KEYS[k]: w.clone().view(1, -1, 1, 1) for k, w in enumerate(self.lin)}
+
+    @classmethod
+    def from_state_dicts(cls, trunk_sd: dict, lin_sd: dict, size: Tuple[int, int], weight: float = 0.05, normalize: bool = True,
+                         prefix: str = "", device=None) -> "Lpips":
+        """From torchvision's `vgg16().state_dict()` (features.{0,2,..,28}.{weight,bias}) and the `lpips` package's state
+        (LPIPS_LIN_KEYS).  `size`: the frames' (H, W)."""
+        mean, std = lpips_mean_std(normalize)
+        f = VggFeatures.from_state_dict(trunk_sd, prefix, LPIPS_VGG16_LAYERS, size=size, mean=mean, std=std, device=device)
+        lin = []
+        for k, key in enumerate(LPIPS_LIN_KEYS):
+            if key not in lin_sd:
+                raise KeyError(f"Lpips: the state lacks {key}")
+            c = LPIPS_VGG16_LAYERS[f.taps[k]].c_out
+            if tuple(lin_sd[key].shape) != (1, c, 1, 1):
+                raise ValueError(f"Lpips: {key} is {tuple(lin_sd[key].shape)}, not {(1, c, 1, 1)}")
+            lin.append(lin_sd[key].reshape(c))
+        return cls(f, lin, weight)
+
+    def __call__(self, img: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
+        return lpips_loss(img, gt, self)
+
+
+def lpips_workspace_bytes(features: VggFeatures) -> int:
+    """include/fr_rasterizer.h's formula of fr_lpips_workspace_bytes, restated."""
+    total, seed_max = workspace_bytes(features), 0
+    for i, (y, (h, w)) in enumerate(zip(features.layers, features.extents())):
+        if y.tap_after:
+            total += _r256(h * w * 3 * 4)
+            if i + 1 < len(features.layers):
+                seed_max = max(seed_max, h * w * y.c_out)
+    return total + _r256(seed_max * 4)
 
 
 def _r256(v: int) -> int:
@@ -311,5 +418,15 @@ def vgg_perceptual_loss(img: torch.Tensor, gt: torch.Tensor, perceptual: Percept
     return _VggPerceptual.apply(img, gt, perceptual)
 
 
-__all__ = ["ConvLayer", "as_layers", "IMAGENET_MEAN", "IMAGENET_STD", "Perceptual", "VGG16_LAYERS", "VggFeatures", "check_layers", "gemm_splits", "pack_backward",
+def lpips_loss(img: torch.Tensor, gt: torch.Tensor, lpips: Lpips) -> torch.Tensor:
+    """The UNWEIGHTED LPIPS distance of two [3,H,W] images in [0,1] as a 0-dim tensor, differentiable with respect to `img`
+    (as vgg_perceptual_loss is).  The objectives add `lpips.weight * lpips_loss(...)`."""
+    if not isinstance(lpips, Lpips):
+        raise TypeError("lpips_loss: `lpips` must be an Lpips")
+    if gt.requires_grad:
+        raise RuntimeError("lpips_loss: the target takes no gradient; detach it")
+    return _VggPerceptual.apply(img, gt, lpips)
+
+
+__all__ = ["LPIPS_LIN_KEYS", "LPIPS_SCALE", "LPIPS_SHIFT", "LPIPS_VGG16_LAYERS", "Lpips", "lpips_loss", "lpips_mean_std", "lpips_workspace_bytes", "ConvLayer", "as_layers", "IMAGENET_MEAN", "IMAGENET_STD", "Perceptual", "VGG16_LAYERS", "VggFeatures", "check_layers", "gemm_splits", "pack_backward",
            "pack_forward", "torchvision_indices", "vgg_perceptual_loss", "workspace_bytes"]

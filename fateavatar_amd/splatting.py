@@ -16,10 +16,13 @@ densification statistics run inside the rasterizer kernels, one L1 launch, one A
 step — mesh pass included — ONE HIP graph.
 
   * the objective — `SplattingAvatarLoss.accumulate_gradients` (train/loss.py:288-323) with config/splattingavatar.yaml:13-20:
-    1.0 x L1 + 10.0 x MSE + 1.0 x the scale term (+ 0.01 x LPIPS, not built).  `SplattingStep(image_loss=REFERENCE_IMAGE_LOSS)`:
+    1.0 x L1 + 10.0 x MSE + 1.0 x the scale term + 0.01 x LPIPS.  `SplattingStep(image_loss=REFERENCE_IMAGE_LOSS)`:
     one launch in the L1 launch's place (`loss.pixel_loss_and_grad`); `SplattingStep(scale_term=REFERENCE_SCALE_TERM)`: two more
-    launches inside the captured step (`loss.scale_term_and_grad`) that add the term's gradient in front of Adam.  Both are opt-in:
-    the default step optimises L1 alone
+    launches inside the captured step (`loss.scale_term_and_grad`) that add the term's gradient in front of Adam;
+    `SplattingStep(lpips=Lpips(..., weight=REFERENCE_LPIPS_WEIGHT))`: one call behind the image-loss launch (csrc/fr_vgg.hip's
+    fr_lpips_loss_grad) that adds the term's gradient to the image gradient.  All are opt-in: the default step optimises L1
+    alone.  The LPIPS term's weights (torchvision's VGG-16 and the `lpips` package's linear layers) are the caller's to load
+    (`perceptual.Lpips.from_state_dicts`); none are shipped
 
   * density control and the triangle walk — `_densify_and_prune`, `_clone_densify`, `_split_densify`, `_prune`,
     `_walking_on_triangles`, `_reset_opacity` (:386-715): `SplattingStep.densify_and_prune / prune / prune_low_opacity /
@@ -32,7 +35,6 @@ step — mesh pass included — ONE HIP graph.
     as in the reference.
 
 NOT here:
-  * its LPIPS loss term (config/splattingavatar.yaml:13-20, weight 0.01): it needs pretrained VGG weights
   * camera gradients for this step (render through a model.PoseCamera), and FLAME itself: `SplattingStep(mesh_grad=True)` hands
     dLoss/dposed_verts back (`d_verts`), the mesh's own parameters and their optimizer stay the caller's torch
   * data-parallel runs of the step (`reduce_densification_stats`)
@@ -61,6 +63,7 @@ NUM_INIT_SAMPLES = 10_000   # config/splattingavatar.yaml:23
 # config/splattingavatar.yaml:13-20 (SplattingAvatarLoss.Params, train/loss.py:261-268)
 REFERENCE_IMAGE_LOSS = PixelLoss(rgb_weight=1.0, mse_weight=10.0)
 REFERENCE_SCALE_TERM = ScaleTerm(weight=1.0, scale_threshold=10.0, max_scaling=0.008)
+REFERENCE_LPIPS_WEIGHT = 0.01
 
 
 def sample_bary_on_triangles(num_faces: int, num_samples: int, generator: Optional[torch.Generator] = None):
@@ -153,7 +156,7 @@ class SplattingStep(CloneSplitStep):
 
     def __init__(self, pc: SplattingGaussians, canonical: PhongCanonical, camera: TorchCamera, bg: torch.Tensor, verts: torch.Tensor,
                  lrs: Optional[dict] = None, use_graph: bool = True, fold_binding: bool = True, vertex_grad: bool = False,
-                 mesh_grad: bool = False, image_loss=None, scale_term: Optional[ScaleTerm] = None):
+                 mesh_grad: bool = False, image_loss=None, scale_term: Optional[ScaleTerm] = None, lpips=None):
         """`canonical`: `binding.phong_canonical(cano_verts, faces)`; `verts` [V,3]: any pose of the mesh (sizes the step's
         static vertex buffer and is its first content).  `fold_binding` (default): the per-Gaussian binding is evaluated
         inside the rasterizer's per-Gaussian kernels (fr_aux::binding with FR_BIND_PHONG).  False: the stand-alone
@@ -171,7 +174,12 @@ class SplattingStep(CloneSplitStep):
         step.)  None (default): the image term is L1 with weight 1, `loss_terms` is None.
         `scale_term`: a `ScaleTerm` (REFERENCE_SCALE_TERM holds the reference's values) adds the scale term of
         train/loss.py:307-315 to every step — two launches between the backward and Adam; `reg_loss` then holds the step's
-        unweighted scale_loss and the number of rows it selected.  None (default): no such launch, `reg_loss` is None."""
+        unweighted scale_loss and the number of rows it selected.  None (default): no such launch, `reg_loss` is None.
+        `lpips`: a `perceptual.Lpips` (the reference's weight: REFERENCE_LPIPS_WEIGHT) adds the LPIPS term of
+        train/loss.py:259-323 to every step: ONE call behind the image-loss launch adds weight x its gradient to the step's
+        image-gradient buffer, in front of the rasterizer's backward; `lpips_loss` [1 + T] then holds the step's UNWEIGHTED
+        terms (their sum first); `loss` and `loss_terms` keep their meaning.  None (default): not one launch changes."""
+        self._init_lpips(lpips, pc)
         if scale_term is not None and not isinstance(scale_term, ScaleTerm):
             raise TypeError(f"SplattingStep: `scale_term` is a ScaleTerm or None, not {type(scale_term).__name__}")
         self.mesh_grad = bool(mesh_grad)
@@ -212,7 +220,9 @@ class SplattingStep(CloneSplitStep):
             bound = bind_gaussians_phong(verts, self.faces, pc.face_index, pc.bary_coords, frame, pc._uvd, pc._rotation,
                                          pc._scaling)
             out = render(self.cam, _SplattingFrame(pc, stats, bound), self.bg)
-        out["render"].backward(self._image_loss_and_grad(out["render"]))   # see TrainStep
+        g = self._image_loss_and_grad(out["render"])                       # see TrainStep
+        self._add_lpips(out["render"], g)
+        out["render"].backward(g)
         if self.mesh_grad and not self.fold_binding:     # (the ops' backward allocates its own: copied into the step's buffer)
             self.d_verts.copy_(verts.grad)
         pc.collect_grads()
@@ -293,4 +303,4 @@ class SplattingStep(CloneSplitStep):
     RESUME_REMAPPED = False     # resumes FRESH
 
 
-__all__ = ["NUM_INIT_SAMPLES", "REFERENCE_IMAGE_LOSS", "REFERENCE_SCALE_TERM", "SPLATTING_LRS", "SplattingGaussians", "SplattingStep", "phong_canonical", "sample_bary_on_triangles"]
+__all__ = ["NUM_INIT_SAMPLES", "REFERENCE_IMAGE_LOSS", "REFERENCE_LPIPS_WEIGHT", "REFERENCE_SCALE_TERM", "SPLATTING_LRS", "SplattingGaussians", "SplattingStep", "phong_canonical", "sample_bary_on_triangles"]

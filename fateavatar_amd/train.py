@@ -441,6 +441,28 @@ class BoundStep(TrainStep):
         self.verts = verts.detach().to(self.dev, torch.float32).clone().contiguous()   # static input of the captured step
         self._init_step_state(camera, use_graph, image_loss)
 
+    # -- the LPIPS term of the objectives that carry one (FlashStep, SplattingStep): `lpips=` of their constructors
+    lpips = lpips_loss = None
+
+    def _init_lpips(self, lpips, pc) -> None:
+        """The checks of AvatarStep's `perceptual=` for `lpips=` (before anything is built); None: nothing changes."""
+        if lpips is not None:
+            from .perceptual import Lpips
+            if not isinstance(lpips, Lpips):
+                raise TypeError(f"{type(self).__name__}: `lpips` must be a perceptual.Lpips")
+            if lpips.features.device != pc.flat.device:
+                raise ValueError(f"{type(self).__name__}: the LPIPS term and the Gaussians live on different devices")
+            # [1 + T]: the step's UNWEIGHTED terms (the objective adds lpips.weight x lpips_loss[0]); `loss` / `loss_terms` keep
+            # their meaning
+            self.lpips_loss = torch.zeros(1 + lpips.n_terms, device=pc.flat.device)
+        self.lpips = lpips
+
+    def _add_lpips(self, image: torch.Tensor, g: torch.Tensor) -> None:
+        """ONE call behind the step's image-loss launch (csrc/fr_vgg.hip) ADDS weight x the term's gradient to the image
+        gradient `g` in place, in front of the rasterizer's backward."""
+        if self.lpips is not None:
+            self.lpips.loss_and_grad(image, self.gt, loss_out=self.lpips_loss, grad_out=g, accumulate=True)
+
     def adam_segments(self):
         """The optimizer groups (train/optim.py, one per parameter in the holder's order) as runs of the flat buffer; an
         empty field keeps its place and rate."""

@@ -1026,6 +1026,32 @@ size_t fr_vgg_workspace_bytes(const fr_vgg* vgg);
 int fr_vgg_loss_grad(const fr_vgg* vgg, float weight, int accumulate, float* loss_out, float* d_image, void* workspace,
                      void* hip_stream);
 
+/* ---- The LPIPS term over the same descriptor (reference: lpips.LPIPS(net='vgg') called with normalize=True, in
+ * FlashAvatar's objective at weight 0.05 after step 15 000 and SplattingAvatar's at 0.01, train/loss.py:203-323, and the
+ * evaluation metric, train/metrics.py:69).  Its input (2x - 1 - shift) / scale equals (x - mean) / std with the ImageNet
+ * statistics, i.e. the descriptor's `mean` / `std`; its trunk is vgg16.features[:30]: 13 layers, 4 pools, 5 taps; it does
+ * not resize (size == (H, W)), though the descriptor may.  Per tap, with a / b the rendered / target feature [h,w,C]:
+ *   n_a(p) = sqrt(sum_c a_c(p)^2),  a^ = a / (n_a + 1e-10)   (the same for b),
+ *   term   = (1 / (h w)) sum_p sum_c lin_c (a^_c - b^_c)^2,   the loss = the sum of the terms,
+ *   dterm/da_c = r g_c - a^_c T / n_a   with g_c = 2 lin_c (a^_c - b^_c) / (h w), r = 1 / (n_a + 1e-10), T = sum_c g_c a^_c.
+ * DEAD PIXELS, a deviation from stock autograd: where n_a(p) == 0 autograd yields NaN (sqrt's backward at 0 is inf x 0).  Here
+ * n == 0 makes the hat vector 0, the pixel contributes sum_c lin_c b^_c^2, its gradient is exactly 0 (every unit behind it is
+ * a ReLU at 0, whose mask passes nothing anyway), and nothing non-finite is ever produced.
+ * `lin`: the taps' [c_out] vectors concatenated in tap order, 16-byte aligned; a tapped layer has c_out <= 512.  loss_out is
+ * [1 + T] as above; `weight`, `accumulate`, d_image == NULL and `tile` mean what they mean for fr_vgg_loss_grad, and the same
+ * bits come out of every launch and replay (a wave per pixel, fixed-order sums, no float atomics).
+ * The tap gradient is MATERIALISED, not recomputed in the epilogues: a small kernel writes a tap's seed (already behind the
+ * ReLU mask) from the two saved activations, the pixel's three scalars and lin — the LAST tap's into a gradient buffer, from
+ * which the backward starts on the plain fetch; an earlier tap's into ONE seed buffer just ahead of the GEMM whose epilogue
+ * (in-kernel, split-reduce or un-pool) adds it.  The L1 kernels are the same templates with the other term kind.
+ * `workspace`: fr_lpips_workspace_bytes() bytes = the fr_vgg_workspace_bytes() layout, unchanged, followed by
+ *   + sum over the taps of r256(3 h_l w_l * 4)                         per pixel (r_a, r_b, T / n_a), all 0 at a dead pixel
+ *   + r256(max over the taps but the last of h_l w_l c_out_l * 4)      the seed buffer
+ * (763.4 MB + 4.2 MB + 67.1 MB = 834.7 MB for the 13-layer trunk at 512^2; 168.2 MB at 224^2.) */
+size_t fr_lpips_workspace_bytes(const fr_vgg* vgg);
+int fr_lpips_loss_grad(const fr_vgg* vgg, const float* lin, float weight, int accumulate, float* loss_out, float* d_image,
+                       void* workspace, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,13 @@ ten outputs; torch.optim.Adam at 1e-4) that is trained through `step.d_deform`; 
 The same loop with the deformation network INSIDE the captured step (fateavatar_amd/mlp.py: `FlashStep(deformer=DeformMLP(...))`,
 the reference's embedding order and network shape, f32-MFMA kernels, a second fused Adam at 1e-4): one graph replay per step.
 
+    python tools/train_synthetic.py --flash --lpips [--lpips-start 0] [--fused-mlp]       | --flash --torch-lpips
+    python tools/train_synthetic.py --splatting --reference-loss --lpips                 | --splatting --reference-loss --torch-lpips
+The reference's LPIPS term inside the step (`FlashStep(lpips=Lpips(.., weight=0.05))`, `SplattingStep(lpips=Lpips(.., weight=0.01))`):
+one call behind the image-loss launch adds its gradient to the image gradient (csrc/fr_vgg.hip, fr_lpips_loss_grad) — the 13-layer
+trunk at the frame's size, seeded weights.  --torch-lpips: the A/B, the same term at the same place through F.conv2d and autograd.
+The report gains `lpips_loss` (the sum of the five tap terms, then the terms).
+
     python tools/train_synthetic.py --splatting --track-mesh [--track-offset 0.005 --track-lr 5e-4] [--binding-op | --torch-binding]
 SplattingAvatar's step with the reference's tracking optimisation next to it (train/base.py:113-156), reduced to a rigid pose: every
 frame's posed mesh gets an axis-angle and translation correction, a torch leaf of six numbers that starts --track-offset away
@@ -147,6 +154,15 @@ def main():
     ap.add_argument("--vgg-weights", default=None, metavar="FILE",
                     help="--perceptual / --torch-perceptual: a torch-saved state dict in torchvision's naming (vgg16().state_dict())")
     ap.add_argument("--perceptual-size", type=int, default=224, help="what both images are resized to (the reference: 224)")
+    ap.add_argument("--lpips", action="store_true",
+                    help="--flash, or --splatting --reference-loss: the reference's LPIPS term inside the step (FlashStep(lpips=Lpips(.., "
+                         "weight=0.05), lpips_start=--lpips-start) / SplattingStep(lpips=Lpips(.., weight=0.01)), csrc/fr_vgg.hip's "
+                         "fr_lpips_loss_grad); seeded random weights (pretrained ones are the caller's: Lpips.from_state_dicts)")
+    ap.add_argument("--torch-lpips", action="store_true",
+                    help="the A/B of --lpips: the same term at the same place of the same step through F.conv2d and autograd")
+    ap.add_argument("--lpips-start", type=int, default=0,
+                    help="--flash --lpips: the term is launched from this step + 1 on (the reference: 15000; default 0, so that the "
+                         "timed loop carries it)")
     ap.add_argument("--track-camera", action="store_true",
                     help="--fateavatar: train a per-frame camera translation leaf through AvatarStep(camera_grad=True)")
     ap.add_argument("--track-offset", type=float, default=0.005, help="--track-camera: RMS start error of the translations, per axis (m)")
@@ -232,6 +248,10 @@ def main():
         if not (a.fateavatar and a.views_per_step == 1) or (a.perceptual and a.torch_perceptual) or a.train_mesh or a.track_camera:
             raise SystemExit("--perceptual / --torch-perceptual: one of the two, with --fateavatar at one frame per step, without "
                              "--train-mesh / --track-camera")
+    if a.lpips or a.torch_lpips:
+        if (a.lpips and a.torch_lpips) or not (a.flash or (a.splatting and a.reference_loss)) or a.torch_binding or a.track_mesh:
+            raise SystemExit("--lpips / --torch-lpips: one of the two, with --flash or --splatting --reference-loss, without "
+                             "--torch-binding / --track-mesh")
     if a.track_mesh and not a.splatting:
         raise SystemExit("--track-mesh goes with --splatting")
     if a.fateavatar:
@@ -328,6 +348,46 @@ def make_perceptual(a, dev):
             grad_out.add_(g, alpha=self.weight if weight is None else weight) if accumulate else grad_out.copy_(g * self.weight)
             return loss_out, grad_out
     return TorchPerceptual(feats, weight=0.1)
+
+
+def make_lpips(a, dev, weight):
+    """The step's LPIPS term for --lpips / --torch-lpips (None without either): the 13-layer trunk at the frame's size with seeded
+    He-normal weights and uniform `lin`, at the objective's `weight`; --torch-lpips: the same object with its one call replaced
+    by stock convolutions, the unit normalisation from stock ops and autograd, so that both sit at the same place of the step."""
+    if not (a.lpips or a.torch_lpips):
+        return None
+    import torch.nn.functional as F
+    from fateavatar_amd.perceptual import Lpips
+    rng = torch.get_rng_state()
+    torch.manual_seed(0)
+    feats = Lpips.trunk((a.res, a.res), device=dev)
+    torch.set_rng_state(rng)
+    if a.lpips:
+        return Lpips(feats, weight=weight)
+
+    m = torch.tensor(feats.mean, device=dev).view(1, 3, 1, 1)      # (made here: a captured step cannot copy from the host)
+    s = torch.tensor(feats.std, device=dev).view(1, 3, 1, 1)
+
+    class TorchLpips(Lpips):
+        def loss_and_grad(self, img, gt, loss_out=None, grad_out=None, accumulate=False, weight=None):
+            f = self.features
+            with torch.enable_grad():
+                x = img.detach().requires_grad_(True)
+                h = (torch.stack([x, gt]) - m) / s
+                terms = []
+                for y, w, b in zip(f.layers, f.weights, f.biases):
+                    if y.pool_before:
+                        h = F.max_pool2d(h, 2, 2)
+                    h = F.relu(F.conv2d(h, w, b, padding=1))
+                    if y.tap_after:
+                        u = h / (h.pow(2).sum(1, keepdim=True).sqrt() + 1e-10)
+                        terms.append((self.lin[len(terms)].view(1, -1, 1, 1) * (u[0:1] - u[1:2].detach()).pow(2)).sum(1).mean())
+                total = torch.stack(terms).sum()
+                (g,) = torch.autograd.grad(total, x)
+            loss_out.copy_(torch.cat([total.detach().reshape(1), torch.stack(terms).detach()]))
+            grad_out.add_(g, alpha=self.weight if weight is None else weight) if accumulate else grad_out.copy_(g * self.weight)
+            return loss_out, grad_out
+    return TorchLpips(feats, weight=weight)
 
 
 def fateavatar_setup(P, res, dev, views=8, views_per_step=1, use_graph=True, chain=True, fold_binding=True, order="uv",
@@ -758,7 +818,7 @@ def main_rigged(a, rank, world, dev):
 
 
 def splatting_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_binding=False, mesh_grad=False,
-                    reference_loss=False):
+                    reference_loss=False, lpips=None):
     """SplattingAvatar's optimisation step on the synthetic INSTA-layout sequence (frame 0 is the canonical mesh): P Gaussians
     sampled on the template as the reference samples them, the step object, cameras, posed meshes and targets rendered from a
     hidden ground-truth set of the same embedding.  `reference_loss`: the step optimises the reference's L1 + MSE + scale term."""
@@ -810,7 +870,7 @@ def splatting_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, tor
         cls = TorchBoundStep
     st = cls(pc, canonical, TorchCamera(insta.camera_arrays(transform)[0], dev), bg, posed_t[0], use_graph=use_graph,
              fold_binding=fold_binding, mesh_grad=mesh_grad, image_loss=REFERENCE_IMAGE_LOSS if reference_loss else None,
-             scale_term=REFERENCE_SCALE_TERM if reference_loss else None)
+             scale_term=REFERENCE_SCALE_TERM if reference_loss else None, lpips=lpips)
     return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames)
 
 
@@ -887,7 +947,7 @@ def main_splatting(a, rank, world, dev):
         return main_track_mesh(a, rank, world, dev)
     P = a.P if "--P" in sys.argv else 10_000
     su = splatting_setup(P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
-                         torch_binding=a.torch_binding, reference_loss=a.reference_loss)
+                         torch_binding=a.torch_binding, reference_loss=a.reference_loss, lpips=make_lpips(a, dev, 0.01))
     st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
     # the compressed maintenance schedule, in steps of the timed loop (config/splattingavatar.yaml:35-44,
     # train/iteration.py:271-298: densify every 100 steps from 600, reset opacity every 3 500, walk every 100)
@@ -927,6 +987,10 @@ def main_splatting(a, rank, world, dev):
         terms = {"l1": round(lt[1], 6), "mse": round(lt[2], 6), "scale_loss": round(rl[0], 6), "scale_selected": int(rl[1])}
         print(f"last step: l1 {lt[1]:.6f}, mse {lt[2]:.6f}, scale_loss {rl[0]:.6f} over {int(rl[1])} selected rows", file=sys.stderr)
     objective = "L1 + MSE + scale term" if a.reference_loss else "L1"
+    if st.lpips is not None:
+        objective += " + 0.01 LPIPS"
+        terms["lpips"] = "torch" if a.torch_lpips else "fused"
+        terms["lpips_loss"] = [round(float(x), 6) for x in st.lpips_loss]
     print(json.dumps({"host_enqueue_ms_per_step": round(t_host / a.steps * 1e3, 4),
                       "metric": f"SplattingAvatar optimisation steps/s (mesh pass + bind + render + {objective} + backward + stats + Adam)",
                       "reference_loss": bool(a.reference_loss), **terms,
@@ -959,7 +1023,7 @@ class DeformNet(torch.nn.Module):
 
 
 def flash_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_binding=False, mouth_mask=False, vertex_grad=False,
-                fused_mlp=False):
+                fused_mlp=False, lpips=None, lpips_start=0):
     """FlashAvatar's optimisation step on the synthetic INSTA-layout sequence: P Gaussians at fixed points of the template (the
     reference's UV-raster sampling when P is its row count, else uniform faces), the step object, the deformation network with
     its per-frame conditions (the frame's jaw and rigid rotations, from the sequence), cameras, posed meshes, mouth masks and
@@ -1032,7 +1096,7 @@ def flash_setup(P, res, dev, views=8, use_graph=True, fold_binding=True, torch_b
                 self.out = self._kept(out)
         cls = TorchBoundStep
     st = cls(pc, faces_t, TorchCamera(insta.camera_arrays(transform)[0], dev), bg, posed_t[0], use_graph=use_graph,
-             fold_binding=fold_binding, mouth_mask=mouth_mask, vertex_grad=vertex_grad, **extra)
+             fold_binding=fold_binding, mouth_mask=mouth_mask, vertex_grad=vertex_grad, lpips=lpips, lpips_start=lpips_start, **extra)
     return dict(st=st, net=net, conds=conds, cams=cams, posed=posed_t, gts=gts, masks=masks, n_frames=n_frames)
 
 
@@ -1041,7 +1105,8 @@ def main_flash(a, rank, world, dev):
         raise SystemExit("--flash: data-parallel runs are not built")
     P = a.P if "--P" in sys.argv else 16_384
     su = flash_setup(P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
-                     torch_binding=a.torch_binding, mouth_mask=a.mouth_mask, vertex_grad=a.vertex_grad, fused_mlp=a.fused_mlp)
+                     torch_binding=a.torch_binding, mouth_mask=a.mouth_mask, vertex_grad=a.vertex_grad, fused_mlp=a.fused_mlp,
+                     lpips=make_lpips(a, dev, 0.05), lpips_start=a.lpips_start)
     st, net, conds, cams, posed_t, gts, masks, n_frames = (su[k] for k in ("st", "net", "conds", "cams", "posed", "gts", "masks", "n_frames"))
     # the reference's `deformer` group (train/optim.py:55-59); with --fused-mlp the step's own second Adam
     opt = None if a.fused_mlp else torch.optim.Adam(net.parameters(), lr=1e-4)
@@ -1082,6 +1147,8 @@ def main_flash(a, rank, world, dev):
                       "mlp": "fused (fr_mlp, inside the step)" if a.fused_mlp else "stock PyTorch", "binding": how, "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "P": st.pc.P,
                       "res": a.res, "frames": n_frames, "graph": not a.no_graph, "overflows": st.overflows,
                       "mouth_mask": bool(a.mouth_mask), "vertex_grad": bool(st.vertex_grad),
+                      "lpips": None if st.lpips is None else ("torch" if a.torch_lpips else "fused"),
+                      "lpips_loss": None if st.lpips is None else [round(float(x), 6) for x in st.lpips_loss],
                       "loss_terms": [round(float(x), 6) for x in st.loss_terms], "mlp_weights_moved": moved,
                       "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
 
