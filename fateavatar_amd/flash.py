@@ -149,14 +149,19 @@ class FlashStep(BoundStep):
         `lpips`: a `perceptual.Lpips` adds the LPIPS term from step `lpips_start` + 1 on (the reference multiplies it by 0 until
         `cur_step > 15000`; here it is not launched before): ONE call behind the Huber launch adds weight x its gradient to the
         step's image-gradient buffer, in front of the rasterizer's backward.  `lpips_loss` [1 + T] holds the step's UNWEIGHTED
-        terms and stays zero until then; `loss` and `loss_terms` keep their meaning.  The step's number is `host_steps` (step()
-        calls, restored from the Adam count by a checkpoint): no device word is read.  At the crossing the captured graph is
-        dropped ONCE (`lpips_switches` counts it) and the step re-captured with the launch in it, as after an overflow.
-        None (default): not one launch changes."""
+        terms and stays zero until then; `loss` and `loss_terms` keep their meaning.  The step's number is `schedule_steps`, a
+        host count of the schedule's own: step() calls, and after `load_state_dict` the checkpoint's `global_step` — as the
+        reference's loader restores it (train/loader.py:102) and applies `cur_step > 15000` to it (train/loss.py:250) — so a
+        checkpoint in the reference's own layout (`global_step` and `model`, no `optimizer` entry) resumes the SCHEDULE where
+        it was although the optimizer starts fresh (`host_steps`, `adam.step_count` and `skipped_steps` keep their meaning and
+        restart at 0 there).  No device word is read.  At a crossing — the start, or a checkpoint from the other side of it —
+        the captured graph is dropped ONCE (`lpips_switches` counts it) and the step re-captured with or without the launch in
+        it, as after an overflow.  None (default): not one launch changes."""
         self._init_lpips(lpips, pc)
         if int(lpips_start) < 0:
             raise ValueError("FlashStep: lpips_start is a step count, >= 0")
         self.lpips_start, self._lpips_on, self.lpips_switches, self.captures = int(lpips_start), False, 0, 0
+        self.schedule_steps = 0
         if deformer is not None:
             if not isinstance(deformer, DeformMLP):
                 raise TypeError("FlashStep: `deformer` must be a mlp.DeformMLP")
@@ -257,7 +262,8 @@ class FlashStep(BoundStep):
             extra = [(self.deform, deform.detach())]
         if mouth_mask is not None:
             extra.append((self.mask, mouth_mask.detach().reshape(self.mask.shape)))
-        on = self.lpips is not None and self.host_steps + 1 > self.lpips_start
+        self.schedule_steps += 1
+        on = self.lpips is not None and self.schedule_steps > self.lpips_start
         if on != self._lpips_on:       # the schedule's crossing: the captured step does not hold the launch (or holds it: a restored count)
             self._lpips_on, self._graph, self._eager_steps = on, None, 0
             self.lpips_switches += 1
@@ -299,8 +305,10 @@ class FlashStep(BoundStep):
     @torch.no_grad()
     def load_state_dict(self, sd: dict) -> list:
         """BoundStep.load_state_dict; with a deformer the `deformNet.*` entries are LOADED (in place) instead of being returned
-        as ignored, and `deformer_optimizer`, if the checkpoint has one, restores the network's Adam (else it starts fresh)."""
+        as ignored, and `deformer_optimizer`, if the checkpoint has one, restores the network's Adam (else it starts fresh).
+        The LPIPS schedule goes on at the checkpoint's `global_step` (train/loader.py:102), with or without an `optimizer` entry."""
         ignored = super().load_state_dict(sd)
+        self.schedule_steps = int(sd["global_step"]) if "global_step" in sd else self.host_steps
         if self.deformer is None:
             return ignored
         self.deformer.load_state_dict(sd["model"], DEFORM_PREFIX)

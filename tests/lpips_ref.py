@@ -128,6 +128,27 @@ def dead_pixel_case():
     return W, B, lin_weights(vgg_ref.SMALL, seed=5), img, gt
 
 
+def dead_target_case():
+    """`dead_pixel_case` with black patches in the TARGET too: its bottom-right 12 x 12 (over live rendered pixels: target-only
+    dead, where the target takes no gradient and stock autograd is finite) and its top-left 6 x 6 (inside the rendered image's
+    black patch: both dead, contribution and scalars exactly 0)."""
+    W, B, lin, img, gt = dead_pixel_case()
+    gt = gt.clone()
+    gt[:, 12:, 12:] = 0.0
+    gt[:, :6, :6] = 0.0
+    return W, B, lin, img, gt
+
+
+def dead_classes(acts, layers):
+    """Per tap bool masks [h,w] (both dead, rendered only, target only) of `acts` (per layer [2,C,h,w])."""
+    out = []
+    for l, y in enumerate(layers):
+        if y[3]:
+            da, db = acts[l][0].pow(2).sum(0) == 0, acts[l][1].pow(2).sum(0) == 0
+            out.append((da & db, da & ~db, ~da & db))
+    return out
+
+
 def dead_pixels(acts, layers):
     """Per tap (dead rendered pixels, dead target pixels) of `acts` (per layer [2,C,h,w])."""
     return [(int((acts[l][0].pow(2).sum(0) == 0).sum()), int((acts[l][1].pow(2).sum(0) == 0).sum()))

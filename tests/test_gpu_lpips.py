@@ -9,17 +9,19 @@ could be recorded (tests/golden has none for this term), and the weights are see
 As in tests/test_gpu_vgg.py the forward is compared directly and the backward twice: against the PINNED float64 backward at the
 device's own saved activations (ReLU masks, pool argmaxes; the tap seed is continuous and has no decision of its own), and end
 to end against float64 autograd on inputs whose float64 decisions are clear.  Dead pixels (all-zero feature vectors, where stock
-autograd is NaN), identical images, the GEMM split plans and the call contract have tests of their own."""
+autograd is NaN) in the rendered image, in the target and in both, identical images, the GEMM split plans, taps beyond one sweep
+of k_lpips_tap's grid, widths that are odd multiples of 64, flat regions (vgg_ref.patchwork) and the call contract have tests of
+their own."""
 import functools
 
 import pytest
 
 from tests import lpips_ref, vgg_ref
-from tests.test_gpu_vgg import CEILING, CLEAR, FACTOR, FLOOR, MASK_Z, WIDE_CASES, _bound, _rel
+from tests.test_gpu_vgg import CEILING, CLEAR, FACTOR, FLOOR, MASK_Z, ODD_CASES, WIDE_CASES, _background_interior, _bound, _rel
 
 pytestmark = pytest.mark.gpu
 
-STACKS = {"lpips13": lpips_ref.LPIPS13, "small": vgg_ref.SMALL, "wide": vgg_ref.WIDE}
+STACKS = {"lpips13": lpips_ref.LPIPS13, "small": vgg_ref.SMALL, "wide": vgg_ref.WIDE, "odd": vgg_ref.ODD}
 # (stack, H, W, size_h, size_w)
 CASES = [("lpips13", 32, 32, 32, 32),     # deepest map 2 x 2
          ("lpips13", 48, 32, 48, 32),     # non-square, ragged M
@@ -30,6 +32,14 @@ END_TO_END = [CASES[0], CASES[2], CASES[4]]
 # The first seed from 0 on at which the float64 restatement keeps every ReLU and pool decision CLEAR (lpips_ref.decisions_clear),
 # found by this same float64-only search on the CPU; the loop in _clear_case still checks the criterion.
 FIRST_CLEAR_SEED = {CASES[0]: 71, CASES[2]: 2, CASES[4]: 5}
+# k_lpips_tap runs FR_VGG_LOSS_BLOCKS workgroups of four waves, one pixel a wave: 4096 pixels a sweep (tests/test_lpips_host.py
+# holds the arithmetic against the library's constant).  CASES stay inside one sweep; these do not:
+PAST_THE_CAP = [("small", 70, 62, 70, 62),       # tap 1: 4340 pixels, a second sweep that 61 workgroups take part in; tap 2: 1085
+                                                 # pixels, not a multiple of 4 — the last workgroup has three idle waves
+                ("lpips13", 80, 64, 80, 64)]     # tap 1: 5120 pixels (the smallest such size divisible by 16); 1280, 320, 80, 20
+# vgg_ref.patchwork's flat regions (identity sizes): a pool, the 13-layer trunk, and the stack whose GEMMs add the seed in the
+# MASK epilogue and the split-reduce
+PATCHWORK = [("small", 24, 24, 24, 24), ("lpips13", 32, 32, 32, 32), ("wide", 32, 32, 32, 32)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -39,11 +49,11 @@ def _weights(stack):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(stack, H, W, sh, sw):
+def _case(stack, H, W, sh, sw, patchwork=False):
     """Weights, images and both restatements' forwards on the CPU: computed once, shared, never modified."""
     import torch
     Wt, B, lin = _weights(stack)
-    img, gt = vgg_ref.images(H, W, seed=1000 * H + W)
+    img, gt = (vgg_ref.patchwork if patchwork else vgg_ref.images)(H, W, seed=1000 * H + W)
     r64 = lpips_ref.forward(Wt, B, lin, STACKS[stack], img, gt, (sh, sw), torch.float64)
     r32 = lpips_ref.forward(Wt, B, lin, STACKS[stack], img, gt, (sh, sw), torch.float32)
     return dict(W=Wt, B=B, lin=lin, img=img, gt=gt, r64=r64, r32=r32)
@@ -160,12 +170,126 @@ def test_dead_pixels_are_finite_and_take_no_gradient(gpu_device):
     assert float(grad.abs().max()) > 0
 
 
-@pytest.mark.parametrize("stack,hw", [("small", (24, 24)), ("lpips13", (32, 32))])
-def test_identical_images_give_exact_zeros(gpu_device, stack, hw):
+@pytest.mark.parametrize("case", PAST_THE_CAP + ODD_CASES, ids=_ids)
+def test_past_the_grid_cap_and_odd_widths_against_float64(gpu_device, case):
+    """The held set where k_lpips_tap's pixel loop takes a second sweep (PAST_THE_CAP: a wave carries its sum over two pixels,
+    `px` rows written in the second sweep are read by k_lpips_seed, and a tap of 1085 pixels leaves waves of the last workgroup
+    idle in the last-workgroup sum), and on vgg_ref.ODD, whose taps hold 3, 5 and 7 values a lane behind the kernel's `j < nv`
+    guards and whose GEMMs have 3, 5 and 7 column tiles."""
+    stack, H, W, sh, sw = case
+    _held_to_float64(gpu_device, _ids(case), STACKS[stack], _case(*case), (H, W), (sh, sw))
+
+
+def test_past_the_grid_cap_same_bits_on_every_launch(gpu_device):
+    import torch
+    dev = gpu_device
+    stack, H, W, sh, sw = PAST_THE_CAP[0]
+    c = _case(*PAST_THE_CAP[0])
+    img, gt = c["img"].to(dev), c["gt"].to(dev)
+    p = _lpips(STACKS[stack], c["W"], c["B"], c["lin"], (sh, sw), dev)
+    first = [t.clone() for t in p.loss_and_grad(img, gt)]
+    second = [t.clone() for t in p.loss_and_grad(img, gt)]
+    torch.cuda.synchronize()
+    assert float(first[0][0]) > 0 and float(first[1].abs().max()) > 0
+    assert torch.equal(first[0], second[0]) and torch.equal(first[1], second[1])
+
+
+@functools.lru_cache(maxsize=None)
+def _dead_target_case():
+    import torch
+    W, B, lin, img, gt = lpips_ref.dead_target_case()
+    return dict(W=W, B=B, lin=lin, img=img, gt=gt, r64=lpips_ref.forward(W, B, lin, vgg_ref.SMALL, img, gt, (24, 24), torch.float64),
+                r32=lpips_ref.forward(W, B, lin, vgg_ref.SMALL, img, gt, (24, 24), torch.float32))
+
+
+def _check_dead_classes(classes, pxs, both, rendered, target):
+    """The per-pixel scalars (r_a, r_b, T / n_a) on each class of dead pixels; `both`, `rendered`, `target`: the positions of
+    those classes in a tap's triple of masks (the swapped call exchanges the last two)."""
+    import torch
+    for masks, px in zip(classes, pxs):
+        assert bool(torch.isfinite(px).all())
+        t = px[masks[target]]
+        assert bool((t[:, 1] == 0).all()) and bool((t[:, 0] > 0).all())
+        r = px[masks[rendered]]
+        assert bool((r[:, 0] == 0).all()) and bool((r[:, 2] == 0).all()) and bool((r[:, 1] > 0).all())
+        assert bool((px[masks[both]] == 0).all())
+        live = ~(masks[0] | masks[1] | masks[2])
+        assert bool((px[live][:, :2] > 0).all())
+
+
+def test_dead_targets_and_doubly_dead_pixels(gpu_device):
+    """lpips_ref.dead_target_case: per tap (31, 92, 138) and (1, 15, 21) pixels are dead in both images, in the rendered one
+    alone and in the target alone in float64 (tests/test_lpips_host.py).  The device has all three classes at both taps, holds
+    the restatement's terms and the pinned backward, and its scalars say which is which: r_b == 0 at a dead target under a live
+    rendered pixel, r_a == 0 and T / n_a == 0 at a dead rendered pixel, all three 0 where both are dead.  With the images
+    swapped the terms are the same (the term is symmetric) and the two one-sided classes change places."""
+    import torch
+    dev = gpu_device
+    layers = vgg_ref.SMALL
+    c = _dead_target_case()
+    loss, grad, saved, p = _held_to_float64(dev, "dead-targets", layers, c, (24, 24), (24, 24))
+    classes = lpips_ref.dead_classes(saved, layers)
+    counts = [tuple(int(m.sum()) for m in masks) for masks in classes]
+    counts64 = [tuple(int(m.sum()) for m in masks) for masks in lpips_ref.dead_classes(c["r64"]["a"], layers)]
+    print(f"dead-targets (both, rendered only, target only) per tap on the device: {counts}  float64: {counts64}")
+    assert all(n > 0 for tap in counts for n in tap)
+    pxs = [px.cpu().clone() for px in p.saved_pixel_scalars()]
+    _check_dead_classes(classes, pxs, both=0, rendered=1, target=2)
+    assert bool(torch.isfinite(loss).all()) and bool(torch.isfinite(grad).all()) and float(grad.abs().max()) > 0
+    # ---- swapped: the same terms, the classes change places (the gradient, the other image's, is not compared)
+    loss_s, grad_s = p.loss_and_grad(c["gt"].to(dev), c["img"].to(dev), weight=1.0)
+    torch.cuda.synchronize()
+    loss_s = loss_s.cpu()
+    assert bool(torch.isfinite(loss_s).all()) and bool(torch.isfinite(grad_s).all())
+    ref64, ref32 = torch.stack(c["r64"]["terms"]), torch.stack(c["r32"]["terms"])
+    e32, err = _rel(ref32, ref64), _rel(loss_s[1:], ref64)
+    print(f"dead-targets swapped terms: kernel {err:.3e}  float32 restatement {e32:.3e}  ratio {err / max(e32, FLOOR):.2f}")
+    assert err <= _bound(e32), (err, e32)
+    swapped = lpips_ref.dead_classes([vgg_ref.nchw(a) for a in p.saved_activations()], layers)
+    for masks, masks_s in zip(classes, swapped):
+        assert torch.equal(masks_s[0], masks[0]) and torch.equal(masks_s[1], masks[2]) and torch.equal(masks_s[2], masks[1])
+    _check_dead_classes(classes, [px.cpu() for px in p.saved_pixel_scalars()], both=0, rendered=2, target=1)
+
+
+@pytest.mark.parametrize("case", PATCHWORK, ids=_ids)
+def test_flat_regions_against_float64(gpu_device, case):
+    """The held set on vgg_ref.patchwork under the LPIPS term kind: the VGG_TERM_LPIPS instantiations of k_vgg_unpool, of the
+    MASK epilogue and of the split-reduce add a seed read from a buffer where the L1 term computes a sign.  Thousands of live
+    pool windows are exact ties (none in vgg_ref.WIDE, which has no pool: there only the live zero tap differences count), and
+    inside the shared background a^ - b^ is exactly 0, so T / n_a is exactly 0 and the interior of the quadrant takes a gradient
+    of exactly 0, tied pools included.  The interior is empty for the 13-layer trunk at 32 x 32 (its margin is 195 pixels)."""
+    import torch
+    stack, H, W, sh, sw = case
+    layers = STACKS[stack]
+    c = _case(*case, patchwork=True)
+    loss, grad, saved, p = _held_to_float64(gpu_device, _ids(case) + " patchwork", layers, c, (H, W), (sh, sw))
+    ties64, zeros64 = vgg_ref.live_ties(c["r64"]["a"], layers)
+    ties, zeros = vgg_ref.live_ties(saved, layers)
+    print(f"{_ids(case)} patchwork: live tied windows {ties} on the device (float64: {ties64}), live zero tap differences {zeros} "
+          f"(float64: {zeros64})")
+    if any(y[2] for y in layers):
+        assert ties64 >= 1000
+    assert zeros64 >= 1000
+    assert 2 * ties >= ties64 and 2 * zeros >= zeros64
+    rows, cols = _background_interior(layers, H, W, sh, sw)
+    print(f"{_ids(case)} patchwork: shared-background interior {rows} x {cols} pixels")
+    assert (rows > 0 and cols > 0) == (stack != "lpips13")
+    assert bool((grad[:, :rows, :cols] == 0).all())
+    assert float(grad[:, H // 2:, :].abs().max()) > 0 and float(grad[:, :, W // 2:].abs().max()) > 0
+    # inside the interior the two images' activations are the same bits, layer by layer
+    for (h, w), a in zip(p.features.extents(), p.saved_activations()):
+        k = rows // (H // h)
+        if k:
+            assert torch.equal(a[0, :k, :k], a[1, :k, :k])
+
+
+@pytest.mark.parametrize("stack,hw,patchwork", [("small", (24, 24), False), ("lpips13", (32, 32), False), ("small", (24, 24), True)],
+                         ids=["small-hw0", "lpips13-hw1", "small-patchwork"])
+def test_identical_images_give_exact_zeros(gpu_device, stack, hw, patchwork):
     import torch
     dev = gpu_device
     Wt, B, lin = _weights(stack)
-    x = vgg_ref.images(*hw, seed=9)[0].to(dev)
+    x = (vgg_ref.patchwork if patchwork else vgg_ref.images)(*hw, seed=9)[0].to(dev)
     p = _lpips(STACKS[stack], Wt, B, lin, hw, dev)
     loss = torch.full((1 + p.n_terms,), float("nan"), device=dev)
     grad = torch.full_like(x, float("nan"))

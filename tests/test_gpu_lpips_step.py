@@ -1,7 +1,10 @@
 """-m gpu: the LPIPS term inside SplattingAvatar's and FlashAvatar's steps (SplattingStep(lpips=...), FlashStep(lpips=...,
 lpips_start=...)) on small bound scenes — 64 x 64 frames, the 13-layer trunk's widths with seeded weights, no resize: what the
 step's image-gradient buffer and `lpips_loss` hold after a step, eager steps against graph replays, FlashAvatar's schedule with
-its one dropped graph, and the refusals.  Mirrors tests/test_gpu_vgg_step.py."""
+its one dropped graph, the schedule across a checkpoint (full, from before the start, in the reference's own layout), the
+reference's whole objectives around the term, and the refusals.  Mirrors tests/test_gpu_vgg_step.py."""
+import functools
+
 import pytest
 
 from tests import lpips_ref, vgg_ref
@@ -59,7 +62,7 @@ class _Flash(_Splatting):
         self.dev = dev
         self.S = _flash_template(dev, RES, FRAMES)
         self.bg = torch.ones(3, device=dev)
-        self.make, self.gts, _, _ = _flash_targets(self.S, dev, self.bg, FRAMES, N)
+        self.make, self.gts, self.masks, _ = _flash_targets(self.S, dev, self.bg, FRAMES, N)
         g = torch.Generator().manual_seed(8)
         self.deforms = [_deform(N, g, dev) for _ in range(FRAMES)]
 
@@ -74,7 +77,7 @@ class _Flash(_Splatting):
                          lpips_start=lpips_start, **kw)
 
     def frame(self, st, f):
-        return st.step(self.S["cams"][f], self.S["posed"][f], self.deforms[f], self.gts[f])
+        return st.step(self.S["cams"][f], self.S["posed"][f], self.deforms[f], self.gts[f], None if st.mask is None else self.masks[f])
 
     def image_term(self, render, gt):
         from fateavatar_amd.loss import huber_loss_and_grad
@@ -111,6 +114,144 @@ def test_one_step_adds_the_weighted_gradient_to_the_image_gradient(gpu_device, w
     sc.frame(plain, 1)
     torch.cuda.synchronize()
     assert torch.equal(plain._dimage, sc.image_term(plain.out["render"], sc.gts[1])[1])
+
+
+@pytest.mark.parametrize("which", list(SCENES))
+def test_one_step_of_the_full_objective_adds_the_weighted_gradient(gpu_device, which):
+    """The reference's whole objectives, not the default image term: SplattingStep(image_loss=REFERENCE_IMAGE_LOSS,
+    scale_term=REFERENCE_SCALE_TERM, mesh_grad=True, lpips=...) and FlashStep(mouth_mask=True, lpips=..., lpips_start=0) with a
+    mask.  After one eager step the image-gradient buffer is, bit for bit, a second call of the same image-loss entry on the
+    step's render plus another Lpips object's weighted gradient, and `lpips_loss` that object's terms."""
+    import torch
+    dev = gpu_device
+    sc = SCENES[which](dev)
+    if which == "splatting":
+        from fateavatar_amd.loss import pixel_loss_and_grad
+        from fateavatar_amd.splatting import REFERENCE_IMAGE_LOSS, REFERENCE_SCALE_TERM
+        st = sc.build(_lpips(dev, sc.WEIGHT), image_loss=REFERENCE_IMAGE_LOSS, scale_term=REFERENCE_SCALE_TERM, mesh_grad=True)
+        image_term = lambda render: pixel_loss_and_grad(render, sc.gts[1], REFERENCE_IMAGE_LOSS)  # noqa: E731
+    else:
+        from fateavatar_amd.loss import huber_loss_and_grad
+        st = sc.build(_lpips(dev, sc.WEIGHT), lpips_start=0, mouth_mask=True)
+        assert float(sc.masks[1].sum()) > 0
+        image_term = lambda render: huber_loss_and_grad(render, sc.gts[1], st.huber, mask=sc.masks[1])  # noqa: E731
+    loss = sc.frame(st, 1)
+    torch.cuda.synchronize()
+    render = st.out["render"]
+    base_terms, g_base = image_term(render)
+    other = _lpips(dev, sc.WEIGHT)
+    terms, g_p = other.loss_and_grad(render, sc.gts[1])
+    assert float(g_p.abs().max()) > 0 and float(g_base.abs().max()) > 0
+    assert tuple(st.loss_terms.shape) == (3,) and torch.equal(st.loss_terms, base_terms) and torch.equal(loss, base_terms[0])
+    assert float(base_terms[1]) > 0 and float(base_terms[2]) > 0                 # (l1, mse) / (huber, mouth)
+    assert torch.equal(st.lpips_loss, terms) and float(terms[0]) > 0 and bool((terms[1:] > 0).all())
+    assert torch.equal(st._dimage, g_base + g_p)
+    assert not torch.equal(st._dimage, g_base)
+    if which == "splatting":      # (the rest of the objective ran: the scale term's words, the mesh gradient)
+        assert bool(torch.isfinite(st.reg_loss).all()) and float(st.d_verts.abs().max()) > 0 and bool(torch.isfinite(st.d_verts).all())
+
+
+def _still(sc):
+    return {k: 0.0 for k in sc.lrs()}
+
+
+@functools.lru_cache(maxsize=None)
+def _resume_runs(dev):
+    """FlashStep(lpips_start=2) at learning rates 0 (a frame's render is the same bits at every step): a checkpoint after one
+    step, one after four, and what the uninterrupted run's fifth step holds."""
+    import torch
+    sc = _Flash(dev)
+    st = sc.build(_lpips(dev, 0.05), use_graph=False, lrs=_still(sc), lpips_start=2)
+    sc.frame(st, 0)
+    torch.cuda.synchronize()
+    sd1 = st.state_dict()
+    for f in (1, 2, 3):
+        sc.frame(st, f)
+    torch.cuda.synchronize()
+    sd4 = st.state_dict()
+    assert sd1["global_step"] == 1 and sd4["global_step"] == 4 and st.lpips_switches == 1
+    sc.frame(st, 4)
+    torch.cuda.synchronize()
+    fifth = (st.lpips_loss.clone(), st._dimage.clone())
+    assert float(fifth[0][0]) > 0 and not torch.equal(fifth[1], sc.image_term(st.out["render"], sc.gts[4])[1])
+    return sc, sd1, sd4, fifth
+
+
+def test_flash_schedule_resumes_from_a_full_checkpoint_on_either_side_of_the_start(gpu_device):
+    """(a) A full checkpoint from step 4 into a fresh FlashStep(lpips_start=2, use_graph=True): the count comes back, the first
+    step has the term on and holds the uninterrupted run's fifth step bit for bit, the step is captured once with the launch in
+    it.  (b) A checkpoint from step 1 into that object, which is past the start and holds a graph: the term goes off and the
+    graph is dropped, `lpips_loss` is zero and the image gradient the Huber term's alone for one step, then the term is back."""
+    import torch
+    dev = gpu_device
+    sc, sd1, sd4, fifth = _resume_runs(dev)
+    st = sc.build(_lpips(dev, 0.05), use_graph=True, lrs=_still(sc), lpips_start=2)
+    st.load_state_dict(sd4)
+    assert st.host_steps == 4 and st.adam.step_count == 4 and st.lpips_switches == 0
+    sc.frame(st, 4)
+    torch.cuda.synchronize()
+    assert st.lpips_switches == 1 and st.host_steps == 5
+    assert torch.equal(st.lpips_loss, fifth[0]) and torch.equal(st._dimage, fifth[1])
+    seen = []
+    for f in (0, 1, 2):
+        sc.frame(st, f)
+        torch.cuda.synchronize()
+        seen.append((st.captures, st._graph is not None, float(st.lpips_loss[0]) > 0))
+    assert seen == [(0, False, True), (1, True, True), (1, True, True)], seen
+    other = _lpips(dev, 0.05)
+    terms, _ = other.loss_and_grad(st.out["render"], sc.gts[2])
+    assert torch.equal(st.lpips_loss, terms) and st.lpips_switches == 1
+    # ---- (b)
+    st.load_state_dict(sd1)
+    assert st.host_steps == 1 and st._graph is None
+    sc.frame(st, 1)                                                              # step 2: not past the start
+    torch.cuda.synchronize()
+    assert st.lpips_switches == 2 and st._graph is None and bool((st.lpips_loss == 0).all())
+    assert torch.equal(st._dimage, sc.image_term(st.out["render"], sc.gts[1])[1])
+    sc.frame(st, 2)                                                              # step 3: the term is back
+    torch.cuda.synchronize()
+    assert st.lpips_switches == 3 and st.host_steps == 3
+    terms, g_p = other.loss_and_grad(st.out["render"], sc.gts[2])
+    assert torch.equal(st.lpips_loss, terms) and float(terms[0]) > 0
+    assert torch.equal(st._dimage, sc.image_term(st.out["render"], sc.gts[2])[1] + g_p)
+    for f in (3, 4):                                                             # and the step is captured again, the launch in it
+        sc.frame(st, f)
+        torch.cuda.synchronize()
+    assert st.captures == 2 and st._graph is not None
+    terms, _ = other.loss_and_grad(st.out["render"], sc.gts[4])
+    assert torch.equal(st.lpips_loss, terms) and torch.equal(st.lpips_loss, fifth[0])
+
+
+def test_flash_schedule_resumes_from_a_reference_layout_checkpoint(gpu_device):
+    """(c) The reference saves `global_step` and `model` and no optimizer state (train/trainer.py:396-435); its loader restores
+    `global_step` (train/loader.py:102) and the loss applies `cur_step > 15000` to it (train/loss.py:250).  Such a checkpoint
+    from step 4 leaves the optimizer fresh — `host_steps`, `adam.step_count` and `skipped_steps` are 0, as
+    tests/test_gpu_step_resume.py holds — and the SCHEDULE at 4: the next step has the term on and holds the uninterrupted
+    run's fifth step bit for bit.  (With the schedule read from `host_steps` the term stayed off for another `lpips_start`
+    steps: a run resumed at step 20 000 would have trained 15 000 steps without it.)"""
+    import torch
+    dev = gpu_device
+    sc, sd1, sd4, fifth = _resume_runs(dev)
+    bare = {k: v for k, v in sd4.items() if k not in ("optimizer", "densification")}
+    assert sorted(bare) == ["global_step", "model"] and bare["global_step"] == 4
+    st = sc.build(_lpips(dev, 0.05), use_graph=False, lrs=_still(sc), lpips_start=2)
+    assert st.load_state_dict(bare) == []
+    assert st.host_steps == 0 and st.adam.step_count == 0 and st.skipped_steps == 0
+    assert not st.adam.exp_avg.any() and not st.adam.exp_avg_sq.any()
+    sc.frame(st, 4)
+    torch.cuda.synchronize()
+    assert float(st.lpips_loss[0]) > 0 and st.lpips_switches == 1, "the term is off after a resume past lpips_start"
+    assert torch.equal(st.lpips_loss, fifth[0]) and torch.equal(st._dimage, fifth[1])
+    assert st.host_steps == 1 and st.adam.step_count == 1 and st.schedule_steps == 5
+    # a reference-layout checkpoint from BEFORE the start leaves the term off until its step comes
+    st = sc.build(_lpips(dev, 0.05), use_graph=False, lrs=_still(sc), lpips_start=2)
+    st.load_state_dict({k: v for k, v in sd1.items() if k not in ("optimizer", "densification")})
+    seen = []
+    for f in (1, 2):
+        sc.frame(st, f)
+        torch.cuda.synchronize()
+        seen.append((st.schedule_steps, float(st.lpips_loss[0]) > 0, st.lpips_switches))
+    assert seen == [(2, False, 0), (3, True, 1)], seen
 
 
 def _run(sc, dev, use_graph, with_term=True, lrs=None):

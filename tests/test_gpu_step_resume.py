@@ -1,13 +1,14 @@
-"""GPU: what `load_state_dict` leaves behind in each of the four steps, with and without the `optimizer` / `densification`
+"""GPU: what `load_state_dict` leaves behind in each of the five steps, with and without the `optimizer` / `densification`
 entries of the checkpoint.  This is the one place where the steps differ on purpose: TrainStep and AvatarStep REMAP the
-optimizer onto the loaded buffers (the loading object's step count is kept), RiggedStep and SplattingStep build a FRESH one
-(step count 0).  Everything asserted here is exact: counts, zeros and bitwise copies.
+optimizer onto the loaded buffers (the loading object's step count is kept), RiggedStep, SplattingStep and FlashStep build a
+FRESH one (step count 0; FlashStep's LPIPS schedule has a count of its own, tests/test_gpu_lpips_step.py).  Everything asserted
+here is exact: counts, zeros and bitwise copies.
 
 Smallest shapes at which the step is a real one: a tetrahedron (4 faces), 65 Gaussians (one more than a wave), a 64 x 64
 image, no graph.
 
 A checkpoint without an `optimizer` entry, loaded into a step object that has not stepped yet, ends at step count 0 in all
-four classes — the remapped optimizer keeps the count of the object it belongs to, and that is 0.  So the two ways to
+five classes — the remapped optimizer keeps the count of the object it belongs to, and that is 0.  So the two ways to
 rebind cannot be told apart there; the bare checkpoint is therefore ALSO loaded back into the object that took the three
 steps, where the count stays 3 under a remap and returns to 0 under a fresh optimizer."""
 import numpy as np
@@ -19,7 +20,7 @@ from fateavatar_amd import scenes
 P, RES, STEPS = 65, 64, 3
 VERTS = (0.2 * np.array([[1, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]], np.float32) + np.array([0, 0, 1], np.float32))
 FACES = np.array([[0, 1, 2], [0, 3, 1], [0, 2, 3], [1, 3, 2]], np.int32)
-KEEPS_COUNT = {"train": True, "avatar": True, "rigged": False, "splatting": False}
+KEEPS_COUNT = {"train": True, "avatar": True, "rigged": False, "splatting": False, "flash": False}
 
 
 class Case:
@@ -50,6 +51,11 @@ class Case:
             with torch.no_grad():
                 pc._scaling.fill_(float(np.log(0.2)))
             self.st = RiggedStep(pc, faces, cam, bg, verts, use_graph=False)
+        elif kind == "flash":
+            from fateavatar_amd.flash import DEFORM_COLS, FlashGaussians, FlashStep
+            self.st = FlashStep(FlashGaussians(fi, bc, float(np.log(0.05)), dev), faces, cam, bg, verts, use_graph=False)
+            deform = torch.from_numpy((0.01 * rng.standard_normal((P, DEFORM_COLS))).astype(np.float32)).to(dev)
+            self.args = [(cam, verts + 0.01 * k, deform, self.gt) for k in range(STEPS)]
         else:
             from fateavatar_amd.binding import phong_canonical
             from fateavatar_amd.splatting import SplattingGaussians, SplattingStep
@@ -76,7 +82,7 @@ def check_restarted(st, count, kind):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind", ["train", "avatar", "rigged", "splatting"])
+@pytest.mark.parametrize("kind", ["train", "avatar", "rigged", "splatting", "flash"])
 def test_resume_with_and_without_the_optimizer_entries(gpu_device, kind):
     case = Case(kind, gpu_device)
     st = case.run()

@@ -27,7 +27,7 @@ pytestmark = pytest.mark.gpu
 FACTOR, CEILING, FLOOR = 4.0, 2e-4, 2.0 ** -24
 MASK_Z = 1e-5            # a decision that differs from float64's lies within MASK_Z x the layer's RMS pre-activation of its threshold
 CLEAR = 2e-5             # the end-to-end inputs keep every float64 decision this x RMS clear of its threshold
-STACKS = {"vgg16": vgg_ref.VGG16, "small": vgg_ref.SMALL, "wide": vgg_ref.WIDE, "narrow": vgg_ref.NARROW}
+STACKS = {"vgg16": vgg_ref.VGG16, "small": vgg_ref.SMALL, "wide": vgg_ref.WIDE, "narrow": vgg_ref.NARROW, "odd": vgg_ref.ODD}
 # (stack, H, W, size_h, size_w)
 CASES = [("vgg16", 37, 53, 24, 24),       # non-integer downsampling, ragged M in every block
          ("vgg16", 13, 17, 24, 24),       # upsampling, the clamped source coordinates
@@ -45,6 +45,9 @@ PATCHWORK = [("small", 24, 24, 24, 24),   # identity
 WIDE_CASES = [("wide", 31, 39, 26, 30),   # 3 3 3 / 9 3 3: three planes (VGG-16's block 4 at 224^2), ragged M = 1560 / 780
               ("wide", 32, 32, 32, 32),   # 1 1 1 / 9 3 3: the forward exactly at tiles == 256
               ("wide", 40, 24, 64, 32)]   # 1 1 1 / 9 1 1: the gradient unsplit too (at tiles == 256), SEED and MASK epilogues in-kernel
+# vgg_ref.ODD: GEMMs with N = 192, 320 and 448 — three, five and seven 64-column tiles, where every other stack has 1, 2, 4 or 8
+ODD_CASES = [("odd", 16, 16, 16, 16),     # M = 512 / 128: whole 64-row tiles
+             ("odd", 24, 40, 24, 40)]     # non-square, M = 1920 / 480: ragged against 128 rows
 
 
 def _rel(a, b):
@@ -277,6 +280,13 @@ def test_every_split_plan_against_float64(gpu_device, case):
         torch.cuda.synchronize()
         assert torch.equal(loss_t.cpu(), loss) and torch.equal(g_t.cpu(), grad), tile
         assert all(torch.equal(a, b) for a, b in zip(p.saved_activations(), acts)), tile
+
+
+@pytest.mark.parametrize("case", ODD_CASES, ids=_ids)
+def test_odd_widths_against_float64(gpu_device, case):
+    """The held set on vgg_ref.ODD, whose widths are odd multiples of 64: the forward GEMMs' N is 192, 320 and 448, the gradient
+    GEMMs' 320, 192 and 64, and the last column tile of each is the third, fifth or seventh — no power of two anywhere."""
+    _held_to_float64(gpu_device, case, _case(*case))
 
 
 @pytest.mark.parametrize("case", END_TO_END, ids=_ids)

@@ -252,6 +252,76 @@ def test_dead_pixel_construct_yields_dead_pixels_in_float64():
     assert float((pin - g).norm() / g.norm()) < 1e-13
 
 
+def test_dead_target_construct_yields_all_three_classes_in_float64():
+    W, B, lin, img, gt = lpips_ref.dead_target_case()
+    r = lpips_ref.forward(W, B, lin, vgg_ref.SMALL, img, gt, (24, 24))
+    assert lpips_ref.dead_pixels(r["a"], vgg_ref.SMALL) == [(123, 169), (16, 22)]
+    # (both dead, rendered only, target only)
+    assert [tuple(int(m.sum()) for m in masks) for masks in lpips_ref.dead_classes(r["a"], vgg_ref.SMALL)] == [(31, 92, 138), (1, 15, 21)]
+    assert abs(float(r["loss"]) - 0.0138) < 5e-5
+    loss, g = lpips_ref.autograd_gradient(W, B, lin, vgg_ref.SMALL, img, gt, (24, 24))
+    assert bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0 and float(loss) == float(r["loss"])
+    pin = lpips_ref.pinned_backward(W, lin, vgg_ref.SMALL, r["a"], (24, 24), (24, 24))
+    assert float((pin - g).norm() / g.norm()) < 1e-13
+
+
+def test_dead_target_rule_is_stock_autograd():
+    """The target half of the dead-pixel rule is the package's own behaviour: the target takes no gradient, b / (0 + eps) is a
+    finite 0, so STOCK autograd through the formula as the package writes it is finite at a dead target under a live rendered
+    pixel — and equals the restatement's closed-form seed there, at both taps of the dead-target case."""
+    W, B, lin, img, gt = lpips_ref.dead_target_case()
+    r = lpips_ref.forward(W, B, lin, vgg_ref.SMALL, img, gt, (24, 24))
+    taps = [l for l, y in enumerate(vgg_ref.SMALL) if y[3]]
+    for l, w, (both, rendered, target) in zip(taps, lin, lpips_ref.dead_classes(r["a"], vgg_ref.SMALL)):
+        a, b = r["a"][l][0], r["a"][l][1]
+        assert int(target.sum()) > 0 and bool((b[:, target] == 0).all()) and bool((a[:, target].pow(2).sum(0) > 0).all())
+        leaf = a[:, target].clone().requires_grad_(True)
+        term = lpips_ref.tap_term_stock(leaf, b[:, target], w.double()) / (a.shape[1] * a.shape[2])
+        (g,) = torch.autograd.grad(term, leaf)
+        seed = lpips_ref.tap_seed(a, b, w)[:, target]
+        assert bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0
+        assert float((seed - g).abs().max()) <= 1e-12 * float(g.abs().max())
+
+
+def test_new_gpu_cases_pass_the_tap_kernels_grid_cap_and_have_odd_widths():
+    """k_lpips_tap: FR_VGG_LOSS_BLOCKS workgroups of four waves, one pixel a wave and sweep.  A change of the cap breaks this
+    test instead of silently emptying tests/test_gpu_lpips.py's second sweep."""
+    from fateavatar_amd import _lib
+    from fateavatar_amd import perceptual as P
+    from tests import test_gpu_lpips as T
+    sweep = 4 * _lib.FR_VGG_LOSS_BLOCKS
+    first_taps = []
+    for stack, H, W, sh, sw in T.PAST_THE_CAP:
+        f = _features(T.STACKS[stack], (sh, sw))
+        taps = [h * w for (h, w), y in zip(f.extents(), f.layers) if y.tap_after]
+        first_taps.append(taps[0])
+        assert sweep < taps[0] < 2 * sweep and all(t < sweep for t in taps[1:])
+    assert first_taps == [70 * 62, 80 * 64] and (35 * 31) % 4 != 0 and (70 * 62 - sweep) // 4 == 61
+    assert all(h * w <= sweep for c in T.CASES for h, w in [c[3:5]])                  # the earlier cases: one sweep
+    P.check_layers(vgg_ref.ODD, (16, 16))
+    P.check_layers(vgg_ref.ODD, (24, 40))
+    assert {c // 64 for _, c, _, tap in vgg_ref.ODD if tap} == {3, 5, 7}
+    assert [c[0] for c in T.PAST_THE_CAP + T.ODD_CASES] == ["small", "lpips13", "odd", "odd"]
+
+
+def test_patchwork_cases_have_ties_and_an_interior_in_float64():
+    """tests/test_gpu_lpips.py's flat-region cases in float64: more than 1000 live tied pool windows wherever the stack has a
+    pool (vgg_ref.WIDE has none: 0), more than 1000 live units whose rendered and target values are equal, no dead pixel, and
+    a non-empty interior of the shared background for the two shallow stacks."""
+    from tests import test_gpu_lpips as T
+    from tests.test_gpu_vgg import _background_interior
+    seen = {}
+    for case in T.PATCHWORK:
+        c = T._case(*case, patchwork=True)
+        layers = T.STACKS[case[0]]
+        seen[case[0]] = (vgg_ref.live_ties(c["r64"]["a"], layers), _background_interior(layers, *case[1:]))
+        assert lpips_ref.dead_pixels(c["r64"]["a"], layers) == [(0, 0)] * sum(1 for y in layers if y[3])
+    print(seen)
+    assert seen["small"][0][0] >= 1000 and seen["lpips13"][0][0] >= 1000 and seen["wide"][0][0] == 0
+    assert all(v[0][1] >= 1000 for v in seen.values())
+    assert seen["small"][1] == (3, 3) and seen["wide"][1] == (8, 8) and seen["lpips13"][1] == (0, 0)
+
+
 def test_wide_cases_send_the_seed_through_every_epilogue():
     """vgg_ref.WIDE has taps behind layers 1 and 3 and no pool: the tap-1 seed is added by the epilogue of layer 2's gradient
     GEMM (N = 512) — in-kernel where that GEMM is unsplit, in the split-reduce where it is split — and the last tap's seed is

@@ -19,6 +19,8 @@ SMALL = ((3, 64, False, False), (64, 64, False, True), (64, 128, True, True))
 WIDE = ((3, 64, False, False), (64, 512, False, True), (512, 512, False, False), (512, 512, False, True))
 # VGG16's flags with every width 64: the stack the recorded run of the reference's own module uses (tests/golden/make_reference_runs.py)
 NARROW = tuple((3 if i == 0 else 64, 64, pool, tap) for i, (_, _, pool, tap) in enumerate(VGG16))
+# widths whose c_out / 64 is odd: three, five and seven 64-column GEMM tiles, and as many values per lane in the LPIPS tap kernel
+ODD = ((3, 64, False, False), (64, 192, False, True), (192, 320, True, True), (320, 448, False, True))
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 
