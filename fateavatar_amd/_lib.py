@@ -181,6 +181,10 @@ class fr_scale_term_config(C.Structure):
     _fields_ = [("weight", C.c_float), ("scale_threshold", C.c_float), ("max_scaling", C.c_float)]
 
 
+class fr_scale_ratio_config(C.Structure):
+    _fields_ = [("weight", C.c_float), ("scale_threshold", C.c_float)]
+
+
 class fr_inputs(C.Structure):
     _fields_ = [(n, _fp) for n in ("background", "means3D", "shs", "colors_precomp", "opacities", "scales",
                                    "rotations", "cov3D_precomp", "viewmatrix", "projmatrix", "campos")]
@@ -198,7 +202,7 @@ class fr_counts(C.Structure):
 
 EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile_enable", "fr_profile_read", "fr_geometry_bytes", "fr_image_bytes",
            "fr_binning_bytes", "fr_planes_bytes", "fr_camera_grad_workspace_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
-           "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_huber_workspace_bytes", "fr_huber_loss_grad", "fr_pixel_loss_workspace_bytes", "fr_pixel_loss_grad", "fr_scale_term_workspace_bytes", "fr_scale_term", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_mesh_terms_workspace_bytes", "fr_mesh_terms", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
+           "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_huber_workspace_bytes", "fr_huber_loss_grad", "fr_pixel_loss_workspace_bytes", "fr_pixel_loss_grad", "fr_scale_term_workspace_bytes", "fr_scale_term", "fr_scale_ratio_workspace_bytes", "fr_scale_ratio_term", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_mesh_terms_workspace_bytes", "fr_mesh_terms", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
            "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_bind_backward_deform", "fr_phong_frame", "fr_bind_backward_phong_frame", "fr_phong_frame_backward_workspace_bytes", "fr_phong_frame_backward", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward",
            "fr_point_lbs_forward", "fr_point_lbs_backward", "fr_point_lbs_pose_workspace_bytes", "fr_point_lbs_backward_pose", "fr_nearest_vertex", "fr_lbs_terms_workspace_bytes", "fr_lbs_terms",
            "fr_mlp_workspace_bytes", "fr_mlp_forward", "fr_mlp_backward",
@@ -343,6 +347,10 @@ def lib():
     L.fr_scale_term_workspace_bytes.restype = C.c_size_t
     L.fr_scale_term.argtypes = [C.POINTER(fr_scale_term_config), C.c_int32, _fp, _fp, _fp, C.c_void_p, C.c_void_p]
     L.fr_scale_term.restype = C.c_int
+    L.fr_scale_ratio_workspace_bytes.argtypes = []
+    L.fr_scale_ratio_workspace_bytes.restype = C.c_size_t
+    L.fr_scale_ratio_term.argtypes = [C.POINTER(fr_scale_ratio_config), C.c_int32, _fp, _fp, _fp, C.c_void_p, C.c_void_p]
+    L.fr_scale_ratio_term.restype = C.c_int
     L.fr_regularise_workspace_bytes.argtypes = []
     L.fr_regularise_workspace_bytes.restype = C.c_size_t
     L.fr_gaussian_regularise.argtypes = [C.POINTER(fr_regularise_config), C.c_int32, _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p]

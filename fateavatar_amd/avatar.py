@@ -18,6 +18,7 @@ statistics and broadcast, so every rank appends identical rows.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import numpy as np
@@ -32,7 +33,8 @@ from .model import TorchCamera
 from .optim import FusedAdam
 from .perceptual import Perceptual
 from .render import render
-from .loss import MeshTerms, l1_loss_and_grad, l1_workspace, mesh_terms_and_grad, mesh_terms_workspace
+from .loss import (MeshTerms, ScaleRatioTerm, l1_loss_and_grad, l1_workspace, mesh_terms_and_grad, mesh_terms_workspace,
+                   scale_ratio_term_and_grad, scale_ratio_workspace)
 from .train import BoundStep, TrainStep
 
 # config/fateavatar.yaml:34-39 (group names of train/optim.py:15-21)
@@ -40,6 +42,8 @@ FATE_LRS = dict(opacity=0.05, offset=0.0016, color=0.0025, rotation=0.001, scali
 # config/fateavatar.yaml:41-47
 FATE_MAINTAIN = dict(opacity_reset_interval=60000, densify_interval=3000, prune_interval=2000, min_opacity=0.005,
                      increase_num=1000, max_points_num=200000)
+# config/fateavatar.yaml:13-25: scale_loss 0.1, scale_threshold 9.0
+REFERENCE_SCALE_TERM = ScaleRatioTerm(0.1, 9.0)
 
 
 class AvatarGaussians(FlatParams):
@@ -126,12 +130,14 @@ class AvatarStep(BoundStep):
     LRS = FATE_LRS
     LR_KEYS = {"_opacity": "opacity", "_offset": "offset", "_features_dc": "color", "_rotation": "rotation", "_scaling": "scaling"}
     CAMERA_GRAD = True
+    K = 1                   # frames per step (AvatarBatchStep: its views_per_step)
 
     def __init__(self, pc: AvatarGaussians, faces: torch.Tensor, canonical_verts: torch.Tensor, camera: TorchCamera,
                  bg: torch.Tensor, lrs: Optional[dict] = None, shell_len: float = 0.05, resize_scale: bool = True,
                  use_graph: bool = True, fold_binding: bool = True, keep_coherent: bool = False, vertex_grad: bool = False,
                  mesh_terms: Optional[MeshTerms] = None, camera_grad: bool = False, flame: Optional[FlameMesh] = None,
-                 flame_lrs: Optional[dict] = None, perceptual: Optional[Perceptual] = None):
+                 flame_lrs: Optional[dict] = None, perceptual: Optional[Perceptual] = None,
+                 scale_term: Optional[ScaleRatioTerm] = None):
         """`keep_coherent`: after every `uv_densify` the rows are re-stored in a spatially coherent order (`sort_coherent`):
         the reference appends the new rows at the end (model/fateavatar.py:640-665), so a set that started in UV-raster
         order (mesh_sampling.py:86-138: neighbours in storage are neighbours on the mesh) grows an unordered tail; the
@@ -162,7 +168,16 @@ class AvatarStep(BoundStep):
         ONE call directly behind the L1 launch (csrc/fr_vgg.hip) ADDS weight x its gradient to the L1 gradient in the step's
         image-gradient buffer, before the rasterizer's backward; `perceptual_loss` [1 + T] then holds the step's unweighted
         sum of the tap terms and the terms, `loss` stays the L1 term (the reference's total is
-        loss + perceptual.weight * perceptual_loss[0] + ...).  None (default): not one launch changes."""
+        loss + perceptual.weight * perceptual_loss[0] + ...).  None (default): not one launch changes.
+        `scale_term`: a `ScaleRatioTerm` (REFERENCE_SCALE_TERM holds the reference's 0.1 / 9.0) adds FateAvatar's scale term
+        (train/loss.py:144-151) on the RAW `_scaling` to every step: ONE launch (`loss.scale_ratio_term_and_grad`) behind the
+        frame's backward adds weight x its gradient into the flat gradient buffer, in front of the data-parallel exchange and
+        Adam; `reg_loss` [2] then holds the step's unweighted (scale_loss, rows over the threshold), `loss` stays the L1 term.
+        The term has no state: checkpoints and density control are what they are without it.  None (default): no such
+        launch, `reg_loss` is None."""
+        if scale_term is not None and not isinstance(scale_term, ScaleRatioTerm):
+            raise TypeError(f"AvatarStep: `scale_term` is a ScaleRatioTerm or None, not {type(scale_term).__name__}")
+        self.scale_term = None if scale_term is None else ScaleRatioTerm(*[float(x) for x in scale_term])
         self.keep_coherent = bool(keep_coherent)
         if perceptual is not None:
             if not isinstance(perceptual, Perceptual):
@@ -193,6 +208,10 @@ class AvatarStep(BoundStep):
             self.d_expression, self.d_pose = torch.zeros(flame.n_exp, device=self.dev), torch.zeros(15, device=self.dev)
         # (the term's workspace is its own, allocated with it: outside any capture)
         self.perceptual_loss = None if perceptual is None else torch.zeros(1 + perceptual.n_terms, device=self.dev)
+        # the reference's out['scale_loss'] of the step (unweighted) and the rows over the threshold, written by the term's
+        # launch; the scratch is the step's own and its size does not depend on P: density control leaves both alone
+        self.reg_loss = None if self.scale_term is None else torch.zeros(2, device=self.dev)
+        self._ratio_ws = None if self.scale_term is None else scale_ratio_workspace(self.dev)
         self.mesh_loss = self.verts_orig = self.laplacian = self._mesh_ws = None
         if self.mesh_terms is not None:
             from .binding import mesh_laplacian
@@ -227,6 +246,18 @@ class AvatarStep(BoundStep):
         if self.flame is not None:
             self.flame_adam.step()
 
+    def _add_scale_term(self, pc):
+        """train/loss.py:144-151: weight x the scale term's gradient is ADDED to the image term's dL/d_scaling in `pc`'s flat
+        gradient buffer, ONCE per step, in front of the exchange and Adam.  Adam divides the summed gradient by the step's K
+        frames and the ranks: the launch carries K x weight (K = 1 here; exact in float32 for the batch step's K = 2, 4), and
+        under data-parallel every rank adds weight x g to identical parameters, so the all-reduced sum is world x weight x g
+        and Adam's 1 / world gives weight x g.  A replay that overflowed its binning capacity back-propagated zeros and its
+        Adam launch skips the step (the overflow word): what this launch added to the zeroed gradient is never applied."""
+        pc.collect_grads()
+        t = self.scale_term
+        scale_ratio_term_and_grad(pc._scaling, pc.grad_view("_scaling"), out=self.reg_loss,
+                                  terms=ScaleRatioTerm(ctypes.c_float(t.weight).value * self.K, t.scale_threshold), workspace=self._ratio_ws)
+
     def _forward_backward_on(self, L):
         """Bind, render, L1, backward for one frame.  `L` holds what the frame reads and writes — pc, verts, cam, gt, loss,
         _dimage, xyz_gradient_accum, denom, out: this object itself, or one lane of an AvatarBatchStep."""
@@ -257,6 +288,8 @@ class AvatarStep(BoundStep):
                                 workspace=self._mesh_ws)
         if self.flame is not None:     # d_verts -> the deltas' flat gradient, d_expression, d_pose: two launches
             self.flame.backward_from(self.d_verts, self.expression, self.pose, self.d_expression, self.d_pose)
+        if self.scale_term is not None and getattr(L, "k", 0) == 0:    # (a batch step's lanes: once per step, in lane 0's body)
+            self._add_scale_term(pc)
         L.out = self._kept(out)
 
     def step(self, camera: TorchCamera, posed_verts, gt_image: torch.Tensor,
@@ -496,6 +529,8 @@ class AvatarBatchStep(AvatarStep):
         for L, out in zip(self.lanes, outs):
             L.out = self._kept(out)
         torch.autograd.backward(images, grad_tensors=grads)
+        if self.scale_term is not None:            # once per step, into lane 0's gradient: K x weight (_add_scale_term)
+            self._add_scale_term(self.lanes[0].pc)
         if self.exchange:                          # sum of the local lanes, then the sum over the ranks; Adam scales
             flat = [L.pc.exchange_buffer() for L in self.lanes]   # (gradients + overflow words: the words add up too)
             for g in flat[1:]:

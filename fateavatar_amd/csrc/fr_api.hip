@@ -676,6 +676,19 @@ int fr_scale_term(const fr_scale_term_config* cfg, int32_t P, const float* scali
     return launch_scale_term(*cfg, P, scaling, d_scaling, loss, workspace, static_cast<hipStream_t>(stream));
 }
 
+size_t fr_scale_ratio_workspace_bytes(void) { return scale_ratio_workspace_bytes(); }
+
+int fr_scale_ratio_term(const fr_scale_ratio_config* cfg, int32_t P, const float* scaling, float* d_scaling, float* loss,
+                        void* workspace, void* stream)
+{
+    if (!cfg || P < 0) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_scale_ratio_term: null configuration or negative P");
+    // (the rows over the threshold are counted in floats: exact below 2^24)
+    if (P >= (1 << 24)) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_scale_ratio_term: P < 2^24");
+    if (P > 0 && !scaling) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_scale_ratio_term: null parameter array");
+    if (!workspace || !loss) return fail_msg(FR_ERR_INVALID_ARGUMENT, "fr_scale_ratio_term: null workspace or loss");
+    return launch_scale_ratio_term(*cfg, P, scaling, d_scaling, loss, workspace, static_cast<hipStream_t>(stream));
+}
+
 void fr_ssim_window(float out[11])
 {
     if (out) ssim_window(out);

@@ -533,6 +533,9 @@ int launch_pixel_loss_grad(const fr_pixel_loss_config& cfg, int C, int H, int W,
 size_t scale_term_workspace_bytes();
 int launch_scale_term(const fr_scale_term_config& cfg, int P, const float* scaling, float* d_scaling, float* loss, void* workspace,
                       hipStream_t s);
+size_t scale_ratio_workspace_bytes();
+int launch_scale_ratio_term(const fr_scale_ratio_config& cfg, int P, const float* scaling, float* d_scaling, float* loss,
+                            void* workspace, hipStream_t s);
 // L1 + D-SSIM image loss and its gradient (fr_ssim.hip)
 void ssim_window(float out[11]);
 size_t image_loss_workspace_bytes(int C, int H, int W);

@@ -622,4 +622,82 @@ int launch_scale_term(const fr_scale_term_config& cfg, int P, const float* scali
     return FR_OK;
 }
 
+// ---------------------------------------------------------------- FateAvatar's scale-ratio term, one launch
+// reference: FateAvatarLoss.accumulate_gradients (train/loss.py:144-151) on model_outputs['scale'] = exp(_scaling), the RAW
+// parameter (model/fateavatar.py:282: not the face-resized scale the rasterizer sees):
+//     ratio      = scale.max(-1) / scale.min(-1)
+//     scale_loss = relu(ratio - scale_threshold).mean()
+// The mean's denominator is P, known at launch: unlike SplattingAvatar's term above, ONE launch gives the loss and the
+// gradient.  Lane = Gaussian: the row's relu(ratio - threshold) and, over the threshold,  +weight / P x ratio  ADDED to its
+// largest component's gradient and  -weight / P x ratio  to its smallest (d ratio / d _scaling[argmax] = ratio, [argmin] =
+// -ratio), by the lane that owns the row (no atomics).  The ratio is the reference's float32 quotient of the two activated
+// components, not exp(smax - smin).  Sub-gradients are autograd's: relu passes nothing at exactly 0; max / min give their
+// gradient to ONE index, the FIRST of equal components (scale_row's rule); where argmax == argmin (three equal components)
+// the two contributions are formed in registers and cancel to an exact 0 in one store.  A row whose ratio is not finite — a
+// NaN component, exp overflowing, the smallest component underflowing to 0 — adds nothing to the loss, the count or the
+// gradient (a non-finite Gaussian is dropped from a frame the same way; stock PyTorch would make the loss NaN or inf).  The
+// count of rows over the threshold travels as a float, exact below 2^24 rows (the entry point refuses more).
+struct ScaleRatioArgs {
+    const float* scaling;
+    float* d_scaling;     // null: no gradient traffic (also what a zero weight gives)
+    float* partial;       // [2][kRegMaxBlocks]
+    unsigned* counter;
+    float* loss;          // {scale_loss, rows over the threshold}, unweighted
+    int P;
+    float g, scale_threshold;   // g = weight / P
+};
+
+__global__ void __launch_bounds__(kSumThreads) k_scale_ratio_term(ScaleRatioArgs a)
+{
+    const float* __restrict__ scaling = a.scaling;
+    float* __restrict__ d_scaling = a.d_scaling;
+    const unsigned stride = gridDim.x * blockDim.x;
+    float acc[2] = {0.f, 0.f};   // sum of relu(ratio - threshold), rows over the threshold
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)a.P; i += stride) {
+        const size_t o = (size_t)i * 3;
+        const float e0 = act_exp(scaling[o]), e1 = act_exp(scaling[o + 1]), e2 = act_exp(scaling[o + 2]);
+        float smax = e0, smin = e0;
+        int amax = 0, amin = 0;
+        if (e1 > smax) smax = e1, amax = 1;
+        if (e2 > smax) smax = e2, amax = 2;
+        if (e1 < smin) smin = e1, amin = 1;
+        if (e2 < smin) smin = e2, amin = 2;
+        const float ratio = smax / smin;
+        // (every comparison with a NaN is false: a NaN component, inf / inf and 0 / 0 fail the last one; x / 0 the one before)
+        const bool finite = e0 == e0 && e1 == e1 && e2 == e2 && fabsf(ratio) < INFINITY;
+        if (!finite || !(ratio > a.scale_threshold)) continue;
+        acc[0] += ratio - a.scale_threshold, acc[1] += 1.f;
+        if (!d_scaling) continue;
+        const float g = a.g * ratio;
+        if (amax == amin) {
+            d_scaling[o + amax] += g - g;
+        } else {
+            d_scaling[o + amax] += g;
+            d_scaling[o + amin] -= g;
+        }
+    }
+    if (!sum_over_workgroups(acc, a.partial, kRegMaxBlocks, a.counter, blockIdx.x, gridDim.x)) return;
+    a.loss[0] = acc[0] / (float)a.P;
+    a.loss[1] = acc[1];
+}
+
+size_t scale_ratio_workspace_bytes() { return done_workspace_bytes(2 * kRegMaxBlocks); }
+
+int launch_scale_ratio_term(const fr_scale_ratio_config& cfg, int P, const float* scaling, float* d_scaling, float* loss,
+                            void* workspace, hipStream_t s)
+{
+    if (P <= 0) return FR_OK;
+    const unsigned blocks = capped_blocks((unsigned)P, kSumThreads, kRegMaxBlocks);
+    const DoneWorkspace ws = done_workspace(workspace);
+    ScaleRatioArgs a;
+    a.scaling = scaling;
+    a.d_scaling = cfg.weight != 0.f ? d_scaling : nullptr;   // a zero weight: the array is not touched
+    a.counter = ws.counter, a.partial = ws.partial;
+    a.loss = loss, a.P = P;
+    a.g = (float)((double)cfg.weight / (double)P), a.scale_threshold = cfg.scale_threshold;
+    hipLaunchKernelGGL(k_scale_ratio_term, dim3(blocks), dim3(kSumThreads), 0, s, a);
+    FR_HIP(hipGetLastError());
+    return FR_OK;
+}
+
 }  // namespace fr

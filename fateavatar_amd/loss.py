@@ -9,7 +9,9 @@ launch of the HIP library (`fr_l1_loss_grad`, include/fr_rasterizer.h); the call
 reference's function as an autograd op on those kernels.  `huber_loss_and_grad` is FlashAvatar's Huber term with its optional
 mouth-mask term (train/loss.py:217-221, :231-239) in one launch (`fr_huber_loss_grad`).  `pixel_loss_and_grad` is
 SplattingAvatar's L1 + MSE image term (train/loss.py:279-283, :288-304) in one launch (`fr_pixel_loss_grad`) and
-`scale_term_and_grad` its scale term (:307-315) in two (`fr_scale_term`).  There is no CPU path."""
+`scale_term_and_grad` its scale term (:307-315) in two (`fr_scale_term`).  `scale_ratio_term_and_grad` is FateAvatar's scale-ratio
+term (:144-151) in one launch (`fr_scale_ratio_term`) and `scale_ratio_loss` the same expression as an autograd op.  There is no
+CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,6 +27,7 @@ _l1_ws = StreamWorkspace("l1_workspace", lambda: _lib.lib().fr_l1_workspace_byte
 _huber_ws = StreamWorkspace("huber_workspace", lambda: _lib.lib().fr_huber_workspace_bytes(), "image's")
 _pixel_ws = StreamWorkspace("pixel_loss_workspace", lambda: _lib.lib().fr_pixel_loss_workspace_bytes(), "image's")
 _scale_ws = StreamWorkspace("scale_term_workspace", lambda: _lib.lib().fr_scale_term_workspace_bytes(), "parameters'")
+_ratio_ws = StreamWorkspace("scale_ratio_workspace", lambda: _lib.lib().fr_scale_ratio_workspace_bytes(), "parameters'")
 _reg_ws = StreamWorkspace("regulariser_workspace", lambda: _lib.lib().fr_regularise_workspace_bytes(), "parameters'")
 _mesh_ws = StreamWorkspace("mesh_terms_workspace", lambda: _lib.lib().fr_mesh_terms_workspace_bytes(), "vertices'")
 
@@ -247,6 +250,71 @@ def scale_term_and_grad(scaling: torch.Tensor, d_scaling: Optional[torch.Tensor]
     _lib.launch("fr_scale_term", dev, C.byref(cfg), P, scaling.data_ptr() if P else None,
                 d_scaling.data_ptr() if d_scaling is not None and P else None, loss.data_ptr(), ws.data_ptr())
     return loss
+
+
+# ---- FateAvatar's scale-ratio term (FateAvatarLoss, train/loss.py:144-151): ONE launch (`fr_scale_ratio_term`) gives the unweighted
+# loss with the number of rows over the threshold and adds the weighted gradient into dL/d_scaling
+class ScaleRatioTerm(NamedTuple):
+    """FateAvatar's scale term: its weight and the ratio a row's largest scale may have to its smallest before the term acts
+    (config/fateavatar.yaml:13-25 has scale_loss 0.1, scale_threshold 9.0)."""
+    weight: float = 0.1
+    scale_threshold: float = 9.0
+
+
+def scale_ratio_workspace(dev: torch.device) -> torch.Tensor:
+    """A fresh zeroed workspace for `scale_ratio_term_and_grad(..., workspace=)`."""
+    return _ratio_ws.fresh(dev)
+
+
+def scale_ratio_term_and_grad(scaling: torch.Tensor, d_scaling: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
+                              terms=ScaleRatioTerm(), workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """FateAvatar's scale term (train/loss.py:144-151) on the raw `_scaling` [P,3] in ONE launch (`fr_scale_ratio_term`): with
+    scale = exp(scaling) and ratio = scale.max(-1) / scale.min(-1), returns `out` = (mean over all P rows of relu(ratio -
+    terms.scale_threshold), the number of rows over the threshold), UNWEIGHTED, a 2-element device tensor, and ADDS terms.weight *
+    d scale_loss / d _scaling into `d_scaling` ([P,3] gradient buffer: +weight / P * ratio on a row's largest component, the
+    same subtracted from its smallest, the first of equal components; None, or a weight of 0: no gradient traffic).  A row
+    whose ratio is not finite (a NaN, an overflowing exp, a smallest scale that underflows to 0) adds nothing anywhere.
+    `workspace`: scratch from `scale_ratio_workspace()`; by default one is kept per (device, current stream) — launches that
+    may overlap must not share one.  There is no CPU path."""
+    if not scaling.is_cuda:
+        raise RuntimeError("scale_ratio_term_and_grad needs device tensors (there is no CPU path)")
+    dev = scaling.device
+    P = int(scaling.shape[0])
+    scaling = scaling.detach()
+    _check_rows3("scale_ratio_term_and_grad", dev, P, (scaling, d_scaling), "[P,3] tensors of one device")
+    loss = _out_words("scale_ratio_term_and_grad", out, 2, dev, "parameters'", fresh=torch.zeros)   # (P == 0 launches nothing)
+    ws = _ratio_ws.resolve(dev, workspace, "scale_ratio_term_and_grad")
+    cfg = _lib.fr_scale_ratio_config(float(terms[0]), float(terms[1]))
+    _lib.launch("fr_scale_ratio_term", dev, C.byref(cfg), P, scaling.data_ptr() if P else None,
+                d_scaling.data_ptr() if d_scaling is not None and P else None, loss.data_ptr(), ws.data_ptr())
+    return loss
+
+
+class _ScaleRatio(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scaling, scale_threshold):
+        s = _f32c(scaling.detach())
+        grad = torch.zeros_like(s) if ctx.needs_input_grad[0] else None     # None: the loss only
+        loss = scale_ratio_term_and_grad(s, grad, terms=ScaleRatioTerm(1.0, scale_threshold))
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        ctx.in_dtype = scaling.dtype
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        return (grad * grad_output).to(ctx.in_dtype), None
+
+
+def scale_ratio_loss(scaling: torch.Tensor, scale_threshold: float = 9.0) -> torch.Tensor:
+    """FateAvatar's scale expression — also `UVDecoderLoss`'s scale term on a baked avatar's decoded log-scales
+    (train/loss.py:597-604) — as a 0-dim tensor, UNWEIGHTED: relu(exp(scaling).max(-1) / exp(scaling).min(-1) -
+    scale_threshold).mean(), differentiable with respect to `scaling` [P,3] (the fused kernel's gradient with weight 1, scaled
+    by the incoming one), with `scale_ratio_term_and_grad`'s rules for ties and non-finite rows."""
+    if scaling.dim() != 2 or scaling.shape[-1] != 3:
+        raise RuntimeError(f"scale_ratio_loss: log-scales are [P,3], got {tuple(scaling.shape)}")
+    return _ScaleRatio.apply(scaling, float(scale_threshold))
 
 
 def regulariser_workspace(dev: torch.device) -> torch.Tensor:

@@ -479,6 +479,30 @@ size_t fr_scale_term_workspace_bytes(void);
 int fr_scale_term(const fr_scale_term_config* cfg, int32_t P, const float* scaling, float* d_scaling, float* loss,
                   void* workspace, void* hip_stream);
 
+/* ---- FateAvatar's scale-ratio term and its gradient in ONE launch (reference: FateAvatarLoss.accumulate_gradients,
+ * train/loss.py:144-151, on model_outputs['scale'] = exp(_scaling), the RAW parameter, model/fateavatar.py:282).  `scaling`: P
+ * rows of 3 raw floats.  With scale = exp(scaling), smax / smin a row's largest / smallest component and ratio = smax / smin
+ * (the float32 quotient, as the reference forms it):
+ *   loss[0] = mean over ALL P rows of relu(ratio - scale_threshold),   loss[1] = the rows with ratio > scale_threshold
+ * both UNWEIGHTED (the count an exact integer), and for every such row `weight / P * ratio` is ADDED to d_scaling[row][argmax]
+ * and SUBTRACTED from d_scaling[row][argmin] (read-modify-write by the lane that owns the row, no atomics; nothing anywhere
+ * else).  Sub-gradients are autograd's: a ratio exactly at the threshold adds nothing; the FIRST of equal components takes
+ * max's / min's gradient; where argmax == argmin (three equal components) the two contributions cancel to an exact 0.  A row
+ * whose ratio is not finite (a NaN component, exp overflowing, the smallest component underflowing to 0) adds nothing to the
+ * loss, the count or the gradient, where stock PyTorch would make the loss NaN or inf.  Per-workgroup partials summed in
+ * index order by the workgroup that finishes last: the same bits on every run.  `d_scaling` NULL or a weight of 0: no
+ * gradient traffic.  `workspace`: fr_scale_ratio_workspace_bytes() bytes of device memory, zeroed ONCE by the caller; the
+ * kernel leaves it zeroed; not to be shared by launches that can overlap on the device.  No allocation, no synchronisation:
+ * the call can be captured in a graph.  P == 0 launches nothing and leaves `loss` as it is; P >= 2^24 is
+ * FR_ERR_INVALID_ARGUMENT (the count is summed in floats, exact below that).  `loss`: two device floats. */
+typedef struct fr_scale_ratio_config {
+    float weight;                         /* reference: 0.1 (scale_loss, config/fateavatar.yaml:13-25) */
+    float scale_threshold;                /* reference: 9.0 */
+} fr_scale_ratio_config;
+size_t fr_scale_ratio_workspace_bytes(void);
+int fr_scale_ratio_term(const fr_scale_ratio_config* cfg, int32_t P, const float* scaling, float* d_scaling, float* loss,
+                        void* workspace, void* hip_stream);
+
 /* ---- GaussianAvatars' two per-Gaussian regularisers and their gradients in ONE launch (reference:
  * GaussianAvatarsLoss.accumulate_gradients, train/loss.py:367-379, on the raw local parameters,
  * model/baseline/gaussianavatars.py:196-197):

@@ -30,6 +30,10 @@ FateAvatar's VGG perceptual term at weight 0.1 in the step: `AvatarStep(perceptu
 behind the L1 launch adds its gradient to the L1 gradient (csrc/fr_vgg.hip).  Seeded He-normal weights unless --vgg-weights names
 a torch-saved state dict in torchvision's naming.  --torch-perceptual: the A/B, the same term at the same place through
 F.conv2d and autograd.  The report gains `perceptual_loss` (the sum of the tap terms, then the terms).
+    python tools/train_synthetic.py --fateavatar --scale-term [--fused-flame --perceptual | --train-mesh | --views-per-step K]
+FateAvatar's scale-ratio term at weight 0.1, threshold 9.0 in the step: `AvatarStep(scale_term=REFERENCE_SCALE_TERM)` — one launch
+behind the backward adds its gradient to `_scaling`'s in front of Adam (csrc/fr_optim.hip, `k_scale_ratio_term`); with
+--fused-flame --perceptual the reference's whole objective.  The report gains `reg_loss` (scale_loss, rows over the threshold).
     python tools/train_synthetic.py --fateavatar --track-camera [--track-offset 0.005]
 FateAvatar's step with the reference's camera tracking next to it (train/base.py:123,142: one translation per frame in an
 embedding, at `tracking_lr`): every frame's camera translation is a torch leaf that starts --track-offset metres (RMS per axis)
@@ -148,6 +152,10 @@ def main():
                     help="--fateavatar (plain loop, --fused-flame or --torch-flame): FateAvatar's VGG perceptual term at weight 0.1 inside "
                          "the step (AvatarStep(perceptual=Perceptual(VggFeatures.vgg16())), csrc/fr_vgg.hip); seeded random weights "
                          "unless --vgg-weights is given")
+    ap.add_argument("--scale-term", action="store_true",
+                    help="--fateavatar (any of its loops, any --views-per-step): FateAvatar's scale-ratio term at weight 0.1, threshold "
+                         "9.0 inside the step (AvatarStep(scale_term=REFERENCE_SCALE_TERM), one launch in front of Adam); with "
+                         "--fused-flame --perceptual the reference's whole objective; the report gains `reg_loss`")
     ap.add_argument("--torch-perceptual", action="store_true",
                     help="the A/B of --perceptual: the same term at the same place of the same loop through F.conv2d and autograd "
                          "(the reference's route, tools/loss_utils/vgg_feature.py)")
@@ -254,6 +262,8 @@ def main():
                              "--torch-binding / --track-mesh")
     if a.track_mesh and not a.splatting:
         raise SystemExit("--track-mesh goes with --splatting")
+    if a.scale_term and not a.fateavatar:
+        raise SystemExit("--scale-term goes with --fateavatar (SplattingAvatar's own scale term: --splatting --reference-loss)")
     if a.fateavatar:
         if a.image_loss:
             raise SystemExit("--fateavatar: the D-SSIM term is not part of FateAvatar's objective (dssim_loss 0.0)")
@@ -391,11 +401,12 @@ def make_lpips(a, dev, weight):
 
 
 def fateavatar_setup(P, res, dev, views=8, views_per_step=1, use_graph=True, chain=True, fold_binding=True, order="uv",
-                     keep_coherent=False, vertex_grad=False, mesh_terms=None, target_delta=None, camera_grad=False, perceptual=None):
+                     keep_coherent=False, vertex_grad=False, mesh_terms=None, target_delta=None, camera_grad=False, perceptual=None,
+                     scale_term=None):
     """FateAvatar's optimisation step on the synthetic INSTA-layout sequence: the mesh-bound Gaussian
     set, its step object (AvatarStep, or AvatarBatchStep for K > 1 frames per step), cameras, posed meshes and targets
     rendered from a hidden ground-truth set.  Used by this script and by bench.py's `avatar` mode.
-    `vertex_grad`, `mesh_terms`, `camera_grad`: AvatarStep's options (K = 1).  `target_delta` [V,3] (numpy): the targets are rendered from
+    `vertex_grad`, `mesh_terms`, `camera_grad`: AvatarStep's options (K = 1); `scale_term`: both steps'.  `target_delta` [V,3] (numpy): the targets are rendered from
     the template displaced by it (`pose`, also returned, poses a displaced template differentiably).
     `order="uv"`: the reference's own initialisation — `uniform_sampling_barycoords(P, ...)` on the template's UV raster
     (model/fateavatar.py:128-133), rows in row-major texel order; `order="random"`: the area-weighted draw as drawn (the A/B)."""
@@ -444,14 +455,30 @@ def fateavatar_setup(P, res, dev, views=8, views_per_step=1, use_graph=True, cha
             extra["camera_grad"] = True
         if perceptual is not None:
             extra["perceptual"] = perceptual
+        if scale_term is not None:
+            extra["scale_term"] = scale_term
         st = AvatarStep(pc, faces_t, canon, cam0, bg, use_graph=use_graph, fold_binding=fold_binding, keep_coherent=keep_coherent,
                         **extra)
     else:   # the reference's batch of K frames per step (model/fateavatar.py:251-276), in flight together
         from fateavatar_amd.avatar import AvatarBatchStep
         st = AvatarBatchStep(pc, faces_t, canon, cam0, bg, views_per_step=K, use_graph=use_graph, chain=chain,
-                             fold_binding=fold_binding, keep_coherent=keep_coherent)
+                             fold_binding=fold_binding, keep_coherent=keep_coherent,
+                             **({} if scale_term is None else {"scale_term": scale_term}))
     return dict(st=st, cams=cams, posed=posed_t, gts=gts, n_frames=n_frames, K=K, pose=pose, canon=canon,
                 camera_arrays=insta.camera_arrays(transform))
+
+
+def scale_term_of(a):
+    """The step's scale term for --scale-term (None without it): the reference's 0.1 / 9.0."""
+    if not a.scale_term:
+        return None
+    from fateavatar_amd.avatar import REFERENCE_SCALE_TERM
+    return REFERENCE_SCALE_TERM
+
+
+def reg_words(st):
+    """`reg_loss` of a report: the step's unweighted scale_loss and the rows over the threshold (None without the term)."""
+    return None if st.reg_loss is None else [round(float(st.reg_loss[0]), 6), int(st.reg_loss[1])]
 
 
 def smooth_bump(verts, seed=0, height=0.004, width=0.03):
@@ -474,7 +501,8 @@ def main_train_mesh(a, rank, world, dev):
     verts, _, _ = scenes.head_geometry()
     bump = smooth_bump(np.asarray(verts, dtype=np.float32))
     su = fateavatar_setup(a.P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
-                           order="random" if a.random_order else "uv", mesh_terms=terms, target_delta=bump)
+                           order="random" if a.random_order else "uv", mesh_terms=terms, target_delta=bump,
+                           scale_term=scale_term_of(a))
     st, cams, posed_t, gts, n_frames, pose = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"], su["pose"]
     bump_t = torch.from_numpy(bump).to(dev)
     delta = torch.zeros_like(bump_t, requires_grad=True)           # the reference's delta_vertex (model/fateavatar.py:93-94)
@@ -491,7 +519,7 @@ def main_train_mesh(a, rank, world, dev):
     def report():
         torch.cuda.synchronize()
         return dict(image_loss=round(float(st.loss), 6), laplacian_loss=float(st.mesh_loss[0]), flame_loss=float(st.mesh_loss[1]),
-                    delta_minus_bump=round(float((delta.detach() - bump_t).norm()), 6))
+                    delta_minus_bump=round(float((delta.detach() - bump_t).norm()), 6), reg_loss=reg_words(st))
 
     warm = 10
     one_step(0)
@@ -557,6 +585,8 @@ def main_flame(a, rank, world, dev):
     common = dict(use_graph=not a.no_graph, fold_binding=not a.binding_op, mesh_terms=terms)
     if a.perceptual or a.torch_perceptual:
         common["perceptual"] = make_perceptual(a, dev)
+    if a.scale_term:
+        common["scale_term"] = scale_term_of(a)
     if a.fused_flame:
         st = AvatarStep(pc, faces_t, canon, cams[0].clone(), bg, flame=fm, **common)
         delta_vertex = lambda: fm.delta_vertex  # noqa: E731
@@ -585,7 +615,7 @@ def main_flame(a, rank, world, dev):
     def report():
         torch.cuda.synchronize()
         return dict(image_loss=round(float(st.loss), 6), laplacian_loss=float(st.mesh_loss[0]), flame_loss=float(st.mesh_loss[1]),
-                    delta_minus_bump=round(float((delta_vertex() - bump_t).norm()), 6))
+                    delta_minus_bump=round(float((delta_vertex() - bump_t).norm()), 6), reg_loss=reg_words(st))
 
     warm = 10
     one_step(0)
@@ -616,7 +646,7 @@ def main_track_camera(a, rank, world, dev):
         raise SystemExit("--track-camera: one GPU, without --train-mesh / --mesh-terms")
     from fateavatar_amd.model import PoseCamera
     su = fateavatar_setup(a.P, a.res, dev, views=a.views, use_graph=not a.no_graph, fold_binding=not a.binding_op,
-                           order="random" if a.random_order else "uv", camera_grad=True)
+                           order="random" if a.random_order else "uv", camera_grad=True, scale_term=scale_term_of(a))
     st, cams, posed_t, gts, n_frames = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"]
     arrays = su["camera_arrays"]
     # world_view_transform = [[R, 0], [T, 1]] (model.PoseCamera): the truth's rotation and translation of every frame
@@ -640,7 +670,8 @@ def main_track_camera(a, rank, world, dev):
 
     def report():
         torch.cuda.synchronize()
-        return dict(image_loss=round(float(st.loss), 6), translation_rms_error=float((T.detach() - T_true).pow(2).mean().sqrt()))
+        return dict(image_loss=round(float(st.loss), 6), translation_rms_error=float((T.detach() - T_true).pow(2).mean().sqrt()),
+                    reg_loss=reg_words(st))
 
     warm = 10
     one_step(0)
@@ -674,7 +705,8 @@ def main_fateavatar(a, rank, world, dev):
         mesh_terms = MeshTerms(*a.mesh_terms)
     su = fateavatar_setup(a.P, a.res, dev, views=a.views, views_per_step=a.views_per_step, use_graph=not a.no_graph, chain=a.chain,
                            fold_binding=not a.binding_op, order="random" if a.random_order else "uv", keep_coherent=a.keep_coherent,
-                           vertex_grad=a.vertex_grad, mesh_terms=mesh_terms, perceptual=make_perceptual(a, dev))
+                           vertex_grad=a.vertex_grad, mesh_terms=mesh_terms, perceptual=make_perceptual(a, dev),
+                           scale_term=scale_term_of(a))
     st, cams, posed_t, gts, n_frames, K = su["st"], su["cams"], su["posed"], su["gts"], su["n_frames"], su["K"]
     if mesh_terms is not None:
         bump = torch.from_numpy(smooth_bump(np.asarray(scenes.head_geometry()[0], dtype=np.float32))).to(dev)
@@ -721,6 +753,7 @@ def main_fateavatar(a, rank, world, dev):
                           "mesh_loss": [float(x) for x in st.mesh_loss] if mesh_terms else None,
                           "perceptual": None if st.perceptual is None else ("torch" if a.torch_perceptual else "fused"),
                           "perceptual_loss": None if st.perceptual is None else [round(float(x), 6) for x in st.perceptual_loss],
+                          "reg_loss": reg_words(st),
                           "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
