@@ -2,7 +2,7 @@
 zjwfufu/FateAvatar (volume_rendering/render_3dgs.py -> diff_gaussian_rasterization, simple_knn).
 
 Product modules: rasterizer (operator interface), render (caller-facing `render()`), knn (`distCUDA2`, initial scale),
-binding (mesh binding of the Gaussians), texture / baked (attributes looked up from UV attribute maps: the baked avatar), optim (fused Adam), train (the per-frame optimisation step), dp (data-parallel
+binding (mesh binding of the Gaussians), texture / baked / bake (attributes looked up from UV attribute maps: the baked avatar and the neural-baking step), optim (fused Adam), train (the per-frame optimisation step), dp (data-parallel
 frame sharding), model (flat parameter holder), ply / obj / mesh_sampling (formats and init-time sampling), scenes
 (synthetic inputs).  All device compute runs in hand-written HIP kernels behind the C ABI of include/fr_rasterizer.h
 (fateavatar_amd/libfr_hip.so); there is no CPU fallback.

@@ -204,6 +204,7 @@ EXPORTS = ["fr_create", "fr_destroy", "fr_last_error", "fr_version", "fr_profile
            "fr_binning_bytes", "fr_planes_bytes", "fr_camera_grad_workspace_bytes", "fr_forward", "fr_forward_batch", "fr_read_counts", "fr_backward", "fr_backward_batch", "fr_mark_visible", "fr_image_final_T",
            "fr_image_n_contrib", "fr_debug_geometry_field", "fr_debug_binning_region", "fr_debug_selftest_reduce", "fr_knn_workspace_bytes", "fr_knn_mean_dist2", "fr_knn_nearest_dist2", "fr_adam_step", "fr_adam_step_multi", "fr_l1_workspace_bytes", "fr_l1_loss_grad", "fr_l1_loss_grad_batch", "fr_huber_workspace_bytes", "fr_huber_loss_grad", "fr_pixel_loss_workspace_bytes", "fr_pixel_loss_grad", "fr_scale_term_workspace_bytes", "fr_scale_term", "fr_scale_ratio_workspace_bytes", "fr_scale_ratio_term", "fr_regularise_workspace_bytes", "fr_gaussian_regularise", "fr_mesh_terms_workspace_bytes", "fr_mesh_terms", "fr_ssim_window", "fr_image_loss_workspace_bytes", "fr_image_loss_grad", "fr_multi_copy", "fr_scaled_sum", "fr_face_scale",
            "fr_bind_forward", "fr_bind_backward", "fr_bind_backward_local", "fr_bind_backward_phong", "fr_bind_backward_deform", "fr_phong_frame", "fr_bind_backward_phong_frame", "fr_phong_frame_backward_workspace_bytes", "fr_phong_frame_backward", "fr_triwalk", "fr_phong_fit", "fr_texture_corners", "fr_texture_lookup", "fr_texture_lookup_backward",
+           "fr_bake_decode", "fr_bake_decode_backward", "fr_rot_term_workspace_bytes", "fr_rot_term",
            "fr_point_lbs_forward", "fr_point_lbs_backward", "fr_point_lbs_pose_workspace_bytes", "fr_point_lbs_backward_pose", "fr_nearest_vertex", "fr_lbs_terms_workspace_bytes", "fr_lbs_terms",
            "fr_mlp_workspace_bytes", "fr_mlp_forward", "fr_mlp_backward",
            "fr_flame_workspace_bytes", "fr_flame_workspace_zeroed_bytes", "fr_flame_forward", "fr_flame_backward",
@@ -322,6 +323,15 @@ def lib():
     L.fr_texture_lookup_backward.argtypes = [C.c_int32, _fp, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.POINTER(fr_tex_layer),
                                              C.c_void_p]
     L.fr_texture_lookup_backward.restype = C.c_int
+    L.fr_bake_decode.argtypes = [C.c_int32, _fp, C.c_int32, C.c_int32, _fp, C.c_float, C.c_float, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
+    L.fr_bake_decode.restype = C.c_int
+    L.fr_bake_decode_backward.argtypes = [C.c_int32, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_float, C.c_float, _fp, _fp, _fp, _fp,
+                                          _fp, _fp, C.c_void_p]
+    L.fr_bake_decode_backward.restype = C.c_int
+    L.fr_rot_term_workspace_bytes.argtypes = []
+    L.fr_rot_term_workspace_bytes.restype = C.c_size_t
+    L.fr_rot_term.argtypes = [C.c_float, C.c_int32, _fp, _fp, _fp, C.c_void_p, C.c_void_p]
+    L.fr_rot_term.restype = C.c_int
     L.fr_adam_step.argtypes = [C.POINTER(fr_adam_config), _fp, _fp, _fp, _fp, C.c_uint64, _fp, C.c_void_p]
     L.fr_adam_step.restype = C.c_int
     L.fr_adam_step_multi.argtypes = [C.POINTER(fr_adam_config), _fp, C.POINTER(C.c_void_p), C.c_int32, _fp, _fp, C.c_uint64, _fp,

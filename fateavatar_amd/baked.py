@@ -9,8 +9,8 @@ dictionary) and `_export_avatar_model` (:342-385, baked textures back into a pla
 What is native here: the look-up of all attribute maps is one HIP kernel per direction (`texture.texture_lookup`) and its
 [N,C] outputs are what `render_bound_batch` takes as RAW parameters, so a baked frame is: rotation activation (torch, on the
 texture) -> one look-up launch -> the rasterizer's launch chain with the binding inside its per-Gaussian kernels.  One look-up
-serves all K views of a batch.  The U-Net / decoder that produces the textures in training, the baking trainer and the
-texture editor stay stock PyTorch.
+serves all K views of a batch.  The baking trainer's step is `bake.BakeStep`, on this class; the U-Net / decoder that produces
+the textures in training and the texture editor stay stock PyTorch.
 """
 from __future__ import annotations
 

@@ -10,8 +10,9 @@ reference's function as an autograd op on those kernels.  `huber_loss_and_grad` 
 mouth-mask term (train/loss.py:217-221, :231-239) in one launch (`fr_huber_loss_grad`).  `pixel_loss_and_grad` is
 SplattingAvatar's L1 + MSE image term (train/loss.py:279-283, :288-304) in one launch (`fr_pixel_loss_grad`) and
 `scale_term_and_grad` its scale term (:307-315) in two (`fr_scale_term`).  `scale_ratio_term_and_grad` is FateAvatar's scale-ratio
-term (:144-151) in one launch (`fr_scale_ratio_term`) and `scale_ratio_loss` the same expression as an autograd op.  There is no
-CPU path."""
+term (:144-151) in one launch (`fr_scale_ratio_term`) and `scale_ratio_loss` the same expression as an autograd op.
+`rot_term_and_grad` is neural baking's rotation term (UVDecoderLoss, :612-617) in one launch (`fr_rot_term`) and `rot_loss` the
+same as an autograd op.  There is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -28,6 +29,7 @@ _huber_ws = StreamWorkspace("huber_workspace", lambda: _lib.lib().fr_huber_works
 _pixel_ws = StreamWorkspace("pixel_loss_workspace", lambda: _lib.lib().fr_pixel_loss_workspace_bytes(), "image's")
 _scale_ws = StreamWorkspace("scale_term_workspace", lambda: _lib.lib().fr_scale_term_workspace_bytes(), "parameters'")
 _ratio_ws = StreamWorkspace("scale_ratio_workspace", lambda: _lib.lib().fr_scale_ratio_workspace_bytes(), "parameters'")
+_rot_ws = StreamWorkspace("rot_term_workspace", lambda: _lib.lib().fr_rot_term_workspace_bytes(), "rotations'")
 _reg_ws = StreamWorkspace("regulariser_workspace", lambda: _lib.lib().fr_regularise_workspace_bytes(), "parameters'")
 _mesh_ws = StreamWorkspace("mesh_terms_workspace", lambda: _lib.lib().fr_mesh_terms_workspace_bytes(), "vertices'")
 
@@ -315,6 +317,62 @@ def scale_ratio_loss(scaling: torch.Tensor, scale_threshold: float = 9.0) -> tor
     if scaling.dim() != 2 or scaling.shape[-1] != 3:
         raise RuntimeError(f"scale_ratio_loss: log-scales are [P,3], got {tuple(scaling.shape)}")
     return _ScaleRatio.apply(scaling, float(scale_threshold))
+
+
+# ---- the baking objective's rotation term (UVDecoderLoss, train/loss.py:612-617): ONE launch (`fr_rot_term`) gives the
+# unweighted loss and adds the weighted gradient into dL/d(decoded rotation)
+def rot_term_workspace(dev: torch.device) -> torch.Tensor:
+    """A fresh zeroed workspace for `rot_term_and_grad(..., workspace=)`."""
+    return _rot_ws.fresh(dev)
+
+
+def rot_term_and_grad(rotation: torch.Tensor, d_rotation: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
+                      weight: float = 0.1, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Neural baking's rot_loss (train/loss.py:612-617) on the decoded rotation rows [N,4] in ONE launch (`fr_rot_term`): with
+    raw = quaternion_to_axis_angle(rotation) (pytorch3d 0.7.7's formula; element 0 of a row is taken for the real part, as
+    the reference runs it on its shuffled rows), returns `out` = mean(raw[:,0]^2) + mean(raw[:,2]^2), UNWEIGHTED, a 1-element
+    device tensor, and ADDS weight * d rot_loss / d rotation into `d_rotation` ([N,4] gradient buffer; None, or a weight of 0:
+    no gradient traffic).  A row whose vector part is 0 passes no gradient through the norm (autograd's rule).  `workspace`:
+    scratch from `rot_term_workspace()`; by default one is kept per (device, current stream) — launches that may overlap must
+    not share one.  There is no CPU path."""
+    who = "rot_term_and_grad"
+    if not rotation.is_cuda:
+        raise RuntimeError(f"{who} needs device tensors (there is no CPU path)")
+    dev, N = rotation.device, int(rotation.shape[0])
+    rotation = rotation.detach()
+    for t in (rotation, d_rotation):
+        if t is not None and (t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (N, 4)):
+            raise RuntimeError(f"{who}: contiguous float32 [N,4] tensors of one device")
+    loss = _out_words(who, out, 1, dev, "rotations'", fresh=torch.zeros)   # (N == 0 launches nothing)
+    ws = _rot_ws.resolve(dev, workspace, who)
+    _lib.launch("fr_rot_term", dev, float(weight), N, rotation.data_ptr() if N else None,
+                d_rotation.data_ptr() if d_rotation is not None and N else None, loss.data_ptr(), ws.data_ptr())
+    return loss
+
+
+class _RotLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rotation):
+        r = _f32c(rotation.detach())
+        grad = torch.zeros_like(r) if ctx.needs_input_grad[0] else None     # None: the loss only
+        loss = rot_term_and_grad(r, grad, weight=1.0)
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        ctx.in_dtype = rotation.dtype
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        return (grad * grad_output).to(ctx.in_dtype)
+
+
+def rot_loss(rotation: torch.Tensor) -> torch.Tensor:
+    """`rot_term_and_grad`'s expression as a 0-dim tensor, UNWEIGHTED, differentiable with respect to `rotation` [N,4] (the
+    fused kernel's gradient with weight 1, scaled by the incoming one)."""
+    if rotation.dim() != 2 or rotation.shape[-1] != 4:
+        raise RuntimeError(f"rot_loss: rotations are [N,4], got {tuple(rotation.shape)}")
+    return _RotLoss.apply(rotation)
 
 
 def regulariser_workspace(dev: torch.device) -> torch.Tensor:

@@ -11,7 +11,9 @@ Here the look-up of ALL textures is one HIP kernel (lane = point, output row-maj
 with the colour / offset / scaling activations applied to the texels inside it, and the backward is one kernel with lane =
 TEXEL that gathers over a plan built once per UV set (`TexturePlan`) and stores every texel of every gradient: no zero
 fill, no float atomics, the same bits on every run (include/fr_rasterizer.h, csrc/fr_texture.hip).  The rotation activation
-(axis-angle -> quaternion) stays torch, on the texture (`rotation_activation`).
+(axis-angle -> quaternion) stays torch, on the texture (`rotation_activation`), on this route; `decode_attributes` is the
+baking trainer's: the decoder's packed output, the rotation activation inside the kernel, one launch per direction
+(csrc/fr_bake.hip).
 """
 from __future__ import annotations
 
@@ -256,6 +258,77 @@ def gather_attributes(neural_texture: torch.Tensor, plan: TexturePlan, mean_scal
         acts[name] = {"color": COLOR_ACTIVATION, "scaling": scaling_activation(mean_scaling, max_scaling),
                       "offset": OFFSET_ACTIVATION}.get(name)
     return texture_dict, texture_lookup(tex, plan, acts)
+
+
+class _DecodeAttributes(torch.autograd.Function):
+    """The decoder's packed output -> the five [N,C] attribute arrays: `fr_bake_decode` / `fr_bake_decode_backward`."""
+
+    @staticmethod
+    def forward(ctx, plan: TexturePlan, mean_scaling: float, max_scaling: float, tex_out):
+        dev = plan.device
+        tex = tex_out.contiguous()
+        outs = [torch.empty((plan.N, c + (name == "rotation")), dtype=torch.float32, device=dev) for name, c in TEXTURE_CHANNELS]
+        _lib.launch("fr_bake_decode", dev, plan.N, plan.uv.data_ptr(), plan.H, plan.W, tex.data_ptr(), mean_scaling, max_scaling,
+                    *[o.data_ptr() for o in outs])
+        ctx.plan, ctx.scaling = plan, (mean_scaling, max_scaling)
+        ctx.save_for_backward(tex)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *d_outs):
+        plan, (tex,) = ctx.plan, ctx.saved_tensors
+        if not ctx.needs_input_grad[3]:
+            return None, None, None, None
+        d_tex = torch.empty(tex.shape, dtype=torch.float32, device=plan.device)
+        decode_backward_into(plan, tex, *ctx.scaling, d_outs, d_tex)
+        return None, None, None, d_tex
+
+
+def decode_backward_into(plan: TexturePlan, tex_out: torch.Tensor, mean_scaling: float, max_scaling: float, d_values,
+                         d_tex_out: torch.Tensor) -> torch.Tensor:
+    """`fr_bake_decode_backward`: the gradients of the five decoded arrays (`TEXTURE_CHANNELS` order; None: zero) gathered
+    per texel over `plan.csr()` in ONE walk into `d_tex_out` (the shape of `tex_out`, contiguous), every texel stored."""
+    row_start, entries = plan.csr()
+    g = [None if d is None else d.to(torch.float32).contiguous() for d in d_values]
+    _lib.launch("fr_bake_decode_backward", plan.device, plan.N, plan.uv.data_ptr(), plan.H, plan.W, row_start.data_ptr(),
+                entries.data_ptr(), tex_out.data_ptr(), float(mean_scaling), float(max_scaling),
+                *[None if d is None else d.data_ptr() for d in g], d_tex_out.data_ptr())
+    return d_tex_out
+
+
+def _check_decoder_output(tex_out, plan: TexturePlan, who: str) -> None:
+    n_ch = sum(c for _, c in TEXTURE_CHANNELS)
+    if not isinstance(tex_out, torch.Tensor) or tex_out.dim() not in (3, 4) or (tex_out.dim() == 4 and tex_out.shape[0] != 1) \
+            or tex_out.shape[-3] != n_ch:
+        raise RuntimeError(f"{who}: the decoder output must be [1,{n_ch},H,W] (or [{n_ch},H,W])")
+    if tuple(tex_out.shape[-2:]) != (plan.H, plan.W):
+        raise RuntimeError(f"{who}: the decoder output is {tex_out.shape[-2]} x {tex_out.shape[-1]}, the plan was made for "
+                           f"{plan.H} x {plan.W}")
+    if tex_out.dtype != torch.float32:
+        raise RuntimeError(f"{who}: the decoder output must be float32")
+    if not tex_out.is_cuda:
+        raise RuntimeError(f"{who}: the decoder output must be on a HIP device (there is no CPU path)")
+    if tex_out.device != plan.device:
+        raise RuntimeError(f"{who}: the decoder output is on {tex_out.device}, the plan on {plan.device}")
+
+
+def decode_attributes(tex_out: torch.Tensor, plan: TexturePlan, mean_scaling: float, max_scaling: float):
+    """`gather_attributes` with the ROTATION ACTIVATION inside the look-up: the decoder's [1,11,H,W] output (slices of
+    uv_decoder.py:225-245) -> (texture_dict, value_dict), the raw slices and the looked-up [N,C] values, in ONE launch
+    (`fr_bake_decode`: per corner texel tanh x 2 pi -> axis-angle -> quaternion -> the reference's shuffle, then the
+    interpolation — what `rotation_activation` followed by the look-up gives, without the activated map and its dozen
+    element-wise launches).  The colour, opacity, scaling and offset rows are `gather_attributes`' bit for bit.
+    Differentiable with respect to `tex_out`: ONE launch (`fr_bake_decode_backward`) walks every texel's entry list once for
+    all twelve gradient channels and stores every texel of the gradient (no zero fill, no float atomics, the same bits on every
+    run).  Under torch.no_grad() no inverse map is needed (or built)."""
+    _check_decoder_output(tex_out, plan, "decode_attributes")
+    texture_dict, off = {}, 0
+    view = tex_out if tex_out.dim() == 4 else tex_out.unsqueeze(0)
+    for name, c in TEXTURE_CHANNELS:
+        texture_dict[name] = view[:, off:off + c]
+        off += c
+    values = _DecodeAttributes.apply(plan, float(mean_scaling), float(max_scaling), tex_out)
+    return texture_dict, dict(zip(texture_dict, values))
 
 
 def uv_of_binding(face_index, bary_coords, uv_layout: Optional[tuple] = None) -> torch.Tensor:

@@ -769,6 +769,42 @@ int fr_texture_lookup(int32_t N, const float* uv, int32_t H, int32_t W, int32_t 
 int fr_texture_lookup_backward(int32_t N, const float* uv, int32_t H, int32_t W, const int32_t* row_start,
                                const int32_t* entries, int32_t n_layers, const fr_tex_layer* layers, void* hip_stream);
 
+/* ---- Neural baking: the decoder's packed output decoded into the five attribute arrays, one launch per direction
+ * (reference `UVDecoder.forward`, model/uv_decoder.py:387-542 -> `_gather_attribute` :85-107 on the channel slices of
+ * :225-245, `UVDecoderLoss` train/loss.py:522-677).  `tex_out`: planar [11,H,W] floats — colour 0:3, opacity 3:4, scaling
+ * 4:7, rotation 7:10, offset 10:11.  Outputs row-major: colour [N,3] = tanh(t) * 0.5 / C0, opacity [N,1] = t, scaling [N,3] =
+ * max_scaling - softplus(-(t + mean_scaling) + max_scaling), offset [N,1] = tanh(t) — these four rows are those of
+ * fr_texture_lookup with the matching FR_TEX_ACT_*, bit for bit — and rotation [N,4]: per corner texel a = tanh(t) * 2 pi over
+ * the three channels, theta = |a|, q = (cos(theta / 2), a * s) with s = sin(theta / 2) / theta (theta < 1e-6: 0.5 - theta^2 /
+ * 48), emitted as (q[3], q[0], q[1], q[2]) (`_rotation_activation`, uv_decoder.py:158-174, as it runs), then the four
+ * components interpolated: what activating the whole map and sampling it gives, without the activated map.  The rotation
+ * rows are read and written sixteen bytes at a time: 16-byte aligned arrays.  Argument checks run before the first HIP call;
+ * N == 0 is FR_OK and launches nothing.  No call allocates or synchronises: each can be captured in a HIP graph. */
+int fr_bake_decode(int32_t N, const float* uv, int32_t H, int32_t W, const float* tex_out, float mean_scaling,
+                   float max_scaling, float* color, float* opacity, float* scaling, float* rotation, float* offset,
+                   void* hip_stream);
+/* The backward as a gather per texel over the CSR of fr_texture_lookup_backward, walked ONCE: the twelve gradient channels
+ * are summed in list order, taken through the per-texel Jacobians (rotation: the 4 -> 3 transpose through the quaternion map
+ * and the tanh; at a texel whose three rotation channels are 0 the Taylor branch is taken and nothing divides by theta: every
+ * non-zero entry of d out / d t is pi there) and STORED for every texel of d_tex_out [11,H,W]: no zero fill, no float atomics,
+ * the same bits on every run.  A NULL d_* array stands for a zero gradient.  Entries whose point is not in 0 .. N - 1 are
+ * skipped. */
+int fr_bake_decode_backward(int32_t N, const float* uv, int32_t H, int32_t W, const int32_t* row_start,
+                            const int32_t* entries, const float* tex_out, float mean_scaling, float max_scaling,
+                            const float* d_color, const float* d_opacity, const float* d_scaling, const float* d_rotation,
+                            const float* d_offset, float* d_tex_out, void* hip_stream);
+/* The baking objective's rotation term and its gradient in ONE launch (train/loss.py:612-617 on raw_rot =
+ * quaternion_to_axis_angle(decode_rotation), uv_decoder.py:516; pytorch3d 0.7.7's formula, element 0 of a row taken for the
+ * real part): n = |q[1:]|, half = atan2(n, q[0]), ang = 2 half, s = sin(half) / ang (|ang| < 1e-6: 0.5 - ang^2 / 48), raw =
+ * q[1:] / s;  loss[0] = mean(raw[:,0]^2) + mean(raw[:,2]^2), UNWEIGHTED, and weight x its gradient is ADDED to the rows of
+ * d_rotation [N,4] by the lane that owns the row (NULL, or a weight of 0: no gradient traffic).  |q[1:]| = 0 passes no
+ * gradient through the norm.  Per-workgroup partials summed in index order by the workgroup that finishes last: the same
+ * bits on every run.  `workspace`: fr_rot_term_workspace_bytes() bytes of device memory, zeroed ONCE by the caller, left
+ * zeroed; not to be shared by launches that can overlap.  16-byte aligned rows.  N == 0 launches nothing and leaves `loss`. */
+size_t fr_rot_term_workspace_bytes(void);
+int fr_rot_term(float weight, int32_t N, const float* rotation, float* d_rotation, float* loss, void* workspace,
+                void* hip_stream);
+
 /* present[i] = view-space z of means3D[i] > 0.2 (auxiliary.h:154). */
 int fr_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                     uint8_t* present, void* hip_stream);

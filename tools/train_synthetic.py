@@ -41,6 +41,14 @@ from the truth; each step the frame's camera is built from it as `model.PoseCame
 AvatarStep(camera_grad=True), and `step.d_view / d_proj / d_campos` are chained back through that construction into
 torch.optim.Adam(lr=5e-4).  Prints steps/s, the image loss and the RMS translation error before and after.
 
+    python tools/train_synthetic.py --bake [--res 512 --views 8 --steps 300]             | --torch-bake
+FateAvatar's SECOND stage, neural baking, in feature-map mode (fateavatar_amd/bake.py: `BakeStep(texture="feature_map")`): the head
+template's 65 536 UV-raster points + 65 536 template points, one [1,11,512,512] texture trained by the step's own fused Adam at 1e-3
+towards frames rendered from a second random texture; L1 + the rot term at 0.1, every attribute baked: decode, frame, terms, decode
+backward and Adam in ONE replayed graph.  --torch-bake: the A/B, the same loop through `BakedAvatar.render(return_values=True)` + the
+torch rot term (tests/bake_ref.py: run it from a checkout that has tests/) + torch.optim.Adam, eager.  Prints steps/s and the image
+loss at start and end.
+
     python tools/train_synthetic.py --rigged [--P 10006 --sh-degree 3 --binding-op]
 GaussianAvatars' step (fateavatar_amd/rigged.py): Gaussians rigged to the triangles of the posed template, one GPU.
     python tools/train_synthetic.py --rigged --P 10006 --regularisers --densify-from 0.3 --densify-interval 0.1 --reset-interval 0.5
@@ -133,6 +141,10 @@ def main():
     ap.add_argument("--fateavatar", action="store_true",
                     help="FateAvatar's own loop: mesh-bound parameters (offset / rotation / scaling / colour / opacity), "
                          "synthetic INSTA-layout sequence with per-frame posed mesh, SH degree 0")
+    ap.add_argument("--bake", action="store_true",
+                    help="neural baking in feature-map mode: BakeStep(texture='feature_map') on the head template (one GPU)")
+    ap.add_argument("--torch-bake", action="store_true",
+                    help="the A/B of --bake: BakedAvatar.render + torch rot term + torch.optim.Adam, eager")
     ap.add_argument("--vertex-grad", action="store_true",
                     help="--fateavatar: AvatarStep(vertex_grad=True): every step leaves dLoss/dposed_verts in step.d_verts")
     ap.add_argument("--train-mesh", action="store_true",
@@ -232,6 +244,10 @@ def main():
     a.image_loss = ImageLoss(*a.image_loss) if a.image_loss else (ImageLoss(0.8, 0.2) if a.dssim else None)
     if a.reference_loss and (not a.splatting or a.torch_binding):
         raise SystemExit("--reference-loss goes with --splatting (and its fused terms: not with --torch-binding)")
+    if a.bake or a.torch_bake:
+        if (a.bake and a.torch_bake) or a.image_loss or a.fateavatar or a.rigged or a.splatting or a.flash or a.mono or world > 1:
+            raise SystemExit("--bake / --torch-bake: one of the two, alone (L1 + the rot term), on one GPU")
+        return main_bake(a, dev)
     if a.mono:
         if a.image_loss or a.train_mesh or a.mesh_terms or a.fateavatar or a.rigged or a.splatting or a.flash:
             raise SystemExit("--mono: the image term is L1 and there are no mesh terms; one model per run")
@@ -314,6 +330,70 @@ def main():
                           "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
+
+
+def main_bake(a, dev):
+    """--bake / --torch-bake: see the module docstring."""
+    from fateavatar_amd import insta
+    from fateavatar_amd.avatar import AvatarGaussians
+    from fateavatar_amd.bake import BAKE_LR, REFERENCE_ROT_TERM, BakeStep
+    from fateavatar_amd.baked import ATTRIBUTES, TEMPLATE_POINTS, BakedAvatar
+    from fateavatar_amd.texture import SH_C0, TEXTURE_CHANNELS
+    transform, posed, faces = insta.synthetic_sequence(a.views, a.res, 0)
+    verts, _, _ = scenes.head_geometry()
+    cams = [TorchCamera(c, dev) for c in insta.camera_arrays(transform)]
+    posed, faces, canon = torch.from_numpy(posed).to(dev), torch.from_numpy(faces).to(dev), torch.from_numpy(verts).to(dev)
+    bg = torch.ones(3, device=dev)
+    pc = AvatarGaussians.from_template(dev, uv_resolution=256)               # 65 536 points: the reference's tex_size 256
+    baked = BakedAvatar(pc, tex_size=512, template_points=TEMPLATE_POINTS, rng=np.random.default_rng(0))
+    gen = torch.Generator().manual_seed(1)
+    # the targets: the frames of a second random texture (a step that owns no texture renders them)
+    truth = torch.empty(1, 11, 512, 512).uniform_(-1, 1, generator=gen).to(dev)
+    show = BakeStep(baked, faces, canon, cams[0].clone(), bg, use_graph=False)
+    gts = []
+    for v in range(a.views):
+        show.step(cams[v], posed[v], torch.zeros(3, a.res, a.res, device=dev), truth)
+        gts.append(show.out["render"].clone())
+    st = BakeStep(baked, faces, canon, cams[0].clone(), bg, texture="feature_map", use_graph=not a.no_graph,
+                  generator=torch.Generator().manual_seed(2))
+    if a.torch_bake:
+        from tests import bake_ref
+        leaf = st.optim_texture.clone().requires_grad_(True)
+        opt = torch.optim.Adam([leaf], lr=BAKE_LR)
+
+        def step(v):
+            td, off = {}, 0
+            for name, c in TEXTURE_CHANNELS:
+                td[name] = leaf[:, off:off + c]
+                off += c
+            td["color"] = torch.tanh(td["color"]) * (0.5 / SH_C0)
+            outs, values = baked.render([cams[v]], [posed[v]], st.binding, bg, texture_dict=td, bake_attribute=ATTRIBUTES,
+                                        return_values=True)
+            l1 = torch.nn.functional.l1_loss(outs[0]["render"], gts[v])
+            opt.zero_grad(set_to_none=True)
+            (l1 + REFERENCE_ROT_TERM.weight * bake_ref.rot_loss(values["rotation"])).backward()
+            opt.step()
+            return l1.detach()
+    else:
+        step = lambda v: st.step(cams[v], posed[v], gts[v])  # noqa: E731
+    losses, warm = [], 10
+    for it in range(warm):
+        losses.append(step(it % a.views).clone())
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(warm, warm + a.steps):
+        loss = step(it % a.views)
+        if it >= warm + a.steps - 4:
+            losses.append(loss.clone())
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if a.bake:
+        st.check()
+    l = [float(x) for x in losses]
+    print(json.dumps({"metric": "neural-baking steps/s (decode + frame + L1 + rot term + backward + Adam, feature-map mode)",
+                      "value": round(a.steps / dt, 1), "ms_per_step": round(dt / a.steps * 1e3, 4), "route": "torch" if a.torch_bake else "fused",
+                      "points": baked.N, "texture": [11, 512, 512], "res": a.res, "views": a.views, "graph": bool(a.bake and not a.no_graph),
+                      "loss_first": round(float(np.mean(l[:4])), 6), "loss_last": round(float(np.mean(l[-4:])), 6)}))
 
 
 def make_perceptual(a, dev):
